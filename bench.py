@@ -13,10 +13,12 @@ transcriber_faster_whisper.py:1125-1127), so xRT = 30 s x steps / wall and p50 c
 Multi-GPU: streams are independent — one process per GPU, one engine + one stream each, no
 data-path collective; barrier + max-over-ranks timing; value = aggregate audio seconds / wall ("weak" scaling).
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant decode kernel,
-timed inside the engine on the slot's stream: a captured graph of just that kernel's launches of one step between
-one HIP-event pair) and `cpu_baseline` (the torch-fp32 CPU oracle on a
-bounded sample of the same workload, rank 0 at N=1 only).
+Output: ONE JSON line on rank 0. A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`,
+`ms_per_step`, `p50_chunk_latency_ms`, `stage_ms`). `--full` adds every other figure after the headline: `roofline`
+(dominant decode kernel, timed inside the engine on the slot's stream: a captured graph of just that kernel's launches of
+one step between one HIP-event pair, plus the rocprofv3 passes), the conditioned window, the stream and throughput legs
+and `cpu_baseline` (the torch-fp32 CPU oracle on a bounded sample of the same workload, rank 0 at N=1 only).
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) for output-by-output comparisons of builds.
 """
 from __future__ import annotations
 
@@ -573,12 +575,14 @@ def config5(args, rank, world, local, dist, torch):
         wall = float(tw.item())
     out = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [(r[0], r[1], r[2]) for r in res], [], args.decode_steps)
         n_tok = [len(r[0]) for r in res]
         slot = tr._slots[0] if tr._slots else None
         rows = MB * 5
         step_ms = None
         try:
-            if slot is not None:
+            if slot is not None and args.full:
                 step_ms = slot.debug_time_decode_step(rows=rows, t=1 + args.decode_steps // 2, iters=20)
         except Exception as e:  # noqa: BLE001 — the step probe is an extra; the measured line must survive it
             note(f"decode-step probe at {rows} rows unavailable: {e}")
@@ -676,6 +680,39 @@ def throughput_leg(eng, spec, torch, ids, eids, gen_kw, decode_steps, TS=3, TB=4
             sl.close()
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6            # the dump stays under 64 MB with its .npy headers
+
+
+def dump_outputs(out_dir: str, results, windows, n_tokens: int = 0):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, as `out_dir/<name>.npy`. `results`: one
+    (tokens, score, no-speech probability) per window; `windows`: (slot, item) per window whose log-mel features and encoder
+    output are still resident (empty for config 5, whose worker recycles its slots). Tokens (padded with -1 to `n_tokens` or
+    the longest), scores and no-speech probabilities of every window in float64; features and encoder output in float32 for
+    the first windows that fit DUMP_BUDGET_BYTES (a fixed sample: the window order and the inputs are fixed by seeds)."""
+    os.makedirs(out_dir, exist_ok=True)
+    width = max([n_tokens] + [len(t) for t, _, _ in results])
+    toks = np.full((len(results), width), -1.0, dtype=np.float64)
+    for i, (t, _, _) in enumerate(results):
+        toks[i, :len(t)] = t
+    arrays = {"tokens": toks, "scores": np.asarray([s for _, s, _ in results], dtype=np.float64),
+              "no_speech_prob": np.asarray([p for _, _, p in results], dtype=np.float64)}
+    used = sum(a.nbytes for a in arrays.values())
+    feats, encs = [], []
+    for sl, b in windows:
+        f, e = sl.features(b), sl.encoder_output(b)
+        if used + f.nbytes + e.nbytes > DUMP_BUDGET_BYTES:
+            break
+        feats.append(f)
+        encs.append(e)
+        used += f.nbytes + e.nbytes
+    if feats:
+        arrays["logmel"] = np.stack(feats).astype(np.float32)
+        arrays["encoder_output"] = np.stack(encs).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    note(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {list(a.shape)}" for k, a in arrays.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -709,6 +746,10 @@ def main():
     ap.add_argument("--rccl", action="store_true", help="--gpus 1: initialise torch.distributed over RCCL (backend nccl, world size 1) anyway and run the "
                     "barriers, the max-over-ranks all_reduce, the latency gather and (config 5) the record all_gather through it with device tensors "
                     "— the N-rank code path's collectives executed on the one GPU a box has (tests/test_gpu_rccl.py)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every other figure: roofline and per-kernel probes with their "
+                    "rocprofv3 passes, the conditioned window, the stream leg, the CPU baseline and parity, the throughput leg (the --no-* "
+                    "switches above drop single legs of it); without it a run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--ws-client", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -794,7 +835,7 @@ def main():
         t0 = time.perf_counter()
         Ts = [sl.logmel_resident(b) for b in range(B)]
         sl.encode(B, seek=[0] * B, seg=[min(T - 1, 3000) for T in Ts])
-        r = sl.generate([[ids["sot"]]] * B, eids, **gen_kw)[0]
+        r = sl.generate([[ids["sot"]]] * B, eids, **gen_kw)
         return time.perf_counter() - t0, r
 
     if S == 1:
@@ -809,7 +850,7 @@ def main():
         def step():
             t0 = time.perf_counter()
             res = list(pool.map(step_on, slots))
-            return time.perf_counter() - t0, res[0][1]
+            return time.perf_counter() - t0, [g for _, r in res for g in r]
 
     for _ in range(args.warmup):
         step()
@@ -843,7 +884,7 @@ def main():
         res = list(pool.map(run_stream, range(S)))
         for out_l, _ in res:
             lat.extend(out_l)
-        last = res[0][1]
+        last = [g for _, r in res for g in r]
         tm = slot.timings()
         for k in stage:
             stage[k] = tm[k]
@@ -867,8 +908,28 @@ def main():
 
     out = None
     if rank == 0:
-        n_tok = len(last.sequences_ids[0])
+        n_tok = len(last[0].sequences_ids[0])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [(g.sequences_ids[0], g.scores[0], g.no_speech_prob) for g in last],
+                         [(sl, b) for sl in slots for b in range(B)])
         xrt = world * S * B * args.steps * WINDOW_S / wall
+        out = {
+            "metric": "real-time factor (xRT), Whisper-small 30 s window (p50 chunk latency in p50_chunk_latency_ms)",
+            "value": xrt, "unit": "xRT (audio s / wall s)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1000.0 * wall / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f16 (MFMA operands; f32 accumulate, f32 residual stream, f32 log-mel)", "data": "synthetic",
+            "p50_chunk_latency_ms": 1000.0 * float(np.median(lat)),
+            # what `value` times and what it leaves out (VERDICT r05 item 6): the PCM is resident in HBM when the timed region starts
+            # (wlx_pcm_put outside it); the upload of one window, measured with --full, is NOT in `value` — the stream leg, which goes
+            # through the server with host buffers, includes it
+            "timed_region": "per step: wlx_logmel_resident (PCM already in HBM) + wlx_encode + wlx_generate; excludes the host-to-device copy of the window's PCM (h2d_excluded_ms)",
+            "config": {"workload": f"configs[{1 if S == 1 else 2}]: Whisper-{args.model}, {S} stream{'s' if S > 1 else ''} per GPU, one 30 s window per stream per step "
+                                   f"(480000 samples 16 kHz f32 resident in HBM -> log-mel -> encoder -> beam-5 decode, "
+                                   f"{n_tok} generated tokens forced by suppressing EOT), seeded random weights",
+                       "streams_per_gpu": S, "batch_per_stream": B, "beam_size": 5, "decode_steps": n_tok, "window_s": WINDOW_S},
+            "stage_ms": stage,
+        }
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel, HIP-event timed inside the engine on the slot stream
         # one slot's decode step as this run executes it: B windows x 5 beams rows per launch (--streams: S such steps run
         # concurrently on S slots; the probe is one slot's step alone)
@@ -908,27 +969,11 @@ def main():
             slot.pcm_put(pcm, 0)
             h2d.append(time.perf_counter() - th)
         h2d_ms = 1e3 * float(np.median(h2d))
-        out = {
-            "metric": "real-time factor (xRT), Whisper-small 30 s window (p50 chunk latency in p50_chunk_latency_ms)",
-            "value": xrt, "unit": "xRT (audio s / wall s)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1000.0 * wall / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f16 (MFMA operands; f32 accumulate, f32 residual stream, f32 log-mel)", "data": "synthetic",
-            "p50_chunk_latency_ms": 1000.0 * float(np.median(lat)),
-            # what `value` times and what it leaves out (VERDICT r05 item 6): the PCM is resident in HBM when the timed region starts
-            # (wlx_pcm_put outside it); the upload of one window, measured below, is NOT in `value` — the stream leg, which goes
-            # through the server with host buffers, includes it
-            "timed_region": "per step: wlx_logmel_resident (PCM already in HBM) + wlx_encode + wlx_generate; excludes the host-to-device copy of the window's PCM (h2d_excluded_ms)",
-            "h2d_excluded_ms": h2d_ms,
-            "config": {"workload": f"configs[{1 if S == 1 else 2}]: Whisper-{args.model}, {S} stream{'s' if S > 1 else ''} per GPU, one 30 s window per stream per step "
-                                   f"(480000 samples 16 kHz f32 resident in HBM -> log-mel -> encoder -> beam-5 decode, "
-                                   f"{n_tok} generated tokens forced by suppressing EOT), seeded random weights",
-                       "streams_per_gpu": S, "batch_per_stream": B, "beam_size": 5, "decode_steps": n_tok, "window_s": WINDOW_S},
-            "stage_ms": stage,
-            "decode_step": {"rows": prows, "graph_replay_ms": step_graph_ms, "sum_kernel_us": step_us, "algorithmic_bytes": sb,
-                            "hbm_frac_of_peak": sb / (step_graph_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                            "kernels": prof},
-            "roofline": roof,
-        }
+        out["h2d_excluded_ms"] = h2d_ms
+        out["decode_step"] = {"rows": prows, "graph_replay_ms": step_graph_ms, "sum_kernel_us": step_us, "algorithmic_bytes": sb,
+                              "hbm_frac_of_peak": sb / (step_graph_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                              "kernels": prof}
+        out["roofline"] = roof
         # the MFMA-regime roofline (SURVEY.md §8d asks for both regimes): encoder + cross-K/V of the timed run
         ef = encoder_flops(spec) * B
         out["roofline_encoder"] = dict(bound="mfma", flops=ef, ms=stage["encode_ms"], achieved=ef / (stage["encode_ms"] * 1e-3) / 1e12,
@@ -992,7 +1037,7 @@ def main():
                                       "fp16-vs-fp32 near-tie ends the common prefix")
     for sl in slots:
         sl.close()
-    if rank == 0 and world == 1 and S == 1 and B == 1 and not args.no_throughput:
+    if rank == 0 and args.full and world == 1 and S == 1 and B == 1 and not args.no_throughput:
         ts_, tb_ = (int(v) for v in args.throughput_shape.lower().split("x"))
         note(f"throughput leg ({ts_} streams x {tb_} windows per decode)")
         try:

@@ -6,12 +6,12 @@ TAG=${1:-r01}; shift || true
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python bench.py --steps 20 --warmup 3 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full --steps 20 --warmup 3 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$?"; tail -c 3000 "$OUT/bench.json"; tail -5 "$OUT/bench.err"
 REPO=$PWD
 cd /tmp
 rocprofv3 --kernel-trace --stats -d "$OUT/rocprof" -o wlx --output-format csv -- \
-  python "$REPO/bench.py" --steps 5 --warmup 1 --no-cpu-baseline "$@" > "$OUT/rocprof.log" 2>&1
+  python "$REPO/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline "$@" > "$OUT/rocprof.log" 2>&1
 echo "rocprof rc=$?"
 cd "$REPO"
 find "$OUT/rocprof" -name '*kernel_stats*' | head

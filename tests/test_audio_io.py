@@ -1,7 +1,8 @@
 """Audio file input (whisperlive_amd/audio_io.py): RIFF/WAVE and FLAC readers, down-mix, resampling — and the one audio
 clip the reference ships, assets/jfk.flac (24-bit stereo 44.1 kHz, the clip of its end-to-end test, tests/test_server.py:73-118),
 decoded here without FFmpeg: the FLAC decoder is pinned by the MD5 of the unencoded audio that the file itself carries.
-The jfk tests skip where /root/reference is absent."""
+The clip's first 3.34 s are committed as tests/golden/jfk_head.flac (the encoder's frames unchanged, STREAMINFO rewritten for the
+shorter stream: tests/golden/make_jfk_head_flac.py), the whole clip at 16 kHz as tests/golden/jfk_16k.npz."""
 import io
 import os
 import struct
@@ -12,8 +13,9 @@ import pytest
 
 from whisperlive_amd import audio_io, vad
 
-JFK = "/root/reference/assets/jfk.flac"
-needs_jfk = pytest.mark.skipif(not os.path.isfile(JFK), reason="reference assets not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+JFK = os.path.join(GOLDEN, "jfk_head.flac")
+JFK_HEAD_16K = 53499                                                   # 147 456 samples at 44.1 kHz resampled to 16 kHz
 
 
 def _wav_bytes(x, sr, width):
@@ -59,24 +61,25 @@ def test_load_audio_downmix_and_resample_keep_a_tone():
     assert y2.shape == (sr,) and np.abs(y2 - tone).max() < 1e-4       # already 16 kHz mono: untouched
 
 
-@needs_jfk
 def test_flac_decoder_matches_the_files_own_md5_and_rejects_damage():
     x, sr = audio_io.read_flac(JFK)                                    # raises unless the decode matches STREAMINFO's MD5
-    assert (sr, x.shape, x.dtype) == (44100, (485100, 2), np.float32) and 0.5 < np.abs(x).max() < 1.0
+    assert (sr, x.shape, x.dtype) == (44100, (147456, 2), np.float32) and 0.5 < np.abs(x).max() < 1.0
     b = bytearray(open(JFK, "rb").read())
     b[200_000] ^= 0x10                                                 # one flipped bit inside a frame
     with pytest.raises(ValueError):
         audio_io.read_flac(bytes(b))
 
 
-@needs_jfk
 def test_jfk_feeds_the_front_end_and_the_vad_gate():
     """the reference's clip through this repo's front half: 11.0 s -> 176 000 samples -> [80, 1101] log-mel (oracle; the
     HIP kernel is held to it on the GPU), and the reference's only VAD assertion (tests/test_vad.py:18-26: speech ->
     detected, silence -> not) on the segmentation logic with the LABELLED energy stand-in (no Silero weights offline)."""
     from oracle import logmel as olm
-    pcm = audio_io.load_audio(JFK)
+    pcm = np.load(os.path.join(GOLDEN, "jfk_16k.npz"))["pcm"]          # audio_io.load_audio of the whole clip (make_jfk_fixture.py)
     assert pcm.shape == (176000,) and pcm.dtype == np.float32
+    head = audio_io.load_audio(JFK)                                    # decode + down-mix + resample of the committed head
+    assert head.shape == (JFK_HEAD_16K,) and head.dtype == np.float32
+    assert np.array_equal(head[:-400], pcm[:JFK_HEAD_16K - 400])      # equal up to the resampler's reach of the cut
     feats = olm.log_mel_spectrogram(pcm, 80)
     assert feats.shape == (80, 1101) and np.isfinite(feats).all() and feats.max() <= 2.0 and feats.min() >= feats.max() - 2.0 - 1e-6
     gate = vad.EnergyGateModel()
@@ -87,7 +90,6 @@ def test_jfk_feeds_the_front_end_and_the_vad_gate():
     assert vad.get_speech_timestamps(np.zeros(176000, np.float32), vad.VadOptions(threshold=0.5), model=gate) == []
 
 
-@needs_jfk
 def test_transcribe_accepts_a_flac_path():
     from tests.fakes import FakeEngine
     from whisperlive_amd.tokenizer import synthetic_tokenizer
@@ -97,4 +99,4 @@ def test_transcribe_accepts_a_flac_path():
     eng.default_tokens = [tb, 300, 301, tb + 100]
     m = WhisperModelHIP("fake", engine=eng, hf_tokenizer=synthetic_tokenizer(eng.spec.vocab))
     segs, info = m.transcribe(JFK, language="en")
-    assert info.duration == 11.0 and segs and eng.slots[0].calls[0] == ("logmel", 0, 176000)
+    assert info.duration == JFK_HEAD_16K / 16000 and segs and eng.slots[0].calls[0] == ("logmel", 0, JFK_HEAD_16K)

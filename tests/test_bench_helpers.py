@@ -64,3 +64,27 @@ def test_cpu_baseline_leg_on_a_tiny_model():
     assert q8["kind"] == "port-int8" and "scaled to 6" in q8["sample"] and len(toks8) == 3
     if aff is not None:
         assert os.sched_getaffinity(0) == aff          # the pinning is undone
+
+
+def test_dump_outputs_writes_every_window_and_caps_the_dense_arrays(tmp_path):
+    """--dump-outputs: tokens / scores / no-speech probabilities of every window in float64, log-mel and encoder output of the
+    first windows that fit the budget in float32, the whole dump under 64 MB"""
+    class Slot:
+        def features(self, b):
+            return np.full((80, 3001), b, np.float32)
+
+        def encoder_output(self, b):
+            return np.full((1500, 768), -b, np.float32)
+    sl = Slot()
+    results = [([7, 8, 9][: 1 + b % 3], -0.25 * b, 0.01 * b) for b in range(16)]
+    bench.dump_outputs(str(tmp_path), results, [(sl, b) for b in range(16)], 3)
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert set(got) == {"tokens", "scores", "no_speech_prob", "logmel", "encoder_output"}
+    assert got["tokens"].dtype == got["scores"].dtype == np.float64 and got["tokens"].shape == (16, 3)
+    assert got["tokens"][0].tolist() == [7, -1, -1] and got["tokens"][2].tolist() == [7, 8, 9] and got["scores"][4] == -1.0
+    k = got["logmel"].shape[0]
+    assert 0 < k < 16 and got["encoder_output"].shape == (k, 1500, 768) and got["logmel"].dtype == np.float32
+    assert got["logmel"][k - 1, 0, 0] == k - 1 and got["encoder_output"][k - 1, 0, 0] == 1 - k
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64e6
+    bench.dump_outputs(str(tmp_path / "c5"), results, [], 0)              # config 5: no resident windows
+    assert sorted(p.stem for p in (tmp_path / "c5").iterdir()) == ["no_speech_prob", "scores", "tokens"]

@@ -15,7 +15,7 @@ from oracle import silero_vad as sv
 from tests import helpers as H
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jfk_16k.npz")
-JFK = "/root/reference/assets/jfk.flac"
+JFK_HEAD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jfk_head.flac")   # the clip's first 3.34 s
 
 
 @pytest.fixture(scope="module")
@@ -32,9 +32,9 @@ def test_fixture_is_the_reference_clip(jfk):
     feats = olm.log_mel_spectrogram(jfk, 80)
     assert feats.shape == (80, 1101) and np.isfinite(feats).all()
     assert float(feats.max() - feats.min()) == pytest.approx(2.0, abs=1e-5)       # the (max - 8) clamp is active: /4 scaling
-    if os.path.isfile(JFK):
-        from whisperlive_amd import audio_io
-        assert np.array_equal(audio_io.load_audio(JFK, sampling_rate=16000), jfk)
+    from whisperlive_amd import audio_io
+    head = audio_io.load_audio(JFK_HEAD, sampling_rate=16000)
+    assert np.array_equal(head[:-400], jfk[:head.size - 400])         # equal up to the resampler's reach of the cut
 
 
 @pytest.mark.gpu

@@ -9,7 +9,7 @@ and skips cleanly without the artefacts:
                     a model directory the loaders understand: CTranslate2 (model.bin + tokenizer.json / vocabulary.*,
                     e.g. Systran/faster-whisper-base.en — what the reference serves) or Hugging Face
                     (model.safetensors + tokenizer.json), whisperlive_amd/weights.py::load_model_dir
-    WLX_WAV         (optional) a WAV / FLAC file; default: the reference's assets/jfk.flac when that checkout is present
+    WLX_WAV         (optional) a WAV / FLAC file; default: the reference's assets/jfk.flac as tests/golden/jfk_16k.npz
     WLX_REF_TEXT    (optional) the expected transcript of WLX_WAV; default: the reference test's ground truth for jfk
     WLX_MAX_WER     (optional) default 0.05, the reference's bound
 
@@ -22,7 +22,6 @@ import re
 import numpy as np
 import pytest
 
-JFK = "/root/reference/assets/jfk.flac"
 JFK_TEXT = ("And so my fellow Americans, ask not, what your country can do for you. "
             "Ask what you can do for your country!")          # tests/test_server.py:92 of the reference
 
@@ -50,8 +49,6 @@ def _find_wav():
     w = os.environ.get("WLX_WAV")
     if w:
         return w
-    if os.path.isfile(JFK):
-        return JFK
     fx = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jfk_16k.npz")     # the same clip, decoded (tests/golden/make_jfk_fixture.py)
     return fx if os.path.isfile(fx) else None
 

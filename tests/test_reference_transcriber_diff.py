@@ -5,7 +5,7 @@ numerical call sites that live in wheels we do not have (ctranslate2, faster_whi
 ``sys.modules`` the file loads unmodified, and ``WhisperModel.__new__`` gives an instance whose ``transcribe`` /
 ``generate_segments`` / ``generate_with_fallback`` / ``get_prompt`` / ``_split_segments_by_timestamps`` /
 ``add_word_timestamps`` / ``find_alignment`` / ``detect_language`` / ``restore_speech_timestamps`` are the reference's
-own (:692-1817). Both that instance and ``WhisperModelHIP(engine=FakeEngine)`` are driven by ONE scripted stand-in for
+own (:692-1817). That instance and ``WhisperModelHIP(engine=FakeEngine)`` are driven by ONE scripted stand-in for
 ``model.generate`` / ``model.detect_language`` / ``model.align`` / the VAD probabilities (a seeded generator: the n-th
 call returns the same thing on both sides), and the test requires
 
@@ -14,32 +14,29 @@ call returns the same thing on both sides), and the test requires
 * identical call sequences at the numerical boundary (prompts and every decoding argument of every ``generate``,
   every ``align``'s tokens / frame count, every ``detect_language``).
 
-Nothing of the reference is stored here: the file is loaded by path at run time and the test skips where
-/root/reference is absent (the GPU box). The un-vendored helpers the reference imports (Tokenizer, VAD segmentation,
+The reference's side is recorded: tests/golden/make_ref_transcriber_golden.py runs it on every case and stores only its answers
+(segments, info, options, error, call log) in tests/golden/ref_transcriber_golden.json.gz; the test runs the repo's side and
+compares it with that record, so it needs no reference checkout. The un-vendored helpers the reference imports (Tokenizer, VAD segmentation,
 SpeechTimestampsMap, get_end, pad_or_trim) are bound to this repo's restatements on BOTH sides — they are the
 dependency's code, not the reference's, and are pinned separately (tests/test_host_logic.py, test_word_timing.py)."""
 from __future__ import annotations
 
 import dataclasses
-import importlib.util
-import logging
+import gzip
+import json
 import os
-import sys
-import types
 from typing import List
 
 import numpy as np
 import pytest
 
 from tests.fakes import FakeEngine, FakeSlot
-from whisperlive_amd import vad as wvad
-from whisperlive_amd import word_timing as wwt
 from whisperlive_amd.engine import GenerationResult
-from whisperlive_amd.tokenizer import LANGUAGE_CODES, Tokenizer, synthetic_tokenizer
+from whisperlive_amd.tokenizer import Tokenizer, synthetic_tokenizer
 from whisperlive_amd.transcriber import WhisperModelHIP
 
-REF_FILE = "/root/reference/whisper_live/transcriber/transcriber_faster_whisper.py"
-pytestmark = pytest.mark.skipif(not os.path.isfile(REF_FILE), reason="reference checkout not present (GPU box)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_transcriber_golden.json.gz")
+INFO_FIELDS = ("language", "language_probability", "duration", "duration_after_vad", "all_language_probs")
 
 V = 2310
 N_CASES = 320
@@ -141,142 +138,6 @@ class Script:
             p[i:i + run] = level
             i += run
         return p
-
-
-# ------------------------------------------------------------------------------------------------------------------
-# reference side: module loaded by path with the un-vendored imports stubbed
-def _load_reference(script_holder):
-    names = ["ctranslate2", "faster_whisper", "faster_whisper.audio", "faster_whisper.feature_extractor",
-             "faster_whisper.tokenizer", "faster_whisper.utils", "faster_whisper.vad"]
-    saved = {n: sys.modules.get(n) for n in names}
-    ct2 = types.ModuleType("ctranslate2")
-
-    class StorageView:
-        @staticmethod
-        def from_array(a):
-            return a
-    ct2.StorageView = StorageView
-    ct2.models = types.SimpleNamespace(Whisper=object, WhisperGenerationResult=object)
-    fw = types.ModuleType("faster_whisper")
-    audio = types.ModuleType("faster_whisper.audio")
-
-    def pad_or_trim(array, length=3000, axis=-1):
-        n = array.shape[axis]
-        if n > length:
-            return array.take(indices=range(length), axis=axis)
-        if n < length:
-            w = [(0, 0)] * array.ndim
-            w[axis] = (0, length - n)
-            return np.pad(array, w)
-        return array
-    audio.pad_or_trim = pad_or_trim
-    audio.decode_audio = lambda *a, **k: (_ for _ in ()).throw(RuntimeError("no decoder in the test"))
-    fe = types.ModuleType("faster_whisper.feature_extractor")
-    fe.FeatureExtractor = object
-    tokm = types.ModuleType("faster_whisper.tokenizer")
-    tokm.Tokenizer = Tokenizer
-    tokm._LANGUAGE_CODES = LANGUAGE_CODES
-    utils = types.ModuleType("faster_whisper.utils")
-    utils.download_model = lambda *a, **k: (_ for _ in ()).throw(RuntimeError("offline"))
-    utils.format_timestamp = lambda s, *a, **k: f"{s:.3f}"
-    utils.get_logger = lambda: logging.getLogger("faster_whisper")
-    utils.get_end = wwt.last_word_end
-    vadm = types.ModuleType("faster_whisper.vad")
-    vadm.VadOptions = wvad.VadOptions
-    vadm.SpeechTimestampsMap = wvad.SpeechTimestampsMap
-    vadm.collect_chunks = wvad.collect_chunks
-    vadm.get_speech_timestamps = lambda audio_, opts=None, **kw: wvad.get_speech_timestamps(
-        audio_, opts, model=script_holder["vad"])
-    mods = dict(zip(names, [ct2, fw, audio, fe, tokm, utils, vadm]))
-    sys.modules.update(mods)
-    try:
-        spec = importlib.util.spec_from_file_location("_ref_transcriber_under_test", REF_FILE)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        for n, m in saved.items():
-            if m is None:
-                sys.modules.pop(n, None)
-            else:
-                sys.modules[n] = m
-    return mod
-
-
-class _RefFeatureExtractor:
-    """attributes the reference reads (:656-665,1058,1115-1126) + a frame-count-only __call__"""
-    n_fft, hop_length, chunk_length, sampling_rate = 400, 160, 30, 16000
-    n_samples, nb_max_frames, time_per_frame = 480000, 3000, 0.01
-
-    def __call__(self, waveform, padding=160, chunk_length=None):
-        # column j carries j + 1, so the scripted encoder can read (seek, window size) back from what it is handed
-        t = (len(waveform) + padding) // 160
-        return np.broadcast_to(np.arange(1, t + 1, dtype=np.float32), (80, t)).copy()
-
-
-class _RefCT2:
-    """ctranslate2.models.Whisper as the reference calls it, answering from the script"""
-    device, device_index = "cuda", [0]
-
-    def __init__(self, script: Script, hf_tok, multilingual: bool):
-        self.s, self.hf, self.is_multilingual = script, hf_tok, multilingual
-        bt = Tokenizer(hf_tok, False)
-        self.langs = bt.language_token_ids()
-        self.non_speech = set(bt.non_speech_tokens)
-
-    def encode(self, features, to_cpu=False):
-        f = np.asarray(features)
-        assert f.shape == (1, 80, 3000)                   # pad_or_trim'ed window, batch axis added (:1344-1348)
-        row = f[0, 0]
-        self.s.log.append(("encode", int(row[0]) - 1, int(np.count_nonzero(row))))
-        return object()
-
-    def generate(self, enc, prompts, **kw):
-        assert len(prompts) == 1
-        prompt = list(prompts[0])
-        sup = sorted(set(kw.get("suppress_tokens") or ()))
-        beam = kw.get("beam_size", 5)
-        temp = 0.0 if beam > 1 else (float(kw.get("sampling_temperature", 1.0)) if kw.get("sampling_topk", 1) != 1 else 0.0)
-        self.s.log.append(("generate", prompt, beam, float(kw.get("patience", 1)), kw.get("num_hypotheses", 1),
-                           float(kw["length_penalty"]), float(kw["repetition_penalty"]), kw["no_repeat_ngram_size"],
-                           kw["max_length"], bool(kw["suppress_blank"]), tuple(sup), kw["max_initial_timestamp_index"],
-                           round(temp, 6)))
-        toks, score, nsp = self.s.generate(prompt, kw["max_length"] - len(prompt))
-        return [types.SimpleNamespace(sequences_ids=[toks], scores=[score], no_speech_prob=nsp)]
-
-    def detect_language(self, enc):
-        self.s.log.append(("detect_language",))
-        p = self.s.lang_probs()
-        pairs = [(f"<|{c}|>", float(np.float32(x))) for (c, _i), x in zip(self.langs, p)]
-        return [sorted(pairs, key=lambda x: -x[1])]
-
-    def align(self, enc, start_sequence, text_tokens, num_frames, median_filter_width=7):
-        out = []
-        for toks in text_tokens:
-            if not toks:
-                # the reference still calls align for a window without text tokens and then discards the result
-                # (:1670-1678 "return on eot only"); the HIP host skips that device call — the one tolerated difference
-                out.append(types.SimpleNamespace(alignments=[], text_token_probs=[]))
-                continue
-            self.s.log.append(("align", list(start_sequence), list(toks), int(num_frames), median_filter_width))
-            pairs, probs = self.s.align(len(toks), num_frames)
-            out.append(types.SimpleNamespace(alignments=pairs, text_token_probs=probs))
-        return out
-
-
-def _make_reference(refmod, script, hf_tok, multilingual):
-    m = refmod.WhisperModel.__new__(refmod.WhisperModel)
-    m.logger = logging.getLogger("faster_whisper")
-    m.model = _RefCT2(script, hf_tok, multilingual)
-    m.hf_tokenizer = hf_tok
-    m.feat_kwargs = {}
-    m.feature_extractor = _RefFeatureExtractor()
-    m.input_stride = 2
-    m.num_samples_per_token = 320
-    m.frames_per_second = 100
-    m.tokens_per_second = 50
-    m.time_precision = 0.02
-    m.max_length = 448
-    return m
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -383,69 +244,80 @@ def _seg_tuple(s):
             s.temperature, words)
 
 
-@pytest.fixture(scope="module")
-def refmod():
-    holder = {"vad": None}
-    mod = _load_reference(holder)
-    mod._script_holder = holder
-    return mod
+def _jsonable(x):
+    if isinstance(x, np.generic):
+        return x.item()
+    if isinstance(x, np.ndarray):
+        return x.tolist()
+    raise TypeError(f"{type(x).__name__} is not recorded")
 
 
-def _run_both(refmod, seed):
+def _record(segs, info, err, log, kw=None):
+    """one side's answer to one case in the form the golden file stores (JSON: tuples become lists, floats round-trip exactly)"""
+    rec = dict(kw=kw, err=err, log=log, segs=None if segs is None else [_seg_tuple(s) for s in segs], info=None, options=None)
+    if info is not None:
+        rec["info"] = {f: getattr(info, f) for f in INFO_FIELDS}
+        o = dataclasses.asdict(info.transcription_options)
+        o["temperatures"] = list(o["temperatures"])
+        o["suppress_tokens"] = None if o["suppress_tokens"] is None else list(o["suppress_tokens"])
+        rec["options"] = o
+    return json.loads(json.dumps(rec, default=_jsonable))
+
+
+def run_case(seed, make_model):
+    """transcribe() of case `seed` on the model `make_model(script, hf_tokenizer, multilingual_model, vad_model)` builds"""
     multilingual_model, seconds, kw = _case(seed)
     hf = synthetic_tokenizer(V)
     n_lang = len(Tokenizer(hf, False).language_token_ids())
-    style = dict(without_timestamps=kw.get("without_timestamps", False))
-    audio = np.zeros(int(seconds * 16000), np.float32)
+    script = Script(seed, hf, n_lang, dict(without_timestamps=kw.get("without_timestamps", False)))
+    vad_model = lambda padded: script.vad_probs(padded.shape[0] // 512)   # noqa: E731
+    m = make_model(script, hf, multilingual_model, vad_model)
+    try:
+        segs, info = m.transcribe(np.zeros(int(seconds * 16000), np.float32),
+                                  **{k: (list(v) if isinstance(v, list) else v) for k, v in kw.items()})
+        err = None
+    except Exception as e:                                    # noqa: BLE001  (error behaviour must match too)
+        segs, info, err = None, None, (type(e).__name__, str(e))
+    return _record(segs, info, err, script.log, kw)
 
-    def run(side):
-        script = Script(seed, hf, n_lang, style)
-        vad_model = lambda padded: script.vad_probs(padded.shape[0] // 512)   # noqa: E731
-        if side == "ref":
-            refmod._script_holder["vad"] = vad_model
-            m = _make_reference(refmod, script, hf, multilingual_model)
-        else:
-            m = WhisperModelHIP("fake", engine=_ScriptEngine(script), hf_tokenizer=hf, multilingual=multilingual_model,
-                                vad_model=vad_model)
-        try:
-            segs, info = m.transcribe(audio.copy(), **{k: (list(v) if isinstance(v, list) else v) for k, v in kw.items()})
-            err = None
-        except Exception as e:                                    # noqa: BLE001  (error behaviour must match too)
-            segs, info, err = None, None, (type(e).__name__, str(e))
-        return segs, info, err, script.log
 
-    return kw, run("ref"), run("hip")
+def _hip_model(script, hf, multilingual_model, vad_model):
+    return WhisperModelHIP("fake", engine=_ScriptEngine(script), hf_tokenizer=hf, multilingual=multilingual_model, vad_model=vad_model)
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with gzip.open(GOLDEN, "rt", encoding="utf-8") as f:
+        cases = json.load(f)
+    assert len(cases) == N_CASES
+    return cases
 
 
 @pytest.mark.parametrize("block", range(8))
-def test_transcribe_matches_reference_code(refmod, block):
+def test_transcribe_matches_reference_code(golden, block):
     per = N_CASES // 8
-    n_segments = n_words = n_generate = 0
+    n_generate = 0
     for seed in range(block * per, (block + 1) * per):
-        kw, (rs, ri, rerr, rlog), (hs, hi, herr, hlog) = _run_both(refmod, seed)
-        ctx = f"seed {seed} kw {kw}"
-        assert rerr == herr, ctx
+        ref, hip = golden[seed], run_case(seed, _hip_model)
+        ctx = f"seed {seed} kw {hip['kw']}"
+        assert ref["kw"] == hip["kw"], f"{ctx}: the golden file was made from other cases"
+        assert ref["err"] == hip["err"], ctx
+        rlog, hlog = ref["log"], hip["log"]
         assert rlog == hlog, f"{ctx}\nfirst differing call: " + next(
             (f"#{i}: ref {a} != hip {b}" for i, (a, b) in enumerate(zip(rlog, hlog)) if a != b),
             f"length {len(rlog)} vs {len(hlog)}")
-        if rs is None:
-            assert hs is None and hi is None and ri is None, ctx
+        if ref["segs"] is None:
+            assert hip["segs"] is None and hip["info"] is None and ref["info"] is None, ctx
             continue
-        assert [_seg_tuple(s) for s in rs] == [_seg_tuple(s) for s in hs], ctx
-        for f in ("language", "language_probability", "duration", "duration_after_vad", "all_language_probs"):
-            assert getattr(ri, f) == getattr(hi, f), f"{ctx}: info.{f}"
-        ro, ho = dataclasses.asdict(ri.transcription_options), dataclasses.asdict(hi.transcription_options)
-        ro["temperatures"], ho["temperatures"] = list(ro["temperatures"]), list(ho["temperatures"])
-        ro["suppress_tokens"] = None if ro["suppress_tokens"] is None else list(ro["suppress_tokens"])
-        ho["suppress_tokens"] = None if ho["suppress_tokens"] is None else list(ho["suppress_tokens"])
-        assert ro == ho, ctx
-        n_segments += len(rs)
-        n_words += sum(len(s.words or []) for s in rs)
+        assert ref["segs"] == hip["segs"], ctx
+        for f in INFO_FIELDS:
+            assert ref["info"][f] == hip["info"][f], f"{ctx}: info.{f}"
+        assert ref["options"] == hip["options"], ctx
         n_generate += sum(1 for c in rlog if c[0] == "generate")
     assert n_generate > per                                         # the block did real work
 
 
-def test_case_generator_covers_the_branches(refmod):
+def test_case_generator_covers_the_branches(golden):
     """the random cases reach the paths the verdict named: word timestamps, multilingual, clip_timestamps,
     hallucination_silence_threshold, VAD-gated transcribe, temperature fallback, (None, None)"""
     seen = dict(words=0, multilingual=0, clips=0, halluc=0, vad=0, fallback=0, none=0, detect=0, align=0)
@@ -457,7 +329,7 @@ def test_case_generator_covers_the_branches(refmod):
         seen["halluc"] += "hallucination_silence_threshold" in kw
         seen["vad"] += bool(kw.get("vad_filter"))
     for seed in range(0, N_CASES, 4):
-        _kw, (rs, _ri, _e, rlog), _hip = _run_both(refmod, seed)
+        rs, rlog = golden[seed]["segs"], golden[seed]["log"]
         seen["none"] += rs is None
         seen["fallback"] += any(c[0] == "generate" and c[-1] > 0 for c in rlog)
         seen["detect"] += any(c[0] == "detect_language" for c in rlog)
