@@ -284,6 +284,42 @@ int32_t wlx_vad_segments(const float* probs, int32_t n_windows, int64_t n_sample
 int32_t wlx_logmel_ring(wlx_engine* e, int32_t slot, int32_t item, wlx_ring* r, const int64_t* ranges, int32_t n_ranges,
                         int32_t* n_frames_out);
 
+/* ---- text translation (M2M100 / small100) — PRODUCT entry points of the `enable_translation` side channel ----
+ * Replaces the reference's per-client M2M100ForConditionalGeneration.generate() on torch.cuda
+ * (whisper_live/backend/translation_backend.py:62-66,86-96; wired in whisper_live/server.py:203-229).
+ * Weights: float32 tensors named with their Hugging Face M2M100 keys ("model.shared.weight",
+ * "model.encoder.layers.{i}.self_attn.q_proj.weight", ...; the output projection is tied to model.shared), host or device
+ * pointers as for wlx_engine_create. A slot owns a NON-BLOCKING stream (it takes none of the hardware queues of the ASR slots)
+ * and every device buffer of a call for max_batch items of <= max_src source tokens and max_rows_per_item beams; calls on a
+ * busy slot return WLX_ERR_STATE. */
+typedef struct {
+    int32_t d_model, n_heads, enc_layers, dec_layers, ffn, vocab;
+    int32_t max_positions;       /* max_position_embeddings (1024): source length and max_length are bounded by it */
+    int32_t pad_id, eos_id, decoder_start_id;
+    int32_t scale_embedding;     /* embeddings scaled by sqrt(d_model) */
+} wlx_mt_spec;
+typedef struct wlx_mt wlx_mt;
+/* Generation options = the beam-search settings of transformers' generate() (M2M100's generation_config.json). */
+typedef struct {
+    int32_t num_beams;             /* 1 = greedy search */
+    int32_t max_length;            /* decoder tokens including the decoder start token, <= min(448, max_positions) */
+    int32_t early_stopping;        /* 0 = False, 1 = True, 2 = "never" */
+    float   length_penalty;
+    int32_t no_repeat_ngram_size;  /* 0 = off */
+    int32_t forced_eos_token_id;   /* -1 = none */
+} wlx_mt_gen_opts;
+int32_t wlx_mt_create(const wlx_mt_spec* spec, const wlx_tensor* weights, int32_t n_weights, int32_t device, wlx_mt** out);
+void    wlx_mt_destroy(wlx_mt* mt);
+int32_t wlx_mt_slot_create(wlx_mt* mt, int32_t max_batch, int32_t max_rows_per_item, int32_t max_src, int32_t* slot_out);
+int32_t wlx_mt_slot_destroy(wlx_mt* mt, int32_t slot);
+/* Translate `batch` sources (src_ids[i][0 .. src_lens[i]) with row stride src_stride: [tgt_lang_code] + pieces + [eos] for
+ * small100). Outputs per item: the best hypothesis' generated tokens (decoder start and final EOS excluded, at most
+ * tokens_stride), their count, and its score (beam search: Hugging Face's sequences_scores = sum of log-probabilities /
+ * generated_length ** length_penalty; greedy: the sum of the log-probabilities). Returns when the results are final. */
+int32_t wlx_mt_translate(wlx_mt* mt, int32_t slot, int32_t batch, const int32_t* src_ids, const int32_t* src_lens,
+                         int32_t src_stride, const wlx_mt_gen_opts* opts, int32_t* tokens_out, int32_t tokens_stride,
+                         int32_t* n_tokens_out, float* scores_out);
+
 /* ==== everything below: TEST / PROFILING hooks (used only by tests/, scripts/ and bench.py's roofline leg; not part of
  * the drop-in boundary; the product entry points end here) ================================================================= */
 /* next-token logits [rows, vocab] of the last decoder step executed on the slot */
@@ -313,6 +349,15 @@ int32_t wlx_debug_trace_step(wlx_engine* e, int32_t slot, int32_t rows, int32_t 
 
 int32_t wlx_debug_profile_step(wlx_engine* e, int32_t slot, int32_t rows, int32_t t, int32_t iters,
                                wlx_kernel_stat* out, int32_t cap, int32_t* n_out);
+
+/* translation engine: float32 final encoder output of `batch` sources, packed item after item ([sum src_lens][d_model]) */
+int32_t wlx_mt_debug_encode(wlx_mt* mt, int32_t slot, int32_t batch, const int32_t* src_ids, const int32_t* src_lens,
+                            int32_t src_stride, float* out, int64_t cap_floats);
+/* translation engine: teacher-forced decoder logits [n][vocab] of one source and decoder tokens dec_tokens[0 .. n) */
+int32_t wlx_mt_debug_decode_logits(wlx_mt* mt, int32_t slot, const int32_t* src_ids, int32_t src_len, const int32_t* dec_tokens,
+                                   int32_t n, float* out);
+/* translation engine: device times (HIP events) of the slot's last wlx_mt_translate: encoder pass, decode loop, decode steps */
+int32_t wlx_mt_debug_timings(wlx_mt* mt, int32_t slot, float* encode_ms, float* decode_ms, int32_t* steps);
 
 #ifdef __cplusplus
 }

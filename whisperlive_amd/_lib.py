@@ -13,14 +13,16 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "engine.hip", "vad.hip"]
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "engine.hip", "vad.hip", "mt.hip", "mt_engine.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
     "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
     "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
+    "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
+    "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings",
 ]
 
 
@@ -72,6 +74,16 @@ class wlx_vad_weights(C.Structure):
     _fields_ = [("stft_basis", C.POINTER(C.c_float)), ("enc_w", C.POINTER(C.c_float) * 4), ("enc_b", C.POINTER(C.c_float) * 4),
                 ("lstm_w_ih", C.POINTER(C.c_float)), ("lstm_w_hh", C.POINTER(C.c_float)), ("lstm_b_ih", C.POINTER(C.c_float)),
                 ("lstm_b_hh", C.POINTER(C.c_float)), ("out_w", C.POINTER(C.c_float)), ("out_b", C.POINTER(C.c_float))]
+
+
+class wlx_mt_spec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d_model", "n_heads", "enc_layers", "dec_layers", "ffn", "vocab", "max_positions",
+                                         "pad_id", "eos_id", "decoder_start_id", "scale_embedding")]
+
+
+class wlx_mt_gen_opts(C.Structure):
+    _fields_ = [("num_beams", C.c_int32), ("max_length", C.c_int32), ("early_stopping", C.c_int32),
+                ("length_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32), ("forced_eos_token_id", C.c_int32)]
 
 
 _extra_ok = None
@@ -237,9 +249,18 @@ def load() -> C.CDLL:
     lib.wlx_debug_time_decode_step.argtypes = [vp, i32, i32, i32, i32, f32p]
     lib.wlx_debug_profile_step.argtypes = [vp, i32, i32, i32, i32, C.POINTER(wlx_kernel_stat), i32, i32p]
     lib.wlx_debug_trace_step.argtypes = [vp, i32, i32, i32, i32, C.POINTER(C.c_uint64), i64, C.c_char_p, i32p]
+    lib.wlx_mt_create.argtypes = [C.POINTER(wlx_mt_spec), C.POINTER(wlx_tensor), i32, i32, C.POINTER(vp)]
+    lib.wlx_mt_destroy.argtypes = [vp]
+    lib.wlx_mt_destroy.restype = None
+    lib.wlx_mt_slot_create.argtypes = [vp, i32, i32, i32, i32p]
+    lib.wlx_mt_slot_destroy.argtypes = [vp, i32]
+    lib.wlx_mt_translate.argtypes = [vp, i32, i32, i32p, i32p, i32, C.POINTER(wlx_mt_gen_opts), i32p, i32, i32p, f32p]
+    lib.wlx_mt_debug_encode.argtypes = [vp, i32, i32, i32p, i32p, i32, f32p, i64]
+    lib.wlx_mt_debug_decode_logits.argtypes = [vp, i32, i32p, i32, i32p, i32, f32p]
+    lib.wlx_mt_debug_timings.argtypes = [vp, i32, f32p, f32p, i32p]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy"):
+        if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_mt_destroy"):
             fn.restype = i32
     if lib.wlx_abi_version() != 1:
         raise WlxError("libwlx.so ABI version mismatch")

@@ -176,3 +176,56 @@ def download_silero(fetch: Optional[Callable[[str, str], None]] = None) -> Optio
     except Exception as e:  # noqa: BLE001
         logging.debug("silero download: %s: %s", type(e).__name__, e)
         return None
+
+
+# ---- the translation model of the `enable_translation` side channel (reference: whisper_live/backend/translation_backend.py:25,62)
+TRANSLATION_MODEL = "alirezamsh/small100"
+_MT_FILES = ["config.json", "generation_config.json", "model.safetensors", "model.safetensors.index.json", "model-*.safetensors",
+             "pytorch_model.bin", "vocab.json", "sentencepiece.bpe.model", "tokenizer_config.json", "special_tokens_map.json"]
+
+
+def is_mt_model_dir(path: str) -> bool:
+    """config.json + weights (safetensors or pytorch_model.bin) + vocab.json + a sentencepiece model"""
+    if not (path and os.path.isdir(path)):
+        return False
+    j = lambda f: os.path.isfile(os.path.join(path, f))
+    has_w = j("model.safetensors") or j("model.safetensors.index.json") or j("pytorch_model.bin")
+    return has_w and j("config.json") and j("vocab.json") and (j("sentencepiece.bpe.model") or j("spm.model"))
+
+
+def resolve_translation_model(name_or_path: str = TRANSLATION_MODEL, download_root: Optional[str] = None,
+                              local_files_only: Optional[bool] = None,
+                              snapshot: Optional[Callable[[str, Optional[str], bool], Optional[str]]] = None) -> Optional[str]:
+    """A translation checkpoint DIRECTORY or None: an existing directory -> $WLX_MODEL_ROOT/<name> -> the Hugging Face cache
+    (local_files_only) -> a download (unless local_files_only / HF_HUB_OFFLINE=1 / WLX_NO_DOWNLOAD=1). `snapshot` replaces the hub
+    call in tests."""
+    def hub(repo, cache_dir, local_only):
+        try:
+            from huggingface_hub import snapshot_download
+        except ImportError:
+            return None
+        try:
+            return snapshot_download(repo_id=repo, repo_type="model", cache_dir=cache_dir, local_files_only=local_only,
+                                     allow_patterns=_MT_FILES, etag_timeout=5)
+        except Exception as e:  # noqa: BLE001
+            logging.debug("hub %s: %s: %s", repo, type(e).__name__, e)
+            return None
+    snap = snapshot or hub
+    p = os.path.expanduser(str(name_or_path))
+    if is_mt_model_dir(p):
+        return p
+    root = os.environ.get("WLX_MODEL_ROOT")
+    if root:
+        for cand in (os.path.join(root, name_or_path), os.path.join(root, os.path.basename(str(name_or_path)))):
+            if is_mt_model_dir(cand):
+                return cand
+    if "/" not in str(name_or_path) or str(name_or_path).startswith((".", "/", "~")):
+        return None
+    d = snap(str(name_or_path), download_root, True)
+    if d and is_mt_model_dir(d):
+        return d
+    if downloads_allowed(local_files_only):
+        d = snap(str(name_or_path), download_root, False)
+        if d and is_mt_model_dir(d):
+            return d
+    return None

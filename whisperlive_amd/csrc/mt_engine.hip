@@ -1,0 +1,829 @@
+// mt_engine.hip — the M2M100 / small100 translation engine behind the wlx_mt_* entry points of include/wlx.h.
+//
+// Per call: the items' sources are packed by length (no pad rows), embedded (scale * shared + sinusoidal positions), run through
+// the pre-norm encoder, and the cross K / V of every decoder layer is computed once from the final encoder output (one GEMM over
+// all layers). The decoder then runs one eager step per generated token for batch x num_beams rows: fused q/k/v projection, KV
+// append, self-attention through the beam ancestry table, cross-attention over each item's own source length, ReLU MLP, final
+// LayerNorm and the tied vocabulary projection in fp32, followed by the two-stage log-softmax + top-k kernels of mt.hip. The
+// candidates (2 x num_beams per row) come back to the host, where Hugging Face's beam-search bookkeeping (generation/utils.py
+// _beam_search of transformers 5.x: length normaliser, early_stopping heuristics, forced EOS, no_repeat_ngram) runs in a few
+// microseconds per step. All projections use the MFMA GEMM of gemm.hip; nothing is captured into a graph.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "engine.h"
+#include "mt.h"
+
+using namespace wlx;
+
+#define MCK(call)                                                                                                 \
+    do {                                                                                                          \
+        hipError_t e_ = (call);                                                                                   \
+        if (e_ != hipSuccess)                                                                                     \
+            return set_error(WLX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+#define MCKR(call)                   \
+    do {                             \
+        int r_ = (call);             \
+        if (r_ != WLX_OK) return r_; \
+    } while (0)
+
+namespace {
+
+struct MtLayer {
+    float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr, *ln3_g = nullptr, *ln3_b = nullptr;
+    half_t *Wqkv = nullptr, *Wo = nullptr, *Wcq = nullptr, *Wco = nullptr, *W1 = nullptr, *W2 = nullptr;
+    float *bqkv = nullptr, *bo = nullptr, *bcq = nullptr, *bco = nullptr, *b1 = nullptr, *b2 = nullptr;
+};
+
+struct MtSlot {
+    std::atomic<bool> busy{false};
+    int B = 0, R = 0, max_src = 0, rows_cap = 0, src_cap = 0, tmax = WLX_T_TEXT;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[4] = {};
+    std::vector<void*> allocs, host_allocs;
+    // encoder (packed source rows)
+    float *xe = nullptr, *enc32 = nullptr;
+    half_t *he = nullptr, *qkve = nullptr, *atte = nullptr, *ffe = nullptr, *ckv = nullptr;   // ckv: [src_cap][L * 2d]
+    // decoder rows
+    float *xd = nullptr, *logits = nullptr, *tk_scratch = nullptr, *tk_val = nullptr;
+    half_t *hd = nullptr, *qkvd = nullptr, *qd = nullptr, *attd = nullptr, *ffd = nullptr, *kc = nullptr, *vc = nullptr;
+    int *tk_cidx = nullptr, *tk_idx = nullptr;
+    int *d_tok = nullptr, *d_pos = nullptr, *d_anc = nullptr, *d_ban = nullptr, *d_nban = nullptr;
+    int *d_src_tok = nullptr, *d_src_pos = nullptr;
+    MtAttnGroup *d_genc = nullptr, *d_gself = nullptr, *d_gcross = nullptr;
+    int ban_ld = 0;
+    // pinned host staging. An asynchronous copy reads its pinned source when it EXECUTES, so a buffer is rewritten only after the
+    // stream has been synchronised past the copies that read it. The encoder has its own buffers (h_src_*, h_genc): run_generate
+    // fills the decoder's h_tok / h_pos right after encode() returns, while the encoder's copies may still be queued.
+    int *h_src_tok = nullptr, *h_src_pos = nullptr;
+    int *h_tok = nullptr, *h_pos = nullptr, *h_anc = nullptr, *h_ban = nullptr, *h_nban = nullptr, *h_tk_idx = nullptr;
+    float* h_tk_val = nullptr;
+    MtAttnGroup *h_genc = nullptr, *h_gself = nullptr, *h_gcross = nullptr;
+    // state of the last encode
+    int n_items = 0, n_src = 0;
+    std::vector<int> src_off, src_len;
+    float enc_ms = 0.f, dec_ms = 0.f;
+    int steps = 0;
+};
+
+}  // namespace
+
+struct wlx_mt {
+    wlx_mt_spec spec{};
+    int device = 0;
+    std::vector<MtLayer> enc, dec;
+    float *enc_ln_g = nullptr, *enc_ln_b = nullptr, *dec_ln_g = nullptr, *dec_ln_b = nullptr;
+    half_t* E = nullptr;          // shared embedding, packed (vocab x d): token rows for the embedding, the tied output projection
+    half_t* Wckv = nullptr;       // cross k / v of every decoder layer: [L * 2d][d] packed
+    float* bckv = nullptr;
+    float* sinpos = nullptr;      // [max_positions + 2][d]
+    float embed_scale = 1.f;
+    std::vector<void*> allocs;
+    std::mutex mu;
+    std::map<int, MtSlot*> slots;
+    int next_slot = 0;
+};
+
+namespace {
+
+template <class T>
+int dalloc(std::vector<void*>& list, T** p, size_t n) {
+    void* q = nullptr;
+    MCK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+    list.push_back(q);
+    *p = reinterpret_cast<T*>(q);
+    return WLX_OK;
+}
+template <class T>
+int halloc(std::vector<void*>& list, T** p, size_t n) {
+    void* q = nullptr;
+    MCK(hipHostMalloc(&q, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault));
+    list.push_back(q);
+    *p = reinterpret_cast<T*>(q);
+    return WLX_OK;
+}
+
+__global__ void mt_scale_kernel(float* x, long n, float a) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] *= a;
+}
+
+struct Loader {
+    const wlx_tensor* w;
+    int n;
+    hipStream_t st;
+    // ONE fp32 staging buffer for the matrices, grown to the largest one: a pack kernel reads it on `st`, and the next copy into
+    // it is queued behind that kernel on the same stream, so it is reused without a wait (a full fp32 copy of small100 is ~1.3 GB)
+    float* stage = nullptr;
+    size_t stage_bytes = 0;
+    ~Loader() {
+        if (stage) (void)hipFree(stage);
+    }
+    const wlx_tensor* find(const std::string& name) const {
+        for (int i = 0; i < n; ++i)
+            if (w[i].name && name == w[i].name) return &w[i];
+        return nullptr;
+    }
+    // fp32 device copy of tensor `name` of shape [r] (c == 0) or [r][c]; `dst` may be given (then the copy goes there)
+    int get(const std::string& name, long r, long c, float** out, float* dst = nullptr) {
+        const wlx_tensor* t = find(name);
+        if (!t) return set_error(WLX_ERR_WEIGHT, "missing weight %s", name.c_str());
+        const bool ok = c == 0 ? (t->ndim == 1 && t->shape[0] == r) : (t->ndim == 2 && t->shape[0] == r && t->shape[1] == c);
+        if (!ok) return set_error(WLX_ERR_WEIGHT, "weight %s: expected shape [%ld%s%ld]", name.c_str(), r, c ? ", " : "", c ? c : 0L);
+        const size_t bytes = (size_t)r * (c ? c : 1) * sizeof(float);
+        if (!dst) {
+            if (bytes > stage_bytes) {
+                MCK(hipStreamSynchronize(st));            // (the kernels still reading the old buffer)
+                if (stage) MCK(hipFree(stage));
+                stage = nullptr;
+                stage_bytes = 0;
+                MCK(hipMalloc((void**)&stage, bytes));
+                stage_bytes = bytes;
+            }
+            dst = stage;
+        }
+        MCK(hipMemcpyAsync(dst, t->data, bytes, t->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        MCK(hipStreamSynchronize(st));      // (host tensors may be pageable temporaries of the caller)
+        *out = dst;
+        return WLX_OK;
+    }
+};
+
+int pack(Loader& L, const std::string& name, int N, int K, half_t* Wp, int KT, int nt0, float scale = 1.f) {
+    float* w = nullptr;
+    MCKR(L.get(name, N, K, &w));
+    if (scale != 1.f) hipLaunchKernelGGL(mt_scale_kernel, dim3((unsigned)(((long)N * K + 255) / 256)), dim3(256), 0, L.st, w, (long)N * K, scale);
+    launch_pack_linear(w, N, K, K, Wp, KT, nt0, L.st);
+    MCK(hipGetLastError());
+    return WLX_OK;
+}
+int vec(Loader& L, std::vector<void*>& allocs, const std::string& name, int n, float** out) {
+    MCKR(dalloc(allocs, out, n));
+    float* p = nullptr;
+    return L.get(name, n, 0, &p, *out);
+}
+int vec_into(Loader& L, const std::string& name, int n, float* dst, float scale = 1.f) {
+    float* p = nullptr;
+    MCKR(L.get(name, n, 0, &p, dst));
+    if (scale != 1.f) hipLaunchKernelGGL(mt_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, L.st, dst, (long)n, scale);
+    return WLX_OK;
+}
+
+// C = A W^T + b (fp16 out) or X += A W^T + b (fp32): the encoder GEMM of gemm.hip
+void gemm(const half_t* A, long lda, int M, const half_t* Wp, int K, int N, const float* bias, int mode, half_t* C, long ldc,
+          float* X, long ldx, hipStream_t s) {
+    GemmParams p{};
+    p.A = A; p.lda = lda; p.Wp = Wp; p.KT = K / 32; p.M = M; p.N = N; p.mode = mode; p.bias = bias;
+    p.C = C; p.ldc = ldc; p.X = X; p.ldx = ldx;
+    launch_gemm(p, 1, s);
+}
+
+MtSlot* slot_of(wlx_mt* m, int id) {
+    std::lock_guard<std::mutex> g(m->mu);
+    auto it = m->slots.find(id);
+    return it == m->slots.end() ? nullptr : it->second;
+}
+
+struct Busy {
+    MtSlot* s;
+    bool ok;
+    explicit Busy(MtSlot* s_) : s(s_) { bool f = false; ok = s->busy.compare_exchange_strong(f, true); }
+    ~Busy() { if (ok) s->busy.store(false); }
+};
+
+// HF create_position_ids_from_input_ids: non-pad tokens count from padding_idx + 1 (+ past), pad tokens sit at padding_idx
+inline int position_of(int tok, int nonpad_before_incl, int past, int pad) { return tok != pad ? nonpad_before_incl + past + pad : pad; }
+
+int encode(wlx_mt* m, MtSlot* s, int batch, const int32_t* src, const int32_t* lens, int stride) {
+    const wlx_mt_spec& sp = m->spec;
+    const int d = sp.d_model, F = sp.ffn, H = sp.n_heads, Ld = sp.dec_layers;
+    if (batch < 1 || batch > s->B) return set_error(WLX_ERR_ARG, "batch %d outside 1..%d (slot max_batch)", batch, s->B);
+    if (!src || !lens) return set_error(WLX_ERR_ARG, "null source");
+    s->src_off.assign(batch, 0);
+    s->src_len.assign(batch, 0);
+    int n = 0, ng = 0;
+    for (int i = 0; i < batch; ++i) {
+        const int S = lens[i];
+        if (S < 1 || S > s->max_src || S > stride) return set_error(WLX_ERR_ARG, "item %d: source length %d outside 1..%d", i, S, std::min(s->max_src, stride));
+        s->src_off[i] = n;
+        s->src_len[i] = S;
+        int c = 0;
+        for (int j = 0; j < S; ++j) {
+            const int tok = src[(long)i * stride + j];
+            if (tok < 0 || tok >= sp.vocab) return set_error(WLX_ERR_ARG, "item %d: token %d outside the vocabulary", i, tok);
+            c += tok != sp.pad_id;
+            s->h_src_tok[n + j] = tok;
+            s->h_src_pos[n + j] = position_of(tok, c, 0, sp.pad_id);
+        }
+        for (int j = 0; j < S; j += 16) s->h_genc[ng++] = MtAttnGroup{n + j, std::min(16, S - j), n, S};
+        n += S;
+    }
+    s->n_items = batch;
+    s->n_src = n;
+    hipStream_t st = s->st;
+    MCK(hipEventRecord(s->ev[0], st));
+    MCK(hipMemcpyAsync(s->d_src_tok, s->h_src_tok, n * sizeof(int), hipMemcpyHostToDevice, st));
+    MCK(hipMemcpyAsync(s->d_src_pos, s->h_src_pos, n * sizeof(int), hipMemcpyHostToDevice, st));
+    MCK(hipMemcpyAsync(s->d_genc, s->h_genc, ng * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
+    launch_mt_embed(s->d_src_tok, s->d_src_pos, n, m->E, d / 32, m->embed_scale, m->sinpos, d, s->xe, st);
+    for (const MtLayer& w : m->enc) {
+        launch_layernorm_f16(s->xe, d, w.ln1_g, w.ln1_b, s->he, d, n, d, st);
+        gemm(s->he, d, n, w.Wqkv, d, 3 * d, w.bqkv, GEMM_STORE_F16, s->qkve, 3 * d, nullptr, 0, st);
+        launch_mt_attn(s->qkve, 3 * d, s->qkve + d, 3 * d, s->qkve + 2 * d, 3 * d, s->atte, d, s->d_genc, ng, 16, H, nullptr, 0, 0, st);
+        gemm(s->atte, d, n, w.Wo, d, d, w.bo, GEMM_RESID_F32, nullptr, 0, s->xe, d, st);
+        launch_layernorm_f16(s->xe, d, w.ln3_g, w.ln3_b, s->he, d, n, d, st);
+        gemm(s->he, d, n, w.W1, d, F, w.b1, GEMM_STORE_F16, s->ffe, F, nullptr, 0, st);
+        launch_mt_relu_f16(s->ffe, F, n, F, st);
+        gemm(s->ffe, F, n, w.W2, F, d, w.b2, GEMM_RESID_F32, nullptr, 0, s->xe, d, st);
+    }
+    launch_layernorm_f16_f32(s->xe, d, m->enc_ln_g, m->enc_ln_b, s->he, s->enc32, d, n, d, st);
+    gemm(s->he, d, n, m->Wckv, d, 2 * d * Ld, m->bckv, GEMM_STORE_F16, s->ckv, 2L * d * Ld, nullptr, 0, st);
+    MCK(hipGetLastError());
+    MCK(hipEventRecord(s->ev[1], st));
+    return WLX_OK;
+}
+
+// one decoder step for `rows` rows (R per item over the slot's encoded items) at position t: logits -> s->logits.
+// h_tok / h_pos / h_anc of the rows are set by the caller.
+int decode_step(wlx_mt* m, MtSlot* s, int rows, int R, int t) {
+    const wlx_mt_spec& sp = m->spec;
+    const int d = sp.d_model, F = sp.ffn, H = sp.n_heads, Ld = sp.dec_layers, T = s->tmax;
+    hipStream_t st = s->st;
+    for (int r = 0; r < rows; ++r) s->h_gself[r] = MtAttnGroup{r, 1, 0, t + 1};
+    for (int i = 0; i < s->n_items; ++i) s->h_gcross[i] = MtAttnGroup{i * R, R, s->src_off[i], s->src_len[i]};
+    MCK(hipMemcpyAsync(s->d_tok, s->h_tok, rows * sizeof(int), hipMemcpyHostToDevice, st));
+    MCK(hipMemcpyAsync(s->d_pos, s->h_pos, rows * sizeof(int), hipMemcpyHostToDevice, st));
+    MCK(hipMemcpyAsync(s->d_anc, s->h_anc, (size_t)rows * T * sizeof(int), hipMemcpyHostToDevice, st));
+    MCK(hipMemcpyAsync(s->d_gself, s->h_gself, rows * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
+    MCK(hipMemcpyAsync(s->d_gcross, s->h_gcross, s->n_items * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
+    launch_mt_embed(s->d_tok, s->d_pos, rows, m->E, d / 32, m->embed_scale, m->sinpos, d, s->xd, st);
+    const long cache_layer = (long)s->rows_cap * T * d;
+    for (int l = 0; l < Ld; ++l) {
+        const MtLayer& w = m->dec[l];
+        half_t* kc = s->kc + l * cache_layer;
+        half_t* vc = s->vc + l * cache_layer;
+        launch_layernorm_f16(s->xd, d, w.ln1_g, w.ln1_b, s->hd, d, rows, d, st);
+        gemm(s->hd, d, rows, w.Wqkv, d, 3 * d, w.bqkv, GEMM_STORE_F16, s->qkvd, 3 * d, nullptr, 0, st);
+        launch_mt_kv_append(s->qkvd, 3 * d, rows, d, kc, vc, T, t, st);
+        launch_mt_attn(s->qkvd, 3 * d, kc, d, vc, d, s->attd, d, s->d_gself, rows, 1, H, s->d_anc, T, T, st);
+        gemm(s->attd, d, rows, w.Wo, d, d, w.bo, GEMM_RESID_F32, nullptr, 0, s->xd, d, st);
+        launch_layernorm_f16(s->xd, d, w.ln2_g, w.ln2_b, s->hd, d, rows, d, st);
+        gemm(s->hd, d, rows, w.Wcq, d, d, w.bcq, GEMM_STORE_F16, s->qd, d, nullptr, 0, st);
+        const long ldkv = 2L * d * Ld;
+        launch_mt_attn(s->qd, d, s->ckv + 2L * d * l, ldkv, s->ckv + 2L * d * l + d, ldkv, s->attd, d, s->d_gcross, s->n_items, R, H,
+                       nullptr, 0, 0, st);
+        gemm(s->attd, d, rows, w.Wco, d, d, w.bco, GEMM_RESID_F32, nullptr, 0, s->xd, d, st);
+        launch_layernorm_f16(s->xd, d, w.ln3_g, w.ln3_b, s->hd, d, rows, d, st);
+        gemm(s->hd, d, rows, w.W1, d, F, w.b1, GEMM_STORE_F16, s->ffd, F, nullptr, 0, st);
+        launch_mt_relu_f16(s->ffd, F, rows, F, st);
+        gemm(s->ffd, F, rows, w.W2, F, d, w.b2, GEMM_RESID_F32, nullptr, 0, s->xd, d, st);
+    }
+    launch_layernorm_f16(s->xd, d, m->dec_ln_g, m->dec_ln_b, s->hd, d, rows, d, st);
+    MCK(hipMemsetAsync(s->logits, 0, (size_t)rows * sp.vocab * sizeof(float), st));
+    gemm(s->hd, d, rows, m->E, d, sp.vocab, nullptr, GEMM_RESID_F32, nullptr, 0, s->logits, sp.vocab, st);
+    MCK(hipGetLastError());
+    return WLX_OK;
+}
+
+// top-k candidates of the step's rows -> pinned host h_tk_val / h_tk_idx [rows][k]; waits for the stream
+int fetch_topk(wlx_mt* m, MtSlot* s, int rows, int k, bool with_bans) {
+    hipStream_t st = s->st;
+    if (with_bans) {
+        MCK(hipMemcpyAsync(s->d_nban, s->h_nban, rows * sizeof(int), hipMemcpyHostToDevice, st));
+        MCK(hipMemcpyAsync(s->d_ban, s->h_ban, (size_t)rows * s->ban_ld * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    launch_mt_topk(s->logits, rows, m->spec.vocab, with_bans ? s->d_ban : nullptr, with_bans ? s->d_nban : nullptr, s->ban_ld, k,
+                   s->tk_scratch, s->tk_cidx, s->tk_val, s->tk_idx, st);
+    MCK(hipGetLastError());
+    MCK(hipMemcpyAsync(s->h_tk_val, s->tk_val, (size_t)rows * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    MCK(hipMemcpyAsync(s->h_tk_idx, s->tk_idx, (size_t)rows * k * sizeof(int), hipMemcpyDeviceToHost, st));
+    MCK(hipStreamSynchronize(st));
+    return WLX_OK;
+}
+
+// banned next tokens of one hypothesis (HF NoRepeatNGramLogitsProcessor over the whole sequence incl. the decoder start)
+void banned_ngrams(const int* seq, int cur_len, int n, std::vector<int>& out) {
+    out.clear();
+    if (n <= 0 || cur_len + 1 < n) return;
+    const int start = cur_len + 1 - n;
+    for (int a = 0; a + n <= cur_len; ++a) {
+        bool eq = true;
+        for (int j = 0; j < n - 1 && eq; ++j) eq = seq[a + j] == seq[start + j];
+        if (eq) out.push_back(seq[a + n - 1]);
+    }
+}
+
+struct Cand { float v; int beam, tok; long flat; };
+
+int run_generate(wlx_mt* m, MtSlot* s, const wlx_mt_gen_opts& o, int32_t* tokens_out, int tokens_stride, int32_t* n_out,
+                 float* scores_out) {
+    const wlx_mt_spec& sp = m->spec;
+    const int B = s->n_items, R = o.num_beams, rows = B * R, T = s->tmax, ML = o.max_length, V = sp.vocab;
+    const int eos = sp.eos_id, pad = sp.pad_id;
+    const bool forced = o.forced_eos_token_id >= 0;
+    const int K = R == 1 ? 1 : 2 * R;
+    const int nng = o.no_repeat_ngram_size;
+    // sequences incl. the decoder start
+    std::vector<int> run(rows * ML, pad), fin(rows * ML, pad), fin_len(rows, 0);
+    std::vector<float> run_score(rows, 0.f), fin_score(rows, -1.0e9f);
+    std::vector<char> fin_done(rows, 0), unsat(B, 1), item_done(B, 0);
+    std::vector<float> greedy_score(B, 0.f);
+    for (int r = 0; r < rows; ++r) {
+        run[r * ML] = sp.decoder_start_id;
+        if (r % R) run_score[r] = -1.0e9f;
+    }
+    for (int r = 0; r < rows; ++r)
+        for (int j = 0; j < T; ++j) s->h_anc[(long)r * T + j] = r;
+    int cur_len = 1;
+    s->steps = 0;
+    MCK(hipEventRecord(s->ev[2], s->st));
+    std::vector<int> ban;
+    while (true) {
+        const int t = cur_len - 1;                 // position of the token fed in this step
+        const bool force_now = forced && cur_len == ML - 1;
+        if (!force_now) {
+            for (int r = 0; r < rows; ++r) {
+                s->h_tok[r] = run[r * ML + t];
+                s->h_anc[(long)r * T + t] = r;
+                s->h_pos[r] = position_of(run[r * ML + t], 1, t, pad);
+            }
+            MCKR(decode_step(m, s, rows, R, t));
+            bool any_ban = false;
+            for (int r = 0; r < rows; ++r) {
+                banned_ngrams(&run[r * ML], cur_len, nng, ban);
+                const int nb = std::min((int)ban.size(), s->ban_ld);
+                s->h_nban[r] = nb;
+                for (int j = 0; j < nb; ++j) s->h_ban[(long)r * s->ban_ld + j] = ban[j];
+                any_ban |= nb > 0;
+            }
+            MCKR(fetch_topk(m, s, rows, K, any_ban));
+            s->steps++;
+        }
+        if (R == 1) {   // greedy (HF _sample with do_sample = False)
+            bool all_done = true;
+            for (int b = 0; b < B; ++b) {
+                int tok;
+                float lp;
+                if (force_now) { tok = o.forced_eos_token_id; lp = 0.f; }
+                else { tok = s->h_tk_idx[b]; lp = s->h_tk_val[b]; }
+                if (item_done[b]) tok = pad;
+                else greedy_score[b] += lp;
+                run[b * ML + cur_len] = tok;
+                if (!item_done[b]) {
+                    fin_len[b] = cur_len + 1;
+                    if (tok == eos) item_done[b] = 1;
+                }
+                all_done &= item_done[b] != 0;
+            }
+            cur_len++;
+            if (all_done || cur_len >= ML) break;
+            continue;
+        }
+        // beam search, per item (HF _beam_search: _get_top_k_continuations, _get_running_beams_for_next_iteration,
+        // _update_finished_beams, _check_early_stop_heuristic)
+        const int K2 = 2 * R;
+        bool any_unsat = false, all_fin = true, all_hit = true;
+        std::vector<int> nrun(rows * ML), nanc((size_t)rows * T);
+        std::vector<float> nscore(rows);
+        for (int b = 0; b < B; ++b) {
+            std::vector<Cand> c;
+            c.reserve(R * K2);
+            for (int bb = 0; bb < R; ++bb) {
+                const int r = b * R + bb;
+                if (force_now) {
+                    c.push_back(Cand{0.f + run_score[r], bb, o.forced_eos_token_id, (long)bb * V + o.forced_eos_token_id});
+                    continue;
+                }
+                for (int k = 0; k < K2; ++k) {
+                    const int tok = s->h_tk_idx[r * K2 + k];
+                    if (tok < 0) continue;
+                    c.push_back(Cand{s->h_tk_val[r * K2 + k] + run_score[r], bb, tok, (long)bb * V + tok});
+                }
+            }
+            std::sort(c.begin(), c.end(), [](const Cand& a, const Cand& z) { return a.v > z.v || (a.v == z.v && a.flat < z.flat); });
+            if ((int)c.size() > K2) c.resize(K2);
+            const int nk = (int)c.size();
+            std::vector<char> hit(nk);
+            for (int k = 0; k < nk; ++k) {
+                hit[k] = c[k].tok == eos || cur_len + 1 >= ML;
+                all_hit &= hit[k] != 0;
+            }
+            // running beams of the next step
+            std::vector<int> order(nk);
+            std::vector<float> rv(nk);
+            for (int k = 0; k < nk; ++k) { order[k] = k; rv[k] = c[k].v + (hit[k] ? -1.0e9f : 0.f); }
+            std::stable_sort(order.begin(), order.end(), [&](int a, int z) { return rv[a] > rv[z]; });
+            for (int bb = 0; bb < R; ++bb) {
+                const int r = b * R + bb;
+                if (bb >= nk) { nscore[r] = -INFINITY; std::copy(&run[r * ML], &run[r * ML] + ML, &nrun[r * ML]); continue; }
+                const Cand& q = c[order[bb]];
+                const int src = b * R + q.beam;
+                std::copy(&run[src * ML], &run[src * ML] + ML, &nrun[r * ML]);
+                nrun[r * ML + cur_len] = q.tok;
+                nscore[r] = rv[order[bb]];
+                for (int j = 0; j <= t; ++j) nanc[(long)r * T + j] = s->h_anc[(long)src * T + j];
+            }
+            // finished beams
+            const float denom = (float)pow((double)cur_len, (double)o.length_penalty);
+            bool full = o.early_stopping == 1;
+            for (int bb = 0; bb < R; ++bb) full &= fin_done[b * R + bb] != 0;
+            std::vector<float> ms(R + nk);
+            std::vector<int> mseq((R + nk) * ML), mlen(R + nk);
+            std::vector<char> mfin(R + nk);
+            for (int bb = 0; bb < R; ++bb) {
+                const int r = b * R + bb;
+                ms[bb] = fin_score[r];
+                std::copy(&fin[r * ML], &fin[r * ML] + ML, &mseq[bb * ML]);
+                mlen[bb] = fin_len[r];
+                mfin[bb] = fin_done[r];
+            }
+            for (int k = 0; k < nk; ++k) {
+                const bool just = hit[k] && k < R;
+                float v = c[k].v / denom;
+                v += full ? -1.0e9f : 0.f;
+                v += unsat[b] ? 0.f : -1.0e9f;
+                v += just ? 0.f : -1.0e9f;
+                ms[R + k] = v;
+                const int src = b * R + c[k].beam;
+                std::copy(&run[src * ML], &run[src * ML] + ML, &mseq[(R + k) * ML]);
+                mseq[(R + k) * ML + cur_len] = c[k].tok;
+                mlen[R + k] = cur_len + 1;
+                mfin[R + k] = just;
+            }
+            std::vector<int> mo(R + nk);
+            for (int i = 0; i < R + nk; ++i) mo[i] = i;
+            std::stable_sort(mo.begin(), mo.end(), [&](int a, int z) { return ms[a] > ms[z]; });
+            for (int bb = 0; bb < R; ++bb) {
+                const int r = b * R + bb, i = mo[bb];
+                fin_score[r] = ms[i];
+                std::copy(&mseq[i * ML], &mseq[i * ML] + ML, &fin[r * ML]);
+                fin_len[r] = mlen[i];
+                fin_done[r] = mfin[i];
+            }
+        }
+        // the ancestry rows are gathered from the OLD table (a row may be the parent of a row written before it)
+        for (int r = 0; r < rows; ++r) std::copy(&nanc[(long)r * T], &nanc[(long)r * T] + t + 1, &s->h_anc[(long)r * T]);
+        run.swap(nrun);
+        cur_len++;
+        for (int b = 0; b < B; ++b) {
+            const float best_len = (o.early_stopping == 2 && o.length_penalty > 0.f) ? (float)(ML - 1) : (float)(cur_len - 1);
+            const float best = nscore[b * R] / (float)pow((double)best_len, (double)o.length_penalty);
+            float worst = INFINITY;
+            for (int bb = 0; bb < R; ++bb) worst = std::min(worst, fin_score[b * R + bb]);
+            bool anyb = false;
+            for (int bb = 0; bb < R; ++bb) anyb |= best > (fin_done[b * R + bb] ? worst : -1.0e9f);
+            unsat[b] = unsat[b] && anyb;
+            any_unsat |= unsat[b] != 0;
+            for (int bb = 0; bb < R; ++bb) all_fin &= fin_done[b * R + bb] != 0;
+        }
+        for (int r = 0; r < rows; ++r) run_score[r] = nscore[r];
+        const bool open = !(all_fin && o.early_stopping == 1);
+        if (!(any_unsat && open && !all_hit)) break;
+        if (cur_len >= ML) break;
+    }
+    MCK(hipEventRecord(s->ev[3], s->st));
+    // outputs: generated tokens after the decoder start, the final EOS excluded
+    for (int b = 0; b < B; ++b) {
+        const int* seq;
+        int len;
+        float score;
+        if (R == 1) { seq = &run[b * ML]; len = fin_len[b] ? fin_len[b] : cur_len; score = greedy_score[b]; }
+        else { seq = &fin[b * R * ML]; len = fin_len[b * R]; score = fin_score[b * R]; }
+        int n = std::max(0, len - 1);
+        if (n > 0 && seq[len - 1] == eos) n--;
+        n = std::min(n, tokens_stride);
+        for (int j = 0; j < n; ++j) tokens_out[(long)b * tokens_stride + j] = seq[1 + j];
+        n_out[b] = n;
+        if (scores_out) scores_out[b] = score;
+    }
+    return WLX_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ entry points
+extern "C" int32_t wlx_mt_create(const wlx_mt_spec* spec, const wlx_tensor* w, int32_t n, int32_t device, wlx_mt** out) {
+    if (!spec || !w || !out) return set_error(WLX_ERR_ARG, "null argument");
+    *out = nullptr;
+    const wlx_mt_spec sp = *spec;
+    if (sp.d_model <= 0 || sp.d_model % 64 || sp.d_model > 2048 || sp.n_heads * 64 != sp.d_model)
+        return set_error(WLX_ERR_ARG, "d_model %d / heads %d: head_dim must be 64 and d_model a multiple of 64 (<= 2048)", sp.d_model, sp.n_heads);
+    if (sp.ffn <= 0 || sp.ffn % 64) return set_error(WLX_ERR_ARG, "ffn %d must be a positive multiple of 64", sp.ffn);
+    if (sp.vocab <= 0 || sp.vocab % 16 || sp.vocab > WLX_MT_CHUNKS * 4096)
+        return set_error(WLX_ERR_ARG, "vocab %d must be a multiple of 16 and <= %d", sp.vocab, WLX_MT_CHUNKS * 4096);
+    if (sp.enc_layers < 1 || sp.dec_layers < 1 || sp.enc_layers > 64 || sp.dec_layers > 64) return set_error(WLX_ERR_ARG, "bad layer counts");
+    if (sp.max_positions < 1 || sp.pad_id < 0 || sp.eos_id < 0 || sp.decoder_start_id < 0 || sp.pad_id >= sp.vocab ||
+        sp.eos_id >= sp.vocab || sp.decoder_start_id >= sp.vocab)
+        return set_error(WLX_ERR_ARG, "bad special ids / max_positions");
+    MCK(hipSetDevice(device));
+    MCK((hipError_t)gemm_prepare_device());
+    wlx_mt* m = new wlx_mt();
+    m->spec = sp;
+    m->device = device;
+    m->embed_scale = sp.scale_embedding ? sqrtf((float)sp.d_model) : 1.f;
+    hipStream_t st = nullptr;
+    int rc = [&]() -> int {
+        MCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        Loader L{w, n, st};
+        const int d = sp.d_model, F = sp.ffn, KTd = d / 32, KTf = F / 32;
+        const float qs = 0.125f;     // head_dim ** -0.5, applied after the bias (folded into q_proj's weight and bias)
+        auto attn_ln = [&](const std::string& pre, float** g, float** b) -> int {
+            MCKR(vec(L, m->allocs, pre + ".weight", d, g));
+            return vec(L, m->allocs, pre + ".bias", d, b);
+        };
+        auto qkv = [&](const std::string& pre, MtLayer& y) -> int {
+            MCKR(dalloc(m->allocs, &y.Wqkv, (size_t)3 * d * d));
+            MCKR(pack(L, pre + ".q_proj.weight", d, d, y.Wqkv, KTd, 0, qs));
+            MCKR(pack(L, pre + ".k_proj.weight", d, d, y.Wqkv, KTd, d / 16));
+            MCKR(pack(L, pre + ".v_proj.weight", d, d, y.Wqkv, KTd, 2 * d / 16));
+            MCKR(dalloc(m->allocs, &y.bqkv, 3 * d));
+            MCKR(vec_into(L, pre + ".q_proj.bias", d, y.bqkv, qs));
+            MCKR(vec_into(L, pre + ".k_proj.bias", d, y.bqkv + d));
+            MCKR(vec_into(L, pre + ".v_proj.bias", d, y.bqkv + 2 * d));
+            MCKR(dalloc(m->allocs, &y.Wo, (size_t)d * d));
+            MCKR(pack(L, pre + ".out_proj.weight", d, d, y.Wo, KTd, 0));
+            return vec(L, m->allocs, pre + ".out_proj.bias", d, &y.bo);
+        };
+        auto mlp = [&](const std::string& pre, MtLayer& y) -> int {
+            MCKR(dalloc(m->allocs, &y.W1, (size_t)F * d));
+            MCKR(pack(L, pre + ".fc1.weight", F, d, y.W1, KTd, 0));
+            MCKR(vec(L, m->allocs, pre + ".fc1.bias", F, &y.b1));
+            MCKR(dalloc(m->allocs, &y.W2, (size_t)d * F));
+            MCKR(pack(L, pre + ".fc2.weight", d, F, y.W2, KTf, 0));
+            return vec(L, m->allocs, pre + ".fc2.bias", d, &y.b2);
+        };
+        const long NTv = sp.vocab / 16;
+        MCKR(dalloc(m->allocs, &m->E, (size_t)NTv * 16 * d));
+        MCKR(pack(L, "model.shared.weight", sp.vocab, d, m->E, KTd, 0));
+        m->enc.resize(sp.enc_layers);
+        for (int l = 0; l < sp.enc_layers; ++l) {
+            const std::string pre = "model.encoder.layers." + std::to_string(l);
+            MtLayer& y = m->enc[l];
+            MCKR(attn_ln(pre + ".self_attn_layer_norm", &y.ln1_g, &y.ln1_b));
+            MCKR(attn_ln(pre + ".final_layer_norm", &y.ln3_g, &y.ln3_b));
+            MCKR(qkv(pre + ".self_attn", y));
+            MCKR(mlp(pre, y));
+        }
+        MCKR(attn_ln("model.encoder.layer_norm", &m->enc_ln_g, &m->enc_ln_b));
+        const int Ld = sp.dec_layers;
+        MCKR(dalloc(m->allocs, &m->Wckv, (size_t)2 * Ld * d * d));
+        MCKR(dalloc(m->allocs, &m->bckv, (size_t)2 * Ld * d));
+        m->dec.resize(Ld);
+        for (int l = 0; l < Ld; ++l) {
+            const std::string pre = "model.decoder.layers." + std::to_string(l);
+            MtLayer& y = m->dec[l];
+            MCKR(attn_ln(pre + ".self_attn_layer_norm", &y.ln1_g, &y.ln1_b));
+            MCKR(attn_ln(pre + ".encoder_attn_layer_norm", &y.ln2_g, &y.ln2_b));
+            MCKR(attn_ln(pre + ".final_layer_norm", &y.ln3_g, &y.ln3_b));
+            MCKR(qkv(pre + ".self_attn", y));
+            MCKR(dalloc(m->allocs, &y.Wcq, (size_t)d * d));
+            MCKR(pack(L, pre + ".encoder_attn.q_proj.weight", d, d, y.Wcq, KTd, 0, qs));
+            MCKR(dalloc(m->allocs, &y.bcq, d));
+            MCKR(vec_into(L, pre + ".encoder_attn.q_proj.bias", d, y.bcq, qs));
+            MCKR(pack(L, pre + ".encoder_attn.k_proj.weight", d, d, m->Wckv, KTd, (2 * l) * d / 16));
+            MCKR(pack(L, pre + ".encoder_attn.v_proj.weight", d, d, m->Wckv, KTd, (2 * l + 1) * d / 16));
+            MCKR(vec_into(L, pre + ".encoder_attn.k_proj.bias", d, m->bckv + 2L * l * d));
+            MCKR(vec_into(L, pre + ".encoder_attn.v_proj.bias", d, m->bckv + (2L * l + 1) * d));
+            MCKR(dalloc(m->allocs, &y.Wco, (size_t)d * d));
+            MCKR(pack(L, pre + ".encoder_attn.out_proj.weight", d, d, y.Wco, KTd, 0));
+            MCKR(vec(L, m->allocs, pre + ".encoder_attn.out_proj.bias", d, &y.bco));
+            MCKR(mlp(pre, y));
+        }
+        MCKR(attn_ln("model.decoder.layer_norm", &m->dec_ln_g, &m->dec_ln_b));
+        // M2M100SinusoidalPositionalEmbedding.get_embedding, in fp32 as torch computes it
+        const int npos = sp.max_positions + 2, half = d / 2;
+        std::vector<float> sp_h((size_t)npos * d, 0.f);
+        const float neg = (float)(-(log(10000.0) / (half - 1)));
+        for (int p = 0; p < npos; ++p) {
+            if (p == sp.pad_id) continue;
+            for (int i = 0; i < half; ++i) {
+                const float a = (float)p * expf((float)i * neg);
+                sp_h[(size_t)p * d + i] = sinf(a);
+                sp_h[(size_t)p * d + half + i] = cosf(a);
+            }
+        }
+        MCKR(dalloc(m->allocs, &m->sinpos, sp_h.size()));
+        MCK(hipMemcpyAsync(m->sinpos, sp_h.data(), sp_h.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        MCK(hipStreamSynchronize(st));
+        return WLX_OK;
+    }();
+    if (st) (void)hipStreamDestroy(st);
+    if (rc != WLX_OK) {
+        for (void* p : m->allocs) (void)hipFree(p);
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return WLX_OK;
+}
+
+static void slot_free(MtSlot* s) {
+    if (s->st) (void)hipStreamSynchronize(s->st);
+    for (void* p : s->allocs) (void)hipFree(p);
+    for (void* p : s->host_allocs) (void)hipHostFree(p);
+    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    if (s->st) (void)hipStreamDestroy(s->st);
+    delete s;
+}
+
+extern "C" void wlx_mt_destroy(wlx_mt* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    for (auto& kv : m->slots) slot_free(kv.second);
+    for (void* p : m->allocs) (void)hipFree(p);
+    delete m;
+}
+
+extern "C" int32_t wlx_mt_slot_create(wlx_mt* m, int32_t max_batch, int32_t max_rows_per_item, int32_t max_src, int32_t* slot_out) {
+    if (!m || !slot_out) return set_error(WLX_ERR_ARG, "null argument");
+    const wlx_mt_spec& sp = m->spec;
+    if (max_batch < 1 || max_batch > 64) return set_error(WLX_ERR_ARG, "max_batch %d outside 1..64", max_batch);
+    if (max_rows_per_item < 1 || max_rows_per_item > 16) return set_error(WLX_ERR_ARG, "max_rows_per_item %d outside 1..16", max_rows_per_item);
+    if (max_src < 1 || max_src > WLX_MT_MAX_SRC || max_src > sp.max_positions)
+        return set_error(WLX_ERR_ARG, "max_src %d outside 1..%d", max_src, std::min(WLX_MT_MAX_SRC, sp.max_positions));
+    MCK(hipSetDevice(m->device));
+    const int d = sp.d_model, F = sp.ffn, Ld = sp.dec_layers, B = max_batch, R = max_rows_per_item, T = WLX_T_TEXT;
+    const long rows = (long)B * R, src = (long)B * max_src;
+    const int ban_ld = T;
+    const double bytes = (double)src * (d * (4.0 + 4.0 + 2 + 6 + 2) + F * 2.0 + 4.0 * d * Ld) +
+                         (double)rows * (d * (4.0 + 2 + 6 + 2 + 2) + F * 2.0 + sp.vocab * 4.0 + 4.0 * Ld * T * d + T * 4.0 + ban_ld * 4.0) +
+                         (double)rows * WLX_MT_CHUNKS * WLX_MT_MAXK * 12.0;
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            if (bytes > (double)free_b)
+                return set_error(WLX_ERR_NOMEM, "a translation slot of %d items x %d rows x %d source tokens needs ~%.2f GB of device memory; %.2f GB are free on device %d",
+                                 B, R, max_src, bytes / 1e9, free_b / 1e9, m->device);
+        } else (void)hipGetLastError();
+    }
+    MtSlot* s = new MtSlot();
+    s->B = B; s->R = R; s->max_src = max_src; s->rows_cap = (int)rows; s->src_cap = (int)src; s->ban_ld = ban_ld;
+    int rc = [&]() -> int {
+        MCK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+        for (auto& e : s->ev) MCK(hipEventCreate(&e));
+        auto& A = s->allocs;
+        MCKR(dalloc(A, &s->xe, src * d));
+        MCKR(dalloc(A, &s->enc32, src * d));
+        MCKR(dalloc(A, &s->he, src * d));
+        MCKR(dalloc(A, &s->qkve, src * 3 * d));
+        MCKR(dalloc(A, &s->atte, src * d));
+        MCKR(dalloc(A, &s->ffe, src * F));
+        MCKR(dalloc(A, &s->ckv, src * 2 * d * Ld));
+        MCKR(dalloc(A, &s->xd, rows * d));
+        MCKR(dalloc(A, &s->hd, rows * d));
+        MCKR(dalloc(A, &s->qkvd, rows * 3 * d));
+        MCKR(dalloc(A, &s->qd, rows * d));
+        MCKR(dalloc(A, &s->attd, rows * d));
+        MCKR(dalloc(A, &s->ffd, rows * F));
+        MCKR(dalloc(A, &s->kc, (size_t)Ld * rows * T * d));
+        MCKR(dalloc(A, &s->vc, (size_t)Ld * rows * T * d));
+        MCKR(dalloc(A, &s->logits, rows * sp.vocab));
+        MCKR(dalloc(A, &s->tk_scratch, rows * WLX_MT_CHUNKS * (2 + WLX_MT_MAXK)));
+        MCKR(dalloc(A, &s->tk_cidx, rows * WLX_MT_CHUNKS * WLX_MT_MAXK));
+        MCKR(dalloc(A, &s->tk_val, rows * WLX_MT_MAXK));
+        MCKR(dalloc(A, &s->tk_idx, rows * WLX_MT_MAXK));
+        MCKR(dalloc(A, &s->d_tok, rows));
+        MCKR(dalloc(A, &s->d_pos, rows));
+        MCKR(dalloc(A, &s->d_src_tok, src));
+        MCKR(dalloc(A, &s->d_src_pos, src));
+        MCKR(dalloc(A, &s->d_anc, rows * T));
+        MCKR(dalloc(A, &s->d_ban, rows * ban_ld));
+        MCKR(dalloc(A, &s->d_nban, rows));
+        MCKR(dalloc(A, &s->d_genc, src));
+        MCKR(dalloc(A, &s->d_gself, rows));
+        MCKR(dalloc(A, &s->d_gcross, B));
+        auto& H = s->host_allocs;
+        MCKR(halloc(H, &s->h_tok, rows));
+        MCKR(halloc(H, &s->h_pos, rows));
+        MCKR(halloc(H, &s->h_src_tok, src));
+        MCKR(halloc(H, &s->h_src_pos, src));
+        MCKR(halloc(H, &s->h_anc, rows * T));
+        MCKR(halloc(H, &s->h_ban, rows * ban_ld));
+        MCKR(halloc(H, &s->h_nban, rows));
+        MCKR(halloc(H, &s->h_tk_idx, rows * WLX_MT_MAXK));
+        MCKR(halloc(H, &s->h_tk_val, rows * WLX_MT_MAXK));
+        MCKR(halloc(H, &s->h_genc, src));
+        MCKR(halloc(H, &s->h_gself, rows));
+        MCKR(halloc(H, &s->h_gcross, B));
+        return WLX_OK;
+    }();
+    if (rc != WLX_OK) {
+        slot_free(s);
+        return rc;
+    }
+    std::lock_guard<std::mutex> g(m->mu);
+    const int id = m->next_slot++;
+    m->slots[id] = s;
+    *slot_out = id;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_mt_slot_destroy(wlx_mt* m, int32_t slot) {
+    if (!m) return set_error(WLX_ERR_ARG, "null engine");
+    MtSlot* s = nullptr;
+    {
+        std::lock_guard<std::mutex> g(m->mu);
+        auto it = m->slots.find(slot);
+        if (it == m->slots.end()) return set_error(WLX_ERR_ARG, "no translation slot %d", slot);
+        s = it->second;
+        bool f = false;
+        if (!s->busy.compare_exchange_strong(f, true)) return set_error(WLX_ERR_STATE, "translation slot %d is busy", slot);
+        m->slots.erase(it);
+    }
+    (void)hipSetDevice(m->device);
+    slot_free(s);
+    return WLX_OK;
+}
+
+static int check_opts(const wlx_mt* m, const MtSlot* s, const wlx_mt_gen_opts* o) {
+    if (!o) return set_error(WLX_ERR_ARG, "null options");
+    if (o->num_beams < 1 || o->num_beams > s->R) return set_error(WLX_ERR_ARG, "num_beams %d outside 1..%d (slot max_rows_per_item)", o->num_beams, s->R);
+    if (2 * o->num_beams > WLX_MT_MAXK && o->num_beams > 1) return set_error(WLX_ERR_ARG, "num_beams %d > %d", o->num_beams, WLX_MT_MAXK / 2);
+    const int ml_cap = std::min(WLX_T_TEXT, m->spec.max_positions);
+    if (o->max_length < 2 || o->max_length > ml_cap) return set_error(WLX_ERR_ARG, "max_length %d outside 2..%d", o->max_length, ml_cap);
+    if (o->early_stopping < 0 || o->early_stopping > 2) return set_error(WLX_ERR_ARG, "early_stopping must be 0 (False), 1 (True) or 2 (never)");
+    if (o->no_repeat_ngram_size < 0) return set_error(WLX_ERR_ARG, "no_repeat_ngram_size < 0");
+    if (o->forced_eos_token_id >= m->spec.vocab) return set_error(WLX_ERR_ARG, "forced_eos_token_id outside the vocabulary");
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_mt_translate(wlx_mt* m, int32_t slot, int32_t batch, const int32_t* src_ids, const int32_t* src_lens,
+                                    int32_t src_stride, const wlx_mt_gen_opts* opts, int32_t* tokens_out, int32_t tokens_stride,
+                                    int32_t* n_tokens_out, float* scores_out) {
+    if (!m || !tokens_out || !n_tokens_out || tokens_stride < 1) return set_error(WLX_ERR_ARG, "null argument");
+    MtSlot* s = slot_of(m, slot);
+    if (!s) return set_error(WLX_ERR_ARG, "no translation slot %d", slot);
+    Busy busy(s);
+    if (!busy.ok) return set_error(WLX_ERR_STATE, "translation slot %d is busy (a call is in flight)", slot);
+    MCKR(check_opts(m, s, opts));
+    MCK(hipSetDevice(m->device));
+    MCKR(encode(m, s, batch, src_ids, src_lens, src_stride));
+    MCKR(run_generate(m, s, *opts, tokens_out, tokens_stride, n_tokens_out, scores_out));
+    MCK(hipStreamSynchronize(s->st));
+    float a = 0.f, b = 0.f;
+    if (hipEventElapsedTime(&a, s->ev[0], s->ev[1]) == hipSuccess) s->enc_ms = a;
+    if (hipEventElapsedTime(&b, s->ev[2], s->ev[3]) == hipSuccess) s->dec_ms = b;
+    (void)hipGetLastError();
+    return WLX_OK;
+}
+
+// ---- test / profiling hooks
+extern "C" int32_t wlx_mt_debug_encode(wlx_mt* m, int32_t slot, int32_t batch, const int32_t* src_ids, const int32_t* src_lens,
+                                       int32_t src_stride, float* out, int64_t cap_floats) {
+    if (!m || !out) return set_error(WLX_ERR_ARG, "null argument");
+    MtSlot* s = slot_of(m, slot);
+    if (!s) return set_error(WLX_ERR_ARG, "no translation slot %d", slot);
+    Busy busy(s);
+    if (!busy.ok) return set_error(WLX_ERR_STATE, "translation slot %d is busy", slot);
+    MCK(hipSetDevice(m->device));
+    MCKR(encode(m, s, batch, src_ids, src_lens, src_stride));
+    const long need = (long)s->n_src * m->spec.d_model;
+    if (cap_floats < need) return set_error(WLX_ERR_ARG, "output holds %lld floats, %ld needed", (long long)cap_floats, need);
+    MCK(hipMemcpyAsync(out, s->enc32, need * sizeof(float), hipMemcpyDeviceToHost, s->st));
+    MCK(hipStreamSynchronize(s->st));
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_mt_debug_decode_logits(wlx_mt* m, int32_t slot, const int32_t* src_ids, int32_t src_len,
+                                              const int32_t* dec_tokens, int32_t n, float* out) {
+    if (!m || !out || !dec_tokens) return set_error(WLX_ERR_ARG, "null argument");
+    MtSlot* s = slot_of(m, slot);
+    if (!s) return set_error(WLX_ERR_ARG, "no translation slot %d", slot);
+    Busy busy(s);
+    if (!busy.ok) return set_error(WLX_ERR_STATE, "translation slot %d is busy", slot);
+    if (n < 1 || n > s->tmax) return set_error(WLX_ERR_ARG, "n %d outside 1..%d", n, s->tmax);
+    MCK(hipSetDevice(m->device));
+    MCKR(encode(m, s, 1, src_ids, &src_len, src_len));
+    const int V = m->spec.vocab;
+    int c = 0;
+    for (int j = 0; j < s->tmax; ++j) s->h_anc[j] = 0;
+    for (int t = 0; t < n; ++t) {
+        const int tok = dec_tokens[t];
+        if (tok < 0 || tok >= V) return set_error(WLX_ERR_ARG, "token %d outside the vocabulary", tok);
+        c += tok != m->spec.pad_id;
+        s->h_tok[0] = tok;
+        s->h_pos[0] = position_of(tok, c, 0, m->spec.pad_id);
+        MCKR(decode_step(m, s, 1, 1, t));
+        MCK(hipMemcpyAsync(out + (long)t * V, s->logits, V * sizeof(float), hipMemcpyDeviceToHost, s->st));
+        MCK(hipStreamSynchronize(s->st));     // (h_tok / h_pos are rewritten by the next step)
+    }
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_mt_debug_timings(wlx_mt* m, int32_t slot, float* encode_ms, float* decode_ms, int32_t* steps) {
+    if (!m) return set_error(WLX_ERR_ARG, "null engine");
+    MtSlot* s = slot_of(m, slot);
+    if (!s) return set_error(WLX_ERR_ARG, "no translation slot %d", slot);
+    if (encode_ms) *encode_ms = s->enc_ms;
+    if (decode_ms) *decode_ms = s->dec_ms;
+    if (steps) *steps = s->steps;
+    return WLX_OK;
+}

@@ -17,9 +17,13 @@ What differs, on purpose:
     the reference's own WARNING message (server.py:253-258, 282-286), since neither stack exists on this hardware;
   * GPUs: ``devices=[...]`` shards connections over GPUs, connection i -> ``devices[i mod n]`` (sharding.assign_gpu;
     SURVEY.md §8e) — one engine + slot pool per GPU, no cross-GPU traffic;
-  * translation, diarization and the OpenAI-style REST endpoint are separate products around the path (their own
-    models / HTTP stack) and are not provided: the options are accepted and ignored with a log line, ``enable_rest``
-    raises;
+  * translation (``enable_translation`` / ``target_language``) runs on the HIP M2M100 engine (whisperlive_amd/translation.py):
+    when a small100 checkpoint resolves (artifacts.resolve_translation_model: a directory, $WLX_MODEL_ROOT, the Hugging Face
+    cache), each translating client gets the reference's queue + ``ServeClientTranslation`` + daemon thread (server.py:203-229)
+    and receives ``translated_segments`` messages; no ``transformers`` model is loaded. Without a checkpoint the option is
+    ignored with a log line, as before;
+  * diarization and the OpenAI-style REST endpoint are separate products around the path (their own models / HTTP stack) and
+    are not provided: the options are accepted and ignored with a log line, ``enable_rest`` raises;
   * ``use_vad`` is kept per connection (the reference stores it on the server object, server.py:394, so two clients
     with different settings race).
 """
@@ -49,6 +53,19 @@ MAX_SLOT_BATCH = 64         # clips one engine slot encodes and decodes together
 
 END_OF_AUDIO = b"END_OF_AUDIO"      # whisper_live/server.py:376, client.py:23
 AUDIO_FORMATS = ("float32", "int16", "uint8")
+
+
+def _attach_translation_cleanup(client):
+    """the client's cleanup also stops its translation thread (exit flag + None on the queue) and joins it"""
+    inner = client.cleanup
+
+    def cleanup(*a, **k):
+        try:
+            return inner(*a, **k)
+        finally:
+            client.translation_client.cleanup()
+            client.translation_thread.join(timeout=5.0)
+    client.cleanup = cleanup
 
 
 def _websocket_auth(api_key, connection, request):
@@ -173,10 +190,16 @@ class TranscriptionServer:
             self._n_connections += 1
         return self.devices[assign_gpu(i, len(self.devices))]
 
+    translation_model = os.environ.get("WLX_TRANSLATION_MODEL", "alirezamsh/small100")   # a directory or a hub id
+
     def initialize_client(self, websocket, options, faster_whisper_custom_model_path, whisper_tensorrt_path,
                           trt_multilingual, trt_py_session=False):
+        translation_dir = None
         if options.get("enable_translation", False):
-            logging.warning("enable_translation: the translation side-channel is not part of this server; ignored")
+            from .artifacts import resolve_translation_model
+            translation_dir = resolve_translation_model(self.translation_model)
+            if translation_dir is None:
+                logging.warning("enable_translation: the translation side-channel is not part of this server; ignored")
         if options.get("enable_diarization", False):
             logging.warning("enable_diarization: speaker diarization is not part of this server; disabled")
 
@@ -194,6 +217,22 @@ class TranscriptionServer:
                 logging.info(f"Using custom model {faster_whisper_custom_model_path}")
                 options["model"] = faster_whisper_custom_model_path
             device_index = self._next_device()
+            translation_queue = translation_client = translation_thread = None
+            if translation_dir is not None:
+                # server.py:203-229 of the reference: a bounded queue the transcription client fills with its segments, the
+                # translation client and its daemon thread (the model itself is shared per GPU and loaded on first use)
+                import queue as _queue
+                from .translation import ServeClientTranslation
+                translation_queue = _queue.Queue(maxsize=ServeClientBase.MAX_TRANSLATION_QUEUE_SIZE)
+                translation_client = ServeClientTranslation(
+                    client_uid=options["uid"], websocket=websocket, translation_queue=translation_queue,
+                    target_language=options.get("target_language", "fr"),
+                    send_last_n_segments=options.get("send_last_n_segments", 10), model_name=translation_dir,
+                    device=device_index)
+                translation_thread = threading.Thread(target=translation_client.speech_to_text, daemon=True)
+                translation_thread.start()
+                logging.info(f"Translation enabled for client {options['uid']} with target language: "
+                             f"{translation_client.target_language}")
             use_vad = bool(options.get("use_vad"))
             if use_vad and self.model_factory is None:
                 # the gate must be the reference's detector or nothing: without Silero weights the client is told and
@@ -225,8 +264,14 @@ class TranscriptionServer:
                 device_index=device_index,
                 model_factory=self.model_factory,
                 max_batch=self.batch_config["max_batch_size"] if self.batch_config is not None else 1,
+                translation_queue=translation_queue,
             )
+            if translation_client is not None:
+                client.translation_client, client.translation_thread = translation_client, translation_thread
+                _attach_translation_cleanup(client)
             if not hasattr(client, "transcriber"):          # model load failed: ERROR already sent, socket closed
+                if translation_client is not None:
+                    client.cleanup()
                 return
             logging.info(f"Running HIP backend on GPU {device_index}.")
             # one batch worker per GPU, started once that GPU's shared transcriber exists (server.py:334-344)
