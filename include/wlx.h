@@ -358,6 +358,22 @@ int32_t wlx_mt_debug_decode_logits(wlx_mt* mt, int32_t slot, const int32_t* src_
                                    int32_t n, float* out);
 /* translation engine: device times (HIP events) of the slot's last wlx_mt_translate: encoder pass, decode loop, decode steps */
 int32_t wlx_mt_debug_timings(wlx_mt* mt, int32_t slot, float* encode_ms, float* decode_ms, int32_t* steps);
+/* translation engine kernels, one launch each on host arrays (fp16 as uint16 bits), on a private stream of `device`; every
+ * shape the launcher cannot serve fails with WLX_ERR_ARG before any launch.
+ * Attention: groups [n_groups][4] = (q0, nq, k0, nk), head h at columns 64 h of Q / K / V / O (strides ldq / ldk / ldv / ldo);
+ * 1 <= nq <= max_nq <= 16. With `anc` (rows (max q0 + 1) x ld_anc, nk <= min(ld_anc, tmax)) key j of a group is row
+ * anc[q0 * ld_anc + j] * tmax + j of K / V, else row k0 + j. O is copied in and out: rows no group owns come back unchanged. */
+int32_t wlx_mt_debug_attn(int32_t device, const uint16_t* q, int64_t ldq, int64_t q_rows, const uint16_t* k, int64_t ldk,
+                          const uint16_t* v, int64_t ldv, int64_t kv_rows, const int32_t* groups, int32_t n_groups, int32_t max_nq,
+                          int32_t heads, const int32_t* anc, int32_t ld_anc, int32_t tmax, uint16_t* o, int64_t ldo, int64_t o_rows);
+/* log-softmax + top-k over float32 logits [rows][vocab] (vocab a multiple of 16, <= 262144; 1 <= k <= 32), optional bans
+ * ban[r][0 .. nban[r]) (row stride ban_ld; nban may be null): out_val / out_idx [rows][k], -inf / -1 past the eligible tokens */
+int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_t rows, int32_t vocab, const int32_t* ban, const int32_t* nban,
+                          int32_t ban_ld, int32_t k, float* out_val, int32_t* out_idx);
+/* token embedding: E float32 [vocab][d] (d a multiple of 32) packed as the engine packs it, x[r] = scale * E[tok[r]] +
+ * sinpos[pos[r]] with sinpos float32 [n_pos][d]; x float32 [rows][d] */
+int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vocab, int32_t d, const int32_t* tok, const int32_t* pos,
+                           int32_t rows, float scale, const float* sinpos, int32_t n_pos, float* x);
 
 #ifdef __cplusplus
 }

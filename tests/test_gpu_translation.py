@@ -57,7 +57,7 @@ def fix():
 def full():
     from whisperlive_amd.translation import HipMTEngine
     w = random_mt_weights(FULL, seed=3, peaked=True)
-    eng = HipMTEngine(FULL, w, device=0, max_batch=2, max_rows=5, max_src=64)
+    eng = HipMTEngine(FULL, w, device=0, max_batch=2, max_rows=5, max_src=1024)
     yield eng, M2M100Oracle(FULL, w, fp16_matrices=True)
     eng.close()
 
@@ -137,16 +137,18 @@ def test_source_of_max_src_tokens(fix):
         eng.translate_ids([src + [5]], o)
 
 
-def _near_tie(orc, src, a, b, o):
-    """the two hypotheses score within 2e-3 under the restatement's own forced decoding"""
-    enc = orc.encode(src)
+def _forced_score(orc, src, seq, o, eos=True):
+    """HF's beam score of `seq` (generated tokens, without the decoder start; with the final EOS unless the hypothesis ran to
+    max_length) under the restatement's own forced decoding"""
+    full = [orc.spec.decoder_start_id] + list(seq) + ([orc.spec.eos_id] if eos else [])
+    lp = orc.decode_logits(orc.encode(src), full[:-1]).log_softmax(-1)
+    s = float(sum(lp[i, full[i + 1]] for i in range(len(full) - 1)))
+    return s / (len(full) - 1) ** o.length_penalty
 
-    def score(seq):
-        full = [orc.spec.decoder_start_id] + seq + [orc.spec.eos_id]
-        lp = orc.decode_logits(enc, full[:-1]).log_softmax(-1)
-        s = float(sum(lp[i, full[i + 1]] for i in range(len(full) - 1)))
-        return s / (len(full) - 1) ** o.length_penalty
-    return abs(score(a) - score(b)) <= 2e-3
+
+def _near_tie(orc, src, a, b, o, eos=True):
+    """the two hypotheses score within 2e-3 under the restatement's own forced decoding"""
+    return abs(_forced_score(orc, src, a, o, eos) - _forced_score(orc, src, b, o, eos)) <= 2e-3
 
 
 def test_full_dims_translate_against_oracle(full):
@@ -263,3 +265,78 @@ def test_server_client_receives_translated_segments(tmp_path, fix):
         server.cleanup(ws)
         srv.ServeClientHIP.MODELS.pop((0, "mt-server-test"), None)
     assert not client.translation_thread.is_alive()
+
+
+# ------------------------------------------------------------------ the regime small100 runs in: long beam decodes, 16 beams,
+# 448-token KV caches, 1024-token sources
+@pytest.fixture(scope="module")
+def long_fix():
+    """the fixture's dimensions with the EOS row of the tied embedding at zero, on a 16-row slot: the EOS logit is 0 at every
+    step, far below the top 2 x num_beams of 2112 logits of unit spread, so no beam finishes before max_length. (A large
+    negative eos_margin of random_mt_weights(peaked=True) does not do it: the direction it adds meets the decoder's hidden state
+    with either sign, and at the first steps it lifts EOS above everything.)"""
+    from whisperlive_amd.translation import HipMTEngine
+    w = random_mt_weights(FIX, seed=GOLD["seed"])
+    w["model.shared.weight"][FIX.eos_id] = 0.0
+    eng = HipMTEngine(FIX, w, device=0, max_batch=1, max_rows=16, max_src=128)
+    yield eng, M2M100Oracle(FIX, w, fp16_matrices=True)
+    eng.close()
+
+
+def _beam_against_oracle(eng, orc, srcs, o, n_expect=None):
+    toks, scores = eng.translate_ids(srcs, o)
+    ref, ref_scores = orc.generate(srcs, o)
+    for i, src in enumerate(srcs):
+        if n_expect is not None:
+            assert len(toks[i]) == n_expect and len(ref[i]) == n_expect, (i, len(toks[i]), len(ref[i]))
+        ended = n_expect is None
+        # tie-independent: the engine's score is that of its own hypothesis (a wrong ancestry gather scores another history)
+        fs = _forced_score(orc, src, toks[i], o, eos=ended)
+        assert abs(scores[i] - fs) <= 2e-3 * max(1.0, abs(fs)), (i, scores[i], fs)
+        if toks[i] != ref[i]:
+            assert _near_tie(orc, src, toks[i], ref[i], o, eos=ended), (i, toks[i], ref[i])
+        else:
+            assert abs(scores[i] - ref_scores[i]) <= 2e-3 * max(1.0, abs(ref_scores[i])), (i, scores[i], ref_scores[i])
+
+
+def test_beam_decode_to_max_length_200(long_fix):
+    """5 beams to max_length 200 (small100's generation config): the decoder self-attention crosses four key tiles through
+    the ancestry table; every hypothesis runs to max_length (199 tokens, EOS pushed down)"""
+    eng, orc = long_fix
+    srcs = [GOLD["sources"][1]]
+    _beam_against_oracle(eng, orc, srcs, MTGenOptions(num_beams=5, max_length=200, early_stopping=True), n_expect=199)
+
+
+def test_sixteen_beams(long_fix):
+    """num_beams 16: 32 candidates per row (top-k at its limit) and 16-row cross-attention groups (the four-wave kernel)"""
+    eng, orc = long_fix
+    srcs = [GOLD["sources"][3]]
+    _beam_against_oracle(eng, orc, srcs, MTGenOptions(num_beams=16, max_length=40, early_stopping=True), n_expect=39)
+
+
+def test_teacher_forced_logits_448_tokens(fix):
+    """the whole KV cache: 448 decoder tokens (WLX_T_TEXT), seven key tiles of the self-attention"""
+    eng, w = fix
+    orc = M2M100Oracle(FIX, w, fp16_matrices=True)
+    rng = np.random.default_rng(13)
+    src = GOLD["sources"][2]
+    dec = [FIX.decoder_start_id] + [int(x) for x in rng.integers(3, FIX.vocab, size=447)]
+    got = eng.decoder_logits(src, dec)
+    ref = orc.decode_logits(orc.encode(src), dec).numpy()
+    assert got.shape == ref.shape == (448, FIX.vocab)
+    assert rel_rms(got, ref) <= 2e-3
+    assert rel_rms(got[384:], ref[384:]) <= 2e-3          # the last tile on its own
+
+
+def test_full_dims_source_of_1024_tokens(full):
+    """a 1024-token source (WLX_MT_MAX_SRC) at small100 dimensions: 16 key tiles in the encoder and the cross-attention"""
+    eng, orc = full
+    rng = np.random.default_rng(17)
+    src = [128000] + [int(x) for x in rng.integers(4, 128000, size=1022)] + [2]
+    assert len(src) == 1024
+    got = eng.encoder_output([src])
+    assert rel_rms(got, orc.encode(src).numpy()) <= 2e-3
+    o = MTGenOptions(num_beams=1, max_length=8)
+    toks, _ = eng.translate_ids([src], o)
+    ref, _ = orc.generate([src], o)
+    assert toks[0] == ref[0]

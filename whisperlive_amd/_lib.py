@@ -22,7 +22,8 @@ EXPORTS = [
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
-    "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings",
+    "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
+    "wlx_mt_debug_embed",
 ]
 
 
@@ -258,6 +259,10 @@ def load() -> C.CDLL:
     lib.wlx_mt_debug_encode.argtypes = [vp, i32, i32, i32p, i32p, i32, f32p, i64]
     lib.wlx_mt_debug_decode_logits.argtypes = [vp, i32, i32p, i32, i32p, i32, f32p]
     lib.wlx_mt_debug_timings.argtypes = [vp, i32, f32p, f32p, i32p]
+    u16p = C.POINTER(C.c_uint16)
+    lib.wlx_mt_debug_attn.argtypes = [i32, u16p, i64, i64, u16p, i64, u16p, i64, i64, i32p, i32, i32, i32, i32p, i32, i32, u16p, i64, i64]
+    lib.wlx_mt_debug_topk.argtypes = [i32, f32p, i32, i32, i32p, i32p, i32, i32, f32p, i32p]
+    lib.wlx_mt_debug_embed.argtypes = [i32, f32p, i32, i32, i32p, i32p, i32, C.c_float, f32p, i32, f32p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_mt_destroy"):

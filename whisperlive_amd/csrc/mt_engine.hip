@@ -827,3 +827,150 @@ extern "C" int32_t wlx_mt_debug_timings(wlx_mt* m, int32_t slot, float* encode_m
     if (steps) *steps = s->steps;
     return WLX_OK;
 }
+
+// ---- kernel-level test hooks: host arrays in, the production launcher unchanged on a private stream, host arrays out.
+// Every shape a launcher cannot serve is refused (WLX_ERR_ARG) before anything is allocated or launched.
+namespace {
+
+// device buffers and the stream of one hook call, released on every return path
+struct HookScope {
+    std::vector<void*> allocs;
+    hipStream_t st = nullptr;
+    ~HookScope() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (void* p : allocs) (void)hipFree(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    int begin(int device) {
+        int n = 0;
+        MCK(hipGetDeviceCount(&n));
+        if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
+        MCK(hipSetDevice(device));
+        MCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        return WLX_OK;
+    }
+    template <class T>
+    int upload(T** d, const T* h, size_t n) {
+        MCKR(dalloc(allocs, d, n));
+        if (h && n) MCK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+        return WLX_OK;
+    }
+    template <class T>
+    int download(T* h, const T* d, size_t n) {
+        MCK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st));
+        return WLX_OK;
+    }
+    int finish() {
+        MCK(hipGetLastError());
+        MCK(hipStreamSynchronize(st));
+        return WLX_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" int32_t wlx_mt_debug_attn(int32_t device, const uint16_t* q, int64_t ldq, int64_t q_rows, const uint16_t* k, int64_t ldk,
+                                     const uint16_t* v, int64_t ldv, int64_t kv_rows, const int32_t* groups, int32_t n_groups,
+                                     int32_t max_nq, int32_t heads, const int32_t* anc, int32_t ld_anc, int32_t tmax, uint16_t* o,
+                                     int64_t ldo, int64_t o_rows) {
+    if (!q || !k || !v || !o || !groups) return set_error(WLX_ERR_ARG, "null argument");
+    if (n_groups < 1 || heads < 1 || heads > 65535) return set_error(WLX_ERR_ARG, "n_groups %d / heads %d", n_groups, heads);
+    if (max_nq < 1 || max_nq > 16) return set_error(WLX_ERR_ARG, "max_nq %d outside 1..16", max_nq);   // (4 waves x 4 rows)
+    const int64_t w = 64L * heads;
+    if (ldq < w || ldk < w || ldv < w || ldo < w || ldk % 8 || ldv % 8)
+        return set_error(WLX_ERR_ARG, "row strides must cover heads * 64 columns (K / V strides: multiples of 8)");
+    if (q_rows < 1 || kv_rows < 1 || o_rows < 1) return set_error(WLX_ERR_ARG, "empty Q / K / V / O");
+    if (anc && (tmax < 1 || ld_anc < 1)) return set_error(WLX_ERR_ARG, "ancestry table with tmax %d / ld_anc %d", tmax, ld_anc);
+    int64_t anc_rows = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const int32_t q0 = groups[4 * g], nq = groups[4 * g + 1], k0 = groups[4 * g + 2], nk = groups[4 * g + 3];
+        if (nq < 1 || nq > max_nq) return set_error(WLX_ERR_ARG, "group %d: nq %d outside 1..max_nq %d", g, nq, max_nq);
+        if (q0 < 0 || (int64_t)q0 + nq > q_rows || (int64_t)q0 + nq > o_rows) return set_error(WLX_ERR_ARG, "group %d: query rows outside Q / O", g);
+        if (nk < 1) return set_error(WLX_ERR_ARG, "group %d: nk %d < 1", g, nk);
+        if (!anc) {
+            if (k0 < 0 || (int64_t)k0 + nk > kv_rows) return set_error(WLX_ERR_ARG, "group %d: key rows [%d, %lld) outside K / V", g, k0, (long long)k0 + nk);
+            continue;
+        }
+        if (nk > ld_anc || nk > tmax) return set_error(WLX_ERR_ARG, "group %d: nk %d exceeds ld_anc %d / tmax %d", g, nk, ld_anc, tmax);
+        for (int j = 0; j < nk; ++j) {      // key j of the group: row anc[q0][j] * tmax + j
+            const int64_t a = anc[(int64_t)q0 * ld_anc + j];
+            if (a < 0 || a * tmax + j >= kv_rows) return set_error(WLX_ERR_ARG, "group %d: ancestry row %lld of key %d outside K / V", g, (long long)a, j);
+        }
+        anc_rows = std::max<int64_t>(anc_rows, (int64_t)q0 + 1);
+    }
+    HookScope S;
+    MCKR(S.begin(device));
+    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
+    int32_t *dg = nullptr, *da = nullptr;
+    MCKR(S.upload(&dq, reinterpret_cast<const half_t*>(q), (size_t)q_rows * ldq));
+    MCKR(S.upload(&dk, reinterpret_cast<const half_t*>(k), (size_t)kv_rows * ldk));
+    MCKR(S.upload(&dv, reinterpret_cast<const half_t*>(v), (size_t)kv_rows * ldv));
+    MCKR(S.upload(&dout, reinterpret_cast<const half_t*>(o), (size_t)o_rows * ldo));
+    MCKR(S.upload(&dg, groups, (size_t)4 * n_groups));
+    if (anc) MCKR(S.upload(&da, anc, (size_t)anc_rows * ld_anc));
+    static_assert(sizeof(MtAttnGroup) == 4 * sizeof(int32_t), "MtAttnGroup is four int32");
+    launch_mt_attn(dq, ldq, dk, ldk, dv, ldv, dout, ldo, reinterpret_cast<const MtAttnGroup*>(dg), n_groups, max_nq, heads, da,
+                   anc ? ld_anc : 0, anc ? tmax : 0, S.st);
+    MCKR(S.download(reinterpret_cast<half_t*>(o), dout, (size_t)o_rows * ldo));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_t rows, int32_t vocab, const int32_t* ban,
+                                     const int32_t* nban, int32_t ban_ld, int32_t k, float* out_val, int32_t* out_idx) {
+    if (!logits || !out_val || !out_idx) return set_error(WLX_ERR_ARG, "null argument");
+    if (rows < 1 || rows > 65535) return set_error(WLX_ERR_ARG, "rows %d outside 1..65535", rows);
+    if (k < 1 || k > WLX_MT_MAXK) return set_error(WLX_ERR_ARG, "k %d outside 1..%d", k, WLX_MT_MAXK);
+    if (vocab < 16 || vocab % 16 || vocab > WLX_MT_CHUNKS * 4096)      // (the chunk kernel holds 4096 logits in LDS)
+        return set_error(WLX_ERR_ARG, "vocab %d must be a multiple of 16 in 16..%d", vocab, WLX_MT_CHUNKS * 4096);
+    int max_nb = 0;
+    if (nban) {
+        for (int r = 0; r < rows; ++r) {
+            if (nban[r] < 0) return set_error(WLX_ERR_ARG, "row %d: nban %d < 0", r, nban[r]);
+            max_nb = std::max(max_nb, nban[r]);
+        }
+        if (max_nb > 0 && (!ban || ban_ld < max_nb)) return set_error(WLX_ERR_ARG, "ban table missing or ban_ld %d < %d", ban_ld, max_nb);
+    }
+    HookScope S;
+    MCKR(S.begin(device));
+    float *dl = nullptr, *scratch = nullptr, *dval = nullptr;
+    int32_t *dban = nullptr, *dnban = nullptr, *cidx = nullptr, *didx = nullptr;
+    MCKR(S.upload(&dl, logits, (size_t)rows * vocab));
+    if (nban) {
+        MCKR(S.upload(&dnban, nban, (size_t)rows));
+        MCKR(S.upload(&dban, max_nb > 0 ? ban : nullptr, max_nb > 0 ? (size_t)rows * ban_ld : 0));
+    }
+    MCKR(S.upload(&scratch, (const float*)nullptr, (size_t)rows * WLX_MT_CHUNKS * (2 + k)));
+    MCKR(S.upload(&cidx, (const int32_t*)nullptr, (size_t)rows * WLX_MT_CHUNKS * k));
+    MCKR(S.upload(&dval, (const float*)nullptr, (size_t)rows * k));
+    MCKR(S.upload(&didx, (const int32_t*)nullptr, (size_t)rows * k));
+    launch_mt_topk(dl, rows, vocab, dban, dnban, nban ? ban_ld : 0, k, scratch, cidx, dval, didx, S.st);
+    MCKR(S.download(out_val, dval, (size_t)rows * k));
+    MCKR(S.download(out_idx, didx, (size_t)rows * k));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vocab, int32_t d, const int32_t* tok,
+                                      const int32_t* pos, int32_t rows, float scale, const float* sinpos, int32_t n_pos, float* x) {
+    if (!E || !tok || !pos || !sinpos || !x) return set_error(WLX_ERR_ARG, "null argument");
+    if (vocab < 1 || d < 32 || d % 32 || rows < 1 || rows > 65535 || n_pos < 1)
+        return set_error(WLX_ERR_ARG, "vocab %d / d %d (a multiple of 32) / rows %d / n_pos %d", vocab, d, rows, n_pos);
+    for (int r = 0; r < rows; ++r)
+        if (tok[r] < 0 || tok[r] >= vocab || pos[r] < 0 || pos[r] >= n_pos)
+            return set_error(WLX_ERR_ARG, "row %d: token %d / position %d outside the tables", r, tok[r], pos[r]);
+    HookScope S;
+    MCKR(S.begin(device));
+    float *dE = nullptr, *dsin = nullptr, *dx = nullptr;
+    half_t* Ep = nullptr;
+    int32_t *dtok = nullptr, *dpos = nullptr;
+    const int NT = (vocab + 15) / 16;
+    MCKR(S.upload(&dE, E, (size_t)vocab * d));
+    MCKR(dalloc(S.allocs, &Ep, (size_t)NT * 16 * d));
+    launch_pack_linear(dE, vocab, d, d, Ep, d / 32, 0, S.st);      // as wlx_mt_create packs model.shared.weight
+    MCKR(S.upload(&dtok, tok, (size_t)rows));
+    MCKR(S.upload(&dpos, pos, (size_t)rows));
+    MCKR(S.upload(&dsin, sinpos, (size_t)n_pos * d));
+    MCKR(S.upload(&dx, (const float*)nullptr, (size_t)rows * d));
+    launch_mt_embed(dtok, dpos, rows, Ep, d / 32, scale, dsin, d, dx, S.st);
+    MCKR(S.download(x, dx, (size_t)rows * d));
+    return S.finish();
+}
