@@ -8,12 +8,14 @@ import shutil
 import subprocess
 from pathlib import Path
 
+import numpy as np
+
 PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "engine.hip", "vad.hip", "mt.hip", "mt_engine.hip"]
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "host.hip", "engine.hip", "vad.hip", "mt.hip", "mt_engine.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
     "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
@@ -271,6 +273,31 @@ def load() -> C.CDLL:
         raise WlxError("libwlx.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def tensor_array(weights):
+    """dict of name -> numpy array / torch tensor -> (wlx_tensor[], keep): fp32, contiguous; a torch tensor on the GPU goes
+    over as a device pointer (on_device = 1). `keep` holds the converted arrays: keep it alive while the C side reads them."""
+    keep = []
+    arr = (wlx_tensor * len(weights))()
+    for i, (name, t) in enumerate(weights.items()):
+        on_dev = 0
+        if hasattr(t, "data_ptr"):            # torch tensor (PyTorch-ROCm holds the weights)
+            import torch
+            t = t.detach().to(torch.float32).contiguous()
+            on_dev = 1 if t.is_cuda else 0
+            ptr, shape = t.data_ptr(), tuple(t.shape)
+        else:
+            t = np.ascontiguousarray(t, dtype=np.float32)
+            ptr, shape = t.ctypes.data, t.shape
+        keep.append(t)
+        arr[i].name = name.encode()
+        arr[i].data = ptr
+        arr[i].ndim = len(shape)
+        for j, s in enumerate(shape):
+            arr[i].shape[j] = s
+        arr[i].on_device = on_dev
+    return arr, keep
 
 
 def check(rc: int):

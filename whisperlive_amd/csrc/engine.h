@@ -7,24 +7,9 @@
 #include <vector>
 #include "../../include/wlx.h"
 #include "decoder.h"
+#include "host.h"
 
 namespace wlx {
-
-// writes the thread-local message wlx_last_error() returns; shared by every translation unit of the library
-int set_error(int code, const char* fmt, ...);
-// per-device non-blocking stream for set-up work (see engine.hip: the legacy stream is never used)
-hipStream_t util_stream();
-
-struct EncLayerW {
-    float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-    half_t *Wqkv, *Wo, *W1, *W2;
-    float *bqkv, *bo, *b1, *b2;
-};
-struct DecLayerW {
-    float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *ln3_g, *ln3_b;
-    half_t *Wqkv, *Wo, *Wcq, *Wco, *W1, *W2;
-    float *bqkv, *bo, *bcq, *bco, *b1, *b2;
-};
 
 struct StepGraphKey {
     int rows, R, groups;
@@ -56,7 +41,7 @@ struct Slot {
     bool gen_pending = false;                  // the last generate's device time / step count: read in wlx_timings_get, not in wlx_generate
     std::vector<int> lm_items;          // items whose log-mel was requested and not launched yet (engine.hip flush_logmel)
     bool busy_variant = false;          // the decode launches of this slot use the work-saving shapes (three or more live slots on the device; engine.hip device_is_busy)
-    std::vector<void*> allocs;
+    std::vector<void*> allocs, host_allocs;   // device / pinned buffers of the slot's whole life (slot_free)
     // features
     float* pcm = nullptr; size_t pcm_cap = 0;       // [B][pcm_cap]
     float* feats = nullptr; long feat_ld = 0;        // [B][n_mels][feat_ld]
@@ -108,7 +93,7 @@ struct Slot {
     // word alignment (wlx_align): while `align` is set, decoder_pass also writes the raw cross-attention scores of the
     // alignment heads for the rows of the current chunk
     struct AlignCapture { float* scores; const int32_t* heads; int n_heads, n_tok, row0, item; }* align = nullptr;
-    float* align_scores = nullptr; size_t align_cap = 0;     // [n_heads][n_tok][1536] fp32, grown on demand
+    float* align_scores = nullptr; size_t align_cap = 0;     // [n_heads][n_tok][1536] fp32, grown on demand (so owned by name, not by `allocs`)
     int* d_align_tgt = nullptr; float* d_align_prob = nullptr;   // [448]
 };
 
@@ -135,11 +120,11 @@ struct Engine {
     half_t *conv1_w = nullptr, *conv2_w = nullptr;
     float *conv1_b = nullptr, *conv2_b = nullptr, *enc_pos = nullptr, *enc_ln_g = nullptr, *enc_ln_b = nullptr;
     int conv1_KT = 0;
-    std::vector<EncLayerW> enc;
+    std::vector<LayerW> enc;
     half_t* Wckv = nullptr; float* bckv = nullptr;
     half_t *tok_emb16 = nullptr, *Wvocab = nullptr;
     float *dec_pos = nullptr, *dec_ln_g = nullptr, *dec_ln_b = nullptr;
-    std::vector<DecLayerW> dec;
+    std::vector<LayerW> dec;
     std::mutex mu;
     std::vector<Slot*> slots;
     bool use_graph = true;

@@ -7,10 +7,6 @@
 #include <limits>
 #include <algorithm>
 #include <cmath>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,162 +25,7 @@ static inline void cpu_relax() {
     asm volatile("" ::: "memory");
 #endif
 }
-static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-int wlx::set_error(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-#define CK(call)                                                                                       \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(WLX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define CKR(call)                                 \
-    do {                                          \
-        int r_ = (call);                          \
-        if (r_ != WLX_OK) return r_;              \
-    } while (0)
-
 extern "C" int32_t wlx_abi_version(void) { return WLX_ABI_VERSION; }
-extern "C" const char* wlx_last_error(void) { return g_err; }
-
-// ------------------------------------------------------------------------------------------------
-// Nothing in this library may touch the legacy (null) stream once slots exist: while ANY stream is capturing a decode
-// graph, a legacy-stream operation from another thread (hipMemset, synchronous hipMemcpy, hipDeviceSynchronize) fails with
-// "would make the legacy stream depend on a capturing ... stream" AND invalidates that capture — i.e. a second client
-// connecting (slot creation) used to be able to break the first client's transcription. Set-up work that is not tied to a
-// slot therefore runs on a per-device non-blocking utility stream and waits for it explicitly.
-hipStream_t wlx::util_stream() {
-    static std::mutex mu;
-    static std::map<int, hipStream_t> streams;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> g(mu);
-    auto it = streams.find(dev);
-    if (it != streams.end()) return it->second;
-    hipStream_t st = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return nullptr;
-    streams[dev] = st;
-    return st;
-}
-static int upload_sync(void* dst, const void* src, size_t bytes) {      // host -> device, complete on return
-    hipStream_t us = wlx::util_stream();
-    if (!us) return fail(WLX_ERR_HIP, "utility stream creation failed");
-    CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, us));
-    CK(hipStreamSynchronize(us));
-    return WLX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// allocation helpers
-template <typename T>
-static int dalloc(std::vector<void*>& pool, T** out, size_t count, bool zero = true) {
-    void* p = nullptr;
-    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) return fail(WLX_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    if (zero) {
-        hipStream_t us = wlx::util_stream();
-        if (!us) return fail(WLX_ERR_HIP, "utility stream creation failed");
-        e = hipMemsetAsync(p, 0, bytes, us);
-        if (e == hipSuccess) e = hipStreamSynchronize(us);
-        if (e != hipSuccess) return fail(WLX_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-    }
-    pool.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return WLX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight ingestion
-struct WeightSource {
-    std::map<std::string, const wlx_tensor*> by_name;
-    float* staging = nullptr;   // device fp32 staging for host tensors
-    size_t staging_cap = 0;
-    hipStream_t stream = nullptr;
-
-    const wlx_tensor* find(const std::string& n) const {
-        auto it = by_name.find(n);
-        return it == by_name.end() ? nullptr : it->second;
-    }
-    static size_t numel(const wlx_tensor* t) {
-        size_t n = 1;
-        for (int i = 0; i < t->ndim; ++i) n *= (size_t)t->shape[i];
-        return n;
-    }
-    // device fp32 view of a tensor (valid until the next call when the tensor lives on the host)
-    int device_f32(const wlx_tensor* t, const float** out) {
-        if (t->on_device) { *out = reinterpret_cast<const float*>(t->data); return WLX_OK; }
-        size_t n = numel(t);
-        if (n > staging_cap) {
-            if (staging) (void)hipFree(staging);
-            staging = nullptr;
-            CK(hipMalloc(reinterpret_cast<void**>(&staging), n * sizeof(float)));
-            staging_cap = n;
-        }
-        CK(hipStreamSynchronize(stream));  // previous consumer of the staging buffer
-        CKR(upload_sync(staging, t->data, n * sizeof(float)));
-        *out = staging;
-        return WLX_OK;
-    }
-};
-
-static int need(WeightSource& ws, const std::string& name, std::initializer_list<int64_t> shape,
-                const wlx_tensor** out) {
-    const wlx_tensor* t = ws.find(name);
-    if (!t) return fail(WLX_ERR_WEIGHT, "missing weight '%s'", name.c_str());
-    if (t->ndim != (int)shape.size()) return fail(WLX_ERR_WEIGHT, "weight '%s': ndim %d", name.c_str(), t->ndim);
-    int i = 0;
-    for (int64_t s : shape) {
-        if (t->shape[i] != s)
-            return fail(WLX_ERR_WEIGHT, "weight '%s': dim %d is %lld, expected %lld", name.c_str(), i,
-                        (long long)t->shape[i], (long long)s);
-        ++i;
-    }
-    *out = t;
-    return WLX_OK;
-}
-
-// copy an fp32 vector into engine memory at dst+offset (dst pre-allocated, zeroed)
-static int load_vec(WeightSource& ws, const std::string& name, int64_t n, float* dst) {
-    const wlx_tensor* t;
-    CKR(need(ws, name, {n}, &t));
-    if (t->on_device) CK(hipMemcpyAsync(dst, t->data, n * sizeof(float), hipMemcpyDeviceToDevice, ws.stream));
-    else CKR(upload_sync(dst, t->data, n * sizeof(float)));
-    return WLX_OK;
-}
-static int alloc_vec(Engine* e, WeightSource& ws, const std::string& name, int64_t n, float** out) {
-    CKR(dalloc(e->allocs, out, (size_t)n));
-    return load_vec(ws, name, n, *out);
-}
-// pack W[N][K] into a packed image (already allocated, [NT_total][KT]) at n-tile offset nt0
-static int pack_into(WeightSource& ws, const std::string& name, int64_t N, int64_t K, half_t* Wp, int KT, int nt0) {
-    const wlx_tensor* t;
-    CKR(need(ws, name, {N, K}, &t));
-    const float* src;
-    CKR(ws.device_f32(t, &src));
-    launch_pack_linear(src, (int)N, (int)K, K, Wp, KT, nt0, ws.stream);
-    CK(hipGetLastError());
-    return WLX_OK;
-}
-static int alloc_packed(Engine* e, int64_t N, int64_t K, half_t** out, int* KT_out) {
-    int KT = (int)((K + 31) / 32);
-    int NT = (int)((N + 15) / 16);
-    CKR(dalloc(e->allocs, out, (size_t)NT * KT * 512));
-    *KT_out = KT;
-    return WLX_OK;
-}
 
 // Slaney mel filterbank exactly as faster-whisper's FeatureExtractor.get_mel_filters builds it
 // (librosa.filters.mel(sr=16000, n_fft=400, n_mels, htk=False, norm="slaney"); float64 math,
@@ -229,8 +70,8 @@ static int build_logmel_consts(Engine* e) {
     }
     build_mel_filters(e->spec.n_mels, filt, range);
     float *dwin, *dtw, *dfilt; int* drange;
-    CKR(dalloc(e->allocs, &dwin, 400)); CKR(dalloc(e->allocs, &dtw, 800));
-    CKR(dalloc(e->allocs, &dfilt, filt.size())); CKR(dalloc(e->allocs, &drange, range.size()));
+    CKR(dalloc(e->allocs, &dwin, 400, true)); CKR(dalloc(e->allocs, &dtw, 800, true));
+    CKR(dalloc(e->allocs, &dfilt, filt.size(), true)); CKR(dalloc(e->allocs, &drange, range.size(), true));
     CKR(upload_sync(dwin, win.data(), 400 * 4));
     CKR(upload_sync(dtw, tw.data(), 800 * 4));
     CKR(upload_sync(dfilt, filt.data(), filt.size() * 4));
@@ -239,118 +80,58 @@ static int build_logmel_consts(Engine* e) {
     return WLX_OK;
 }
 
-static int load_attn_qkv(Engine* e, WeightSource& ws, const std::string& pre, int d, half_t** W, float** b) {
-    int KT;
-    CKR(alloc_packed(e, 3 * d, d, W, &KT));
-    CKR(pack_into(ws, pre + "q_proj.weight", d, d, *W, KT, 0));
-    CKR(pack_into(ws, pre + "k_proj.weight", d, d, *W, KT, d / 16));
-    CKR(pack_into(ws, pre + "v_proj.weight", d, d, *W, KT, 2 * d / 16));
-    CKR(dalloc(e->allocs, b, (size_t)3 * d));
-    CKR(load_vec(ws, pre + "q_proj.bias", d, *b));
-    CKR(load_vec(ws, pre + "v_proj.bias", d, *b + 2 * d));   // k_proj has no bias
-    return WLX_OK;
-}
-static int load_linear(Engine* e, WeightSource& ws, const std::string& pre, int N, int K, half_t** W, float** b) {
-    int KT;
-    CKR(alloc_packed(e, N, K, W, &KT));
-    CKR(pack_into(ws, pre + ".weight", N, K, *W, KT, 0));
-    CKR(alloc_vec(e, ws, pre + ".bias", N, b));
-    return WLX_OK;
-}
-
 static int engine_load(Engine* e, const wlx_tensor* weights, int n_weights) {
     const wlx_spec& sp = e->spec;
     const int d = sp.d_model, F = sp.ffn, V = sp.vocab;
-    WeightSource ws;
-    for (int i = 0; i < n_weights; ++i) ws.by_name[weights[i].name] = &weights[i];
-    CK(hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking));
-    int rc = WLX_OK;
-    auto body = [&]() -> int {
-        CKR(build_logmel_consts(e));
-        // ---- encoder stem
-        {
-            const wlx_tensor* t; const float* src;
-            CKR(need(ws, "model.encoder.conv1.weight", {d, sp.n_mels, 3}, &t));
-            e->conv1_KT = (3 * sp.n_mels + 31) / 32;
-            CKR(dalloc(e->allocs, &e->conv1_w, (size_t)(d / 16) * e->conv1_KT * 512));
-            CKR(ws.device_f32(t, &src));
-            launch_pack_conv3(src, d, sp.n_mels, e->conv1_w, e->conv1_KT, ws.stream);
-            CKR(need(ws, "model.encoder.conv2.weight", {d, d, 3}, &t));
-            CKR(dalloc(e->allocs, &e->conv2_w, (size_t)(d / 16) * (3 * d / 32) * 512));
-            CKR(ws.device_f32(t, &src));
-            launch_pack_conv3(src, d, d, e->conv2_w, 3 * d / 32, ws.stream);
-            CKR(alloc_vec(e, ws, "model.encoder.conv1.bias", d, &e->conv1_b));
-            CKR(alloc_vec(e, ws, "model.encoder.conv2.bias", d, &e->conv2_b));
-            CKR(need(ws, "model.encoder.embed_positions.weight", {sp.n_audio_ctx, d}, &t));
-            CKR(dalloc(e->allocs, &e->enc_pos, (size_t)sp.n_audio_ctx * d));
-            CKR(ws.device_f32(t, &src));
-            CK(hipMemcpyAsync(e->enc_pos, src, (size_t)sp.n_audio_ctx * d * 4, hipMemcpyDeviceToDevice, ws.stream));
-        }
-        e->enc.resize(sp.enc_layers);
-        for (int l = 0; l < sp.enc_layers; ++l) {
-            EncLayerW& w = e->enc[l];
-            const std::string p = "model.encoder.layers." + std::to_string(l) + ".";
-            CKR(alloc_vec(e, ws, p + "self_attn_layer_norm.weight", d, &w.ln1_g));
-            CKR(alloc_vec(e, ws, p + "self_attn_layer_norm.bias", d, &w.ln1_b));
-            CKR(load_attn_qkv(e, ws, p + "self_attn.", d, &w.Wqkv, &w.bqkv));
-            CKR(load_linear(e, ws, p + "self_attn.out_proj", d, d, &w.Wo, &w.bo));
-            CKR(alloc_vec(e, ws, p + "final_layer_norm.weight", d, &w.ln2_g));
-            CKR(alloc_vec(e, ws, p + "final_layer_norm.bias", d, &w.ln2_b));
-            CKR(load_linear(e, ws, p + "fc1", F, d, &w.W1, &w.b1));
-            CKR(load_linear(e, ws, p + "fc2", d, F, &w.W2, &w.b2));
-        }
-        CKR(alloc_vec(e, ws, "model.encoder.layer_norm.weight", d, &e->enc_ln_g));
-        CKR(alloc_vec(e, ws, "model.encoder.layer_norm.bias", d, &e->enc_ln_b));
-        // ---- decoder
-        {
-            const wlx_tensor* t; const float* src;
-            CKR(need(ws, "model.decoder.embed_tokens.weight", {V, d}, &t));
-            CKR(dalloc(e->allocs, &e->tok_emb16, (size_t)V * d));
-            CKR(ws.device_f32(t, &src));
-            launch_f32_to_f16(src, e->tok_emb16, (long)V * d, ws.stream);
-            int KT;
-            CKR(alloc_packed(e, V, d, &e->Wvocab, &KT));
-            launch_pack_linear(src, V, d, d, e->Wvocab, KT, 0, ws.stream);   // tied output projection
-            CKR(need(ws, "model.decoder.embed_positions.weight", {sp.n_text_ctx, d}, &t));
-            CKR(dalloc(e->allocs, &e->dec_pos, (size_t)sp.n_text_ctx * d));
-            CKR(ws.device_f32(t, &src));
-            CK(hipMemcpyAsync(e->dec_pos, src, (size_t)sp.n_text_ctx * d * 4, hipMemcpyDeviceToDevice, ws.stream));
-        }
-        e->dec.resize(sp.dec_layers);
-        int KTd = d / 32;
-        CKR(dalloc(e->allocs, &e->Wckv, (size_t)(sp.dec_layers * 2 * d / 16) * KTd * 512));
-        CKR(dalloc(e->allocs, &e->bckv, (size_t)sp.dec_layers * 2 * d));
-        for (int l = 0; l < sp.dec_layers; ++l) {
-            DecLayerW& w = e->dec[l];
-            const std::string p = "model.decoder.layers." + std::to_string(l) + ".";
-            CKR(alloc_vec(e, ws, p + "self_attn_layer_norm.weight", d, &w.ln1_g));
-            CKR(alloc_vec(e, ws, p + "self_attn_layer_norm.bias", d, &w.ln1_b));
-            CKR(load_attn_qkv(e, ws, p + "self_attn.", d, &w.Wqkv, &w.bqkv));
-            CKR(load_linear(e, ws, p + "self_attn.out_proj", d, d, &w.Wo, &w.bo));
-            CKR(alloc_vec(e, ws, p + "encoder_attn_layer_norm.weight", d, &w.ln2_g));
-            CKR(alloc_vec(e, ws, p + "encoder_attn_layer_norm.bias", d, &w.ln2_b));
-            CKR(load_linear(e, ws, p + "encoder_attn.q_proj", d, d, &w.Wcq, &w.bcq));
-            CKR(load_linear(e, ws, p + "encoder_attn.out_proj", d, d, &w.Wco, &w.bco));
-            // cross K/V projections of all layers are fused into one encoder-side GEMM
-            CKR(pack_into(ws, p + "encoder_attn.k_proj.weight", d, d, e->Wckv, KTd, l * 2 * d / 16));
-            CKR(pack_into(ws, p + "encoder_attn.v_proj.weight", d, d, e->Wckv, KTd, (l * 2 * d + d) / 16));
-            CKR(load_vec(ws, p + "encoder_attn.v_proj.bias", d, e->bckv + (size_t)l * 2 * d + d));
-            CKR(alloc_vec(e, ws, p + "final_layer_norm.weight", d, &w.ln3_g));
-            CKR(alloc_vec(e, ws, p + "final_layer_norm.bias", d, &w.ln3_b));
-            CKR(load_linear(e, ws, p + "fc1", F, d, &w.W1, &w.b1));
-            CKR(load_linear(e, ws, p + "fc2", d, F, &w.W2, &w.b2));
-        }
-        CKR(alloc_vec(e, ws, "model.decoder.layer_norm.weight", d, &e->dec_ln_g));
-        CKR(alloc_vec(e, ws, "model.decoder.layer_norm.bias", d, &e->dec_ln_b));
-        CK(hipStreamSynchronize(ws.stream));
-        CK(hipGetLastError());
+    std::vector<void*>& A = e->allocs;
+    Weights ws;
+    CKR(ws.open(weights, n_weights));
+    CKR(build_logmel_consts(e));
+    const wlx_tensor* t; const float* src;
+    auto conv = [&](const char* name, int cin, half_t** W, int* KT) -> int {
+        CKR(ws.need(name, {d, cin, 3}, &t));
+        CKR(alloc_packed(A, d, 3 * cin, W, KT, true));
+        CKR(ws.device_f32(t, &src));
+        launch_pack_conv3(src, d, cin, *W, *KT, ws.st);
         return WLX_OK;
     };
-    rc = body();
-    (void)hipStreamSynchronize(ws.stream);
-    if (ws.staging) (void)hipFree(ws.staging);
-    (void)hipStreamDestroy(ws.stream);
-    return rc;
+    auto positions = [&](const char* name, int rows, float** out) -> int {
+        CKR(ws.need(name, {rows, d}, &t));
+        CKR(dalloc(A, out, (size_t)rows * d, true));
+        CKR(ws.device_f32(t, &src));
+        CK(hipMemcpyAsync(*out, src, (size_t)rows * d * 4, hipMemcpyDeviceToDevice, ws.st));
+        return WLX_OK;
+    };
+    // ---- encoder stem
+    int KT;
+    CKR(conv("model.encoder.conv1.weight", sp.n_mels, &e->conv1_w, &e->conv1_KT));
+    CKR(conv("model.encoder.conv2.weight", d, &e->conv2_w, &KT));
+    CKR(ws.alloc_vec(A, "model.encoder.conv1.bias", d, &e->conv1_b, true));
+    CKR(ws.alloc_vec(A, "model.encoder.conv2.bias", d, &e->conv2_b, true));
+    CKR(positions("model.encoder.embed_positions.weight", sp.n_audio_ctx, &e->enc_pos));
+    LayerOpts o{/*k_bias=*/false, /*q_scale=*/1.f, /*zero=*/true};
+    e->enc.resize(sp.enc_layers);
+    for (int l = 0; l < sp.enc_layers; ++l)
+        CKR(load_layer(ws, A, "model.encoder.layers." + std::to_string(l) + ".", d, F, o, e->enc[l]));
+    CKR(ws.alloc_vec(A, "model.encoder.layer_norm.weight", d, &e->enc_ln_g, true));
+    CKR(ws.alloc_vec(A, "model.encoder.layer_norm.bias", d, &e->enc_ln_b, true));
+    // ---- decoder
+    CKR(ws.need("model.decoder.embed_tokens.weight", {V, d}, &t));
+    CKR(dalloc(A, &e->tok_emb16, (size_t)V * d, true));
+    CKR(ws.device_f32(t, &src));
+    launch_f32_to_f16(src, e->tok_emb16, (long)V * d, ws.st);
+    CKR(alloc_packed(A, V, d, &e->Wvocab, &KT, true));
+    launch_pack_linear(src, V, d, d, e->Wvocab, KT, 0, ws.st);   // tied output projection
+    CKR(positions("model.decoder.embed_positions.weight", sp.n_text_ctx, &e->dec_pos));
+    CKR(alloc_packed(A, (int64_t)sp.dec_layers * 2 * d, d, &e->Wckv, nullptr, true));
+    CKR(dalloc(A, &e->bckv, (size_t)sp.dec_layers * 2 * d, true));
+    o.Wckv = e->Wckv; o.bckv = e->bckv;
+    e->dec.resize(sp.dec_layers);
+    for (o.l = 0; o.l < sp.dec_layers; ++o.l)
+        CKR(load_layer(ws, A, "model.decoder.layers." + std::to_string(o.l) + ".", d, F, o, e->dec[o.l]));
+    CKR(ws.alloc_vec(A, "model.decoder.layer_norm.weight", d, &e->dec_ln_g, true));
+    CKR(ws.alloc_vec(A, "model.decoder.layer_norm.bias", d, &e->dec_ln_b, true));
+    return ws.finish();
 }
 
 // The process holds device memory that PyTorch (or another runtime) manages — a weight tensor arrived with on_device = 1: the
@@ -361,20 +142,20 @@ static int engine_load(Engine* e, const wlx_tensor* weights, int n_weights) {
 static std::atomic<bool> g_embedded_device_memory{false};
 extern "C" int32_t wlx_engine_create(const wlx_spec* spec, const wlx_tensor* weights, int32_t n_weights,
                                      int32_t device, wlx_engine** out) {
-    if (!spec || !weights || !out) return fail(WLX_ERR_ARG, "null argument");
+    if (!spec || !weights || !out) return set_error(WLX_ERR_ARG, "null argument");
     if (spec->d_model % 64 || spec->d_model / 64 != spec->n_heads)
-        return fail(WLX_ERR_ARG, "d_model must be 64*n_heads");
-    if (spec->d_model % 128 || spec->d_model > 1536) return fail(WLX_ERR_ARG, "d_model must be a multiple of 128, <= 1536");
-    if (spec->ffn % 128) return fail(WLX_ERR_ARG, "ffn must be a multiple of 128");
-    if (spec->n_mels != 80 && spec->n_mels != 128) return fail(WLX_ERR_ARG, "n_mels must be 80 or 128");
+        return set_error(WLX_ERR_ARG, "d_model must be 64*n_heads");
+    if (spec->d_model % 128 || spec->d_model > 1536) return set_error(WLX_ERR_ARG, "d_model must be a multiple of 128, <= 1536");
+    if (spec->ffn % 128) return set_error(WLX_ERR_ARG, "ffn must be a multiple of 128");
+    if (spec->n_mels != 80 && spec->n_mels != 128) return set_error(WLX_ERR_ARG, "n_mels must be 80 or 128");
     if (spec->n_audio_ctx != WLX_T_AUDIO || spec->n_text_ctx != WLX_T_TEXT)
-        return fail(WLX_ERR_ARG, "n_audio_ctx/n_text_ctx must be 1500/448");
-    if (spec->vocab > 1024 * 52) return fail(WLX_ERR_ARG, "vocab too large");
+        return set_error(WLX_ERR_ARG, "n_audio_ctx/n_text_ctx must be 1500/448");
+    if (spec->vocab > 1024 * 52) return set_error(WLX_ERR_ARG, "vocab too large");
     int ndev = 0;
     CK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(WLX_ERR_ARG, "device %d out of range (%d)", device, ndev);
+    if (device < 0 || device >= ndev) return set_error(WLX_ERR_ARG, "device %d out of range (%d)", device, ndev);
     CK(hipSetDevice(device));
-    if (int pe = gemm_prepare_device()) return fail(WLX_ERR_HIP, "GEMM kernel set-up failed on device %d (hip error %d)", device, pe);
+    if (int pe = gemm_prepare_device()) return set_error(WLX_ERR_HIP, "GEMM kernel set-up failed on device %d (hip error %d)", device, pe);
     wlx_engine* e = new wlx_engine();
     e->spec = *spec;
     e->device = device;
@@ -416,10 +197,7 @@ static void slot_free(Slot* s) {
     if (s->align_scores) (void)hipFree(s->align_scores);
     for (auto& kv : s->graphs) (void)hipGraphExecDestroy(kv.second);
     for (void* p : s->allocs) (void)hipFree(p);
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
-    if (s->h_gen) (void)hipHostFree(s->h_gen);
-    if (s->h_hyp) (void)hipHostFree(s->h_hyp);
-    if (s->h_pf) (void)hipHostFree(s->h_pf);
+    for (void* p : s->host_allocs) (void)hipHostFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->ev_lm0) (void)hipEventDestroy(s->ev_lm0);
@@ -440,7 +218,7 @@ extern "C" void wlx_engine_destroy(wlx_engine* e) {
 }
 
 extern "C" int32_t wlx_engine_spec(const wlx_engine* e, wlx_spec* out) {
-    if (!e || !out) return fail(WLX_ERR_ARG, "null argument");
+    if (!e || !out) return set_error(WLX_ERR_ARG, "null argument");
     *out = e->spec;
     return WLX_OK;
 }
@@ -457,14 +235,14 @@ struct SlotGuard {
 static int create_slot_stream(int device, hipStream_t* out, bool* dedicated_out);
 static bool dedicated_streams_possible();
 static int slot_acquire(wlx_engine* e, int slot, SlotGuard& g) {
-    if (!e) return fail(WLX_ERR_ARG, "null engine");
+    if (!e) return set_error(WLX_ERR_ARG, "null engine");
     Slot* s = nullptr;
     {
         std::lock_guard<std::mutex> lk(e->mu);
-        if (slot < 0 || slot >= (int)e->slots.size() || !e->slots[slot]) return fail(WLX_ERR_ARG, "bad slot %d", slot);
+        if (slot < 0 || slot >= (int)e->slots.size() || !e->slots[slot]) return set_error(WLX_ERR_ARG, "bad slot %d", slot);
         s = e->slots[slot];
         if (!s->call_mu.try_lock())
-            return fail(WLX_ERR_STATE, "slot %d is busy in another call (a slot serves one call at a time)", slot);
+            return set_error(WLX_ERR_STATE, "slot %d is busy in another call (a slot serves one call at a time)", slot);
         g.s = s;
     }
     // From here on the slot is ours (call_mu) and the engine mutex is released: a stream swap below waits for the slot's own
@@ -518,7 +296,7 @@ static int slot_grow_audio(Engine* e, Slot* s, size_t n_samples) {
     float* npcm; float* nfe;
     long ld = (long)(cap / 160 + 64);
     CKR(dalloc(s->allocs, &npcm, (size_t)s->B * cap, false));
-    CKR(dalloc(s->allocs, &nfe, (size_t)s->B * e->spec.n_mels * ld));
+    CKR(dalloc(s->allocs, &nfe, (size_t)s->B * e->spec.n_mels * ld, true));
     // (old buffers stay in the pool until slot destruction; growth is rare: 1-2 times per stream)
     if (s->pcm_cap) {
         // keep what the other items of a batch already hold: a batched encode runs log-mel item by item, and a later,
@@ -604,10 +382,10 @@ static int create_slot_stream(int device, hipStream_t* out, bool* dedicated_out)
 }
 
 extern "C" int32_t wlx_slot_create(wlx_engine* e, int32_t max_batch, int32_t max_rows_per_item, int32_t* slot_out) {
-    if (!e || !slot_out) return fail(WLX_ERR_ARG, "null argument");
-    if (max_batch < 1 || max_batch > 64) return fail(WLX_ERR_ARG, "max_batch out of range");
-    if (max_rows_per_item < 1 || max_rows_per_item > 16) return fail(WLX_ERR_ARG, "max_rows_per_item must be 1..16");
-    if (max_batch * max_rows_per_item > WLX_MAX_DEC_ROWS) return fail(WLX_ERR_ARG, "max_batch*max_rows_per_item must be <= %d", WLX_MAX_DEC_ROWS);
+    if (!e || !slot_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (max_batch < 1 || max_batch > 64) return set_error(WLX_ERR_ARG, "max_batch out of range");
+    if (max_rows_per_item < 1 || max_rows_per_item > 16) return set_error(WLX_ERR_ARG, "max_rows_per_item must be 1..16");
+    if (max_batch * max_rows_per_item > WLX_MAX_DEC_ROWS) return set_error(WLX_ERR_ARG, "max_batch*max_rows_per_item must be <= %d", WLX_MAX_DEC_ROWS);
     CK(hipSetDevice(e->device));
     const wlx_spec& sp = e->spec;
     const int d = sp.d_model, F = sp.ffn, L = sp.dec_layers, B = max_batch, R = max_rows_per_item;
@@ -623,7 +401,7 @@ extern "C" int32_t wlx_slot_create(wlx_engine* e, int32_t max_batch, int32_t max
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             if (bytes > (double)free_b)
-                return fail(WLX_ERR_NOMEM, "a slot of %d items x %d rows needs ~%.1f GB of device memory (encoder activations, cross K/V, KV cache, logits); "
+                return set_error(WLX_ERR_NOMEM, "a slot of %d items x %d rows needs ~%.1f GB of device memory (encoder activations, cross K/V, KV cache, logits); "
                             "%.1f GB are free on device %d: lower max_batch (--batch_max_size) or the number of lanes", B, R, bytes / 1e9, free_b / 1e9, e->device);
         } else (void)hipGetLastError();
         if (bytes > 8e9 && getenv("WLX_QUIET") == nullptr)
@@ -649,44 +427,44 @@ extern "C" int32_t wlx_slot_create(wlx_engine* e, int32_t max_batch, int32_t max
         CK(hipEventCreate(&s->ev_lm0)); CK(hipEventCreate(&s->ev_lm1));
         CK(hipEventCreate(&s->ev_en0)); CK(hipEventCreate(&s->ev_en1));
         CKR(slot_grow_audio(e, s, 480000));
-        CKR(dalloc(s->allocs, &s->gmax, (size_t)B));
-        CKR(dalloc(s->allocs, &s->d_rng, (size_t)2 * WLX_LM_MAXRANGES));
+        CKR(dalloc(s->allocs, &s->gmax, (size_t)B, true));
+        CKR(dalloc(s->allocs, &s->d_rng, (size_t)2 * WLX_LM_MAXRANGES, true));
         s->featT_stride = (long)(WLX_N_FRAMES + 2) * sp.n_mels + 64;
         s->h1_stride = (long)(WLX_N_FRAMES + 2) * d;
-        CKR(dalloc(s->allocs, &s->featT, (size_t)B * s->featT_stride));
-        CKR(dalloc(s->allocs, &s->h1, (size_t)B * s->h1_stride));
+        CKR(dalloc(s->allocs, &s->featT, (size_t)B * s->featT_stride, true));
+        CKR(dalloc(s->allocs, &s->h1, (size_t)B * s->h1_stride, true));
         const size_t TB = (size_t)B * WLX_T_AUDIO;
-        CKR(dalloc(s->allocs, &s->x, TB * d));
-        CKR(dalloc(s->allocs, &s->ln, TB * d));
-        CKR(dalloc(s->allocs, &s->q, TB * d));
-        CKR(dalloc(s->allocs, &s->k, (size_t)B * WLX_T_AUDIO_PAD * d));
-        CKR(dalloc(s->allocs, &s->vt, (size_t)B * d * WLX_T_AUDIO_PAD));
-        CKR(dalloc(s->allocs, &s->attn, TB * d));
-        CKR(dalloc(s->allocs, &s->h2, TB * F));
-        CKR(dalloc(s->allocs, &s->enc16, TB * d));
-        CKR(dalloc(s->allocs, &s->enc32, TB * d));
-        CKR(dalloc(s->allocs, &s->ck, (size_t)L * B * WLX_T_AUDIO_PAD * d));
-        CKR(dalloc(s->allocs, &s->cvt, (size_t)L * B * d * WLX_T_AUDIO_PAD));
-        CKR(dalloc(s->allocs, &s->kc, (size_t)L * s->cache_rows * WLX_T_TEXT * d));
-        CKR(dalloc(s->allocs, &s->vc, (size_t)L * s->cache_rows * WLX_T_TEXT * d));
+        CKR(dalloc(s->allocs, &s->x, TB * d, true));
+        CKR(dalloc(s->allocs, &s->ln, TB * d, true));
+        CKR(dalloc(s->allocs, &s->q, TB * d, true));
+        CKR(dalloc(s->allocs, &s->k, (size_t)B * WLX_T_AUDIO_PAD * d, true));
+        CKR(dalloc(s->allocs, &s->vt, (size_t)B * d * WLX_T_AUDIO_PAD, true));
+        CKR(dalloc(s->allocs, &s->attn, TB * d, true));
+        CKR(dalloc(s->allocs, &s->h2, TB * F, true));
+        CKR(dalloc(s->allocs, &s->enc16, TB * d, true));
+        CKR(dalloc(s->allocs, &s->enc32, TB * d, true));
+        CKR(dalloc(s->allocs, &s->ck, (size_t)L * B * WLX_T_AUDIO_PAD * d, true));
+        CKR(dalloc(s->allocs, &s->cvt, (size_t)L * B * d * WLX_T_AUDIO_PAD, true));
+        CKR(dalloc(s->allocs, &s->kc, (size_t)L * s->cache_rows * WLX_T_TEXT * d, true));
+        CKR(dalloc(s->allocs, &s->vc, (size_t)L * s->cache_rows * WLX_T_TEXT * d, true));
         const int RC = s->rows_cap;
-        CKR(dalloc(s->allocs, &s->xd, (size_t)RC * d));
-        CKR(dalloc(s->allocs, &s->qd, (size_t)RC * d));
-        CKR(dalloc(s->allocs, &s->attnd, (size_t)RC * d));
-        CKR(dalloc(s->allocs, &s->hd, (size_t)RC * F));
-        CKR(dalloc(s->allocs, &s->slab, (size_t)WLX_FC2_KS * RC * d));
-        CKR(dalloc(s->allocs, &s->part_o, (size_t)s->groups_cap * e->H * WLX_XSPLIT * 16 * 64));
-        CKR(dalloc(s->allocs, &s->part_ml, (size_t)s->groups_cap * e->H * WLX_XSPLIT * 16 * 2));
+        CKR(dalloc(s->allocs, &s->xd, (size_t)RC * d, true));
+        CKR(dalloc(s->allocs, &s->qd, (size_t)RC * d, true));
+        CKR(dalloc(s->allocs, &s->attnd, (size_t)RC * d, true));
+        CKR(dalloc(s->allocs, &s->hd, (size_t)RC * F, true));
+        CKR(dalloc(s->allocs, &s->slab, (size_t)WLX_FC2_KS * RC * d, true));
+        CKR(dalloc(s->allocs, &s->part_o, (size_t)s->groups_cap * e->H * WLX_XSPLIT * 16 * 64, true));
+        CKR(dalloc(s->allocs, &s->part_ml, (size_t)s->groups_cap * e->H * WLX_XSPLIT * 16 * 2, true));
         {   // the one-pass prompt prefill's working set: up to WLX_T_TEXT rows (engine.hip prefill_tokens)
             const size_t PR = WLX_T_TEXT, PG = (WLX_T_TEXT + 15) / 16;
             Slot::DecBufs& b = s->pf;
             b.slab_rows = (int)PR;
-            CKR(dalloc(s->allocs, &b.xd, PR * d)); CKR(dalloc(s->allocs, &b.qd, PR * d)); CKR(dalloc(s->allocs, &b.attnd, PR * d));
-            CKR(dalloc(s->allocs, &b.hd, PR * F)); CKR(dalloc(s->allocs, &b.slab, (size_t)WLX_FC2_KS * PR * d));
-            CKR(dalloc(s->allocs, &b.part_o, PG * e->H * WLX_XSPLIT * 16 * 64));
-            CKR(dalloc(s->allocs, &b.part_ml, PG * e->H * WLX_XSPLIT * 16 * 2));
-            CKR(dalloc(s->allocs, &b.d_token, PR)); CKR(dalloc(s->allocs, &b.d_pos, PR)); CKR(dalloc(s->allocs, &b.d_cache, PR));
-            CKR(dalloc(s->allocs, &b.d_ancrow, PR)); CKR(dalloc(s->allocs, &b.d_group_item, PG));
+            CKR(dalloc(s->allocs, &b.xd, PR * d, true)); CKR(dalloc(s->allocs, &b.qd, PR * d, true)); CKR(dalloc(s->allocs, &b.attnd, PR * d, true));
+            CKR(dalloc(s->allocs, &b.hd, PR * F, true)); CKR(dalloc(s->allocs, &b.slab, (size_t)WLX_FC2_KS * PR * d, true));
+            CKR(dalloc(s->allocs, &b.part_o, PG * e->H * WLX_XSPLIT * 16 * 64, true));
+            CKR(dalloc(s->allocs, &b.part_ml, PG * e->H * WLX_XSPLIT * 16 * 2, true));
+            CKR(dalloc(s->allocs, &b.d_token, PR, true)); CKR(dalloc(s->allocs, &b.d_pos, PR, true)); CKR(dalloc(s->allocs, &b.d_cache, PR, true));
+            CKR(dalloc(s->allocs, &b.d_ancrow, PR, true)); CKR(dalloc(s->allocs, &b.d_group_item, PG, true));
             // usable when every projection of this model takes the lean kernel in row chunks (d_model a multiple of 256, ...)
             GemvParams q{};
             static const float dummy_bias = 0.f;
@@ -696,59 +474,59 @@ extern "C" int32_t wlx_slot_create(wlx_engine* e, int32_t max_batch, int32_t max
                        lean(GEMV_IN_LN, GEMV_OUT_GELU_F16, F, d) && lean(GEMV_IN_F16, GEMV_OUT_RESID, d, F);
         }
         s->ldl = ((sp.vocab + 15) / 16) * 16;
-        CKR(dalloc(s->allocs, &s->logits, (size_t)RC * s->ldl));
-        CKR(dalloc(s->allocs, &s->d_token, (size_t)RC));
-        CKR(dalloc(s->allocs, &s->d_pos, (size_t)RC));
-        CKR(dalloc(s->allocs, &s->d_cache, (size_t)RC));
-        CKR(dalloc(s->allocs, &s->d_ancrow, (size_t)RC));
-        CKR(dalloc(s->allocs, &s->d_group_item, (size_t)RC));
+        CKR(dalloc(s->allocs, &s->logits, (size_t)RC * s->ldl, true));
+        CKR(dalloc(s->allocs, &s->d_token, (size_t)RC, true));
+        CKR(dalloc(s->allocs, &s->d_pos, (size_t)RC, true));
+        CKR(dalloc(s->allocs, &s->d_cache, (size_t)RC, true));
+        CKR(dalloc(s->allocs, &s->d_ancrow, (size_t)RC, true));
+        CKR(dalloc(s->allocs, &s->d_group_item, (size_t)RC, true));
         const int CR = std::max(s->cache_rows, RC);
-        CKR(dalloc(s->allocs, &s->d_anc, (size_t)CR * WLX_T_TEXT));
-        CKR(dalloc(s->allocs, &s->d_intok, (size_t)CR * WLX_T_TEXT));
+        CKR(dalloc(s->allocs, &s->d_anc, (size_t)CR * WLX_T_TEXT, true));
+        CKR(dalloc(s->allocs, &s->d_intok, (size_t)CR * WLX_T_TEXT, true));
         SearchState& st = s->st;
-        CKR(dalloc(s->allocs, &st.step, 1)); CKR(dalloc(s->allocs, &st.done, 1)); CKR(dalloc(s->allocs, &st.n_finished, 1));
-        CKR(dalloc(s->allocs, &st.item_done, (size_t)B)); CKR(dalloc(s->allocs, &st.plen, (size_t)B));
-        CKR(dalloc(s->allocs, &st.cum, (size_t)RC)); CKR(dalloc(s->allocs, &st.row_done, (size_t)RC));
-        CKR(dalloc(s->allocs, &st.cand_score, (size_t)RC * WLX_MAX_CAND));
-        CKR(dalloc(s->allocs, &st.cand_tok, (size_t)RC * WLX_MAX_CAND));
-        CKR(dalloc(s->allocs, &st.samp_tok, (size_t)RC)); CKR(dalloc(s->allocs, &st.samp_lp, (size_t)RC));
+        CKR(dalloc(s->allocs, &st.step, 1, true)); CKR(dalloc(s->allocs, &st.done, 1, true)); CKR(dalloc(s->allocs, &st.n_finished, 1, true));
+        CKR(dalloc(s->allocs, &st.item_done, (size_t)B, true)); CKR(dalloc(s->allocs, &st.plen, (size_t)B, true));
+        CKR(dalloc(s->allocs, &st.cum, (size_t)RC, true)); CKR(dalloc(s->allocs, &st.row_done, (size_t)RC, true));
+        CKR(dalloc(s->allocs, &st.cand_score, (size_t)RC * WLX_MAX_CAND, true));
+        CKR(dalloc(s->allocs, &st.cand_tok, (size_t)RC * WLX_MAX_CAND, true));
+        CKR(dalloc(s->allocs, &st.samp_tok, (size_t)RC, true)); CKR(dalloc(s->allocs, &st.samp_lp, (size_t)RC, true));
         // the results of a generate live in pinned host memory (round 6, search.hip finish_item): the update kernels store them there and the host
         // reads them when it sees the done word — no copies, no wait for the step that is already in flight behind the finish
         {
             const size_t ints = (size_t)B * (2 + 2 * WLX_MAX_HYP + (size_t)WLX_MAX_HYP * WLX_T_TEXT);
-            CK(hipHostMalloc(reinterpret_cast<void**>(&s->h_hyp), ints * sizeof(int), hipHostMallocDefault));
+            CKR(halloc(s->host_allocs, &s->h_hyp, ints));
             memset(s->h_hyp, 0, ints * sizeof(int));
             s->max_items = B;
-            CK(hipHostMalloc(reinterpret_cast<void**>(&s->h_pf), (size_t)(5 * WLX_T_TEXT + 64) * sizeof(int), hipHostMallocDefault));
+            CKR(halloc(s->host_allocs, &s->h_pf, (size_t)(5 * WLX_T_TEXT + 64)));
             st.n_hyp_host = s->h_hyp;
             st.hyp_len = st.n_hyp_host + B;
             st.hyp_score = reinterpret_cast<float*>(st.hyp_len + (size_t)B * WLX_MAX_HYP);
             st.no_speech = st.hyp_score + (size_t)B * WLX_MAX_HYP;
             st.hyp_tokens = reinterpret_cast<int*>(st.no_speech + B);
         }
-        CKR(dalloc(s->allocs, &st.n_hyp, (size_t)B));
-        CKR(dalloc(s->allocs, &st.nsp_row, (size_t)RC));
+        CKR(dalloc(s->allocs, &st.n_hyp, (size_t)B, true));
+        CKR(dalloc(s->allocs, &st.nsp_row, (size_t)RC, true));
         st.token = s->d_token; st.pos = s->d_pos; st.anc = s->d_anc; st.intok = s->d_intok;
-        CKR(dalloc(s->allocs, &st.scan_stats, (size_t)RC * SC_MAXCH * SC_NSTAT));
-        CKR(dalloc(s->allocs, &st.scan_cv, (size_t)RC * (SC_MAXCH + 1) * WLX_MAX_CAND));
-        CKR(dalloc(s->allocs, &st.scan_ci, (size_t)RC * (SC_MAXCH + 1) * WLX_MAX_CAND));
-        CKR(dalloc(s->allocs, &st.rule, (size_t)RC * 4));
-        CKR(dalloc(s->allocs, &s->d_align_tgt, (size_t)WLX_T_TEXT));
-        CKR(dalloc(s->allocs, &s->d_align_prob, (size_t)WLX_T_TEXT));
-        CKR(dalloc(s->allocs, &s->d_sp, 1));
-        CKR(dalloc(s->allocs, &s->d_suppress, (size_t)(1024 * 52 / 32)));
-        CKR(dalloc(s->allocs, &s->d_lang_ids, 256));
-        CKR(dalloc(s->allocs, &s->d_probs, (size_t)B * 256));
-        CKR(dalloc(s->allocs, &s->d_tokprob, (size_t)RC));
+        CKR(dalloc(s->allocs, &st.scan_stats, (size_t)RC * SC_MAXCH * SC_NSTAT, true));
+        CKR(dalloc(s->allocs, &st.scan_cv, (size_t)RC * (SC_MAXCH + 1) * WLX_MAX_CAND, true));
+        CKR(dalloc(s->allocs, &st.scan_ci, (size_t)RC * (SC_MAXCH + 1) * WLX_MAX_CAND, true));
+        CKR(dalloc(s->allocs, &st.rule, (size_t)RC * 4, true));
+        CKR(dalloc(s->allocs, &s->d_align_tgt, (size_t)WLX_T_TEXT, true));
+        CKR(dalloc(s->allocs, &s->d_align_prob, (size_t)WLX_T_TEXT, true));
+        CKR(dalloc(s->allocs, &s->d_sp, 1, true));
+        CKR(dalloc(s->allocs, &s->d_suppress, (size_t)(1024 * 52 / 32), true));
+        CKR(dalloc(s->allocs, &s->d_lang_ids, 256, true));
+        CKR(dalloc(s->allocs, &s->d_probs, (size_t)B * 256, true));
+        CKR(dalloc(s->allocs, &s->d_tokprob, (size_t)RC, true));
         s->h_stage_ints = 1 << 16;
-        CK(hipHostMalloc(reinterpret_cast<void**>(&s->h_stage), s->h_stage_ints * sizeof(int), hipHostMallocDefault));
+        CKR(halloc(s->host_allocs, &s->h_stage, s->h_stage_ints));
         // the search kernels raise this pinned word themselves when every item is finished (no per-step D2H copy)
         s->st.done_host = s->h_stage + (s->h_stage_ints - 4);
         // wlx_generate's pinned staging: [set-up: SearchParams | cum | rule | plen | nsp | ancestry rows] [results: n_hyp |
         // hyp_len | hyp_score | no_speech | step | hyp_tokens]
         s->h_gen_bytes = 4096 + (size_t)RC * (4 + 16 + 4) + (size_t)B * 4 + (size_t)RC * WLX_T_TEXT * 2 + 256 + ((size_t)RC * 4 + B) * 4 + 128 +
                          (size_t)B * (4 + WLX_MAX_HYP * 8 + 4) + 64 + (size_t)B * WLX_MAX_HYP * WLX_T_TEXT * 4;
-        CK(hipHostMalloc(reinterpret_cast<void**>(&s->h_gen), s->h_gen_bytes, hipHostMallocDefault));
+        CKR(halloc(s->host_allocs, &s->h_gen, s->h_gen_bytes));
         CK(hipStreamSynchronize(s->stream));      // (allocations were zeroed on the utility stream and waited for in dalloc)
         return WLX_OK;
     }();
@@ -762,12 +540,12 @@ extern "C" int32_t wlx_slot_create(wlx_engine* e, int32_t max_batch, int32_t max
 }
 
 extern "C" int32_t wlx_slot_destroy(wlx_engine* e, int32_t slot) {
-    if (!e) return fail(WLX_ERR_ARG, "null engine");
+    if (!e) return set_error(WLX_ERR_ARG, "null engine");
     Slot* s = nullptr;
     for (;;) {      // wait for a call still running on the slot in another thread (a session being torn down mid-chunk)
         {
             std::lock_guard<std::mutex> g(e->mu);
-            if (slot < 0 || slot >= (int)e->slots.size() || !e->slots[slot]) return fail(WLX_ERR_ARG, "bad slot %d", slot);
+            if (slot < 0 || slot >= (int)e->slots.size() || !e->slots[slot]) return set_error(WLX_ERR_ARG, "bad slot %d", slot);
             if (e->slots[slot]->call_mu.try_lock()) {
                 s = e->slots[slot];
                 e->slots[slot] = nullptr;        // no other thread can reach it any more
@@ -822,7 +600,7 @@ extern "C" int32_t wlx_timings_get(wlx_engine* e, int32_t slot, wlx_timings* out
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!out) return fail(WLX_ERR_ARG, "null out");
+    if (!out) return set_error(WLX_ERR_ARG, "null out");
     CKR(flush_logmel(e, s));
     if (s->en_pending) {                      // the last encoder pass
         CK(hipSetDevice(e->device));
@@ -855,9 +633,9 @@ extern "C" int32_t wlx_pcm_put(wlx_engine* e, int32_t slot, int32_t item, const 
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!pcm || n <= 0) return fail(WLX_ERR_ARG, "empty audio");
-    if (item < 0 || item >= s->B) return fail(WLX_ERR_ARG, "bad item %d", item);
-    if (n > 16000LL * 3600) return fail(WLX_ERR_ARG, "audio chunk too long");
+    if (!pcm || n <= 0) return set_error(WLX_ERR_ARG, "empty audio");
+    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", item);
+    if (n > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
     CK(hipSetDevice(e->device));
     if ((size_t)n > s->pcm_cap || std::find(s->lm_items.begin(), s->lm_items.end(), (int)item) != s->lm_items.end())
         CKR(flush_logmel(e, s));            // a recorded log-mel request reads this item's PCM (or the buffers are about to be re-allocated)
@@ -872,19 +650,19 @@ extern "C" int32_t wlx_pcm_put(wlx_engine* e, int32_t slot, int32_t item, const 
 // ------------------------------------------------------------------------------------------------
 // PCM ring (include/wlx.h): whisper_live/backend/base.py:173-234 on the device
 extern "C" int32_t wlx_ring_create(wlx_engine* e, int64_t capacity_samples, wlx_ring** out) {
-    if (!e || !out) return fail(WLX_ERR_ARG, "null argument");
-    if (capacity_samples < 0 || capacity_samples > 16000LL * 3600) return fail(WLX_ERR_ARG, "ring capacity out of range");
+    if (!e || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (capacity_samples < 0 || capacity_samples > 16000LL * 3600) return set_error(WLX_ERR_ARG, "ring capacity out of range");
     CK(hipSetDevice(e->device));
     wlx_ring* r = new wlx_ring();
     r->device = e->device;
     r->cap = (size_t)(capacity_samples > 0 ? capacity_samples : 16000LL * 64);
-    hipError_t he = hipMalloc(reinterpret_cast<void**>(&r->buf), r->cap * sizeof(float));
+    hipError_t he = hipMalloc(reinterpret_cast<void**>(&r->buf), r->cap * sizeof(float));   // owned by name: wlx_ring_append grows it
     if (he == hipSuccess) he = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
     if (he == hipSuccess) he = hipEventCreateWithFlags(&r->last_read, hipEventDisableTiming);
     if (he != hipSuccess) {
         (void)hipGetLastError();
         wlx_ring_destroy(r);
-        return fail(WLX_ERR_HIP, "wlx_ring_create: %s", hipGetErrorString(he));
+        return set_error(WLX_ERR_HIP, "wlx_ring_create: %s", hipGetErrorString(he));
     }
     *out = r;
     return WLX_OK;
@@ -908,8 +686,8 @@ static int ring_wait_readers(Ring* r) {
 
 extern "C" int32_t wlx_ring_append(wlx_ring* r, const float* samples, int64_t n, int64_t max_resident, int64_t trim,
                                    int64_t* dropped_out, int64_t* base_out, int64_t* resident_out) {
-    if (!r || n < 0 || (n > 0 && !samples)) return fail(WLX_ERR_ARG, "wlx_ring_append: bad argument");
-    if (n > 16000LL * 3600) return fail(WLX_ERR_ARG, "audio chunk too long");
+    if (!r || n < 0 || (n > 0 && !samples)) return set_error(WLX_ERR_ARG, "wlx_ring_append: bad argument");
+    if (n > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
     std::lock_guard<std::mutex> lk(r->mu);
     CK(hipSetDevice(r->device));
     int64_t dropped = 0;
@@ -929,7 +707,7 @@ extern "C" int32_t wlx_ring_append(wlx_ring* r, const float* samples, int64_t n,
         size_t cap = r->cap;
         while (cap < (size_t)(r->resident + n)) cap *= 2;
         float* nb = nullptr;
-        CK(hipMalloc(reinterpret_cast<void**>(&nb), cap * sizeof(float)));
+        CK(hipMalloc(reinterpret_cast<void**>(&nb), cap * sizeof(float)));       // replaces r->buf, which is freed below: no free list
         CKR(ring_wait_readers(r));
         CK(hipMemcpyAsync(nb, r->buf, (size_t)r->resident * sizeof(float), hipMemcpyDeviceToDevice, r->stream));
         CK(hipStreamSynchronize(r->stream));
@@ -946,7 +724,7 @@ extern "C" int32_t wlx_ring_append(wlx_ring* r, const float* samples, int64_t n,
 }
 
 extern "C" int32_t wlx_ring_state(wlx_ring* r, int64_t* base_out, int64_t* resident_out) {
-    if (!r) return fail(WLX_ERR_ARG, "null ring");
+    if (!r) return set_error(WLX_ERR_ARG, "null ring");
     std::lock_guard<std::mutex> lk(r->mu);
     if (base_out) *base_out = r->base;
     if (resident_out) *resident_out = r->resident;
@@ -958,24 +736,24 @@ extern "C" int32_t wlx_logmel_ring(wlx_engine* e, int32_t slot, int32_t item, wl
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!r || !ranges || n_ranges < 1) return fail(WLX_ERR_ARG, "wlx_logmel_ring: bad argument");
-    if (n_ranges > WLX_LM_MAXRANGES) return fail(WLX_ERR_ARG, "wlx_logmel_ring: more than %d ranges", WLX_LM_MAXRANGES);
-    if (item < 0 || item >= s->B) return fail(WLX_ERR_ARG, "bad item %d", item);
-    if (r->device != e->device) return fail(WLX_ERR_ARG, "wlx_logmel_ring: the ring lives on device %d, the engine on %d", r->device, e->device);
+    if (!r || !ranges || n_ranges < 1) return set_error(WLX_ERR_ARG, "wlx_logmel_ring: bad argument");
+    if (n_ranges > WLX_LM_MAXRANGES) return set_error(WLX_ERR_ARG, "wlx_logmel_ring: more than %d ranges", WLX_LM_MAXRANGES);
+    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", item);
+    if (r->device != e->device) return set_error(WLX_ERR_ARG, "wlx_logmel_ring: the ring lives on device %d, the engine on %d", r->device, e->device);
     CK(hipSetDevice(e->device));
     std::lock_guard<std::mutex> lk(r->mu);
     long long tab[2 * WLX_LM_MAXRANGES];
     int64_t total = 0, prev_end = r->base;
     for (int i = 0; i < n_ranges; ++i) {
         const int64_t a = ranges[2 * i], b = ranges[2 * i + 1];
-        if (a < prev_end || b <= a) return fail(a < r->base ? WLX_ERR_STATE : WLX_ERR_ARG, "wlx_logmel_ring: range %d = [%lld, %lld) is empty, out of order or no longer resident (ring starts at %lld)",
+        if (a < prev_end || b <= a) return set_error(a < r->base ? WLX_ERR_STATE : WLX_ERR_ARG, "wlx_logmel_ring: range %d = [%lld, %lld) is empty, out of order or no longer resident (ring starts at %lld)",
                                                 i, (long long)a, (long long)b, (long long)r->base);
-        if (b > r->base + r->resident) return fail(WLX_ERR_STATE, "wlx_logmel_ring: range %d ends at %lld, the ring at %lld", i, (long long)b, (long long)(r->base + r->resident));
+        if (b > r->base + r->resident) return set_error(WLX_ERR_STATE, "wlx_logmel_ring: range %d ends at %lld, the ring at %lld", i, (long long)b, (long long)(r->base + r->resident));
         tab[2 * i] = a - r->base; tab[2 * i + 1] = total;
         total += b - a;
         prev_end = b;
     }
-    if (total > 16000LL * 3600) return fail(WLX_ERR_ARG, "audio chunk too long");
+    if (total > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
     // a reader launched from ANOTHER stream may still be pending: its event is about to be re-recorded on this stream, so this stream first
     // waits for it (the new record then stands for both; one session = one slot = one stream makes this the rare case)
     if (r->read_pending && r->last_read_stream != s->stream) CK(hipStreamWaitEvent(s->stream, r->last_read, 0));
@@ -1004,9 +782,9 @@ extern "C" int32_t wlx_logmel_resident(wlx_engine* e, int32_t slot, int32_t item
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (item < 0 || item >= s->B) return fail(WLX_ERR_ARG, "bad item %d", item);
+    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", item);
     const int64_t n = s->npcm[item];
-    if (n <= 0) return fail(WLX_ERR_STATE, "item %d: no PCM resident (call wlx_pcm_put first)", item);
+    if (n <= 0) return set_error(WLX_ERR_STATE, "item %d: no PCM resident (call wlx_pcm_put first)", item);
     CK(hipSetDevice(e->device));
     const int T = (int)((n + 160) / 160);
     float* dp = s->pcm + (size_t)item * s->pcm_cap;
@@ -1032,12 +810,12 @@ extern "C" int32_t wlx_features_get(wlx_engine* e, int32_t slot, int32_t item, f
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (item < 0 || item >= s->B) return fail(WLX_ERR_ARG, "bad item");
+    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "bad item");
     const int T = s->nframes[item], nm = e->spec.n_mels;
     if (n_frames_out) *n_frames_out = T;
     if (!out) return WLX_OK;
     CKR(flush_logmel(e, s));
-    if ((int64_t)T * nm > cap_floats) return fail(WLX_ERR_ARG, "output buffer too small");
+    if ((int64_t)T * nm > cap_floats) return set_error(WLX_ERR_ARG, "output buffer too small");
     CK(hipSetDevice(e->device));
     const float* df = s->feats + (size_t)item * nm * s->feat_ld;
     CK(hipMemcpy2DAsync(out, (size_t)T * 4, df, (size_t)s->feat_ld * 4, (size_t)T * 4, nm, hipMemcpyDeviceToHost, s->stream));
@@ -1050,8 +828,8 @@ extern "C" int32_t wlx_features_set(wlx_engine* e, int32_t slot, int32_t item, c
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (item < 0 || item >= s->B || !feats) return fail(WLX_ERR_ARG, "bad item / null");
-    if (n_mels != e->spec.n_mels || n_frames < 1) return fail(WLX_ERR_ARG, "features must be [%d, T>=1]", e->spec.n_mels);
+    if (item < 0 || item >= s->B || !feats) return set_error(WLX_ERR_ARG, "bad item / null");
+    if (n_mels != e->spec.n_mels || n_frames < 1) return set_error(WLX_ERR_ARG, "features must be [%d, T>=1]", e->spec.n_mels);
     CK(hipSetDevice(e->device));
     CKR(flush_logmel(e, s));                // (a recorded request for this item must not overwrite the features set here)
     CKR(slot_grow_audio(e, s, (size_t)n_frames * 160));
@@ -1069,7 +847,7 @@ extern "C" int32_t wlx_encode(wlx_engine* e, int32_t slot, int32_t batch, const 
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (batch < 1 || batch > s->B) return fail(WLX_ERR_ARG, "batch %d out of range (slot max %d)", batch, s->B);
+    if (batch < 1 || batch > s->B) return set_error(WLX_ERR_ARG, "batch %d out of range (slot max %d)", batch, s->B);
     const wlx_spec& sp = e->spec;
     const int d = sp.d_model, F = sp.ffn, nm = sp.n_mels, H = e->H, T = WLX_T_AUDIO;
     CK(hipSetDevice(e->device));
@@ -1081,7 +859,7 @@ extern "C" int32_t wlx_encode(wlx_engine* e, int32_t slot, int32_t batch, const 
         const int sk = seek ? seek[b] : 0;
         int sg = seg ? seg[b] : (s->nframes[b] - sk);
         if (sk < 0 || sg < 0 || sk + sg > s->nframes[b])
-            return fail(WLX_ERR_ARG, "item %d: window [%d,%d) outside %d feature frames", b, sk, sk + sg, s->nframes[b]);
+            return set_error(WLX_ERR_ARG, "item %d: window [%d,%d) outside %d feature frames", b, sk, sk + sg, s->nframes[b]);
         if (sg > WLX_N_FRAMES) sg = WLX_N_FRAMES;
         pw.seek[b] = sk; pw.seg[b] = sg;
     }
@@ -1102,7 +880,7 @@ extern "C" int32_t wlx_encode(wlx_engine* e, int32_t slot, int32_t batch, const 
     launch_gemm(g, batch, st);
     const int M = batch * T;
     for (int l = 0; l < sp.enc_layers; ++l) {
-        const EncLayerW& w = e->enc[l];
+        const LayerW& w = e->enc[l];
         launch_layernorm_f16(s->x, d, w.ln1_g, w.ln1_b, s->ln, d, M, d, st);
         g = GemmParams{};
         g.A = s->ln; g.lda = d; g.Wp = w.Wqkv; g.KT = d / 32; g.M = M; g.N = 3 * d; g.mode = GEMM_QKV; g.bias = w.bqkv;
@@ -1115,7 +893,7 @@ extern "C" int32_t wlx_encode(wlx_engine* e, int32_t slot, int32_t batch, const 
         g.A = s->attn; g.lda = d; g.Wp = w.Wo; g.KT = d / 32; g.M = M; g.N = d; g.mode = GEMM_RESID_F32; g.bias = w.bo;
         g.X = s->x; g.ldx = d;
         launch_gemm(g, 1, st);
-        launch_layernorm_f16(s->x, d, w.ln2_g, w.ln2_b, s->ln, d, M, d, st);
+        launch_layernorm_f16(s->x, d, w.ln3_g, w.ln3_b, s->ln, d, M, d, st);
         g = GemmParams{};
         g.A = s->ln; g.lda = d; g.Wp = w.W1; g.KT = d / 32; g.M = M; g.N = F; g.mode = GEMM_GELU_F16; g.bias = w.b1;
         g.C = s->h2; g.ldc = F;
@@ -1147,9 +925,9 @@ extern "C" int32_t wlx_encoder_output_get(wlx_engine* e, int32_t slot, int32_t i
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (item < 0 || item >= s->enc_batch) return fail(WLX_ERR_STATE, "item %d not encoded", item);
+    if (item < 0 || item >= s->enc_batch) return set_error(WLX_ERR_STATE, "item %d not encoded", item);
     const size_t n = (size_t)WLX_T_AUDIO * e->spec.d_model;
-    if (!out || (int64_t)n > cap_floats) return fail(WLX_ERR_ARG, "output buffer too small");
+    if (!out || (int64_t)n > cap_floats) return set_error(WLX_ERR_ARG, "output buffer too small");
     CK(hipSetDevice(e->device));
     CK(hipMemcpyAsync(out, s->enc32 + (size_t)item * n, n * 4, hipMemcpyDeviceToHost, s->stream));
     CK(hipStreamSynchronize(s->stream));
@@ -1204,7 +982,7 @@ static void decoder_pass(Engine* e, Slot* s_, int rows, int R, int groups, bool 
     const long crs = (long)WLX_T_TEXT * d;
     // ---- the parameter sets of one layer (the first projection's residual source is filled in below)
     auto qkv_params = [&](int l, int xsrc) {
-        const DecLayerW& w = e->dec[l];
+        const LayerW& w = e->dec[l];
         GemvParams p{};
         p.in_mode = GEMV_IN_LN; p.out_mode = GEMV_OUT_QKV; p.M = rows; p.K = d; p.KT = d / 32; p.N = 3 * d;
         p.Wp = w.Wqkv; p.bias = w.bqkv; p.X = s.xd; p.ldx = d; p.gamma = w.ln1_g; p.beta = w.ln1_b;
@@ -1219,7 +997,7 @@ static void decoder_pass(Engine* e, Slot* s_, int rows, int R, int groups, bool 
         return p;
     };
     auto oproj_params = [&](int l, int xsrc) {
-        const DecLayerW& w = e->dec[l];
+        const LayerW& w = e->dec[l];
         GemvParams p{};
         p.in_mode = GEMV_IN_F16; p.out_mode = GEMV_OUT_RESID; p.M = rows; p.K = d; p.KT = d / 32; p.N = d;
         p.Wp = w.Wo; p.bias = w.bo; p.Xh = s.attnd; p.ldxh = d; p.Xres = s.xd; p.ldxres = d; p.qscale = 1.f; p.done = done;
@@ -1264,7 +1042,7 @@ static void decoder_pass(Engine* e, Slot* s_, int rows, int R, int groups, bool 
         plaunch(s.base, "dec_embed_kernel", (double)rows * d * (2 + 4), [&] { launch_dec_embed(e->tok_emb16, e->dec_pos, d, rt, rows, s.xd, done, st); });
     bool slabs_pending = false;             // the residual stream is xd + slabs until the next residual update writes the sum back
     for (int l = 0; l < sp.dec_layers; ++l) {
-        const DecLayerW& w = e->dec[l];
+        const LayerW& w = e->dec[l];
         half_t* kc = s->kc + (size_t)l * s->cache_rows * crs;
         half_t* vc = s->vc + (size_t)l * s->cache_rows * crs;
         // LN1 + QKV, K/V appended to the self-attention cache
@@ -1342,7 +1120,7 @@ static int upload_rows(Slot* s, const std::vector<int>& token, const std::vector
                        const std::vector<int>& cache, const std::vector<int>& ancrow, const std::vector<int>& group_item,
                        int* own_staging = nullptr) {
     const size_t rows = token.size(), ng = group_item.size();
-    if (4 * rows + ng > s->h_stage_ints) return fail(WLX_ERR_ARG, "row table too large");
+    if (4 * rows + ng > s->h_stage_ints) return set_error(WLX_ERR_ARG, "row table too large");
     s->anc_ident = true;                                    // every row reads its history through its own ancestry row
     for (size_t i = 0; i < rows; ++i) s->anc_ident = s->anc_ident && ancrow[i] == (int)i;
     // the shared staging buffer may still be the source of an earlier pass's copies: wait; a caller that brings its own
@@ -1498,7 +1276,7 @@ static int get_step_graph(Engine* e, Slot* s, int rows, int R, int groups, bool 
             (void)hipStreamDestroy(s->stream);
             s->stream = ns;
         }
-        return fail(WLX_ERR_HIP, "decode-step graph capture failed: %s (slot stream replaced)", hipGetErrorString(ce));
+        return set_error(WLX_ERR_HIP, "decode-step graph capture failed: %s (slot stream replaced)", hipGetErrorString(ce));
     }
     hipGraphExec_t exec;
     CK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
@@ -1546,19 +1324,19 @@ static int fill_search_params(Engine* e, Slot* s, int batch, int R, const wlx_ge
 }
 
 static int validate_opts(Engine* e, Slot* s, int batch, const wlx_gen_opts* o) {
-    if (!o) return fail(WLX_ERR_ARG, "null opts");
+    if (!o) return set_error(WLX_ERR_ARG, "null opts");
     const int V = e->spec.vocab;
     auto bad = [&](int id) { return id < 0 || id >= V; };
     if (bad(o->ids.sot) || bad(o->ids.eot) || bad(o->ids.no_timestamps) || bad(o->ids.timestamp_begin) || bad(o->ids.no_speech))
-        return fail(WLX_ERR_ARG, "token ids out of vocabulary");
-    if (o->max_length < 2 || o->max_length > WLX_T_TEXT) return fail(WLX_ERR_ARG, "max_length must be 2..448");
+        return set_error(WLX_ERR_ARG, "token ids out of vocabulary");
+    if (o->max_length < 2 || o->max_length > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "max_length must be 2..448");
     const bool sampling = (o->sampling_temperature > 0.f || o->beam_size <= 1);
     const int R = sampling ? std::max(1, o->num_hypotheses) : o->beam_size;
-    if (R < 1 || R > s->R) return fail(WLX_ERR_ARG, "beam_size/num_hypotheses %d exceeds slot rows per item %d", R, s->R);
-    if (!sampling && o->num_hypotheses > o->beam_size) return fail(WLX_ERR_ARG, "num_hypotheses > beam_size");
-    if (!sampling && 2 * o->beam_size > WLX_MAX_CAND) return fail(WLX_ERR_ARG, "beam_size too large");
-    if (batch * R > s->rows_cap) return fail(WLX_ERR_ARG, "too many decoder rows");
-    if (o->n_suppress_tokens < 0 || (o->n_suppress_tokens > 0 && !o->suppress_tokens)) return fail(WLX_ERR_ARG, "bad suppress_tokens");
+    if (R < 1 || R > s->R) return set_error(WLX_ERR_ARG, "beam_size/num_hypotheses %d exceeds slot rows per item %d", R, s->R);
+    if (!sampling && o->num_hypotheses > o->beam_size) return set_error(WLX_ERR_ARG, "num_hypotheses > beam_size");
+    if (!sampling && 2 * o->beam_size > WLX_MAX_CAND) return set_error(WLX_ERR_ARG, "beam_size too large");
+    if (batch * R > s->rows_cap) return set_error(WLX_ERR_ARG, "too many decoder rows");
+    if (o->n_suppress_tokens < 0 || (o->n_suppress_tokens > 0 && !o->suppress_tokens)) return set_error(WLX_ERR_ARG, "bad suppress_tokens");
     return WLX_OK;
 }
 
@@ -1600,10 +1378,10 @@ static int generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, 
     bool apply_ts = true;
     for (int b = 0; b < batch; ++b) {
         const int pl = plens[b];
-        if (pl < 1 || pl >= o->max_length) return fail(WLX_ERR_ARG, "item %d: prompt length %d vs max_length %d", b, pl, o->max_length);
+        if (pl < 1 || pl >= o->max_length) return set_error(WLX_ERR_ARG, "item %d: prompt length %d vs max_length %d", b, pl, o->max_length);
         const int32_t* pr = prompts + (size_t)b * pstride;
         for (int i = 0; i < pl; ++i) {
-            if (pr[i] < 0 || pr[i] >= V) return fail(WLX_ERR_ARG, "prompt token out of vocabulary");
+            if (pr[i] < 0 || pr[i] >= V) return set_error(WLX_ERR_ARG, "prompt token out of vocabulary");
             if (pr[i] == o->ids.no_timestamps) apply_ts = false;   // CT2: timestamp rules only without <|notimestamps|>
         }
         max_steps = std::max(max_steps, o->max_length - pl);
@@ -1669,7 +1447,7 @@ static int generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, 
             const int d = e->spec.d_model;
             for (int b0 = 0; b0 < batch; b0 += IB) {
                 const int nb = std::min(IB, batch - b0), prow = 16 * nb;
-                if ((size_t)(4 * prow + nb) > s->h_stage_ints - 8) return fail(WLX_ERR_ARG, "batch too large");
+                if ((size_t)(4 * prow + nb) > s->h_stage_ints - 8) return set_error(WLX_ERR_ARG, "batch too large");
                 CK(hipStreamSynchronize(st));                        // the shared staging may still feed an earlier pass's copies
                 int* h = s->h_stage;
                 for (int bi = 0; bi < nb; ++bi) {
@@ -1780,7 +1558,7 @@ static int generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, 
                     spins = 0; ++rounds;
                     const hipError_t q = hipStreamQuery(st);
                     if (q == hipSuccess) break;                // drained: the counter is final
-                    if (q != hipErrorNotReady) return fail(WLX_ERR_HIP, "decode loop: %s", hipGetErrorString(q));
+                    if (q != hipErrorNotReady) return set_error(WLX_ERR_HIP, "decode loop: %s", hipGetErrorString(q));
                 }
             }
             if (gen_trace) tg_wait += now_us() - ta;
@@ -1844,13 +1622,13 @@ extern "C" int32_t wlx_generate_ex(wlx_engine* e, int32_t slot, int32_t batch, c
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!prompts || !prompt_lens || !tokens_out || !n_tokens_out || !scores_out) return fail(WLX_ERR_ARG, "null argument");
-    if (batch < 1 || batch > s->B) return fail(WLX_ERR_ARG, "batch %d out of range (slot max %d)", batch, s->B);
-    if (s->enc_batch < 1) return fail(WLX_ERR_STATE, "generate before encode");
+    if (!prompts || !prompt_lens || !tokens_out || !n_tokens_out || !scores_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (batch < 1 || batch > s->B) return set_error(WLX_ERR_ARG, "batch %d out of range (slot max %d)", batch, s->B);
+    if (s->enc_batch < 1) return set_error(WLX_ERR_STATE, "generate before encode");
     for (int b = 0; b < batch; ++b) {
         const int it = enc_items ? enc_items[b] : b;
         if (it < 0 || it >= s->enc_batch)
-            return fail(WLX_ERR_STATE, "generate: item %d uses encoder item %d but only %d are encoded", b, it, s->enc_batch);
+            return set_error(WLX_ERR_STATE, "generate: item %d uses encoder item %d but only %d are encoded", b, it, s->enc_batch);
     }
     CK(hipSetDevice(e->device));
     return generate_impl(e, s, batch, prompts, prompt_lens, prompt_stride, enc_items, opts, false, nullptr, 0, tokens_out,
@@ -1871,7 +1649,7 @@ extern "C" int32_t wlx_debug_search(wlx_engine* e, int32_t slot, const float* lo
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!logits || !prompt || !opts) return fail(WLX_ERR_ARG, "null argument");
+    if (!logits || !prompt || !opts) return set_error(WLX_ERR_ARG, "null argument");
     CK(hipSetDevice(e->device));
     float nsp;
     return generate_impl(e, s, 1, prompt, &prompt_len, prompt_len, nullptr, opts, true, logits, steps, tokens_out, tokens_stride,
@@ -1883,10 +1661,10 @@ extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batc
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (batch < 1 || batch > s->enc_batch) return fail(WLX_ERR_STATE, "detect_language before encode");
-    if (!lang_ids || n_lang < 1 || n_lang > 256 || !probs_out) return fail(WLX_ERR_ARG, "bad language id list");
-    if (sot < 0 || sot >= e->spec.vocab) return fail(WLX_ERR_ARG, "bad sot id");
-    for (int i = 0; i < n_lang; ++i) if (lang_ids[i] < 0 || lang_ids[i] >= e->spec.vocab) return fail(WLX_ERR_ARG, "bad language id");
+    if (batch < 1 || batch > s->enc_batch) return set_error(WLX_ERR_STATE, "detect_language before encode");
+    if (!lang_ids || n_lang < 1 || n_lang > 256 || !probs_out) return set_error(WLX_ERR_ARG, "bad language id list");
+    if (sot < 0 || sot >= e->spec.vocab) return set_error(WLX_ERR_ARG, "bad sot id");
+    for (int i = 0; i < n_lang; ++i) if (lang_ids[i] < 0 || lang_ids[i] >= e->spec.vocab) return set_error(WLX_ERR_ARG, "bad language id");
     CK(hipSetDevice(e->device));
     hipStream_t st = s->stream;
     // one decoder step on [sot] per item: row b -> cache row b*R (distinct per item)
@@ -2003,15 +1781,15 @@ extern "C" int32_t wlx_align(wlx_engine* e, int32_t slot, int32_t item, const in
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!tokens || !heads || !text_indices || !time_indices || !n_path_out || !text_token_probs) return fail(WLX_ERR_ARG, "null argument");
-    if (item < 0 || item >= s->enc_batch) return fail(WLX_ERR_STATE, "align: item %d not encoded", item);
-    if (n_sot < 1 || n_tokens < n_sot + 3 || n_tokens > WLX_T_TEXT) return fail(WLX_ERR_ARG, "align: %d tokens with a start sequence of %d", n_tokens, n_sot);
-    if (n_heads < 1 || n_heads > e->spec.dec_layers * e->H) return fail(WLX_ERR_ARG, "align: bad head count");
+    if (!tokens || !heads || !text_indices || !time_indices || !n_path_out || !text_token_probs) return set_error(WLX_ERR_ARG, "null argument");
+    if (item < 0 || item >= s->enc_batch) return set_error(WLX_ERR_STATE, "align: item %d not encoded", item);
+    if (n_sot < 1 || n_tokens < n_sot + 3 || n_tokens > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "align: %d tokens with a start sequence of %d", n_tokens, n_sot);
+    if (n_heads < 1 || n_heads > e->spec.dec_layers * e->H) return set_error(WLX_ERR_ARG, "align: bad head count");
     for (int i = 0; i < n_heads; ++i)
         if (heads[2 * i] < 0 || heads[2 * i] >= e->spec.dec_layers || heads[2 * i + 1] < 0 || heads[2 * i + 1] >= e->H)
-            return fail(WLX_ERR_ARG, "align: head (%d, %d) out of range", heads[2 * i], heads[2 * i + 1]);
-    for (int i = 0; i < n_tokens; ++i) if (tokens[i] < 0 || tokens[i] >= e->spec.vocab) return fail(WLX_ERR_ARG, "align: token out of vocabulary");
-    if (eot < 1 || eot > e->spec.vocab || median_filter_width < 1 || (median_filter_width & 1) == 0) return fail(WLX_ERR_ARG, "align: bad eot / filter width");
+            return set_error(WLX_ERR_ARG, "align: head (%d, %d) out of range", heads[2 * i], heads[2 * i + 1]);
+    for (int i = 0; i < n_tokens; ++i) if (tokens[i] < 0 || tokens[i] >= e->spec.vocab) return set_error(WLX_ERR_ARG, "align: token out of vocabulary");
+    if (eot < 1 || eot > e->spec.vocab || median_filter_width < 1 || (median_filter_width & 1) == 0) return set_error(WLX_ERR_ARG, "align: bad eot / filter width");
     int nf = num_frames / 2;
     if (nf < 1) nf = 1;
     if (nf > WLX_T_AUDIO) nf = WLX_T_AUDIO;
@@ -2023,7 +1801,7 @@ extern "C" int32_t wlx_align(wlx_engine* e, int32_t slot, int32_t item, const in
         CK(hipStreamSynchronize(st));
         if (s->align_scores) CK(hipFree(s->align_scores));
         s->align_scores = nullptr; s->align_cap = 0;
-        CK(hipMalloc(reinterpret_cast<void**>(&s->align_scores), need * sizeof(float)));
+        CK(hipMalloc(reinterpret_cast<void**>(&s->align_scores), need * sizeof(float)));   // grown on demand, the old one freed above: no free list
         s->align_cap = need;
     }
     const int crow = item * s->R;
@@ -2052,14 +1830,14 @@ extern "C" int32_t wlx_align(wlx_engine* e, int32_t slot, int32_t item, const in
         if (hipStreamSynchronize(st) != hipSuccess) { rc = WLX_ERR_HIP; break; }   // tgt / staging reuse
     }
     s->align = nullptr;
-    if (rc != WLX_OK) return fail(rc, "align: decoder pass failed");
+    if (rc != WLX_OK) return set_error(rc, "align: decoder pass failed");
     CK(hipGetLastError());
     std::vector<float> scores(need);
     CK(hipMemcpyAsync(scores.data(), s->align_scores, need * sizeof(float), hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
     std::vector<int32_t> ti, fi;
     align_postprocess(scores, n_heads, n_tokens, n_sot, nf, median_filter_width, ti, fi);
-    if ((int)ti.size() > path_cap) return fail(WLX_ERR_ARG, "align: path of %d steps exceeds the caller's capacity %d", (int)ti.size(), path_cap);
+    if ((int)ti.size() > path_cap) return set_error(WLX_ERR_ARG, "align: path of %d steps exceeds the caller's capacity %d", (int)ti.size(), path_cap);
     memcpy(text_indices, ti.data(), ti.size() * 4);
     memcpy(time_indices, fi.data(), fi.size() * 4);
     *n_path_out = (int32_t)ti.size();
@@ -2074,7 +1852,7 @@ extern "C" int32_t wlx_debug_logits_get(wlx_engine* e, int32_t slot, float* out,
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
     const int V = e->spec.vocab;
-    if (!out || rows < 1 || rows > s->rows_cap || (int64_t)rows * V > cap_floats) return fail(WLX_ERR_ARG, "bad rows/cap");
+    if (!out || rows < 1 || rows > s->rows_cap || (int64_t)rows * V > cap_floats) return set_error(WLX_ERR_ARG, "bad rows/cap");
     CK(hipSetDevice(e->device));
     CK(hipMemcpy2DAsync(out, (size_t)V * 4, s->logits, (size_t)s->ldl * 4, (size_t)V * 4, rows, hipMemcpyDeviceToHost, s->stream));
     CK(hipStreamSynchronize(s->stream));
@@ -2085,9 +1863,9 @@ extern "C" int32_t wlx_debug_decode_logits(wlx_engine* e, int32_t slot, const in
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!tokens || !out || n < 1 || n > WLX_T_TEXT) return fail(WLX_ERR_ARG, "bad tokens");
-    if (s->enc_batch < 1) return fail(WLX_ERR_STATE, "decode before encode");
-    for (int i = 0; i < n; ++i) if (tokens[i] < 0 || tokens[i] >= e->spec.vocab) return fail(WLX_ERR_ARG, "token out of vocabulary");
+    if (!tokens || !out || n < 1 || n > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "bad tokens");
+    if (s->enc_batch < 1) return set_error(WLX_ERR_STATE, "decode before encode");
+    for (int i = 0; i < n; ++i) if (tokens[i] < 0 || tokens[i] >= e->spec.vocab) return set_error(WLX_ERR_ARG, "token out of vocabulary");
     CK(hipSetDevice(e->device));
     std::vector<short> anc(WLX_T_TEXT, 0);   // cache row 0, identity ancestry
     CKR(set_anc_rows(s, anc, 0, 1));
@@ -2102,9 +1880,9 @@ extern "C" int32_t wlx_debug_time_decode_step(wlx_engine* e, int32_t slot, int32
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
     if (rows < 1 || rows > s->cache_rows || rows > s->rows_cap || t < 0 || t >= WLX_T_TEXT || iters < 1 || !avg_ms_out)
-        return fail(WLX_ERR_ARG, "bad arguments");
-    if (rows > 16 && (rows % s->R != 0 || rows / s->R > s->B)) return fail(WLX_ERR_ARG, "more than 16 rows: a multiple of the slot's rows per item");
-    if (s->enc_batch < 1) return fail(WLX_ERR_STATE, "decode before encode");
+        return set_error(WLX_ERR_ARG, "bad arguments");
+    if (rows > 16 && (rows % s->R != 0 || rows / s->R > s->B)) return set_error(WLX_ERR_ARG, "more than 16 rows: a multiple of the slot's rows per item");
+    if (s->enc_batch < 1) return set_error(WLX_ERR_STATE, "decode before encode");
     s->busy_variant = device_is_busy(s);     // (the launch shapes a step captured now would use)
     CK(hipSetDevice(e->device));
     hipStream_t st = s->stream;
@@ -2144,15 +1922,15 @@ extern "C" int32_t wlx_debug_trace_step(wlx_engine* e, int32_t slot, int32_t row
                                         uint64_t* out, int64_t cap_u64, char* names, int32_t* n_launches_out) {
 #ifndef WLX_TRACE
     (void)e; (void)slot; (void)rows; (void)t; (void)with_search; (void)out; (void)cap_u64; (void)names; (void)n_launches_out;
-    return fail(WLX_ERR_STATE, "libwlx.so was built without -DWLX_TRACE (use libwlx_trace.so, scripts/trace_step.py)");
+    return set_error(WLX_ERR_STATE, "libwlx.so was built without -DWLX_TRACE (use libwlx_trace.so, scripts/trace_step.py)");
 #else
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
     if (rows < 1 || rows > s->cache_rows || rows > s->rows_cap || t < 0 || t >= WLX_T_TEXT || !out || !names || !n_launches_out)
-        return fail(WLX_ERR_ARG, "bad arguments");
-    if (rows > 16 && (rows % s->R != 0 || rows / s->R > s->B)) return fail(WLX_ERR_ARG, "more than 16 rows: a multiple of the slot's rows per item");
-    if (s->enc_batch < 1) return fail(WLX_ERR_STATE, "decode before encode");
+        return set_error(WLX_ERR_ARG, "bad arguments");
+    if (rows > 16 && (rows % s->R != 0 || rows / s->R > s->B)) return set_error(WLX_ERR_ARG, "more than 16 rows: a multiple of the slot's rows per item");
+    if (s->enc_batch < 1) return set_error(WLX_ERR_STATE, "decode before encode");
     CK(hipSetDevice(e->device));
     hipStream_t st = s->stream;
     const int tR = rows > 16 ? s->R : rows, tG = rows / tR;
@@ -2162,7 +1940,7 @@ extern "C" int32_t wlx_debug_trace_step(wlx_engine* e, int32_t slot, int32_t row
     for (int r = 0; r < rows; ++r) { ca[r] = an[r] = r; for (int p = 0; p < WLX_T_TEXT; ++p) anc[(size_t)r * WLX_T_TEXT + p] = (short)r; }
     const size_t max_launch = 320;
     unsigned long long* buf = nullptr;
-    CK(hipMalloc(&buf, max_launch * WLX_TR_STRIDE * 8));
+    CK(hipMalloc(&buf, max_launch * WLX_TR_STRIDE * 8));       // lives for this call only, freed on its way out
     g_trace_buf = buf; g_trace_seq = 0;
     hipGraph_t graph; hipGraphExec_t exec;
     auto reset_state = [&]() -> int {
@@ -2186,7 +1964,7 @@ extern "C" int32_t wlx_debug_trace_step(wlx_engine* e, int32_t slot, int32_t row
     CK(hipGraphDestroy(graph));
     const int n = g_trace_seq;
     g_trace_buf = nullptr;
-    if (n > (int)max_launch) { (void)hipGraphExecDestroy(exec); (void)hipFree(buf); return fail(WLX_ERR_ARG, "trace: %d launches exceed the trace buffer (%d)", n, (int)max_launch); }
+    if (n > (int)max_launch) { (void)hipGraphExecDestroy(exec); (void)hipFree(buf); return set_error(WLX_ERR_ARG, "trace: %d launches exceed the trace buffer (%d)", n, (int)max_launch); }
     for (int i = 0; i < 3; ++i) { CKR(reset_state()); CK(hipGraphLaunch(exec, st)); }
     CKR(reset_state());
     CK(hipMemsetAsync(buf, 0, max_launch * WLX_TR_STRIDE * 8, st));
@@ -2194,7 +1972,7 @@ extern "C" int32_t wlx_debug_trace_step(wlx_engine* e, int32_t slot, int32_t row
     CK(hipGraphLaunch(exec, st));
     CK(hipStreamSynchronize(st));
     CK(hipGraphExecDestroy(exec));
-    if ((int64_t)n * WLX_TR_STRIDE > cap_u64) { (void)hipFree(buf); return fail(WLX_ERR_ARG, "trace buffer too small"); }
+    if ((int64_t)n * WLX_TR_STRIDE > cap_u64) { (void)hipFree(buf); return set_error(WLX_ERR_ARG, "trace buffer too small"); }
     CK(hipMemcpyAsync(out, buf, (size_t)n * WLX_TR_STRIDE * 8, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
     CK(hipFree(buf));
@@ -2210,9 +1988,9 @@ extern "C" int32_t wlx_debug_profile_step(wlx_engine* e, int32_t slot, int32_t r
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
     if (rows < 1 || rows > s->cache_rows || rows > s->rows_cap || t < 0 || t >= WLX_T_TEXT || iters < 1 || !out || !n_out || cap < 1)
-        return fail(WLX_ERR_ARG, "bad arguments");
-    if (rows > 16 && (rows % s->R != 0 || rows / s->R > s->B)) return fail(WLX_ERR_ARG, "more than 16 rows: a multiple of the slot's rows per item");
-    if (s->enc_batch < 1) return fail(WLX_ERR_STATE, "decode before encode");
+        return set_error(WLX_ERR_ARG, "bad arguments");
+    if (rows > 16 && (rows % s->R != 0 || rows / s->R > s->B)) return set_error(WLX_ERR_ARG, "more than 16 rows: a multiple of the slot's rows per item");
+    if (s->enc_batch < 1) return set_error(WLX_ERR_STATE, "decode before encode");
     s->busy_variant = device_is_busy(s);     // (the launch shapes a step captured now would use)
     CK(hipSetDevice(e->device));
     hipStream_t st = s->stream;
@@ -2258,7 +2036,7 @@ extern "C" int32_t wlx_debug_profile_step(wlx_engine* e, int32_t slot, int32_t r
         kv.second.us = 1000.0 * ms / iters;                                       // all launches of this kernel in one step
     }
     s->prof = nullptr;
-    if (rc != WLX_OK) return fail(rc, "profile capture failed");
+    if (rc != WLX_OK) return set_error(rc, "profile capture failed");
     CK(hipGetLastError());
     int n = 0;
     for (auto& kv : agg) {

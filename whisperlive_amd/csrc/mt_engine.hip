@@ -7,7 +7,8 @@
 // LayerNorm and the tied vocabulary projection in fp32, followed by the two-stage log-softmax + top-k kernels of mt.hip. The
 // candidates (2 x num_beams per row) come back to the host, where Hugging Face's beam-search bookkeeping (generation/utils.py
 // _beam_search of transformers 5.x: length normaliser, early_stopping heuristics, forced EOS, no_repeat_ngram) runs in a few
-// microseconds per step. All projections use the MFMA GEMM of gemm.hip; nothing is captured into a graph.
+// microseconds per step. All projections use the MFMA GEMM of gemm.hip; nothing is captured into a graph. Error macros, allocation
+// and weight ingestion (the layer loader included) are the shared host layer of host.h.
 #include <math.h>
 #include <string.h>
 
@@ -23,25 +24,7 @@
 
 using namespace wlx;
 
-#define MCK(call)                                                                                                 \
-    do {                                                                                                          \
-        hipError_t e_ = (call);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return set_error(WLX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define MCKR(call)                   \
-    do {                             \
-        int r_ = (call);             \
-        if (r_ != WLX_OK) return r_; \
-    } while (0)
-
 namespace {
-
-struct MtLayer {
-    float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr, *ln3_g = nullptr, *ln3_b = nullptr;
-    half_t *Wqkv = nullptr, *Wo = nullptr, *Wcq = nullptr, *Wco = nullptr, *W1 = nullptr, *W2 = nullptr;
-    float *bqkv = nullptr, *bo = nullptr, *bcq = nullptr, *bco = nullptr, *b1 = nullptr, *b2 = nullptr;
-};
 
 struct MtSlot {
     std::atomic<bool> busy{false};
@@ -79,7 +62,7 @@ struct MtSlot {
 struct wlx_mt {
     wlx_mt_spec spec{};
     int device = 0;
-    std::vector<MtLayer> enc, dec;
+    std::vector<LayerW> enc, dec;
     float *enc_ln_g = nullptr, *enc_ln_b = nullptr, *dec_ln_g = nullptr, *dec_ln_b = nullptr;
     half_t* E = nullptr;          // shared embedding, packed (vocab x d): token rows for the embedding, the tied output projection
     half_t* Wckv = nullptr;       // cross k / v of every decoder layer: [L * 2d][d] packed
@@ -93,89 +76,6 @@ struct wlx_mt {
 };
 
 namespace {
-
-template <class T>
-int dalloc(std::vector<void*>& list, T** p, size_t n) {
-    void* q = nullptr;
-    MCK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    list.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return WLX_OK;
-}
-template <class T>
-int halloc(std::vector<void*>& list, T** p, size_t n) {
-    void* q = nullptr;
-    MCK(hipHostMalloc(&q, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault));
-    list.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return WLX_OK;
-}
-
-__global__ void mt_scale_kernel(float* x, long n, float a) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] *= a;
-}
-
-struct Loader {
-    const wlx_tensor* w;
-    int n;
-    hipStream_t st;
-    // ONE fp32 staging buffer for the matrices, grown to the largest one: a pack kernel reads it on `st`, and the next copy into
-    // it is queued behind that kernel on the same stream, so it is reused without a wait (a full fp32 copy of small100 is ~1.3 GB)
-    float* stage = nullptr;
-    size_t stage_bytes = 0;
-    ~Loader() {
-        if (stage) (void)hipFree(stage);
-    }
-    const wlx_tensor* find(const std::string& name) const {
-        for (int i = 0; i < n; ++i)
-            if (w[i].name && name == w[i].name) return &w[i];
-        return nullptr;
-    }
-    // fp32 device copy of tensor `name` of shape [r] (c == 0) or [r][c]; `dst` may be given (then the copy goes there)
-    int get(const std::string& name, long r, long c, float** out, float* dst = nullptr) {
-        const wlx_tensor* t = find(name);
-        if (!t) return set_error(WLX_ERR_WEIGHT, "missing weight %s", name.c_str());
-        const bool ok = c == 0 ? (t->ndim == 1 && t->shape[0] == r) : (t->ndim == 2 && t->shape[0] == r && t->shape[1] == c);
-        if (!ok) return set_error(WLX_ERR_WEIGHT, "weight %s: expected shape [%ld%s%ld]", name.c_str(), r, c ? ", " : "", c ? c : 0L);
-        const size_t bytes = (size_t)r * (c ? c : 1) * sizeof(float);
-        if (!dst) {
-            if (bytes > stage_bytes) {
-                MCK(hipStreamSynchronize(st));            // (the kernels still reading the old buffer)
-                if (stage) MCK(hipFree(stage));
-                stage = nullptr;
-                stage_bytes = 0;
-                MCK(hipMalloc((void**)&stage, bytes));
-                stage_bytes = bytes;
-            }
-            dst = stage;
-        }
-        MCK(hipMemcpyAsync(dst, t->data, bytes, t->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        MCK(hipStreamSynchronize(st));      // (host tensors may be pageable temporaries of the caller)
-        *out = dst;
-        return WLX_OK;
-    }
-};
-
-int pack(Loader& L, const std::string& name, int N, int K, half_t* Wp, int KT, int nt0, float scale = 1.f) {
-    float* w = nullptr;
-    MCKR(L.get(name, N, K, &w));
-    if (scale != 1.f) hipLaunchKernelGGL(mt_scale_kernel, dim3((unsigned)(((long)N * K + 255) / 256)), dim3(256), 0, L.st, w, (long)N * K, scale);
-    launch_pack_linear(w, N, K, K, Wp, KT, nt0, L.st);
-    MCK(hipGetLastError());
-    return WLX_OK;
-}
-int vec(Loader& L, std::vector<void*>& allocs, const std::string& name, int n, float** out) {
-    MCKR(dalloc(allocs, out, n));
-    float* p = nullptr;
-    return L.get(name, n, 0, &p, *out);
-}
-int vec_into(Loader& L, const std::string& name, int n, float* dst, float scale = 1.f) {
-    float* p = nullptr;
-    MCKR(L.get(name, n, 0, &p, dst));
-    if (scale != 1.f) hipLaunchKernelGGL(mt_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, L.st, dst, (long)n, scale);
-    return WLX_OK;
-}
 
 // C = A W^T + b (fp16 out) or X += A W^T + b (fp32): the encoder GEMM of gemm.hip
 void gemm(const half_t* A, long lda, int M, const half_t* Wp, int K, int N, const float* bias, int mode, half_t* C, long ldc,
@@ -229,12 +129,12 @@ int encode(wlx_mt* m, MtSlot* s, int batch, const int32_t* src, const int32_t* l
     s->n_items = batch;
     s->n_src = n;
     hipStream_t st = s->st;
-    MCK(hipEventRecord(s->ev[0], st));
-    MCK(hipMemcpyAsync(s->d_src_tok, s->h_src_tok, n * sizeof(int), hipMemcpyHostToDevice, st));
-    MCK(hipMemcpyAsync(s->d_src_pos, s->h_src_pos, n * sizeof(int), hipMemcpyHostToDevice, st));
-    MCK(hipMemcpyAsync(s->d_genc, s->h_genc, ng * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
+    CK(hipEventRecord(s->ev[0], st));
+    CK(hipMemcpyAsync(s->d_src_tok, s->h_src_tok, n * sizeof(int), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_src_pos, s->h_src_pos, n * sizeof(int), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_genc, s->h_genc, ng * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
     launch_mt_embed(s->d_src_tok, s->d_src_pos, n, m->E, d / 32, m->embed_scale, m->sinpos, d, s->xe, st);
-    for (const MtLayer& w : m->enc) {
+    for (const LayerW& w : m->enc) {
         launch_layernorm_f16(s->xe, d, w.ln1_g, w.ln1_b, s->he, d, n, d, st);
         gemm(s->he, d, n, w.Wqkv, d, 3 * d, w.bqkv, GEMM_STORE_F16, s->qkve, 3 * d, nullptr, 0, st);
         launch_mt_attn(s->qkve, 3 * d, s->qkve + d, 3 * d, s->qkve + 2 * d, 3 * d, s->atte, d, s->d_genc, ng, 16, H, nullptr, 0, 0, st);
@@ -246,8 +146,8 @@ int encode(wlx_mt* m, MtSlot* s, int batch, const int32_t* src, const int32_t* l
     }
     launch_layernorm_f16_f32(s->xe, d, m->enc_ln_g, m->enc_ln_b, s->he, s->enc32, d, n, d, st);
     gemm(s->he, d, n, m->Wckv, d, 2 * d * Ld, m->bckv, GEMM_STORE_F16, s->ckv, 2L * d * Ld, nullptr, 0, st);
-    MCK(hipGetLastError());
-    MCK(hipEventRecord(s->ev[1], st));
+    CK(hipGetLastError());
+    CK(hipEventRecord(s->ev[1], st));
     return WLX_OK;
 }
 
@@ -259,15 +159,15 @@ int decode_step(wlx_mt* m, MtSlot* s, int rows, int R, int t) {
     hipStream_t st = s->st;
     for (int r = 0; r < rows; ++r) s->h_gself[r] = MtAttnGroup{r, 1, 0, t + 1};
     for (int i = 0; i < s->n_items; ++i) s->h_gcross[i] = MtAttnGroup{i * R, R, s->src_off[i], s->src_len[i]};
-    MCK(hipMemcpyAsync(s->d_tok, s->h_tok, rows * sizeof(int), hipMemcpyHostToDevice, st));
-    MCK(hipMemcpyAsync(s->d_pos, s->h_pos, rows * sizeof(int), hipMemcpyHostToDevice, st));
-    MCK(hipMemcpyAsync(s->d_anc, s->h_anc, (size_t)rows * T * sizeof(int), hipMemcpyHostToDevice, st));
-    MCK(hipMemcpyAsync(s->d_gself, s->h_gself, rows * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
-    MCK(hipMemcpyAsync(s->d_gcross, s->h_gcross, s->n_items * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_tok, s->h_tok, rows * sizeof(int), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_pos, s->h_pos, rows * sizeof(int), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_anc, s->h_anc, (size_t)rows * T * sizeof(int), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_gself, s->h_gself, rows * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_gcross, s->h_gcross, s->n_items * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
     launch_mt_embed(s->d_tok, s->d_pos, rows, m->E, d / 32, m->embed_scale, m->sinpos, d, s->xd, st);
     const long cache_layer = (long)s->rows_cap * T * d;
     for (int l = 0; l < Ld; ++l) {
-        const MtLayer& w = m->dec[l];
+        const LayerW& w = m->dec[l];
         half_t* kc = s->kc + l * cache_layer;
         half_t* vc = s->vc + l * cache_layer;
         launch_layernorm_f16(s->xd, d, w.ln1_g, w.ln1_b, s->hd, d, rows, d, st);
@@ -287,9 +187,9 @@ int decode_step(wlx_mt* m, MtSlot* s, int rows, int R, int t) {
         gemm(s->ffd, F, rows, w.W2, F, d, w.b2, GEMM_RESID_F32, nullptr, 0, s->xd, d, st);
     }
     launch_layernorm_f16(s->xd, d, m->dec_ln_g, m->dec_ln_b, s->hd, d, rows, d, st);
-    MCK(hipMemsetAsync(s->logits, 0, (size_t)rows * sp.vocab * sizeof(float), st));
+    CK(hipMemsetAsync(s->logits, 0, (size_t)rows * sp.vocab * sizeof(float), st));
     gemm(s->hd, d, rows, m->E, d, sp.vocab, nullptr, GEMM_RESID_F32, nullptr, 0, s->logits, sp.vocab, st);
-    MCK(hipGetLastError());
+    CK(hipGetLastError());
     return WLX_OK;
 }
 
@@ -297,15 +197,15 @@ int decode_step(wlx_mt* m, MtSlot* s, int rows, int R, int t) {
 int fetch_topk(wlx_mt* m, MtSlot* s, int rows, int k, bool with_bans) {
     hipStream_t st = s->st;
     if (with_bans) {
-        MCK(hipMemcpyAsync(s->d_nban, s->h_nban, rows * sizeof(int), hipMemcpyHostToDevice, st));
-        MCK(hipMemcpyAsync(s->d_ban, s->h_ban, (size_t)rows * s->ban_ld * sizeof(int), hipMemcpyHostToDevice, st));
+        CK(hipMemcpyAsync(s->d_nban, s->h_nban, rows * sizeof(int), hipMemcpyHostToDevice, st));
+        CK(hipMemcpyAsync(s->d_ban, s->h_ban, (size_t)rows * s->ban_ld * sizeof(int), hipMemcpyHostToDevice, st));
     }
     launch_mt_topk(s->logits, rows, m->spec.vocab, with_bans ? s->d_ban : nullptr, with_bans ? s->d_nban : nullptr, s->ban_ld, k,
                    s->tk_scratch, s->tk_cidx, s->tk_val, s->tk_idx, st);
-    MCK(hipGetLastError());
-    MCK(hipMemcpyAsync(s->h_tk_val, s->tk_val, (size_t)rows * k * sizeof(float), hipMemcpyDeviceToHost, st));
-    MCK(hipMemcpyAsync(s->h_tk_idx, s->tk_idx, (size_t)rows * k * sizeof(int), hipMemcpyDeviceToHost, st));
-    MCK(hipStreamSynchronize(st));
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(s->h_tk_val, s->tk_val, (size_t)rows * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(s->h_tk_idx, s->tk_idx, (size_t)rows * k * sizeof(int), hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
     return WLX_OK;
 }
 
@@ -344,7 +244,7 @@ int run_generate(wlx_mt* m, MtSlot* s, const wlx_mt_gen_opts& o, int32_t* tokens
         for (int j = 0; j < T; ++j) s->h_anc[(long)r * T + j] = r;
     int cur_len = 1;
     s->steps = 0;
-    MCK(hipEventRecord(s->ev[2], s->st));
+    CK(hipEventRecord(s->ev[2], s->st));
     std::vector<int> ban;
     while (true) {
         const int t = cur_len - 1;                 // position of the token fed in this step
@@ -355,7 +255,7 @@ int run_generate(wlx_mt* m, MtSlot* s, const wlx_mt_gen_opts& o, int32_t* tokens
                 s->h_anc[(long)r * T + t] = r;
                 s->h_pos[r] = position_of(run[r * ML + t], 1, t, pad);
             }
-            MCKR(decode_step(m, s, rows, R, t));
+            CKR(decode_step(m, s, rows, R, t));
             bool any_ban = false;
             for (int r = 0; r < rows; ++r) {
                 banned_ngrams(&run[r * ML], cur_len, nng, ban);
@@ -364,7 +264,7 @@ int run_generate(wlx_mt* m, MtSlot* s, const wlx_mt_gen_opts& o, int32_t* tokens
                 for (int j = 0; j < nb; ++j) s->h_ban[(long)r * s->ban_ld + j] = ban[j];
                 any_ban |= nb > 0;
             }
-            MCKR(fetch_topk(m, s, rows, K, any_ban));
+            CKR(fetch_topk(m, s, rows, K, any_ban));
             s->steps++;
         }
         if (R == 1) {   // greedy (HF _sample with do_sample = False)
@@ -489,7 +389,7 @@ int run_generate(wlx_mt* m, MtSlot* s, const wlx_mt_gen_opts& o, int32_t* tokens
         if (!(any_unsat && open && !all_hit)) break;
         if (cur_len >= ML) break;
     }
-    MCK(hipEventRecord(s->ev[3], s->st));
+    CK(hipEventRecord(s->ev[3], s->st));
     // outputs: generated tokens after the decoder start, the final EOS excluded
     for (int b = 0; b < B; ++b) {
         const int* seq;
@@ -523,81 +423,35 @@ extern "C" int32_t wlx_mt_create(const wlx_mt_spec* spec, const wlx_tensor* w, i
     if (sp.max_positions < 1 || sp.pad_id < 0 || sp.eos_id < 0 || sp.decoder_start_id < 0 || sp.pad_id >= sp.vocab ||
         sp.eos_id >= sp.vocab || sp.decoder_start_id >= sp.vocab)
         return set_error(WLX_ERR_ARG, "bad special ids / max_positions");
-    MCK(hipSetDevice(device));
-    MCK((hipError_t)gemm_prepare_device());
+    CK(hipSetDevice(device));
+    CK((hipError_t)gemm_prepare_device());
     wlx_mt* m = new wlx_mt();
     m->spec = sp;
     m->device = device;
     m->embed_scale = sp.scale_embedding ? sqrtf((float)sp.d_model) : 1.f;
-    hipStream_t st = nullptr;
     int rc = [&]() -> int {
-        MCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        Loader L{w, n, st};
-        const int d = sp.d_model, F = sp.ffn, KTd = d / 32, KTf = F / 32;
-        const float qs = 0.125f;     // head_dim ** -0.5, applied after the bias (folded into q_proj's weight and bias)
-        auto attn_ln = [&](const std::string& pre, float** g, float** b) -> int {
-            MCKR(vec(L, m->allocs, pre + ".weight", d, g));
-            return vec(L, m->allocs, pre + ".bias", d, b);
-        };
-        auto qkv = [&](const std::string& pre, MtLayer& y) -> int {
-            MCKR(dalloc(m->allocs, &y.Wqkv, (size_t)3 * d * d));
-            MCKR(pack(L, pre + ".q_proj.weight", d, d, y.Wqkv, KTd, 0, qs));
-            MCKR(pack(L, pre + ".k_proj.weight", d, d, y.Wqkv, KTd, d / 16));
-            MCKR(pack(L, pre + ".v_proj.weight", d, d, y.Wqkv, KTd, 2 * d / 16));
-            MCKR(dalloc(m->allocs, &y.bqkv, 3 * d));
-            MCKR(vec_into(L, pre + ".q_proj.bias", d, y.bqkv, qs));
-            MCKR(vec_into(L, pre + ".k_proj.bias", d, y.bqkv + d));
-            MCKR(vec_into(L, pre + ".v_proj.bias", d, y.bqkv + 2 * d));
-            MCKR(dalloc(m->allocs, &y.Wo, (size_t)d * d));
-            MCKR(pack(L, pre + ".out_proj.weight", d, d, y.Wo, KTd, 0));
-            return vec(L, m->allocs, pre + ".out_proj.bias", d, &y.bo);
-        };
-        auto mlp = [&](const std::string& pre, MtLayer& y) -> int {
-            MCKR(dalloc(m->allocs, &y.W1, (size_t)F * d));
-            MCKR(pack(L, pre + ".fc1.weight", F, d, y.W1, KTd, 0));
-            MCKR(vec(L, m->allocs, pre + ".fc1.bias", F, &y.b1));
-            MCKR(dalloc(m->allocs, &y.W2, (size_t)d * F));
-            MCKR(pack(L, pre + ".fc2.weight", d, F, y.W2, KTf, 0));
-            return vec(L, m->allocs, pre + ".fc2.bias", d, &y.b2);
-        };
-        const long NTv = sp.vocab / 16;
-        MCKR(dalloc(m->allocs, &m->E, (size_t)NTv * 16 * d));
-        MCKR(pack(L, "model.shared.weight", sp.vocab, d, m->E, KTd, 0));
+        Weights ws;
+        CKR(ws.open(w, n));
+        std::vector<void*>& A = m->allocs;      // (none of this engine's allocations is zeroed: every element is written below)
+        const int d = sp.d_model, F = sp.ffn, Ld = sp.dec_layers;
+        int KT;
+        CKR(alloc_packed(A, sp.vocab, d, &m->E, &KT, false));
+        CKR(ws.pack("model.shared.weight", sp.vocab, d, m->E, KT, 0));
+        // head_dim ** -0.5 is applied after the bias: folded into q_proj's weight and bias
+        LayerOpts o{/*k_bias=*/true, /*q_scale=*/0.125f, /*zero=*/false};
         m->enc.resize(sp.enc_layers);
-        for (int l = 0; l < sp.enc_layers; ++l) {
-            const std::string pre = "model.encoder.layers." + std::to_string(l);
-            MtLayer& y = m->enc[l];
-            MCKR(attn_ln(pre + ".self_attn_layer_norm", &y.ln1_g, &y.ln1_b));
-            MCKR(attn_ln(pre + ".final_layer_norm", &y.ln3_g, &y.ln3_b));
-            MCKR(qkv(pre + ".self_attn", y));
-            MCKR(mlp(pre, y));
-        }
-        MCKR(attn_ln("model.encoder.layer_norm", &m->enc_ln_g, &m->enc_ln_b));
-        const int Ld = sp.dec_layers;
-        MCKR(dalloc(m->allocs, &m->Wckv, (size_t)2 * Ld * d * d));
-        MCKR(dalloc(m->allocs, &m->bckv, (size_t)2 * Ld * d));
+        for (int l = 0; l < sp.enc_layers; ++l)
+            CKR(load_layer(ws, A, "model.encoder.layers." + std::to_string(l) + ".", d, F, o, m->enc[l]));
+        CKR(ws.alloc_vec(A, "model.encoder.layer_norm.weight", d, &m->enc_ln_g, false));
+        CKR(ws.alloc_vec(A, "model.encoder.layer_norm.bias", d, &m->enc_ln_b, false));
+        CKR(alloc_packed(A, 2L * Ld * d, d, &m->Wckv, nullptr, false));
+        CKR(dalloc(A, &m->bckv, (size_t)2 * Ld * d, false));
+        o.Wckv = m->Wckv; o.bckv = m->bckv;
         m->dec.resize(Ld);
-        for (int l = 0; l < Ld; ++l) {
-            const std::string pre = "model.decoder.layers." + std::to_string(l);
-            MtLayer& y = m->dec[l];
-            MCKR(attn_ln(pre + ".self_attn_layer_norm", &y.ln1_g, &y.ln1_b));
-            MCKR(attn_ln(pre + ".encoder_attn_layer_norm", &y.ln2_g, &y.ln2_b));
-            MCKR(attn_ln(pre + ".final_layer_norm", &y.ln3_g, &y.ln3_b));
-            MCKR(qkv(pre + ".self_attn", y));
-            MCKR(dalloc(m->allocs, &y.Wcq, (size_t)d * d));
-            MCKR(pack(L, pre + ".encoder_attn.q_proj.weight", d, d, y.Wcq, KTd, 0, qs));
-            MCKR(dalloc(m->allocs, &y.bcq, d));
-            MCKR(vec_into(L, pre + ".encoder_attn.q_proj.bias", d, y.bcq, qs));
-            MCKR(pack(L, pre + ".encoder_attn.k_proj.weight", d, d, m->Wckv, KTd, (2 * l) * d / 16));
-            MCKR(pack(L, pre + ".encoder_attn.v_proj.weight", d, d, m->Wckv, KTd, (2 * l + 1) * d / 16));
-            MCKR(vec_into(L, pre + ".encoder_attn.k_proj.bias", d, m->bckv + 2L * l * d));
-            MCKR(vec_into(L, pre + ".encoder_attn.v_proj.bias", d, m->bckv + (2L * l + 1) * d));
-            MCKR(dalloc(m->allocs, &y.Wco, (size_t)d * d));
-            MCKR(pack(L, pre + ".encoder_attn.out_proj.weight", d, d, y.Wco, KTd, 0));
-            MCKR(vec(L, m->allocs, pre + ".encoder_attn.out_proj.bias", d, &y.bco));
-            MCKR(mlp(pre, y));
-        }
-        MCKR(attn_ln("model.decoder.layer_norm", &m->dec_ln_g, &m->dec_ln_b));
+        for (o.l = 0; o.l < Ld; ++o.l)
+            CKR(load_layer(ws, A, "model.decoder.layers." + std::to_string(o.l) + ".", d, F, o, m->dec[o.l]));
+        CKR(ws.alloc_vec(A, "model.decoder.layer_norm.weight", d, &m->dec_ln_g, false));
+        CKR(ws.alloc_vec(A, "model.decoder.layer_norm.bias", d, &m->dec_ln_b, false));
         // M2M100SinusoidalPositionalEmbedding.get_embedding, in fp32 as torch computes it
         const int npos = sp.max_positions + 2, half = d / 2;
         std::vector<float> sp_h((size_t)npos * d, 0.f);
@@ -610,12 +464,10 @@ extern "C" int32_t wlx_mt_create(const wlx_mt_spec* spec, const wlx_tensor* w, i
                 sp_h[(size_t)p * d + half + i] = cosf(a);
             }
         }
-        MCKR(dalloc(m->allocs, &m->sinpos, sp_h.size()));
-        MCK(hipMemcpyAsync(m->sinpos, sp_h.data(), sp_h.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        MCK(hipStreamSynchronize(st));
-        return WLX_OK;
+        CKR(dalloc(A, &m->sinpos, sp_h.size(), false));
+        CK(hipMemcpyAsync(m->sinpos, sp_h.data(), sp_h.size() * sizeof(float), hipMemcpyHostToDevice, ws.st));
+        return ws.finish();
     }();
-    if (st) (void)hipStreamDestroy(st);
     if (rc != WLX_OK) {
         for (void* p : m->allocs) (void)hipFree(p);
         delete m;
@@ -649,7 +501,7 @@ extern "C" int32_t wlx_mt_slot_create(wlx_mt* m, int32_t max_batch, int32_t max_
     if (max_rows_per_item < 1 || max_rows_per_item > 16) return set_error(WLX_ERR_ARG, "max_rows_per_item %d outside 1..16", max_rows_per_item);
     if (max_src < 1 || max_src > WLX_MT_MAX_SRC || max_src > sp.max_positions)
         return set_error(WLX_ERR_ARG, "max_src %d outside 1..%d", max_src, std::min(WLX_MT_MAX_SRC, sp.max_positions));
-    MCK(hipSetDevice(m->device));
+    CK(hipSetDevice(m->device));
     const int d = sp.d_model, F = sp.ffn, Ld = sp.dec_layers, B = max_batch, R = max_rows_per_item, T = WLX_T_TEXT;
     const long rows = (long)B * R, src = (long)B * max_src;
     const int ban_ld = T;
@@ -667,52 +519,52 @@ extern "C" int32_t wlx_mt_slot_create(wlx_mt* m, int32_t max_batch, int32_t max_
     MtSlot* s = new MtSlot();
     s->B = B; s->R = R; s->max_src = max_src; s->rows_cap = (int)rows; s->src_cap = (int)src; s->ban_ld = ban_ld;
     int rc = [&]() -> int {
-        MCK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-        for (auto& e : s->ev) MCK(hipEventCreate(&e));
-        auto& A = s->allocs;
-        MCKR(dalloc(A, &s->xe, src * d));
-        MCKR(dalloc(A, &s->enc32, src * d));
-        MCKR(dalloc(A, &s->he, src * d));
-        MCKR(dalloc(A, &s->qkve, src * 3 * d));
-        MCKR(dalloc(A, &s->atte, src * d));
-        MCKR(dalloc(A, &s->ffe, src * F));
-        MCKR(dalloc(A, &s->ckv, src * 2 * d * Ld));
-        MCKR(dalloc(A, &s->xd, rows * d));
-        MCKR(dalloc(A, &s->hd, rows * d));
-        MCKR(dalloc(A, &s->qkvd, rows * 3 * d));
-        MCKR(dalloc(A, &s->qd, rows * d));
-        MCKR(dalloc(A, &s->attd, rows * d));
-        MCKR(dalloc(A, &s->ffd, rows * F));
-        MCKR(dalloc(A, &s->kc, (size_t)Ld * rows * T * d));
-        MCKR(dalloc(A, &s->vc, (size_t)Ld * rows * T * d));
-        MCKR(dalloc(A, &s->logits, rows * sp.vocab));
-        MCKR(dalloc(A, &s->tk_scratch, rows * WLX_MT_CHUNKS * (2 + WLX_MT_MAXK)));
-        MCKR(dalloc(A, &s->tk_cidx, rows * WLX_MT_CHUNKS * WLX_MT_MAXK));
-        MCKR(dalloc(A, &s->tk_val, rows * WLX_MT_MAXK));
-        MCKR(dalloc(A, &s->tk_idx, rows * WLX_MT_MAXK));
-        MCKR(dalloc(A, &s->d_tok, rows));
-        MCKR(dalloc(A, &s->d_pos, rows));
-        MCKR(dalloc(A, &s->d_src_tok, src));
-        MCKR(dalloc(A, &s->d_src_pos, src));
-        MCKR(dalloc(A, &s->d_anc, rows * T));
-        MCKR(dalloc(A, &s->d_ban, rows * ban_ld));
-        MCKR(dalloc(A, &s->d_nban, rows));
-        MCKR(dalloc(A, &s->d_genc, src));
-        MCKR(dalloc(A, &s->d_gself, rows));
-        MCKR(dalloc(A, &s->d_gcross, B));
+        CK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+        for (auto& e : s->ev) CK(hipEventCreate(&e));
+        auto& A = s->allocs;      // (not zeroed: the K / V caches alone are L x rows x 448 x d halfs)
+        CKR(dalloc(A, &s->xe, src * d, false));
+        CKR(dalloc(A, &s->enc32, src * d, false));
+        CKR(dalloc(A, &s->he, src * d, false));
+        CKR(dalloc(A, &s->qkve, src * 3 * d, false));
+        CKR(dalloc(A, &s->atte, src * d, false));
+        CKR(dalloc(A, &s->ffe, src * F, false));
+        CKR(dalloc(A, &s->ckv, src * 2 * d * Ld, false));
+        CKR(dalloc(A, &s->xd, rows * d, false));
+        CKR(dalloc(A, &s->hd, rows * d, false));
+        CKR(dalloc(A, &s->qkvd, rows * 3 * d, false));
+        CKR(dalloc(A, &s->qd, rows * d, false));
+        CKR(dalloc(A, &s->attd, rows * d, false));
+        CKR(dalloc(A, &s->ffd, rows * F, false));
+        CKR(dalloc(A, &s->kc, (size_t)Ld * rows * T * d, false));
+        CKR(dalloc(A, &s->vc, (size_t)Ld * rows * T * d, false));
+        CKR(dalloc(A, &s->logits, rows * sp.vocab, false));
+        CKR(dalloc(A, &s->tk_scratch, rows * WLX_MT_CHUNKS * (2 + WLX_MT_MAXK), false));
+        CKR(dalloc(A, &s->tk_cidx, rows * WLX_MT_CHUNKS * WLX_MT_MAXK, false));
+        CKR(dalloc(A, &s->tk_val, rows * WLX_MT_MAXK, false));
+        CKR(dalloc(A, &s->tk_idx, rows * WLX_MT_MAXK, false));
+        CKR(dalloc(A, &s->d_tok, rows, false));
+        CKR(dalloc(A, &s->d_pos, rows, false));
+        CKR(dalloc(A, &s->d_src_tok, src, false));
+        CKR(dalloc(A, &s->d_src_pos, src, false));
+        CKR(dalloc(A, &s->d_anc, rows * T, false));
+        CKR(dalloc(A, &s->d_ban, rows * ban_ld, false));
+        CKR(dalloc(A, &s->d_nban, rows, false));
+        CKR(dalloc(A, &s->d_genc, src, false));
+        CKR(dalloc(A, &s->d_gself, rows, false));
+        CKR(dalloc(A, &s->d_gcross, B, false));
         auto& H = s->host_allocs;
-        MCKR(halloc(H, &s->h_tok, rows));
-        MCKR(halloc(H, &s->h_pos, rows));
-        MCKR(halloc(H, &s->h_src_tok, src));
-        MCKR(halloc(H, &s->h_src_pos, src));
-        MCKR(halloc(H, &s->h_anc, rows * T));
-        MCKR(halloc(H, &s->h_ban, rows * ban_ld));
-        MCKR(halloc(H, &s->h_nban, rows));
-        MCKR(halloc(H, &s->h_tk_idx, rows * WLX_MT_MAXK));
-        MCKR(halloc(H, &s->h_tk_val, rows * WLX_MT_MAXK));
-        MCKR(halloc(H, &s->h_genc, src));
-        MCKR(halloc(H, &s->h_gself, rows));
-        MCKR(halloc(H, &s->h_gcross, B));
+        CKR(halloc(H, &s->h_tok, rows));
+        CKR(halloc(H, &s->h_pos, rows));
+        CKR(halloc(H, &s->h_src_tok, src));
+        CKR(halloc(H, &s->h_src_pos, src));
+        CKR(halloc(H, &s->h_anc, rows * T));
+        CKR(halloc(H, &s->h_ban, rows * ban_ld));
+        CKR(halloc(H, &s->h_nban, rows));
+        CKR(halloc(H, &s->h_tk_idx, rows * WLX_MT_MAXK));
+        CKR(halloc(H, &s->h_tk_val, rows * WLX_MT_MAXK));
+        CKR(halloc(H, &s->h_genc, src));
+        CKR(halloc(H, &s->h_gself, rows));
+        CKR(halloc(H, &s->h_gcross, B));
         return WLX_OK;
     }();
     if (rc != WLX_OK) {
@@ -763,11 +615,11 @@ extern "C" int32_t wlx_mt_translate(wlx_mt* m, int32_t slot, int32_t batch, cons
     if (!s) return set_error(WLX_ERR_ARG, "no translation slot %d", slot);
     Busy busy(s);
     if (!busy.ok) return set_error(WLX_ERR_STATE, "translation slot %d is busy (a call is in flight)", slot);
-    MCKR(check_opts(m, s, opts));
-    MCK(hipSetDevice(m->device));
-    MCKR(encode(m, s, batch, src_ids, src_lens, src_stride));
-    MCKR(run_generate(m, s, *opts, tokens_out, tokens_stride, n_tokens_out, scores_out));
-    MCK(hipStreamSynchronize(s->st));
+    CKR(check_opts(m, s, opts));
+    CK(hipSetDevice(m->device));
+    CKR(encode(m, s, batch, src_ids, src_lens, src_stride));
+    CKR(run_generate(m, s, *opts, tokens_out, tokens_stride, n_tokens_out, scores_out));
+    CK(hipStreamSynchronize(s->st));
     float a = 0.f, b = 0.f;
     if (hipEventElapsedTime(&a, s->ev[0], s->ev[1]) == hipSuccess) s->enc_ms = a;
     if (hipEventElapsedTime(&b, s->ev[2], s->ev[3]) == hipSuccess) s->dec_ms = b;
@@ -783,12 +635,12 @@ extern "C" int32_t wlx_mt_debug_encode(wlx_mt* m, int32_t slot, int32_t batch, c
     if (!s) return set_error(WLX_ERR_ARG, "no translation slot %d", slot);
     Busy busy(s);
     if (!busy.ok) return set_error(WLX_ERR_STATE, "translation slot %d is busy", slot);
-    MCK(hipSetDevice(m->device));
-    MCKR(encode(m, s, batch, src_ids, src_lens, src_stride));
+    CK(hipSetDevice(m->device));
+    CKR(encode(m, s, batch, src_ids, src_lens, src_stride));
     const long need = (long)s->n_src * m->spec.d_model;
     if (cap_floats < need) return set_error(WLX_ERR_ARG, "output holds %lld floats, %ld needed", (long long)cap_floats, need);
-    MCK(hipMemcpyAsync(out, s->enc32, need * sizeof(float), hipMemcpyDeviceToHost, s->st));
-    MCK(hipStreamSynchronize(s->st));
+    CK(hipMemcpyAsync(out, s->enc32, need * sizeof(float), hipMemcpyDeviceToHost, s->st));
+    CK(hipStreamSynchronize(s->st));
     return WLX_OK;
 }
 
@@ -800,8 +652,8 @@ extern "C" int32_t wlx_mt_debug_decode_logits(wlx_mt* m, int32_t slot, const int
     Busy busy(s);
     if (!busy.ok) return set_error(WLX_ERR_STATE, "translation slot %d is busy", slot);
     if (n < 1 || n > s->tmax) return set_error(WLX_ERR_ARG, "n %d outside 1..%d", n, s->tmax);
-    MCK(hipSetDevice(m->device));
-    MCKR(encode(m, s, 1, src_ids, &src_len, src_len));
+    CK(hipSetDevice(m->device));
+    CKR(encode(m, s, 1, src_ids, &src_len, src_len));
     const int V = m->spec.vocab;
     int c = 0;
     for (int j = 0; j < s->tmax; ++j) s->h_anc[j] = 0;
@@ -811,9 +663,9 @@ extern "C" int32_t wlx_mt_debug_decode_logits(wlx_mt* m, int32_t slot, const int
         c += tok != m->spec.pad_id;
         s->h_tok[0] = tok;
         s->h_pos[0] = position_of(tok, c, 0, m->spec.pad_id);
-        MCKR(decode_step(m, s, 1, 1, t));
-        MCK(hipMemcpyAsync(out + (long)t * V, s->logits, V * sizeof(float), hipMemcpyDeviceToHost, s->st));
-        MCK(hipStreamSynchronize(s->st));     // (h_tok / h_pos are rewritten by the next step)
+        CKR(decode_step(m, s, 1, 1, t));
+        CK(hipMemcpyAsync(out + (long)t * V, s->logits, V * sizeof(float), hipMemcpyDeviceToHost, s->st));
+        CK(hipStreamSynchronize(s->st));     // (h_tok / h_pos are rewritten by the next step)
     }
     return WLX_OK;
 }
@@ -843,26 +695,26 @@ struct HookScope {
     }
     int begin(int device) {
         int n = 0;
-        MCK(hipGetDeviceCount(&n));
+        CK(hipGetDeviceCount(&n));
         if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
-        MCK(hipSetDevice(device));
-        MCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        CK(hipSetDevice(device));
+        CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         return WLX_OK;
     }
     template <class T>
     int upload(T** d, const T* h, size_t n) {
-        MCKR(dalloc(allocs, d, n));
-        if (h && n) MCK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+        CKR(dalloc(allocs, d, n, false));
+        if (h && n) CK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
         return WLX_OK;
     }
     template <class T>
     int download(T* h, const T* d, size_t n) {
-        MCK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st));
+        CK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st));
         return WLX_OK;
     }
     int finish() {
-        MCK(hipGetLastError());
-        MCK(hipStreamSynchronize(st));
+        CK(hipGetLastError());
+        CK(hipStreamSynchronize(st));
         return WLX_OK;
     }
 };
@@ -899,19 +751,19 @@ extern "C" int32_t wlx_mt_debug_attn(int32_t device, const uint16_t* q, int64_t 
         anc_rows = std::max<int64_t>(anc_rows, (int64_t)q0 + 1);
     }
     HookScope S;
-    MCKR(S.begin(device));
+    CKR(S.begin(device));
     half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
     int32_t *dg = nullptr, *da = nullptr;
-    MCKR(S.upload(&dq, reinterpret_cast<const half_t*>(q), (size_t)q_rows * ldq));
-    MCKR(S.upload(&dk, reinterpret_cast<const half_t*>(k), (size_t)kv_rows * ldk));
-    MCKR(S.upload(&dv, reinterpret_cast<const half_t*>(v), (size_t)kv_rows * ldv));
-    MCKR(S.upload(&dout, reinterpret_cast<const half_t*>(o), (size_t)o_rows * ldo));
-    MCKR(S.upload(&dg, groups, (size_t)4 * n_groups));
-    if (anc) MCKR(S.upload(&da, anc, (size_t)anc_rows * ld_anc));
+    CKR(S.upload(&dq, reinterpret_cast<const half_t*>(q), (size_t)q_rows * ldq));
+    CKR(S.upload(&dk, reinterpret_cast<const half_t*>(k), (size_t)kv_rows * ldk));
+    CKR(S.upload(&dv, reinterpret_cast<const half_t*>(v), (size_t)kv_rows * ldv));
+    CKR(S.upload(&dout, reinterpret_cast<const half_t*>(o), (size_t)o_rows * ldo));
+    CKR(S.upload(&dg, groups, (size_t)4 * n_groups));
+    if (anc) CKR(S.upload(&da, anc, (size_t)anc_rows * ld_anc));
     static_assert(sizeof(MtAttnGroup) == 4 * sizeof(int32_t), "MtAttnGroup is four int32");
     launch_mt_attn(dq, ldq, dk, ldk, dv, ldv, dout, ldo, reinterpret_cast<const MtAttnGroup*>(dg), n_groups, max_nq, heads, da,
                    anc ? ld_anc : 0, anc ? tmax : 0, S.st);
-    MCKR(S.download(reinterpret_cast<half_t*>(o), dout, (size_t)o_rows * ldo));
+    CKR(S.download(reinterpret_cast<half_t*>(o), dout, (size_t)o_rows * ldo));
     return S.finish();
 }
 
@@ -931,21 +783,21 @@ extern "C" int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_
         if (max_nb > 0 && (!ban || ban_ld < max_nb)) return set_error(WLX_ERR_ARG, "ban table missing or ban_ld %d < %d", ban_ld, max_nb);
     }
     HookScope S;
-    MCKR(S.begin(device));
+    CKR(S.begin(device));
     float *dl = nullptr, *scratch = nullptr, *dval = nullptr;
     int32_t *dban = nullptr, *dnban = nullptr, *cidx = nullptr, *didx = nullptr;
-    MCKR(S.upload(&dl, logits, (size_t)rows * vocab));
+    CKR(S.upload(&dl, logits, (size_t)rows * vocab));
     if (nban) {
-        MCKR(S.upload(&dnban, nban, (size_t)rows));
-        MCKR(S.upload(&dban, max_nb > 0 ? ban : nullptr, max_nb > 0 ? (size_t)rows * ban_ld : 0));
+        CKR(S.upload(&dnban, nban, (size_t)rows));
+        CKR(S.upload(&dban, max_nb > 0 ? ban : nullptr, max_nb > 0 ? (size_t)rows * ban_ld : 0));
     }
-    MCKR(S.upload(&scratch, (const float*)nullptr, (size_t)rows * WLX_MT_CHUNKS * (2 + k)));
-    MCKR(S.upload(&cidx, (const int32_t*)nullptr, (size_t)rows * WLX_MT_CHUNKS * k));
-    MCKR(S.upload(&dval, (const float*)nullptr, (size_t)rows * k));
-    MCKR(S.upload(&didx, (const int32_t*)nullptr, (size_t)rows * k));
+    CKR(S.upload(&scratch, (const float*)nullptr, (size_t)rows * WLX_MT_CHUNKS * (2 + k)));
+    CKR(S.upload(&cidx, (const int32_t*)nullptr, (size_t)rows * WLX_MT_CHUNKS * k));
+    CKR(S.upload(&dval, (const float*)nullptr, (size_t)rows * k));
+    CKR(S.upload(&didx, (const int32_t*)nullptr, (size_t)rows * k));
     launch_mt_topk(dl, rows, vocab, dban, dnban, nban ? ban_ld : 0, k, scratch, cidx, dval, didx, S.st);
-    MCKR(S.download(out_val, dval, (size_t)rows * k));
-    MCKR(S.download(out_idx, didx, (size_t)rows * k));
+    CKR(S.download(out_val, dval, (size_t)rows * k));
+    CKR(S.download(out_idx, didx, (size_t)rows * k));
     return S.finish();
 }
 
@@ -958,19 +810,18 @@ extern "C" int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vo
         if (tok[r] < 0 || tok[r] >= vocab || pos[r] < 0 || pos[r] >= n_pos)
             return set_error(WLX_ERR_ARG, "row %d: token %d / position %d outside the tables", r, tok[r], pos[r]);
     HookScope S;
-    MCKR(S.begin(device));
+    CKR(S.begin(device));
     float *dE = nullptr, *dsin = nullptr, *dx = nullptr;
     half_t* Ep = nullptr;
     int32_t *dtok = nullptr, *dpos = nullptr;
-    const int NT = (vocab + 15) / 16;
-    MCKR(S.upload(&dE, E, (size_t)vocab * d));
-    MCKR(dalloc(S.allocs, &Ep, (size_t)NT * 16 * d));
+    CKR(S.upload(&dE, E, (size_t)vocab * d));
+    CKR(alloc_packed(S.allocs, vocab, d, &Ep, nullptr, false));
     launch_pack_linear(dE, vocab, d, d, Ep, d / 32, 0, S.st);      // as wlx_mt_create packs model.shared.weight
-    MCKR(S.upload(&dtok, tok, (size_t)rows));
-    MCKR(S.upload(&dpos, pos, (size_t)rows));
-    MCKR(S.upload(&dsin, sinpos, (size_t)n_pos * d));
-    MCKR(S.upload(&dx, (const float*)nullptr, (size_t)rows * d));
+    CKR(S.upload(&dtok, tok, (size_t)rows));
+    CKR(S.upload(&dpos, pos, (size_t)rows));
+    CKR(S.upload(&dsin, sinpos, (size_t)n_pos * d));
+    CKR(S.upload(&dx, (const float*)nullptr, (size_t)rows * d));
     launch_mt_embed(dtok, dpos, rows, Ep, d / 32, scale, dsin, d, dx, S.st);
-    MCKR(S.download(x, dx, (size_t)rows * d));
+    CKR(S.download(x, dx, (size_t)rows * d));
     return S.finish();
 }

@@ -323,20 +323,12 @@ struct wlx_vad {
     std::mutex mu;
 };
 
-#define VCK(call)                                                                                              \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess)                                                                                  \
-            return set_error(WLX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 static int vad_upload(wlx_vad* v, const std::vector<float>& host, const float** out) {
-    void* p = nullptr;
-    VCK(hipMalloc(&p, host.size() * sizeof(float)));
-    v->pool.push_back(p);
-    VCK(hipMemcpyAsync(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, v->stream));   // never the legacy stream
-    VCK(hipStreamSynchronize(v->stream));
-    *out = reinterpret_cast<const float*>(p);
+    float* p = nullptr;
+    CKR(dalloc(v->pool, &p, host.size(), false));
+    CK(hipMemcpyAsync(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, v->stream));   // never the legacy stream
+    CK(hipStreamSynchronize(v->stream));
+    *out = p;
     return WLX_OK;
 }
 
@@ -350,11 +342,12 @@ static int vad_reserve(wlx_vad* v, long long n_samples) {
     v->d_pcm = v->d_gx = v->d_hs = v->d_probs = v->h_pin = nullptr;
     v->cap_samples = 0;
     const long long wins = cap / VAD_WINDOW + 1;
-    VCK(hipMalloc((void**)&v->d_pcm, cap * sizeof(float)));
-    VCK(hipMalloc((void**)&v->d_gx, wins * 512 * sizeof(float)));
-    VCK(hipMalloc((void**)&v->d_hs, wins * 512 * sizeof(float)));
-    VCK(hipMalloc((void**)&v->d_probs, wins * sizeof(float)));
-    VCK(hipHostMalloc((void**)&v->h_pin, cap * sizeof(float), hipHostMallocDefault));
+    // grown with the longest chunk seen, the old buffers freed above: owned by name, not by a free list
+    CK(hipMalloc((void**)&v->d_pcm, cap * sizeof(float)));
+    CK(hipMalloc((void**)&v->d_gx, wins * 512 * sizeof(float)));
+    CK(hipMalloc((void**)&v->d_hs, wins * 512 * sizeof(float)));
+    CK(hipMalloc((void**)&v->d_probs, wins * sizeof(float)));
+    CK(hipHostMalloc((void**)&v->h_pin, cap * sizeof(float), hipHostMallocDefault));
     v->cap_samples = cap;
     return WLX_OK;
 }
@@ -365,7 +358,7 @@ extern "C" int32_t wlx_vad_create(const wlx_vad_weights* w, int32_t device, wlx_
                            w->enc_b[2], w->enc_b[3], w->lstm_w_ih, w->lstm_w_hh, w->lstm_b_ih, w->lstm_b_hh, w->out_w, w->out_b};
     for (const float* p : need)
         if (!p) return set_error(WLX_ERR_WEIGHT, "wlx_vad_create: a weight pointer is null");
-    VCK(hipSetDevice(device));
+    CK(hipSetDevice(device));
     wlx_vad* v = new wlx_vad();
     v->device = device;
     auto bail = [&](int rc) { wlx_vad_destroy(v); return rc; };
@@ -443,23 +436,23 @@ extern "C" int32_t wlx_vad_probs(wlx_vad* v, const float* pcm, int64_t n, float*
     if (T == 0) return WLX_OK;
     if (T > cap) return set_error(WLX_ERR_ARG, "wlx_vad_probs: %lld windows do not fit the output buffer (%d)", T, cap);
     std::lock_guard<std::mutex> lk(v->mu);
-    VCK(hipSetDevice(v->device));
+    CK(hipSetDevice(v->device));
     (void)hipGetLastError();                  // a stale error of this thread must not be blamed on the launches below
     int rc = vad_reserve(v, n);
     if (rc) return rc;
     memcpy(v->h_pin, pcm, (size_t)n * sizeof(float));
-    VCK(hipMemcpyAsync(v->d_pcm, v->h_pin, (size_t)n * sizeof(float), hipMemcpyHostToDevice, v->stream));
-    VCK(hipEventRecord(v->ev0, v->stream));
+    CK(hipMemcpyAsync(v->d_pcm, v->h_pin, (size_t)n * sizeof(float), hipMemcpyHostToDevice, v->stream));
+    CK(hipEventRecord(v->ev0, v->stream));
     const int fe_blocks = (int)((T + VAD_WT - 1) / VAD_WT);
     hipLaunchKernelGGL(vad_frontend_kernel, dim3(fe_blocks), dim3(VAD_FE_THREADS), 0, v->stream, v->d_pcm, (long long)n, (int)T, v->W, v->d_gx);
     hipLaunchKernelGGL(vad_lstm_kernel, dim3(1), dim3(512), 0, v->stream, v->d_gx, v->W.whhP, v->d_hs, (int)T);
     hipLaunchKernelGGL(vad_out_kernel, dim3((int)((T + 3) / 4)), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, (int)T);
-    VCK(hipGetLastError());
-    VCK(hipEventRecord(v->ev1, v->stream));
-    VCK(hipMemcpyAsync(v->h_pin, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-    VCK(hipStreamSynchronize(v->stream));
+    CK(hipGetLastError());
+    CK(hipEventRecord(v->ev1, v->stream));
+    CK(hipMemcpyAsync(v->h_pin, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+    CK(hipStreamSynchronize(v->stream));
     memcpy(probs_out, v->h_pin, (size_t)T * sizeof(float));
-    if (device_ms_out) VCK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
+    if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
     return WLX_OK;
 }
 
@@ -481,22 +474,22 @@ extern "C" int32_t wlx_vad_probs_resident(wlx_vad* v, wlx_ring* r, int64_t start
     if (start < r->base || start + n > r->base + r->resident)
         return set_error(WLX_ERR_STATE, "wlx_vad_probs_resident: [%lld, %lld) is not resident (ring holds [%lld, %lld))", (long long)start,
                          (long long)(start + n), (long long)r->base, (long long)(r->base + r->resident));
-    VCK(hipSetDevice(v->device));
+    CK(hipSetDevice(v->device));
     (void)hipGetLastError();
     int rc = vad_reserve(v, n + (long long)extra_zero_windows * VAD_WINDOW);
     if (rc) return rc;
     const float* pcm = r->buf + (start - r->base);
-    VCK(hipEventRecord(v->ev0, v->stream));
+    CK(hipEventRecord(v->ev0, v->stream));
     const int fe_blocks = (int)((T + VAD_WT - 1) / VAD_WT);
     hipLaunchKernelGGL(vad_frontend_kernel, dim3(fe_blocks), dim3(VAD_FE_THREADS), 0, v->stream, pcm, (long long)n, (int)T, v->W, v->d_gx);
     hipLaunchKernelGGL(vad_lstm_kernel, dim3(1), dim3(512), 0, v->stream, v->d_gx, v->W.whhP, v->d_hs, (int)T);
     hipLaunchKernelGGL(vad_out_kernel, dim3((int)((T + 3) / 4)), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, (int)T);
-    VCK(hipGetLastError());
-    VCK(hipEventRecord(v->ev1, v->stream));
-    VCK(hipMemcpyAsync(v->h_pin, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-    VCK(hipStreamSynchronize(v->stream));
+    CK(hipGetLastError());
+    CK(hipEventRecord(v->ev1, v->stream));
+    CK(hipMemcpyAsync(v->h_pin, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+    CK(hipStreamSynchronize(v->stream));
     memcpy(probs_out, v->h_pin, (size_t)T * sizeof(float));
-    if (device_ms_out) VCK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
+    if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
     return WLX_OK;
 }
 

@@ -51,25 +51,7 @@ class HipWhisperEngine:
         self.device = device
         cs = _lib.wlx_spec(spec.n_mels, spec.d_model, spec.n_heads, spec.enc_layers, spec.dec_layers, spec.ffn,
                            spec.vocab, spec.n_audio_ctx, spec.n_text_ctx)
-        keep = []
-        arr = (_lib.wlx_tensor * len(weights))()
-        for i, (name, t) in enumerate(weights.items()):
-            on_dev = 0
-            if hasattr(t, "data_ptr"):            # torch tensor (PyTorch-ROCm holds the weights)
-                import torch
-                t = t.detach().to(torch.float32).contiguous()
-                on_dev = 1 if t.is_cuda else 0
-                ptr, shape = t.data_ptr(), tuple(t.shape)
-            else:
-                t = np.ascontiguousarray(t, dtype=np.float32)
-                ptr, shape = t.ctypes.data, t.shape
-            keep.append(t)
-            arr[i].name = name.encode()
-            arr[i].data = ptr
-            arr[i].ndim = len(shape)
-            for j, s in enumerate(shape):
-                arr[i].shape[j] = s
-            arr[i].on_device = on_dev
+        arr, keep = _lib.tensor_array(weights)      # (keep: alive until the create call returns)
         h = C.c_void_p()
         check(self.lib.wlx_engine_create(C.byref(cs), arr, len(weights), device, C.byref(h)))
         self._h = h

@@ -25,23 +25,14 @@ from .mt_weights import MTGenOptions, MTSpec, generation_options, load_mt_dir
 class HipMTEngine:
     """one wlx_mt engine and one slot of max_batch items x num_beams rows x max_src source tokens"""
 
-    def __init__(self, spec: MTSpec, weights: Dict[str, np.ndarray], device: int = 0, max_batch: int = 8, max_rows: int = 5,
+    def __init__(self, spec: MTSpec, weights: Dict[str, "np.ndarray"], device: int = 0, max_batch: int = 8, max_rows: int = 5,
                  max_src: int = 256):
         self.lib = _lib.load()
         self.spec = spec
         self.max_batch, self.max_rows, self.max_src = max_batch, max_rows, max_src
         cs = _lib.wlx_mt_spec(spec.d_model, spec.n_heads, spec.enc_layers, spec.dec_layers, spec.ffn, spec.vocab, spec.max_positions,
                               spec.pad_id, spec.eos_id, spec.decoder_start_id, int(spec.scale_embedding))
-        keep, arr = [], (_lib.wlx_tensor * len(weights))()
-        for i, (k, v) in enumerate(weights.items()):
-            a = np.ascontiguousarray(v, dtype=np.float32)
-            keep.append(a)
-            arr[i].name = k.encode()
-            arr[i].data = a.ctypes.data
-            arr[i].ndim = a.ndim
-            for j, s in enumerate(a.shape):
-                arr[i].shape[j] = s
-            arr[i].on_device = 0
+        arr, keep = _lib.tensor_array(weights)      # (keep: alive until the create call returns)
         h = C.c_void_p()
         _lib.check(self.lib.wlx_mt_create(C.byref(cs), arr, len(weights), device, C.byref(h)))
         self.h = h
