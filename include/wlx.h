@@ -375,6 +375,55 @@ int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_t rows, int
 int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vocab, int32_t d, const int32_t* tok, const int32_t* pos,
                            int32_t rows, float scale, const float* sinpos, int32_t n_pos, float* x);
 
+/* Whisper kernels, one launch each (csrc/kernel_hooks.hip), same conventions: host arrays (fp16 as uint16 bits), a private stream
+ * of `device`, outputs copied in AND out (bytes no thread owns come back unchanged), WLX_ERR_ARG before any launch for every
+ * shape the launcher cannot serve.
+ * LayerNorm of x float32 [M][ldx] over d columns (a multiple of 4, <= 2048; strides multiples of 4): out16 fp16 [M][ldo] and,
+ * when out32 is not null, the float32 copy [M][ldo] (launch_layernorm_f16_f32, else launch_layernorm_f16). */
+int32_t wlx_debug_layernorm(int32_t device, const float* x, int64_t ldx, const float* gamma, const float* beta, int32_t M, int32_t d,
+                            uint16_t* out16, float* out32, int64_t ldo);
+/* encoder self-attention (launch_attn_encoder): per item Q [T][ldq], K [T][ldk] (q pre-scaled), V^T [H * 64][ldvt] with
+ * ldvt >= T rounded up to 32, O [T][ldo]; item strides isq / isk / isv / iso in halfs. 65 <= T (three 32-key tiles in flight);
+ * Q / K / V^T strides multiples of 8. items * T >= 4000 runs the eight-wave kernel, else the four-wave one. */
+int32_t wlx_debug_attn_encoder(int32_t device, const uint16_t* q, int64_t ldq, int64_t isq, const uint16_t* k, int64_t ldk, int64_t isk,
+                               const uint16_t* vt, int64_t ldvt, int64_t isv, uint16_t* o, int64_t ldo, int64_t iso, int32_t T,
+                               int32_t H, int32_t items);
+/* One encoder GEMM launch (gemm.hip): A fp16 [zbatch][M][lda] (free lda / strideA: the conv-as-GEMM rows overlap), W float32 [N][K]
+ * (conv3_cin != 0: a conv weight [N][Cin][3], K = 3 Cin) packed by the hook with the production pack kernels into KT k-tiles (even,
+ * KT * 32 >= K), bias [N] (nullable), pos [M][N] (mode 2). mode = GemmMode 0..5 (store fp16, GELU fp16, GELU + pos fp32, residual fp32,
+ * QKV, tile-packed cross K / V). force_form -1: launch_gemm's own pick; 0 / 1 / 2: the second form's 64 x 96, 96 x 96, 128 x 128 tile;
+ * 3: the large-M form. *_len: halfs / floats of the caller's arrays, all copied in and out. ran_out[4] = form, LDS-transposed
+ * epilogue (0 / 1), XCD remap a, b (0, 0 = off). */
+typedef struct {
+    int32_t zbatch, M, N, K, KT, conv3_cin, mode, force_form;
+    int32_t d, rows_per_item;
+    float qscale;
+    int32_t reserved;
+    int64_t lda, strideA, a_len;
+    int64_t ldc, strideC, c_len;
+    int64_t ldx, strideX, x_len;
+    int64_t ldk, kv_item_stride_k, kv_layer_stride_k, k_len;
+    int64_t ldvt, kv_item_stride_v, kv_layer_stride_v, v_len;
+} wlx_debug_gemm_args;
+int32_t wlx_debug_gemm(int32_t device, const wlx_debug_gemm_args* a, const uint16_t* A, const float* W, const float* bias,
+                       const float* pos, uint16_t* C, float* X, uint16_t* kout, uint16_t* vt, int32_t* ran_out);
+/* decode cross-attention: launch_dec_cross_attn then launch_dec_xattn_combine. q [rows][ldq]; kp / vp: tile-packed cross K / V of
+ * ONE layer ([n_items][item_stride], the layout of the GEMM_CROSS_KV epilogue: 1536 padded keys); groups of R <= 16 rows, group g
+ * attends to item group_item[g]; (groups - 1) * R < rows <= groups * R. Returns the split partials part_o fp16
+ * [groups][H][8][16][64], part_ml float32 [groups][H][16][8][2] and the combined rows out fp16 [rows][ldo]. With align_out (float32
+ * [rows][1536]) also launch_dec_align_scores of head align_head on item align_item's packed K. */
+int32_t wlx_debug_dec_cross_attn(int32_t device, const uint16_t* q, int64_t ldq, const uint16_t* kp, const uint16_t* vp,
+                                 int64_t item_stride, int32_t n_items, int32_t H, int32_t R, int32_t groups, int32_t rows,
+                                 const int32_t* group_item, uint16_t* part_o, float* part_ml, uint16_t* out, int64_t ldo,
+                                 int32_t align_item, int32_t align_head, float* align_out);
+/* decode self-attention over the KV cache (launch_dec_self_attn): q [rows][ldq], kc / vc [cache_rows][cache_row_stride] with
+ * position p of a cache row at p * d (cache_row_stride covers at least the positions in use), row r attends to positions 0..pos[r], position p read from cache row
+ * anc[ancrow[r]][p] (anc int16 [cache_rows][448]). ident_ancestry = 1 requires ancrow[r] == r (rows <= 16: the eight-wave
+ * kernel, else four waves); 0 runs the table-lookup form. out fp16 [rows][ldo]. */
+int32_t wlx_debug_dec_self_attn(int32_t device, const uint16_t* q, int64_t ldq, const uint16_t* kc, const uint16_t* vc,
+                                int64_t cache_row_stride, int32_t cache_rows, int32_t d, int32_t H, int32_t rows, const int32_t* pos,
+                                const int32_t* ancrow, const int16_t* anc, int32_t ident_ancestry, uint16_t* out, int64_t ldo);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "host.hip", "engine.hip", "vad.hip", "mt.hip", "mt_engine.hip"]
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "host.hip", "engine.hip", "vad.hip", "mt.hip", "mt_engine.hip", "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
     "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
@@ -26,6 +26,7 @@ EXPORTS = [
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
     "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
     "wlx_mt_debug_embed",
+    "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
 ]
 
 
@@ -82,6 +83,14 @@ class wlx_vad_weights(C.Structure):
 class wlx_mt_spec(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("d_model", "n_heads", "enc_layers", "dec_layers", "ffn", "vocab", "max_positions",
                                          "pad_id", "eos_id", "decoder_start_id", "scale_embedding")]
+
+
+class wlx_debug_gemm_args(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("zbatch", "M", "N", "K", "KT", "conv3_cin", "mode", "force_form", "d", "rows_per_item")] +
+                [("qscale", C.c_float), ("reserved", C.c_int32)] +
+                [(n, C.c_int64) for n in ("lda", "strideA", "a_len", "ldc", "strideC", "c_len", "ldx", "strideX", "x_len",
+                                          "ldk", "kv_item_stride_k", "kv_layer_stride_k", "k_len",
+                                          "ldvt", "kv_item_stride_v", "kv_layer_stride_v", "v_len")])
 
 
 class wlx_mt_gen_opts(C.Structure):
@@ -265,6 +274,13 @@ def load() -> C.CDLL:
     lib.wlx_mt_debug_attn.argtypes = [i32, u16p, i64, i64, u16p, i64, u16p, i64, i64, i32p, i32, i32, i32, i32p, i32, i32, u16p, i64, i64]
     lib.wlx_mt_debug_topk.argtypes = [i32, f32p, i32, i32, i32p, i32p, i32, i32, f32p, i32p]
     lib.wlx_mt_debug_embed.argtypes = [i32, f32p, i32, i32, i32p, i32p, i32, C.c_float, f32p, i32, f32p]
+    lib.wlx_debug_layernorm.argtypes = [i32, f32p, i64, f32p, f32p, i32, i32, u16p, f32p, i64]
+    lib.wlx_debug_attn_encoder.argtypes = [i32, u16p, i64, i64, u16p, i64, i64, u16p, i64, i64, u16p, i64, i64, i32, i32, i32]
+    lib.wlx_debug_dec_cross_attn.argtypes = [i32, u16p, i64, u16p, u16p, i64, i32, i32, i32, i32, i32, i32p, u16p, f32p, u16p, i64,
+                                             i32, i32, f32p]
+    lib.wlx_debug_dec_self_attn.argtypes = [i32, u16p, i64, u16p, u16p, i64, i32, i32, i32, i32, i32p, i32p, C.POINTER(C.c_int16), i32,
+                                            u16p, i64]
+    lib.wlx_debug_gemm.argtypes = [i32, C.POINTER(wlx_debug_gemm_args), u16p, f32p, f32p, f32p, u16p, f32p, u16p, u16p, i32p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_mt_destroy"):

@@ -395,6 +395,8 @@ void launch_attn_encoder(const half_t* Q, long ldq, const half_t* K, long ldk, c
     // EIGHT waves sharing a K / V tile (12 windows 7.41 -> 7.05 ms per encoder, large-v3 x 8 24.8 -> 24.1 ms; one window 1.63 vs 1.66 ms,
     // profiles/r4attn2_*). The other ring depths / wave counts measured in rounds 2-4 are no longer instantiated.
     // XCD-aware (pair, query block) order: see attn_map.
+    // (T >= 65, i.e. at least DEPTH - 1 = 3 key tiles: the kernels' first counted wait assumes them; the encoder runs T = 1500 and the
+    // test hook wlx_debug_attn_encoder refuses less)
     const bool batched = (long)items * T >= 4000;
     const int nw = batched ? 8 : 4;
     AttnMap am;

@@ -728,7 +728,7 @@ static bool gemm3_ok(const GemmParams& p, int zbatch) {
     if (mode != 2 && p.mode == GEMM_CROSS_KV && p.M >= 1024 && p.N >= 8192) return true;
     return mode == 2 ? p.M >= 256 : p.M >= 4000;
 }
-static void gemm3_go(const GemmParams& p0, hipStream_t s) {
+static void gemm3_go(const GemmParams& p0, hipStream_t s, GemmParams* ran = nullptr) {
     GemmParams p = p0;
     if (p.rows_per_item <= 0) p.rows_per_item = 4;
     const bool scatter = p.mode == GEMM_QKV || p.mode == GEMM_CROSS_KV;
@@ -740,12 +740,13 @@ static void gemm3_go(const GemmParams& p0, hipStream_t s) {
     // workgroup id % 8 is the XCD
     static const int n_cu = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) n = pr.multiProcessorCount; return n; }();
     const int nwg = std::min((n_cu / 8) * 8, ((p.g3_tiles + 7) / 8) * 8);   // (workgroups past the end of their XCD's run leave at once)
+    if (ran) *ran = p;
     hipLaunchKernelGGL(gemm3_kernel, dim3(nwg), dim3(512), G3_LDS_BYTES, s, p);
 }
 
 // the second form's launch: (WNT, WMT) wave tiles -> workgroup tile (32 WNT) x (32 WMT), ring of DEPTH stages, XCD-aware tile map
 template <int WNT, int WMT, int DEPTH, int KS = 2>
-static void gemm2_go(const GemmParams& p0, int zbatch, hipStream_t s) {
+static void gemm2_go(const GemmParams& p0, int zbatch, hipStream_t s, GemmParams* ran = nullptr) {
     constexpr size_t shm = (size_t)DEPTH * (2 * KS * (WNT + WMT)) * 1024;
     const int NT_total = (p0.N + 15) / 16;
     dim3 grid((NT_total + 2 * WNT - 1) / (2 * WNT), (p0.M + 32 * WMT - 1) / (32 * WMT), zbatch);
@@ -765,6 +766,7 @@ static void gemm2_go(const GemmParams& p0, int zbatch, hipStream_t s) {
             if (bytes < best) { best = bytes; p.xcd_a = a; p.xcd_b = b; }
         }
     }
+    if (ran) *ran = p;
     hipLaunchKernelGGL((gemm2_kernel<WNT, WMT, DEPTH, KS>), grid, dim3(256), shm, s, p);
 }
 template <int WNT, int WMT, int DEPTH, int KS = 2>
@@ -844,6 +846,19 @@ void launch_gemm(const GemmParams& p, int zbatch, hipStream_t s) {
         case 1: gemm2_go<3, 3, 3>(p, zbatch, s); return;
         case 2: gemm2_go<4, 4, 2>(p, zbatch, s); return;
         default: gemm2_go<2, 3, 4>(p, zbatch, s); return;
+    }
+}
+
+// Test hooks (kernel_hooks.hip wlx_debug_gemm): the form launch_gemm would pick (0 / 1 / 2 = the second form's 64 x 96, 96 x 96, 128 x 128
+// tiles, 3 = the large-M form), and one launch on a GIVEN form, whatever the cost model says. The caller has checked that the form can
+// run the shape (gemm3: N % 256, KT % 4, KT >= 8, zbatch 1, 32-bit offsets; second form: KT even). `ran`: the parameters as launched.
+int gemm_form_of(const GemmParams& p, int zbatch) { return gemm3_ok(p, zbatch) ? 3 : gemm2_pick(p, zbatch); }
+void launch_gemm_form(const GemmParams& p, int zbatch, int form, GemmParams* ran, hipStream_t s) {
+    switch (form) {
+        case 0: gemm2_go<2, 3, 4>(p, zbatch, s, ran); return;
+        case 1: gemm2_go<3, 3, 3>(p, zbatch, s, ran); return;
+        case 2: gemm2_go<4, 4, 2>(p, zbatch, s, ran); return;
+        default: gemm3_go(p, s, ran); return;
     }
 }
 

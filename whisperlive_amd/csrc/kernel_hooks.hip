@@ -1,0 +1,318 @@
+// kernel_hooks.hip — kernel-level test hooks of the Whisper kernels: wlx_debug_layernorm, wlx_debug_attn_encoder,
+// wlx_debug_dec_cross_attn, wlx_debug_dec_self_attn (include/wlx.h, below the TEST / PROFILING line).
+// Same conventions as the translation hooks (mt_engine.hip wlx_mt_debug_attn): host arrays in, ONE call of the production
+// launcher on a private non-blocking stream, host arrays out. Outputs are copied in AND out, so bytes no thread owns come back
+// unchanged. Every shape a launcher cannot serve is refused (WLX_ERR_ARG) before anything is allocated or launched. No engine
+// or slot is needed, and no product code path runs differently because these exist.
+#include "decoder.h"
+#include "host.h"
+
+namespace wlx {
+namespace {
+
+// device buffers and the stream of one hook call, released on every return path
+struct HookScope {
+    std::vector<void*> allocs;
+    hipStream_t st = nullptr;
+    ~HookScope() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (void* p : allocs) (void)hipFree(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    int begin(int device) {
+        int n = 0;
+        CK(hipGetDeviceCount(&n));
+        if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
+        CK(hipSetDevice(device));
+        CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        return WLX_OK;
+    }
+    template <class T>
+    int upload(T** d, const T* h, size_t n) {
+        CKR(dalloc(allocs, d, n, false));
+        if (h && n) CK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+        return WLX_OK;
+    }
+    template <class T>
+    int download(T* h, const T* d, size_t n) {
+        CK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st));
+        return WLX_OK;
+    }
+    int finish() {
+        CK(hipGetLastError());
+        CK(hipStreamSynchronize(st));
+        return WLX_OK;
+    }
+};
+
+inline const half_t* h16(const uint16_t* p) { return reinterpret_cast<const half_t*>(p); }
+inline half_t* h16(uint16_t* p) { return reinterpret_cast<half_t*>(p); }
+
+}  // namespace
+}  // namespace wlx
+
+using namespace wlx;
+
+extern "C" int32_t wlx_debug_layernorm(int32_t device, const float* x, int64_t ldx, const float* gamma, const float* beta, int32_t M,
+                                       int32_t d, uint16_t* out16, float* out32, int64_t ldo) {
+    if (!x || !gamma || !beta || !out16) return set_error(WLX_ERR_ARG, "null argument");
+    // layernorm_kernel holds a row in float4 v[8] per lane (64 lanes x 8 x 4 = 2048 columns) and moves float4 / f16x4
+    if (d < 4 || d % 4 || d > 2048) return set_error(WLX_ERR_ARG, "d %d must be a multiple of 4 in 4..2048", d);
+    if (M < 1 || M > (1 << 24)) return set_error(WLX_ERR_ARG, "M %d outside 1..2^24", M);
+    if (ldx < d || ldo < d || ldx % 4 || ldo % 4)
+        return set_error(WLX_ERR_ARG, "row strides %lld / %lld must cover d and be multiples of 4", (long long)ldx, (long long)ldo);
+    HookScope S;
+    CKR(S.begin(device));
+    float *dx = nullptr, *dg = nullptr, *db = nullptr, *d32 = nullptr;
+    half_t* d16 = nullptr;
+    CKR(S.upload(&dx, x, (size_t)M * ldx));
+    CKR(S.upload(&dg, gamma, (size_t)d));
+    CKR(S.upload(&db, beta, (size_t)d));
+    CKR(S.upload(&d16, h16(out16), (size_t)M * ldo));
+    if (out32) {
+        CKR(S.upload(&d32, out32, (size_t)M * ldo));
+        launch_layernorm_f16_f32(dx, ldx, dg, db, d16, d32, ldo, M, d, S.st);
+        CKR(S.download(out32, d32, (size_t)M * ldo));
+    } else {
+        launch_layernorm_f16(dx, ldx, dg, db, d16, ldo, M, d, S.st);
+    }
+    CKR(S.download(h16(out16), d16, (size_t)M * ldo));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_debug_attn_encoder(int32_t device, const uint16_t* q, int64_t ldq, int64_t isq, const uint16_t* k, int64_t ldk,
+                                          int64_t isk, const uint16_t* vt, int64_t ldvt, int64_t isv, uint16_t* o, int64_t ldo,
+                                          int64_t iso, int32_t T, int32_t H, int32_t items) {
+    if (!q || !k || !vt || !o) return set_error(WLX_ERR_ARG, "null argument");
+    if (H < 1 || H > 64 || items < 1 || items > 64) return set_error(WLX_ERR_ARG, "H %d / items %d outside 1..64", H, items);
+    // Both kernels put DEPTH - 1 = 3 key tiles in flight behind the two query pieces and then wait until at most 3 tiles' worth of
+    // requests is outstanding: with fewer than 3 tiles (T <= 64) that wait is already satisfied while the query pieces may still
+    // be in flight. The launcher's contract is therefore T >= 65 (the encoder runs T = 1500).
+    if (T < 65 || T > 32768) return set_error(WLX_ERR_ARG, "T %d outside 65..32768 (the kernels need at least three 32-key tiles)", T);
+    const int64_t w = 64L * H, tpad = ((int64_t)T + 31) / 32 * 32;
+    if (ldq < w || ldk < w || ldo < w) return set_error(WLX_ERR_ARG, "Q / K / O row strides must cover H * 64 columns");
+    if (ldvt < tpad) return set_error(WLX_ERR_ARG, "ldvt %lld does not cover the 32-key padding (%lld columns)", (long long)ldvt, (long long)tpad);
+    if (ldq % 8 || ldk % 8 || ldvt % 8 || isq % 8 || isk % 8 || isv % 8 || ldo % 4 || iso % 4)
+        return set_error(WLX_ERR_ARG, "Q / K / V^T strides must be multiples of 8 halfs (16-byte loads), O strides of 4");
+    if (isq < (int64_t)T * ldq || isk < (int64_t)T * ldk || isv < w * ldvt || iso < (int64_t)T * ldo)
+        return set_error(WLX_ERR_ARG, "item strides must cover T rows of Q / K / O and H * 64 rows of V^T");
+    HookScope S;
+    CKR(S.begin(device));
+    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
+    CKR(S.upload(&dq, h16(q), (size_t)items * isq));
+    CKR(S.upload(&dk, h16(k), (size_t)items * isk));
+    CKR(S.upload(&dv, h16(vt), (size_t)items * isv));
+    CKR(S.upload(&dout, h16(o), (size_t)items * iso));
+    launch_attn_encoder(dq, ldq, dk, ldk, dv, ldvt, dout, ldo, T, H, items, isq, isk, isv, iso, S.st);
+    CKR(S.download(h16(o), dout, (size_t)items * iso));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_debug_dec_cross_attn(int32_t device, const uint16_t* q, int64_t ldq, const uint16_t* kp, const uint16_t* vp,
+                                            int64_t item_stride, int32_t n_items, int32_t H, int32_t R, int32_t groups, int32_t rows,
+                                            const int32_t* group_item, uint16_t* part_o, float* part_ml, uint16_t* out, int64_t ldo,
+                                            int32_t align_item, int32_t align_head, float* align_out) {
+    if (!q || !kp || !vp || !group_item || !part_o || !part_ml || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (H < 1 || H > 64 || n_items < 1) return set_error(WLX_ERR_ARG, "H %d outside 1..64 / n_items %d", H, n_items);
+    if (R < 1 || R > 16) return set_error(WLX_ERR_ARG, "R %d outside 1..16 (one 16-row MFMA query tile per group)", R);
+    if (groups < 1 || groups > 65535) return set_error(WLX_ERR_ARG, "groups %d outside 1..65535", groups);
+    // a dead query lane of a group falls back to the group's first row, which must exist; the combine maps row m to group m / R
+    if ((int64_t)rows <= (int64_t)(groups - 1) * R || (int64_t)rows > (int64_t)groups * R)
+        return set_error(WLX_ERR_ARG, "rows %d outside ((groups - 1) * R, groups * R] = (%d, %d]", rows, (groups - 1) * R, groups * R);
+    const int64_t w = 64L * H, image = w * WLX_T_AUDIO_PAD;
+    if (ldq < w || ldo < w || ldq % 8 || ldo % 8) return set_error(WLX_ERR_ARG, "q / out row strides must cover H * 64 columns and be multiples of 8");
+    if (item_stride < image || item_stride % 8)
+        return set_error(WLX_ERR_ARG, "item_stride %lld below the packed image of H heads (%lld halfs) or not a multiple of 8", (long long)item_stride, (long long)image);
+    for (int g = 0; g < groups; ++g)
+        if (group_item[g] < 0 || group_item[g] >= n_items) return set_error(WLX_ERR_ARG, "group %d: item %d outside 0..%d", g, group_item[g], n_items - 1);
+    if (align_out && (align_item < 0 || align_item >= n_items || align_head < 0 || align_head >= H))
+        return set_error(WLX_ERR_ARG, "alignment scores of item %d / head %d outside the packed K", align_item, align_head);
+    HookScope S;
+    CKR(S.begin(device));
+    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dpo = nullptr, *dout = nullptr;
+    float *dml = nullptr, *dal = nullptr;
+    int32_t* dgi = nullptr;
+    const size_t n_po = (size_t)groups * H * WLX_XSPLIT * 16 * 64, n_ml = (size_t)groups * H * 16 * WLX_XSPLIT * 2;
+    CKR(S.upload(&dq, h16(q), (size_t)rows * ldq));
+    CKR(S.upload(&dk, h16(kp), (size_t)n_items * item_stride));
+    CKR(S.upload(&dv, h16(vp), (size_t)n_items * item_stride));
+    CKR(S.upload(&dgi, group_item, (size_t)groups));
+    CKR(S.upload(&dpo, h16(part_o), n_po));
+    CKR(S.upload(&dml, part_ml, n_ml));
+    CKR(S.upload(&dout, h16(out), (size_t)rows * ldo));
+    launch_dec_cross_attn(dq, ldq, dk, dv, item_stride, H, R, groups, rows, dgi, dpo, dml, S.st);
+    launch_dec_xattn_combine(dpo, dml, rows, H, R, dout, ldo, S.st);
+    if (align_out) {
+        CKR(S.upload(&dal, align_out, (size_t)rows * WLX_T_AUDIO_PAD));
+        launch_dec_align_scores(dq, ldq, dk + (int64_t)align_item * item_stride, align_head, rows, dal, S.st);
+        CKR(S.download(align_out, dal, (size_t)rows * WLX_T_AUDIO_PAD));
+    }
+    CKR(S.download(h16(part_o), dpo, n_po));
+    CKR(S.download(part_ml, dml, n_ml));
+    CKR(S.download(h16(out), dout, (size_t)rows * ldo));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_debug_dec_self_attn(int32_t device, const uint16_t* q, int64_t ldq, const uint16_t* kc, const uint16_t* vc,
+                                           int64_t cache_row_stride, int32_t cache_rows, int32_t d, int32_t H, int32_t rows,
+                                           const int32_t* pos, const int32_t* ancrow, const int16_t* anc, int32_t ident_ancestry,
+                                           uint16_t* out, int64_t ldo) {
+    if (!q || !kc || !vc || !pos || !ancrow || !anc || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (H < 1 || H > 64 || rows < 1 || rows > 65535) return set_error(WLX_ERR_ARG, "H %d outside 1..64 / rows %d outside 1..65535", H, rows);
+    const int64_t w = 64L * H;
+    if (d < w || d % 8 || ldq < w || ldq % 8 || ldo < w) return set_error(WLX_ERR_ARG, "d / ldq (multiples of 8) / ldo must cover H * 64 columns");
+    if (cache_rows < 1 || cache_rows > 32767) return set_error(WLX_ERR_ARG, "cache_rows %d outside 1..32767 (int16 ancestry)", cache_rows);
+    int max_pos = 0;
+    for (int r = 0; r < rows; ++r) max_pos = std::max(max_pos, pos[r]);
+    if (max_pos >= WLX_T_TEXT) max_pos = WLX_T_TEXT - 1;    // (refused row by row below)
+    if (cache_row_stride < (int64_t)(max_pos + 1) * d || cache_row_stride % 8)      // (the engine's cache rows hold all 448 positions)
+        return set_error(WLX_ERR_ARG, "cache_row_stride %lld must cover positions 0..%d of d columns and be a multiple of 8", (long long)cache_row_stride, max_pos);
+    if ((int64_t)cache_rows * cache_row_stride >= (1LL << 31))
+        return set_error(WLX_ERR_ARG, "cache of %d rows x %lld halfs exceeds the kernel's 32-bit element offsets", cache_rows, (long long)cache_row_stride);
+    for (int r = 0; r < rows; ++r) {
+        if (pos[r] < 0 || pos[r] >= WLX_T_TEXT) return set_error(WLX_ERR_ARG, "row %d: position %d outside 0..447", r, pos[r]);
+        if (ancrow[r] < 0 || ancrow[r] >= cache_rows) return set_error(WLX_ERR_ARG, "row %d: ancestry row %d outside the table", r, ancrow[r]);
+        if (ident_ancestry && ancrow[r] != r) return set_error(WLX_ERR_ARG, "ident_ancestry with ancrow[%d] = %d", r, ancrow[r]);
+        const int16_t* ar = anc + (int64_t)ancrow[r] * WLX_T_TEXT;
+        for (int p = 0; p <= pos[r]; ++p)
+            if (ar[p] < 0 || ar[p] >= cache_rows) return set_error(WLX_ERR_ARG, "row %d: cache row %d at position %d outside the cache", r, ar[p], p);
+    }
+    HookScope S;
+    CKR(S.begin(device));
+    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
+    int32_t *dpos = nullptr, *danr = nullptr;
+    int16_t* danc = nullptr;
+    CKR(S.upload(&dq, h16(q), (size_t)rows * ldq));
+    CKR(S.upload(&dk, h16(kc), (size_t)cache_rows * cache_row_stride));
+    CKR(S.upload(&dv, h16(vc), (size_t)cache_rows * cache_row_stride));
+    CKR(S.upload(&dpos, pos, (size_t)rows));
+    CKR(S.upload(&danr, ancrow, (size_t)rows));
+    CKR(S.upload(&danc, anc, (size_t)cache_rows * WLX_T_TEXT));
+    CKR(S.upload(&dout, h16(out), (size_t)rows * ldo));
+    RowTables rt{};
+    rt.pos = dpos; rt.ancrow = danr; rt.anc = danc;
+    launch_dec_self_attn(dq, ldq, dk, dv, cache_row_stride, d, H, rt, rows, dout, ldo, nullptr, ident_ancestry != 0, S.st);
+    CKR(S.download(h16(out), dout, (size_t)rows * ldo));
+    return S.finish();
+}
+
+// One launch_gemm (force_form -1) or one launch on a given form. W is float32 and packed here with the production pack kernels.
+extern "C" int32_t wlx_debug_gemm(int32_t device, const wlx_debug_gemm_args* a, const uint16_t* A, const float* W, const float* bias,
+                                  const float* pos, uint16_t* C, float* X, uint16_t* kout, uint16_t* vt, int32_t* ran_out) {
+    if (!a || !A || !W || !ran_out) return set_error(WLX_ERR_ARG, "null argument");
+    const int mode = a->mode, M = a->M, N = a->N, K = a->K, KT = a->KT, Z = a->zbatch, d = a->d, rpi = a->rows_per_item;
+    if (mode < 0 || mode > 5) return set_error(WLX_ERR_ARG, "mode %d outside 0..5", mode);
+    if (a->force_form < -1 || a->force_form > 3) return set_error(WLX_ERR_ARG, "force_form %d outside -1..3", a->force_form);
+    if (M < 1 || N < 8 || N % 8 || K < 1 || Z < 1 || Z > 64) return set_error(WLX_ERR_ARG, "M %d / N %d (a multiple of 8: 16-byte output pieces) / K %d / zbatch %d", M, N, K, Z);
+    if (KT < 2 || (KT & 1) || (int64_t)KT * 32 < K) return set_error(WLX_ERR_ARG, "KT %d must be even and cover K %d (a stage is two k-tiles)", KT, K);
+    if (a->conv3_cin && K != 3 * a->conv3_cin) return set_error(WLX_ERR_ARG, "conv weight: K %d != 3 * Cin %d", K, a->conv3_cin);
+    if (a->lda < 8 || a->lda % 8 || a->strideA % 8) return set_error(WLX_ERR_ARG, "lda / strideA must be multiples of 8 halfs");
+    // every row is read for KT * 32 columns from its start (columns past K meet zero weights), rows past M are clamped
+    if ((int64_t)(Z - 1) * a->strideA + (int64_t)(M - 1) * a->lda + (int64_t)KT * 32 > a->a_len || (Z > 1 && a->strideA < 0))
+        return set_error(WLX_ERR_ARG, "A (%lld halfs) does not hold KT * 32 columns behind its last row", (long long)a->a_len);
+    const bool scatter = mode == GEMM_QKV || mode == GEMM_CROSS_KV;
+    if (mode == GEMM_STORE_F16 || mode == GEMM_GELU_F16) {
+        if (!C || a->ldc < N || a->ldc % 8 || a->strideC % 8 || a->strideC < 0 || (int64_t)(Z - 1) * a->strideC + (int64_t)(M - 1) * a->ldc + N > a->c_len)
+            return set_error(WLX_ERR_ARG, "C: ldc / strideC (multiples of 8) / length do not hold [zbatch][M][N]");
+    } else if (mode == GEMM_GELU_POS_F32 || mode == GEMM_RESID_F32) {
+        if (!X || a->ldx < N || a->ldx % 4 || a->strideX % 4 || a->strideX < 0 || (int64_t)(Z - 1) * a->strideX + (int64_t)(M - 1) * a->ldx + N > a->x_len)
+            return set_error(WLX_ERR_ARG, "X: ldx / strideX (multiples of 4) / length do not hold [zbatch][M][N]");
+        if (mode == GEMM_GELU_POS_F32 && !pos) return set_error(WLX_ERR_ARG, "mode 2 needs pos [M][N]");
+    } else {
+        if (Z != 1) return set_error(WLX_ERR_ARG, "the scattering modes take zbatch 1");
+        if (!kout || !vt || d < 64 || d % 64 || rpi < 1) return set_error(WLX_ERR_ARG, "scatter: K / V^T outputs, d %d (a multiple of 64), rows_per_item %d", d, rpi);
+        const int64_t items = ((int64_t)M + rpi - 1) / rpi, tl = std::min(M, rpi);
+        if (a->kv_item_stride_k % 8 || a->kv_item_stride_v % 8 || a->kv_item_stride_k < 0 || a->kv_item_stride_v < 0)
+            return set_error(WLX_ERR_ARG, "item strides must be non-negative multiples of 8");
+        if (mode == GEMM_QKV) {
+            if (N != 3 * d) return set_error(WLX_ERR_ARG, "QKV: N %d != 3 d", N);
+            if (!C || a->ldc < d || a->ldc % 8 || (int64_t)(M - 1) * a->ldc + d > a->c_len) return set_error(WLX_ERR_ARG, "q: ldc / length do not hold [M][d]");
+            if (a->ldk < d || a->ldk % 8 || (items - 1) * a->kv_item_stride_k + (tl - 1) * a->ldk + d > a->k_len)
+                return set_error(WLX_ERR_ARG, "K rows: ldk / item stride / length do not hold [items][rows_per_item][d]");
+            if (a->ldvt < (rpi + 3) / 4 * 4 || a->ldvt % 4 || (items - 1) * a->kv_item_stride_v + (int64_t)(d - 1) * a->ldvt + (tl + 3) / 4 * 4 > a->v_len)
+                return set_error(WLX_ERR_ARG, "V^T: ldvt (a multiple of 4 covering rows_per_item) / item stride / length do not hold [items][d][ldvt]");
+        } else {
+            if (N % (2 * d)) return set_error(WLX_ERR_ARG, "cross K/V: N %d is not a multiple of 2 d", N);
+            const int64_t L = N / (2 * d), image = (int64_t)d * WLX_T_AUDIO_PAD;
+            if (rpi > WLX_T_AUDIO_PAD) return set_error(WLX_ERR_ARG, "cross K/V: rows_per_item %d exceeds the 1536 keys of a packed image", rpi);
+            if (a->kv_item_stride_k < image || a->kv_item_stride_v < image || a->kv_layer_stride_k % 8 || a->kv_layer_stride_v % 8 ||
+                a->kv_layer_stride_k < 0 || a->kv_layer_stride_v < 0)
+                return set_error(WLX_ERR_ARG, "cross K/V: item strides below a packed image of d * 1536 halfs, or layer strides not multiples of 8");
+            if ((L - 1) * a->kv_layer_stride_k + (items - 1) * a->kv_item_stride_k + image > a->k_len ||
+                (L - 1) * a->kv_layer_stride_v + (items - 1) * a->kv_item_stride_v + image > a->v_len)
+                return set_error(WLX_ERR_ARG, "cross K/V: the packed outputs do not hold [layers][items][d * 1536]");
+        }
+    }
+    GemmParams p{};
+    p.lda = a->lda; p.strideA = a->strideA; p.KT = KT; p.M = M; p.N = N; p.mode = mode;
+    p.ldc = a->ldc; p.strideC = a->strideC; p.ldx = a->ldx; p.strideX = a->strideX;
+    p.d = d; p.qscale = a->qscale; p.ldk = a->ldk; p.ldvt = a->ldvt; p.rows_per_item = rpi;
+    p.kv_item_stride_k = a->kv_item_stride_k; p.kv_item_stride_v = a->kv_item_stride_v;
+    p.kv_layer_stride_k = a->kv_layer_stride_k; p.kv_layer_stride_v = a->kv_layer_stride_v;
+    const int form_req = a->force_form;
+    if (form_req >= 0 && form_req <= 2) {
+        static const int wnt[3] = {2, 3, 4};
+        if (scatter && d % (32 * wnt[form_req])) return set_error(WLX_ERR_ARG, "form %d: d %d is not a multiple of its %d-column tile", form_req, d, 32 * wnt[form_req]);
+    } else if (form_req == 3) {
+        if (Z != 1 || (N & 255) || (KT & 3) || KT < 8) return set_error(WLX_ERR_ARG, "the large-M form needs zbatch 1, N %% 256 == 0, KT %% 4 == 0, KT >= 8");
+        if ((int64_t)M * a->lda * 2 >= (1LL << 31) || (int64_t)N * KT * 64 >= (1LL << 31)) return set_error(WLX_ERR_ARG, "the large-M form uses 32-bit buffer offsets");
+    }
+    HookScope S;
+    CKR(S.begin(device));
+    if (gemm_prepare_device() != 0) return set_error(WLX_ERR_HIP, "gemm_prepare_device failed");
+    half_t *dA = nullptr, *dWp = nullptr, *dC = nullptr, *dK = nullptr, *dV = nullptr;
+    float *dW = nullptr, *db = nullptr, *dpos = nullptr, *dX = nullptr;
+    CKR(S.upload(&dA, h16(A), (size_t)a->a_len));
+    CKR(S.upload(&dW, W, (size_t)N * K));
+    int kt_alloc = 0;
+    CKR(alloc_packed(S.allocs, N, (int64_t)KT * 32, &dWp, &kt_alloc, true));
+    if (a->conv3_cin) launch_pack_conv3(dW, N, a->conv3_cin, dWp, KT, S.st);
+    else launch_pack_linear(dW, N, K, K, dWp, KT, 0, S.st);
+    if (bias) CKR(S.upload(&db, bias, (size_t)N));
+    if (pos && mode == GEMM_GELU_POS_F32) CKR(S.upload(&dpos, pos, (size_t)M * N));
+    if (C && a->c_len > 0) CKR(S.upload(&dC, h16(C), (size_t)a->c_len));
+    if (X && a->x_len > 0) CKR(S.upload(&dX, X, (size_t)a->x_len));
+    if (scatter) {
+        CKR(S.upload(&dK, h16(kout), (size_t)a->k_len));
+        CKR(S.upload(&dV, h16(vt), (size_t)a->v_len));
+    }
+    p.A = dA; p.Wp = dWp; p.bias = db; p.pos = dpos; p.C = dC; p.X = dX; p.Kout = dK; p.Vt = dV;
+    const int form = form_req >= 0 ? form_req : gemm_form_of(p, Z);
+    GemmParams ran = p;
+    if (form_req < 0) {
+        launch_gemm(p, Z, S.st);
+        // what launch_gemm did with it: the same function on the picked form fills `ran` without launching twice — recomputed below
+        if (form == 3) { ran.epi_lds = ((std::max(rpi, 0) ? rpi : 4) & 3) == 0 && (!scatter || d % 256 == 0); ran.xcd_a = ran.xcd_b = 0; }
+    } else {
+        launch_gemm_form(p, Z, form, &ran, S.st);
+    }
+    static const int wnt[3] = {2, 3, 4}, wmt[3] = {3, 3, 4};
+    const bool f16_out = mode == GEMM_STORE_F16 || mode == GEMM_GELU_F16 || scatter;
+    const int rp = rpi > 0 ? rpi : 4;
+    int epi, xa = 0, xb = 0;
+    if (form == 3) epi = f16_out && (rp & 3) == 0 && (!scatter || d % 256 == 0);
+    else {
+        epi = f16_out && (rp & 3) == 0 && (!scatter || d % (32 * wnt[form]) == 0);
+        if (form_req >= 0) { xa = ran.xcd_a; xb = ran.xcd_b; }
+        else {          // the launcher's rule, restated for the report only (gemm2_go)
+            const int gx = ((N + 15) / 16 + 2 * wnt[form] - 1) / (2 * wnt[form]), gy = (M + 32 * wmt[form] - 1) / (32 * wmt[form]);
+            if (Z == 1 && (gx * gy) % 8 == 0 && gx * gy >= 16) {
+                double best = 1e300;
+                for (int aa = 1; aa <= 8; aa <<= 1) {
+                    const int bb = 8 / aa;
+                    if (gy % aa || gx % bb) continue;
+                    const double bytes = (double)M / aa + (double)N / bb;
+                    if (bytes < best) { best = bytes; xa = aa; xb = bb; }
+                }
+            }
+        }
+    }
+    ran_out[0] = form; ran_out[1] = epi; ran_out[2] = xa; ran_out[3] = xb;
+    if (dC) CKR(S.download(h16(C), dC, (size_t)a->c_len));
+    if (dX) CKR(S.download(X, dX, (size_t)a->x_len));
+    if (scatter) {
+        CKR(S.download(h16(kout), dK, (size_t)a->k_len));
+        CKR(S.download(h16(vt), dV, (size_t)a->v_len));
+    }
+    return S.finish();
+}

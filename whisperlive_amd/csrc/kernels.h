@@ -71,6 +71,9 @@ struct GemmParams {
     int g3_gx, g3_tiles;                       // (set by the launcher, third GEMM form) tiles along n, tiles in all
 };
 void launch_gemm(const GemmParams& p, int zbatch, hipStream_t s);
+// test hooks: the form launch_gemm picks (0..2 second-form tiles, 3 large-M form); one launch on a given form (gemm.hip)
+int gemm_form_of(const GemmParams& p, int zbatch);
+void launch_gemm_form(const GemmParams& p, int zbatch, int form, GemmParams* ran, hipStream_t s);
 // per-device set-up of the GEMM kernels (large dynamic-LDS opt-in); returns a hipError_t value
 int gemm_prepare_device();
 // x fp32 [M][d] -> fp16 LN(x)*gamma+beta [M][d]
