@@ -1,14 +1,54 @@
 // Which dec_gemv2_kernel instantiation the launcher picks per projection (host only, no GPU): the rules of decoder.hip gemv2_cfg made visible.
 //   hipcc -std=c++17 -O1 -DWLX_AB scripts/gemv_pick_probe.cpp -o /tmp/gemv_pick_probe -Lwhisperlive_amd -l:libwlx_ab.so -Wl,-rpath,$PWD/whisperlive_amd
 //   WLX_G2_CHMAX=6 /tmp/gemv_pick_probe   (libwlx_ab.so reads the A/B switches; build it with scripts/build_all.sh libwlx_ab.so:WLX_AB)
+// --sweep: the whole decision space instead of the listed projections (tests/test_gemv_picks.py compares it with tests/golden/gemv_pick_sweep.txt.gz).
+// First line "M <every row count>", then one line per (in, out, xsrc, K, N, bias, busy_device, slab, KTS) series:
+//   in out xsrc K N b<bias?> u<busy> s<slab?> k<KTS>|<M first>-<M last>:<slab_split>,<lean>,<kernel name>|...      (run-length over M)
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include "../whisperlive_amd/csrc/common.h"
 #include "../whisperlive_amd/csrc/decoder.h"
 using namespace wlx;
-int main() {
-    static float bias = 0.f;
+static float bias = 0.f;
+static int sweep() {
+    static float slab = 0.f;
+    int Ms[63], nM = 0;
+    for (int m = 1; m <= 50; ++m) Ms[nM++] = m;
+    for (int m : {60, 64, 65, 80, 96, 112, 120, 128, 160, 224, 240, 320, 321}) Ms[nM++] = m;
+    printf("M");
+    for (int i = 0; i < nM; ++i) printf(" %d", Ms[i]);
+    printf("\n");
+    for (int in = 0; in < 3; ++in) for (int out = 0; out < 6; ++out) for (int xsrc = 0; xsrc < 3; ++xsrc)
+    for (int d : {384, 512, 768, 1024, 1280, 96, 128, 640, 1536}) {
+        const struct { int K, N; bool vocab; } shapes[] = {{d, d, false}, {d, 3 * d, false}, {d, 4 * d, false}, {4 * d, d, false},
+                                                             {d, 51864, true}, {d, 51865, true}, {d, 51866, true}};
+        for (auto& sh : shapes) for (int wb = 0; wb < 2; ++wb) for (int busy = 0; busy < 2; ++busy) for (int ws = 0; ws < 2; ++ws)
+        for (int wk = 0; wk < (out == GEMV_OUT_SLAB ? 2 : 1); ++wk) {
+            const int KTS = wk ? sh.K / 32 / WLX_FC2_KS : 0;
+            printf("%d %d %d %d %d b%d u%d s%d k%d", in, out, xsrc, sh.K, sh.N, wb, busy, ws, KTS);
+            char prev[160] = "", cur[160];
+            int first = 0;
+            for (int i = 0; i <= nM; ++i) {
+                if (i < nM) {
+                    GemvParams p; memset(&p, 0, sizeof p);
+                    p.in_mode = in; p.out_mode = out; p.M = Ms[i]; p.K = sh.K; p.KT = sh.K / 32; p.N = sh.N; p.xsrc = xsrc;
+                    p.bias = wb ? &bias : nullptr; p.busy_device = busy; p.slab = ws ? &slab : nullptr; p.KTS = KTS;
+                    p.H = sh.K / 64; p.R = 5;
+                    snprintf(cur, sizeof cur, "%d,%d,%s", dec_gemv_slab_split(Ms[i], sh.K, sh.N), (int)dec_gemv_is_lean(p), dec_gemv_kernel_name(p));
+                }
+                if (i == nM || (i > 0 && strcmp(cur, prev))) { printf("|%d-%d:%s", Ms[first], Ms[i - 1], prev); first = i; }
+                strcpy(prev, cur);
+            }
+            printf("\n");
+        }
+    }
+    return 0;
+}
+int main(int argc, char** argv) {
+    if (const char* v1 = getenv("WLX_DECODE_V1")) g_decode_v1 = v1[0] == '1';   // (the engine sets it when it is created)
+    if (argc > 1 && !strcmp(argv[1], "--sweep")) return sweep();
     struct { const char* what; int in, out, M, K, N, xsrc, KS; } cases[] = {
         {"small o-proj M5", GEMV_IN_F16, GEMV_OUT_RESID, 5, 768, 768, GEMV_X_PLAIN, 0},
         {"small fc2 slab M5", GEMV_IN_F16, GEMV_OUT_SLAB, 5, 3072, 768, GEMV_X_PLAIN, WLX_FC2_KS},

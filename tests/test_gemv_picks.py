@@ -1,11 +1,19 @@
-"""Host-only (-m "not gpu"): which `dec_gemv2_kernel` instantiation the launcher picks for every decode projection of the Whisper
-family — the rules of `csrc/decoder.hip gemv2_cfg` as round 6 left them (DESIGN.md §7.3 logs G5, G7-G10), pinned so that a change of
-the search loop shows up here before it shows up as a slower step or, as it did once this round, as a launch past its bound.
+"""Host-only (-m "not gpu"): which `dec_gemv2_kernel` / `dec_vocab_kernel` instantiation the launcher picks for every decode projection
+of the Whisper family — the rules of `csrc/decoder.hip gemv2_cfg` as round 6 left them (DESIGN.md §7.3 logs G5, G7-G10), pinned so that
+a change of the search loop shows up here before it shows up as a slower step or, as it did once that round, as a launch past its bound.
 
-`scripts/gemv_pick_probe.cpp` is compiled for the HOST (hipcc, no device code) and linked against the production `libwlx.so`,
-whose `wlx::dec_gemv_kernel_name` prints the template arguments <CH, LNV, IN, OUT, NTB, MT, XS> the launcher would use:
-CH = k-tiles per wave (so K / 32 / CH waves stream the weights), IN 0 = LayerNorm-fronted, 1 = fp16 rows in, 2 = split combine.
-No kernel is launched and no GPU is needed."""
+`scripts/gemv_pick_probe.cpp` is compiled for the HOST (hipcc, no device code) and linked against the production `libwlx.so`.
+`wlx::dec_gemv_kernel_name` is the name leaf of `decoder.hip gemv2_dispatch` / `vocab2_dispatch`, the one walk that the eligibility
+probe (`dec_gemv_is_lean`, `dec_gemv_slab_split`) and the launch go through as well: it prints the template arguments
+<CH, LNV, IN, OUT, NTB, MT, XS> of the instantiation that runs. CH = k-tiles per wave (so K / 32 / CH waves stream the weights),
+IN 0 = LayerNorm-fronted, 1 = fp16 rows in, 2 = split combine. No kernel is launched and no GPU is needed.
+
+Two layers: 27 named picks of the Whisper models (EXPECTED), and the probe's `--sweep` — every (in, out, xsrc) combination, the ones the
+lean kernels refuse included, over 63 row counts, the family's and four other widths, with and without bias / busy device / slab pointer /
+K slices — compared point for point with `tests/golden/gemv_pick_sweep.txt.gz`: the answers of the commit before the dispatch became one
+walk, recorded by linking the probe against that commit's library. A change of a pick is then a change of that file, made on purpose
+(`gemv_pick_probe --sweep | gzip -9n`)."""
+import gzip
 import shutil
 import subprocess
 from pathlib import Path
@@ -53,7 +61,7 @@ EXPECTED = {
 
 
 @pytest.fixture(scope="module")
-def picks(tmp_path_factory):
+def probe(tmp_path_factory):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not Path(hipcc).exists():
         pytest.skip("hipcc not found")
@@ -64,7 +72,12 @@ def picks(tmp_path_factory):
            f"-L{lib.parent}", f"-l:{lib.name}", f"-Wl,-rpath,{lib.parent}"]
     proc = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert proc.returncode == 0, proc.stderr[-2000:]
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def picks(probe):
+    out = subprocess.run([str(probe)], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr[-2000:]
     got = {}
     for line in out.stdout.splitlines():
@@ -89,3 +102,86 @@ def test_k_split_of_the_mlp_output_projection(picks):
     """two K slices for one stream's rows and for row tiles; none for the 16-row unsplit case the probe lists"""
     assert "slab_split=2" in picks["small fc2 slab M5"][2] and "slab_split=2" in picks["large fc2 slab M5"][2]
     assert "slab_split=0" in picks["medium fc2 resid M16"][2]
+
+
+# ---------------------------------------------------------------- the whole decision space
+GOLDEN = ROOT / "tests" / "golden" / "gemv_pick_sweep.txt.gz"
+
+
+def _parse_sweep(text):
+    """-> (row counts, {series key: [(slab_split, lean, kernel name) per row count]}); the line format: scripts/gemv_pick_probe.cpp"""
+    lines = text.splitlines()
+    assert lines and lines[0].startswith("M "), lines[:1]
+    ms = [int(m) for m in lines[0].split()[1:]]
+    at = {m: i for i, m in enumerate(ms)}
+    series = {}
+    for line in lines[1:]:
+        key, *runs = line.split("|")
+        answers = []
+        for run in runs:
+            span, answer = run.split(":", 1)
+            first, last = (int(m) for m in span.split("-"))
+            split, lean, name = answer.split(",", 2)
+            answers += [(int(split), int(lean), name)] * (at[last] - at[first] + 1)
+        assert len(answers) == len(ms) and key not in series, line
+        series[key] = answers
+    return ms, series
+
+
+def _point(key, m):
+    i, o, x, k, n, *flags = key.split()
+    return f"(in={i}, out={o}, xsrc={x}, M={m}, K={k}, N={n}, flags={' '.join(flags)})"
+
+
+@pytest.fixture(scope="module")
+def sweep(probe):
+    out = subprocess.run([str(probe), "--sweep"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return _parse_sweep(out.stdout)
+
+
+def test_sweep_equals_the_recorded_answers(sweep):
+    ms, got = sweep
+    with gzip.open(GOLDEN, "rt") as f:
+        want_ms, want = _parse_sweep(f.read())
+    assert ms == want_ms
+    assert list(got) == list(want), sorted(set(got) ^ set(want))[:5]
+    assert len(want) >= 54 * 9 * 7 * 8                                   # every combination x width x shape x flag set is in the file
+    for key, answers in want.items():
+        if got[key] == answers:
+            continue
+        for m, g, w in zip(ms, got[key], answers):
+            assert g == w, f"{_point(key, m)}: (slab_split, lean, kernel) is {g}, recorded {w}"
+
+
+def test_sweep_lean_answer_and_kernel_name_agree(sweep):
+    """what engine.hip decoder_pass asks before it builds a pass (lean?) and what the profiling hook filters by (the name) are one answer"""
+    ms, got = sweep
+    n_lean = 0
+    for key, answers in got.items():
+        for m, (split, lean, name) in zip(ms, answers):
+            if lean:
+                n_lean += 1
+                assert name.startswith(("dec_gemv2_kernel<", "dec_vocab_kernel<")), (_point(key, m), name)
+            else:
+                assert name.startswith("dec_gemv_kernel<"), (_point(key, m), name)
+    assert n_lean > 10000                                                # (the sweep does reach the lean kernels)
+
+
+def test_sweep_slab_split_implies_a_lean_k_split_launch(sweep):
+    """dec_gemv_slab_split(M, K, N) = KS != 0 promises that fp16 rows in -> GEMV_OUT_SLAB with KTS = K / 32 / KS runs on the lean kernel:
+    the engine splits the MLP output projection on that answer, and the first-generation kernel does not know GEMV_OUT_SLAB"""
+    ms, got = sweep
+    n_split = 0
+    for key, answers in got.items():
+        i, o, x, k, n, b, u, s, kts = key.split()
+        if (i, o, x, b) != ("1", "5", "0", "b1"):                        # (GEMV_IN_F16, GEMV_OUT_SLAB, GEMV_X_PLAIN, with a bias)
+            continue
+        for m, (split, lean, name) in zip(ms, answers):
+            if split and kts == f"k{int(k) // 32 // split}":
+                n_split += 1
+                assert lean and name.startswith("dec_gemv2_kernel<") and ", 1, 5, " in name, (_point(key, m), split, lean, name)
+    assert n_split > 100
+    for key, answers in got.items():                                     # the split is a function of (M, K, N) alone
+        ref = got[" ".join(["1", "5", "0"] + key.split()[3:5] + ["b1", "u0", "s0", "k0"])]
+        assert [a[0] for a in answers] == [a[0] for a in ref], key

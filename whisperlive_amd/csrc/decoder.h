@@ -56,7 +56,7 @@ struct GemvParams {
     int M;                                   // live rows (of one row chunk: <= 48 on the lean kernel)
     int Mtot;                                // (lean kernel) 0, or the rows of the whole pass, walked in row chunks, see dec_gemv2_kernel
     int chunk;                               // (set by the launcher) rows per chunk: 48 (prompt prefill, grid.z) or 16 (batched decode steps)
-    int busy_device;                         // (set by the engine) three or more slots are live on this device: prefer work-saving launch shapes (gemv2_cfg)
+    int busy_device;                         // (set by the engine) three or more slots are live on this device: prefer work-saving launch shapes (gemv2_cfg_tiles, gemv_chunked)
     int rt_nz, rt_tiles, rt_magic;           // (set by the launcher) 16-row chunks folded into blockIdx.x: chunks, live n-tile workgroups, 65536 / rt_nz + 1
     int K, KT, N;                            // K real, KT = Kpad/32, N real outputs
     int KTW;                                 // (set by the launcher) k-tiles per wave, even
@@ -102,12 +102,16 @@ static inline WlxTrace trace_next(const char* name) {
 #else
 #define WLX_TR_ARG(name)
 #endif
+// The three functions below answer from ONE walk per kernel family (decoder.hip gemv2_dispatch, vocab2_dispatch) from the parameters to
+// the template arguments of the instantiation: the launch, the probe and the name are its leaves, so they cannot disagree. Once the
+// probe has said yes, launch_dec_gemv cannot reach the first-generation kernel (scripts/gemv_pick_probe.cpp --sweep prints all three).
 void launch_dec_gemv(const GemvParams& p, hipStream_t s);
-// kernel name (as rocprofv3 prints it) the launcher picks for these parameters — profiling hook
+// name of the kernel launch_dec_gemv runs for these parameters, formatted from the template arguments themselves — profiling hook
+// (dec_gemv2_kernel<CH, LNV, IN, OUT, NTB, MT, XS>, dec_vocab_kernel<KT, KC, MT>, dec_gemv_kernel<MT, NTB, IN>)
 const char* dec_gemv_kernel_name(const GemvParams& p);
 // WLX_DECODE_V1=1 selects the first-generation decode kernels (kept as the in-tree A/B reference)
 extern bool g_decode_v1;
-// true when launch_dec_gemv runs these parameters on the lean kernel (the only one that knows xsrc / GEMV_OUT_SLAB)
+// true when launch_dec_gemv runs these parameters on a lean kernel (the only ones that know xsrc / GEMV_OUT_SLAB)
 bool dec_gemv_is_lean(const GemvParams& p);
 // K slices the lean kernel would cut an M x K -> N residual projection into (0: keep the single RESID launch).
 // WLX_FC2_KS=0 in the environment turns the split off (A/B).

@@ -1098,55 +1098,40 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
 // larger models: 30 rows x 1280 fp16 = 77 KiB of staged activations) raise the kernel's limit first, once. The first
 // launch of every shape happens OUTSIDE stream capture (engine.hip runs a decoder pass eagerly before it captures one).
 #define WLX_G2_LDS_MAX (152 * 1024)
-// Set when a device refused the raised limit (another GPU generation, a lower per-block LDS limit): gemv2_cfg then keeps
+// Set when a device refused the raised limit (another GPU generation, a lower per-block LDS limit): gemv2_cfg / vocab2_ok then keep
 // every shape that needs more than 64 KiB on the general kernel instead of launching something that cannot run.
 static std::atomic<bool> g_lds_optin_refused{false};
+// the opt-in of `kernel` on the current device; `granted`: the caller's table of that instantiation (the opt-in is a property of the function ON a device)
+static void lds_optin(const void* kernel, std::atomic<signed char> (&granted)[64], const char* what) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || granted[dev].load(std::memory_order_acquire) != 0) return;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WLX_G2_LDS_MAX);
+    if (e == hipSuccess) { granted[dev].store(1, std::memory_order_release); return; }
+    // the caller's launch then fails with the runtime's own error, which the engine's hipGetLastError check reports for
+    // THIS call; later calls take the general kernel (gemv2_cfg, vocab2_ok)
+    (void)hipGetLastError();
+    g_lds_optin_refused.store(true);
+    fprintf(stderr, "[wlx] device %d refused %d KiB of dynamic LDS (%s): %s to the general kernel\n", dev, WLX_G2_LDS_MAX / 1024, hipGetErrorString(e), what);
+}
 template <int CH, int LNV, int IN, int OUT, int NTB, int MT, int XS>
 static void g2_launch(dim3 grid, dim3 block, size_t shm, hipStream_t s, const GemvParams& p) {
     if (shm > 64 * 1024) {
-        static std::atomic<signed char> granted[64] = {};   // per device: the opt-in is a property of the function ON a device
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev >= 0 && dev < 64 && granted[dev].load(std::memory_order_acquire) == 0) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_gemv2_kernel<CH, LNV, IN, OUT, NTB, MT, XS>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, WLX_G2_LDS_MAX);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                g_lds_optin_refused.store(true);
-                fprintf(stderr, "[wlx] device %d refused %d KiB of dynamic LDS (%s): batched decode projections fall back to the general kernel\n",
-                        dev, WLX_G2_LDS_MAX / 1024, hipGetErrorString(e));
-                // the launch below then fails with the runtime's own error, which the engine's hipGetLastError check reports for
-                // THIS call; later calls take the general kernel (gemv2_cfg)
-            } else {
-                granted[dev].store(1, std::memory_order_release);
-            }
-        }
+        static std::atomic<signed char> granted[64] = {};
+        lds_optin(reinterpret_cast<const void*>(&dec_gemv2_kernel<CH, LNV, IN, OUT, NTB, MT, XS>), granted, "batched decode projections fall back");
     }
     hipLaunchKernelGGL((dec_gemv2_kernel<CH, LNV, IN, OUT, NTB, MT, XS>), grid, block, shm, s, p);
 }
+// A configuration that a probe accepted and whose launch finds no instantiation is a bug in the dispatch below. No other kernel runs in its
+// place: launching no function leaves hipErrorInvalidDeviceFunction behind, which the engine's hipGetLastError check after the pass reports.
+static void dispatch_bug(const char* kernel, hipStream_t s) {
+    fprintf(stderr, "[wlx] launch_dec_gemv: no %s instantiation for a configuration its probe accepted\n", kernel);
+    (void)hipLaunchKernel(nullptr, dim3(1), dim3(64), nullptr, 0, s);
+}
 
-struct Gemv2Cfg { bool ok, xstage; int nw, CH, NCH, LNV, NTB, MT; size_t shm; };
-static Gemv2Cfg gemv2_cfg(const GemvParams& p) {
-    Gemv2Cfg c{};
-    c.ok = false;
-    if (g_decode_v1 || p.M > 48 || p.M < 1) return c;
-    if (p.bias ? (p.N & 15) != 0 : p.out_mode != GEMV_OUT_F32) return c;      // bias <=> not the vocabulary projection
-    const bool combo = (p.in_mode == GEMV_IN_LN && (p.out_mode == GEMV_OUT_QKV || p.out_mode == GEMV_OUT_F16 ||
-                                                    p.out_mode == GEMV_OUT_GELU_F16 || p.out_mode == GEMV_OUT_F32)) ||
-                       (p.in_mode != GEMV_IN_LN && p.out_mode == GEMV_OUT_RESID) ||
-                       (p.in_mode == GEMV_IN_F16 && p.out_mode == GEMV_OUT_SLAB);
-    if (!combo || p.K != p.KT * 32) return c;
-    // sources other than the plain rows: one row tile, and only where the kernel is instantiated for them
-    if (p.xsrc != GEMV_X_PLAIN) {
-        const bool ln_ok = p.in_mode == GEMV_IN_LN && p.out_mode == GEMV_OUT_QKV;
-        const bool res_ok = p.in_mode == GEMV_IN_F16 && p.out_mode == GEMV_OUT_RESID && p.xsrc == GEMV_X_SLABS;
-        if (!(ln_ok || res_ok)) return c;
-    }
-    int KTf = p.KT;                                                           // k-tiles one workgroup multiplies
-    if (p.out_mode == GEMV_OUT_SLAB) {
-        if (p.KTS < 1 || p.KT % p.KTS || p.KT / p.KTS != WLX_FC2_KS) return c;
-        KTf = p.KTS;
-    }
+struct Gemv2Cfg { bool ok, xstage; int nw, CH, NCH, LNV, NTB, MT; size_t shm; };   // (LNV: the kernel's argument, 1 where no LayerNorm runs)
+// gemv2_cfg, first decision: waves and chunk width. The KTf k-tiles of a workgroup = nw waves x NCH chunks x CH k-tiles; with them LNV.
+static bool gemv2_cfg_waves(const GemvParams& p, int KTf, Gemv2Cfg& c) {
     const int cap = (p.in_mode == GEMV_IN_F16 && p.out_mode != GEMV_OUT_SLAB && p.M <= 16) ? 16 : 8;
     // exact factorisation KTf = nw * CH * NCH, CH in {6, 5, 4}: fewest chunks first, then the widest chunk
     int best_nch = 1 << 30;
@@ -1166,78 +1151,86 @@ static Gemv2Cfg gemv2_cfg(const GemvParams& p) {
             break;
         }
     } else {     // (the split combine as 8 weight-streaming waves instead of 4 + helpers measured equal, profiles/r2h_*: not instantiated any more)
-    // Fewer waves with longer K slices (log G5, round 6): once no workgroup barrier stands in front of the MFMAs (wave-local staging, log G2) a wave's
-    // cost is its fixed part (row loads, LDS reduction leg, its place at the epilogue's barrier) more than its k-tiles — K = 768 as two waves of twelve
-    // k-tiles instead of four of six (step graph 367.9 -> 363.6 us, headline +0.8 %), 1024 as four of eight instead of eight of four (medium.en
-    // +2.9 %), 512 as two of eight (+0.3 %). Measured and left alone (profiles/r6as_*, r6ao_*): ONE wave of 24 k-tiles for K = 768 (-2.0 %: one wave
-    // cannot keep 24 KiB of loads in flight AND the chain of 24 dependent MFMAs is 0.4 us), two waves of sixteen for K = 1024 (equal), K = 1280 as five
-    // waves of eight (uneven over the four SIMDs: -1 %; it runs as four of ten, below), the row tiles of a batched step (12 windows per decode -1.8 %:
-    // Mtot > 0 keeps the narrow slices), the split combine of the cross-attention output projection as three waves of eight / two of twelve with
-    // three / four items peeled per lane (-1.5 % / -10 %: its waves are bound by the partials they gather, not by their count). Wide slices stay
-    // within their launch bound (512 threads: an instantiation bound to 512 launched with 1024 is 'unspecified launch failure') and on SIMD-even counts.
-    // WLX_G2_CHMAX (A/B builds): the widest chunk tried, 4..12 (6 = the pick until log G5). scripts/gemv_pick_probe.cpp prints the picks on the host.
-    static const int chmax_env = [] { const char* e = wlx_ab("WLX_G2_CHMAX"); const int v = e ? atoi(e) : 12; return (v >= 4 && v <= 12) ? v : 12; }();
-    // (8 / 12 k-tiles per wave: fp16 rows in only, staged rows (one row tile) — the split combine peels two items per lane for six k-tiles)
-    // K = 1280 as four waves of ten k-tiles instead of eight of five (large-v3 step graph 1300 -> 1288 us, +1.1 %: profiles/r6au_*); WLX_G2_CH10=0
-    // (A/B builds) = eight of five
-    static const bool ch10 = [] { const char* e = wlx_ab("WLX_G2_CH10"); return !(e && e[0] == '0'); }();
-    // Log G8 (round 6): the LayerNorm-fronted projections on PLAIN rows of one stream's step (cross-attention query where it is not fused, first MLP
-    // projection) as four waves instead of eight for K = 1024 / 1280 — 8 / 10 k-tiles per wave, five rows in two row trips: large-v3 step graph
-    // 1287 -> 1250 us (+3.5 %), medium.en 859 -> 832 us (+2.9 %), profiles/r6aw_*. WLX_G2_LN_WIDE=0 (A/B builds) = eight waves.
-    static const bool ln_wide = [] { const char* e = wlx_ab("WLX_G2_LN_WIDE"); return !(e && e[0] == '0'); }();
-    const bool ln_wide_here = ln_wide && p.in_mode == GEMV_IN_LN && p.M <= 8 && p.Mtot == 0 && (p.K == 1024 || p.K == 1280) && (p.xsrc == GEMV_X_PLAIN || xs_few_here);
-    const int chmax = (p.in_mode == GEMV_IN_F16 && p.M <= 16 && p.Mtot == 0) ? chmax_env : ln_wide_here ? 10 : std::min(chmax_env, 6);
-    for (int CH = chmax; CH >= 4; --CH) {
-        if (CH != 12 && CH != 10 && CH != 8 && CH > 6) continue;
-        if (CH == 10 && !ch10 && !ln_wide_here) continue;
-        if (ln_wide_here && CH > 6 && CH * 128 != p.K) continue;
-        if (KTf % CH) continue;
-        const int q = KTf / CH;                     // = nw * NCH
-        for (int nw = std::min(CH > 6 ? std::min(cap, 8) : cap, q); nw >= 1; --nw) {
-            if (q % nw) continue;
-            if (CH > 6 && nw > 4 && (nw & 3)) break;
-            const int nch = q / nw;
-            if (nch < best_nch) { best_nch = nch; c.nw = nw; c.CH = CH; c.NCH = nch; }
-            break;
+        // Fewer waves with longer K slices (log G5, round 6): once no workgroup barrier stands in front of the MFMAs (wave-local staging, log G2) a wave's
+        // cost is its fixed part (row loads, LDS reduction leg, its place at the epilogue's barrier) more than its k-tiles — K = 768 as two waves of twelve
+        // k-tiles instead of four of six (step graph 367.9 -> 363.6 us, headline +0.8 %), 1024 as four of eight instead of eight of four (medium.en
+        // +2.9 %), 512 as two of eight (+0.3 %). Measured and left alone (profiles/r6as_*, r6ao_*): ONE wave of 24 k-tiles for K = 768 (-2.0 %: one wave
+        // cannot keep 24 KiB of loads in flight AND the chain of 24 dependent MFMAs is 0.4 us), two waves of sixteen for K = 1024 (equal), K = 1280 as five
+        // waves of eight (uneven over the four SIMDs: -1 %; it runs as four of ten, below), the row tiles of a batched step (12 windows per decode -1.8 %:
+        // Mtot > 0 keeps the narrow slices), the split combine of the cross-attention output projection as three waves of eight / two of twelve with
+        // three / four items peeled per lane (-1.5 % / -10 %: its waves are bound by the partials they gather, not by their count). Wide slices stay
+        // within their launch bound (512 threads: an instantiation bound to 512 launched with 1024 is 'unspecified launch failure') and on SIMD-even counts.
+        // WLX_G2_CHMAX (A/B builds): the widest chunk tried, 4..12 (6 = the pick until log G5). scripts/gemv_pick_probe.cpp prints the picks on the host.
+        static const int chmax_env = [] { const char* e = wlx_ab("WLX_G2_CHMAX"); const int v = e ? atoi(e) : 12; return (v >= 4 && v <= 12) ? v : 12; }();
+        // (8 / 12 k-tiles per wave: fp16 rows in only, staged rows (one row tile) — the split combine peels two items per lane for six k-tiles)
+        // K = 1280 as four waves of ten k-tiles instead of eight of five (large-v3 step graph 1300 -> 1288 us, +1.1 %: profiles/r6au_*); WLX_G2_CH10=0
+        // (A/B builds) = eight of five
+        static const bool ch10 = [] { const char* e = wlx_ab("WLX_G2_CH10"); return !(e && e[0] == '0'); }();
+        // Log G8 (round 6): the LayerNorm-fronted projections on PLAIN rows of one stream's step (cross-attention query where it is not fused, first MLP
+        // projection) as four waves instead of eight for K = 1024 / 1280 — 8 / 10 k-tiles per wave, five rows in two row trips: large-v3 step graph
+        // 1287 -> 1250 us (+3.5 %), medium.en 859 -> 832 us (+2.9 %), profiles/r6aw_*. WLX_G2_LN_WIDE=0 (A/B builds) = eight waves.
+        static const bool ln_wide = [] { const char* e = wlx_ab("WLX_G2_LN_WIDE"); return !(e && e[0] == '0'); }();
+        const bool ln_wide_here = ln_wide && p.in_mode == GEMV_IN_LN && p.M <= 8 && p.Mtot == 0 && (p.K == 1024 || p.K == 1280) && (p.xsrc == GEMV_X_PLAIN || xs_few_here);
+        const int chmax = (p.in_mode == GEMV_IN_F16 && p.M <= 16 && p.Mtot == 0) ? chmax_env : ln_wide_here ? 10 : std::min(chmax_env, 6);
+        for (int CH = chmax; CH >= 4; --CH) {
+            if (CH != 12 && CH != 10 && CH != 8 && CH > 6) continue;
+            if (CH == 10 && !ch10 && !ln_wide_here) continue;
+            if (ln_wide_here && CH > 6 && CH * 128 != p.K) continue;
+            if (KTf % CH) continue;
+            const int q = KTf / CH;                     // = nw * NCH
+            for (int nw = std::min(CH > 6 ? std::min(cap, 8) : cap, q); nw >= 1; --nw) {
+                if (q % nw) continue;
+                if (CH > 6 && nw > 4 && (nw & 3)) break;
+                const int nch = q / nw;
+                if (nch < best_nch) { best_nch = nch; c.nw = nw; c.CH = CH; c.NCH = nch; }
+                break;
+            }
         }
-    }
     }
     if (p.in_mode == GEMV_IN_LN && p.K == 384) {
         // d_model 384 (tiny / tiny.en, round 5): 12 k-tiles as six waves of two, so that six waves share the LayerNorm of the rows
         // (the general search above would pick two waves of six k-tiles: three LayerNorm trips for five rows)
         best_nch = 1; c.nw = 6; c.CH = 2; c.NCH = 1;
     }
-    if (best_nch == (1 << 30)) return c;
-    if (p.in_mode != GEMV_IN_F16 && c.NCH != 1) return c;
-    c.LNV = 0;
+    if (best_nch == (1 << 30)) return false;
+    if (p.in_mode != GEMV_IN_F16 && c.NCH != 1) return false;
+    c.LNV = 1;
     if (p.in_mode == GEMV_IN_LN) {
         if (p.K == 384) c.LNV = 15;                 // 1.5 x 256: see dec_gemv2_kernel
         else {
-            if (p.K % 256 || p.K / 256 < 2 || p.K / 256 > 5) return c;
+            if (p.K % 256 || p.K / 256 < 2 || p.K / 256 > 5) return false;
             c.LNV = p.K / 256;
         }
     }
-    c.NTB = (p.out_mode == GEMV_OUT_F32 && p.N > 8192) ? 2 : 1;
+    return true;
+}
+// gemv2_cfg, second decision: 16-column tiles per workgroup (the staging decision may still take two back to one)
+static int gemv2_cfg_tiles(const GemvParams& p) {
+    int NTB = (p.out_mode == GEMV_OUT_F32 && p.N > 8192) ? 2 : 1;
     // more 16-column tiles than CUs (large-v3's first MLP projection: 320): two tiles per workgroup keep the launch to one
     // round of workgroups and halve the redundant LayerNorm prologues. WLX_GELU_NTB2=0 keeps one tile (A/B).
-    if (p.in_mode == GEMV_IN_LN && p.out_mode == GEMV_OUT_GELU_F16 && p.xsrc == GEMV_X_PLAIN && (p.N + 15) / 16 > 256 && ((p.N + 15) / 16) % 2 == 0) c.NTB = 2;
+    if (p.in_mode == GEMV_IN_LN && p.out_mode == GEMV_OUT_GELU_F16 && p.xsrc == GEMV_X_PLAIN && (p.N + 15) / 16 > 256 && ((p.N + 15) / 16) % 2 == 0) NTB = 2;
     // row tiles of a batched step (round 4): every 16-column workgroup of a LayerNorm-fronted projection normalises its 16 rows again —
     // at 60 rows ~90 % of its instructions. Two column tiles per workgroup halve that redundant work (and the workgroup count) for the
     // wide projections (>= 128 tiles: QKV, first MLP projection). WLX_RT_NTB2=0 keeps one tile (A/B).
     if (p.Mtot > 0 && p.rt_nz > 0 && p.in_mode == GEMV_IN_LN && p.xsrc == GEMV_X_PLAIN &&
-        (p.out_mode == GEMV_OUT_GELU_F16 || p.out_mode == GEMV_OUT_QKV) && (p.N + 15) / 16 >= 128 && ((p.N + 15) / 16) % 2 == 0) c.NTB = 2;
+        (p.out_mode == GEMV_OUT_GELU_F16 || p.out_mode == GEMV_OUT_QKV) && (p.N + 15) / 16 >= 128 && ((p.N + 15) / 16) % 2 == 0) NTB = 2;
     // ... four where the tile count allows (60 rows, Whisper-small: first projection 6.6 -> 6.1 us, first MLP projection 6.5 -> 5.9 us; the 4 x 12
     // configuration +1.5 %, profiles/r4r_*). WLX_RT_NTB4=0 keeps two (A/B).
-    if (c.NTB == 2 && p.Mtot > 0 && p.rt_nz > 0 && ((p.N + 15) / 16) % 4 == 0 && p.M <= 16) c.NTB = 4;
+    if (NTB == 2 && p.Mtot > 0 && p.rt_nz > 0 && ((p.N + 15) / 16) % 4 == 0 && p.M <= 16) NTB = 4;
     // The row-tiled fp16-rows-in residual projections stage their 16 rows x K per 16-column workgroup as well. Two column tiles per
     // workgroup cost a single slot latency (4.7 -> 5.3 us per launch: half as many workgroups for a launch of 192) but save work, and with
     // three or more slots decoding on the device the GPU is work-bound: 4 x 12 windows +3 % (profiles/r4r_*). The engine
     // passes that situation in as GemvParams::busy_device. WLX_RT_F16_NTB2=0 / 1 forces it off / on (A/B).
     static const int rt_f16_ntb2 = [] { const char* e = wlx_ab("WLX_RT_F16_NTB2"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
     const bool f16_wide = rt_f16_ntb2 >= 0 ? rt_f16_ntb2 == 1 : p.busy_device != 0;
-    if (f16_wide && p.Mtot > 0 && p.rt_nz > 0 && p.M <= 16 && p.in_mode == GEMV_IN_F16 && p.out_mode == GEMV_OUT_RESID && p.xsrc == GEMV_X_PLAIN && ((p.N + 15) / 16) % 2 == 0) c.NTB = 2;   // (one row tile per chunk: the only two-tile instantiation)
+    if (f16_wide && p.Mtot > 0 && p.rt_nz > 0 && p.M <= 16 && p.in_mode == GEMV_IN_F16 && p.out_mode == GEMV_OUT_RESID && p.xsrc == GEMV_X_PLAIN && ((p.N + 15) / 16) % 2 == 0) NTB = 2;   // (one row tile per chunk: the only two-tile instantiation)
     // (measured and dropped, profiles/r4t_*: two tiles for the N = d_model LayerNorm + query projection under a busy device — no change;
     // four tiles for the residual projections — spills at their 1024-thread launch bound, -17 %)
+    return NTB;
+}
+// gemv2_cfg, third decision: row tiles, whether the fp16 rows are staged through LDS, and the LDS budget
+static bool gemv2_cfg_staging(const GemvParams& p, int KTf, Gemv2Cfg& c) {
     c.MT = (p.M + 15) / 16;
     c.shm = sizeof(float) * (size_t)c.nw * c.NTB * c.MT * 256;
     const size_t xs_bytes = (size_t)p.M * (KTf * 32 + 8) * sizeof(half_t);    // fp16 activation rows
@@ -1253,61 +1246,121 @@ static Gemv2Cfg gemv2_cfg(const GemvParams& p) {
     const size_t xstage_max = (p.Mtot > 0 && p.rt_nz > 0) ? (size_t)WLX_G2_LDS_MAX : (size_t)64 * 1024;
     if (p.in_mode == GEMV_IN_F16 && (c.MT > 1 || c.shm + xs_bytes > xstage_max)) c.xstage = false;   // fragments from global instead
     if (c.xstage) c.shm += xs_bytes;
-    if (c.shm > WLX_G2_LDS_MAX) return c;                              // beyond a CU's LDS (160 KiB, less a margin): older kernel
-    if (c.shm > 64 * 1024 && g_lds_optin_refused.load(std::memory_order_relaxed)) return c;   // the device refused the raised limit once
-    c.ok = true;
+    if (c.shm > WLX_G2_LDS_MAX) return false;                          // beyond a CU's LDS (160 KiB, less a margin): older kernel
+    if (c.shm > 64 * 1024 && g_lds_optin_refused.load(std::memory_order_relaxed)) return false;   // the device refused the raised limit once
+    return true;
+}
+// what the lean kernel takes at all, then the three decisions in sequence; ok = false: the first-generation kernel
+static Gemv2Cfg gemv2_cfg(const GemvParams& p) {
+    Gemv2Cfg c{};
+    if (g_decode_v1 || p.M > 48 || p.M < 1) return c;
+    if (p.bias ? (p.N & 15) != 0 : p.out_mode != GEMV_OUT_F32) return c;      // bias <=> not the vocabulary projection
+    const bool combo = (p.in_mode == GEMV_IN_LN && (p.out_mode == GEMV_OUT_QKV || p.out_mode == GEMV_OUT_F16 ||
+                                                    p.out_mode == GEMV_OUT_GELU_F16 || p.out_mode == GEMV_OUT_F32)) ||
+                       (p.in_mode != GEMV_IN_LN && p.out_mode == GEMV_OUT_RESID) ||
+                       (p.in_mode == GEMV_IN_F16 && p.out_mode == GEMV_OUT_SLAB);
+    if (!combo || p.K != p.KT * 32) return c;
+    // sources other than the plain rows: one row tile, and only where the kernel is instantiated for them
+    if (p.xsrc != GEMV_X_PLAIN) {
+        const bool ln_ok = p.in_mode == GEMV_IN_LN && p.out_mode == GEMV_OUT_QKV;
+        const bool res_ok = p.in_mode == GEMV_IN_F16 && p.out_mode == GEMV_OUT_RESID && p.xsrc == GEMV_X_SLABS;
+        if (!(ln_ok || res_ok)) return c;
+    }
+    int KTf = p.KT;                                                           // k-tiles one workgroup multiplies
+    if (p.out_mode == GEMV_OUT_SLAB) {
+        if (p.KTS < 1 || p.KT % p.KTS || p.KT / p.KTS != WLX_FC2_KS) return c;
+        KTf = p.KTS;
+    }
+    if (!gemv2_cfg_waves(p, KTf, c)) return c;
+    c.NTB = gemv2_cfg_tiles(p);
+    c.ok = gemv2_cfg_staging(p, KTf, c);
     return c;
 }
 
-template <int CH, int LNV, int MT>
-static bool gemv2_launch_ln(const GemvParams& p, const Gemv2Cfg& c, dim3 grid, dim3 block, hipStream_t s) {
-#define WLX_G2(OUT_, NTB_, XS_) g2_launch<CH, LNV, GEMV_IN_LN, OUT_, NTB_, MT, XS_>(grid, block, c.shm, s, p)
-    switch (p.out_mode) {
-        case GEMV_OUT_QKV:
-            if (c.NTB == 4 && MT == 1) { g2_launch<CH, LNV, GEMV_IN_LN, GEMV_OUT_QKV, 4, 1, GEMV_X_PLAIN>(grid, block, c.shm, s, p); return true; }
-            if (c.NTB == 2) WLX_G2(GEMV_OUT_QKV, 2, GEMV_X_PLAIN);
-            else WLX_G2(GEMV_OUT_QKV, 1, GEMV_X_PLAIN);
-            return true;
-        case GEMV_OUT_F16:
-            WLX_G2(GEMV_OUT_F16, 1, GEMV_X_PLAIN); return true;
-        case GEMV_OUT_GELU_F16:
-            if (c.NTB == 4 && MT == 1) { g2_launch<CH, LNV, GEMV_IN_LN, GEMV_OUT_GELU_F16, 4, 1, GEMV_X_PLAIN>(grid, block, c.shm, s, p); return true; }
-            if (c.NTB == 2) WLX_G2(GEMV_OUT_GELU_F16, 2, GEMV_X_PLAIN);
-            else WLX_G2(GEMV_OUT_GELU_F16, 1, GEMV_X_PLAIN);
-            return true;
-        case GEMV_OUT_F32:
-            if (c.NTB == 2) WLX_G2(GEMV_OUT_F32, 2, GEMV_X_PLAIN);
-            else WLX_G2(GEMV_OUT_F32, 1, GEMV_X_PLAIN);
-            return true;
-        default: return false;
+// ---- THE dispatch of dec_gemv2_kernel: one walk from (parameters, configuration) to the template arguments <CH, LNV, IN, OUT, NTB, MT, XS>,
+// handed to `leaf` as a G2Args value. gemv2_ok (leaf: say yes), gemv2_launch (leaf: g2_launch) and dec_gemv_kernel_name (leaf: print the
+// arguments) all go through it, so what is probed, what runs and what is named cannot differ. false: no instantiation for this configuration.
+template <int CH_, int LNV_, int IN_, int OUT_, int NTB_, int MT_, int XS_>
+struct G2Args { static constexpr int CH = CH_, LNV = LNV_, IN = IN_, OUT = OUT_, NTB = NTB_, MT = MT_, XS = XS_; };
+// The rows a launch reads decide which (CH, LNV) pairs and which output modes exist: LayerNorm over slab / embedding rows (a layer's first
+// projection), LayerNorm over plain rows, or no LayerNorm (fp16 rows in, split combine).
+enum G2Rows { G2_LN_XS, G2_LN_PLAIN, G2_NO_LN };
+// LayerNorm over plain rows: column tiles per workgroup, NTBMAX = what the output mode is instantiated for (four tiles: one row tile only)
+template <int CH, int LNV, int OUT, int MT, int NTBMAX, class Leaf>
+static bool gemv2_dispatch_ntb(const Gemv2Cfg& c, Leaf& leaf) {
+    if (c.NTB == 1) return leaf(G2Args<CH, LNV, GEMV_IN_LN, OUT, 1, MT, GEMV_X_PLAIN>{});
+    if constexpr (NTBMAX >= 2) { if (c.NTB == 2) return leaf(G2Args<CH, LNV, GEMV_IN_LN, OUT, 2, MT, GEMV_X_PLAIN>{}); }
+    if constexpr (NTBMAX >= 4 && MT == 1) { if (c.NTB == 4) return leaf(G2Args<CH, LNV, GEMV_IN_LN, OUT, 4, 1, GEMV_X_PLAIN>{}); }
+    return false;
+}
+template <int ROWS, int CH, int LNV, int MT, class Leaf>
+static bool gemv2_dispatch_modes(const GemvParams& p, const Gemv2Cfg& c, Leaf& leaf) {
+    if constexpr (ROWS == G2_LN_XS) {                 // one column tile, QKV only
+        if (p.out_mode != GEMV_OUT_QKV || c.NTB != 1) return false;
+        if (p.xsrc == GEMV_X_SLABS) return leaf(G2Args<CH, LNV, GEMV_IN_LN, GEMV_OUT_QKV, 1, MT, GEMV_X_SLABS>{});
+        return p.xsrc == GEMV_X_EMBED && leaf(G2Args<CH, LNV, GEMV_IN_LN, GEMV_OUT_QKV, 1, MT, GEMV_X_EMBED>{});
+    } else if constexpr (ROWS == G2_LN_PLAIN) {
+        switch (p.out_mode) {
+            case GEMV_OUT_QKV: return gemv2_dispatch_ntb<CH, LNV, GEMV_OUT_QKV, MT, 4>(c, leaf);
+            case GEMV_OUT_F16: return gemv2_dispatch_ntb<CH, LNV, GEMV_OUT_F16, MT, 1>(c, leaf);
+            case GEMV_OUT_GELU_F16: return gemv2_dispatch_ntb<CH, LNV, GEMV_OUT_GELU_F16, MT, 4>(c, leaf);
+            case GEMV_OUT_F32: return gemv2_dispatch_ntb<CH, LNV, GEMV_OUT_F32, MT, 2>(c, leaf);
+            default: return false;
+        }
+    } else {
+        if (p.in_mode == GEMV_IN_XATTN) {             // the split combine: at most six k-tiles per wave (two items peeled per lane)
+            if constexpr (CH <= 6) { if (p.out_mode == GEMV_OUT_RESID && p.xsrc == GEMV_X_PLAIN && c.NTB == 1) return leaf(G2Args<CH, 1, GEMV_IN_XATTN, GEMV_OUT_RESID, 1, MT, GEMV_X_PLAIN>{}); }
+            return false;
+        }
+        if (p.in_mode != GEMV_IN_F16) return false;
+        if (p.out_mode == GEMV_OUT_SLAB) return p.xsrc == GEMV_X_PLAIN && c.NTB == 1 && leaf(G2Args<CH, 1, GEMV_IN_F16, GEMV_OUT_SLAB, 1, MT, GEMV_X_PLAIN>{});
+        if (p.out_mode != GEMV_OUT_RESID) return false;
+        if (p.xsrc == GEMV_X_SLABS) return c.NTB == 1 && leaf(G2Args<CH, 1, GEMV_IN_F16, GEMV_OUT_RESID, 1, MT, GEMV_X_SLABS>{});
+        if (p.xsrc != GEMV_X_PLAIN) return false;
+        if (c.NTB == 1) return leaf(G2Args<CH, 1, GEMV_IN_F16, GEMV_OUT_RESID, 1, MT, GEMV_X_PLAIN>{});
+        if constexpr (MT == 1) { if (c.NTB == 2) return leaf(G2Args<CH, 1, GEMV_IN_F16, GEMV_OUT_RESID, 2, 1, GEMV_X_PLAIN>{}); }   // (row tiles under a busy device)
+        return false;
     }
-#undef WLX_G2
 }
-// the first projection of a layer reading slab / embedding rows (one row tile): its own (CH, LNV) pairs, see gemv2_cfg
-template <int CH, int LNV, int MT>
-static bool gemv2_launch_qkv_xs_mt(const GemvParams& p, const Gemv2Cfg& c, dim3 grid, dim3 block, hipStream_t s) {
-    if (p.xsrc == GEMV_X_SLABS) g2_launch<CH, LNV, GEMV_IN_LN, GEMV_OUT_QKV, 1, MT, GEMV_X_SLABS>(grid, block, c.shm, s, p);
-    else g2_launch<CH, LNV, GEMV_IN_LN, GEMV_OUT_QKV, 1, MT, GEMV_X_EMBED>(grid, block, c.shm, s, p);
+// one (CH, LNV) pair of a list below; MTMAX = 3: any row-tile count of a 48-row chunk, 1: one row tile only (the wide chunks, d_model 384)
+template <int ROWS, int CH, int LNV, int MTMAX, class Leaf>
+static bool gemv2_dispatch_pair(const GemvParams& p, const Gemv2Cfg& c, Leaf& leaf) {
+    if (c.CH != CH || c.LNV != LNV) return false;
+    if (c.MT == 1) return gemv2_dispatch_modes<ROWS, CH, LNV, 1>(p, c, leaf);
+    if constexpr (MTMAX == 3) return c.MT == 2 ? gemv2_dispatch_modes<ROWS, CH, LNV, 2>(p, c, leaf) : c.MT == 3 && gemv2_dispatch_modes<ROWS, CH, LNV, 3>(p, c, leaf);
+    return false;
+}
+// The (CH, LNV) pairs that exist, once. The Whisper family: d_model 384 (2,15), 512 (4,2), 768 (6,3), 1024 (4,4) / (8,4), 1280 (5,5) / (10,5);
+// slab / embedding rows run one row per wave, hence their narrower chunks (gemv2_cfg_waves). At most one pair of a list matches a configuration.
+template <class Leaf>
+static bool gemv2_dispatch(const GemvParams& p, const Gemv2Cfg& c, Leaf leaf) {
+    if (p.in_mode == GEMV_IN_LN && p.xsrc != GEMV_X_PLAIN)
+        return gemv2_dispatch_pair<G2_LN_XS, 4, 3, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_XS, 3, 3, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_XS, 2, 2, 3>(p, c, leaf) ||
+               gemv2_dispatch_pair<G2_LN_XS, 4, 4, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_XS, 5, 5, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_XS, 2, 15, 1>(p, c, leaf) ||
+               gemv2_dispatch_pair<G2_LN_XS, 6, 3, 1>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_XS, 8, 4, 1>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_XS, 10, 5, 1>(p, c, leaf);
+    if (p.in_mode == GEMV_IN_LN)
+        return gemv2_dispatch_pair<G2_LN_PLAIN, 6, 3, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_PLAIN, 5, 5, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_PLAIN, 4, 2, 3>(p, c, leaf) ||
+               gemv2_dispatch_pair<G2_LN_PLAIN, 4, 4, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_PLAIN, 10, 5, 1>(p, c, leaf) || gemv2_dispatch_pair<G2_LN_PLAIN, 8, 4, 1>(p, c, leaf) ||
+               gemv2_dispatch_pair<G2_LN_PLAIN, 2, 15, 1>(p, c, leaf);   // (2,15), one row tile: batched rows run as row tiles
+    // no LayerNorm: 8 / 10 / 12 k-tiles per wave with fp16 rows in and one row tile only. gemv2_cfg_waves searches CH in {12, 10, 8, 6, 5, 4}
+    // here: no other value arrives (the pick sweep, tests/test_gemv_picks.py).
+    return gemv2_dispatch_pair<G2_NO_LN, 12, 1, 1>(p, c, leaf) || gemv2_dispatch_pair<G2_NO_LN, 10, 1, 1>(p, c, leaf) || gemv2_dispatch_pair<G2_NO_LN, 8, 1, 1>(p, c, leaf) ||
+           gemv2_dispatch_pair<G2_NO_LN, 6, 1, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_NO_LN, 5, 1, 3>(p, c, leaf) || gemv2_dispatch_pair<G2_NO_LN, 4, 1, 3>(p, c, leaf);
+}
+// Instantiated and never dispatched (the split combine stops at six k-tiles per wave): kept so that the set of kernels in the code object
+// stays what it was; pruning them is a change of its own.
+template __global__ void dec_gemv2_kernel<12, 1, GEMV_IN_XATTN, GEMV_OUT_RESID, 1, 1, GEMV_X_PLAIN>(GemvParams);
+template __global__ void dec_gemv2_kernel<10, 1, GEMV_IN_XATTN, GEMV_OUT_RESID, 1, 1, GEMV_X_PLAIN>(GemvParams);
+template __global__ void dec_gemv2_kernel<8, 1, GEMV_IN_XATTN, GEMV_OUT_RESID, 1, 1, GEMV_X_PLAIN>(GemvParams);
+
+// the lean kernel runs these parameters (of one row chunk: gemv_chunked) with configuration *out
+static bool gemv2_ok(const GemvParams& p, Gemv2Cfg* out) {
+    const Gemv2Cfg c = gemv2_cfg(p);
+    if (!c.ok || !gemv2_dispatch(p, c, [](auto) { return true; })) return false;   // (the probe leaf: instantiates nothing)
+    if (out) *out = c;
     return true;
 }
-template <int CH, int LNV>
-static bool gemv2_launch_qkv_xs(const GemvParams& p, const Gemv2Cfg& c, dim3 grid, dim3 block, hipStream_t s) {
-    return c.MT == 1 ? gemv2_launch_qkv_xs_mt<CH, LNV, 1>(p, c, grid, block, s)
-         : c.MT == 2 ? gemv2_launch_qkv_xs_mt<CH, LNV, 2>(p, c, grid, block, s)
-                     : gemv2_launch_qkv_xs_mt<CH, LNV, 3>(p, c, grid, block, s);
-}
-template <int CH, int MT>
-static bool gemv2_launch_other(const GemvParams& p, const Gemv2Cfg& c, dim3 grid, dim3 block, hipStream_t s) {
-    if (p.in_mode == GEMV_IN_F16) {
-        if (p.out_mode == GEMV_OUT_SLAB) { g2_launch<CH, 1, GEMV_IN_F16, GEMV_OUT_SLAB, 1, MT, GEMV_X_PLAIN>(grid, block, c.shm, s, p); return true; }
-        if (p.xsrc == GEMV_X_SLABS) { g2_launch<CH, 1, GEMV_IN_F16, GEMV_OUT_RESID, 1, MT, GEMV_X_SLABS>(grid, block, c.shm, s, p); return true; }
-        if (c.NTB == 2 && MT == 1) { g2_launch<CH, 1, GEMV_IN_F16, GEMV_OUT_RESID, 2, 1, GEMV_X_PLAIN>(grid, block, c.shm, s, p); return true; }
-        g2_launch<CH, 1, GEMV_IN_F16, GEMV_OUT_RESID, 1, MT, GEMV_X_PLAIN>(grid, block, c.shm, s, p);
-    } else g2_launch<CH, 1, GEMV_IN_XATTN, GEMV_OUT_RESID, 1, MT, GEMV_X_PLAIN>(grid, block, c.shm, s, p);
-    return true;
-}
-// the (CH, LNV) pairs of the Whisper family: d_model 512 (4,2), 768 (6,3), 1024 (4,4), 1280 (5,5)
-static bool gemv2_launch(const GemvParams& p0, const Gemv2Cfg& c, hipStream_t s) {
+static void gemv2_launch(const GemvParams& p0, const Gemv2Cfg& c, hipStream_t s) {
     GemvParams p = p0;
     p.KTW = c.CH * c.NCH; p.NCH = c.NCH; p.xstage = c.xstage ? 1 : 0; p.nwm = c.nw;
 #ifdef WLX_TRACE
@@ -1327,57 +1380,8 @@ static bool gemv2_launch(const GemvParams& p0, const Gemv2Cfg& c, hipStream_t s)
         const int want = (p.M * p.H * 8 + 63) / 64;
         block.x = 64 * std::max(c.nw, std::min(c.MT > 1 ? 8 : 16, want));
     }
-#define WLX_G2_LN(CH_, LNV_) (c.MT == 1 ? gemv2_launch_ln<CH_, LNV_, 1>(p, c, grid, block, s) : c.MT == 2 ? gemv2_launch_ln<CH_, LNV_, 2>(p, c, grid, block, s) : gemv2_launch_ln<CH_, LNV_, 3>(p, c, grid, block, s))
-#define WLX_G2_OT(CH_) (c.MT == 1 ? gemv2_launch_other<CH_, 1>(p, c, grid, block, s) : c.MT == 2 ? gemv2_launch_other<CH_, 2>(p, c, grid, block, s) : gemv2_launch_other<CH_, 3>(p, c, grid, block, s))
-    if (p.in_mode == GEMV_IN_LN && p.xsrc != GEMV_X_PLAIN) {
-        if (c.CH == 4 && c.LNV == 3) return gemv2_launch_qkv_xs<4, 3>(p, c, grid, block, s);
-        if (c.CH == 3 && c.LNV == 3) return gemv2_launch_qkv_xs<3, 3>(p, c, grid, block, s);
-        if (c.CH == 2 && c.LNV == 2) return gemv2_launch_qkv_xs<2, 2>(p, c, grid, block, s);
-        if (c.CH == 2 && c.LNV == 15) return c.MT == 1 ? gemv2_launch_qkv_xs_mt<2, 15, 1>(p, c, grid, block, s) : false;
-        if (c.CH == 4 && c.LNV == 4) return gemv2_launch_qkv_xs<4, 4>(p, c, grid, block, s);
-        if (c.CH == 5 && c.LNV == 5) return gemv2_launch_qkv_xs<5, 5>(p, c, grid, block, s);
-        if (c.CH == 6 && c.LNV == 3) return c.MT == 1 ? gemv2_launch_qkv_xs_mt<6, 3, 1>(p, c, grid, block, s) : false;
-        if (c.CH == 8 && c.LNV == 4) return c.MT == 1 ? gemv2_launch_qkv_xs_mt<8, 4, 1>(p, c, grid, block, s) : false;
-        if (c.CH == 10 && c.LNV == 5) return c.MT == 1 ? gemv2_launch_qkv_xs_mt<10, 5, 1>(p, c, grid, block, s) : false;
-        return false;
-    }
-    if (p.in_mode == GEMV_IN_LN) {
-        if (c.CH == 6 && c.LNV == 3) return WLX_G2_LN(6, 3);
-        if (c.CH == 5 && c.LNV == 5) return WLX_G2_LN(5, 5);
-        if (c.CH == 10 && c.LNV == 5) return c.MT == 1 ? gemv2_launch_ln<10, 5, 1>(p, c, grid, block, s) : false;
-        if (c.CH == 8 && c.LNV == 4) return c.MT == 1 ? gemv2_launch_ln<8, 4, 1>(p, c, grid, block, s) : false;
-        if (c.CH == 4 && c.LNV == 2) return WLX_G2_LN(4, 2);
-        if (c.CH == 4 && c.LNV == 4) return WLX_G2_LN(4, 4);
-        if (c.CH == 2 && c.LNV == 15) return c.MT == 1 ? gemv2_launch_ln<2, 15, 1>(p, c, grid, block, s) : false;   // (one row tile: batched rows run as row tiles)
-        return false;
-    }
-    switch (c.CH) {
-        case 12: return c.MT == 1 && p.in_mode == GEMV_IN_F16 ? gemv2_launch_other<12, 1>(p, c, grid, block, s) : false;
-        case 10: return c.MT == 1 && p.in_mode == GEMV_IN_F16 ? gemv2_launch_other<10, 1>(p, c, grid, block, s) : false;
-        case 8: return c.MT == 1 && p.in_mode == GEMV_IN_F16 ? gemv2_launch_other<8, 1>(p, c, grid, block, s) : false;
-        case 6: return WLX_G2_OT(6);
-        case 5: return WLX_G2_OT(5);
-        default: return WLX_G2_OT(4);
-    }
-#undef WLX_G2_LN
-#undef WLX_G2_OT
-}
-static bool gemv2_ok(const GemvParams& p, Gemv2Cfg* out) {
-    const Gemv2Cfg c = gemv2_cfg(p);
-    if (!c.ok) return false;
-    if (p.in_mode == GEMV_IN_LN && p.xsrc != GEMV_X_PLAIN) {
-        const bool pair = (c.CH == 4 && c.LNV == 3) || (c.CH == 3 && c.LNV == 3) || (c.CH == 2 && c.LNV == 2) || (c.CH == 4 && c.LNV == 4) || (c.CH == 5 && c.LNV == 5) ||
-                          (c.MT == 1 && ((c.CH == 6 && c.LNV == 3) || (c.CH == 8 && c.LNV == 4) || (c.CH == 10 && c.LNV == 5))) ||
-                          (c.CH == 2 && c.LNV == 15 && c.MT == 1);
-        if (!pair) return false;
-    } else if (p.in_mode == GEMV_IN_LN) {
-        const bool pair = (c.CH == 6 && c.LNV == 3) || (c.CH == 5 && c.LNV == 5) || (c.CH == 4 && c.LNV == 2) || (c.CH == 4 && c.LNV == 4) ||
-                          (c.CH == 10 && c.LNV == 5 && c.MT == 1) || (c.CH == 8 && c.LNV == 4 && c.MT == 1) ||
-                          (c.CH == 2 && c.LNV == 15 && c.MT == 1);
-        if (!pair) return false;
-    }
-    if (out) *out = c;
-    return true;
+    const bool launched = gemv2_dispatch(p, c, [&](auto a) { using A = decltype(a); g2_launch<A::CH, A::LNV, A::IN, A::OUT, A::NTB, A::MT, A::XS>(grid, block, c.shm, s, p); return true; });
+    if (!launched) dispatch_bug("dec_gemv2_kernel", s);
 }
 // more than 48 rows (prompt prefill): the lean kernel in row chunks of 48 (grid.z), configured for a full chunk
 // 17..WLX_ROWTILE_MAX rows (batched decode steps): row chunks of one 16-row tile folded into blockIdx.x (round 4, see
@@ -1428,8 +1432,6 @@ static GemvParams gemv_chunked(const GemvParams& p) {
 // 0.913 / 1.365 ms on the 16-row tiles; large-v3 at 80 / 160 rows: 3.61 / 4.85 against 3.06 / 5.03 ms — the three LayerNorm launches per layer
 // (2 us each) and the 64-row workgroups' lower occupancy cost what the saved L2 re-reads give back; only large-v3 at 160 rows gains (3.6 %).
 // profiles/r6c_wide_rows_*, r6d_wide_rows_*; DESIGN.md §7.3 B4. The 16-row tiles stay.)
-static bool vocab2_ok(const GemvParams& p);   // (dec_vocab_kernel, below)
-bool dec_gemv_is_lean(const GemvParams& p) { return vocab2_ok(p) || gemv2_ok(gemv_chunked(p), nullptr); }
 
 int dec_gemv_slab_split(int M, int K, int N) {
     if (WLX_FC2_KS < 2) return 0;                                             // (the slab count is a compile-time constant of the consumers: -DWLX_FC2_KS)
@@ -1442,25 +1444,6 @@ int dec_gemv_slab_split(int M, int K, int N) {
     Gemv2Cfg c;
     if (!gemv2_ok(p, &c) || (p.M <= 16 && !c.xstage)) return 0;
     return WLX_FC2_KS;
-}
-
-static bool vocab2_ok(const GemvParams& p);   // (dec_vocab_kernel, below)
-static int vocab2_chunk_rows(int K);
-const char* dec_gemv_kernel_name(const GemvParams& p_any) {
-    static thread_local char buf[64];
-    if (vocab2_ok(p_any)) {
-        snprintf(buf, sizeof(buf), "dec_vocab_kernel<%d, %d, %d>", p_any.KT, p_any.KT == 24 ? 6 : p_any.KT == 40 ? 5 : p_any.KT == 12 ? 3 : 4, (std::min(p_any.M, vocab2_chunk_rows(p_any.K)) + 15) / 16);
-        return buf;
-    }
-    const GemvParams p = gemv_chunked(p_any);
-    const int MT = (p.M + 15) / 16;
-    Gemv2Cfg c2;
-    if (gemv2_ok(p, &c2)) {
-        snprintf(buf, sizeof(buf), "dec_gemv2_kernel<%d, %d, %d, %d, %d, %d, %d>", c2.CH, c2.LNV ? c2.LNV : 1, p.in_mode, p.out_mode, c2.NTB, c2.MT, p.xsrc);
-        return buf;
-    }
-    snprintf(buf, sizeof(buf), "dec_gemv_kernel<%d, %d, %d>", MT > 4 ? 4 : MT, MT == 1 ? 2 : 1, p.in_mode);
-    return buf;
 }
 
 // ------------------------------------------------------------------ vocabulary projection: final LayerNorm + tied output projection
@@ -1635,34 +1618,36 @@ __global__ __launch_bounds__(512) void dec_vocab_kernel(VocabParams p) {
     WLX_TR_END(p.trc);
 }
 
-template <int KT, int KC, int MT, bool SLABS = false>
+template <int KT, int KC, int MT, bool SLABS>
 static void vocab_go(const VocabParams& p, hipStream_t s) {
     const size_t shm = (size_t)p.M * (KT * 32 + 8) * sizeof(half_t);
     if (shm > 64 * 1024) {          // > 64 KiB of dynamic LDS: opt in once per device (first launch of a shape happens outside capture)
         static std::atomic<signed char> granted[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev >= 0 && dev < 64 && granted[dev].load(std::memory_order_acquire) == 0) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_vocab_kernel<KT, KC, MT, SLABS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    WLX_G2_LDS_MAX) == hipSuccess) granted[dev].store(1, std::memory_order_release);
-            else {                  // this launch fails with the runtime's own error (reported for THIS call); later calls take the general kernel (vocab2_ok)
-                (void)hipGetLastError();
-                g_lds_optin_refused.store(true);
-                fprintf(stderr, "[wlx] device %d refused %d KiB of dynamic LDS: the batched vocabulary projection falls back to the general kernel\n", dev, WLX_G2_LDS_MAX / 1024);
-            }
-        }
+        lds_optin(reinterpret_cast<const void*>(&dec_vocab_kernel<KT, KC, MT, SLABS>), granted, "the batched vocabulary projection falls back");
     }
     const int pairs = (p.NT + 1) / 2;
     hipLaunchKernelGGL((dec_vocab_kernel<KT, KC, MT, SLABS>), dim3((pairs + 7) / 8), dim3(512), shm, s, p);
 }
-template <int KT, int KC>
-static void vocab_go_mt(const VocabParams& p, hipStream_t s) {
-    if (p.slab) { vocab_go<KT, KC, 1, true>(p, s); return; }        // (vocab2_ok: one row tile)
-    switch ((p.M + 15) / 16) {
-        case 1: vocab_go<KT, KC, 1>(p, s); break;
-        case 2: vocab_go<KT, KC, 2>(p, s); break;
-        case 3: vocab_go<KT, KC, 3>(p, s); break;
-        default: vocab_go<KT, KC, 4>(p, s); break;
+// ---- THE dispatch of dec_vocab_kernel, as gemv2_dispatch: vocab2_ok, vocab2_launch and dec_gemv_kernel_name go through it
+template <int KT_, int KC_, int MT_, bool SLABS_>
+struct VocabArgs { static constexpr int KT = KT_, KC = KC_, MT = MT_; static constexpr bool SLABS = SLABS_; };
+// row tiles of one launch: 1..4; rows + slabs: decode steps of one row tile
+template <int KT, int KC, class Leaf>
+static bool vocab2_dispatch_mt(int MT, bool slabs, Leaf& leaf) {
+    if (slabs) return MT == 1 && leaf(VocabArgs<KT, KC, 1, true>{});
+    return MT == 1 ? leaf(VocabArgs<KT, KC, 1, false>{}) : MT == 2 ? leaf(VocabArgs<KT, KC, 2, false>{}) : MT == 3 ? leaf(VocabArgs<KT, KC, 3, false>{})
+         : MT == 4 ? leaf(VocabArgs<KT, KC, 4, false>{}) : false;
+}
+// the KT -> KC table, once: the d_model of the Whisper family as an even number of chunks of KC k-tiles
+template <class Leaf>
+static bool vocab2_dispatch(int KT, int MT, bool slabs, Leaf leaf) {
+    switch (KT) {
+        case 12: return vocab2_dispatch_mt<12, 3>(MT, slabs, leaf);
+        case 16: return vocab2_dispatch_mt<16, 4>(MT, slabs, leaf);
+        case 24: return vocab2_dispatch_mt<24, 6>(MT, slabs, leaf);
+        case 32: return vocab2_dispatch_mt<32, 4>(MT, slabs, leaf);
+        case 40: return vocab2_dispatch_mt<40, 5>(MT, slabs, leaf);
+        default: return false;
     }
 }
 // rows one launch of dec_vocab_kernel takes: its fp16 LayerNorm rows must fit the workgroup's LDS (152 KiB: d_model <= 1024 64 rows,
@@ -1677,8 +1662,8 @@ static bool vocab2_ok(const GemvParams& p) {
     if (g_decode_v1 || p.in_mode != GEMV_IN_LN || p.out_mode != GEMV_OUT_F32 || p.bias || p.Mtot != 0) return false;
     if (p.xsrc != GEMV_X_PLAIN && !(p.xsrc == GEMV_X_SLABS && p.M <= 16 && p.slab != nullptr)) return false;   // rows + slabs: decode steps of one row tile
     if (p.M < 1 || p.M > WLX_MAX_DEC_ROWS || p.K != p.KT * 32 || p.N < 256) return false;
-    if (!(p.KT == 12 || p.KT == 16 || p.KT == 24 || p.KT == 32 || p.KT == 40)) return false;
     const int rows = std::min(p.M, vocab2_chunk_rows(p.K));
+    if (!vocab2_dispatch(p.KT, (rows + 15) / 16, p.xsrc == GEMV_X_SLABS, [](auto) { return true; })) return false;
     const size_t shm = (size_t)rows * (p.K + 8) * sizeof(half_t);
     if (shm > 64 * 1024 && g_lds_optin_refused.load(std::memory_order_relaxed)) return false;   // the device refused the raised LDS limit once: general kernel
     return shm <= WLX_G2_LDS_MAX;
@@ -1693,13 +1678,8 @@ static void vocab2_launch(const GemvParams& g, hipStream_t s) {
 #ifdef WLX_TRACE
         p.trc = trace_next("vocab2");
 #endif
-        switch (g.KT) {
-            case 12: vocab_go_mt<12, 3>(p, s); break;
-            case 16: vocab_go_mt<16, 4>(p, s); break;
-            case 24: vocab_go_mt<24, 6>(p, s); break;
-            case 32: vocab_go_mt<32, 4>(p, s); break;
-            default: vocab_go_mt<40, 5>(p, s); break;
-        }
+        const bool launched = vocab2_dispatch(g.KT, (p.M + 15) / 16, g.xsrc == GEMV_X_SLABS, [&](auto a) { using A = decltype(a); vocab_go<A::KT, A::KC, A::MT, A::SLABS>(p, s); return true; });
+        if (!launched) { dispatch_bug("dec_vocab_kernel", s); return; }
     }
 }
 
@@ -1712,18 +1692,39 @@ static void gemv_dispatch_in(const GemvParams& p, dim3 grid, dim3 block, size_t 
     }
 }
 
-void launch_dec_gemv(const GemvParams& p_any, hipStream_t s) {
-    if (vocab2_ok(p_any)) { vocab2_launch(p_any, s); return; }
+bool dec_gemv_is_lean(const GemvParams& p) { return vocab2_ok(p) || gemv2_ok(gemv_chunked(p), nullptr); }
+
+// the name leaf of the two dispatches: the template arguments of the instantiation launch_dec_gemv runs, not a second account of them
+const char* dec_gemv_kernel_name(const GemvParams& p_any) {
+    static thread_local char buf[64];
+    if (vocab2_ok(p_any)) {
+        vocab2_dispatch(p_any.KT, (std::min(p_any.M, vocab2_chunk_rows(p_any.K)) + 15) / 16, p_any.xsrc == GEMV_X_SLABS,
+                        [&](auto a) { using A = decltype(a); snprintf(buf, sizeof(buf), "dec_vocab_kernel<%d, %d, %d>", A::KT, A::KC, A::MT); return true; });
+        return buf;
+    }
+    const GemvParams p = gemv_chunked(p_any);
     Gemv2Cfg c2;
-    const GemvParams pc = gemv_chunked(p_any);
-    if (gemv2_ok(pc, &c2) && gemv2_launch(pc, c2, s)) return;
-    if (p_any.M > 16 * WLX_MAX_MT) {
+    if (gemv2_ok(p, &c2)) {
+        gemv2_dispatch(p, c2, [&](auto a) { using A = decltype(a); snprintf(buf, sizeof(buf), "dec_gemv2_kernel<%d, %d, %d, %d, %d, %d, %d>", A::CH, A::LNV, A::IN, A::OUT, A::NTB, A::MT, A::XS); return true; });
+        return buf;
+    }
+    const int MT = (p.M + 15) / 16;
+    snprintf(buf, sizeof(buf), "dec_gemv_kernel<%d, %d, %d>", MT > 4 ? 4 : MT, MT == 1 ? 2 : 1, p.in_mode);
+    return buf;
+}
+
+void launch_dec_gemv(const GemvParams& p, hipStream_t s) {
+    if (vocab2_ok(p)) { vocab2_launch(p, s); return; }
+    Gemv2Cfg c2;
+    const GemvParams pc = gemv_chunked(p);
+    if (gemv2_ok(pc, &c2)) { gemv2_launch(pc, c2, s); return; }   // (from here on the first-generation kernel: it knows neither xsrc nor GEMV_OUT_SLAB)
+    if (p.M > 16 * WLX_MAX_MT) {
         // the general kernel holds WLX_MAX_MT row tiles per launch: a wider pass (round 5) runs as consecutive row chunks on rebased row
         // pointers (64 rows; the split-combine prologue indexes its partials by (item, row in item), so its chunks are whole items)
-        const int CHK = (p_any.in_mode == GEMV_IN_XATTN && p_any.R > 0) ? (16 * WLX_MAX_MT / p_any.R) * p_any.R : 16 * WLX_MAX_MT;
-        for (int r0 = 0; r0 < p_any.M; r0 += CHK) {
-            GemvParams q = p_any;
-            q.M = std::min(CHK, p_any.M - r0);
+        const int CHK = (p.in_mode == GEMV_IN_XATTN && p.R > 0) ? (16 * WLX_MAX_MT / p.R) * p.R : 16 * WLX_MAX_MT;
+        for (int r0 = 0; r0 < p.M; r0 += CHK) {
+            GemvParams q = p;
+            q.M = std::min(CHK, p.M - r0);
             if (q.X) q.X += (long)r0 * q.ldx;
             if (q.Xh) q.Xh += (long)r0 * q.ldxh;
             if (q.Yh) q.Yh += (long)r0 * q.ldyh;
@@ -1740,8 +1741,6 @@ void launch_dec_gemv(const GemvParams& p_any, hipStream_t s) {
         }
         return;
     }
-    const GemvParams& p0 = p_any;
-    const GemvParams& p = p0;
     const int MT = (p.M + 15) / 16;
     const int NT_total = (p.N + 15) / 16;
     // waves per workgroup: enough K-split that each wave streams <= GV_CH k-tiles per chunk and,
