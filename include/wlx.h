@@ -63,7 +63,8 @@ typedef enum {
     WLX_ERR_HIP = 2,      /* a HIP runtime call failed */
     WLX_ERR_WEIGHT = 3,   /* missing / mis-shaped weight tensor */
     WLX_ERR_STATE = 4,    /* call order (e.g. generate before encode) */
-    WLX_ERR_NOMEM = 5
+    WLX_ERR_NOMEM = 5,
+    WLX_ERR_TOO_SHORT = 6 /* speaker embedding: under 0.3 s of audio (the caller labels the segment with no speaker) */
 } wlx_status;
 
 /* Whisper architecture. n_audio_ctx = 1500, n_text_ctx = 448, head_dim = 64. */
@@ -320,6 +321,30 @@ int32_t wlx_mt_translate(wlx_mt* mt, int32_t slot, int32_t batch, const int32_t*
                          int32_t src_stride, const wlx_mt_gen_opts* opts, int32_t* tokens_out, int32_t tokens_stride,
                          int32_t* n_tokens_out, float* scores_out);
 
+/* ---- speaker embedding (WeSpeaker ResNet34) — PRODUCT entry points of the `enable_diarization` option ----
+ * Replaces the pyannote.audio Inference(window="whole") call of the reference's SpeakerDiarizer._compute_embedding
+ * (whisper_live/diarization.py:100-118): Kaldi filterbank (80 bins, 25 ms / 10 ms, per-bin mean over the frames removed) ->
+ * ResNet (3 x 3 stem, four stages of BasicBlocks) -> statistics pooling -> Linear -> L2 normalisation, all on the device.
+ * Weights: float32 tensors with BatchNorm ALREADY FOLDED into the convolutions and the values rounded to fp16
+ * (whisperlive_amd/spk_weights.py fold()): "conv1.weight" [planes][1][3][3], "conv1.bias", "layer{1..4}.{b}.conv1.weight" /
+ * ".conv1.bias" / ".conv2.weight" / ".conv2.bias", "layer{2..4}.0.shortcut.weight" [C][Cin][1][1] / ".shortcut.bias",
+ * "seg_1.weight" [embed_dim][2 * 8 planes * n_mels / 8], "seg_1.bias". One engine per GPU: it owns a NON-BLOCKING stream and
+ * every buffer of a call of up to max_seconds of audio; concurrent calls are serialised inside. */
+typedef struct {
+    int32_t n_mels;        /* 80; a multiple of 8 */
+    int32_t planes;        /* channels of the stem and the first stage (32); stage L has planes << L */
+    int32_t blocks[4];     /* BasicBlocks per stage: {3, 4, 6, 3} */
+    int32_t embed_dim;     /* 256 */
+    int32_t max_seconds;   /* longest segment of one call (45: the session buffer's cap) */
+    float   pool_eps;      /* std = sqrt(var_unbiased + pool_eps); WeSpeaker's TSTP uses 1e-7 (UNPINNED: no checkpoint to compare) */
+} wlx_spk_spec;
+typedef struct wlx_spk wlx_spk;
+int32_t wlx_spk_create(const wlx_spk_spec* spec, const wlx_tensor* weights, int32_t n_weights, int32_t device, wlx_spk** out);
+void    wlx_spk_destroy(wlx_spk* spk);
+/* L2-normalised embedding out[embed_dim] of 16 kHz mono PCM in [-1, 1]. WLX_ERR_TOO_SHORT under 4800 samples (0.3 s, where the
+ * reference returns no embedding), WLX_ERR_ARG over max_seconds. Returns when the result is final. */
+int32_t wlx_spk_embed(wlx_spk* spk, const float* pcm_f32, int64_t n_samples, float* out);
+
 /* ==== everything below: TEST / PROFILING hooks (used only by tests/, scripts/ and bench.py's roofline leg; not part of
  * the drop-in boundary; the product entry points end here) ================================================================= */
 /* next-token logits [rows, vocab] of the last decoder step executed on the slot */
@@ -374,6 +399,22 @@ int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_t rows, int
  * sinpos[pos[r]] with sinpos float32 [n_pos][d]; x float32 [rows][d] */
 int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vocab, int32_t d, const int32_t* tok, const int32_t* pos,
                            int32_t rows, float scale, const float* sinpos, int32_t n_pos, float* x);
+
+/* speaker engine: device times (HIP events) of the last wlx_spk_embed: filterbank, then network + pooling + head */
+int32_t wlx_spk_debug_timings(wlx_spk* spk, float* fbank_ms, float* net_ms);
+/* speaker engine kernels, one launch each on host arrays, same conventions as the hooks above.
+ * Filterbank of n_samples >= 400 samples: frames_out float32 [T][n_mels] (log-mel, per-bin mean removed) and image_out, its fp16
+ * rounding transposed to [n_mels][T] (what the stem reads), T = 1 + (n_samples - 400) / 160 <= cap_frames. */
+int32_t wlx_spk_debug_fbank(int32_t device, const float* pcm, int64_t n_samples, int32_t n_mels, float* frames_out, uint16_t* image_out,
+                            int32_t cap_frames, int32_t* n_frames_out);
+/* One convolution: in fp16 [H][W][Cin], w float32 [Cout][Cin][ksize][ksize] (rounded to fp16 and packed by the hook as the engine
+ * does), bias float32 [Cout] or null, resid fp16 [OH][OW][Cout] or null, out fp16 [OH][OW][Cout], OH = (H - 1) / stride + 1.
+ * ksize 3 (padding 1) or 1 (padding 0), stride 1 or 2. Cin = 1 runs the stem's vector-ALU kernel (ksize 3, w kept float32, Cout a
+ * multiple of 4); otherwise Cin and Cout are multiples of 32 and the MFMA kernel runs. */
+int32_t wlx_spk_debug_conv(int32_t device, const uint16_t* in, int32_t H, int32_t W, int32_t Cin, const float* w, const float* bias,
+                           const uint16_t* resid, int32_t Cout, int32_t stride, int32_t ksize, int32_t relu, uint16_t* out);
+/* Statistics pooling of x fp16 [F][T][C] over T >= 2 (C a multiple of 64): out float32 [2][C][F], mean then sqrt(var_unbiased + eps) */
+int32_t wlx_spk_debug_pool(int32_t device, const uint16_t* x, int32_t F, int32_t T, int32_t C, float eps, float* out);
 
 /* Whisper kernels, one launch each (csrc/kernel_hooks.hip), same conventions: host arrays (fp16 as uint16 bits), a private stream
  * of `device`, outputs copied in AND out (bytes no thread owns come back unchanged), WLX_ERR_ARG before any launch for every

@@ -15,7 +15,8 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "host.hip", "engine.hip", "vad.hip", "mt.hip", "mt_engine.hip", "kernel_hooks.hip"]
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "host.hip", "engine.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
+           "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
     "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
@@ -23,9 +24,11 @@ EXPORTS = [
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
+    "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
     "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
     "wlx_mt_debug_embed",
+    "wlx_spk_debug_timings", "wlx_spk_debug_fbank", "wlx_spk_debug_conv", "wlx_spk_debug_pool",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
 ]
 
@@ -83,6 +86,14 @@ class wlx_vad_weights(C.Structure):
 class wlx_mt_spec(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("d_model", "n_heads", "enc_layers", "dec_layers", "ffn", "vocab", "max_positions",
                                          "pad_id", "eos_id", "decoder_start_id", "scale_embedding")]
+
+
+class wlx_spk_spec(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("planes", C.c_int32), ("blocks", C.c_int32 * 4), ("embed_dim", C.c_int32),
+                ("max_seconds", C.c_int32), ("pool_eps", C.c_float)]
+
+
+ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
 
 
 class wlx_debug_gemm_args(C.Structure):
@@ -274,6 +285,14 @@ def load() -> C.CDLL:
     lib.wlx_mt_debug_attn.argtypes = [i32, u16p, i64, i64, u16p, i64, u16p, i64, i64, i32p, i32, i32, i32, i32p, i32, i32, u16p, i64, i64]
     lib.wlx_mt_debug_topk.argtypes = [i32, f32p, i32, i32, i32p, i32p, i32, i32, f32p, i32p]
     lib.wlx_mt_debug_embed.argtypes = [i32, f32p, i32, i32, i32p, i32p, i32, C.c_float, f32p, i32, f32p]
+    lib.wlx_spk_create.argtypes = [C.POINTER(wlx_spk_spec), C.POINTER(wlx_tensor), i32, i32, C.POINTER(vp)]
+    lib.wlx_spk_destroy.argtypes = [vp]
+    lib.wlx_spk_destroy.restype = None
+    lib.wlx_spk_embed.argtypes = [vp, f32p, i64, f32p]
+    lib.wlx_spk_debug_timings.argtypes = [vp, f32p, f32p]
+    lib.wlx_spk_debug_fbank.argtypes = [i32, f32p, i64, i32, f32p, u16p, i32, i32p]
+    lib.wlx_spk_debug_conv.argtypes = [i32, u16p, i32, i32, i32, f32p, f32p, u16p, i32, i32, i32, i32, u16p]
+    lib.wlx_spk_debug_pool.argtypes = [i32, u16p, i32, i32, i32, C.c_float, f32p]
     lib.wlx_debug_layernorm.argtypes = [i32, f32p, i64, f32p, f32p, i32, i32, u16p, f32p, i64]
     lib.wlx_debug_attn_encoder.argtypes = [i32, u16p, i64, i64, u16p, i64, i64, u16p, i64, i64, u16p, i64, i64, i32, i32, i32]
     lib.wlx_debug_dec_cross_attn.argtypes = [i32, u16p, i64, u16p, u16p, i64, i32, i32, i32, i32, i32, i32p, u16p, f32p, u16p, i64,
@@ -283,7 +302,7 @@ def load() -> C.CDLL:
     lib.wlx_debug_gemm.argtypes = [i32, C.POINTER(wlx_debug_gemm_args), u16p, f32p, f32p, f32p, u16p, f32p, u16p, u16p, i32p]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_mt_destroy"):
+        if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):
             fn.restype = i32
     if lib.wlx_abi_version() != 1:
         raise WlxError("libwlx.so ABI version mismatch")

@@ -19,6 +19,9 @@ own cache directory) and download when the deployment allows it. Order, first hi
           installed faster_whisper / silero_vad package (located without importing them)  ->  a download to the reference's cache
           path (same conditions)
 
+  speaker: an existing checkpoint file or directory  ->  $WLX_MODEL_ROOT/<name>  ->  the Hugging Face cache  ->  a download (same
+          conditions); the name is $WLX_DIARIZATION_MODEL or pyannote/wespeaker-voxceleb-resnet34-LM
+
 A directory counts as a model when the loaders can read it (whisperlive_amd/weights.py::load_model_dir): CTranslate2 `model.bin` or
 Hugging Face `model.safetensors` (single or sharded), plus `tokenizer.json`.
 """
@@ -227,5 +230,60 @@ def resolve_translation_model(name_or_path: str = TRANSLATION_MODEL, download_ro
     if downloads_allowed(local_files_only):
         d = snap(str(name_or_path), download_root, False)
         if d and is_mt_model_dir(d):
+            return d
+    return None
+
+
+# ---- the speaker-embedding model of the `enable_diarization` option (reference: whisper_live/diarization.py:61,87)
+DIARIZATION_MODEL = "pyannote/wespeaker-voxceleb-resnet34-LM"
+_SPK_FILES = ["pytorch_model.bin", "model.safetensors", "avg_model.pt", "config.yaml"]
+_SPK_WEIGHT_FILES = ("model.safetensors", "pytorch_model.bin", "avg_model.pt", "model.pt")
+
+
+def is_diarization_model(path: str) -> bool:
+    """a checkpoint file (.safetensors / .bin / .pt / .ckpt) or a directory that holds one under a known name"""
+    if not path:
+        return False
+    if os.path.isfile(path):
+        return path.endswith((".safetensors", ".bin", ".pt", ".pth", ".ckpt"))
+    return os.path.isdir(path) and any(os.path.isfile(os.path.join(path, f)) for f in _SPK_WEIGHT_FILES)
+
+
+def resolve_diarization_model(name_or_path: Optional[str] = None, download_root: Optional[str] = None,
+                              local_files_only: Optional[bool] = None,
+                              snapshot: Optional[Callable[[str, Optional[str], bool], Optional[str]]] = None) -> Optional[str]:
+    """A speaker-embedding checkpoint (file or directory) or None, in the order of resolve_translation_model: an existing file or
+    directory -> $WLX_MODEL_ROOT/<name> -> the Hugging Face cache (local_files_only) -> a download (unless local_files_only /
+    HF_HUB_OFFLINE=1 / WLX_NO_DOWNLOAD=1). No name = $WLX_DIARIZATION_MODEL, else the reference's default. `snapshot` replaces the
+    hub call in tests."""
+    def hub(repo, cache_dir, local_only):
+        try:
+            from huggingface_hub import snapshot_download
+        except ImportError:
+            return None
+        try:
+            return snapshot_download(repo_id=repo, repo_type="model", cache_dir=cache_dir, local_files_only=local_only,
+                                     allow_patterns=_SPK_FILES, etag_timeout=5)
+        except Exception as e:  # noqa: BLE001
+            logging.debug("hub %s: %s: %s", repo, type(e).__name__, e)
+            return None
+    snap = snapshot or hub
+    name = str(name_or_path or os.environ.get("WLX_DIARIZATION_MODEL") or DIARIZATION_MODEL)
+    p = os.path.expanduser(name)
+    if is_diarization_model(p):
+        return p
+    root = os.environ.get("WLX_MODEL_ROOT")
+    if root:
+        for cand in (os.path.join(root, name), os.path.join(root, os.path.basename(name))):
+            if is_diarization_model(cand):
+                return cand
+    if "/" not in name or name.startswith((".", "/", "~")):
+        return None
+    d = snap(name, download_root, True)
+    if d and is_diarization_model(d):
+        return d
+    if downloads_allowed(local_files_only):
+        d = snap(name, download_root, False)
+        if d and is_diarization_model(d):
             return d
     return None

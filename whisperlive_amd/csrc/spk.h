@@ -1,0 +1,47 @@
+// spk.h — launchers of the gfx950 kernels of the speaker-embedding engine (spk.hip; engine in spk_engine.hip): the Kaldi
+// filterbank front end of WeSpeaker, the ResNet convolutions as implicit GEMMs on mfma_f32_16x16x32_f16, statistics pooling
+// and the embedding head. Activations are NHWC fp16 ([H = frequency][W = time][C]), accumulation is fp32.
+#pragma once
+#include "kernels.h"
+
+namespace wlx {
+
+#define WLX_SPK_FRAME 400        // 25 ms at 16 kHz
+#define WLX_SPK_SHIFT 160        // 10 ms
+#define WLX_SPK_NFFT 512
+#define WLX_SPK_BINS 256         // Kaldi's mel banks leave the Nyquist bin out
+#define WLX_SPK_MIN_SAMPLES 4800 // 0.3 s: what the reference's SpeakerDiarizer refuses to embed
+
+// frames of a snip_edges filterbank over n samples (0 below one frame)
+inline int spk_frames(long n) { return n < WLX_SPK_FRAME ? 0 : 1 + (int)((n - WLX_SPK_FRAME) / WLX_SPK_SHIFT); }
+
+// Kaldi fbank: frame t = pcm[160 t .. 160 t + 400) * 2^15, DC removed, pre-emphasis 0.97, Hamming window, 512-point power spectrum
+// (direct DFT against `twiddle` = cos(2 pi j / 512), j = 0..511, fp32), n_mels triangular bins `mel` [n_mels][256], natural log with
+// a float32-epsilon floor -> logmel fp32 [T][n_mels]. `window` [400].
+void launch_spk_fbank(const float* pcm, int T, const float* window, const float* twiddle, const float* mel, int n_mels,
+                      float* logmel, hipStream_t s);
+// per-bin mean over the T frames subtracted in place (fp32 [T][n_mels]); the fp16 copy goes to out16 [n_mels][T], the [H][W][1]
+// image the first convolution reads
+void launch_spk_cmn(float* logmel, int T, int n_mels, half_t* out16, hipStream_t s);
+
+// Convolution, ks = 3 (padding 1) or 1 (padding 0), stride 1 or 2: in [H][W][Cin] -> out [OH][OW][Cout] with
+// OH = (H - 1) / stride + 1, OW likewise. Wp: the weight w[Cout][Cin][ks][ks] packed by spk_pack_conv into MFMA fragment order
+// (common.h) over k = (kh * ks + kw) * Cin + ci. out = act(conv + bias [+ resid]), resid [OH][OW][Cout]. Cin and Cout multiples
+// of 32. bias [Cout] is required (zeros for a convolution without one), resid may be null. Returns false (nothing launched) for
+// a shape it cannot serve or a null in / Wp / bias / out.
+bool launch_spk_conv(const half_t* in, int H, int W, int Cin, const half_t* Wp, const float* bias, const half_t* resid, int Cout,
+                     int stride, int ks, bool relu, half_t* out, hipStream_t s);
+// the same for Cin = 1, ks = 3 on the vector ALU: w fp32 [Cout][9], Cout a multiple of 4
+bool launch_spk_conv_c1(const half_t* in, int H, int W, const float* w, const float* bias, const half_t* resid, int Cout, int stride,
+                        bool relu, half_t* out, hipStream_t s);
+// host side: w fp32 [Cout][Cin][ks][ks] -> fragment order, ks * ks * Cin / 32 k-tiles per 16 output channels
+void spk_pack_conv(const float* w, int Cout, int Cin, int ks, half_t* Wp);
+inline size_t spk_packed_halfs(int Cout, int Cin, int ks) { return (size_t)(Cout / 16) * (size_t)(ks * ks * Cin / 32) * 512; }
+
+// Statistics pooling of x [F][T][C] over T (T >= 2): out[c * F + f] = mean, out[C * F + c * F + f] = sqrt(var_unbiased + eps).
+// C a multiple of 64.
+bool launch_spk_pool(const half_t* x, int F, int T, int C, float eps, float* out, hipStream_t s);
+// emb = W pooled + b (W fp16 [E][D] row-major, D a multiple of 8), then emb /= |emb|. E <= 1024.
+void launch_spk_head(const float* pooled, const half_t* W, const float* b, int E, int D, float* emb, hipStream_t s);
+
+}  // namespace wlx

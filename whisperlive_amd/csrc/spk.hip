@@ -1,0 +1,293 @@
+// spk.hip — kernels of the speaker-embedding engine (spk.h): Kaldi filterbank, the ResNet convolutions, statistics pooling and
+// the embedding head of WeSpeaker ResNet34. Every reduction runs in a fixed order: two embeds of the same audio are bit-identical.
+#include "spk.h"
+
+namespace wlx {
+
+// ------------------------------------------------------------------------------------------------ filterbank
+// One workgroup per frame. The DFT is direct (400 x 256 multiply-adds per frame, fp32, four partial sums per bin): at 100 frames
+// per second it is noise beside the network, and its twiddles are table entries rounded from float64, exact in their index
+// (k n mod 512), so the only fp32 error is the accumulation.
+__global__ __launch_bounds__(256) void spk_fbank_kernel(const float* __restrict__ pcm, const float* __restrict__ window,
+                                                         const float* __restrict__ twiddle, const float* __restrict__ mel, int n_mels,
+                                                         float* __restrict__ logmel) {
+    __shared__ float x[WLX_SPK_FRAME];
+    __shared__ float tw[WLX_SPK_NFFT];
+    __shared__ float pw[WLX_SPK_BINS];
+    __shared__ float part[4];
+    const int tid = threadIdx.x, t = blockIdx.x;
+    const float* src = pcm + (long)t * WLX_SPK_SHIFT;
+    float a = src[tid] * 32768.f, b = 0.f;
+    if (tid + 256 < WLX_SPK_FRAME) b = src[tid + 256] * 32768.f;
+    tw[tid] = twiddle[tid];
+    tw[tid + 256] = twiddle[tid + 256];
+    const float ws = wave_sum(a + b);
+    if ((tid & 63) == 0) part[tid >> 6] = ws;
+    __syncthreads();
+    const float mean = (((part[0] + part[1]) + part[2]) + part[3]) * (1.f / WLX_SPK_FRAME);
+    x[tid] = a - mean;
+    if (tid + 256 < WLX_SPK_FRAME) x[tid + 256] = b - mean;
+    __syncthreads();
+    // pre-emphasis against the previous sample (the first against itself), then the window
+    const float z0 = (x[tid] - 0.97f * x[tid > 0 ? tid - 1 : 0]) * window[tid];
+    float z1 = 0.f;
+    if (tid + 256 < WLX_SPK_FRAME) z1 = (x[tid + 256] - 0.97f * x[tid + 255]) * window[tid + 256];
+    __syncthreads();
+    x[tid] = z0;
+    if (tid + 256 < WLX_SPK_FRAME) x[tid + 256] = z1;
+    __syncthreads();
+    float re[4] = {0.f, 0.f, 0.f, 0.f}, im[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < WLX_SPK_FRAME; n += 4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int idx = (tid * (n + j)) & (WLX_SPK_NFFT - 1);
+            const float v = x[n + j];
+            re[j] += v * tw[idx];
+            im[j] += v * tw[(idx - WLX_SPK_NFFT / 4) & (WLX_SPK_NFFT - 1)];
+        }
+    }
+    const float r = (re[0] + re[1]) + (re[2] + re[3]), i = (im[0] + im[1]) + (im[2] + im[3]);
+    pw[tid] = r * r + i * i;
+    __syncthreads();
+    if (tid < n_mels) {
+        const float* m = mel + (long)tid * WLX_SPK_BINS;
+        float e[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < WLX_SPK_BINS; k += 4) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e[j] += m[k + j] * pw[k + j];
+        }
+        const float s = (e[0] + e[1]) + (e[2] + e[3]);
+        logmel[(long)t * n_mels + tid] = logf(fmaxf(s, 1.1920928955078125e-07f));
+    }
+}
+
+void launch_spk_fbank(const float* pcm, int T, const float* window, const float* twiddle, const float* mel, int n_mels,
+                      float* logmel, hipStream_t s) {
+    hipLaunchKernelGGL(spk_fbank_kernel, dim3((unsigned)T), dim3(256), 0, s, pcm, window, twiddle, mel, n_mels, logmel);
+}
+
+__global__ __launch_bounds__(256) void spk_cmn_kernel(float* __restrict__ logmel, int T, int n_mels, half_t* __restrict__ out16) {
+    __shared__ float part[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    float acc = 0.f;
+    for (int t = tid; t < T; t += 256) acc += logmel[(long)t * n_mels + b];
+    const float ws = wave_sum(acc);
+    if ((tid & 63) == 0) part[tid >> 6] = ws;
+    __syncthreads();
+    const float mean = (((part[0] + part[1]) + part[2]) + part[3]) / (float)T;
+    for (int t = tid; t < T; t += 256) {
+        const float v = logmel[(long)t * n_mels + b] - mean;
+        logmel[(long)t * n_mels + b] = v;
+        out16[(long)b * T + t] = (half_t)v;
+    }
+}
+
+void launch_spk_cmn(float* logmel, int T, int n_mels, half_t* out16, hipStream_t s) {
+    hipLaunchKernelGGL(spk_cmn_kernel, dim3((unsigned)n_mels), dim3(256), 0, s, logmel, T, n_mels, out16);
+}
+
+// ------------------------------------------------------------------------------------------------ convolution
+// Implicit GEMM in the swapped form of common.h: D[n = output channel][m = output pixel] = sum_k W[n][k] X[m][k] with
+// k = tap * Cin + ci. NHWC makes the 8 halfs a lane feeds per MFMA (k = g * 8 .. g * 8 + 7 of a 32-wide k-tile) contiguous in
+// memory for every tap, so the activation fragment is one 16-byte load from the input image, zero where the tap falls into the
+// padding; no im2col buffer and no LDS. A wave owns 16 pixels x NT * 16 output channels, a workgroup four waves = 64 pixels.
+// Each lane ends with 4 consecutive channels of one pixel: one 8-byte store.
+template <int NT>
+__global__ __launch_bounds__(256) void spk_conv_kernel(const half_t* __restrict__ in, const half_t* __restrict__ Wp,
+                                                        const float* __restrict__ bias, const half_t* __restrict__ resid,
+                                                        half_t* __restrict__ out, int H, int W, int Cin, int OH, int OW, int Cout,
+                                                        int stride, int ks, int relu) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const long P = (long)OH * OW;
+    const long m0 = ((long)blockIdx.x * 4 + wave) * 16;
+    if (m0 >= P) return;                       // wave-uniform: the MFMAs below always run with all 64 lanes
+    const long m = m0 + c;
+    const bool live = m < P;
+    const int oh = live ? (int)(m / OW) : 0, ow = live ? (int)(m % OW) : 0;
+    const int nt0 = blockIdx.y * NT;
+    const int cpt = Cin >> 5, KT = ks * ks * cpt, pad = ks >> 1;
+    f32x4 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const half_t* wbase = Wp + ((long)nt0 * KT * 64 + lane) * 8;
+    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    int kt = 0;
+    for (int kh = 0; kh < ks; ++kh) {
+        for (int kw = 0; kw < ks; ++kw) {
+            const int ih = oh * stride + kh - pad, iw = ow * stride + kw - pad;
+            const bool ok = live && ih >= 0 && ih < H && iw >= 0 && iw < W;
+            const half_t* src = in + ((long)(ok ? ih : 0) * W + (ok ? iw : 0)) * Cin + g * 8;
+            for (int q = 0; q < cpt; ++q, ++kt) {
+                const f16x8 b = ok ? ld_f16x8(src + q * 32) : zero;
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    const f16x8 a = ld_f16x8(wbase + ((long)j * KT + kt) * 512);
+                    acc[j] = mfma16(a, b, acc[j]);
+                }
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int n = (nt0 + j) * 16 + g * 4;
+        const float4 bv = *reinterpret_cast<const float4*>(bias + n);
+        float v[4] = {acc[j][0] + bv.x, acc[j][1] + bv.y, acc[j][2] + bv.z, acc[j][3] + bv.w};
+        if (resid) {
+            const f16x4 rv = ld_f16x4(resid + m * Cout + n);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] += (float)rv[r];
+        }
+        f16x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (half_t)(relu ? fmaxf(v[r], 0.f) : v[r]);
+        *reinterpret_cast<f16x4*>(out + m * Cout + n) = o;
+    }
+}
+
+bool launch_spk_conv(const half_t* in, int H, int W, int Cin, const half_t* Wp, const float* bias, const half_t* resid, int Cout,
+                     int stride, int ks, bool relu, half_t* out, hipStream_t s) {
+    // bias is required (a convolution without one passes zeros); resid may be null
+    if (!in || !Wp || !bias || !out) return false;
+    if (H < 1 || W < 1 || Cin < 32 || Cin % 32 || Cout < 32 || Cout % 32 || (stride != 1 && stride != 2) || (ks != 1 && ks != 3))
+        return false;
+    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+    const long P = (long)OH * OW;
+    if (P > (1L << 30)) return false;
+    const unsigned gx = (unsigned)((P + 63) / 64);
+    if (Cout % 64 == 0)
+        hipLaunchKernelGGL(spk_conv_kernel<4>, dim3(gx, (unsigned)(Cout / 64)), dim3(256), 0, s, in, Wp, bias, resid, out, H, W, Cin, OH,
+                           OW, Cout, stride, ks, relu ? 1 : 0);
+    else
+        hipLaunchKernelGGL(spk_conv_kernel<2>, dim3(gx, (unsigned)(Cout / 32)), dim3(256), 0, s, in, Wp, bias, resid, out, H, W, Cin, OH,
+                           OW, Cout, stride, ks, relu ? 1 : 0);
+    return true;
+}
+
+void spk_pack_conv(const float* w, int Cout, int Cin, int ks, half_t* Wp) {
+    const int cpt = Cin / 32, KT = ks * ks * cpt;
+    for (int nt = 0; nt < Cout / 16; ++nt)
+        for (int kt = 0; kt < KT; ++kt) {
+            const int tap = kt / cpt, kh = tap / ks, kw = tap % ks;
+            for (int l = 0; l < 64; ++l)
+                for (int e = 0; e < 8; ++e) {
+                    const int n = nt * 16 + (l & 15), ci = (kt % cpt) * 32 + (l >> 4) * 8 + e;
+                    Wp[(((size_t)nt * KT + kt) * 64 + l) * 8 + e] = (half_t)w[(((size_t)n * Cin + ci) * ks + kh) * ks + kw];
+                }
+        }
+}
+
+// The stem (Cin = 1, K = 9): a thread computes 4 output channels of one pixel on the vector ALU.
+__global__ __launch_bounds__(256) void spk_conv_c1_kernel(const half_t* __restrict__ in, const float* __restrict__ w,
+                                                           const float* __restrict__ bias, const half_t* __restrict__ resid,
+                                                           half_t* __restrict__ out, int H, int W, int OH, int OW, int Cout, int stride,
+                                                           int relu) {
+    const int q = Cout >> 2;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)OH * OW * q) return;
+    const long m = i / q;
+    const int n = (int)(i % q) * 4;
+    const int oh = (int)(m / OW), ow = (int)(m % OW);
+    float v[4] = {bias[n], bias[n + 1], bias[n + 2], bias[n + 3]};
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+            const int ih = oh * stride + kh - 1, iw = ow * stride + kw - 1;
+            if (ih < 0 || ih >= H || iw < 0 || iw >= W) continue;
+            const float x = (float)in[(long)ih * W + iw];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] += x * w[(n + r) * 9 + kh * 3 + kw];
+        }
+    if (resid) {
+        const f16x4 rv = ld_f16x4(resid + m * Cout + n);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] += (float)rv[r];
+    }
+    f16x4 o;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = (half_t)(relu ? fmaxf(v[r], 0.f) : v[r]);
+    *reinterpret_cast<f16x4*>(out + m * Cout + n) = o;
+}
+
+bool launch_spk_conv_c1(const half_t* in, int H, int W, const float* w, const float* bias, const half_t* resid, int Cout, int stride,
+                        bool relu, half_t* out, hipStream_t s) {
+    if (!in || !w || !bias || !out) return false;          // as launch_spk_conv: bias required, resid optional
+    if (H < 1 || W < 1 || Cout < 4 || Cout % 4 || (stride != 1 && stride != 2)) return false;
+    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+    const long n = (long)OH * OW * (Cout / 4);
+    if (n > (1L << 38)) return false;
+    hipLaunchKernelGGL(spk_conv_c1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, w, bias, resid, out, H, W, OH, OW, Cout,
+                       stride, relu ? 1 : 0);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ pooling and head
+// A workgroup owns 64 channels of one frequency row; its four waves take the frames t = wave, wave + 4, ... Two passes (mean, then
+// squared deviations) in fp32.
+__global__ __launch_bounds__(256) void spk_pool_kernel(const half_t* __restrict__ x, int F, int T, int C, float eps,
+                                                        float* __restrict__ out) {
+    __shared__ float part[4][64];
+    const int ch = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int f = blockIdx.x, c = blockIdx.y * 64 + ch;
+    const half_t* p = x + (long)f * T * C + c;
+    float acc = 0.f;
+    for (int t = sl; t < T; t += 4) acc += (float)p[(long)t * C];
+    part[sl][ch] = acc;
+    __syncthreads();
+    const float mean = (((part[0][ch] + part[1][ch]) + part[2][ch]) + part[3][ch]) / (float)T;
+    __syncthreads();
+    acc = 0.f;
+    for (int t = sl; t < T; t += 4) {
+        const float d = (float)p[(long)t * C] - mean;
+        acc += d * d;
+    }
+    part[sl][ch] = acc;
+    __syncthreads();
+    if (sl == 0) {
+        const float var = (((part[0][ch] + part[1][ch]) + part[2][ch]) + part[3][ch]) / (float)(T - 1);
+        out[(long)c * F + f] = mean;
+        out[(long)C * F + (long)c * F + f] = sqrtf(var + eps);
+    }
+}
+
+bool launch_spk_pool(const half_t* x, int F, int T, int C, float eps, float* out, hipStream_t s) {
+    if (F < 1 || T < 2 || C < 64 || C % 64) return false;
+    hipLaunchKernelGGL(spk_pool_kernel, dim3((unsigned)F, (unsigned)(C / 64)), dim3(256), 0, s, x, F, T, C, eps, out);
+    return true;
+}
+
+__global__ __launch_bounds__(64) void spk_linear_kernel(const float* __restrict__ x, const half_t* __restrict__ W,
+                                                         const float* __restrict__ b, int D, float* __restrict__ y) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    const half_t* w = W + (long)e * D;
+    float acc = 0.f;
+    for (int i = lane * 8; i < D; i += 512) {
+        const f16x8 wv = ld_f16x8(w + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += (float)wv[j] * x[i + j];
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) y[e] = acc + b[e];
+}
+
+__global__ __launch_bounds__(256) void spk_l2norm_kernel(float* __restrict__ y, int E) {
+    __shared__ float part[4];
+    const int tid = threadIdx.x;
+    float acc = 0.f;
+    for (int i = tid; i < E; i += 256) acc += y[i] * y[i];
+    const float ws = wave_sum(acc);
+    if ((tid & 63) == 0) part[tid >> 6] = ws;
+    __syncthreads();
+    // an all-zero head output stays zero instead of turning into NaN
+    const float inv = 1.f / sqrtf(fmaxf(((part[0] + part[1]) + part[2]) + part[3], 1e-30f));
+    for (int i = tid; i < E; i += 256) y[i] *= inv;
+}
+
+void launch_spk_head(const float* pooled, const half_t* W, const float* b, int E, int D, float* emb, hipStream_t s) {
+    hipLaunchKernelGGL(spk_linear_kernel, dim3((unsigned)E), dim3(64), 0, s, pooled, W, b, D, emb);
+    hipLaunchKernelGGL(spk_l2norm_kernel, dim3(1), dim3(256), 0, s, emb, E);
+}
+
+}  // namespace wlx

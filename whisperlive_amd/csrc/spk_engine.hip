@@ -1,0 +1,373 @@
+// spk_engine.hip — the speaker-embedding engine behind `enable_diarization` (include/wlx.h wlx_spk_*): WeSpeaker ResNet34 on the
+// kernels of spk.hip. One engine per GPU on a non-blocking stream of its own; every buffer is sized at create for max_seconds of
+// audio and fully rewritten by each call up to the extent that call reads, so no call sees another's data. Calls are serialised
+// by the engine's mutex. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv / _pool.
+#include <cmath>
+#include <mutex>
+#include "host.h"
+#include "spk.h"
+
+namespace wlx {
+namespace {
+
+struct SpkConv {
+    half_t* Wp = nullptr;
+    float* bias = nullptr;
+    int cin = 0, cout = 0, stride = 1, ks = 3;
+};
+struct SpkBlock {
+    SpkConv c1, c2, sc;
+    bool has_sc = false;
+};
+
+// Kaldi's tables in float64, rounded once: Hamming window, cos(2 pi j / 512), and the triangular mel banks over 20 Hz .. Nyquist on
+// the 1127 ln(1 + f / 700) scale, evaluated at the centres of the first 256 FFT bins (the Nyquist bin carries no weight)
+void spk_tables(int n_mels, std::vector<float>& window, std::vector<float>& twiddle, std::vector<float>& mel) {
+    const double pi = 3.14159265358979323846;
+    window.resize(WLX_SPK_FRAME);
+    for (int i = 0; i < WLX_SPK_FRAME; ++i) window[i] = (float)(0.54 - 0.46 * std::cos(2.0 * pi * i / (WLX_SPK_FRAME - 1)));
+    twiddle.resize(WLX_SPK_NFFT);
+    for (int j = 0; j < WLX_SPK_NFFT; ++j) twiddle[j] = (float)std::cos(2.0 * pi * j / WLX_SPK_NFFT);
+    auto to_mel = [](double f) { return 1127.0 * std::log(1.0 + f / 700.0); };
+    const double lo = to_mel(20.0), hi = to_mel(8000.0), delta = (hi - lo) / (n_mels + 1), bin_hz = 16000.0 / WLX_SPK_NFFT;
+    mel.assign((size_t)n_mels * WLX_SPK_BINS, 0.f);
+    for (int b = 0; b < n_mels; ++b) {
+        const double left = lo + b * delta, centre = left + delta, right = centre + delta;
+        for (int k = 0; k < WLX_SPK_BINS; ++k) {
+            const double m = to_mel(bin_hz * k);
+            const double up = (m - left) / (centre - left), down = (right - m) / (right - centre);
+            mel[(size_t)b * WLX_SPK_BINS + k] = (float)std::max(0.0, std::min(up, down));
+        }
+    }
+}
+
+int upload_tables(std::vector<void*>& pool, int n_mels, float** window, float** twiddle, float** mel) {
+    std::vector<float> w, t, m;
+    spk_tables(n_mels, w, t, m);
+    CKR(dalloc(pool, window, w.size(), false));
+    CKR(dalloc(pool, twiddle, t.size(), false));
+    CKR(dalloc(pool, mel, m.size(), false));
+    CKR(upload_sync(*window, w.data(), w.size() * sizeof(float)));
+    CKR(upload_sync(*twiddle, t.data(), t.size() * sizeof(float)));
+    return upload_sync(*mel, m.data(), m.size() * sizeof(float));
+}
+
+// a named tensor as host floats (a device tensor is copied back on the utility stream)
+int fetch(const Weights& ws, const std::string& name, std::initializer_list<int64_t> shape, std::vector<float>& out) {
+    const wlx_tensor* t;
+    CKR(ws.need(name, shape, &t));
+    size_t n = 1;
+    for (int64_t s : shape) n *= (size_t)s;
+    out.resize(n);
+    if (t->on_device) {
+        hipStream_t us = util_stream();
+        if (!us) return set_error(WLX_ERR_HIP, "utility stream creation failed");
+        CK(hipMemcpyAsync(out.data(), t->data, n * sizeof(float), hipMemcpyDeviceToHost, us));
+        CK(hipStreamSynchronize(us));
+    } else {
+        std::copy(reinterpret_cast<const float*>(t->data), reinterpret_cast<const float*>(t->data) + n, out.begin());
+    }
+    return WLX_OK;
+}
+
+int load_conv(const Weights& ws, std::vector<void*>& pool, const std::string& name, int cout, int cin, int ks, int stride, SpkConv& c) {
+    std::vector<float> w, b;
+    CKR(fetch(ws, name + ".weight", {cout, cin, ks, ks}, w));
+    CKR(fetch(ws, name + ".bias", {cout}, b));
+    std::vector<half_t> packed(spk_packed_halfs(cout, cin, ks));
+    spk_pack_conv(w.data(), cout, cin, ks, packed.data());
+    CKR(dalloc(pool, &c.Wp, packed.size(), false));
+    CKR(dalloc(pool, &c.bias, b.size(), false));
+    CKR(upload_sync(c.Wp, packed.data(), packed.size() * sizeof(half_t)));
+    CKR(upload_sync(c.bias, b.data(), b.size() * sizeof(float)));
+    c.cin = cin, c.cout = cout, c.ks = ks, c.stride = stride;
+    return WLX_OK;
+}
+
+}  // namespace
+}  // namespace wlx
+
+using namespace wlx;
+
+struct wlx_spk {
+    int device = 0;
+    wlx_spk_spec spec{};
+    hipStream_t st = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    std::vector<void*> pool;
+    std::mutex mu;
+    float *window = nullptr, *twiddle = nullptr, *mel = nullptr;
+    float *stem_w = nullptr, *stem_b = nullptr, *head_b = nullptr;
+    half_t* head_W = nullptr;
+    std::vector<SpkBlock> blocks;
+    long max_samples = 0;
+    int pool_dim = 0;
+    // per-call buffers
+    float *pcm = nullptr, *logmel = nullptr, *pooled = nullptr, *emb = nullptr;
+    half_t* feat16 = nullptr;
+    half_t* act[4] = {nullptr, nullptr, nullptr, nullptr};
+    float fbank_ms = 0.f, net_ms = 0.f;
+    bool timed = false;
+};
+
+static void spk_free(wlx_spk* k) {
+    if (!k) return;
+    (void)hipSetDevice(k->device);
+    if (k->st) (void)hipStreamSynchronize(k->st);
+    for (hipEvent_t e : k->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (void* p : k->pool) (void)hipFree(p);
+    if (k->st) (void)hipStreamDestroy(k->st);
+    delete k;
+}
+
+static int spk_build(wlx_spk* k, const wlx_tensor* weights, int n_weights) {
+    const wlx_spk_spec& sp = k->spec;
+    CK(hipSetDevice(k->device));
+    CK(hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking));
+    for (hipEvent_t& e : k->ev) CK(hipEventCreate(&e));
+    CKR(upload_tables(k->pool, sp.n_mels, &k->window, &k->twiddle, &k->mel));
+    Weights ws;
+    CKR(ws.open(weights, n_weights));
+    const int m = sp.planes;
+    std::vector<float> w, b;
+    CKR(fetch(ws, "conv1.weight", {m, 1, 3, 3}, w));
+    CKR(fetch(ws, "conv1.bias", {m}, b));
+    CKR(dalloc(k->pool, &k->stem_w, w.size(), false));
+    CKR(dalloc(k->pool, &k->stem_b, b.size(), false));
+    CKR(upload_sync(k->stem_w, w.data(), w.size() * sizeof(float)));
+    CKR(upload_sync(k->stem_b, b.data(), b.size() * sizeof(float)));
+    int cin = m;
+    for (int L = 0; L < 4; ++L) {
+        const int planes = m << L;
+        for (int B = 0; B < sp.blocks[L]; ++B) {
+            const int stride = (B == 0 && L > 0) ? 2 : 1;
+            const std::string p = "layer" + std::to_string(L + 1) + "." + std::to_string(B) + ".";
+            SpkBlock blk;
+            CKR(load_conv(ws, k->pool, p + "conv1", planes, cin, 3, stride, blk.c1));
+            CKR(load_conv(ws, k->pool, p + "conv2", planes, planes, 3, 1, blk.c2));
+            blk.has_sc = stride != 1 || cin != planes;
+            if (blk.has_sc) CKR(load_conv(ws, k->pool, p + "shortcut", planes, cin, 1, stride, blk.sc));
+            k->blocks.push_back(blk);
+            cin = planes;
+        }
+    }
+    k->pool_dim = 2 * (m << 3) * (sp.n_mels >> 3);
+    CKR(fetch(ws, "seg_1.weight", {sp.embed_dim, k->pool_dim}, w));
+    CKR(fetch(ws, "seg_1.bias", {sp.embed_dim}, b));
+    std::vector<half_t> w16(w.size());
+    for (size_t i = 0; i < w.size(); ++i) w16[i] = (half_t)w[i];
+    CKR(dalloc(k->pool, &k->head_W, w16.size(), false));
+    CKR(dalloc(k->pool, &k->head_b, b.size(), false));
+    CKR(upload_sync(k->head_W, w16.data(), w16.size() * sizeof(half_t)));
+    CKR(upload_sync(k->head_b, b.data(), b.size() * sizeof(float)));
+    CKR(ws.finish());
+
+    k->max_samples = (long)sp.max_seconds * 16000;
+    const size_t Tmax = (size_t)spk_frames(k->max_samples);
+    CKR(dalloc(k->pool, &k->pcm, (size_t)k->max_samples, false));
+    CKR(dalloc(k->pool, &k->logmel, Tmax * sp.n_mels, false));
+    CKR(dalloc(k->pool, &k->feat16, Tmax * sp.n_mels, false));
+    // the stem's output is the largest activation: every stride-2 stage halves H and W and doubles C
+    for (half_t*& a : k->act) CKR(dalloc(k->pool, &a, Tmax * sp.n_mels * m, false));
+    CKR(dalloc(k->pool, &k->pooled, (size_t)k->pool_dim, false));
+    CKR(dalloc(k->pool, &k->emb, (size_t)sp.embed_dim, false));
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_spk_create(const wlx_spk_spec* spec, const wlx_tensor* weights, int32_t n_weights, int32_t device, wlx_spk** out) {
+    if (!spec || !weights || !out || n_weights < 1) return set_error(WLX_ERR_ARG, "null argument");
+    if (spec->n_mels < 8 || spec->n_mels % 8 || spec->n_mels > 256)
+        return set_error(WLX_ERR_ARG, "n_mels %d must be a multiple of 8 in 8..256", spec->n_mels);
+    if (spec->planes < 32 || spec->planes % 32 || spec->planes > 128)
+        return set_error(WLX_ERR_ARG, "planes %d must be 32, 64, 96 or 128", spec->planes);
+    for (int L = 0; L < 4; ++L)
+        if (spec->blocks[L] < 1 || spec->blocks[L] > 64) return set_error(WLX_ERR_ARG, "blocks[%d] = %d outside 1..64", L, spec->blocks[L]);
+    if (spec->embed_dim < 1 || spec->embed_dim > 1024) return set_error(WLX_ERR_ARG, "embed_dim %d outside 1..1024", spec->embed_dim);
+    if (spec->max_seconds < 1 || spec->max_seconds > 120) return set_error(WLX_ERR_ARG, "max_seconds %d outside 1..120", spec->max_seconds);
+    if (!(spec->pool_eps >= 0.f)) return set_error(WLX_ERR_ARG, "pool_eps must be >= 0");
+    int n = 0;
+    CK(hipGetDeviceCount(&n));
+    if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
+    wlx_spk* k = new wlx_spk();
+    k->device = device;
+    k->spec = *spec;
+    const int rc = spk_build(k, weights, n_weights);
+    if (rc != WLX_OK) {
+        spk_free(k);
+        return rc;
+    }
+    *out = k;
+    return WLX_OK;
+}
+
+extern "C" void wlx_spk_destroy(wlx_spk* k) {
+    if (!k) return;
+    { std::lock_guard<std::mutex> g(k->mu); }      // a call in flight finishes first
+    spk_free(k);
+}
+
+extern "C" int32_t wlx_spk_embed(wlx_spk* k, const float* pcm, int64_t n_samples, float* out) {
+    if (!k || !pcm || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (n_samples < WLX_SPK_MIN_SAMPLES)
+        return set_error(WLX_ERR_TOO_SHORT, "%lld samples: under 0.3 s of audio", (long long)n_samples);
+    if (n_samples > k->max_samples)
+        return set_error(WLX_ERR_ARG, "%lld samples exceed the engine's %d s", (long long)n_samples, k->spec.max_seconds);
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    const wlx_spk_spec& sp = k->spec;
+    hipStream_t st = k->st;
+    const int T = spk_frames((long)n_samples);
+    CK(hipMemcpyAsync(k->pcm, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, st));
+    CK(hipEventRecord(k->ev[0], st));
+    launch_spk_fbank(k->pcm, T, k->window, k->twiddle, k->mel, sp.n_mels, k->logmel, st);
+    launch_spk_cmn(k->logmel, T, sp.n_mels, k->feat16, st);
+    CK(hipEventRecord(k->ev[1], st));
+    int H = sp.n_mels, W = T;
+    half_t *x = k->act[0], *t1 = k->act[1], *y = k->act[2], *sc = k->act[3];
+    if (!launch_spk_conv_c1(k->feat16, H, W, k->stem_w, k->stem_b, nullptr, sp.planes, 1, true, x, st))
+        return set_error(WLX_ERR_ARG, "stem convolution refused %d x %d", H, W);
+    for (const SpkBlock& b : k->blocks) {
+        const int s = b.c1.stride, OH = (H - 1) / s + 1, OW = (W - 1) / s + 1;
+        bool ok = launch_spk_conv(x, H, W, b.c1.cin, b.c1.Wp, b.c1.bias, nullptr, b.c1.cout, s, 3, true, t1, st);
+        const half_t* resid = x;
+        if (b.has_sc) {
+            ok = ok && launch_spk_conv(x, H, W, b.sc.cin, b.sc.Wp, b.sc.bias, nullptr, b.sc.cout, s, 1, false, sc, st);
+            resid = sc;
+        }
+        ok = ok && launch_spk_conv(t1, OH, OW, b.c2.cin, b.c2.Wp, b.c2.bias, resid, b.c2.cout, 1, 3, true, y, st);
+        if (!ok) return set_error(WLX_ERR_ARG, "convolution refused %d x %d x %d", H, W, b.c1.cin);
+        std::swap(x, y);
+        H = OH, W = OW;
+    }
+    if (!launch_spk_pool(x, H, W, sp.planes << 3, sp.pool_eps, k->pooled, st))
+        return set_error(WLX_ERR_ARG, "pooling refused %d x %d", H, W);
+    launch_spk_head(k->pooled, k->head_W, k->head_b, sp.embed_dim, k->pool_dim, k->emb, st);
+    CK(hipEventRecord(k->ev[2], st));
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(out, k->emb, (size_t)sp.embed_dim * sizeof(float), hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));
+    CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
+    k->timed = true;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_spk_debug_timings(wlx_spk* k, float* fbank_ms, float* net_ms) {
+    if (!k || !fbank_ms || !net_ms) return set_error(WLX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> g(k->mu);
+    if (!k->timed) return set_error(WLX_ERR_STATE, "no embed has run on this engine");
+    *fbank_ms = k->fbank_ms;
+    *net_ms = k->net_ms;
+    return WLX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ one-launch hooks
+namespace {
+struct SpkHook {
+    std::vector<void*> allocs;
+    hipStream_t st = nullptr;
+    ~SpkHook() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (void* p : allocs) (void)hipFree(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    int begin(int device) {
+        int n = 0;
+        CK(hipGetDeviceCount(&n));
+        if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
+        CK(hipSetDevice(device));
+        CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        return WLX_OK;
+    }
+    template <class T>
+    int upload(T** d, const void* h, size_t n) {
+        CKR(dalloc(allocs, d, n, false));
+        if (h && n) CK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+        return WLX_OK;
+    }
+    int finish() {
+        CK(hipGetLastError());
+        CK(hipStreamSynchronize(st));
+        return WLX_OK;
+    }
+};
+}  // namespace
+
+extern "C" int32_t wlx_spk_debug_fbank(int32_t device, const float* pcm, int64_t n_samples, int32_t n_mels, float* frames_out,
+                                       uint16_t* image_out, int32_t cap_frames, int32_t* n_frames_out) {
+    if (!pcm || !frames_out || !image_out || !n_frames_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (n_mels < 1 || n_mels > 256) return set_error(WLX_ERR_ARG, "n_mels %d outside 1..256", n_mels);
+    if (n_samples < WLX_SPK_FRAME || n_samples > (1LL << 28)) return set_error(WLX_ERR_ARG, "n_samples %lld outside 400..2^28", (long long)n_samples);
+    const int T = spk_frames((long)n_samples);
+    if (T > cap_frames) return set_error(WLX_ERR_ARG, "%d frames exceed the caller's %d", T, cap_frames);
+    SpkHook S;
+    CKR(S.begin(device));
+    float *window, *twiddle, *mel, *dpcm, *dlm;
+    half_t* d16;
+    CKR(upload_tables(S.allocs, n_mels, &window, &twiddle, &mel));
+    CKR(S.upload(&dpcm, pcm, (size_t)n_samples));
+    CKR(S.upload(&dlm, nullptr, (size_t)T * n_mels));
+    CKR(S.upload(&d16, nullptr, (size_t)T * n_mels));
+    launch_spk_fbank(dpcm, T, window, twiddle, mel, n_mels, dlm, S.st);
+    launch_spk_cmn(dlm, T, n_mels, d16, S.st);
+    CK(hipMemcpyAsync(frames_out, dlm, (size_t)T * n_mels * sizeof(float), hipMemcpyDeviceToHost, S.st));
+    CK(hipMemcpyAsync(image_out, d16, (size_t)T * n_mels * sizeof(half_t), hipMemcpyDeviceToHost, S.st));
+    *n_frames_out = T;
+    return S.finish();
+}
+
+extern "C" int32_t wlx_spk_debug_conv(int32_t device, const uint16_t* in, int32_t H, int32_t W, int32_t Cin, const float* w, const float* bias,
+                                      const uint16_t* resid, int32_t Cout, int32_t stride, int32_t ksize, int32_t relu, uint16_t* out) {
+    if (!in || !w || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (H < 1 || W < 1 || (long)H * W > (1L << 24)) return set_error(WLX_ERR_ARG, "H %d x W %d outside 1..2^24 pixels", H, W);
+    if (stride != 1 && stride != 2) return set_error(WLX_ERR_ARG, "stride %d must be 1 or 2", stride);
+    const bool c1 = Cin == 1;
+    if (c1 ? (ksize != 3 || Cout < 4 || Cout % 4 || Cout > 1024)
+           : ((ksize != 1 && ksize != 3) || Cin < 32 || Cin % 32 || Cin > 1024 || Cout < 32 || Cout % 32 || Cout > 1024))
+        return set_error(WLX_ERR_ARG, "Cin %d / Cout %d / ksize %d: Cin = 1 (ksize 3, Cout a multiple of 4) or Cin and Cout multiples of 32 up "
+                         "to 1024 with ksize 1 or 3", Cin, Cout, ksize);
+    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+    const size_t n_out = (size_t)OH * OW * Cout;
+    std::vector<float> zeros;          // (host staging declared before S: it outlives the stream's copies on every return path)
+    std::vector<half_t> packed;
+    SpkHook S;
+    CKR(S.begin(device));
+    half_t *din, *dres = nullptr, *dout;
+    float* dbias;
+    CKR(S.upload(&din, in, (size_t)H * W * Cin));
+    if (!bias) zeros.assign((size_t)Cout, 0.f);
+    CKR(S.upload(&dbias, bias ? bias : zeros.data(), (size_t)Cout));
+    if (resid) CKR(S.upload(&dres, resid, n_out));
+    CKR(S.upload(&dout, out, n_out));
+    bool ok;
+    if (c1) {
+        float* dw;
+        CKR(S.upload(&dw, w, (size_t)Cout * 9));
+        ok = launch_spk_conv_c1(din, H, W, dw, dbias, dres, Cout, stride, relu != 0, dout, S.st);
+    } else {
+        packed.resize(spk_packed_halfs(Cout, Cin, ksize));
+        spk_pack_conv(w, Cout, Cin, ksize, packed.data());
+        half_t* dWp;
+        CKR(S.upload(&dWp, packed.data(), packed.size()));
+        ok = launch_spk_conv(din, H, W, Cin, dWp, dbias, dres, Cout, stride, ksize, relu != 0, dout, S.st);
+    }
+    if (!ok) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CK(hipMemcpyAsync(out, dout, n_out * sizeof(half_t), hipMemcpyDeviceToHost, S.st));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_spk_debug_pool(int32_t device, const uint16_t* x, int32_t F, int32_t T, int32_t C, float eps, float* out) {
+    if (!x || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (F < 1 || F > 4096 || T < 2 || T > (1 << 20) || C < 64 || C % 64 || C > 4096 || !(eps >= 0.f))
+        return set_error(WLX_ERR_ARG, "F %d / T %d / C %d: F in 1..4096, T in 2..2^20, C a multiple of 64 up to 4096", F, T, C);
+    SpkHook S;
+    CKR(S.begin(device));
+    half_t* dx;
+    float* dout;
+    CKR(S.upload(&dx, x, (size_t)F * T * C));
+    CKR(S.upload(&dout, out, (size_t)2 * F * C));
+    if (!launch_spk_pool(dx, F, T, C, eps, dout, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CK(hipMemcpyAsync(out, dout, (size_t)2 * F * C * sizeof(float), hipMemcpyDeviceToHost, S.st));
+    return S.finish();
+}

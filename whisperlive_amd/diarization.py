@@ -1,0 +1,184 @@
+"""Speaker labels for completed transcript segments — the `enable_diarization` option of the WhisperLive protocol (reference:
+whisper_live/diarization.py, created per client in whisper_live/server.py:346-363 and called inline on the transcription thread from
+base.py `_identify_speaker`).
+
+* ``SpeakerEmbedderHIP`` — ctypes binding of the wlx_spk_* entry points: one WeSpeaker ResNet34 engine on one GPU. ``embed(pcm)``
+                           returns the L2-normalised embedding, or None under 0.3 s. ``shared_embedder`` keeps one per (checkpoint,
+                           device), loaded by the first client that asks for diarization.
+* ``SpeakerDiarizer``    — the reference's online clustering, unchanged in behaviour: cosine similarity against the running
+                           centroids, threshold 0.55, 0.9 / 0.1 running average with renormalisation, closest speaker at the cap,
+                           ``speaker_names``, ``enroll_speaker``, ``reset``, labels ``SPEAKER_%02d``. ``embedder`` is any callable
+                           (pcm float32, sample_rate) -> unit vector or None, so the clustering is testable without a GPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+from typing import Callable, Dict, Optional, Tuple
+
+import numpy as np
+
+from . import _lib
+from .spk_weights import SpkSpec
+
+MIN_SECONDS = 0.3
+
+
+class SpeakerEmbedderHIP:
+    """one wlx_spk engine: `weights` are the FOLDED tensors of spk_weights.fold()"""
+
+    def __init__(self, spec: SpkSpec, weights: Dict[str, np.ndarray], device: int = 0):
+        self.lib = _lib.load()
+        self.spec = spec
+        self.device = device
+        cs = _lib.wlx_spk_spec(spec.n_mels, spec.planes, (C.c_int32 * 4)(*spec.blocks), spec.embed_dim, spec.max_seconds,
+                               float(spec.pool_eps))
+        arr, keep = _lib.tensor_array(weights)      # (keep: alive until the create call returns)
+        h = C.c_void_p()
+        _lib.check(self.lib.wlx_spk_create(C.byref(cs), arr, len(weights), device, C.byref(h)))
+        del keep
+        self.h = h
+
+    @classmethod
+    def from_checkpoint(cls, path: str, device: int = 0, **kw) -> "SpeakerEmbedderHIP":
+        from .spk_weights import load
+        spec, w = load(path, **kw)
+        return cls(spec, w, device)
+
+    def embed(self, pcm, sample_rate: int = 16000) -> Optional[np.ndarray]:
+        if sample_rate != 16000:
+            raise ValueError("the speaker engine takes 16 kHz audio")
+        if self.h is None:
+            raise _lib.WlxError("speaker engine is closed")
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        cap = self.spec.max_seconds * 16000
+        if len(pcm) > cap:              # (the session buffer holds 45 s; a longer enrolment clip is cut, not refused)
+            pcm = pcm[:cap]
+        out = np.zeros(self.spec.embed_dim, dtype=np.float32)
+        f32p = C.POINTER(C.c_float)
+        rc = self.lib.wlx_spk_embed(self.h, pcm.ctypes.data_as(f32p), len(pcm), out.ctypes.data_as(f32p))
+        if rc == _lib.ERR_TOO_SHORT:
+            return None
+        _lib.check(rc)
+        return out
+
+    __call__ = embed
+
+    def timings(self) -> Tuple[float, float]:
+        """device milliseconds of the last embed: (filterbank, network)"""
+        a, b = C.c_float(), C.c_float()
+        _lib.check(self.lib.wlx_spk_debug_timings(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.wlx_spk_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+_shared: Dict[Tuple[str, int], SpeakerEmbedderHIP] = {}
+_shared_mu = threading.Lock()
+
+
+def shared_embedder(checkpoint: str, device: int = 0) -> SpeakerEmbedderHIP:
+    """one engine per (checkpoint, device), created by the first client that asks for diarization"""
+    with _shared_mu:
+        key = (checkpoint, device)
+        if key not in _shared or _shared[key].h is None:
+            _shared[key] = SpeakerEmbedderHIP.from_checkpoint(checkpoint, device)
+        return _shared[key]
+
+
+def close_shared():
+    with _shared_mu:
+        for e in _shared.values():
+            e.close()
+        _shared.clear()
+
+
+class SpeakerDiarizer:
+    """Online speaker clustering on unit-norm embeddings, behaving as the reference's class of the same name
+    (whisper_live/diarization.py). `embedder`: a callable (pcm, sample_rate) -> embedding or None; None = the HIP engine of
+    `embedding_model` on `device`, loaded on first use. `hf_token` is accepted for the reference's signature; the look-up of
+    artifacts.resolve_diarization_model reads the hub's own environment."""
+
+    def __init__(self, similarity_threshold=0.55, max_speakers=10, embedding_model="pyannote/wespeaker-voxceleb-resnet34-LM",
+                 hf_token=None, speaker_names=None, embedder: Optional[Callable] = None, device: int = 0):
+        self.similarity_threshold = similarity_threshold
+        self.max_speakers = max_speakers
+        self.speaker_names = [] if not speaker_names else list(speaker_names)
+        self.speakers = {}          # label -> running centroid (unit norm), in order of first appearance
+        self._created = 0           # speakers made by identify_speaker since the last reset (enrolments do not count)
+        self._embed = embedder
+        self._checkpoint_name = embedding_model
+        self._device = device
+
+    def _auto_label(self) -> str:
+        return "SPEAKER_%02d" % self._created
+
+    def _ensure_embedder(self):
+        if self._embed is None:
+            from .artifacts import resolve_diarization_model
+            path = resolve_diarization_model(self._checkpoint_name)
+            if path is None:
+                raise FileNotFoundError(f"no speaker-embedding checkpoint found for '{self._checkpoint_name}'")
+            self._embed = shared_embedder(path, self._device)
+
+    def _compute_embedding(self, audio_np, sample_rate=16000):
+        """unit-norm embedding of the audio, None under MIN_SECONDS"""
+        self._ensure_embedder()
+        if len(audio_np) < sample_rate * MIN_SECONDS:
+            return None
+        emb = self._embed(audio_np, sample_rate)
+        if emb is None:
+            return None
+        emb = np.asarray(emb)
+        return emb / np.linalg.norm(emb)
+
+    def _closest(self, emb):
+        """(label, similarity) of the centroid nearest to `emb`: the first one in insertion order on a tie, (None, -1.0)
+        when there is none (or none above -1)"""
+        ids = list(self.speakers)
+        if not ids:
+            return None, -1.0
+        sims = [float(np.dot(emb, self.speakers[i])) for i in ids]       # cosine: both sides are unit vectors
+        k = int(np.argmax(sims))            # first maximum, as a strict '>' scan finds it
+        return (ids[k], sims[k]) if sims[k] > -1.0 else (None, -1.0)
+
+    def identify_speaker(self, audio_np, sample_rate=16000):
+        """the label of the segment's speaker, or None when the audio is too short to embed"""
+        emb = self._compute_embedding(audio_np, sample_rate)
+        if emb is None:
+            return None
+        who, sim = self._closest(emb)
+        if sim >= self.similarity_threshold:
+            # matched: the centroid moves a tenth of the way and goes back onto the unit sphere
+            c = self.speakers[who] * 0.9 + emb * 0.1
+            self.speakers[who] = c / np.linalg.norm(c)
+            return who
+        if len(self.speakers) >= self.max_speakers:
+            # at the cap nobody new is created: the nearest speaker takes the segment, its centroid unchanged
+            return who or self._auto_label()
+        # a new speaker: the next of `speaker_names` while they last, then the numbered label
+        who = self.speaker_names[self._created] if self._created < len(self.speaker_names) else self._auto_label()
+        self._created += 1
+        self.speakers[who] = emb
+        return who
+
+    def enroll_speaker(self, speaker_name, audio_np, sample_rate=16000):
+        """store the audio's embedding as `speaker_name`'s centroid; False when the audio is too short"""
+        emb = self._compute_embedding(audio_np, sample_rate)
+        if emb is not None:
+            self.speakers[speaker_name] = emb
+        return emb is not None
+
+    def reset(self):
+        """forget every speaker, enrolled ones included; numbering starts again at 0"""
+        self.speakers = {}
+        self._created = 0

@@ -22,8 +22,13 @@ What differs, on purpose:
     cache), each translating client gets the reference's queue + ``ServeClientTranslation`` + daemon thread (server.py:203-229)
     and receives ``translated_segments`` messages; no ``transformers`` model is loaded. Without a checkpoint the option is
     ignored with a log line, as before;
-  * diarization and the OpenAI-style REST endpoint are separate products around the path (their own models / HTTP stack) and
-    are not provided: the options are accepted and ignored with a log line, ``enable_rest`` raises;
+  * diarization (``enable_diarization`` / ``diarization_threshold`` / ``max_speakers``) runs on the HIP WeSpeaker ResNet34 engine
+    (whisperlive_amd/diarization.py): when a checkpoint resolves (artifacts.resolve_diarization_model: a file or directory,
+    $WLX_MODEL_ROOT, the Hugging Face cache) each such client gets its own ``SpeakerDiarizer`` (server.py:346-363 of the
+    reference) on the GPU's shared embedder and its completed segments carry ``speaker``; ``pyannote.audio`` is never loaded and
+    ``hf_token`` is not used. Without a checkpoint the option is ignored with a log line, as before;
+  * the OpenAI-style REST endpoint is a separate product around the path (its own HTTP stack) and is not provided:
+    ``enable_rest`` raises;
   * ``use_vad`` is kept per connection (the reference stores it on the server object, server.py:394, so two clients
     with different settings race).
 """
@@ -192,6 +197,25 @@ class TranscriptionServer:
 
     translation_model = os.environ.get("WLX_TRANSLATION_MODEL", "alirezamsh/small100")   # a directory or a hub id
 
+    # a checkpoint file, a directory or a hub id; None = $WLX_DIARIZATION_MODEL as it stands when a client asks, else the
+    # reference's default (artifacts.resolve_diarization_model)
+    diarization_model: Optional[str] = None
+    # (checkpoint path, device index) -> callable (pcm, sample_rate) -> embedding or None. None = the HIP engine
+    # (diarization.shared_embedder); an embedding application, or a test, may supply its own embedder here
+    embedder_factory: Optional[Callable] = None
+
+    def _create_diarizer(self, options, path, device_index):
+        """the reference's per-client SpeakerDiarizer (server.py:346-363) on this GPU's shared HIP embedder"""
+        from .diarization import SpeakerDiarizer, shared_embedder
+        make = self.embedder_factory or shared_embedder
+        try:
+            embedder = make(path, device_index)
+        except Exception as e:  # noqa: BLE001 — an unreadable checkpoint costs the labels, not the session
+            logging.error(f"enable_diarization: cannot load {path}: {e}; disabled")
+            return None
+        return SpeakerDiarizer(similarity_threshold=options.get("diarization_threshold", 0.55),
+                               max_speakers=options.get("max_speakers", 10), embedder=embedder, device=device_index)
+
     def initialize_client(self, websocket, options, faster_whisper_custom_model_path, whisper_tensorrt_path,
                           trt_multilingual, trt_py_session=False):
         translation_dir = None
@@ -200,8 +224,12 @@ class TranscriptionServer:
             translation_dir = resolve_translation_model(self.translation_model)
             if translation_dir is None:
                 logging.warning("enable_translation: the translation side-channel is not part of this server; ignored")
+        diarization_path = None
         if options.get("enable_diarization", False):
-            logging.warning("enable_diarization: speaker diarization is not part of this server; disabled")
+            from .artifacts import resolve_diarization_model
+            diarization_path = resolve_diarization_model(self.diarization_model)
+            if diarization_path is None:
+                logging.warning("enable_diarization: speaker diarization is not part of this server; disabled")
 
         if self.backend.is_tensorrt() or self.backend.is_openvino():
             name = "TensorRT-LLM" if self.backend.is_tensorrt() else "OpenVINO"
@@ -265,6 +293,7 @@ class TranscriptionServer:
                 model_factory=self.model_factory,
                 max_batch=self.batch_config["max_batch_size"] if self.batch_config is not None else 1,
                 translation_queue=translation_queue,
+                diarization=self._create_diarizer(options, diarization_path, device_index) if diarization_path is not None else None,
             )
             if translation_client is not None:
                 client.translation_client, client.translation_thread = translation_client, translation_thread
