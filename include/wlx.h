@@ -159,6 +159,36 @@ int32_t wlx_logmel(wlx_engine* e, int32_t slot, int32_t item, const float* pcm, 
  * itself surface at that later call. */
 int32_t wlx_pcm_put(wlx_engine* e, int32_t slot, int32_t item, const float* pcm, int64_t n);
 int32_t wlx_logmel_resident(wlx_engine* e, int32_t slot, int32_t item, int32_t* n_frames_out);
+/* ---- file audio front end (PRODUCT entry points of the file path: transcribe(path), the REST endpoint) ----
+ * Replaces the host-side down-mix and float64 scipy.signal.resample_poly of whisperlive_amd/audio_io.py load_audio (which stands in
+ * for faster_whisper.audio.decode_audio, whisper_live/transcriber/transcriber_faster_whisper.py:821): the file's samples cross
+ * PCIe ONCE, in their file format, and arrive as 16 kHz mono float32 in the item's PCM buffer.
+ * `frames`: host pointer, interleaved [n_frames][channels], 1 <= channels <= WLX_PCM_MAX_CHANNELS; sample_format WLX_PCM_F32 (values
+ * used as they are) or WLX_PCM_S16 (int16 scaled by 1 / 32768). Mono = the float32 mean (channels added in order, one division).
+ * Output m = sum_j mono[j] * h[half_len + m * down - j * up] with up / down = 16000 / sample_rate reduced, half_len = 10 * max(up, down)
+ * and h = up * firwin(2 * half_len + 1, 1 / max(up, down), window = ("kaiser", 5.0)) — the filter of scipy.signal.resample_poly's
+ * defaults, designed by the library in double, rounded to float32 once, cached per ratio; float32 accumulation in a fixed order.
+ * *n_out = ceil(n_frames * up / down) samples are resident afterwards and a following wlx_logmel_resident behaves exactly as after
+ * a wlx_pcm_put of those samples. sample_rate == 16000 converts and down-mixes only: the samples are copied, not filtered (mono F32:
+ * bit-identical to wlx_pcm_put, negative zeros included).
+ * RATES: a rate is served when max(up, down) <= 640 AND the tap table with the input span of 64 outputs fits 64 KB of LDS:
+ *     (2 * half_len + 1) + floor((63 * down + 2 * half_len) / up) + 2 <= 16384 floats.
+ * The second condition binds steep down-sampling only (up = 1: down <= 159, i.e. up to 2.544 MHz); every ratio with up >= down and
+ * max <= 640 passes it. Served: 8000, 11025, 12000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000, 352800, 384000,
+ * 768000 Hz among others. Any other rate (44101 Hz, say) is REFUSED with WLX_ERR_ARG before any launch: nothing is read, nothing
+ * becomes resident, and the caller resamples on the host (whisperlive_amd/engine.py resample_supported restates the rule;
+ * transcribe() answers a refusal with its host route). n_frames is bounded by the 3600 s of OUTPUT (plus one second of input).
+ * The file streams through a bounded pinned staging buffer in blocks (8 MB of file bytes each, two in flight), each block carrying
+ * the filter's history and look-ahead; the result does not depend on where the block seams fall. wlx_pcm_put's conventions hold:
+ * at most 3600 s of OUTPUT, the PCM buffer grows, recorded log-mel requests that read the item go out first, one call per slot at
+ * a time, never the null stream; the caller's frames may be reused on return. */
+#define WLX_PCM_F32 0
+#define WLX_PCM_S16 1
+#define WLX_PCM_MAX_CHANNELS 8
+int32_t wlx_pcm_put_frames(wlx_engine* e, int32_t slot, int32_t item, const void* frames, int64_t n_frames, int32_t channels,
+                           int32_t sample_format, int32_t sample_rate, int64_t* n_out);
+/* Copy the item's resident PCM (wlx_pcm_put / wlx_pcm_put_frames) to the host: *n_out samples (nullable `out`: the count only). */
+int32_t wlx_pcm_get(wlx_engine* e, int32_t slot, int32_t item, float* out, int64_t cap, int64_t* n_out);
 /* Copy an item's device features to host / replace them from host (float32 [n_mels, n_frames]). */
 int32_t wlx_features_get(wlx_engine* e, int32_t slot, int32_t item, float* out, int64_t cap_floats,
                          int32_t* n_frames_out);
@@ -464,6 +494,19 @@ int32_t wlx_debug_dec_cross_attn(int32_t device, const uint16_t* q, int64_t ldq,
 int32_t wlx_debug_dec_self_attn(int32_t device, const uint16_t* q, int64_t ldq, const uint16_t* kc, const uint16_t* vc,
                                 int64_t cache_row_stride, int32_t cache_rows, int32_t d, int32_t H, int32_t rows, const int32_t* pos,
                                 const int32_t* ancrow, const int16_t* anc, int32_t ident_ancestry, uint16_t* out, int64_t ldo);
+
+/* The audio front end's kernel (csrc/resample.hip), same conventions: host arrays, a private stream of `device`, `out` (cap floats)
+ * copied in AND out so floats past *n_out come back unchanged. ONE copy and ONE launch per block of block_frames input frames
+ * (0: the product default, 8 MB of file bytes); a block's outputs read its own frames only, so block_frames moves the seams.
+ * WLX_ERR_ARG before any launch: channels outside 1..WLX_PCM_MAX_CHANNELS, sample_rate <= 0, n_frames < 0, an unknown format, a
+ * ratio the kernel does not serve (wlx_pcm_put_frames RATES), n_frames > 2^50, block_frames below the filter's reach of ceil(2 * half_len / up) + 2 frames,
+ * cap < ceil(n_frames * up / down). */
+int32_t wlx_debug_resample(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
+                           int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out);
+/* The same, and the summed HIP-event time of the block launches (scripts/resample_time.py). */
+int32_t wlx_debug_resample_timed(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
+                                 int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out,
+                                 float* kernel_ms_out);
 
 #ifdef __cplusplus
 }

@@ -15,11 +15,11 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "host.hip", "engine.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "host.hip", "engine.hip", "resample.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
-    "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
+    "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
     "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
@@ -30,6 +30,7 @@ EXPORTS = [
     "wlx_mt_debug_embed",
     "wlx_spk_debug_timings", "wlx_spk_debug_fbank", "wlx_spk_debug_conv", "wlx_spk_debug_pool",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
+    "wlx_debug_resample", "wlx_debug_resample_timed",
 ]
 
 
@@ -41,7 +42,7 @@ HIPCC_EXTRA = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 
 
 class WlxError(RuntimeError):
-    pass
+    code = None             # the wlx_status the library returned (set by `check`)
 
 
 class wlx_spec(C.Structure):
@@ -94,6 +95,13 @@ class wlx_spk_spec(C.Structure):
 
 
 ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
+ERR_ARG = 1             # wlx_status WLX_ERR_ARG
+PCM_F32, PCM_S16 = 0, 1           # wlx.h WLX_PCM_F32 / WLX_PCM_S16
+PCM_MAX_CHANNELS = 8
+# what the device resampler serves (csrc/resample.hip resample_ratio; engine.resample_supported restates its rule)
+RESAMPLE_MAX_RATIO = 640          # max(up, down) of 16000 / rate (RS_MAX_RATIO)
+RESAMPLE_MIN_TILE = 64            # the smallest tile of outputs a workgroup takes (RS_MIN_TILE) ...
+RESAMPLE_MAX_LDS = 64 * 1024      # ... whose input span, with the tap table, has to fit this many bytes (RS_MAX_LDS)
 
 
 class wlx_debug_gemm_args(C.Structure):
@@ -242,6 +250,8 @@ def load() -> C.CDLL:
     lib.wlx_slot_destroy.argtypes = [vp, i32]
     lib.wlx_logmel.argtypes = [vp, i32, i32, f32p, i64, i32p]
     lib.wlx_pcm_put.argtypes = [vp, i32, i32, f32p, i64]
+    lib.wlx_pcm_put_frames.argtypes = [vp, i32, i32, vp, i64, i32, i32, i32, C.POINTER(C.c_int64)]
+    lib.wlx_pcm_get.argtypes = [vp, i32, i32, f32p, i64, C.POINTER(C.c_int64)]
     lib.wlx_logmel_resident.argtypes = [vp, i32, i32, i32p]
     lib.wlx_features_get.argtypes = [vp, i32, i32, f32p, i64, i32p]
     lib.wlx_features_set.argtypes = [vp, i32, i32, f32p, i32, i32]
@@ -300,6 +310,8 @@ def load() -> C.CDLL:
     lib.wlx_debug_dec_self_attn.argtypes = [i32, u16p, i64, u16p, u16p, i64, i32, i32, i32, i32, i32p, i32p, C.POINTER(C.c_int16), i32,
                                             u16p, i64]
     lib.wlx_debug_gemm.argtypes = [i32, C.POINTER(wlx_debug_gemm_args), u16p, f32p, f32p, f32p, u16p, f32p, u16p, u16p, i32p]
+    lib.wlx_debug_resample.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p]
+    lib.wlx_debug_resample_timed.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p, f32p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):
@@ -338,4 +350,6 @@ def tensor_array(weights):
 def check(rc: int):
     if rc != 0:
         msg = load().wlx_last_error()
-        raise WlxError(f"libwlx error {rc}: {msg.decode() if msg else '?'}")
+        err = WlxError(f"libwlx error {rc}: {msg.decode() if msg else '?'}")
+        err.code = rc
+        raise err

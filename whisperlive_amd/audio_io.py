@@ -6,7 +6,9 @@ available offline, and the only audio the reference ships — ``assets/jfk.flac`
 (tests/test_server.py:73-118) — is 24-bit stereo 44.1 kHz FLAC. This module is a dependency-free reader for exactly that
 job: a FLAC decoder (fixed / LPC / verbatim / constant subframes, partitioned Rice residuals, stereo decorrelation; checked
 against the MD5 of the unencoded audio that every FLAC file carries in its STREAMINFO block), a RIFF/WAVE reader, channel
-down-mix and polyphase resampling (``scipy.signal.resample_poly``). It is host-side plumbing: FFmpeg's resampler is a
+down-mix and polyphase resampling (``scipy.signal.resample_poly``). ``read_audio`` stops after the decode and returns the file's own
+frames and rate: the file path of ``transcribe`` hands those to the device front end (``Slot.put_frames``), which converts,
+down-mixes and resamples there. It is host-side plumbing: FFmpeg's resampler is a
 different filter, so samples agree with the reference's decode to resampler tolerance, not bit for bit.
 """
 from __future__ import annotations
@@ -31,10 +33,8 @@ def _read_all(src: PathOrFile) -> bytes:
 
 
 # ---------------------------------------------------------------------------------------------------------------- WAV
-def read_wav(src: PathOrFile) -> Tuple[np.ndarray, int]:
-    """RIFF/WAVE -> (float32 [frames, channels] in [-1, 1), sample rate). PCM 8/16/24/32-bit, IEEE float 32/64,
-    WAVE_FORMAT_EXTENSIBLE wrappers of those."""
-    b = _read_all(src)
+def _wav_parse(b: bytes):
+    """-> (format tag, channels, sample rate, bits per sample, the data chunk's bytes)"""
     if b[:4] != b"RIFF" or b[8:12] != b"WAVE":
         raise ValueError("not a RIFF/WAVE file")
     pos, fmt, data = 12, None, None
@@ -52,6 +52,13 @@ def read_wav(src: PathOrFile) -> Tuple[np.ndarray, int]:
     tag, ch, sr, _br, _ba, bits = struct.unpack_from("<HHIIHH", fmt, 0)
     if tag == 0xFFFE and len(fmt) >= 26:                      # extensible: the real format is the first GUID word
         tag = struct.unpack_from("<H", fmt, 24)[0]
+    return tag, ch, sr, bits, data
+
+
+def read_wav(src: PathOrFile) -> Tuple[np.ndarray, int]:
+    """RIFF/WAVE -> (float32 [frames, channels] in [-1, 1), sample rate). PCM 8/16/24/32-bit, IEEE float 32/64,
+    WAVE_FORMAT_EXTENSIBLE wrappers of those."""
+    tag, ch, sr, bits, data = _wav_parse(_read_all(src))
     if tag == 1:
         if bits == 8:
             x = (np.frombuffer(data, np.uint8).astype(np.float32) - 128.0) / 128.0
@@ -313,6 +320,35 @@ def load_audio(src: PathOrFile, sampling_rate: int = 16000) -> np.ndarray:
     else:
         raise ValueError("unsupported audio container (WAV and FLAC are read natively; decode other formats to 16 kHz "
                          "float32 PCM first)")
+    mono = x.mean(axis=1) if x.shape[1] > 1 else x[:, 0]
+    if sr != sampling_rate:
+        from scipy.signal import resample_poly
+        g = gcd(int(sr), int(sampling_rate))
+        mono = resample_poly(mono.astype(np.float64), sampling_rate // g, sr // g)
+    return np.ascontiguousarray(mono, dtype=np.float32)
+
+
+def read_audio(src: PathOrFile) -> Tuple[np.ndarray, int]:
+    """File / bytes / file object -> (frames [n, channels], sample rate) in the file's own rate and channel count, for the device
+    front end (engine.Slot.put_frames): 16-bit PCM WAV comes back as int16 (half the bytes to upload; the device scales by 1 / 32768
+    as read_wav does), everything else as float32 in [-1, 1)."""
+    b = _read_all(src)
+    if b[:4] == b"fLaC":
+        return read_flac(b)
+    if b[:4] == b"RIFF":
+        tag, ch, sr, bits, data = _wav_parse(b)
+        if tag == 1 and bits == 16 and ch >= 1:
+            x = np.frombuffer(data[: len(data) // 2 * 2], "<i2")
+            return x[: x.size // ch * ch].reshape(-1, ch), sr
+        return read_wav(b)
+    raise ValueError("unsupported audio container (WAV and FLAC are read natively; decode other formats to 16 kHz "
+                     "float32 PCM first)")
+
+
+def frames_to_mono(frames: np.ndarray, sr: int, sampling_rate: int = 16000) -> np.ndarray:
+    """load_audio's host route on frames read_audio returned: float32 channel mean, then resample_poly in float64."""
+    x = np.asarray(frames)
+    x = x.astype(np.float32) / 32768.0 if x.dtype == np.int16 else x.astype(np.float32, copy=False)
     mono = x.mean(axis=1) if x.shape[1] > 1 else x[:, 0]
     if sr != sampling_rate:
         from scipy.signal import resample_poly

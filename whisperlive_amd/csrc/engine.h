@@ -48,6 +48,8 @@ struct Slot {
     std::vector<int> nframes;
     std::vector<int64_t> npcm;                       // samples resident per item
     unsigned* gmax = nullptr;
+    ResampleStage rs{};                              // staging of wlx_pcm_put_frames, allocated at its first call (engine.hip)
+    bool rs_ready = false;
     long long* d_rng = nullptr;                      // [2 * WLX_LM_MAXRANGES] range table of the last wlx_logmel_ring
     // encoder
     half_t *featT = nullptr, *h1 = nullptr, *ln = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr,

@@ -204,6 +204,7 @@ static void slot_free(Slot* s) {
     if (s->ev_lm1) (void)hipEventDestroy(s->ev_lm1);
     if (s->ev_en0) (void)hipEventDestroy(s->ev_en0);
     if (s->ev_en1) (void)hipEventDestroy(s->ev_en1);
+    for (hipEvent_t ev : s->rs.copied) if (ev) (void)hipEventDestroy(ev);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -644,6 +645,57 @@ extern "C" int32_t wlx_pcm_put(wlx_engine* e, int32_t slot, int32_t item, const 
     CK(hipMemcpyAsync(dp, pcm, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     CK(hipStreamSynchronize(s->stream));   // the caller's PCM buffer may be reused after return
     s->npcm[item] = n;
+    return WLX_OK;
+}
+
+// file frames -> 16 kHz mono float32 in the item's PCM buffer (resample.hip): wlx_pcm_put with the conversion, the down-mix and the
+// resampler on the device. Everything is validated before the first byte of `frames` is read.
+extern "C" int32_t wlx_pcm_put_frames(wlx_engine* e, int32_t slot, int32_t item, const void* frames, int64_t n_frames, int32_t channels,
+                                      int32_t sample_format, int32_t sample_rate, int64_t* n_out) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (!frames || n_frames <= 0) return set_error(WLX_ERR_ARG, "empty audio");
+    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", item);
+    CKR(resample_check_args(frames, n_frames, channels, sample_format, sample_rate));
+    if (n_frames > (int64_t)sample_rate * 3600 + sample_rate) return set_error(WLX_ERR_ARG, "audio chunk too long");
+    ResamplePlan pl{};
+    CKR(resample_plan(e->device, sample_rate, &pl));
+    const int64_t n = resample_out_len(pl, n_frames);
+    if (n > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
+    CK(hipSetDevice(e->device));
+    if ((size_t)n > s->pcm_cap || std::find(s->lm_items.begin(), s->lm_items.end(), (int)item) != s->lm_items.end())
+        CKR(flush_logmel(e, s));            // a recorded log-mel request reads this item's PCM (or the buffers are about to be re-allocated)
+    CKR(slot_grow_audio(e, s, (size_t)n));
+    const long long block = resample_default_block(channels, sample_format);
+    if (!s->rs_ready) {                     // two pinned and two device blocks, for the slot's life
+        for (int b = 0; b < 2; ++b) {
+            if (!s->rs.pinned[b]) CKR(halloc(s->host_allocs, &s->rs.pinned[b], RS_BLOCK_BYTES));
+            if (!s->rs.dev[b]) CKR(dalloc(s->allocs, &s->rs.dev[b], RS_BLOCK_BYTES, false));
+            if (!s->rs.copied[b]) CK(hipEventCreateWithFlags(&s->rs.copied[b], hipEventDisableTiming));
+        }
+        s->rs_ready = true;
+    }
+    s->npcm[item] = 0;                      // (a failed run leaves no half-written audio resident)
+    CKR(resample_run(pl, frames, n_frames, channels, sample_format, block, s->rs, s->pcm + (size_t)item * s->pcm_cap, s->stream, nullptr));
+    s->npcm[item] = n;
+    if (n_out) *n_out = n;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_pcm_get(wlx_engine* e, int32_t slot, int32_t item, float* out, int64_t cap, int64_t* n_out) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", item);
+    const int64_t n = s->npcm[item];
+    if (n_out) *n_out = n;
+    if (!out) return WLX_OK;
+    if (n <= 0) return set_error(WLX_ERR_STATE, "item %d: no PCM resident", item);
+    if (n > cap) return set_error(WLX_ERR_ARG, "output buffer too small");
+    CK(hipSetDevice(e->device));
+    CK(hipMemcpyAsync(out, s->pcm + (size_t)item * s->pcm_cap, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    CK(hipStreamSynchronize(s->stream));
     return WLX_OK;
 }
 

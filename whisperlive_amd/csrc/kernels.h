@@ -90,4 +90,21 @@ void launch_attn_encoder(const half_t* Q, long ldq, const half_t* K, long ldk, c
                          long item_stride_q, long item_stride_k, long item_stride_vt, long item_stride_o,
                          hipStream_t s);
 
+// ---------------------------------------------------------------- resample.hip
+// file audio -> 16 kHz mono float32: sample conversion, channel mean and polyphase resampling (scipy.signal.resample_poly's filter)
+constexpr size_t RS_BLOCK_BYTES = 8u << 20;                                // file bytes per staged block of the product path
+struct ResamplePlan { int up, down, half_len, tile; const float* taps; }; // tile: outputs per workgroup; taps: device, [2 * half_len + 1], cached per device and ratio
+// the two halves of the bounded staging a run streams the file through: device blocks, and (product path) pinned host blocks with
+// the event recorded behind the copy out of each
+struct ResampleStage { unsigned char* pinned[2]; unsigned char* dev[2]; hipEvent_t copied[2]; bool used[2]; };
+int resample_check_args(const void* frames, long long n_frames, int channels, int sample_format, int sample_rate);
+int resample_plan(int device, int sample_rate, ResamplePlan* out);        // WLX_ERR_ARG for a ratio the kernel does not serve
+long long resample_out_len(const ResamplePlan& pl, long long n_frames);   // ceil(n_frames * up / down)
+long long resample_reach(const ResamplePlan& pl);                         // smallest legal block, in input frames
+long long resample_default_block(int channels, int sample_format);        // frames per staged block of the product path
+// host frames -> d_out[0 .. out_len), one copy and one launch per block of `block_frames` input frames on `st`; waits for `st`.
+// kernel_ms (nullable): the launches' summed HIP-event time.
+int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames, int channels, int sample_format, long long block_frames,
+                 ResampleStage& sg, float* d_out, hipStream_t st, float* kernel_ms);
+
 }  // namespace wlx

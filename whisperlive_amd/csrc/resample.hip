@@ -1,0 +1,343 @@
+// resample.hip — the device audio front end of the file path: sample conversion (int16 / float32), channel down-mix and polyphase
+// resampling to 16 kHz in one kernel (include/wlx.h wlx_pcm_put_frames; test hook wlx_debug_resample).
+//
+// Arithmetic = scipy.signal.resample_poly(mean over channels, up, down) with its default filter, which is what
+// whisperlive_amd/audio_io.py load_audio computes on the host in float64:
+//   half_len = 10 * max(up, down);  h = up * firwin(2 * half_len + 1, 1 / max(up, down), window = ("kaiser", 5.0))
+//   y[m] = sum_j x[j] * h[half_len + m * down - j * up]          (indices inside h; x is zero outside the file)
+// The taps are designed here in double (sinc x Kaiser, unit gain at DC), rounded to float32 once and cached per device and ratio.
+// The kernel accumulates in float32, ALWAYS in the same order for a given output (k ascending = input index descending from the newest
+// sample the output reaches), and an output depends on nothing but the absolute input indices: where a block or tile seam falls
+// cannot change a bit of the result.
+//
+// Work split: a workgroup of 256 lanes owns a tile of 1024 consecutive outputs (512 ... 64 for the steep down-sampling ratios whose
+// input span would not fit otherwise, resample_ratio). It copies the whole tap table into LDS in its natural
+// order and stages the input span its tile reaches — (tile - 1) * down / up frames plus 2 * half_len / up of history and look-ahead —
+// converting and down-mixing on the way in, so every file sample is converted once per tile and then read ~(taps per output * up /
+// down) times from LDS. The natural order of h IS the phase order: lane i of a wave reads h[p_i + k * up] with p_i = (half_len + m_i *
+// down) mod up for consecutive m_i, i.e. addresses that step by (down mod up) — odd for 441 against 160 / 320 / 640 / 80, so the
+// lanes of a half wave fall into distinct banks; up = 1 or 2 (every rate that is a multiple of 8 kHz) is an LDS broadcast. The input
+// reads step by down / up frames per lane (two- to four-way conflicts at 96 / 192 kHz, where the kernel is still far shorter than
+// the upload of its input). The job is bound by the PCIe upload, not by this kernel.
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <tuple>
+#include "host.h"
+
+namespace wlx {
+
+constexpr int RS_TILE = 1024;           // outputs per workgroup ...
+constexpr int RS_MIN_TILE = 64;         // ... halved down to this while the tile's input span does not fit the LDS (resample_ratio)
+constexpr int RS_THREADS = 256;
+constexpr int RS_MAX_RATIO = 640;       // max(up, down): 11025 Hz (640 / 441); a tap table of 12801 floats
+constexpr int RS_MAX_LDS = 64 * 1024;   // taps + staged span, bytes (the default dynamic-LDS limit; two workgroups per CU at the largest)
+
+struct ResampleArgs {
+    const void* raw;        // interleaved frames [j_base, j_base + raw_frames) of the file, in the file's format
+    long long j_base, raw_frames, n_frames;
+    int channels;
+    int up, down, half_len;
+    int tile;               // outputs per workgroup
+    const float* taps;      // [2 * half_len + 1]
+    float* out;             // out[m] for m in [m0, m1)
+    long long m0, m1;
+};
+
+__device__ __forceinline__ long long floor_div(long long a, long long b) {       // b > 0
+    long long q = a / b;
+    return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+template <int FMT>
+__device__ __forceinline__ float rs_sample(const void* raw, long long idx) {
+    if (FMT == WLX_PCM_S16) return (float)reinterpret_cast<const short*>(raw)[idx] * (1.0f / 32768.0f);
+    return reinterpret_cast<const float*>(raw)[idx];
+}
+
+template <int FMT>
+__global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs p) {
+    extern __shared__ float rs_lds[];
+    const int ntaps = 2 * p.half_len + 1;
+    float* hs = rs_lds;
+    float* xs = rs_lds + ntaps;
+    const long long mA = p.m0 + (long long)blockIdx.x * p.tile;
+    const long long mB = mA + p.tile < p.m1 ? mA + p.tile : p.m1;
+    // the input span of the tile: j with 0 <= half_len + m * down - j * up <= 2 * half_len for some m in [mA, mB)
+    const long long j_lo = -floor_div(-(mA * p.down - p.half_len), p.up);          // ceil((mA * down - half_len) / up)
+    const long long j_hi = floor_div((long long)p.half_len + (mB - 1) * p.down, p.up);
+    const int span = (int)(j_hi - j_lo + 1);
+    for (int i = threadIdx.x; i < ntaps; i += RS_THREADS) hs[i] = p.taps[i];
+    const int ch = p.channels;
+    const float fch = (float)ch;
+    for (int i = threadIdx.x; i < span; i += RS_THREADS) {
+        const long long j = j_lo + i;
+        float v = 0.f;
+        const long long r = j - p.j_base;
+        if (j >= 0 && j < p.n_frames && r >= 0 && r < p.raw_frames) {
+            const long long b = r * ch;
+            v = rs_sample<FMT>(p.raw, b);
+            if (ch > 1) {                          // the float32 mean: channels added in order, one division
+                for (int c = 1; c < ch; ++c) v += rs_sample<FMT>(p.raw, b + c);
+                v = v / fch;
+            }
+        }
+        xs[i] = v;
+    }
+    __syncthreads();
+    for (long long m = mA + threadIdx.x; m < mB; m += RS_THREADS) {
+        if (p.half_len == 0) {                                 // 16 kHz in: the converted, down-mixed sample itself (a -0.0f stays -0.0f)
+            p.out[m] = xs[m - j_lo];
+            continue;
+        }
+        const long long t = (long long)p.half_len + m * p.down;
+        const long long jh = t / p.up;                         // the newest input the output reaches
+        const int ph = (int)(t - jh * p.up);                   // its tap = the output's phase
+        const int K = (2 * p.half_len - ph) / p.up + 1;
+        const float* x = xs + (jh - j_lo);
+        const float* h = hs + ph;
+        float acc = 0.f;
+        for (int k = 0; k < K; ++k) acc = fmaf(x[-k], h[(long)k * p.up], acc);
+        p.out[m] = acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the plan of one ratio
+static double bessel_i0(double x) {             // sum ((x / 2)^k / k!)^2: converges in ~25 terms at x = 5
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 200; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-20 * sum) break;
+    }
+    return sum;
+}
+
+static long long gcd_ll(long long a, long long b) { while (b) { long long t = a % b; a = b; b = t; } return a; }
+
+void resample_design(int up, int down, std::vector<float>& taps, int* half_len_out) {
+    if (up == down) {                           // 16 kHz in: conversion and down-mix only (the kernel copies, the tap is not read)
+        taps.assign(1, 1.0f);
+        *half_len_out = 0;
+        return;
+    }
+    const int mx = std::max(up, down), hl = 10 * mx, n = 2 * hl + 1;
+    const double c = 1.0 / mx, pi = 3.14159265358979323846, i0b = bessel_i0(5.0);
+    std::vector<double> h((size_t)n);
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double m = (double)(i - hl), a = pi * c * m;
+        const double sinc = (i == hl) ? 1.0 : std::sin(a) / a;
+        const double r = m / (double)hl;
+        const double w = bessel_i0(5.0 * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+        h[i] = c * sinc * w;
+        s += h[i];
+    }
+    taps.resize((size_t)n);
+    for (int i = 0; i < n; ++i) taps[i] = (float)((double)up * (h[i] / s));
+    *half_len_out = hl;
+}
+
+static size_t rs_lds_bytes(int up, int down, int half_len, int tile) {
+    const long long span = ((long long)(tile - 1) * down + 2LL * half_len) / up + 2;
+    return (size_t)(2 * half_len + 1 + span) * sizeof(float);
+}
+
+// 16000 / sample_rate reduced, and the tile the kernel runs that ratio with. SERVED (include/wlx.h; mirrored by
+// whisperlive_amd/engine.py resample_supported): max(up, down) <= RS_MAX_RATIO, and the tap table plus the input span of RS_MIN_TILE
+// outputs fit RS_MAX_LDS. Needs no device.
+int resample_ratio(int sample_rate, int* up, int* down, int* tile) {
+    if (sample_rate <= 0) return set_error(WLX_ERR_ARG, "sample rate %d must be positive", sample_rate);
+    const long long g = gcd_ll(16000, sample_rate);
+    const long long u = 16000 / g, d = sample_rate / g;
+    if (std::max(u, d) > RS_MAX_RATIO)
+        return set_error(WLX_ERR_ARG, "sample rate %d Hz: 16000 / rate reduces to %lld / %lld, over the %d the device resampler serves "
+                         "(resample on the host)", sample_rate, u, d, RS_MAX_RATIO);
+    const int hl = u == d ? 0 : 10 * (int)std::max(u, d);
+    int t = RS_TILE;
+    while (t > RS_MIN_TILE && rs_lds_bytes((int)u, (int)d, hl, t) > (size_t)RS_MAX_LDS) t /= 2;
+    if (rs_lds_bytes((int)u, (int)d, hl, t) > (size_t)RS_MAX_LDS)
+        return set_error(WLX_ERR_ARG, "sample rate %d Hz: the tap table and the input span of %d outputs do not fit the device resampler's "
+                         "LDS (resample on the host)", sample_rate, RS_MIN_TILE);
+    *up = (int)u; *down = (int)d; *tile = t;
+    return WLX_OK;
+}
+
+// the filter's reach in input frames: the smallest block that still yields one output (resample_block_outputs >= 1)
+long long resample_reach(const ResamplePlan& pl) { return (2LL * pl.half_len + pl.up - 1) / pl.up + 2; }
+// outputs a block of `block_frames` input frames serves, wherever it starts
+static long long resample_block_outputs(const ResamplePlan& pl, long long block_frames) {
+    return ((block_frames - 2) * pl.up - 2LL * pl.half_len) / pl.down + 1;
+}
+
+int resample_plan(int device, int sample_rate, ResamplePlan* out) {
+    int up = 0, down = 0, tile = 0;
+    CKR(resample_ratio(sample_rate, &up, &down, &tile));
+    static std::mutex mu;
+    static std::map<std::tuple<int, int, int>, ResamplePlan> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find({device, up, down});
+    if (it != cache.end()) { *out = it->second; return WLX_OK; }
+    std::vector<float> taps;
+    ResamplePlan pl{};
+    pl.up = up; pl.down = down; pl.tile = tile;
+    resample_design(up, down, taps, &pl.half_len);
+    CK(hipSetDevice(device));
+    float* d = nullptr;
+    CK(hipMalloc(reinterpret_cast<void**>(&d), taps.size() * sizeof(float)));      // lives as long as the process: <= 51 KB per ratio and device
+    CKR(upload_sync(d, taps.data(), taps.size() * sizeof(float)));
+    pl.taps = d;
+    cache[{device, up, down}] = pl;
+    *out = pl;
+    return WLX_OK;
+}
+
+long long resample_out_len(const ResamplePlan& pl, long long n_frames) { return (n_frames * pl.up + pl.down - 1) / pl.down; }
+
+long long resample_default_block(int channels, int sample_format) {
+    return (long long)(RS_BLOCK_BYTES / ((size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4)));
+}
+
+int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames, int channels, int sample_format, long long block_frames,
+                 ResampleStage& sg, float* d_out, hipStream_t st, float* kernel_ms) {
+    const size_t fb = (size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4);
+    const long long n_out = resample_out_len(pl, n_frames);
+    const long long per = block_frames >= resample_reach(pl) ? resample_block_outputs(pl, block_frames) : 0;
+    if (per < 1) return set_error(WLX_ERR_ARG, "block of %lld frames is smaller than the filter's reach (%lld)", block_frames, resample_reach(pl));
+    const size_t lds = rs_lds_bytes(pl.up, pl.down, pl.half_len, pl.tile);
+    std::vector<hipEvent_t> evs;
+    int rc = WLX_OK;
+    long long blk = 0;
+    for (long long m0 = 0; m0 < n_out && rc == WLX_OK; m0 += per, ++blk) {
+        const long long m1 = std::min(n_out, m0 + per);
+        // the file frames outputs [m0, m1) reach, clamped to the file
+        long long a = m0 * pl.down - pl.half_len;
+        long long j_lo = a >= 0 ? (a + pl.up - 1) / pl.up : -((-a) / pl.up);
+        long long j_hi = ((long long)pl.half_len + (m1 - 1) * pl.down) / pl.up;
+        j_lo = std::max(j_lo, 0LL); j_hi = std::min(j_hi, n_frames - 1);
+        const long long nfr = std::max(0LL, j_hi - j_lo + 1);            // <= block_frames by the choice of `per`
+        const int b = (int)(blk & 1);
+        const char* src = static_cast<const char*>(frames) + (size_t)j_lo * fb;
+        rc = [&]() -> int {
+            if (nfr > 0) {
+                if (sg.pinned[b]) {
+                    // the pinned half is free once the copy out of it (two blocks ago) has run
+                    if (sg.used[b]) CK(hipEventSynchronize(sg.copied[b]));
+                    std::memcpy(sg.pinned[b], src, (size_t)nfr * fb);
+                    CK(hipMemcpyAsync(sg.dev[b], sg.pinned[b], (size_t)nfr * fb, hipMemcpyHostToDevice, st));
+                    CK(hipEventRecord(sg.copied[b], st));
+                    sg.used[b] = true;
+                } else {
+                    CK(hipMemcpyAsync(sg.dev[b], src, (size_t)nfr * fb, hipMemcpyHostToDevice, st));   // pageable source: staged by the runtime before it returns
+                }
+            }
+            ResampleArgs p{};
+            p.raw = sg.dev[b]; p.j_base = j_lo; p.raw_frames = nfr; p.n_frames = n_frames; p.channels = channels;
+            p.up = pl.up; p.down = pl.down; p.half_len = pl.half_len; p.tile = pl.tile; p.taps = pl.taps; p.out = d_out; p.m0 = m0; p.m1 = m1;
+            const unsigned grid = (unsigned)((m1 - m0 + pl.tile - 1) / pl.tile);
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            if (kernel_ms) {
+                CK(hipEventCreate(&e0)); evs.push_back(e0);
+                CK(hipEventCreate(&e1)); evs.push_back(e1);
+                CK(hipEventRecord(e0, st));
+            }
+            if (sample_format == WLX_PCM_S16) hipLaunchKernelGGL(resample_kernel<WLX_PCM_S16>, dim3(grid), dim3(RS_THREADS), lds, st, p);
+            else hipLaunchKernelGGL(resample_kernel<WLX_PCM_F32>, dim3(grid), dim3(RS_THREADS), lds, st, p);
+            CK(hipGetLastError());
+            if (kernel_ms) CK(hipEventRecord(e1, st));
+            return WLX_OK;
+        }();
+    }
+    if (rc == WLX_OK) {
+        hipError_t he = hipStreamSynchronize(st);     // the caller's frames and the staging halves may be reused after return
+        if (he != hipSuccess) rc = set_error(WLX_ERR_HIP, "resample: %s", hipGetErrorString(he));
+    } else {
+        (void)hipStreamSynchronize(st);
+    }
+    sg.used[0] = sg.used[1] = false;
+    if (kernel_ms) {
+        float total = 0.f;
+        for (size_t i = 0; i + 1 < evs.size() && rc == WLX_OK; i += 2) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, evs[i], evs[i + 1]) == hipSuccess) total += ms;
+        }
+        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+        *kernel_ms = total;
+    }
+    return rc;
+}
+
+// one validation for the product entry point and the hook: everything that does not need a device
+int resample_check_args(const void* frames, long long n_frames, int channels, int sample_format, int sample_rate) {
+    if (n_frames < 0) return set_error(WLX_ERR_ARG, "negative frame count");
+    if (n_frames > (1LL << 50)) return set_error(WLX_ERR_ARG, "frame count out of range");      // n_frames * up stays inside int64
+    if (channels < 1 || channels > WLX_PCM_MAX_CHANNELS) return set_error(WLX_ERR_ARG, "channels %d outside 1..%d", channels, WLX_PCM_MAX_CHANNELS);
+    if (sample_format != WLX_PCM_F32 && sample_format != WLX_PCM_S16) return set_error(WLX_ERR_ARG, "unknown sample format %d", sample_format);
+    if (sample_rate <= 0) return set_error(WLX_ERR_ARG, "sample rate %d must be positive", sample_rate);
+    if (n_frames > 0 && !frames) return set_error(WLX_ERR_ARG, "null frames");
+    int up, down, tile;
+    return resample_ratio(sample_rate, &up, &down, &tile);
+}
+
+}  // namespace wlx
+
+using namespace wlx;
+
+// ------------------------------------------------------------------------------------------------ test hooks (kernel_hooks.hip conventions)
+static int debug_resample(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format, int32_t sample_rate,
+                          int64_t block_frames, float* out, int64_t cap, int64_t* n_out, float* kernel_ms) {
+    if (!out || !n_out || cap < 0) return set_error(WLX_ERR_ARG, "null argument");
+    CKR(resample_check_args(frames, n_frames, channels, sample_format, sample_rate));
+    if (block_frames < 0) return set_error(WLX_ERR_ARG, "negative block size");
+    int up, down, tile;
+    CKR(resample_ratio(sample_rate, &up, &down, &tile));
+    {   // reach and output length need no device either
+        ResamplePlan tmp{}; tmp.up = up; tmp.down = down;
+        tmp.half_len = up == down ? 0 : 10 * std::max(up, down);
+        if (block_frames == 0) block_frames = resample_default_block(channels, sample_format);
+        if (block_frames < resample_reach(tmp))
+            return set_error(WLX_ERR_ARG, "block of %lld frames is smaller than the filter's reach (%lld)", (long long)block_frames, resample_reach(tmp));
+        if (resample_out_len(tmp, n_frames) > cap) return set_error(WLX_ERR_ARG, "output buffer too small");
+    }
+    int ndev = 0;
+    CK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, ndev - 1);
+    ResamplePlan pl{};
+    CKR(resample_plan(device, sample_rate, &pl));
+    CK(hipSetDevice(device));
+    const long long nout = resample_out_len(pl, n_frames);
+    *n_out = nout;
+    if (nout == 0) return WLX_OK;
+    const size_t fb = (size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4);
+    const long long bf = std::min<long long>(block_frames, n_frames);
+    struct Scope {
+        std::vector<void*> allocs; hipStream_t st = nullptr;
+        ~Scope() { if (st) (void)hipStreamSynchronize(st); for (void* p : allocs) (void)hipFree(p); if (st) (void)hipStreamDestroy(st); }
+    } S;
+    CK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
+    ResampleStage sg{};
+    unsigned char *r0 = nullptr, *r1 = nullptr;
+    float* dout = nullptr;
+    CKR(dalloc(S.allocs, &r0, (size_t)bf * fb, false));
+    CKR(dalloc(S.allocs, &r1, (size_t)bf * fb, false));
+    CKR(dalloc(S.allocs, &dout, (size_t)cap, false));
+    sg.dev[0] = r0; sg.dev[1] = r1;
+    CK(hipMemcpyAsync(dout, out, (size_t)cap * sizeof(float), hipMemcpyHostToDevice, S.st));     // copied in AND out
+    CKR(resample_run(pl, frames, n_frames, channels, sample_format, block_frames, sg, dout, S.st, kernel_ms));
+    CK(hipMemcpyAsync(out, dout, (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, S.st));
+    CK(hipStreamSynchronize(S.st));
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_debug_resample(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
+                                      int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out) {
+    return debug_resample(device, frames, n_frames, channels, sample_format, sample_rate, block_frames, out, cap, n_out, nullptr);
+}
+
+extern "C" int32_t wlx_debug_resample_timed(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
+                                            int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out,
+                                            float* kernel_ms_out) {
+    if (!kernel_ms_out) return set_error(WLX_ERR_ARG, "null argument");
+    return debug_resample(device, frames, n_frames, channels, sample_format, sample_rate, block_frames, out, cap, n_out, kernel_ms_out);
+}

@@ -83,6 +83,22 @@ class HipWhisperEngine:
         return Slot(self, sid.value, max_batch, max_rows_per_item)
 
 
+def resample_supported(sample_rate: int, channels: int = 1) -> bool:
+    """True when wlx_pcm_put_frames serves this file shape; other files keep the host route of audio_io.load_audio. Restates the
+    library's rule (include/wlx.h RATES, csrc/resample.hip resample_ratio): at most 8 channels; for up / down = 16000 / rate reduced,
+    max(up, down) <= 640, and the tap table plus the input span of 64 outputs fit 64 KB of LDS."""
+    from math import gcd
+    if sample_rate <= 0 or not 1 <= channels <= _lib.PCM_MAX_CHANNELS:
+        return False
+    g = gcd(16000, int(sample_rate))
+    up, down = 16000 // g, int(sample_rate) // g
+    if max(up, down) > _lib.RESAMPLE_MAX_RATIO:
+        return False
+    half_len = 0 if up == down else 10 * max(up, down)
+    span = ((_lib.RESAMPLE_MIN_TILE - 1) * down + 2 * half_len) // up + 2
+    return 4 * (2 * half_len + 1 + span) <= _lib.RESAMPLE_MAX_LDS
+
+
 class PcmRing:
     """The device-side mirror of ServeClientBase.frames_np (whisper_live/backend/base.py:173-234): a client's packets are appended
     ONCE, the VAD gate and the log-mel front end read them in HBM. Positions are absolute stream sample positions."""
@@ -135,6 +151,29 @@ class Slot:
     def pcm_put(self, pcm: np.ndarray, item: int = 0):
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         check(self.lib.wlx_pcm_put(self.engine._h, self.sid, item, _f32p(pcm), pcm.shape[0]))
+
+    def put_frames(self, frames: np.ndarray, sample_rate: int, item: int = 0) -> int:
+        """File frames [n, channels] (int16, or anything else as float32) at `sample_rate` -> 16 kHz mono float32 resident in the
+        item's PCM buffer, converted, down-mixed and resampled on the device (wlx_pcm_put_frames). -> samples resident.
+        Raises WlxError for a rate the device resampler does not serve (see `resample_supported`)."""
+        x = np.asarray(frames)
+        if x.ndim == 1:
+            x = x[:, None]
+        fmt = _lib.PCM_S16 if x.dtype == np.int16 else _lib.PCM_F32
+        x = np.ascontiguousarray(x, dtype=np.int16 if fmt == _lib.PCM_S16 else np.float32)
+        n = C.c_int64(0)
+        check(self.lib.wlx_pcm_put_frames(self.engine._h, self.sid, item, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], fmt,
+                                          int(sample_rate), C.byref(n)))
+        return n.value
+
+    def pcm(self, item: int = 0) -> np.ndarray:
+        """Host copy of the item's resident PCM (16 kHz mono float32)."""
+        n = C.c_int64(0)
+        check(self.lib.wlx_pcm_get(self.engine._h, self.sid, item, None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.float32)
+        if n.value:
+            check(self.lib.wlx_pcm_get(self.engine._h, self.sid, item, _f32p(out), out.size, C.byref(n)))
+        return out
 
     def logmel_ring(self, ring: "PcmRing", ranges: Sequence[Tuple[int, int]], item: int = 0) -> int:
         """log-mel of the concatenation of ring ranges [(start, end), ...] (absolute positions) -> frames; see wlx_logmel_ring"""

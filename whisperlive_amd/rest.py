@@ -1,0 +1,606 @@
+"""OpenAI-style file transcription endpoint: ``POST /v1/audio/transcriptions`` (multipart form -> text / json / verbose_json /
+srt / vtt, or server-sent events with ``stream=true``).
+
+A restatement of the reference's handler (whisper_live/server.py:490-598, 692-867) on the standard library — ``http.server`` and a
+multipart parser of its own, as ws.py does for WebSockets — with two deliberate differences:
+
+  * the reference builds a new ``WhisperModel`` per request; here every request runs on the GPU's SHARED transcriber, the one the
+    ``single_model`` WebSocket sessions use (``ServeClientHIP.MODELS``: a process that runs both servers holds one copy of the
+    weights), on a slot of the transcriber's pool that is handed back when the request ends. Requests rotate over ``devices`` as
+    connections do (sharding.assign_gpu);
+  * the uploaded file is not written to a temporary file: ``transcribe`` takes the bytes, decodes WAV / FLAC
+    (whisperlive_amd/audio_io.py) and hands the frames to the device front end (``Slot.put_frames``).
+
+The middleware order is the reference's (Starlette runs the last one added first): rate limit, then the API key, then CORS, then
+routing — so a 429 or a 401 carries no CORS headers, and every request counts against the limit, whatever it asks for.
+
+``TranscriptionServer.run(enable_rest=True)`` still raises NotImplementedError: this module is the endpoint, started on its own
+(``RestServer(...).start()`` or ``python -m whisperlive_amd.rest``); wiring the flag to it is a separate change.
+"""
+from __future__ import annotations
+
+import collections
+import json
+import logging
+import re
+import threading
+import time
+from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+from . import metrics as wl_metrics
+from .sharding import assign_gpu
+
+SUPPORTED_FORMATS = ["json", "text", "srt", "verbose_json", "vtt"]
+ROUTE = "/v1/audio/transcriptions"
+_CORS_METHODS = "DELETE, GET, HEAD, OPTIONS, PATCH, POST, PUT"
+
+
+# ------------------------------------------------------------------------------------------------------------ multipart
+class Part:
+    __slots__ = ("name", "filename", "content_type", "data")
+
+    def __init__(self, name: str, filename: Optional[str], content_type: Optional[str], data: bytes):
+        self.name, self.filename, self.content_type, self.data = name, filename, content_type, data
+
+    @property
+    def text(self) -> str:
+        return self.data.decode("utf-8", "replace")
+
+
+def _boundary_of(content_type: str) -> bytes:
+    if not content_type or not content_type.lower().lstrip().startswith("multipart/form-data"):
+        raise ValueError("Content-Type must be multipart/form-data")
+    m = re.search(r';\s*boundary=(?:"([^"]+)"|([^;\s]+))', content_type, re.I)
+    if not m:
+        raise ValueError("multipart/form-data without a boundary")
+    b = (m.group(1) or m.group(2)).encode("latin-1")
+    if not 1 <= len(b) <= 70:
+        raise ValueError("multipart boundary must be 1..70 characters")
+    return b
+
+
+def _delimiter_end(body: bytes, pos: int) -> Optional[Tuple[int, bool]]:
+    """`pos` is just behind '--boundary'. A real delimiter line goes on with '--' (the last one) or optional blanks and CRLF;
+    -> (position behind the line, last?) or None when these bytes only look like a boundary (file content)."""
+    if body[pos:pos + 2] == b"--":
+        return pos + 2, True
+    q = pos
+    while q < len(body) and body[q:q + 1] in (b" ", b"\t"):
+        q += 1
+    if body[q:q + 2] == b"\r\n":
+        return q + 2, False
+    return None
+
+
+def parse_multipart(body: bytes, content_type: str) -> List[Part]:
+    """multipart/form-data -> parts in order (repeated names kept). Raises ValueError for anything malformed."""
+    delim = b"--" + _boundary_of(content_type)
+    if body.startswith(delim):
+        start = 0
+    else:
+        start = body.find(b"\r\n" + delim)
+        if start < 0:
+            raise ValueError("multipart body without its boundary")
+        start += 2
+    end = _delimiter_end(body, start + len(delim))
+    if end is None:
+        raise ValueError("malformed multipart boundary line")
+    pos, last = end
+    parts: List[Part] = []
+    while not last:
+        head_end = body.find(b"\r\n\r\n", pos)
+        if head_end < 0:
+            raise ValueError("multipart part without a header block")
+        headers: Dict[str, str] = {}
+        for line in body[pos:head_end].split(b"\r\n"):
+            if not line:
+                continue
+            k, sep, v = line.decode("utf-8", "replace").partition(":")
+            if not sep:
+                raise ValueError("malformed multipart part header")
+            headers[k.strip().lower()] = v.strip()
+        disp = headers.get("content-disposition", "")
+        if not disp.lower().startswith("form-data"):
+            raise ValueError("multipart part without a form-data Content-Disposition")
+        params = {m.group(1).lower(): (m.group(2) if m.group(2) is not None else m.group(3))
+                  for m in re.finditer(r';\s*([A-Za-z*]+)=(?:"((?:[^"\\]|\\.)*)"|([^;\s]*))', disp)}
+        if "name" not in params:
+            raise ValueError("multipart part without a name")
+        data_start = head_end + 4
+        search = data_start - 2                    # (an empty part: the CRLF of the blank line is the delimiter's)
+        while True:
+            i = body.find(b"\r\n" + delim, search)
+            if i < 0:
+                raise ValueError("multipart part without a closing boundary")
+            end = _delimiter_end(body, i + 2 + len(delim))
+            if end is not None:
+                break
+            search = i + 2                         # boundary-like bytes inside the content
+        parts.append(Part(params["name"], params.get("filename"), headers.get("content-type"), body[data_start:max(data_start, i)]))
+        pos, last = end
+    return parts
+
+
+def normalize_form_list(values: Sequence[str]) -> List[str]:
+    """repeated and / or comma-separated form fields -> one list (server.py:540-548)"""
+    out: List[str] = []
+    for value in values or []:
+        if isinstance(value, str):
+            out.extend(item.strip() for item in value.split(",") if item.strip())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ rendering
+def _json_bytes(obj) -> bytes:
+    """Starlette's JSONResponse rendering (what FastAPI sends for a returned dict)"""
+    return json.dumps(obj, ensure_ascii=False, allow_nan=False, indent=None, separators=(",", ":")).encode("utf-8")
+
+
+def _stamp(t: float) -> str:
+    return f"{int(t // 3600):02}:{int((t % 3600) // 60):02}:{t % 60:06.3f}"
+
+
+def _words(seg) -> list:
+    return [{"word": w.word, "start": w.start, "end": w.end, "probability": w.probability} for w in seg.words]
+
+
+def render_subtitles(segments, response_format: str) -> str:
+    output = []
+    for i, seg in enumerate(segments, 1):
+        start, end = _stamp(seg.start), _stamp(seg.end)
+        if response_format == "srt":
+            output.append(f"{i}\n{start.replace('.', ',')} --> {end.replace('.', ',')}\n{seg.text.strip()}\n")
+        else:
+            output.append(f"{start} --> {end}\n{seg.text.strip()}\n")
+    return "\n".join(output)
+
+
+def speaker_labels_for_segments(segments, audio_np, diarizer, sample_rate: int = 16000) -> Dict[int, str]:
+    """server.py:585-598"""
+    if diarizer is None or audio_np is None:
+        return {}
+    labels = {}
+    for index, segment in enumerate(segments):
+        start = max(0, int(segment.start * sample_rate))
+        end = min(len(audio_np), int(segment.end * sample_rate))
+        if end <= start:
+            continue
+        speaker = diarizer.identify_speaker(audio_np[start:end], sample_rate)
+        if speaker:
+            labels[index] = speaker
+    return labels
+
+
+class _HttpError(Exception):
+    def __init__(self, status: int, payload: dict):
+        super().__init__(payload.get("error", ""))
+        self.status, self.payload = status, payload
+
+
+_TRUE = {"true", "1", "yes", "on", "t", "y"}
+_FALSE = {"false", "0", "no", "off", "f", "n", ""}
+
+
+# ------------------------------------------------------------------------------------------------------------ the server
+class RestServer:
+    """Threaded HTTP server of the endpoint. ``model``: what the transcriber of a GPU is built from (a size name or a model
+    directory, as the WebSocket server's faster_whisper_custom_model_path); ``model_factory(model, device_index)`` replaces the
+    construction, as in TranscriptionServer. ``start()`` returns once the socket listens (``port`` 0: see ``.port``);
+    ``shutdown()`` waits for the requests in flight and leaves no thread behind."""
+
+    def __init__(self, host: str, port: int, model: str, *, devices: Sequence[int] = (0,), api_key: Optional[str] = None,
+                 cors_origins: Optional[str] = None, rate_limit_rpm: int = 0, model_factory: Optional[Callable] = None,
+                 max_body_bytes: int = 512 << 20, diarization_model: Optional[str] = None,
+                 embedder_factory: Optional[Callable] = None):
+        self.host, self.port, self.model = host, int(port), model
+        self.devices = list(devices) if devices else [0]
+        if any(d < 0 for d in self.devices):
+            raise ValueError("devices must be non-negative GPU indices")
+        self.api_key = api_key
+        self.origins = [o.strip() for o in cors_origins.split(",")] if cors_origins else []
+        self.rate_limit_rpm = int(rate_limit_rpm)
+        self.model_factory = model_factory
+        self.max_body_bytes = int(max_body_bytes)
+        self.diarization_model = diarization_model
+        self.embedder_factory = embedder_factory
+        self._rate_lock = threading.Lock()
+        self._rate_buckets: Dict[str, collections.deque] = {}
+        self._n_requests = 0
+        self._req_lock = threading.Lock()
+        self._httpd: Optional[ThreadingHTTPServer] = None
+        self._thread: Optional[threading.Thread] = None
+
+    # ---- life cycle
+    def start(self) -> "RestServer":
+        server = self
+
+        class Handler(_Handler):
+            rest = server
+
+        self._httpd = ThreadingHTTPServer((self.host, self.port), Handler)
+        self._httpd.daemon_threads = False          # server_close() joins the request threads
+        self.port = self._httpd.server_address[1]
+        self._thread = threading.Thread(target=self._httpd.serve_forever, kwargs={"poll_interval": 0.05}, name="wlx-rest")
+        self._thread.start()
+        logging.info(f"OpenAI-compatible API started on http://{self.host}:{self.port}")
+        return self
+
+    def shutdown(self):
+        if self._httpd is not None:
+            self._httpd.shutdown()
+            self._httpd.server_close()
+            self._httpd = None
+        if self._thread is not None:
+            self._thread.join()
+            self._thread = None
+
+    def serve_forever(self):
+        self.start()
+        try:
+            while self._thread is not None and self._thread.is_alive():
+                self._thread.join(0.5)
+        except KeyboardInterrupt:
+            pass
+        finally:
+            self.shutdown()
+
+    # ---- the pieces of a request
+    def rate_limited(self, client_ip: str) -> bool:
+        if self.rate_limit_rpm <= 0:
+            return False
+        now = time.time()
+        with self._rate_lock:
+            bucket = self._rate_buckets.setdefault(client_ip, collections.deque())
+            while bucket and bucket[0] < now - 60:
+                bucket.popleft()
+            if len(bucket) >= self.rate_limit_rpm:
+                return True
+            bucket.append(now)
+        return False
+
+    def _next_device(self) -> int:
+        with self._req_lock:
+            i = self._n_requests
+            self._n_requests += 1
+        return self.devices[assign_gpu(i, len(self.devices))]
+
+    def transcriber_for(self, device_index: int):
+        """the GPU's shared transcriber: the cache (and lock) of the single_model WebSocket sessions"""
+        from .serve_client import ServeClientHIP
+        with ServeClientHIP.MODELS_LOCK:
+            if device_index not in ServeClientHIP.MODELS:
+                if self.model_factory is not None:
+                    ServeClientHIP.MODELS[device_index] = self.model_factory(self.model, device_index)
+                else:
+                    ServeClientHIP.MODELS[device_index] = ServeClientHIP.create_model(self.model, device_index)
+            return ServeClientHIP.MODELS[device_index]
+
+    def create_rest_diarizer(self, known_speaker_names, known_speaker_references, device_index: int):
+        """server.py:550-583 on this GPU's shared embedder; ValueError = a 400"""
+        speaker_names = normalize_form_list(known_speaker_names)
+        speaker_references = known_speaker_references or []
+        if speaker_references and not speaker_names:
+            raise ValueError("known_speaker_references requires matching known_speaker_names")
+        if speaker_names and speaker_references and len(speaker_names) != len(speaker_references):
+            raise ValueError("known_speaker_names and known_speaker_references must have the same length")
+        if not speaker_names and not speaker_references:
+            return None
+        from .artifacts import resolve_diarization_model
+        from .audio_io import load_audio
+        from .diarization import SpeakerDiarizer, shared_embedder
+        path = resolve_diarization_model(self.diarization_model)
+        if path is None and self.embedder_factory is None:
+            raise ValueError("known speakers requested but no speaker-embedding checkpoint is available on this server")
+        embedder = (self.embedder_factory or shared_embedder)(path, device_index)
+        diarizer = SpeakerDiarizer(max_speakers=max(10, len(speaker_names)), speaker_names=speaker_names, embedder=embedder,
+                                   device=device_index)
+        for speaker_name, reference in zip(speaker_names, speaker_references):
+            audio_np = load_audio(reference.data)
+            if not diarizer.enroll_speaker(speaker_name, audio_np):
+                raise ValueError(f"known_speaker_references for '{speaker_name}' is too short")
+        return diarizer
+
+
+class _Handler(BaseHTTPRequestHandler):
+    rest: RestServer = None           # set by RestServer.start()
+    server_version = "whisperlive-amd-rest"
+    timeout = 60                      # seconds a socket read or write may stall: a stuck client does not hold shutdown() for ever
+    DRAIN_BYTES = 16 << 20            # of an unread body, this much is read and dropped before an early answer (see _drain)
+    _body_unread = 0
+    _expects_continue = False
+
+    def _drain(self):
+        """Before an answer that did not read the body: read and drop what the client is still sending (a bounded amount), so that
+        it sees the status and not a reset connection. A client that waits for 100 Continue has sent nothing."""
+        left = 0 if self._expects_continue else min(self._body_unread, self.DRAIN_BYTES)
+        self._body_unread = 0
+        try:
+            while left > 0:
+                chunk = self.rfile.read(min(left, 1 << 16))
+                if not chunk:
+                    break
+                left -= len(chunk)
+        except OSError:                # (a timeout among them) the answer is still attempted
+            pass
+
+    def log_message(self, fmt, *args):          # the access log goes where the rest of the server logs
+        logging.debug("rest %s - %s", self.address_string(), fmt % args)
+
+    # ---- responses
+    def _send(self, status: int, body: bytes, content_type: str, extra: Optional[Dict[str, str]] = None, cors: bool = True):
+        self._drain()
+        self.send_response(status)
+        self.send_header("Content-Type", content_type)
+        self.send_header("Content-Length", str(len(body)))
+        self.send_header("Connection", "close")
+        for k, v in (self._cors_simple() if cors else {}).items():
+            self.send_header(k, v)
+        for k, v in (extra or {}).items():
+            self.send_header(k, v)
+        self.end_headers()
+        if self.command != "HEAD":
+            self.wfile.write(body)
+        self.close_connection = True
+
+    def _json(self, status: int, obj, **kw):
+        self._send(status, _json_bytes(obj), "application/json", **kw)
+
+    def _text(self, status: int, text: str, **kw):
+        self._send(status, text.encode("utf-8"), "text/plain; charset=utf-8", **kw)
+
+    # ---- CORS (Starlette's CORSMiddleware with allow_credentials, every method and every header allowed)
+    def _origin_allowed(self, origin: str) -> bool:
+        return "*" in self.rest.origins or origin in self.rest.origins
+
+    def _cors_simple(self) -> Dict[str, str]:
+        origin = self.headers.get("Origin")
+        if origin is None:
+            return {}
+        h = {"Access-Control-Allow-Credentials": "true"}
+        if "*" in self.rest.origins and "Cookie" not in self.headers:
+            h["Access-Control-Allow-Origin"] = "*"
+        elif self._origin_allowed(origin):
+            h["Access-Control-Allow-Origin"] = origin
+            h["Vary"] = "Origin"
+        return h
+
+    def _preflight(self):
+        origin = self.headers.get("Origin")
+        h = {"Access-Control-Allow-Methods": _CORS_METHODS, "Access-Control-Max-Age": "600",
+             "Access-Control-Allow-Credentials": "true", "Vary": "Origin"}
+        req_headers = self.headers.get("Access-Control-Request-Headers")
+        if req_headers is not None:
+            h["Access-Control-Allow-Headers"] = req_headers
+        if self._origin_allowed(origin):
+            h["Access-Control-Allow-Origin"] = origin
+            self._text(200, "OK", extra=h, cors=False)
+        else:
+            self._text(400, "Disallowed CORS origin", extra=h, cors=False)
+
+    # ---- the middleware chain, then routing
+    def _dispatch(self):
+        rest = self.rest
+        try:
+            self._body_unread = max(0, int(self.headers.get("Content-Length", "0")))
+        except ValueError:
+            self._body_unread = 0
+        # `Expect: 100-continue`: the go-ahead is sent by _form, after the checks that need no body — a client that waits for it gets
+        # its 401 / 413 / 429 without having sent the upload
+        self._expects_continue = (self.request_version == "HTTP/1.1" and self.headers.get("Expect", "").strip().lower() == "100-continue")
+        if rest.rate_limited(self.client_address[0] if self.client_address else "unknown"):
+            return self._json(429, {"error": "Rate limit exceeded"}, cors=False)
+        if rest.api_key and self.headers.get("Authorization", "") != f"Bearer {rest.api_key}":
+            return self._json(401, {"error": "Invalid or missing API key"}, cors=False)
+        if self.command == "OPTIONS" and "Origin" in self.headers and "Access-Control-Request-Method" in self.headers:
+            return self._preflight()
+        path = self.path.split("?", 1)[0]
+        if path != ROUTE:
+            return self._json(404, {"detail": "Not Found"})
+        if self.command != "POST":
+            return self._json(405, {"detail": "Method Not Allowed"}, extra={"Allow": "POST"})
+        try:
+            self._transcriptions()
+        except _HttpError as e:
+            wl_metrics.track_rest_request(endpoint="transcriptions", status=e.status)
+            self._json(e.status, e.payload)
+
+    do_GET = do_POST = do_PUT = do_DELETE = do_PATCH = do_HEAD = do_OPTIONS = _dispatch
+
+    # ---- POST /v1/audio/transcriptions (server.py:733-859)
+    def _form(self):
+        try:
+            length = int(self.headers.get("Content-Length", ""))
+        except ValueError:
+            raise _HttpError(400, {"error": "Content-Length is required"})
+        if length < 0:
+            raise _HttpError(400, {"error": "Content-Length is required"})
+        if length > self.rest.max_body_bytes:
+            raise _HttpError(413, {"error": f"Request body of {length} bytes exceeds the limit of {self.rest.max_body_bytes}"})
+        if self._expects_continue:
+            self.wfile.write(b"HTTP/1.1 100 Continue\r\n\r\n")
+            self.wfile.flush()
+            self._expects_continue = False
+        try:
+            body = self.rfile.read(length)
+        except TimeoutError:
+            self._body_unread = 0
+            raise _HttpError(408, {"error": "Timed out reading the request body"})
+        self._body_unread = 0
+        if len(body) != length:
+            raise _HttpError(400, {"error": "Request body shorter than its Content-Length"})
+        try:
+            return parse_multipart(body, self.headers.get("Content-Type", ""))
+        except ValueError as e:
+            raise _HttpError(400, {"error": str(e)})
+
+    def _transcriptions(self):
+        parts = self._form()
+        fields: Dict[str, List[Part]] = {}
+        for p in parts:
+            fields.setdefault(p.name, []).append(p)
+
+        def one(name, default=None):
+            return fields[name][-1].text if name in fields else default
+
+        def many(name):
+            return [p.text for p in fields.get(name, [])]
+
+        if "file" not in fields:
+            raise _HttpError(400, {"error": "Missing required form field 'file'"})
+        file = fields["file"][0]
+        model = one("model", "whisper-1")
+        language, prompt, hotwords = one("language"), one("prompt"), one("hotwords")
+        response_format = one("response_format", "json")
+        try:
+            temperature = float(one("temperature", "0.0"))
+        except ValueError:
+            raise _HttpError(400, {"error": "temperature must be a number"})
+        stream_s = (one("stream", "false") or "").strip().lower()
+        if stream_s not in _TRUE and stream_s not in _FALSE:
+            raise _HttpError(400, {"error": "stream must be a boolean"})
+        timestamp_granularities = normalize_form_list(many("timestamp_granularities") + many("timestamp_granularities[]")) or None
+        chunking_strategy = one("chunking_strategy")
+        include = many("include") + many("include[]") or None
+        known_speaker_names = many("known_speaker_names") + many("known_speaker_names[]")
+        known_speaker_references = fields.get("known_speaker_references", []) + fields.get("known_speaker_references[]", [])
+        want_words = bool(timestamp_granularities and "word" in timestamp_granularities)
+        rest = self.rest
+
+        if stream_s in _TRUE:
+            return self._stream(file, language, prompt, temperature, want_words)
+
+        ignored_params = []
+        if chunking_strategy:
+            ignored_params.append(f"chunking_strategy='{chunking_strategy}'")
+        if include:
+            ignored_params.append(f"include={include}")
+        if ignored_params:
+            logging.warning(f"Unsupported OpenAI params ignored: {', '.join(ignored_params)}")
+        if response_format not in SUPPORTED_FORMATS:
+            raise _HttpError(400, {"error": f"Unsupported response_format. Supported: {SUPPORTED_FORMATS}"})
+        if model != "whisper-1":
+            logging.warning(f"Model '{model}' requested; using '{rest.model}' as fallback.")
+        if file.data[:4] not in (b"fLaC", b"RIFF"):
+            raise _HttpError(400, {"error": "Unsupported audio: the file is neither WAV nor FLAC"})
+
+        transcriber = None
+        try:
+            device_index = rest._next_device()
+            transcriber = rest.transcriber_for(device_index)
+            segments, info = transcriber.transcribe(file.data, language=language, initial_prompt=prompt, temperature=temperature,
+                                                    vad_filter=False, word_timestamps=want_words, hotwords=hotwords)
+            segments = list(segments or [])
+            text = " ".join([s.text.strip() for s in segments])
+            if response_format == "text":
+                wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
+                return self._text(200, text)
+            if response_format == "json":
+                wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
+                return self._json(200, {"text": text})
+            if response_format == "verbose_json":
+                verbose = {"task": "transcribe", "language": info.language if info else language,
+                           "duration": info.duration if info else 0.0, "text": text, "segments": []}
+                speaker_labels = {}
+                try:
+                    rest_diarizer = rest.create_rest_diarizer(known_speaker_names, known_speaker_references, device_index)
+                except ValueError as e:
+                    raise _HttpError(400, {"error": str(e)})
+                if rest_diarizer is not None:
+                    from .audio_io import load_audio
+                    speaker_labels = speaker_labels_for_segments(segments, load_audio(file.data), rest_diarizer)
+                for index, seg in enumerate(segments):
+                    seg_dict = {"id": seg.id, "seek": seg.seek, "start": seg.start, "end": seg.end, "text": seg.text.strip(),
+                                "tokens": seg.tokens, "temperature": seg.temperature, "avg_logprob": seg.avg_logprob,
+                                "compression_ratio": seg.compression_ratio, "no_speech_prob": seg.no_speech_prob}
+                    if index in speaker_labels:
+                        seg_dict["speaker"] = speaker_labels[index]
+                    if want_words:
+                        seg_dict["words"] = _words(seg)
+                    verbose["segments"].append(seg_dict)
+                wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
+                return self._json(200, verbose)
+            wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
+            return self._text(200, render_subtitles(segments, response_format))
+        except _HttpError:
+            raise
+        except Exception as e:  # noqa: BLE001 — server.py:853-856
+            wl_metrics.track_rest_request(endpoint="transcriptions", status=500)
+            wl_metrics.track_error("rest_transcription")
+            self._release(transcriber)          # before the answer: the client may act on it at once
+            transcriber = None
+            return self._json(500, {"error": str(e)})
+        finally:
+            self._release(transcriber)
+
+    @staticmethod
+    def _release(transcriber):
+        """the request thread ends here: its slot goes back to the transcriber's pool"""
+        release = getattr(transcriber, "release_slot", None)
+        if release is not None:
+            try:
+                release()
+            except Exception:  # noqa: BLE001
+                logging.exception("rest: release_slot failed")
+
+    def _stream(self, file, language, prompt, temperature, want_words):
+        """server.py:490-537: one `data:` event per segment, `[DONE]` at the end, an error as an event of its own"""
+        self.send_response(200)
+        self.send_header("Content-Type", "text/event-stream; charset=utf-8")
+        self.send_header("Cache-Control", "no-cache")
+        self.send_header("Connection", "close")
+        for k, v in self._cors_simple().items():
+            self.send_header(k, v)
+        self.end_headers()
+        self.close_connection = True
+
+        def emit(s: str):
+            self.wfile.write(s.encode("utf-8"))
+            self.wfile.flush()
+
+        transcriber = None
+        try:
+            try:
+                transcriber = self.rest.transcriber_for(self.rest._next_device())
+                segments, _info = transcriber.transcribe(file.data, language=language, initial_prompt=prompt, temperature=temperature,
+                                                         vad_filter=False, word_timestamps=want_words)
+                for seg in segments or []:
+                    seg_dict = {"id": seg.id, "start": seg.start, "end": seg.end, "text": seg.text.strip()}
+                    if want_words:
+                        seg_dict["words"] = _words(seg)
+                    emit(f"data: {json.dumps(seg_dict)}\n\n")
+                emit("data: [DONE]\n\n")
+            except (BrokenPipeError, ConnectionResetError):
+                raise
+            except Exception as e:  # noqa: BLE001
+                emit(f"data: {json.dumps({'error': str(e)})}\n\n")
+        except (BrokenPipeError, ConnectionResetError):
+            logging.debug("rest: the client went away mid-stream")
+        finally:
+            self._release(transcriber)
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description="OpenAI-style transcription endpoint on the MI355X engine")
+    ap.add_argument("--host", default="0.0.0.0")
+    ap.add_argument("--port", "-p", type=int, default=8000)
+    ap.add_argument("--model_path", "-m", default="small", help="model size name or model directory")
+    ap.add_argument("--devices", default="0", help="comma-separated GPU indices to rotate requests over")
+    ap.add_argument("--api_key", default=None)
+    ap.add_argument("--cors_origins", default=None, help="comma-separated allowed origins")
+    ap.add_argument("--rate_limit_rpm", type=int, default=0, help="requests per minute per client IP (0 = unlimited)")
+    ap.add_argument("--max_body_mb", type=int, default=512)
+    ap.add_argument("--diarization_model", default=None)
+    ap.add_argument("--metrics_port", type=int, default=0)
+    a = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    if a.metrics_port > 0:
+        wl_metrics.start_metrics_server(a.metrics_port)
+    RestServer(a.host, a.port, a.model_path, devices=[int(x) for x in a.devices.split(",") if x != ""], api_key=a.api_key,
+               cors_origins=a.cors_origins, rate_limit_rpm=a.rate_limit_rpm, max_body_bytes=a.max_body_mb << 20,
+               diarization_model=a.diarization_model).serve_forever()
+
+
+if __name__ == "__main__":
+    main()

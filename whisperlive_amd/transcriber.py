@@ -31,7 +31,7 @@ import numpy as np
 
 from . import vad as _vad
 from . import word_timing as _wt
-from ._lib import WlxError as _WlxError
+from ._lib import ERR_ARG as _ERR_ARG, WlxError as _WlxError
 from .engine import GenerationResult, HipWhisperEngine, Slot, TokenIds
 from .specs import WhisperSpec, get_spec, spec_from_state_dict
 from .tokenizer import LANGUAGE_CODES, Tokenizer
@@ -498,6 +498,7 @@ class WhisperModelHIP:
                                 "setting to False instead.")
             multilingual = False
         resident = None
+        file_slot = None                 # the slot whose PCM buffer already holds this call's audio (file input)
         if isinstance(audio, ResidentAudio):
             resident, audio = audio, audio.host
         if not isinstance(audio, np.ndarray):
@@ -505,8 +506,32 @@ class WhisperModelHIP:
             # (whisperlive_amd/audio_io.py), anything else must arrive as 16 kHz float32 PCM
             if not isinstance(audio, (str, bytes, bytearray)) and not hasattr(audio, "read"):
                 raise TypeError("audio must be a float32 numpy waveform at 16 kHz, or a WAV / FLAC path, bytes or file object")
-            from .audio_io import load_audio
-            audio = load_audio(audio, sampling_rate=sr)
+            # The decoded frames go to the device in the file's own format: the slot's front end converts, down-mixes and resamples
+            # them into its PCM buffer (Slot.put_frames), the log-mel kernel reads them there, and the host takes the 16 kHz mono copy
+            # back for the duration, the VAD filter and speaker labels. A rate or channel count the device resampler does not serve
+            # keeps the host route (audio_io.load_audio's arithmetic).
+            from .audio_io import frames_to_mono, read_audio
+            from .engine import resample_supported
+            file_frames, file_sr = read_audio(audio)
+            temps_f = temperature if isinstance(temperature, (list, tuple)) else [temperature]
+            file_slot = self._slot(rows=max(int(beam_size), int(best_of) if any(t > 0 for t in temps_f) else 1))
+            # (an engine injected through `engine=` whose slots take 16 kHz PCM only — the host-logic test doubles — has no front end)
+            on_device = (sr == 16000 and file_frames.shape[0] > 0 and resample_supported(file_sr, file_frames.shape[1])
+                         and hasattr(file_slot, "put_frames"))
+            if on_device:
+                try:
+                    with file_slot.lock:
+                        file_slot.put_frames(file_frames, file_sr)
+                        audio = file_slot.pcm()
+                except _WlxError as e:
+                    if e.code != _ERR_ARG:             # only a REFUSED shape (nothing was launched) keeps the host route
+                        raise
+                    self.logger.debug("device front end refused the file: %s", e)
+                    on_device = False
+            if not on_device:
+                self.logger.debug("file audio at %d Hz x %d channels: resampled on the host", file_sr, file_frames.shape[1])
+                file_slot = None
+                audio = frames_to_mono(file_frames, file_sr, sr)
         audio = np.ascontiguousarray(audio, dtype=np.float32)
         duration = audio.shape[0] / sr
         duration_after_vad = duration
@@ -519,6 +544,7 @@ class WhisperModelHIP:
             elif isinstance(vad_parameters, dict):
                 vad_parameters = VadOptions(**vad_parameters)
             vad_model = self._vad_model()
+            file_slot = None             # the filter trims the audio: the trimmed host samples are uploaded as before
             if ranges is not None and hasattr(vad_model, "probs_resident") and getattr(vad_model, "device", None) == getattr(resident.ring, "device", -1):
                 try:
                     speech_chunks = _vad.get_speech_timestamps_resident(resident.ring, resident.start, resident.n, vad_parameters, model=vad_model)
@@ -555,6 +581,8 @@ class WhisperModelHIP:
                     if speech_chunks is not None:
                         chunks, _meta = _vad.collect_chunks(audio, speech_chunks)
                         audio = np.concatenate(chunks, axis=0)
+            if n_frames is None and file_slot is slot:
+                n_frames = slot.logmel_resident()              # the file's PCM is resident already (put_frames): no second upload
             if n_frames is None:
                 n_frames = slot.logmel(audio)                  # PCM -> HBM -> log-mel, stays on the device
             features = DeviceFeatures(slot, n_frames)
