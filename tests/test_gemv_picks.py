@@ -155,7 +155,7 @@ def test_sweep_equals_the_recorded_answers(sweep):
 
 
 def test_sweep_lean_answer_and_kernel_name_agree(sweep):
-    """what engine.hip decoder_pass asks before it builds a pass (lean?) and what the profiling hook filters by (the name) are one answer"""
+    """what engine_decode.hip decoder_pass asks before it builds a pass (lean?) and what the profiling hook filters by (the name) are one answer"""
     ms, got = sweep
     n_lean = 0
     for key, answers in got.items():

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the results of a generate are read from pinned host memory the moment the host sees the done word, while the decode step it had
-already enqueued behind the finish is still running (round 6, engine.hip generate / search.hip finish_item). What must hold: a call's results are
+already enqueued behind the finish is still running (round 6, engine_decode.hip generate_impl / search.hip finish_item). What must hold: a call's results are
 complete and its own when it returns — whatever the previous call left in flight on the slot's stream, and however the decode ended (an
 end-of-text in the first step, an end-of-text later, max_length) — for one item and for a batch whose items finish at different steps."""
 import numpy as np
@@ -94,7 +94,7 @@ def test_batch_whose_items_finish_at_different_steps(tiny):
 
 
 def test_two_steps_per_graph_equal_one_step_per_graph(tiny):
-    """One live slot on the device decodes two steps per graph launch, two or more live slots one step per launch (engine.hip graph_steps_for): the
+    """One live slot on the device decodes two steps per graph launch, two or more live slots one step per launch (engine_decode.hip graph_steps_for): the
     same calls give the same tokens, scores and step counts either way — end of text in an even step, in an odd step, odd and even step budgets
     (an odd budget ends on a one-step graph), and back to back without a pause."""
     spec, eng, pcm_of = tiny

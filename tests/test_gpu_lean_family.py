@@ -250,7 +250,7 @@ def test_twentyfour_items_batched_equal_singles_and_120_rows(fam):
 def test_thirtytwo_items_with_short_prompts_prefill_in_blocks(fam):
     """batch_inference batches of multilingual requests, wider than the prefill working set: every item carries `[sot, lang, task]`
     (+ a prefix); 32 items x 16 prompt rows pass the 448-row prefill buffers, so the joint prefill runs in two blocks of 28 + 4 items
-    (engine.hip generate_impl, round 5). Every item must equal its single decode — tokens, score, and no_speech_prob, which is read from the
+    (engine_decode.hip gen_prefill, round 5). Every item must equal its single decode — tokens, score, and no_speech_prob, which is read from the
     prefill logits at the item's <|startoftranscript|> row — also across the block boundary. Then detect_language on the 32-item batch
     (one decoder pass of 32 rows, R = 1) against per-item calls."""
     name, spec, eng, oracle, slot, enc = fam
@@ -295,7 +295,7 @@ def test_thirtytwo_items_with_short_prompts_prefill_in_blocks(fam):
 
 def test_busy_device_launch_shapes_give_identical_results(fam):
     """With three or more live slots on the device the engine captures a second step graph per slot whose row-tiled residual projections
-    take two 16-column tiles per workgroup (work-saving shapes for a work-bound GPU: engine.hip device_is_busy, decoder.hip gemv2_cfg). The
+    take two 16-column tiles per workgroup (work-saving shapes for a work-bound GPU: engine_decode.hip device_is_busy, decoder.hip gemv2_cfg). The
     tile grouping does not touch any summation order: an 8-item batched beam-5 decode must give the SAME tokens and bit-identical scores
     with and without the extra live slots."""
     name, spec, eng, oracle, slot, enc = fam
@@ -325,3 +325,20 @@ def test_busy_device_launch_shapes_give_identical_results(fam):
     # restore the fixture's encoder state (item 0 of the shared slot)
     pcm = olm.speech_like_pcm(5.0, seed=21)
     T = slot.logmel(pcm); slot.encode(1, seek=[0], seg=[T - 1])
+
+
+def test_decode_step_launch_tables_equal_the_recorded_ones(fam):
+    """The launches of one decode step — which kernels, how many of each, the bytes each has to stream — are decided on the host
+    (engine_decode.hip decoder_pass). Per model, at the smallest row counts that reach each of its branches (tests/golden/make_decode_goldens.py
+    STEP_ROWS), the table wlx_debug_profile_step lists equals the one recorded before the host code was reorganised: exact equality,
+    the table is the library's own earlier answer."""
+    import json
+    import os
+    from tests.golden import make_decode_goldens as mk
+    name, spec, eng, oracle, slot, enc = fam
+    with open(os.path.join(os.path.dirname(os.path.abspath(mk.__file__)), "decode_step_launches.json")) as f:
+        want = json.load(f)[name]
+    got = mk.step_launch_tables(eng, olm.speech_like_pcm(5.0, seed=21))
+    assert sorted(got) == sorted(want) == sorted(str(r) for r in mk.STEP_ROWS)
+    for rows in got:
+        assert got[rows] == want[rows], (name, rows, {k: (got[rows].get(k), want[rows].get(k)) for k in set(got[rows]) | set(want[rows]) if got[rows].get(k) != want[rows].get(k)})

@@ -198,3 +198,20 @@ def test_twelve_utterances_in_one_worker_batch_are_one_60_row_decode(gpu, widene
     finally:
         model.close()
         model.engine.close()
+
+
+@pytest.mark.gpu
+def test_generate_routes_equal_the_recorded_results_bit_for_bit(gpu):
+    """One `generate` call per prompt-prefill route of wlx_generate (engine_decode.hip: no prefill, one-pass, chunked, joint over a batch,
+    per item inside a batch) and one sampling call, on the trained checkpoint and on a seeded d_model-512 model whose shapes select the
+    one-pass and joint routes (tests/golden/make_decode_goldens.py route_calls): tokens, float32 score bits and no_speech_prob bits equal
+    what the library returned before its host code was reorganised. Same launches, so no tolerance."""
+    from tests.golden import make_decode_goldens as mk
+    with open(os.path.join(os.path.dirname(DIR), "generate_routes.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(mk.ROUTE_MODELS)
+    for model in mk.ROUTE_MODELS:
+        got = mk.run_routes(model)
+        assert [r["route"] for r in got] == [r["route"] for r in want[model]]
+        for g, w in zip(got, want[model]):
+            assert g == w, (model, g["route"], g, w)

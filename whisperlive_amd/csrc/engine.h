@@ -1,9 +1,11 @@
 // engine.h — host-side state of libwlx: weights in kernel layout, per-slot device buffers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 #include "../../include/wlx.h"
 #include "decoder.h"
@@ -11,13 +13,22 @@
 
 namespace wlx {
 
+// what a captured decode-step graph depends on (engine_decode.hip get_step_graph)
 struct StepGraphKey {
-    int rows, R, groups;
+    int rows, R, groups, nsteps;
+    bool busy, sampling;
     bool operator<(const StepGraphKey& o) const {
-        if (rows != o.rows) return rows < o.rows;
-        if (R != o.R) return R < o.R;
-        return groups < o.groups;
+        return std::tie(rows, R, groups, nsteps, busy, sampling) < std::tie(o.rows, o.R, o.groups, o.nsteps, o.busy, o.sampling);
     }
+};
+
+// the decoder pass's working set (scratch rows + row tables); a slot holds two (Slot::step, Slot::pf; engine.hip alloc_decbufs)
+struct DecBufs {
+    float* xd; half_t *qd, *attnd, *hd;
+    float* slab; int slab_rows;                      // [WLX_FC2_KS][slab_rows][d] partial sums of the K-split MLP output projection (decoder.hip GEMV_OUT_SLAB)
+    half_t* part_o; float* part_ml;
+    int *d_token, *d_pos, *d_cache, *d_ancrow, *d_group_item;
+    bool prefill;                                    // the prompt-prefill set: decoder_pass picks its launch forms by it
 };
 
 // decode-step profiler (wlx_debug_profile_step): pass 1 only lists the launches of a step (name, algorithmic bytes);
@@ -26,7 +37,7 @@ struct ProfRec { std::string name; double bytes; };
 struct Prof { std::vector<ProfRec> recs; bool list_only = true; std::string only; int t = 0; };
 
 struct Slot {
-    std::mutex call_mu;      // held by the entry point currently using the slot (engine.hip: slot_acquire)
+    std::mutex call_mu;      // held by the entry point currently using the slot (engine.hip slot_acquire)
     int B = 0, R = 0, rows_cap = 0, cache_rows = 0, groups_cap = 0;
     hipStream_t stream = nullptr;
     bool dedicated_queue = false;       // the stream owns a hardware queue (engine.hip create_slot_stream); counted per device
@@ -40,7 +51,7 @@ struct Slot {
     bool lm_pending = false;
     bool gen_pending = false;                  // the last generate's device time / step count: read in wlx_timings_get, not in wlx_generate
     std::vector<int> lm_items;          // items whose log-mel was requested and not launched yet (engine.hip flush_logmel)
-    bool busy_variant = false;          // the decode launches of this slot use the work-saving shapes (three or more live slots on the device; engine.hip device_is_busy)
+    bool busy_variant = false;          // the decode launches of this slot use the work-saving shapes (three or more live slots on the device; engine_decode.hip device_is_busy)
     std::vector<void*> allocs, host_allocs;   // device / pinned buffers of the slot's whole life (slot_free)
     // features
     float* pcm = nullptr; size_t pcm_cap = 0;       // [B][pcm_cap]
@@ -60,20 +71,11 @@ struct Slot {
     int enc_batch = 0;
     // decoder
     half_t *kc = nullptr, *vc = nullptr;             // self cache [L][cache_rows][448][d]
-    float* xd = nullptr; half_t *qd = nullptr, *attnd = nullptr, *hd = nullptr;
-    float* slab = nullptr;                           // [WLX_FC2_KS][48][d] partial sums of the K-split MLP output projection (decoder.hip GEMV_OUT_SLAB)
-    half_t* part_o = nullptr;
-    float *part_ml = nullptr, *logits = nullptr;
+    float* logits = nullptr;
     long ldl = 0;
-    int *d_token = nullptr, *d_pos = nullptr, *d_cache = nullptr, *d_ancrow = nullptr, *d_group_item = nullptr;
-    // the decoder pass's working set (scratch rows + row tables): `step` = the decode steps and chunked passes (rows_cap = 64
-    // rows, the members above), `pf` = the one-pass prompt prefill (up to 448 rows: engine.hip prefill_tokens)
-    struct DecBufs {
-        float* xd; half_t *qd, *attnd, *hd; float* slab; int slab_rows; half_t* part_o; float* part_ml;
-        int *d_token, *d_pos, *d_cache, *d_ancrow, *d_group_item;
-    };
-    DecBufs pf{};
-    bool pf_one_pass = false;           // set around the one-pass prompt prefill's decoder pass (engine.hip prefill_tokens): no K-split MLP projection there
+    // the decoder pass's working sets: `step` = the decode steps and chunked passes (rows_cap rows), `pf` = the one-pass and the joint
+    // prompt prefill (up to WLX_T_TEXT rows: engine_decode.hip prefill_tokens, gen_prefill)
+    DecBufs step{}, pf{};
     bool pf_ok = false;                 // every projection of this model runs on the lean kernel in row chunks (decided at creation)
     short* d_anc = nullptr; int* d_intok = nullptr;
     bool anc_ident = false;                          // the uploaded row tables have ancrow[r] == r (decode steps; upload_rows)
@@ -83,9 +85,9 @@ struct Slot {
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging
     int* h_stage = nullptr; size_t h_stage_ints = 0;
-    // pinned staging of wlx_generate: set-up tables in (one async copy each, no synchronisation) and results out
-    unsigned char* h_gen = nullptr; size_t h_gen_bytes = 0;
-    int* h_pf = nullptr; bool h_pf_used = false;   // pinned staging of the one-pass prompt prefill's row tables (its own: no wait for the stream before the first prefill of a call)
+    // pinned staging of wlx_generate: set-up tables in (one async copy each, no synchronisation); the results come back through h_hyp
+    unsigned char* h_gen = nullptr; size_t h_gen_bytes = 0;      // laid out by gen_staging
+    int* h_pf = nullptr; bool h_pf_used = false;   // pinned staging of the one-pass prompt prefill's row tables (its own: no wait for the stream before the first prefill of a call; engine_decode.hip prefill_tokens)
     int* h_hyp = nullptr;                      // pinned result area the update kernels write: [n_hyp B | hyp_len B*H | hyp_score B*H | no_speech B | hyp_tokens B*H*448]
     int max_items = 0;                         // B of that layout
     std::vector<int> last_suppress; bool suppress_valid = false;   // the suppress mask on the device was built from this list
@@ -136,3 +138,41 @@ struct Engine {
 
 struct wlx_engine : public wlx::Engine {};
 struct wlx_ring : public wlx::Ring {};
+
+// ------------------------------------------------------------------------------------------------
+// shared between engine.hip (slots, streams), engine_decode.hip (decode) and engine_debug.hip (hooks)
+namespace wlx {
+
+// Every entry point holds the slot's call mutex for its duration: a slot is one unit of concurrency (one stream, one set
+// of scratch buffers), so a second call on it is refused rather than corrupting the first, and wlx_slot_destroy waits for
+// a call in flight instead of freeing buffers under it.
+struct SlotGuard {
+    Slot* s = nullptr;
+    ~SlotGuard() { if (s) s->call_mu.unlock(); }
+};
+int slot_acquire(wlx_engine* e, int slot, SlotGuard& g);                                  // engine.hip
+int create_slot_stream(int device, hipStream_t* out, bool* dedicated_out);
+extern std::atomic<int> g_dedicated_live[64];      // live slots with a hardware queue of their own, per device (create_slot_stream)
+extern std::atomic<int> g_slots_live[64];          // live slots per device
+
+// wlx_generate's pinned set-up staging (Slot::h_gen): [SearchParams | cum | rule | nsp | plen | ancestry rows | decode row tables].
+// One layout for the allocation (wlx_slot_create: base = nullptr, only `bytes` is read) and the call (generate_impl).
+struct GenStaging {
+    SearchParams* sp; float* cum; int* rule; int* nsp; int* plen; short* anc; int* rows;
+    size_t bytes;
+};
+GenStaging gen_staging(unsigned char* base, int rows_cap, int B);                         // engine_decode.hip
+
+bool device_is_busy(const Slot* s);
+void decoder_pass(Engine* e, Slot* s, const DecBufs& b, int rows, int R, int groups, bool with_logits, bool check_done, bool one_pass_prefill = false);
+int upload_rows(Slot* s, const std::vector<int>& token, const std::vector<int>& pos, const std::vector<int>& cache,
+                const std::vector<int>& ancrow, const std::vector<int>& group_item);
+int prefill_tokens(Engine* e, Slot* s, int item, int crow, const int* tokens, int pos0, int n, float* logits_host, int nsp_index, int nsp_token,
+                   float* nsp_out);
+int set_anc_rows(Slot* s, const std::vector<short>& anc_host, int first_row, int nrows);
+void launch_search(Engine* e, Slot* s, int rows, int R, int groups, bool sampling);
+int generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, const int32_t* plens, int pstride, const int32_t* enc_items,
+                  const wlx_gen_opts* o, bool injected_logits, const float* inj, int inj_steps, int32_t* tokens_out, int tstride,
+                  int32_t* n_tokens_out, float* scores_out, float* nsp_out);
+
+}  // namespace wlx
