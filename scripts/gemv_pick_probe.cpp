@@ -1,6 +1,6 @@
-// Which dec_gemv2_kernel instantiation the launcher picks per projection (host only, no GPU): the rules of decoder.hip gemv2_cfg made visible.
-//   hipcc -std=c++17 -O1 -DWLX_AB scripts/gemv_pick_probe.cpp -o /tmp/gemv_pick_probe -Lwhisperlive_amd -l:libwlx_ab.so -Wl,-rpath,$PWD/whisperlive_amd
-//   WLX_G2_CHMAX=6 /tmp/gemv_pick_probe   (libwlx_ab.so reads the A/B switches; build it with scripts/build_all.sh libwlx_ab.so:WLX_AB)
+// Which dec_gemv2_kernel instantiation the launcher picks per projection (host only, no GPU): the rules of dec_gemv.hip gemv2_cfg made visible.
+//   hipcc -std=c++17 -O1 scripts/gemv_pick_probe.cpp -o /tmp/gemv_pick_probe -Lwhisperlive_amd -l:libwlx.so -Wl,-rpath,$PWD/whisperlive_amd
+//   /tmp/gemv_pick_probe                  (WLX_DECODE_V1=1 in front: the answers with the first-generation kernels selected)
 // --sweep: the whole decision space instead of the listed projections (tests/test_gemv_picks.py compares it with tests/golden/gemv_pick_sweep.txt.gz).
 // First line "M <every row count>", then one line per (in, out, xsrc, K, N, bias, busy_device, slab, KTS) series:
 //   in out xsrc K N b<bias?> u<busy> s<slab?> k<KTS>|<M first>-<M last>:<slab_split>,<lean>,<kernel name>|...      (run-length over M)

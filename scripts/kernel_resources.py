@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """VGPR / SGPR / scratch / LDS of every kernel of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
-usage: kernel_resources.py whisperlive_amd/csrc/decoder.hip [substring]"""
+usage: kernel_resources.py whisperlive_amd/csrc/dec_gemv.hip [substring]"""
 import re, subprocess, sys, tempfile, os
 src = sys.argv[1]; pat = sys.argv[2] if len(sys.argv) > 2 else ""
 with tempfile.TemporaryDirectory() as d:

@@ -1,6 +1,6 @@
 """One decode step at `rows` decoder rows: captured-graph time and the per-kernel table (wlx_debug_profile_step).
-usage: [WLX_ROWTILE=0 ...] python scripts/step_profile.py MODEL ROWS [T] [--json out.json]
-Env A/B switches are read by libwlx at first use, so one process = one configuration."""
+usage: [WLX_LIB=path] python scripts/step_profile.py MODEL ROWS [T] [--json out.json]
+WLX_* variables are read by libwlx at first use, so one process = one configuration."""
 import json
 import os
 import sys

@@ -1,7 +1,9 @@
-// chain2.hip — the REAL decode kernels (decoder.hip is compiled into this binary) in synthetic dependent chains:
+// chain2.hip — the REAL decode kernels (decoder.hip, dec_gemv.hip and dec_vocab.hip are compiled into this binary) in synthetic dependent chains:
 // per-launch cost of each kernel type alone vs in the order a decoder layer runs them. Weight regions advance per
 // launch through a 640 MB pool so nothing is cache-resident. build: see scripts/ubench/run.sh
 #include "../../whisperlive_amd/csrc/decoder.hip"
+#include "../../whisperlive_amd/csrc/dec_gemv.hip"
+#include "../../whisperlive_amd/csrc/dec_vocab.hip"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

@@ -1,9 +1,9 @@
 """Host-only (-m "not gpu"): which `dec_gemv2_kernel` / `dec_vocab_kernel` instantiation the launcher picks for every decode projection
-of the Whisper family — the rules of `csrc/decoder.hip gemv2_cfg` as round 6 left them (DESIGN.md §7.3 logs G5, G7-G10), pinned so that
+of the Whisper family — the rules of `csrc/dec_gemv.hip gemv2_cfg` as round 6 left them (DESIGN.md §7.3 logs G5, G7-G10), pinned so that
 a change of the search loop shows up here before it shows up as a slower step or, as it did once that round, as a launch past its bound.
 
 `scripts/gemv_pick_probe.cpp` is compiled for the HOST (hipcc, no device code) and linked against the production `libwlx.so`.
-`wlx::dec_gemv_kernel_name` is the name leaf of `decoder.hip gemv2_dispatch` / `vocab2_dispatch`, the one walk that the eligibility
+`wlx::dec_gemv_kernel_name` is the name leaf of `dec_gemv.hip gemv2_dispatch` / `dec_vocab.hip vocab2_dispatch`, the one walk per family that the eligibility
 probe (`dec_gemv_is_lean`, `dec_gemv_slab_split`) and the launch go through as well: it prints the template arguments
 <CH, LNV, IN, OUT, NTB, MT, XS> of the instantiation that runs. CH = k-tiles per wave (so K / 32 / CH waves stream the weights),
 IN 0 = LayerNorm-fronted, 1 = fp16 rows in, 2 = split combine. No kernel is launched and no GPU is needed.

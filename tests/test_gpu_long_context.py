@@ -381,7 +381,7 @@ def test_three_items_with_different_prompts_batched_equal_singles(peaked):
 def test_batched_items_with_short_prompts_share_one_prefill_pass(peaked, monkeypatch):
     """batch_inference's batches of multilingual requests: every item carries `[sot, lang, task]` (+ a prefix / previous text), a
     few rows each. Their prompt rows run in ONE decoder pass (item b = row group b) instead of one pass per item; the result must
-    equal the per-item form (WLX_PREFILL_JOINT=0 is read at library load, so the reference here is each item decoded alone) —
+    equal the per-item form (the joint pass is not switchable, so the reference here is each item decoded alone) —
     tokens, scores, and no_speech_prob, which is read from the prefill logits at each item's <|startoftranscript|> row."""
     spec, eng, oracle, slot, enc, _ = peaked
     ids = H.token_ids_for(spec.vocab)

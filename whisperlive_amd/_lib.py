@@ -15,7 +15,7 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "search.hip", "host.hip", "engine.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
@@ -201,15 +201,15 @@ def build_trace() -> Path:
 
 def build_ab() -> Path:
     """libwlx_ab.so: the same sources with -DWLX_AB — the A/B switches that survive in the source (csrc/common.h wlx_ab: WLX_GEMM3,
-    WLX_ROWTILE, WLX_RT_F16_NTB2, WLX_NO_FUSED_CQ, WLX_PREFILL_JOINT, WLX_DECODE_V1) read the
-    environment in THIS library only; the production libwlx.so compiles them out. Select with WLX_LIB=<path>."""
+    WLX_GEMM2_SHAPE, WLX_DECODE_V1) read the environment in THIS library only; the production libwlx.so compiles them out.
+    Select with WLX_LIB=<path>."""
     out = PKG_DIR / "libwlx_ab.so"
     return out if _fresh(out) else _compile(out, ["WLX_AB"])
 
 
 def build_variant(name: str, defines) -> Path:
-    """A/B builds of the same sources with extra -D flags (e.g. libwlx_wfirst.so: -DWLX_X_FIRST=0, the decode GEMVs with
-    their weight stream requested BEFORE the activations, the round-1 order); selected at run time with WLX_LIB=<path>."""
+    """Builds of the same sources with extra -D flags (e.g. libwlx_ks4.so: -DWLX_FC2_KS=4, the MLP output projection cut into
+    four K slices; -DWLX_RESID_BATCHED=0, the encoder's tile-by-tile residual update); selected at run time with WLX_LIB=<path>."""
     out = PKG_DIR / name
     return out if _fresh(out) else _compile(out, list(defines))
 

@@ -12,7 +12,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // A/B switches (host side). The production library reads NO experiment switches from the environment: wlx_ab() is a constant there and
 // every alternative behind it is dead code the optimiser drops. `-DWLX_AB` (whisperlive_amd/_lib.py build_variant("ab", ["WLX_AB"]) ->
-// libwlx_ab.so, loaded with WLX_LIB) builds the library in which the surviving switches read the environment, for
+// libwlx_ab.so, loaded with WLX_LIB) builds the library in which the surviving switches (WLX_GEMM3, WLX_GEMM2_SHAPE, WLX_DECODE_V1: DESIGN.md §8) read the environment, for
 // re-measuring an alternative from the same source. Runtime CONFIGURATION (WLX_SLOT_CU_MASK, WLX_DEDICATED_QUEUES, WLX_NO_GRAPH,
 // WLX_QUIET, WLX_GEN_TRACE) and the two test hooks of the prompt prefill stay ordinary getenv() reads in engine_decode.hip.
 #include <cstdlib>

@@ -1,4 +1,4 @@
-// decoder.h — launchers for the autoregressive-decoder kernels (decoder.hip, search.hip).
+// decoder.h — launchers for the autoregressive-decoder kernels (decoder.hip, dec_gemv.hip, dec_vocab.hip, search.hip).
 #pragma once
 #include "kernels.h"
 
@@ -35,18 +35,6 @@ enum GemvOut : int { GEMV_OUT_F16 = 0, GEMV_OUT_GELU_F16 = 1, GEMV_OUT_F32 = 2, 
 //          (nobody materialises the sum until the next residual update writes it back);
 //   EMBED  token embedding + position (layer 0: the separate embedding launch folded into the first projection's prologue).
 enum GemvXsrc : int { GEMV_X_PLAIN = 0, GEMV_X_SLABS = 1, GEMV_X_EMBED = 2 };
-#ifndef WLX_CQ_GB_LDS
-#define WLX_CQ_GB_LDS 1       // dec_cq_cross_attn_kernel: LayerNorm gamma / beta requested once per workgroup and shared through LDS (0 = once per wave: A/B)
-#endif
-#ifndef WLX_CQ_SWAP
-#define WLX_CQ_SWAP 1         // dec_cq_cross_attn_kernel: softmax max / sum over the four lane rows by v_permlane swaps (0 = ds_bpermute: A/B)
-#endif
-#ifndef WLX_STAGE_WAVE
-#define WLX_STAGE_WAVE 1      // dec_gemv2_kernel, fp16 rows in: every wave stages its own K slice of the rows, no workgroup barrier before the MFMAs (0 = cooperative copy + barrier: A/B)
-#endif
-#ifndef WLX_XCOMB_WAVE
-#define WLX_XCOMB_WAVE 1      // dec_gemv2_kernel, cross-attention output projection: every wave combines the split partials of its own K slice, no helper waves, no barrier (0 = cooperative combine: A/B)
-#endif
 #ifndef WLX_FC2_KS
 #define WLX_FC2_KS 2          // K slices of the lean MLP output projection (compile time: the consumers unroll over the slabs)
 #endif
@@ -102,7 +90,7 @@ static inline WlxTrace trace_next(const char* name) {
 #else
 #define WLX_TR_ARG(name)
 #endif
-// The three functions below answer from ONE walk per kernel family (decoder.hip gemv2_dispatch, vocab2_dispatch) from the parameters to
+// The three functions below answer from ONE walk per kernel family (dec_gemv.hip gemv2_dispatch, dec_vocab.hip vocab2_dispatch) from the parameters to
 // the template arguments of the instantiation: the launch, the probe and the name are its leaves, so they cannot disagree. Once the
 // probe has said yes, launch_dec_gemv cannot reach the first-generation kernel (scripts/gemv_pick_probe.cpp --sweep prints all three).
 void launch_dec_gemv(const GemvParams& p, hipStream_t s);
@@ -113,8 +101,7 @@ const char* dec_gemv_kernel_name(const GemvParams& p);
 extern bool g_decode_v1;
 // true when launch_dec_gemv runs these parameters on a lean kernel (the only ones that know xsrc / GEMV_OUT_SLAB)
 bool dec_gemv_is_lean(const GemvParams& p);
-// K slices the lean kernel would cut an M x K -> N residual projection into (0: keep the single RESID launch).
-// WLX_FC2_KS=0 in the environment turns the split off (A/B).
+// K slices the lean kernel would cut an M x K -> N residual projection into (0: keep the single RESID launch; a build with -DWLX_FC2_KS=1 never splits).
 int dec_gemv_slab_split(int M, int K, int N);
 
 // causal self-attention over the KV cache, one wave per (row, head)
@@ -134,7 +121,7 @@ bool dec_cq_cross_attn_eligible(int d, int H, int R);
 void launch_dec_cq_cross_attn(const float* X, long ldx, const float* gamma, const float* beta, const half_t* Wp, const float* bias,
                               float qscale, int d, const half_t* Kp, const half_t* Vp, long item_stride, int H, int R, int groups,
                               int rows, const int* group_item, half_t* part_o, float* part_ml, hipStream_t s);
-// combine of the cross attention's split partials into fp16 rows out[M][H*64] (batched rows: see decoder.hip)
+// combine of the cross attention's split partials into fp16 rows out[M][H*64] (batched rows: see decoder.hip dec_xattn_combine_kernel)
 void launch_dec_xattn_combine(const half_t* part_o, const float* part_ml, int M, int H, int R, half_t* out, long ldo, hipStream_t s);
 // raw cross-attention scores of head h (tile-packed K of one layer AND item) for `rows` query rows -> out[rows][1536] fp32
 void launch_dec_align_scores(const half_t* q, long ldq, const half_t* Kp_item, int h, int rows, float* out, hipStream_t s);

@@ -25,7 +25,7 @@ struct StepGraphKey {
 // the decoder pass's working set (scratch rows + row tables); a slot holds two (Slot::step, Slot::pf; engine.hip alloc_decbufs)
 struct DecBufs {
     float* xd; half_t *qd, *attnd, *hd;
-    float* slab; int slab_rows;                      // [WLX_FC2_KS][slab_rows][d] partial sums of the K-split MLP output projection (decoder.hip GEMV_OUT_SLAB)
+    float* slab; int slab_rows;                      // [WLX_FC2_KS][slab_rows][d] partial sums of the K-split MLP output projection (dec_gemv.hip GEMV_OUT_SLAB)
     half_t* part_o; float* part_ml;
     int *d_token, *d_pos, *d_cache, *d_ancrow, *d_group_item;
     bool prefill;                                    // the prompt-prefill set: decoder_pass picks its launch forms by it

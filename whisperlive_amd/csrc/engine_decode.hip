@@ -327,10 +327,8 @@ void wlx::launch_search(Engine* e, Slot* s, int rows, int R, int groups, bool sa
 // step leaves two — 1.5 on average against 1 with one step per graph. The call itself returns at the done word either way (the results are in pinned
 // memory); only work queued behind it on the same stream sees the extra 0.2 ms. So two steps are used where latency is what counts and the GPU has
 // room — ONE live slot on the device, one stream's rows (<= 16) — and one step everywhere else (several clients' slots, batched rows).
-// WLX_GRAPH_STEPS=1 forces one step per graph (A/B).
 static int graph_steps_for(const Slot* s, int rows) {
-    static const int env = [] { const char* v = wlx_ab("WLX_GRAPH_STEPS"); const int n = v ? atoi(v) : 2; return (n == 1 || n == 2) ? n : 2; }();
-    if (env == 1 || rows > 16) return 1;
+    if (rows > 16) return 1;
     const bool alone = s->device_of >= 0 && s->device_of < 64 && g_slots_live[s->device_of].load(std::memory_order_relaxed) <= 1;
     return alone ? 2 : 1;
 }
@@ -349,7 +347,7 @@ static int get_step_graph(Engine* e, Slot* s, int rows, int R, int groups, bool 
     if (it != s->graphs.end()) { *out = it->second; return WLX_OK; }
     hipGraph_t graph;
     // One eager pass first: the first launch of a kernel instantiation may have to raise its dynamic-LDS limit
-    // (decoder.hip g2_launch), which must not happen inside a capture. It only rewrites scratch and re-appends the K/V the
+    // (dec_gemv.hip g2_launch), which must not happen inside a capture. It only rewrites scratch and re-appends the K/V the
     // captured replay appends again (same rows, same positions); the search, which mutates state, is not run.
     decoder_pass(e, s, s->step, rows, R, groups, true, true);
     CK(hipGetLastError());
@@ -514,8 +512,7 @@ static int gen_prefill(Engine* e, Slot* s, const wlx_gen_opts* o, int batch, int
         longest = std::max(longest, pl - 1);
         with_prompt += pl > 1 ? 1 : 0;
     }
-    static const bool joint = [] { const char* v = wlx_ab("WLX_PREFILL_JOINT"); return !(v && v[0] == '0'); }();
-    if (!(joint && batch > 1 && with_prompt > 1 && longest <= 16 && s->pf_ok && !s->align && !s->prof && !g_decode_v1)) {
+    if (!(batch > 1 && with_prompt > 1 && longest <= 16 && s->pf_ok && !s->align && !s->prof && !g_decode_v1)) {
         for (int b = 0; b < batch; ++b) {
             const int pl = plens[b];
             if (pl > 1)
