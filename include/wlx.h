@@ -402,6 +402,14 @@ void    wlx_spk_destroy(wlx_spk* spk);
 /* L2-normalised embedding out[embed_dim] of 16 kHz mono PCM in [-1, 1]. WLX_ERR_TOO_SHORT under 4800 samples (0.3 s, where the
  * reference returns no embedding), WLX_ERR_ARG over max_seconds. Returns when the result is final. */
 int32_t wlx_spk_embed(wlx_spk* spk, const float* pcm_f32, int64_t n_samples, float* out);
+/* The same for 1 <= n <= WLX_SPK_MAX_BATCH segments in ONE pass over the network (one upload, one launch sequence, one wait):
+ * pcm_f32 holds the segments back to back (host), n_samples[i] the length of each, out [n][embed_dim] one embedding per segment,
+ * with the bits wlx_spk_embed gives for that segment alone, whatever else is in the batch. status[i] = WLX_OK, or
+ * WLX_ERR_TOO_SHORT for a segment under 4800 samples: its row is zero and it takes no part in the pass (all too short: WLX_OK,
+ * nothing launched). The segments share the engine's buffers: WLX_ERR_ARG, nothing launched and nothing written, when their
+ * lengths sum to more than max_seconds, for n outside its range and for a null pointer. */
+#define WLX_SPK_MAX_BATCH 64
+int32_t wlx_spk_embed_batch(wlx_spk* spk, const float* pcm_f32, const int64_t* n_samples, int32_t n, float* out, int32_t* status);
 
 /* ==== everything below: TEST / PROFILING hooks (used only by tests/, scripts/ and bench.py's roofline leg; not part of
  * the drop-in boundary; the product entry points end here) ================================================================= */
@@ -458,7 +466,8 @@ int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_t rows, int
 int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vocab, int32_t d, const int32_t* tok, const int32_t* pos,
                            int32_t rows, float scale, const float* sinpos, int32_t n_pos, float* x);
 
-/* speaker engine: device times (HIP events) of the last wlx_spk_embed: filterbank, then network + pooling + head */
+/* speaker engine: device times (HIP events) of the last wlx_spk_embed or wlx_spk_embed_batch that launched: filterbank, then
+ * network + pooling + head */
 int32_t wlx_spk_debug_timings(wlx_spk* spk, float* fbank_ms, float* net_ms);
 /* speaker engine kernels, one launch each on host arrays, same conventions as the hooks above.
  * Filterbank of n_samples >= 400 samples: frames_out float32 [T][n_mels] (log-mel, per-bin mean removed) and image_out, its fp16
@@ -473,6 +482,14 @@ int32_t wlx_spk_debug_conv(int32_t device, const uint16_t* in, int32_t H, int32_
                            const uint16_t* resid, int32_t Cout, int32_t stride, int32_t ksize, int32_t relu, uint16_t* out);
 /* Statistics pooling of x fp16 [F][T][C] over T >= 2 (C a multiple of 64): out float32 [2][C][F], mean then sqrt(var_unbiased + eps) */
 int32_t wlx_spk_debug_pool(int32_t device, const uint16_t* x, int32_t F, int32_t T, int32_t C, float eps, float* out);
+/* The ragged forms, one launch over n <= WLX_SPK_MAX_BATCH items packed back to back without padding. Convolution: item i is its own
+ * [H][widths[i]][Cin] image in `in` and its own [OH][(widths[i] - 1) / stride + 1][Cout] image in `resid` / `out`; the rest as
+ * wlx_spk_debug_conv, Cin = 1 included. Pooling: item i is [F][frames[i]][C] (frames[i] >= 2), out float32 [n][2][C][F]. */
+int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, int32_t H, int32_t n, const int32_t* widths, int32_t Cin,
+                                 const float* w, const float* bias, const uint16_t* resid, int32_t Cout, int32_t stride, int32_t ksize,
+                                 int32_t relu, uint16_t* out);
+int32_t wlx_spk_debug_pool_batch(int32_t device, const uint16_t* x, int32_t F, int32_t n, const int32_t* frames, int32_t C, float eps,
+                                 float* out);
 
 /* Whisper kernels, one launch each (csrc/kernel_hooks.hip), same conventions: host arrays (fp16 as uint16 bits), a private stream
  * of `device`, outputs copied in AND out (bytes no thread owns come back unchanged), WLX_ERR_ARG before any launch for every

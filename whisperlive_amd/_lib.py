@@ -25,11 +25,12 @@ EXPORTS = [
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
     "wlx_logmel_chunks", "wlx_vad_probs_pcm",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
-    "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed",
+    "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
     "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
     "wlx_mt_debug_embed",
     "wlx_spk_debug_timings", "wlx_spk_debug_fbank", "wlx_spk_debug_conv", "wlx_spk_debug_pool",
+    "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
     "wlx_debug_resample", "wlx_debug_resample_timed",
 ]
@@ -96,6 +97,7 @@ class wlx_spk_spec(C.Structure):
 
 
 ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
+SPK_MAX_BATCH = 64      # wlx.h WLX_SPK_MAX_BATCH: segments of one wlx_spk_embed_batch call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
 ERR_STATE = 4           # wlx_status WLX_ERR_STATE
 LM_MAXRANGES = 256      # wlx.h WLX_LM_MAXRANGES: ranges per chunk of wlx_logmel_chunks / wlx_logmel_ring
@@ -304,10 +306,13 @@ def load() -> C.CDLL:
     lib.wlx_spk_destroy.argtypes = [vp]
     lib.wlx_spk_destroy.restype = None
     lib.wlx_spk_embed.argtypes = [vp, f32p, i64, f32p]
+    lib.wlx_spk_embed_batch.argtypes = [vp, f32p, i64p, i32, f32p, i32p]
     lib.wlx_spk_debug_timings.argtypes = [vp, f32p, f32p]
     lib.wlx_spk_debug_fbank.argtypes = [i32, f32p, i64, i32, f32p, u16p, i32, i32p]
     lib.wlx_spk_debug_conv.argtypes = [i32, u16p, i32, i32, i32, f32p, f32p, u16p, i32, i32, i32, i32, u16p]
     lib.wlx_spk_debug_pool.argtypes = [i32, u16p, i32, i32, i32, C.c_float, f32p]
+    lib.wlx_spk_debug_conv_batch.argtypes = [i32, u16p, i32, i32, i32p, i32, f32p, f32p, u16p, i32, i32, i32, i32, u16p]
+    lib.wlx_spk_debug_pool_batch.argtypes = [i32, u16p, i32, i32, i32p, i32, C.c_float, f32p]
     lib.wlx_debug_layernorm.argtypes = [i32, f32p, i64, f32p, f32p, i32, i32, u16p, f32p, i64]
     lib.wlx_debug_attn_encoder.argtypes = [i32, u16p, i64, i64, u16p, i64, i64, u16p, i64, i64, u16p, i64, i64, i32, i32, i32]
     lib.wlx_debug_dec_cross_attn.argtypes = [i32, u16p, i64, u16p, u16p, i64, i32, i32, i32, i32, i32, i32p, u16p, f32p, u16p, i64,

@@ -2,6 +2,7 @@
 // filterbank front end of WeSpeaker, the ResNet convolutions as implicit GEMMs on mfma_f32_16x16x32_f16, statistics pooling
 // and the embedding head. Activations are NHWC fp16 ([H = frequency][W = time][C]), accumulation is fp32.
 #pragma once
+#include "../../include/wlx.h"          // WLX_SPK_MAX_BATCH: items of one ragged batch (their table travels in the kernel arguments)
 #include "kernels.h"
 
 namespace wlx {
@@ -43,5 +44,23 @@ inline size_t spk_packed_halfs(int Cout, int Cin, int ks) { return (size_t)(Cout
 bool launch_spk_pool(const half_t* x, int F, int T, int C, float eps, float* out, hipStream_t s);
 // emb = W pooled + b (W fp16 [E][D] row-major, D a multiple of 8), then emb /= |emb|. E <= 1024.
 void launch_spk_head(const float* pooled, const half_t* W, const float* b, int E, int D, float* emb, hipStream_t s);
+
+// ---- ragged batch: n <= WLX_SPK_MAX_BATCH items of different lengths in one launch, packed back to back without padding. At a
+// stage of geometry (H, C) item i is its own [H][W_i][C] image at pixel offset H * sum_{j<i} W_j; a stride-s convolution gives
+// OW_i = (W_i - 1) / s + 1 per item. Every item's output has the bits of the single-item launcher above on that item alone; no tap
+// reads a neighbouring item. `widths` / `frames` / `offsets` are HOST arrays, read before the call returns. False = nothing launched.
+// frame t of item i = pcm[offsets[i] + 160 t ...), logmel rows in item order ([sum frames][n_mels])
+bool launch_spk_fbank_batch(const float* pcm, const long* offsets, const int* frames, int n, const float* window, const float* twiddle,
+                            const float* mel, int n_mels, float* logmel, hipStream_t s);
+// per item: the mean over its own frames; out16 item i = [n_mels][frames[i]] at n_mels * sum_{j<i} frames[j]
+bool launch_spk_cmn_batch(float* logmel, const int* frames, int n, int n_mels, half_t* out16, hipStream_t s);
+bool launch_spk_conv_batch(const half_t* in, int H, const int* widths, int n, int Cin, const half_t* Wp, const float* bias,
+                           const half_t* resid, int Cout, int stride, int ks, bool relu, half_t* out, hipStream_t s);
+bool launch_spk_conv_c1_batch(const half_t* in, int H, const int* widths, int n, const float* w, const float* bias, const half_t* resid,
+                              int Cout, int stride, bool relu, half_t* out, hipStream_t s);
+// x item i = [F][frames[i]][C] (frames[i] >= 2); out [n][2][C][F]
+bool launch_spk_pool_batch(const half_t* x, int F, const int* frames, int n, int C, float eps, float* out, hipStream_t s);
+// pooled [n][D] -> emb [n][E]
+void launch_spk_head_batch(const float* pooled, const half_t* W, const float* b, int E, int D, int n, float* emb, hipStream_t s);
 
 }  // namespace wlx

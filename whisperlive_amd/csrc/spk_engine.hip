@@ -1,7 +1,9 @@
 // spk_engine.hip — the speaker-embedding engine behind `enable_diarization` (include/wlx.h wlx_spk_*): WeSpeaker ResNet34 on the
 // kernels of spk.hip. One engine per GPU on a non-blocking stream of its own; every buffer is sized at create for max_seconds of
 // audio and fully rewritten by each call up to the extent that call reads, so no call sees another's data. Calls are serialised
-// by the engine's mutex. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv / _pool.
+// by the engine's mutex. wlx_spk_embed_batch runs up to WLX_SPK_MAX_BATCH segments as one ragged pass through the same buffers (the
+// sum of their lengths is what has to fit max_seconds). Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
+// _pool and their ragged forms _conv_batch / _pool_batch.
 #include <cmath>
 #include <mutex>
 #include "host.h"
@@ -106,6 +108,7 @@ struct wlx_spk {
     float *pcm = nullptr, *logmel = nullptr, *pooled = nullptr, *emb = nullptr;
     half_t* feat16 = nullptr;
     half_t* act[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* h_emb = nullptr;          // pinned [WLX_SPK_MAX_BATCH][embed_dim]: where a batch's embeddings land before they are dealt to rows
     float fbank_ms = 0.f, net_ms = 0.f;
     bool timed = false;
 };
@@ -117,6 +120,7 @@ static void spk_free(wlx_spk* k) {
     for (hipEvent_t e : k->ev)
         if (e) (void)hipEventDestroy(e);
     for (void* p : k->pool) (void)hipFree(p);
+    if (k->h_emb) (void)hipHostFree(k->h_emb);
     if (k->st) (void)hipStreamDestroy(k->st);
     delete k;
 }
@@ -170,8 +174,11 @@ static int spk_build(wlx_spk* k, const wlx_tensor* weights, int n_weights) {
     CKR(dalloc(k->pool, &k->feat16, Tmax * sp.n_mels, false));
     // the stem's output is the largest activation: every stride-2 stage halves H and W and doubles C
     for (half_t*& a : k->act) CKR(dalloc(k->pool, &a, Tmax * sp.n_mels * m, false));
-    CKR(dalloc(k->pool, &k->pooled, (size_t)k->pool_dim, false));
-    CKR(dalloc(k->pool, &k->emb, (size_t)sp.embed_dim, false));
+    // (a batch packs its items into the buffers above: sum T_i <= spk_frames(sum n_i), and from the second stage on the rounded-up
+    // halves sum to at most (sum W_i + n) / 2 columns of half the rows and twice the channels: under the stem's extent, n <= sum W_i)
+    CKR(dalloc(k->pool, &k->pooled, (size_t)k->pool_dim * WLX_SPK_MAX_BATCH, false));
+    CKR(dalloc(k->pool, &k->emb, (size_t)sp.embed_dim * WLX_SPK_MAX_BATCH, false));
+    CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_emb), (size_t)sp.embed_dim * WLX_SPK_MAX_BATCH * sizeof(float), hipHostMallocDefault));
     return WLX_OK;
 }
 
@@ -247,6 +254,78 @@ extern "C" int32_t wlx_spk_embed(wlx_spk* k, const float* pcm, int64_t n_samples
     CK(hipGetLastError());
     CK(hipMemcpyAsync(out, k->emb, (size_t)sp.embed_dim * sizeof(float), hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
+    CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));
+    CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
+    k->timed = true;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_spk_embed_batch(wlx_spk* k, const float* pcm, const int64_t* n_samples, int32_t n, float* out, int32_t* status) {
+    if (!k || !pcm || !n_samples || !out || !status) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_MAX_BATCH) return set_error(WLX_ERR_ARG, "%d items outside 1..%d", n, WLX_SPK_MAX_BATCH);
+    long total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] < 0 || n_samples[i] > k->max_samples)
+            return set_error(WLX_ERR_ARG, "item %d: %lld samples outside 0..the engine's %d s", i, (long long)n_samples[i], k->spec.max_seconds);
+        total += (long)n_samples[i];
+    }
+    if (total > k->max_samples)
+        return set_error(WLX_ERR_ARG, "%ld samples in %d items exceed the engine's %d s", total, n, k->spec.max_seconds);
+    const wlx_spk_spec& sp = k->spec;
+    // the items that take part: where each starts in the upload, its frames, the row of `out` it fills
+    long offs[WLX_SPK_MAX_BATCH];
+    int widths[WLX_SPK_MAX_BATCH], row[WLX_SPK_MAX_BATCH], m = 0;
+    long at = 0;
+    for (int i = 0; i < n; ++i) {
+        const bool too_short = n_samples[i] < WLX_SPK_MIN_SAMPLES;
+        status[i] = too_short ? WLX_ERR_TOO_SHORT : WLX_OK;
+        if (too_short) {
+            std::fill(out + (size_t)i * sp.embed_dim, out + (size_t)(i + 1) * sp.embed_dim, 0.f);
+        } else {
+            offs[m] = at, widths[m] = spk_frames((long)n_samples[i]), row[m] = i;
+            ++m;
+        }
+        at += (long)n_samples[i];
+    }
+    if (m == 0) return WLX_OK;
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    hipStream_t st = k->st;
+    // one upload: the caller's items lie back to back, the short ones among them are carried along and never read
+    CK(hipMemcpyAsync(k->pcm, pcm, (size_t)total * sizeof(float), hipMemcpyHostToDevice, st));
+    CK(hipEventRecord(k->ev[0], st));
+    if (!launch_spk_fbank_batch(k->pcm, offs, widths, m, k->window, k->twiddle, k->mel, sp.n_mels, k->logmel, st) ||
+        !launch_spk_cmn_batch(k->logmel, widths, m, sp.n_mels, k->feat16, st))
+        return set_error(WLX_ERR_ARG, "front end refused a batch of %d", m);
+    CK(hipEventRecord(k->ev[1], st));
+    int H = sp.n_mels;
+    half_t *x = k->act[0], *t1 = k->act[1], *y = k->act[2], *sc = k->act[3];
+    if (!launch_spk_conv_c1_batch(k->feat16, H, widths, m, k->stem_w, k->stem_b, nullptr, sp.planes, 1, true, x, st))
+        return set_error(WLX_ERR_ARG, "stem convolution refused a batch of %d", m);
+    for (const SpkBlock& b : k->blocks) {
+        const int s = b.c1.stride, OH = (H - 1) / s + 1;
+        int ow[WLX_SPK_MAX_BATCH];
+        for (int i = 0; i < m; ++i) ow[i] = (widths[i] - 1) / s + 1;
+        bool ok = launch_spk_conv_batch(x, H, widths, m, b.c1.cin, b.c1.Wp, b.c1.bias, nullptr, b.c1.cout, s, 3, true, t1, st);
+        const half_t* resid = x;
+        if (b.has_sc) {
+            ok = ok && launch_spk_conv_batch(x, H, widths, m, b.sc.cin, b.sc.Wp, b.sc.bias, nullptr, b.sc.cout, s, 1, false, sc, st);
+            resid = sc;
+        }
+        ok = ok && launch_spk_conv_batch(t1, OH, ow, m, b.c2.cin, b.c2.Wp, b.c2.bias, resid, b.c2.cout, 1, 3, true, y, st);
+        if (!ok) return set_error(WLX_ERR_ARG, "convolution refused a batch of %d at H %d x Cin %d", m, H, b.c1.cin);
+        std::swap(x, y);
+        H = OH;
+        std::copy(ow, ow + m, widths);
+    }
+    if (!launch_spk_pool_batch(x, H, widths, m, sp.planes << 3, sp.pool_eps, k->pooled, st))
+        return set_error(WLX_ERR_ARG, "pooling refused a batch of %d", m);
+    launch_spk_head_batch(k->pooled, k->head_W, k->head_b, sp.embed_dim, k->pool_dim, m, k->emb, st);
+    CK(hipEventRecord(k->ev[2], st));
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(k->h_emb, k->emb, (size_t)m * sp.embed_dim * sizeof(float), hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    for (int a = 0; a < m; ++a) std::copy(k->h_emb + (size_t)a * sp.embed_dim, k->h_emb + (size_t)(a + 1) * sp.embed_dim, out + (size_t)row[a] * sp.embed_dim);
     CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));
     CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
     k->timed = true;
@@ -369,5 +448,76 @@ extern "C" int32_t wlx_spk_debug_pool(int32_t device, const uint16_t* x, int32_t
     CKR(S.upload(&dout, out, (size_t)2 * F * C));
     if (!launch_spk_pool(dx, F, T, C, eps, dout, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
     CK(hipMemcpyAsync(out, dout, (size_t)2 * F * C * sizeof(float), hipMemcpyDeviceToHost, S.st));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, int32_t H, int32_t n, const int32_t* widths, int32_t Cin,
+                                            const float* w, const float* bias, const uint16_t* resid, int32_t Cout, int32_t stride,
+                                            int32_t ksize, int32_t relu, uint16_t* out) {
+    if (!in || !w || !out || !widths) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_MAX_BATCH) return set_error(WLX_ERR_ARG, "%d items outside 1..%d", n, WLX_SPK_MAX_BATCH);
+    if (stride != 1 && stride != 2) return set_error(WLX_ERR_ARG, "stride %d must be 1 or 2", stride);
+    long Wsum = 0, OWsum = 0;
+    for (int i = 0; i < n; ++i) {
+        if (widths[i] < 1 || widths[i] > (1 << 24)) return set_error(WLX_ERR_ARG, "widths[%d] = %d outside 1..2^24", i, widths[i]);
+        Wsum += widths[i], OWsum += (widths[i] - 1) / stride + 1;
+    }
+    if (H < 1 || (long)H * Wsum > (1L << 24)) return set_error(WLX_ERR_ARG, "H %d x sum of widths %ld outside 1..2^24 pixels", H, Wsum);
+    const bool c1 = Cin == 1;
+    if (c1 ? (ksize != 3 || Cout < 4 || Cout % 4 || Cout > 1024)
+           : ((ksize != 1 && ksize != 3) || Cin < 32 || Cin % 32 || Cin > 1024 || Cout < 32 || Cout % 32 || Cout > 1024))
+        return set_error(WLX_ERR_ARG, "Cin %d / Cout %d / ksize %d: Cin = 1 (ksize 3, Cout a multiple of 4) or Cin and Cout multiples of 32 up "
+                         "to 1024 with ksize 1 or 3", Cin, Cout, ksize);
+    const int OH = (H - 1) / stride + 1;
+    const size_t n_out = (size_t)OH * OWsum * Cout;
+    std::vector<float> zeros;          // (host staging declared before S, as in wlx_spk_debug_conv)
+    std::vector<half_t> packed;
+    SpkHook S;
+    CKR(S.begin(device));
+    half_t *din, *dres = nullptr, *dout;
+    float* dbias;
+    CKR(S.upload(&din, in, (size_t)H * Wsum * Cin));
+    if (!bias) zeros.assign((size_t)Cout, 0.f);
+    CKR(S.upload(&dbias, bias ? bias : zeros.data(), (size_t)Cout));
+    if (resid) CKR(S.upload(&dres, resid, n_out));
+    CKR(S.upload(&dout, out, n_out));
+    bool ok;
+    if (c1) {
+        float* dw;
+        CKR(S.upload(&dw, w, (size_t)Cout * 9));
+        ok = launch_spk_conv_c1_batch(din, H, widths, n, dw, dbias, dres, Cout, stride, relu != 0, dout, S.st);
+    } else {
+        packed.resize(spk_packed_halfs(Cout, Cin, ksize));
+        spk_pack_conv(w, Cout, Cin, ksize, packed.data());
+        half_t* dWp;
+        CKR(S.upload(&dWp, packed.data(), packed.size()));
+        ok = launch_spk_conv_batch(din, H, widths, n, Cin, dWp, dbias, dres, Cout, stride, ksize, relu != 0, dout, S.st);
+    }
+    if (!ok) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CK(hipMemcpyAsync(out, dout, n_out * sizeof(half_t), hipMemcpyDeviceToHost, S.st));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_spk_debug_pool_batch(int32_t device, const uint16_t* x, int32_t F, int32_t n, const int32_t* frames, int32_t C,
+                                            float eps, float* out) {
+    if (!x || !out || !frames) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_MAX_BATCH) return set_error(WLX_ERR_ARG, "%d items outside 1..%d", n, WLX_SPK_MAX_BATCH);
+    if (F < 1 || F > 4096 || C < 64 || C % 64 || C > 4096 || !(eps >= 0.f))
+        return set_error(WLX_ERR_ARG, "F %d / C %d: F in 1..4096, C a multiple of 64 up to 4096", F, C);
+    long Tsum = 0;
+    for (int i = 0; i < n; ++i) {
+        if (frames[i] < 2 || frames[i] > (1 << 20)) return set_error(WLX_ERR_ARG, "frames[%d] = %d outside 2..2^20", i, frames[i]);
+        Tsum += frames[i];
+    }
+    if (Tsum > (1 << 20)) return set_error(WLX_ERR_ARG, "%ld frames in all exceed 2^20", Tsum);
+    SpkHook S;
+    CKR(S.begin(device));
+    half_t* dx;
+    float* dout;
+    const size_t n_out = (size_t)n * 2 * F * C;
+    CKR(S.upload(&dx, x, (size_t)F * Tsum * C));
+    CKR(S.upload(&dout, out, n_out));
+    if (!launch_spk_pool_batch(dx, F, frames, n, C, eps, dout, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CK(hipMemcpyAsync(out, dout, n_out * sizeof(float), hipMemcpyDeviceToHost, S.st));
     return S.finish();
 }

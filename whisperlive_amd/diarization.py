@@ -3,18 +3,23 @@ whisper_live/diarization.py, created per client in whisper_live/server.py:346-36
 base.py `_identify_speaker`).
 
 * ``SpeakerEmbedderHIP`` — ctypes binding of the wlx_spk_* entry points: one WeSpeaker ResNet34 engine on one GPU. ``embed(pcm)``
-                           returns the L2-normalised embedding, or None under 0.3 s. ``shared_embedder`` keeps one per (checkpoint,
-                           device), loaded by the first client that asks for diarization.
+                           returns the L2-normalised embedding, or None under 0.3 s; ``embed_many(pcms)`` the same for a list of
+                           segments, packed by ``plan_embed_groups`` into as few wlx_spk_embed_batch passes as the engine's
+                           buffers allow (a file's segments; the streaming server embeds one at a time). ``shared_embedder``
+                           keeps one per (checkpoint, device), loaded by the first client that asks for diarization.
 * ``SpeakerDiarizer``    — the reference's online clustering, unchanged in behaviour: cosine similarity against the running
                            centroids, threshold 0.55, 0.9 / 0.1 running average with renormalisation, closest speaker at the cap,
                            ``speaker_names``, ``enroll_speaker``, ``reset``, labels ``SPEAKER_%02d``. ``embedder`` is any callable
                            (pcm float32, sample_rate) -> unit vector or None, so the clustering is testable without a GPU.
+                           ``identify_speakers(audios)`` labels a list of segments: every embedding first (one ``embed_many``
+                           call when the embedder has it), then the same clustering step in order, so the labels are those of
+                           ``identify_speaker`` called once per segment.
 """
 from __future__ import annotations
 
 import ctypes as C
 import threading
-from typing import Callable, Dict, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -22,6 +27,27 @@ from . import _lib
 from .spk_weights import SpkSpec
 
 MIN_SECONDS = 0.3
+
+
+def plan_embed_groups(lengths: Sequence[int], cap_samples: int, max_items: int = _lib.SPK_MAX_BATCH) -> List[List[int]]:
+    """Indices of `lengths` (samples per segment) grouped greedily, in order, into batches of one wlx_spk_embed_batch call each:
+    a group holds at most `max_items` segments and at most `cap_samples` samples in all. A segment longer than the cap is a group of
+    its own (the caller cuts it to the cap, as `embed` does)."""
+    if cap_samples < 1 or max_items < 1:
+        raise ValueError("cap_samples and max_items must be positive")
+    groups: List[List[int]] = []
+    cur: List[int] = []
+    total = 0
+    for i, n in enumerate(lengths):
+        n = int(n)
+        if cur and (len(cur) >= max_items or total + n > cap_samples):
+            groups.append(cur)
+            cur, total = [], 0
+        cur.append(i)
+        total += n
+    if cur:
+        groups.append(cur)
+    return groups
 
 
 class SpeakerEmbedderHIP:
@@ -63,6 +89,31 @@ class SpeakerEmbedderHIP:
         return out
 
     __call__ = embed
+
+    def embed_many(self, pcms, sample_rate: int = 16000) -> List[Optional[np.ndarray]]:
+        """`embed` of every segment of `pcms`, None where one is under 0.3 s; each embedding has the bits `embed` gives for that
+        segment alone. One wlx_spk_embed_batch call per group of plan_embed_groups."""
+        if sample_rate != 16000:
+            raise ValueError("the speaker engine takes 16 kHz audio")
+        if self.h is None:
+            raise _lib.WlxError("speaker engine is closed")
+        cap = self.spec.max_seconds * 16000
+        pcms = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1)[:cap] for p in pcms]
+        result: List[Optional[np.ndarray]] = [None] * len(pcms)
+        f32p = C.POINTER(C.c_float)
+        for group in plan_embed_groups([len(p) for p in pcms], cap):
+            packed = np.ascontiguousarray(np.concatenate([pcms[i] for i in group]))
+            lengths = np.array([len(pcms[i]) for i in group], dtype=np.int64)
+            out = np.zeros((len(group), self.spec.embed_dim), dtype=np.float32)
+            status = np.zeros(len(group), dtype=np.int32)
+            _lib.check(self.lib.wlx_spk_embed_batch(self.h, packed.ctypes.data_as(f32p), lengths.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    len(group), out.ctypes.data_as(f32p), status.ctypes.data_as(C.POINTER(C.c_int32))))
+            for row, i in enumerate(group):
+                if status[row] == _lib.ERR_TOO_SHORT:
+                    continue
+                _lib.check(int(status[row]))
+                result[i] = out[row].copy()
+        return result
 
     def timings(self) -> Tuple[float, float]:
         """device milliseconds of the last embed: (filterbank, network)"""
@@ -153,7 +204,27 @@ class SpeakerDiarizer:
 
     def identify_speaker(self, audio_np, sample_rate=16000):
         """the label of the segment's speaker, or None when the audio is too short to embed"""
-        emb = self._compute_embedding(audio_np, sample_rate)
+        return self._assign(self._compute_embedding(audio_np, sample_rate))
+
+    def identify_speakers(self, audios, sample_rate=16000) -> List[Optional[str]]:
+        """`identify_speaker` of every segment of `audios`, in order, with all embeddings computed first: through the embedder's
+        `embed_many` (one call for all segments of at least MIN_SECONDS) when it has one, else one call per segment"""
+        self._ensure_embedder()
+        audios = list(audios)
+        many = getattr(self._embed, "embed_many", None)
+        if many is None:
+            embs = [self._compute_embedding(a, sample_rate) for a in audios]
+        else:
+            asked = [i for i, a in enumerate(audios) if len(a) >= sample_rate * MIN_SECONDS]
+            embs = [None] * len(audios)
+            for i, emb in zip(asked, many([audios[i] for i in asked], sample_rate) if asked else []):
+                if emb is not None:
+                    emb = np.asarray(emb)
+                    embs[i] = emb / np.linalg.norm(emb)
+        return [self._assign(emb) for emb in embs]
+
+    def _assign(self, emb):
+        """the clustering step: the label for a unit-norm embedding (None stays None), the centroids updated"""
         if emb is None:
             return None
         who, sim = self._closest(emb)

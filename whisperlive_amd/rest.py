@@ -157,19 +157,21 @@ def render_subtitles(segments, response_format: str) -> str:
 
 
 def speaker_labels_for_segments(segments, audio_np, diarizer, sample_rate: int = 16000) -> Dict[int, str]:
-    """server.py:585-598"""
+    """server.py:585-598. A diarizer with `identify_speakers` gets all non-empty ranges in one call (SpeakerDiarizer embeds them in
+    batches on the device); the labels are those of the one-by-one loop, which any other diarizer still gets."""
     if diarizer is None or audio_np is None:
         return {}
-    labels = {}
+    ranges = []
     for index, segment in enumerate(segments):
         start = max(0, int(segment.start * sample_rate))
         end = min(len(audio_np), int(segment.end * sample_rate))
-        if end <= start:
-            continue
-        speaker = diarizer.identify_speaker(audio_np[start:end], sample_rate)
-        if speaker:
-            labels[index] = speaker
-    return labels
+        if end > start:
+            ranges.append((index, start, end))
+    if hasattr(diarizer, "identify_speakers"):
+        speakers = diarizer.identify_speakers([audio_np[start:end] for _, start, end in ranges], sample_rate)
+    else:
+        speakers = [diarizer.identify_speaker(audio_np[start:end], sample_rate) for _, start, end in ranges]
+    return {index: speaker for (index, _, _), speaker in zip(ranges, speakers) if speaker}
 
 
 class _HttpError(Exception):
