@@ -329,6 +329,27 @@ int32_t wlx_vad_probs_resident(wlx_vad* v, wlx_ring* r, int64_t start, int64_t n
  * WLX_ERR_STATE. */
 int32_t wlx_vad_probs_pcm(wlx_vad* v, wlx_engine* e, int32_t slot, int32_t item, int64_t start, int64_t n, int32_t extra_zero_windows,
                           float* probs_out, int32_t cap, int32_t* n_windows_out, float* device_ms_out);
+/* The gate of a BATCH (the batch worker's requests, whisper_live/batch_inference.py:245-248, where the reference calls the network once
+ * per item): 1 <= n <= WLX_VAD_MAX_BATCH sequences of different lengths in ONE pass — one upload, one launch of each kernel, one
+ * download, one wait. The recurrences are independent and run side by side, one workgroup (one CU) each.
+ * wlx_vad_probs_batch: `pcm` holds the n segments back to back on the host, segment i of n_samples[i] samples.
+ * T_i = ceil(n_samples[i] / 512) + extra_zero_windows[i] windows (0 <= extra <= 4, meaning as in wlx_vad_probs_resident; a null
+ * `extra_zero_windows` is all 0). probs_out receives the rows packed in item order (sum T_i <= cap floats), n_windows_out[i] = T_i.
+ * Row i has the bits wlx_vad_probs returns for segment i zero-padded to 512 * T_i samples, whatever else is in the batch and in
+ * whatever order: every item starts from a zero state and no workgroup serves two items. An item with T_i == 0 takes no part (all
+ * empty: WLX_OK, nothing launched). WLX_ERR_ARG before any launch, nothing written: n outside 1..WLX_VAD_MAX_BATCH, a null pointer, a
+ * negative count, an extra out of range, sum T_i > cap, more than 3600 s of samples in all.
+ * wlx_vad_probs_pcm_batch: the same on samples [0, n_samples[i]) of the resident PCM of slot items first_item + i (wlx_pcm_put /
+ * wlx_pcm_put_frames): no host-to-device copy of audio, the VAD object's PCM buffers (device and pinned) are not touched, its stream is
+ * ordered behind the slot's with ONE event, the slot counts as busy for the call. Errors as wlx_vad_probs_pcm: WLX_ERR_ARG for
+ * different devices or items outside the slot, WLX_ERR_STATE for a busy slot or an item holding fewer than n_samples[i] samples.
+ * device_ms_out (nullable): HIP-event time from the first to the last kernel. */
+#define WLX_VAD_MAX_BATCH 64
+int32_t wlx_vad_probs_batch(wlx_vad* v, const float* pcm, const int64_t* n_samples, const int32_t* extra_zero_windows, int32_t n,
+                            float* probs_out, int64_t cap, int32_t* n_windows_out, float* device_ms_out);
+int32_t wlx_vad_probs_pcm_batch(wlx_vad* v, wlx_engine* e, int32_t slot, int32_t first_item, const int64_t* n_samples,
+                                const int32_t* extra_zero_windows, int32_t n, float* probs_out, int64_t cap,
+                                int32_t* n_windows_out, float* device_ms_out);
 /* Host only (no device work): the hysteresis segmentation of per-window speech probabilities into padded sample ranges —
  * faster_whisper.vad.get_speech_timestamps' loop (reference call site: transcriber_faster_whisper.py:825-852), statement for
  * statement whisperlive_amd/vad.py speech_segments_from_probs. It runs between the VAD launch and the log-mel launch, with the

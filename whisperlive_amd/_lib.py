@@ -23,7 +23,7 @@ EXPORTS = [
     "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
-    "wlx_logmel_chunks", "wlx_vad_probs_pcm",
+    "wlx_logmel_chunks", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
     "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
@@ -98,6 +98,7 @@ class wlx_spk_spec(C.Structure):
 
 ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
 SPK_MAX_BATCH = 64      # wlx.h WLX_SPK_MAX_BATCH: segments of one wlx_spk_embed_batch call
+VAD_MAX_BATCH = 64      # wlx.h WLX_VAD_MAX_BATCH: sequences of one wlx_vad_probs_batch / wlx_vad_probs_pcm_batch call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
 ERR_STATE = 4           # wlx_status WLX_ERR_STATE
 LM_MAXRANGES = 256      # wlx.h WLX_LM_MAXRANGES: ranges per chunk of wlx_logmel_chunks / wlx_logmel_ring
@@ -283,6 +284,8 @@ def load() -> C.CDLL:
     lib.wlx_logmel_ring.argtypes = [vp, i32, i32, vp, i64p, i32, i32p]
     lib.wlx_logmel_chunks.argtypes = [vp, i32, i32, i64p, i32p, i32, i32, i32p]
     lib.wlx_vad_probs_pcm.argtypes = [vp, vp, i32, i32, i64, i64, i32, f32p, i32, i32p, f32p]
+    lib.wlx_vad_probs_batch.argtypes = [vp, f32p, i64p, i32p, i32, f32p, i64, i32p, f32p]
+    lib.wlx_vad_probs_pcm_batch.argtypes = [vp, vp, i32, i32, i64p, i32p, i32, f32p, i64, i32p, f32p]
     lib.wlx_debug_logits_get.argtypes = [vp, i32, f32p, i32, i64]
     lib.wlx_debug_decode_logits.argtypes = [vp, i32, i32p, i32, f32p]
     lib.wlx_debug_search.argtypes = [vp, i32, f32p, i32, i32p, i32, C.POINTER(wlx_gen_opts), i32p, i32, i32p, f32p]

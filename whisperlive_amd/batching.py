@@ -180,10 +180,59 @@ class BatchInferenceWorker:
         feats = np.stack([pad_or_trim(tr.feature_extractor(a)) for a in audios])
         return tr.encode(feats)
 
+    def _gate_batch(self, batch: List[BatchRequest]):
+        """The batched front half on the device when the transcriber has one (WhisperModelHIP.encode_audio_batch_gated: one upload per
+        request, ONE pass of the VAD gate over all of them, features cut out of the resident PCM, one encoder chain).
+        -> (ready, enc) with the requests that go on to the decoder, or None: the caller runs the per-request gate and
+        `_encode_batch`. A request whose vad_parameters are invalid gets its error here and takes no part; nothing else is set on a
+        request before the batched front half has succeeded, so a fallback starts from the same requests."""
+        tr = self.transcriber
+        if getattr(type(tr), "encode_audio_batch_gated", None) is None:      # class-level: a MagicMock transcriber has "every" attribute
+            return None
+        good, opts_list = [], []
+        for req in batch:
+            try:
+                opts = None
+                if req.use_vad:
+                    params = req.vad_parameters or {}
+                    opts = _vad.VadOptions(**params) if isinstance(params, dict) else params
+                good.append(req)
+                opts_list.append(opts)
+            except Exception as e:  # noqa: BLE001 — this request's error alone
+                req.error = e
+                req.future.set()
+        if not good:
+            return [], None
+        try:
+            got = tr.encode_audio_batch_gated([r.audio for r in good], opts_list)
+        except Exception as e:  # noqa: BLE001 — the per-request route decides what is an error
+            logging.warning(f"[BatchInference] batched VAD front half failed ({type(e).__name__}: {e}); using the per-request gate")
+            got = None
+        if got is None:
+            return None
+        enc, counts = got
+        sr = tr.feature_extractor.sampling_rate
+        ready = []
+        for req, count in zip(good, counts):
+            if count == 0:
+                req.result = []
+                req.info = self._make_info(req, 0.0, 0.0)
+                req.future.set()
+                continue
+            ready.append((req, req.audio, count / sr))
+        return ready, enc
+
     def _process_multi(self, batch: List[BatchRequest]):
         tr = self.transcriber
         sr = tr.feature_extractor.sampling_rate
         ready = []
+        enc = None
+        gated = self._gate_batch(batch)
+        if gated is not None:
+            ready, enc = gated
+            batch = []
+        else:
+            batch = [r for r in batch if not r.future.is_set()]      # (a request refused for its vad_parameters has its error already)
         for req in batch:
             try:
                 audio = req.audio
@@ -207,7 +256,8 @@ class BatchInferenceWorker:
         if not ready:
             return
         try:
-            enc = self._encode_batch([a for _, a, _ in ready])
+            if enc is None:
+                enc = self._encode_batch([a for _, a, _ in ready])
             n = len(ready)
             lang_results = None
             toks: List[Tokenizer] = []

@@ -14,6 +14,8 @@
 //     reduction, the gate non-linearities and one barrier. It is latency-bound by construction (938 dependent steps);
 //     the CPU path it replaces is the same chain at ~30-50 us per step.
 //   output: p[t] = sigmoid(w_out . relu(h_t) + b), parallel over windows.
+//   ragged batch (wlx_vad_probs_batch): up to 64 sequences packed window after window; the front end and the recurrence run the SAME
+//     bodies per item (one recurrence workgroup per item, side by side), so a row has the bits of the single call on that item.
 // fp32 throughout (the gate thresholds at 0.5 / 0.35 are compared against these numbers; the oracle's own fp32-vs-fp64
 // difference is 5e-7). Everything is deterministic: fixed summation orders, no atomics.
 #include "engine.h"
@@ -51,8 +53,10 @@ __device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builti
 
 // ---------------------------------------------------------------------------------------------------------------------
 // front end: VAD_WT windows per workgroup, PCM -> gx
-__global__ __launch_bounds__(VAD_FE_THREADS) void vad_frontend_kernel(const float* __restrict__ pcm, long long n, int n_windows,
-                                                                       VadW W, float* __restrict__ gx) {
+// One workgroup's work, shared by the single-item and the ragged-batch kernel: windows [w0, w0 + VAD_WT) of ONE sequence of `n` samples
+// and `n_windows` windows whose gx rows start at `gx`. A sample position < 0 or >= n, or a window >= n_windows, reads 0.
+__device__ __forceinline__ void vad_frontend_body(const float* __restrict__ pcm, long long n, int n_windows, int w0, const VadW& W,
+                                                  float* __restrict__ gx) {
     __shared__ __attribute__((aligned(16))) float xs[VAD_WT][VAD_XLEN];
     __shared__ __attribute__((aligned(16))) float mag[VAD_WT][VAD_BINS][6];    // positions -1..4 (zero pads at both ends)
     __shared__ __attribute__((aligned(16))) float y1[VAD_WT][128][6];
@@ -61,7 +65,6 @@ __global__ __launch_bounds__(VAD_FE_THREADS) void vad_frontend_kernel(const floa
     __shared__ float y4[VAD_WT][VAD_H];
     __shared__ float nyq[16][VAD_WT * 4][2];
     const int tid = threadIdx.x;
-    const int w0 = blockIdx.x * VAD_WT;
 
     // ---- A: context + window (zeros before the start and past the end), then the reflected tail
     for (int i = tid; i < VAD_WT * (VAD_CTX + VAD_WINDOW); i += VAD_FE_THREADS) {
@@ -225,6 +228,43 @@ __global__ __launch_bounds__(VAD_FE_THREADS) void vad_frontend_kernel(const floa
     }
 }
 
+__global__ __launch_bounds__(VAD_FE_THREADS) void vad_frontend_kernel(const float* __restrict__ pcm, long long n, int n_windows,
+                                                                       VadW W, float* __restrict__ gx) {
+    vad_frontend_body(pcm, n, n_windows, (int)blockIdx.x * VAD_WT, W, gx);
+}
+
+// ---- ragged batch: up to WLX_VAD_MAX_BATCH sequences of different lengths, packed window after window without padding: item i owns
+// windows [w0, w0 + T) of gx / hs / probs. The table travels BY VALUE in the kernel arguments (2 KiB, copied by the launch call itself,
+// like spk.hip's item table): no staging buffer, no copy that could outlive the caller's frame. Only items with T >= 1 are in it.
+struct VadItem {
+    const float* pcm;    // the item's first sample (device)
+    long long n;         // its samples: positions >= n read 0
+    int T;               // its windows (ceil(n / 512) + extra zero windows)
+    int w0;              // its first window in the packed buffers
+    int g0;              // its first front-end workgroup (groups of VAD_WT windows, rounded up PER ITEM: no workgroup straddles two items)
+    int pad_;
+};
+struct VadBatch {
+    int n;
+    VadItem it[WLX_VAD_MAX_BATCH];
+};
+
+// the item that owns front-end workgroup `grp`: the last one with g0 <= grp (g0 is strictly increasing: every item has a window)
+__device__ __forceinline__ int vad_item_of(const VadBatch& tab, int grp) {
+    int lo = 0, hi = tab.n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab.it[mid].g0 <= grp) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(VAD_FE_THREADS) void vad_frontend_batch_kernel(VadBatch tab, VadW W, float* __restrict__ gx) {
+    const VadItem it = tab.it[vad_item_of(tab, (int)blockIdx.x)];              // workgroup-uniform
+    vad_frontend_body(it.pcm, it.n, it.T, ((int)blockIdx.x - it.g0) * VAD_WT, W, gx + (long long)it.w0 * 512);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // recurrence: one workgroup, W_hh register-resident
 template <int CTRL>
@@ -232,8 +272,9 @@ __device__ __forceinline__ float quad_perm(float v) {      // DPP quad_perm move
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
 
-__global__ __launch_bounds__(512) void vad_lstm_kernel(const float* __restrict__ gx, const float* __restrict__ whhP,
-                                                        float* __restrict__ hs, int T) {
+// One workgroup's whole sequence, shared by the single-item and the ragged-batch kernel (same arithmetic, same bits): T steps from
+// zero h and c over the gx rows at `gx`, states to the hs rows at `hs`.
+__device__ __forceinline__ void vad_lstm_body(const float* __restrict__ gx, const float* __restrict__ whhP, float* __restrict__ hs, int T) {
     __shared__ __attribute__((aligned(16))) float hbuf[2][VAD_H];
     const int tid = threadIdx.x, j = tid >> 2, q = tid & 3;
     f32x2 wi[16], wf[16], wg[16], wo[16];
@@ -292,6 +333,20 @@ __global__ __launch_bounds__(512) void vad_lstm_kernel(const float* __restrict__
         // gx prefetch on every one of the T dependent steps
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
+}
+
+__global__ __launch_bounds__(512) void vad_lstm_kernel(const float* __restrict__ gx, const float* __restrict__ whhP,
+                                                        float* __restrict__ hs, int T) {
+    vad_lstm_body(gx, whhP, hs, T);
+}
+
+// ragged batch: blockIdx.x is the item; the recurrences are independent and run side by side, one CU each (a workgroup takes a CU's
+// whole register file, so items beyond the free CUs queue behind the first to finish)
+__global__ __launch_bounds__(512) void vad_lstm_batch_kernel(VadBatch tab, const float* __restrict__ gx, const float* __restrict__ whhP,
+                                                              float* __restrict__ hs) {
+    const int T = tab.it[blockIdx.x].T;
+    const long long row0 = (long long)tab.it[blockIdx.x].w0 * 512;
+    vad_lstm_body(gx + row0, whhP, hs + row0, T);
 }
 
 // output layer: p[t] = sigmoid(w_out . relu(h_t) + b); one wave per window
@@ -553,6 +608,117 @@ extern "C" int32_t wlx_vad_probs_pcm(wlx_vad* v, wlx_engine* e, int32_t slot, in
     memcpy(probs_out, v->h_probs, (size_t)T * sizeof(float));
     if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
     return WLX_OK;
+}
+
+// ------------------------------------------------------------------ ragged batch (include/wlx.h wlx_vad_probs_batch)
+// Everything both batch entry points refuse on the arguments alone, and the geometry of the pass: the table of the items that have a
+// window (window offsets, front-end groups rounded up per item), T_i of EVERY item, the packed window count and the sample total. The
+// sample pointers are filled in by the caller. Nothing of the caller's is written here.
+struct VadPlan {
+    VadBatch tab;
+    int src[WLX_VAD_MAX_BATCH];              // table entry -> item of the call
+    int T[WLX_VAD_MAX_BATCH];
+    long long windows = 0, samples = 0;
+    int groups = 0;
+};
+
+static int vad_plan(const char* who, const int64_t* n_samples, const int32_t* extra, int32_t n, int64_t cap, VadPlan& pl) {
+    if (n < 1 || n > WLX_VAD_MAX_BATCH) return set_error(WLX_ERR_ARG, "%s: %d items (1..%d)", who, n, WLX_VAD_MAX_BATCH);
+    pl.tab.n = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t ni = n_samples[i];
+        const int ex = extra ? extra[i] : 0;
+        if (ni < 0) return set_error(WLX_ERR_ARG, "%s: item %d has a negative sample count", who, i);
+        if (ex < 0 || ex > 4) return set_error(WLX_ERR_ARG, "%s: item %d: extra_zero_windows out of range", who, i);
+        if (ni > 16000LL * 3600 || (pl.samples += ni) > 16000LL * 3600) return set_error(WLX_ERR_ARG, "%s: more than 3600 s of audio", who);
+        const int T = (int)((ni + VAD_WINDOW - 1) / VAD_WINDOW) + ex;
+        pl.T[i] = T;
+        if (T == 0) continue;
+        pl.src[pl.tab.n] = i;
+        pl.tab.it[pl.tab.n++] = VadItem{nullptr, (long long)ni, T, (int)pl.windows, pl.groups, 0};
+        pl.windows += T;
+        pl.groups += (T + VAD_WT - 1) / VAD_WT;
+    }
+    for (int k = pl.tab.n; k < WLX_VAD_MAX_BATCH; ++k) pl.tab.it[k] = VadItem{nullptr, 0, 0, 0, 0, 0};
+    if (pl.windows > cap) return set_error(WLX_ERR_ARG, "%s: %lld windows do not fit the output buffer (%lld)", who, pl.windows, (long long)cap);
+    return WLX_OK;
+}
+
+// the pass itself on v->stream: one launch of each kernel over the packed windows, one download, one wait. v->mu is held.
+static int vad_run_batch(wlx_vad* v, const VadPlan& pl, float* probs_out, float* device_ms_out) {
+    const int T = (int)pl.windows;
+    CK(hipEventRecord(v->ev0, v->stream));
+    hipLaunchKernelGGL(vad_frontend_batch_kernel, dim3(pl.groups), dim3(VAD_FE_THREADS), 0, v->stream, pl.tab, v->W, v->d_gx);
+    hipLaunchKernelGGL(vad_lstm_batch_kernel, dim3(pl.tab.n), dim3(512), 0, v->stream, pl.tab, v->d_gx, v->W.whhP, v->d_hs);
+    hipLaunchKernelGGL(vad_out_kernel, dim3((T + 3) / 4), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, T);
+    CK(hipGetLastError());
+    CK(hipEventRecord(v->ev1, v->stream));
+    CK(hipMemcpyAsync(v->h_probs, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+    CK(hipStreamSynchronize(v->stream));
+    memcpy(probs_out, v->h_probs, (size_t)T * sizeof(float));
+    if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_vad_probs_batch(wlx_vad* v, const float* pcm, const int64_t* n_samples, const int32_t* extra_zero_windows, int32_t n,
+                                       float* probs_out, int64_t cap, int32_t* n_windows_out, float* device_ms_out) {
+    if (!v || !pcm || !n_samples || !probs_out || !n_windows_out) return set_error(WLX_ERR_ARG, "wlx_vad_probs_batch: null argument");
+    VadPlan pl;
+    CKR(vad_plan("wlx_vad_probs_batch", n_samples, extra_zero_windows, n, cap, pl));
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (pl.windows > 0) {
+        CK(hipSetDevice(v->device));
+        (void)hipGetLastError();
+        CKR(vad_reserve(v, pl.samples));
+        CKR(vad_reserve_windows(v, pl.windows));
+    }
+    for (int i = 0; i < n; ++i) n_windows_out[i] = pl.T[i];
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (pl.windows == 0) return WLX_OK;
+    // the segments lie back to back in `pcm`: one copy to the pinned buffer, one to the device, and the table points into it
+    if (pl.samples > 0) {
+        memcpy(v->h_pin, pcm, (size_t)pl.samples * sizeof(float));
+        CK(hipMemcpyAsync(v->d_pcm, v->h_pin, (size_t)pl.samples * sizeof(float), hipMemcpyHostToDevice, v->stream));
+    }
+    std::vector<long long> off(n + 1, 0);
+    for (int i = 0; i < n; ++i) off[i + 1] = off[i] + n_samples[i];
+    for (int k = 0; k < pl.tab.n; ++k) pl.tab.it[k].pcm = v->d_pcm + off[pl.src[k]];
+    return vad_run_batch(v, pl, probs_out, device_ms_out);
+}
+
+extern "C" int32_t wlx_vad_probs_pcm_batch(wlx_vad* v, wlx_engine* e, int32_t slot, int32_t first_item, const int64_t* n_samples,
+                                           const int32_t* extra_zero_windows, int32_t n, float* probs_out, int64_t cap,
+                                           int32_t* n_windows_out, float* device_ms_out) {
+    if (!v || !e || !n_samples || !probs_out || !n_windows_out) return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm_batch: null argument");
+    if (e->device != v->device)
+        return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm_batch: the engine lives on device %d, the VAD model on %d", e->device, v->device);
+    VadPlan pl;
+    CKR(vad_plan("wlx_vad_probs_pcm_batch", n_samples, extra_zero_windows, n, cap, pl));
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (first_item < 0 || first_item + (int64_t)n > s->B)
+        return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm_batch: items [%d, %lld) outside the slot's %d", first_item, (long long)first_item + n, s->B);
+    for (int i = 0; i < n; ++i)
+        if (n_samples[i] > s->npcm[first_item + i])
+            return set_error(WLX_ERR_STATE, "wlx_vad_probs_pcm_batch: [0, %lld) is not resident (item %d holds %lld samples)", (long long)n_samples[i],
+                             first_item + i, (long long)s->npcm[first_item + i]);
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (pl.windows > 0) {
+        CK(hipSetDevice(v->device));
+        (void)hipGetLastError();
+        CKR(vad_reserve_windows(v, pl.windows));
+    }
+    for (int i = 0; i < n; ++i) n_windows_out[i] = pl.T[i];
+    if (device_ms_out) *device_ms_out = 0.0f;
+    if (pl.windows == 0) return WLX_OK;
+    if (!s->ev_pcm) CK(hipEventCreateWithFlags(&s->ev_pcm, hipEventDisableTiming));
+    CK(hipEventRecord(s->ev_pcm, s->stream));                 // whatever wrote the items' PCM on the slot's stream ...
+    CK(hipStreamWaitEvent(v->stream, s->ev_pcm, 0));          // ... is finished before the gate reads it
+    // (an item with n == 0 and extra windows reads no sample: its pointer is never dereferenced, s->pcm may still be null)
+    for (int k = 0; k < pl.tab.n; ++k)
+        pl.tab.it[k].pcm = s->pcm ? s->pcm + (size_t)(first_item + pl.src[k]) * s->pcm_cap : nullptr;
+    return vad_run_batch(v, pl, probs_out, device_ms_out);
 }
 
 // ------------------------------------------------------------------ host: hysteresis segmentation of the probabilities

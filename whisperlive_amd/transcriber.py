@@ -475,6 +475,78 @@ class WhisperModelHIP:
         slot._enc_generation += 1
         return EncoderOutput(slot, n, slot._enc_generation)
 
+    def speech_timestamps_batch(self, audios: Sequence[np.ndarray], options_list: Sequence[Optional[VadOptions]]):
+        """The speech ranges of every audio from ONE pass of the gate (vad.get_speech_timestamps_many) when the gate is the Silero
+        network on the GPU; None otherwise (the energy gate, an ONNX session, a test double: the caller keeps its per-item loop)."""
+        vm = self._vad_model()
+        if not isinstance(vm, _vad.SileroHIPModel):
+            return None
+        return _vad.get_speech_timestamps_many(audios, options_list, vm, self.feature_extractor.sampling_rate)
+
+    def encode_audio_batch_gated(self, audios: Sequence[np.ndarray], options_list: Sequence[Optional[VadOptions]]):
+        """`encode_audio_batch` with the VAD gate in front, the whole front half of a worker batch on the device
+        (whisper_live/batch_inference.py:236-271): every audio is uploaded ONCE into its slot item (pcm_put), one pass of the gate reads
+        the gated items there (probs_pcm_many; options_list[i] None = no gate for item i), the segmentation runs on the host, and the
+        features of a gated item with speech are cut out of its resident PCM (wlx_logmel_chunks, bit-identical to the log-mel of the
+        concatenated ranges). Items without a gate, and gated items in which no speech was found, keep their whole audio — the worker's
+        `if chunks:` rule. Then ONE encoder launch chain.
+        -> (EncoderOutput, counts): counts[i] = samples of audio i behind the gate; the encoder items are the audios with a non-zero
+        count, in order (an empty audio has nothing to encode). None when the device route does not apply — the gate is not a
+        SileroHIPModel, or the library refuses a request (more than WLX_LM_MAXRANGES speech ranges in one item) — which is decided
+        before any feature or encoder launch: the caller takes its host route."""
+        from ._lib import LM_MAXRANGES
+        gated = [i for i, o in enumerate(options_list) if o is not None]
+        vm = None
+        if gated:
+            vm = self._vad_model()
+            if not isinstance(vm, _vad.SileroHIPModel):
+                return None
+        xs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in audios]
+        live = [i for i, x in enumerate(xs) if x.shape[0] > 0]          # slot item k holds audio live[k]
+        counts = [0] * len(xs)
+        slot = self._slot()
+        if not all(hasattr(slot, m) for m in ("pcm_put", "logmel_chunks", "logmel_resident")):
+            return None                                                  # an engine without the resident-PCM entry points
+        if len(live) > slot.max_batch:
+            raise ValueError(f"batch {len(live)} exceeds the slot's max_batch {slot.max_batch}")
+        if not live:
+            return EncoderOutput(slot, 0, slot._enc_generation), counts
+        sr = self.feature_extractor.sampling_rate
+        try:
+            for k, i in enumerate(live):
+                slot.pcm_put(xs[i], item=k)
+            ranges: Dict[int, List[Tuple[int, int]]] = {}
+            # ONE pass of the gate over slot items [first gated, last gated]; an item in between that asked for no gate takes part
+            # with 0 samples (a single all-zero window, dropped below) instead of splitting the pass in two
+            ks = [k for k, i in enumerate(live) if options_list[i] is not None]
+            if ks:
+                span = range(ks[0], ks[-1] + 1)
+                rows = vm.probs_pcm_many(slot, [xs[live[k]].shape[0] if options_list[live[k]] is not None else 0 for k in span],
+                                         first_item=ks[0])
+                for k in ks:
+                    a = live[k]
+                    sp = _vad.speech_segments_from_probs_native(rows[k - ks[0]], xs[a].shape[0], options_list[a], sr)
+                    if sp:
+                        ranges[k] = [(c["start"], c["end"]) for c in sp]
+            if any(len(r) > LM_MAXRANGES for r in ranges.values()):
+                return None
+            frames = []
+            for k, i in enumerate(live):
+                if k in ranges:
+                    frames.append(slot.logmel_chunks([ranges[k]], src_item=k, first_item=k)[0])
+                    counts[i] = sum(b - a for a, b in ranges[k])
+                else:
+                    frames.append(slot.logmel_resident(item=k))
+                    counts[i] = xs[i].shape[0]
+        except _WlxError as e:
+            if e.code == _ERR_ARG:
+                return None
+            raise
+        n = len(live)
+        slot.encode(n, seek=[0] * n, seg=[min(t, 3000) for t in frames])
+        slot._enc_generation += 1
+        return EncoderOutput(slot, n, slot._enc_generation), counts
+
     # ---- transcribe (transcriber_faster_whisper.py:692-968)
     def transcribe(self, audio: np.ndarray, language: Optional[str] = None, task: str = "transcribe",
                    log_progress: bool = False, beam_size: int = 5, best_of: int = 5, patience: float = 1,

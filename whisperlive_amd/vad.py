@@ -170,6 +170,54 @@ class SileroHIPModel:
         self.last_device_ms = float(ms.value)
         return probs[: n_out.value].copy()
 
+    def _many(self, counts: Sequence[int], call) -> List[np.ndarray]:
+        """the batch entry points' shared host side: `counts` samples per item -> one probability row per item. Lists longer than
+        WLX_VAD_MAX_BATCH go out as consecutive calls; `call(first, n, counts64, extra32, probs, cap, n_windows, ms)` makes one."""
+        import ctypes as C
+        counts = [int(c) for c in counts]
+        out: List[np.ndarray] = []
+        total_ms = 0.0
+        width = self._lib.VAD_MAX_BATCH
+        for a in range(0, len(counts), width):
+            part = counts[a:a + width]
+            cnt = np.asarray(part, dtype=np.int64)
+            extra = np.asarray([1 if c % WINDOW == 0 else 0 for c in part], dtype=np.int32)     # as probs_resident: pad to the NEXT multiple
+            cap = int(sum(-(-c // WINDOW) for c in part) + int(extra.sum()))
+            probs = np.empty(max(cap, 1), np.float32)
+            nw = np.zeros(len(part), np.int32)
+            ms = C.c_float(0.0)
+            self._lib.check(call(a, len(part), cnt.ctypes.data_as(C.POINTER(C.c_int64)), extra.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 probs.ctypes.data_as(C.POINTER(C.c_float)), cap, nw.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms)))
+            total_ms += float(ms.value)
+            ends = np.cumsum(nw)
+            out.extend(probs[e - t:e].copy() for e, t in zip(ends.tolist(), nw.tolist()))
+        self.last_device_ms = total_ms
+        return out
+
+    def probs_many(self, audios: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """One row per UNPADDED audio, each equal to `self(np.pad(x, (0, 512 - n % 512)))`, from one pass over the network per 64 items:
+        one upload, one launch of each kernel, one download (include/wlx.h wlx_vad_probs_batch)."""
+        import ctypes as C
+        xs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in audios]
+        starts = np.concatenate([[0], np.cumsum([x.shape[0] for x in xs])]).astype(np.int64) if xs else np.zeros(1, np.int64)
+        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
+        if flat.shape[0] == 0:
+            flat = np.zeros(1, np.float32)                  # a valid pointer for a batch of empty audios (nothing is read)
+        base = flat.ctypes.data
+
+        def call(first, n, cnt, extra, probs, cap, nw, ms):
+            src = C.cast(C.c_void_p(base + 4 * int(starts[first])), C.POINTER(C.c_float))
+            return self.lib.wlx_vad_probs_batch(self.handle, src, cnt, extra, n, probs, cap, nw, ms)
+        return self._many([x.shape[0] for x in xs], call)
+
+    def probs_pcm_many(self, slot, counts: Sequence[int], first_item: int = 0) -> List[np.ndarray]:
+        """`probs_pcm(slot, 0, counts[i], item=first_item + i)` for every i from one pass per 64 items: the samples are read where
+        pcm_put / put_frames left them, nothing is uploaded (include/wlx.h wlx_vad_probs_pcm_batch)."""
+        def call(first, n, cnt, extra, probs, cap, nw, ms):
+            return self.lib.wlx_vad_probs_pcm_batch(self.handle, slot.engine._h, slot.sid, int(first_item) + first, cnt, extra, n,
+                                                    probs, cap, nw, ms)
+        return self._many(counts, call)
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.wlx_vad_destroy(self.handle)
@@ -435,6 +483,15 @@ def get_speech_timestamps_pcm(slot, n: int, vad_options: Optional[VadOptions] = 
     opt = vad_options or VadOptions()
     probs = model.probs_pcm(slot, 0, n, item=item)
     return speech_segments_from_probs_native(probs, int(n), opt, sampling_rate)
+
+
+def get_speech_timestamps_many(audios: Sequence[np.ndarray], options_list: Sequence[Optional[VadOptions]], model,
+                               sampling_rate: int = 16000) -> List[List[Dict[str, int]]]:
+    """`get_speech_timestamps(audios[i], options_list[i], model=model)` for every i with ONE pass over the network for all of them
+    (`model.probs_many`, a SileroHIPModel); the segmentation runs per item on the host as before."""
+    probs = model.probs_many(audios)
+    return [speech_segments_from_probs_native(p, int(a.shape[0]), o or VadOptions(), sampling_rate)
+            for p, a, o in zip(probs, audios, options_list)]
 
 
 def collect_chunks(audio: np.ndarray, chunks: List[Dict[str, int]], sampling_rate: int = 16000,
