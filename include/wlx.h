@@ -265,6 +265,25 @@ int32_t wlx_align(wlx_engine* e, int32_t slot, int32_t item, const int32_t* toke
                   int32_t* text_indices, int32_t* time_indices, int32_t path_cap, int32_t* n_path_out,
                   float* text_token_probs);
 
+/* The same for a group of up to WLX_ALIGN_MAX_BATCH entries in ONE launch sequence with ONE wait at its end: entry i means what wlx_align
+ * means for encoder item items[i] (NULL = identity; an item may repeat), the tokens at tokens[i * tokens_stride .. + n_tokens[i]) and
+ * num_frames[i]. The teacher-forced pass runs entry by entry, 64 rows at a time, with the kernels of wlx_align (text_token_probs are
+ * bit-identical to its); softmax / normalise / median / head mean and the DTW run ON THE DEVICE for all entries at once (csrc/align.hip),
+ * in float32: the path of entry i is exactly the DTW of the float32 cost matrix the device computed for it. Outputs of entry i at
+ * i * path_stride (text_indices, time_indices; n_path_out[i] steps) and i * probs_stride. n == 0 launches nothing.
+ * WLX_ERR_ARG / WLX_ERR_STATE before any launch, nothing written: n outside 0..WLX_ALIGN_MAX_BATCH, a null pointer, an item that is
+ * not encoded, n_tokens[i] outside n_sot + 3 .. 448, a bad head / token / eot (as wlx_align), median_filter_width even or outside
+ * 1..WLX_ALIGN_MAX_MEDIAN, path_stride < n_tokens[i] - 1 - n_sot + frames of entry i (the longest path), probs_stride < n_tokens[i] - n_sot - 2.
+ * WLX_ERR_NOMEM before any launch if the score scratch (n_heads * n_tokens[i] * 1536 floats per entry, grown on demand) cannot be had. */
+#define WLX_ALIGN_MAX_BATCH 64
+#define WLX_ALIGN_MAX_MEDIAN 15
+int32_t wlx_align_batch(wlx_engine* e, int32_t slot, int32_t n, const int32_t* items,
+                        const int32_t* tokens, const int32_t* n_tokens, int32_t tokens_stride, int32_t n_sot,
+                        const int32_t* num_frames, int32_t median_filter_width,
+                        const int32_t* heads, int32_t n_heads, int32_t eot,
+                        int32_t* text_indices, int32_t* time_indices, int32_t path_stride, int32_t* n_path_out,
+                        float* text_token_probs, int32_t probs_stride);
+
 /* ---- voice-activity probabilities (Silero VAD, 16 kHz) — PRODUCT entry points: the VAD gate of every use_vad session ----
  * Replaces the model call inside faster_whisper.vad.get_speech_timestamps (onnxruntime, one CPU thread) that the
  * reference makes before every transcription when the client asks for VAD:
@@ -573,6 +592,20 @@ int32_t wlx_debug_resample(int32_t device, const void* frames, int64_t n_frames,
 int32_t wlx_debug_resample_timed(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
                                  int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out,
                                  float* kernel_ms_out);
+
+/* Word alignment's post-processing kernels (csrc/align.hip), same conventions; n <= WLX_ALIGN_MAX_BATCH entries packed back to back, outputs
+ * copied in AND out. wlx_debug_dtw: the DTW kernel alone on caller matrices x [N[e]][M[e]] float32 (1 <= N <= 448, 1 <= M <= 1500,
+ * path_stride >= N + M); path rows at e * path_stride, n_path[e] steps. wlx_debug_align_post: the whole sequence on caller scores
+ * [n_heads][n_tok[e]][1536] per entry (the layout of dec_align_scores_kernel; frames past nf[e] are not read): cost_out is the DTW cost
+ * matrix packed [n_tok[e] - 1 - n_sot][nf[e]], the path is the DTW of exactly that matrix. WLX_ERR_ARG before any launch: n outside
+ * 0..64, a width that is even or outside 1..15, nf outside 1..1500, n_tok outside n_sot + 3 .. 448, path_stride below N + nf. */
+int32_t wlx_debug_dtw(int32_t device, const float* x, int32_t n, const int32_t* N, const int32_t* M, int32_t* text_indices,
+                      int32_t* time_indices, int32_t path_stride, int32_t* n_path);
+int32_t wlx_debug_align_post(int32_t device, const float* scores, int32_t n, int32_t n_heads, const int32_t* n_tok, int32_t n_sot,
+                             const int32_t* nf, int32_t median_filter_width, float* cost_out, int32_t* text_indices,
+                             int32_t* time_indices, int32_t path_stride, int32_t* n_path);
+/* HIP-event times of the slot's last wlx_align_batch: the decoder passes with their score capture, and everything behind them. */
+int32_t wlx_debug_align_timings(wlx_engine* e, int32_t slot, float* pass_ms, float* post_ms);
 
 #ifdef __cplusplus
 }

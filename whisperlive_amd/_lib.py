@@ -15,12 +15,12 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
     "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
-    "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_timings_get", "wlx_sync",
+    "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_align_batch", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
     "wlx_logmel_chunks", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
@@ -33,6 +33,7 @@ EXPORTS = [
     "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
     "wlx_debug_resample", "wlx_debug_resample_timed",
+    "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings",
 ]
 
 
@@ -99,6 +100,8 @@ class wlx_spk_spec(C.Structure):
 ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
 SPK_MAX_BATCH = 64      # wlx.h WLX_SPK_MAX_BATCH: segments of one wlx_spk_embed_batch call
 VAD_MAX_BATCH = 64      # wlx.h WLX_VAD_MAX_BATCH: sequences of one wlx_vad_probs_batch / wlx_vad_probs_pcm_batch call
+ALIGN_MAX_BATCH = 64    # wlx.h WLX_ALIGN_MAX_BATCH: entries of one wlx_align_batch call
+ALIGN_MAX_MEDIAN = 15   # wlx.h WLX_ALIGN_MAX_MEDIAN: the widest median filter the device post-processing serves
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
 ERR_STATE = 4           # wlx_status WLX_ERR_STATE
 LM_MAXRANGES = 256      # wlx.h WLX_LM_MAXRANGES: ranges per chunk of wlx_logmel_chunks / wlx_logmel_ring
@@ -267,6 +270,7 @@ def load() -> C.CDLL:
     lib.wlx_generate_ex.argtypes = [vp, i32, i32, i32p, i32p, i32p, i32, C.POINTER(wlx_gen_opts), i32p, i32, i32p, f32p, f32p]
     lib.wlx_detect_language.argtypes = [vp, i32, i32, i32, i32p, i32, f32p]
     lib.wlx_align.argtypes = [vp, i32, i32, i32p, i32, i32, i32, i32, i32p, i32, i32, i32p, i32p, i32, i32p, f32p]
+    lib.wlx_align_batch.argtypes = [vp, i32, i32, i32p, i32p, i32p, i32, i32, i32p, i32, i32p, i32, i32, i32p, i32p, i32, i32p, f32p, i32]
     lib.wlx_timings_get.argtypes = [vp, i32, C.POINTER(wlx_timings)]
     lib.wlx_sync.argtypes = [vp, i32]
     lib.wlx_vad_create.argtypes = [C.POINTER(wlx_vad_weights), i32, C.POINTER(vp)]
@@ -325,6 +329,9 @@ def load() -> C.CDLL:
     lib.wlx_debug_gemm.argtypes = [i32, C.POINTER(wlx_debug_gemm_args), u16p, f32p, f32p, f32p, u16p, f32p, u16p, u16p, i32p]
     lib.wlx_debug_resample.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p]
     lib.wlx_debug_resample_timed.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p, f32p]
+    lib.wlx_debug_dtw.argtypes = [i32, f32p, i32, i32p, i32p, i32p, i32p, i32, i32p]
+    lib.wlx_debug_align_post.argtypes = [i32, f32p, i32, i32, i32p, i32, i32p, i32, f32p, i32p, i32p, i32, i32p]
+    lib.wlx_debug_align_timings.argtypes = [vp, i32, f32p, f32p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):

@@ -112,13 +112,26 @@ class BatchedInferencePipeline:
                      seek=int(chunk_metadata["start_time"] * self.model.frames_per_second))
                 for subsegment in subsegments])
         if options.word_timestamps:
-            # the existing one-item alignment (wlx_align), chunk after chunk, with the last-speech time carried along
+            # chunk after chunk (the route add_word_timestamps takes where it is not given a group form), with the last-speech time carried along
             def align_fn(text_tokens, _num_frames, window):
                 r = self.model.model.align(encoder_output.select([window]), tokenizer.sot_sequence, [text_tokens],
                                            segment_sizes[window])[0]
                 pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
                 return pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)
 
+            # ... or, where the model's align takes a group, every chunk that has text in ONE call (wlx_align_batch), as the reference does
+            def align_many_fn(requests):
+                res = self.model.model.align(encoder_output.select([r[2] for r in requests]), tokenizer.sot_sequence,
+                                             [r[0] for r in requests], [segment_sizes[r[2]] for r in requests])
+                out = []
+                for r in res:
+                    pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
+                    out.append((pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)))
+                return out
+
+            # (handed over on the function, the form add_word_timestamps also takes: the call keeps the nine positional arguments a
+            # stand-in for add_word_timestamps is written against)
+            align_fn.align_many = align_many_fn
             self.last_speech_timestamp = _wt.add_word_timestamps(
                 segmented_outputs, tokenizer, align_fn, 0, self.model.tokens_per_second, self.model.frames_per_second,
                 options.prepend_punctuations, options.append_punctuations, self.last_speech_timestamp)

@@ -8,6 +8,7 @@
 #include <tuple>
 #include <vector>
 #include "../../include/wlx.h"
+#include "align.h"
 #include "decoder.h"
 #include "host.h"
 
@@ -105,6 +106,13 @@ struct Slot {
     struct AlignCapture { float* scores; const int32_t* heads; int n_heads, n_tok, row0, item; }* align = nullptr;
     float* align_scores = nullptr; size_t align_cap = 0;     // [n_heads][n_tok][1536] fp32, grown on demand (so owned by name, not by `allocs`)
     int* d_align_tgt = nullptr; float* d_align_prob = nullptr;   // [448]
+    // wlx_align_batch (allocated at its first call): pinned staging laid out by align_staging (entry table, per-chunk row tables and targets in;
+    // paths, counts and probabilities out), the device entry table, and ONE device scratch for stats | cost matrices | DTW traces, grown on demand
+    unsigned char* h_align = nullptr;
+    AlignEnt* d_align_ent = nullptr;
+    float* align_post = nullptr; size_t align_post_cap = 0;   // in floats (owned by name, like align_scores)
+    hipEvent_t ev_al0 = nullptr, ev_al1 = nullptr, ev_al2 = nullptr;
+    float align_pass_ms = 0.f, align_post_ms = 0.f;
 };
 
 // Device-resident PCM ring of one client stream (include/wlx.h: wlx_ring_*; engine.hip). Samples [base, base + resident) of the

@@ -183,6 +183,8 @@ static void slot_free(Slot* s) {
         }
     }
     if (s->align_scores) (void)hipFree(s->align_scores);
+    if (s->align_post) (void)hipFree(s->align_post);
+    for (hipEvent_t ev : {s->ev_al0, s->ev_al1, s->ev_al2}) if (ev) (void)hipEventDestroy(ev);
     for (auto& kv : s->graphs) (void)hipGraphExecDestroy(kv.second);
     for (void* p : s->allocs) (void)hipFree(p);
     for (void* p : s->host_allocs) (void)hipHostFree(p);

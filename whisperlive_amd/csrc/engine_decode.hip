@@ -933,3 +933,175 @@ extern "C" int32_t wlx_align(wlx_engine* e, int32_t slot, int32_t item, const in
     for (int i = 0; i < n_text; ++i) text_token_probs[i] = probs[n_sot + i];
     return WLX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// wlx_align_batch: the same alignment for a group of entries. The decoder passes run entry by entry with wlx_align's own launches (one
+// entry's rows per pass: packing entries into a pass would change the row count, the GEMV dispatch and the bits of text_token_probs); what
+// changes is everything around them. Every table of every chunk is written to pinned staging BEFORE the first launch, so nothing between
+// the entries or chunks waits for the stream; the raw scores of all entries stay on the device, back to back, and align.hip turns them into
+// cost matrices and DTW paths in one launch sequence; paths, counts and probabilities land in pinned memory and the call waits once.
+namespace {
+
+constexpr int AL_PS = 1952;             // path row of the pinned result area (>= 446 + 1500, the longest path)
+constexpr int AL_CHUNKS = (WLX_T_TEXT + 63) / 64;
+constexpr int AL_CHUNK_INTS = 64 * 5 + 8;       // [token | pos | cache | ancrow : rows each | group_item : groups | target : rows], rows <= 64
+struct AlignStaging {
+    AlignEnt* ent; int* rows; int32_t *ti, *fi, *np; float* probs;
+    size_t bytes;
+};
+AlignStaging align_staging(unsigned char* base) {
+    AlignStaging g{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { unsigned char* p = base + off; off += (bytes + 63) / 64 * 64; return p; };
+    g.ent = reinterpret_cast<AlignEnt*>(take(sizeof(AlignEnt) * WLX_ALIGN_MAX_BATCH));
+    g.rows = reinterpret_cast<int*>(take(sizeof(int) * (size_t)WLX_ALIGN_MAX_BATCH * AL_CHUNKS * AL_CHUNK_INTS));
+    g.ti = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * (size_t)WLX_ALIGN_MAX_BATCH * AL_PS));
+    g.fi = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * (size_t)WLX_ALIGN_MAX_BATCH * AL_PS));
+    g.np = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * WLX_ALIGN_MAX_BATCH));
+    g.probs = reinterpret_cast<float*>(take(sizeof(float) * (size_t)WLX_ALIGN_MAX_BATCH * WLX_T_TEXT));
+    g.bytes = off;
+    return g;
+}
+
+// a device buffer owned by name, grown on demand: WLX_ERR_NOMEM (and an empty buffer) when the larger one cannot be had
+int grow_floats(Slot* s, float** buf, size_t* cap, size_t need, const char* what) {
+    if (need <= *cap) return WLX_OK;
+    CK(hipStreamSynchronize(s->stream));
+    if (*buf) CK(hipFree(*buf));
+    *buf = nullptr; *cap = 0;
+    if (hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        return set_error(WLX_ERR_NOMEM, "align: %zu bytes of %s cannot be allocated", need * sizeof(float), what);
+    }
+    *cap = need;
+    return WLX_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t wlx_align_batch(wlx_engine* e, int32_t slot, int32_t n, const int32_t* items, const int32_t* tokens, const int32_t* n_tokens,
+                                   int32_t tokens_stride, int32_t n_sot, const int32_t* num_frames, int32_t median_filter_width,
+                                   const int32_t* heads, int32_t n_heads, int32_t eot, int32_t* text_indices, int32_t* time_indices,
+                                   int32_t path_stride, int32_t* n_path_out, float* text_token_probs, int32_t probs_stride) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (n < 0 || n > WLX_ALIGN_MAX_BATCH) return set_error(WLX_ERR_ARG, "align: %d entries outside 0..%d", n, WLX_ALIGN_MAX_BATCH);
+    if (!tokens || !n_tokens || !num_frames || !heads || !text_indices || !time_indices || !n_path_out || !text_token_probs)
+        return set_error(WLX_ERR_ARG, "null argument");
+    if (n_sot < 1) return set_error(WLX_ERR_ARG, "align: a start sequence of %d", n_sot);
+    if (n_heads < 1 || n_heads > e->spec.dec_layers * e->H) return set_error(WLX_ERR_ARG, "align: bad head count");
+    for (int i = 0; i < n_heads; ++i)
+        if (heads[2 * i] < 0 || heads[2 * i] >= e->spec.dec_layers || heads[2 * i + 1] < 0 || heads[2 * i + 1] >= e->H)
+            return set_error(WLX_ERR_ARG, "align: head (%d, %d) out of range", heads[2 * i], heads[2 * i + 1]);
+    if (eot < 1 || eot > e->spec.vocab) return set_error(WLX_ERR_ARG, "align: bad eot");
+    if (median_filter_width < 1 || median_filter_width > WLX_ALIGN_MAX_MEDIAN || (median_filter_width & 1) == 0)
+        return set_error(WLX_ERR_ARG, "align: filter width %d must be odd in 1..%d", median_filter_width, WLX_ALIGN_MAX_MEDIAN);
+    AlignEnt ent[WLX_ALIGN_MAX_BATCH];
+    int item_of[WLX_ALIGN_MAX_BATCH];
+    for (int i = 0; i < n; ++i) {
+        const int item = items ? items[i] : i, nt = n_tokens[i];
+        if (item < 0 || item >= s->enc_batch) return set_error(WLX_ERR_STATE, "align: entry %d: item %d not encoded", i, item);
+        if (nt < n_sot + 3 || nt > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "align: entry %d: %d tokens with a start sequence of %d", i, nt, n_sot);
+        if (tokens_stride < nt) return set_error(WLX_ERR_ARG, "align: tokens_stride %d below the %d tokens of entry %d", tokens_stride, nt, i);
+        const int32_t* tk = tokens + (size_t)i * tokens_stride;
+        for (int k = 0; k < nt; ++k) if (tk[k] < 0 || tk[k] >= e->spec.vocab) return set_error(WLX_ERR_ARG, "align: entry %d: token out of vocabulary", i);
+        const int nf = std::min(std::max(num_frames[i] / 2, 1), (int)WLX_T_AUDIO);
+        ent[i] = AlignEnt{};
+        ent[i].n_tok = nt; ent[i].nf = nf; ent[i].N = nt - 1 - n_sot;
+        item_of[i] = item;
+        if (path_stride < ent[i].N + nf) return set_error(WLX_ERR_ARG, "align: path_stride %d below the longest path (%d) of entry %d", path_stride, ent[i].N + nf, i);
+        if (probs_stride < nt - n_sot - 2) return set_error(WLX_ERR_ARG, "align: probs_stride %d below the %d text tokens of entry %d", probs_stride, nt - n_sot - 2, i);
+    }
+    if (n == 0) return WLX_OK;
+    AlignPlan plan{};
+    align_layout(ent, n, n_heads, &plan);
+    CK(hipSetDevice(e->device));
+    hipStream_t st = s->stream;
+    // ---- memory, all of it before the first launch
+    if (!s->h_align) {
+        CKR(halloc(s->host_allocs, &s->h_align, align_staging(nullptr).bytes));
+        CKR(dalloc(s->allocs, &s->d_align_ent, (size_t)WLX_ALIGN_MAX_BATCH, false));
+    }
+    for (hipEvent_t* ev : {&s->ev_al0, &s->ev_al1, &s->ev_al2}) if (!*ev) CK(hipEventCreate(ev));
+    CKR(grow_floats(s, &s->align_scores, &s->align_cap, plan.score_floats, "alignment scores"));
+    const size_t post_need = plan.stat_floats + plan.x_floats + plan.trace_words;
+    CKR(grow_floats(s, &s->align_post, &s->align_post_cap, post_need, "alignment scratch"));
+    float* d_stats = s->align_post;
+    float* d_x = d_stats + plan.stat_floats;
+    unsigned* d_trace = reinterpret_cast<unsigned*>(d_x + plan.x_floats);
+    // ---- every table of the call into the pinned staging (free: the previous call on this slot ended with a wait for the stream)
+    const AlignStaging g = align_staging(s->h_align);
+    memcpy(g.ent, ent, sizeof(AlignEnt) * n);
+    for (int i = 0; i < n; ++i) {
+        const int nt = ent[i].n_tok, n_text = nt - n_sot - 2, crow = item_of[i] * s->R;
+        const int32_t* tk = tokens + (size_t)i * tokens_stride;
+        for (int c0 = 0, c = 0; c0 < nt; c0 += 64, ++c) {
+            const int rows = std::min(64, nt - c0), groups = (rows + 15) / 16;
+            int* h = g.rows + ((size_t)i * AL_CHUNKS + c) * AL_CHUNK_INTS;
+            int* tgt = h + 4 * rows + groups;
+            for (int r = 0; r < rows; ++r) {
+                const int p = c0 + r;                       // logits at position p predict tokens[p + 1]
+                h[r] = tk[p]; h[rows + r] = p; h[2 * rows + r] = crow; h[3 * rows + r] = crow;
+                tgt[r] = (p >= n_sot && p < n_sot + n_text) ? tk[p + 1] : -1;
+            }
+            for (int gi = 0; gi < groups; ++gi) h[4 * rows + gi] = item_of[i];
+        }
+    }
+    // ---- one launch sequence
+    int rc = WLX_OK;
+    auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == WLX_OK) rc = WLX_ERR_HIP; return rc == WLX_OK; };
+    ok(hipEventRecord(s->ev_al0, st));
+    ok(hipMemcpyAsync(s->d_align_ent, g.ent, sizeof(AlignEnt) * n, hipMemcpyHostToDevice, st));
+    Slot::AlignCapture cap{s->align_scores, heads, n_heads, 0, 0, 0};
+    s->align = &cap;
+    for (int i = 0; i < n && rc == WLX_OK; ++i) {
+        const int nt = ent[i].n_tok, crow = item_of[i] * s->R;
+        // identity ancestry of the entry's cache row (what wlx_align uploads: 448 times its own row)
+        if (!ok(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(s->d_anc + (size_t)crow * WLX_T_TEXT), (unsigned short)crow, WLX_T_TEXT, st))) break;
+        cap.scores = s->align_scores + ent[i].score_off; cap.n_tok = nt; cap.item = item_of[i];
+        for (int c0 = 0, c = 0; c0 < nt && rc == WLX_OK; c0 += 64, ++c) {
+            const int rows = std::min(64, nt - c0), groups = (rows + 15) / 16;
+            const int* h = g.rows + ((size_t)i * AL_CHUNKS + c) * AL_CHUNK_INTS;
+            s->anc_ident = rows == 1 && crow == 0;          // upload_rows' rule (ancrow[r] == r for every row) on these tables
+            if (upload_row_tables(s, s->step, h, rows, groups) != WLX_OK) { rc = WLX_ERR_HIP; break; }
+            cap.row0 = c0;
+            decoder_pass(e, s, s->step, rows, 16, groups, true, false);
+            if (!ok(hipMemcpyAsync(s->d_align_tgt, h + 4 * rows + groups, (size_t)rows * 4, hipMemcpyHostToDevice, st))) break;
+            launch_token_prob_rows(s->logits, s->ldl, eot, rows, s->d_align_tgt, s->d_align_prob, st);
+            ok(hipMemcpyAsync(g.probs + (size_t)i * WLX_T_TEXT + c0, s->d_align_prob, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    s->align = nullptr;
+    if (rc == WLX_OK) {
+        ok(hipEventRecord(s->ev_al1, st));
+        launch_align_cost(s->d_align_ent, n, n_heads, n_sot, median_filter_width, plan, s->align_scores, d_stats, d_x, st);
+        launch_align_dtw(s->d_align_ent, n, plan.max_N, d_x, d_trace, g.ti, g.fi, AL_PS, g.np, st);
+        ok(hipEventRecord(s->ev_al2, st));
+    }
+    const hipError_t waited = hipStreamSynchronize(st);     // the one wait of the call
+    if (rc != WLX_OK) return set_error(rc, "align: a launch of the batch failed");
+    CK(waited);
+    CK(hipGetLastError());
+    CK(hipEventElapsedTime(&s->align_pass_ms, s->ev_al0, s->ev_al1));
+    CK(hipEventElapsedTime(&s->align_post_ms, s->ev_al1, s->ev_al2));
+    for (int i = 0; i < n; ++i) {
+        const int np = g.np[i], n_text = ent[i].n_tok - n_sot - 2;
+        if (np < 0 || np > path_stride) return set_error(WLX_ERR_HIP, "align: entry %d came back with a path of %d steps", i, np);
+        memcpy(text_indices + (size_t)i * path_stride, g.ti + (size_t)i * AL_PS, (size_t)np * 4);
+        memcpy(time_indices + (size_t)i * path_stride, g.fi + (size_t)i * AL_PS, (size_t)np * 4);
+        n_path_out[i] = np;
+        for (int k = 0; k < n_text; ++k) text_token_probs[(size_t)i * probs_stride + k] = g.probs[(size_t)i * WLX_T_TEXT + n_sot + k];
+    }
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_debug_align_timings(wlx_engine* e, int32_t slot, float* pass_ms, float* post_ms) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    if (!pass_ms || !post_ms) return set_error(WLX_ERR_ARG, "null argument");
+    *pass_ms = sg_.s->align_pass_ms;
+    *post_ms = sg_.s->align_post_ms;
+    return WLX_OK;
+}

@@ -1,9 +1,11 @@
 // kernel_hooks.hip — kernel-level test hooks of the Whisper kernels: wlx_debug_layernorm, wlx_debug_attn_encoder,
-// wlx_debug_dec_cross_attn, wlx_debug_dec_self_attn (include/wlx.h, below the TEST / PROFILING line).
+// wlx_debug_dec_cross_attn, wlx_debug_dec_self_attn, wlx_debug_gemm, wlx_debug_dtw, wlx_debug_align_post (include/wlx.h, below the
+// TEST / PROFILING line).
 // Same conventions as the translation hooks (mt_engine.hip wlx_mt_debug_attn): host arrays in, ONE call of the production
 // launcher on a private non-blocking stream, host arrays out. Outputs are copied in AND out, so bytes no thread owns come back
 // unchanged. Every shape a launcher cannot serve is refused (WLX_ERR_ARG) before anything is allocated or launched. No engine
 // or slot is needed, and no product code path runs differently because these exist.
+#include "align.h"
 #include "decoder.h"
 #include "host.h"
 
@@ -314,5 +316,85 @@ extern "C" int32_t wlx_debug_gemm(int32_t device, const wlx_debug_gemm_args* a, 
         CKR(S.download(h16(kout), dK, (size_t)a->k_len));
         CKR(S.download(h16(vt), dV, (size_t)a->v_len));
     }
+    return S.finish();
+}
+
+// ---- word alignment's post-processing (align.hip). Both hooks take a ragged batch of up to WLX_ALIGN_MAX_BATCH entries packed back to back.
+static int align_hook_paths(HookScope& S, int n, int32_t* ti, int32_t* fi, int32_t path_stride, int32_t* n_path, int32_t** dti, int32_t** dfi,
+                            int32_t** dnp) {
+    CKR(S.upload(dti, ti, (size_t)n * path_stride));
+    CKR(S.upload(dfi, fi, (size_t)n * path_stride));
+    CKR(S.upload(dnp, n_path, (size_t)n));
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_debug_dtw(int32_t device, const float* x, int32_t n, const int32_t* N, const int32_t* M, int32_t* text_indices,
+                                 int32_t* time_indices, int32_t path_stride, int32_t* n_path) {
+    if (!x || !N || !M || !text_indices || !time_indices || !n_path) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 0 || n > WLX_ALIGN_MAX_BATCH) return set_error(WLX_ERR_ARG, "dtw: %d entries outside 0..%d", n, WLX_ALIGN_MAX_BATCH);
+    if (n == 0) return WLX_OK;
+    AlignEnt ent[WLX_ALIGN_MAX_BATCH];
+    for (int e = 0; e < n; ++e) {
+        // one thread per text row (<= 448 of them), the path buffer of the kernel holds N + M <= 2048 steps
+        if (N[e] < 1 || N[e] > AL_MAX_TOK || M[e] < 1 || M[e] > AL_MAX_NF)
+            return set_error(WLX_ERR_ARG, "dtw: entry %d is %d x %d, outside 1..%d x 1..%d", e, N[e], M[e], AL_MAX_TOK, AL_MAX_NF);
+        if (path_stride < N[e] + M[e]) return set_error(WLX_ERR_ARG, "dtw: path_stride %d below N + M = %d of entry %d", path_stride, N[e] + M[e], e);
+        ent[e] = AlignEnt{};
+        ent[e].N = N[e]; ent[e].nf = M[e]; ent[e].n_tok = 0;
+    }
+    AlignPlan plan{};
+    align_layout(ent, n, 0, &plan);
+    HookScope S;
+    CKR(S.begin(device));
+    AlignEnt* dent = nullptr; float* dx = nullptr; unsigned* dtr = nullptr;
+    int32_t *dti = nullptr, *dfi = nullptr, *dnp = nullptr;
+    CKR(S.upload(&dent, ent, (size_t)n));
+    CK(hipStreamSynchronize(S.st));             // (`ent` is this frame's memory)
+    CKR(S.upload(&dx, x, plan.x_floats));
+    CKR(S.upload(&dtr, (const unsigned*)nullptr, plan.trace_words));
+    CKR(align_hook_paths(S, n, text_indices, time_indices, path_stride, n_path, &dti, &dfi, &dnp));
+    launch_align_dtw(dent, n, plan.max_N, dx, dtr, dti, dfi, path_stride, dnp, S.st);
+    CKR(S.download(text_indices, dti, (size_t)n * path_stride));
+    CKR(S.download(time_indices, dfi, (size_t)n * path_stride));
+    CKR(S.download(n_path, dnp, (size_t)n));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_debug_align_post(int32_t device, const float* scores, int32_t n, int32_t n_heads, const int32_t* n_tok, int32_t n_sot,
+                                        const int32_t* nf, int32_t median_filter_width, float* cost_out, int32_t* text_indices,
+                                        int32_t* time_indices, int32_t path_stride, int32_t* n_path) {
+    if (!scores || !n_tok || !nf || !cost_out || !text_indices || !time_indices || !n_path) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 0 || n > WLX_ALIGN_MAX_BATCH) return set_error(WLX_ERR_ARG, "align_post: %d entries outside 0..%d", n, WLX_ALIGN_MAX_BATCH);
+    if (n_heads < 1 || n_heads > 65535 || n_sot < 1) return set_error(WLX_ERR_ARG, "align_post: n_heads %d outside 1..65535 / n_sot %d", n_heads, n_sot);
+    if (median_filter_width < 1 || median_filter_width > WLX_ALIGN_MAX_MEDIAN || (median_filter_width & 1) == 0)
+        return set_error(WLX_ERR_ARG, "align_post: filter width %d must be odd in 1..%d", median_filter_width, WLX_ALIGN_MAX_MEDIAN);
+    if (n == 0) return WLX_OK;
+    AlignEnt ent[WLX_ALIGN_MAX_BATCH];
+    for (int e = 0; e < n; ++e) {
+        if (n_tok[e] < n_sot + 3 || n_tok[e] > AL_MAX_TOK) return set_error(WLX_ERR_ARG, "align_post: entry %d has %d tokens, outside %d..%d", e, n_tok[e], n_sot + 3, AL_MAX_TOK);
+        if (nf[e] < 1 || nf[e] > AL_MAX_NF) return set_error(WLX_ERR_ARG, "align_post: entry %d has %d frames, outside 1..%d", e, nf[e], AL_MAX_NF);
+        ent[e] = AlignEnt{};
+        ent[e].n_tok = n_tok[e]; ent[e].nf = nf[e]; ent[e].N = n_tok[e] - 1 - n_sot;
+        if (path_stride < ent[e].N + nf[e]) return set_error(WLX_ERR_ARG, "align_post: path_stride %d below N + nf = %d of entry %d", path_stride, ent[e].N + nf[e], e);
+    }
+    AlignPlan plan{};
+    align_layout(ent, n, n_heads, &plan);
+    HookScope S;
+    CKR(S.begin(device));
+    AlignEnt* dent = nullptr; float *ds = nullptr, *dstat = nullptr, *dx = nullptr; unsigned* dtr = nullptr;
+    int32_t *dti = nullptr, *dfi = nullptr, *dnp = nullptr;
+    CKR(S.upload(&dent, ent, (size_t)n));
+    CK(hipStreamSynchronize(S.st));
+    CKR(S.upload(&ds, scores, plan.score_floats));
+    CKR(S.upload(&dstat, (const float*)nullptr, plan.stat_floats));
+    CKR(S.upload(&dx, cost_out, plan.x_floats));
+    CKR(S.upload(&dtr, (const unsigned*)nullptr, plan.trace_words));
+    CKR(align_hook_paths(S, n, text_indices, time_indices, path_stride, n_path, &dti, &dfi, &dnp));
+    launch_align_cost(dent, n, n_heads, n_sot, median_filter_width, plan, ds, dstat, dx, S.st);
+    launch_align_dtw(dent, n, plan.max_N, dx, dtr, dti, dfi, path_stride, dnp, S.st);
+    CKR(S.download(cost_out, dx, plan.x_floats));
+    CKR(S.download(text_indices, dti, (size_t)n * path_stride));
+    CKR(S.download(time_indices, dfi, (size_t)n * path_stride));
+    CKR(S.download(n_path, dnp, (size_t)n));
     return S.finish();
 }

@@ -286,6 +286,44 @@ class Slot:
                                  _i32p(hd), hd.shape[0], int(eot), _i32p(ti), _i32p(fi), cap, C.byref(n_path), _f32p(probs)))
         return ti[: n_path.value].copy(), fi[: n_path.value].copy(), probs
 
+    def align_batch(self, token_lists: Sequence[Sequence[int]], n_sot: int, num_frames: Sequence[int], heads: Sequence[Tuple[int, int]],
+                    eot: int, median_filter_width: int = 7, items: Optional[Sequence[int]] = None):
+        """`align` for a group of entries in one wlx_align_batch call (one launch sequence, one wait; softmax / median / DTW on the
+        device): entry i is token_lists[i] over num_frames[i] on encoder item items[i] (None = identity, repeats allowed).
+        Returns one (text_indices, time_indices, text_token_probs) per entry. At most _lib.ALIGN_MAX_BATCH entries, odd filter
+        widths up to _lib.ALIGN_MAX_MEDIAN."""
+        n = len(token_lists)
+        if n == 0:
+            return []
+        nt = np.asarray([len(t) for t in token_lists], dtype=np.int32)
+        stride = int(nt.max())
+        tk = np.zeros((n, stride), dtype=np.int32)
+        for i, t in enumerate(token_lists):
+            tk[i, :nt[i]] = t
+        nfr = np.ascontiguousarray(num_frames, dtype=np.int32)
+        if nfr.shape != (n,):
+            raise ValueError(f"{nfr.size} num_frames for {n} entries")
+        it = np.ascontiguousarray(items, dtype=np.int32) if items is not None else None
+        if it is not None and it.shape != (n,):
+            raise ValueError(f"{it.size} items for {n} entries")
+        hd = np.ascontiguousarray(np.asarray(heads, dtype=np.int32).reshape(-1, 2))
+        cap = stride + 1500 + 8
+        ti = np.zeros((n, cap), dtype=np.int32)
+        fi = np.zeros((n, cap), dtype=np.int32)
+        n_path = np.zeros(n, dtype=np.int32)
+        pstride = max(1, stride - n_sot - 2)
+        probs = np.zeros((n, pstride), dtype=np.float32)
+        check(self.lib.wlx_align_batch(self.engine._h, self.sid, n, _i32p(it) if it is not None else None, _i32p(tk), _i32p(nt), stride,
+                                       n_sot, _i32p(nfr), int(median_filter_width), _i32p(hd), hd.shape[0], int(eot),
+                                       _i32p(ti), _i32p(fi), cap, _i32p(n_path), _f32p(probs), pstride))
+        return [(ti[i, : n_path[i]].copy(), fi[i, : n_path[i]].copy(), probs[i, : max(0, int(nt[i]) - n_sot - 2)].copy()) for i in range(n)]
+
+    def align_timings(self) -> Tuple[float, float]:
+        """HIP-event milliseconds of the last align_batch: (decoder passes with the score capture, post-processing behind them)"""
+        a, b = C.c_float(0), C.c_float(0)
+        check(self.lib.wlx_debug_align_timings(self.engine._h, self.sid, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def detect_language(self, batch: int, sot: int, lang_ids: Sequence[int]) -> np.ndarray:
         li = np.asarray(lang_ids, dtype=np.int32)
         probs = np.zeros((batch, li.size), dtype=np.float32)

@@ -29,6 +29,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
+from . import _lib
 from . import vad as _vad
 from . import word_timing as _wt
 from ._lib import ERR_ARG as _ERR_ARG, WlxError as _WlxError
@@ -249,12 +250,20 @@ class _EngineModel:
             raise ValueError(f"{len(text_tokens)} token lists for an encoder batch of {encoder_output.batch}")
         frames = [num_frames] * len(text_tokens) if isinstance(num_frames, int) else list(num_frames)
         bt = o._base_tokenizer
+        seqs = [list(start_sequence) + [bt.no_timestamps] + list(toks) + [bt.eot] for toks in text_tokens]
+        items = encoder_output.items if encoder_output.items is not None else list(range(len(seqs)))
         out = []
-        for i, toks in enumerate(text_tokens):
-            seq = list(start_sequence) + [bt.no_timestamps] + list(toks) + [bt.eot]
+        if median_filter_width <= _lib.ALIGN_MAX_MEDIAN and hasattr(slot, "align_batch"):
+            # every item of the call through wlx_align_batch: one launch sequence and one wait per group, post-processing on the device
+            for a in range(0, len(seqs), _lib.ALIGN_MAX_BATCH):
+                b = a + _lib.ALIGN_MAX_BATCH
+                for ti, fi, probs in slot.align_batch(seqs[a:b], len(start_sequence), frames[a:b], o.alignment_heads, bt.eot,
+                                                      median_filter_width=median_filter_width, items=items[a:b]):
+                    out.append(AlignmentResult(list(zip(ti.tolist(), fi.tolist())), probs.tolist()))
+            return out
+        for i, seq in enumerate(seqs):          # a filter wider than the device kernels serve: item by item, post-processing on the host
             ti, fi, probs = slot.align(seq, len(start_sequence), frames[i], o.alignment_heads, bt.eot,
-                                       median_filter_width=median_filter_width,
-                                       item=encoder_output.items[i] if encoder_output.items is not None else i)
+                                       median_filter_width=median_filter_width, item=items[i])
             out.append(AlignmentResult(list(zip(ti.tolist(), fi.tolist())), probs.tolist()))
         return out
 
@@ -810,11 +819,18 @@ class WhisperModelHIP:
                     pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
                     return pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)   # fp32 values, means in double like np.mean over CT2's Python floats
 
+                def align_many_fn(requests):
+                    res = self.model.align(enc_now.select([0] * len(requests)), tokenizer.sot_sequence, [r[0] for r in requests],
+                                           [r[1] for r in requests])
+                    return [(np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)[:, 0],
+                             np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)[:, 1],
+                             np.asarray(r.text_token_probs, dtype=np.float64)) for r in res]
+
                 # the reference discards add_word_timestamps' return value here (:1227-1235): the last-speech time only
                 # moves at the end of this block, so the hallucination rules below still see the PREVIOUS window's
                 _wt.add_word_timestamps([current], tokenizer, align_fn, segment_size, self.tokens_per_second,
                                         self.frames_per_second, options.prepend_punctuations,
-                                        options.append_punctuations, last_speech_timestamp)
+                                        options.append_punctuations, last_speech_timestamp, align_many_fn=align_many_fn)
                 if not single_ts_ending:
                     lwe = _wt.last_word_end(current)
                     if lwe is not None and lwe > time_offset:

@@ -66,22 +66,36 @@ def words_from_path(tokenizer, text_tokens: Sequence[int], text_indices: np.ndar
 
 def add_word_timestamps(segments: List[List[dict]], tokenizer, align_fn: Callable, num_frames: int, tokens_per_second: int,
                         frames_per_second: int, prepend_punctuations: str, append_punctuations: str,
-                        last_speech_timestamp: float) -> Optional[float]:
+                        last_speech_timestamp: float, *, align_many_fn: Optional[Callable] = None) -> Optional[float]:
     """(:1515-1644) `segments` = one list of sub-segment dicts per encoded window; align_fn(text_tokens, num_frames, window)
-    -> (text_indices, time_indices, text_token_probs). Fills sub-segment["words"], may move sub-segment start / end, and
-    returns the updated last-speech timestamp."""
+    -> (text_indices, time_indices, text_token_probs). With align_many_fn(requests) -> results, every window that has text is
+    aligned in ONE call instead: requests = [(text_tokens, num_frames, window), ...], results = one align_fn-shaped triple per
+    request, in order (an `align_many` attribute on align_fn is taken the same way). Fills sub-segment["words"], may move
+    sub-segment start / end, and returns the updated last-speech timestamp."""
     if not segments:
         return None
+    if align_many_fn is None:
+        align_many_fn = getattr(align_fn, "align_many", None)
     per_window_tokens = []
-    alignments = []
-    for wi, window in enumerate(segments):
+    flats = []
+    for window in segments:
         per_sub = [[t for t in sub["tokens"] if t < tokenizer.eot] for sub in window]
         per_window_tokens.append(per_sub)
-        flat = [t for toks in per_sub for t in toks]
+        flats.append([t for toks in per_sub for t in toks])
+    requests = [(flat, num_frames, wi) for wi, flat in enumerate(flats) if flat]
+    if align_many_fn is not None:
+        results = list(align_many_fn(requests)) if requests else []
+        if len(results) != len(requests):
+            raise ValueError(f"align_many_fn returned {len(results)} results for {len(requests)} requests")
+    else:
+        results = [align_fn(*rq) for rq in requests]
+    aligned = {rq[2]: res for rq, res in zip(requests, results)}
+    alignments = []
+    for wi, flat in enumerate(flats):
         if not flat:
             alignments.append([])
             continue
-        ti, fi, probs = align_fn(flat, num_frames, wi)
+        ti, fi, probs = aligned[wi]
         alignments.append(words_from_path(tokenizer, flat, ti, fi, probs, tokens_per_second))
     limits = []
     for al in alignments:
