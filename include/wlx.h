@@ -572,6 +572,44 @@ int32_t wlx_debug_dec_cross_attn(int32_t device, const uint16_t* q, int64_t ldq,
                                  int64_t item_stride, int32_t n_items, int32_t H, int32_t R, int32_t groups, int32_t rows,
                                  const int32_t* group_item, uint16_t* part_o, float* part_ml, uint16_t* out, int64_t ldo,
                                  int32_t align_item, int32_t align_head, float* align_out);
+/* One launch_dec_gemv (csrc/dec_gemv.hip, dec_vocab.hip) on a GemvParams built as engine_decode.hip decoder_pass builds it, done = null.
+ * in_mode / out_mode / xsrc: GemvIn / GemvOut / GemvXsrc of csrc/decoder.h. W float32 [N][K], packed by the hook into KT = K / 32
+ * k-tiles; bias [N] or null (null: fp32 rows out only — the vocabulary projection). Inputs by mode: X float32 [M][ldx] (LayerNorm
+ * prologue, with gamma / beta [K]); Xh fp16 [M][ldxh]; part_o fp16 [ceil(M / R)][H][8][16][64] and part_ml float32
+ * [ceil(M / R)][H][16][8][2] (split combine, K = 64 H); slab float32 [2][rows][ld] at slab_stride floats, ld = ldx under a LayerNorm
+ * prologue and ldxres otherwise (read with xsrc = SLABS, written by GEMV_OUT_SLAB, KTS = KT / 2 k-tiles per slice); tok_emb fp16
+ * [tokens][K], pos_emb float32 [positions][K], emb_token / row_pos / row_cache int32 [M] (xsrc = EMBED and GEMV_OUT_QKV).
+ * Outputs, copied in AND out: Yh fp16 [M][ldyh] (N columns, d for QKV); Y float32 [M][ldy]; Xres float32 [M][ldxres] (read and
+ * written); Kc / Vc fp16 [cache rows][cache_row_stride], row r at row_cache[r], position row_pos[r] * d; slab; X and intok int32
+ * [cache rows][448] (xsrc = EMBED: the gathered rows and the fed tokens). *_len: elements of the caller's arrays. name_out: the
+ * kernel launch_dec_gemv runs for these parameters (dec_gemv_kernel_name).
+ * WLX_ERR_ARG before any launch: M outside 1..320; K != 32 KT; a LayerNorm prologue with K > 1536; ldx / ldy / ldxres /
+ * slab_stride / cache_row_stride / ldyh not multiples of 4 or ldxh not a multiple of 8 (the kernels' 16- and 8-byte pieces); a stride
+ * below its row; a length that does not hold what is addressed; a bias missing or N not a multiple of 16 where the epilogue is not
+ * fp32 rows out; fp32 rows out WITH a bias and N > 8192; QKV with N != 3 d; a position outside 0..447 or a cache row outside
+ * 0..32767; R outside 1..16 or K != 64 H in the split combine; xsrc != PLAIN or GEMV_OUT_SLAB where no lean kernel serves the
+ * parameters (dec_gemv_is_lean: the first-generation kernel knows neither). */
+typedef struct {
+    int32_t in_mode, out_mode, xsrc, M, K, KT, N, busy_device, KTS, H, R, d;
+    float qscale;
+    int32_t reserved;
+    int64_t ldx, ldxh, ldyh, ldy, ldxres, cache_row_stride, slab_stride;
+    int64_t x_len, xh_len, part_o_len, part_ml_len, slab_len, tok_emb_len, pos_emb_len, yh_len, y_len, xres_len, kc_len, vc_len, intok_len;
+} wlx_debug_dec_gemv_args;
+int32_t wlx_debug_dec_gemv(int32_t device, const wlx_debug_dec_gemv_args* a, const float* W, const float* bias, const float* gamma,
+                           const float* beta, float* X, const uint16_t* Xh, const uint16_t* part_o, const float* part_ml, float* slab,
+                           const uint16_t* tok_emb, const float* pos_emb, const int32_t* emb_token, const int32_t* row_pos,
+                           const int32_t* row_cache, uint16_t* Yh, float* Y, float* Xres, uint16_t* Kc, uint16_t* Vc, int32_t* intok,
+                           char* name_out, int32_t name_cap);
+/* One launch_dec_cq_cross_attn (csrc/decoder.hip): LayerNorm of x float32 [rows][ldx] + query projection (Wq float32 [d][d], packed by
+ * the hook; bias [d]; scaled by qscale) + the split partials of the cross attention; kp / vp / item_stride / group_item / part_o /
+ * part_ml as wlx_debug_dec_cross_attn (query lanes past a group's live rows compute the group's LAST live row again).
+ * WLX_ERR_ARG unless dec_cq_cross_attn_eligible(d, H, R) (d = 768, H = 12, R in 1..16), (groups - 1) * R < rows <= groups * R, ldx a
+ * multiple of 4 covering d, item_stride a multiple of 8 covering the packed image, every group_item inside 0..n_items - 1. */
+int32_t wlx_debug_dec_cq_cross_attn(int32_t device, const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wq,
+                                    const float* bias, float qscale, int32_t d, const uint16_t* kp, const uint16_t* vp,
+                                    int64_t item_stride, int32_t n_items, int32_t H, int32_t R, int32_t groups, int32_t rows,
+                                    const int32_t* group_item, uint16_t* part_o, float* part_ml);
 /* decode self-attention over the KV cache (launch_dec_self_attn): q [rows][ldq], kc / vc [cache_rows][cache_row_stride] with
  * position p of a cache row at p * d (cache_row_stride covers at least the positions in use), row r attends to positions 0..pos[r], position p read from cache row
  * anc[ancrow[r]][p] (anc int16 [cache_rows][448]). ident_ancestry = 1 requires ancrow[r] == r (rows <= 16: the eight-wave

@@ -5,7 +5,9 @@ tests/whisper_kernel_ref.py: rc == 0, everything finite, excess = max |got - flo
 byte no thread owns bit-identical to the +-1000 it was filled with. tests/test_whisper_kernel_ref.py shows on the host that the
 nearest wrong answers fall outside the same bounds. Refusal tests: every documented limit is WLX_ERR_ARG with the outputs
 unchanged (the hooks return before anything is launched). wlx_debug_gemm runs launch_gemm / pack.hip the same way: the engine's
-shapes on the launcher's pick, every form forced, form coverage and bit-identity across forms. Out of scope here: the decode GEMV chain, the fused dec_cq_cross_attn kernel, search.hip, log-mel and VAD."""
+shapes on the launcher's pick, every form forced, form coverage and bit-identity across forms. The decode GEMV chain and the fused
+dec_cq_cross_attn kernel have their own module of the same kind (tests/test_gpu_dec_gemv_kernels.py); search.hip has token-exact
+injected-logits tests. Out of scope here: log-mel and VAD."""
 import os
 
 import numpy as np

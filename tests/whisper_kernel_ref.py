@@ -430,7 +430,7 @@ def xa_case(H, R, groups, rows, n_items, pattern, seed=0):
                 align_out=garbage(rng, (rows, T_PAD)).astype(np.float32))
 
 
-def xa_ref(c, item_of=None, nkeys=T_AUDIO, drop=None, swap=None):
+def xa_ref(c, item_of=None, nkeys=T_AUDIO, drop=None, swap=None, q=None, qb=None, dead_last=False):
     """dict of float64 references and bounds of one wlx_debug_dec_cross_attn call:
       part_o [groups][H][8][16][64]: softmax(q k^T) v over the live keys of each split of 192 keys (six 32-key tiles, one per wave, merged
         with one exponential each: n_exp = 2; weights rounded to fp16 for the second MFMA), fp16 — query lanes past R or past `rows`
@@ -444,9 +444,15 @@ def xa_ref(c, item_of=None, nkeys=T_AUDIO, drop=None, swap=None):
         exponential of m_sp - mmax, Rm = its range) + 16 U32 (eight products and additions, the division), then the fp16 rounding.
     Rm is clamped at 104 = 150 ln 2: below exp(-104) an fp32 value is under the smallest subnormal 2^-149, so __expf returns 0 (or a
     subnormal whose ABSOLUTE error is what matters: it is below 2^-149 times l_sp, nothing against the other splits' weights >= 1).
-    The keyword arguments give the wrong answers (another item's K / V, a padded key taken for live, a key dropped, V rows swapped)."""
+    The keyword arguments give the wrong answers (another item's K / V, a padded key taken for live, a key dropped, V rows swapped).
+    q / qb (the fused LayerNorm + query projection + attention launch, tests/dec_gemv_kernel_ref.py): the query rows as float64 values
+    the kernel's own fp16 query lies within qb of, element by element. A query off by dq moves score j by at most es_j = sum_d qb_d
+    |k_jd|; with es = max_j es_j every weight p_j keeps its value up to a factor exp(+-2 es) against the others (its own shift and the
+    maximum's), so m moves by <= es, l by the relative 2 es and O by 2 es S, S = sum_j p_j |v_j| / sum_j p_j (first order; SLACK
+    covers exp(2 es) - 1 against 2 es for es <= 0.045 — (e^0.09 - 1) / 0.09 = 1.046 — which the cases keep). dead_last: that launch's query lanes past a group's live
+    rows compute the group's LAST live row again, not its first."""
     H, R, G, rows = c["H"], c["R"], c["groups"], c["rows"]
-    q64 = c["q"].astype(np.float64)
+    q64 = (c["q"] if q is None else q).astype(np.float64)
     po = np.zeros((G, H, XSPLIT, 16, 64))
     pob = np.zeros_like(po)
     pm = np.zeros((G, H, 16, XSPLIT))
@@ -455,7 +461,8 @@ def xa_ref(c, item_of=None, nkeys=T_AUDIO, drop=None, swap=None):
     outb = np.zeros_like(out)
     for g in range(G):
         it = int(c["group_item"][g]) if item_of is None else item_of(g)
-        qr = np.array([g * R + cc if (cc < R and g * R + cc < rows) else g * R for cc in range(16)])
+        dead = min(g * R + R, rows) - 1 if dead_last else g * R
+        qr = np.array([g * R + cc if (cc < R and g * R + cc < rows) else dead for cc in range(16)])
         for h in range(H):
             k = c["K"][it, h].astype(np.float64)
             v = c["V"][it, h].astype(np.float64)
@@ -472,15 +479,20 @@ def xa_ref(c, item_of=None, nkeys=T_AUDIO, drop=None, swap=None):
                 ks = np.arange(192 * sp, 192 * sp + 192)
                 ks = ks[live[ks]]
                 O, b32, s = attn_block(qq, k[ks], v[ks], a_steps=128, n_exp=2, p16=True)
-                po[g, h, sp], pob[g, h, sp] = O, to16(O, b32)
                 m = s.max(1)
+                es = 0.0
+                if qb is not None:
+                    es = (qb[qr, 64 * h:64 * h + 64] @ np.abs(k[ks]).T).max(1)
+                    pw = np.exp(s - m[:, None])
+                    b32 = b32 + SLACK * 2 * es[:, None] * (pw @ np.abs(v[ks])) / pw.sum(1, keepdims=True)
+                po[g, h, sp], pob[g, h, sp] = O, to16(O, b32)
                 A = (np.abs(qq) @ np.abs(k[ks]).T).max(1)
                 Rr = m - s.min(1)
                 em = 128 * U32 * A
-                pm[g, h, :, sp], pmb[g, h, :, sp] = m, SLACK * em + U32 * np.abs(m) + 1e-30
+                pm[g, h, :, sp], pmb[g, h, :, sp] = m, SLACK * (em + es) + U32 * np.abs(m) + 1e-30
                 l = np.exp(s - m[:, None]).sum(1)
                 eps_p = U32 * (128 * A + 12 * (Rr + 1))
-                pl[g, h, :, sp], plb[g, h, :, sp] = l, SLACK * l * (2 * eps_p + 2 * em + 256 * U32)
+                pl[g, h, :, sp], plb[g, h, :, sp] = l, SLACK * l * (2 * eps_p + 2 * em + 256 * U32 + 2 * es)
                 mass[:, sp] = l
             mmax = pm[g, h].max(1, keepdims=True)
             wgt = np.exp(pm[g, h] - mmax) * mass
@@ -896,6 +908,12 @@ def gemm_w16(c):
     return W.astype(np.float16).astype(np.float64)
 
 
+def acc_bound(absdot, K):
+    """bound of an fp32 accumulation of K exact fp16 products in any association, absdot = sum_k |a_k w_k|: every accumulation step is
+    charged 2 U32 since the rounding of the MFMA's internal additions is not documented (the derivation is gemm_logical's)"""
+    return 2 * (K + 2) * U32 * absdot
+
+
 def gemm_logical(c, wrong=None):
     """(values [Z][M][N] float64 the epilogue stores or adds, bound32 of their fp32 form, x0 or None).
     acc = A W^T: exact fp16 products, K fp32 accumulation steps (plus the zero-weight padding steps, which add exact zeros) charged
@@ -911,7 +929,7 @@ def gemm_logical(c, wrong=None):
     if wrong == "bias_shift":
         bias[16:32] = bias[20:36]
     x = rows @ w.T + bias
-    e = 2 * (c["K"] + 2) * U32 * (np.abs(rows) @ np.abs(w).T) + U32 * np.abs(c["bias"].astype(np.float64))
+    e = acc_bound(np.abs(rows) @ np.abs(w).T, c["K"]) + U32 * np.abs(c["bias"].astype(np.float64))
     mode = c["mode"]
     x0 = None
     if mode in (1, 2):

@@ -32,6 +32,7 @@ EXPORTS = [
     "wlx_spk_debug_timings", "wlx_spk_debug_fbank", "wlx_spk_debug_conv", "wlx_spk_debug_pool",
     "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
+    "wlx_debug_dec_gemv", "wlx_debug_dec_cq_cross_attn",
     "wlx_debug_resample", "wlx_debug_resample_timed",
     "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings",
 ]
@@ -119,6 +120,14 @@ class wlx_debug_gemm_args(C.Structure):
                 [(n, C.c_int64) for n in ("lda", "strideA", "a_len", "ldc", "strideC", "c_len", "ldx", "strideX", "x_len",
                                           "ldk", "kv_item_stride_k", "kv_layer_stride_k", "k_len",
                                           "ldvt", "kv_item_stride_v", "kv_layer_stride_v", "v_len")])
+
+
+class wlx_debug_dec_gemv_args(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("in_mode", "out_mode", "xsrc", "M", "K", "KT", "N", "busy_device", "KTS", "H", "R", "d")] +
+                [("qscale", C.c_float), ("reserved", C.c_int32)] +
+                [(n, C.c_int64) for n in ("ldx", "ldxh", "ldyh", "ldy", "ldxres", "cache_row_stride", "slab_stride",
+                                          "x_len", "xh_len", "part_o_len", "part_ml_len", "slab_len", "tok_emb_len", "pos_emb_len",
+                                          "yh_len", "y_len", "xres_len", "kc_len", "vc_len", "intok_len")])
 
 
 class wlx_mt_gen_opts(C.Structure):
@@ -327,6 +336,10 @@ def load() -> C.CDLL:
     lib.wlx_debug_dec_self_attn.argtypes = [i32, u16p, i64, u16p, u16p, i64, i32, i32, i32, i32, i32p, i32p, C.POINTER(C.c_int16), i32,
                                             u16p, i64]
     lib.wlx_debug_gemm.argtypes = [i32, C.POINTER(wlx_debug_gemm_args), u16p, f32p, f32p, f32p, u16p, f32p, u16p, u16p, i32p]
+    lib.wlx_debug_dec_gemv.argtypes = [i32, C.POINTER(wlx_debug_dec_gemv_args), f32p, f32p, f32p, f32p, f32p, u16p, u16p, f32p, f32p, u16p, f32p,
+                                       i32p, i32p, i32p, u16p, f32p, f32p, u16p, u16p, i32p, C.c_char_p, i32]
+    lib.wlx_debug_dec_cq_cross_attn.argtypes = [i32, f32p, i64, f32p, f32p, f32p, f32p, C.c_float, i32, u16p, u16p, i64, i32, i32, i32, i32, i32,
+                                                i32p, u16p, f32p]
     lib.wlx_debug_resample.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p]
     lib.wlx_debug_resample_timed.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p, f32p]
     lib.wlx_debug_dtw.argtypes = [i32, f32p, i32, i32p, i32p, i32p, i32p, i32, i32p]

@@ -1,6 +1,12 @@
-// kernel_hooks.hip — kernel-level test hooks of the Whisper kernels: wlx_debug_layernorm, wlx_debug_attn_encoder,
-// wlx_debug_dec_cross_attn, wlx_debug_dec_self_attn, wlx_debug_gemm, wlx_debug_dtw, wlx_debug_align_post (include/wlx.h, below the
-// TEST / PROFILING line).
+// kernel_hooks.hip — kernel-level test hooks of the Whisper kernels (include/wlx.h, below the TEST / PROFILING line):
+//   wlx_debug_layernorm          launch_layernorm_f16 / _f16_f32 (gemm.hip)
+//   wlx_debug_attn_encoder       launch_attn_encoder (attention.hip)
+//   wlx_debug_dec_cross_attn     launch_dec_cross_attn + launch_dec_xattn_combine (+ launch_dec_align_scores) (decoder.hip)
+//   wlx_debug_dec_self_attn      launch_dec_self_attn (decoder.hip)
+//   wlx_debug_gemm               launch_gemm / launch_gemm_form, weights packed by pack.hip (gemm.hip)
+//   wlx_debug_dec_gemv           launch_dec_gemv: dec_gemv2_kernel, dec_vocab_kernel, dec_gemv_kernel (dec_gemv.hip, dec_vocab.hip)
+//   wlx_debug_dec_cq_cross_attn  launch_dec_cq_cross_attn (decoder.hip)
+//   wlx_debug_dtw, wlx_debug_align_post   launch_align_dtw / launch_align_cost (align.hip)
 // Same conventions as the translation hooks (mt_engine.hip wlx_mt_debug_attn): host arrays in, ONE call of the production
 // launcher on a private non-blocking stream, host arrays out. Outputs are copied in AND out, so bytes no thread owns come back
 // unchanged. Every shape a launcher cannot serve is refused (WLX_ERR_ARG) before anything is allocated or launched. No engine
@@ -316,6 +322,190 @@ extern "C" int32_t wlx_debug_gemm(int32_t device, const wlx_debug_gemm_args* a, 
         CKR(S.download(h16(kout), dK, (size_t)a->k_len));
         CKR(S.download(h16(vt), dV, (size_t)a->v_len));
     }
+    return S.finish();
+}
+
+// One launch_dec_gemv on a GemvParams built from the arguments, as engine_decode.hip decoder_pass builds them (done = null: the lean kernels
+// do not read it). W is float32 [N][K], packed here with the production pack kernel.
+extern "C" int32_t wlx_debug_dec_gemv(int32_t device, const wlx_debug_dec_gemv_args* a, const float* W, const float* bias, const float* gamma,
+                                      const float* beta, float* X, const uint16_t* Xh, const uint16_t* part_o, const float* part_ml,
+                                      float* slab, const uint16_t* tok_emb, const float* pos_emb, const int32_t* emb_token,
+                                      const int32_t* row_pos, const int32_t* row_cache, uint16_t* Yh, float* Y, float* Xres, uint16_t* Kc,
+                                      uint16_t* Vc, int32_t* intok, char* name_out, int32_t name_cap) {
+    if (!a || !W || !name_out || name_cap < 1) return set_error(WLX_ERR_ARG, "null argument");
+    const int in = a->in_mode, out = a->out_mode, xs = a->xsrc, M = a->M, K = a->K, KT = a->KT, N = a->N, d = a->d;
+    if (in < GEMV_IN_LN || in > GEMV_IN_XATTN || out < GEMV_OUT_F16 || out > GEMV_OUT_SLAB || xs < GEMV_X_PLAIN || xs > GEMV_X_EMBED)
+        return set_error(WLX_ERR_ARG, "in_mode %d / out_mode %d / xsrc %d outside their enums", in, out, xs);
+    if (M < 1 || M > WLX_MAX_DEC_ROWS) return set_error(WLX_ERR_ARG, "M %d outside 1..%d", M, WLX_MAX_DEC_ROWS);
+    if (K < 32 || KT < 1 || K != 32 * KT) return set_error(WLX_ERR_ARG, "K %d != 32 * KT %d (the decode projections take whole k-tiles)", K, KT);
+    if (N < 1 || N > (1 << 20)) return set_error(WLX_ERR_ARG, "N %d outside 1..2^20", N);
+    // every epilogue but the fp32 logits stores 4-column pieces of whole 16-column tiles and reads its bias as float4
+    if (out != GEMV_OUT_F32 && (!bias || (N & 15))) return set_error(WLX_ERR_ARG, "out_mode %d needs a bias and N %d a multiple of 16", out, N);
+    // (fp32 rows out with a bias is no launch of the engine's: above 8192 columns the lean kernel pairs column tiles without a clamp)
+    if (out == GEMV_OUT_F32 && bias && ((N & 15) || N > 8192)) return set_error(WLX_ERR_ARG, "fp32 rows out with a bias: N %d must be a multiple of 16, <= 8192", N);
+    if (a->busy_device != 0 && a->busy_device != 1) return set_error(WLX_ERR_ARG, "busy_device %d", a->busy_device);
+    // (the first-generation kernel's LayerNorm prologue holds one chunk of six k-tiles on each of at most eight waves)
+    if (in == GEMV_IN_LN && KT > 48) return set_error(WLX_ERR_ARG, "LayerNorm prologue: K %d above 1536", K);
+    if (xs != GEMV_X_PLAIN && !(in == GEMV_IN_LN || (in == GEMV_IN_F16 && out == GEMV_OUT_RESID && xs == GEMV_X_SLABS)))
+        return set_error(WLX_ERR_ARG, "xsrc %d: LayerNorm prologue, or slabs under the residual epilogue of fp16 rows", xs);
+    if (xs == GEMV_X_EMBED && out != GEMV_OUT_QKV) return set_error(WLX_ERR_ARG, "embedding rows feed a layer's first projection (QKV) only");
+    const bool slabs_in = xs == GEMV_X_SLABS, slab_used = slabs_in || out == GEMV_OUT_SLAB;
+    const int64_t rows1 = M - 1;
+    // ---- inputs by mode
+    if (in == GEMV_IN_LN) {
+        if (!gamma || !beta) return set_error(WLX_ERR_ARG, "LayerNorm prologue without gamma / beta");
+        if (!X || a->ldx < K || a->ldx % 4 || rows1 * a->ldx + K > a->x_len)
+            return set_error(WLX_ERR_ARG, "X: ldx %lld (a multiple of 4 covering K) / length %lld do not hold [M][K]", (long long)a->ldx, (long long)a->x_len);
+    } else if (in == GEMV_IN_F16) {
+        if (!Xh || a->ldxh < K || a->ldxh % 8 || rows1 * a->ldxh + K > a->xh_len)
+            return set_error(WLX_ERR_ARG, "Xh: ldxh %lld (a multiple of 8 covering K) / length %lld do not hold [M][K]", (long long)a->ldxh, (long long)a->xh_len);
+    } else {
+        if (!part_o || !part_ml || a->R < 1 || a->R > 16 || a->H < 1 || 64 * a->H != K)
+            return set_error(WLX_ERR_ARG, "split combine: partials, R %d in 1..16, H %d * 64 == K %d", a->R, a->H, K);
+        if (xs != GEMV_X_PLAIN || out != GEMV_OUT_RESID) return set_error(WLX_ERR_ARG, "split combine: plain rows, residual epilogue");
+        const int64_t items = ((int64_t)M + a->R - 1) / a->R;
+        if (items * a->H * WLX_XSPLIT * 16 * 64 > a->part_o_len || items * a->H * 16 * WLX_XSPLIT * 2 > a->part_ml_len)
+            return set_error(WLX_ERR_ARG, "split combine: partials of %lld groups do not fit part_o / part_ml", (long long)items);
+    }
+    // ---- outputs by mode
+    if (out == GEMV_OUT_F16 || out == GEMV_OUT_GELU_F16 || out == GEMV_OUT_QKV) {
+        const int w = out == GEMV_OUT_QKV ? d : N;
+        if (out == GEMV_OUT_QKV && (d < 16 || d % 16 || N != 3 * d)) return set_error(WLX_ERR_ARG, "QKV: N %d != 3 d, d %d a multiple of 16", N, d);
+        if (!Yh || a->ldyh < w || a->ldyh % 4 || rows1 * a->ldyh + w > a->yh_len)
+            return set_error(WLX_ERR_ARG, "Yh: ldyh %lld (a multiple of 4) / length %lld do not hold [M][%d]", (long long)a->ldyh, (long long)a->yh_len, w);
+    } else if (out == GEMV_OUT_F32) {
+        if (!Y || a->ldy < N || a->ldy % 4 || rows1 * a->ldy + N > a->y_len)
+            return set_error(WLX_ERR_ARG, "Y: ldy %lld (a multiple of 4) / length %lld do not hold [M][N]", (long long)a->ldy, (long long)a->y_len);
+    }
+    if (out == GEMV_OUT_RESID || out == GEMV_OUT_SLAB) {
+        if (a->ldxres < N || a->ldxres % 4) return set_error(WLX_ERR_ARG, "ldxres %lld must cover N and be a multiple of 4", (long long)a->ldxres);
+        if (out == GEMV_OUT_RESID && (!Xres || rows1 * a->ldxres + N > a->xres_len)) return set_error(WLX_ERR_ARG, "Xres (%lld floats) does not hold [M][N]", (long long)a->xres_len);
+    }
+    if (slab_used) {
+        const int64_t ld = in == GEMV_IN_LN ? a->ldx : a->ldxres, w = in == GEMV_IN_LN ? K : N;
+        if (!slab || a->slab_stride < 0 || a->slab_stride % 4 || (int64_t)(WLX_FC2_KS - 1) * a->slab_stride + rows1 * ld + w > a->slab_len)
+            return set_error(WLX_ERR_ARG, "slab: stride %lld (a multiple of 4) / length %lld do not hold [%d][M][%lld]", (long long)a->slab_stride, (long long)a->slab_len, WLX_FC2_KS, (long long)w);
+    }
+    if (out == GEMV_OUT_QKV) {
+        if (!row_pos || !row_cache || !Kc || !Vc || a->cache_row_stride < d || a->cache_row_stride % 4)
+            return set_error(WLX_ERR_ARG, "QKV: row tables, caches, cache_row_stride %lld (a multiple of 4)", (long long)a->cache_row_stride);
+        for (int r = 0; r < M; ++r) {
+            if (row_pos[r] < 0 || row_pos[r] >= WLX_T_TEXT || row_cache[r] < 0 || row_cache[r] > 32767)
+                return set_error(WLX_ERR_ARG, "row %d: position %d outside 0..447 or cache row %d outside 0..32767", r, row_pos[r], row_cache[r]);
+            const int64_t end = (int64_t)row_cache[r] * a->cache_row_stride + (int64_t)row_pos[r] * d + d;
+            if ((int64_t)(row_pos[r] + 1) * d > a->cache_row_stride || end > a->kc_len || end > a->vc_len)
+                return set_error(WLX_ERR_ARG, "row %d: cache row %d position %d outside the caches", r, row_cache[r], row_pos[r]);
+        }
+    }
+    if (xs == GEMV_X_EMBED) {
+        if (!tok_emb || !pos_emb || !emb_token || !intok) return set_error(WLX_ERR_ARG, "embedding rows: tables, tokens, intok");
+        for (int r = 0; r < M; ++r) {
+            if (emb_token[r] < 0 || ((int64_t)emb_token[r] + 1) * K > a->tok_emb_len) return set_error(WLX_ERR_ARG, "row %d: token %d outside the table", r, emb_token[r]);
+            if (((int64_t)row_pos[r] + 1) * K > a->pos_emb_len) return set_error(WLX_ERR_ARG, "row %d: position %d outside the table", r, row_pos[r]);
+            if ((int64_t)row_cache[r] * WLX_T_TEXT + row_pos[r] >= a->intok_len) return set_error(WLX_ERR_ARG, "row %d: intok entry outside the table", r);
+        }
+    }
+    GemvParams p{};
+    p.in_mode = in; p.out_mode = out; p.xsrc = xs; p.M = M; p.K = K; p.KT = KT; p.N = N; p.busy_device = a->busy_device;
+    p.KTS = out == GEMV_OUT_SLAB ? a->KTS : 0; p.H = a->H; p.R = a->R; p.d = d; p.qscale = a->qscale;
+    p.ldx = a->ldx; p.ldxh = a->ldxh; p.ldyh = a->ldyh; p.ldy = a->ldy; p.ldxres = a->ldxres;
+    p.cache_row_stride = a->cache_row_stride; p.slab_stride = a->slab_stride; p.done = nullptr;
+    if (xs == GEMV_X_EMBED) p.ldxres = a->ldx;                      // the gathered rows land in X, where the later residual updates read them
+    {   // what the engine asks before it builds such a pass: the first-generation kernel knows neither xsrc nor GEMV_OUT_SLAB
+        GemvParams q = p;
+        static const float dummy = 0.f;
+        static float dummy_slab = 0.f;
+        q.bias = bias ? &dummy : nullptr;                           // (the probe only asks whether there is one)
+        q.slab = slab_used ? &dummy_slab : nullptr;
+        if ((xs != GEMV_X_PLAIN || out == GEMV_OUT_SLAB) && !dec_gemv_is_lean(q))
+            return set_error(WLX_ERR_ARG, "xsrc %d / out_mode %d: no lean kernel for M %d K %d N %d KTS %d", xs, out, M, K, N, a->KTS);
+        // rows the first-generation kernel holds per launch are whole groups in the split combine: nothing to check; its vocabulary
+        // form reads no bias. M > 64 there runs as consecutive chunks (launch_dec_gemv): still one call of the launcher.
+    }
+    HookScope S;
+    CKR(S.begin(device));
+    float *dW = nullptr, *db = nullptr, *dg = nullptr, *dbe = nullptr, *dX = nullptr, *dml = nullptr, *dsl = nullptr, *dpe = nullptr, *dY = nullptr,
+          *dXr = nullptr;
+    half_t *dWp = nullptr, *dXh = nullptr, *dpo = nullptr, *dte = nullptr, *dYh = nullptr, *dK = nullptr, *dV = nullptr;
+    int32_t *dtok = nullptr, *dpos = nullptr, *dcache = nullptr, *dintok = nullptr;
+    CKR(S.upload(&dW, W, (size_t)N * K));
+    int kt_alloc = 0;
+    CKR(alloc_packed(S.allocs, N, K, &dWp, &kt_alloc, true));
+    launch_pack_linear(dW, N, K, K, dWp, KT, 0, S.st);
+    if (bias) CKR(S.upload(&db, bias, (size_t)N));
+    if (in == GEMV_IN_LN) { CKR(S.upload(&dg, gamma, (size_t)K)); CKR(S.upload(&dbe, beta, (size_t)K)); }
+    const bool x_used = in == GEMV_IN_LN;
+    if (x_used) CKR(S.upload(&dX, X, (size_t)a->x_len));
+    if (in == GEMV_IN_F16) CKR(S.upload(&dXh, h16(Xh), (size_t)a->xh_len));
+    if (in == GEMV_IN_XATTN) { CKR(S.upload(&dpo, h16(part_o), (size_t)a->part_o_len)); CKR(S.upload(&dml, part_ml, (size_t)a->part_ml_len)); }
+    if (slab_used) CKR(S.upload(&dsl, slab, (size_t)a->slab_len));
+    if (out == GEMV_OUT_QKV) {
+        CKR(S.upload(&dpos, row_pos, (size_t)M)); CKR(S.upload(&dcache, row_cache, (size_t)M));
+        CKR(S.upload(&dK, h16(Kc), (size_t)a->kc_len)); CKR(S.upload(&dV, h16(Vc), (size_t)a->vc_len));
+    }
+    if (xs == GEMV_X_EMBED) {
+        CKR(S.upload(&dte, h16(tok_emb), (size_t)a->tok_emb_len)); CKR(S.upload(&dpe, pos_emb, (size_t)a->pos_emb_len));
+        CKR(S.upload(&dtok, emb_token, (size_t)M)); CKR(S.upload(&dintok, intok, (size_t)a->intok_len));
+    }
+    const bool yh_used = out == GEMV_OUT_F16 || out == GEMV_OUT_GELU_F16 || out == GEMV_OUT_QKV;
+    if (yh_used) CKR(S.upload(&dYh, h16(Yh), (size_t)a->yh_len));
+    if (out == GEMV_OUT_F32) CKR(S.upload(&dY, Y, (size_t)a->y_len));
+    if (out == GEMV_OUT_RESID) CKR(S.upload(&dXr, Xres, (size_t)a->xres_len));
+    p.Wp = dWp; p.bias = db; p.X = dX; p.gamma = dg; p.beta = dbe; p.Xh = dXh; p.part_o = dpo; p.part_ml = dml;
+    p.Yh = dYh; p.Y = dY; p.Xres = xs == GEMV_X_EMBED ? dX : dXr; p.Kc = dK; p.Vc = dV; p.row_cache = dcache; p.row_pos = dpos;
+    p.slab = dsl; p.tok_emb = dte; p.pos_emb = dpe; p.emb_token = dtok; p.intok = dintok;
+    snprintf(name_out, (size_t)name_cap, "%s", dec_gemv_kernel_name(p));
+    launch_dec_gemv(p, S.st);
+    if (x_used) CKR(S.download(X, dX, (size_t)a->x_len));
+    if (slab_used) CKR(S.download(slab, dsl, (size_t)a->slab_len));
+    if (yh_used) CKR(S.download(h16(Yh), dYh, (size_t)a->yh_len));
+    if (dY) CKR(S.download(Y, dY, (size_t)a->y_len));
+    if (dXr) CKR(S.download(Xres, dXr, (size_t)a->xres_len));
+    if (out == GEMV_OUT_QKV) { CKR(S.download(h16(Kc), dK, (size_t)a->kc_len)); CKR(S.download(h16(Vc), dV, (size_t)a->vc_len)); }
+    if (xs == GEMV_X_EMBED) CKR(S.download(intok, dintok, (size_t)a->intok_len));
+    return S.finish();
+}
+
+// One launch_dec_cq_cross_attn: LayerNorm of x + query projection (Wq float32 [d][d], packed here) + the split partials of the cross attention.
+extern "C" int32_t wlx_debug_dec_cq_cross_attn(int32_t device, const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wq,
+                                               const float* bias, float qscale, int32_t d, const uint16_t* kp, const uint16_t* vp,
+                                               int64_t item_stride, int32_t n_items, int32_t H, int32_t R, int32_t groups, int32_t rows,
+                                               const int32_t* group_item, uint16_t* part_o, float* part_ml) {
+    if (!x || !gamma || !beta || !Wq || !bias || !kp || !vp || !group_item || !part_o || !part_ml) return set_error(WLX_ERR_ARG, "null argument");
+    if (H < 1 || H > 64 || n_items < 1 || d < 64) return set_error(WLX_ERR_ARG, "H %d outside 1..64 / n_items %d / d %d", H, n_items, d);
+    if (!dec_cq_cross_attn_eligible(d, H, R)) return set_error(WLX_ERR_ARG, "the fused launch does not serve d %d / H %d / R %d", d, H, R);
+    if (groups < 1 || groups > 65535) return set_error(WLX_ERR_ARG, "groups %d outside 1..65535", groups);
+    // a group's dead query lanes fall back to its last live row, which must exist
+    if ((int64_t)rows <= (int64_t)(groups - 1) * R || (int64_t)rows > (int64_t)groups * R)
+        return set_error(WLX_ERR_ARG, "rows %d outside ((groups - 1) * R, groups * R] = (%d, %d]", rows, (groups - 1) * R, groups * R);
+    if (ldx < d || ldx % 4) return set_error(WLX_ERR_ARG, "ldx %lld must cover d and be a multiple of 4", (long long)ldx);
+    const int64_t image = (int64_t)d * WLX_T_AUDIO_PAD;
+    if (item_stride < image || item_stride % 8)
+        return set_error(WLX_ERR_ARG, "item_stride %lld below the packed image of H heads (%lld halfs) or not a multiple of 8", (long long)item_stride, (long long)image);
+    for (int g = 0; g < groups; ++g)
+        if (group_item[g] < 0 || group_item[g] >= n_items) return set_error(WLX_ERR_ARG, "group %d: item %d outside 0..%d", g, group_item[g], n_items - 1);
+    HookScope S;
+    CKR(S.begin(device));
+    float *dx = nullptr, *dg = nullptr, *dbe = nullptr, *dW = nullptr, *db = nullptr, *dml = nullptr;
+    half_t *dWp = nullptr, *dk = nullptr, *dv = nullptr, *dpo = nullptr;
+    int32_t* dgi = nullptr;
+    const size_t n_po = (size_t)groups * H * WLX_XSPLIT * 16 * 64, n_ml = (size_t)groups * H * 16 * WLX_XSPLIT * 2;
+    CKR(S.upload(&dx, x, (size_t)rows * ldx));
+    CKR(S.upload(&dg, gamma, (size_t)d));
+    CKR(S.upload(&dbe, beta, (size_t)d));
+    CKR(S.upload(&dW, Wq, (size_t)d * d));
+    CKR(S.upload(&db, bias, (size_t)d));
+    int kt_alloc = 0;
+    CKR(alloc_packed(S.allocs, d, d, &dWp, &kt_alloc, true));
+    launch_pack_linear(dW, d, d, d, dWp, d / 32, 0, S.st);
+    CKR(S.upload(&dk, h16(kp), (size_t)n_items * item_stride));
+    CKR(S.upload(&dv, h16(vp), (size_t)n_items * item_stride));
+    CKR(S.upload(&dgi, group_item, (size_t)groups));
+    CKR(S.upload(&dpo, h16(part_o), n_po));
+    CKR(S.upload(&dml, part_ml, n_ml));
+    launch_dec_cq_cross_attn(dx, ldx, dg, dbe, dWp, db, qscale, d, dk, dv, item_stride, H, R, groups, rows, dgi, dpo, dml, S.st);
+    CKR(S.download(h16(part_o), dpo, n_po));
+    CKR(S.download(part_ml, dml, n_ml));
     return S.finish();
 }
 
