@@ -450,6 +450,21 @@ int32_t wlx_spk_embed(wlx_spk* spk, const float* pcm_f32, int64_t n_samples, flo
  * lengths sum to more than max_seconds, for n outside its range and for a null pointer. */
 #define WLX_SPK_MAX_BATCH 64
 int32_t wlx_spk_embed_batch(wlx_spk* spk, const float* pcm_f32, const int64_t* n_samples, int32_t n, float* out, int32_t* status);
+/* wlx_spk_embed_batch on ranges of RESIDENT audio: entry i is samples [starts[i], starts[i] + n_samples[i]) of the resident PCM of
+ * slot item `item` (wlx_pcm_put / wlx_pcm_put_frames). No host-to-device copy of audio; the engine's PCM buffer is not touched. The
+ * ranges may touch, overlap and repeat: they are only read. out, status, WLX_ERR_TOO_SHORT and the bits of every row as above. The
+ * engine's stream is ordered behind the slot's with ONE event (a wlx_pcm_put_frames resample may still be in flight); the slot counts
+ * as busy for the call; one wait, at the end. Every refusal happens before any launch and writes nothing. WLX_ERR_ARG: a null
+ * pointer, n outside 1..WLX_SPK_MAX_BATCH, a negative start or count, one range or the sum of all over max_seconds (the ranges share the
+ * engine's activation buffers), `spk` and `e` on different devices, an item outside the slot. WLX_ERR_STATE: a busy slot, no PCM
+ * resident in the item, a range ending past the resident count. */
+int32_t wlx_spk_embed_pcm_batch(wlx_spk* spk, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts,
+                                const int64_t* n_samples, int32_t n, float* out, int32_t* status);
+/* the same on ABSOLUTE stream positions of a device PCM ring (wlx_ring_*, below). The ring's mutex is held for the call, as in
+ * wlx_vad_probs_resident: an append or a trim from the socket thread waits its turn. WLX_ERR_STATE for a range that starts below the
+ * ring's base (trimmed away) or ends past base + resident. */
+int32_t wlx_spk_embed_ring_batch(wlx_spk* spk, wlx_ring* r, const int64_t* starts, const int64_t* n_samples, int32_t n,
+                                 float* out, int32_t* status);
 
 /* ==== everything below: TEST / PROFILING hooks (used only by tests/, scripts/ and bench.py's roofline leg; not part of
  * the drop-in boundary; the product entry points end here) ================================================================= */
@@ -506,8 +521,8 @@ int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_t rows, int
 int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vocab, int32_t d, const int32_t* tok, const int32_t* pos,
                            int32_t rows, float scale, const float* sinpos, int32_t n_pos, float* x);
 
-/* speaker engine: device times (HIP events) of the last wlx_spk_embed or wlx_spk_embed_batch that launched: filterbank, then
- * network + pooling + head */
+/* speaker engine: device times (HIP events) of the last wlx_spk_embed, wlx_spk_embed_batch, wlx_spk_embed_pcm_batch or
+ * wlx_spk_embed_ring_batch that launched: filterbank, then network + pooling + head */
 int32_t wlx_spk_debug_timings(wlx_spk* spk, float* fbank_ms, float* net_ms);
 /* speaker engine kernels, one launch each on host arrays, same conventions as the hooks above.
  * Filterbank of n_samples >= 400 samples: frames_out float32 [T][n_mels] (log-mel, per-bin mean removed) and image_out, its fp16

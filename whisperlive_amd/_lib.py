@@ -25,7 +25,7 @@ EXPORTS = [
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
     "wlx_logmel_chunks", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
-    "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch",
+    "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch", "wlx_spk_embed_pcm_batch", "wlx_spk_embed_ring_batch",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
     "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
     "wlx_mt_debug_embed",
@@ -323,6 +323,8 @@ def load() -> C.CDLL:
     lib.wlx_spk_destroy.restype = None
     lib.wlx_spk_embed.argtypes = [vp, f32p, i64, f32p]
     lib.wlx_spk_embed_batch.argtypes = [vp, f32p, i64p, i32, f32p, i32p]
+    lib.wlx_spk_embed_pcm_batch.argtypes = [vp, vp, i32, i32, i64p, i64p, i32, f32p, i32p]
+    lib.wlx_spk_embed_ring_batch.argtypes = [vp, vp, i64p, i64p, i32, f32p, i32p]
     lib.wlx_spk_debug_timings.argtypes = [vp, f32p, f32p]
     lib.wlx_spk_debug_fbank.argtypes = [i32, f32p, i64, i32, f32p, u16p, i32, i32p]
     lib.wlx_spk_debug_conv.argtypes = [i32, u16p, i32, i32, i32, f32p, f32p, u16p, i32, i32, i32, i32, u16p]

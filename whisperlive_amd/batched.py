@@ -23,6 +23,7 @@ import numpy as np
 from . import vad as _vad
 from . import word_timing as _wt
 from ._lib import ERR_ARG as _ERR_ARG, LM_MAXRANGES as _MAXRANGES, WlxError as _WlxError
+from .engine import ResidentPcm
 from .tokenizer import Tokenizer
 from .transcriber import EncoderOutput, get_compression_ratio, get_suppressed_tokens, pad_or_trim, restore_speech_timestamps
 from .types import Segment, TranscriptionInfo, TranscriptionOptions, Word
@@ -260,6 +261,8 @@ class BatchedInferencePipeline:
 
         # ---- the audio becomes resident once (device route) or stays on the host (engines without the front end)
         slot = model._slot(rows=int(beam_size))
+        if hasattr(model, "_tls"):
+            model._tls.file_audio = None      # (what an earlier call of this thread left resident is about to be overwritten)
         device = all(hasattr(slot, m) for m in ("logmel_chunks", "pcm_put", "pcm"))
         host_audio = None            # the 16 kHz host waveform, a callable that fetches it, or None until something asks
         n_samples = None
@@ -325,6 +328,9 @@ class BatchedInferencePipeline:
             chunk_ranges, chunks_metadata = [], []
         if device:
             features = DeviceChunks(slot, chunk_ranges, host_audio, 0, n_samples)
+            if n_samples > 0 and hasattr(model, "_tls"):
+                # what reads the file after the transcription (speaker labels) finds it in the source item: WhisperModelHIP.resident_file_audio
+                model._tls.file_audio = ResidentPcm(slot, 0, n_samples, features.shared)
         else:
             wave = _resolve(host_audio, slot)
             features = [model.feature_extractor(np.concatenate([wave[s:e] for s, e in rg]))[..., :-1] for rg in chunk_ranges]

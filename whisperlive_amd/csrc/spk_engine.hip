@@ -2,10 +2,12 @@
 // kernels of spk.hip. One engine per GPU on a non-blocking stream of its own; every buffer is sized at create for max_seconds of
 // audio and fully rewritten by each call up to the extent that call reads, so no call sees another's data. Calls are serialised
 // by the engine's mutex. wlx_spk_embed_batch runs up to WLX_SPK_MAX_BATCH segments as one ragged pass through the same buffers (the
-// sum of their lengths is what has to fit max_seconds). Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
+// sum of their lengths is what has to fit max_seconds); wlx_spk_embed_pcm_batch / _ring_batch run the same pass on ranges of audio that
+// is already in HBM (a slot item's PCM, a client's PCM ring), with no upload. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
 // _pool and their ragged forms _conv_batch / _pool_batch.
 #include <cmath>
 #include <mutex>
+#include "engine.h"
 #include "host.h"
 #include "spk.h"
 
@@ -260,41 +262,55 @@ extern "C" int32_t wlx_spk_embed(wlx_spk* k, const float* pcm, int64_t n_samples
     return WLX_OK;
 }
 
-extern "C" int32_t wlx_spk_embed_batch(wlx_spk* k, const float* pcm, const int64_t* n_samples, int32_t n, float* out, int32_t* status) {
-    if (!k || !pcm || !n_samples || !out || !status) return set_error(WLX_ERR_ARG, "null argument");
-    if (n < 1 || n > WLX_SPK_MAX_BATCH) return set_error(WLX_ERR_ARG, "%d items outside 1..%d", n, WLX_SPK_MAX_BATCH);
-    long total = 0;
-    for (int i = 0; i < n; ++i) {
-        if (n_samples[i] < 0 || n_samples[i] > k->max_samples)
-            return set_error(WLX_ERR_ARG, "item %d: %lld samples outside 0..the engine's %d s", i, (long long)n_samples[i], k->spec.max_seconds);
-        total += (long)n_samples[i];
-    }
-    if (total > k->max_samples)
-        return set_error(WLX_ERR_ARG, "%ld samples in %d items exceed the engine's %d s", total, n, k->spec.max_seconds);
-    const wlx_spk_spec& sp = k->spec;
-    // the items that take part: where each starts in the upload, its frames, the row of `out` it fills
-    long offs[WLX_SPK_MAX_BATCH];
+// ------------------------------------------------------------------------------------------------ ragged batch
+// What the three batch entry points decide on the arguments alone: status and the zero row of every item that is too short, and of the
+// m items that take part their frames and the row of `out` each fills. Written to the CALLER's arrays only by spk_plan_commit, after
+// every refusal of the entry point has had its turn.
+struct SpkPlan {
+    long offs[WLX_SPK_MAX_BATCH];            // first sample of the item in the buffer the front end reads
     int widths[WLX_SPK_MAX_BATCH], row[WLX_SPK_MAX_BATCH], m = 0;
+    long total = 0;
+};
+
+static int spk_plan(const char* who, const wlx_spk* k, const int64_t* starts, const int64_t* n_samples, int n, SpkPlan& pl) {
+    if (n < 1 || n > WLX_SPK_MAX_BATCH) return set_error(WLX_ERR_ARG, "%s: %d items outside 1..%d", who, n, WLX_SPK_MAX_BATCH);
     long at = 0;
     for (int i = 0; i < n; ++i) {
-        const bool too_short = n_samples[i] < WLX_SPK_MIN_SAMPLES;
-        status[i] = too_short ? WLX_ERR_TOO_SHORT : WLX_OK;
-        if (too_short) {
-            std::fill(out + (size_t)i * sp.embed_dim, out + (size_t)(i + 1) * sp.embed_dim, 0.f);
-        } else {
-            offs[m] = at, widths[m] = spk_frames((long)n_samples[i]), row[m] = i;
-            ++m;
+        if (n_samples[i] < 0 || n_samples[i] > k->max_samples)
+            return set_error(WLX_ERR_ARG, "%s: item %d: %lld samples outside 0..the engine's %d s", who, i, (long long)n_samples[i], k->spec.max_seconds);
+        if (starts && starts[i] < 0) return set_error(WLX_ERR_ARG, "%s: item %d starts at %lld", who, i, (long long)starts[i]);
+        if (n_samples[i] >= WLX_SPK_MIN_SAMPLES) {
+            pl.offs[pl.m] = starts ? (long)starts[i] : at, pl.widths[pl.m] = spk_frames((long)n_samples[i]), pl.row[pl.m] = i;
+            ++pl.m;
         }
         at += (long)n_samples[i];
     }
-    if (m == 0) return WLX_OK;
-    std::lock_guard<std::mutex> g(k->mu);
-    CK(hipSetDevice(k->device));
+    pl.total = at;
+    if (at > k->max_samples)
+        return set_error(WLX_ERR_ARG, "%s: %ld samples in %d items exceed the engine's %d s", who, at, n, k->spec.max_seconds);
+    return WLX_OK;
+}
+
+static void spk_plan_commit(const wlx_spk* k, const int64_t* n_samples, int n, float* out, int32_t* status) {
+    const int E = k->spec.embed_dim;
+    for (int i = 0; i < n; ++i) {
+        const bool too_short = n_samples[i] < WLX_SPK_MIN_SAMPLES;
+        status[i] = too_short ? WLX_ERR_TOO_SHORT : WLX_OK;
+        if (too_short) std::fill(out + (size_t)i * E, out + (size_t)(i + 1) * E, 0.f);
+    }
+}
+
+// The pass itself on k->st, behind whatever the caller put there (an upload, a wait for another stream): item a of the plan is the
+// samples src[offs[a] ...) — the engine's upload buffer or resident audio, the launches do not know which. One launch sequence, one
+// download, one wait. k->mu is held and the device is set.
+static int spk_run_batch(wlx_spk* k, const float* src, const SpkPlan& pl, float* out) {
+    const wlx_spk_spec& sp = k->spec;
     hipStream_t st = k->st;
-    // one upload: the caller's items lie back to back, the short ones among them are carried along and never read
-    CK(hipMemcpyAsync(k->pcm, pcm, (size_t)total * sizeof(float), hipMemcpyHostToDevice, st));
+    const int m = pl.m;
+    int widths[WLX_SPK_MAX_BATCH];
+    std::copy(pl.widths, pl.widths + m, widths);
     CK(hipEventRecord(k->ev[0], st));
-    if (!launch_spk_fbank_batch(k->pcm, offs, widths, m, k->window, k->twiddle, k->mel, sp.n_mels, k->logmel, st) ||
+    if (!launch_spk_fbank_batch(src, pl.offs, widths, m, k->window, k->twiddle, k->mel, sp.n_mels, k->logmel, st) ||
         !launch_spk_cmn_batch(k->logmel, widths, m, sp.n_mels, k->feat16, st))
         return set_error(WLX_ERR_ARG, "front end refused a batch of %d", m);
     CK(hipEventRecord(k->ev[1], st));
@@ -325,11 +341,79 @@ extern "C" int32_t wlx_spk_embed_batch(wlx_spk* k, const float* pcm, const int64
     CK(hipGetLastError());
     CK(hipMemcpyAsync(k->h_emb, k->emb, (size_t)m * sp.embed_dim * sizeof(float), hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
-    for (int a = 0; a < m; ++a) std::copy(k->h_emb + (size_t)a * sp.embed_dim, k->h_emb + (size_t)(a + 1) * sp.embed_dim, out + (size_t)row[a] * sp.embed_dim);
+    for (int a = 0; a < m; ++a) std::copy(k->h_emb + (size_t)a * sp.embed_dim, k->h_emb + (size_t)(a + 1) * sp.embed_dim, out + (size_t)pl.row[a] * sp.embed_dim);
     CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));
     CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
     k->timed = true;
     return WLX_OK;
+}
+
+extern "C" int32_t wlx_spk_embed_batch(wlx_spk* k, const float* pcm, const int64_t* n_samples, int32_t n, float* out, int32_t* status) {
+    if (!k || !pcm || !n_samples || !out || !status) return set_error(WLX_ERR_ARG, "null argument");
+    SpkPlan pl;
+    CKR(spk_plan("wlx_spk_embed_batch", k, nullptr, n_samples, n, pl));
+    spk_plan_commit(k, n_samples, n, out, status);
+    if (pl.m == 0) return WLX_OK;
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    // one upload: the caller's items lie back to back, the short ones among them are carried along and never read
+    CK(hipMemcpyAsync(k->pcm, pcm, (size_t)pl.total * sizeof(float), hipMemcpyHostToDevice, k->st));
+    return spk_run_batch(k, k->pcm, pl, out);
+}
+
+// The same on ranges of a slot item's resident PCM (wlx_pcm_put / wlx_pcm_put_frames): the front end reads s->pcm where the upload route
+// reads k->pcm, nothing else differs, so no sample crosses the bus. The engine's stream is ordered behind the slot's with an event (the
+// resample launches of wlx_pcm_put_frames may still be running); the slot is held for the whole call, so nothing replaces or re-allocates
+// its PCM under the kernels.
+extern "C" int32_t wlx_spk_embed_pcm_batch(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts,
+                                           const int64_t* n_samples, int32_t n, float* out, int32_t* status) {
+    if (!k || !e || !starts || !n_samples || !out || !status) return set_error(WLX_ERR_ARG, "wlx_spk_embed_pcm_batch: null argument");
+    if (e->device != k->device)
+        return set_error(WLX_ERR_ARG, "wlx_spk_embed_pcm_batch: the engine lives on device %d, the speaker engine on %d", e->device, k->device);
+    SpkPlan pl;
+    CKR(spk_plan("wlx_spk_embed_pcm_batch", k, starts, n_samples, n, pl));
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "wlx_spk_embed_pcm_batch: item %d outside the slot's %d", item, s->B);
+    const int64_t resident = s->npcm[item];
+    if (resident <= 0 || !s->pcm) return set_error(WLX_ERR_STATE, "wlx_spk_embed_pcm_batch: item %d: no PCM resident", item);
+    for (int i = 0; i < n; ++i)
+        if (starts[i] > resident - n_samples[i])
+            return set_error(WLX_ERR_STATE, "wlx_spk_embed_pcm_batch: range %d = [%lld, %lld) is not resident (item %d holds %lld samples)", i,
+                             (long long)starts[i], (long long)(starts[i] + n_samples[i]), item, (long long)resident);
+    spk_plan_commit(k, n_samples, n, out, status);
+    if (pl.m == 0) return WLX_OK;
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    if (!s->ev_pcm) CK(hipEventCreateWithFlags(&s->ev_pcm, hipEventDisableTiming));
+    CK(hipEventRecord(s->ev_pcm, s->stream));                 // whatever wrote the PCM on the slot's stream ...
+    CK(hipStreamWaitEvent(k->st, s->ev_pcm, 0));              // ... is finished before the filterbank reads it
+    return spk_run_batch(k, s->pcm + (size_t)item * s->pcm_cap, pl, out);
+}
+
+// The same on absolute stream positions of a device PCM ring. The ring keeps [base, base + resident) contiguous at buf[0 ...) (engine.h
+// Ring): a range never wraps, position p is buf[p - base]. The ring's mutex is held until the pass has been waited for, as in
+// wlx_vad_probs_resident: an append or a trim of the socket thread waits its turn and never moves samples under the kernels. Samples an
+// append put there are final when it returns (it waits for the ring's stream), so there is no stream to order behind.
+extern "C" int32_t wlx_spk_embed_ring_batch(wlx_spk* k, wlx_ring* r, const int64_t* starts, const int64_t* n_samples, int32_t n, float* out,
+                                            int32_t* status) {
+    if (!k || !r || !starts || !n_samples || !out || !status) return set_error(WLX_ERR_ARG, "wlx_spk_embed_ring_batch: null argument");
+    if (r->device != k->device)
+        return set_error(WLX_ERR_ARG, "wlx_spk_embed_ring_batch: the ring lives on device %d, the speaker engine on %d", r->device, k->device);
+    SpkPlan pl;
+    CKR(spk_plan("wlx_spk_embed_ring_batch", k, starts, n_samples, n, pl));
+    std::lock_guard<std::mutex> g(k->mu);
+    std::lock_guard<std::mutex> lr(r->mu);          // no append / trim while the kernels read (the call waits for them below)
+    for (int i = 0; i < n; ++i)
+        if (starts[i] < r->base || starts[i] - r->base > r->resident - n_samples[i])
+            return set_error(WLX_ERR_STATE, "wlx_spk_embed_ring_batch: range %d = [%lld, %lld) is not resident (ring holds [%lld, %lld))", i,
+                             (long long)starts[i], (long long)(starts[i] + n_samples[i]), (long long)r->base, (long long)(r->base + r->resident));
+    spk_plan_commit(k, n_samples, n, out, status);
+    if (pl.m == 0) return WLX_OK;
+    for (int a = 0; a < pl.m; ++a) pl.offs[a] -= (long)r->base;
+    CK(hipSetDevice(k->device));
+    return spk_run_batch(k, r->buf, pl, out);
 }
 
 extern "C" int32_t wlx_spk_debug_timings(wlx_spk* k, float* fbank_ms, float* net_ms) {

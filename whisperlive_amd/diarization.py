@@ -5,7 +5,10 @@ base.py `_identify_speaker`).
 * ``SpeakerEmbedderHIP`` — ctypes binding of the wlx_spk_* entry points: one WeSpeaker ResNet34 engine on one GPU. ``embed(pcm)``
                            returns the L2-normalised embedding, or None under 0.3 s; ``embed_many(pcms)`` the same for a list of
                            segments, packed by ``plan_embed_groups`` into as few wlx_spk_embed_batch passes as the engine's
-                           buffers allow (a file's segments; the streaming server embeds one at a time). ``shared_embedder``
+                           buffers allow (a file's segments; the streaming server embeds one at a time).
+                           ``embed_resident(slot, item, ranges)`` / ``embed_ring(ring, ranges)`` do the same on (start, n_samples)
+                           ranges of audio that is ALREADY in HBM (a slot item's PCM, a session's PCM ring): nothing is uploaded
+                           (wlx_spk_embed_pcm_batch / wlx_spk_embed_ring_batch). ``shared_embedder``
                            keeps one per (checkpoint, device), loaded by the first client that asks for diarization.
 * ``SpeakerDiarizer``    — the reference's online clustering, unchanged in behaviour: cosine similarity against the running
                            centroids, threshold 0.55, 0.9 / 0.1 running average with renormalisation, closest speaker at the cap,
@@ -13,7 +16,8 @@ base.py `_identify_speaker`).
                            (pcm float32, sample_rate) -> unit vector or None, so the clustering is testable without a GPU.
                            ``identify_speakers(audios)`` labels a list of segments: every embedding first (one ``embed_many``
                            call when the embedder has it), then the same clustering step in order, so the labels are those of
-                           ``identify_speaker`` called once per segment.
+                           ``identify_speaker`` called once per segment. ``identify_speakers_resident(source, ranges)`` is
+                           the same on ranges of device-resident audio (``ResidentPcm`` or a PCM ring).
 """
 from __future__ import annotations
 
@@ -24,6 +28,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from .engine import ResidentPcm
 from .spk_weights import SpkSpec
 
 MIN_SECONDS = 0.3
@@ -114,6 +119,41 @@ class SpeakerEmbedderHIP:
                 _lib.check(int(status[row]))
                 result[i] = out[row].copy()
         return result
+
+    def _embed_ranges(self, ranges, call) -> List[Optional[np.ndarray]]:
+        """(start, n_samples) ranges -> embeddings through `call(starts, counts, n, out, status)`, one call per group of
+        plan_embed_groups; a range longer than the engine's max_seconds is cut to it, as `embed` cuts a segment"""
+        if self.h is None:
+            raise _lib.WlxError("speaker engine is closed")
+        cap = self.spec.max_seconds * 16000
+        ranges = [(int(a), min(int(n), cap)) for a, n in ranges]
+        result: List[Optional[np.ndarray]] = [None] * len(ranges)
+        f32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        for group in plan_embed_groups([n for _, n in ranges], cap):
+            starts = np.array([ranges[i][0] for i in group], dtype=np.int64)
+            counts = np.array([ranges[i][1] for i in group], dtype=np.int64)
+            out = np.zeros((len(group), self.spec.embed_dim), dtype=np.float32)
+            status = np.zeros(len(group), dtype=np.int32)
+            _lib.check(call(starts.ctypes.data_as(i64p), counts.ctypes.data_as(i64p), len(group), out.ctypes.data_as(f32p),
+                            status.ctypes.data_as(C.POINTER(C.c_int32))))
+            for row, i in enumerate(group):
+                if status[row] == _lib.ERR_TOO_SHORT:
+                    continue
+                _lib.check(int(status[row]))
+                result[i] = out[row].copy()
+        return result
+
+    def embed_resident(self, slot, item: int, ranges) -> List[Optional[np.ndarray]]:
+        """`embed` of samples [start, start + n) of the PCM resident in `item` of `slot`, for every (start, n) of `ranges`; None where a
+        range is under 0.3 s. No audio is uploaded; each embedding has the bits `embed` gives for those samples. Raises WlxError
+        (ERR_STATE) when a range is not resident. The slot's lock is held for the calls: a slot serves one call at a time."""
+        with slot.lock:
+            return self._embed_ranges(ranges, lambda *a: self.lib.wlx_spk_embed_pcm_batch(self.h, slot.engine._h, slot.sid, int(item), *a))
+
+    def embed_ring(self, ring, ranges) -> List[Optional[np.ndarray]]:
+        """the same on ABSOLUTE stream positions of a device PCM ring (whisperlive_amd.engine.PcmRing); ERR_STATE when a range has been
+        trimmed away or has not arrived"""
+        return self._embed_ranges(ranges, lambda *a: self.lib.wlx_spk_embed_ring_batch(self.h, ring._h, *a))
 
     def timings(self) -> Tuple[float, float]:
         """device milliseconds of the last embed: (filterbank, network)"""
@@ -222,6 +262,34 @@ class SpeakerDiarizer:
                     emb = np.asarray(emb)
                     embs[i] = emb / np.linalg.norm(emb)
         return [self._assign(emb) for emb in embs]
+
+    def supports_resident(self, source) -> bool:
+        """True when `identify_speakers_resident` can serve `source` (a ResidentPcm, or a PCM ring): the embedder has the entry
+        point. An embedder that is not loaded yet is loaded to find out, as `identify_speakers` would."""
+        if source is None:
+            return False
+        self._ensure_embedder()
+        return hasattr(self._embed, "embed_resident" if isinstance(source, ResidentPcm) else "embed_ring")
+
+    def identify_speakers_resident(self, source, ranges) -> List[Optional[str]]:
+        """`identify_speakers` on (start, n_samples) ranges of 16 kHz audio that is resident on the device: `source` is a ResidentPcm
+        (a slot item) or a PCM ring (absolute stream positions). Every embedding first, without an upload; then the same clustering
+        step in order, so the labels equal `identify_speakers` on the same samples. An error of the embedder (a range that is not
+        resident) is raised before any speaker is touched."""
+        self._ensure_embedder()
+        ranges = [(int(a), int(n)) for a, n in ranges]
+        if isinstance(source, ResidentPcm):
+            embs = self._embed.embed_resident(source.slot, source.item, ranges)
+        else:
+            embs = self._embed.embed_ring(source, ranges)
+        units = []
+        for (_, n), emb in zip(ranges, embs):
+            if emb is None or n < 16000 * MIN_SECONDS:
+                units.append(None)
+            else:
+                emb = np.asarray(emb)
+                units.append(emb / np.linalg.norm(emb))
+        return [self._assign(emb) for emb in units]
 
     def _assign(self, emb):
         """the clustering step: the label for a unit-norm embedding (None stays None), the centroids updated"""

@@ -128,6 +128,25 @@ class PcmRing:
             self._h = None
 
 
+class ResidentPcm:
+    """16 kHz mono audio resident in item `item` of `slot` (after pcm_put / put_frames): `n_samples` of it — what a reader on the device
+    (SpeakerEmbedderHIP.embed_resident) needs to find it. The handle does not own the slot: the thread that made it keeps the slot
+    until it is done with the handle. `intact()`: the item still holds those samples, as far as the handle can tell — `state`, when
+    given, is the dict whose "resident" entry the owner clears when it overwrites the item (batched.DeviceChunks.shared)."""
+
+    def __init__(self, slot: "Slot", item: int, n_samples: int, state: Optional[dict] = None):
+        self.slot, self.item, self.n_samples, self.state = slot, int(item), int(n_samples), state
+
+    def intact(self) -> bool:
+        if self.slot.sid < 0 or self.n_samples <= 0 or (self.state is not None and not self.state.get("resident", False)):
+            return False
+        count = getattr(self.slot, "pcm_count", None)           # (a test double of a slot without the entry point: not resident)
+        if count is None:
+            return False
+        with self.slot.lock:
+            return count(self.item) == self.n_samples
+
+
 class Slot:
     """One unit of concurrency (own HIP stream + scratch). Not re-entrant: one call at a time per slot."""
 
@@ -174,6 +193,12 @@ class Slot:
         if n.value:
             check(self.lib.wlx_pcm_get(self.engine._h, self.sid, item, _f32p(out), out.size, C.byref(n)))
         return out
+
+    def pcm_count(self, item: int = 0) -> int:
+        """samples of PCM resident in the item (0: none)"""
+        n = C.c_int64(0)
+        check(self.lib.wlx_pcm_get(self.engine._h, self.sid, item, None, 0, C.byref(n)))
+        return n.value
 
     def logmel_ring(self, ring: "PcmRing", ranges: Sequence[Tuple[int, int]], item: int = 0) -> int:
         """log-mel of the concatenation of ring ranges [(start, end), ...] (absolute positions) -> frames; see wlx_logmel_ring"""

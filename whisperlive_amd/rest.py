@@ -29,6 +29,7 @@ from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 from . import metrics as wl_metrics
+from ._lib import WlxError as _WlxError
 from .sharding import assign_gpu
 
 SUPPORTED_FORMATS = ["json", "text", "srt", "verbose_json", "vtt"]
@@ -156,22 +157,51 @@ def render_subtitles(segments, response_format: str) -> str:
     return "\n".join(output)
 
 
-def speaker_labels_for_segments(segments, audio_np, diarizer, sample_rate: int = 16000) -> Dict[int, str]:
-    """server.py:585-598. A diarizer with `identify_speakers` gets all non-empty ranges in one call (SpeakerDiarizer embeds them in
-    batches on the device); the labels are those of the one-by-one loop, which any other diarizer still gets."""
-    if diarizer is None or audio_np is None:
-        return {}
+def segment_sample_ranges(segments, n_samples: int, sample_rate: int = 16000) -> List[Tuple[int, int, int]]:
+    """(segment index, start, end) in samples for every segment with audio in [0, n_samples): int(t * sample_rate), clamped to the
+    file; an empty segment or one outside the file has no entry (server.py:588-592)"""
     ranges = []
     for index, segment in enumerate(segments):
         start = max(0, int(segment.start * sample_rate))
-        end = min(len(audio_np), int(segment.end * sample_rate))
+        end = min(int(n_samples), int(segment.end * sample_rate))
         if end > start:
             ranges.append((index, start, end))
+    return ranges
+
+
+def speaker_labels_for_segments(segments, audio_np, diarizer, sample_rate: int = 16000, resident=None) -> Dict[int, str]:
+    """server.py:585-598. A diarizer with `identify_speakers` gets all non-empty ranges in one call (SpeakerDiarizer embeds them in
+    batches on the device); the labels are those of the one-by-one loop, which any other diarizer still gets.
+    `resident`: the file's 16 kHz audio where the transcription left it on the device (engine.ResidentPcm), or None. With it, and a
+    diarizer that can read it (`identify_speakers_resident`), the segments are embedded from there and `audio_np` is not touched.
+    `audio_np` may be a callable that returns the waveform: it is called only when the host route is taken (the file is then decoded a
+    second time), which is also where a resident route that fails before any speaker was assigned ends up."""
+    if diarizer is None or (audio_np is None and resident is None):
+        return {}
+    if resident is not None and sample_rate == 16000 and _reads_resident(diarizer, resident):
+        ranges = segment_sample_ranges(segments, resident.n_samples, sample_rate)
+        try:
+            speakers = diarizer.identify_speakers_resident(resident, [(start, end - start) for _, start, end in ranges])
+            return {index: speaker for (index, _, _), speaker in zip(ranges, speakers) if speaker}
+        except _WlxError as e:          # evicted or released under us: refused before any launch and before any clustering step
+            logging.warning(f"speaker labels: the resident audio could not be read ({e}); decoding the file again")
+    if callable(audio_np):
+        audio_np = audio_np()
+    if audio_np is None:
+        return {}
+    ranges = segment_sample_ranges(segments, len(audio_np), sample_rate)
     if hasattr(diarizer, "identify_speakers"):
         speakers = diarizer.identify_speakers([audio_np[start:end] for _, start, end in ranges], sample_rate)
     else:
         speakers = [diarizer.identify_speaker(audio_np[start:end], sample_rate) for _, start, end in ranges]
     return {index: speaker for (index, _, _), speaker in zip(ranges, speakers) if speaker}
+
+
+def _reads_resident(diarizer, resident) -> bool:
+    if not hasattr(diarizer, "identify_speakers_resident"):
+        return False
+    supports = getattr(diarizer, "supports_resident", None)
+    return bool(supports(resident)) if supports is not None else True
 
 
 class _HttpError(Exception):
@@ -291,6 +321,17 @@ class RestServer:
             return transcriber.transcribe(data, vad_filter=False, **kw)
         from .batched import BatchedInferencePipeline
         return BatchedInferencePipeline(transcriber).transcribe(data, vad_filter=True, batch_size=self.file_batch_size, **kw)
+
+    @staticmethod
+    def resident_audio(transcriber):
+        """the file the calling thread just transcribed, where it lies on the device (engine.ResidentPcm), or None: a transcriber
+        without the front end, a file that went the host route, a slot already released"""
+        get = getattr(transcriber, "resident_file_audio", None)
+        try:
+            return get() if get is not None else None
+        except Exception:  # noqa: BLE001 — labelling then takes the host route
+            logging.exception("rest: resident_file_audio failed")
+            return None
 
     def create_rest_diarizer(self, known_speaker_names, known_speaker_references, device_index: int):
         """server.py:550-583 on this GPU's shared embedder; ValueError = a 400"""
@@ -523,8 +564,11 @@ class _Handler(BaseHTTPRequestHandler):
                 except ValueError as e:
                     raise _HttpError(400, {"error": str(e)})
                 if rest_diarizer is not None:
-                    from .audio_io import load_audio
-                    speaker_labels = speaker_labels_for_segments(segments, load_audio(file.data), rest_diarizer)
+                    # from the audio the transcription left in the thread's slot (held until _release below); the file is decoded
+                    # a second time only when nothing is resident (host-resampled rate, an engine without the front end)
+                    from . import audio_io
+                    speaker_labels = speaker_labels_for_segments(segments, lambda: audio_io.load_audio(file.data), rest_diarizer,
+                                                                 resident=rest.resident_audio(transcriber))
                 for index, seg in enumerate(segments):
                     seg_dict = {"id": seg.id, "seek": seg.seek, "start": seg.start, "end": seg.end, "text": seg.text.strip(),
                                 "tokens": seg.tokens, "temperature": seg.temperature, "avg_logprob": seg.avg_logprob,

@@ -27,6 +27,7 @@ import numpy as np
 
 from . import metrics as wl_metrics
 from . import vad as _vad
+from ._lib import WlxError as _WlxError
 
 
 class ServeClientBase:
@@ -436,6 +437,37 @@ class ServeClientHIP(ServeClientBase):
             return input_sample
         from .transcriber import ResidentAudio
         return ResidentAudio(ring, ca[0], ca[1], input_sample)
+
+    def _identify_speaker(self, segment):
+        """The base class's step, reading the segment in the device PCM ring when the session has one and the diarizer's embedder
+        can: the ring mirrors `frames_np` sample for sample (buffer index k = stream position round(frames_offset * RATE) + k, as
+        `_chunk_abs`), so the label is computed on the very samples the host slice holds, without uploading them. A segment that a trim
+        has taken out of the ring meanwhile, or any other refusal, goes the host route."""
+        ring, diar = self._ring, self.diarization
+        if diar is None or self.frames_np is None or not ring or not hasattr(diar, "identify_speakers_resident"):
+            return super()._identify_speaker(segment)
+        try:
+            if not diar.supports_resident(ring):
+                return super()._identify_speaker(segment)
+            s0 = int(self.get_segment_start(segment) * self.RATE)
+            s1 = int(self.get_segment_end(segment) * self.RATE)
+            with self.lock:             # one consistent view of the buffer; the ring call itself runs outside (an append takes this lock)
+                base = max(0, int((self.timestamp_offset - self.frames_offset) * self.RATE))
+                origin, held = int(round(self.frames_offset * self.RATE)), self.frames_np.shape[0]
+                piece = self.frames_np[base + s0: base + s1]
+            if base + s0 < 0 or base + s1 < 0:           # (a slice that counts from the end: only the host form has a meaning for it)
+                return super()._identify_speaker(segment)
+            a, b = min(base + s0, held), min(base + s1, held)
+            if b - a < self.RATE * 0.3:
+                return None
+            try:
+                return diar.identify_speakers_resident(ring, [(origin + a, b - a)])[0]
+            except _WlxError as e:      # trimmed away under us: `piece` still holds the samples
+                logging.debug(f"speaker step fell back to the host slice: {e}")
+                return diar.identify_speaker(piece, self.RATE)
+        except Exception as e:  # noqa: BLE001
+            logging.error(f"Diarization error: {e}")
+            return None
 
     def transcribe_audio(self, input_sample):
         worker = ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS.get(self.device_index)

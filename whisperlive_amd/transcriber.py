@@ -33,7 +33,7 @@ from . import _lib
 from . import vad as _vad
 from . import word_timing as _wt
 from ._lib import ERR_ARG as _ERR_ARG, WlxError as _WlxError
-from .engine import GenerationResult, HipWhisperEngine, Slot, TokenIds
+from .engine import GenerationResult, HipWhisperEngine, ResidentPcm, Slot, TokenIds
 from .specs import WhisperSpec, get_spec, spec_from_state_dict
 from .tokenizer import LANGUAGE_CODES, Tokenizer
 from .types import Segment, TranscriptionInfo, TranscriptionOptions, Word  # noqa: F401
@@ -426,8 +426,19 @@ class WhisperModelHIP:
                 old.close()
         return s
 
+    def resident_file_audio(self):
+        """The 16 kHz audio the calling thread's last file transcription (`transcribe`, or BatchedInferencePipeline on this model) left
+        resident in its slot, as an engine.ResidentPcm — for what reads the audio after the transcription (speaker labels) without a
+        second decode. None when that call took the host route, when the item has been overwritten since, or after release_slot():
+        a released slot may be refilled by another request, so the handle is good only while this thread keeps its slot."""
+        h = getattr(self._tls, "file_audio", None)
+        if h is None or h.slot is not getattr(self._tls, "slot", None) or not h.intact():
+            return None
+        return h
+
     def release_slot(self):
         """Hand the calling thread's slot back to the pool (a session thread calls this when it exits)."""
+        self._tls.file_audio = None
         s = getattr(self._tls, "slot", None)
         if s is not None:
             self._tls.slot = None
@@ -580,6 +591,7 @@ class WhisperModelHIP:
             multilingual = False
         resident = None
         file_slot = None                 # the slot whose PCM buffer already holds this call's audio (file input)
+        self._tls.file_audio = None      # (resident_file_audio: what an earlier call of this thread left is about to be overwritten)
         if isinstance(audio, ResidentAudio):
             resident, audio = audio, audio.host
         if not isinstance(audio, np.ndarray):
@@ -664,6 +676,7 @@ class WhisperModelHIP:
                         audio = np.concatenate(chunks, axis=0)
             if n_frames is None and file_slot is slot:
                 n_frames = slot.logmel_resident()              # the file's PCM is resident already (put_frames): no second upload
+                self._tls.file_audio = ResidentPcm(slot, 0, audio.shape[0])
             if n_frames is None:
                 n_frames = slot.logmel(audio)                  # PCM -> HBM -> log-mel, stays on the device
             features = DeviceFeatures(slot, n_frames)
