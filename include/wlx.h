@@ -64,7 +64,8 @@ typedef enum {
     WLX_ERR_WEIGHT = 3,   /* missing / mis-shaped weight tensor */
     WLX_ERR_STATE = 4,    /* call order (e.g. generate before encode) */
     WLX_ERR_NOMEM = 5,
-    WLX_ERR_TOO_SHORT = 6 /* speaker embedding: under 0.3 s of audio (the caller labels the segment with no speaker) */
+    WLX_ERR_TOO_SHORT = 6,/* speaker embedding: under 0.3 s of audio (the caller labels the segment with no speaker) */
+    WLX_ERR_DATA = 7      /* damaged input (wlx_flac_probe, wlx_pcm_put_flac: a FLAC stream that is not a refused SHAPE but broken) */
 } wlx_status;
 
 /* Whisper architecture. n_audio_ctx = 1500, n_text_ctx = 448, head_dim = 64. */
@@ -187,6 +188,43 @@ int32_t wlx_logmel_resident(wlx_engine* e, int32_t slot, int32_t item, int32_t* 
 #define WLX_PCM_MAX_CHANNELS 8
 int32_t wlx_pcm_put_frames(wlx_engine* e, int32_t slot, int32_t item, const void* frames, int64_t n_frames, int32_t channels,
                            int32_t sample_format, int32_t sample_rate, int64_t* n_out);
+/* ---- FLAC front end (PRODUCT entry points of the file path, beside wlx_pcm_put_frames) ----
+ * Replaces the Python FLAC decoder of whisperlive_amd/audio_io.py (read_flac: a loop over Rice symbols and LPC samples at well under
+ * real time) in front of wlx_pcm_put_frames: the file's COMPRESSED bytes cross PCIe once, the frames are decoded in HBM — FLAC frames are
+ * independent of one another, one lane each — and the existing resampler reads the decoded float32 frames there.
+ * wlx_flac_probe is HOST ONLY (no device work, like wlx_vad_segments): the metadata blocks up to the last one, STREAMINFO, and the frame
+ * index, built WITHOUT decoding: a position starts a frame only if its header parses with no reserved code, its CRC-8 matches, its
+ * coded frame / sample number (UTF-8 style, up to 36 bits; fixed and variable block size) is the expected next one and the CRC-16 of the
+ * previous frame's bytes up to it matches; anything less is a false sync inside a frame. The last frame ends at the end of the data
+ * (bytes behind the last frame, a trailing tag for instance, fail its CRC-16). *out: the stream's shape, its frame count, and
+ * served = 1 when wlx_pcm_put_flac takes it: 1..8 channels, <= 24 bits per sample, <= 3600 s, a rate wlx_pcm_put_frames serves (RATES).
+ * WLX_ERR_DATA, a DAMAGED stream: no fLaC magic, metadata past the end, no STREAMINFO, lost sync, a frame number out of sequence, no
+ * CRC-consistent continuation, a sample count that disagrees with STREAMINFO. WLX_ERR_ARG, a container or shape the index does not take
+ * apart: Ogg FLAC, an ID3 tag in front of the magic, a frame that changes the rate, width, channel count or blocking mid-stream.
+ * wlx_pcm_put_flac: afterwards the item's resident PCM is BIT-IDENTICAL to that of wlx_pcm_put_frames(read_flac(bytes), WLX_PCM_F32,
+ * channels, sample_rate): integers of at most 24 bits are exact in float32 and the scale 2^-(bps - 1) is a power of two, so the device
+ * frames are read_flac's float64 quotients rounded to float32, and from there it is the same kernel on the same values (one launch
+ * over the whole file; the result does not depend on block seams). *info_out (nullable) as wlx_flac_probe, written whenever the index
+ * succeeds; *n_out = samples resident. Everything wlx_flac_probe can find, a stream with served = 0 (WLX_ERR_ARG: the caller decodes on
+ * the host, as for an unserved WAV rate) and a scratch that cannot be had (WLX_ERR_NOMEM) are answered BEFORE any launch and leave the
+ * item's resident PCM exactly as it was. Then: one upload of the bytes and the frame table through the slot's pinned staging blocks (two
+ * in flight), the frame decode, the finish (stereo decorrelation, scale, interleave), the resample, ONE wait, and the per-frame status
+ * words are read: a frame that does not decode (ran past its end, reserved code, inconsistent partition order, did not end exactly at
+ * its CRC-16) gives WLX_ERR_DATA and leaves NO PCM resident in the item, as a failed wlx_pcm_put_frames run does. The decoder is
+ * memory-safe on any bit pattern. The STREAMINFO MD5 is NOT checked on this route (it would mean downloading the samples): the CRC-16
+ * of every frame on the host and the end check of every frame on the device stand in for it. The scratch (bytes, table, int32 planes,
+ * float32 frames: ~8 bytes per sample and channel) is the slot's, grows on demand, and at most 16 MB of it stay allocated after the
+ * call. wlx_pcm_put's conventions hold: recorded log-mel requests that read the item go out first, one call per slot at a time, never
+ * the null stream; the caller's bytes may be reused on return. */
+typedef struct {
+    int32_t sample_rate, channels, bits_per_sample;
+    int64_t total_samples;
+    int32_t n_frames, max_blocksize;
+    int32_t served;   /* 1: wlx_pcm_put_flac takes it; 0: host route */
+} wlx_flac_info;
+int32_t wlx_flac_probe(const void* bytes, int64_t n_bytes, wlx_flac_info* out);
+int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, const void* bytes, int64_t n_bytes, wlx_flac_info* info_out,
+                         int64_t* n_out);
 /* ---- batched long-form front end (PRODUCT entry points of BatchedInferencePipeline: whisperlive_amd/batched.py) ----
  * Replaces faster_whisper.vad.collect_chunks + one FeatureExtractor call per chunk of the reference's BatchedInferencePipeline.transcribe
  * (whisper_live/transcriber/transcriber_faster_whisper.py:424-429): B chunks are cut out of ONE resident PCM buffer into B feature items
@@ -645,6 +683,16 @@ int32_t wlx_debug_resample(int32_t device, const void* frames, int64_t n_frames,
 int32_t wlx_debug_resample_timed(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
                                  int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out,
                                  float* kernel_ms_out);
+
+/* The FLAC frame decoder and the finish kernel (csrc/flac.hip, csrc/flac_core.h) without the resampler, on a private stream of `device`:
+ * the stream's decoded INTEGER samples, interleaved [n][channels], nothing scaled or resampled; *n_frames_out = n (samples per
+ * channel), cap_samples = the int32 values samples_out holds (>= n * channels). Any rate; <= 24 bits, <= 8 channels. The index runs
+ * first: WLX_ERR_DATA / WLX_ERR_ARG as wlx_flac_probe before any launch; WLX_ERR_DATA after the one wait for a frame that does not decode. */
+int32_t wlx_debug_flac_decode(int32_t device, const void* bytes, int64_t n_bytes, int32_t* samples_out, int64_t cap_samples,
+                              int64_t* n_frames_out, int32_t* channels_out);
+/* The last completed wlx_pcm_put_flac of the slot (scripts/flac_time.py): ms_out[5] = host index + CRC time (wall), then the HIP-event
+ * times of the upload (the host's copies into the pinned blocks included), flac_frames_kernel, flac_finish_kernel and the resample launch. */
+int32_t wlx_debug_flac_timings(wlx_engine* e, int32_t slot, float* ms_out);
 
 /* Word alignment's post-processing kernels (csrc/align.hip), same conventions; n <= WLX_ALIGN_MAX_BATCH entries packed back to back, outputs
  * copied in AND out. wlx_debug_dtw: the DTW kernel alone on caller matrices x [N[e]][M[e]] float32 (1 <= N <= 448, 1 <= M <= 1500,

@@ -309,6 +309,18 @@ def read_flac(src: PathOrFile, verify_md5: bool = True) -> Tuple[np.ndarray, int
     return (pcm / float(1 << (bps - 1))).astype(np.float32), sr
 
 
+def flac_probe(data: bytes):
+    """Metadata and frame index of a FLAC stream, on the host, without decoding it (wlx_flac_probe: STREAMINFO, and the CRC-8 / CRC-16 of
+    every frame) -> _lib.wlx_flac_info (sample_rate, channels, bits_per_sample, total_samples, n_frames, max_blocksize, served: whether
+    the device route engine.Slot.put_flac takes the stream). Raises WlxError: code ERR_DATA for a damaged stream, ERR_ARG for a container
+    or a mid-stream change the index does not take apart."""
+    from . import _lib
+    data = bytes(data)
+    info = _lib.wlx_flac_info()
+    _lib.check(_lib.load().wlx_flac_probe(data, len(data), info))
+    return info
+
+
 # ---------------------------------------------------------------------------------------------------------------- API
 def load_audio(src: PathOrFile, sampling_rate: int = 16000) -> np.ndarray:
     """File / bytes / file object -> mono float32 waveform at `sampling_rate` (the shape ``transcribe`` expects)."""

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import vad as _vad
 from . import word_timing as _wt
-from ._lib import ERR_ARG as _ERR_ARG, LM_MAXRANGES as _MAXRANGES, WlxError as _WlxError
+from ._lib import ERR_ARG as _ERR_ARG, ERR_DATA as _ERR_DATA, LM_MAXRANGES as _MAXRANGES, WlxError as _WlxError
 from .engine import ResidentPcm
 from .tokenizer import Tokenizer
 from .transcriber import EncoderOutput, get_compression_ratio, get_suppressed_tokens, pad_or_trim, restore_speech_timestamps
@@ -269,22 +269,38 @@ class BatchedInferencePipeline:
         if not isinstance(audio, np.ndarray):
             if not isinstance(audio, (str, bytes, bytearray)) and not hasattr(audio, "read"):
                 raise TypeError("audio must be a float32 numpy waveform at 16 kHz, or a WAV / FLAC path, bytes or file object")
-            from .audio_io import frames_to_mono, read_audio
+            from .audio_io import _read_all, frames_to_mono, read_audio
             from .engine import resample_supported
-            file_frames, file_sr = read_audio(audio)
-            on_device = (device and sampling_rate == 16000 and file_frames.shape[0] > 0 and hasattr(slot, "put_frames")
-                         and resample_supported(file_sr, file_frames.shape[1]))
-            if on_device:
+            data = _read_all(audio)
+            # a FLAC file is decoded on the device (Slot.put_flac leaves resident what put_frames(read_flac(file)) would); a stream that
+            # route does not serve keeps the host decode below, a damaged one is the ValueError the host decoder raises
+            on_device = False
+            if device and data[:4] == b"fLaC" and sampling_rate == 16000 and hasattr(slot, "put_flac"):
                 try:
                     with slot.lock:
-                        n_samples = slot.put_frames(file_frames, file_sr)
-                    host_audio = slot.pcm          # fetched only when something on the host needs it
+                        n_samples, _ = slot.put_flac(data)
+                    host_audio = slot.pcm
+                    on_device = True
                 except _WlxError as e:
-                    if e.code != _ERR_ARG:             # only a REFUSED shape (nothing was launched) keeps the host route
+                    if e.code == _ERR_DATA:
+                        raise ValueError(f"damaged FLAC stream: {e}") from e
+                    if e.code != _ERR_ARG:
                         raise
-                    on_device = False
             if not on_device:
-                audio = frames_to_mono(file_frames, file_sr, sampling_rate)
+                file_frames, file_sr = read_audio(data)
+                on_device = (device and sampling_rate == 16000 and file_frames.shape[0] > 0 and hasattr(slot, "put_frames")
+                             and resample_supported(file_sr, file_frames.shape[1]))
+                if on_device:
+                    try:
+                        with slot.lock:
+                            n_samples = slot.put_frames(file_frames, file_sr)
+                        host_audio = slot.pcm          # fetched only when something on the host needs it
+                    except _WlxError as e:
+                        if e.code != _ERR_ARG:             # only a REFUSED shape (nothing was launched) keeps the host route
+                            raise
+                        on_device = False
+                if not on_device:
+                    audio = frames_to_mono(file_frames, file_sr, sampling_rate)
         if n_samples is None:
             audio = np.ascontiguousarray(audio, dtype=np.float32)
             host_audio, n_samples = audio, audio.shape[0]

@@ -62,6 +62,9 @@ struct Slot {
     unsigned* gmax = nullptr;
     ResampleStage rs{};                              // staging of wlx_pcm_put_frames, allocated at its first call (engine.hip)
     bool rs_ready = false;
+    // wlx_pcm_put_flac (flac.hip): ONE device scratch for file bytes | frame table | status words | int32 planes | float32 frames, grown
+    // on demand and owned by name; a call keeps at most 2 * RS_BLOCK_BYTES of it afterwards. ev: upload / frames / finish / resample marks
+    struct FlacScratch { unsigned char* buf = nullptr; size_t cap = 0; hipEvent_t ev[5] = {}; float index_ms = 0.f; bool timed = false; } flac;
     long long* d_rng = nullptr;                      // [2 * WLX_LM_MAXRANGES] range table of the last wlx_logmel_ring
     // wlx_logmel_chunks: [B] chunk descriptors and [B][WLX_LM_MAXRANGES][2] range pairs, pinned staging and device copy (allocated at
     // its first call); `ck_staged` is recorded behind the copy: the next call waits for it before it rewrites the pinned side
@@ -166,6 +169,9 @@ struct SlotGuard {
 };
 int slot_acquire(wlx_engine* e, int slot, SlotGuard& g);                                  // engine.hip
 int create_slot_stream(int device, hipStream_t* out, bool* dedicated_out);
+int flush_logmel(Engine* e, Slot* s);                      // engine.hip: the recorded log-mel requests go out
+int slot_grow_audio(Engine* e, Slot* s, size_t n_samples); // engine.hip: PCM + feature buffers for n_samples per item
+int slot_resample_stage(Slot* s);                          // engine.hip: Slot::rs, allocated at the first call
 extern std::atomic<int> g_dedicated_live[64];      // live slots with a hardware queue of their own, per device (create_slot_stream)
 extern std::atomic<int> g_slots_live[64];          // live slots per device
 

@@ -184,6 +184,8 @@ static void slot_free(Slot* s) {
     }
     if (s->align_scores) (void)hipFree(s->align_scores);
     if (s->align_post) (void)hipFree(s->align_post);
+    if (s->flac.buf) (void)hipFree(s->flac.buf);
+    for (hipEvent_t ev : s->flac.ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {s->ev_al0, s->ev_al1, s->ev_al2}) if (ev) (void)hipEventDestroy(ev);
     for (auto& kv : s->graphs) (void)hipGraphExecDestroy(kv.second);
     for (void* p : s->allocs) (void)hipFree(p);
@@ -273,7 +275,7 @@ int wlx::slot_acquire(wlx_engine* e, int slot, SlotGuard& g) {
     return WLX_OK;
 }
 
-static int slot_grow_audio(Engine* e, Slot* s, size_t n_samples) {
+int wlx::slot_grow_audio(Engine* e, Slot* s, size_t n_samples) {
     if (n_samples <= s->pcm_cap) return WLX_OK;
     // grow PCM + feature buffers (sizes rounded up to whole 30 s windows)
     size_t cap = ((n_samples + 479999) / 480000) * 480000;
@@ -540,7 +542,7 @@ extern "C" int32_t wlx_slot_destroy(wlx_engine* e, int32_t slot) {
 // Log-mel requests are collected and launched together (round 4): wlx_logmel_resident only records the item; the launches — ONE set of
 // three kernels for all recorded items — go out in front of the first consumer of the features (wlx_encode, wlx_features_get), of a
 // timing read, or of anything that overwrites what a recorded item depends on (its PCM, the audio buffers).
-static int flush_logmel(Engine* e, Slot* s) {
+int wlx::flush_logmel(Engine* e, Slot* s) {
     if (s->lm_items.empty()) return WLX_OK;
     CK(hipSetDevice(e->device));
     CK(hipEventRecord(s->ev_lm0, s->stream));
@@ -623,6 +625,18 @@ extern "C" int32_t wlx_pcm_put(wlx_engine* e, int32_t slot, int32_t item, const 
     return WLX_OK;
 }
 
+// the staging of the file front ends (wlx_pcm_put_frames, wlx_pcm_put_flac): two pinned and two device blocks, for the slot's life
+int wlx::slot_resample_stage(Slot* s) {
+    if (s->rs_ready) return WLX_OK;
+    for (int b = 0; b < 2; ++b) {
+        if (!s->rs.pinned[b]) CKR(halloc(s->host_allocs, &s->rs.pinned[b], RS_BLOCK_BYTES));
+        if (!s->rs.dev[b]) CKR(dalloc(s->allocs, &s->rs.dev[b], RS_BLOCK_BYTES, false));
+        if (!s->rs.copied[b]) CK(hipEventCreateWithFlags(&s->rs.copied[b], hipEventDisableTiming));
+    }
+    s->rs_ready = true;
+    return WLX_OK;
+}
+
 // file frames -> 16 kHz mono float32 in the item's PCM buffer (resample.hip): wlx_pcm_put with the conversion, the down-mix and the
 // resampler on the device. Everything is validated before the first byte of `frames` is read.
 extern "C" int32_t wlx_pcm_put_frames(wlx_engine* e, int32_t slot, int32_t item, const void* frames, int64_t n_frames, int32_t channels,
@@ -643,14 +657,7 @@ extern "C" int32_t wlx_pcm_put_frames(wlx_engine* e, int32_t slot, int32_t item,
         CKR(flush_logmel(e, s));            // a recorded log-mel request reads this item's PCM (or the buffers are about to be re-allocated)
     CKR(slot_grow_audio(e, s, (size_t)n));
     const long long block = resample_default_block(channels, sample_format);
-    if (!s->rs_ready) {                     // two pinned and two device blocks, for the slot's life
-        for (int b = 0; b < 2; ++b) {
-            if (!s->rs.pinned[b]) CKR(halloc(s->host_allocs, &s->rs.pinned[b], RS_BLOCK_BYTES));
-            if (!s->rs.dev[b]) CKR(dalloc(s->allocs, &s->rs.dev[b], RS_BLOCK_BYTES, false));
-            if (!s->rs.copied[b]) CK(hipEventCreateWithFlags(&s->rs.copied[b], hipEventDisableTiming));
-        }
-        s->rs_ready = true;
-    }
+    CKR(slot_resample_stage(s));
     s->npcm[item] = 0;                      // (a failed run leaves no half-written audio resident)
     CKR(resample_run(pl, frames, n_frames, channels, sample_format, block, s->rs, s->pcm + (size_t)item * s->pcm_cap, s->stream, nullptr));
     s->npcm[item] = n;

@@ -112,5 +112,7 @@ long long resample_default_block(int channels, int sample_format);        // fra
 // kernel_ms (nullable): the launches' summed HIP-event time.
 int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames, int channels, int sample_format, long long block_frames,
                  ResampleStage& sg, float* d_out, hipStream_t st, float* kernel_ms);
+// device float32 frames [n_frames][channels] -> d_out[0 .. out_len): one launch on `st`, no copy, no wait (the FLAC front end, flac.hip)
+int resample_run_device(const ResamplePlan& pl, const float* d_frames, long long n_frames, int channels, float* d_out, hipStream_t st);
 
 }  // namespace wlx

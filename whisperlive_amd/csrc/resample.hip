@@ -268,6 +268,20 @@ int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames,
     return rc;
 }
 
+// The device-source path (flac.hip): the file's float32 frames are in HBM already, so the whole file is ONE block — raw = the device
+// frames, j_base = 0, raw_frames = n_frames — and one launch of the same kernel with the same arithmetic. Does not wait.
+int resample_run_device(const ResamplePlan& pl, const float* d_frames, long long n_frames, int channels, float* d_out, hipStream_t st) {
+    const long long n_out = resample_out_len(pl, n_frames);
+    if (n_out <= 0) return WLX_OK;
+    ResampleArgs p{};
+    p.raw = d_frames; p.j_base = 0; p.raw_frames = n_frames; p.n_frames = n_frames; p.channels = channels;
+    p.up = pl.up; p.down = pl.down; p.half_len = pl.half_len; p.tile = pl.tile; p.taps = pl.taps; p.out = d_out; p.m0 = 0; p.m1 = n_out;
+    const unsigned grid = (unsigned)((n_out + pl.tile - 1) / pl.tile);
+    hipLaunchKernelGGL(resample_kernel<WLX_PCM_F32>, dim3(grid), dim3(RS_THREADS), rs_lds_bytes(pl.up, pl.down, pl.half_len, pl.tile), st, p);
+    CK(hipGetLastError());
+    return WLX_OK;
+}
+
 // one validation for the product entry point and the hook: everything that does not need a device
 int resample_check_args(const void* frames, long long n_frames, int channels, int sample_format, int sample_rate) {
     if (n_frames < 0) return set_error(WLX_ERR_ARG, "negative frame count");

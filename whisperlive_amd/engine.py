@@ -147,6 +147,19 @@ class ResidentPcm:
             return count(self.item) == self.n_samples
 
 
+class FlacFrames:
+    """The frames of a FLAC file, still compressed: what Slot.put_frames takes in place of decoded frames (Slot.put_flac makes one).
+    sample_rate: STREAMINFO's, read here without the library (0 when the first metadata block is not a STREAMINFO: the library then
+    says what is wrong with the stream); info: the stream's shape (_lib.wlx_flac_info) once put_frames has taken the frames."""
+
+    def __init__(self, data: bytes):
+        self.data = bytes(data)
+        d = self.data
+        ok = len(d) >= 42 and d[:4] == b"fLaC" and (d[4] & 0x7F) == 0
+        self.sample_rate = int.from_bytes(d[18:21], "big") >> 4 if ok else 0
+        self.info = None
+
+
 class Slot:
     """One unit of concurrency (own HIP stream + scratch). Not re-entrant: one call at a time per slot."""
 
@@ -172,9 +185,15 @@ class Slot:
         check(self.lib.wlx_pcm_put(self.engine._h, self.sid, item, _f32p(pcm), pcm.shape[0]))
 
     def put_frames(self, frames: np.ndarray, sample_rate: int, item: int = 0) -> int:
-        """File frames [n, channels] (int16, or anything else as float32) at `sample_rate` -> 16 kHz mono float32 resident in the
+        """File frames [n, channels] (int16, or anything else as float32; or a FlacFrames: a FLAC file's frames, still compressed) at
+        `sample_rate` -> 16 kHz mono float32 resident in the
         item's PCM buffer, converted, down-mixed and resampled on the device (wlx_pcm_put_frames). -> samples resident.
         Raises WlxError for a rate the device resampler does not serve (see `resample_supported`)."""
+        if isinstance(frames, FlacFrames):         # still compressed: the library decodes them on the device (STREAMINFO's rate holds)
+            n, info = C.c_int64(0), _lib.wlx_flac_info()
+            check(self.lib.wlx_pcm_put_flac(self.engine._h, self.sid, item, frames.data, len(frames.data), C.byref(info), C.byref(n)))
+            frames.info = info
+            return n.value
         x = np.asarray(frames)
         if x.ndim == 1:
             x = x[:, None]
@@ -184,6 +203,16 @@ class Slot:
         check(self.lib.wlx_pcm_put_frames(self.engine._h, self.sid, item, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], fmt,
                                           int(sample_rate), C.byref(n)))
         return n.value
+
+    def put_flac(self, data: bytes, item: int = 0):
+        """The bytes of a FLAC file -> 16 kHz mono float32 resident in the item's PCM buffer: indexed on the host, decoded, down-mixed and
+        resampled on the device (wlx_pcm_put_flac); bit-identical to put_frames(audio_io.read_flac(data)). -> (samples resident, info)
+        with info = the stream's shape (a _lib.wlx_flac_info). Raises WlxError: code ERR_ARG for a stream the device route does not
+        serve (nothing launched, the item untouched: decode on the host), ERR_DATA for a damaged stream.
+        It goes through put_frames, the one way file frames reach the slot: the frames are handed over still compressed (FlacFrames)."""
+        frames = FlacFrames(data)
+        n = self.put_frames(frames, frames.sample_rate, item)
+        return n, frames.info
 
     def pcm(self, item: int = 0) -> np.ndarray:
         """Host copy of the item's resident PCM (16 kHz mono float32)."""

@@ -32,7 +32,7 @@ import numpy as np
 from . import _lib
 from . import vad as _vad
 from . import word_timing as _wt
-from ._lib import ERR_ARG as _ERR_ARG, WlxError as _WlxError
+from ._lib import ERR_ARG as _ERR_ARG, ERR_DATA as _ERR_DATA, WlxError as _WlxError
 from .engine import GenerationResult, HipWhisperEngine, ResidentPcm, Slot, TokenIds
 from .specs import WhisperSpec, get_spec, spec_from_state_dict
 from .tokenizer import LANGUAGE_CODES, Tokenizer
@@ -603,28 +603,46 @@ class WhisperModelHIP:
             # them into its PCM buffer (Slot.put_frames), the log-mel kernel reads them there, and the host takes the 16 kHz mono copy
             # back for the duration, the VAD filter and speaker labels. A rate or channel count the device resampler does not serve
             # keeps the host route (audio_io.load_audio's arithmetic).
-            from .audio_io import frames_to_mono, read_audio
+            from .audio_io import _read_all, frames_to_mono, read_audio
             from .engine import resample_supported
-            file_frames, file_sr = read_audio(audio)
+            data = _read_all(audio)
             temps_f = temperature if isinstance(temperature, (list, tuple)) else [temperature]
             file_slot = self._slot(rows=max(int(beam_size), int(best_of) if any(t > 0 for t in temps_f) else 1))
-            # (an engine injected through `engine=` whose slots take 16 kHz PCM only — the host-logic test doubles — has no front end)
-            on_device = (sr == 16000 and file_frames.shape[0] > 0 and resample_supported(file_sr, file_frames.shape[1])
-                         and hasattr(file_slot, "put_frames"))
-            if on_device:
+            # A FLAC file goes to the device as it is: the slot indexes its frames on the host and decodes them in HBM (Slot.put_flac),
+            # which leaves resident exactly what put_frames(read_flac(file)) would. A stream the device route does not serve
+            # (WLX_ERR_ARG: nothing was launched) is decoded by audio_io.read_flac below; a damaged one is the ValueError read_flac raises.
+            on_device = False
+            if data[:4] == b"fLaC" and sr == 16000 and hasattr(file_slot, "put_flac"):
                 try:
                     with file_slot.lock:
-                        file_slot.put_frames(file_frames, file_sr)
+                        file_slot.put_flac(data)
                         audio = file_slot.pcm()
+                    on_device = True
                 except _WlxError as e:
-                    if e.code != _ERR_ARG:             # only a REFUSED shape (nothing was launched) keeps the host route
+                    if e.code == _ERR_DATA:
+                        raise ValueError(f"damaged FLAC stream: {e}") from e
+                    if e.code != _ERR_ARG:
                         raise
                     self.logger.debug("device front end refused the file: %s", e)
-                    on_device = False
             if not on_device:
-                self.logger.debug("file audio at %d Hz x %d channels: resampled on the host", file_sr, file_frames.shape[1])
-                file_slot = None
-                audio = frames_to_mono(file_frames, file_sr, sr)
+                file_frames, file_sr = read_audio(data)
+                # (an engine injected through `engine=` whose slots take 16 kHz PCM only — the host-logic test doubles — has no front end)
+                on_device = (sr == 16000 and file_frames.shape[0] > 0 and resample_supported(file_sr, file_frames.shape[1])
+                             and hasattr(file_slot, "put_frames"))
+                if on_device:
+                    try:
+                        with file_slot.lock:
+                            file_slot.put_frames(file_frames, file_sr)
+                            audio = file_slot.pcm()
+                    except _WlxError as e:
+                        if e.code != _ERR_ARG:             # only a REFUSED shape (nothing was launched) keeps the host route
+                            raise
+                        self.logger.debug("device front end refused the file: %s", e)
+                        on_device = False
+                if not on_device:
+                    self.logger.debug("file audio at %d Hz x %d channels: resampled on the host", file_sr, file_frames.shape[1])
+                    file_slot = None
+                    audio = frames_to_mono(file_frames, file_sr, sr)
         audio = np.ascontiguousarray(audio, dtype=np.float32)
         duration = audio.shape[0] / sr
         duration_after_vad = duration
