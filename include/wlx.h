@@ -188,6 +188,17 @@ int32_t wlx_logmel_resident(wlx_engine* e, int32_t slot, int32_t item, int32_t* 
 #define WLX_PCM_MAX_CHANNELS 8
 int32_t wlx_pcm_put_frames(wlx_engine* e, int32_t slot, int32_t item, const void* frames, int64_t n_frames, int32_t channels,
                            int32_t sample_format, int32_t sample_rate, int64_t* n_out);
+/* The CHANNEL-SPLIT form (BatchedInferencePipeline.transcribe(multichannel=True): a two-party call recording, one transcript per
+ * channel): the same ONE upload of the interleaved frames through the same pinned staging blocks, but no down-mix — channel c
+ * (0 <= c < channels) arrives as 16 kHz mono float32 in the PCM buffer of item first_item + c, *n_out samples resident in EACH of the
+ * `channels` items. The kernel is the split instantiation of the one above (blockIdx.y = channel; it reads sample r * channels + c, no
+ * mean, no division; same taps, tile, accumulation order and seam logic), so item first_item + c is BIT-IDENTICAL to
+ * wlx_pcm_put_frames of the one-channel array frames[:, c], both formats, the 16 kHz copy path with its negative zeros included, and
+ * independent of where block seams fall. Refused with WLX_ERR_ARG before any launch, every item's resident PCM left as it was:
+ * first_item < 0 or first_item + channels > max_batch, and everything wlx_pcm_put_frames refuses. A failed run leaves no PCM resident
+ * in any of the `channels` items; recorded log-mel requests that read any of them go out first. */
+int32_t wlx_pcm_put_frames_split(wlx_engine* e, int32_t slot, int32_t first_item, const void* frames, int64_t n_frames, int32_t channels,
+                                 int32_t sample_format, int32_t sample_rate, int64_t* n_out);
 /* ---- FLAC front end (PRODUCT entry points of the file path, beside wlx_pcm_put_frames) ----
  * Replaces the Python FLAC decoder of whisperlive_amd/audio_io.py (read_flac: a loop over Rice symbols and LPC samples at well under
  * real time) in front of wlx_pcm_put_frames: the file's COMPRESSED bytes cross PCIe once, the frames are decoded in HBM — FLAC frames are
@@ -225,6 +236,13 @@ typedef struct {
 int32_t wlx_flac_probe(const void* bytes, int64_t n_bytes, wlx_flac_info* out);
 int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, const void* bytes, int64_t n_bytes, wlx_flac_info* info_out,
                          int64_t* n_out);
+/* The CHANNEL-SPLIT form: the same probe, upload, frame decode and finish, then ONE split resample launch over the device frames (the
+ * kernel of wlx_pcm_put_frames_split) and ONE wait. Item first_item + c is BIT-IDENTICAL to wlx_pcm_put_frames(read_flac(bytes)[:, c]);
+ * *n_out samples are resident in each of the stream's `channels` items. WLX_ERR_DATA, WLX_ERR_ARG and WLX_ERR_NOMEM as
+ * wlx_pcm_put_flac, and first_item < 0 or first_item + channels > max_batch is WLX_ERR_ARG: all before any launch, every item's
+ * resident PCM left as it was. A frame that does not decode gives WLX_ERR_DATA and leaves NO PCM resident in any of the items. */
+int32_t wlx_pcm_put_flac_split(wlx_engine* e, int32_t slot, int32_t first_item, const void* bytes, int64_t n_bytes,
+                               wlx_flac_info* info_out, int64_t* n_out);
 /* ---- batched long-form front end (PRODUCT entry points of BatchedInferencePipeline: whisperlive_amd/batched.py) ----
  * Replaces faster_whisper.vad.collect_chunks + one FeatureExtractor call per chunk of the reference's BatchedInferencePipeline.transcribe
  * (whisper_live/transcriber/transcriber_faster_whisper.py:424-429): B chunks are cut out of ONE resident PCM buffer into B feature items
@@ -245,6 +263,18 @@ int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, const void* 
 #define WLX_LM_MAXRANGES 256
 int32_t wlx_logmel_chunks(wlx_engine* e, int32_t slot, int32_t src_item, const int64_t* ranges, const int32_t* range_off,
                           int32_t n_chunks, int32_t first_item, int32_t* n_frames_out);
+/* wlx_logmel_chunks with a source PER CHUNK (the channels of a file, wlx_pcm_put_frames_split): chunk c is cut out of the resident PCM
+ * of item src_items[c] (src_items: n_chunks entries), everything else as above — still ONE launch of each log-mel kernel for the whole
+ * group whatever the mix of sources, the features of chunk c bit-identical to wlx_logmel on the concatenated samples of ITS source.
+ * (A slot's PCM is one allocation with one row per item: the launch gets the row of the lowest source as its base and the range
+ * starts of the other sources are offset on the host; the kernel is the one wlx_logmel_chunks launches.)
+ * AFTERWARDS every item named in src_items keeps its PCM resident and unchanged; a destination item that is not a source counts as
+ * having no PCM resident. Refusals before any launch, nothing written: everything wlx_logmel_chunks refuses, checked per chunk
+ * against the resident count of that chunk's own source; a null src_items (WLX_ERR_ARG); a source item outside the slot (WLX_ERR_ARG)
+ * or with no PCM resident (WLX_ERR_STATE); sources whose rows lie more than 2^31 - 1 samples apart (WLX_ERR_ARG: hours of audio in
+ * items far apart — use neighbouring items). */
+int32_t wlx_logmel_chunks_multi(wlx_engine* e, int32_t slot, const int32_t* src_items, const int64_t* ranges, const int32_t* range_off,
+                                int32_t n_chunks, int32_t first_item, int32_t* n_frames_out);
 /* Copy the item's resident PCM (wlx_pcm_put / wlx_pcm_put_frames) to the host: *n_out samples (nullable `out`: the count only). */
 int32_t wlx_pcm_get(wlx_engine* e, int32_t slot, int32_t item, float* out, int64_t cap, int64_t* n_out);
 /* Copy an item's device features to host / replace them from host (float32 [n_mels, n_frames]). */
@@ -679,6 +709,10 @@ int32_t wlx_debug_dec_self_attn(int32_t device, const uint16_t* q, int64_t ldq, 
  * cap < ceil(n_frames * up / down). */
 int32_t wlx_debug_resample(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
                            int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out);
+/* The channel-split instantiation (wlx_pcm_put_frames_split): same arguments and refusals, `out` is [channels][cap] floats, copied in
+ * AND out like the above, and channel c lands in row c (*n_out floats of it; every other float comes back unchanged). */
+int32_t wlx_debug_resample_split(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
+                                 int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out);
 /* The same, and the summed HIP-event time of the block launches (scripts/resample_time.py). */
 int32_t wlx_debug_resample_timed(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
                                  int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out,

@@ -19,11 +19,11 @@ SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
-    "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
+    "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_put_frames_split", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_put_flac_split", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
     "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_align_batch", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
-    "wlx_logmel_chunks", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
+    "wlx_logmel_chunks", "wlx_logmel_chunks_multi", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
     "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch", "wlx_spk_embed_pcm_batch", "wlx_spk_embed_ring_batch",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
@@ -33,7 +33,7 @@ EXPORTS = [
     "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
     "wlx_debug_dec_gemv", "wlx_debug_dec_cq_cross_attn",
-    "wlx_debug_resample", "wlx_debug_resample_timed", "wlx_debug_flac_decode", "wlx_debug_flac_timings",
+    "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_flac_decode", "wlx_debug_flac_timings",
     "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings",
 ]
 
@@ -275,8 +275,10 @@ def load() -> C.CDLL:
     lib.wlx_logmel.argtypes = [vp, i32, i32, f32p, i64, i32p]
     lib.wlx_pcm_put.argtypes = [vp, i32, i32, f32p, i64]
     lib.wlx_pcm_put_frames.argtypes = [vp, i32, i32, vp, i64, i32, i32, i32, C.POINTER(C.c_int64)]
+    lib.wlx_pcm_put_frames_split.argtypes = [vp, i32, i32, vp, i64, i32, i32, i32, C.POINTER(C.c_int64)]
     lib.wlx_flac_probe.argtypes = [vp, i64, C.POINTER(wlx_flac_info)]
     lib.wlx_pcm_put_flac.argtypes = [vp, i32, i32, vp, i64, C.POINTER(wlx_flac_info), C.POINTER(C.c_int64)]
+    lib.wlx_pcm_put_flac_split.argtypes = [vp, i32, i32, vp, i64, C.POINTER(wlx_flac_info), C.POINTER(C.c_int64)]
     lib.wlx_pcm_get.argtypes = [vp, i32, i32, f32p, i64, C.POINTER(C.c_int64)]
     lib.wlx_logmel_resident.argtypes = [vp, i32, i32, i32p]
     lib.wlx_features_get.argtypes = [vp, i32, i32, f32p, i64, i32p]
@@ -304,6 +306,7 @@ def load() -> C.CDLL:
     lib.wlx_vad_segments.argtypes = [f32p, i32, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i64p, i32, i32p]
     lib.wlx_logmel_ring.argtypes = [vp, i32, i32, vp, i64p, i32, i32p]
     lib.wlx_logmel_chunks.argtypes = [vp, i32, i32, i64p, i32p, i32, i32, i32p]
+    lib.wlx_logmel_chunks_multi.argtypes = [vp, i32, i32p, i64p, i32p, i32, i32, i32p]
     lib.wlx_vad_probs_pcm.argtypes = [vp, vp, i32, i32, i64, i64, i32, f32p, i32, i32p, f32p]
     lib.wlx_vad_probs_batch.argtypes = [vp, f32p, i64p, i32p, i32, f32p, i64, i32p, f32p]
     lib.wlx_vad_probs_pcm_batch.argtypes = [vp, vp, i32, i32, i64p, i32p, i32, f32p, i64, i32p, f32p]
@@ -351,6 +354,7 @@ def load() -> C.CDLL:
     lib.wlx_debug_dec_cq_cross_attn.argtypes = [i32, f32p, i64, f32p, f32p, f32p, f32p, C.c_float, i32, u16p, u16p, i64, i32, i32, i32, i32, i32,
                                                 i32p, u16p, f32p]
     lib.wlx_debug_resample.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p]
+    lib.wlx_debug_resample_split.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p]
     lib.wlx_debug_resample_timed.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p, f32p]
     lib.wlx_debug_flac_decode.argtypes = [i32, vp, i64, i32p, i64, C.POINTER(C.c_int64), i32p]
     lib.wlx_debug_flac_timings.argtypes = [vp, i32, f32p]

@@ -15,6 +15,7 @@ test doubles) takes the host-chunk route: ``collect_chunks`` + one feature-extra
 """
 from __future__ import annotations
 
+import inspect
 from math import ceil
 from typing import BinaryIO, Iterable, List, Optional, Sequence, Tuple, Union
 
@@ -35,11 +36,15 @@ MAX_DEC_ROWS = 320          # decoder rows of one step (include/wlx.h wlx_slot_c
 class DeviceChunks:
     """The `features` of the device route: the chunks of one file as sample ranges of the PCM resident in item `src_item` of `slot`.
     Nothing is computed until a group is decoded (`generate_segment_batched`); slicing gives the group. `host_audio()` returns the
-    16 kHz host copy — fetched from the device only when something on the host needs it (a chunk that falls back)."""
+    16 kHz host copy — fetched from the device only when something on the host needs it (a chunk that falls back).
+    A list `src_item` carries one source item PER CHUNK (multichannel: the chunks of several channels pooled into one list; a group
+    then goes out through wlx_logmel_chunks_multi). There the sources lie behind every group's destination items, so nothing a group
+    does evicts a source, and `host_audio` is a callable of the source item."""
 
     def __init__(self, slot, ranges: List[List[Tuple[int, int]]], host_audio, src_item: int = 0, n_resident: int = 0):
         self.slot, self.ranges, self._host, self.src_item, self.n_resident = slot, ranges, host_audio, src_item, n_resident
         self.shared = {"resident": True}        # one state for every slice: a fallback into the source item evicts the source
+        self.channels = None                    # multichannel: the file channel of each chunk (sliced with the chunks)
 
     def __len__(self):
         return len(self.ranges)
@@ -47,7 +52,9 @@ class DeviceChunks:
     def __getitem__(self, key):
         if not isinstance(key, slice):
             raise TypeError("DeviceChunks is cut into groups with slices")
-        g = DeviceChunks(self.slot, self.ranges[key], self._host, self.src_item, self.n_resident)
+        src = self.src_item[key] if isinstance(self.src_item, list) else self.src_item
+        g = DeviceChunks(self.slot, self.ranges[key], self._host, src, self.n_resident)
+        g.channels = self.channels[key] if self.channels is not None else None
         g.shared = self.shared
         return g
 
@@ -64,6 +71,8 @@ class DeviceChunks:
     def to_device(self) -> List[int]:
         """The group's features into items 0 .. len - 1 of the slot -> frames per item (incl. the pad frame)."""
         slot, n = self.slot, len(self.ranges)
+        if isinstance(self.src_item, list):
+            return self._to_device_multi()
         if not self.shared["resident"]:
             slot.pcm_put(self.host_audio(), item=self.src_item)
             self.shared["resident"] = True
@@ -87,6 +96,28 @@ class DeviceChunks:
                     self.shared["resident"] = False
         return frames
 
+    def _to_device_multi(self) -> List[int]:
+        slot, n = self.slot, len(self.ranges)
+        if n > min(self.src_item):
+            raise ValueError(f"a group of {n} chunks would overwrite source item {min(self.src_item)}")
+        frames = [0] * n
+        ok = [len(r) <= _MAXRANGES for r in self.ranges]
+        a = 0
+        while a < n:                                 # as above: one launch of each kernel per run, whatever the mix of sources
+            if not ok[a]:
+                a += 1
+                continue
+            b = a
+            while b < n and ok[b]:
+                b += 1
+            frames[a:b] = slot.logmel_chunks(self.ranges[a:b], src_item=self.src_item[a:b], first_item=a)
+            a = b
+        for i in range(n):
+            if not ok[i]:
+                audio = self._host(self.src_item[i])
+                frames[i] = slot.logmel(np.concatenate([audio[s:e] for s, e in self.ranges[i]]), item=i)
+        return frames
+
 
 class BatchedInferencePipeline:
     def __init__(self, model):
@@ -95,6 +126,10 @@ class BatchedInferencePipeline:
 
     # ---- (:121-174)
     def forward(self, features, tokenizer, chunks_metadata, options):
+        # multichannel: the group carries the file channel of each of its chunks; the word-timestamp pass then runs per run of equal
+        # channel, each with its own channel's last-speech time, kept in the state all groups of the file share (a group that
+        # straddles a channel boundary aligns once per run)
+        channels = getattr(features, "channels", None)
         encoder_output, outputs = self.generate_segment_batched(features, tokenizer, options)
 
         segmented_outputs = []
@@ -114,28 +149,47 @@ class BatchedInferencePipeline:
                 for subsegment in subsegments])
         if options.word_timestamps:
             # chunk after chunk (the route add_word_timestamps takes where it is not given a group form), with the last-speech time carried along
-            def align_fn(text_tokens, _num_frames, window):
-                r = self.model.model.align(encoder_output.select([window]), tokenizer.sot_sequence, [text_tokens],
-                                           segment_sizes[window])[0]
-                pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
-                return pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)
-
-            # ... or, where the model's align takes a group, every chunk that has text in ONE call (wlx_align_batch), as the reference does
-            def align_many_fn(requests):
-                res = self.model.model.align(encoder_output.select([r[2] for r in requests]), tokenizer.sot_sequence,
-                                             [r[0] for r in requests], [segment_sizes[r[2]] for r in requests])
-                out = []
-                for r in res:
+            def aligners(base):
+                """the align functions for a list of windows that starts at window `base` of the group"""
+                def align_fn(text_tokens, _num_frames, window):
+                    window += base
+                    r = self.model.model.align(encoder_output.select([window]), tokenizer.sot_sequence, [text_tokens],
+                                               segment_sizes[window])[0]
                     pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
-                    out.append((pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)))
-                return out
+                    return pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)
 
-            # (handed over on the function, the form add_word_timestamps also takes: the call keeps the nine positional arguments a
-            # stand-in for add_word_timestamps is written against)
-            align_fn.align_many = align_many_fn
-            self.last_speech_timestamp = _wt.add_word_timestamps(
-                segmented_outputs, tokenizer, align_fn, 0, self.model.tokens_per_second, self.model.frames_per_second,
-                options.prepend_punctuations, options.append_punctuations, self.last_speech_timestamp)
+                # ... or, where the model's align takes a group, every chunk that has text in ONE call (wlx_align_batch), as the reference does
+                def align_many_fn(requests):
+                    res = self.model.model.align(encoder_output.select([base + r[2] for r in requests]), tokenizer.sot_sequence,
+                                                 [r[0] for r in requests], [segment_sizes[base + r[2]] for r in requests])
+                    out = []
+                    for r in res:
+                        pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
+                        out.append((pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)))
+                    return out
+
+                # (handed over on the function, the form add_word_timestamps also takes: the call keeps the nine positional arguments a
+                # stand-in for add_word_timestamps is written against)
+                align_fn.align_many = align_many_fn
+                return align_fn
+
+            if channels is None:
+                self.last_speech_timestamp = _wt.add_word_timestamps(
+                    segmented_outputs, tokenizer, aligners(0), 0, self.model.tokens_per_second, self.model.frames_per_second,
+                    options.prepend_punctuations, options.append_punctuations, self.last_speech_timestamp)
+            else:
+                last = features.shared.setdefault("last_speech", {})        # per channel, for every group of this file
+                end = 0
+                while end < len(channels):
+                    base = end
+                    while end < len(channels) and channels[end] == channels[base]:
+                        end += 1
+                    got = _wt.add_word_timestamps(
+                        segmented_outputs[base:end], tokenizer, aligners(base), 0, self.model.tokens_per_second,
+                        self.model.frames_per_second, options.prepend_punctuations, options.append_punctuations,
+                        last.get(channels[base], 0.0))
+                    if got is not None:
+                        last[channels[base]] = got
         return segmented_outputs
 
     # ---- (:176-254)
@@ -197,7 +251,7 @@ class BatchedInferencePipeline:
         return encoder_output, output
 
     # ---- (:256-532)
-    def transcribe(
+    def _transcribe(
         self,
         audio: Union[str, BinaryIO, np.ndarray],
         language: Optional[str] = None,
@@ -314,12 +368,7 @@ class BatchedInferencePipeline:
         # if no segment split is provided, use vad_model and generate segments
         if not clip_timestamps:
             if vad_filter:
-                if vad_parameters is None:
-                    vad_parameters = VadOptions(max_speech_duration_s=chunk_length, min_silence_duration_ms=160)
-                elif isinstance(vad_parameters, dict):
-                    if "max_speech_duration_s" in vad_parameters.keys():
-                        vad_parameters.pop("max_speech_duration_s")
-                    vad_parameters = VadOptions(**vad_parameters, max_speech_duration_s=chunk_length)
+                vad_parameters = _vad_options(vad_parameters, chunk_length)
                 vad_model = model._vad_model()
                 if (device and n_samples > 0 and hasattr(vad_model, "probs_pcm")
                         and getattr(vad_model, "device", None) == getattr(slot.engine, "device", -1)):
@@ -351,46 +400,16 @@ class BatchedInferencePipeline:
             wave = _resolve(host_audio, slot)
             features = [model.feature_extractor(np.concatenate([wave[s:e] for s, e in rg]))[..., :-1] for rg in chunk_ranges]
 
-        all_language_probs = None
         # detecting the language if not provided
-        if language is None:
-            if not model.model.is_multilingual:
-                language = "en"
-                language_probability = 1
-            else:
-                need = language_detection_segments * model.feature_extractor.nb_max_frames
-                language, language_probability, all_language_probs = model.detect_language(
-                    features=np.concatenate(
-                        self._leading_features(features, need)
-                        + [np.full((model.model.n_mels, 1), -1.5, dtype="float32")], axis=1),  # a dummy feature to account for empty audio
-                    language_detection_segments=language_detection_segments,
-                    language_detection_threshold=language_detection_threshold)
-                model.logger.info("Detected language '%s' with probability %.2f", language, language_probability)
-        else:
-            if not model.model.is_multilingual and language != "en":
-                model.logger.warning("The current model is English-only but the language parameter is set to '%s'; "
-                                     "using 'en' instead." % language)
-                language = "en"
-            language_probability = 1
+        language, language_probability, all_language_probs = self._language(
+            features, language, language_detection_segments, language_detection_threshold)
 
         tokenizer = Tokenizer(model.hf_tokenizer, model.model.is_multilingual, task=task, language=language)
 
         if not device:
             features = np.stack([pad_or_trim(feature) for feature in features]) if features else []
 
-        options = TranscriptionOptions(
-            beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
-            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-            log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
-            compression_ratio_threshold=compression_ratio_threshold,
-            temperatures=(list(temperature[:1]) if isinstance(temperature, (list, tuple)) else [temperature]),
-            initial_prompt=initial_prompt, prefix=prefix, suppress_blank=suppress_blank,
-            suppress_tokens=get_suppressed_tokens(tokenizer, suppress_tokens),
-            prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
-            max_new_tokens=max_new_tokens, hotwords=hotwords, word_timestamps=word_timestamps,
-            hallucination_silence_threshold=None, condition_on_previous_text=False, clip_timestamps=clip_timestamps,
-            prompt_reset_on_temperature=0.5, multilingual=multilingual, without_timestamps=without_timestamps,
-            max_initial_timestamp=0.0)
+        options = _options(tokenizer, locals(), clip_timestamps)
 
         info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
                                  duration_after_vad=duration_after_vad, transcription_options=options,
@@ -401,17 +420,56 @@ class BatchedInferencePipeline:
             segments = self._restored(segments, clip_timestamps, sampling_rate)
         return segments, info
 
-    def _leading_features(self, features, need_frames: int) -> List[np.ndarray]:
-        """the first chunks' features ([..., :-1] each) on the host, as many as the language vote reads"""
+    def transcribe(self, audio, *args, multichannel: bool = False, **kwargs):
+        """The reference's transcribe — every argument of `_transcribe` above, by position or by name — and ONE keyword-only switch
+        the reference does not have. multichannel=False is `_transcribe`, untouched. multichannel=True: every channel of the file is
+        transcribed on its own while the chunks of all channels share the decode groups; segments carry `channel` and come sorted by
+        (start, channel) — whisperlive_amd/multichannel.py. (`__wrapped__` below: the signature introspection reports is the
+        reference's, which is what a caller written against the reference binds to.)"""
+        if not multichannel:
+            return self._transcribe(audio, *args, **kwargs)
+        from .multichannel import transcribe_multichannel
+        bound = inspect.signature(self._transcribe).bind(audio, *args, **kwargs)
+        bound.apply_defaults()
+        return transcribe_multichannel(self, dict(bound.arguments))
+
+    transcribe.__wrapped__ = _transcribe
+
+    def _language(self, features, language, language_detection_segments, language_detection_threshold, group_size=None):
+        """-> (language, probability, all probabilities or None): the language given (an English-only model knows one), or the one
+        detected on the leading `features` of a multilingual model. group_size: see _leading_features"""
+        model = self.model
+        if language is not None:
+            if not model.model.is_multilingual and language != "en":
+                model.logger.warning("The current model is English-only but the language parameter is set to '%s'; "
+                                     "using 'en' instead." % language)
+                language = "en"
+            return language, 1, None
+        if not model.model.is_multilingual:
+            return "en", 1, None
+        need = language_detection_segments * model.feature_extractor.nb_max_frames
+        language, language_probability, all_language_probs = model.detect_language(
+            features=np.concatenate(
+                self._leading_features(features, need, group_size)
+                + [np.full((model.model.n_mels, 1), -1.5, dtype="float32")], axis=1),  # a dummy feature to account for empty audio
+            language_detection_segments=language_detection_segments,
+            language_detection_threshold=language_detection_threshold)
+        model.logger.info("Detected language '%s' with probability %.2f", language, language_probability)
+        return language, language_probability, all_language_probs
+
+    def _leading_features(self, features, need_frames: int, group_size: Optional[int] = None) -> List[np.ndarray]:
+        """the first chunks' features ([..., :-1] each) on the host, as many as the language vote reads. group_size: chunks per
+        log-mel launch (default: every item of the slot; multichannel keeps the groups in front of the source items)"""
         if not isinstance(features, DeviceChunks):
             return list(features)
         out, have = [], 0
         slot = features.slot
+        step = int(group_size or slot.max_batch)
         with slot.lock:
-            for a in range(0, len(features), slot.max_batch):
+            for a in range(0, len(features), step):
                 if have >= need_frames:
                     break
-                group = features[a:a + slot.max_batch]
+                group = features[a:a + step]
                 group.to_device()
                 for i in range(len(group)):
                     if have >= need_frames:
@@ -449,6 +507,36 @@ class BatchedInferencePipeline:
             if log_progress:
                 self.model.logger.info("batched transcription: %d / %d chunks", min(i + batch_size, len(features)), len(features))
         self.last_speech_timestamp = 0.0
+
+
+def _vad_options(vad_parameters, chunk_length) -> VadOptions:
+    """the gate's options of a batched transcription: chunks of at most chunk_length seconds, whatever the caller's dict says"""
+    if vad_parameters is None:
+        return VadOptions(max_speech_duration_s=chunk_length, min_silence_duration_ms=160)
+    if isinstance(vad_parameters, dict):
+        if "max_speech_duration_s" in vad_parameters.keys():
+            vad_parameters.pop("max_speech_duration_s")
+        return VadOptions(**vad_parameters, max_speech_duration_s=chunk_length)
+    return vad_parameters
+
+
+def _options(tokenizer, a: dict, clip_timestamps) -> TranscriptionOptions:
+    """the options a batched transcription decodes with, from transcribe's arguments `a` (by name): no conditioning on previous text,
+    the first temperature only, no initial-timestamp limit, as the reference forces them"""
+    temperature = a["temperature"]
+    return TranscriptionOptions(
+        beam_size=a["beam_size"], best_of=a["best_of"], patience=a["patience"], length_penalty=a["length_penalty"],
+        repetition_penalty=a["repetition_penalty"], no_repeat_ngram_size=a["no_repeat_ngram_size"],
+        log_prob_threshold=a["log_prob_threshold"], no_speech_threshold=a["no_speech_threshold"],
+        compression_ratio_threshold=a["compression_ratio_threshold"],
+        temperatures=(list(temperature[:1]) if isinstance(temperature, (list, tuple)) else [temperature]),
+        initial_prompt=a["initial_prompt"], prefix=a["prefix"], suppress_blank=a["suppress_blank"],
+        suppress_tokens=get_suppressed_tokens(tokenizer, a["suppress_tokens"]),
+        prepend_punctuations=a["prepend_punctuations"], append_punctuations=a["append_punctuations"],
+        max_new_tokens=a["max_new_tokens"], hotwords=a["hotwords"], word_timestamps=a["word_timestamps"],
+        hallucination_silence_threshold=None, condition_on_previous_text=False, clip_timestamps=clip_timestamps,
+        prompt_reset_on_temperature=0.5, multilingual=a["multilingual"], without_timestamps=a["without_timestamps"],
+        max_initial_timestamp=0.0)
 
 
 def _resolve(host_audio, slot) -> np.ndarray:

@@ -665,6 +665,40 @@ extern "C" int32_t wlx_pcm_put_frames(wlx_engine* e, int32_t slot, int32_t item,
     return WLX_OK;
 }
 
+// the channel-split form (resample.hip): channel c of the file -> item first_item + c, one upload, no down-mix. Everything is validated
+// before the first byte of `frames` is read and before any item's PCM is touched.
+extern "C" int32_t wlx_pcm_put_frames_split(wlx_engine* e, int32_t slot, int32_t first_item, const void* frames, int64_t n_frames,
+                                            int32_t channels, int32_t sample_format, int32_t sample_rate, int64_t* n_out) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (!frames || n_frames <= 0) return set_error(WLX_ERR_ARG, "empty audio");
+    CKR(resample_check_args(frames, n_frames, channels, sample_format, sample_rate));
+    if (first_item < 0 || (int64_t)first_item + channels > s->B)
+        return set_error(WLX_ERR_ARG, "wlx_pcm_put_frames_split: items [%d, %lld) outside the slot's %d", first_item,
+                         (long long)first_item + channels, s->B);
+    if (n_frames > (int64_t)sample_rate * 3600 + sample_rate) return set_error(WLX_ERR_ARG, "audio chunk too long");
+    ResamplePlan pl{};
+    CKR(resample_plan(e->device, sample_rate, &pl));
+    const int64_t n = resample_out_len(pl, n_frames);
+    if (n > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
+    CK(hipSetDevice(e->device));
+    bool recorded = false;
+    for (int c = 0; c < channels; ++c)
+        recorded = recorded || std::find(s->lm_items.begin(), s->lm_items.end(), first_item + c) != s->lm_items.end();
+    if ((size_t)n > s->pcm_cap || recorded)
+        CKR(flush_logmel(e, s));            // a recorded log-mel request reads one of these items' PCM (or the buffers are about to be re-allocated)
+    CKR(slot_grow_audio(e, s, (size_t)n));
+    const long long block = resample_default_block(channels, sample_format);
+    CKR(slot_resample_stage(s));
+    for (int c = 0; c < channels; ++c) s->npcm[first_item + c] = 0;      // (a failed run leaves no half-written audio resident)
+    CKR(resample_run(pl, frames, n_frames, channels, sample_format, block, s->rs, s->pcm + (size_t)first_item * s->pcm_cap, s->stream, nullptr,
+                     (long long)s->pcm_cap));
+    for (int c = 0; c < channels; ++c) s->npcm[first_item + c] = n;
+    if (n_out) *n_out = n;
+    return WLX_OK;
+}
+
 extern "C" int32_t wlx_pcm_get(wlx_engine* e, int32_t slot, int32_t item, float* out, int64_t cap, int64_t* n_out) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
@@ -812,35 +846,56 @@ extern "C" int32_t wlx_logmel_ring(wlx_engine* e, int32_t slot, int32_t item, wl
     return WLX_OK;
 }
 
-// B chunks cut out of ONE resident PCM buffer into B feature items, one launch of each kernel (include/wlx.h). Everything is validated
-// before anything is staged, recorded or launched.
-extern "C" int32_t wlx_logmel_chunks(wlx_engine* e, int32_t slot, int32_t src_item, const int64_t* ranges, const int32_t* range_off,
-                                     int32_t n_chunks, int32_t first_item, int32_t* n_frames_out) {
+// B chunks cut out of resident PCM into B feature items, one launch of each kernel (include/wlx.h): out of ONE item's buffer
+// (wlx_logmel_chunks: src_items == nullptr, every chunk reads src_item) or each chunk out of its own source (wlx_logmel_chunks_multi:
+// chunk c reads src_items[c]). A slot's PCM is one allocation with row stride pcm_cap, so the multi form hands the kernel the row of the
+// LOWEST source as its base and adds (src_items[c] - lowest) * pcm_cap to the chunk's range starts on the host: logmel_chunks_kernel
+// only ever adds a range start to its base pointer (its reflections are in the chunk's concatenated coordinates, logmel.hip), so it
+// is the same kernel with the same arithmetic. Everything is validated before anything is staged, recorded or launched.
+static int logmel_chunks_run(wlx_engine* e, int32_t slot, int32_t src_item, const int32_t* src_items, const int64_t* ranges,
+                             const int32_t* range_off, int32_t n_chunks, int32_t first_item, int32_t* n_frames_out) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!ranges || !range_off || !n_frames_out || n_chunks < 1) return set_error(WLX_ERR_ARG, "wlx_logmel_chunks: bad argument");
-    if (src_item < 0 || src_item >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", src_item);
-    if (first_item < 0 || first_item + (int64_t)n_chunks > s->B)
-        return set_error(WLX_ERR_ARG, "wlx_logmel_chunks: items [%d, %lld) outside the slot's %d", first_item, (long long)first_item + n_chunks, s->B);
-    const int64_t resident = s->npcm[src_item];
-    if (resident <= 0) return set_error(WLX_ERR_STATE, "item %d: no PCM resident (call wlx_pcm_put first)", src_item);
+    const char* fn = src_items ? "wlx_logmel_chunks_multi" : "wlx_logmel_chunks";
+    if (!ranges || !range_off || !n_frames_out || n_chunks < 1) return set_error(WLX_ERR_ARG, "%s: bad argument", fn);
+    if (first_item < 0 || first_item + (int64_t)n_chunks > s->B) {
+        if (!src_items && (src_item < 0 || src_item >= s->B)) return set_error(WLX_ERR_ARG, "bad item %d", src_item);
+        return set_error(WLX_ERR_ARG, "%s: items [%d, %lld) outside the slot's %d", fn, first_item, (long long)first_item + n_chunks, s->B);
+    }
+    int src_lo = src_item, src_hi = src_item;
+    for (int c = 0; c < n_chunks; ++c) {
+        const int src = src_items ? src_items[c] : src_item;
+        if (src < 0 || src >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", src);
+        if (s->npcm[src] <= 0) return set_error(WLX_ERR_STATE, "item %d: no PCM resident (call wlx_pcm_put first)", src);
+        src_lo = c == 0 ? src : std::min(src_lo, src);
+        src_hi = c == 0 ? src : std::max(src_hi, src);
+    }
     int64_t longest = 0;
     for (int c = 0; c < n_chunks; ++c) {
+        const int64_t resident = s->npcm[src_items ? src_items[c] : src_item];
         const int64_t r0 = range_off[c], nr = (int64_t)range_off[c + 1] - r0;
-        if (r0 < 0 || (c == 0 && r0 != 0)) return set_error(WLX_ERR_ARG, "wlx_logmel_chunks: range_off must start at 0 and ascend");
-        if (nr < 1 || nr > WLX_LM_MAXRANGES) return set_error(WLX_ERR_ARG, "wlx_logmel_chunks: chunk %d has %lld ranges (1..%d)", c, (long long)nr, WLX_LM_MAXRANGES);
+        if (r0 < 0 || (c == 0 && r0 != 0)) return set_error(WLX_ERR_ARG, "%s: range_off must start at 0 and ascend", fn);
+        if (nr < 1 || nr > WLX_LM_MAXRANGES) return set_error(WLX_ERR_ARG, "%s: chunk %d has %lld ranges (1..%d)", fn, c, (long long)nr, WLX_LM_MAXRANGES);
         int64_t total = 0, prev_end = 0;
         for (int64_t i = r0; i < r0 + nr; ++i) {
             const int64_t a = ranges[2 * i], b = ranges[2 * i + 1];
-            if (a < prev_end || b <= a) return set_error(WLX_ERR_ARG, "wlx_logmel_chunks: chunk %d range %lld = [%lld, %lld) is empty, out of order or overlaps",
-                                                          c, (long long)(i - r0), (long long)a, (long long)b);
-            if (b > resident) return set_error(WLX_ERR_STATE, "wlx_logmel_chunks: chunk %d range %lld ends at %lld, the resident PCM at %lld", c,
+            if (a < prev_end || b <= a) return set_error(WLX_ERR_ARG, "%s: chunk %d range %lld = [%lld, %lld) is empty, out of order or overlaps",
+                                                          fn, c, (long long)(i - r0), (long long)a, (long long)b);
+            if (b > resident) return set_error(WLX_ERR_STATE, "%s: chunk %d range %lld ends at %lld, the resident PCM at %lld", fn, c,
                                                (long long)(i - r0), (long long)b, (long long)resident);
             total += b - a;
             prev_end = b;
         }
         longest = std::max(longest, total);
+    }
+    // the kernel keeps a range's physical start as an int offset from its base pointer (logmel.hip rphys): the sources' rows must lie
+    // within 2^31 - 1 samples of the lowest one, at the row stride the buffers will have when the launch goes out
+    {
+        const size_t cap_after = std::max(s->pcm_cap, (((size_t)longest + 479999) / 480000) * 480000);
+        if ((uint64_t)(src_hi - src_lo) * cap_after + cap_after > 0x7fffffffull)
+            return set_error(WLX_ERR_ARG, "%s: source items %d and %d lie %llu samples apart, past the 2^31 - 1 the chunk kernel addresses "
+                             "(use neighbouring source items)", fn, src_lo, src_hi, (unsigned long long)((uint64_t)(src_hi - src_lo) * cap_after));
     }
     CK(hipSetDevice(e->device));
     if (!s->h_chunks) {
@@ -856,9 +911,10 @@ extern "C" int32_t wlx_logmel_chunks(wlx_engine* e, int32_t slot, int32_t src_it
     int Tmax = 0, nrows = 0;
     for (int c = 0; c < n_chunks; ++c) {
         const int r0 = range_off[c], nr = range_off[c + 1] - r0;
+        const long long row = src_items ? (long long)(src_items[c] - src_lo) * (long long)s->pcm_cap : 0;   // the source's row, from the base
         int64_t total = 0;
         for (int i = 0; i < nr; ++i) {
-            s->h_crng[2 * (nrows + i)] = ranges[2 * (r0 + i)]; s->h_crng[2 * (nrows + i) + 1] = total;
+            s->h_crng[2 * (nrows + i)] = row + ranges[2 * (r0 + i)]; s->h_crng[2 * (nrows + i) + 1] = total;
             total += ranges[2 * (r0 + i) + 1] - ranges[2 * (r0 + i)];
         }
         const int T = (int)((total + 160) / 160);
@@ -872,7 +928,7 @@ extern "C" int32_t wlx_logmel_chunks(wlx_engine* e, int32_t slot, int32_t src_it
     CK(hipEventRecord(s->ck_staged, s->stream));
     s->ck_pending = true;
     CK(hipEventRecord(s->ev_lm0, s->stream));
-    launch_logmel_chunks(s->pcm + (size_t)src_item * s->pcm_cap, s->d_chunks, n_chunks, Tmax, s->d_crng, s->feats,
+    launch_logmel_chunks(s->pcm + (size_t)src_lo * s->pcm_cap, s->d_chunks, n_chunks, Tmax, s->d_crng, s->feats,
                          (long)e->spec.n_mels * s->feat_ld, s->gmax, e->spec.n_mels, e->lm, s->feat_ld, s->stream);
     CK(hipGetLastError());
     CK(hipEventRecord(s->ev_lm1, s->stream));
@@ -880,9 +936,22 @@ extern "C" int32_t wlx_logmel_chunks(wlx_engine* e, int32_t slot, int32_t src_it
     for (int c = 0; c < n_chunks; ++c) {
         const int item = first_item + c;
         s->nframes[item] = s->h_chunks[c].T;
-        if (item != src_item) s->npcm[item] = 0;     // the item's own PCM buffer does not hold this audio; the source stays resident
+        bool is_src = item == src_item;
+        for (int k = 0; src_items && k < n_chunks && !is_src; ++k) is_src = src_items[k] == item;
+        if (!is_src) s->npcm[item] = 0;              // the item's own PCM buffer does not hold this audio; the source(s) stay resident
     }
     return WLX_OK;
+}
+
+extern "C" int32_t wlx_logmel_chunks(wlx_engine* e, int32_t slot, int32_t src_item, const int64_t* ranges, const int32_t* range_off,
+                                     int32_t n_chunks, int32_t first_item, int32_t* n_frames_out) {
+    return logmel_chunks_run(e, slot, src_item, nullptr, ranges, range_off, n_chunks, first_item, n_frames_out);
+}
+
+extern "C" int32_t wlx_logmel_chunks_multi(wlx_engine* e, int32_t slot, const int32_t* src_items, const int64_t* ranges, const int32_t* range_off,
+                                           int32_t n_chunks, int32_t first_item, int32_t* n_frames_out) {
+    if (!src_items) return set_error(WLX_ERR_ARG, "wlx_logmel_chunks_multi: null src_items");
+    return logmel_chunks_run(e, slot, -1, src_items, ranges, range_off, n_chunks, first_item, n_frames_out);
 }
 
 extern "C" int32_t wlx_logmel_resident(wlx_engine* e, int32_t slot, int32_t item, int32_t* n_frames_out) {

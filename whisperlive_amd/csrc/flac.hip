@@ -324,8 +324,10 @@ extern "C" int32_t wlx_flac_probe(const void* bytes, int64_t n_bytes, wlx_flac_i
     return WLX_OK;
 }
 
-extern "C" int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, const void* bytes, int64_t n_bytes, wlx_flac_info* info_out,
-                                    int64_t* n_out) {
+// wlx_pcm_put_flac (split = false: the down-mix into `item`) and wlx_pcm_put_flac_split (split = true: channel c into item + c): the
+// same probe, upload, frame decode and finish; they differ in the ONE resample launch behind them and in the items that become resident
+static int pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, const void* bytes, int64_t n_bytes, wlx_flac_info* info_out,
+                        int64_t* n_out, bool split) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
@@ -341,6 +343,9 @@ extern "C" int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, c
     CKR(flac_served(fs));
     const long long total = fs.info.total_samples;
     const int ch = fs.info.channels;
+    const int n_items = split ? ch : 1;         // the items that take audio: item .. item + n_items - 1
+    if (item + n_items > s->B)
+        return set_error(WLX_ERR_ARG, "wlx_pcm_put_flac_split: items [%d, %d) outside the slot's %d", item, item + n_items, s->B);
     ResamplePlan pl{};
     CKR(resample_plan(e->device, fs.info.sample_rate, &pl));
     const int64_t n = resample_out_len(pl, total);
@@ -361,17 +366,23 @@ extern "C" int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, c
     (void)flac_layout(fs, n_bytes, s->flac.buf, &d);
     CKR(slot_resample_stage(s));
     for (hipEvent_t& ev : s->flac.ev) if (!ev) CK(hipEventCreate(&ev));
-    if ((size_t)n > s->pcm_cap || std::find(s->lm_items.begin(), s->lm_items.end(), (int)item) != s->lm_items.end())
+    bool recorded = false;
+    for (int c = 0; c < n_items; ++c) recorded = recorded || std::find(s->lm_items.begin(), s->lm_items.end(), (int)item + c) != s->lm_items.end();
+    if ((size_t)n > s->pcm_cap || recorded)
         CKR(flush_logmel(e, s));            // a recorded log-mel request reads this item's PCM (or the buffers are about to be re-allocated)
     CKR(slot_grow_audio(e, s, (size_t)n));
     // ---- device: upload, decode, finish, resample; one wait
-    s->npcm[item] = 0;                      // (a failed run leaves no half-written audio resident)
+    for (int c = 0; c < n_items; ++c) s->npcm[item + c] = 0;      // (a failed run leaves no half-written audio resident)
     const size_t nf = fs.frames.size();
     std::vector<int> status_host;
     int* status = nullptr;
     int rc = [&]() -> int {
         CKR(flac_launch<float>(fs, bytes, n_bytes, d, &s->rs, s->stream, s->flac.ev));
-        CKR(resample_run_device(pl, static_cast<const float*>(d.frames), total, ch, s->pcm + (size_t)item * s->pcm_cap, s->stream));
+        if (split)
+            CKR(resample_run_device_split(pl, static_cast<const float*>(d.frames), total, ch, s->pcm + (size_t)item * s->pcm_cap,
+                                          (long long)s->pcm_cap, s->stream));
+        else
+            CKR(resample_run_device(pl, static_cast<const float*>(d.frames), total, ch, s->pcm + (size_t)item * s->pcm_cap, s->stream));
         CK(hipEventRecord(s->flac.ev[4], s->stream));
         if (nf * sizeof(int) <= RS_BLOCK_BYTES) {      // the status words come back through a pinned block (the copies out of it are ahead in the stream)
             status = reinterpret_cast<int*>(s->rs.pinned[0]);
@@ -384,7 +395,7 @@ extern "C" int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, c
     }();
     hipError_t he = hipStreamSynchronize(s->stream);       // the caller's bytes and the staging halves may be reused after return
     s->rs.used[0] = s->rs.used[1] = false;
-    if (rc == WLX_OK && he != hipSuccess) rc = set_error(WLX_ERR_HIP, "wlx_pcm_put_flac: %s", hipGetErrorString(he));
+    if (rc == WLX_OK && he != hipSuccess) rc = set_error(WLX_ERR_HIP, "%s: %s", split ? "wlx_pcm_put_flac_split" : "wlx_pcm_put_flac", hipGetErrorString(he));
     if (rc == WLX_OK) rc = flac_check_status(status, nf);
     if (rc == WLX_OK) s->flac.timed = true;
     if (s->flac.cap > 2 * RS_BLOCK_BYTES) {                // a long file's scratch does not stay with the slot
@@ -392,9 +403,19 @@ extern "C" int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, c
         s->flac.buf = nullptr; s->flac.cap = 0;
     }
     CKR(rc);
-    s->npcm[item] = n;
+    for (int c = 0; c < n_items; ++c) s->npcm[item + c] = n;
     if (n_out) *n_out = n;
     return WLX_OK;
+}
+
+extern "C" int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, const void* bytes, int64_t n_bytes, wlx_flac_info* info_out,
+                                    int64_t* n_out) {
+    return pcm_put_flac(e, slot, item, bytes, n_bytes, info_out, n_out, false);
+}
+
+extern "C" int32_t wlx_pcm_put_flac_split(wlx_engine* e, int32_t slot, int32_t first_item, const void* bytes, int64_t n_bytes,
+                                          wlx_flac_info* info_out, int64_t* n_out) {
+    return pcm_put_flac(e, slot, first_item, bytes, n_bytes, info_out, n_out, true);
 }
 
 // ------------------------------------------------------------------------------------------------ test hooks (kernel_hooks.hip conventions)

@@ -109,10 +109,14 @@ long long resample_out_len(const ResamplePlan& pl, long long n_frames);   // cei
 long long resample_reach(const ResamplePlan& pl);                         // smallest legal block, in input frames
 long long resample_default_block(int channels, int sample_format);        // frames per staged block of the product path
 // host frames -> d_out[0 .. out_len), one copy and one launch per block of `block_frames` input frames on `st`; waits for `st`.
-// kernel_ms (nullable): the launches' summed HIP-event time.
+// kernel_ms (nullable): the launches' summed HIP-event time. split_stride > 0: the channel-split form — no down-mix, channel c goes to
+// d_out + c * split_stride (one launch per block still, blockIdx.y = channel).
 int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames, int channels, int sample_format, long long block_frames,
-                 ResampleStage& sg, float* d_out, hipStream_t st, float* kernel_ms);
+                 ResampleStage& sg, float* d_out, hipStream_t st, float* kernel_ms, long long split_stride = 0);
 // device float32 frames [n_frames][channels] -> d_out[0 .. out_len): one launch on `st`, no copy, no wait (the FLAC front end, flac.hip)
 int resample_run_device(const ResamplePlan& pl, const float* d_frames, long long n_frames, int channels, float* d_out, hipStream_t st);
+// ... and its channel-split sibling: channel c -> d_out + c * out_stride, one launch with blockIdx.y = channel
+int resample_run_device_split(const ResamplePlan& pl, const float* d_frames, long long n_frames, int channels, float* d_out,
+                              long long out_stride, hipStream_t st);
 
 }  // namespace wlx

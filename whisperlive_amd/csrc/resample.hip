@@ -19,6 +19,12 @@
 // lanes of a half wave fall into distinct banks; up = 1 or 2 (every rate that is a multiple of 8 kHz) is an LDS broadcast. The input
 // reads step by down / up frames per lane (two- to four-way conflicts at 96 / 192 kHz, where the kernel is still far shorter than
 // the upload of its input). The job is bound by the PCIe upload, not by this kernel.
+//
+// The channel-split form (include/wlx.h wlx_pcm_put_frames_split, wlx_pcm_put_flac_split; test hook wlx_debug_resample_split) is the
+// SPLIT instantiation of the same kernel: blockIdx.y = channel c, the staging loop reads sample r * channels + c — no mean, no
+// division — and the outputs go to out + c * out_stride. Tap table, LDS layout, tile, accumulation order and seam logic are the ones
+// above, so channel c is BIT-IDENTICAL to the down-mix form run on the one-channel array frames[:, c]: the mono path of that form does
+// no division either (its `ch > 1` branch is not taken), and an output depends on nothing but the absolute input indices.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -42,6 +48,7 @@ struct ResampleArgs {
     const float* taps;      // [2 * half_len + 1]
     float* out;             // out[m] for m in [m0, m1)
     long long m0, m1;
+    long long out_stride;   // SPLIT only: channel c writes out[c * out_stride + m]
 };
 
 __device__ __forceinline__ long long floor_div(long long a, long long b) {       // b > 0
@@ -55,7 +62,7 @@ __device__ __forceinline__ float rs_sample(const void* raw, long long idx) {
     return reinterpret_cast<const float*>(raw)[idx];
 }
 
-template <int FMT>
+template <int FMT, bool SPLIT = false>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs p) {
     extern __shared__ float rs_lds[];
     const int ntaps = 2 * p.half_len + 1;
@@ -76,8 +83,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs p) {
         const long long r = j - p.j_base;
         if (j >= 0 && j < p.n_frames && r >= 0 && r < p.raw_frames) {
             const long long b = r * ch;
-            v = rs_sample<FMT>(p.raw, b);
-            if (ch > 1) {                          // the float32 mean: channels added in order, one division
+            v = rs_sample<FMT>(p.raw, SPLIT ? b + blockIdx.y : b);
+            if (!SPLIT && ch > 1) {                          // the float32 mean: channels added in order, one division
                 for (int c = 1; c < ch; ++c) v += rs_sample<FMT>(p.raw, b + c);
                 v = v / fch;
             }
@@ -85,9 +92,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs p) {
         xs[i] = v;
     }
     __syncthreads();
+    float* out = SPLIT ? p.out + (long long)blockIdx.y * p.out_stride : p.out;
     for (long long m = mA + threadIdx.x; m < mB; m += RS_THREADS) {
         if (p.half_len == 0) {                                 // 16 kHz in: the converted, down-mixed sample itself (a -0.0f stays -0.0f)
-            p.out[m] = xs[m - j_lo];
+            out[m] = xs[m - j_lo];
             continue;
         }
         const long long t = (long long)p.half_len + m * p.down;
@@ -98,7 +106,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs p) {
         const float* h = hs + ph;
         float acc = 0.f;
         for (int k = 0; k < K; ++k) acc = fmaf(x[-k], h[(long)k * p.up], acc);
-        p.out[m] = acc;
+        out[m] = acc;
     }
 }
 
@@ -199,8 +207,21 @@ long long resample_default_block(int channels, int sample_format) {
     return (long long)(RS_BLOCK_BYTES / ((size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4)));
 }
 
+// one launch: the down-mix form (split_stride == 0: grid.y = 1) or the split form (grid.y = channels, p.out_stride = split_stride)
+static void rs_launch(int sample_format, unsigned grid, size_t lds, hipStream_t st, ResampleArgs& p, long long split_stride) {
+    if (split_stride > 0) {
+        p.out_stride = split_stride;
+        const dim3 g(grid, (unsigned)p.channels);
+        if (sample_format == WLX_PCM_S16) hipLaunchKernelGGL((resample_kernel<WLX_PCM_S16, true>), g, dim3(RS_THREADS), lds, st, p);
+        else hipLaunchKernelGGL((resample_kernel<WLX_PCM_F32, true>), g, dim3(RS_THREADS), lds, st, p);
+        return;
+    }
+    if (sample_format == WLX_PCM_S16) hipLaunchKernelGGL(resample_kernel<WLX_PCM_S16>, dim3(grid), dim3(RS_THREADS), lds, st, p);
+    else hipLaunchKernelGGL(resample_kernel<WLX_PCM_F32>, dim3(grid), dim3(RS_THREADS), lds, st, p);
+}
+
 int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames, int channels, int sample_format, long long block_frames,
-                 ResampleStage& sg, float* d_out, hipStream_t st, float* kernel_ms) {
+                 ResampleStage& sg, float* d_out, hipStream_t st, float* kernel_ms, long long split_stride) {
     const size_t fb = (size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4);
     const long long n_out = resample_out_len(pl, n_frames);
     const long long per = block_frames >= resample_reach(pl) ? resample_block_outputs(pl, block_frames) : 0;
@@ -242,8 +263,7 @@ int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames,
                 CK(hipEventCreate(&e1)); evs.push_back(e1);
                 CK(hipEventRecord(e0, st));
             }
-            if (sample_format == WLX_PCM_S16) hipLaunchKernelGGL(resample_kernel<WLX_PCM_S16>, dim3(grid), dim3(RS_THREADS), lds, st, p);
-            else hipLaunchKernelGGL(resample_kernel<WLX_PCM_F32>, dim3(grid), dim3(RS_THREADS), lds, st, p);
+            rs_launch(sample_format, grid, lds, st, p, split_stride);
             CK(hipGetLastError());
             if (kernel_ms) CK(hipEventRecord(e1, st));
             return WLX_OK;
@@ -282,6 +302,20 @@ int resample_run_device(const ResamplePlan& pl, const float* d_frames, long long
     return WLX_OK;
 }
 
+// The split sibling: channel c of the device frames -> d_out + c * out_stride, one launch with grid.y = channels. Does not wait.
+int resample_run_device_split(const ResamplePlan& pl, const float* d_frames, long long n_frames, int channels, float* d_out,
+                              long long out_stride, hipStream_t st) {
+    const long long n_out = resample_out_len(pl, n_frames);
+    if (n_out <= 0) return WLX_OK;
+    ResampleArgs p{};
+    p.raw = d_frames; p.j_base = 0; p.raw_frames = n_frames; p.n_frames = n_frames; p.channels = channels;
+    p.up = pl.up; p.down = pl.down; p.half_len = pl.half_len; p.tile = pl.tile; p.taps = pl.taps; p.out = d_out; p.m0 = 0; p.m1 = n_out;
+    const unsigned grid = (unsigned)((n_out + pl.tile - 1) / pl.tile);
+    rs_launch(WLX_PCM_F32, grid, rs_lds_bytes(pl.up, pl.down, pl.half_len, pl.tile), st, p, out_stride);
+    CK(hipGetLastError());
+    return WLX_OK;
+}
+
 // one validation for the product entry point and the hook: everything that does not need a device
 int resample_check_args(const void* frames, long long n_frames, int channels, int sample_format, int sample_rate) {
     if (n_frames < 0) return set_error(WLX_ERR_ARG, "negative frame count");
@@ -299,8 +333,9 @@ int resample_check_args(const void* frames, long long n_frames, int channels, in
 using namespace wlx;
 
 // ------------------------------------------------------------------------------------------------ test hooks (kernel_hooks.hip conventions)
+// split: out is [channels][cap] and channel c lands in row c (the split instantiation); else out is [cap] (the down-mix)
 static int debug_resample(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format, int32_t sample_rate,
-                          int64_t block_frames, float* out, int64_t cap, int64_t* n_out, float* kernel_ms) {
+                          int64_t block_frames, float* out, int64_t cap, int64_t* n_out, float* kernel_ms, bool split = false) {
     if (!out || !n_out || cap < 0) return set_error(WLX_ERR_ARG, "null argument");
     CKR(resample_check_args(frames, n_frames, channels, sample_format, sample_rate));
     if (block_frames < 0) return set_error(WLX_ERR_ARG, "negative block size");
@@ -335,11 +370,12 @@ static int debug_resample(int32_t device, const void* frames, int64_t n_frames, 
     float* dout = nullptr;
     CKR(dalloc(S.allocs, &r0, (size_t)bf * fb, false));
     CKR(dalloc(S.allocs, &r1, (size_t)bf * fb, false));
-    CKR(dalloc(S.allocs, &dout, (size_t)cap, false));
+    const size_t out_floats = (size_t)cap * (split ? (size_t)channels : 1);
+    CKR(dalloc(S.allocs, &dout, out_floats, false));
     sg.dev[0] = r0; sg.dev[1] = r1;
-    CK(hipMemcpyAsync(dout, out, (size_t)cap * sizeof(float), hipMemcpyHostToDevice, S.st));     // copied in AND out
-    CKR(resample_run(pl, frames, n_frames, channels, sample_format, block_frames, sg, dout, S.st, kernel_ms));
-    CK(hipMemcpyAsync(out, dout, (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, S.st));
+    CK(hipMemcpyAsync(dout, out, out_floats * sizeof(float), hipMemcpyHostToDevice, S.st));     // copied in AND out
+    CKR(resample_run(pl, frames, n_frames, channels, sample_format, block_frames, sg, dout, S.st, kernel_ms, split ? (long long)cap : 0));
+    CK(hipMemcpyAsync(out, dout, out_floats * sizeof(float), hipMemcpyDeviceToHost, S.st));
     CK(hipStreamSynchronize(S.st));
     return WLX_OK;
 }
@@ -354,4 +390,9 @@ extern "C" int32_t wlx_debug_resample_timed(int32_t device, const void* frames, 
                                             float* kernel_ms_out) {
     if (!kernel_ms_out) return set_error(WLX_ERR_ARG, "null argument");
     return debug_resample(device, frames, n_frames, channels, sample_format, sample_rate, block_frames, out, cap, n_out, kernel_ms_out);
+}
+
+extern "C" int32_t wlx_debug_resample_split(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
+                                            int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out) {
+    return debug_resample(device, frames, n_frames, channels, sample_format, sample_rate, block_frames, out, cap, n_out, nullptr, true);
 }

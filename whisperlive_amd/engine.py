@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import threading
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -204,6 +204,34 @@ class Slot:
                                           int(sample_rate), C.byref(n)))
         return n.value
 
+    def put_frames_split(self, frames: np.ndarray, sample_rate: int, first_item: int = 0) -> int:
+        """File frames [n, channels] (or a FlacFrames) -> channel c as 16 kHz mono float32 resident in item first_item + c: ONE upload,
+        no down-mix, each item bit-identical to put_frames(frames[:, c]) (wlx_pcm_put_frames_split / wlx_pcm_put_flac_split).
+        -> samples resident in each of the `channels` items. Raises WlxError (ERR_ARG) for a shape the device front end refuses and for
+        first_item + channels > max_batch: nothing is launched, every item is left as it was."""
+        if isinstance(frames, FlacFrames):
+            n, info = C.c_int64(0), _lib.wlx_flac_info()
+            check(self.lib.wlx_pcm_put_flac_split(self.engine._h, self.sid, first_item, frames.data, len(frames.data), C.byref(info), C.byref(n)))
+            frames.info = info
+            return n.value
+        x = np.asarray(frames)
+        if x.ndim == 1:
+            x = x[:, None]
+        fmt = _lib.PCM_S16 if x.dtype == np.int16 else _lib.PCM_F32
+        x = np.ascontiguousarray(x, dtype=np.int16 if fmt == _lib.PCM_S16 else np.float32)
+        n = C.c_int64(0)
+        check(self.lib.wlx_pcm_put_frames_split(self.engine._h, self.sid, first_item, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1],
+                                                fmt, int(sample_rate), C.byref(n)))
+        return n.value
+
+    def put_flac_split(self, data: bytes, first_item: int = 0):
+        """The bytes of a FLAC file -> channel c resident in item first_item + c, decoded and resampled on the device with one split launch
+        (wlx_pcm_put_flac_split); each item bit-identical to put_frames(audio_io.read_flac(data)[0][:, c]). -> (samples resident per
+        item, info). WlxError codes as put_flac."""
+        frames = FlacFrames(data)
+        n = self.put_frames_split(frames, frames.sample_rate, first_item)
+        return n, frames.info
+
     def put_flac(self, data: bytes, item: int = 0):
         """The bytes of a FLAC file -> 16 kHz mono float32 resident in the item's PCM buffer: indexed on the host, decoded, down-mixed and
         resampled on the device (wlx_pcm_put_flac); bit-identical to put_frames(audio_io.read_flac(data)). -> (samples resident, info)
@@ -236,13 +264,22 @@ class Slot:
         check(self.lib.wlx_logmel_ring(self.engine._h, self.sid, item, ring._h, rg.ctypes.data_as(C.POINTER(C.c_int64)), rg.shape[0], C.byref(nf)))
         return nf.value
 
-    def logmel_chunks(self, chunks: Sequence[Sequence[Tuple[int, int]]], src_item: int = 0, first_item: int = 0) -> List[int]:
+    def logmel_chunks(self, chunks: Sequence[Sequence[Tuple[int, int]]], src_item: Union[int, Sequence[int]] = 0,
+                      first_item: int = 0) -> List[int]:
         """One launch of each log-mel kernel for len(chunks) chunks of the resident PCM of `src_item`: chunk c = the concatenation of
-        its [(start, end), ...] sample ranges -> features of item first_item + c. -> frames per chunk; see wlx_logmel_chunks"""
+        its [(start, end), ...] sample ranges -> features of item first_item + c. -> frames per chunk; see wlx_logmel_chunks.
+        A sequence `src_item` names one source item PER CHUNK (the channels of a file): wlx_logmel_chunks_multi, still one launch."""
         off = np.zeros(len(chunks) + 1, dtype=np.int32)
         off[1:] = np.cumsum([len(c) for c in chunks])
         rg = np.ascontiguousarray(np.asarray([r for c in chunks for r in c], dtype=np.int64).reshape(-1, 2))
         nf = np.zeros(max(1, len(chunks)), dtype=np.int32)
+        if not isinstance(src_item, (int, np.integer)):
+            src = np.ascontiguousarray(list(src_item), dtype=np.int32)
+            if src.shape != (len(chunks),):
+                raise ValueError(f"{src.size} source items for {len(chunks)} chunks")
+            check(self.lib.wlx_logmel_chunks_multi(self.engine._h, self.sid, _i32p(src), rg.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(off),
+                                                   len(chunks), first_item, _i32p(nf)))
+            return nf[: len(chunks)].tolist()
         check(self.lib.wlx_logmel_chunks(self.engine._h, self.sid, src_item, rg.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(off),
                                          len(chunks), first_item, _i32p(nf)))
         return nf[: len(chunks)].tolist()

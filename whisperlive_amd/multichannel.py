@@ -1,0 +1,240 @@
+"""BatchedInferencePipeline.transcribe(multichannel=True): every channel of a file transcribed on its own, in shared decode groups.
+
+A two-party call recording carries one speaker per channel; the down-mix every other route starts from sums overlapping talk and
+throws the channel's speaker identity away. Here the file's C channels become resident — one upload, no down-mix — in the LAST C items
+of the calling thread's slot (item max_batch - C + c: ``Slot.put_frames_split`` / ``put_flac_split``), the gate reads all of them in one
+pass (``SileroHIPModel.probs_pcm_many``), and the chunks of all channels are pooled in order (channel, start) and decoded
+``batch_size`` at a time whatever their channel: per group ``logmel_chunks`` with one source item per chunk
+(``wlx_logmel_chunks_multi``), ``encode``, ``generate`` and — with ``word_timestamps`` — ``align_batch``. The destination items of a
+group are 0 .. batch_size - 1 and ``batch_size <= max_batch - C``, so no group ever overwrites a source. Nothing but the one upload and
+the range tables crosses PCIe. There is NO host route: a shape the device front end refuses is a ValueError.
+
+The functions above ``transcribe_multichannel`` are host logic only (tests/test_multichannel_host.py).
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import vad as _vad
+from ._lib import ERR_ARG as _ERR_ARG, ERR_DATA as _ERR_DATA, WlxError as _WlxError
+from .engine import FlacFrames, ResidentPcm, resample_supported
+from .tokenizer import Tokenizer
+from .transcriber import restore_speech_timestamps
+from .types import Segment, TranscriptionInfo, Word
+
+
+def check_batch(batch_size: int, max_batch: int, channels: int):
+    """the C channels take the last C items of the slot; a decode group's destination items must stay in front of them"""
+    if batch_size > max_batch - channels:
+        raise ValueError(f"multichannel: batch_size {batch_size} exceeds max_batch {max_batch} - {channels} channels = "
+                         f"{max_batch - channels} (the file's channels stay resident in the slot's last {channels} items): "
+                         f"create the model with max_batch >= {batch_size + channels} or lower batch_size")
+
+
+def pool_chunks(per_channel: Sequence[Tuple[list, list]]):
+    """per channel (chunk ranges, chunk metadata), each in start order -> (ranges, metadata, channel per chunk) of all channels in
+    order (channel, start)"""
+    ranges, meta, channels = [], [], []
+    for c, (rg, md) in enumerate(per_channel):
+        ranges.extend(rg)
+        meta.extend(md)
+        channels.extend([c] * len(rg))
+    return ranges, meta, channels
+
+
+def language_channel(speech_samples: Sequence[int]) -> int:
+    """the channel the file's language is detected on: the one with the most speech after the gate, the lowest index on a tie"""
+    best = 0
+    for c, n in enumerate(speech_samples):
+        if n > speech_samples[best]:
+            best = c
+    return best
+
+
+def order_segments(segments: List[Segment]) -> List[Segment]:
+    """segments of all channels, each on its own channel's timeline -> sorted by (start, channel), ids 1..N in that order"""
+    out = sorted(segments, key=lambda s: (s.start, s.channel))          # (stable: equal keys keep their decode order)
+    for i, s in enumerate(out):
+        s.id = i + 1
+    return out
+
+
+def parse_waveform(audio: np.ndarray) -> np.ndarray:
+    """1-D waveform -> [n, 1]; 2-D [n, C] stays; anything else is refused"""
+    if audio.ndim == 1:
+        return audio[:, None]
+    if audio.ndim != 2:
+        raise ValueError(f"multichannel: a waveform is [n] or [n, channels] at 16 kHz, not {audio.ndim}-dimensional")
+    return audio
+
+
+_NO_HOST = "multichannel=True has no host route: convert the file, or transcribe its down-mix with multichannel=False"
+
+
+def _make_resident(slot, audio, max_batch: int, batch_size: int):
+    """-> (channels, samples per channel, first item): the file's channels resident in the last C items of the slot"""
+    if isinstance(audio, np.ndarray):
+        frames = parse_waveform(audio)
+        frames = frames if frames.dtype == np.int16 else np.ascontiguousarray(frames, dtype=np.float32)
+        rate, flac = 16000, None
+    else:
+        if not isinstance(audio, (str, bytes, bytearray)) and not hasattr(audio, "read"):
+            raise TypeError("audio must be a float32 numpy waveform at 16 kHz, or a WAV / FLAC path, bytes or file object")
+        from .audio_io import _read_all, read_audio
+        data = _read_all(audio)
+        if data[:4] == b"fLaC":
+            import ctypes as C
+            from . import _lib
+            lib = slot.lib
+            info = _lib.wlx_flac_info()
+            rc = lib.wlx_flac_probe(data, len(data), C.byref(info))
+            if rc == _ERR_DATA:
+                raise ValueError(f"damaged FLAC stream: {lib.wlx_last_error().decode()}")
+            if rc != 0 or not info.served:
+                raise ValueError(f"FLAC stream of {info.sample_rate} Hz x {info.channels} channels x {info.bits_per_sample} bits: the device "
+                                 f"front end does not serve it. {_NO_HOST}")
+            flac, frames, rate = FlacFrames(data), None, info.sample_rate
+            channels = info.channels
+        else:
+            frames, rate = read_audio(data)
+            flac = None
+    if flac is None:
+        channels = frames.shape[1]
+        if frames.shape[0] == 0:
+            raise ValueError("multichannel: empty audio")
+        if not resample_supported(rate, channels):
+            raise ValueError(f"{rate} Hz x {channels} channels: the device front end does not serve this shape. {_NO_HOST}")
+    if channels >= max_batch:
+        raise ValueError(f"multichannel: {channels} channels need a transcriber with max_batch >= {channels + 1}, this one has {max_batch}")
+    check_batch(batch_size, max_batch, channels)
+    first = max_batch - channels
+    try:
+        with slot.lock:
+            n = slot.put_frames_split(flac if flac is not None else frames, rate, first)
+    except _WlxError as e:
+        if e.code == _ERR_DATA:
+            raise ValueError(f"damaged FLAC stream: {e}") from e
+        if e.code == _ERR_ARG:
+            raise ValueError(f"the device front end refused the audio ({e}). {_NO_HOST}") from e
+        raise
+    return channels, n, first
+
+
+def source_rows_addressable(channels: int, n_samples: int) -> bool:
+    """wlx_logmel_chunks_multi addresses every source row from the lowest one with a 32-bit offset (csrc/logmel.hip keeps a range's
+    physical start as an int): the C neighbouring rows, each as long as the slot's PCM buffers become for n_samples (whole 30 s
+    windows), must span at most 2^31 - 1 samples. Eight channels of one hour are 4.6e8: what the front end serves always fits."""
+    cap = -(-max(int(n_samples), 1) // 480000) * 480000
+    return channels * cap <= 0x7FFFFFFF
+
+
+def transcribe_multichannel(pipe, a: dict):
+    """The body of BatchedInferencePipeline.transcribe(multichannel=True); `a`: that method's arguments by name, defaults applied.
+    -> (segment generator, info): segments sorted by (start, channel) with ids 1..N in that order, each with its `channel` and times
+    on its own channel's timeline; info.duration = the file's, info.duration_after_vad = the sum over channels. One language for the
+    file."""
+    from .batched import MAX_DEC_ROWS, DeviceChunks, _collect_ranges, _options, _vad_options
+    model = pipe.model
+    sampling_rate = model.feature_extractor.sampling_rate
+    a = dict(a)
+    if a["multilingual"] and not model.model.is_multilingual:
+        model.logger.warning("The current model is English-only but the multilingual parameter is set to"
+                             "True; setting to False instead.")
+        a["multilingual"] = False
+    batch_size, beam_size = int(a["batch_size"]), int(a["beam_size"])
+    if batch_size < 1:
+        raise ValueError(f"batch_size {batch_size}: at least one chunk per decode")
+    if batch_size * beam_size > MAX_DEC_ROWS:
+        raise ValueError(f"batch_size {batch_size} x beam_size {beam_size} = {batch_size * beam_size} decoder rows: "
+                         f"one decode step holds at most {MAX_DEC_ROWS}")
+    slot = model._slot(rows=beam_size)
+    if hasattr(model, "_tls"):
+        model._tls.file_audio = None
+    if sampling_rate != 16000 or not all(hasattr(slot, m) for m in ("put_frames_split", "logmel_chunks", "pcm")):
+        raise ValueError(f"multichannel=True needs the device front end (Slot.put_frames_split), which this engine lacks. {_NO_HOST}")
+    max_batch = int(getattr(slot, "max_batch", getattr(model, "max_batch", batch_size)))
+    n_channels, n_samples, first = _make_resident(slot, a["audio"], max_batch, batch_size)
+    if not source_rows_addressable(n_channels, n_samples):          # before any decode, not from the middle of the generator
+        raise ValueError(f"multichannel: {n_channels} channels of {n_samples} samples lie further apart in the slot than the chunk "
+                         "gather addresses (2^31 - 1 samples)")
+    items = [first + c for c in range(n_channels)]
+    duration = n_samples / sampling_rate
+
+    chunk_length = a["chunk_length"] or model.feature_extractor.chunk_length
+    clip_timestamps, vad_parameters = a["clip_timestamps"], a["vad_parameters"]
+    from_vad = False
+    if clip_timestamps:
+        clips = [[dict(c) for c in clip_timestamps] for _ in items]          # explicit clips apply to every channel
+    elif a["vad_filter"]:
+        vad_parameters = _vad_options(vad_parameters, chunk_length)
+        vad_model = model._vad_model()
+        if hasattr(vad_model, "probs_pcm_many") and getattr(vad_model, "device", None) == getattr(slot.engine, "device", -1):
+            with slot.lock:                  # the gate of ALL channels in one pass over the network
+                probs = vad_model.probs_pcm_many(slot, [n_samples] * n_channels, first_item=first)
+            clips = [_vad.speech_segments_from_probs_native(p, n_samples, vad_parameters, sampling_rate) for p in probs]
+        else:                                # a gate with no device path reads the host copy, channel by channel
+            with slot.lock:
+                waves = [slot.pcm(i) for i in items]
+            clips = [_vad.get_speech_timestamps(w, vad_parameters, sampling_rate, model=vad_model) for w in waves]
+        from_vad = True
+    elif duration < chunk_length:
+        clips = [[{"start": 0, "end": n_samples}] for _ in items]
+    else:
+        raise RuntimeError("No clip timestamps found. "
+                           "Set 'vad_filter' to True or provide 'clip_timestamps'.")
+    clips = [[c for c in cl if c["end"] > c["start"]] for cl in clips]
+    speech = [sum(c["end"] - c["start"] for c in cl) for cl in clips]
+    duration_after_vad = sum(speech) / sampling_rate
+
+    per_channel = [_collect_ranges(cl, sampling_rate, chunk_length) if cl else ([], []) for cl in clips]
+    ranges, meta, channels = pool_chunks(per_channel)
+
+    def host_audio(item):
+        return slot.pcm(item)
+
+    features = DeviceChunks(slot, ranges, host_audio, [items[c] for c in channels], n_samples)
+    if hasattr(model, "_tls"):
+        # what reads the file after the transcription (speaker labels) finds each channel in its item: resident_file_audio(channel)
+        model._tls.file_audio = [ResidentPcm(slot, i, n_samples) for i in items]
+
+    # one language for the file: detected (a multilingual model, none given) on the channel with the most speech, in groups of
+    # batch_size chunks so that the detection's log-mel launches stay in front of the source items too
+    lc = language_channel(speech)
+    lead = features[channels.index(lc): channels.index(lc) + channels.count(lc)] if lc in channels else features[0:0]
+    language, language_probability, all_language_probs = pipe._language(
+        lead, a["language"], a["language_detection_segments"], a["language_detection_threshold"], group_size=batch_size)
+
+    tokenizer = Tokenizer(model.hf_tokenizer, model.model.is_multilingual, task=a["task"], language=language)
+    options = _options(tokenizer, a, clip_timestamps if clip_timestamps else clips)
+    info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
+                             duration_after_vad=duration_after_vad, transcription_options=options,
+                             vad_options=vad_parameters, all_language_probs=all_language_probs)
+    return _segments(pipe, features, tokenizer, meta, channels, batch_size, options, a["log_progress"],
+                     clips if from_vad else None, sampling_rate), info
+
+
+def _segments(pipe, features, tokenizer, meta, channels, batch_size, options, log_progress, vad_clips: Optional[list], sampling_rate):
+    """decode the pooled chunks group by group, restore each segment's times on its own channel's timeline, then yield all of them in
+    (start, channel) order (the order is known only when the last group is done)"""
+    slot = features.slot
+    features.channels = channels            # every group is cut with its chunks' channels (batched.forward reads them)
+    out: List[Segment] = []
+    for i in range(0, len(features), batch_size):
+        chans = channels[i: i + batch_size]
+        with slot.lock:
+            results = pipe.forward(features[i: i + batch_size], tokenizer, meta[i: i + batch_size], options)
+        for ch, result in zip(chans, results):
+            for segment in result:
+                seg = Segment(
+                    seek=segment["seek"], id=0, text=segment["text"], start=round(segment["start"], 3), end=round(segment["end"], 3),
+                    words=(None if not options.word_timestamps else [Word(**word) for word in segment["words"]]),
+                    tokens=segment["tokens"], avg_logprob=segment["avg_logprob"], no_speech_prob=segment["no_speech_prob"],
+                    compression_ratio=segment["compression_ratio"], temperature=options.temperatures[0], channel=ch)
+                if vad_clips is not None:
+                    seg = restore_speech_timestamps([seg], vad_clips[ch], sampling_rate)[0]
+                out.append(seg)
+        if log_progress:
+            pipe.model.logger.info("batched transcription: %d / %d chunks", min(i + batch_size, len(features)), len(features))
+    yield from order_segments(out)

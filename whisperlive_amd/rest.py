@@ -147,14 +147,54 @@ def _words(seg) -> list:
 
 
 def render_subtitles(segments, response_format: str) -> str:
+    """A segment that carries a channel (a multichannel request) has its cue text prefixed `[ch N] `."""
     output = []
     for i, seg in enumerate(segments, 1):
         start, end = _stamp(seg.start), _stamp(seg.end)
+        ch = getattr(seg, "channel", None)
+        cue = ("" if ch is None else f"[ch {ch}] ") + seg.text.strip()
         if response_format == "srt":
-            output.append(f"{i}\n{start.replace('.', ',')} --> {end.replace('.', ',')}\n{seg.text.strip()}\n")
+            output.append(f"{i}\n{start.replace('.', ',')} --> {end.replace('.', ',')}\n{cue}\n")
         else:
-            output.append(f"{start} --> {end}\n{seg.text.strip()}\n")
+            output.append(f"{start} --> {end}\n{cue}\n")
     return "\n".join(output)
+
+
+def render_text(segments, multichannel: bool = False) -> str:
+    """the `text` of a response: the segments joined with spaces; a multichannel request gets one line per segment, in time order"""
+    return ("\n" if multichannel else " ").join([s.text.strip() for s in segments])
+
+
+def parse_bool_field(value: Optional[str], name: str) -> bool:
+    """the truthiness parsing of the `stream` form field, for any boolean field; _HttpError 400 for anything else"""
+    s = (value or "").strip().lower()
+    if s not in _TRUE and s not in _FALSE:
+        raise _HttpError(400, {"error": f"{name} must be a boolean"})
+    return s in _TRUE
+
+
+def file_channels(data: bytes) -> int:
+    """channel count of a WAV / FLAC upload from its header (0: not readable there; the transcription then says what is wrong)"""
+    try:
+        if data[:4] == b"fLaC" and len(data) >= 42 and (data[4] & 0x7F) == 0:
+            return ((data[20] >> 1) & 7) + 1
+        if data[:4] == b"RIFF":
+            from .audio_io import _wav_parse
+            return int(_wav_parse(data)[1])
+    except Exception:  # noqa: BLE001
+        pass
+    return 0
+
+
+def speaker_labels_per_channel(segments, diarizer, resident_of) -> Dict[int, str]:
+    """speaker_labels_for_segments for a multichannel transcription: each segment's audio is read from its OWN channel's resident
+    item (`resident_of(channel)` -> engine.ResidentPcm or None), one embedding call per channel. -> {segment index: speaker}"""
+    labels: Dict[int, str] = {}
+    for ch in sorted({s.channel for s in segments if s.channel is not None}):
+        index = [i for i, s in enumerate(segments) if s.channel == ch]
+        got = speaker_labels_for_segments([segments[i] for i in index], None, diarizer, resident=resident_of(ch))
+        labels.update({index[k]: v for k, v in got.items()})
+    return labels
 
 
 def segment_sample_ranges(segments, n_samples: int, sample_rate: int = 16000) -> List[Tuple[int, int, int]]:
@@ -314,9 +354,21 @@ class RestServer:
                     ServeClientHIP.MODELS[device_index] = ServeClientHIP.create_model(self.model, device_index, **kw)
             return ServeClientHIP.MODELS[device_index]
 
-    def transcribe_file(self, transcriber, data: bytes, **kw):
+    def transcribe_file(self, transcriber, data: bytes, multichannel: bool = False, **kw):
         """-> (iterable of segments or None, info or None). file_batch_size = 0: today's sequential path, exactly. Otherwise the batched
-        pipeline with the VAD chunking; its segments arrive lazily, group by group."""
+        pipeline with the VAD chunking; its segments arrive lazily, group by group. multichannel: always the batched pipeline on the
+        shared transcriber, each channel on its own; a transcriber that cannot hold the channels and one chunk is a 400."""
+        if multichannel:
+            from .batched import BatchedInferencePipeline
+            channels, max_batch = max(1, file_channels(data)), int(getattr(transcriber, "max_batch", 1))
+            if max_batch < channels + 1:
+                raise _HttpError(400, {"error": f"multichannel: a file of {channels} channels needs a transcriber that holds {channels + 1} "
+                                                f"items, this server's holds {max_batch} (start it with a file batch size >= {channels + 1})"})
+            batch = min(self.file_batch_size if self.file_batch_size > 0 else max_batch, max_batch - channels)
+            try:
+                return BatchedInferencePipeline(transcriber).transcribe(data, vad_filter=True, batch_size=batch, multichannel=True, **kw)
+            except ValueError as e:              # a shape the device front end refuses: there is no host route
+                raise _HttpError(400, {"error": str(e)})
         if self.file_batch_size <= 0:
             return transcriber.transcribe(data, vad_filter=False, **kw)
         from .batched import BatchedInferencePipeline
@@ -516,6 +568,7 @@ class _Handler(BaseHTTPRequestHandler):
         stream_s = (one("stream", "false") or "").strip().lower()
         if stream_s not in _TRUE and stream_s not in _FALSE:
             raise _HttpError(400, {"error": "stream must be a boolean"})
+        multichannel = parse_bool_field(one("multichannel", "false"), "multichannel")
         timestamp_granularities = normalize_form_list(many("timestamp_granularities") + many("timestamp_granularities[]")) or None
         chunking_strategy = one("chunking_strategy")
         include = many("include") + many("include[]") or None
@@ -525,6 +578,8 @@ class _Handler(BaseHTTPRequestHandler):
         rest = self.rest
 
         if stream_s in _TRUE:
+            if multichannel:     # the segments of a multichannel file are ordered only when its last group is done: nothing to stream
+                raise _HttpError(400, {"error": "multichannel cannot be combined with stream: send the request without stream"})
             return self._stream(file, language, prompt, temperature, want_words)
 
         ignored_params = []
@@ -545,10 +600,11 @@ class _Handler(BaseHTTPRequestHandler):
         try:
             device_index = rest._next_device()
             transcriber = rest.transcriber_for(device_index)
+            mc = {"multichannel": True} if multichannel else {}
             segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
-                                                  temperature=temperature, word_timestamps=want_words, hotwords=hotwords)
+                                                  temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)
             segments = list(segments or [])
-            text = " ".join([s.text.strip() for s in segments])
+            text = render_text(segments, multichannel)
             if response_format == "text":
                 wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
                 return self._text(200, text)
@@ -563,7 +619,9 @@ class _Handler(BaseHTTPRequestHandler):
                     rest_diarizer = rest.create_rest_diarizer(known_speaker_names, known_speaker_references, device_index)
                 except ValueError as e:
                     raise _HttpError(400, {"error": str(e)})
-                if rest_diarizer is not None:
+                if rest_diarizer is not None and multichannel:
+                    speaker_labels = speaker_labels_per_channel(segments, rest_diarizer, getattr(transcriber, "resident_file_audio", lambda c: None))
+                elif rest_diarizer is not None:
                     # from the audio the transcription left in the thread's slot (held until _release below); the file is decoded
                     # a second time only when nothing is resident (host-resampled rate, an engine without the front end)
                     from . import audio_io
@@ -573,6 +631,8 @@ class _Handler(BaseHTTPRequestHandler):
                     seg_dict = {"id": seg.id, "seek": seg.seek, "start": seg.start, "end": seg.end, "text": seg.text.strip(),
                                 "tokens": seg.tokens, "temperature": seg.temperature, "avg_logprob": seg.avg_logprob,
                                 "compression_ratio": seg.compression_ratio, "no_speech_prob": seg.no_speech_prob}
+                    if multichannel:
+                        seg_dict["channel"] = seg.channel
                     if index in speaker_labels:
                         seg_dict["speaker"] = speaker_labels[index]
                     if want_words:

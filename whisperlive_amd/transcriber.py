@@ -426,12 +426,17 @@ class WhisperModelHIP:
                 old.close()
         return s
 
-    def resident_file_audio(self):
+    def resident_file_audio(self, channel: Optional[int] = None):
         """The 16 kHz audio the calling thread's last file transcription (`transcribe`, or BatchedInferencePipeline on this model) left
         resident in its slot, as an engine.ResidentPcm — for what reads the audio after the transcription (speaker labels) without a
         second decode. None when that call took the host route, when the item has been overwritten since, or after release_slot():
-        a released slot may be refilled by another request, so the handle is good only while this thread keeps its slot."""
+        a released slot may be refilled by another request, so the handle is good only while this thread keeps its slot.
+        `channel`: after a multichannel transcription the handles are left per channel and the channel has to be named."""
         h = getattr(self._tls, "file_audio", None)
+        if isinstance(h, (list, tuple)):         # a multichannel transcription left one handle per channel: name the channel
+            h = h[channel] if channel is not None and 0 <= channel < len(h) else None
+        elif channel not in (None, 0):
+            h = None
         if h is None or h.slot is not getattr(self._tls, "slot", None) or not h.intact():
             return None
         return h

@@ -28,6 +28,7 @@ class Segment:
     no_speech_prob: float
     words: Optional[List[Word]] = None
     temperature: Optional[float] = None
+    channel: Optional[int] = None       # the file channel the segment was heard on (BatchedInferencePipeline multichannel=True), else None
 
 
 @dataclass
