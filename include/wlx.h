@@ -378,7 +378,8 @@ int32_t wlx_vad_create(const wlx_vad_weights* w, int32_t device, wlx_vad** out);
 void    wlx_vad_destroy(wlx_vad* v);
 /* `n` float32 samples (host pointer) -> ceil(n/512) probabilities (host buffer of `cap` floats); the last window is
  * zero-padded. Each call starts from a zero state, like get_speech_timestamps on a fresh chunk. Thread-safe (calls on
- * one object are serialised; it owns its HIP stream). device_ms_out (nullable): kernel time between HIP events. */
+ * one object are serialised; it owns its HIP stream). device_ms_out (nullable): kernel time between HIP events.
+ * The pass is that of wlx_vad_probs_batch (below) with one item; so are wlx_vad_probs_resident and wlx_vad_probs_pcm. */
 int32_t wlx_vad_probs(wlx_vad* v, const float* pcm, int64_t n, float* probs_out, int32_t cap,
                       int32_t* n_windows_out, float* device_ms_out);
 
@@ -409,7 +410,7 @@ int32_t wlx_ring_state(wlx_ring* r, int64_t* base_out, int64_t* resident_out);
 int32_t wlx_vad_probs_resident(wlx_vad* v, wlx_ring* r, int64_t start, int64_t n, int32_t extra_zero_windows,
                                float* probs_out, int32_t cap, int32_t* n_windows_out, float* device_ms_out);
 /* wlx_vad_probs_resident with the resident PCM of a slot item (wlx_pcm_put / wlx_pcm_put_frames) in place of the ring: samples
- * [start, start + n) of item `item`, same contract and kernels, no host-to-device copy, and the VAD object's own PCM buffers (device
+ * [start, start + n) of item `item`, same contract, no host-to-device copy, and the VAD object's own PCM buffers (device
  * and pinned) do not grow with the file — only its per-window buffers do. The VAD object's stream is ordered behind the slot's stream
  * with an event (a wlx_pcm_put_frames resample may still be in flight), never through the null stream. The slot counts as busy for
  * the call (WLX_ERR_STATE on a busy slot). `v` and `e` on different devices: WLX_ERR_ARG; a span outside the resident samples:
@@ -422,10 +423,11 @@ int32_t wlx_vad_probs_pcm(wlx_vad* v, wlx_engine* e, int32_t slot, int32_t item,
  * wlx_vad_probs_batch: `pcm` holds the n segments back to back on the host, segment i of n_samples[i] samples.
  * T_i = ceil(n_samples[i] / 512) + extra_zero_windows[i] windows (0 <= extra <= 4, meaning as in wlx_vad_probs_resident; a null
  * `extra_zero_windows` is all 0). probs_out receives the rows packed in item order (sum T_i <= cap floats), n_windows_out[i] = T_i.
- * Row i has the bits wlx_vad_probs returns for segment i zero-padded to 512 * T_i samples, whatever else is in the batch and in
- * whatever order: every item starts from a zero state and no workgroup serves two items. An item with T_i == 0 takes no part (all
- * empty: WLX_OK, nothing launched). WLX_ERR_ARG before any launch, nothing written: n outside 1..WLX_VAD_MAX_BATCH, a null pointer, a
- * negative count, an extra out of range, sum T_i > cap, more than 3600 s of samples in all.
+ * Row i does not depend on what else is in the batch, or in what order: every item starts from a zero state and no workgroup serves
+ * two items. (wlx_vad_probs on segment i zero-padded to 512 * T_i samples is this pass with that one item, so it returns the same
+ * bits.) An item with T_i == 0 takes no part (all empty: WLX_OK, nothing launched). WLX_ERR_ARG before any launch, nothing written:
+ * n outside 1..WLX_VAD_MAX_BATCH, a null pointer, a negative count, an extra out of range, sum T_i > cap, more than 3600 s of
+ * samples in all.
  * wlx_vad_probs_pcm_batch: the same on samples [0, n_samples[i]) of the resident PCM of slot items first_item + i (wlx_pcm_put /
  * wlx_pcm_put_frames): no host-to-device copy of audio, the VAD object's PCM buffers (device and pinned) are not touched, its stream is
  * ordered behind the slot's with ONE event, the slot counts as busy for the call. Errors as wlx_vad_probs_pcm: WLX_ERR_ARG for
@@ -508,14 +510,16 @@ typedef struct wlx_spk wlx_spk;
 int32_t wlx_spk_create(const wlx_spk_spec* spec, const wlx_tensor* weights, int32_t n_weights, int32_t device, wlx_spk** out);
 void    wlx_spk_destroy(wlx_spk* spk);
 /* L2-normalised embedding out[embed_dim] of 16 kHz mono PCM in [-1, 1]. WLX_ERR_TOO_SHORT under 4800 samples (0.3 s, where the
- * reference returns no embedding), WLX_ERR_ARG over max_seconds. Returns when the result is final. */
+ * reference returns no embedding; `out` is not written), WLX_ERR_ARG over max_seconds. Returns when the result is final. The pass is
+ * that of wlx_spk_embed_batch with one segment. */
 int32_t wlx_spk_embed(wlx_spk* spk, const float* pcm_f32, int64_t n_samples, float* out);
-/* The same for 1 <= n <= WLX_SPK_MAX_BATCH segments in ONE pass over the network (one upload, one launch sequence, one wait):
- * pcm_f32 holds the segments back to back (host), n_samples[i] the length of each, out [n][embed_dim] one embedding per segment,
- * with the bits wlx_spk_embed gives for that segment alone, whatever else is in the batch. status[i] = WLX_OK, or
- * WLX_ERR_TOO_SHORT for a segment under 4800 samples: its row is zero and it takes no part in the pass (all too short: WLX_OK,
- * nothing launched). The segments share the engine's buffers: WLX_ERR_ARG, nothing launched and nothing written, when their
- * lengths sum to more than max_seconds, for n outside its range and for a null pointer. */
+/* 1 <= n <= WLX_SPK_MAX_BATCH segments in ONE pass over the network (one upload, one launch sequence, one wait):
+ * pcm_f32 holds the segments back to back (host), n_samples[i] the length of each, out [n][embed_dim] one embedding per segment.
+ * A row does not depend on what else is in the batch or where the segment stands in it (so it has the bits of wlx_spk_embed
+ * on that segment, which is this pass with n = 1). status[i] = WLX_OK, or WLX_ERR_TOO_SHORT for a segment under 4800
+ * samples: its row is zero and it takes no part in the pass (all too short: WLX_OK, nothing launched). The segments share
+ * the engine's buffers: WLX_ERR_ARG, nothing launched and nothing written, when their lengths sum to more than max_seconds,
+ * for n outside its range and for a null pointer. */
 #define WLX_SPK_MAX_BATCH 64
 int32_t wlx_spk_embed_batch(wlx_spk* spk, const float* pcm_f32, const int64_t* n_samples, int32_t n, float* out, int32_t* status);
 /* wlx_spk_embed_batch on ranges of RESIDENT audio: entry i is samples [starts[i], starts[i] + n_samples[i]) of the resident PCM of
@@ -607,7 +611,9 @@ int32_t wlx_spk_debug_conv(int32_t device, const uint16_t* in, int32_t H, int32_
 int32_t wlx_spk_debug_pool(int32_t device, const uint16_t* x, int32_t F, int32_t T, int32_t C, float eps, float* out);
 /* The ragged forms, one launch over n <= WLX_SPK_MAX_BATCH items packed back to back without padding. Convolution: item i is its own
  * [H][widths[i]][Cin] image in `in` and its own [OH][(widths[i] - 1) / stride + 1][Cout] image in `resid` / `out`; the rest as
- * wlx_spk_debug_conv, Cin = 1 included. Pooling: item i is [F][frames[i]][C] (frames[i] >= 2), out float32 [n][2][C][F]. */
+ * wlx_spk_debug_conv, Cin = 1 included. Pooling: item i is [F][frames[i]][C] (frames[i] >= 2), out float32 [n][2][C][F].
+ * wlx_spk_debug_conv and _pool go through the same launchers with n = 1 (for Cin >= 32 the launcher then picks a kernel without the
+ * item table around the same tile code, as it does for wlx_spk_embed); the filterbank has no ragged hook. */
 int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, int32_t H, int32_t n, const int32_t* widths, int32_t Cin,
                                  const float* w, const float* bias, const uint16_t* resid, int32_t Cout, int32_t stride, int32_t ksize,
                                  int32_t relu, uint16_t* out);

@@ -14,10 +14,12 @@ REL_RMS = 2e-3
 NETWORK_CONVS = [(32, 32, 1, 3), (32, 64, 2, 3), (64, 64, 1, 3), (64, 128, 2, 3), (128, 128, 1, 3), (128, 256, 2, 3), (256, 256, 1, 3),
                  (32, 64, 2, 1), (64, 128, 2, 1), (128, 256, 2, 1)]
 # (H, W, Cin, Cout, stride, ksize): odd H and W under stride 2; W of 1, 2 and 17; H W not a multiple of the 16-pixel wave tile or
-# the 64-pixel workgroup tile; the 40 pixels x K = 2304 of a 0.3 s segment in the last stage; one tile exactly
+# the 64-pixel workgroup tile; the 40 pixels x K = 2304 of a 0.3 s segment in the last stage; one tile exactly; H = 5 with
+# W = 1 / 17 under stride 2 with two and with four channel tiles per wave (one item: the launcher's table-free n = 1 kernel)
 EDGE_CONVS = [(7, 9, 32, 64, 2, 3), (5, 3, 64, 128, 2, 3), (7, 9, 32, 64, 2, 1), (10, 1, 32, 32, 1, 3), (10, 1, 64, 128, 2, 3),
               (10, 2, 32, 32, 1, 3), (3, 17, 64, 64, 1, 3), (3, 17, 128, 256, 2, 3), (1, 1, 32, 32, 1, 3), (1, 5, 32, 64, 2, 1),
-              (10, 4, 256, 256, 1, 3), (13, 5, 128, 128, 1, 3), (4, 4, 32, 32, 1, 3), (8, 8, 64, 64, 1, 3), (9, 29, 32, 96, 1, 3)]
+              (10, 4, 256, 256, 1, 3), (13, 5, 128, 128, 1, 3), (4, 4, 32, 32, 1, 3), (8, 8, 64, 64, 1, 3), (9, 29, 32, 96, 1, 3),
+              (5, 1, 32, 32, 2, 3), (5, 1, 32, 64, 2, 3), (5, 17, 32, 32, 2, 3), (5, 17, 32, 64, 2, 3)]
 
 
 def f16(a):

@@ -90,6 +90,13 @@ def test_short_and_long_audio_statuses(net):
     f32p = C.POINTER(C.c_float)
     assert eng.lib.wlx_spk_embed(eng.h, big.ctypes.data_as(f32p), len(big), out.ctypes.data_as(f32p)) == 1     # WLX_ERR_ARG
     assert _lib.ERR_TOO_SHORT == 6
+    # one sample under the minimum: the status is the return value and `out` is not written; exactly the minimum is served
+    edge = voice_pcm(0, 0.3, 1)
+    out[:] = 7.0
+    assert len(edge) == 4800 and eng.lib.wlx_spk_embed(eng.h, edge.ctypes.data_as(f32p), 4799, out.ctypes.data_as(f32p)) == 6
+    assert (out == 7.0).all()
+    assert eng.lib.wlx_spk_embed(eng.h, edge.ctypes.data_as(f32p), 4800, out.ctypes.data_as(f32p)) == 0
+    assert (out.view(np.uint32) == eng.embed(edge).view(np.uint32)).all()
 
 
 def _oracle_labels(w, pcms, threshold, max_speakers=10):

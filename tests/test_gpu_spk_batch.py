@@ -1,6 +1,11 @@
-"""GPU tests of the ragged-batch speaker path: the one-launch hooks wlx_spk_debug_conv_batch / _pool_batch against the single-item
-hooks (bit for bit) and the float64 references of tests/spk_kernel_ref.py, and wlx_spk_embed_batch / embed_many /
-identify_speakers on the whole seeded ResNet34 against the single-item calls (bit for bit)."""
+"""GPU tests of the ragged-batch speaker path. The single-item hooks and wlx_spk_embed go through the same launchers with a batch of
+one; for the stem, the pooling and the head that is the same kernel, for the filterbank, the mean removal and the MFMA convolution the
+launcher picks at n = 1 a kernel without the item table around the same device function. So the bit-for-bit comparisons state that an
+item's result does not depend on its neighbours, its position or the table's fill, and for those three also on which of the two
+kernels around one body computed it: the
+one-launch hooks wlx_spk_debug_conv_batch / _pool_batch against each item as a batch of one, and wlx_spk_embed_batch / embed_many /
+identify_speakers on the whole seeded ResNet34 against each segment on its own. The absolute references are the float64 ones of
+tests/spk_kernel_ref.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -59,7 +64,7 @@ def _check_conv_batch(Cin, Cout, stride, ks, resid):
         r = rs[i] if resid else None
         rc1, alone = R.run_conv(xs[i], w, b, r, stride, relu)
         assert rc1 == 0 and got[i].shape == alone.shape and np.isfinite(got[i].astype(np.float32)).all()
-        assert (_bits(got[i]) == _bits(alone)).all(), f"item {i} (W = {W}) differs from the single-item launch"
+        assert (_bits(got[i]) == _bits(alone)).all(), f"item {i} (W = {W}) differs from the item as a batch of one"
         e = R.rel_rms(got[i], R.conv_ref(xs[i], w, b, r, stride, relu))
         print(f"conv batch item W={W} {Cin}->{Cout} s{stride} k{ks} resid={resid}: rel-rms {e:.3e}")
         assert e <= R.REL_RMS, (i, e)
@@ -102,7 +107,7 @@ def test_pool_batch(Cn):
     assert rc == 0 and np.isfinite(out).all()
     for i, x in enumerate(xs):
         rc1, alone = R.run_pool(x, 1e-7)
-        assert rc1 == 0 and (_bits(out[i]) == _bits(alone)).all(), f"item {i} (T = {frames[i]}) differs from the single-item launch"
+        assert rc1 == 0 and (_bits(out[i]) == _bits(alone)).all(), f"item {i} (T = {frames[i]}) differs from the item as a batch of one"
 
 
 # ------------------------------------------------------------------------------------------------ the whole engine

@@ -1,6 +1,6 @@
-"""GPU tests of the speaker kernels of csrc/spk.hip, one launch each through wlx_spk_debug_fbank / _conv / _pool, against the
-float64 references of tests/spk_kernel_ref.py on the same fp16-rounded operands (bound: spk_kernel_ref.REL_RMS, derived there)
-and, for the filterbank, the float64 restatement of tests/spk_oracle.py."""
+"""GPU tests of the speaker kernels of csrc/spk.hip, one launch each (a batch of one) through wlx_spk_debug_fbank / _conv / _pool,
+against the float64 references of tests/spk_kernel_ref.py on the same fp16-rounded operands (bound: spk_kernel_ref.REL_RMS, derived
+there) and, for the filterbank, the float64 restatement of tests/spk_oracle.py."""
 from __future__ import annotations
 
 import numpy as np
@@ -63,7 +63,8 @@ def test_conv_network_shapes(Cin, Cout, stride, ks, resid):
 @pytest.mark.parametrize("H,W,Cin,Cout,stride,ks", R.EDGE_CONVS)
 def test_conv_edge_shapes(H, W, Cin, Cout, stride, ks, resid):
     """spk_kernel_ref.EDGE_CONVS: odd H and W under stride 2, W of 1 / 2 / 17, H W off the tile, a single pixel, 40 pixels against
-    K = 2304, a Cout that is a multiple of 32 only; ReLU on without residual and off with it"""
+    K = 2304, a Cout that is a multiple of 32 only, H = 5 with W = 1 / 17 under stride 2 at Cout 32 and 64; ReLU on without residual
+    and off with it"""
     _check_conv(H, W, Cin, Cout, stride, ks, resid, relu=not resid)
 
 

@@ -1,6 +1,7 @@
 """GPU tests (-m gpu) of speaker embedding on device-resident audio: wlx_spk_embed_pcm_batch on ranges of a slot item's PCM and
-wlx_spk_embed_ring_batch on absolute positions of a PCM ring, each row against wlx_spk_embed of the same samples (bit for bit), the
-refusals, a concurrent ring writer, and the file endpoint's labelling helper on the audio a transcription left resident."""
+wlx_spk_embed_ring_batch on absolute positions of a PCM ring, each row against the upload of the same samples as a batch of one
+(wlx_spk_embed), bit for bit: a row depends neither on where its samples lie nor on the other rows; the refusals, a concurrent
+ring writer, and the file endpoint's labelling helper on the audio a transcription left resident."""
 from __future__ import annotations
 
 import ctypes as C

@@ -1,6 +1,7 @@
-"""GPU tests (-m gpu) of the ragged-batch VAD gate (include/wlx.h wlx_vad_probs_batch / wlx_vad_probs_pcm_batch): every row of a batch
-has the bits of the single-item entry point on that item alone — compared through .view(np.uint32), no tolerance — whatever else is in
-the batch and in whatever order; and the batch worker's front half built on it (WhisperModelHIP.encode_audio_batch_gated) produces the
+"""GPU tests (-m gpu) of the ragged-batch VAD gate (include/wlx.h wlx_vad_probs_batch / wlx_vad_probs_pcm_batch): a row of a batch does
+not depend on its neighbours, its position or the table's fill — it is compared with the same item as a batch of ONE (which is what the
+single entry points run) through .view(np.uint32), no tolerance; the absolute reference is oracle/silero_vad.py; and the batch worker's
+front half built on it (WhisperModelHIP.encode_audio_batch_gated) produces the
 features, encoder outputs and results of the per-request host gate."""
 import ctypes as C
 
@@ -49,7 +50,7 @@ def eng(gpu):
 
 @pytest.fixture(scope="module")
 def ragged(vm):
-    """the ragged set and its rows through the single-item entry point, computed once"""
+    """the ragged set and the row of each item on its own (wlx_vad_probs: a batch of one), computed once"""
     src = speech_like_pcm(3.0, seed=77)
     clips = [src[37 * i: 37 * i + n].copy() for i, n in enumerate(RAGGED)]
     return clips, [vm(padded(x)) for x in clips]
@@ -61,6 +62,7 @@ def test_ragged_batch_equals_singles_in_any_order(vm, ragged):
     assert [g.shape[0] for g in got] == [n // 512 + 1 for n in RAGGED]
     for i, (g, w) in enumerate(zip(got, want)):
         assert same(g, w), (i, RAGGED[i])
+        assert same(vm.probs_many([clips[i]])[0], w), (i, RAGGED[i])        # the batch entry point with one item
     for order in (list(range(len(clips)))[::-1], np.random.default_rng(5).permutation(len(clips)).tolist()):
         got = vm.probs_many([clips[i] for i in order])
         for k, i in enumerate(order):

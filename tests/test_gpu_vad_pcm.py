@@ -1,5 +1,8 @@
-"""GPU tests (-m gpu) of the VAD gate over a slot item's resident PCM (include/wlx.h wlx_vad_probs_pcm): the same kernels as the upload
-path on the same samples, bit for bit; ordered behind the slot's stream; nothing of the VAD object's PCM buffers involved."""
+"""GPU tests (-m gpu) of the VAD gate over a slot item's resident PCM (include/wlx.h wlx_vad_probs_pcm): the same pass as the upload
+path and the ring path (each a batch of one) on the same samples, bit for bit, wherever the samples lie; ordered behind the slot's
+stream; nothing of the VAD object's PCM buffers involved."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -34,20 +37,48 @@ def resident(eng):
     pcm = speech_like_pcm(3.0, seed=21)[:48000]
     slot = eng.create_slot(2, 5)
     slot.pcm_put(pcm, item=1)
-    yield slot, pcm
+    ring = eng.create_ring()
+    ring.append(pcm)                                                  # the same samples at stream positions 0 ...
+    yield slot, pcm, ring
+    ring.close()
     slot.close()
+
+
+def raw_probs(vm, x=None, ring=None, slot=None, start=0, n=0, extra=0):
+    """one of the three single entry points with an explicit extra_zero_windows (the Python wrappers choose it themselves)"""
+    if x is not None:
+        x = np.ascontiguousarray(x, np.float32)
+        n, extra = x.shape[0], 0
+    cap = -(-n // 512) + extra
+    probs, nw = np.full(cap + 1, -7.0, np.float32), C.c_int32(-1)
+    out = probs.ctypes.data_as(C.POINTER(C.c_float))
+    if x is not None:
+        rc = vm.lib.wlx_vad_probs(vm.handle, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0], out, cap, C.byref(nw), None)
+    elif ring is not None:
+        rc = vm.lib.wlx_vad_probs_resident(vm.handle, ring._h, start, n, extra, out, cap, C.byref(nw), None)
+    else:
+        rc = vm.lib.wlx_vad_probs_pcm(vm.handle, slot.engine._h, slot.sid, 1, start, n, extra, out, cap, C.byref(nw), None)
+    assert rc == 0 and nw.value == cap and probs[cap] == -7.0
+    return probs[:cap]
 
 
 @pytest.mark.parametrize("start", [0, 777])
 @pytest.mark.parametrize("n", [1, 511, 512, 513, 2560, 40000])
 def test_gate_on_resident_pcm_equals_gate_on_the_upload(vm, resident, n, start):
     from whisperlive_amd import vad
-    slot, pcm = resident
+    slot, pcm, ring = resident
     x = pcm[start:start + n]
     want = vm(np.pad(x, (0, vad.WINDOW - n % vad.WINDOW)))            # a whole zero window when n is a multiple of 512
     got = vm.probs_pcm(slot, start, n, item=1)
     assert got.shape == want.shape == (n // 512 + 1,)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    # the three single entry points are one pass: with no and with the most extra zero windows they agree bit for bit on the same
+    # samples (the upload has no such argument: it is given the zeros)
+    for extra in (0, 4):
+        up = raw_probs(vm, x=np.pad(x, (0, 512 * (-(-n // 512) + extra) - n)))
+        assert up.shape == (-(-n // 512) + extra,)
+        assert np.array_equal(up.view(np.uint32), raw_probs(vm, ring=ring, start=start, n=n, extra=extra).view(np.uint32)), extra
+        assert np.array_equal(up.view(np.uint32), raw_probs(vm, slot=slot, start=start, n=n, extra=extra).view(np.uint32)), extra
     if start == 0:
         opt = vad.VadOptions(threshold=0.5)
         assert vad.get_speech_timestamps_pcm(slot, n, opt, model=vm, item=1) == vad.get_speech_timestamps(x, opt, model=vm)
@@ -71,7 +102,7 @@ def test_gate_right_behind_put_frames_sees_the_resampled_audio(eng, vm):
 
 
 def test_span_outside_the_resident_samples_is_a_state_error(vm, resident):
-    slot, pcm = resident
+    slot, pcm, _ = resident
     for start, n, item in ((47000, 1001, 1), (0, 48001, 1), (0, 16, 0)):         # item 0 holds nothing
         with pytest.raises(WlxError, match="not resident") as ei:
             vm.probs_pcm(slot, start, n, item=item)

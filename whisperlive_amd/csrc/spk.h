@@ -16,51 +16,39 @@ namespace wlx {
 // frames of a snip_edges filterbank over n samples (0 below one frame)
 inline int spk_frames(long n) { return n < WLX_SPK_FRAME ? 0 : 1 + (int)((n - WLX_SPK_FRAME) / WLX_SPK_SHIFT); }
 
-// Kaldi fbank: frame t = pcm[160 t .. 160 t + 400) * 2^15, DC removed, pre-emphasis 0.97, Hamming window, 512-point power spectrum
-// (direct DFT against `twiddle` = cos(2 pi j / 512), j = 0..511, fp32), n_mels triangular bins `mel` [n_mels][256], natural log with
-// a float32-epsilon floor -> logmel fp32 [T][n_mels]. `window` [400].
-void launch_spk_fbank(const float* pcm, int T, const float* window, const float* twiddle, const float* mel, int n_mels,
-                      float* logmel, hipStream_t s);
-// per-bin mean over the T frames subtracted in place (fp32 [T][n_mels]); the fp16 copy goes to out16 [n_mels][T], the [H][W][1]
-// image the first convolution reads
-void launch_spk_cmn(float* logmel, int T, int n_mels, half_t* out16, hipStream_t s);
+// ---- every launcher takes a ragged batch: n in 1..WLX_SPK_MAX_BATCH items of different lengths in one launch, packed back to back
+// without padding (a single embed is n = 1). At a stage of geometry (H, C) item i is its own [H][W_i][C] image at pixel offset
+// H * sum_{j<i} W_j; a stride-s convolution gives OW_i = (W_i - 1) / s + 1 per item. An item's output does not depend on its
+// neighbours, its position or n; no tap reads a neighbouring item. `widths` / `frames` / `offsets` are HOST arrays, read before the
+// call returns. False = nothing launched.
 
-// Convolution, ks = 3 (padding 1) or 1 (padding 0), stride 1 or 2: in [H][W][Cin] -> out [OH][OW][Cout] with
+// Kaldi fbank: frame t of item i = pcm[offsets[i] + 160 t .. + 400) * 2^15, DC removed, pre-emphasis 0.97, Hamming window, 512-point
+// power spectrum (direct DFT against `twiddle` = cos(2 pi j / 512), j = 0..511, fp32), n_mels triangular bins `mel` [n_mels][256],
+// natural log with a float32-epsilon floor -> logmel fp32 [sum frames][n_mels], rows in item order. `window` [400].
+bool launch_spk_fbank_batch(const float* pcm, const long* offsets, const int* frames, int n, const float* window, const float* twiddle,
+                            const float* mel, int n_mels, float* logmel, hipStream_t s);
+// per item and bin, the mean over the item's own frames subtracted in place; the fp16 copy goes to out16, item i = [n_mels][frames[i]]
+// at n_mels * sum_{j<i} frames[j]: the [H][W][1] image the first convolution reads
+bool launch_spk_cmn_batch(float* logmel, const int* frames, int n, int n_mels, half_t* out16, hipStream_t s);
+
+// Convolution, ks = 3 (padding 1) or 1 (padding 0), stride 1 or 2: per item in [H][W][Cin] -> out [OH][OW][Cout] with
 // OH = (H - 1) / stride + 1, OW likewise. Wp: the weight w[Cout][Cin][ks][ks] packed by spk_pack_conv into MFMA fragment order
 // (common.h) over k = (kh * ks + kw) * Cin + ci. out = act(conv + bias [+ resid]), resid [OH][OW][Cout]. Cin and Cout multiples
 // of 32. bias [Cout] is required (zeros for a convolution without one), resid may be null. Returns false (nothing launched) for
-// a shape it cannot serve or a null in / Wp / bias / out.
-bool launch_spk_conv(const half_t* in, int H, int W, int Cin, const half_t* Wp, const float* bias, const half_t* resid, int Cout,
-                     int stride, int ks, bool relu, half_t* out, hipStream_t s);
+// a shape it cannot serve (an item of more than 2^30 output pixels among them) or a null in / Wp / bias / out.
+bool launch_spk_conv_batch(const half_t* in, int H, const int* widths, int n, int Cin, const half_t* Wp, const float* bias,
+                           const half_t* resid, int Cout, int stride, int ks, bool relu, half_t* out, hipStream_t s);
 // the same for Cin = 1, ks = 3 on the vector ALU: w fp32 [Cout][9], Cout a multiple of 4
-bool launch_spk_conv_c1(const half_t* in, int H, int W, const float* w, const float* bias, const half_t* resid, int Cout, int stride,
-                        bool relu, half_t* out, hipStream_t s);
+bool launch_spk_conv_c1_batch(const half_t* in, int H, const int* widths, int n, const float* w, const float* bias, const half_t* resid,
+                              int Cout, int stride, bool relu, half_t* out, hipStream_t s);
 // host side: w fp32 [Cout][Cin][ks][ks] -> fragment order, ks * ks * Cin / 32 k-tiles per 16 output channels
 void spk_pack_conv(const float* w, int Cout, int Cin, int ks, half_t* Wp);
 inline size_t spk_packed_halfs(int Cout, int Cin, int ks) { return (size_t)(Cout / 16) * (size_t)(ks * ks * Cin / 32) * 512; }
 
-// Statistics pooling of x [F][T][C] over T (T >= 2): out[c * F + f] = mean, out[C * F + c * F + f] = sqrt(var_unbiased + eps).
-// C a multiple of 64.
-bool launch_spk_pool(const half_t* x, int F, int T, int C, float eps, float* out, hipStream_t s);
-// emb = W pooled + b (W fp16 [E][D] row-major, D a multiple of 8), then emb /= |emb|. E <= 1024.
-void launch_spk_head(const float* pooled, const half_t* W, const float* b, int E, int D, float* emb, hipStream_t s);
-
-// ---- ragged batch: n <= WLX_SPK_MAX_BATCH items of different lengths in one launch, packed back to back without padding. At a
-// stage of geometry (H, C) item i is its own [H][W_i][C] image at pixel offset H * sum_{j<i} W_j; a stride-s convolution gives
-// OW_i = (W_i - 1) / s + 1 per item. Every item's output has the bits of the single-item launcher above on that item alone; no tap
-// reads a neighbouring item. `widths` / `frames` / `offsets` are HOST arrays, read before the call returns. False = nothing launched.
-// frame t of item i = pcm[offsets[i] + 160 t ...), logmel rows in item order ([sum frames][n_mels])
-bool launch_spk_fbank_batch(const float* pcm, const long* offsets, const int* frames, int n, const float* window, const float* twiddle,
-                            const float* mel, int n_mels, float* logmel, hipStream_t s);
-// per item: the mean over its own frames; out16 item i = [n_mels][frames[i]] at n_mels * sum_{j<i} frames[j]
-bool launch_spk_cmn_batch(float* logmel, const int* frames, int n, int n_mels, half_t* out16, hipStream_t s);
-bool launch_spk_conv_batch(const half_t* in, int H, const int* widths, int n, int Cin, const half_t* Wp, const float* bias,
-                           const half_t* resid, int Cout, int stride, int ks, bool relu, half_t* out, hipStream_t s);
-bool launch_spk_conv_c1_batch(const half_t* in, int H, const int* widths, int n, const float* w, const float* bias, const half_t* resid,
-                              int Cout, int stride, bool relu, half_t* out, hipStream_t s);
-// x item i = [F][frames[i]][C] (frames[i] >= 2); out [n][2][C][F]
+// Statistics pooling of x, item i = [F][frames[i]][C], over its frames (frames[i] >= 2): out [n][2][C][F],
+// out[i][c * F + f] = mean, out[i][C * F + c * F + f] = sqrt(var_unbiased + eps). C a multiple of 64.
 bool launch_spk_pool_batch(const half_t* x, int F, const int* frames, int n, int C, float eps, float* out, hipStream_t s);
-// pooled [n][D] -> emb [n][E]
+// pooled [n][D] -> emb [n][E]: emb = W pooled + b (W fp16 [E][D] row-major, D a multiple of 8), then emb /= |emb|. E <= 1024.
 void launch_spk_head_batch(const float* pooled, const half_t* W, const float* b, int E, int D, int n, float* emb, hipStream_t s);
 
 }  // namespace wlx

@@ -1,15 +1,66 @@
 // spk.hip — kernels of the speaker-embedding engine (spk.h): Kaldi filterbank, the ResNet convolutions, statistics pooling and
 // the embedding head of WeSpeaker ResNet34. Every reduction runs in a fixed order: two embeds of the same audio are bit-identical.
+// ONE launcher family: every launch takes a ragged batch of 1..WLX_SPK_MAX_BATCH items, and a single embed is a batch of one. For
+// n == 1 the filterbank, mean-removal and convolution launchers pick a kernel without the by-value table around the same body: the
+// table's cost per launch was measured outside the run-to-run spread there (profiles/single_as_batch_of_one.txt).
 #include "spk.h"
 
 namespace wlx {
+
+// ------------------------------------------------------------------------------------------------ ragged batch
+// N items of different lengths in one pass, packed without padding: at a stage of geometry (H, C) item i is its own [H][W_i][C]
+// image at pixel offset H * sum_{j<i} W_j. Every kernel below finds its item, moves the base pointers there and runs the
+// per-item body (*_body / *_tile / *_quad) with the item's own W / OW / T, so a tap outside the item's image is padding (zero),
+// never a neighbour's pixel, and every reduction keeps its per-item order: an item's bits do not depend on its neighbours, its
+// position or the table's fill. The table of widths, column offsets and first workgroups travels BY VALUE in the kernel arguments
+// (1 KiB, copied by the launch call itself): no staging buffer and no copy that could outlive the launcher's frame.
+struct SpkItem {
+    int W;           // columns of the item at the launch's input (frames, for the front end and the pooling)
+    int in0, out0;   // sum of the earlier items' columns at the input and at the output
+    int blk0;        // first workgroup (blockIdx.x) of the item, where the grid's x runs over all items
+};
+struct SpkBatch {
+    int n;
+    SpkItem it[WLX_SPK_MAX_BATCH];
+};
+struct SpkOffsets {
+    long off[WLX_SPK_MAX_BATCH];
+};
+
+// the item that owns workgroup `blk`: the last one with blk0 <= blk (blk0 is strictly increasing: every item has work)
+__device__ __forceinline__ int spk_item_of(const SpkBatch& tab, int blk) {
+    int lo = 0, hi = tab.n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab.it[mid].blk0 <= blk) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// Host side: items of `widths` columns, `units_per_col` work units per OUTPUT column, `per_blk` units per workgroup. False when a
+// width is < 1, an item alone exceeds `unit_cap` units or the grid exceeds 2^31 - 1 workgroups.
+static bool spk_table(const int* widths, int n, int stride, long units_per_col, int per_blk, long unit_cap, SpkBatch& tab, long& blocks) {
+    if (!widths || n < 1 || n > WLX_SPK_MAX_BATCH) return false;
+    long in0 = 0, out0 = 0;
+    blocks = 0;
+    tab.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (widths[i] < 1) return false;
+        const long ow = (widths[i] - 1) / stride + 1, units = ow * units_per_col;
+        if (units > unit_cap || in0 > 0x7fffffffL || out0 > 0x7fffffffL || blocks > 0x7fffffffL) return false;
+        tab.it[i] = SpkItem{widths[i], (int)in0, (int)out0, (int)blocks};
+        in0 += widths[i], out0 += ow, blocks += (units + per_blk - 1) / per_blk;
+    }
+    for (int i = n; i < WLX_SPK_MAX_BATCH; ++i) tab.it[i] = SpkItem{0, 0, 0, 0};
+    return blocks <= 0x7fffffffL;
+}
 
 // ------------------------------------------------------------------------------------------------ filterbank
 // One workgroup per frame. The DFT is direct (400 x 256 multiply-adds per frame, fp32, four partial sums per bin): at 100 frames
 // per second it is noise beside the network, and its twiddles are table entries rounded from float64, exact in their index
 // (k n mod 512), so the only fp32 error is the accumulation.
-// `src`: the frame's 400 samples, `dst`: its n_mels outputs. The single and the ragged-batch kernel both run this body, so a frame's
-// bits do not depend on which of them computed it; the same holds for every *_body / *_tile / *_quad function below.
+// `src`: the frame's 400 samples, `dst`: its n_mels outputs.
 __device__ __forceinline__ void spk_fbank_body(const float* __restrict__ src, const float* __restrict__ window,
                                                const float* __restrict__ twiddle, const float* __restrict__ mel, int n_mels,
                                                float* __restrict__ dst) {
@@ -62,6 +113,8 @@ __device__ __forceinline__ void spk_fbank_body(const float* __restrict__ src, co
     }
 }
 
+// one item without the tables, selected by the launcher on n == 1 (as spk_conv_kernel below: the 1.5 KiB of arguments measured 0.8 us
+// on the 24 us front end of a 1 s embed, outside the run-to-run spread)
 __global__ __launch_bounds__(256) void spk_fbank_kernel(const float* __restrict__ pcm, const float* __restrict__ window,
                                                          const float* __restrict__ twiddle, const float* __restrict__ mel, int n_mels,
                                                          float* __restrict__ logmel) {
@@ -69,9 +122,29 @@ __global__ __launch_bounds__(256) void spk_fbank_kernel(const float* __restrict_
     spk_fbank_body(pcm + t * WLX_SPK_SHIFT, window, twiddle, mel, n_mels, logmel + t * n_mels);
 }
 
-void launch_spk_fbank(const float* pcm, int T, const float* window, const float* twiddle, const float* mel, int n_mels,
-                      float* logmel, hipStream_t s) {
-    hipLaunchKernelGGL(spk_fbank_kernel, dim3((unsigned)T), dim3(256), 0, s, pcm, window, twiddle, mel, n_mels, logmel);
+__global__ __launch_bounds__(256) void spk_fbank_batch_kernel(const float* __restrict__ pcm, SpkOffsets offs, SpkBatch tab,
+                                                               const float* __restrict__ window, const float* __restrict__ twiddle,
+                                                               const float* __restrict__ mel, int n_mels, float* __restrict__ logmel) {
+    const int i = spk_item_of(tab, (int)blockIdx.x);
+    const long t = (int)blockIdx.x - tab.it[i].blk0;
+    spk_fbank_body(pcm + offs.off[i] + t * WLX_SPK_SHIFT, window, twiddle, mel, n_mels, logmel + (long)blockIdx.x * n_mels);
+}
+
+bool launch_spk_fbank_batch(const float* pcm, const long* offsets, const int* frames, int n, const float* window, const float* twiddle,
+                            const float* mel, int n_mels, float* logmel, hipStream_t s) {
+    SpkBatch tab;
+    long blocks;
+    if (!pcm || !offsets || !logmel || !spk_table(frames, n, 1, 1, 1, 1L << 30, tab, blocks)) return false;
+    for (int i = 0; i < n; ++i)
+        if (offsets[i] < 0) return false;
+    if (n == 1) {
+        hipLaunchKernelGGL(spk_fbank_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pcm + offsets[0], window, twiddle, mel, n_mels, logmel);
+        return true;
+    }
+    SpkOffsets offs;
+    for (int i = 0; i < WLX_SPK_MAX_BATCH; ++i) offs.off[i] = i < n ? offsets[i] : 0;
+    hipLaunchKernelGGL(spk_fbank_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pcm, offs, tab, window, twiddle, mel, n_mels, logmel);
+    return true;
 }
 
 __device__ __forceinline__ void spk_cmn_body(float* __restrict__ logmel, int T, int n_mels, half_t* __restrict__ out16, int b) {
@@ -91,11 +164,25 @@ __device__ __forceinline__ void spk_cmn_body(float* __restrict__ logmel, int T, 
 }
 
 __global__ __launch_bounds__(256) void spk_cmn_kernel(float* __restrict__ logmel, int T, int n_mels, half_t* __restrict__ out16) {
-    spk_cmn_body(logmel, T, n_mels, out16, (int)blockIdx.x);
+    spk_cmn_body(logmel, T, n_mels, out16, (int)blockIdx.x);          // one item without the table (n == 1, as spk_fbank_kernel)
 }
 
-void launch_spk_cmn(float* logmel, int T, int n_mels, half_t* out16, hipStream_t s) {
-    hipLaunchKernelGGL(spk_cmn_kernel, dim3((unsigned)n_mels), dim3(256), 0, s, logmel, T, n_mels, out16);
+__global__ __launch_bounds__(256) void spk_cmn_batch_kernel(float* __restrict__ logmel, SpkBatch tab, int n_mels,
+                                                             half_t* __restrict__ out16) {
+    const SpkItem it = tab.it[blockIdx.y];
+    spk_cmn_body(logmel + (long)it.in0 * n_mels, it.W, n_mels, out16 + (long)it.in0 * n_mels, (int)blockIdx.x);
+}
+
+bool launch_spk_cmn_batch(float* logmel, const int* frames, int n, int n_mels, half_t* out16, hipStream_t s) {
+    SpkBatch tab;
+    long blocks;
+    if (!logmel || !out16 || !spk_table(frames, n, 1, 1, 1, 1L << 30, tab, blocks)) return false;
+    if (n == 1) {
+        hipLaunchKernelGGL(spk_cmn_kernel, dim3((unsigned)n_mels), dim3(256), 0, s, logmel, frames[0], n_mels, out16);
+        return true;
+    }
+    hipLaunchKernelGGL(spk_cmn_batch_kernel, dim3((unsigned)n_mels, (unsigned)n), dim3(256), 0, s, logmel, tab, n_mels, out16);
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------ convolution
@@ -158,6 +245,9 @@ __device__ __forceinline__ void spk_conv_tile(const half_t* __restrict__ in, con
     }
 }
 
+// One item without the table: a 1 KiB by-value table on each of the 35 convolution launches of an
+// embed measured 11 - 13 us of device time per embed (1.5 %, ten times the run-to-run spread) over this form; launch_spk_conv_batch
+// selects it on n == 1. Same tile function, same bits.
 template <int NT>
 __global__ __launch_bounds__(256) void spk_conv_kernel(const half_t* __restrict__ in, const half_t* __restrict__ Wp,
                                                         const float* __restrict__ bias, const half_t* __restrict__ resid,
@@ -166,22 +256,43 @@ __global__ __launch_bounds__(256) void spk_conv_kernel(const half_t* __restrict_
     spk_conv_tile<NT>(in, Wp, bias, resid, out, H, W, Cin, OH, OW, Cout, stride, ks, relu, (long)blockIdx.x, (int)blockIdx.y * NT);
 }
 
-bool launch_spk_conv(const half_t* in, int H, int W, int Cin, const half_t* Wp, const float* bias, const half_t* resid, int Cout,
-                     int stride, int ks, bool relu, half_t* out, hipStream_t s) {
-    // bias is required (a convolution without one passes zeros); resid may be null
+template <int NT>
+__global__ __launch_bounds__(256) void spk_conv_batch_kernel(const half_t* __restrict__ in, const half_t* __restrict__ Wp,
+                                                              const float* __restrict__ bias, const half_t* __restrict__ resid,
+                                                              half_t* __restrict__ out, SpkBatch tab, int H, int Cin, int OH, int Cout,
+                                                              int stride, int ks, int relu) {
+    const SpkItem it = tab.it[spk_item_of(tab, (int)blockIdx.x)];          // workgroup-uniform: the item of all four waves
+    const int OW = (it.W - 1) / stride + 1;
+    const long o0 = (long)OH * it.out0 * Cout;
+    spk_conv_tile<NT>(in + (long)H * it.in0 * Cin, Wp, bias, resid ? resid + o0 : nullptr, out + o0, H, it.W, Cin, OH, OW, Cout, stride,
+                      ks, relu, (long)((int)blockIdx.x - it.blk0), (int)blockIdx.y * NT);
+}
+
+bool launch_spk_conv_batch(const half_t* in, int H, const int* widths, int n, int Cin, const half_t* Wp, const float* bias,
+                           const half_t* resid, int Cout, int stride, int ks, bool relu, half_t* out, hipStream_t s) {
     if (!in || !Wp || !bias || !out) return false;
-    if (H < 1 || W < 1 || Cin < 32 || Cin % 32 || Cout < 32 || Cout % 32 || (stride != 1 && stride != 2) || (ks != 1 && ks != 3))
-        return false;
-    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-    const long P = (long)OH * OW;
-    if (P > (1L << 30)) return false;
-    const unsigned gx = (unsigned)((P + 63) / 64);
+    if (H < 1 || Cin < 32 || Cin % 32 || Cout < 32 || Cout % 32 || (stride != 1 && stride != 2) || (ks != 1 && ks != 3)) return false;
+    const int OH = (H - 1) / stride + 1;
+    SpkBatch tab;
+    long blocks;
+    if (!spk_table(widths, n, stride, OH, 64, 1L << 30, tab, blocks)) return false;
+    const int r = relu ? 1 : 0;
+    if (n == 1) {
+        const int W = widths[0], OW = (W - 1) / stride + 1;
+        if (Cout % 64 == 0)
+            hipLaunchKernelGGL(spk_conv_kernel<4>, dim3((unsigned)blocks, (unsigned)(Cout / 64)), dim3(256), 0, s, in, Wp, bias, resid, out, H,
+                               W, Cin, OH, OW, Cout, stride, ks, r);
+        else
+            hipLaunchKernelGGL(spk_conv_kernel<2>, dim3((unsigned)blocks, (unsigned)(Cout / 32)), dim3(256), 0, s, in, Wp, bias, resid, out, H,
+                               W, Cin, OH, OW, Cout, stride, ks, r);
+        return true;
+    }
     if (Cout % 64 == 0)
-        hipLaunchKernelGGL(spk_conv_kernel<4>, dim3(gx, (unsigned)(Cout / 64)), dim3(256), 0, s, in, Wp, bias, resid, out, H, W, Cin, OH,
-                           OW, Cout, stride, ks, relu ? 1 : 0);
+        hipLaunchKernelGGL(spk_conv_batch_kernel<4>, dim3((unsigned)blocks, (unsigned)(Cout / 64)), dim3(256), 0, s, in, Wp, bias, resid, out,
+                           tab, H, Cin, OH, Cout, stride, ks, r);
     else
-        hipLaunchKernelGGL(spk_conv_kernel<2>, dim3(gx, (unsigned)(Cout / 32)), dim3(256), 0, s, in, Wp, bias, resid, out, H, W, Cin, OH,
-                           OW, Cout, stride, ks, relu ? 1 : 0);
+        hipLaunchKernelGGL(spk_conv_batch_kernel<2>, dim3((unsigned)blocks, (unsigned)(Cout / 32)), dim3(256), 0, s, in, Wp, bias, resid, out,
+                           tab, H, Cin, OH, Cout, stride, ks, r);
     return true;
 }
 
@@ -231,22 +342,27 @@ __device__ __forceinline__ void spk_conv_c1_quad(const half_t* __restrict__ in, 
     *reinterpret_cast<f16x4*>(out + m * Cout + n) = o;
 }
 
-__global__ __launch_bounds__(256) void spk_conv_c1_kernel(const half_t* __restrict__ in, const float* __restrict__ w,
-                                                           const float* __restrict__ bias, const half_t* __restrict__ resid,
-                                                           half_t* __restrict__ out, int H, int W, int OH, int OW, int Cout, int stride,
-                                                           int relu) {
-    spk_conv_c1_quad(in, w, bias, resid, out, H, W, OH, OW, Cout, stride, relu, (long)blockIdx.x * 256 + threadIdx.x);
+__global__ __launch_bounds__(256) void spk_conv_c1_batch_kernel(const half_t* __restrict__ in, const float* __restrict__ w,
+                                                                 const float* __restrict__ bias, const half_t* __restrict__ resid,
+                                                                 half_t* __restrict__ out, SpkBatch tab, int H, int OH, int Cout,
+                                                                 int stride, int relu) {
+    const SpkItem it = tab.it[spk_item_of(tab, (int)blockIdx.x)];
+    const int OW = (it.W - 1) / stride + 1;
+    const long o0 = (long)OH * it.out0 * Cout;
+    spk_conv_c1_quad(in + (long)H * it.in0, w, bias, resid ? resid + o0 : nullptr, out + o0, H, it.W, OH, OW, Cout, stride, relu,
+                     (long)((int)blockIdx.x - it.blk0) * 256 + threadIdx.x);
 }
 
-bool launch_spk_conv_c1(const half_t* in, int H, int W, const float* w, const float* bias, const half_t* resid, int Cout, int stride,
-                        bool relu, half_t* out, hipStream_t s) {
-    if (!in || !w || !bias || !out) return false;          // as launch_spk_conv: bias required, resid optional
-    if (H < 1 || W < 1 || Cout < 4 || Cout % 4 || (stride != 1 && stride != 2)) return false;
-    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-    const long n = (long)OH * OW * (Cout / 4);
-    if (n > (1L << 38)) return false;
-    hipLaunchKernelGGL(spk_conv_c1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, w, bias, resid, out, H, W, OH, OW, Cout,
-                       stride, relu ? 1 : 0);
+bool launch_spk_conv_c1_batch(const half_t* in, int H, const int* widths, int n, const float* w, const float* bias, const half_t* resid,
+                              int Cout, int stride, bool relu, half_t* out, hipStream_t s) {
+    if (!in || !w || !bias || !out) return false;
+    if (H < 1 || Cout < 4 || Cout % 4 || (stride != 1 && stride != 2)) return false;
+    const int OH = (H - 1) / stride + 1;
+    SpkBatch tab;
+    long blocks;
+    if (!spk_table(widths, n, stride, (long)OH * (Cout / 4), 256, 1L << 38, tab, blocks)) return false;
+    hipLaunchKernelGGL(spk_conv_c1_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, w, bias, resid, out, tab, H, OH, Cout, stride,
+                       relu ? 1 : 0);
     return true;
 }
 
@@ -279,14 +395,20 @@ __device__ __forceinline__ void spk_pool_body(const half_t* __restrict__ x, int 
     }
 }
 
-__global__ __launch_bounds__(256) void spk_pool_kernel(const half_t* __restrict__ x, int F, int T, int C, float eps,
-                                                        float* __restrict__ out) {
-    spk_pool_body(x, F, T, C, eps, out, (int)blockIdx.x, (int)blockIdx.y * 64);
+__global__ __launch_bounds__(256) void spk_pool_batch_kernel(const half_t* __restrict__ x, SpkBatch tab, int F, int C, float eps,
+                                                              float* __restrict__ out) {
+    const SpkItem it = tab.it[blockIdx.z];
+    spk_pool_body(x + (long)F * it.in0 * C, F, it.W, C, eps, out + (long)blockIdx.z * 2 * C * F, (int)blockIdx.x, (int)blockIdx.y * 64);
 }
 
-bool launch_spk_pool(const half_t* x, int F, int T, int C, float eps, float* out, hipStream_t s) {
-    if (F < 1 || T < 2 || C < 64 || C % 64) return false;
-    hipLaunchKernelGGL(spk_pool_kernel, dim3((unsigned)F, (unsigned)(C / 64)), dim3(256), 0, s, x, F, T, C, eps, out);
+bool launch_spk_pool_batch(const half_t* x, int F, const int* frames, int n, int C, float eps, float* out, hipStream_t s) {
+    if (!x || !out || F < 1 || C < 64 || C % 64) return false;
+    SpkBatch tab;
+    long blocks;
+    if (!spk_table(frames, n, 1, 1, 1, 1L << 30, tab, blocks)) return false;
+    for (int i = 0; i < n; ++i)
+        if (frames[i] < 2) return false;
+    hipLaunchKernelGGL(spk_pool_batch_kernel, dim3((unsigned)F, (unsigned)(C / 64), (unsigned)n), dim3(256), 0, s, x, tab, F, C, eps, out);
     return true;
 }
 
@@ -304,11 +426,6 @@ __device__ __forceinline__ void spk_linear_body(const float* __restrict__ x, con
     if (lane == 0) y[e] = acc + b[e];
 }
 
-__global__ __launch_bounds__(64) void spk_linear_kernel(const float* __restrict__ x, const half_t* __restrict__ W,
-                                                         const float* __restrict__ b, int D, float* __restrict__ y) {
-    spk_linear_body(x, W, b, D, y, (int)blockIdx.x);
-}
-
 __device__ __forceinline__ void spk_l2norm_body(float* __restrict__ y, int E) {
     __shared__ float part[4];
     const int tid = threadIdx.x;
@@ -320,167 +437,6 @@ __device__ __forceinline__ void spk_l2norm_body(float* __restrict__ y, int E) {
     // an all-zero head output stays zero instead of turning into NaN
     const float inv = 1.f / sqrtf(fmaxf(((part[0] + part[1]) + part[2]) + part[3], 1e-30f));
     for (int i = tid; i < E; i += 256) y[i] *= inv;
-}
-
-__global__ __launch_bounds__(256) void spk_l2norm_kernel(float* __restrict__ y, int E) { spk_l2norm_body(y, E); }
-
-void launch_spk_head(const float* pooled, const half_t* W, const float* b, int E, int D, float* emb, hipStream_t s) {
-    hipLaunchKernelGGL(spk_linear_kernel, dim3((unsigned)E), dim3(64), 0, s, pooled, W, b, D, emb);
-    hipLaunchKernelGGL(spk_l2norm_kernel, dim3(1), dim3(256), 0, s, emb, E);
-}
-
-// ------------------------------------------------------------------------------------------------ ragged batch
-// N items of different lengths in one pass, packed without padding: at a stage of geometry (H, C) item i is its own [H][W_i][C]
-// image at pixel offset H * sum_{j<i} W_j. Every kernel below finds its item, moves the base pointers there and runs the
-// single-item body with the item's own W / OW / T, so a tap outside the item's image is padding (zero), never a neighbour's
-// pixel, and every reduction keeps its per-item order: an item's bits are those of the single-item launch. The table of widths,
-// column offsets and first workgroups travels BY VALUE in the kernel arguments (1 KiB, copied by the launch call itself): no
-// staging buffer and no copy that could outlive the launcher's frame.
-struct SpkItem {
-    int W;           // columns of the item at the launch's input (frames, for the front end and the pooling)
-    int in0, out0;   // sum of the earlier items' columns at the input and at the output
-    int blk0;        // first workgroup (blockIdx.x) of the item, where the grid's x runs over all items
-};
-struct SpkBatch {
-    int n;
-    SpkItem it[WLX_SPK_MAX_BATCH];
-};
-struct SpkOffsets {
-    long off[WLX_SPK_MAX_BATCH];
-};
-
-// the item that owns workgroup `blk`: the last one with blk0 <= blk (blk0 is strictly increasing: every item has work)
-__device__ __forceinline__ int spk_item_of(const SpkBatch& tab, int blk) {
-    int lo = 0, hi = tab.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab.it[mid].blk0 <= blk) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// Host side: items of `widths` columns, `units_per_col` work units per OUTPUT column, `per_blk` units per workgroup. False when a
-// width is < 1, an item alone exceeds `unit_cap` units or the grid exceeds 2^31 - 1 workgroups.
-static bool spk_table(const int* widths, int n, int stride, long units_per_col, int per_blk, long unit_cap, SpkBatch& tab, long& blocks) {
-    if (!widths || n < 1 || n > WLX_SPK_MAX_BATCH) return false;
-    long in0 = 0, out0 = 0;
-    blocks = 0;
-    tab.n = n;
-    for (int i = 0; i < n; ++i) {
-        if (widths[i] < 1) return false;
-        const long ow = (widths[i] - 1) / stride + 1, units = ow * units_per_col;
-        if (units > unit_cap || in0 > 0x7fffffffL || out0 > 0x7fffffffL || blocks > 0x7fffffffL) return false;
-        tab.it[i] = SpkItem{widths[i], (int)in0, (int)out0, (int)blocks};
-        in0 += widths[i], out0 += ow, blocks += (units + per_blk - 1) / per_blk;
-    }
-    for (int i = n; i < WLX_SPK_MAX_BATCH; ++i) tab.it[i] = SpkItem{0, 0, 0, 0};
-    return blocks <= 0x7fffffffL;
-}
-
-__global__ __launch_bounds__(256) void spk_fbank_batch_kernel(const float* __restrict__ pcm, SpkOffsets offs, SpkBatch tab,
-                                                               const float* __restrict__ window, const float* __restrict__ twiddle,
-                                                               const float* __restrict__ mel, int n_mels, float* __restrict__ logmel) {
-    const int i = spk_item_of(tab, (int)blockIdx.x);
-    const long t = (int)blockIdx.x - tab.it[i].blk0;
-    spk_fbank_body(pcm + offs.off[i] + t * WLX_SPK_SHIFT, window, twiddle, mel, n_mels, logmel + (long)blockIdx.x * n_mels);
-}
-
-bool launch_spk_fbank_batch(const float* pcm, const long* offsets, const int* frames, int n, const float* window, const float* twiddle,
-                            const float* mel, int n_mels, float* logmel, hipStream_t s) {
-    SpkBatch tab;
-    SpkOffsets offs;
-    long blocks;
-    if (!pcm || !offsets || !logmel || !spk_table(frames, n, 1, 1, 1, 1L << 30, tab, blocks)) return false;
-    for (int i = 0; i < WLX_SPK_MAX_BATCH; ++i) offs.off[i] = i < n ? offsets[i] : 0;
-    for (int i = 0; i < n; ++i)
-        if (offsets[i] < 0) return false;
-    hipLaunchKernelGGL(spk_fbank_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pcm, offs, tab, window, twiddle, mel, n_mels, logmel);
-    return true;
-}
-
-__global__ __launch_bounds__(256) void spk_cmn_batch_kernel(float* __restrict__ logmel, SpkBatch tab, int n_mels,
-                                                             half_t* __restrict__ out16) {
-    const SpkItem it = tab.it[blockIdx.y];
-    spk_cmn_body(logmel + (long)it.in0 * n_mels, it.W, n_mels, out16 + (long)it.in0 * n_mels, (int)blockIdx.x);
-}
-
-bool launch_spk_cmn_batch(float* logmel, const int* frames, int n, int n_mels, half_t* out16, hipStream_t s) {
-    SpkBatch tab;
-    long blocks;
-    if (!logmel || !out16 || !spk_table(frames, n, 1, 1, 1, 1L << 30, tab, blocks)) return false;
-    hipLaunchKernelGGL(spk_cmn_batch_kernel, dim3((unsigned)n_mels, (unsigned)n), dim3(256), 0, s, logmel, tab, n_mels, out16);
-    return true;
-}
-
-template <int NT>
-__global__ __launch_bounds__(256) void spk_conv_batch_kernel(const half_t* __restrict__ in, const half_t* __restrict__ Wp,
-                                                              const float* __restrict__ bias, const half_t* __restrict__ resid,
-                                                              half_t* __restrict__ out, SpkBatch tab, int H, int Cin, int OH, int Cout,
-                                                              int stride, int ks, int relu) {
-    const SpkItem it = tab.it[spk_item_of(tab, (int)blockIdx.x)];          // workgroup-uniform: the item of all four waves
-    const int OW = (it.W - 1) / stride + 1;
-    const long o0 = (long)OH * it.out0 * Cout;
-    spk_conv_tile<NT>(in + (long)H * it.in0 * Cin, Wp, bias, resid ? resid + o0 : nullptr, out + o0, H, it.W, Cin, OH, OW, Cout, stride,
-                      ks, relu, (long)((int)blockIdx.x - it.blk0), (int)blockIdx.y * NT);
-}
-
-bool launch_spk_conv_batch(const half_t* in, int H, const int* widths, int n, int Cin, const half_t* Wp, const float* bias,
-                           const half_t* resid, int Cout, int stride, int ks, bool relu, half_t* out, hipStream_t s) {
-    if (!in || !Wp || !bias || !out) return false;
-    if (H < 1 || Cin < 32 || Cin % 32 || Cout < 32 || Cout % 32 || (stride != 1 && stride != 2) || (ks != 1 && ks != 3)) return false;
-    const int OH = (H - 1) / stride + 1;
-    SpkBatch tab;
-    long blocks;
-    if (!spk_table(widths, n, stride, OH, 64, 1L << 30, tab, blocks)) return false;
-    if (Cout % 64 == 0)
-        hipLaunchKernelGGL(spk_conv_batch_kernel<4>, dim3((unsigned)blocks, (unsigned)(Cout / 64)), dim3(256), 0, s, in, Wp, bias, resid, out,
-                           tab, H, Cin, OH, Cout, stride, ks, relu ? 1 : 0);
-    else
-        hipLaunchKernelGGL(spk_conv_batch_kernel<2>, dim3((unsigned)blocks, (unsigned)(Cout / 32)), dim3(256), 0, s, in, Wp, bias, resid, out,
-                           tab, H, Cin, OH, Cout, stride, ks, relu ? 1 : 0);
-    return true;
-}
-
-__global__ __launch_bounds__(256) void spk_conv_c1_batch_kernel(const half_t* __restrict__ in, const float* __restrict__ w,
-                                                                 const float* __restrict__ bias, const half_t* __restrict__ resid,
-                                                                 half_t* __restrict__ out, SpkBatch tab, int H, int OH, int Cout,
-                                                                 int stride, int relu) {
-    const SpkItem it = tab.it[spk_item_of(tab, (int)blockIdx.x)];
-    const int OW = (it.W - 1) / stride + 1;
-    const long o0 = (long)OH * it.out0 * Cout;
-    spk_conv_c1_quad(in + (long)H * it.in0, w, bias, resid ? resid + o0 : nullptr, out + o0, H, it.W, OH, OW, Cout, stride, relu,
-                     (long)((int)blockIdx.x - it.blk0) * 256 + threadIdx.x);
-}
-
-bool launch_spk_conv_c1_batch(const half_t* in, int H, const int* widths, int n, const float* w, const float* bias, const half_t* resid,
-                              int Cout, int stride, bool relu, half_t* out, hipStream_t s) {
-    if (!in || !w || !bias || !out) return false;
-    if (H < 1 || Cout < 4 || Cout % 4 || (stride != 1 && stride != 2)) return false;
-    const int OH = (H - 1) / stride + 1;
-    SpkBatch tab;
-    long blocks;
-    if (!spk_table(widths, n, stride, (long)OH * (Cout / 4), 256, 1L << 38, tab, blocks)) return false;
-    hipLaunchKernelGGL(spk_conv_c1_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, w, bias, resid, out, tab, H, OH, Cout, stride,
-                       relu ? 1 : 0);
-    return true;
-}
-
-__global__ __launch_bounds__(256) void spk_pool_batch_kernel(const half_t* __restrict__ x, SpkBatch tab, int F, int C, float eps,
-                                                              float* __restrict__ out) {
-    const SpkItem it = tab.it[blockIdx.z];
-    spk_pool_body(x + (long)F * it.in0 * C, F, it.W, C, eps, out + (long)blockIdx.z * 2 * C * F, (int)blockIdx.x, (int)blockIdx.y * 64);
-}
-
-bool launch_spk_pool_batch(const half_t* x, int F, const int* frames, int n, int C, float eps, float* out, hipStream_t s) {
-    if (!x || !out || F < 1 || C < 64 || C % 64) return false;
-    SpkBatch tab;
-    long blocks;
-    if (!spk_table(frames, n, 1, 1, 1, 1L << 30, tab, blocks)) return false;
-    for (int i = 0; i < n; ++i)
-        if (frames[i] < 2) return false;
-    hipLaunchKernelGGL(spk_pool_batch_kernel, dim3((unsigned)F, (unsigned)(C / 64), (unsigned)n), dim3(256), 0, s, x, tab, F, C, eps, out);
-    return true;
 }
 
 __global__ __launch_bounds__(64) void spk_linear_batch_kernel(const float* __restrict__ x, const half_t* __restrict__ W,

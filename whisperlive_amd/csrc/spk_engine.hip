@@ -1,10 +1,11 @@
 // spk_engine.hip — the speaker-embedding engine behind `enable_diarization` (include/wlx.h wlx_spk_*): WeSpeaker ResNet34 on the
 // kernels of spk.hip. One engine per GPU on a non-blocking stream of its own; every buffer is sized at create for max_seconds of
 // audio and fully rewritten by each call up to the extent that call reads, so no call sees another's data. Calls are serialised
-// by the engine's mutex. wlx_spk_embed_batch runs up to WLX_SPK_MAX_BATCH segments as one ragged pass through the same buffers (the
-// sum of their lengths is what has to fit max_seconds); wlx_spk_embed_pcm_batch / _ring_batch run the same pass on ranges of audio that
-// is already in HBM (a slot item's PCM, a client's PCM ring), with no upload. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
-// _pool and their ragged forms _conv_batch / _pool_batch.
+// by the engine's mutex. ONE pass (spk_run_batch) serves every entry point: up to WLX_SPK_MAX_BATCH segments as one ragged batch
+// through the same buffers (the sum of their lengths is what has to fit max_seconds). wlx_spk_embed is a batch of one;
+// wlx_spk_embed_batch uploads its items; wlx_spk_embed_pcm_batch / _ring_batch run the pass on ranges of audio that is already in HBM
+// (a slot item's PCM, a client's PCM ring), with no upload. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
+// _pool (one item) and _conv_batch / _pool_batch (ragged), each pair on one implementation.
 #include <cmath>
 #include <mutex>
 #include "engine.h"
@@ -177,7 +178,8 @@ static int spk_build(wlx_spk* k, const wlx_tensor* weights, int n_weights) {
     // the stem's output is the largest activation: every stride-2 stage halves H and W and doubles C
     for (half_t*& a : k->act) CKR(dalloc(k->pool, &a, Tmax * sp.n_mels * m, false));
     // (a batch packs its items into the buffers above: sum T_i <= spk_frames(sum n_i), and from the second stage on the rounded-up
-    // halves sum to at most (sum W_i + n) / 2 columns of half the rows and twice the channels: under the stem's extent, n <= sum W_i)
+    // halves sum to at most (sum W_i + n) / 2 columns of half the rows and twice the channels: under the stem's extent, n <= sum W_i.
+    // A single embed is the case n = 1, sum T_i = T)
     CKR(dalloc(k->pool, &k->pooled, (size_t)k->pool_dim * WLX_SPK_MAX_BATCH, false));
     CKR(dalloc(k->pool, &k->emb, (size_t)sp.embed_dim * WLX_SPK_MAX_BATCH, false));
     CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_emb), (size_t)sp.embed_dim * WLX_SPK_MAX_BATCH * sizeof(float), hipHostMallocDefault));
@@ -216,53 +218,7 @@ extern "C" void wlx_spk_destroy(wlx_spk* k) {
     spk_free(k);
 }
 
-extern "C" int32_t wlx_spk_embed(wlx_spk* k, const float* pcm, int64_t n_samples, float* out) {
-    if (!k || !pcm || !out) return set_error(WLX_ERR_ARG, "null argument");
-    if (n_samples < WLX_SPK_MIN_SAMPLES)
-        return set_error(WLX_ERR_TOO_SHORT, "%lld samples: under 0.3 s of audio", (long long)n_samples);
-    if (n_samples > k->max_samples)
-        return set_error(WLX_ERR_ARG, "%lld samples exceed the engine's %d s", (long long)n_samples, k->spec.max_seconds);
-    std::lock_guard<std::mutex> g(k->mu);
-    CK(hipSetDevice(k->device));
-    const wlx_spk_spec& sp = k->spec;
-    hipStream_t st = k->st;
-    const int T = spk_frames((long)n_samples);
-    CK(hipMemcpyAsync(k->pcm, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, st));
-    CK(hipEventRecord(k->ev[0], st));
-    launch_spk_fbank(k->pcm, T, k->window, k->twiddle, k->mel, sp.n_mels, k->logmel, st);
-    launch_spk_cmn(k->logmel, T, sp.n_mels, k->feat16, st);
-    CK(hipEventRecord(k->ev[1], st));
-    int H = sp.n_mels, W = T;
-    half_t *x = k->act[0], *t1 = k->act[1], *y = k->act[2], *sc = k->act[3];
-    if (!launch_spk_conv_c1(k->feat16, H, W, k->stem_w, k->stem_b, nullptr, sp.planes, 1, true, x, st))
-        return set_error(WLX_ERR_ARG, "stem convolution refused %d x %d", H, W);
-    for (const SpkBlock& b : k->blocks) {
-        const int s = b.c1.stride, OH = (H - 1) / s + 1, OW = (W - 1) / s + 1;
-        bool ok = launch_spk_conv(x, H, W, b.c1.cin, b.c1.Wp, b.c1.bias, nullptr, b.c1.cout, s, 3, true, t1, st);
-        const half_t* resid = x;
-        if (b.has_sc) {
-            ok = ok && launch_spk_conv(x, H, W, b.sc.cin, b.sc.Wp, b.sc.bias, nullptr, b.sc.cout, s, 1, false, sc, st);
-            resid = sc;
-        }
-        ok = ok && launch_spk_conv(t1, OH, OW, b.c2.cin, b.c2.Wp, b.c2.bias, resid, b.c2.cout, 1, 3, true, y, st);
-        if (!ok) return set_error(WLX_ERR_ARG, "convolution refused %d x %d x %d", H, W, b.c1.cin);
-        std::swap(x, y);
-        H = OH, W = OW;
-    }
-    if (!launch_spk_pool(x, H, W, sp.planes << 3, sp.pool_eps, k->pooled, st))
-        return set_error(WLX_ERR_ARG, "pooling refused %d x %d", H, W);
-    launch_spk_head(k->pooled, k->head_W, k->head_b, sp.embed_dim, k->pool_dim, k->emb, st);
-    CK(hipEventRecord(k->ev[2], st));
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(out, k->emb, (size_t)sp.embed_dim * sizeof(float), hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));
-    CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
-    k->timed = true;
-    return WLX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ ragged batch
+// ------------------------------------------------------------------------------------------------ the pass and its entry points
 // What the three batch entry points decide on the arguments alone: status and the zero row of every item that is too short, and of the
 // m items that take part their frames and the row of `out` each fills. Written to the CALLER's arrays only by spk_plan_commit, after
 // every refusal of the entry point has had its turn.
@@ -346,6 +302,21 @@ static int spk_run_batch(wlx_spk* k, const float* src, const SpkPlan& pl, float*
     CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
     k->timed = true;
     return WLX_OK;
+}
+
+// one segment: a batch of one with refusals of its own (too short is the RETURN value here, and `out` stays untouched)
+extern "C" int32_t wlx_spk_embed(wlx_spk* k, const float* pcm, int64_t n_samples, float* out) {
+    if (!k || !pcm || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (n_samples < WLX_SPK_MIN_SAMPLES)
+        return set_error(WLX_ERR_TOO_SHORT, "%lld samples: under 0.3 s of audio", (long long)n_samples);
+    if (n_samples > k->max_samples)
+        return set_error(WLX_ERR_ARG, "%lld samples exceed the engine's %d s", (long long)n_samples, k->spec.max_seconds);
+    SpkPlan pl;
+    pl.offs[0] = 0, pl.widths[0] = spk_frames((long)n_samples), pl.row[0] = 0, pl.m = 1, pl.total = (long)n_samples;
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    CK(hipMemcpyAsync(k->pcm, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, k->st));
+    return spk_run_batch(k, k->pcm, pl, out);
 }
 
 extern "C" int32_t wlx_spk_embed_batch(wlx_spk* k, const float* pcm, const int64_t* n_samples, int32_t n, float* out, int32_t* status) {
@@ -472,81 +443,20 @@ extern "C" int32_t wlx_spk_debug_fbank(int32_t device, const float* pcm, int64_t
     CKR(S.upload(&dpcm, pcm, (size_t)n_samples));
     CKR(S.upload(&dlm, nullptr, (size_t)T * n_mels));
     CKR(S.upload(&d16, nullptr, (size_t)T * n_mels));
-    launch_spk_fbank(dpcm, T, window, twiddle, mel, n_mels, dlm, S.st);
-    launch_spk_cmn(dlm, T, n_mels, d16, S.st);
+    const long offset = 0;          // one item at the start of the upload
+    if (!launch_spk_fbank_batch(dpcm, &offset, &T, 1, window, twiddle, mel, n_mels, dlm, S.st) ||
+        !launch_spk_cmn_batch(dlm, &T, 1, n_mels, d16, S.st))
+        return set_error(WLX_ERR_ARG, "the launcher refused the shape");
     CK(hipMemcpyAsync(frames_out, dlm, (size_t)T * n_mels * sizeof(float), hipMemcpyDeviceToHost, S.st));
     CK(hipMemcpyAsync(image_out, d16, (size_t)T * n_mels * sizeof(half_t), hipMemcpyDeviceToHost, S.st));
     *n_frames_out = T;
     return S.finish();
 }
 
-extern "C" int32_t wlx_spk_debug_conv(int32_t device, const uint16_t* in, int32_t H, int32_t W, int32_t Cin, const float* w, const float* bias,
-                                      const uint16_t* resid, int32_t Cout, int32_t stride, int32_t ksize, int32_t relu, uint16_t* out) {
-    if (!in || !w || !out) return set_error(WLX_ERR_ARG, "null argument");
-    if (H < 1 || W < 1 || (long)H * W > (1L << 24)) return set_error(WLX_ERR_ARG, "H %d x W %d outside 1..2^24 pixels", H, W);
-    if (stride != 1 && stride != 2) return set_error(WLX_ERR_ARG, "stride %d must be 1 or 2", stride);
-    const bool c1 = Cin == 1;
-    if (c1 ? (ksize != 3 || Cout < 4 || Cout % 4 || Cout > 1024)
-           : ((ksize != 1 && ksize != 3) || Cin < 32 || Cin % 32 || Cin > 1024 || Cout < 32 || Cout % 32 || Cout > 1024))
-        return set_error(WLX_ERR_ARG, "Cin %d / Cout %d / ksize %d: Cin = 1 (ksize 3, Cout a multiple of 4) or Cin and Cout multiples of 32 up "
-                         "to 1024 with ksize 1 or 3", Cin, Cout, ksize);
-    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-    const size_t n_out = (size_t)OH * OW * Cout;
-    std::vector<float> zeros;          // (host staging declared before S: it outlives the stream's copies on every return path)
-    std::vector<half_t> packed;
-    SpkHook S;
-    CKR(S.begin(device));
-    half_t *din, *dres = nullptr, *dout;
-    float* dbias;
-    CKR(S.upload(&din, in, (size_t)H * W * Cin));
-    if (!bias) zeros.assign((size_t)Cout, 0.f);
-    CKR(S.upload(&dbias, bias ? bias : zeros.data(), (size_t)Cout));
-    if (resid) CKR(S.upload(&dres, resid, n_out));
-    CKR(S.upload(&dout, out, n_out));
-    bool ok;
-    if (c1) {
-        float* dw;
-        CKR(S.upload(&dw, w, (size_t)Cout * 9));
-        ok = launch_spk_conv_c1(din, H, W, dw, dbias, dres, Cout, stride, relu != 0, dout, S.st);
-    } else {
-        packed.resize(spk_packed_halfs(Cout, Cin, ksize));
-        spk_pack_conv(w, Cout, Cin, ksize, packed.data());
-        half_t* dWp;
-        CKR(S.upload(&dWp, packed.data(), packed.size()));
-        ok = launch_spk_conv(din, H, W, Cin, dWp, dbias, dres, Cout, stride, ksize, relu != 0, dout, S.st);
-    }
-    if (!ok) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
-    CK(hipMemcpyAsync(out, dout, n_out * sizeof(half_t), hipMemcpyDeviceToHost, S.st));
-    return S.finish();
-}
-
-extern "C" int32_t wlx_spk_debug_pool(int32_t device, const uint16_t* x, int32_t F, int32_t T, int32_t C, float eps, float* out) {
-    if (!x || !out) return set_error(WLX_ERR_ARG, "null argument");
-    if (F < 1 || F > 4096 || T < 2 || T > (1 << 20) || C < 64 || C % 64 || C > 4096 || !(eps >= 0.f))
-        return set_error(WLX_ERR_ARG, "F %d / T %d / C %d: F in 1..4096, T in 2..2^20, C a multiple of 64 up to 4096", F, T, C);
-    SpkHook S;
-    CKR(S.begin(device));
-    half_t* dx;
-    float* dout;
-    CKR(S.upload(&dx, x, (size_t)F * T * C));
-    CKR(S.upload(&dout, out, (size_t)2 * F * C));
-    if (!launch_spk_pool(dx, F, T, C, eps, dout, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
-    CK(hipMemcpyAsync(out, dout, (size_t)2 * F * C * sizeof(float), hipMemcpyDeviceToHost, S.st));
-    return S.finish();
-}
-
-extern "C" int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, int32_t H, int32_t n, const int32_t* widths, int32_t Cin,
-                                            const float* w, const float* bias, const uint16_t* resid, int32_t Cout, int32_t stride,
-                                            int32_t ksize, int32_t relu, uint16_t* out) {
-    if (!in || !w || !out || !widths) return set_error(WLX_ERR_ARG, "null argument");
-    if (n < 1 || n > WLX_SPK_MAX_BATCH) return set_error(WLX_ERR_ARG, "%d items outside 1..%d", n, WLX_SPK_MAX_BATCH);
-    if (stride != 1 && stride != 2) return set_error(WLX_ERR_ARG, "stride %d must be 1 or 2", stride);
-    long Wsum = 0, OWsum = 0;
-    for (int i = 0; i < n; ++i) {
-        if (widths[i] < 1 || widths[i] > (1 << 24)) return set_error(WLX_ERR_ARG, "widths[%d] = %d outside 1..2^24", i, widths[i]);
-        Wsum += widths[i], OWsum += (widths[i] - 1) / stride + 1;
-    }
-    if (H < 1 || (long)H * Wsum > (1L << 24)) return set_error(WLX_ERR_ARG, "H %d x sum of widths %ld outside 1..2^24 pixels", H, Wsum);
+// wlx_spk_debug_conv (n = 1, widths = {W}) and wlx_spk_debug_conv_batch behind their own geometry checks: `Wsum` / `OWsum` columns in
+// all at the input / the output, stride is 1 or 2.
+static int spk_debug_conv_run(int device, const uint16_t* in, int H, int n, const int32_t* widths, long Wsum, long OWsum, int Cin, const float* w,
+                              const float* bias, const uint16_t* resid, int Cout, int stride, int ksize, int relu, uint16_t* out) {
     const bool c1 = Cin == 1;
     if (c1 ? (ksize != 3 || Cout < 4 || Cout % 4 || Cout > 1024)
            : ((ksize != 1 && ksize != 3) || Cin < 32 || Cin % 32 || Cin > 1024 || Cout < 32 || Cout % 32 || Cout > 1024))
@@ -554,7 +464,7 @@ extern "C" int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, 
                          "to 1024 with ksize 1 or 3", Cin, Cout, ksize);
     const int OH = (H - 1) / stride + 1;
     const size_t n_out = (size_t)OH * OWsum * Cout;
-    std::vector<float> zeros;          // (host staging declared before S, as in wlx_spk_debug_conv)
+    std::vector<float> zeros;          // (host staging declared before S: it outlives the stream's copies on every return path)
     std::vector<half_t> packed;
     SpkHook S;
     CKR(S.begin(device));
@@ -582,6 +492,50 @@ extern "C" int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, 
     return S.finish();
 }
 
+extern "C" int32_t wlx_spk_debug_conv(int32_t device, const uint16_t* in, int32_t H, int32_t W, int32_t Cin, const float* w, const float* bias,
+                                      const uint16_t* resid, int32_t Cout, int32_t stride, int32_t ksize, int32_t relu, uint16_t* out) {
+    if (!in || !w || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (H < 1 || W < 1 || (long)H * W > (1L << 24)) return set_error(WLX_ERR_ARG, "H %d x W %d outside 1..2^24 pixels", H, W);
+    if (stride != 1 && stride != 2) return set_error(WLX_ERR_ARG, "stride %d must be 1 or 2", stride);
+    return spk_debug_conv_run(device, in, H, 1, &W, W, (W - 1) / stride + 1, Cin, w, bias, resid, Cout, stride, ksize, relu, out);
+}
+
+extern "C" int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, int32_t H, int32_t n, const int32_t* widths, int32_t Cin,
+                                            const float* w, const float* bias, const uint16_t* resid, int32_t Cout, int32_t stride,
+                                            int32_t ksize, int32_t relu, uint16_t* out) {
+    if (!in || !w || !out || !widths) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_MAX_BATCH) return set_error(WLX_ERR_ARG, "%d items outside 1..%d", n, WLX_SPK_MAX_BATCH);
+    if (stride != 1 && stride != 2) return set_error(WLX_ERR_ARG, "stride %d must be 1 or 2", stride);
+    long Wsum = 0, OWsum = 0;
+    for (int i = 0; i < n; ++i) {
+        if (widths[i] < 1 || widths[i] > (1 << 24)) return set_error(WLX_ERR_ARG, "widths[%d] = %d outside 1..2^24", i, widths[i]);
+        Wsum += widths[i], OWsum += (widths[i] - 1) / stride + 1;
+    }
+    if (H < 1 || (long)H * Wsum > (1L << 24)) return set_error(WLX_ERR_ARG, "H %d x sum of widths %ld outside 1..2^24 pixels", H, Wsum);
+    return spk_debug_conv_run(device, in, H, n, widths, Wsum, OWsum, Cin, w, bias, resid, Cout, stride, ksize, relu, out);
+}
+
+// wlx_spk_debug_pool (n = 1, frames = {T}) and wlx_spk_debug_pool_batch behind their own range checks: `Tsum` frames in all
+static int spk_debug_pool_run(int device, const uint16_t* x, int F, int n, const int32_t* frames, long Tsum, int C, float eps, float* out) {
+    SpkHook S;
+    CKR(S.begin(device));
+    half_t* dx;
+    float* dout;
+    const size_t n_out = (size_t)n * 2 * F * C;
+    CKR(S.upload(&dx, x, (size_t)F * Tsum * C));
+    CKR(S.upload(&dout, out, n_out));
+    if (!launch_spk_pool_batch(dx, F, frames, n, C, eps, dout, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CK(hipMemcpyAsync(out, dout, n_out * sizeof(float), hipMemcpyDeviceToHost, S.st));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_spk_debug_pool(int32_t device, const uint16_t* x, int32_t F, int32_t T, int32_t C, float eps, float* out) {
+    if (!x || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (F < 1 || F > 4096 || T < 2 || T > (1 << 20) || C < 64 || C % 64 || C > 4096 || !(eps >= 0.f))
+        return set_error(WLX_ERR_ARG, "F %d / T %d / C %d: F in 1..4096, T in 2..2^20, C a multiple of 64 up to 4096", F, T, C);
+    return spk_debug_pool_run(device, x, F, 1, &T, T, C, eps, out);
+}
+
 extern "C" int32_t wlx_spk_debug_pool_batch(int32_t device, const uint16_t* x, int32_t F, int32_t n, const int32_t* frames, int32_t C,
                                             float eps, float* out) {
     if (!x || !out || !frames) return set_error(WLX_ERR_ARG, "null argument");
@@ -594,14 +548,5 @@ extern "C" int32_t wlx_spk_debug_pool_batch(int32_t device, const uint16_t* x, i
         Tsum += frames[i];
     }
     if (Tsum > (1 << 20)) return set_error(WLX_ERR_ARG, "%ld frames in all exceed 2^20", Tsum);
-    SpkHook S;
-    CKR(S.begin(device));
-    half_t* dx;
-    float* dout;
-    const size_t n_out = (size_t)n * 2 * F * C;
-    CKR(S.upload(&dx, x, (size_t)F * Tsum * C));
-    CKR(S.upload(&dout, out, n_out));
-    if (!launch_spk_pool_batch(dx, F, frames, n, C, eps, dout, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
-    CK(hipMemcpyAsync(out, dout, n_out * sizeof(float), hipMemcpyDeviceToHost, S.st));
-    return S.finish();
+    return spk_debug_pool_run(device, x, F, n, frames, Tsum, C, eps, out);
 }

@@ -14,8 +14,9 @@
 //     reduction, the gate non-linearities and one barrier. It is latency-bound by construction (938 dependent steps);
 //     the CPU path it replaces is the same chain at ~30-50 us per step.
 //   output: p[t] = sigmoid(w_out . relu(h_t) + b), parallel over windows.
-//   ragged batch (wlx_vad_probs_batch): up to 64 sequences packed window after window; the front end and the recurrence run the SAME
-//     bodies per item (one recurrence workgroup per item, side by side), so a row has the bits of the single call on that item.
+//   ONE pass for every entry point (vad_run_batch): up to 64 sequences packed window after window, the front end and the recurrence
+//     per item (one recurrence workgroup per item, side by side). wlx_vad_probs / _resident / _pcm are a batch of one; an item's bits
+//     do not depend on its neighbours, its position or the table's fill.
 // fp32 throughout (the gate thresholds at 0.5 / 0.35 are compared against these numbers; the oracle's own fp32-vs-fp64
 // difference is 5e-7). Everything is deterministic: fixed summation orders, no atomics.
 #include "engine.h"
@@ -53,7 +54,7 @@ __device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builti
 
 // ---------------------------------------------------------------------------------------------------------------------
 // front end: VAD_WT windows per workgroup, PCM -> gx
-// One workgroup's work, shared by the single-item and the ragged-batch kernel: windows [w0, w0 + VAD_WT) of ONE sequence of `n` samples
+// One workgroup's work: windows [w0, w0 + VAD_WT) of ONE sequence of `n` samples
 // and `n_windows` windows whose gx rows start at `gx`. A sample position < 0 or >= n, or a window >= n_windows, reads 0.
 __device__ __forceinline__ void vad_frontend_body(const float* __restrict__ pcm, long long n, int n_windows, int w0, const VadW& W,
                                                   float* __restrict__ gx) {
@@ -228,11 +229,6 @@ __device__ __forceinline__ void vad_frontend_body(const float* __restrict__ pcm,
     }
 }
 
-__global__ __launch_bounds__(VAD_FE_THREADS) void vad_frontend_kernel(const float* __restrict__ pcm, long long n, int n_windows,
-                                                                       VadW W, float* __restrict__ gx) {
-    vad_frontend_body(pcm, n, n_windows, (int)blockIdx.x * VAD_WT, W, gx);
-}
-
 // ---- ragged batch: up to WLX_VAD_MAX_BATCH sequences of different lengths, packed window after window without padding: item i owns
 // windows [w0, w0 + T) of gx / hs / probs. The table travels BY VALUE in the kernel arguments (2 KiB, copied by the launch call itself,
 // like spk.hip's item table): no staging buffer, no copy that could outlive the caller's frame. Only items with T >= 1 are in it.
@@ -272,8 +268,7 @@ __device__ __forceinline__ float quad_perm(float v) {      // DPP quad_perm move
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
 
-// One workgroup's whole sequence, shared by the single-item and the ragged-batch kernel (same arithmetic, same bits): T steps from
-// zero h and c over the gx rows at `gx`, states to the hs rows at `hs`.
+// One workgroup's whole sequence: T steps from zero h and c over the gx rows at `gx`, states to the hs rows at `hs`.
 __device__ __forceinline__ void vad_lstm_body(const float* __restrict__ gx, const float* __restrict__ whhP, float* __restrict__ hs, int T) {
     __shared__ __attribute__((aligned(16))) float hbuf[2][VAD_H];
     const int tid = threadIdx.x, j = tid >> 2, q = tid & 3;
@@ -335,12 +330,7 @@ __device__ __forceinline__ void vad_lstm_body(const float* __restrict__ gx, cons
     }
 }
 
-__global__ __launch_bounds__(512) void vad_lstm_kernel(const float* __restrict__ gx, const float* __restrict__ whhP,
-                                                        float* __restrict__ hs, int T) {
-    vad_lstm_body(gx, whhP, hs, T);
-}
-
-// ragged batch: blockIdx.x is the item; the recurrences are independent and run side by side, one CU each (a workgroup takes a CU's
+// blockIdx.x is the item; the recurrences are independent and run side by side, one CU each (a workgroup takes a CU's
 // whole register file, so items beyond the free CUs queue behind the first to finish)
 __global__ __launch_bounds__(512) void vad_lstm_batch_kernel(VadBatch tab, const float* __restrict__ gx, const float* __restrict__ whhP,
                                                               float* __restrict__ hs) {
@@ -373,9 +363,9 @@ struct wlx_vad {
     std::vector<void*> pool;
     VadW W{};
     float *d_pcm = nullptr, *d_gx = nullptr, *d_hs = nullptr, *d_probs = nullptr;
-    float* h_pin = nullptr;              // pinned staging: PCM in, probabilities out
+    float* h_pin = nullptr;              // pinned staging: PCM in
     long long cap_samples = 0;
-    float* h_probs = nullptr;            // pinned, probabilities out of wlx_vad_probs_pcm (which never touches d_pcm / h_pin)
+    float* h_probs = nullptr;            // pinned staging: probabilities out
     long long cap_windows = 0;           // windows d_gx / d_hs / d_probs / h_probs hold
     std::mutex mu;
 };
@@ -499,6 +489,67 @@ extern "C" void wlx_vad_destroy(wlx_vad* v) {
     delete v;
 }
 
+// ------------------------------------------------------------------ the pass (every wlx_vad_probs* entry point ends in vad_run_batch)
+// The geometry of a pass: the table of the items that have a window (window offsets, front-end groups rounded up per item), T_i of
+// EVERY item, the packed window count and the sample total. The sample pointers are filled in by the caller.
+struct VadPlan {
+    VadBatch tab;
+    int src[WLX_VAD_MAX_BATCH];              // table entry -> item of the call
+    int T[WLX_VAD_MAX_BATCH];
+    long long windows = 0, samples = 0;
+    int groups = 0;
+};
+
+// Everything both batch entry points refuse on the arguments alone. Nothing of the caller's is written here.
+static int vad_plan(const char* who, const int64_t* n_samples, const int32_t* extra, int32_t n, int64_t cap, VadPlan& pl) {
+    if (n < 1 || n > WLX_VAD_MAX_BATCH) return set_error(WLX_ERR_ARG, "%s: %d items (1..%d)", who, n, WLX_VAD_MAX_BATCH);
+    pl.tab.n = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t ni = n_samples[i];
+        const int ex = extra ? extra[i] : 0;
+        if (ni < 0) return set_error(WLX_ERR_ARG, "%s: item %d has a negative sample count", who, i);
+        if (ex < 0 || ex > 4) return set_error(WLX_ERR_ARG, "%s: item %d: extra_zero_windows out of range", who, i);
+        if (ni > 16000LL * 3600 || (pl.samples += ni) > 16000LL * 3600) return set_error(WLX_ERR_ARG, "%s: more than 3600 s of audio", who);
+        const int T = (int)((ni + VAD_WINDOW - 1) / VAD_WINDOW) + ex;
+        pl.T[i] = T;
+        if (T == 0) continue;
+        pl.src[pl.tab.n] = i;
+        pl.tab.it[pl.tab.n++] = VadItem{nullptr, (long long)ni, T, (int)pl.windows, pl.groups, 0};
+        pl.windows += T;
+        pl.groups += (T + VAD_WT - 1) / VAD_WT;
+    }
+    for (int k = pl.tab.n; k < WLX_VAD_MAX_BATCH; ++k) pl.tab.it[k] = VadItem{nullptr, 0, 0, 0, 0, 0};
+    if (pl.windows > cap) return set_error(WLX_ERR_ARG, "%s: %lld windows do not fit the output buffer (%lld)", who, pl.windows, (long long)cap);
+    return WLX_OK;
+}
+
+// the plan of the single entry points, which keep their own refusals: one item of T >= 1 windows over the n samples at `pcm`
+static void vad_plan_one(const float* pcm, long long n, int T, VadPlan& pl) {
+    pl.tab.n = 1;
+    pl.tab.it[0] = VadItem{pcm, n, T, 0, 0, 0};
+    for (int k = 1; k < WLX_VAD_MAX_BATCH; ++k) pl.tab.it[k] = VadItem{nullptr, 0, 0, 0, 0, 0};
+    pl.src[0] = 0, pl.T[0] = T;
+    pl.windows = T, pl.samples = n, pl.groups = (T + VAD_WT - 1) / VAD_WT;
+}
+
+// the pass itself on v->stream, behind whatever the caller put there (an upload, a wait for another stream): one launch of each kernel
+// over the packed windows, one download, one wait. v->mu is held, the device is set and the per-window buffers hold pl.windows.
+static int vad_run_batch(wlx_vad* v, const VadPlan& pl, float* probs_out, float* device_ms_out) {
+    const int T = (int)pl.windows;
+    CK(hipEventRecord(v->ev0, v->stream));
+    hipLaunchKernelGGL(vad_frontend_batch_kernel, dim3(pl.groups), dim3(VAD_FE_THREADS), 0, v->stream, pl.tab, v->W, v->d_gx);
+    hipLaunchKernelGGL(vad_lstm_batch_kernel, dim3(pl.tab.n), dim3(512), 0, v->stream, pl.tab, v->d_gx, v->W.whhP, v->d_hs);
+    hipLaunchKernelGGL(vad_out_kernel, dim3((T + 3) / 4), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, T);
+    CK(hipGetLastError());
+    CK(hipEventRecord(v->ev1, v->stream));
+    CK(hipMemcpyAsync(v->h_probs, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+    CK(hipStreamSynchronize(v->stream));
+    memcpy(probs_out, v->h_probs, (size_t)T * sizeof(float));
+    if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
+    return WLX_OK;
+}
+
+// ------------------------------------------------------------------ one sequence: a batch of one (the refusals are each entry point's own)
 extern "C" int32_t wlx_vad_probs(wlx_vad* v, const float* pcm, int64_t n, float* probs_out, int32_t cap,
                                  int32_t* n_windows_out, float* device_ms_out) {
     if (!v || !n_windows_out || (n > 0 && (!pcm || !probs_out))) return set_error(WLX_ERR_ARG, "wlx_vad_probs: null argument");
@@ -511,22 +562,12 @@ extern "C" int32_t wlx_vad_probs(wlx_vad* v, const float* pcm, int64_t n, float*
     std::lock_guard<std::mutex> lk(v->mu);
     CK(hipSetDevice(v->device));
     (void)hipGetLastError();                  // a stale error of this thread must not be blamed on the launches below
-    int rc = vad_reserve(v, n);
-    if (rc) return rc;
+    CKR(vad_reserve(v, n));
     memcpy(v->h_pin, pcm, (size_t)n * sizeof(float));
     CK(hipMemcpyAsync(v->d_pcm, v->h_pin, (size_t)n * sizeof(float), hipMemcpyHostToDevice, v->stream));
-    CK(hipEventRecord(v->ev0, v->stream));
-    const int fe_blocks = (int)((T + VAD_WT - 1) / VAD_WT);
-    hipLaunchKernelGGL(vad_frontend_kernel, dim3(fe_blocks), dim3(VAD_FE_THREADS), 0, v->stream, v->d_pcm, (long long)n, (int)T, v->W, v->d_gx);
-    hipLaunchKernelGGL(vad_lstm_kernel, dim3(1), dim3(512), 0, v->stream, v->d_gx, v->W.whhP, v->d_hs, (int)T);
-    hipLaunchKernelGGL(vad_out_kernel, dim3((int)((T + 3) / 4)), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, (int)T);
-    CK(hipGetLastError());
-    CK(hipEventRecord(v->ev1, v->stream));
-    CK(hipMemcpyAsync(v->h_pin, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-    CK(hipStreamSynchronize(v->stream));
-    memcpy(probs_out, v->h_pin, (size_t)T * sizeof(float));
-    if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
-    return WLX_OK;
+    VadPlan pl;
+    vad_plan_one(v->d_pcm, n, (int)T, pl);
+    return vad_run_batch(v, pl, probs_out, device_ms_out);
 }
 
 // The same on samples that are already in HBM: [start, start + n) of a client's PCM ring (engine.hip wlx_ring_*, include/wlx.h) — the
@@ -543,27 +584,16 @@ extern "C" int32_t wlx_vad_probs_resident(wlx_vad* v, wlx_ring* r, int64_t start
     if (T == 0) return WLX_OK;
     if (T > cap) return set_error(WLX_ERR_ARG, "wlx_vad_probs_resident: %lld windows do not fit the output buffer (%d)", T, cap);
     std::lock_guard<std::mutex> lk(v->mu);
-    std::lock_guard<std::mutex> lr(r->mu);          // no append / trim while the kernels read (the call waits for them below)
+    std::lock_guard<std::mutex> lr(r->mu);          // no append / trim while the kernels read (vad_run_batch waits for them)
     if (start < r->base || start + n > r->base + r->resident)
         return set_error(WLX_ERR_STATE, "wlx_vad_probs_resident: [%lld, %lld) is not resident (ring holds [%lld, %lld))", (long long)start,
                          (long long)(start + n), (long long)r->base, (long long)(r->base + r->resident));
     CK(hipSetDevice(v->device));
     (void)hipGetLastError();
-    int rc = vad_reserve(v, n + (long long)extra_zero_windows * VAD_WINDOW);
-    if (rc) return rc;
-    const float* pcm = r->buf + (start - r->base);
-    CK(hipEventRecord(v->ev0, v->stream));
-    const int fe_blocks = (int)((T + VAD_WT - 1) / VAD_WT);
-    hipLaunchKernelGGL(vad_frontend_kernel, dim3(fe_blocks), dim3(VAD_FE_THREADS), 0, v->stream, pcm, (long long)n, (int)T, v->W, v->d_gx);
-    hipLaunchKernelGGL(vad_lstm_kernel, dim3(1), dim3(512), 0, v->stream, v->d_gx, v->W.whhP, v->d_hs, (int)T);
-    hipLaunchKernelGGL(vad_out_kernel, dim3((int)((T + 3) / 4)), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, (int)T);
-    CK(hipGetLastError());
-    CK(hipEventRecord(v->ev1, v->stream));
-    CK(hipMemcpyAsync(v->h_pin, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-    CK(hipStreamSynchronize(v->stream));
-    memcpy(probs_out, v->h_pin, (size_t)T * sizeof(float));
-    if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
-    return WLX_OK;
+    CKR(vad_reserve(v, n + (long long)extra_zero_windows * VAD_WINDOW));
+    VadPlan pl;
+    vad_plan_one(r->buf + (start - r->base), n, (int)T, pl);
+    return vad_run_batch(v, pl, probs_out, device_ms_out);
 }
 
 // The same on a slot item's resident PCM (wlx_pcm_put / wlx_pcm_put_frames): the gate of a FILE reads the 16 kHz copy the front end left
@@ -595,71 +625,12 @@ extern "C" int32_t wlx_vad_probs_pcm(wlx_vad* v, wlx_engine* e, int32_t slot, in
     if (!s->ev_pcm) CK(hipEventCreateWithFlags(&s->ev_pcm, hipEventDisableTiming));
     CK(hipEventRecord(s->ev_pcm, s->stream));                 // whatever wrote the PCM on the slot's stream ...
     CK(hipStreamWaitEvent(v->stream, s->ev_pcm, 0));          // ... is finished before the gate reads it
-    const float* pcm = s->pcm + (size_t)item * s->pcm_cap + start;
-    CK(hipEventRecord(v->ev0, v->stream));
-    const int fe_blocks = (int)((T + VAD_WT - 1) / VAD_WT);
-    hipLaunchKernelGGL(vad_frontend_kernel, dim3(fe_blocks), dim3(VAD_FE_THREADS), 0, v->stream, pcm, (long long)n, (int)T, v->W, v->d_gx);
-    hipLaunchKernelGGL(vad_lstm_kernel, dim3(1), dim3(512), 0, v->stream, v->d_gx, v->W.whhP, v->d_hs, (int)T);
-    hipLaunchKernelGGL(vad_out_kernel, dim3((int)((T + 3) / 4)), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, (int)T);
-    CK(hipGetLastError());
-    CK(hipEventRecord(v->ev1, v->stream));
-    CK(hipMemcpyAsync(v->h_probs, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-    CK(hipStreamSynchronize(v->stream));
-    memcpy(probs_out, v->h_probs, (size_t)T * sizeof(float));
-    if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
-    return WLX_OK;
+    VadPlan pl;
+    vad_plan_one(s->pcm + (size_t)item * s->pcm_cap + start, n, (int)T, pl);
+    return vad_run_batch(v, pl, probs_out, device_ms_out);
 }
 
 // ------------------------------------------------------------------ ragged batch (include/wlx.h wlx_vad_probs_batch)
-// Everything both batch entry points refuse on the arguments alone, and the geometry of the pass: the table of the items that have a
-// window (window offsets, front-end groups rounded up per item), T_i of EVERY item, the packed window count and the sample total. The
-// sample pointers are filled in by the caller. Nothing of the caller's is written here.
-struct VadPlan {
-    VadBatch tab;
-    int src[WLX_VAD_MAX_BATCH];              // table entry -> item of the call
-    int T[WLX_VAD_MAX_BATCH];
-    long long windows = 0, samples = 0;
-    int groups = 0;
-};
-
-static int vad_plan(const char* who, const int64_t* n_samples, const int32_t* extra, int32_t n, int64_t cap, VadPlan& pl) {
-    if (n < 1 || n > WLX_VAD_MAX_BATCH) return set_error(WLX_ERR_ARG, "%s: %d items (1..%d)", who, n, WLX_VAD_MAX_BATCH);
-    pl.tab.n = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t ni = n_samples[i];
-        const int ex = extra ? extra[i] : 0;
-        if (ni < 0) return set_error(WLX_ERR_ARG, "%s: item %d has a negative sample count", who, i);
-        if (ex < 0 || ex > 4) return set_error(WLX_ERR_ARG, "%s: item %d: extra_zero_windows out of range", who, i);
-        if (ni > 16000LL * 3600 || (pl.samples += ni) > 16000LL * 3600) return set_error(WLX_ERR_ARG, "%s: more than 3600 s of audio", who);
-        const int T = (int)((ni + VAD_WINDOW - 1) / VAD_WINDOW) + ex;
-        pl.T[i] = T;
-        if (T == 0) continue;
-        pl.src[pl.tab.n] = i;
-        pl.tab.it[pl.tab.n++] = VadItem{nullptr, (long long)ni, T, (int)pl.windows, pl.groups, 0};
-        pl.windows += T;
-        pl.groups += (T + VAD_WT - 1) / VAD_WT;
-    }
-    for (int k = pl.tab.n; k < WLX_VAD_MAX_BATCH; ++k) pl.tab.it[k] = VadItem{nullptr, 0, 0, 0, 0, 0};
-    if (pl.windows > cap) return set_error(WLX_ERR_ARG, "%s: %lld windows do not fit the output buffer (%lld)", who, pl.windows, (long long)cap);
-    return WLX_OK;
-}
-
-// the pass itself on v->stream: one launch of each kernel over the packed windows, one download, one wait. v->mu is held.
-static int vad_run_batch(wlx_vad* v, const VadPlan& pl, float* probs_out, float* device_ms_out) {
-    const int T = (int)pl.windows;
-    CK(hipEventRecord(v->ev0, v->stream));
-    hipLaunchKernelGGL(vad_frontend_batch_kernel, dim3(pl.groups), dim3(VAD_FE_THREADS), 0, v->stream, pl.tab, v->W, v->d_gx);
-    hipLaunchKernelGGL(vad_lstm_batch_kernel, dim3(pl.tab.n), dim3(512), 0, v->stream, pl.tab, v->d_gx, v->W.whhP, v->d_hs);
-    hipLaunchKernelGGL(vad_out_kernel, dim3((T + 3) / 4), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, T);
-    CK(hipGetLastError());
-    CK(hipEventRecord(v->ev1, v->stream));
-    CK(hipMemcpyAsync(v->h_probs, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-    CK(hipStreamSynchronize(v->stream));
-    memcpy(probs_out, v->h_probs, (size_t)T * sizeof(float));
-    if (device_ms_out) CK(hipEventElapsedTime(device_ms_out, v->ev0, v->ev1));
-    return WLX_OK;
-}
-
 extern "C" int32_t wlx_vad_probs_batch(wlx_vad* v, const float* pcm, const int64_t* n_samples, const int32_t* extra_zero_windows, int32_t n,
                                        float* probs_out, int64_t cap, int32_t* n_windows_out, float* device_ms_out) {
     if (!v || !pcm || !n_samples || !probs_out || !n_windows_out) return set_error(WLX_ERR_ARG, "wlx_vad_probs_batch: null argument");
