@@ -107,7 +107,7 @@ typedef struct {
  * passes them (transcriber_faster_whisper.py:1380-1407). */
 typedef struct {
     int32_t beam_size;                 /* T=0: 5 ; T>0: 1 */
-    float   patience;                  /* 1 */
+    float   patience;                  /* 1 ; round(beam_size * patience) <= 32, else WLX_ERR_ARG */
     int32_t num_hypotheses;            /* T=0: 1 ; T>0: best_of=5 */
     float   length_penalty;            /* 1 */
     float   repetition_penalty;        /* 1 */
@@ -549,6 +549,14 @@ int32_t wlx_debug_decode_logits(wlx_engine* e, int32_t slot, const int32_t* toke
 int32_t wlx_debug_search(wlx_engine* e, int32_t slot, const float* logits, int32_t steps,
                          const int32_t* prompt, int32_t prompt_len, const wlx_gen_opts* opts,
                          int32_t* tokens_out, int32_t tokens_stride, int32_t* n_tokens_out, float* scores_out);
+/* the same for `batch` items in one call (wlx_debug_search is its batch of one): logits float32 [steps][batch * R][vocab], host,
+ * R = beam_size in beam mode, num_hypotheses when sampling; item b's rows are [b * R, (b + 1) * R). prompts [batch][prompt_stride] as
+ * wlx_generate; outputs tokens_out [batch][NH][tokens_stride], n_tokens_out / scores_out [batch][NH], NH = max(1, num_hypotheses).
+ * WLX_ERR_ARG, with nothing launched and no output written: a null argument, batch < 1 or above the slot's items, steps < 1, and
+ * whatever wlx_generate refuses (rows, prompt length against max_length, tokens outside the vocabulary, options). */
+int32_t wlx_debug_search_batch(wlx_engine* e, int32_t slot, const float* logits, int32_t steps, int32_t batch,
+                               const int32_t* prompts, const int32_t* prompt_lens, int32_t prompt_stride, const wlx_gen_opts* opts,
+                               int32_t* tokens_out, int32_t tokens_stride, int32_t* n_tokens_out, float* scores_out);
 /* time `iters` replays of one full decode step (rows x vocab GEMV chain) with HIP events; returns avg ms */
 int32_t wlx_debug_time_decode_step(wlx_engine* e, int32_t slot, int32_t rows, int32_t t, int32_t iters,
                                    float* avg_ms_out);

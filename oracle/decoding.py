@@ -206,8 +206,13 @@ def sample_token(v: np.ndarray, mx: np.float32, temperature: float, u: np.float3
     return int(pick)
 
 
-def generate(provider: LogitsProvider, prompt: Sequence[int], o: GenOptions, row_base: int = 0) -> GenResult:
-    """One audio item. Mirrors wlx_generate / search.hip."""
+def generate(provider: LogitsProvider, prompt: Sequence[int], o: GenOptions, row_base: int = 0,
+             observer: Optional[Callable[[dict], None]] = None) -> GenResult:
+    """One audio item. Mirrors wlx_generate / search.hip.
+
+    `observer` (tests): called with a dict per beam step — ``step``, ``cands`` (every row's candidates merged and sorted, BEFORE the cut to
+    2 * beam: (score, row, rank, token)), ``is_last`` — and once at the end with ``hyps`` (every finished hypothesis, in the order they
+    finished: (score, tokens)). It sees copies; no result depends on it."""
     ids = o.ids
     prompt = list(prompt)
     plen = len(prompt)
@@ -250,8 +255,10 @@ def generate(provider: LogitsProvider, prompt: Sequence[int], o: GenOptions, row
                     cands.append((sc, b, rank, int(tok)))
             with np.errstate(invalid="ignore"):
                 cands.sort(key=lambda c: (-c[0] if not np.isnan(c[0]) else np.inf, c[1], c[2]))
-            cands = cands[:ncand]
             is_last = step + 1 >= max_new
+            if observer is not None:
+                observer(dict(step=step, cands=list(cands), is_last=is_last))
+            cands = cands[:ncand]
             new_parent, new_tok, new_cum = [], [], []
             top_finished = False
             for k, (sc, b, rank, tok) in enumerate(cands):
@@ -277,6 +284,8 @@ def generate(provider: LogitsProvider, prompt: Sequence[int], o: GenOptions, row
                 hist.append(list(hist[-1])); new_parent.append(new_parent[-1]); new_tok.append(ids.eot); new_cum.append(NEG_INF)
             cum = np.asarray(new_cum, dtype=np.float32)
             feed, parents = new_tok, new_parent
+        if observer is not None:
+            observer(dict(hyps=[(sc, list(t)) for sc, t in hyps]))
         order = sorted(range(len(hyps)), key=lambda i: -hyps[i][0])   # stable: insertion order on ties
         order = order[: o.num_hypotheses]
         return GenResult([hyps[i][1] for i in order], [hyps[i][0] for i in order], no_speech, steps)

@@ -8,7 +8,9 @@ namespace wlx {
 #define WLX_MAX_DEC_ROWS 320  // decoder rows of one step (items x beams): 64 items x 5 beams (round 5: was 64 rows — a slot decoded at most 12 clips per step)
 #define WLX_XSPLIT 8          // key splits of the decode cross-attention (flash-decoding)
 #define WLX_MAX_CAND 32       // 2*beam candidates per row
-#define WLX_MAX_HYP 32        // finished hypotheses kept per item
+#define WLX_MAX_HYP_ASK 32    // the most finished hypotheses a beam search may wait for: round(beam_size * patience) (validate_opts)
+#define WLX_MAX_HYP 48        // finished hypotheses kept per item: up to WLX_MAX_HYP_ASK - 1 before the step that ends the search, and that step adds up to
+                              // one per beam (16): all are ranked (with 32 slots the step that reached the count lost the ones past the store)
 
 // Row tables (device, int32[rows]) describing what each decoder row is in this pass:
 //   token   : token id fed at this row

@@ -7,17 +7,26 @@
 
 using namespace wlx;
 
-extern "C" int32_t wlx_debug_search(wlx_engine* e, int32_t slot, const float* logits, int32_t steps,
-                                    const int32_t* prompt, int32_t prompt_len, const wlx_gen_opts* opts,
-                                    int32_t* tokens_out, int32_t tokens_stride, int32_t* n_tokens_out, float* scores_out) {
+// the production search launches (launch_search, through generate_impl's loop) on caller-supplied logits: `batch` items, rows = batch * R
+// per step, R = beam_size (beam mode) or num_hypotheses (sampling / greedy). Everything is checked before anything is launched or written.
+extern "C" int32_t wlx_debug_search_batch(wlx_engine* e, int32_t slot, const float* logits, int32_t steps, int32_t batch,
+                                          const int32_t* prompts, const int32_t* prompt_lens, int32_t prompt_stride, const wlx_gen_opts* opts,
+                                          int32_t* tokens_out, int32_t tokens_stride, int32_t* n_tokens_out, float* scores_out) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
-    if (!logits || !prompt || !opts) return set_error(WLX_ERR_ARG, "null argument");
+    if (!logits || !prompts || !prompt_lens || !opts || !tokens_out || !n_tokens_out || !scores_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (batch < 1 || batch > s->B) return set_error(WLX_ERR_ARG, "batch %d out of range (slot max %d)", batch, s->B);
+    if (steps < 1) return set_error(WLX_ERR_ARG, "steps %d: at least one step of logits", steps);
     CK(hipSetDevice(e->device));
-    float nsp;
-    return generate_impl(e, s, 1, prompt, &prompt_len, prompt_len, nullptr, opts, true, logits, steps, tokens_out, tokens_stride,
-                         n_tokens_out, scores_out, &nsp);
+    return generate_impl(e, s, batch, prompts, prompt_lens, prompt_stride, nullptr, opts, true, logits, steps, tokens_out, tokens_stride,
+                         n_tokens_out, scores_out, nullptr);
+}
+
+extern "C" int32_t wlx_debug_search(wlx_engine* e, int32_t slot, const float* logits, int32_t steps,
+                                    const int32_t* prompt, int32_t prompt_len, const wlx_gen_opts* opts,
+                                    int32_t* tokens_out, int32_t tokens_stride, int32_t* n_tokens_out, float* scores_out) {
+    return wlx_debug_search_batch(e, slot, logits, steps, 1, prompt, &prompt_len, prompt_len, opts, tokens_out, tokens_stride, n_tokens_out, scores_out);
 }
 
 // ------------------------------------------------------------------------------------------------

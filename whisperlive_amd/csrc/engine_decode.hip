@@ -423,6 +423,8 @@ static int validate_opts(Engine* e, Slot* s, int batch, const wlx_gen_opts* o) {
     if (R < 1 || R > s->R) return set_error(WLX_ERR_ARG, "beam_size/num_hypotheses %d exceeds slot rows per item %d", R, s->R);
     if (!sampling && o->num_hypotheses > o->beam_size) return set_error(WLX_ERR_ARG, "num_hypotheses > beam_size");
     if (!sampling && 2 * o->beam_size > WLX_MAX_CAND) return set_error(WLX_ERR_ARG, "beam_size too large");
+    if (!sampling && std::lround((double)o->beam_size * (double)o->patience) > WLX_MAX_HYP_ASK)
+        return set_error(WLX_ERR_ARG, "beam_size * patience asks for %ld finished hypotheses, the limit is %d", std::lround((double)o->beam_size * (double)o->patience), WLX_MAX_HYP_ASK);
     if (batch * R > s->rows_cap) return set_error(WLX_ERR_ARG, "too many decoder rows");
     if (o->n_suppress_tokens < 0 || (o->n_suppress_tokens > 0 && !o->suppress_tokens)) return set_error(WLX_ERR_ARG, "bad suppress_tokens");
     return WLX_OK;

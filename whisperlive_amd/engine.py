@@ -456,6 +456,31 @@ class Slot:
         seqs = [toks[h, :nt[h]].tolist() for h in range(nh) if np.isfinite(sc[h])]
         return GenerationResult(seqs, [float(x) for x in sc if np.isfinite(x)], 0.0)
 
+    def debug_search_batch(self, logits: np.ndarray, prompts: Sequence[Sequence[int]], ids: TokenIds, **kw) -> List[GenerationResult]:
+        """`debug_search` for len(prompts) items in one call: logits [steps, items * R, V], item b's rows are [b * R, (b + 1) * R)
+        (R = beam_size in beam mode, num_hypotheses when sampling)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        d = dict(beam_size=5, patience=1.0, num_hypotheses=1, length_penalty=1.0, repetition_penalty=1.0,
+                 no_repeat_ngram_size=0, max_length=448, suppress_blank=True, suppress_tokens=(),
+                 max_initial_timestamp_index=50, sampling_topk=0, sampling_temperature=0.0, seed=0)
+        d.update(kw)
+        o, keep = self._opts(ids, **d)
+        batch = len(prompts)
+        stride = max(len(p) for p in prompts)
+        pr = np.zeros((batch, stride), dtype=np.int32)
+        pl = np.zeros(batch, dtype=np.int32)
+        for i, p in enumerate(prompts):
+            pr[i, :len(p)] = p
+            pl[i] = len(p)
+        nh = max(1, int(d["num_hypotheses"]))
+        toks = np.zeros((batch, nh, 448), dtype=np.int32)
+        nt = np.zeros((batch, nh), dtype=np.int32)
+        sc = np.zeros((batch, nh), dtype=np.float32)
+        check(self.lib.wlx_debug_search_batch(self.engine._h, self.sid, _f32p(logits), logits.shape[0], batch, _i32p(pr), _i32p(pl), stride,
+                                              C.byref(o), _i32p(toks), 448, _i32p(nt), _f32p(sc)))
+        return [GenerationResult([toks[b, h, :nt[b, h]].tolist() for h in range(nh) if np.isfinite(sc[b, h])],
+                                 [float(sc[b, h]) for h in range(nh) if np.isfinite(sc[b, h])], 0.0) for b in range(batch)]
+
     def debug_time_decode_step(self, rows: int, t: int, iters: int = 50) -> float:
         ms = C.c_float(0)
         check(self.lib.wlx_debug_time_decode_step(self.engine._h, self.sid, rows, t, iters, C.byref(ms)))
