@@ -43,6 +43,11 @@ EXPORTS = [
 # a v_accvgpr_write per register: a third of all VALU instructions of the encoder attention kernel (576 of 1738 per six key
 # tiles), which is VALU-issue bound (rocprofv3: SQ_ACTIVE_INST_VALU 56 % of its wave cycles). No kernel spills with it.
 HIPCC_EXTRA = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+# Kernel-argument preload (csrc/dec_gemv_internal.h, WLX_KERNARG_HEAD): the command processor places the leading kernel-argument dwords into user SGPRs
+# at dispatch. The translation units of the decode step's kernels only (the vocabulary projection's not yet: it takes one struct) — their launches last 2 us each, an argument fetch is a tenth of that; the encoder, VAD, MT
+# and speaker kernels run 15-30 us launches and keep their flags. A build with -DWLX_KERNARG_HEAD=0 (the previous argument layout) leaves it out.
+KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
+KERNARG_PRELOAD_SOURCES = ("dec_gemv.hip", "decoder.hip", "search.hip")   # (decoder.hip, search.hip: flat argument lists as they stand)
 
 
 class WlxError(RuntimeError):
@@ -142,6 +147,7 @@ class wlx_mt_gen_opts(C.Structure):
 
 
 _extra_ok = None
+_preload_ok = None
 
 
 def _hipcc() -> str:
@@ -156,8 +162,10 @@ def _compile(out: Path, defines=(), verbose: bool = False, force: bool = False) 
     csrc/.obj/<variant>/ and rebuilt when the source or any header is newer), linked into a temporary file and renamed
     (concurrent builders never see a half-written library). HIPCC_EXTRA is a hidden LLVM option: a hipcc that does not know
     it fails with 'Unknown command line argument' — retry once without it (the AGPR-form build: correct, the encoder
-    attention ~8 % slower) and remember the answer for the other builds of this process."""
-    global _extra_ok
+    attention ~8 % slower) and remember the answer for the other builds of this process. KERNARG_PRELOAD is decided on its own:
+    a hipcc that rejects only that option keeps HIPCC_EXTRA, says so, and builds the argument head without the preload (correct:
+    the kernels fetch the head themselves; the decode step loses log K1's gain)."""
+    global _extra_ok, _preload_ok
     from concurrent.futures import ThreadPoolExecutor
     hipcc = _hipcc()
     defines = list(defines)
@@ -165,18 +173,21 @@ def _compile(out: Path, defines=(), verbose: bool = False, force: bool = False) 
     hdr_time = max(h.stat().st_mtime for h in hdrs)
     base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + [f"-D{d}" for d in defines]
 
-    def objects(extra):
-        tag = "_".join(["base" if extra else "agpr"] + [d.replace("=", "-") for d in defines])
+    want_pre = "WLX_KERNARG_HEAD=0" not in defines
+
+    def objects(extra, preload):
+        tag = "_".join(["base" if extra else "agpr"] + (["nopre"] if want_pre and not preload else []) + [d.replace("=", "-") for d in defines])
         odir = CSRC / ".obj" / tag
         odir.mkdir(parents=True, exist_ok=True)
 
         def one(src):
-            obj = odir / (src + ".o")
+            pre = KERNARG_PRELOAD if (preload and src in KERNARG_PRELOAD_SOURCES) else []
+            obj = odir / (src + (".pre.o" if pre else ".o"))       # (the option is part of the cached object's name: the list of sources that get it may change)
             sp = CSRC / src
             if not force and obj.exists() and obj.stat().st_mtime >= max(sp.stat().st_mtime, hdr_time):
                 return obj, None           # (force=True: a new hipcc / ROCm or changed flags must not link stale objects)
             tmp = obj.with_name(obj.name + f".tmp{os.getpid()}")
-            proc = subprocess.run(base + extra + ["-c", str(sp), "-o", str(tmp)], capture_output=True, text=True)
+            proc = subprocess.run(base + extra + pre + ["-c", str(sp), "-o", str(tmp)], capture_output=True, text=True)
             if verbose and (proc.stdout or proc.stderr):
                 print(proc.stdout, proc.stderr)
             if proc.returncode != 0:
@@ -188,12 +199,16 @@ def _compile(out: Path, defines=(), verbose: bool = False, force: bool = False) 
         with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4)) as ex:
             return list(ex.map(one, SOURCES))
 
-    for extra in ([HIPCC_EXTRA, []] if _extra_ok is not False else [[]]):
-        res = objects(extra)
+    for _attempt in range(3):
+        extra = HIPCC_EXTRA if _extra_ok is not False else []
+        preload = want_pre and _preload_ok is not False
+        res = objects(extra, preload)
         bad = [p for o, p in res if o is None]
         if not bad:
             if extra:
                 _extra_ok = True
+            if preload:
+                _preload_ok = True
             tmp = out.with_name(out.name + f".tmp{os.getpid()}")
             proc = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(tmp)] + [str(o) for o, _ in res],
                                   capture_output=True, text=True)
@@ -204,9 +219,16 @@ def _compile(out: Path, defines=(), verbose: bool = False, force: bool = False) 
             os.replace(tmp, out)
             return out
         err = bad[0].stderr
-        if extra and ("Unknown command line argument" in err or "unknown argument" in err.lower()):
-            _extra_ok = False
-            print(f"[wlx build] this hipcc rejects {' '.join(HIPCC_EXTRA)}: building with MFMA accumulators in AGPR form")
+        if (extra or preload) and ("Unknown command line argument" in err or "unknown argument" in err.lower()):
+            # the error names the option it does not know; where it names neither, both go
+            no_pre = preload and (KERNARG_PRELOAD[1].split("=")[0] in err or HIPCC_EXTRA[1].split("=")[0] not in err)
+            no_extra = bool(extra) and (HIPCC_EXTRA[1].split("=")[0] in err or KERNARG_PRELOAD[1].split("=")[0] not in err)
+            if no_pre:
+                _preload_ok = False
+                print(f"[wlx build] this hipcc rejects {' '.join(KERNARG_PRELOAD)}: the decode projections fetch their argument head themselves")
+            if no_extra:
+                _extra_ok = False
+                print(f"[wlx build] this hipcc rejects {' '.join(HIPCC_EXTRA)}: building with MFMA accumulators in AGPR form")
             continue
         raise WlxError(f"hipcc failed ({bad[0].returncode}):\n{err[-4000:]}")
     raise WlxError("hipcc failed")
@@ -236,6 +258,12 @@ def build_variant(name: str, defines) -> Path:
     four K slices; -DWLX_RESID_BATCHED=0, the encoder's tile-by-tile residual update); selected at run time with WLX_LIB=<path>."""
     out = PKG_DIR / name
     return out if _fresh(out) else _compile(out, list(defines))
+
+
+def build_nohead() -> Path:
+    """libwlx_nohead.so: -DWLX_KERNARG_HEAD=0 — the decode projections with their arguments in one by-value struct and no kernel-argument
+    preload (the layout before the argument head): the A/B partner of libwlx.so for that change. Select with WLX_LIB=<path>."""
+    return build_variant("libwlx_nohead.so", ["WLX_KERNARG_HEAD=0"])
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:

@@ -395,7 +395,7 @@ __device__ __forceinline__ void stage_rows_f16_wave(const half_t* __restrict__ X
 template <int CH, int LNV, int IN, int OUT, int NTB, int MT, int XS>
 // (<= 8 waves wherever the kernel holds more than one row tile of fragments: 256 VGPRs per lane — at 16 waves the
 // two- and three-tile residual projections spilled, 36-180 bytes of scratch per lane)
-__global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1 || CH > 6 || IN == GEMV_IN_XATTN) ? 512 : 1024) void dec_gemv2_kernel(GemvParams p_in) {
+__global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1 || CH > 6 || IN == GEMV_IN_XATTN) ? 512 : 1024) void dec_gemv2_kernel(WLX_G2_HEAD_PARAMS GemvParams p_in) {
     // Row chunks (prompt prefill, round 3): a pass over up to 448 rows runs every projection as ONE launch whose grid.z walks
     // chunks of 48 rows (three MFMA row tiles, the widest this kernel holds); a chunk is this kernel on rebased row pointers.
     // Decode steps launch with Mtot = 0 and skip the block (a scalar branch).
@@ -406,19 +406,74 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
     // workgroup) made every one of the N / 16 workgroups normalise / stage ALL rows on N / 16 CUs (60 rows, d_model 768:
     // 7.1 us per residual projection at 0.04 of the HBM peak); row tiles spread the same work over 4x the CUs.
     GemvParams p = p_in;
+#if WLX_KERNARG_HEAD
+    // The argument head (dec_gemv_internal.h GemvHead): what the first trip of loads and the weight request need arrives in SGPRs with the wave. Nothing in
+    // front of the weight request reads a field that only the struct holds, so the first wait on the scalar counter stands behind it. (Where hipcc puts
+    // the struct's own scalar fetch is its choice: in the rows + slabs form it issues it behind the activation and weight requests, not at entry.)
+    p.Wp = h_wp; p.gamma = h_gamma; p.beta = h_beta;
+    p.M = h_dims & 0xff; p.nwm = (h_dims >> 8) & 0xff; p.KTW = (h_dims >> 16) & 0xff; p.xstage = (h_dims >> 24) & 1;
+    p.KT = h_kt & 0xff; p.KTS = (h_kt >> 8) & 0xff; p.K = p.KT * 32;          // (gemv2_cfg: K == 32 KT)
+    const int h_mtot = (int)((unsigned)h_kt >> 16);
+    if constexpr (IN == GEMV_IN_LN) {
+        if constexpr (XS != GEMV_X_EMBED) { p.X = static_cast<const float*>(h_rows); p.ldx = h_ld; }
+        if constexpr (XS == GEMV_X_SLABS) { p.slab = const_cast<float*>(static_cast<const float*>(h_aux)); p.slab_stride = h_aux_i; }
+    } else if constexpr (IN == GEMV_IN_F16) {
+        p.Xh = static_cast<const half_t*>(h_rows); p.ldxh = h_ld;
+    } else {
+        p.part_o = static_cast<const half_t*>(h_rows); p.part_ml = static_cast<const float*>(h_aux); p.R = h_aux_i & 0xffff; p.H = h_aux_i >> 16;
+    }
+#else
+    const int h_mtot = p_in.Mtot;
+#endif
     int tile = blockIdx.x;
-    if (p_in.Mtot > 0) {
+#if WLX_KERNARG_HEAD
+    int row0 = 0;
+#endif
+    if (h_mtot > 0) {
+#if WLX_KERNARG_HEAD
+        // The chunk fields are read where they are used, through the kernel-argument pointer and behind a compile-time fence: as fields of p_in hipcc
+        // hoists their scalar fetch above this branch, and a decode step, which never takes it, then waits for that fetch before it may reuse the
+        // destination registers — in front of its first trip's loads.
+        const __attribute__((address_space(4))) char* ka = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        const __attribute__((address_space(4))) GemvParams& pc = *reinterpret_cast<const __attribute__((address_space(4))) GemvParams*>(ka + sizeof(GemvHead));
+#else
+        const GemvParams& pc = p_in;
+#endif
+        const int c_nz = pc.rt_nz, c_magic = pc.rt_magic, c_tiles = pc.rt_tiles, c_chunk = pc.chunk, c_mtot = pc.Mtot;
         int zc = (int)blockIdx.z;
-        if (p_in.rt_nz > 0) {
+        if (c_nz > 0) {
             const int lin = (int)blockIdx.x, t = lin >> 3;
-            const int tq = (int)(((unsigned)t * (unsigned)p_in.rt_magic) >> 16);      // t / rt_nz (host: magic = 65536 / nz + 1, exact for t < 32768)
-            zc = t - tq * p_in.rt_nz;
+            const int tq = (int)(((unsigned)t * (unsigned)c_magic) >> 16);            // t / rt_nz (host: magic = 65536 / nz + 1, exact for t < 32768)
+            zc = t - tq * c_nz;
             tile = tq * 8 + (lin & 7);
-            if (tile >= p_in.rt_tiles) return;                                        // (the tile count is padded to a multiple of 8)
+            if (tile >= c_tiles) return;                                              // (the tile count is padded to a multiple of 8)
         }
-        const int CHK = p_in.chunk;
+        const int CHK = c_chunk;
         const int r0 = zc * CHK;
-        p.M = (p_in.Mtot - r0 < CHK) ? p_in.Mtot - r0 : CHK;
+        p.M = (c_mtot - r0 < CHK) ? c_mtot - r0 : CHK;
+#if WLX_KERNARG_HEAD
+        row0 = r0;
+    }
+    {
+        // (with the argument head the rebase stands OUTSIDE the branch, by a row offset that is 0 for a decode step, and tests no pointer: inside the
+        // branch, or behind a test, every pointer of the struct is a value merged behind a branch, and the merge waits for the struct's scalar
+        // fetch in front of the first trip's loads. A pointer the form does not use is moved and never read.)
+        // The pointers the head holds, and the row tables of the embedding gather, move here; the struct's other pointers move where the epilogue
+        // operands are requested (rebase_late): scalar arithmetic on a struct field up here is one more wait in front of the first loads.
+        const long r0 = row0;
+        p.X += r0 * p.ldx; p.Xh += r0 * p.ldxh;
+        if constexpr (IN == GEMV_IN_LN) p.slab += r0 * p.ldx;
+        if constexpr (XS == GEMV_X_EMBED) { p.emb_token += r0; p.row_cache += r0; p.row_pos += r0; }
+    }
+    auto rebase_late = [&]() {
+        long r0 = row0;
+        asm volatile("" : "+s"(r0));            // (an opaque value: the products below are otherwise computed once, above both ways to load_weights)
+        p.Yh += r0 * p.ldyh; p.Y += r0 * p.ldy; p.Xres += r0 * p.ldxres;
+        if constexpr (IN != GEMV_IN_LN) p.slab += r0 * p.ldxres;
+        if constexpr (XS != GEMV_X_EMBED) { p.row_cache += r0; p.row_pos += r0; }
+    };
+#else
         if (p.emb_token) p.emb_token += r0;
         if (p.X) p.X += (long)r0 * p.ldx;
         if (p.Xh) p.Xh += (long)r0 * p.ldxh;
@@ -429,6 +484,7 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
         if (p.row_cache) p.row_cache += r0;
         if (p.row_pos) p.row_pos += r0;
     }
+#endif
     static_assert(XS == GEMV_X_PLAIN || IN == GEMV_IN_LN || (IN == GEMV_IN_F16 && OUT == GEMV_OUT_RESID && NTB == 1),
                   "slab / embedding sources: LayerNorm prologue or residual epilogue only");
     static_assert(OUT != GEMV_OUT_SLAB || (IN == GEMV_IN_F16 && NTB == 1), "K-split form: fp16 rows in");
@@ -461,6 +517,41 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
     const half_t* wp = p.Wp + ((long)(tile * NTB) * p.KT + kw0) * 512 + lane * 8;
     const long wstep = (long)p.KT * 512;                                   // next n-tile
     f16x8 wf[CH][NTB];
+    // epilogue operands of the FIRST pair this wave finishes (pair = wave: n-tile pair / MT, row tile pair % MT),
+    // requested now (every lane, clamped row: no branch around a load); further pairs (batched rows) load theirs late
+    int crow[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) crow[mt] = (mt * 16 + c < p.M) ? mt * 16 + c : p.M - 1;
+    const int pair0 = (wave < NP) ? wave : 0;
+    const int nt_e = tile * NTB + pair0 / MT;
+    const int n_e = nt_e * 16 + g * 4;
+    int row_e = (pair0 % MT) * 16 + c;
+    if (row_e >= p.M) row_e = p.M - 1;
+    float4 bias_e = make_float4(0.f, 0.f, 0.f, 0.f), res_e = bias_e;
+    int rc_e = 0, rp_e = 0;
+    float4 slab_e[(OUT == GEMV_OUT_RESID && XS == GEMV_X_SLABS) ? WLX_FC2_KS : 1];
+    auto load_epilogue_operands = [&]() {
+        int row_q = row_e;
+#if WLX_KERNARG_HEAD
+        rebase_late();
+        asm volatile("" : "+v"(row_q));         // (opaque, as the row offset of rebase_late: the row's byte offset is not computed above the first loads)
+#endif
+        if constexpr (OUT != GEMV_OUT_F32) bias_e = *reinterpret_cast<const float4*>(p.bias + n_e);
+        if constexpr (OUT == GEMV_OUT_RESID) res_e = *reinterpret_cast<const float4*>(p.Xres + (long)row_q * p.ldxres + n_e);
+        if constexpr (OUT == GEMV_OUT_QKV) { rc_e = p.row_cache[row_q]; rp_e = p.row_pos[row_q]; }
+        if constexpr (OUT == GEMV_OUT_RESID && XS == GEMV_X_SLABS) {       // the residual is rows + slabs (summed at the store)
+#pragma unroll
+            for (int sl = 0; sl < WLX_FC2_KS; ++sl)
+                slab_e[sl] = *reinterpret_cast<const float4*>(p.slab + sl * p.slab_stride + (long)row_q * p.ldxres + n_e);
+        }
+        if constexpr (OUT == GEMV_OUT_SLAB) { if (blockIdx.y != 0) bias_e = make_float4(0.f, 0.f, 0.f, 0.f); }   // the bias once: slice 0
+    };
+    // Their addresses come from the struct. With the argument head they are requested BEHIND the weight stream (load_weights), so that the wait for
+    // the struct's scalar fetch stands behind the first trip's loads and the weight request instead of in front of them; vmcnt retires in order and
+    // the epilogue needs the weights' MFMAs first, so nothing waits longer for it.
+#if !WLX_KERNARG_HEAD
+    load_epilogue_operands();
+#endif
     // The weight stream is requested AFTER the activation loads have been issued (round 2): vmcnt retires in order, so with the weights first the wave's wait for its few activation
     // loads (L2) was a wait for its whole weight slice (HBM) as well, and the LayerNorm / staging / combine that must
     // precede the MFMAs started only once the weights had landed (decode-step trace: "LN done" 1.4 us into a 2.2 us
@@ -477,30 +568,12 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
         for (int j = 0; j < CH; ++j)
 #pragma unroll
             for (int i = 0; i < NTB; ++i) wf[j][i] = ld_nt_f16x8(wq + i * is + j * js);
+#if WLX_KERNARG_HEAD
+        asm volatile("" ::: "memory");          // (the epilogue operands stay behind the weight requests: see load_epilogue_operands;
+        __builtin_amdgcn_sched_barrier(0);      //  so does their scalar address arithmetic, which the scheduler otherwise lifts in front of the first loads)
+        load_epilogue_operands();
+#endif
     };
-
-    // epilogue operands of the FIRST pair this wave finishes (pair = wave: n-tile pair / MT, row tile pair % MT),
-    // requested now (every lane, clamped row: no branch around a load); further pairs (batched rows) load theirs late
-    int crow[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) crow[mt] = (mt * 16 + c < p.M) ? mt * 16 + c : p.M - 1;
-    const int pair0 = (wave < NP) ? wave : 0;
-    const int nt_e = tile * NTB + pair0 / MT;
-    const int n_e = nt_e * 16 + g * 4;
-    int row_e = (pair0 % MT) * 16 + c;
-    if (row_e >= p.M) row_e = p.M - 1;
-    float4 bias_e = make_float4(0.f, 0.f, 0.f, 0.f), res_e = bias_e;
-    int rc_e = 0, rp_e = 0;
-    if constexpr (OUT != GEMV_OUT_F32) bias_e = *reinterpret_cast<const float4*>(p.bias + n_e);
-    if constexpr (OUT == GEMV_OUT_RESID) res_e = *reinterpret_cast<const float4*>(p.Xres + (long)row_e * p.ldxres + n_e);
-    if constexpr (OUT == GEMV_OUT_QKV) { rc_e = p.row_cache[row_e]; rp_e = p.row_pos[row_e]; }
-    float4 slab_e[(OUT == GEMV_OUT_RESID && XS == GEMV_X_SLABS) ? WLX_FC2_KS : 1];
-    if constexpr (OUT == GEMV_OUT_RESID && XS == GEMV_X_SLABS) {           // the residual is rows + slabs (summed at the store)
-#pragma unroll
-        for (int sl = 0; sl < WLX_FC2_KS; ++sl)
-            slab_e[sl] = *reinterpret_cast<const float4*>(p.slab + sl * p.slab_stride + (long)row_e * p.ldxres + n_e);
-    }
-    if constexpr (OUT == GEMV_OUT_SLAB) { if (blockIdx.y != 0) bias_e = make_float4(0.f, 0.f, 0.f, 0.f); }   // the bias once: slice 0
 
     f32x4 acc[NTB][MT];
 #pragma unroll
@@ -1014,14 +1087,41 @@ void lds_optin(const void* kernel, std::atomic<signed char> (&granted)[64], cons
     g_lds_optin_refused.store(true);
     fprintf(stderr, "[wlx] device %d refused %d KiB of dynamic LDS (%s): %s to the general kernel\n", dev, WLX_G2_LDS_MAX / 1024, hipGetErrorString(e), what);
 }
+// the argument head of a launch (dec_gemv_internal.h): every slot repeats a field of p, chosen by the input form as the kernel reads it back
+static bool g2_head_fits(const GemvParams& p) {
+    const long lim = 0x7fffffffL;
+    return p.KT >= 0 && p.KT <= 255 && p.KTS >= 0 && p.KTS <= 255 && p.Mtot >= 0 && p.Mtot <= 65535 && p.M >= 0 && p.M <= 255 &&
+           p.ldx >= 0 && p.ldx <= lim && p.ldxh >= 0 && p.ldxh <= lim && p.slab_stride >= 0 && p.slab_stride <= lim &&
+           (p.in_mode != GEMV_IN_XATTN || (p.R >= 0 && p.R <= 0xffff && p.H >= 0 && p.H <= 0x7fff));
+}
+bool g2_head(const GemvParams& p, GemvHead* h) {
+    if (!g2_head_fits(p) || p.nwm < 0 || p.nwm > 255 || p.KTW < 0 || p.KTW > 255) return false;
+    *h = GemvHead{};
+    h->gamma = p.gamma; h->beta = p.beta; h->wp = p.Wp;
+    h->dims = p.M | (p.nwm << 8) | (p.KTW << 16) | ((p.xstage ? 1 : 0) << 24);
+    h->kt = p.KT | (p.KTS << 8) | (int)((unsigned)p.Mtot << 16);
+    if (p.in_mode == GEMV_IN_LN) {
+        if (p.xsrc != GEMV_X_EMBED) { h->rows = p.X; h->ld = (int)p.ldx; }      // (embedding rows: a dependent gather through the struct's tables)
+        if (p.xsrc == GEMV_X_SLABS) { h->aux = p.slab; h->aux_i = (int)p.slab_stride; }
+    } else if (p.in_mode == GEMV_IN_F16) {
+        h->rows = p.Xh; h->ld = (int)p.ldxh;
+    } else {
+        h->rows = p.part_o; h->aux = p.part_ml; h->aux_i = p.R | (p.H << 16);
+    }
+    return true;
+}
 // one launch of an instantiation
 template <int CH, int LNV, int IN, int OUT, int NTB, int MT, int XS>
 static void g2_launch(dim3 grid, dim3 block, size_t shm, hipStream_t s, const GemvParams& p) {
+#if WLX_KERNARG_HEAD
+    GemvHead h;
+    if (!g2_head(p, &h)) { dispatch_bug("dec_gemv2_kernel (argument head)", s); return; }
+#endif
     if (shm > 64 * 1024) {
         static std::atomic<signed char> granted[64] = {};
         lds_optin(reinterpret_cast<const void*>(&dec_gemv2_kernel<CH, LNV, IN, OUT, NTB, MT, XS>), granted, "batched decode projections fall back");
     }
-    hipLaunchKernelGGL((dec_gemv2_kernel<CH, LNV, IN, OUT, NTB, MT, XS>), grid, block, shm, s, p);
+    hipLaunchKernelGGL((dec_gemv2_kernel<CH, LNV, IN, OUT, NTB, MT, XS>), grid, block, shm, s, WLX_G2_HEAD_ARGS(h) p);
 }
 void dispatch_bug(const char* kernel, hipStream_t s) {
     fprintf(stderr, "[wlx] launch_dec_gemv: no %s instantiation for a configuration its probe accepted\n", kernel);
@@ -1150,6 +1250,9 @@ static Gemv2Cfg gemv2_cfg(const GemvParams& p) {
                        (p.in_mode != GEMV_IN_LN && p.out_mode == GEMV_OUT_RESID) ||
                        (p.in_mode == GEMV_IN_F16 && p.out_mode == GEMV_OUT_SLAB);
     if (!combo || p.K != p.KT * 32) return c;
+#if WLX_KERNARG_HEAD
+    if (!g2_head_fits(p)) return c;                                           // (a field past its slot of the argument head: no Whisper shape)
+#endif
     // sources other than the plain rows: one row tile, and only where the kernel is instantiated for them
     if (p.xsrc != GEMV_X_PLAIN) {
         const bool ln_ok = p.in_mode == GEMV_IN_LN && p.out_mode == GEMV_OUT_QKV;
@@ -1244,15 +1347,19 @@ static bool gemv2_ok(const GemvParams& p, Gemv2Cfg* out) {
     if (out) *out = c;
     return true;
 }
+// the fields the launcher derives from the configuration (what the kernel, and its argument head, read back)
+static void gemv2_launch_fields(GemvParams& p, const Gemv2Cfg& c) {
+    p.KTW = c.CH * c.NCH; p.NCH = c.NCH; p.xstage = c.xstage ? 1 : 0; p.nwm = c.nw;
+    if (p.Mtot > 0 && p.chunk <= 0) p.chunk = 48;
+}
 static void gemv2_launch(const GemvParams& p0, const Gemv2Cfg& c, hipStream_t s) {
     GemvParams p = p0;
-    p.KTW = c.CH * c.NCH; p.NCH = c.NCH; p.xstage = c.xstage ? 1 : 0; p.nwm = c.nw;
+    gemv2_launch_fields(p, c);
 #ifdef WLX_TRACE
     { static thread_local char nm[512][48]; const int q = g_trace_seq < 512 ? g_trace_seq : 511;
       snprintf(nm[q], 48, "gemv2<%d,%d,%d> N%d K%d", p.in_mode, p.out_mode, p.xsrc, p.N, p.K); p.trc = trace_next(nm[q]); }
 #endif
     const int NT_total = (p.N + 15) / 16;
-    if (p.Mtot > 0 && p.chunk <= 0) p.chunk = 48;
     dim3 grid((NT_total + c.NTB - 1) / c.NTB, p.out_mode == GEMV_OUT_SLAB ? p.KT / p.KTS : 1, p.Mtot > 0 ? (p.Mtot + p.chunk - 1) / p.chunk : 1), block(c.nw * 64);
     if (p.Mtot > 0 && p.rt_nz > 0) {       // row tiles folded into x (see dec_gemv2_kernel)
         p.rt_tiles = (int)grid.x;
@@ -1335,6 +1442,15 @@ static void gemv_dispatch_in(const GemvParams& p, dim3 grid, dim3 block, size_t 
     }
 }
 
+bool dec_gemv_head(const GemvParams& p_any, GemvHead* h, GemvParams* launched) {
+    if (vocab2_ok(p_any)) return false;
+    GemvParams p = gemv_chunked(p_any);
+    Gemv2Cfg c;
+    if (!gemv2_ok(p, &c)) return false;
+    gemv2_launch_fields(p, c);
+    *launched = p;
+    return g2_head(p, h);
+}
 bool dec_gemv_is_lean(const GemvParams& p) { return vocab2_ok(p) || gemv2_ok(gemv_chunked(p), nullptr); }
 
 // the name leaf of gemv2_dispatch (the vocabulary projection names itself): the template arguments of the instantiation launch_dec_gemv runs, not a
