@@ -403,6 +403,41 @@ void    wlx_ring_destroy(wlx_ring* r);
 int32_t wlx_ring_append(wlx_ring* r, const float* samples, int64_t n, int64_t max_resident, int64_t trim,
                         int64_t* dropped_out, int64_t* base_out, int64_t* resident_out);
 int32_t wlx_ring_state(wlx_ring* r, int64_t* base_out, int64_t* resident_out);
+/* ---- live sessions at any served sample rate (PRODUCT entry points of the streaming path) ----
+ * A ring may be given a WIRE FORMAT once, before the first append: the client's packets then cross PCIe as they came off the socket
+ * and are converted, down-mixed and resampled to 16 kHz on the device, packet by packet, by the kernel of wlx_pcm_put_frames.
+ * sample_format: WLX_PCM_F32, WLX_PCM_S16, or one of the 8-bit formats below (code 2 is unassigned; the FILE entry points —
+ * wlx_pcm_put_frames, wlx_pcm_put_frames_split, wlx_debug_resample* — keep taking F32 and S16 only). channels 1..WLX_PCM_MAX_CHANNELS,
+ * down-mixed as the file path does (float32 mean, channels added in order, one division); sample_rate under the RATES rule of
+ * wlx_pcm_put_frames. WLX_ERR_ARG: an unknown format, a bad channel count, an unserved rate. WLX_ERR_STATE: a ring that has a format
+ * already or has been appended to. A refusal changes nothing. */
+#define WLX_PCM_U8    3   /* (x - 128) / 128 */
+#define WLX_PCM_MULAW 4   /* G.711 mu-law -> its 16-bit linear value / 32768 */
+#define WLX_PCM_ALAW  5   /* G.711 A-law  -> its 16-bit linear value / 32768 */
+int32_t wlx_ring_set_format(wlx_ring* r, int32_t sample_format, int32_t channels, int32_t sample_rate);
+/* The streaming append of a ring with a format: `frames` = n_frames interleaved frames in the wire format (host). With J input frames
+ * seen so far and M outputs in the stream, the call appends the outputs m in [M, M') at absolute positions m, J' = J + n_frames:
+ *   flush == 0: every output whose newest input exists, floor((half_len + m * down) / up) <= J' - 1;
+ *   flush != 0: M' = ceil(J' * up / down), the one-shot length, inputs past the end being zero; the stream is then CLOSED and
+ *               further appends give WLX_ERR_STATE.
+ * For ANY cutting of a stream into packets (empty ones, one-frame ones, ones shorter than the filter's reach) followed by a flush, the
+ * concatenation of what the calls appended is BIT-IDENTICAL to wlx_pcm_put_frames / wlx_debug_resample of the concatenated frames:
+ * same taps, same float32 accumulation order per output, zeros in front of the stream; no emitted sample is ever revised. At 16 kHz
+ * in, the call converts and down-mixes only (M' = J').
+ * The trim rule (max_resident, trim) is applied BEFORE the append exactly as in wlx_ring_append; dropped / base / resident are in
+ * 16 kHz samples. new_out (nullable, `cap` floats): the call's M' - M new samples, copied to the host in the same wait (the session's
+ * host mirror stays sample for sample with the ring); cap < M' - M is refused before any launch, nothing changed. *n_new_out = M' - M.
+ * State of a stream: J, M, the last ceil(2 * half_len / up) + 2 input frames (device) and a staging buffer for [tail | packet], grown
+ * on demand. The copy is complete on return; calls are serialised by the ring's mutex; the ring's own stream, never the null stream;
+ * readers are waited for only where data moves under them. wlx_ring_append on a ring with a format is WLX_ERR_STATE; this call on a
+ * ring without one is WLX_ERR_STATE. */
+int32_t wlx_ring_append_frames(wlx_ring* r, const void* frames, int64_t n_frames, int32_t flush,
+                               int64_t max_resident, int64_t trim,
+                               float* new_out, int64_t cap, int64_t* n_new_out,
+                               int64_t* dropped_out, int64_t* base_out, int64_t* resident_out);
+/* Host only (no device work, like wlx_vad_segments): M' of the stream form as a function of J' = frames_seen alone. WLX_ERR_ARG for an
+ * unserved rate or a negative count. */
+int32_t wlx_resample_stream_count(int32_t sample_rate, int64_t frames_seen, int32_t flush, int64_t* n_out);
 /* wlx_vad_probs on ring samples [start, start + n): no host-to-device copy. Same contract otherwise (zero initial
  * state, ceil(n / 512) windows, the last one zero-padded) plus `extra_zero_windows` all-zero windows behind them
  * (faster_whisper.vad pads n to the NEXT multiple of 512 — a whole window of zeros when n already is one — and the
@@ -731,6 +766,17 @@ int32_t wlx_debug_resample_split(int32_t device, const void* frames, int64_t n_f
 int32_t wlx_debug_resample_timed(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
                                  int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out,
                                  float* kernel_ms_out);
+
+/* The stream form of the same kernel (wlx_ring_append_frames) without an engine: a fresh stream state is fed the packets [0, cuts[0]),
+ * [cuts[0], cuts[1]), ... [cuts[n_cuts - 1], n_frames) — n_cuts + 1 calls; cuts ascending, repeated values give empty packets — each
+ * call waited for as the product call is. flush = 0: no flush; 1: one more call, an empty flushing packet; 2: the LAST packet carries the
+ * flush (data and flush in the same call). All five sample formats. `out` (cap floats) is copied in AND out; *n_out = outputs emitted;
+ * per_call_counts (nullable): n_cuts + 1 entries, one more when flush == 1. WLX_ERR_ARG before any launch: what wlx_ring_set_format
+ * refuses, cuts out of order or past n_frames, cap below the total the planner gives. */
+int32_t wlx_debug_resample_stream(int32_t device, const void* frames, int64_t n_frames, int32_t channels,
+                                  int32_t sample_format, int32_t sample_rate,
+                                  const int64_t* cuts, int32_t n_cuts, int32_t flush,
+                                  float* out, int64_t cap, int64_t* n_out, int64_t* per_call_counts);
 
 /* The FLAC frame decoder and the finish kernel (csrc/flac.hip, csrc/flac_core.h) without the resampler, on a private stream of `device`:
  * the stream's decoded INTEGER samples, interleaved [n][channels], nothing scaled or resampled; *n_frames_out = n (samples per

@@ -22,7 +22,7 @@ EXPORTS = [
     "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_put_frames_split", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_put_flac_split", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
     "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_align_batch", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
-    "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
+    "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_ring_set_format", "wlx_ring_append_frames", "wlx_resample_stream_count", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
     "wlx_logmel_chunks", "wlx_logmel_chunks_multi", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
     "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch", "wlx_spk_embed_pcm_batch", "wlx_spk_embed_ring_batch",
@@ -33,7 +33,7 @@ EXPORTS = [
     "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
     "wlx_debug_dec_gemv", "wlx_debug_dec_cq_cross_attn",
-    "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_flac_decode", "wlx_debug_flac_timings",
+    "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_resample_stream", "wlx_debug_flac_decode", "wlx_debug_flac_timings",
     "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings",
 ]
 
@@ -118,6 +118,7 @@ ERR_ARG = 1             # wlx_status WLX_ERR_ARG
 ERR_STATE = 4           # wlx_status WLX_ERR_STATE
 LM_MAXRANGES = 256      # wlx.h WLX_LM_MAXRANGES: ranges per chunk of wlx_logmel_chunks / wlx_logmel_ring
 PCM_F32, PCM_S16 = 0, 1           # wlx.h WLX_PCM_F32 / WLX_PCM_S16
+PCM_U8, PCM_MULAW, PCM_ALAW = 3, 4, 5   # wlx.h WLX_PCM_U8 / _MULAW / _ALAW: the live path's 8-bit wire formats (wlx_ring_set_format); 2 is unassigned
 PCM_MAX_CHANNELS = 8
 # what the device resampler serves (csrc/resample.hip resample_ratio; engine.resample_supported restates its rule)
 RESAMPLE_MAX_RATIO = 640          # max(up, down) of 16000 / rate (RS_MAX_RATIO)
@@ -330,6 +331,9 @@ def load() -> C.CDLL:
     lib.wlx_ring_destroy.restype = None
     lib.wlx_ring_append.argtypes = [vp, f32p, i64, i64, i64, i64p, i64p, i64p]
     lib.wlx_ring_state.argtypes = [vp, i64p, i64p]
+    lib.wlx_ring_set_format.argtypes = [vp, i32, i32, i32]
+    lib.wlx_ring_append_frames.argtypes = [vp, vp, i64, i32, i64, i64, f32p, i64, i64p, i64p, i64p, i64p]
+    lib.wlx_resample_stream_count.argtypes = [i32, i64, i32, i64p]
     lib.wlx_vad_probs_resident.argtypes = [vp, vp, i64, i64, i32, f32p, i32, i32p, f32p]
     lib.wlx_vad_segments.argtypes = [f32p, i32, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i64p, i32, i32p]
     lib.wlx_logmel_ring.argtypes = [vp, i32, i32, vp, i64p, i32, i32p]
@@ -385,6 +389,7 @@ def load() -> C.CDLL:
     lib.wlx_debug_resample.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p]
     lib.wlx_debug_resample_split.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p]
     lib.wlx_debug_resample_timed.argtypes = [i32, vp, i64, i32, i32, i32, i64, f32p, i64, i64p, f32p]
+    lib.wlx_debug_resample_stream.argtypes = [i32, vp, i64, i32, i32, i32, i64p, i32, i32, f32p, i64, i64p, i64p]
     lib.wlx_debug_flac_decode.argtypes = [i32, vp, i64, i32p, i64, C.POINTER(C.c_int64), i32p]
     lib.wlx_debug_flac_timings.argtypes = [vp, i32, f32p]
     lib.wlx_debug_dtw.argtypes = [i32, f32p, i32, i32p, i32p, i32p, i32p, i32, i32p]

@@ -130,6 +130,10 @@ struct Ring {
     int64_t base = 0, resident = 0;
     hipStream_t stream = nullptr;
     hipEvent_t last_read = nullptr; bool read_pending = false; hipStream_t last_read_stream = nullptr;
+    // the live path's wire format (wlx_ring_set_format): packets arrive as the client sent them and wlx_ring_append_frames resamples
+    // them into buf; for such a ring base + resident == fmt.M at all times. `appended`: some append call has succeeded.
+    bool has_format = false, appended = false;
+    ResampleStream fmt{};
 };
 
 struct Engine {

@@ -743,6 +743,7 @@ extern "C" void wlx_ring_destroy(wlx_ring* r) {
     if (r->stream) { (void)hipStreamSynchronize(r->stream); (void)hipStreamDestroy(r->stream); }
     if (r->last_read) (void)hipEventDestroy(r->last_read);
     if (r->buf) (void)hipFree(r->buf);
+    resample_stream_free(r->fmt);
     delete r;
 }
 
@@ -752,12 +753,8 @@ static int ring_wait_readers(Ring* r) {
     return WLX_OK;
 }
 
-extern "C" int32_t wlx_ring_append(wlx_ring* r, const float* samples, int64_t n, int64_t max_resident, int64_t trim,
-                                   int64_t* dropped_out, int64_t* base_out, int64_t* resident_out) {
-    if (!r || n < 0 || (n > 0 && !samples)) return set_error(WLX_ERR_ARG, "wlx_ring_append: bad argument");
-    if (n > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
-    std::lock_guard<std::mutex> lk(r->mu);
-    CK(hipSetDevice(r->device));
+// the front half of every append: the trim rule of add_frames, then room for n more samples behind the resident ones
+static int ring_make_room(Ring* r, int64_t n, int64_t max_resident, int64_t trim, int64_t* dropped_out) {
     int64_t dropped = 0;
     if (max_resident > 0 && trim > 0 && r->resident > max_resident) {
         // add_frames (base.py:191-198): the buffer is past its cap — the oldest `trim` samples go, the rest moves to the front
@@ -782,9 +779,65 @@ extern "C" int32_t wlx_ring_append(wlx_ring* r, const float* samples, int64_t n,
         CK(hipFree(r->buf));
         r->buf = nb; r->cap = cap;
     }
+    *dropped_out = dropped;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_ring_append(wlx_ring* r, const float* samples, int64_t n, int64_t max_resident, int64_t trim,
+                                   int64_t* dropped_out, int64_t* base_out, int64_t* resident_out) {
+    if (!r || n < 0 || (n > 0 && !samples)) return set_error(WLX_ERR_ARG, "wlx_ring_append: bad argument");
+    if (n > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (r->has_format) return set_error(WLX_ERR_STATE, "wlx_ring_append: the ring has a wire format (wlx_ring_append_frames)");
+    CK(hipSetDevice(r->device));
+    int64_t dropped = 0;
+    CKR(ring_make_room(r, n, max_resident, trim, &dropped));
     if (n > 0) CK(hipMemcpyAsync(r->buf + r->resident, samples, (size_t)n * sizeof(float), hipMemcpyHostToDevice, r->stream));
     CK(hipStreamSynchronize(r->stream));            // the caller's buffer may be reused; readers launched after this return see the samples
     r->resident += n;
+    r->appended = true;
+    if (dropped_out) *dropped_out = dropped;
+    if (base_out) *base_out = r->base;
+    if (resident_out) *resident_out = r->resident;
+    return WLX_OK;
+}
+
+// ---- the live path's wire format (include/wlx.h): the packets are resampled into the ring by the stream form of resample.hip
+extern "C" int32_t wlx_ring_set_format(wlx_ring* r, int32_t sample_format, int32_t channels, int32_t sample_rate) {
+    if (!r) return set_error(WLX_ERR_ARG, "null ring");
+    CKR(resample_stream_check(sample_format, channels, sample_rate));
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (r->has_format) return set_error(WLX_ERR_STATE, "wlx_ring_set_format: the ring has a format already");
+    if (r->appended || r->resident > 0 || r->base > 0) return set_error(WLX_ERR_STATE, "wlx_ring_set_format: the ring has been appended to");
+    CKR(resample_stream_open(r->device, sample_format, channels, sample_rate, &r->fmt));
+    r->has_format = true;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_ring_append_frames(wlx_ring* r, const void* frames, int64_t n_frames, int32_t flush, int64_t max_resident,
+                                          int64_t trim, float* new_out, int64_t cap, int64_t* n_new_out, int64_t* dropped_out,
+                                          int64_t* base_out, int64_t* resident_out) {
+    if (!r || n_frames < 0 || (n_frames > 0 && !frames)) return set_error(WLX_ERR_ARG, "wlx_ring_append_frames: bad argument");
+    if (new_out && cap < 0) return set_error(WLX_ERR_ARG, "wlx_ring_append_frames: negative capacity");
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (!r->has_format) return set_error(WLX_ERR_STATE, "wlx_ring_append_frames: the ring has no wire format (wlx_ring_set_format)");
+    ResampleStream& rs = r->fmt;
+    if (rs.closed) return set_error(WLX_ERR_STATE, "wlx_ring_append_frames: the stream has been flushed");
+    if (n_frames > (1LL << 50) - rs.J) return set_error(WLX_ERR_ARG, "frame count out of range");
+    const int64_t n_new = resample_stream_next(rs, n_frames, flush);
+    if (n_new > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
+    if (new_out && cap < n_new) return set_error(WLX_ERR_ARG, "wlx_ring_append_frames: %lld new samples, room for %lld", (long long)n_new, (long long)cap);
+    CK(hipSetDevice(r->device));
+    CKR(resample_stream_reserve(rs, n_frames));
+    int64_t dropped = 0;
+    CKR(ring_make_room(r, n_new, max_resident, trim, &dropped));
+    float* dst = r->buf + r->resident;
+    CKR(resample_stream_enqueue(rs, frames, n_frames, flush, dst, r->stream));
+    if (new_out && n_new > 0) CK(hipMemcpyAsync(new_out, dst, (size_t)n_new * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    CK(hipStreamSynchronize(r->stream));            // ONE wait: the caller's frames may be reused, new_out is filled, readers see the samples
+    r->resident += n_new;
+    r->appended = true;
+    if (n_new_out) *n_new_out = n_new;
     if (dropped_out) *dropped_out = dropped;
     if (base_out) *base_out = r->base;
     if (resident_out) *resident_out = r->resident;

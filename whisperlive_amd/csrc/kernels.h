@@ -119,4 +119,28 @@ int resample_run_device(const ResamplePlan& pl, const float* d_frames, long long
 int resample_run_device_split(const ResamplePlan& pl, const float* d_frames, long long n_frames, int channels, float* d_out,
                               long long out_stride, hipStream_t st);
 
+// The STREAM form (the live path: wlx_ring_append_frames; test hook wlx_debug_resample_stream): the same kernel fed packet by packet.
+// With J input frames seen and M outputs emitted, a packet of n frames completes the outputs [M, M') whose newest input exists
+// (flush: all of the one-shot's ceil(J' up / down), frames past the end being zero). The state is J, M and the last `tail_len` <=
+// resample_reach input frames on the device, in the wire format; a call stages [tail | packet] and launches ONE grid over [M, M')
+// with the window's absolute start as j_base — an output depends on absolute input indices only, so the packet seams cannot move a
+// bit against the one-shot.
+struct ResampleStream {
+    ResamplePlan pl{};
+    int fmt = 0, channels = 0, rate = 0;
+    bool closed = false;                                    // flushed: no further packets
+    long long J = 0, M = 0;
+    unsigned char* tail = nullptr; long long tail_len = 0;  // device, [resample_reach][channels] in the wire format
+    unsigned char* stage = nullptr; size_t stage_cap = 0;   // device, bytes: [tail | packet], grown on demand
+};
+int resample_format_bytes(int sample_format);                                               // 4 / 2 / 1; 0 for an unknown code
+int resample_stream_check(int sample_format, int channels, int sample_rate);                // host only: format, channels, RATES
+long long resample_stream_count(int up, int down, int half_len, long long frames_seen, int flush);   // M' as a function of J'
+int resample_stream_open(int device, int sample_format, int channels, int sample_rate, ResampleStream* rs);
+long long resample_stream_next(const ResampleStream& rs, long long n_frames, int flush);    // M' - M of the next call
+int resample_stream_reserve(ResampleStream& rs, long long n_frames);                        // staging for a packet; nothing of rs in flight
+// copies and ONE launch on `st`, output M lands at d_dst[0]; does not wait (the caller's frames are pageable: wait before returning them)
+int resample_stream_enqueue(ResampleStream& rs, const void* frames, long long n_frames, int flush, float* d_dst, hipStream_t st);
+void resample_stream_free(ResampleStream& rs);
+
 }  // namespace wlx

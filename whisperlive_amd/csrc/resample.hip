@@ -25,7 +25,13 @@
 // division — and the outputs go to out + c * out_stride. Tap table, LDS layout, tile, accumulation order and seam logic are the ones
 // above, so channel c is BIT-IDENTICAL to the down-mix form run on the one-channel array frames[:, c]: the mono path of that form does
 // no division either (its `ch > 1` branch is not taken), and an output depends on nothing but the absolute input indices.
+//
+// The STREAM form (include/wlx.h wlx_ring_set_format / wlx_ring_append_frames; test hook wlx_debug_resample_stream; kernels.h
+// ResampleStream) is the same kernel fed packet by packet: raw = [the last `reach` frames | the packet] with j_base its absolute
+// start, [m0, m1) = the outputs the packet completes, `out` rebased so that output m0 lands where the caller wants it. It adds the
+// 8-bit wire formats of live sources (uint8, G.711 mu-law / A-law) to rs_sample; nothing else in the kernel knows about streams.
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <mutex>
 #include <tuple>
@@ -56,9 +62,27 @@ __device__ __forceinline__ long long floor_div(long long a, long long b) {      
     return (a % b != 0 && a < 0) ? q - 1 : q;
 }
 
+// G.711 (ITU-T): one code byte -> its 16-bit linear value, in plain integer arithmetic (no table). tests/test_stream_resample_host.py
+// pins the anchors: mu-law 0xFF -> 0, 0x00 -> -32124, 0x80 -> +32124; A-law 0xD5 -> +8, 0x55 -> -8, 0xAA -> +32256.
+__host__ __device__ __forceinline__ int g711_mulaw(unsigned b) {
+    const unsigned u = ~b & 255u;
+    const int t = (int)((((u & 15u) << 3) + 132u) << ((u >> 4) & 7u));
+    return (u & 128u) ? 132 - t : t - 132;
+}
+__host__ __device__ __forceinline__ int g711_alaw(unsigned b) {
+    const unsigned a = (b ^ 0x55u) & 255u, s = (a >> 4) & 7u;
+    int t = (int)((a & 15u) << 4);
+    t = s == 0 ? t + 8 : (t + 0x108) << (s - 1);
+    return (a & 128u) ? t : -t;
+}
+
+// the 8-bit formats are the live path's (wlx_ring_set_format); every value is exact in float32
 template <int FMT>
 __device__ __forceinline__ float rs_sample(const void* raw, long long idx) {
     if (FMT == WLX_PCM_S16) return (float)reinterpret_cast<const short*>(raw)[idx] * (1.0f / 32768.0f);
+    if (FMT == WLX_PCM_U8) return (float)((int)reinterpret_cast<const unsigned char*>(raw)[idx] - 128) * (1.0f / 128.0f);
+    if (FMT == WLX_PCM_MULAW) return (float)g711_mulaw(reinterpret_cast<const unsigned char*>(raw)[idx]) * (1.0f / 32768.0f);
+    if (FMT == WLX_PCM_ALAW) return (float)g711_alaw(reinterpret_cast<const unsigned char*>(raw)[idx]) * (1.0f / 32768.0f);
     return reinterpret_cast<const float*>(raw)[idx];
 }
 
@@ -216,8 +240,13 @@ static void rs_launch(int sample_format, unsigned grid, size_t lds, hipStream_t 
         else hipLaunchKernelGGL((resample_kernel<WLX_PCM_F32, true>), g, dim3(RS_THREADS), lds, st, p);
         return;
     }
-    if (sample_format == WLX_PCM_S16) hipLaunchKernelGGL(resample_kernel<WLX_PCM_S16>, dim3(grid), dim3(RS_THREADS), lds, st, p);
-    else hipLaunchKernelGGL(resample_kernel<WLX_PCM_F32>, dim3(grid), dim3(RS_THREADS), lds, st, p);
+    switch (sample_format) {                            // the 8-bit formats reach here from the stream form only (resample_stream_check)
+    case WLX_PCM_S16: hipLaunchKernelGGL(resample_kernel<WLX_PCM_S16>, dim3(grid), dim3(RS_THREADS), lds, st, p); break;
+    case WLX_PCM_U8: hipLaunchKernelGGL(resample_kernel<WLX_PCM_U8>, dim3(grid), dim3(RS_THREADS), lds, st, p); break;
+    case WLX_PCM_MULAW: hipLaunchKernelGGL(resample_kernel<WLX_PCM_MULAW>, dim3(grid), dim3(RS_THREADS), lds, st, p); break;
+    case WLX_PCM_ALAW: hipLaunchKernelGGL(resample_kernel<WLX_PCM_ALAW>, dim3(grid), dim3(RS_THREADS), lds, st, p); break;
+    default: hipLaunchKernelGGL(resample_kernel<WLX_PCM_F32>, dim3(grid), dim3(RS_THREADS), lds, st, p); break;
+    }
 }
 
 int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames, int channels, int sample_format, long long block_frames,
@@ -328,6 +357,97 @@ int resample_check_args(const void* frames, long long n_frames, int channels, in
     return resample_ratio(sample_rate, &up, &down, &tile);
 }
 
+// ------------------------------------------------------------------------------------------------ the stream form (kernels.h)
+int resample_format_bytes(int sample_format) {
+    switch (sample_format) {
+    case WLX_PCM_F32: return 4;
+    case WLX_PCM_S16: return 2;
+    case WLX_PCM_U8: case WLX_PCM_MULAW: case WLX_PCM_ALAW: return 1;
+    default: return 0;
+    }
+}
+
+int resample_stream_check(int sample_format, int channels, int sample_rate) {
+    if (!resample_format_bytes(sample_format)) return set_error(WLX_ERR_ARG, "unknown sample format %d", sample_format);
+    if (channels < 1 || channels > WLX_PCM_MAX_CHANNELS) return set_error(WLX_ERR_ARG, "channels %d outside 1..%d", channels, WLX_PCM_MAX_CHANNELS);
+    int up, down, tile;
+    return resample_ratio(sample_rate, &up, &down, &tile);
+}
+
+// no flush: the outputs whose newest input, floor((half_len + m * down) / up), is below J', i.e. half_len + m * down <= J' * up - 1;
+// flush: the one-shot length. The first never exceeds the second, and both grow with J'.
+long long resample_stream_count(int up, int down, int half_len, long long frames_seen, int flush) {
+    if (flush) return (frames_seen * up + down - 1) / down;
+    const long long a = frames_seen * up - 1 - half_len;
+    return a < 0 ? 0 : a / down + 1;
+}
+
+int resample_stream_open(int device, int sample_format, int channels, int sample_rate, ResampleStream* rs) {
+    CKR(resample_stream_check(sample_format, channels, sample_rate));
+    ResampleStream s{};
+    CKR(resample_plan(device, sample_rate, &s.pl));
+    s.fmt = sample_format; s.channels = channels; s.rate = sample_rate;
+    CK(hipSetDevice(device));
+    CK(hipMalloc(reinterpret_cast<void**>(&s.tail), (size_t)resample_reach(s.pl) * channels * resample_format_bytes(sample_format)));   // owned by name: resample_stream_free
+    *rs = s;
+    return WLX_OK;
+}
+
+long long resample_stream_next(const ResampleStream& rs, long long n_frames, int flush) {
+    return resample_stream_count(rs.pl.up, rs.pl.down, rs.pl.half_len, rs.J + n_frames, flush) - rs.M;
+}
+
+int resample_stream_reserve(ResampleStream& rs, long long n_frames) {
+    const size_t need = (size_t)(rs.tail_len + n_frames) * rs.channels * resample_format_bytes(rs.fmt);
+    if (need <= rs.stage_cap) return WLX_OK;
+    size_t cap = std::max<size_t>(rs.stage_cap, 64u << 10);
+    while (cap < need) cap *= 2;
+    unsigned char* nb = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&nb), cap) != hipSuccess) {          // replaces rs.stage, freed below: nothing of it is in flight between calls
+        (void)hipGetLastError();
+        return set_error(WLX_ERR_NOMEM, "stream resampler: %zu bytes of staging cannot be had", cap);
+    }
+    if (rs.stage) CK(hipFree(rs.stage));
+    rs.stage = nb; rs.stage_cap = cap;
+    return WLX_OK;
+}
+
+int resample_stream_enqueue(ResampleStream& rs, const void* frames, long long n_frames, int flush, float* d_dst, hipStream_t st) {
+    const size_t fb = (size_t)rs.channels * resample_format_bytes(rs.fmt);
+    const long long tl = rs.tail_len, total = tl + n_frames;
+    const long long n_new = resample_stream_next(rs, n_frames, flush);
+    if (n_new > 0 || n_frames > 0) {
+        if (tl > 0) CK(hipMemcpyAsync(rs.stage, rs.tail, (size_t)tl * fb, hipMemcpyDeviceToDevice, st));
+        if (n_frames > 0) CK(hipMemcpyAsync(rs.stage + (size_t)tl * fb, frames, (size_t)n_frames * fb, hipMemcpyHostToDevice, st));
+    }
+    if (n_new > 0) {
+        ResampleArgs p{};
+        // the window [J - tail_len, J') of the stream; frames at and past J' read as zero, which only a flush's outputs reach
+        p.raw = rs.stage; p.j_base = rs.J - tl; p.raw_frames = total; p.n_frames = rs.J + n_frames; p.channels = rs.channels;
+        p.up = rs.pl.up; p.down = rs.pl.down; p.half_len = rs.pl.half_len; p.tile = rs.pl.tile; p.taps = rs.pl.taps;
+        // the kernel writes out[m] at the absolute m: output M lands at d_dst (the pointer is rebased on the host, never read here)
+        p.out = reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(d_dst) - (uintptr_t)rs.M * sizeof(float));
+        p.m0 = rs.M; p.m1 = rs.M + n_new;
+        const unsigned grid = (unsigned)((n_new + rs.pl.tile - 1) / rs.pl.tile);
+        rs_launch(rs.fmt, grid, rs_lds_bytes(rs.pl.up, rs.pl.down, rs.pl.half_len, rs.pl.tile), st, p, 0);
+        CK(hipGetLastError());
+    }
+    if (n_frames > 0) {                                     // the new tail: the last min(J', reach) frames of the window
+        const long long keep = std::min(total, resample_reach(rs.pl));
+        CK(hipMemcpyAsync(rs.tail, rs.stage + (size_t)(total - keep) * fb, (size_t)keep * fb, hipMemcpyDeviceToDevice, st));
+        rs.tail_len = keep;
+    }
+    rs.J += n_frames; rs.M += n_new;
+    if (flush) rs.closed = true;
+    return WLX_OK;
+}
+
+void resample_stream_free(ResampleStream& rs) {
+    if (rs.tail) (void)hipFree(rs.tail);
+    if (rs.stage) (void)hipFree(rs.stage);
+    rs.tail = rs.stage = nullptr; rs.stage_cap = 0; rs.tail_len = 0;
+}
+
 }  // namespace wlx
 
 using namespace wlx;
@@ -395,4 +515,57 @@ extern "C" int32_t wlx_debug_resample_timed(int32_t device, const void* frames, 
 extern "C" int32_t wlx_debug_resample_split(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
                                             int32_t sample_rate, int64_t block_frames, float* out, int64_t cap, int64_t* n_out) {
     return debug_resample(device, frames, n_frames, channels, sample_format, sample_rate, block_frames, out, cap, n_out, nullptr, true);
+}
+
+// ------------------------------------------------------------------------------------------------ the stream form: planner and hook
+extern "C" int32_t wlx_resample_stream_count(int32_t sample_rate, int64_t frames_seen, int32_t flush, int64_t* n_out) {
+    if (!n_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (frames_seen < 0 || frames_seen > (1LL << 50)) return set_error(WLX_ERR_ARG, "frame count out of range");
+    int up, down, tile;
+    CKR(resample_ratio(sample_rate, &up, &down, &tile));
+    *n_out = resample_stream_count(up, down, up == down ? 0 : 10 * std::max(up, down), frames_seen, flush);
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_debug_resample_stream(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
+                                             int32_t sample_rate, const int64_t* cuts, int32_t n_cuts, int32_t flush, float* out,
+                                             int64_t cap, int64_t* n_out, int64_t* per_call_counts) {
+    if (!out || !n_out || cap < 0 || n_cuts < 0 || (n_cuts > 0 && !cuts) || flush < 0 || flush > 2) return set_error(WLX_ERR_ARG, "bad argument");
+    if (n_frames < 0 || n_frames > (1LL << 50)) return set_error(WLX_ERR_ARG, "frame count out of range");
+    if (n_frames > 0 && !frames) return set_error(WLX_ERR_ARG, "null frames");
+    CKR(resample_stream_check(sample_format, channels, sample_rate));
+    for (int i = 0; i < n_cuts; ++i)
+        if (cuts[i] < (i ? cuts[i - 1] : 0) || cuts[i] > n_frames) return set_error(WLX_ERR_ARG, "cut %d = %lld is out of order or past the end", i, (long long)cuts[i]);
+    int up, down, tile;
+    CKR(resample_ratio(sample_rate, &up, &down, &tile));
+    const long long total = resample_stream_count(up, down, up == down ? 0 : 10 * std::max(up, down), n_frames, flush);
+    if (total > cap) return set_error(WLX_ERR_ARG, "output buffer too small");
+    int ndev = 0;
+    CK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, ndev - 1);
+    CK(hipSetDevice(device));
+    struct Scope {
+        ResampleStream rs{}; float* dout = nullptr; hipStream_t st = nullptr;
+        ~Scope() { if (st) (void)hipStreamSynchronize(st); resample_stream_free(rs); if (dout) (void)hipFree(dout); if (st) (void)hipStreamDestroy(st); }
+    } S;
+    CK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
+    CKR(resample_stream_open(device, sample_format, channels, sample_rate, &S.rs));
+    CK(hipMalloc(reinterpret_cast<void**>(&S.dout), std::max<size_t>((size_t)cap, 1) * sizeof(float)));     // freed by Scope
+    CK(hipMemcpyAsync(S.dout, out, (size_t)cap * sizeof(float), hipMemcpyHostToDevice, S.st));               // copied in AND out
+    const size_t fb = (size_t)channels * resample_format_bytes(sample_format);
+    const int n_calls = n_cuts + 1 + (flush == 1 ? 1 : 0);
+    for (int c = 0; c < n_calls; ++c) {
+        const bool tail_call = c == n_cuts + 1;              // flush == 1: the empty flushing packet behind the data
+        const long long a = tail_call ? n_frames : (c ? cuts[c - 1] : 0), b = tail_call ? n_frames : (c < n_cuts ? cuts[c] : n_frames);
+        const int fl = tail_call || (flush == 2 && c == n_cuts);
+        const long long before = S.rs.M;
+        CKR(resample_stream_reserve(S.rs, b - a));
+        CKR(resample_stream_enqueue(S.rs, static_cast<const char*>(frames) + (size_t)a * fb, b - a, fl, S.dout + before, S.st));
+        CK(hipStreamSynchronize(S.st));                      // as the product call: a packet is done when its call returns
+        if (per_call_counts) per_call_counts[c] = S.rs.M - before;
+    }
+    CK(hipMemcpyAsync(out, S.dout, (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, S.st));
+    CK(hipStreamSynchronize(S.st));
+    *n_out = S.rs.M;
+    return WLX_OK;
 }

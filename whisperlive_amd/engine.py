@@ -117,6 +117,40 @@ class PcmRing:
                                        self.TRIM if trim is None else int(trim), C.byref(d), C.byref(b), C.byref(r)))
         return d.value, b.value, r.value
 
+    def set_format(self, fmt: int, channels: int, rate: int) -> None:
+        """Give the ring a wire format (_lib.PCM_*; once, before the first append): packets then go through append_frames."""
+        check(self.lib.wlx_ring_set_format(self._h, int(fmt), int(channels), int(rate)))
+        self.format = (int(fmt), int(channels), int(rate))
+        self._frame_bytes = int(channels) * {_lib.PCM_F32: 4, _lib.PCM_S16: 2}.get(int(fmt), 1)
+        self._frames_seen = 0
+
+    def append_frames(self, raw, flush: bool = False, max_resident: Optional[int] = None, trim: Optional[int] = None):
+        """One packet in the wire format (bytes, or a C-contiguous array of wire samples) -> (the packet's new 16 kHz samples, samples
+        dropped by this call, first resident position, resident count). The packet crosses PCIe as it is; the new samples come back
+        in the same wait. flush=True completes the stream to the one-shot length and closes it."""
+        fb = self._frame_bytes
+        if isinstance(raw, np.ndarray):
+            raw = np.ascontiguousarray(raw)
+            nbytes, ptr = raw.nbytes, raw.ctypes.data
+        else:
+            raw = bytes(raw)
+            nbytes, ptr = len(raw), C.cast(C.c_char_p(raw), C.c_void_p).value
+        if nbytes % fb:
+            raise ValueError(f"packet of {nbytes} bytes is not a whole number of {fb}-byte frames")
+        n = nbytes // fb
+        want = C.c_int64(0)
+        check(self.lib.wlx_resample_stream_count(self.format[2], self._frames_seen + n, 1, C.byref(want)))   # the flushed count bounds the other
+        have = C.c_int64(0)
+        check(self.lib.wlx_resample_stream_count(self.format[2], self._frames_seen, 0, C.byref(have)))
+        out = np.empty(max(want.value - have.value, 0), np.float32)
+        k, d, b, r = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self.lib.wlx_ring_append_frames(self._h, ptr if n else None, n, 1 if flush else 0,
+                                              self.MAX_RESIDENT if max_resident is None else int(max_resident),
+                                              self.TRIM if trim is None else int(trim), _f32p(out), out.shape[0], C.byref(k),
+                                              C.byref(d), C.byref(b), C.byref(r)))
+        self._frames_seen += n
+        return out[: k.value], d.value, b.value, r.value
+
     def state(self) -> Tuple[int, int]:
         b, r = C.c_int64(0), C.c_int64(0)
         check(self.lib.wlx_ring_state(self._h, C.byref(b), C.byref(r)))

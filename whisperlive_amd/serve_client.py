@@ -73,21 +73,64 @@ class ServeClientBase:
     # ---- audio buffer ------------------------------------------------------------------------------------------
     def add_frames(self, frame_np: np.ndarray):
         with self.lock:
-            buf = self.frames_np
-            trimmed = 0
-            if buf is not None and buf.shape[0] > self.MAX_BUFFER_DURATION_S * self.RATE:
-                self.frames_offset += float(self.BUFFER_TRIM_DURATION_S)
-                trimmed = int(self.BUFFER_TRIM_DURATION_S * self.RATE)
-                buf = buf[trimmed:]
-                if self.timestamp_offset < self.frames_offset:      # nothing was committed in the dropped audio
-                    self.timestamp_offset = self.frames_offset
-            self.frames_np = frame_np.copy() if buf is None else np.concatenate((buf, frame_np), axis=0)
+            trimmed = self._take_frames(frame_np)
             self._frames_appended(frame_np, trimmed)
         self.frames_ready.set()
+
+    def _take_frames(self, frame_np: np.ndarray) -> int:
+        """The buffer rule (under `self.lock`): past the cap the oldest 30 s go first, then the packet is appended. -> samples trimmed"""
+        buf = self.frames_np
+        trimmed = 0
+        if buf is not None and buf.shape[0] > self.MAX_BUFFER_DURATION_S * self.RATE:
+            self.frames_offset += float(self.BUFFER_TRIM_DURATION_S)
+            trimmed = int(self.BUFFER_TRIM_DURATION_S * self.RATE)
+            buf = buf[trimmed:]
+            if self.timestamp_offset < self.frames_offset:      # nothing was committed in the dropped audio
+                self.timestamp_offset = self.frames_offset
+        self.frames_np = frame_np.copy() if buf is None else np.concatenate((buf, frame_np), axis=0)
+        return trimmed
 
     def _frames_appended(self, frame_np: np.ndarray, trimmed: int):
         """Hook, called under `self.lock` right after `frames_np` took the packet (`trimmed` samples were dropped from its front
         first): backends that keep a device-side mirror of the buffer update it here."""
+
+    # ---- wire-format sessions: the client announced its own sample_rate / channels / audio_format -----------------------------
+    _wire = None                    # stream_resample.StreamResampler: J, M and the raw tail of the stream, kept on the host at all times
+
+    def set_wire_format(self, audio_format: str, channels: int, sample_rate: int):
+        """Before the first packet. ValueError for a format, channel count or rate the resampler does not serve."""
+        from .stream_resample import StreamResampler
+        self._wire = StreamResampler(audio_format, channels, sample_rate)
+
+    def add_wire_frames(self, raw, flush: bool = False):
+        """One packet as it came off the socket (bytes in the announced format; b"" with flush=True ends the stream): its 16 kHz
+        samples — from the device ring where the backend has one (`_wire_samples`), else from the host resampler — go through the
+        buffer rule of add_frames. ValueError for a packet that does not hold whole frames."""
+        wire = self._wire
+        if wire is None:
+            raise RuntimeError("add_wire_frames on a session without a wire format")
+        with self.lock:
+            if wire.closed:
+                return
+            wire.frames(raw)                                 # whole frames, or ValueError before anything changes
+            done = self._wire_samples(raw, flush)
+            if done is None:
+                new, ring_state = wire.feed(raw, flush), None
+            else:
+                new, ring_state = done
+                wire.advance(raw, flush)
+            trimmed = self._take_frames(new)
+            if ring_state is not None:
+                self._wire_appended(new, trimmed, ring_state)
+        self.frames_ready.set()
+
+    def _wire_samples(self, raw, flush: bool):
+        """Hook (under `self.lock`): -> (the packet's new 16 kHz samples, (dropped, base, resident) of the device mirror) when the
+        backend resamples on its device; None: the host resampler takes the packet."""
+        return None
+
+    def _wire_appended(self, new: np.ndarray, trimmed: int, ring_state):
+        """Hook: `frames_np` took what `_wire_samples` returned; the backend checks its mirror against it."""
 
     def clip_audio_if_no_valid_segment(self):
         with self.lock:
@@ -429,6 +472,46 @@ class ServeClientHIP(ServeClientBase):
                     ring.close()
                 except Exception:  # noqa: BLE001
                     pass
+
+    def _ring_off(self, e):
+        logging.warning(f"device PCM ring disabled for {self.client_uid}: {e}")
+        ring, self._ring = self._ring, False
+        if ring:
+            try:
+                ring.close()
+            except Exception:  # noqa: BLE001
+                pass
+
+    def _wire_samples(self, raw, flush):
+        """The packet goes to the ring in its wire format (PcmRing.append_frames: converted, down-mixed and resampled on the device,
+        the new samples back in the same wait). Any failure switches the ring off: the host resampler, whose state the session has
+        kept in step, takes this packet and every later one."""
+        if self._ring is False:
+            return None
+        try:
+            if self._ring is None:
+                eng = getattr(getattr(self, "transcriber", None), "engine", None)
+                make = getattr(eng, "create_ring", None)
+                if make is None or os.environ.get("WLX_PCM_RING", "1") == "0" or (ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS):
+                    self._ring = False
+                    return None
+                if self._wire.J:                             # the stream began on the host: a ring cannot join it half-way
+                    self._ring = False
+                    return None
+                self._ring = make()
+                self._ring.set_format(self._wire.code, self._wire.channels, self._wire.rate)
+            new, dropped, base, resident = self._ring.append_frames(raw, flush)
+            return new, (dropped, base, resident)
+        except Exception as e:  # noqa: BLE001
+            self._ring_off(e)
+            return None
+
+    def _wire_appended(self, new, trimmed, ring_state):
+        """The coherence check of _frames_appended for a packet the ring resampled itself (it is NOT appended a second time)."""
+        dropped, base, resident = ring_state
+        if dropped != trimmed or resident != self.frames_np.shape[0] or base != int(round(self.frames_offset * self.RATE)):
+            self._ring_off(RuntimeError(f"ring out of step with frames_np: dropped {dropped} vs {trimmed}, resident {resident} vs "
+                                        f"{self.frames_np.shape[0]}, base {base} vs {self.frames_offset * self.RATE}"))
 
     def _resident(self, input_sample):
         """`input_sample` as a ResidentAudio when it is the chunk get_audio_chunk_for_processing just took and the ring holds it."""

@@ -58,6 +58,9 @@ MAX_SLOT_BATCH = 64         # clips one engine slot encodes and decodes together
 
 END_OF_AUDIO = b"END_OF_AUDIO"      # whisper_live/server.py:376, client.py:23
 AUDIO_FORMATS = ("float32", "int16", "uint8")
+# formats only a WIRE-FORMAT session speaks (stream_resample.py): one that announces sample_rate != 16000, channels != 1 or one of these.
+# Its packets are not converted here; they go to the session as bytes (ServeClientBase.add_wire_frames).
+WIRE_ONLY_FORMATS = ("mulaw", "alaw")
 
 
 def _attach_translation_cleanup(client):
@@ -179,6 +182,7 @@ class TranscriptionServer:
         self.batch_config = None
         self.raw_pcm_input = False
         self.audio_formats = {}
+        self.wire_sessions = set()            # websockets whose session took a wire format (handle_new_connection)
         self.segment_post_processor = None
         self.backend = BackendType.HIP
         self.cache_path = "~/.cache/whisper-live/"
@@ -345,11 +349,26 @@ class TranscriptionServer:
                 websocket.close()
                 return False
             audio_format = options.get("audio_format", "float32")
-            if audio_format not in AUDIO_FORMATS:
+            sample_rate, channels = options.get("sample_rate", self.RATE), options.get("channels", 1)
+            wire = sample_rate != self.RATE or channels != 1 or audio_format in WIRE_ONLY_FORMATS
+            if audio_format not in AUDIO_FORMATS and not (wire and audio_format in WIRE_ONLY_FORMATS):
                 raise ValueError(f"Unsupported audio_format: {audio_format}")
+            if wire:
+                from .stream_resample import check_format
+                try:
+                    check_format(audio_format, channels, sample_rate)
+                except ValueError as e:
+                    websocket.send(json.dumps({"uid": options.get("uid"), "status": "ERROR", "message": str(e)}))
+                    websocket.close()
+                    return False
             self.audio_formats[websocket] = audio_format
             self.initialize_client(websocket, options, faster_whisper_custom_model_path, whisper_tensorrt_path,
                                    trt_multilingual, trt_py_session=trt_py_session)
+            if wire:
+                client = self.client_manager.get_client(websocket)
+                if client:
+                    client.set_wire_format(audio_format, channels, sample_rate)
+                    self.wire_sessions.add(websocket)
             wl_metrics.track_connection_opened()
             return True
         except json.JSONDecodeError:
@@ -362,7 +381,27 @@ class TranscriptionServer:
             logging.error(f"Error during new connection initialization: {str(e)}")
             return False
 
+    def process_wire_frames(self, websocket):
+        """One packet of a wire-format session: its bytes go to the session unconverted; END_OF_AUDIO flushes the stream first."""
+        frame_data = websocket.recv()
+        client = self.client_manager.get_client(websocket)
+        if not client:
+            return False
+        if frame_data == END_OF_AUDIO:
+            client.add_wire_frames(b"", flush=True)
+            return False
+        if isinstance(frame_data, str):
+            raise ValueError("audio packets must be binary frames")
+        try:
+            client.add_wire_frames(frame_data)
+        except ValueError as e:                          # a packet that does not hold whole frames
+            websocket.send(json.dumps({"uid": client.client_uid, "status": "ERROR", "message": str(e)}))
+            return False
+        return True
+
     def process_audio_frames(self, websocket):
+        if websocket in self.wire_sessions:
+            return self.process_wire_frames(websocket)
         frame_np = self.get_audio_from_websocket(websocket)
         if frame_np is False:
             return False
@@ -393,12 +432,14 @@ class TranscriptionServer:
                 self.cleanup(websocket)
                 websocket.close()
             self.audio_formats.pop(websocket, None)
+            self.wire_sessions.discard(websocket)
             wl_metrics.track_connection_closed()
 
     def cleanup(self, websocket):
         if self.client_manager.get_client(websocket):
             self.client_manager.remove_client(websocket)
         self.audio_formats.pop(websocket, None)
+        self.wire_sessions.discard(websocket)
 
     # ---- entry point ---------------------------------------------------------------------------------------------
     def configure(self, backend="hip", faster_whisper_custom_model_path=None, whisper_tensorrt_path=None,
