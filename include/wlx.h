@@ -438,6 +438,36 @@ int32_t wlx_ring_append_frames(wlx_ring* r, const void* frames, int64_t n_frames
 /* Host only (no device work, like wlx_vad_segments): M' of the stream form as a function of J' = frames_seen alone. WLX_ERR_ARG for an
  * unserved rate or a negative count. */
 int32_t wlx_resample_stream_count(int32_t sample_rate, int64_t frames_seen, int32_t flush, int64_t* n_out);
+/* ---- live MULTICHANNEL sessions: one ring per channel, filled together (PRODUCT entry points of the streaming path) ----
+ * A ring group holds `channels` LANES — one allocation [channels][capacity] — for a stream whose channels are kept apart (a telephony
+ * bridge: agent on channel 0, customer on channel 1). A packet of interleaved frames crosses PCIe once and ONE launch of the
+ * channel-split instantiation of the resampling kernel (blockIdx.y = channel: sample r * channels + c, no mean, no division) writes
+ * every lane; the [tail | packet] staging and the device tail hold whole frames and are shared by the lanes.
+ * wlx_ring_group_create: channels 1..WLX_PCM_MAX_CHANNELS, sample_format and sample_rate as wlx_ring_set_format, and its refusals
+ * (WLX_ERR_ARG; nothing is created). capacity_samples is per lane (0: 64 s).
+ * wlx_ring_group_lane: a BORROWED wlx_ring*, valid until wlx_ring_group_destroy. A lane is a full ring for every reader —
+ * wlx_ring_state, wlx_vad_probs_resident, wlx_logmel_ring, wlx_spk_embed_ring_batch work on it unchanged — and a closed one for
+ * writers: wlx_ring_append, wlx_ring_set_format and wlx_ring_append_frames on a lane are WLX_ERR_STATE, wlx_ring_destroy on a lane
+ * does nothing. A lane index outside 0..channels - 1 is WLX_ERR_ARG.
+ * wlx_ring_group_append_frames: the contract of wlx_ring_append_frames applied to all lanes in lockstep. ONE trim decision and ONE
+ * growth serve all lanes, so every lane has the same base and resident at all times (dropped / base / resident are per lane, in
+ * 16 kHz samples). Per call: one tail copy, one packet upload, one launch over [M, M') x channels, one new tail, one wait.
+ * new_out (nullable): [channels][cap] floats, ONE copy back, lane c's M' - M new samples at new_out + c * cap; cap < M' - M is
+ * refused before anything is enqueued, nothing changed. After a flush further appends are WLX_ERR_STATE.
+ * For ANY cutting of a stream into packets followed by a flush, lane c is BIT-IDENTICAL to a mono ring given
+ * wlx_ring_set_format(fmt, 1, rate) and fed channel c's frames with the same cutting, with equal dropped / base / resident at every
+ * packet; hence to the one-shot resample of that channel, and for F32 / S16 to item c of wlx_pcm_put_frames_split.
+ * Readers of a lane and the group's append are serialised as calls on one ring are (the append holds every lane's mutex); it waits
+ * for pending readers only where data moves under them (a trim, a growth). The group's own stream, never the null stream. */
+typedef struct wlx_ring_group wlx_ring_group;
+int32_t wlx_ring_group_create(wlx_engine* e, int64_t capacity_samples /* per lane; 0: 64 s */, int32_t sample_format, int32_t channels,
+                              int32_t sample_rate, wlx_ring_group** out);
+void    wlx_ring_group_destroy(wlx_ring_group* g);
+int32_t wlx_ring_group_lane(wlx_ring_group* g, int32_t channel, wlx_ring** out);
+int32_t wlx_ring_group_append_frames(wlx_ring_group* g, const void* frames, int64_t n_frames, int32_t flush,
+                                     int64_t max_resident, int64_t trim,
+                                     float* new_out, int64_t cap, int64_t* n_new_out,
+                                     int64_t* dropped_out, int64_t* base_out, int64_t* resident_out);
 /* wlx_vad_probs on ring samples [start, start + n): no host-to-device copy. Same contract otherwise (zero initial
  * state, ceil(n / 512) windows, the last one zero-padded) plus `extra_zero_windows` all-zero windows behind them
  * (faster_whisper.vad pads n to the NEXT multiple of 512 — a whole window of zeros when n already is one — and the

@@ -22,7 +22,8 @@ EXPORTS = [
     "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_put_frames_split", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_put_flac_split", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
     "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_align_batch", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
-    "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_ring_set_format", "wlx_ring_append_frames", "wlx_resample_stream_count", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
+    "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_ring_set_format", "wlx_ring_append_frames", "wlx_resample_stream_count",
+    "wlx_ring_group_create", "wlx_ring_group_destroy", "wlx_ring_group_lane", "wlx_ring_group_append_frames", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
     "wlx_logmel_chunks", "wlx_logmel_chunks_multi", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
     "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch", "wlx_spk_embed_pcm_batch", "wlx_spk_embed_ring_batch",
@@ -334,6 +335,11 @@ def load() -> C.CDLL:
     lib.wlx_ring_set_format.argtypes = [vp, i32, i32, i32]
     lib.wlx_ring_append_frames.argtypes = [vp, vp, i64, i32, i64, i64, f32p, i64, i64p, i64p, i64p, i64p]
     lib.wlx_resample_stream_count.argtypes = [i32, i64, i32, i64p]
+    lib.wlx_ring_group_create.argtypes = [vp, i64, i32, i32, i32, C.POINTER(vp)]
+    lib.wlx_ring_group_destroy.argtypes = [vp]
+    lib.wlx_ring_group_destroy.restype = None
+    lib.wlx_ring_group_lane.argtypes = [vp, i32, C.POINTER(vp)]
+    lib.wlx_ring_group_append_frames.argtypes = [vp, vp, i64, i32, i64, i64, f32p, i64, i64p, i64p, i64p, i64p]
     lib.wlx_vad_probs_resident.argtypes = [vp, vp, i64, i64, i32, f32p, i32, i32p, f32p]
     lib.wlx_vad_segments.argtypes = [f32p, i32, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i64p, i32, i32p]
     lib.wlx_logmel_ring.argtypes = [vp, i32, i32, vp, i64p, i32, i32p]
@@ -397,7 +403,7 @@ def load() -> C.CDLL:
     lib.wlx_debug_align_timings.argtypes = [vp, i32, f32p, f32p]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):
+        if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_ring_group_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):
             fn.restype = i32
     if lib.wlx_abi_version() != 1:
         raise WlxError("libwlx.so ABI version mismatch")

@@ -134,6 +134,22 @@ struct Ring {
     // them into buf; for such a ring base + resident == fmt.M at all times. `appended`: some append call has succeeded.
     bool has_format = false, appended = false;
     ResampleStream fmt{};
+    // a LANE of a ring group (below): buf points into the group's allocation, `stream` is null, the group appends and owns the
+    // memory; the ring's own append / set_format entry points refuse it and wlx_ring_destroy leaves it alone
+    struct RingGroup* group = nullptr;
+};
+
+// Ring group of one multichannel client stream (include/wlx.h: wlx_ring_group_*; engine.hip): `channels` lanes in ONE allocation
+// [channels][cap], filled by one launch of the split stream form of resample.hip per packet. Every lane is a Ring for its readers
+// (own mutex, own last_read event); base and resident are equal on all lanes at all times. The group's append takes `mu`, then the
+// lanes' mutexes in lane order; a reader only ever holds ONE lane's mutex, so the order cannot cycle.
+struct RingGroup {
+    std::mutex mu;
+    int device = 0, channels = 0;
+    float* buf = nullptr; size_t cap = 0;                   // [channels][cap]
+    hipStream_t stream = nullptr;
+    std::vector<wlx_ring*> lanes;
+    ResampleStream fmt{};                                   // J, M, the tail of whole interleaved frames: shared by all lanes
 };
 
 struct Engine {
@@ -159,6 +175,7 @@ struct Engine {
 
 struct wlx_engine : public wlx::Engine {};
 struct wlx_ring : public wlx::Ring {};
+struct wlx_ring_group : public wlx::RingGroup {};
 
 // ------------------------------------------------------------------------------------------------
 // shared between engine.hip (slots, streams), engine_decode.hip (decode) and engine_debug.hip (hooks)

@@ -139,8 +139,11 @@ long long resample_stream_count(int up, int down, int half_len, long long frames
 int resample_stream_open(int device, int sample_format, int channels, int sample_rate, ResampleStream* rs);
 long long resample_stream_next(const ResampleStream& rs, long long n_frames, int flush);    // M' - M of the next call
 int resample_stream_reserve(ResampleStream& rs, long long n_frames);                        // staging for a packet; nothing of rs in flight
-// copies and ONE launch on `st`, output M lands at d_dst[0]; does not wait (the caller's frames are pageable: wait before returning them)
-int resample_stream_enqueue(ResampleStream& rs, const void* frames, long long n_frames, int flush, float* d_dst, hipStream_t st);
+// copies and ONE launch on `st`, output M lands at d_dst[0]; does not wait (the caller's frames are pageable: wait before returning them).
+// lane_stride > 0: the channel-split form of a ring group — no down-mix, ONE launch with blockIdx.y = channel, channel c's output M lands
+// at d_dst[c * lane_stride]; window, tail and staging are the same whole interleaved frames.
+int resample_stream_enqueue(ResampleStream& rs, const void* frames, long long n_frames, int flush, float* d_dst, hipStream_t st,
+                            long long lane_stride = 0);
 void resample_stream_free(ResampleStream& rs);
 
 }  // namespace wlx

@@ -30,6 +30,11 @@
 // ResampleStream) is the same kernel fed packet by packet: raw = [the last `reach` frames | the packet] with j_base its absolute
 // start, [m0, m1) = the outputs the packet completes, `out` rebased so that output m0 lands where the caller wants it. It adds the
 // 8-bit wire formats of live sources (uint8, G.711 mu-law / A-law) to rs_sample; nothing else in the kernel knows about streams.
+//
+// The stream form of the SPLIT instantiation (include/wlx.h wlx_ring_group_append_frames) is the two together: the same [tail | packet]
+// window of whole interleaved frames, shared by all channels, one grid over [M, M') x channels, channel c's outputs rebased into lane c
+// of the group (out_stride = the lane stride). All five formats have a split instantiation for it; lane c is bit-identical to the
+// stream form of the down-mix kernel fed channel c alone, for the reason given above.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -236,8 +241,13 @@ static void rs_launch(int sample_format, unsigned grid, size_t lds, hipStream_t 
     if (split_stride > 0) {
         p.out_stride = split_stride;
         const dim3 g(grid, (unsigned)p.channels);
-        if (sample_format == WLX_PCM_S16) hipLaunchKernelGGL((resample_kernel<WLX_PCM_S16, true>), g, dim3(RS_THREADS), lds, st, p);
-        else hipLaunchKernelGGL((resample_kernel<WLX_PCM_F32, true>), g, dim3(RS_THREADS), lds, st, p);
+        switch (sample_format) {                        // the 8-bit formats reach here from a ring group only (resample_stream_check)
+        case WLX_PCM_S16: hipLaunchKernelGGL((resample_kernel<WLX_PCM_S16, true>), g, dim3(RS_THREADS), lds, st, p); break;
+        case WLX_PCM_U8: hipLaunchKernelGGL((resample_kernel<WLX_PCM_U8, true>), g, dim3(RS_THREADS), lds, st, p); break;
+        case WLX_PCM_MULAW: hipLaunchKernelGGL((resample_kernel<WLX_PCM_MULAW, true>), g, dim3(RS_THREADS), lds, st, p); break;
+        case WLX_PCM_ALAW: hipLaunchKernelGGL((resample_kernel<WLX_PCM_ALAW, true>), g, dim3(RS_THREADS), lds, st, p); break;
+        default: hipLaunchKernelGGL((resample_kernel<WLX_PCM_F32, true>), g, dim3(RS_THREADS), lds, st, p); break;
+        }
         return;
     }
     switch (sample_format) {                            // the 8-bit formats reach here from the stream form only (resample_stream_check)
@@ -412,7 +422,8 @@ int resample_stream_reserve(ResampleStream& rs, long long n_frames) {
     return WLX_OK;
 }
 
-int resample_stream_enqueue(ResampleStream& rs, const void* frames, long long n_frames, int flush, float* d_dst, hipStream_t st) {
+int resample_stream_enqueue(ResampleStream& rs, const void* frames, long long n_frames, int flush, float* d_dst, hipStream_t st,
+                            long long lane_stride) {
     const size_t fb = (size_t)rs.channels * resample_format_bytes(rs.fmt);
     const long long tl = rs.tail_len, total = tl + n_frames;
     const long long n_new = resample_stream_next(rs, n_frames, flush);
@@ -429,7 +440,8 @@ int resample_stream_enqueue(ResampleStream& rs, const void* frames, long long n_
         p.out = reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(d_dst) - (uintptr_t)rs.M * sizeof(float));
         p.m0 = rs.M; p.m1 = rs.M + n_new;
         const unsigned grid = (unsigned)((n_new + rs.pl.tile - 1) / rs.pl.tile);
-        rs_launch(rs.fmt, grid, rs_lds_bytes(rs.pl.up, rs.pl.down, rs.pl.half_len, rs.pl.tile), st, p, 0);
+        // lane_stride > 0 (a ring group): the split instantiation, channel c's output M lands at d_dst + c * lane_stride
+        rs_launch(rs.fmt, grid, rs_lds_bytes(rs.pl.up, rs.pl.down, rs.pl.half_len, rs.pl.tile), st, p, lane_stride);
         CK(hipGetLastError());
     }
     if (n_frames > 0) {                                     // the new tail: the last min(J', reach) frames of the window

@@ -77,6 +77,11 @@ class HipWhisperEngine:
         check(self.lib.wlx_ring_create(self._h, int(capacity_samples), C.byref(h)))
         return PcmRing(self, h)
 
+    def create_ring_group(self, fmt: int, channels: int, rate: int, capacity_samples: int = 0) -> "PcmRingGroup":
+        """The lanes of one multichannel client stream (include/wlx.h wlx_ring_group_*): one device PCM ring per channel, filled
+        together from the interleaved packets in their wire format (_lib.PCM_*)."""
+        return PcmRingGroup(self, fmt, channels, rate, capacity_samples)
+
     def create_slot(self, max_batch: int = 1, max_rows_per_item: int = 5) -> "Slot":
         sid = C.c_int32(-1)
         check(self.lib.wlx_slot_create(self._h, max_batch, max_rows_per_item, C.byref(sid)))
@@ -159,6 +164,100 @@ class PcmRing:
     def close(self):
         if getattr(self, "_h", None):
             self.lib.wlx_ring_destroy(self._h)
+            self._h = None
+
+
+def _packet(raw, frame_bytes: int):
+    """a packet (bytes, or a C-contiguous array of wire samples) -> (object to keep alive, address, frames); ValueError unless whole frames"""
+    if isinstance(raw, np.ndarray):
+        raw = np.ascontiguousarray(raw)
+        nbytes, ptr = raw.nbytes, raw.ctypes.data
+    else:
+        raw = bytes(raw)
+        nbytes, ptr = len(raw), C.cast(C.c_char_p(raw), C.c_void_p).value
+    if nbytes % frame_bytes:
+        raise ValueError(f"packet of {nbytes} bytes is not a whole number of {frame_bytes}-byte frames")
+    return raw, ptr, nbytes // frame_bytes
+
+
+class _PcmRingLane(PcmRing):
+    """Lane c of a PcmRingGroup: a PcmRing for every reader (state, the VAD gate, logmel_ring, the speaker engine). The library refuses
+    its append / set_format / append_frames (WLX_ERR_STATE); close() only drops the borrowed handle, the group owns the memory."""
+
+    def __init__(self, group: "PcmRingGroup", channel: int, handle):
+        super().__init__(group.engine, handle)
+        self.group, self.channel = group, channel
+        self.format = (group.format[0], 1, group.format[2])
+        self._frame_bytes = group._frame_bytes // group.channels
+        self._frames_seen = 0
+
+    def close(self):
+        self._h = None
+
+
+class PcmRingGroup:
+    """One device PCM ring per channel of a multichannel live stream (wlx_ring_group_*): `append_frames` takes the interleaved packet
+    as it came off the socket and fills every lane in one launch; `lane(c)` is the ring the session of channel c reads."""
+    MAX_RESIDENT, TRIM = PcmRing.MAX_RESIDENT, PcmRing.TRIM
+
+    def __init__(self, engine: "HipWhisperEngine", fmt: int, channels: int, rate: int, capacity_samples: int = 0):
+        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or not 1 <= channels <= _lib.PCM_MAX_CHANNELS:
+            raise ValueError(f"channels {channels!r} outside 1..{_lib.PCM_MAX_CHANNELS}")
+        if fmt not in (_lib.PCM_F32, _lib.PCM_S16, _lib.PCM_U8, _lib.PCM_MULAW, _lib.PCM_ALAW):
+            raise ValueError(f"unknown sample format {fmt!r}")
+        if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or not resample_supported(int(rate), int(channels)):
+            raise ValueError(f"sample rate {rate!r} Hz is not a rate the device resampler serves")
+        if capacity_samples < 0:
+            raise ValueError("negative capacity")
+        self.engine, self.lib = engine, engine.lib
+        self.device = getattr(engine, "device", 0)
+        self.format = (int(fmt), int(channels), int(rate))
+        self.channels = int(channels)
+        self._frame_bytes = self.channels * {_lib.PCM_F32: 4, _lib.PCM_S16: 2}.get(int(fmt), 1)
+        self._frames_seen = 0
+        h = C.c_void_p()
+        check(self.lib.wlx_ring_group_create(engine._h, int(capacity_samples), int(fmt), self.channels, int(rate), C.byref(h)))
+        self._h = h
+        self._lanes: List[_PcmRingLane] = []
+        for c in range(self.channels):
+            lh = C.c_void_p()
+            check(self.lib.wlx_ring_group_lane(self._h, c, C.byref(lh)))
+            self._lanes.append(_PcmRingLane(self, c, lh))
+
+    def lane(self, c: int) -> PcmRing:
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < self.channels:
+            raise IndexError(f"lane {c!r} outside 0..{self.channels - 1}")
+        if not self._h:
+            raise RuntimeError("the ring group is closed")
+        return self._lanes[c]
+
+    def append_frames(self, raw, flush: bool = False, max_resident: Optional[int] = None, trim: Optional[int] = None):
+        """One interleaved packet in the wire format -> (new[channels][n]: each lane's new 16 kHz samples, samples dropped per lane by
+        this call, first resident position, resident count — the same on every lane). flush=True completes the stream and closes it."""
+        if not self._h:
+            raise RuntimeError("the ring group is closed")
+        raw, ptr, n = _packet(raw, self._frame_bytes)
+        want, have = C.c_int64(0), C.c_int64(0)
+        check(self.lib.wlx_resample_stream_count(self.format[2], self._frames_seen + n, 1, C.byref(want)))   # the flushed count bounds the other
+        check(self.lib.wlx_resample_stream_count(self.format[2], self._frames_seen, 0, C.byref(have)))
+        cap = max(want.value - have.value, 0)
+        out = np.empty((self.channels, cap), np.float32)
+        k, d, b, r = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self.lib.wlx_ring_group_append_frames(self._h, ptr if n else None, n, 1 if flush else 0,
+                                                    self.MAX_RESIDENT if max_resident is None else int(max_resident),
+                                                    self.TRIM if trim is None else int(trim), _f32p(out), cap, C.byref(k),
+                                                    C.byref(d), C.byref(b), C.byref(r)))
+        self._frames_seen += n
+        return out[:, : k.value], d.value, b.value, r.value
+
+    def state(self) -> Tuple[int, int]:
+        return self._lanes[0].state()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for ln in self._lanes:
+                ln.close()
+            self.lib.wlx_ring_group_destroy(self._h)
             self._h = None
 
 

@@ -132,6 +132,16 @@ class ServeClientBase:
     def _wire_appended(self, new: np.ndarray, trimmed: int, ring_state):
         """Hook: `frames_np` took what `_wire_samples` returned; the backend checks its mirror against it."""
 
+    def take_wire_samples(self, new: np.ndarray, ring_state=None):
+        """One channel of a multichannel session (MultichannelSession): the packet's new 16 kHz samples of THIS channel, resampled by
+        the parent — on the device (`ring_state` = (dropped, base, resident) of this session's lane) or on the host (None) — go
+        through the buffer rule and the coherence check exactly as in add_wire_frames."""
+        with self.lock:
+            trimmed = self._take_frames(new)
+            if ring_state is not None:
+                self._wire_appended(new, trimmed, ring_state)
+        self.frames_ready.set()
+
     def clip_audio_if_no_valid_segment(self):
         with self.lock:
             start = int((self.timestamp_offset - self.frames_offset) * self.RATE)
@@ -600,6 +610,9 @@ class ServeClientHIP(ServeClientBase):
             ring, self._ring = self._ring, False
         if ring:
             ring.close()
+        after = getattr(self, "_after_thread_exit", None)      # a multichannel parent releases its ring group behind its last child
+        if after is not None:
+            after(self)
 
     def handle_transcription_output(self, result, duration):
         segments = []
@@ -608,3 +621,168 @@ class ServeClientHIP(ServeClientBase):
             segments = self.prepare_segments(self.update_segments(result, duration))
         if len(segments):
             self.send_transcription_to_client(segments)
+
+
+class _ChannelSocket:
+    """What a child of a multichannel session holds as its websocket: every message it sends goes out on the session's socket with
+    "channel": c added (one sender at a time). The child's own SERVER_READY is not forwarded — the parent announces the session once."""
+
+    def __init__(self, websocket, channel: int, send_lock):
+        self.websocket, self.channel, self._send_lock = websocket, channel, send_lock
+
+    def send(self, text):
+        msg = json.loads(text)
+        if msg.get("message") == ServeClientBase.SERVER_READY:
+            return
+        msg["channel"] = self.channel
+        with self._send_lock:
+            self.websocket.send(json.dumps(msg))
+
+    def close(self):
+        self.websocket.close()
+
+
+class MultichannelSession:
+    """A live session that keeps the channels of its stream apart (first message: ``multichannel: true``, ``channels >= 2``): ONE
+    socket feeds C per-channel sessions, each an ordinary ServeClientHIP — own `frames_np`, `timestamp_offset`, transcript and
+    `same_output` logic, own transcription thread and engine slot — whose `_ring` is its lane of one device ring group
+    (engine.PcmRingGroup). The parent hands every packet to the group ONCE (one upload, one launch, one wait) and gives each child its
+    new 16 kHz samples through the buffer rule of add_wire_frames. It keeps the C host resampler states in step (`advance`), so when
+    the group fails or there is none — a scripted engine, WLX_PCM_RING=0, a batch worker — the host route
+    (stream_resample.ChannelStreamResamplers) takes over at that very packet without a gap or a repeated sample."""
+    SERVER_READY = ServeClientBase.SERVER_READY
+    DISCONNECT = ServeClientBase.DISCONNECT
+
+    def __init__(self, websocket, client_uid, audio_format: str, channels: int, sample_rate: int, make_child):
+        """make_child(channel, channel_socket) -> a ServeClientHIP built on `channel_socket` (its thread may be running already).
+        ValueError for what the resampler does not serve, before any child is built."""
+        from .stream_resample import ChannelStreamResamplers
+        if isinstance(channels, bool) or not isinstance(channels, int) or channels < 2:
+            raise ValueError(f"multichannel needs channels >= 2, got {channels!r}")
+        self._wire = ChannelStreamResamplers(audio_format, channels, sample_rate)
+        self.websocket, self.client_uid, self.channels = websocket, client_uid, channels
+        self.n_slots = channels                  # engine slots this session holds (ClientManager counts them)
+        self.lock = threading.Lock()
+        self._send_lock = threading.Lock()
+        self._group = None                       # None: not created yet; False: off for this session; else the PcmRingGroup
+        self._dead_groups: list = []             # groups switched off mid-session: destroyed behind the last child's thread
+        self._exited: set = set()
+        self._released = False
+        self.exit = False
+        self.children: List[ServeClientHIP] = []
+        for c in range(channels):
+            child = make_child(c, _ChannelSocket(websocket, c, self._send_lock))
+            child._after_thread_exit = self._child_exited
+            self.children.append(child)
+        self.ready = all(hasattr(ch, "transcriber") for ch in self.children)
+        if self.ready:
+            with self._send_lock:
+                websocket.send(json.dumps({"uid": client_uid, "message": self.SERVER_READY, "backend": ServeClientHIP.BACKEND_NAME,
+                                           "channels": channels}))
+
+    # the server sets this on a client after it is built; every child formats its own segments
+    @property
+    def segment_post_processor(self):
+        return self.children[0].segment_post_processor if self.children else None
+
+    @segment_post_processor.setter
+    def segment_post_processor(self, fn):
+        for ch in self.children:
+            ch.segment_post_processor = fn
+
+    def _group_off(self, e):
+        logging.warning(f"device ring group disabled for {self.client_uid}: {e}")
+        group, self._group = self._group, False
+        for ch in self.children:
+            with ch.lock:
+                lane, ch._ring = ch._ring, False
+            if lane:
+                lane.close()                     # drops the borrowed handle: a reader that still holds the lane gets an error, not freed memory
+        if group:
+            self._dead_groups.append(group)
+
+    def _group_samples(self, raw, flush):
+        """-> (new[C][n], (dropped, base, resident)) from the device ring group; None: the host route takes the packet"""
+        if self._group is False:
+            return None
+        try:
+            if self._group is None:
+                eng = getattr(getattr(self.children[0], "transcriber", None), "engine", None)
+                make = getattr(eng, "create_ring_group", None)
+                if (make is None or os.environ.get("WLX_PCM_RING", "1") == "0" or (ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS)
+                        or self._wire.J):        # (J > 0: the stream began on the host, a group cannot join it half-way)
+                    self._group = False
+                    for ch in self.children:
+                        with ch.lock:
+                            ch._ring = False
+                    return None
+                self._group = make(self._wire.code, self.channels, self._wire.rate)
+                for c, ch in enumerate(self.children):
+                    with ch.lock:
+                        ch._ring = self._group.lane(c)
+            new, dropped, base, resident = self._group.append_frames(raw, flush)
+            return new, (dropped, base, resident)
+        except Exception as e:  # noqa: BLE001
+            self._group_off(e)
+            return None
+
+    def add_wire_frames(self, raw, flush: bool = False):
+        """One interleaved packet as it came off the socket (b"" with flush=True ends the stream). ValueError for a packet that does
+        not hold whole frames, before anything changes."""
+        wire = self._wire
+        with self.lock:
+            if wire.closed or self._released:
+                return
+            wire.frames(raw)
+            done = self._group_samples(raw, flush)
+            if done is None:
+                news, ring_state = wire.feed(raw, flush), None
+            else:
+                news, ring_state = done
+                wire.advance(raw, flush)
+            for c, ch in enumerate(self.children):
+                ch.take_wire_samples(np.ascontiguousarray(news[c], dtype=np.float32), ring_state if ch._ring else None)
+
+    def add_frames(self, frame_np):
+        raise RuntimeError("a multichannel session takes its packets in the wire format (add_wire_frames)")
+
+    def set_wire_format(self, audio_format, channels, sample_rate):
+        """the format was fixed when the session was built"""
+
+    def disconnect(self):
+        with self._send_lock:
+            self.websocket.send(json.dumps({"uid": self.client_uid, "message": self.DISCONNECT}))
+
+    def _child_exited(self, child):
+        with self.lock:
+            self._exited.add(id(child))
+        self._maybe_release()
+
+    def _maybe_release(self):
+        """The ring group goes once the session is over AND no child thread can still read a lane."""
+        with self.lock:
+            if not self.exit or self._released:
+                return
+            for ch in self.children:
+                t = getattr(ch, "trans_thread", None)
+                if id(ch) not in self._exited and t is not None and t.is_alive():
+                    return
+            self._released = True
+            groups = self._dead_groups + ([self._group] if self._group else [])
+            self._group, self._dead_groups = False, []
+            for ch in self.children:
+                with ch.lock:
+                    lane, ch._ring = ch._ring, False
+                if lane:
+                    lane.close()
+        for g in groups:
+            try:
+                g.close()
+            except Exception as e:  # noqa: BLE001
+                logging.warning(f"ring group of {self.client_uid}: {e}")
+
+    def cleanup(self):
+        self.exit = True
+        for ch in self.children:
+            ch.cleanup()
+        self._maybe_release()

@@ -50,7 +50,7 @@ import numpy as np
 from . import metrics as wl_metrics
 from . import vad as _vad
 from . import ws
-from .serve_client import ServeClientBase, ServeClientHIP
+from .serve_client import MultichannelSession, ServeClientBase, ServeClientHIP
 from .sharding import assign_gpu
 from .ws import ConnectionClosed
 
@@ -124,9 +124,17 @@ class ClientManager:
             left = self._min_remaining()
         return left / 60 if left is not None else 0
 
+    def slots_in_use(self) -> int:
+        """engine slots the connected sessions hold: one each, a multichannel session one per channel (its `n_slots`)"""
+        return sum(c.n_slots if isinstance(c, MultichannelSession) else 1 for c in self.clients.values())
+
+    def free_slots(self) -> int:
+        with self.lock:
+            return self.max_clients - self.slots_in_use()
+
     def is_server_full(self, websocket, options):
         with self.lock:
-            if len(self.clients) < self.max_clients:
+            if self.slots_in_use() < self.max_clients:
                 return False
             left = self._min_remaining()
             websocket.send(json.dumps({"uid": options["uid"], "status": "WAIT",
@@ -323,6 +331,87 @@ class TranscriptionServer:
             client.segment_post_processor = self.segment_post_processor
         self.client_manager.add_client(websocket, client)
 
+    # ---- multichannel live sessions: one socket, one transcript per channel ------------------------
+    def open_multichannel(self, websocket, options, audio_format, channels, sample_rate, faster_whisper_custom_model_path=None):
+        """A first message with ``multichannel: true``: refusals get the ERROR message and a closed socket; otherwise C per-channel
+        ServeClientHIP sessions on one GPU behind a MultichannelSession, which is what the client table holds. -> bool"""
+        uid = options.get("uid")
+
+        def refuse(message):
+            websocket.send(json.dumps({"uid": uid, "status": "ERROR", "message": message}))
+            websocket.close()
+            return False
+
+        if isinstance(channels, bool) or not isinstance(channels, int) or channels < 2:
+            return refuse(f"Unsupported channels: multichannel needs channels >= 2, got {channels!r}")
+        from .stream_resample import WIRE_FORMATS, check_format
+        try:
+            if audio_format not in WIRE_FORMATS:
+                raise ValueError(f"Unsupported audio_format: {audio_format}")
+            check_format(audio_format, channels, sample_rate)
+        except ValueError as e:
+            return refuse(str(e))
+        for key in ("enable_diarization", "enable_translation"):
+            if options.get(key, False):
+                return refuse(f"Unsupported option: multichannel cannot be combined with {key} (the channel is the speaker identity; "
+                              "per-channel translation is not served)")
+        free = self.client_manager.free_slots()
+        if free < channels:
+            return refuse(f"Unsupported channels: a multichannel session of {channels} channels needs {channels} free slots, the server has {free}")
+        if self.backend.is_tensorrt() or self.backend.is_openvino():
+            name = "TensorRT-LLM" if self.backend.is_tensorrt() else "OpenVINO"
+            websocket.send(json.dumps({
+                "uid": uid, "status": "WARNING",
+                "message": f"{name} not supported on Server yet. Reverting to available backend: 'faster_whisper'"}))
+            self.backend = BackendType.FASTER_WHISPER
+        try:
+            if faster_whisper_custom_model_path is not None:
+                options["model"] = faster_whisper_custom_model_path
+            device_index = self._next_device()
+            use_vad = bool(options.get("use_vad"))
+            if use_vad and self.model_factory is None:
+                try:
+                    _vad.get_default_model(device_index)
+                except _vad.VadUnavailable as e:
+                    logging.warning(f"use_vad requested by {uid} but unavailable: {e}")
+                    websocket.send(json.dumps({"uid": uid, "status": "WARNING",
+                                               "message": "use_vad ignored: no Silero VAD weights are configured on this server"}))
+                    use_vad = False
+
+            def make_child(channel, channel_socket):
+                return ServeClientHIP(
+                    channel_socket, language=options["language"], task=options["task"], client_uid=uid, model=options["model"],
+                    initial_prompt=options.get("initial_prompt"), vad_parameters=options.get("vad_parameters"), use_vad=use_vad,
+                    single_model=self.single_model, send_last_n_segments=options.get("send_last_n_segments", 10),
+                    no_speech_thresh=options.get("no_speech_thresh", 0.45), clip_audio=options.get("clip_audio", False),
+                    same_output_threshold=options.get("same_output_threshold", 10), cache_path=self.cache_path,
+                    hotwords=options.get("hotwords"), word_timestamps=options.get("word_timestamps", False),
+                    device_index=device_index, model_factory=self.model_factory,
+                    max_batch=self.batch_config["max_batch_size"] if self.batch_config is not None else 1)
+
+            session = MultichannelSession(websocket, uid, audio_format, channels, sample_rate, make_child)
+            if not session.ready:                         # model load failed: ERROR already sent, socket closed
+                session.cleanup()
+                return False
+            if self.batch_config is not None and self.single_model and device_index not in ServeClientHIP.BATCH_WORKERS:
+                from .batching import BatchInferenceWorker
+                with ServeClientHIP.MODELS_LOCK:
+                    if device_index not in ServeClientHIP.BATCH_WORKERS:
+                        worker = BatchInferenceWorker(transcriber=session.children[0].transcriber, lanes=getattr(self, "batch_lanes", 2),
+                                                      **self.batch_config)
+                        worker.start()
+                        ServeClientHIP.BATCH_WORKERS[device_index] = worker
+        except Exception as e:  # noqa: BLE001 — as initialize_client: log and leave the connection unregistered
+            logging.error(e)
+            return False
+        if self.segment_post_processor is not None:
+            session.segment_post_processor = self.segment_post_processor
+        self.client_manager.add_client(websocket, session)
+        self.audio_formats[websocket] = audio_format
+        self.wire_sessions.add(websocket)
+        wl_metrics.track_connection_opened()
+        return True
+
     # ---- socket bytes -> PCM (SURVEY.md §8a row 1) ---------------------------------------------------------------
     def get_audio_from_websocket(self, websocket):
         """One packet -> float32 PCM in [-1, 1); ``False`` on the END_OF_AUDIO terminator (server.py:365-385)."""
@@ -350,6 +439,8 @@ class TranscriptionServer:
                 return False
             audio_format = options.get("audio_format", "float32")
             sample_rate, channels = options.get("sample_rate", self.RATE), options.get("channels", 1)
+            if options.get("multichannel") is True:
+                return self.open_multichannel(websocket, options, audio_format, channels, sample_rate, faster_whisper_custom_model_path)
             wire = sample_rate != self.RATE or channels != 1 or audio_format in WIRE_ONLY_FORMATS
             if audio_format not in AUDIO_FORMATS and not (wire and audio_format in WIRE_ONLY_FORMATS):
                 raise ValueError(f"Unsupported audio_format: {audio_format}")

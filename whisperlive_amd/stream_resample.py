@@ -214,3 +214,54 @@ class StreamResampler:
 
     def flush(self) -> np.ndarray:
         return self.feed(np.zeros((0, self.channels), self.dtype), flush=True)
+
+
+class ChannelStreamResamplers:
+    """The host route and CPU oracle of a MULTICHANNEL live stream (include/wlx.h wlx_ring_group_append_frames): one StreamResampler
+    per channel over that channel's column of the de-interleaved packet — no mean, no division. All channels see the same cutting, so
+    J, M and `closed` are the same on every one of them; `advance` keeps them in step while the device computes the samples."""
+
+    def __init__(self, audio_format: Union[str, int], channels: int, rate: int):
+        self.code, self.dtype = check_format(audio_format, channels, rate)
+        self.channels, self.rate = channels, rate
+        self.lanes = [StreamResampler(audio_format, 1, rate) for _ in range(channels)]
+
+    @property
+    def frame_bytes(self) -> int:
+        return self.channels * self.dtype.itemsize
+
+    @property
+    def J(self) -> int:
+        return self.lanes[0].J
+
+    @property
+    def M(self) -> int:
+        return self.lanes[0].M
+
+    @property
+    def closed(self) -> bool:
+        return self.lanes[0].closed
+
+    def frames(self, raw) -> np.ndarray:
+        """an interleaved packet -> [n, channels]; ValueError when it does not hold whole frames"""
+        if isinstance(raw, (bytes, bytearray, memoryview)):
+            if len(raw) % self.frame_bytes:
+                raise ValueError(f"packet of {len(raw)} bytes is not a whole number of {self.frame_bytes}-byte frames")
+            x = np.frombuffer(raw, dtype=self.dtype)
+        else:
+            x = np.asarray(raw)
+            if x.dtype != self.dtype:
+                raise ValueError(f"packet of dtype {x.dtype}, the stream's format takes {self.dtype}")
+            if x.size % self.channels:
+                raise ValueError(f"packet of {x.size} samples is not a whole number of {self.channels}-channel frames")
+        return x.reshape(-1, self.channels)
+
+    def feed(self, raw, flush: bool = False) -> list:
+        """-> per channel, the packet's new 16 kHz samples (float32)"""
+        x = self.frames(raw)
+        return [ln.feed(np.ascontiguousarray(x[:, c]), flush) for c, ln in enumerate(self.lanes)]
+
+    def advance(self, raw, flush: bool = False) -> int:
+        """book-keeping only: -> how many outputs per channel the packet completed"""
+        x = self.frames(raw)
+        return [ln.advance(np.ascontiguousarray(x[:, c]), flush) for c, ln in enumerate(self.lanes)][0]
