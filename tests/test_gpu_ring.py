@@ -21,17 +21,26 @@ def eng(gpu):
 
 
 class HostBuffer:
-    """ServeClientBase.add_frames (whisperlive_amd/serve_client.py, the reference's base.py:173-198) on a bare numpy buffer"""
+    """ServeClientBase.add_frames (whisperlive_amd/serve_client.py, the reference's base.py:173-198) on a bare numpy buffer. With a
+    `capacity`, it also restates the store's growth rule (csrc/ring.hip make_room: double until the packet fits behind the kept
+    samples) and counts `trims` and `growths`."""
 
-    def __init__(self):
+    def __init__(self, max_resident=45 * 16000, trim=30 * 16000, capacity=None):
         self.buf, self.base = None, 0
+        self.max_resident, self.trim, self.cap = max_resident, trim, capacity
+        self.trims = self.growths = 0
 
     def add(self, pkt):
         dropped = 0
-        if self.buf is not None and self.buf.shape[0] > 45 * 16000:
-            self.buf, dropped = self.buf[30 * 16000:], 30 * 16000
+        if self.buf is not None and self.buf.shape[0] > self.max_resident:
+            self.buf, dropped = self.buf[self.trim:], self.trim
             self.base += dropped
+            self.trims += 1
         self.buf = pkt.copy() if self.buf is None else np.concatenate((self.buf, pkt))
+        if self.cap is not None and self.buf.shape[0] > self.cap:
+            while self.cap < self.buf.shape[0]:
+                self.cap *= 2
+            self.growths += 1
         return dropped
 
 
@@ -62,6 +71,68 @@ def test_ring_follows_the_reference_buffer_rule_and_holds_the_samples(eng):
             slot.logmel_ring(ring, [(host.base, host.base + host.buf.shape[0] + 1)])
     finally:
         slot.close(); one.close(); ring.close()
+
+
+SMALL = dict(capacity=700, max_resident=4000, trim=2000)       # a ring that grows and trims within a few thousand samples
+
+
+def test_small_hot_ring_trims_and_grows_by_the_rule_and_holds_the_samples(eng):
+    """capacity 700, cap 4000 / trim 2000: ten packets cross the capacity four times and the trim rule twice (one packet is larger
+    than max_resident, one is empty); after each the state follows the numpy rule and the whole resident range reads back bit for bit."""
+    ring = eng.create_ring(capacity_samples=SMALL["capacity"])
+    slot = eng.create_slot(1, 5)
+    one = eng.create_slot(1, 5)
+    host = HostBuffer(SMALL["max_resident"], SMALL["trim"], SMALL["capacity"])
+    rng = np.random.default_rng(2)
+    try:
+        for i, n in enumerate([300, 1, 699, 700, 701, 2500, 0, 37, 4100, 5]):
+            pkt = (rng.standard_normal(n) * 0.1).astype(np.float32)
+            want_drop = host.add(pkt)
+            dropped, base, resident = ring.append(pkt, max_resident=SMALL["max_resident"], trim=SMALL["trim"])
+            assert (dropped, base, resident) == (want_drop, host.base, host.buf.shape[0]) and ring.state() == (base, resident), ("packet", i)
+            T = slot.logmel_ring(ring, [(base, base + resident)])
+            got = slot.features()
+            assert one.logmel(host.buf) == T
+            assert np.array_equal(got, one.features()), ("packet", i)
+        assert (host.trims, host.growths) == (2, 4)
+    finally:
+        slot.close(); one.close(); ring.close()
+
+
+@pytest.mark.parametrize("kind", ["mono", "group"])
+def test_a_trim_waits_for_the_reader_launched_before_it(eng, kind):
+    """logmel_ring is launched on the whole resident range and NOT waited for; the next append trims (the survivors move to the front of
+    the memory the launch reads). The features fetched afterwards are those of the samples the reader was launched on. mono: a float
+    ring; group: two lanes of 48 kHz int16, the reader on lane 1."""
+    from whisperlive_amd import _lib
+    slot = eng.create_slot(1, 5)
+    one = eng.create_slot(1, 5)
+    rng = np.random.default_rng(4)
+    kw = dict(max_resident=SMALL["max_resident"], trim=SMALL["trim"])
+    if kind == "mono":
+        store = ring = eng.create_ring(capacity_samples=SMALL["capacity"])
+
+        def append(n):
+            pkt = (rng.standard_normal(n) * 0.1).astype(np.float32)
+            return (pkt,) + ring.append(pkt, **kw)
+    else:
+        store = eng.create_ring_group(_lib.PCM_S16, 2, 48000, SMALL["capacity"])
+        ring = store.lane(1)
+
+        def append(n):
+            new, dropped, base, resident = store.append_frames(rng.integers(-9000, 9000, size=(3 * n, 2), dtype=np.int16), **kw)
+            return new[1].copy(), dropped, base, resident
+    try:
+        before, dropped, base, resident = append(4500)
+        assert (dropped, base) == (0, 0) and resident == before.shape[0] > SMALL["max_resident"]
+        T = slot.logmel_ring(ring, [(base, base + resident)])
+        _, dropped, base, after = append(100)                                  # trims under the pending reader
+        assert (dropped, base) == (SMALL["trim"], SMALL["trim"]) and after < resident
+        got = slot.features()
+        assert one.logmel(before) == T
+        assert np.array_equal(got, one.features())
+    finally:
+        slot.close(); one.close(); store.close()
 
 
 @pytest.mark.parametrize("case", ["one", "ragged", "tiny", "many"])

@@ -118,37 +118,35 @@ struct Slot {
     float align_pass_ms = 0.f, align_post_ms = 0.f;
 };
 
-// Device-resident PCM ring of one client stream (include/wlx.h: wlx_ring_*; engine.hip). Samples [base, base + resident) of the
-// stream live contiguously at buf[0 .. resident): a trim moves the survivors to the front (once per 30 s of audio: <= 1 MB device to
-// device), so every reader sees plain contiguous memory. Writers: the socket thread (append / trim). Readers: kernels of the VAD
-// object's stream and of a slot's stream; `mu` serialises the calls, `last_read` (recorded on the reader's stream behind its launch)
-// is what a trim waits for before it moves data under a reader that was launched but has not run yet.
+// Device-resident PCM of one client stream (include/wlx.h: wlx_ring_*, wlx_ring_group_*; ring.hip). A Ring is what a READER needs:
+// samples [base, base + resident) of the stream live contiguously at buf[0 .. resident) (a trim moves the survivors to the front, once
+// per 30 s of audio: <= 1 MB device to device), so every reader sees plain contiguous memory. Readers are kernels of the VAD object's,
+// the speaker engine's and a slot's stream; `mu` serialises them against the writer, `last_read` (recorded on the reader's stream
+// behind its launch) is what a trim or a growth waits for before it moves data under a reader that was launched but has not run yet.
+struct RingStore;
 struct Ring {
     std::mutex mu;
     int device = 0;
-    float* buf = nullptr; size_t cap = 0;
+    float* buf = nullptr;                                   // this lane's row of the store's allocation
     int64_t base = 0, resident = 0;
-    hipStream_t stream = nullptr;
     hipEvent_t last_read = nullptr; bool read_pending = false; hipStream_t last_read_stream = nullptr;
-    // the live path's wire format (wlx_ring_set_format): packets arrive as the client sent them and wlx_ring_append_frames resamples
-    // them into buf; for such a ring base + resident == fmt.M at all times. `appended`: some append call has succeeded.
-    bool has_format = false, appended = false;
-    ResampleStream fmt{};
-    // a LANE of a ring group (below): buf points into the group's allocation, `stream` is null, the group appends and owns the
-    // memory; the ring's own append / set_format entry points refuse it and wlx_ring_destroy leaves it alone
-    struct RingGroup* group = nullptr;
+    RingStore* store = nullptr;
 };
 
-// Ring group of one multichannel client stream (include/wlx.h: wlx_ring_group_*; engine.hip): `channels` lanes in ONE allocation
-// [channels][cap], filled by one launch of the split stream form of resample.hip per packet. Every lane is a Ring for its readers
-// (own mutex, own last_read event); base and resident are equal on all lanes at all times. The group's append takes `mu`, then the
-// lanes' mutexes in lane order; a reader only ever holds ONE lane's mutex, so the order cannot cycle.
-struct RingGroup {
+// The WRITE side of every ring: `lanes` rings in ONE allocation [lanes][cap], filled by one append (the socket thread). A mono ring
+// (wlx_ring_create) is a store with one lane that down-mixes: the caller's handle is that lane (`lone`), packets are 16 kHz floats or,
+// after wlx_ring_set_format, wire frames. A ring group (wlx_ring_group_create) is a store with one lane per channel in `split` mode, one
+// launch of the split stream form of resample.hip per packet; its lanes are borrowed by readers and refuse the writer entry points.
+// base and resident are equal on all lanes at all times, and base + resident == fmt.M with a format. Lock order: the store's `mu`, then
+// the lanes' `mu` in lane order; a reader only ever holds ONE lane's mutex, so the order cannot cycle.
+struct RingStore {
     std::mutex mu;
-    int device = 0, channels = 0;
-    float* buf = nullptr; size_t cap = 0;                   // [channels][cap]
+    int device = 0;
+    float* buf = nullptr; size_t cap = 0;                   // [lanes][cap]
     hipStream_t stream = nullptr;
     std::vector<wlx_ring*> lanes;
+    bool lone = false, split = false;
+    bool has_format = false, appended = false;              // `appended`: some append call has succeeded (no format after that)
     ResampleStream fmt{};                                   // J, M, the tail of whole interleaved frames: shared by all lanes
 };
 
@@ -175,7 +173,7 @@ struct Engine {
 
 struct wlx_engine : public wlx::Engine {};
 struct wlx_ring : public wlx::Ring {};
-struct wlx_ring_group : public wlx::RingGroup {};
+struct wlx_ring_group : public wlx::RingStore {};   // (also the store behind a mono wlx_ring)
 
 // ------------------------------------------------------------------------------------------------
 // shared between engine.hip (slots, streams), engine_decode.hip (decode) and engine_debug.hip (hooks)

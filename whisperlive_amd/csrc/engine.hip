@@ -1,6 +1,6 @@
 // engine.hip — C-ABI (include/wlx.h) over the gfx950 kernels: weight ingestion/repacking, slots
-// (one HIP stream + all scratch per concurrent stream), the PCM ring, and the host orchestration of
-// log-mel -> encoder. Decode (prefill -> hipGraph-replayed steps): engine_decode.hip; wlx_debug_* hooks: engine_debug.hip.
+// (one HIP stream + all scratch per concurrent stream), and the host orchestration of log-mel -> encoder.
+// Decode (prefill -> hipGraph-replayed steps): engine_decode.hip; the PCM rings' write side: ring.hip; wlx_debug_* hooks: engine_debug.hip.
 #include "engine.h"
 #include <atomic>
 #include <algorithm>
@@ -715,268 +715,7 @@ extern "C" int32_t wlx_pcm_get(wlx_engine* e, int32_t slot, int32_t item, float*
     return WLX_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// PCM ring (include/wlx.h): whisper_live/backend/base.py:173-234 on the device
-extern "C" int32_t wlx_ring_create(wlx_engine* e, int64_t capacity_samples, wlx_ring** out) {
-    if (!e || !out) return set_error(WLX_ERR_ARG, "null argument");
-    if (capacity_samples < 0 || capacity_samples > 16000LL * 3600) return set_error(WLX_ERR_ARG, "ring capacity out of range");
-    CK(hipSetDevice(e->device));
-    wlx_ring* r = new wlx_ring();
-    r->device = e->device;
-    r->cap = (size_t)(capacity_samples > 0 ? capacity_samples : 16000LL * 64);
-    hipError_t he = hipMalloc(reinterpret_cast<void**>(&r->buf), r->cap * sizeof(float));   // owned by name: wlx_ring_append grows it
-    if (he == hipSuccess) he = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&r->last_read, hipEventDisableTiming);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        wlx_ring_destroy(r);
-        return set_error(WLX_ERR_HIP, "wlx_ring_create: %s", hipGetErrorString(he));
-    }
-    *out = r;
-    return WLX_OK;
-}
-
-static void ring_free(wlx_ring* r) {
-    (void)hipSetDevice(r->device);
-    if (r->read_pending && r->last_read) (void)hipEventSynchronize(r->last_read);
-    if (r->stream) { (void)hipStreamSynchronize(r->stream); (void)hipStreamDestroy(r->stream); }
-    if (r->last_read) (void)hipEventDestroy(r->last_read);
-    if (r->buf) (void)hipFree(r->buf);
-    resample_stream_free(r->fmt);
-    delete r;
-}
-
-extern "C" void wlx_ring_destroy(wlx_ring* r) {
-    if (!r || r->group) return;                     // a lane is borrowed: wlx_ring_group_destroy frees it
-    ring_free(r);
-}
-
-// readers launched but possibly not run yet: wait for them before data moves under them
-static int ring_wait_readers(Ring* r) {
-    if (r->read_pending) { CK(hipEventSynchronize(r->last_read)); r->read_pending = false; }
-    return WLX_OK;
-}
-
-// the front half of every append: the trim rule of add_frames, then room for n more samples behind the resident ones
-static int ring_make_room(Ring* r, int64_t n, int64_t max_resident, int64_t trim, int64_t* dropped_out) {
-    int64_t dropped = 0;
-    if (max_resident > 0 && trim > 0 && r->resident > max_resident) {
-        // add_frames (base.py:191-198): the buffer is past its cap — the oldest `trim` samples go, the rest moves to the front
-        dropped = std::min<int64_t>(trim, r->resident);
-        const int64_t keep = r->resident - dropped;
-        CKR(ring_wait_readers(r));
-        for (int64_t done = 0; done < keep; done += dropped) {                      // pieces of <= `dropped` samples: source and destination never overlap
-            const int64_t m = std::min<int64_t>(dropped, keep - done);
-            CK(hipMemcpyAsync(r->buf + done, r->buf + dropped + done, (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, r->stream));
-        }
-        r->base += dropped;
-        r->resident = keep;
-    }
-    if ((size_t)(r->resident + n) > r->cap) {                                      // a packet larger than the head-room: grow (rare)
-        size_t cap = r->cap;
-        while (cap < (size_t)(r->resident + n)) cap *= 2;
-        float* nb = nullptr;
-        CK(hipMalloc(reinterpret_cast<void**>(&nb), cap * sizeof(float)));       // replaces r->buf, which is freed below: no free list
-        CKR(ring_wait_readers(r));
-        CK(hipMemcpyAsync(nb, r->buf, (size_t)r->resident * sizeof(float), hipMemcpyDeviceToDevice, r->stream));
-        CK(hipStreamSynchronize(r->stream));
-        CK(hipFree(r->buf));
-        r->buf = nb; r->cap = cap;
-    }
-    *dropped_out = dropped;
-    return WLX_OK;
-}
-
-extern "C" int32_t wlx_ring_append(wlx_ring* r, const float* samples, int64_t n, int64_t max_resident, int64_t trim,
-                                   int64_t* dropped_out, int64_t* base_out, int64_t* resident_out) {
-    if (!r || n < 0 || (n > 0 && !samples)) return set_error(WLX_ERR_ARG, "wlx_ring_append: bad argument");
-    if (n > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
-    if (r->group) return set_error(WLX_ERR_STATE, "wlx_ring_append: the ring is a lane of a ring group (wlx_ring_group_append_frames)");
-    std::lock_guard<std::mutex> lk(r->mu);
-    if (r->has_format) return set_error(WLX_ERR_STATE, "wlx_ring_append: the ring has a wire format (wlx_ring_append_frames)");
-    CK(hipSetDevice(r->device));
-    int64_t dropped = 0;
-    CKR(ring_make_room(r, n, max_resident, trim, &dropped));
-    if (n > 0) CK(hipMemcpyAsync(r->buf + r->resident, samples, (size_t)n * sizeof(float), hipMemcpyHostToDevice, r->stream));
-    CK(hipStreamSynchronize(r->stream));            // the caller's buffer may be reused; readers launched after this return see the samples
-    r->resident += n;
-    r->appended = true;
-    if (dropped_out) *dropped_out = dropped;
-    if (base_out) *base_out = r->base;
-    if (resident_out) *resident_out = r->resident;
-    return WLX_OK;
-}
-
-// ---- the live path's wire format (include/wlx.h): the packets are resampled into the ring by the stream form of resample.hip
-extern "C" int32_t wlx_ring_set_format(wlx_ring* r, int32_t sample_format, int32_t channels, int32_t sample_rate) {
-    if (!r) return set_error(WLX_ERR_ARG, "null ring");
-    CKR(resample_stream_check(sample_format, channels, sample_rate));
-    if (r->group) return set_error(WLX_ERR_STATE, "wlx_ring_set_format: the ring is a lane of a ring group, which has the format");
-    std::lock_guard<std::mutex> lk(r->mu);
-    if (r->has_format) return set_error(WLX_ERR_STATE, "wlx_ring_set_format: the ring has a format already");
-    if (r->appended || r->resident > 0 || r->base > 0) return set_error(WLX_ERR_STATE, "wlx_ring_set_format: the ring has been appended to");
-    CKR(resample_stream_open(r->device, sample_format, channels, sample_rate, &r->fmt));
-    r->has_format = true;
-    return WLX_OK;
-}
-
-extern "C" int32_t wlx_ring_append_frames(wlx_ring* r, const void* frames, int64_t n_frames, int32_t flush, int64_t max_resident,
-                                          int64_t trim, float* new_out, int64_t cap, int64_t* n_new_out, int64_t* dropped_out,
-                                          int64_t* base_out, int64_t* resident_out) {
-    if (!r || n_frames < 0 || (n_frames > 0 && !frames)) return set_error(WLX_ERR_ARG, "wlx_ring_append_frames: bad argument");
-    if (new_out && cap < 0) return set_error(WLX_ERR_ARG, "wlx_ring_append_frames: negative capacity");
-    if (r->group) return set_error(WLX_ERR_STATE, "wlx_ring_append_frames: the ring is a lane of a ring group (wlx_ring_group_append_frames)");
-    std::lock_guard<std::mutex> lk(r->mu);
-    if (!r->has_format) return set_error(WLX_ERR_STATE, "wlx_ring_append_frames: the ring has no wire format (wlx_ring_set_format)");
-    ResampleStream& rs = r->fmt;
-    if (rs.closed) return set_error(WLX_ERR_STATE, "wlx_ring_append_frames: the stream has been flushed");
-    if (n_frames > (1LL << 50) - rs.J) return set_error(WLX_ERR_ARG, "frame count out of range");
-    const int64_t n_new = resample_stream_next(rs, n_frames, flush);
-    if (n_new > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
-    if (new_out && cap < n_new) return set_error(WLX_ERR_ARG, "wlx_ring_append_frames: %lld new samples, room for %lld", (long long)n_new, (long long)cap);
-    CK(hipSetDevice(r->device));
-    CKR(resample_stream_reserve(rs, n_frames));
-    int64_t dropped = 0;
-    CKR(ring_make_room(r, n_new, max_resident, trim, &dropped));
-    float* dst = r->buf + r->resident;
-    CKR(resample_stream_enqueue(rs, frames, n_frames, flush, dst, r->stream));
-    if (new_out && n_new > 0) CK(hipMemcpyAsync(new_out, dst, (size_t)n_new * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-    CK(hipStreamSynchronize(r->stream));            // ONE wait: the caller's frames may be reused, new_out is filled, readers see the samples
-    r->resident += n_new;
-    r->appended = true;
-    if (n_new_out) *n_new_out = n_new;
-    if (dropped_out) *dropped_out = dropped;
-    if (base_out) *base_out = r->base;
-    if (resident_out) *resident_out = r->resident;
-    return WLX_OK;
-}
-
-extern "C" int32_t wlx_ring_state(wlx_ring* r, int64_t* base_out, int64_t* resident_out) {
-    if (!r) return set_error(WLX_ERR_ARG, "null ring");
-    std::lock_guard<std::mutex> lk(r->mu);
-    if (base_out) *base_out = r->base;
-    if (resident_out) *resident_out = r->resident;
-    return WLX_OK;
-}
-
-// ---- ring group (include/wlx.h): the lanes of one multichannel live stream, filled by ONE launch of the split stream form per packet
-extern "C" void wlx_ring_group_destroy(wlx_ring_group* g) {
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    for (wlx_ring* r : g->lanes) {
-        r->buf = nullptr;                           // part of g->buf
-        ring_free(r);                               // waits for the lane's pending reader
-    }
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    if (g->buf) (void)hipFree(g->buf);
-    resample_stream_free(g->fmt);
-    delete g;
-}
-
-extern "C" int32_t wlx_ring_group_create(wlx_engine* e, int64_t capacity_samples, int32_t sample_format, int32_t channels,
-                                         int32_t sample_rate, wlx_ring_group** out) {
-    if (!e || !out) return set_error(WLX_ERR_ARG, "null argument");
-    if (capacity_samples < 0 || capacity_samples > 16000LL * 3600) return set_error(WLX_ERR_ARG, "ring capacity out of range");
-    CKR(resample_stream_check(sample_format, channels, sample_rate));
-    CK(hipSetDevice(e->device));
-    wlx_ring_group* g = new wlx_ring_group();
-    g->device = e->device; g->channels = channels;
-    g->cap = (size_t)(capacity_samples > 0 ? capacity_samples : 16000LL * 64);
-    hipError_t he = hipMalloc(reinterpret_cast<void**>(&g->buf), (size_t)channels * g->cap * sizeof(float));   // owned by name: the append grows it
-    if (he == hipSuccess) he = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-    for (int c = 0; c < channels && he == hipSuccess; ++c) {
-        wlx_ring* r = new wlx_ring();
-        r->device = e->device; r->group = g; r->buf = g->buf + (size_t)c * g->cap; r->cap = g->cap;
-        g->lanes.push_back(r);
-        he = hipEventCreateWithFlags(&r->last_read, hipEventDisableTiming);
-    }
-    int rc = WLX_OK;
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        rc = set_error(WLX_ERR_HIP, "wlx_ring_group_create: %s", hipGetErrorString(he));
-    } else {
-        rc = resample_stream_open(e->device, sample_format, channels, sample_rate, &g->fmt);
-    }
-    if (rc != WLX_OK) { wlx_ring_group_destroy(g); return rc; }
-    *out = g;
-    return WLX_OK;
-}
-
-extern "C" int32_t wlx_ring_group_lane(wlx_ring_group* g, int32_t channel, wlx_ring** out) {
-    if (!g || !out) return set_error(WLX_ERR_ARG, "null argument");
-    if (channel < 0 || channel >= g->channels) return set_error(WLX_ERR_ARG, "wlx_ring_group_lane: lane %d outside 0..%d", channel, g->channels - 1);
-    *out = g->lanes[(size_t)channel];
-    return WLX_OK;
-}
-
-// ring_make_room for all lanes in lockstep (the lanes' mutexes are held): ONE trim decision, ONE growth
-static int group_make_room(RingGroup* g, int64_t n, int64_t max_resident, int64_t trim, int64_t* dropped_out) {
-    int64_t dropped = 0;
-    const int64_t resident = g->lanes[0]->resident;
-    int64_t keep = resident;
-    if (max_resident > 0 && trim > 0 && resident > max_resident) {
-        dropped = std::min<int64_t>(trim, resident);
-        keep = resident - dropped;
-        for (wlx_ring* r : g->lanes) CKR(ring_wait_readers(r));
-        for (wlx_ring* r : g->lanes)
-            for (int64_t done = 0; done < keep; done += dropped) {                  // pieces of <= `dropped` samples: source and destination never overlap
-                const int64_t m = std::min<int64_t>(dropped, keep - done);
-                CK(hipMemcpyAsync(r->buf + done, r->buf + dropped + done, (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, g->stream));
-            }
-        for (wlx_ring* r : g->lanes) { r->base += dropped; r->resident = keep; }
-    }
-    if ((size_t)(keep + n) > g->cap) {                                             // a packet larger than the head-room: grow (rare)
-        size_t cap = g->cap;
-        while (cap < (size_t)(keep + n)) cap *= 2;
-        float* nb = nullptr;
-        CK(hipMalloc(reinterpret_cast<void**>(&nb), (size_t)g->channels * cap * sizeof(float)));   // replaces g->buf, which is freed below
-        for (wlx_ring* r : g->lanes) CKR(ring_wait_readers(r));
-        for (int c = 0; c < g->channels && keep > 0; ++c)
-            CK(hipMemcpyAsync(nb + (size_t)c * cap, g->lanes[(size_t)c]->buf, (size_t)keep * sizeof(float), hipMemcpyDeviceToDevice, g->stream));
-        CK(hipStreamSynchronize(g->stream));
-        CK(hipFree(g->buf));
-        g->buf = nb; g->cap = cap;
-        for (int c = 0; c < g->channels; ++c) { g->lanes[(size_t)c]->buf = nb + (size_t)c * cap; g->lanes[(size_t)c]->cap = cap; }
-    }
-    *dropped_out = dropped;
-    return WLX_OK;
-}
-
-extern "C" int32_t wlx_ring_group_append_frames(wlx_ring_group* g, const void* frames, int64_t n_frames, int32_t flush, int64_t max_resident,
-                                                int64_t trim, float* new_out, int64_t cap, int64_t* n_new_out, int64_t* dropped_out,
-                                                int64_t* base_out, int64_t* resident_out) {
-    if (!g || n_frames < 0 || (n_frames > 0 && !frames)) return set_error(WLX_ERR_ARG, "wlx_ring_group_append_frames: bad argument");
-    if (new_out && cap < 0) return set_error(WLX_ERR_ARG, "wlx_ring_group_append_frames: negative capacity");
-    std::lock_guard<std::mutex> lk(g->mu);
-    ResampleStream& rs = g->fmt;
-    if (rs.closed) return set_error(WLX_ERR_STATE, "wlx_ring_group_append_frames: the stream has been flushed");
-    if (n_frames > (1LL << 50) - rs.J) return set_error(WLX_ERR_ARG, "frame count out of range");
-    const int64_t n_new = resample_stream_next(rs, n_frames, flush);
-    if (n_new > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
-    if (new_out && cap < n_new) return set_error(WLX_ERR_ARG, "wlx_ring_group_append_frames: %lld new samples per lane, room for %lld", (long long)n_new, (long long)cap);
-    std::vector<std::unique_lock<std::mutex>> held;             // no reader is launched on any lane while the group changes
-    held.reserve(g->lanes.size());
-    for (wlx_ring* r : g->lanes) held.emplace_back(r->mu);
-    CK(hipSetDevice(g->device));
-    CKR(resample_stream_reserve(rs, n_frames));
-    int64_t dropped = 0;
-    CKR(group_make_room(g, n_new, max_resident, trim, &dropped));
-    const int64_t resident = g->lanes[0]->resident;
-    float* dst = g->buf + resident;                             // lane c's write position is dst + c * g->cap
-    CKR(resample_stream_enqueue(rs, frames, n_frames, flush, dst, g->stream, (long long)g->cap));
-    if (new_out && n_new > 0)                                   // ONE copy back: row c = lane c's new samples, host row stride `cap`
-        CK(hipMemcpy2DAsync(new_out, (size_t)cap * sizeof(float), dst, g->cap * sizeof(float), (size_t)n_new * sizeof(float), (size_t)g->channels,
-                            hipMemcpyDeviceToHost, g->stream));
-    CK(hipStreamSynchronize(g->stream));            // ONE wait: the caller's frames may be reused, new_out is filled, readers see the samples
-    for (wlx_ring* r : g->lanes) { r->resident = resident + n_new; r->appended = true; }
-    if (n_new_out) *n_new_out = n_new;
-    if (dropped_out) *dropped_out = dropped;
-    if (base_out) *base_out = g->lanes[0]->base;
-    if (resident_out) *resident_out = resident + n_new;
-    return WLX_OK;
-}
-
+// the range reader of a PCM ring (ring.hip): the ring's mutex is held across the launch, `last_read` is what a later trim waits for
 extern "C" int32_t wlx_logmel_ring(wlx_engine* e, int32_t slot, int32_t item, wlx_ring* r, const int64_t* ranges, int32_t n_ranges,
                                    int32_t* n_frames_out) {
     SlotGuard sg_;

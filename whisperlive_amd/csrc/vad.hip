@@ -570,7 +570,7 @@ extern "C" int32_t wlx_vad_probs(wlx_vad* v, const float* pcm, int64_t n, float*
     return vad_run_batch(v, pl, probs_out, device_ms_out);
 }
 
-// The same on samples that are already in HBM: [start, start + n) of a client's PCM ring (engine.hip wlx_ring_*, include/wlx.h) — the
+// The same on samples that are already in HBM: [start, start + n) of a client's PCM ring (ring.hip wlx_ring_*, include/wlx.h) — the
 // gate of a streaming session reads the ring the socket thread filled, no second host-to-device copy.
 extern "C" int32_t wlx_vad_probs_resident(wlx_vad* v, wlx_ring* r, int64_t start, int64_t n, int32_t extra_zero_windows, float* probs_out, int32_t cap,
                                           int32_t* n_windows_out, float* device_ms_out) {

@@ -104,6 +104,40 @@ def resample_supported(sample_rate: int, channels: int = 1) -> bool:
     return 4 * (2 * half_len + 1 + span) <= _lib.RESAMPLE_MAX_LDS
 
 
+def _packet(raw, frame_bytes: int):
+    """a packet (bytes, or a C-contiguous array of wire samples) -> (object to keep alive, address, frames); ValueError unless whole frames"""
+    if isinstance(raw, np.ndarray):
+        raw = np.ascontiguousarray(raw)
+        nbytes, ptr = raw.nbytes, raw.ctypes.data
+    else:
+        raw = bytes(raw)
+        nbytes, ptr = len(raw), C.cast(C.c_char_p(raw), C.c_void_p).value
+    if nbytes % frame_bytes:
+        raise ValueError(f"packet of {nbytes} bytes is not a whole number of {frame_bytes}-byte frames")
+    return raw, ptr, nbytes // frame_bytes
+
+
+def _sample_bytes(fmt: int) -> int:
+    """bytes of one wire sample (_lib.PCM_*; the 8-bit formats are every other code the library takes)"""
+    return {_lib.PCM_F32: 4, _lib.PCM_S16: 2}.get(int(fmt), 1)
+
+
+def _append_frames(ring, entry, rows: int, raw, flush: bool, max_resident: Optional[int], trim: Optional[int]):
+    """One packet to `entry` (wlx_ring_append_frames / wlx_ring_group_append_frames) of `ring` (a PcmRing or a PcmRingGroup with a
+    wire format) -> (new[rows][n]: the new 16 kHz samples, one row per lane, dropped, base, resident)"""
+    raw, ptr, n = _packet(raw, ring._frame_bytes)
+    want, have = C.c_int64(0), C.c_int64(0)
+    check(ring.lib.wlx_resample_stream_count(ring.format[2], ring._frames_seen + n, 1, C.byref(want)))   # the flushed count bounds the other
+    check(ring.lib.wlx_resample_stream_count(ring.format[2], ring._frames_seen, 0, C.byref(have)))
+    cap = max(want.value - have.value, 0)
+    out = np.empty((rows, cap), np.float32)
+    k, d, b, r = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    check(entry(ring._h, ptr if n else None, n, 1 if flush else 0, ring.MAX_RESIDENT if max_resident is None else int(max_resident),
+                ring.TRIM if trim is None else int(trim), _f32p(out), cap, C.byref(k), C.byref(d), C.byref(b), C.byref(r)))
+    ring._frames_seen += n
+    return out[:, : k.value], d.value, b.value, r.value
+
+
 class PcmRing:
     """The device-side mirror of ServeClientBase.frames_np (whisper_live/backend/base.py:173-234): a client's packets are appended
     ONCE, the VAD gate and the log-mel front end read them in HBM. Positions are absolute stream sample positions."""
@@ -126,35 +160,15 @@ class PcmRing:
         """Give the ring a wire format (_lib.PCM_*; once, before the first append): packets then go through append_frames."""
         check(self.lib.wlx_ring_set_format(self._h, int(fmt), int(channels), int(rate)))
         self.format = (int(fmt), int(channels), int(rate))
-        self._frame_bytes = int(channels) * {_lib.PCM_F32: 4, _lib.PCM_S16: 2}.get(int(fmt), 1)
+        self._frame_bytes = int(channels) * _sample_bytes(fmt)
         self._frames_seen = 0
 
     def append_frames(self, raw, flush: bool = False, max_resident: Optional[int] = None, trim: Optional[int] = None):
         """One packet in the wire format (bytes, or a C-contiguous array of wire samples) -> (the packet's new 16 kHz samples, samples
         dropped by this call, first resident position, resident count). The packet crosses PCIe as it is; the new samples come back
         in the same wait. flush=True completes the stream to the one-shot length and closes it."""
-        fb = self._frame_bytes
-        if isinstance(raw, np.ndarray):
-            raw = np.ascontiguousarray(raw)
-            nbytes, ptr = raw.nbytes, raw.ctypes.data
-        else:
-            raw = bytes(raw)
-            nbytes, ptr = len(raw), C.cast(C.c_char_p(raw), C.c_void_p).value
-        if nbytes % fb:
-            raise ValueError(f"packet of {nbytes} bytes is not a whole number of {fb}-byte frames")
-        n = nbytes // fb
-        want = C.c_int64(0)
-        check(self.lib.wlx_resample_stream_count(self.format[2], self._frames_seen + n, 1, C.byref(want)))   # the flushed count bounds the other
-        have = C.c_int64(0)
-        check(self.lib.wlx_resample_stream_count(self.format[2], self._frames_seen, 0, C.byref(have)))
-        out = np.empty(max(want.value - have.value, 0), np.float32)
-        k, d, b, r = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(self.lib.wlx_ring_append_frames(self._h, ptr if n else None, n, 1 if flush else 0,
-                                              self.MAX_RESIDENT if max_resident is None else int(max_resident),
-                                              self.TRIM if trim is None else int(trim), _f32p(out), out.shape[0], C.byref(k),
-                                              C.byref(d), C.byref(b), C.byref(r)))
-        self._frames_seen += n
-        return out[: k.value], d.value, b.value, r.value
+        new, d, b, r = _append_frames(self, self.lib.wlx_ring_append_frames, 1, raw, flush, max_resident, trim)
+        return new[0], d, b, r
 
     def state(self) -> Tuple[int, int]:
         b, r = C.c_int64(0), C.c_int64(0)
@@ -165,19 +179,6 @@ class PcmRing:
         if getattr(self, "_h", None):
             self.lib.wlx_ring_destroy(self._h)
             self._h = None
-
-
-def _packet(raw, frame_bytes: int):
-    """a packet (bytes, or a C-contiguous array of wire samples) -> (object to keep alive, address, frames); ValueError unless whole frames"""
-    if isinstance(raw, np.ndarray):
-        raw = np.ascontiguousarray(raw)
-        nbytes, ptr = raw.nbytes, raw.ctypes.data
-    else:
-        raw = bytes(raw)
-        nbytes, ptr = len(raw), C.cast(C.c_char_p(raw), C.c_void_p).value
-    if nbytes % frame_bytes:
-        raise ValueError(f"packet of {nbytes} bytes is not a whole number of {frame_bytes}-byte frames")
-    return raw, ptr, nbytes // frame_bytes
 
 
 class _PcmRingLane(PcmRing):
@@ -213,7 +214,7 @@ class PcmRingGroup:
         self.device = getattr(engine, "device", 0)
         self.format = (int(fmt), int(channels), int(rate))
         self.channels = int(channels)
-        self._frame_bytes = self.channels * {_lib.PCM_F32: 4, _lib.PCM_S16: 2}.get(int(fmt), 1)
+        self._frame_bytes = self.channels * _sample_bytes(fmt)
         self._frames_seen = 0
         h = C.c_void_p()
         check(self.lib.wlx_ring_group_create(engine._h, int(capacity_samples), int(fmt), self.channels, int(rate), C.byref(h)))
@@ -236,19 +237,7 @@ class PcmRingGroup:
         this call, first resident position, resident count — the same on every lane). flush=True completes the stream and closes it."""
         if not self._h:
             raise RuntimeError("the ring group is closed")
-        raw, ptr, n = _packet(raw, self._frame_bytes)
-        want, have = C.c_int64(0), C.c_int64(0)
-        check(self.lib.wlx_resample_stream_count(self.format[2], self._frames_seen + n, 1, C.byref(want)))   # the flushed count bounds the other
-        check(self.lib.wlx_resample_stream_count(self.format[2], self._frames_seen, 0, C.byref(have)))
-        cap = max(want.value - have.value, 0)
-        out = np.empty((self.channels, cap), np.float32)
-        k, d, b, r = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(self.lib.wlx_ring_group_append_frames(self._h, ptr if n else None, n, 1 if flush else 0,
-                                                    self.MAX_RESIDENT if max_resident is None else int(max_resident),
-                                                    self.TRIM if trim is None else int(trim), _f32p(out), cap, C.byref(k),
-                                                    C.byref(d), C.byref(b), C.byref(r)))
-        self._frames_seen += n
-        return out[:, : k.value], d.value, b.value, r.value
+        return _append_frames(self, self.lib.wlx_ring_group_append_frames, self.channels, raw, flush, max_resident, trim)
 
     def state(self) -> Tuple[int, int]:
         return self._lanes[0].state()

@@ -30,6 +30,28 @@ from . import vad as _vad
 from ._lib import WlxError as _WlxError
 
 
+def _wire_packet(wire, raw, flush: bool, device):
+    """One wire packet through `wire` (stream_resample: one stream or one per channel) -> (its new 16 kHz samples, ring_state).
+    `device(raw, flush)` gives them with the (dropped, base, resident) of its ring, and the host state only advances; where it
+    gives None the host resamples (ring_state None). ValueError for a packet that is not whole frames, before anything changes."""
+    wire.frames(raw)
+    done = device(raw, flush)
+    if done is None:
+        return wire.feed(raw, flush), None
+    wire.advance(raw, flush)
+    return done
+
+
+def _mirror_maker(session, maker: str, wire=None):
+    """The `maker` method of the session's engine (create_ring / create_ring_group) when the session may mirror its audio on the
+    device; None when the engine has none (a scripted one), WLX_PCM_RING=0, a batch worker takes the chunks as host arrays, or the
+    stream began on the host (`wire.J` > 0: a ring cannot join it half-way)."""
+    make = getattr(getattr(getattr(session, "transcriber", None), "engine", None), maker, None)
+    if os.environ.get("WLX_PCM_RING", "1") == "0" or ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS or (wire is not None and wire.J):
+        return None
+    return make
+
+
 class ServeClientBase:
     RATE = 16000
     SERVER_READY = "SERVER_READY"
@@ -112,13 +134,7 @@ class ServeClientBase:
         with self.lock:
             if wire.closed:
                 return
-            wire.frames(raw)                                 # whole frames, or ValueError before anything changes
-            done = self._wire_samples(raw, flush)
-            if done is None:
-                new, ring_state = wire.feed(raw, flush), None
-            else:
-                new, ring_state = done
-                wire.advance(raw, flush)
+            new, ring_state = _wire_packet(wire, raw, flush, self._wire_samples)
             trimmed = self._take_frames(new)
             if ring_state is not None:
                 self._wire_appended(new, trimmed, ring_state)
@@ -462,26 +478,14 @@ class ServeClientHIP(ServeClientBase):
             return
         try:
             if self._ring is None:
-                eng = getattr(getattr(self, "transcriber", None), "engine", None)
-                make = getattr(eng, "create_ring", None)
-                if make is None or os.environ.get("WLX_PCM_RING", "1") == "0" or (ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS):
+                make = _mirror_maker(self, "create_ring")
+                if make is None:
                     self._ring = False
                     return
                 self._ring = make()
-                self._ring_expect = 0
-            dropped, base, resident = self._ring.append(frame_np)
-            self._ring_expect += frame_np.shape[0] - dropped
-            if dropped != trimmed or resident != self.frames_np.shape[0] or base != int(round(self.frames_offset * self.RATE)):
-                raise RuntimeError(f"ring out of step with frames_np: dropped {dropped} vs {trimmed}, resident {resident} vs "
-                                   f"{self.frames_np.shape[0]}, base {base} vs {self.frames_offset * self.RATE}")
+            self._wire_appended(frame_np, trimmed, self._ring.append(frame_np))
         except Exception as e:  # noqa: BLE001
-            logging.warning(f"device PCM ring disabled for {self.client_uid}: {e}")
-            ring, self._ring = self._ring, False
-            if ring:
-                try:
-                    ring.close()
-                except Exception:  # noqa: BLE001
-                    pass
+            self._ring_off(e)
 
     def _ring_off(self, e):
         logging.warning(f"device PCM ring disabled for {self.client_uid}: {e}")
@@ -500,12 +504,8 @@ class ServeClientHIP(ServeClientBase):
             return None
         try:
             if self._ring is None:
-                eng = getattr(getattr(self, "transcriber", None), "engine", None)
-                make = getattr(eng, "create_ring", None)
-                if make is None or os.environ.get("WLX_PCM_RING", "1") == "0" or (ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS):
-                    self._ring = False
-                    return None
-                if self._wire.J:                             # the stream began on the host: a ring cannot join it half-way
+                make = _mirror_maker(self, "create_ring", self._wire)
+                if make is None:
                     self._ring = False
                     return None
                 self._ring = make()
@@ -517,7 +517,8 @@ class ServeClientHIP(ServeClientBase):
             return None
 
     def _wire_appended(self, new, trimmed, ring_state):
-        """The coherence check of _frames_appended for a packet the ring resampled itself (it is NOT appended a second time)."""
+        """The coherence check: the ring took the packet (appended by _frames_appended, or resampled by the ring itself) and made the
+        trim decision `frames_np` made."""
         dropped, base, resident = ring_state
         if dropped != trimmed or resident != self.frames_np.shape[0] or base != int(round(self.frames_offset * self.RATE)):
             self._ring_off(RuntimeError(f"ring out of step with frames_np: dropped {dropped} vs {trimmed}, resident {resident} vs "
@@ -707,10 +708,8 @@ class MultichannelSession:
             return None
         try:
             if self._group is None:
-                eng = getattr(getattr(self.children[0], "transcriber", None), "engine", None)
-                make = getattr(eng, "create_ring_group", None)
-                if (make is None or os.environ.get("WLX_PCM_RING", "1") == "0" or (ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS)
-                        or self._wire.J):        # (J > 0: the stream began on the host, a group cannot join it half-way)
+                make = _mirror_maker(self.children[0], "create_ring_group", self._wire)
+                if make is None:
                     self._group = False
                     for ch in self.children:
                         with ch.lock:
@@ -733,13 +732,7 @@ class MultichannelSession:
         with self.lock:
             if wire.closed or self._released:
                 return
-            wire.frames(raw)
-            done = self._group_samples(raw, flush)
-            if done is None:
-                news, ring_state = wire.feed(raw, flush), None
-            else:
-                news, ring_state = done
-                wire.advance(raw, flush)
+            news, ring_state = _wire_packet(wire, raw, flush, self._group_samples)
             for c, ch in enumerate(self.children):
                 ch.take_wire_samples(np.ascontiguousarray(news[c], dtype=np.float32), ring_state if ch._ring else None)
 

@@ -135,6 +135,22 @@ def check_format(audio_format: Union[str, int], channels: int, rate: int) -> Tup
     return ent
 
 
+def packet_frames(raw, dtype: np.dtype, channels: int) -> np.ndarray:
+    """a packet (bytes, or an array of wire samples, interleaved) -> [n, channels]; ValueError when it does not hold whole frames"""
+    if isinstance(raw, (bytes, bytearray, memoryview)):
+        fb = channels * dtype.itemsize
+        if len(raw) % fb:
+            raise ValueError(f"packet of {len(raw)} bytes is not a whole number of {fb}-byte frames")
+        x = np.frombuffer(raw, dtype=dtype)
+    else:
+        x = np.asarray(raw)
+        if x.dtype != dtype:
+            raise ValueError(f"packet of dtype {x.dtype}, the stream's format takes {dtype}")
+        if x.size % channels:
+            raise ValueError(f"packet of {x.size} samples is not a whole number of {channels}-channel frames")
+    return x.reshape(-1, channels)
+
+
 class StreamResampler:
     """One stream: J frames seen, M outputs emitted, the raw tail (the last <= reach frames, in the wire format)."""
 
@@ -153,18 +169,7 @@ class StreamResampler:
         return self.channels * self.dtype.itemsize
 
     def frames(self, raw) -> np.ndarray:
-        """a packet (bytes, or an array of wire samples) -> [n, channels]; ValueError when it does not hold whole frames"""
-        if isinstance(raw, (bytes, bytearray, memoryview)):
-            if len(raw) % self.frame_bytes:
-                raise ValueError(f"packet of {len(raw)} bytes is not a whole number of {self.frame_bytes}-byte frames")
-            x = np.frombuffer(raw, dtype=self.dtype)
-        else:
-            x = np.asarray(raw)
-            if x.dtype != self.dtype:
-                raise ValueError(f"packet of dtype {x.dtype}, the stream's format takes {self.dtype}")
-            if x.size % self.channels:
-                raise ValueError(f"packet of {x.size} samples is not a whole number of {self.channels}-channel frames")
-        return x.reshape(-1, self.channels)
+        return packet_frames(raw, self.dtype, self.channels)
 
     def _step(self, raw, flush: bool, compute: bool):
         if self.closed:
@@ -243,18 +248,7 @@ class ChannelStreamResamplers:
         return self.lanes[0].closed
 
     def frames(self, raw) -> np.ndarray:
-        """an interleaved packet -> [n, channels]; ValueError when it does not hold whole frames"""
-        if isinstance(raw, (bytes, bytearray, memoryview)):
-            if len(raw) % self.frame_bytes:
-                raise ValueError(f"packet of {len(raw)} bytes is not a whole number of {self.frame_bytes}-byte frames")
-            x = np.frombuffer(raw, dtype=self.dtype)
-        else:
-            x = np.asarray(raw)
-            if x.dtype != self.dtype:
-                raise ValueError(f"packet of dtype {x.dtype}, the stream's format takes {self.dtype}")
-            if x.size % self.channels:
-                raise ValueError(f"packet of {x.size} samples is not a whole number of {self.channels}-channel frames")
-        return x.reshape(-1, self.channels)
+        return packet_frames(raw, self.dtype, self.channels)
 
     def feed(self, raw, flush: bool = False) -> list:
         """-> per channel, the packet's new 16 kHz samples (float32)"""
