@@ -1,4 +1,5 @@
-// engine.h — host-side state of libwlx: weights in kernel layout, per-slot device buffers.
+// engine.h — host-side state of libwlx: weights in kernel layout, per-slot device buffers, the device PCM rings, and PcmLease, the
+// one way an engine on another stream reads audio that is resident in a slot or a ring.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -71,7 +72,7 @@ struct Slot {
     LogmelChunk *h_chunks = nullptr, *d_chunks = nullptr;
     long long *h_crng = nullptr, *d_crng = nullptr;
     hipEvent_t ck_staged = nullptr; bool ck_pending = false;
-    hipEvent_t ev_pcm = nullptr;                     // recorded on `stream` for a reader on another stream (vad.hip wlx_vad_probs_pcm)
+    hipEvent_t ev_pcm = nullptr;                     // recorded on `stream` for a reader on another stream (engine.hip PcmLease::order)
     // encoder
     half_t *featT = nullptr, *h1 = nullptr, *ln = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr,
            *attn = nullptr, *h2 = nullptr, *enc16 = nullptr;
@@ -121,8 +122,9 @@ struct Slot {
 // Device-resident PCM of one client stream (include/wlx.h: wlx_ring_*, wlx_ring_group_*; ring.hip). A Ring is what a READER needs:
 // samples [base, base + resident) of the stream live contiguously at buf[0 .. resident) (a trim moves the survivors to the front, once
 // per 30 s of audio: <= 1 MB device to device), so every reader sees plain contiguous memory. Readers are kernels of the VAD object's,
-// the speaker engine's and a slot's stream; `mu` serialises them against the writer, `last_read` (recorded on the reader's stream
-// behind its launch) is what a trim or a growth waits for before it moves data under a reader that was launched but has not run yet.
+// the speaker engine's and a slot's stream, each behind a PcmLease (below); `mu` serialises them against the writer, `last_read` (recorded
+// on the reader's stream behind its launch) is what a trim or a growth waits for before it moves data under a reader that was launched
+// but has not run yet. Those three fields are ring.hip's alone.
 struct RingStore;
 struct Ring {
     std::mutex mu;
@@ -191,6 +193,38 @@ int create_slot_stream(int device, hipStream_t* out, bool* dedicated_out);
 int flush_logmel(Engine* e, Slot* s);                      // engine.hip: the recorded log-mel requests go out
 int slot_grow_audio(Engine* e, Slot* s, size_t n_samples); // engine.hip: PCM + feature buffers for n_samples per item
 int slot_resample_stage(Slot* s);                          // engine.hip: Slot::rs, allocated at the first call
+
+// The READER's side of resident audio: 16 kHz mono float32 in device memory that belongs to a slot item (wlx_pcm_put*) or to a ring
+// lane, held still for one reader whose kernels run on a stream of its own. The one invariant: nothing moves, frees or rewrites the
+// samples while a reader launched on another stream may still read them. Who holds what, in which order:
+//   slot item   the slot's call mutex (open_slot, for the lease's life), THEN the reader's own mutex. order() puts the reader's stream
+//               behind whatever wrote the PCM on the slot's stream; the reader waits for its pass before it returns.
+//   ring lane   the reader's own mutex, THEN the lane's `mu` (open_ring, for the lease's life); wlx_logmel_ring, whose reader is a slot,
+//               holds that slot's call mutex first. A synchronous reader (it waits for its pass under the lease) owes the ring nothing
+//               more: samples are final when their append returns. An asynchronous reader (it returns behind its launch) brackets the
+//               launch with before_launch / launched: the lane remembers the launch, and a trim or a growth waits for it (ring.hip).
+// The lease never takes the reader's mutex and decides no policy: the entry point refuses its own arguments between same_device and
+// open_*, and takes its mutex where the order above says. view: samples [base, base + resident) lie at buf[0 .. resident).
+struct PcmLease {
+    const float* buf = nullptr;
+    int64_t base = 0, resident = 0;
+    static int same_device(const char* who, const char* what, int device, const char* reader, int reader_device);
+    int open_slot(wlx_engine* e, int slot);                                   // engine.hip
+    int item(const char* who, int first, int count = 1);                     // slot: [first, first + count) inside [0, B); views `first`
+    void view(int item);                                                      // slot: another item of that span
+    int range(const char* who, int64_t start, int64_t n, const float** p = nullptr) const;   // the residency refusal (WLX_ERR_STATE), else the samples
+    int order(hipStream_t reader);                                            // before the reader's launches (nothing to do on a ring)
+    void open_ring(wlx_ring* r);                                              // ring.hip
+    int before_launch(hipStream_t reader);
+    int launched(hipStream_t reader);
+
+private:
+    SlotGuard sg_;
+    std::unique_lock<std::mutex> lane_;
+    wlx_ring* r_ = nullptr;
+    int item_ = -1;
+};
+
 extern std::atomic<int> g_dedicated_live[64];      // live slots with a hardware queue of their own, per device (create_slot_stream)
 extern std::atomic<int> g_slots_live[64];          // live slots per device
 

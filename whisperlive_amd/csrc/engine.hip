@@ -275,6 +275,48 @@ int wlx::slot_acquire(wlx_engine* e, int slot, SlotGuard& g) {
     return WLX_OK;
 }
 
+// ---- PcmLease (engine.h): the slot half, and what both halves share. The ring half is in ring.hip.
+int PcmLease::same_device(const char* who, const char* what, int device, const char* reader, int reader_device) {
+    return device == reader_device ? WLX_OK : set_error(WLX_ERR_ARG, "%s: the %s lives on device %d, the %s on %d", who, what, device, reader, reader_device);
+}
+
+int PcmLease::open_slot(wlx_engine* e, int slot) { return slot_acquire(e, slot, sg_); }
+
+int PcmLease::item(const char* who, int first, int count) {
+    if (first < 0 || first + (int64_t)count > sg_.s->B)
+        return set_error(WLX_ERR_ARG, "%s: items [%d, %lld) outside the slot's %d", who, first, (long long)first + count, sg_.s->B);
+    view(first);
+    return WLX_OK;
+}
+
+void PcmLease::view(int item) {
+    const Slot* s = sg_.s;
+    item_ = item;
+    buf = s->pcm ? s->pcm + (size_t)item * s->pcm_cap : nullptr;
+    base = 0, resident = s->npcm[item];
+}
+
+int PcmLease::range(const char* who, int64_t start, int64_t n, const float** p) const {
+    if (start >= base && start - base <= resident - n) {
+        if (p) *p = buf + (start - base);
+        return WLX_OK;
+    }
+    const long long a = start, b = start + n;
+    return r_ ? set_error(WLX_ERR_STATE, "%s: [%lld, %lld) is not resident (ring holds [%lld, %lld))", who, a, b, (long long)base, (long long)(base + resident))
+              : set_error(WLX_ERR_STATE, "%s: [%lld, %lld) is not resident (item %d holds %lld samples)", who, a, b, item_, (long long)resident);
+}
+
+// whatever wrote the PCM on the slot's stream is finished before the reader's launches read it (wlx_pcm_put_frames returns behind its
+// resample launches). The device is set.
+int PcmLease::order(hipStream_t reader) {
+    Slot* s = sg_.s;
+    if (!s) return WLX_OK;
+    if (!s->ev_pcm) CK(hipEventCreateWithFlags(&s->ev_pcm, hipEventDisableTiming));
+    CK(hipEventRecord(s->ev_pcm, s->stream));
+    CK(hipStreamWaitEvent(reader, s->ev_pcm, 0));
+    return WLX_OK;
+}
+
 int wlx::slot_grow_audio(Engine* e, Slot* s, size_t n_samples) {
     if (n_samples <= s->pcm_cap) return WLX_OK;
     // grow PCM + feature buffers (sizes rounded up to whole 30 s windows)
@@ -715,7 +757,7 @@ extern "C" int32_t wlx_pcm_get(wlx_engine* e, int32_t slot, int32_t item, float*
     return WLX_OK;
 }
 
-// the range reader of a PCM ring (ring.hip): the ring's mutex is held across the launch, `last_read` is what a later trim waits for
+// the range reader of a PCM ring, and the asynchronous one: it returns behind its launch (engine.h PcmLease)
 extern "C" int32_t wlx_logmel_ring(wlx_engine* e, int32_t slot, int32_t item, wlx_ring* r, const int64_t* ranges, int32_t n_ranges,
                                    int32_t* n_frames_out) {
     SlotGuard sg_;
@@ -724,38 +766,35 @@ extern "C" int32_t wlx_logmel_ring(wlx_engine* e, int32_t slot, int32_t item, wl
     if (!r || !ranges || n_ranges < 1) return set_error(WLX_ERR_ARG, "wlx_logmel_ring: bad argument");
     if (n_ranges > WLX_LM_MAXRANGES) return set_error(WLX_ERR_ARG, "wlx_logmel_ring: more than %d ranges", WLX_LM_MAXRANGES);
     if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", item);
-    if (r->device != e->device) return set_error(WLX_ERR_ARG, "wlx_logmel_ring: the ring lives on device %d, the engine on %d", r->device, e->device);
+    CKR(PcmLease::same_device("wlx_logmel_ring", "ring", r->device, "engine", e->device));
     CK(hipSetDevice(e->device));
-    std::lock_guard<std::mutex> lk(r->mu);
+    PcmLease L;
+    L.open_ring(r);
     long long tab[2 * WLX_LM_MAXRANGES];
-    int64_t total = 0, prev_end = r->base;
+    int64_t total = 0, prev_end = L.base;
     for (int i = 0; i < n_ranges; ++i) {
         const int64_t a = ranges[2 * i], b = ranges[2 * i + 1];
-        if (a < prev_end || b <= a) return set_error(a < r->base ? WLX_ERR_STATE : WLX_ERR_ARG, "wlx_logmel_ring: range %d = [%lld, %lld) is empty, out of order or no longer resident (ring starts at %lld)",
-                                                i, (long long)a, (long long)b, (long long)r->base);
-        if (b > r->base + r->resident) return set_error(WLX_ERR_STATE, "wlx_logmel_ring: range %d ends at %lld, the ring at %lld", i, (long long)b, (long long)(r->base + r->resident));
-        tab[2 * i] = a - r->base; tab[2 * i + 1] = total;
+        if (a < prev_end || b <= a) return set_error(a < L.base ? WLX_ERR_STATE : WLX_ERR_ARG, "wlx_logmel_ring: range %d = [%lld, %lld) is empty, out of order or no longer resident (ring starts at %lld)",
+                                                i, (long long)a, (long long)b, (long long)L.base);
+        if (b > L.base + L.resident) return set_error(WLX_ERR_STATE, "wlx_logmel_ring: range %d ends at %lld, the ring at %lld", i, (long long)b, (long long)(L.base + L.resident));
+        tab[2 * i] = a - L.base; tab[2 * i + 1] = total;
         total += b - a;
         prev_end = b;
     }
     if (total > 16000LL * 3600) return set_error(WLX_ERR_ARG, "audio chunk too long");
-    // a reader launched from ANOTHER stream may still be pending: its event is about to be re-recorded on this stream, so this stream first
-    // waits for it (the new record then stands for both; one session = one slot = one stream makes this the rare case)
-    if (r->read_pending && r->last_read_stream != s->stream) CK(hipStreamWaitEvent(s->stream, r->last_read, 0));
+    CKR(L.before_launch(s->stream));
     CKR(flush_logmel(e, s));                         // requests recorded earlier go out first (one of them may be this item's)
     CKR(slot_grow_audio(e, s, (size_t)total));       // the feature buffers are sized with the audio buffers
     CK(hipMemcpyAsync(s->d_rng, tab, (size_t)n_ranges * 2 * sizeof(long long), hipMemcpyHostToDevice, s->stream));   // (pageable source: staged before the call returns)
     const int T = (int)((total + 160) / 160);
     LogmelBatch lb{};
-    lb.n_items = 1; lb.pcm[0] = r->buf; lb.n[0] = (long)total; lb.feats[0] = s->feats + (size_t)item * e->spec.n_mels * s->feat_ld; lb.T[0] = T;
+    lb.n_items = 1; lb.pcm[0] = L.buf; lb.n[0] = (long)total; lb.feats[0] = s->feats + (size_t)item * e->spec.n_mels * s->feat_ld; lb.T[0] = T;
     lb.gmax[0] = s->gmax + item; lb.rng[0] = s->d_rng; lb.nr[0] = n_ranges;
     CK(hipEventRecord(s->ev_lm0, s->stream));
     launch_logmel_batch(lb, e->spec.n_mels, e->lm, s->feat_ld, s->stream);
     CK(hipGetLastError());
     CK(hipEventRecord(s->ev_lm1, s->stream));
-    CK(hipEventRecord(r->last_read, s->stream));     // a later trim waits for this launch before it moves the samples
-    r->read_pending = true;
-    r->last_read_stream = s->stream;
+    CKR(L.launched(s->stream));
     s->lm_pending = true;
     s->npcm[item] = 0;                               // the item's own PCM buffer does not hold this audio (wlx_logmel_resident would be wrong)
     s->nframes[item] = T;

@@ -418,7 +418,7 @@ extern "C" int32_t wlx_pcm_put_flac_split(wlx_engine* e, int32_t slot, int32_t f
     return pcm_put_flac(e, slot, first_item, bytes, n_bytes, info_out, n_out, true);
 }
 
-// ------------------------------------------------------------------------------------------------ test hooks (kernel_hooks.hip conventions)
+// ------------------------------------------------------------------------------------------------ test hooks (host.h HookScope)
 extern "C" int32_t wlx_debug_flac_timings(wlx_engine* e, int32_t slot, float* ms_out) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
@@ -443,25 +443,18 @@ extern "C" int32_t wlx_debug_flac_decode(int32_t device, const void* bytes, int6
     const long long total = fs.info.total_samples;
     const int ch = fs.info.channels;
     if (total * ch > cap_samples) return set_error(WLX_ERR_ARG, "output buffer too small");
-    int ndev = 0;
-    CK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, ndev - 1);
-    CK(hipSetDevice(device));
-    struct Scope {
-        std::vector<void*> allocs; hipStream_t st = nullptr;
-        ~Scope() { if (st) (void)hipStreamSynchronize(st); for (void* p : allocs) (void)hipFree(p); if (st) (void)hipStreamDestroy(st); }
-    } S;
-    CK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
+    std::vector<int> status(fs.frames.size());          // (declared before S: it outlives the stream's copies on every return path)
+    HookScope S;
+    CKR(S.begin(device));
     FlacDev d{};
     const size_t need = flac_layout(fs, n_bytes, nullptr, &d);
     unsigned char* base = nullptr;
-    CKR(dalloc(S.allocs, &base, need, false));
+    CKR(S.alloc(&base, need));
     (void)flac_layout(fs, n_bytes, base, &d);
     CKR(flac_launch<int32_t>(fs, bytes, n_bytes, d, nullptr, S.st, nullptr));
-    std::vector<int> status(fs.frames.size());
-    CK(hipMemcpyAsync(status.data(), d.status, status.size() * sizeof(int), hipMemcpyDeviceToHost, S.st));
-    CK(hipMemcpyAsync(samples_out, d.frames, (size_t)total * ch * sizeof(int32_t), hipMemcpyDeviceToHost, S.st));
-    CK(hipStreamSynchronize(S.st));
+    CKR(S.download(status.data(), d.status, status.size()));
+    CKR(S.download(samples_out, static_cast<const int32_t*>(d.frames), (size_t)total * ch));
+    CKR(S.finish());
     CKR(flac_check_status(status.data(), status.size()));
     *n_frames_out = total;
     *channels_out = ch;

@@ -1,6 +1,7 @@
 // host.h — the host support layer shared by engine.hip, mt_engine.hip and vad.hip: the error macros, the utility stream,
-// device / pinned allocation into an owner's free list, and weight ingestion (lookup, shape check, fp32 staging, packing,
-// one Hugging Face transformer layer).
+// device / pinned allocation into an owner's free list, the scope of a test hook call (HookScope: every wlx_*debug* hook of
+// kernel_hooks.hip, mt_engine.hip, spk_engine.hip, resample.hip and flac.hip), and weight ingestion (lookup, shape check, fp32
+// staging, packing, one Hugging Face transformer layer).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -47,6 +48,49 @@ int halloc(std::vector<void*>& pool, T** out, size_t count) {
 }
 // a packed [ceil(N/16)][ceil(K/32)] fragment image (common.h) for a W[N][K]
 int alloc_packed(std::vector<void*>& pool, int64_t N, int64_t K, half_t** out, int* KT_out, bool zero);
+
+// ---- the scope of one kernel-level test hook call (wlx_*debug*): a private non-blocking stream on `device` and the device buffers of
+// the call, released on every return path (wait, free, destroy). The hooks' conventions: host arrays in, ONE call of the production
+// launcher on `st`, host arrays out; outputs are copied in AND out, so bytes no thread owns come back unchanged; every shape a launcher
+// cannot serve is refused (WLX_ERR_ARG) before begin(), so before anything is allocated or launched.
+struct HookScope {
+    std::vector<void*> allocs;
+    hipStream_t st = nullptr;
+    ~HookScope() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (void* p : allocs) (void)hipFree(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    int begin(int device) {
+        int n = 0;
+        CK(hipGetDeviceCount(&n));
+        if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
+        CK(hipSetDevice(device));
+        CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        return WLX_OK;
+    }
+    template <class T>
+    int alloc(T** d, size_t n) { return dalloc(allocs, d, n, false); }      // not cleared
+    template <class T>
+    int upload(T** d, const T* h, size_t n) {
+        CKR(alloc(d, n));
+        if (h && n) CK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+        return WLX_OK;
+    }
+    template <class T>
+    int download(T* h, const T* d, size_t n) {
+        CK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st));
+        return WLX_OK;
+    }
+    int finish() {
+        CK(hipGetLastError());
+        CK(hipStreamSynchronize(st));
+        return WLX_OK;
+    }
+};
+// the hooks' ABI carries fp16 as uint16_t
+inline const half_t* h16(const uint16_t* p) { return reinterpret_cast<const half_t*>(p); }
+inline half_t* h16(uint16_t* p) { return reinterpret_cast<half_t*>(p); }
 
 // ---- weight ingestion: the caller's tensors by name, brought to the device and into the kernel layouts.
 // All work runs on the source's own non-blocking stream; the destructor synchronises and destroys it and frees the staging

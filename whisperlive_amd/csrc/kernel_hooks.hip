@@ -7,57 +7,11 @@
 //   wlx_debug_dec_gemv           launch_dec_gemv: dec_gemv2_kernel, dec_vocab_kernel, dec_gemv_kernel (dec_gemv.hip, dec_vocab.hip)
 //   wlx_debug_dec_cq_cross_attn  launch_dec_cq_cross_attn (decoder.hip)
 //   wlx_debug_dtw, wlx_debug_align_post   launch_align_dtw / launch_align_cost (align.hip)
-// Same conventions as the translation hooks (mt_engine.hip wlx_mt_debug_attn): host arrays in, ONE call of the production
-// launcher on a private non-blocking stream, host arrays out. Outputs are copied in AND out, so bytes no thread owns come back
-// unchanged. Every shape a launcher cannot serve is refused (WLX_ERR_ARG) before anything is allocated or launched. No engine
-// or slot is needed, and no product code path runs differently because these exist.
+// The hooks' conventions are HookScope's (host.h). No engine or slot is needed, and no product code path runs differently because
+// these exist.
 #include "align.h"
 #include "decoder.h"
 #include "host.h"
-
-namespace wlx {
-namespace {
-
-// device buffers and the stream of one hook call, released on every return path
-struct HookScope {
-    std::vector<void*> allocs;
-    hipStream_t st = nullptr;
-    ~HookScope() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void* p : allocs) (void)hipFree(p);
-        if (st) (void)hipStreamDestroy(st);
-    }
-    int begin(int device) {
-        int n = 0;
-        CK(hipGetDeviceCount(&n));
-        if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
-        CK(hipSetDevice(device));
-        CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        return WLX_OK;
-    }
-    template <class T>
-    int upload(T** d, const T* h, size_t n) {
-        CKR(dalloc(allocs, d, n, false));
-        if (h && n) CK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-        return WLX_OK;
-    }
-    template <class T>
-    int download(T* h, const T* d, size_t n) {
-        CK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st));
-        return WLX_OK;
-    }
-    int finish() {
-        CK(hipGetLastError());
-        CK(hipStreamSynchronize(st));
-        return WLX_OK;
-    }
-};
-
-inline const half_t* h16(const uint16_t* p) { return reinterpret_cast<const half_t*>(p); }
-inline half_t* h16(uint16_t* p) { return reinterpret_cast<half_t*>(p); }
-
-}  // namespace
-}  // namespace wlx
 
 using namespace wlx;
 
@@ -541,7 +495,7 @@ extern "C" int32_t wlx_debug_dtw(int32_t device, const float* x, int32_t n, cons
     CKR(S.upload(&dent, ent, (size_t)n));
     CK(hipStreamSynchronize(S.st));             // (`ent` is this frame's memory)
     CKR(S.upload(&dx, x, plan.x_floats));
-    CKR(S.upload(&dtr, (const unsigned*)nullptr, plan.trace_words));
+    CKR(S.alloc(&dtr, plan.trace_words));
     CKR(align_hook_paths(S, n, text_indices, time_indices, path_stride, n_path, &dti, &dfi, &dnp));
     launch_align_dtw(dent, n, plan.max_N, dx, dtr, dti, dfi, path_stride, dnp, S.st);
     CKR(S.download(text_indices, dti, (size_t)n * path_stride));
@@ -576,9 +530,9 @@ extern "C" int32_t wlx_debug_align_post(int32_t device, const float* scores, int
     CKR(S.upload(&dent, ent, (size_t)n));
     CK(hipStreamSynchronize(S.st));
     CKR(S.upload(&ds, scores, plan.score_floats));
-    CKR(S.upload(&dstat, (const float*)nullptr, plan.stat_floats));
+    CKR(S.alloc(&dstat, plan.stat_floats));
     CKR(S.upload(&dx, cost_out, plan.x_floats));
-    CKR(S.upload(&dtr, (const unsigned*)nullptr, plan.trace_words));
+    CKR(S.alloc(&dtr, plan.trace_words));
     CKR(align_hook_paths(S, n, text_indices, time_indices, path_stride, n_path, &dti, &dfi, &dnp));
     launch_align_cost(dent, n, n_heads, n_sot, median_filter_width, plan, ds, dstat, dx, S.st);
     launch_align_dtw(dent, n, plan.max_N, dx, dtr, dti, dfi, path_stride, dnp, S.st);

@@ -680,47 +680,7 @@ extern "C" int32_t wlx_mt_debug_timings(wlx_mt* m, int32_t slot, float* encode_m
     return WLX_OK;
 }
 
-// ---- kernel-level test hooks: host arrays in, the production launcher unchanged on a private stream, host arrays out.
-// Every shape a launcher cannot serve is refused (WLX_ERR_ARG) before anything is allocated or launched.
-namespace {
-
-// device buffers and the stream of one hook call, released on every return path
-struct HookScope {
-    std::vector<void*> allocs;
-    hipStream_t st = nullptr;
-    ~HookScope() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void* p : allocs) (void)hipFree(p);
-        if (st) (void)hipStreamDestroy(st);
-    }
-    int begin(int device) {
-        int n = 0;
-        CK(hipGetDeviceCount(&n));
-        if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
-        CK(hipSetDevice(device));
-        CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        return WLX_OK;
-    }
-    template <class T>
-    int upload(T** d, const T* h, size_t n) {
-        CKR(dalloc(allocs, d, n, false));
-        if (h && n) CK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-        return WLX_OK;
-    }
-    template <class T>
-    int download(T* h, const T* d, size_t n) {
-        CK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st));
-        return WLX_OK;
-    }
-    int finish() {
-        CK(hipGetLastError());
-        CK(hipStreamSynchronize(st));
-        return WLX_OK;
-    }
-};
-
-}  // namespace
-
+// ---- kernel-level test hooks (host.h HookScope): host arrays in, the production launcher unchanged on a private stream, host arrays out
 extern "C" int32_t wlx_mt_debug_attn(int32_t device, const uint16_t* q, int64_t ldq, int64_t q_rows, const uint16_t* k, int64_t ldk,
                                      const uint16_t* v, int64_t ldv, int64_t kv_rows, const int32_t* groups, int32_t n_groups,
                                      int32_t max_nq, int32_t heads, const int32_t* anc, int32_t ld_anc, int32_t tmax, uint16_t* o,
@@ -754,16 +714,16 @@ extern "C" int32_t wlx_mt_debug_attn(int32_t device, const uint16_t* q, int64_t 
     CKR(S.begin(device));
     half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
     int32_t *dg = nullptr, *da = nullptr;
-    CKR(S.upload(&dq, reinterpret_cast<const half_t*>(q), (size_t)q_rows * ldq));
-    CKR(S.upload(&dk, reinterpret_cast<const half_t*>(k), (size_t)kv_rows * ldk));
-    CKR(S.upload(&dv, reinterpret_cast<const half_t*>(v), (size_t)kv_rows * ldv));
-    CKR(S.upload(&dout, reinterpret_cast<const half_t*>(o), (size_t)o_rows * ldo));
+    CKR(S.upload(&dq, h16(q), (size_t)q_rows * ldq));
+    CKR(S.upload(&dk, h16(k), (size_t)kv_rows * ldk));
+    CKR(S.upload(&dv, h16(v), (size_t)kv_rows * ldv));
+    CKR(S.upload(&dout, h16(o), (size_t)o_rows * ldo));
     CKR(S.upload(&dg, groups, (size_t)4 * n_groups));
     if (anc) CKR(S.upload(&da, anc, (size_t)anc_rows * ld_anc));
     static_assert(sizeof(MtAttnGroup) == 4 * sizeof(int32_t), "MtAttnGroup is four int32");
     launch_mt_attn(dq, ldq, dk, ldk, dv, ldv, dout, ldo, reinterpret_cast<const MtAttnGroup*>(dg), n_groups, max_nq, heads, da,
                    anc ? ld_anc : 0, anc ? tmax : 0, S.st);
-    CKR(S.download(reinterpret_cast<half_t*>(o), dout, (size_t)o_rows * ldo));
+    CKR(S.download(h16(o), dout, (size_t)o_rows * ldo));
     return S.finish();
 }
 
@@ -791,10 +751,10 @@ extern "C" int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_
         CKR(S.upload(&dnban, nban, (size_t)rows));
         CKR(S.upload(&dban, max_nb > 0 ? ban : nullptr, max_nb > 0 ? (size_t)rows * ban_ld : 0));
     }
-    CKR(S.upload(&scratch, (const float*)nullptr, (size_t)rows * WLX_MT_CHUNKS * (2 + k)));
-    CKR(S.upload(&cidx, (const int32_t*)nullptr, (size_t)rows * WLX_MT_CHUNKS * k));
-    CKR(S.upload(&dval, (const float*)nullptr, (size_t)rows * k));
-    CKR(S.upload(&didx, (const int32_t*)nullptr, (size_t)rows * k));
+    CKR(S.alloc(&scratch, (size_t)rows * WLX_MT_CHUNKS * (2 + k)));
+    CKR(S.alloc(&cidx, (size_t)rows * WLX_MT_CHUNKS * k));
+    CKR(S.alloc(&dval, (size_t)rows * k));
+    CKR(S.alloc(&didx, (size_t)rows * k));
     launch_mt_topk(dl, rows, vocab, dban, dnban, nban ? ban_ld : 0, k, scratch, cidx, dval, didx, S.st);
     CKR(S.download(out_val, dval, (size_t)rows * k));
     CKR(S.download(out_idx, didx, (size_t)rows * k));
@@ -820,7 +780,7 @@ extern "C" int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vo
     CKR(S.upload(&dtok, tok, (size_t)rows));
     CKR(S.upload(&dpos, pos, (size_t)rows));
     CKR(S.upload(&dsin, sinpos, (size_t)n_pos * d));
-    CKR(S.upload(&dx, (const float*)nullptr, (size_t)rows * d));
+    CKR(S.alloc(&dx, (size_t)rows * d));
     launch_mt_embed(dtok, dpos, rows, Ep, d / 32, scale, dsin, d, dx, S.st);
     CKR(S.download(x, dx, (size_t)rows * d));
     return S.finish();

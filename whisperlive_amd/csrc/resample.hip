@@ -464,7 +464,7 @@ void resample_stream_free(ResampleStream& rs) {
 
 using namespace wlx;
 
-// ------------------------------------------------------------------------------------------------ test hooks (kernel_hooks.hip conventions)
+// ------------------------------------------------------------------------------------------------ test hooks (host.h HookScope)
 // split: out is [channels][cap] and channel c lands in row c (the split instantiation); else out is [cap] (the down-mix)
 static int debug_resample(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format, int32_t sample_rate,
                           int64_t block_frames, float* out, int64_t cap, int64_t* n_out, float* kernel_ms, bool split = false) {
@@ -481,35 +481,26 @@ static int debug_resample(int32_t device, const void* frames, int64_t n_frames, 
             return set_error(WLX_ERR_ARG, "block of %lld frames is smaller than the filter's reach (%lld)", (long long)block_frames, resample_reach(tmp));
         if (resample_out_len(tmp, n_frames) > cap) return set_error(WLX_ERR_ARG, "output buffer too small");
     }
-    int ndev = 0;
-    CK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, ndev - 1);
+    HookScope S;
+    CKR(S.begin(device));
     ResamplePlan pl{};
     CKR(resample_plan(device, sample_rate, &pl));
-    CK(hipSetDevice(device));
     const long long nout = resample_out_len(pl, n_frames);
     *n_out = nout;
     if (nout == 0) return WLX_OK;
     const size_t fb = (size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4);
     const long long bf = std::min<long long>(block_frames, n_frames);
-    struct Scope {
-        std::vector<void*> allocs; hipStream_t st = nullptr;
-        ~Scope() { if (st) (void)hipStreamSynchronize(st); for (void* p : allocs) (void)hipFree(p); if (st) (void)hipStreamDestroy(st); }
-    } S;
-    CK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
     ResampleStage sg{};
     unsigned char *r0 = nullptr, *r1 = nullptr;
     float* dout = nullptr;
-    CKR(dalloc(S.allocs, &r0, (size_t)bf * fb, false));
-    CKR(dalloc(S.allocs, &r1, (size_t)bf * fb, false));
+    CKR(S.alloc(&r0, (size_t)bf * fb));
+    CKR(S.alloc(&r1, (size_t)bf * fb));
     const size_t out_floats = (size_t)cap * (split ? (size_t)channels : 1);
-    CKR(dalloc(S.allocs, &dout, out_floats, false));
+    CKR(S.upload(&dout, out, out_floats));                  // copied in AND out
     sg.dev[0] = r0; sg.dev[1] = r1;
-    CK(hipMemcpyAsync(dout, out, out_floats * sizeof(float), hipMemcpyHostToDevice, S.st));     // copied in AND out
     CKR(resample_run(pl, frames, n_frames, channels, sample_format, block_frames, sg, dout, S.st, kernel_ms, split ? (long long)cap : 0));
-    CK(hipMemcpyAsync(out, dout, out_floats * sizeof(float), hipMemcpyDeviceToHost, S.st));
-    CK(hipStreamSynchronize(S.st));
-    return WLX_OK;
+    CKR(S.download(out, dout, out_floats));
+    return S.finish();
 }
 
 extern "C" int32_t wlx_debug_resample(int32_t device, const void* frames, int64_t n_frames, int32_t channels, int32_t sample_format,
@@ -552,32 +543,31 @@ extern "C" int32_t wlx_debug_resample_stream(int32_t device, const void* frames,
     CKR(resample_ratio(sample_rate, &up, &down, &tile));
     const long long total = resample_stream_count(up, down, up == down ? 0 : 10 * std::max(up, down), n_frames, flush);
     if (total > cap) return set_error(WLX_ERR_ARG, "output buffer too small");
-    int ndev = 0;
-    CK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, ndev - 1);
-    CK(hipSetDevice(device));
-    struct Scope {
-        ResampleStream rs{}; float* dout = nullptr; hipStream_t st = nullptr;
-        ~Scope() { if (st) (void)hipStreamSynchronize(st); resample_stream_free(rs); if (dout) (void)hipFree(dout); if (st) (void)hipStreamDestroy(st); }
-    } S;
-    CK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-    CKR(resample_stream_open(device, sample_format, channels, sample_rate, &S.rs));
-    CK(hipMalloc(reinterpret_cast<void**>(&S.dout), std::max<size_t>((size_t)cap, 1) * sizeof(float)));     // freed by Scope
-    CK(hipMemcpyAsync(S.dout, out, (size_t)cap * sizeof(float), hipMemcpyHostToDevice, S.st));               // copied in AND out
+    HookScope S;
+    CKR(S.begin(device));
+    // the stream state is owned by name (resample_stream_free), released behind the stream's work and before S lets go of the rest
+    struct Owner {
+        HookScope& S; ResampleStream rs{};
+        ~Owner() { (void)hipStreamSynchronize(S.st); resample_stream_free(rs); }
+    } R{S};
+    ResampleStream& rs = R.rs;
+    CKR(resample_stream_open(device, sample_format, channels, sample_rate, &rs));
+    float* dout = nullptr;
+    CKR(S.upload(&dout, out, (size_t)cap));                  // copied in AND out (cap == 0: one float nobody reads)
     const size_t fb = (size_t)channels * resample_format_bytes(sample_format);
     const int n_calls = n_cuts + 1 + (flush == 1 ? 1 : 0);
     for (int c = 0; c < n_calls; ++c) {
         const bool tail_call = c == n_cuts + 1;              // flush == 1: the empty flushing packet behind the data
         const long long a = tail_call ? n_frames : (c ? cuts[c - 1] : 0), b = tail_call ? n_frames : (c < n_cuts ? cuts[c] : n_frames);
         const int fl = tail_call || (flush == 2 && c == n_cuts);
-        const long long before = S.rs.M;
-        CKR(resample_stream_reserve(S.rs, b - a));
-        CKR(resample_stream_enqueue(S.rs, static_cast<const char*>(frames) + (size_t)a * fb, b - a, fl, S.dout + before, S.st));
+        const long long before = rs.M;
+        CKR(resample_stream_reserve(rs, b - a));
+        CKR(resample_stream_enqueue(rs, static_cast<const char*>(frames) + (size_t)a * fb, b - a, fl, dout + before, S.st));
         CK(hipStreamSynchronize(S.st));                      // as the product call: a packet is done when its call returns
-        if (per_call_counts) per_call_counts[c] = S.rs.M - before;
+        if (per_call_counts) per_call_counts[c] = rs.M - before;
     }
-    CK(hipMemcpyAsync(out, S.dout, (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, S.st));
-    CK(hipStreamSynchronize(S.st));
-    *n_out = S.rs.M;
+    CKR(S.download(out, dout, (size_t)cap));
+    CKR(S.finish());
+    *n_out = rs.M;
     return WLX_OK;
 }

@@ -1,6 +1,7 @@
 // ring.hip — the write side of the device PCM rings (include/wlx.h wlx_ring_*, wlx_ring_group_*; engine.h RingStore):
 // whisper_live/backend/base.py:173-234 on the device. One store, one trim-and-grow rule, one append behind the mono ring and the
-// ring group. The readers: wlx_logmel_ring (engine.hip), wlx_vad_probs_resident (vad.hip), wlx_spk_embed_ring_batch (spk_engine.hip).
+// ring group, and the ring half of PcmLease, through which the readers come: wlx_logmel_ring (engine.hip), wlx_vad_probs_resident
+// (vad.hip), wlx_spk_embed_ring_batch (spk_engine.hip).
 #include "engine.h"
 #include <algorithm>
 
@@ -48,6 +49,28 @@ static int store_create(const char* fn, wlx_engine* e, int64_t capacity_samples,
     }
     if (rc != WLX_OK) { store_free(st); return rc; }
     *out = st;
+    return WLX_OK;
+}
+
+// ---- PcmLease (engine.h): the ring half. No append, trim or growth while the lease is held.
+void PcmLease::open_ring(wlx_ring* r) {
+    lane_ = std::unique_lock<std::mutex>(r->mu);
+    r_ = r;
+    buf = r->buf, base = r->base, resident = r->resident;
+}
+
+// a reader launched from ANOTHER stream may still be pending: its event is about to be re-recorded on this stream, so this stream first
+// waits for it (the new record then stands for both; one session = one slot = one stream makes this the rare case)
+int PcmLease::before_launch(hipStream_t reader) {
+    if (r_->read_pending && r_->last_read_stream != reader) CK(hipStreamWaitEvent(reader, r_->last_read, 0));
+    return WLX_OK;
+}
+
+// a later trim or growth waits for this launch before it moves the samples (wait_readers)
+int PcmLease::launched(hipStream_t reader) {
+    CK(hipEventRecord(r_->last_read, reader));
+    r_->read_pending = true;
+    r_->last_read_stream = reader;
     return WLX_OK;
 }
 

@@ -333,58 +333,42 @@ extern "C" int32_t wlx_spk_embed_batch(wlx_spk* k, const float* pcm, const int64
 }
 
 // The same on ranges of a slot item's resident PCM (wlx_pcm_put / wlx_pcm_put_frames): the front end reads s->pcm where the upload route
-// reads k->pcm, nothing else differs, so no sample crosses the bus. The engine's stream is ordered behind the slot's with an event (the
-// resample launches of wlx_pcm_put_frames may still be running); the slot is held for the whole call, so nothing replaces or re-allocates
-// its PCM under the kernels.
+// reads k->pcm, nothing else differs, so no sample crosses the bus.
 extern "C" int32_t wlx_spk_embed_pcm_batch(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts,
                                            const int64_t* n_samples, int32_t n, float* out, int32_t* status) {
     if (!k || !e || !starts || !n_samples || !out || !status) return set_error(WLX_ERR_ARG, "wlx_spk_embed_pcm_batch: null argument");
-    if (e->device != k->device)
-        return set_error(WLX_ERR_ARG, "wlx_spk_embed_pcm_batch: the engine lives on device %d, the speaker engine on %d", e->device, k->device);
+    CKR(PcmLease::same_device("wlx_spk_embed_pcm_batch", "engine", e->device, "speaker engine", k->device));
     SpkPlan pl;
     CKR(spk_plan("wlx_spk_embed_pcm_batch", k, starts, n_samples, n, pl));
-    SlotGuard sg_;
-    CKR(slot_acquire(e, slot, sg_));
-    Slot* s = sg_.s;
-    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "wlx_spk_embed_pcm_batch: item %d outside the slot's %d", item, s->B);
-    const int64_t resident = s->npcm[item];
-    if (resident <= 0 || !s->pcm) return set_error(WLX_ERR_STATE, "wlx_spk_embed_pcm_batch: item %d: no PCM resident", item);
-    for (int i = 0; i < n; ++i)
-        if (starts[i] > resident - n_samples[i])
-            return set_error(WLX_ERR_STATE, "wlx_spk_embed_pcm_batch: range %d = [%lld, %lld) is not resident (item %d holds %lld samples)", i,
-                             (long long)starts[i], (long long)(starts[i] + n_samples[i]), item, (long long)resident);
+    PcmLease L;
+    CKR(L.open_slot(e, slot));
+    CKR(L.item("wlx_spk_embed_pcm_batch", item));
+    if (L.resident <= 0 || !L.buf) return set_error(WLX_ERR_STATE, "wlx_spk_embed_pcm_batch: item %d: no PCM resident", item);
+    for (int i = 0; i < n; ++i) CKR(L.range("wlx_spk_embed_pcm_batch", starts[i], n_samples[i]));
     spk_plan_commit(k, n_samples, n, out, status);
     if (pl.m == 0) return WLX_OK;
     std::lock_guard<std::mutex> g(k->mu);
     CK(hipSetDevice(k->device));
-    if (!s->ev_pcm) CK(hipEventCreateWithFlags(&s->ev_pcm, hipEventDisableTiming));
-    CK(hipEventRecord(s->ev_pcm, s->stream));                 // whatever wrote the PCM on the slot's stream ...
-    CK(hipStreamWaitEvent(k->st, s->ev_pcm, 0));              // ... is finished before the filterbank reads it
-    return spk_run_batch(k, s->pcm + (size_t)item * s->pcm_cap, pl, out);
+    CKR(L.order(k->st));
+    return spk_run_batch(k, L.buf, pl, out);
 }
 
-// The same on absolute stream positions of a device PCM ring. The ring keeps [base, base + resident) contiguous at buf[0 ...) (engine.h
-// Ring): a range never wraps, position p is buf[p - base]. The ring's mutex is held until the pass has been waited for, as in
-// wlx_vad_probs_resident: an append or a trim of the socket thread waits its turn and never moves samples under the kernels. Samples an
-// append put there are final when it returns (it waits for the ring's stream), so there is no stream to order behind.
+// The same on absolute stream positions of a device PCM ring: a range never wraps, position p is L.buf[p - L.base] (engine.h Ring).
 extern "C" int32_t wlx_spk_embed_ring_batch(wlx_spk* k, wlx_ring* r, const int64_t* starts, const int64_t* n_samples, int32_t n, float* out,
                                             int32_t* status) {
     if (!k || !r || !starts || !n_samples || !out || !status) return set_error(WLX_ERR_ARG, "wlx_spk_embed_ring_batch: null argument");
-    if (r->device != k->device)
-        return set_error(WLX_ERR_ARG, "wlx_spk_embed_ring_batch: the ring lives on device %d, the speaker engine on %d", r->device, k->device);
+    CKR(PcmLease::same_device("wlx_spk_embed_ring_batch", "ring", r->device, "speaker engine", k->device));
     SpkPlan pl;
     CKR(spk_plan("wlx_spk_embed_ring_batch", k, starts, n_samples, n, pl));
     std::lock_guard<std::mutex> g(k->mu);
-    std::lock_guard<std::mutex> lr(r->mu);          // no append / trim while the kernels read (the call waits for them below)
-    for (int i = 0; i < n; ++i)
-        if (starts[i] < r->base || starts[i] - r->base > r->resident - n_samples[i])
-            return set_error(WLX_ERR_STATE, "wlx_spk_embed_ring_batch: range %d = [%lld, %lld) is not resident (ring holds [%lld, %lld))", i,
-                             (long long)starts[i], (long long)(starts[i] + n_samples[i]), (long long)r->base, (long long)(r->base + r->resident));
+    PcmLease L;
+    L.open_ring(r);
+    for (int i = 0; i < n; ++i) CKR(L.range("wlx_spk_embed_ring_batch", starts[i], n_samples[i]));
     spk_plan_commit(k, n_samples, n, out, status);
     if (pl.m == 0) return WLX_OK;
-    for (int a = 0; a < pl.m; ++a) pl.offs[a] -= (long)r->base;
+    for (int a = 0; a < pl.m; ++a) pl.offs[a] -= (long)L.base;
     CK(hipSetDevice(k->device));
-    return spk_run_batch(k, r->buf, pl, out);
+    return spk_run_batch(k, L.buf, pl, out);
 }
 
 extern "C" int32_t wlx_spk_debug_timings(wlx_spk* k, float* fbank_ms, float* net_ms) {
@@ -396,37 +380,7 @@ extern "C" int32_t wlx_spk_debug_timings(wlx_spk* k, float* fbank_ms, float* net
     return WLX_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ one-launch hooks
-namespace {
-struct SpkHook {
-    std::vector<void*> allocs;
-    hipStream_t st = nullptr;
-    ~SpkHook() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void* p : allocs) (void)hipFree(p);
-        if (st) (void)hipStreamDestroy(st);
-    }
-    int begin(int device) {
-        int n = 0;
-        CK(hipGetDeviceCount(&n));
-        if (device < 0 || device >= n) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, n - 1);
-        CK(hipSetDevice(device));
-        CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        return WLX_OK;
-    }
-    template <class T>
-    int upload(T** d, const void* h, size_t n) {
-        CKR(dalloc(allocs, d, n, false));
-        if (h && n) CK(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-        return WLX_OK;
-    }
-    int finish() {
-        CK(hipGetLastError());
-        CK(hipStreamSynchronize(st));
-        return WLX_OK;
-    }
-};
-}  // namespace
+// ------------------------------------------------------------------------------------------------ one-launch hooks (host.h HookScope)
 
 extern "C" int32_t wlx_spk_debug_fbank(int32_t device, const float* pcm, int64_t n_samples, int32_t n_mels, float* frames_out,
                                        uint16_t* image_out, int32_t cap_frames, int32_t* n_frames_out) {
@@ -435,20 +389,20 @@ extern "C" int32_t wlx_spk_debug_fbank(int32_t device, const float* pcm, int64_t
     if (n_samples < WLX_SPK_FRAME || n_samples > (1LL << 28)) return set_error(WLX_ERR_ARG, "n_samples %lld outside 400..2^28", (long long)n_samples);
     const int T = spk_frames((long)n_samples);
     if (T > cap_frames) return set_error(WLX_ERR_ARG, "%d frames exceed the caller's %d", T, cap_frames);
-    SpkHook S;
+    HookScope S;
     CKR(S.begin(device));
     float *window, *twiddle, *mel, *dpcm, *dlm;
     half_t* d16;
     CKR(upload_tables(S.allocs, n_mels, &window, &twiddle, &mel));
     CKR(S.upload(&dpcm, pcm, (size_t)n_samples));
-    CKR(S.upload(&dlm, nullptr, (size_t)T * n_mels));
-    CKR(S.upload(&d16, nullptr, (size_t)T * n_mels));
+    CKR(S.alloc(&dlm, (size_t)T * n_mels));
+    CKR(S.alloc(&d16, (size_t)T * n_mels));
     const long offset = 0;          // one item at the start of the upload
     if (!launch_spk_fbank_batch(dpcm, &offset, &T, 1, window, twiddle, mel, n_mels, dlm, S.st) ||
         !launch_spk_cmn_batch(dlm, &T, 1, n_mels, d16, S.st))
         return set_error(WLX_ERR_ARG, "the launcher refused the shape");
-    CK(hipMemcpyAsync(frames_out, dlm, (size_t)T * n_mels * sizeof(float), hipMemcpyDeviceToHost, S.st));
-    CK(hipMemcpyAsync(image_out, d16, (size_t)T * n_mels * sizeof(half_t), hipMemcpyDeviceToHost, S.st));
+    CKR(S.download(frames_out, dlm, (size_t)T * n_mels));
+    CKR(S.download(h16(image_out), d16, (size_t)T * n_mels));
     *n_frames_out = T;
     return S.finish();
 }
@@ -466,15 +420,15 @@ static int spk_debug_conv_run(int device, const uint16_t* in, int H, int n, cons
     const size_t n_out = (size_t)OH * OWsum * Cout;
     std::vector<float> zeros;          // (host staging declared before S: it outlives the stream's copies on every return path)
     std::vector<half_t> packed;
-    SpkHook S;
+    HookScope S;
     CKR(S.begin(device));
     half_t *din, *dres = nullptr, *dout;
     float* dbias;
-    CKR(S.upload(&din, in, (size_t)H * Wsum * Cin));
+    CKR(S.upload(&din, h16(in), (size_t)H * Wsum * Cin));
     if (!bias) zeros.assign((size_t)Cout, 0.f);
     CKR(S.upload(&dbias, bias ? bias : zeros.data(), (size_t)Cout));
-    if (resid) CKR(S.upload(&dres, resid, n_out));
-    CKR(S.upload(&dout, out, n_out));
+    if (resid) CKR(S.upload(&dres, h16(resid), n_out));
+    CKR(S.upload(&dout, h16(out), n_out));
     bool ok;
     if (c1) {
         float* dw;
@@ -488,7 +442,7 @@ static int spk_debug_conv_run(int device, const uint16_t* in, int H, int n, cons
         ok = launch_spk_conv_batch(din, H, widths, n, Cin, dWp, dbias, dres, Cout, stride, ksize, relu != 0, dout, S.st);
     }
     if (!ok) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
-    CK(hipMemcpyAsync(out, dout, n_out * sizeof(half_t), hipMemcpyDeviceToHost, S.st));
+    CKR(S.download(h16(out), dout, n_out));
     return S.finish();
 }
 
@@ -517,15 +471,15 @@ extern "C" int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, 
 
 // wlx_spk_debug_pool (n = 1, frames = {T}) and wlx_spk_debug_pool_batch behind their own range checks: `Tsum` frames in all
 static int spk_debug_pool_run(int device, const uint16_t* x, int F, int n, const int32_t* frames, long Tsum, int C, float eps, float* out) {
-    SpkHook S;
+    HookScope S;
     CKR(S.begin(device));
     half_t* dx;
     float* dout;
     const size_t n_out = (size_t)n * 2 * F * C;
-    CKR(S.upload(&dx, x, (size_t)F * Tsum * C));
+    CKR(S.upload(&dx, h16(x), (size_t)F * Tsum * C));
     CKR(S.upload(&dout, out, n_out));
     if (!launch_spk_pool_batch(dx, F, frames, n, C, eps, dout, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
-    CK(hipMemcpyAsync(out, dout, n_out * sizeof(float), hipMemcpyDeviceToHost, S.st));
+    CKR(S.download(out, dout, n_out));
     return S.finish();
 }
 

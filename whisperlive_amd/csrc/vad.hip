@@ -576,7 +576,7 @@ extern "C" int32_t wlx_vad_probs_resident(wlx_vad* v, wlx_ring* r, int64_t start
                                           int32_t* n_windows_out, float* device_ms_out) {
     if (!v || !r || !n_windows_out || (n > 0 && !probs_out)) return set_error(WLX_ERR_ARG, "wlx_vad_probs_resident: null argument");
     if (n < 0) return set_error(WLX_ERR_ARG, "wlx_vad_probs_resident: negative sample count");
-    if (r->device != v->device) return set_error(WLX_ERR_ARG, "wlx_vad_probs_resident: the ring lives on device %d, the VAD model on %d", r->device, v->device);
+    CKR(PcmLease::same_device("wlx_vad_probs_resident", "ring", r->device, "VAD model", v->device));
     if (extra_zero_windows < 0 || extra_zero_windows > 4) return set_error(WLX_ERR_ARG, "wlx_vad_probs_resident: extra_zero_windows out of range");
     const long long T = (n + VAD_WINDOW - 1) / VAD_WINDOW + extra_zero_windows;
     *n_windows_out = (int32_t)T;
@@ -584,49 +584,43 @@ extern "C" int32_t wlx_vad_probs_resident(wlx_vad* v, wlx_ring* r, int64_t start
     if (T == 0) return WLX_OK;
     if (T > cap) return set_error(WLX_ERR_ARG, "wlx_vad_probs_resident: %lld windows do not fit the output buffer (%d)", T, cap);
     std::lock_guard<std::mutex> lk(v->mu);
-    std::lock_guard<std::mutex> lr(r->mu);          // no append / trim while the kernels read (vad_run_batch waits for them)
-    if (start < r->base || start + n > r->base + r->resident)
-        return set_error(WLX_ERR_STATE, "wlx_vad_probs_resident: [%lld, %lld) is not resident (ring holds [%lld, %lld))", (long long)start,
-                         (long long)(start + n), (long long)r->base, (long long)(r->base + r->resident));
+    PcmLease L;
+    L.open_ring(r);
+    const float* pcm;
+    CKR(L.range("wlx_vad_probs_resident", start, n, &pcm));
     CK(hipSetDevice(v->device));
     (void)hipGetLastError();
     CKR(vad_reserve(v, n + (long long)extra_zero_windows * VAD_WINDOW));
     VadPlan pl;
-    vad_plan_one(r->buf + (start - r->base), n, (int)T, pl);
+    vad_plan_one(pcm, n, (int)T, pl);
     return vad_run_batch(v, pl, probs_out, device_ms_out);
 }
 
 // The same on a slot item's resident PCM (wlx_pcm_put / wlx_pcm_put_frames): the gate of a FILE reads the 16 kHz copy the front end left
-// in HBM. Nothing of the VAD object grows with the file but the per-window buffers: d_pcm and h_pin are not touched. The VAD object's
-// stream is ordered behind the slot's (the resample launches of wlx_pcm_put_frames may still be running) with an event; the slot is
-// held for the whole call, so nothing replaces or re-allocates its PCM under the kernels.
+// in HBM. Nothing of the VAD object grows with the file but the per-window buffers: d_pcm and h_pin are not touched.
 extern "C" int32_t wlx_vad_probs_pcm(wlx_vad* v, wlx_engine* e, int32_t slot, int32_t item, int64_t start, int64_t n, int32_t extra_zero_windows,
                                      float* probs_out, int32_t cap, int32_t* n_windows_out, float* device_ms_out) {
     if (!v || !e || !n_windows_out || (n > 0 && !probs_out)) return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm: null argument");
     if (n < 0 || start < 0) return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm: negative position or sample count");
-    if (e->device != v->device) return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm: the engine lives on device %d, the VAD model on %d", e->device, v->device);
+    CKR(PcmLease::same_device("wlx_vad_probs_pcm", "engine", e->device, "VAD model", v->device));
     if (extra_zero_windows < 0 || extra_zero_windows > 4) return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm: extra_zero_windows out of range");
-    SlotGuard sg_;
-    CKR(slot_acquire(e, slot, sg_));
-    Slot* s = sg_.s;
-    if (item < 0 || item >= s->B) return set_error(WLX_ERR_ARG, "bad item %d", item);
+    PcmLease L;
+    CKR(L.open_slot(e, slot));
+    CKR(L.item("wlx_vad_probs_pcm", item));
     const long long T = (n + VAD_WINDOW - 1) / VAD_WINDOW + extra_zero_windows;
     *n_windows_out = (int32_t)T;
     if (device_ms_out) *device_ms_out = 0.0f;
-    if (start + n > s->npcm[item])
-        return set_error(WLX_ERR_STATE, "wlx_vad_probs_pcm: [%lld, %lld) is not resident (item %d holds %lld samples)", (long long)start,
-                         (long long)(start + n), item, (long long)s->npcm[item]);
+    const float* pcm;
+    CKR(L.range("wlx_vad_probs_pcm", start, n, &pcm));
     if (T == 0) return WLX_OK;
     if (T > cap) return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm: %lld windows do not fit the output buffer (%d)", T, cap);
     std::lock_guard<std::mutex> lk(v->mu);
     CK(hipSetDevice(v->device));
     (void)hipGetLastError();
     CKR(vad_reserve_windows(v, T));
-    if (!s->ev_pcm) CK(hipEventCreateWithFlags(&s->ev_pcm, hipEventDisableTiming));
-    CK(hipEventRecord(s->ev_pcm, s->stream));                 // whatever wrote the PCM on the slot's stream ...
-    CK(hipStreamWaitEvent(v->stream, s->ev_pcm, 0));          // ... is finished before the gate reads it
+    CKR(L.order(v->stream));
     VadPlan pl;
-    vad_plan_one(s->pcm + (size_t)item * s->pcm_cap + start, n, (int)T, pl);
+    vad_plan_one(pcm, n, (int)T, pl);
     return vad_run_batch(v, pl, probs_out, device_ms_out);
 }
 
@@ -661,19 +655,18 @@ extern "C" int32_t wlx_vad_probs_pcm_batch(wlx_vad* v, wlx_engine* e, int32_t sl
                                            const int32_t* extra_zero_windows, int32_t n, float* probs_out, int64_t cap,
                                            int32_t* n_windows_out, float* device_ms_out) {
     if (!v || !e || !n_samples || !probs_out || !n_windows_out) return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm_batch: null argument");
-    if (e->device != v->device)
-        return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm_batch: the engine lives on device %d, the VAD model on %d", e->device, v->device);
+    CKR(PcmLease::same_device("wlx_vad_probs_pcm_batch", "engine", e->device, "VAD model", v->device));
     VadPlan pl;
     CKR(vad_plan("wlx_vad_probs_pcm_batch", n_samples, extra_zero_windows, n, cap, pl));
-    SlotGuard sg_;
-    CKR(slot_acquire(e, slot, sg_));
-    Slot* s = sg_.s;
-    if (first_item < 0 || first_item + (int64_t)n > s->B)
-        return set_error(WLX_ERR_ARG, "wlx_vad_probs_pcm_batch: items [%d, %lld) outside the slot's %d", first_item, (long long)first_item + n, s->B);
-    for (int i = 0; i < n; ++i)
-        if (n_samples[i] > s->npcm[first_item + i])
-            return set_error(WLX_ERR_STATE, "wlx_vad_probs_pcm_batch: [0, %lld) is not resident (item %d holds %lld samples)", (long long)n_samples[i],
-                             first_item + i, (long long)s->npcm[first_item + i]);
+    PcmLease L;
+    CKR(L.open_slot(e, slot));
+    CKR(L.item("wlx_vad_probs_pcm_batch", first_item, n));
+    // (an item with n == 0 and extra windows reads no sample: its pointer is never dereferenced, the slot may hold no PCM buffer yet)
+    const float* pcm[WLX_VAD_MAX_BATCH];
+    for (int i = 0; i < n; ++i) {
+        L.view(first_item + i);
+        CKR(L.range("wlx_vad_probs_pcm_batch", 0, n_samples[i], &pcm[i]));
+    }
     std::lock_guard<std::mutex> lk(v->mu);
     if (pl.windows > 0) {
         CK(hipSetDevice(v->device));
@@ -683,12 +676,8 @@ extern "C" int32_t wlx_vad_probs_pcm_batch(wlx_vad* v, wlx_engine* e, int32_t sl
     for (int i = 0; i < n; ++i) n_windows_out[i] = pl.T[i];
     if (device_ms_out) *device_ms_out = 0.0f;
     if (pl.windows == 0) return WLX_OK;
-    if (!s->ev_pcm) CK(hipEventCreateWithFlags(&s->ev_pcm, hipEventDisableTiming));
-    CK(hipEventRecord(s->ev_pcm, s->stream));                 // whatever wrote the items' PCM on the slot's stream ...
-    CK(hipStreamWaitEvent(v->stream, s->ev_pcm, 0));          // ... is finished before the gate reads it
-    // (an item with n == 0 and extra windows reads no sample: its pointer is never dereferenced, s->pcm may still be null)
-    for (int k = 0; k < pl.tab.n; ++k)
-        pl.tab.it[k].pcm = s->pcm ? s->pcm + (size_t)(first_item + pl.src[k]) * s->pcm_cap : nullptr;
+    CKR(L.order(v->stream));
+    for (int k = 0; k < pl.tab.n; ++k) pl.tab.it[k].pcm = pcm[pl.src[k]];
     return vad_run_batch(v, pl, probs_out, device_ms_out);
 }
 
