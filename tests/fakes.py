@@ -50,7 +50,44 @@ class FakeSlot:
         return self.engine.script_lang(batch, lang_ids)
 
 
+class FrontEndSlot(FakeSlot):
+    """FakeSlot with the device front end's methods, scripted, for both routes of the batched pipeline: resident PCM per item
+    (`resident`), and the audio every `logmel` was given (`logmel_audio`, per item)."""
+
+    def __init__(self, engine, max_batch, rows):
+        super().__init__(engine, max_batch, rows)
+        self.resident, self.logmel_audio, self._enc_generation = {}, {}, 0
+
+    def pcm_put(self, pcm, item=0):
+        self.calls.append(("pcm_put", item, len(pcm)))
+        self.resident[item] = np.array(pcm, np.float32)
+
+    def put_frames_split(self, frames, rate, first_item=0):
+        frames = np.asarray(frames)
+        self.calls.append(("put_frames_split", frames.shape, rate, first_item))
+        for c in range(frames.shape[1]):
+            self.resident[first_item + c] = np.array(frames[:, c], np.float32)
+        return frames.shape[0]
+
+    def pcm(self, item=0):
+        self.calls.append(("pcm", item))
+        return self.resident[item]
+
+    def logmel(self, pcm, item=0):
+        self.logmel_audio[item] = np.array(pcm, np.float32)
+        self.resident[item] = self.logmel_audio[item]          # (the real slot uploads the audio into the item's PCM buffer)
+        return super().logmel(pcm, item)
+
+    def logmel_chunks(self, chunks, src_item=0, first_item=0):
+        self.calls.append(("logmel_chunks", [len(c) for c in chunks], src_item, first_item))
+        for i, c in enumerate(chunks):
+            self._frames[first_item + i] = (sum(b - a for a, b in c) + 160) // 160
+        return [self._frames[first_item + i] for i in range(len(chunks))]
+
+
 class FakeEngine:
+    slot_type = FakeSlot
+
     def __init__(self, spec: Optional[WhisperSpec] = None):
         self.spec = spec or WhisperSpec(80, 128, 2, 1, 1, 512, 2310)
         self.device = 0
@@ -60,7 +97,7 @@ class FakeEngine:
         self.lang_index = 0
 
     def create_slot(self, max_batch=1, rows=5):
-        s = FakeSlot(self, max_batch, rows)
+        s = self.slot_type(self, max_batch, rows)
         self.slots.append(s)
         return s
 
@@ -73,3 +110,7 @@ class FakeEngine:
         p = np.full((batch, len(lang_ids)), 0.2 / max(1, len(lang_ids) - 1), np.float32)
         p[:, self.lang_index] = 0.8
         return p
+
+
+class FrontEndEngine(FakeEngine):
+    slot_type = FrontEndSlot

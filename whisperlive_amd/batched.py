@@ -12,12 +12,20 @@ Device route (a real engine): the audio becomes resident ONCE in item 0 of the c
 runs: ``wlx_logmel_chunks`` (one launch of each log-mel kernel cuts the group's chunks out of the resident PCM into the slot's
 feature items), ``encode``, optionally ``detect_language``, ``generate``. An engine whose slots lack those methods (the host-logic
 test doubles) takes the host-chunk route: ``collect_chunks`` + one feature-extractor call per chunk, as the reference does.
+
+One plan, two routes. ``_plan`` is the procedure of a file transcription written once — batch checks, slot, clips (explicit, gate or
+short file), chunks pooled in order (channel, start), ``DeviceChunks``, language, tokenizer, options, info — over a ``Resident``
+description of the audio; a mono file is a file with one channel whose source is item 0. The mono route (``_transcribe``) keeps what
+is its own: ``_resident_mono`` (the host routes, the down-mix, the lazy host copy, the gate on item 0), segments yielded as groups
+finish with running ids, ``last_speech_timestamp`` on the pipeline. The multichannel route's own is in multichannel.py. Both decode
+through ``_groups`` and build their segments with ``_segment``.
 """
 from __future__ import annotations
 
 import inspect
+from contextlib import nullcontext
 from math import ceil
-from typing import BinaryIO, Iterable, List, Optional, Sequence, Tuple, Union
+from typing import BinaryIO, Callable, Iterable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -25,6 +33,7 @@ from . import vad as _vad
 from . import word_timing as _wt
 from ._lib import ERR_ARG as _ERR_ARG, ERR_DATA as _ERR_DATA, LM_MAXRANGES as _MAXRANGES, WlxError as _WlxError
 from .engine import ResidentPcm
+from .multichannel import language_channel, pool_chunks
 from .tokenizer import Tokenizer
 from .transcriber import EncoderOutput, get_compression_ratio, get_suppressed_tokens, pad_or_trim, restore_speech_timestamps
 from .types import Segment, TranscriptionInfo, TranscriptionOptions, Word
@@ -34,14 +43,15 @@ MAX_DEC_ROWS = 320          # decoder rows of one step (include/wlx.h wlx_slot_c
 
 
 class DeviceChunks:
-    """The `features` of the device route: the chunks of one file as sample ranges of the PCM resident in item `src_item` of `slot`.
-    Nothing is computed until a group is decoded (`generate_segment_batched`); slicing gives the group. `host_audio()` returns the
-    16 kHz host copy — fetched from the device only when something on the host needs it (a chunk that falls back).
-    A list `src_item` carries one source item PER CHUNK (multichannel: the chunks of several channels pooled into one list; a group
-    then goes out through wlx_logmel_chunks_multi). There the sources lie behind every group's destination items, so nothing a group
-    does evicts a source, and `host_audio` is a callable of the source item."""
+    """The `features` of the device route: the chunks of one file as sample ranges of PCM resident in items of `slot`, one source item
+    per chunk. Nothing is computed until a group is decoded (`generate_segment_batched`); slicing gives the group.
+    `src_item`: an int — every chunk reads that item (the mono route: a group goes out through wlx_logmel_chunks, and a chunk that
+    falls back may land in the source and evict it) — or a list with one item per chunk (multichannel: the chunks of several channels
+    pooled into one list; a group goes out through wlx_logmel_chunks_multi, and the sources lie behind every group's destination
+    items, so nothing a group does evicts one). `host_audio(item)` returns the 16 kHz host copy of a source — fetched from the device
+    only when something on the host needs it (a chunk that falls back)."""
 
-    def __init__(self, slot, ranges: List[List[Tuple[int, int]]], host_audio, src_item: int = 0, n_resident: int = 0):
+    def __init__(self, slot, ranges: List[List[Tuple[int, int]]], host_audio, src_item: Union[int, List[int]] = 0, n_resident: int = 0):
         self.slot, self.ranges, self._host, self.src_item, self.n_resident = slot, ranges, host_audio, src_item, n_resident
         self.shared = {"resident": True}        # one state for every slice: a fallback into the source item evicts the source
         self.channels = None                    # multichannel: the file channel of each chunk (sliced with the chunks)
@@ -62,60 +72,42 @@ class DeviceChunks:
     def shape(self):
         return (len(self.ranges), self.slot.engine.spec.n_mels, 3000)
 
-    def host_audio(self) -> np.ndarray:
-        if callable(self._host):
-            self.shared.setdefault("host", self._host())
-            return self.shared["host"]
-        return self._host
+    def host_audio(self, item: int = 0) -> np.ndarray:
+        if not callable(self._host):
+            return self._host
+        copies = self.shared.setdefault("host", {})
+        if item not in copies:
+            copies[item] = self._host(item)
+        return copies[item]
 
     def to_device(self) -> List[int]:
         """The group's features into items 0 .. len - 1 of the slot -> frames per item (incl. the pad frame)."""
         slot, n = self.slot, len(self.ranges)
-        if isinstance(self.src_item, list):
-            return self._to_device_multi()
-        if not self.shared["resident"]:
-            slot.pcm_put(self.host_audio(), item=self.src_item)
+        one = not isinstance(self.src_item, list)
+        src = [self.src_item] * n if one else self.src_item          # the source item of each chunk
+        if not one and n > min(src):
+            raise ValueError(f"a group of {n} chunks would overwrite source item {min(src)}")
+        if not self.shared["resident"]:              # (only the one source of a mono file is ever evicted: the check above)
+            slot.pcm_put(self.host_audio(src[0]), item=src[0])
             self.shared["resident"] = True
         frames = [0] * n
         ok = [len(r) <= _MAXRANGES for r in self.ranges]
         a = 0
-        while a < n:                                 # runs of chunks the kernel takes: one launch of each kernel per run
+        while a < n:                                 # runs of chunks the kernel takes: one launch of each kernel per run, whatever the mix of sources
             if not ok[a]:
                 a += 1
                 continue
             b = a
             while b < n and ok[b]:
                 b += 1
-            frames[a:b] = slot.logmel_chunks(self.ranges[a:b], src_item=self.src_item, first_item=a)
+            frames[a:b] = slot.logmel_chunks(self.ranges[a:b], src_item=self.src_item if one else src[a:b], first_item=a)
             a = b
         for i in range(n):                           # more ranges than the kernel's table holds: the host concatenation, this chunk alone
             if not ok[i]:
-                audio = self.host_audio()
+                audio = self.host_audio(src[i])
                 frames[i] = slot.logmel(np.concatenate([audio[s:e] for s, e in self.ranges[i]]), item=i)
-                if i == self.src_item:
+                if i in src:
                     self.shared["resident"] = False
-        return frames
-
-    def _to_device_multi(self) -> List[int]:
-        slot, n = self.slot, len(self.ranges)
-        if n > min(self.src_item):
-            raise ValueError(f"a group of {n} chunks would overwrite source item {min(self.src_item)}")
-        frames = [0] * n
-        ok = [len(r) <= _MAXRANGES for r in self.ranges]
-        a = 0
-        while a < n:                                 # as above: one launch of each kernel per run, whatever the mix of sources
-            if not ok[a]:
-                a += 1
-                continue
-            b = a
-            while b < n and ok[b]:
-                b += 1
-            frames[a:b] = slot.logmel_chunks(self.ranges[a:b], src_item=self.src_item[a:b], first_item=a)
-            a = b
-        for i in range(n):
-            if not ok[i]:
-                audio = self._host(self.src_item[i])
-                frames[i] = slot.logmel(np.concatenate([audio[s:e] for s, e in self.ranges[i]]), item=i)
         return frames
 
 
@@ -153,43 +145,35 @@ class BatchedInferencePipeline:
                 """the align functions for a list of windows that starts at window `base` of the group"""
                 def align_fn(text_tokens, _num_frames, window):
                     window += base
-                    r = self.model.model.align(encoder_output.select([window]), tokenizer.sot_sequence, [text_tokens],
-                                               segment_sizes[window])[0]
-                    pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
-                    return pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)
+                    return _wt.unpack_alignment(self.model.model.align(
+                        encoder_output.select([window]), tokenizer.sot_sequence, [text_tokens], segment_sizes[window])[0])
 
                 # ... or, where the model's align takes a group, every chunk that has text in ONE call (wlx_align_batch), as the reference does
                 def align_many_fn(requests):
                     res = self.model.model.align(encoder_output.select([base + r[2] for r in requests]), tokenizer.sot_sequence,
                                                  [r[0] for r in requests], [segment_sizes[base + r[2]] for r in requests])
-                    out = []
-                    for r in res:
-                        pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
-                        out.append((pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)))
-                    return out
+                    return [_wt.unpack_alignment(r) for r in res]
 
                 # (handed over on the function, the form add_word_timestamps also takes: the call keeps the nine positional arguments a
                 # stand-in for add_word_timestamps is written against)
                 align_fn.align_many = align_many_fn
                 return align_fn
 
+            # a mono group is one run (channel None) whose last-speech time lives on the pipeline; a multichannel file keeps one per channel
+            runs = channels if channels is not None else [None] * len(segmented_outputs)
+            last = {None: self.last_speech_timestamp} if channels is None else features.shared.setdefault("last_speech", {})
+            end = 0
+            while end < len(runs):
+                base = end
+                while end < len(runs) and runs[end] == runs[base]:
+                    end += 1
+                got = _wt.add_word_timestamps(
+                    segmented_outputs[base:end], tokenizer, aligners(base), 0, self.model.tokens_per_second,
+                    self.model.frames_per_second, options.prepend_punctuations, options.append_punctuations, last.get(runs[base], 0.0))
+                if got is not None:
+                    last[runs[base]] = got
             if channels is None:
-                self.last_speech_timestamp = _wt.add_word_timestamps(
-                    segmented_outputs, tokenizer, aligners(0), 0, self.model.tokens_per_second, self.model.frames_per_second,
-                    options.prepend_punctuations, options.append_punctuations, self.last_speech_timestamp)
-            else:
-                last = features.shared.setdefault("last_speech", {})        # per channel, for every group of this file
-                end = 0
-                while end < len(channels):
-                    base = end
-                    while end < len(channels) and channels[end] == channels[base]:
-                        end += 1
-                    got = _wt.add_word_timestamps(
-                        segmented_outputs[base:end], tokenizer, aligners(base), 0, self.model.tokens_per_second,
-                        self.model.frames_per_second, options.prepend_punctuations, options.append_punctuations,
-                        last.get(channels[base], 0.0))
-                    if got is not None:
-                        last[channels[base]] = got
+                self.last_speech_timestamp = last[None]
         return segmented_outputs
 
     # ---- (:176-254)
@@ -294,130 +278,12 @@ class BatchedInferencePipeline:
         Arguments as the reference's (:302-377); compression_ratio_threshold, log_prob_threshold, no_speech_threshold,
         condition_on_previous_text, prompt_reset_on_temperature, prefix, max_initial_timestamp and
         hallucination_silence_threshold are accepted and unused there too. `clip_timestamps`: dicts with "start" / "end" in samples."""
-        model = self.model
-        sampling_rate = model.feature_extractor.sampling_rate
-
-        if multilingual and not model.model.is_multilingual:
-            model.logger.warning("The current model is English-only but the multilingual parameter is set to"
-                                 "True; setting to False instead.")
-            multilingual = False
-
-        batch_size = int(batch_size)
-        max_batch = int(getattr(model, "max_batch", batch_size))
-        if batch_size < 1:
-            raise ValueError(f"batch_size {batch_size}: at least one chunk per decode")
-        if batch_size > max_batch:
-            raise ValueError(f"batch_size {batch_size} exceeds this transcriber's max_batch {max_batch} (the items one slot holds): "
-                             f"create the model with max_batch >= {batch_size}")
-        if batch_size * int(beam_size) > MAX_DEC_ROWS:
-            raise ValueError(f"batch_size {batch_size} x beam_size {beam_size} = {batch_size * int(beam_size)} decoder rows: "
-                             f"one decode step holds at most {MAX_DEC_ROWS}")
-
-        # ---- the audio becomes resident once (device route) or stays on the host (engines without the front end)
-        slot = model._slot(rows=int(beam_size))
-        if hasattr(model, "_tls"):
-            model._tls.file_audio = None      # (what an earlier call of this thread left resident is about to be overwritten)
-        device = all(hasattr(slot, m) for m in ("logmel_chunks", "pcm_put", "pcm"))
-        host_audio = None            # the 16 kHz host waveform, a callable that fetches it, or None until something asks
-        n_samples = None
-        if not isinstance(audio, np.ndarray):
-            if not isinstance(audio, (str, bytes, bytearray)) and not hasattr(audio, "read"):
-                raise TypeError("audio must be a float32 numpy waveform at 16 kHz, or a WAV / FLAC path, bytes or file object")
-            from .audio_io import _read_all, frames_to_mono, read_audio
-            from .engine import resample_supported
-            data = _read_all(audio)
-            # a FLAC file is decoded on the device (Slot.put_flac leaves resident what put_frames(read_flac(file)) would); a stream that
-            # route does not serve keeps the host decode below, a damaged one is the ValueError the host decoder raises
-            on_device = False
-            if device and data[:4] == b"fLaC" and sampling_rate == 16000 and hasattr(slot, "put_flac"):
-                try:
-                    with slot.lock:
-                        n_samples, _ = slot.put_flac(data)
-                    host_audio = slot.pcm
-                    on_device = True
-                except _WlxError as e:
-                    if e.code == _ERR_DATA:
-                        raise ValueError(f"damaged FLAC stream: {e}") from e
-                    if e.code != _ERR_ARG:
-                        raise
-            if not on_device:
-                file_frames, file_sr = read_audio(data)
-                on_device = (device and sampling_rate == 16000 and file_frames.shape[0] > 0 and hasattr(slot, "put_frames")
-                             and resample_supported(file_sr, file_frames.shape[1]))
-                if on_device:
-                    try:
-                        with slot.lock:
-                            n_samples = slot.put_frames(file_frames, file_sr)
-                        host_audio = slot.pcm          # fetched only when something on the host needs it
-                    except _WlxError as e:
-                        if e.code != _ERR_ARG:             # only a REFUSED shape (nothing was launched) keeps the host route
-                            raise
-                        on_device = False
-                if not on_device:
-                    audio = frames_to_mono(file_frames, file_sr, sampling_rate)
-        if n_samples is None:
-            audio = np.ascontiguousarray(audio, dtype=np.float32)
-            host_audio, n_samples = audio, audio.shape[0]
-            if device and n_samples > 0:
-                with slot.lock:
-                    slot.pcm_put(audio)
-        duration = n_samples / sampling_rate
-
-        chunk_length = chunk_length or model.feature_extractor.chunk_length
-        from_vad = False
-        # if no segment split is provided, use vad_model and generate segments
-        if not clip_timestamps:
-            if vad_filter:
-                vad_parameters = _vad_options(vad_parameters, chunk_length)
-                vad_model = model._vad_model()
-                if (device and n_samples > 0 and hasattr(vad_model, "probs_pcm")
-                        and getattr(vad_model, "device", None) == getattr(slot.engine, "device", -1)):
-                    with slot.lock:
-                        clip_timestamps = _vad.get_speech_timestamps_pcm(slot, n_samples, vad_parameters, sampling_rate, model=vad_model)
-                else:
-                    clip_timestamps = _vad.get_speech_timestamps(_resolve(host_audio, slot), vad_parameters, sampling_rate, model=vad_model)
-                from_vad = True
-            # run the audio if it is less than 30 sec even without clip_timestamps
-            elif duration < chunk_length:
-                clip_timestamps = [{"start": 0, "end": n_samples}]
-            else:
-                raise RuntimeError("No clip timestamps found. "
-                                   "Set 'vad_filter' to True or provide 'clip_timestamps'.")
-        clip_timestamps = [c for c in clip_timestamps if c["end"] > c["start"]]
-
-        duration_after_vad = sum((segment["end"] - segment["start"]) for segment in clip_timestamps) / sampling_rate
-
-        if duration_after_vad:
-            chunk_ranges, chunks_metadata = _collect_ranges(clip_timestamps, sampling_rate, chunk_length)
-        else:
-            chunk_ranges, chunks_metadata = [], []
-        if device:
-            features = DeviceChunks(slot, chunk_ranges, host_audio, 0, n_samples)
-            if n_samples > 0 and hasattr(model, "_tls"):
-                # what reads the file after the transcription (speaker labels) finds it in the source item: WhisperModelHIP.resident_file_audio
-                model._tls.file_audio = ResidentPcm(slot, 0, n_samples, features.shared)
-        else:
-            wave = _resolve(host_audio, slot)
-            features = [model.feature_extractor(np.concatenate([wave[s:e] for s, e in rg]))[..., :-1] for rg in chunk_ranges]
-
-        # detecting the language if not provided
-        language, language_probability, all_language_probs = self._language(
-            features, language, language_detection_segments, language_detection_threshold)
-
-        tokenizer = Tokenizer(model.hf_tokenizer, model.model.is_multilingual, task=task, language=language)
-
-        if not device:
-            features = np.stack([pad_or_trim(feature) for feature in features]) if features else []
-
-        options = _options(tokenizer, locals(), clip_timestamps)
-
-        info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
-                                 duration_after_vad=duration_after_vad, transcription_options=options,
-                                 vad_options=vad_parameters, all_language_probs=all_language_probs)
-
-        segments = self._batched_segments_generator(features, tokenizer, chunks_metadata, batch_size, options, log_progress)
-        if from_vad:
-            segments = self._restored(segments, clip_timestamps, sampling_rate)
+        a = dict(locals())                     # the arguments by name, as `transcribe` binds them for the multichannel route
+        features, chunks_metadata, _channels, vad_clips, tokenizer, options, info = _plan(
+            self, a, lambda slot: _resident_mono(self.model, slot, audio), max_batch=getattr(self.model, "max_batch", None))
+        segments = self._batched_segments_generator(features, tokenizer, chunks_metadata, int(batch_size), options, log_progress)
+        if vad_clips is not None:
+            segments = self._restored(segments, vad_clips[0], self.model.feature_extractor.sampling_rate)
         return segments, info
 
     def transcribe(self, audio, *args, multichannel: bool = False, **kwargs):
@@ -484,29 +350,194 @@ class BatchedInferencePipeline:
         for seg in segments:
             yield restore_speech_timestamps([seg], speech_chunks, sampling_rate)[0]
 
+    def _groups(self, features, tokenizer, chunks_metadata, batch_size, options, log_progress):
+        """decode `batch_size` chunks at a time, under the slot's lock on the device route -> (index of the group's first chunk, what
+        `forward` returns for the group), group by group"""
+        lock = features.slot.lock if isinstance(features, DeviceChunks) else nullcontext()
+        for i in range(0, len(features), batch_size):
+            with lock:
+                results = self.forward(features[i: i + batch_size], tokenizer, chunks_metadata[i: i + batch_size], options)
+            yield i, results
+            if log_progress:
+                self.model.logger.info("batched transcription: %d / %d chunks", min(i + batch_size, len(features)), len(features))
+
     # ---- (:534-571)
     def _batched_segments_generator(self, features, tokenizer, chunks_metadata, batch_size, options, log_progress):
         seg_idx = 0
-        slot = features.slot if isinstance(features, DeviceChunks) else None
-        for i in range(0, len(features), batch_size):
-            if slot is not None:
-                with slot.lock:
-                    results = self.forward(features[i: i + batch_size], tokenizer, chunks_metadata[i: i + batch_size], options)
-            else:
-                results = self.forward(features[i: i + batch_size], tokenizer, chunks_metadata[i: i + batch_size], options)
-
+        for _i, results in self._groups(features, tokenizer, chunks_metadata, batch_size, options, log_progress):
             for result in results:
                 for segment in result:
                     seg_idx += 1
-                    yield Segment(
-                        seek=segment["seek"], id=seg_idx, text=segment["text"], start=round(segment["start"], 3),
-                        end=round(segment["end"], 3),
-                        words=(None if not options.word_timestamps else [Word(**word) for word in segment["words"]]),
-                        tokens=segment["tokens"], avg_logprob=segment["avg_logprob"], no_speech_prob=segment["no_speech_prob"],
-                        compression_ratio=segment["compression_ratio"], temperature=options.temperatures[0])
-            if log_progress:
-                self.model.logger.info("batched transcription: %d / %d chunks", min(i + batch_size, len(features)), len(features))
+                    yield _segment(segment, options, seg_idx)
         self.last_speech_timestamp = 0.0
+
+
+def _segment(result: dict, options, seg_id: int = 0, channel: Optional[int] = None) -> Segment:
+    """one sub-segment dict of `forward` -> the Segment the caller gets"""
+    return Segment(
+        seek=result["seek"], id=seg_id, text=result["text"], start=round(result["start"], 3), end=round(result["end"], 3),
+        words=(None if not options.word_timestamps else [Word(**word) for word in result["words"]]),
+        tokens=result["tokens"], avg_logprob=result["avg_logprob"], no_speech_prob=result["no_speech_prob"],
+        compression_ratio=result["compression_ratio"], temperature=options.temperatures[0], channel=channel)
+
+
+class Resident(NamedTuple):
+    """The audio of one file as a route left it for `_plan`: `n_samples` at 16 kHz per channel, channel c resident in item
+    `items[c]` of the slot."""
+    n_samples: int
+    items: List[int]
+    host_audio: object                  # the host waveform, or a callable (item) -> its host copy, fetched when something asks
+    gate: Callable                      # (vad_parameters, vad_model) -> the speech clips of each channel
+    device: bool = True                 # False: the audio is on the host only (mono, an engine without the front end)
+    multichannel: bool = False          # True: chunks and segments carry their channel, even when there is one
+
+
+def _plan(pipe, a: dict, make_resident: Callable, max_batch: Optional[int] = None):
+    """The file plan behind both routes of BatchedInferencePipeline.transcribe: from its arguments `a` (by name, defaults applied) to
+    what the segment generators decode. make_resident(slot) -> Resident is the route's own way of reading the audio, called once the
+    batch has been checked and the slot taken; max_batch: the mono route's limit on batch_size (multichannel checks its own, which
+    depends on the channel count, in make_resident).
+    -> (features, chunks_metadata, the channel of each chunk or None (mono), the gate's clips per channel or None (times need no
+    restoring), tokenizer, options, info). The chunks of all channels are pooled in order (channel, start); a mono file is a file
+    with one channel."""
+    model = pipe.model
+    sampling_rate = model.feature_extractor.sampling_rate
+    a = dict(a)
+    if a["multilingual"] and not model.model.is_multilingual:
+        model.logger.warning("The current model is English-only but the multilingual parameter is set to"
+                             "True; setting to False instead.")
+        a["multilingual"] = False
+    batch_size, beam_size = int(a["batch_size"]), int(a["beam_size"])
+    if batch_size < 1:
+        raise ValueError(f"batch_size {batch_size}: at least one chunk per decode")
+    if max_batch is not None and batch_size > int(max_batch):
+        raise ValueError(f"batch_size {batch_size} exceeds this transcriber's max_batch {int(max_batch)} (the items one slot holds): "
+                         f"create the model with max_batch >= {batch_size}")
+    if batch_size * beam_size > MAX_DEC_ROWS:
+        raise ValueError(f"batch_size {batch_size} x beam_size {beam_size} = {batch_size * beam_size} decoder rows: "
+                         f"one decode step holds at most {MAX_DEC_ROWS}")
+    slot = model._slot(rows=beam_size)
+    if hasattr(model, "_tls"):
+        model._tls.file_audio = None          # (what an earlier call of this thread left resident is about to be overwritten)
+    res = make_resident(slot)
+    n_samples = res.n_samples
+    duration = n_samples / sampling_rate
+
+    chunk_length = a["chunk_length"] or model.feature_extractor.chunk_length
+    clip_timestamps, vad_parameters = a["clip_timestamps"], a["vad_parameters"]
+    from_vad = False
+    # if no segment split is provided, use vad_model and generate segments
+    if clip_timestamps:
+        clips = [[dict(c) for c in clip_timestamps] for _ in res.items]          # explicit clips apply to every channel
+    elif a["vad_filter"]:
+        vad_parameters = _vad_options(vad_parameters, chunk_length)
+        clips = res.gate(vad_parameters, model._vad_model())
+        from_vad = True
+    # run the audio if it is less than 30 sec even without clip_timestamps
+    elif duration < chunk_length:
+        clips = [[{"start": 0, "end": n_samples}] for _ in res.items]
+    else:
+        raise RuntimeError("No clip timestamps found. "
+                           "Set 'vad_filter' to True or provide 'clip_timestamps'.")
+    clips = [[c for c in cl if c["end"] > c["start"]] for cl in clips]
+    speech = [sum(c["end"] - c["start"] for c in cl) for cl in clips]
+    duration_after_vad = sum(speech) / sampling_rate
+
+    ranges, chunks_metadata, channels = pool_chunks(
+        [_collect_ranges(cl, sampling_rate, chunk_length) if cl else ([], []) for cl in clips])
+    if res.device:
+        features = DeviceChunks(slot, ranges, res.host_audio, [res.items[c] for c in channels] if res.multichannel else res.items[0],
+                                n_samples)
+        if n_samples > 0 and hasattr(model, "_tls"):
+            # what reads the file after the transcription (speaker labels) finds each channel in its item: resident_file_audio
+            handles = [ResidentPcm(slot, i, n_samples, features.shared) for i in res.items]
+            model._tls.file_audio = handles if res.multichannel else handles[0]
+    else:
+        wave = _resolve(res.host_audio, slot)
+        features = [model.feature_extractor(np.concatenate([wave[s:e] for s, e in rg]))[..., :-1] for rg in ranges]
+
+    # one language for the file: the one given, or detected on the channel with the most speech — multichannel in groups of batch_size
+    # chunks, so that the detection's log-mel launches stay in front of the source items too
+    lc = language_channel(speech)
+    lead = features[channels.index(lc): channels.index(lc) + channels.count(lc)] if lc in channels else features[0:0]
+    language, language_probability, all_language_probs = pipe._language(
+        lead, a["language"], a["language_detection_segments"], a["language_detection_threshold"],
+        group_size=batch_size if res.multichannel else None)
+
+    tokenizer = Tokenizer(model.hf_tokenizer, model.model.is_multilingual, task=a["task"], language=language)
+    if not res.device:
+        features = np.stack([pad_or_trim(feature) for feature in features]) if features else []
+    elif res.multichannel:
+        features.channels = channels            # every group is cut with its chunks' channels (forward reads them)
+    options = _options(tokenizer, a, (clip_timestamps or clips) if res.multichannel else clips[0])
+    info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
+                             duration_after_vad=duration_after_vad, transcription_options=options,
+                             vad_options=vad_parameters, all_language_probs=all_language_probs)
+    return features, chunks_metadata, channels if res.multichannel else None, clips if from_vad else None, tokenizer, options, info
+
+
+def _resident_mono(model, slot, audio) -> Resident:
+    """The mono route's audio: a file is down-mixed and resampled into item 0 on the device (a FLAC file decoded there too), a
+    waveform uploaded; an engine without the front end, or a shape the front end refuses, keeps the audio on the host."""
+    sampling_rate = model.feature_extractor.sampling_rate
+    device = all(hasattr(slot, m) for m in ("logmel_chunks", "pcm_put", "pcm"))
+    host_audio = n_samples = None
+    if not isinstance(audio, np.ndarray):
+        from .audio_io import frames_to_mono, read_audio
+        from .engine import resample_supported
+        data = _file_bytes(audio)
+        # a FLAC file is decoded on the device (Slot.put_flac leaves resident what put_frames(read_flac(file)) would); a stream that
+        # route does not serve keeps the host decode below, a damaged one is the ValueError the host decoder raises
+        on_device = False
+        if device and data[:4] == b"fLaC" and sampling_rate == 16000 and hasattr(slot, "put_flac"):
+            try:
+                with slot.lock:
+                    n_samples, _ = slot.put_flac(data)
+                on_device = True
+            except _WlxError as e:
+                if e.code == _ERR_DATA:
+                    raise ValueError(f"damaged FLAC stream: {e}") from e
+                if e.code != _ERR_ARG:
+                    raise
+        if not on_device:
+            file_frames, file_sr = read_audio(data)
+            on_device = (device and sampling_rate == 16000 and file_frames.shape[0] > 0 and hasattr(slot, "put_frames")
+                         and resample_supported(file_sr, file_frames.shape[1]))
+            if on_device:
+                try:
+                    with slot.lock:
+                        n_samples = slot.put_frames(file_frames, file_sr)
+                except _WlxError as e:
+                    if e.code != _ERR_ARG:             # only a REFUSED shape (nothing was launched) keeps the host route
+                        raise
+                    on_device = False
+            if not on_device:
+                audio = frames_to_mono(file_frames, file_sr, sampling_rate)
+        if on_device:
+            host_audio = slot.pcm                      # fetched only when something on the host needs it
+    if n_samples is None:
+        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        host_audio, n_samples = audio, audio.shape[0]
+        if device and n_samples > 0:
+            with slot.lock:
+                slot.pcm_put(audio)
+
+    def gate(vad_parameters, vad_model):
+        if (device and n_samples > 0 and hasattr(vad_model, "probs_pcm")
+                and getattr(vad_model, "device", None) == getattr(slot.engine, "device", -1)):
+            with slot.lock:
+                return [_vad.get_speech_timestamps_pcm(slot, n_samples, vad_parameters, sampling_rate, model=vad_model)]
+        return [_vad.get_speech_timestamps(_resolve(host_audio, slot), vad_parameters, sampling_rate, model=vad_model)]
+
+    return Resident(n_samples, [0], host_audio, gate, device)
+
+
+def _file_bytes(audio) -> bytes:
+    """the bytes of what is not a waveform: a path, bytes or a file object; anything else is refused"""
+    if not isinstance(audio, (str, bytes, bytearray)) and not hasattr(audio, "read"):
+        raise TypeError("audio must be a float32 numpy waveform at 16 kHz, or a WAV / FLAC path, bytes or file object")
+    from .audio_io import _read_all
+    return _read_all(audio)
 
 
 def _vad_options(vad_parameters, chunk_length) -> VadOptions:

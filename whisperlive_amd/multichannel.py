@@ -9,7 +9,12 @@ pass (``SileroHIPModel.probs_pcm_many``), and the chunks of all channels are poo
 group are 0 .. batch_size - 1 and ``batch_size <= max_batch - C``, so no group ever overwrites a source. Nothing but the one upload and
 the range tables crosses PCIe. There is NO host route: a shape the device front end refuses is a ValueError.
 
-The functions above ``transcribe_multichannel`` are host logic only (tests/test_multichannel_host.py).
+The procedure itself — batch checks, clips, chunks, language, options, info — is ``batched._plan``, the one the mono route follows
+(a mono file is a file with one channel whose source is item 0). This module keeps what is the route's own: how the channels become
+resident (``_make_resident``: the last C items, the ``_NO_HOST`` refusals, ``check_batch``, ``source_rows_addressable``, the one gate
+pass) and how the segments leave (``_segments``: all of them, sorted by (start, channel), when the last group is done).
+
+The functions above ``_make_resident`` are host logic only (tests/test_multichannel_host.py).
 """
 from __future__ import annotations
 
@@ -19,10 +24,9 @@ import numpy as np
 
 from . import vad as _vad
 from ._lib import ERR_ARG as _ERR_ARG, ERR_DATA as _ERR_DATA, WlxError as _WlxError
-from .engine import FlacFrames, ResidentPcm, resample_supported
-from .tokenizer import Tokenizer
+from .engine import FlacFrames, resample_supported
 from .transcriber import restore_speech_timestamps
-from .types import Segment, TranscriptionInfo, Word
+from .types import Segment
 
 
 def check_batch(batch_size: int, max_batch: int, channels: int):
@@ -73,17 +77,20 @@ def parse_waveform(audio: np.ndarray) -> np.ndarray:
 _NO_HOST = "multichannel=True has no host route: convert the file, or transcribe its down-mix with multichannel=False"
 
 
-def _make_resident(slot, audio, max_batch: int, batch_size: int):
-    """-> (channels, samples per channel, first item): the file's channels resident in the last C items of the slot"""
+def _make_resident(model, slot, audio, batch_size: int):
+    """-> batched.Resident: the file's channels resident in the last C items of the slot, and the gate that reads all of them"""
+    from .batched import Resident, _file_bytes
+    sampling_rate = model.feature_extractor.sampling_rate
+    if sampling_rate != 16000 or not all(hasattr(slot, m) for m in ("put_frames_split", "logmel_chunks", "pcm")):
+        raise ValueError(f"multichannel=True needs the device front end (Slot.put_frames_split), which this engine lacks. {_NO_HOST}")
+    max_batch = int(getattr(slot, "max_batch", getattr(model, "max_batch", batch_size)))
     if isinstance(audio, np.ndarray):
         frames = parse_waveform(audio)
         frames = frames if frames.dtype == np.int16 else np.ascontiguousarray(frames, dtype=np.float32)
         rate, flac = 16000, None
     else:
-        if not isinstance(audio, (str, bytes, bytearray)) and not hasattr(audio, "read"):
-            raise TypeError("audio must be a float32 numpy waveform at 16 kHz, or a WAV / FLAC path, bytes or file object")
-        from .audio_io import _read_all, read_audio
-        data = _read_all(audio)
+        from .audio_io import read_audio
+        data = _file_bytes(audio)
         if data[:4] == b"fLaC":
             import ctypes as C
             from . import _lib
@@ -119,7 +126,21 @@ def _make_resident(slot, audio, max_batch: int, batch_size: int):
         if e.code == _ERR_ARG:
             raise ValueError(f"the device front end refused the audio ({e}). {_NO_HOST}") from e
         raise
-    return channels, n, first
+    if not source_rows_addressable(channels, n):          # before any decode, not from the middle of the generator
+        raise ValueError(f"multichannel: {channels} channels of {n} samples lie further apart in the slot than the chunk "
+                         "gather addresses (2^31 - 1 samples)")
+    items = [first + c for c in range(channels)]
+
+    def gate(vad_parameters, vad_model):
+        if hasattr(vad_model, "probs_pcm_many") and getattr(vad_model, "device", None) == getattr(slot.engine, "device", -1):
+            with slot.lock:                  # the gate of ALL channels in one pass over the network
+                probs = vad_model.probs_pcm_many(slot, [n] * channels, first_item=first)
+            return [_vad.speech_segments_from_probs_native(p, n, vad_parameters, sampling_rate) for p in probs]
+        with slot.lock:                      # a gate with no device path reads the host copy, channel by channel
+            waves = [slot.pcm(i) for i in items]
+        return [_vad.get_speech_timestamps(w, vad_parameters, sampling_rate, model=vad_model) for w in waves]
+
+    return Resident(n, items, slot.pcm, gate, multichannel=True)
 
 
 def source_rows_addressable(channels: int, n_samples: int) -> bool:
@@ -134,107 +155,24 @@ def transcribe_multichannel(pipe, a: dict):
     """The body of BatchedInferencePipeline.transcribe(multichannel=True); `a`: that method's arguments by name, defaults applied.
     -> (segment generator, info): segments sorted by (start, channel) with ids 1..N in that order, each with its `channel` and times
     on its own channel's timeline; info.duration = the file's, info.duration_after_vad = the sum over channels. One language for the
-    file."""
-    from .batched import MAX_DEC_ROWS, DeviceChunks, _collect_ranges, _options, _vad_options
-    model = pipe.model
-    sampling_rate = model.feature_extractor.sampling_rate
-    a = dict(a)
-    if a["multilingual"] and not model.model.is_multilingual:
-        model.logger.warning("The current model is English-only but the multilingual parameter is set to"
-                             "True; setting to False instead.")
-        a["multilingual"] = False
-    batch_size, beam_size = int(a["batch_size"]), int(a["beam_size"])
-    if batch_size < 1:
-        raise ValueError(f"batch_size {batch_size}: at least one chunk per decode")
-    if batch_size * beam_size > MAX_DEC_ROWS:
-        raise ValueError(f"batch_size {batch_size} x beam_size {beam_size} = {batch_size * beam_size} decoder rows: "
-                         f"one decode step holds at most {MAX_DEC_ROWS}")
-    slot = model._slot(rows=beam_size)
-    if hasattr(model, "_tls"):
-        model._tls.file_audio = None
-    if sampling_rate != 16000 or not all(hasattr(slot, m) for m in ("put_frames_split", "logmel_chunks", "pcm")):
-        raise ValueError(f"multichannel=True needs the device front end (Slot.put_frames_split), which this engine lacks. {_NO_HOST}")
-    max_batch = int(getattr(slot, "max_batch", getattr(model, "max_batch", batch_size)))
-    n_channels, n_samples, first = _make_resident(slot, a["audio"], max_batch, batch_size)
-    if not source_rows_addressable(n_channels, n_samples):          # before any decode, not from the middle of the generator
-        raise ValueError(f"multichannel: {n_channels} channels of {n_samples} samples lie further apart in the slot than the chunk "
-                         "gather addresses (2^31 - 1 samples)")
-    items = [first + c for c in range(n_channels)]
-    duration = n_samples / sampling_rate
-
-    chunk_length = a["chunk_length"] or model.feature_extractor.chunk_length
-    clip_timestamps, vad_parameters = a["clip_timestamps"], a["vad_parameters"]
-    from_vad = False
-    if clip_timestamps:
-        clips = [[dict(c) for c in clip_timestamps] for _ in items]          # explicit clips apply to every channel
-    elif a["vad_filter"]:
-        vad_parameters = _vad_options(vad_parameters, chunk_length)
-        vad_model = model._vad_model()
-        if hasattr(vad_model, "probs_pcm_many") and getattr(vad_model, "device", None) == getattr(slot.engine, "device", -1):
-            with slot.lock:                  # the gate of ALL channels in one pass over the network
-                probs = vad_model.probs_pcm_many(slot, [n_samples] * n_channels, first_item=first)
-            clips = [_vad.speech_segments_from_probs_native(p, n_samples, vad_parameters, sampling_rate) for p in probs]
-        else:                                # a gate with no device path reads the host copy, channel by channel
-            with slot.lock:
-                waves = [slot.pcm(i) for i in items]
-            clips = [_vad.get_speech_timestamps(w, vad_parameters, sampling_rate, model=vad_model) for w in waves]
-        from_vad = True
-    elif duration < chunk_length:
-        clips = [[{"start": 0, "end": n_samples}] for _ in items]
-    else:
-        raise RuntimeError("No clip timestamps found. "
-                           "Set 'vad_filter' to True or provide 'clip_timestamps'.")
-    clips = [[c for c in cl if c["end"] > c["start"]] for cl in clips]
-    speech = [sum(c["end"] - c["start"] for c in cl) for cl in clips]
-    duration_after_vad = sum(speech) / sampling_rate
-
-    per_channel = [_collect_ranges(cl, sampling_rate, chunk_length) if cl else ([], []) for cl in clips]
-    ranges, meta, channels = pool_chunks(per_channel)
-
-    def host_audio(item):
-        return slot.pcm(item)
-
-    features = DeviceChunks(slot, ranges, host_audio, [items[c] for c in channels], n_samples)
-    if hasattr(model, "_tls"):
-        # what reads the file after the transcription (speaker labels) finds each channel in its item: resident_file_audio(channel)
-        model._tls.file_audio = [ResidentPcm(slot, i, n_samples) for i in items]
-
-    # one language for the file: detected (a multilingual model, none given) on the channel with the most speech, in groups of
-    # batch_size chunks so that the detection's log-mel launches stay in front of the source items too
-    lc = language_channel(speech)
-    lead = features[channels.index(lc): channels.index(lc) + channels.count(lc)] if lc in channels else features[0:0]
-    language, language_probability, all_language_probs = pipe._language(
-        lead, a["language"], a["language_detection_segments"], a["language_detection_threshold"], group_size=batch_size)
-
-    tokenizer = Tokenizer(model.hf_tokenizer, model.model.is_multilingual, task=a["task"], language=language)
-    options = _options(tokenizer, a, clip_timestamps if clip_timestamps else clips)
-    info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
-                             duration_after_vad=duration_after_vad, transcription_options=options,
-                             vad_options=vad_parameters, all_language_probs=all_language_probs)
-    return _segments(pipe, features, tokenizer, meta, channels, batch_size, options, a["log_progress"],
-                     clips if from_vad else None, sampling_rate), info
+    file. The plan is batched._plan, the one the mono route follows; what is this route's own is how the audio becomes resident."""
+    from .batched import _plan
+    features, meta, channels, vad_clips, tokenizer, options, info = _plan(
+        pipe, a, lambda slot: _make_resident(pipe.model, slot, a["audio"], int(a["batch_size"])))
+    return _segments(pipe, features, tokenizer, meta, channels, int(a["batch_size"]), options, a["log_progress"], vad_clips), info
 
 
-def _segments(pipe, features, tokenizer, meta, channels, batch_size, options, log_progress, vad_clips: Optional[list], sampling_rate):
+def _segments(pipe, features, tokenizer, meta, channels, batch_size, options, log_progress, vad_clips: Optional[list]):
     """decode the pooled chunks group by group, restore each segment's times on its own channel's timeline, then yield all of them in
     (start, channel) order (the order is known only when the last group is done)"""
-    slot = features.slot
-    features.channels = channels            # every group is cut with its chunks' channels (batched.forward reads them)
+    from .batched import _segment
+    sampling_rate = pipe.model.feature_extractor.sampling_rate
     out: List[Segment] = []
-    for i in range(0, len(features), batch_size):
-        chans = channels[i: i + batch_size]
-        with slot.lock:
-            results = pipe.forward(features[i: i + batch_size], tokenizer, meta[i: i + batch_size], options)
-        for ch, result in zip(chans, results):
+    for i, results in pipe._groups(features, tokenizer, meta, batch_size, options, log_progress):
+        for ch, result in zip(channels[i:], results):
             for segment in result:
-                seg = Segment(
-                    seek=segment["seek"], id=0, text=segment["text"], start=round(segment["start"], 3), end=round(segment["end"], 3),
-                    words=(None if not options.word_timestamps else [Word(**word) for word in segment["words"]]),
-                    tokens=segment["tokens"], avg_logprob=segment["avg_logprob"], no_speech_prob=segment["no_speech_prob"],
-                    compression_ratio=segment["compression_ratio"], temperature=options.temperatures[0], channel=ch)
+                seg = _segment(segment, options, channel=ch)
                 if vad_clips is not None:
                     seg = restore_speech_timestamps([seg], vad_clips[ch], sampling_rate)[0]
                 out.append(seg)
-        if log_progress:
-            pipe.model.logger.info("batched transcription: %d / %d chunks", min(i + batch_size, len(features)), len(features))
     yield from order_segments(out)

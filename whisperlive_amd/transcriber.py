@@ -851,16 +851,12 @@ class WhisperModelHIP:
                 enc_now = encoder_output
 
                 def align_fn(text_tokens, num_frames, _window):
-                    r = self.model.align(enc_now, tokenizer.sot_sequence, [text_tokens], num_frames)[0]
-                    pairs = np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)
-                    return pairs[:, 0], pairs[:, 1], np.asarray(r.text_token_probs, dtype=np.float64)   # fp32 values, means in double like np.mean over CT2's Python floats
+                    return _wt.unpack_alignment(self.model.align(enc_now, tokenizer.sot_sequence, [text_tokens], num_frames)[0])
 
                 def align_many_fn(requests):
                     res = self.model.align(enc_now.select([0] * len(requests)), tokenizer.sot_sequence, [r[0] for r in requests],
                                            [r[1] for r in requests])
-                    return [(np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)[:, 0],
-                             np.asarray(r.alignments, dtype=np.int64).reshape(-1, 2)[:, 1],
-                             np.asarray(r.text_token_probs, dtype=np.float64)) for r in res]
+                    return [_wt.unpack_alignment(r) for r in res]
 
                 # the reference discards add_word_timestamps' return value here (:1227-1235): the last-speech time only
                 # moves at the end of this block, so the hallucination rules below still see the PREVIOUS window's

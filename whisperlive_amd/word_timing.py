@@ -46,6 +46,14 @@ def merge_punctuations(alignment: List[dict], prepended: str, appended: str) -> 
             prev = j
 
 
+def unpack_alignment(result) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """an alignment result of the engine (`.alignments`: (text index, time index) pairs, `.text_token_probs`) -> (text_indices,
+    time_indices, text_token_probs): what an align_fn returns. The probabilities are fp32 values; their means are taken in double,
+    like np.mean over CT2's Python floats"""
+    pairs = np.asarray(result.alignments, dtype=np.int64).reshape(-1, 2)
+    return pairs[:, 0], pairs[:, 1], np.asarray(result.text_token_probs, dtype=np.float64)
+
+
 def words_from_path(tokenizer, text_tokens: Sequence[int], text_indices: np.ndarray, time_indices: np.ndarray,
                     text_token_probs: np.ndarray, tokens_per_second: int) -> List[dict]:
     """(:1665-1714) word strings / token groups from the tokenizer, word start and end from the first time index at
