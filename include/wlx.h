@@ -65,7 +65,7 @@ typedef enum {
     WLX_ERR_STATE = 4,    /* call order (e.g. generate before encode) */
     WLX_ERR_NOMEM = 5,
     WLX_ERR_TOO_SHORT = 6,/* speaker embedding: under 0.3 s of audio (the caller labels the segment with no speaker) */
-    WLX_ERR_DATA = 7      /* damaged input (wlx_flac_probe, wlx_pcm_put_flac: a FLAC stream that is not a refused SHAPE but broken) */
+    WLX_ERR_DATA = 7      /* damaged input (wlx_flac_probe, wlx_pcm_put_flac, wlx_wav_probe, wlx_pcm_put_wav: a file that is not a refused SHAPE but broken) */
 } wlx_status;
 
 /* Whisper architecture. n_audio_ctx = 1500, n_text_ctx = 448, head_dim = 64. */
@@ -243,6 +243,54 @@ int32_t wlx_pcm_put_flac(wlx_engine* e, int32_t slot, int32_t item, const void* 
  * resident PCM left as it was. A frame that does not decode gives WLX_ERR_DATA and leaves NO PCM resident in any of the items. */
 int32_t wlx_pcm_put_flac_split(wlx_engine* e, int32_t slot, int32_t first_item, const void* bytes, int64_t n_bytes,
                                wlx_flac_info* info_out, int64_t* n_out);
+/* ---- telephony WAV front end (PRODUCT entry points of the file path, beside wlx_pcm_put_flac) ----
+ * The WAVE formats call recorders write — G.711 mu-law / A-law (format tags 7 / 6), IMA / DVI ADPCM (0x11), Microsoft ADPCM (0x02),
+ * WAVE_FORMAT_EXTENSIBLE wrappers included — go to the device as they are: the data chunk crosses PCIe once, one byte (G.711) or half a
+ * byte (ADPCM) per sample, and is decoded in HBM in front of the resampler. whisperlive_amd/audio_io.py read_wav is the host decoder of
+ * the same formats: the oracle of the tests and the fallback for what this route refuses.
+ * wlx_wav_probe is HOST ONLY: the RIFF chunks up to `data` (`fmt `, `fact`), the frame count, and for the ADPCM tags every block's
+ * header. IMA: per channel a 4-byte block header (int16 predictor, uint8 step index, reserved), then 4-byte words interleaved by
+ * channel, low nibble first; samples_per_block = (block_align - 4 ch) * 2 / ch + 1. MS: predictor index (uint8), delta, sample1,
+ * sample2 (int16), each field for all channels in turn, then nibbles, high first, interleaved by channel; samples_per_block =
+ * (block_align - 7 ch) * 2 / ch + 2; coefficient pairs from the fmt extension (wNumCoef, pairs), the 7 standard pairs without one.
+ * n_frames = whole blocks * samples_per_block (a trailing partial block is dropped), cut to the `fact` chunk's count when that is
+ * present, non-zero and smaller; G.711: data bytes / channels. served = 1 when wlx_pcm_put_wav takes the file: one of the four tags,
+ * 8 bits (G.711) or 4 bits (ADPCM) per sample, 1..8 channels, at least one frame and at most 3600 s, a rate wlx_pcm_put_frames serves
+ * (RATES), and for ADPCM a block_align the formulas accept (IMA: whole words; MS: whole nibble rounds; at least the header), at most
+ * 32 coefficient pairs, and a block whose bytes and samples fit the decoder's 64 KB of LDS (5 * block_align, about 13000 bytes).
+ * Tags 1 and 3 and anything else: served = 0 with the header fields filled in (the caller keeps the route it has).
+ * WLX_ERR_DATA, a DAMAGED file: no RIFF / WAVE magic, no `fmt ` or `data` chunk, 0 channels, an IMA step index above 88, an MS
+ * predictor index >= wNumCoef.
+ * wlx_pcm_put_wav: afterwards the item's resident PCM is BIT-IDENTICAL to that of wlx_pcm_put_frames(read_wav(bytes), WLX_PCM_F32,
+ * channels, sample_rate): every decoded value is an int16 scaled by 2^-15, exact in float32, so both routes feed the same kernel the
+ * same floats, and a resampler output depends on nothing but the absolute input indices (not on block seams). *info_out (nullable) as
+ * wlx_wav_probe, written whenever the probe succeeds; *n_out = samples resident. Everything the probe can find, a file with served = 0
+ * (WLX_ERR_ARG: the caller decodes on the host) and a scratch that cannot be had (WLX_ERR_NOMEM) are answered BEFORE any launch and
+ * leave the item's resident PCM exactly as it was. Then, tags 6 / 7: no decode launch, the code bytes are the resampler's input
+ * (wlx_pcm_put_frames's staging, one byte per sample; wlx_pcm_put_frames itself keeps refusing the 8-bit codes). Tags 0x11 / 0x02:
+ * one upload of the data chunk through the slot's pinned staging blocks (two in flight), the block decode (one lane per block and
+ * channel, memory-safe on any bytes) into float32 interleaved frames in the slot's scratch, the resample launch over them, ONE wait.
+ * A failed run leaves NO PCM resident in the item. The scratch (data chunk and float32 frames) is the one wlx_pcm_put_flac uses: the
+ * slot's, grown on demand, at most 16 MB of it stay allocated after the call. wlx_pcm_put's conventions hold: recorded log-mel
+ * requests that read the item go out first, one call per slot at a time, never the null stream; the caller's bytes may be reused on
+ * return. */
+typedef struct {
+    int32_t format_tag;          /* the real tag behind a WAVE_FORMAT_EXTENSIBLE wrapper */
+    int32_t channels, sample_rate, bits_per_sample, block_align;
+    int32_t samples_per_block;   /* per channel; 1 for G.711 and PCM; 0 for a layout the formulas refuse */
+    int64_t data_offset, data_bytes;   /* the data chunk's body within `bytes` (clipped to n_bytes) */
+    int64_t n_frames;
+    int32_t served;              /* 1: wlx_pcm_put_wav takes it; 0: the caller's other routes */
+} wlx_wav_info;
+int32_t wlx_wav_probe(const void* bytes, int64_t n_bytes, wlx_wav_info* out);
+int32_t wlx_pcm_put_wav(wlx_engine* e, int32_t slot, int32_t item, const void* bytes, int64_t n_bytes, wlx_wav_info* info_out,
+                        int64_t* n_out);
+/* The CHANNEL-SPLIT form: the same probe, upload and decode, then ONE split resample launch (G.711: per staged block) and ONE wait.
+ * Item first_item + c is BIT-IDENTICAL to wlx_pcm_put_frames(read_wav(bytes)[:, c]); *n_out samples are resident in each of the file's
+ * `channels` items. WLX_ERR_DATA, WLX_ERR_ARG and WLX_ERR_NOMEM as wlx_pcm_put_wav, and first_item < 0 or first_item + channels >
+ * max_batch is WLX_ERR_ARG: all before any launch, every item's resident PCM left as it was. */
+int32_t wlx_pcm_put_wav_split(wlx_engine* e, int32_t slot, int32_t first_item, const void* bytes, int64_t n_bytes,
+                              wlx_wav_info* info_out, int64_t* n_out);
 /* ---- batched long-form front end (PRODUCT entry points of BatchedInferencePipeline: whisperlive_amd/batched.py) ----
  * Replaces faster_whisper.vad.collect_chunks + one FeatureExtractor call per chunk of the reference's BatchedInferencePipeline.transcribe
  * (whisper_live/transcriber/transcriber_faster_whisper.py:424-429): B chunks are cut out of ONE resident PCM buffer into B feature items
@@ -814,6 +862,11 @@ int32_t wlx_debug_resample_stream(int32_t device, const void* frames, int64_t n_
  * first: WLX_ERR_DATA / WLX_ERR_ARG as wlx_flac_probe before any launch; WLX_ERR_DATA after the one wait for a frame that does not decode. */
 int32_t wlx_debug_flac_decode(int32_t device, const void* bytes, int64_t n_bytes, int32_t* samples_out, int64_t cap_samples,
                               int64_t* n_frames_out, int32_t* channels_out);
+/* The ADPCM block decoder (csrc/adpcm.hip adpcm_decode_kernel, csrc/adpcm_core.h) without the resampler, on a private stream of `device`:
+ * the bytes of an IMA or MS ADPCM WAV file -> samples_out[n][channels], the decoded int16 values, one upload, one launch, one wait; any
+ * sample rate. WLX_ERR_DATA as wlx_wav_probe; WLX_ERR_ARG for another tag, a layout the decoder does not take, or cap_samples < n * channels. */
+int32_t wlx_debug_adpcm_decode(int32_t device, const void* bytes, int64_t n_bytes, int16_t* samples_out, int64_t cap_samples,
+                               int64_t* n_frames_out, int32_t* channels_out);
 /* The last completed wlx_pcm_put_flac of the slot (scripts/flac_time.py): ms_out[5] = host index + CRC time (wall), then the HIP-event
  * times of the upload (the host's copies into the pinned blocks included), flac_frames_kernel, flac_finish_kernel and the resample launch. */
 int32_t wlx_debug_flac_timings(wlx_engine* e, int32_t slot, float* ms_out);

@@ -15,11 +15,11 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
-    "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_put_frames_split", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_put_flac_split", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
+    "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_put_frames_split", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_put_flac_split", "wlx_wav_probe", "wlx_pcm_put_wav", "wlx_pcm_put_wav_split", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
     "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_align_batch", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_ring_set_format", "wlx_ring_append_frames", "wlx_resample_stream_count",
@@ -34,7 +34,7 @@ EXPORTS = [
     "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
     "wlx_debug_dec_gemv", "wlx_debug_dec_cq_cross_attn",
-    "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_resample_stream", "wlx_debug_flac_decode", "wlx_debug_flac_timings",
+    "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_resample_stream", "wlx_debug_flac_decode", "wlx_debug_flac_timings", "wlx_debug_adpcm_decode",
     "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings",
 ]
 
@@ -99,6 +99,12 @@ class wlx_flac_info(C.Structure):
                 ("n_frames", C.c_int32), ("max_blocksize", C.c_int32), ("served", C.c_int32)]
 
 
+class wlx_wav_info(C.Structure):
+    _fields_ = [("format_tag", C.c_int32), ("channels", C.c_int32), ("sample_rate", C.c_int32), ("bits_per_sample", C.c_int32),
+                ("block_align", C.c_int32), ("samples_per_block", C.c_int32), ("data_offset", C.c_int64), ("data_bytes", C.c_int64),
+                ("n_frames", C.c_int64), ("served", C.c_int32)]
+
+
 class wlx_mt_spec(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("d_model", "n_heads", "enc_layers", "dec_layers", "ffn", "vocab", "max_positions",
                                          "pad_id", "eos_id", "decoder_start_id", "scale_embedding")]
@@ -110,7 +116,7 @@ class wlx_spk_spec(C.Structure):
 
 
 ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
-ERR_DATA = 7            # wlx_status WLX_ERR_DATA: damaged input (the FLAC front end)
+ERR_DATA = 7            # wlx_status WLX_ERR_DATA: damaged input (the FLAC and telephony WAV front ends)
 SPK_MAX_BATCH = 64      # wlx.h WLX_SPK_MAX_BATCH: segments of one wlx_spk_embed_batch call
 VAD_MAX_BATCH = 64      # wlx.h WLX_VAD_MAX_BATCH: sequences of one wlx_vad_probs_batch / wlx_vad_probs_pcm_batch call
 ALIGN_MAX_BATCH = 64    # wlx.h WLX_ALIGN_MAX_BATCH: entries of one wlx_align_batch call
@@ -309,6 +315,9 @@ def load() -> C.CDLL:
     lib.wlx_flac_probe.argtypes = [vp, i64, C.POINTER(wlx_flac_info)]
     lib.wlx_pcm_put_flac.argtypes = [vp, i32, i32, vp, i64, C.POINTER(wlx_flac_info), C.POINTER(C.c_int64)]
     lib.wlx_pcm_put_flac_split.argtypes = [vp, i32, i32, vp, i64, C.POINTER(wlx_flac_info), C.POINTER(C.c_int64)]
+    lib.wlx_wav_probe.argtypes = [vp, i64, C.POINTER(wlx_wav_info)]
+    lib.wlx_pcm_put_wav.argtypes = [vp, i32, i32, vp, i64, C.POINTER(wlx_wav_info), C.POINTER(C.c_int64)]
+    lib.wlx_pcm_put_wav_split.argtypes = [vp, i32, i32, vp, i64, C.POINTER(wlx_wav_info), C.POINTER(C.c_int64)]
     lib.wlx_pcm_get.argtypes = [vp, i32, i32, f32p, i64, C.POINTER(C.c_int64)]
     lib.wlx_logmel_resident.argtypes = [vp, i32, i32, i32p]
     lib.wlx_features_get.argtypes = [vp, i32, i32, f32p, i64, i32p]
@@ -398,6 +407,7 @@ def load() -> C.CDLL:
     lib.wlx_debug_resample_stream.argtypes = [i32, vp, i64, i32, i32, i32, i64p, i32, i32, f32p, i64, i64p, i64p]
     lib.wlx_debug_flac_decode.argtypes = [i32, vp, i64, i32p, i64, C.POINTER(C.c_int64), i32p]
     lib.wlx_debug_flac_timings.argtypes = [vp, i32, f32p]
+    lib.wlx_debug_adpcm_decode.argtypes = [i32, vp, i64, C.POINTER(C.c_int16), i64, C.POINTER(C.c_int64), i32p]
     lib.wlx_debug_dtw.argtypes = [i32, f32p, i32, i32p, i32p, i32p, i32p, i32, i32p]
     lib.wlx_debug_align_post.argtypes = [i32, f32p, i32, i32, i32p, i32, i32p, i32, f32p, i32p, i32p, i32, i32p]
     lib.wlx_debug_align_timings.argtypes = [vp, i32, f32p, f32p]

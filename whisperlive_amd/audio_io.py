@@ -1,4 +1,4 @@
-"""Audio file input for the transcription path: WAV (PCM 8/16/24/32-bit, float32) and FLAC -> mono float32 at 16 kHz.
+"""Audio file input for the transcription path: WAV (PCM 8/16/24/32-bit, float32, G.711, IMA / MS ADPCM) and FLAC -> mono float32 at 16 kHz.
 
 The reference accepts a path or file object in ``WhisperModel.transcribe`` and decodes it with PyAV/FFmpeg
 (``faster_whisper.audio.decode_audio``, called at whisper_live/transcriber/transcriber_faster_whisper.py:821); neither is
@@ -33,32 +33,156 @@ def _read_all(src: PathOrFile) -> bytes:
 
 
 # ---------------------------------------------------------------------------------------------------------------- WAV
-def _wav_parse(b: bytes):
-    """-> (format tag, channels, sample rate, bits per sample, the data chunk's bytes)"""
+def _wav_chunks(b: bytes):
+    """-> (fmt chunk, data chunk, data chunk's offset, the `fact` chunk's sample count or 0): the chunks in front of and including `data`"""
     if b[:4] != b"RIFF" or b[8:12] != b"WAVE":
         raise ValueError("not a RIFF/WAVE file")
-    pos, fmt, data = 12, None, None
+    pos, fmt, data, data_at, fact = 12, None, None, 0, 0
     while pos + 8 <= len(b):
         cid, size = b[pos:pos + 4], struct.unpack_from("<I", b, pos + 4)[0]
         body = b[pos + 8: pos + 8 + size]
         if cid == b"fmt ":
             fmt = body
+        elif cid == b"fact" and len(body) >= 4:
+            fact = struct.unpack_from("<I", body, 0)[0]
         elif cid == b"data":
-            data = body
+            data, data_at = body, pos + 8
             break
         pos += 8 + size + (size & 1)
-    if fmt is None or data is None:
+    if fmt is None or data is None or len(fmt) < 16:
         raise ValueError("WAVE file without fmt / data chunk")
+    return fmt, data, data_at, fact
+
+
+def _wav_parse(b: bytes):
+    """-> (format tag, channels, sample rate, bits per sample, the data chunk's bytes)"""
+    fmt, data, _at, _fact = _wav_chunks(b)
     tag, ch, sr, _br, _ba, bits = struct.unpack_from("<HHIIHH", fmt, 0)
     if tag == 0xFFFE and len(fmt) >= 26:                      # extensible: the real format is the first GUID word
         tag = struct.unpack_from("<H", fmt, 24)[0]
     return tag, ch, sr, bits, data
 
 
+# the telephony formats (G.711, IMA / DVI ADPCM, Microsoft ADPCM): the host decoders of what csrc/adpcm.hip decodes on the device. They
+# are the oracle of its tests and the fallback for the files that route refuses, and state the arithmetic of csrc/adpcm_core.h in numpy:
+# the recurrence runs sample by sample, vectorised over the file's blocks (which are independent).
+WAVE_ALAW, WAVE_MULAW, WAVE_IMA_ADPCM, WAVE_MS_ADPCM = 0x06, 0x07, 0x11, 0x02
+_IMA_STEPS = np.array([
+    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143,
+    157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411,
+    1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442,
+    11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767], np.int64)
+_IMA_INDEX = np.array([-1, -1, -1, -1, 2, 4, 6, 8] * 2, np.int64)
+_MS_ADAPT = np.array([230, 230, 230, 230, 307, 409, 512, 614, 768, 614, 512, 409, 307, 230, 230, 230], np.int64)
+MS_ADPCM_COEFS = ((256, 0), (512, -256), (0, 0), (192, 64), (240, 0), (460, -208), (392, -232))      # the 7 standard pairs
+_MS_DELTA_MAX = 0x7FFFFFFF // 768 // 8          # csrc/adpcm_core.h ADPCM_MS_DELTA_MAX: no valid stream gets near it
+
+
+def ima_adpcm_samples_per_block(block_align: int, ch: int) -> int:
+    return (block_align - 4 * ch) * 2 // ch + 1
+
+
+def ms_adpcm_samples_per_block(block_align: int, ch: int) -> int:
+    return (block_align - 7 * ch) * 2 // ch + 2
+
+
+def _ima_adpcm_blocks(blocks: np.ndarray, ch: int) -> np.ndarray:
+    """uint8 [n_blocks, block_align] -> int16 [n_blocks, samples per block, ch]"""
+    nb, ba = blocks.shape
+    spb = ima_adpcm_samples_per_block(ba, ch)
+    out = np.empty((nb, spb, ch), np.int16)
+    head = blocks[:, :4 * ch].reshape(nb, ch, 4)
+    if nb and int(head[:, :, 2].max()) > 88:
+        k, c = np.argwhere(head[:, :, 2] > 88)[0]
+        raise ValueError(f"damaged WAV stream: IMA ADPCM block {k}, channel {c}: step index {head[k, c, 2]} is above 88")
+    words = blocks[:, 4 * ch:].reshape(nb, -1, ch, 4)                       # [block, word, channel, byte]
+    nib = np.stack([words & 15, words >> 4], axis=-1)                       # low nibble first
+    nib = nib.transpose(0, 2, 1, 3, 4).reshape(nb, ch, -1).astype(np.int64)  # [block, channel, nibble in time order]
+    pred = (head[:, :, 0].astype(np.int64) | (head[:, :, 1].astype(np.int64) << 8))
+    pred = ((pred ^ 0x8000) - 0x8000)
+    index = head[:, :, 2].astype(np.int64)
+    out[:, 0, :] = pred
+    for i in range(1, spb):
+        n = nib[:, :, i - 1]
+        step = _IMA_STEPS[index]
+        diff = (step >> 3) + np.where(n & 1, step >> 2, 0) + np.where(n & 2, step >> 1, 0) + np.where(n & 4, step, 0)
+        pred = np.clip(np.where(n & 8, pred - diff, pred + diff), -32768, 32767)
+        index = np.clip(index + _IMA_INDEX[n], 0, 88)
+        out[:, i, :] = pred
+    return out
+
+
+def _ms_adpcm_blocks(blocks: np.ndarray, ch: int, coefs) -> np.ndarray:
+    """uint8 [n_blocks, block_align] -> int16 [n_blocks, samples per block, ch]; coefs: the (c1, c2) pairs of the fmt chunk"""
+    nb, ba = blocks.shape
+    spb = ms_adpcm_samples_per_block(ba, ch)
+    out = np.empty((nb, spb, ch), np.int16)
+    coefs = np.asarray(coefs, np.int64).reshape(-1, 2)
+    pi = blocks[:, :ch].astype(np.int64)
+    if nb and int(pi.max()) >= len(coefs):
+        k, c = np.argwhere(pi >= len(coefs))[0]
+        raise ValueError(f"damaged WAV stream: MS ADPCM block {k}, channel {c}: predictor index {pi[k, c]}, the fmt chunk holds "
+                         f"{len(coefs)} coefficient pairs")
+    c1, c2 = coefs[pi, 0], coefs[pi, 1]
+    fields = np.ascontiguousarray(blocks[:, ch:7 * ch]).view("<i2").reshape(nb, 3, ch).astype(np.int64)
+    delta, s1, s2 = fields[:, 0], fields[:, 1], fields[:, 2]
+    body = blocks[:, 7 * ch:]
+    nib = np.stack([body >> 4, body & 15], axis=-1).reshape(nb, -1)[:, :(spb - 2) * ch]      # high nibble first
+    nib = nib.reshape(nb, spb - 2, ch).astype(np.int64)
+    out[:, 0, :] = s2
+    if spb > 1:
+        out[:, 1, :] = s1
+    for i in range(2, spb):
+        n = nib[:, i - 2, :]
+        delta = np.clip(delta, -_MS_DELTA_MAX, _MS_DELTA_MAX)
+        v = np.clip(((s1 * c1 + s2 * c2) >> 8) + np.where(n >= 8, n - 16, n) * delta, -32768, 32767)
+        delta = np.maximum((_MS_ADAPT[n] * delta) >> 8, 16)
+        s2, s1 = s1, v
+        out[:, i, :] = v
+    return out
+
+
+def _wav_telephony(tag: int, ch: int, bits: int, fmt: bytes, data: bytes, fact: int) -> np.ndarray:
+    """the data chunk of a G.711 / IMA ADPCM / MS ADPCM file -> float32 [frames, channels] = the 16-bit linear values / 32768"""
+    if ch < 1:
+        raise ValueError("WAVE file with 0 channels")
+    if tag in (WAVE_MULAW, WAVE_ALAW):
+        if bits != 8:
+            raise ValueError(f"unsupported G.711 width {bits}")
+        from .stream_resample import decode_alaw, decode_mulaw            # the live host route's G.711 arithmetic, as a 256-entry table
+        table = (decode_mulaw if tag == WAVE_MULAW else decode_alaw)(np.arange(256, dtype=np.uint8)).astype(np.float32) / np.float32(32768.0)
+        x = table[np.frombuffer(data, np.uint8)]
+        return x[: x.size // ch * ch].reshape(-1, ch)
+    ba = struct.unpack_from("<H", fmt, 12)[0]
+    hdr = (4 if tag == WAVE_IMA_ADPCM else 7) * ch
+    whole = ba >= hdr and ((ba - hdr) % (4 * ch) == 0 if tag == WAVE_IMA_ADPCM else ((ba - hdr) * 2) % ch == 0)
+    if bits != 4 or not whole:
+        raise ValueError(f"unsupported ADPCM layout: {bits} bits, block_align {ba}, {ch} channels")
+    nb = len(data) // ba                                       # a trailing partial block is dropped
+    blocks = np.frombuffer(data, np.uint8, nb * ba).reshape(nb, ba)
+    if tag == WAVE_IMA_ADPCM:
+        pcm = _ima_adpcm_blocks(blocks, ch)
+    else:
+        coefs = MS_ADPCM_COEFS
+        n_coef = struct.unpack_from("<H", fmt, 20)[0] if len(fmt) >= 22 else 0
+        if n_coef > 0 and len(fmt) >= 22 + 4 * n_coef:
+            coefs = np.frombuffer(fmt, "<i2", 2 * n_coef, 22).reshape(-1, 2)
+        pcm = _ms_adpcm_blocks(blocks, ch, coefs)
+    pcm = pcm.reshape(-1, ch)
+    if 0 < fact < pcm.shape[0]:
+        pcm = pcm[:fact]
+    return pcm.astype(np.float32) / np.float32(32768.0)
+
+
 def read_wav(src: PathOrFile) -> Tuple[np.ndarray, int]:
-    """RIFF/WAVE -> (float32 [frames, channels] in [-1, 1), sample rate). PCM 8/16/24/32-bit, IEEE float 32/64,
-    WAVE_FORMAT_EXTENSIBLE wrappers of those."""
-    tag, ch, sr, bits, data = _wav_parse(_read_all(src))
+    """RIFF/WAVE -> (float32 [frames, channels] in [-1, 1), sample rate). PCM 8/16/24/32-bit, IEEE float 32/64, G.711 mu-law / A-law,
+    IMA / DVI ADPCM and Microsoft ADPCM (each sample its 16-bit linear value / 32768; ADPCM: whole blocks, cut to the `fact` chunk's
+    count when that is smaller), WAVE_FORMAT_EXTENSIBLE wrappers of those."""
+    b = _read_all(src)
+    tag, ch, sr, bits, data = _wav_parse(b)
+    if tag in (WAVE_MULAW, WAVE_ALAW, WAVE_IMA_ADPCM, WAVE_MS_ADPCM):
+        fmt, data, _at, fact = _wav_chunks(b)
+        return _wav_telephony(tag, ch, bits, fmt, data, fact), sr
     if tag == 1:
         if bits == 8:
             x = (np.frombuffer(data, np.uint8).astype(np.float32) - 128.0) / 128.0
@@ -319,6 +443,38 @@ def flac_probe(data: bytes):
     info = _lib.wlx_flac_info()
     _lib.check(_lib.load().wlx_flac_probe(data, len(data), info))
     return info
+
+
+def wav_probe(data: bytes):
+    """Shape of a RIFF/WAVE file, on the host (wlx_wav_probe: the chunks, the frame count, every ADPCM block header) -> _lib.wlx_wav_info
+    (format_tag, channels, sample_rate, bits_per_sample, block_align, samples_per_block, data_offset, data_bytes, n_frames, served:
+    whether the device route engine.Slot.put_wav takes the file — G.711, IMA and MS ADPCM in a shape it serves). Raises WlxError with
+    code ERR_DATA for a damaged file."""
+    from . import _lib
+    data = bytes(data)
+    info = _lib.wlx_wav_info()
+    _lib.check(_lib.load().wlx_wav_probe(data, len(data), info))
+    return info
+
+
+def wav_served(data: bytes) -> bool:
+    """True for a RIFF/WAVE file of a telephony tag whose probe says the device route serves it (engine.Slot.put_wav); False for
+    everything else — PCM and float files among them, which keep read_audio + Slot.put_frames, and files read_wav has to refuse in
+    its own words. ValueError("damaged WAV stream: ...") for a telephony file the probe finds damaged."""
+    if data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        return False
+    try:
+        if _wav_parse(data)[0] not in (WAVE_MULAW, WAVE_ALAW, WAVE_IMA_ADPCM, WAVE_MS_ADPCM):
+            return False
+    except (ValueError, struct.error):
+        return False
+    from . import _lib
+    try:
+        return bool(wav_probe(data).served)
+    except _lib.WlxError as e:
+        if e.code == _lib.ERR_DATA:
+            raise ValueError(f"damaged WAV stream: {e}") from e
+        raise
 
 
 # ---------------------------------------------------------------------------------------------------------------- API

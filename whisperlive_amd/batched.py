@@ -483,20 +483,26 @@ def _resident_mono(model, slot, audio) -> Resident:
     device = all(hasattr(slot, m) for m in ("logmel_chunks", "pcm_put", "pcm"))
     host_audio = n_samples = None
     if not isinstance(audio, np.ndarray):
-        from .audio_io import frames_to_mono, read_audio
+        from .audio_io import frames_to_mono, read_audio, wav_served
         from .engine import resample_supported
         data = _file_bytes(audio)
-        # a FLAC file is decoded on the device (Slot.put_flac leaves resident what put_frames(read_flac(file)) would); a stream that
-        # route does not serve keeps the host decode below, a damaged one is the ValueError the host decoder raises
+        # a FLAC file is decoded on the device (Slot.put_flac leaves resident what put_frames(read_flac(file)) would), and so is a
+        # telephony WAV file the probe says the device serves (Slot.put_wav: G.711, IMA / MS ADPCM); a stream that route does not serve
+        # keeps the host decode below, a damaged one is a ValueError
         on_device = False
-        if device and data[:4] == b"fLaC" and sampling_rate == 16000 and hasattr(slot, "put_flac"):
+        compressed = None
+        if device and sampling_rate == 16000 and data[:4] == b"fLaC" and hasattr(slot, "put_flac"):
+            compressed = ("FLAC", slot.put_flac)
+        elif device and sampling_rate == 16000 and hasattr(slot, "put_wav") and wav_served(data):
+            compressed = ("WAV", slot.put_wav)
+        if compressed is not None:
             try:
                 with slot.lock:
-                    n_samples, _ = slot.put_flac(data)
+                    n_samples, _ = compressed[1](data)
                 on_device = True
             except _WlxError as e:
                 if e.code == _ERR_DATA:
-                    raise ValueError(f"damaged FLAC stream: {e}") from e
+                    raise ValueError(f"damaged {compressed[0]} stream: {e}") from e
                 if e.code != _ERR_ARG:
                     raise
         if not on_device:

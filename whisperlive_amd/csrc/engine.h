@@ -65,6 +65,7 @@ struct Slot {
     bool rs_ready = false;
     // wlx_pcm_put_flac (flac.hip): ONE device scratch for file bytes | frame table | status words | int32 planes | float32 frames, grown
     // on demand and owned by name; a call keeps at most 2 * RS_BLOCK_BYTES of it afterwards. ev: upload / frames / finish / resample marks
+    // wlx_pcm_put_wav (adpcm.hip) lays its data chunk | float32 frames into the same buf / cap, under the same rule.
     struct FlacScratch { unsigned char* buf = nullptr; size_t cap = 0; hipEvent_t ev[5] = {}; float index_ms = 0.f; bool timed = false; } flac;
     long long* d_rng = nullptr;                      // [2 * WLX_LM_MAXRANGES] range table of the last wlx_logmel_ring
     // wlx_logmel_chunks: [B] chunk descriptors and [B][WLX_LM_MAXRANGES][2] range pairs, pinned staging and device copy (allocated at

@@ -258,8 +258,8 @@ static size_t flac_layout(const FlacStream& s, long long nbytes, unsigned char* 
 }
 
 // host -> device on `st`: through the two pinned staging blocks when there are any (two copies in flight, as resample_run), else straight
-// from the caller's pageable memory
-static int flac_upload(ResampleStage* sg, int* blk, void* dst, const void* src, size_t n, hipStream_t st) {
+// from the caller's pageable memory (kernels.h: adpcm.hip uploads a WAV file's data chunk the same way)
+int staged_upload(ResampleStage* sg, int* blk, void* dst, const void* src, size_t n, hipStream_t st) {
     if (!sg) {
         if (n) CK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st));
         return WLX_OK;
@@ -283,8 +283,8 @@ static int flac_launch(const FlacStream& s, const void* bytes, long long nbytes,
     const long long total = s.info.total_samples;
     int blk = 0;
     if (ev) CK(hipEventRecord(ev[0], st));
-    CKR(flac_upload(sg, &blk, d.bytes, bytes, (size_t)nbytes, st));
-    CKR(flac_upload(sg, &blk, d.tab, s.frames.data(), (size_t)nf * sizeof(FlacFrame), st));
+    CKR(staged_upload(sg, &blk, d.bytes, bytes, (size_t)nbytes, st));
+    CKR(staged_upload(sg, &blk, d.tab, s.frames.data(), (size_t)nf * sizeof(FlacFrame), st));
     if (ev) CK(hipEventRecord(ev[1], st));
     hipLaunchKernelGGL(flac_frames_kernel, dim3((unsigned)((nf + FLAC_FRAMES_THREADS - 1) / FLAC_FRAMES_THREADS)), dim3(FLAC_FRAMES_THREADS), 0, st,
                        d.bytes, d.tab, nf, s.info.bits_per_sample, ch, d.planes, total, d.status);

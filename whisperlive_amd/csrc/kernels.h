@@ -119,6 +119,10 @@ int resample_run_device(const ResamplePlan& pl, const float* d_frames, long long
 int resample_run_device_split(const ResamplePlan& pl, const float* d_frames, long long n_frames, int channels, float* d_out,
                               long long out_stride, hipStream_t st);
 
+// flac.hip: host -> device on `st` through the two pinned staging blocks of `sg` (two copies in flight; *blk counts blocks across calls),
+// or straight from the caller's memory when sg is null. Does not wait: the caller synchronises and then clears sg->used.
+int staged_upload(ResampleStage* sg, int* blk, void* dst, const void* src, size_t n, hipStream_t st);
+
 // The STREAM form (the live path: wlx_ring_append_frames; test hook wlx_debug_resample_stream): the same kernel fed packet by packet.
 // With J input frames seen and M outputs emitted, a packet of n frames completes the outputs [M, M') whose newest input exists
 // (flush: all of the one-shot's ceil(J' up / down), frames past the end being zero). The state is J, M and the last `tail_len` <=

@@ -233,7 +233,7 @@ int resample_plan(int device, int sample_rate, ResamplePlan* out) {
 long long resample_out_len(const ResamplePlan& pl, long long n_frames) { return (n_frames * pl.up + pl.down - 1) / pl.down; }
 
 long long resample_default_block(int channels, int sample_format) {
-    return (long long)(RS_BLOCK_BYTES / ((size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4)));
+    return (long long)(RS_BLOCK_BYTES / ((size_t)channels * (size_t)resample_format_bytes(sample_format)));
 }
 
 // one launch: the down-mix form (split_stride == 0: grid.y = 1) or the split form (grid.y = channels, p.out_stride = split_stride)
@@ -241,7 +241,7 @@ static void rs_launch(int sample_format, unsigned grid, size_t lds, hipStream_t 
     if (split_stride > 0) {
         p.out_stride = split_stride;
         const dim3 g(grid, (unsigned)p.channels);
-        switch (sample_format) {                        // the 8-bit formats reach here from a ring group only (resample_stream_check)
+        switch (sample_format) {                        // the 8-bit formats reach here from a ring group and from a G.711 WAV file (adpcm.hip)
         case WLX_PCM_S16: hipLaunchKernelGGL((resample_kernel<WLX_PCM_S16, true>), g, dim3(RS_THREADS), lds, st, p); break;
         case WLX_PCM_U8: hipLaunchKernelGGL((resample_kernel<WLX_PCM_U8, true>), g, dim3(RS_THREADS), lds, st, p); break;
         case WLX_PCM_MULAW: hipLaunchKernelGGL((resample_kernel<WLX_PCM_MULAW, true>), g, dim3(RS_THREADS), lds, st, p); break;
@@ -250,7 +250,7 @@ static void rs_launch(int sample_format, unsigned grid, size_t lds, hipStream_t 
         }
         return;
     }
-    switch (sample_format) {                            // the 8-bit formats reach here from the stream form only (resample_stream_check)
+    switch (sample_format) {                            // the 8-bit formats reach here from the stream form and from a G.711 WAV file (adpcm.hip)
     case WLX_PCM_S16: hipLaunchKernelGGL(resample_kernel<WLX_PCM_S16>, dim3(grid), dim3(RS_THREADS), lds, st, p); break;
     case WLX_PCM_U8: hipLaunchKernelGGL(resample_kernel<WLX_PCM_U8>, dim3(grid), dim3(RS_THREADS), lds, st, p); break;
     case WLX_PCM_MULAW: hipLaunchKernelGGL(resample_kernel<WLX_PCM_MULAW>, dim3(grid), dim3(RS_THREADS), lds, st, p); break;
@@ -261,7 +261,7 @@ static void rs_launch(int sample_format, unsigned grid, size_t lds, hipStream_t 
 
 int resample_run(const ResamplePlan& pl, const void* frames, long long n_frames, int channels, int sample_format, long long block_frames,
                  ResampleStage& sg, float* d_out, hipStream_t st, float* kernel_ms, long long split_stride) {
-    const size_t fb = (size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4);
+    const size_t fb = (size_t)channels * (size_t)resample_format_bytes(sample_format);
     const long long n_out = resample_out_len(pl, n_frames);
     const long long per = block_frames >= resample_reach(pl) ? resample_block_outputs(pl, block_frames) : 0;
     if (per < 1) return set_error(WLX_ERR_ARG, "block of %lld frames is smaller than the filter's reach (%lld)", block_frames, resample_reach(pl));
@@ -488,7 +488,7 @@ static int debug_resample(int32_t device, const void* frames, int64_t n_frames, 
     const long long nout = resample_out_len(pl, n_frames);
     *n_out = nout;
     if (nout == 0) return WLX_OK;
-    const size_t fb = (size_t)channels * (sample_format == WLX_PCM_S16 ? 2 : 4);
+    const size_t fb = (size_t)channels * (size_t)resample_format_bytes(sample_format);
     const long long bf = std::min<long long>(block_frames, n_frames);
     ResampleStage sg{};
     unsigned char *r0 = nullptr, *r1 = nullptr;

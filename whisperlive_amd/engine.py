@@ -364,6 +364,26 @@ class Slot:
         n = self.put_frames(frames, frames.sample_rate, item)
         return n, frames.info
 
+    def put_wav(self, data: bytes, item: int = 0):
+        """The bytes of a G.711 (mu-law / A-law), IMA ADPCM or MS ADPCM WAV file -> 16 kHz mono float32 resident in the item's PCM
+        buffer: probed on the host, decoded, down-mixed and resampled on the device (wlx_pcm_put_wav); bit-identical to
+        put_frames(audio_io.read_wav(data)). -> (samples resident, info) with info = the file's shape (a _lib.wlx_wav_info). Raises
+        WlxError: code ERR_ARG for a file the device route does not serve (any other tag among them; nothing launched, the item
+        untouched: decode on the host), ERR_DATA for a damaged one."""
+        data = bytes(data)
+        n, info = C.c_int64(0), _lib.wlx_wav_info()
+        check(self.lib.wlx_pcm_put_wav(self.engine._h, self.sid, item, data, len(data), C.byref(info), C.byref(n)))
+        return n.value, info
+
+    def put_wav_split(self, data: bytes, first_item: int = 0):
+        """put_wav without the down-mix: channel c resident in item first_item + c after one upload and one split launch
+        (wlx_pcm_put_wav_split); each item bit-identical to put_frames(audio_io.read_wav(data)[0][:, c]). -> (samples resident per
+        item, info). WlxError codes as put_wav."""
+        data = bytes(data)
+        n, info = C.c_int64(0), _lib.wlx_wav_info()
+        check(self.lib.wlx_pcm_put_wav_split(self.engine._h, self.sid, first_item, data, len(data), C.byref(info), C.byref(n)))
+        return n.value, info
+
     def pcm(self, item: int = 0) -> np.ndarray:
         """Host copy of the item's resident PCM (16 kHz mono float32)."""
         n = C.c_int64(0)

@@ -84,12 +84,13 @@ def _make_resident(model, slot, audio, batch_size: int):
     if sampling_rate != 16000 or not all(hasattr(slot, m) for m in ("put_frames_split", "logmel_chunks", "pcm")):
         raise ValueError(f"multichannel=True needs the device front end (Slot.put_frames_split), which this engine lacks. {_NO_HOST}")
     max_batch = int(getattr(slot, "max_batch", getattr(model, "max_batch", batch_size)))
+    wav = None              # the bytes of a telephony WAV file the device decodes itself
     if isinstance(audio, np.ndarray):
         frames = parse_waveform(audio)
         frames = frames if frames.dtype == np.int16 else np.ascontiguousarray(frames, dtype=np.float32)
         rate, flac = 16000, None
     else:
-        from .audio_io import read_audio
+        from .audio_io import read_audio, wav_probe, wav_served
         data = _file_bytes(audio)
         if data[:4] == b"fLaC":
             import ctypes as C
@@ -104,10 +105,15 @@ def _make_resident(model, slot, audio, batch_size: int):
                                  f"front end does not serve it. {_NO_HOST}")
             flac, frames, rate = FlacFrames(data), None, info.sample_rate
             channels = info.channels
+        elif hasattr(slot, "put_wav_split") and wav_served(data):
+            # a telephony WAV file the device decodes (G.711, IMA / MS ADPCM): its bytes go up as they are (Slot.put_wav_split); one the
+            # probe does not serve is decoded by read_audio below and takes the frames' route
+            info = wav_probe(data)
+            flac, wav, frames, rate, channels = None, data, None, info.sample_rate, info.channels
         else:
             frames, rate = read_audio(data)
             flac = None
-    if flac is None:
+    if flac is None and wav is None:
         channels = frames.shape[1]
         if frames.shape[0] == 0:
             raise ValueError("multichannel: empty audio")
@@ -119,10 +125,13 @@ def _make_resident(model, slot, audio, batch_size: int):
     first = max_batch - channels
     try:
         with slot.lock:
-            n = slot.put_frames_split(flac if flac is not None else frames, rate, first)
+            if wav is not None:
+                n, _ = slot.put_wav_split(wav, first)
+            else:
+                n = slot.put_frames_split(flac if flac is not None else frames, rate, first)
     except _WlxError as e:
         if e.code == _ERR_DATA:
-            raise ValueError(f"damaged FLAC stream: {e}") from e
+            raise ValueError(f"damaged {'WAV' if wav is not None else 'FLAC'} stream: {e}") from e
         if e.code == _ERR_ARG:
             raise ValueError(f"the device front end refused the audio ({e}). {_NO_HOST}") from e
         raise

@@ -608,24 +608,30 @@ class WhisperModelHIP:
             # them into its PCM buffer (Slot.put_frames), the log-mel kernel reads them there, and the host takes the 16 kHz mono copy
             # back for the duration, the VAD filter and speaker labels. A rate or channel count the device resampler does not serve
             # keeps the host route (audio_io.load_audio's arithmetic).
-            from .audio_io import _read_all, frames_to_mono, read_audio
+            from .audio_io import _read_all, frames_to_mono, read_audio, wav_served
             from .engine import resample_supported
             data = _read_all(audio)
             temps_f = temperature if isinstance(temperature, (list, tuple)) else [temperature]
             file_slot = self._slot(rows=max(int(beam_size), int(best_of) if any(t > 0 for t in temps_f) else 1))
             # A FLAC file goes to the device as it is: the slot indexes its frames on the host and decodes them in HBM (Slot.put_flac),
-            # which leaves resident exactly what put_frames(read_flac(file)) would. A stream the device route does not serve
-            # (WLX_ERR_ARG: nothing was launched) is decoded by audio_io.read_flac below; a damaged one is the ValueError read_flac raises.
+            # which leaves resident exactly what put_frames(read_flac(file)) would. So does a telephony WAV file (G.711, IMA / MS ADPCM)
+            # whose probe says the device route serves it (Slot.put_wav). A stream the device route does not serve
+            # (WLX_ERR_ARG: nothing was launched) is decoded by audio_io.read_audio below; a damaged one is a ValueError.
             on_device = False
-            if data[:4] == b"fLaC" and sr == 16000 and hasattr(file_slot, "put_flac"):
+            compressed = None
+            if sr == 16000 and data[:4] == b"fLaC" and hasattr(file_slot, "put_flac"):
+                compressed = ("FLAC", file_slot.put_flac)
+            elif sr == 16000 and hasattr(file_slot, "put_wav") and wav_served(data):
+                compressed = ("WAV", file_slot.put_wav)
+            if compressed is not None:
                 try:
                     with file_slot.lock:
-                        file_slot.put_flac(data)
+                        compressed[1](data)
                         audio = file_slot.pcm()
                     on_device = True
                 except _WlxError as e:
                     if e.code == _ERR_DATA:
-                        raise ValueError(f"damaged FLAC stream: {e}") from e
+                        raise ValueError(f"damaged {compressed[0]} stream: {e}") from e
                     if e.code != _ERR_ARG:
                         raise
                     self.logger.debug("device front end refused the file: %s", e)
