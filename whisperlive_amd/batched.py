@@ -127,18 +127,9 @@ class BatchedInferencePipeline:
         segmented_outputs = []
         segment_sizes = []
         for chunk_metadata, output in zip(chunks_metadata, outputs):
-            duration = chunk_metadata["end_time"] - chunk_metadata["start_time"]
-            segment_size = int(ceil(duration) * self.model.frames_per_second)
+            subsegments, segment_size = self._subsegments(tokenizer, chunk_metadata, output)
             segment_sizes.append(segment_size)
-            subsegments, seek, single_timestamp_ending = self.model._split_segments_by_timestamps(
-                tokenizer=tokenizer, tokens=output["tokens"], time_offset=chunk_metadata["start_time"],
-                segment_size=segment_size, segment_duration=duration, seek=0)
-            segmented_outputs.append([
-                dict(text=tokenizer.decode(subsegment["tokens"]), avg_logprob=output["avg_logprob"],
-                     no_speech_prob=output["no_speech_prob"], tokens=subsegment["tokens"], start=subsegment["start"],
-                     end=subsegment["end"], compression_ratio=get_compression_ratio(tokenizer.decode(subsegment["tokens"])),
-                     seek=int(chunk_metadata["start_time"] * self.model.frames_per_second))
-                for subsegment in subsegments])
+            segmented_outputs.append(subsegments)
         if options.word_timestamps:
             # chunk after chunk (the route add_word_timestamps takes where it is not given a group form), with the last-speech time carried along
             def aligners(base):
@@ -175,6 +166,20 @@ class BatchedInferencePipeline:
             if channels is None:
                 self.last_speech_timestamp = last[None]
         return segmented_outputs
+
+    def _subsegments(self, tokenizer, chunk_metadata, output):
+        """one chunk's decode -> (its sub-segment dicts on the concatenated timeline, the chunk's size in frames)"""
+        duration = chunk_metadata["end_time"] - chunk_metadata["start_time"]
+        segment_size = int(ceil(duration) * self.model.frames_per_second)
+        subsegments, seek, single_timestamp_ending = self.model._split_segments_by_timestamps(
+            tokenizer=tokenizer, tokens=output["tokens"], time_offset=chunk_metadata["start_time"],
+            segment_size=segment_size, segment_duration=duration, seek=0)
+        return [
+            dict(text=tokenizer.decode(subsegment["tokens"]), avg_logprob=output["avg_logprob"],
+                 no_speech_prob=output["no_speech_prob"], tokens=subsegment["tokens"], start=subsegment["start"],
+                 end=subsegment["end"], compression_ratio=get_compression_ratio(tokenizer.decode(subsegment["tokens"])),
+                 seek=int(chunk_metadata["start_time"] * self.model.frames_per_second))
+            for subsegment in subsegments], segment_size
 
     # ---- (:176-254)
     def generate_segment_batched(self, features, tokenizer, options):
@@ -300,6 +305,17 @@ class BatchedInferencePipeline:
         return transcribe_multichannel(self, dict(bound.arguments))
 
     transcribe.__wrapped__ = _transcribe
+
+    def iter_many(self, audios, *, batch_size: int = 8, on_error: str = "return", **kwargs):
+        """Many files as ONE job whose decode groups mix files (whisperlive_amd/many_files.py): yields (index, segments, info) per
+        file — what `transcribe(audios[index], ...)` returns, the segments as a list — or (index, exception, None) for a damaged file."""
+        from .many_files import iter_many
+        return iter_many(self, audios, batch_size=batch_size, on_error=on_error, **kwargs)
+
+    def transcribe_many(self, audios, *, batch_size: int = 8, on_error: str = "return", **kwargs):
+        """`iter_many` to the end -> [(segments, info) or (exception, None)] in input order"""
+        from .many_files import transcribe_many
+        return transcribe_many(self, audios, batch_size=batch_size, on_error=on_error, **kwargs)
 
     def _language(self, features, language, language_detection_segments, language_detection_threshold, group_size=None):
         """-> (language, probability, all probabilities or None): the language given (an English-only model knows one), or the one
@@ -480,6 +496,26 @@ def _resident_mono(model, slot, audio) -> Resident:
     """The mono route's audio: a file is down-mixed and resampled into item 0 on the device (a FLAC file decoded there too), a
     waveform uploaded; an engine without the front end, or a shape the front end refuses, keeps the audio on the host."""
     sampling_rate = model.feature_extractor.sampling_rate
+    n_samples, host_audio, device = _put_audio(model, slot, audio, 0)
+
+    def gate(vad_parameters, vad_model):
+        if (device and n_samples > 0 and hasattr(vad_model, "probs_pcm")
+                and getattr(vad_model, "device", None) == getattr(slot.engine, "device", -1)):
+            with slot.lock:
+                return [_vad.get_speech_timestamps_pcm(slot, n_samples, vad_parameters, sampling_rate, model=vad_model)]
+        return [_vad.get_speech_timestamps(_resolve(host_audio, slot), vad_parameters, sampling_rate, model=vad_model)]
+
+    return Resident(n_samples, [0], host_audio, gate, device)
+
+
+def _put_audio(model, slot, audio, item: int = 0):
+    """One file or waveform into item `item` of `slot`, by the route its kind takes -> (samples at 16 kHz, host audio, device).
+    A FLAC file and a telephony WAV file are decoded on the device (Slot.put_flac / put_wav), any other file is decoded on the host
+    and down-mixed and resampled on the device (put_frames), a waveform is uploaded (pcm_put); a shape the front end refuses is
+    down-mixed and resampled on the host and uploaded as a waveform. host audio: the waveform where one exists on the host, else
+    `slot.pcm` (item -> the host copy, fetched only when something asks). device False: an engine without the front end, nothing
+    was put. A damaged file is a ValueError. (The mono route puts its one file into item 0, a job of many files each into its own.)"""
+    sampling_rate = model.feature_extractor.sampling_rate
     device = all(hasattr(slot, m) for m in ("logmel_chunks", "pcm_put", "pcm"))
     host_audio = n_samples = None
     if not isinstance(audio, np.ndarray):
@@ -498,7 +534,7 @@ def _resident_mono(model, slot, audio) -> Resident:
         if compressed is not None:
             try:
                 with slot.lock:
-                    n_samples, _ = compressed[1](data)
+                    n_samples, _ = compressed[1](data, item=item)
                 on_device = True
             except _WlxError as e:
                 if e.code == _ERR_DATA:
@@ -512,7 +548,7 @@ def _resident_mono(model, slot, audio) -> Resident:
             if on_device:
                 try:
                     with slot.lock:
-                        n_samples = slot.put_frames(file_frames, file_sr)
+                        n_samples = slot.put_frames(file_frames, file_sr, item=item)
                 except _WlxError as e:
                     if e.code != _ERR_ARG:             # only a REFUSED shape (nothing was launched) keeps the host route
                         raise
@@ -526,16 +562,8 @@ def _resident_mono(model, slot, audio) -> Resident:
         host_audio, n_samples = audio, audio.shape[0]
         if device and n_samples > 0:
             with slot.lock:
-                slot.pcm_put(audio)
-
-    def gate(vad_parameters, vad_model):
-        if (device and n_samples > 0 and hasattr(vad_model, "probs_pcm")
-                and getattr(vad_model, "device", None) == getattr(slot.engine, "device", -1)):
-            with slot.lock:
-                return [_vad.get_speech_timestamps_pcm(slot, n_samples, vad_parameters, sampling_rate, model=vad_model)]
-        return [_vad.get_speech_timestamps(_resolve(host_audio, slot), vad_parameters, sampling_rate, model=vad_model)]
-
-    return Resident(n_samples, [0], host_audio, gate, device)
+                slot.pcm_put(audio, item=item)
+    return n_samples, host_audio, device
 
 
 def _file_bytes(audio) -> bytes:

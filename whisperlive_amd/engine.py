@@ -250,6 +250,25 @@ class PcmRingGroup:
             self._h = None
 
 
+MAX_ITEM_SAMPLES = 3600 * 16000          # what one slot item holds (include/wlx.h: "audio chunk too long" past it)
+
+
+def _at_16k(n_frames: int, sample_rate: int) -> int:
+    """frames at sample_rate -> samples at 16 kHz, rounded up (0 where the rate is not known)"""
+    return -(-int(n_frames) * 16000 // int(sample_rate)) if sample_rate and sample_rate > 0 else 0
+
+
+def _wav_at_16k(data: bytes) -> int:
+    """an upper estimate of the 16 kHz samples per channel in a telephony WAV file, from its header (0: not readable there)"""
+    try:
+        from .audio_io import WAVE_IMA_ADPCM, WAVE_MS_ADPCM, _wav_parse
+        tag, ch, rate, bits, body = _wav_parse(data)
+        frames = len(body) * 2 // ch if tag in (WAVE_IMA_ADPCM, WAVE_MS_ADPCM) else len(body) // (ch * max(1, bits // 8))
+        return _at_16k(frames, rate)
+    except Exception:  # noqa: BLE001 — the library says what is wrong with the file
+        return 0
+
+
 class ResidentPcm:
     """16 kHz mono audio resident in item `item` of `slot` (after pcm_put / put_frames): `n_samples` of it — what a reader on the device
     (SpeakerEmbedderHIP.embed_resident) needs to find it. The handle does not own the slot: the thread that made it keeps the slot
@@ -279,6 +298,7 @@ class FlacFrames:
         d = self.data
         ok = len(d) >= 42 and d[:4] == b"fLaC" and (d[4] & 0x7F) == 0
         self.sample_rate = int.from_bytes(d[18:21], "big") >> 4 if ok else 0
+        self.total_samples = int.from_bytes(d[21:26], "big") & ((1 << 36) - 1) if ok else 0      # (0: the encoder did not say)
         self.info = None
 
 
@@ -289,6 +309,14 @@ class Slot:
         self.engine, self.sid, self.max_batch, self.rows = engine, sid, max_batch, rows
         self.lib, self._h = engine.lib, engine._h
         self.lock = threading.Lock()
+        # the longest audio, in samples per item, any call has asked this slot to hold: a floor of the row stride of its PCM buffers,
+        # which the library grows to the longest request (whole 30 s windows) and never shrinks. What sizes its source rows against the
+        # 2^31 - 1 samples wlx_logmel_chunks_multi addresses (many_files.next_wave) reads it; the library has no entry point that tells.
+        self.pcm_longest = 480000
+
+    def _grew(self, n_samples) -> None:
+        if 0 < int(n_samples) <= MAX_ITEM_SAMPLES:           # (a longer request is refused before anything grows)
+            self.pcm_longest = max(self.pcm_longest, int(n_samples))
 
     def close(self):
         if self.sid >= 0 and self.engine._h:
@@ -299,11 +327,13 @@ class Slot:
     def logmel(self, pcm: np.ndarray, item: int = 0) -> int:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         nf = C.c_int32(0)
+        self._grew(pcm.shape[0])
         check(self.lib.wlx_logmel(self.engine._h, self.sid, item, _f32p(pcm), pcm.shape[0], C.byref(nf)))
         return nf.value
 
     def pcm_put(self, pcm: np.ndarray, item: int = 0):
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        self._grew(pcm.shape[0])
         check(self.lib.wlx_pcm_put(self.engine._h, self.sid, item, _f32p(pcm), pcm.shape[0]))
 
     def put_frames(self, frames: np.ndarray, sample_rate: int, item: int = 0) -> int:
@@ -313,8 +343,10 @@ class Slot:
         Raises WlxError for a rate the device resampler does not serve (see `resample_supported`)."""
         if isinstance(frames, FlacFrames):         # still compressed: the library decodes them on the device (STREAMINFO's rate holds)
             n, info = C.c_int64(0), _lib.wlx_flac_info()
+            self._grew(_at_16k(frames.total_samples, frames.sample_rate))      # (the buffers grow before the frames are decoded)
             check(self.lib.wlx_pcm_put_flac(self.engine._h, self.sid, item, frames.data, len(frames.data), C.byref(info), C.byref(n)))
             frames.info = info
+            self._grew(n.value)
             return n.value
         x = np.asarray(frames)
         if x.ndim == 1:
@@ -322,8 +354,10 @@ class Slot:
         fmt = _lib.PCM_S16 if x.dtype == np.int16 else _lib.PCM_F32
         x = np.ascontiguousarray(x, dtype=np.int16 if fmt == _lib.PCM_S16 else np.float32)
         n = C.c_int64(0)
+        self._grew(_at_16k(x.shape[0], sample_rate))
         check(self.lib.wlx_pcm_put_frames(self.engine._h, self.sid, item, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], fmt,
                                           int(sample_rate), C.byref(n)))
+        self._grew(n.value)
         return n.value
 
     def put_frames_split(self, frames: np.ndarray, sample_rate: int, first_item: int = 0) -> int:
@@ -333,8 +367,10 @@ class Slot:
         first_item + channels > max_batch: nothing is launched, every item is left as it was."""
         if isinstance(frames, FlacFrames):
             n, info = C.c_int64(0), _lib.wlx_flac_info()
+            self._grew(_at_16k(frames.total_samples, frames.sample_rate))
             check(self.lib.wlx_pcm_put_flac_split(self.engine._h, self.sid, first_item, frames.data, len(frames.data), C.byref(info), C.byref(n)))
             frames.info = info
+            self._grew(n.value)
             return n.value
         x = np.asarray(frames)
         if x.ndim == 1:
@@ -342,8 +378,10 @@ class Slot:
         fmt = _lib.PCM_S16 if x.dtype == np.int16 else _lib.PCM_F32
         x = np.ascontiguousarray(x, dtype=np.int16 if fmt == _lib.PCM_S16 else np.float32)
         n = C.c_int64(0)
+        self._grew(_at_16k(x.shape[0], sample_rate))
         check(self.lib.wlx_pcm_put_frames_split(self.engine._h, self.sid, first_item, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1],
                                                 fmt, int(sample_rate), C.byref(n)))
+        self._grew(n.value)
         return n.value
 
     def put_flac_split(self, data: bytes, first_item: int = 0):
@@ -372,7 +410,9 @@ class Slot:
         untouched: decode on the host), ERR_DATA for a damaged one."""
         data = bytes(data)
         n, info = C.c_int64(0), _lib.wlx_wav_info()
+        self._grew(_wav_at_16k(data))
         check(self.lib.wlx_pcm_put_wav(self.engine._h, self.sid, item, data, len(data), C.byref(info), C.byref(n)))
+        self._grew(n.value)
         return n.value, info
 
     def put_wav_split(self, data: bytes, first_item: int = 0):
@@ -381,7 +421,9 @@ class Slot:
         item, info). WlxError codes as put_wav."""
         data = bytes(data)
         n, info = C.c_int64(0), _lib.wlx_wav_info()
+        self._grew(_wav_at_16k(data))
         check(self.lib.wlx_pcm_put_wav_split(self.engine._h, self.sid, first_item, data, len(data), C.byref(info), C.byref(n)))
+        self._grew(n.value)
         return n.value, info
 
     def pcm(self, item: int = 0) -> np.ndarray:
@@ -403,6 +445,7 @@ class Slot:
         """log-mel of the concatenation of ring ranges [(start, end), ...] (absolute positions) -> frames; see wlx_logmel_ring"""
         rg = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
         nf = C.c_int32(0)
+        self._grew(int((rg[:, 1] - rg[:, 0]).sum()) if rg.size else 0)
         check(self.lib.wlx_logmel_ring(self.engine._h, self.sid, item, ring._h, rg.ctypes.data_as(C.POINTER(C.c_int64)), rg.shape[0], C.byref(nf)))
         return nf.value
 
@@ -440,6 +483,7 @@ class Slot:
 
     def set_features(self, feats: np.ndarray, item: int = 0):
         feats = np.ascontiguousarray(feats, dtype=np.float32)
+        self._grew(feats.shape[-1] * 160)
         check(self.lib.wlx_features_set(self.engine._h, self.sid, item, _f32p(feats), feats.shape[0], feats.shape[1]))
 
     # ---- encoder

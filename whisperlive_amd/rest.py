@@ -244,6 +244,104 @@ def _reads_resident(diarizer, resident) -> bool:
     return bool(supports(resident)) if supports is not None else True
 
 
+class _Upload:
+    """one request waiting in the batcher"""
+    __slots__ = ("transcriber", "key", "data", "per_file", "shared", "done", "result", "error")
+
+    def __init__(self, transcriber, key, data, per_file, shared):
+        self.transcriber, self.key, self.data, self.per_file, self.shared = transcriber, key, data, per_file, shared
+        self.done, self.result, self.error = threading.Event(), None, None
+
+
+class FileBatcher:
+    """Pools concurrent uploads into BatchedInferencePipeline.iter_many jobs (RestServer keeps one per GPU). One worker thread: it takes the oldest waiting upload,
+    collects for `window_s` seconds the uploads that arrive for the same transcriber with equal group-wide decode options (`shared`:
+    task, beam size, temperature, word_timestamps, ... — compared as a whole; language, prompt and hotwords are per file and may
+    differ), `batch_size` of them at the most (one wave of a transcriber built with max_batch = 2 x batch_size), and runs them as
+    one job; uploads with other options wait for the next job. Each request is answered from its own result as soon as the job yields
+    it. `make_pipeline(transcriber)` -> the pipeline (anything with `iter_many`). `jobs` counts the jobs run."""
+
+    def __init__(self, make_pipeline: Callable, batch_size: int, window_s: float):
+        self.make_pipeline, self.batch_size, self.window_s = make_pipeline, int(batch_size), float(window_s)
+        self.jobs = 0
+        self._waiting: List[_Upload] = []
+        self._cv = threading.Condition()
+        self._closed = False
+        self._thread = threading.Thread(target=self._run, name="wlx-rest-batcher", daemon=True)
+        self._thread.start()
+
+    def submit(self, transcriber, data: bytes, per_file: dict, shared: dict):
+        up = _Upload(transcriber, (id(transcriber), repr(sorted(shared.items()))), data, per_file, shared)
+        with self._cv:
+            if self._closed:
+                raise RuntimeError("the server is shutting down")
+            self._waiting.append(up)
+            self._cv.notify_all()
+        up.done.wait()
+        if up.error is not None:
+            raise up.error
+        return up.result
+
+    def close(self):
+        with self._cv:
+            self._closed = True
+            self._cv.notify_all()
+        self._thread.join()
+
+    def _collect(self) -> Optional[List[_Upload]]:
+        """the next job's uploads: the oldest one and those of its key that arrive within the window (None: closed and drained)"""
+        with self._cv:
+            while not self._waiting:
+                if self._closed:
+                    return None
+                self._cv.wait()
+            key, deadline = self._waiting[0].key, time.monotonic() + self.window_s
+            while True:
+                same = [u for u in self._waiting if u.key == key]
+                left = deadline - time.monotonic()
+                if len(same) >= self.batch_size or left <= 0 or self._closed:
+                    break
+                self._cv.wait(left)
+            job = same[: self.batch_size]
+            self._waiting = [u for u in self._waiting if u not in job]
+            return job
+
+    def _run(self):
+        while True:
+            job = self._collect()
+            if job is None:
+                return
+            self.jobs += 1
+            transcriber = job[0].transcriber
+            try:
+                results = self.make_pipeline(transcriber).iter_many(
+                    [u.data for u in job], batch_size=self.batch_size, vad_filter=True,
+                    **{name: [u.per_file[name] for u in job] for name in ("language", "initial_prompt", "hotwords")}, **job[0].shared)
+                for index, segments, info in results:
+                    up = job[index]
+                    if info is None:
+                        up.error = segments
+                    else:
+                        up.result = (segments, info)
+                    up.done.set()
+            except Exception as e:  # noqa: BLE001 — an error of the job as a whole is every waiting request's error
+                for up in job:
+                    if not up.done.is_set():
+                        up.error = e
+            finally:
+                for up in job:
+                    if not up.done.is_set():
+                        if up.error is None and up.result is None:
+                            up.error = RuntimeError("the pooled job ended without this file's result")
+                        up.done.set()
+                release = getattr(transcriber, "release_slot", None)
+                if release is not None:
+                    try:
+                        release()
+                    except Exception:  # noqa: BLE001
+                        logging.exception("rest: release_slot failed")
+
+
 class _HttpError(Exception):
     def __init__(self, status: int, payload: dict):
         super().__init__(payload.get("error", ""))
@@ -261,16 +359,29 @@ class RestServer:
     construction, as in TranscriptionServer. ``start()`` returns once the socket listens (``port`` 0: see ``.port``);
     ``shutdown()`` waits for the requests in flight and leaves no thread behind."""
 
+    pipeline_factory: Optional[Callable] = None        # (transcriber) -> the pipeline of a file; None: BatchedInferencePipeline
+    batcher: Optional["FileBatcher"] = None            # set when file_batch_window_ms > 0
+
     def __init__(self, host: str, port: int, model: str, *, devices: Sequence[int] = (0,), api_key: Optional[str] = None,
                  cors_origins: Optional[str] = None, rate_limit_rpm: int = 0, model_factory: Optional[Callable] = None,
                  max_body_bytes: int = 512 << 20, diarization_model: Optional[str] = None,
-                 embedder_factory: Optional[Callable] = None, file_batch_size: int = 0):
+                 embedder_factory: Optional[Callable] = None, file_batch_size: int = 0, file_batch_window_ms: int = 0,
+                 pipeline_factory: Optional[Callable] = None):
         self.host, self.port, self.model = host, int(port), model
         # 0: a file is decoded one window after another (WhisperModelHIP.transcribe). N > 0: the GPU's shared transcriber is built with
         # max_batch = N and a file goes through BatchedInferencePipeline, N speech chunks per decode step
         self.file_batch_size = int(file_batch_size)
         if not 0 <= self.file_batch_size <= 64:
             raise ValueError("file_batch_size must be 0 (sequential decoding) or 1..64 chunks per decode step")
+        # 0: every request runs its pipeline alone, as before. W > 0: uploads that arrive within W ms of one another, and decode with
+        # the same group-wide options, run as ONE BatchedInferencePipeline.iter_many job (FileBatcher below); the transcriber is then
+        # built with max_batch = 2 N: N chunks per decode step in front of a wave of up to N files
+        self.file_batch_window_ms = int(file_batch_window_ms)
+        if self.file_batch_window_ms < 0:
+            raise ValueError("file_batch_window_ms must be 0 (off) or a number of milliseconds")
+        if self.file_batch_window_ms > 0 and not 1 <= self.file_batch_size <= 32:
+            raise ValueError("file_batch_window_ms needs file_batch_size 1..32 (the chunks per decode step of the pooled job)")
+        self.pipeline_factory = pipeline_factory
         self.devices = list(devices) if devices else [0]
         if any(d < 0 for d in self.devices):
             raise ValueError("devices must be non-negative GPU indices")
@@ -287,6 +398,12 @@ class RestServer:
         self._req_lock = threading.Lock()
         self._httpd: Optional[ThreadingHTTPServer] = None
         self._thread: Optional[threading.Thread] = None
+        # last, when nothing above can refuse the arguments any more: one batcher (one worker thread) per GPU, so that the pooled jobs
+        # of different devices run side by side; `batcher` is the first device's
+        self._batchers: Dict[int, FileBatcher] = {}
+        if self.file_batch_window_ms > 0:
+            self._batchers = {d: FileBatcher(self._pipeline, self.file_batch_size, self.file_batch_window_ms / 1000.0) for d in self.devices}
+            self.batcher = self._batchers[self.devices[0]]
 
     # ---- life cycle
     def start(self) -> "RestServer":
@@ -311,6 +428,8 @@ class RestServer:
         if self._thread is not None:
             self._thread.join()
             self._thread = None
+        for b in getattr(self, "_batchers", {}).values():
+            b.close()
 
     def serve_forever(self):
         self.start()
@@ -347,7 +466,7 @@ class RestServer:
         from .serve_client import ServeClientHIP
         with ServeClientHIP.MODELS_LOCK:
             if device_index not in ServeClientHIP.MODELS:
-                kw = {"max_batch": self.file_batch_size} if self.file_batch_size > 0 else {}
+                kw = {"max_batch": self.file_batch_size * (2 if self.batcher is not None else 1)} if self.file_batch_size > 0 else {}
                 if self.model_factory is not None:
                     ServeClientHIP.MODELS[device_index] = self.model_factory(self.model, device_index, **kw)
                 else:
@@ -371,8 +490,21 @@ class RestServer:
                 raise _HttpError(400, {"error": str(e)})
         if self.file_batch_size <= 0:
             return transcriber.transcribe(data, vad_filter=False, **kw)
+        return self._pipeline(transcriber).transcribe(data, vad_filter=True, batch_size=self.file_batch_size, **kw)
+
+    def _pipeline(self, transcriber):
+        if self.pipeline_factory is not None:
+            return self.pipeline_factory(transcriber)
         from .batched import BatchedInferencePipeline
-        return BatchedInferencePipeline(transcriber).transcribe(data, vad_filter=True, batch_size=self.file_batch_size, **kw)
+        return BatchedInferencePipeline(transcriber)
+
+    def transcribe_pooled(self, transcriber, data: bytes, *, device_index: Optional[int] = None, language=None, initial_prompt=None,
+                          hotwords=None, **shared):
+        """`transcribe_file` through the batcher (file_batch_window_ms > 0): the upload joins the uploads that arrive within the window
+        and decode with the same `shared` options; -> (list of segments, info) of this upload, or its own error raised here, in the
+        request's thread, where the single route would have raised it. Nothing is left for `resident_file_audio` after a pooled job
+        (many_files.py), so speaker labels fall back to the second decode; requests with known speakers are not pooled at all."""
+        return self._batchers.get(device_index, self.batcher).submit(transcriber, data, dict(language=language, initial_prompt=initial_prompt, hotwords=hotwords), shared)
 
     @staticmethod
     def resident_audio(transcriber):
@@ -601,8 +733,12 @@ class _Handler(BaseHTTPRequestHandler):
             device_index = rest._next_device()
             transcriber = rest.transcriber_for(device_index)
             mc = {"multichannel": True} if multichannel else {}
-            segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
-                                                  temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)
+            if rest.batcher is not None and not multichannel and not known_speaker_names and not known_speaker_references:
+                segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
+                                                        temperature=temperature, word_timestamps=want_words, hotwords=hotwords)
+            else:
+                segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
+                                                      temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)
             segments = list(segments or [])
             text = render_text(segments, multichannel)
             if response_format == "text":
@@ -715,13 +851,17 @@ def main(argv=None):
     ap.add_argument("--metrics_port", type=int, default=0)
     ap.add_argument("--file_batch_size", type=int, default=0,
                     help="speech chunks decoded per step by the batched long-form pipeline (0 = decode a file window after window)")
+    ap.add_argument("--file_batch_window_ms", type=int, default=0,
+                    help="pool uploads that arrive within this many milliseconds into one job whose decode steps mix files "
+                         "(needs --file_batch_size; 0 = every request runs alone)")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if a.metrics_port > 0:
         wl_metrics.start_metrics_server(a.metrics_port)
     RestServer(a.host, a.port, a.model_path, devices=[int(x) for x in a.devices.split(",") if x != ""], api_key=a.api_key,
                cors_origins=a.cors_origins, rate_limit_rpm=a.rate_limit_rpm, max_body_bytes=a.max_body_mb << 20,
-               diarization_model=a.diarization_model, file_batch_size=a.file_batch_size).serve_forever()
+               diarization_model=a.diarization_model, file_batch_size=a.file_batch_size,
+               file_batch_window_ms=a.file_batch_window_ms).serve_forever()
 
 
 if __name__ == "__main__":
