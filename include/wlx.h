@@ -651,6 +651,40 @@ int32_t wlx_spk_embed_pcm_batch(wlx_spk* spk, wlx_engine* e, int32_t slot, int32
 int32_t wlx_spk_embed_ring_batch(wlx_spk* spk, wlx_ring* r, const int64_t* starts, const int64_t* n_samples, int32_t n,
                                  float* out, int32_t* status);
 
+/* ---- offline speaker clustering: all embeddings of a file at once (the online rule of the live sessions is host code) ----
+ * Average-linkage (UPGMA) agglomerative clustering of the cosine DISTANCES 1 - dot(x_i, x_j) of n unit embeddings, float32 throughout,
+ * in one launch of one workgroup. The rules are exact (whisperlive_amd/file_diarization.py cluster_host restates them in NumPy float32
+ * and the tests ask for equality): clusters are named by their lowest member; each round merges the pair (i, j), i < j, of live
+ * clusters with the smallest (distance, i, j) in lexicographic order, j into i, and every other live k gets
+ * d(k, i) = (n_i d(k, i) + n_j d(k, j)) / (n_i + n_j), each operation rounded on its own; it stops at one cluster, or when the smallest
+ * distance is > threshold and (max_clusters == 0 or live clusters <= max_clusters): max_clusters forces merges past the threshold.
+ * labels number the clusters 0 .. K-1 by lowest member: with windows in time order, by first appearance. */
+#define WLX_SPK_CLUSTER_MAX 2048
+typedef struct {
+    float   threshold;     /* cosine DISTANCE at which merging stops (1 - similarity), in [0, 2] */
+    int32_t max_clusters;  /* 0 = no cap */
+} wlx_spk_cluster_opts;
+/* host embeddings emb [n][dim] (unit rows, dim = the engine's embed_dim, 1 <= n <= WLX_SPK_CLUSTER_MAX) -> labels [n], *n_clusters = K,
+ * and, when `centroids` is not null, its first K rows [dim]: the normalised mean of each cluster's members (the buffer holds up to n
+ * rows; rows from K on are not written). n = 1: label 0, nothing launched. One upload, one wait. WLX_ERR_ARG, before any launch and
+ * with nothing written: a null pointer, n or dim out of range, a threshold that is NaN or outside [0, 2], max_clusters < 0. */
+int32_t wlx_spk_cluster(wlx_spk* spk, const float* emb, int32_t n, int32_t dim, const wlx_spk_cluster_opts* opts,
+                        int32_t* labels, float* centroids, int32_t* n_clusters);
+/* A whole file: windows [starts[i], starts[i] + n_samples[i]) of the resident PCM of a slot item, 1 <= n <= WLX_SPK_CLUSTER_MAX. ALL of
+ * them are embedded — n may exceed WLX_SPK_MAX_BATCH and their sum max_seconds: the call groups them itself, greedily in order, by
+ * the rule of one wlx_spk_embed_pcm_batch call per group (at most WLX_SPK_MAX_BATCH windows and max_seconds of samples), and enqueues
+ * the ragged passes back to back, each writing its rows into one device table — then clustered as above, with ONE wait at the end.
+ * A window under 4800 samples: status[i] = WLX_ERR_TOO_SHORT, labels[i] = -1, a zero row of emb_out; it takes no part. The m others
+ * get status WLX_OK and their cluster in labels. Nullable outputs: emb_out [n][embed_dim], row i with the bits wlx_spk_embed_pcm_batch
+ * gives for that range; dist_out [m][m], the matrix the device clustered, over the windows that took part in their order;
+ * centroids, K rows as above (room for m). m = 1: label 0, no clustering launch; m = 0: *n_clusters = 0, nothing launched.
+ * Ordering behind the slot's stream, the busy rule, the device check and WLX_ERR_STATE as in wlx_spk_embed_pcm_batch. WLX_ERR_ARG,
+ * before any launch and with nothing written: a null pointer, n out of range, the options as above, a negative start or count, a
+ * single window over max_seconds. */
+int32_t wlx_spk_diarize_pcm(wlx_spk* spk, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts, const int64_t* n_samples,
+                            int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, float* emb_out,
+                            float* dist_out, float* centroids, int32_t* n_clusters);
+
 /* ==== everything below: TEST / PROFILING hooks (used only by tests/, scripts/ and bench.py's roofline leg; not part of
  * the drop-in boundary; the product entry points end here) ================================================================= */
 /* next-token logits [rows, vocab] of the last decoder step executed on the slot */
@@ -740,6 +774,15 @@ int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, int32_t H, 
                                  int32_t relu, uint16_t* out);
 int32_t wlx_spk_debug_pool_batch(int32_t device, const uint16_t* x, int32_t F, int32_t n, const int32_t* frames, int32_t C, float eps,
                                  float* out);
+/* The clustering kernels, one launch each. Affinity: X float32 [n][dim] (1 <= n <= WLX_SPK_CLUSTER_MAX, 1 <= dim <= 1024) ->
+ * dist_out [n][n] = 1 - X X^T, exactly symmetric, diagonal exactly 0. */
+int32_t wlx_spk_debug_affinity(int32_t device, const float* X, int32_t n, int32_t dim, float* dist_out);
+/* Clustering of a given symmetric matrix dist [n][n] (not written): labels [n], merges [n - 1][2] as (i, j), heights [n - 1],
+ * *n_merges, *n_clusters; rows of merges / heights from *n_merges on come back unchanged. */
+int32_t wlx_spk_debug_ahc(int32_t device, const float* dist, int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels,
+                          int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters);
+/* device times (HIP events) of the last wlx_spk_cluster or wlx_spk_diarize_pcm that clustered: the distance matrix, the clustering */
+int32_t wlx_spk_debug_cluster_timings(wlx_spk* spk, float* affinity_ms, float* ahc_ms);
 
 /* Whisper kernels, one launch each (csrc/kernel_hooks.hip), same conventions: host arrays (fp16 as uint16 bits), a private stream
  * of `device`, outputs copied in AND out (bytes no thread owns come back unchanged), WLX_ERR_ARG before any launch for every

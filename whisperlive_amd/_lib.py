@@ -15,7 +15,7 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
@@ -27,11 +27,13 @@ EXPORTS = [
     "wlx_logmel_chunks", "wlx_logmel_chunks_multi", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
     "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch", "wlx_spk_embed_pcm_batch", "wlx_spk_embed_ring_batch",
+    "wlx_spk_cluster", "wlx_spk_diarize_pcm",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_search_batch", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
     "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
     "wlx_mt_debug_embed",
     "wlx_spk_debug_timings", "wlx_spk_debug_fbank", "wlx_spk_debug_conv", "wlx_spk_debug_pool",
     "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
+    "wlx_spk_debug_affinity", "wlx_spk_debug_ahc", "wlx_spk_debug_cluster_timings",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
     "wlx_debug_dec_gemv", "wlx_debug_dec_cq_cross_attn",
     "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_resample_stream", "wlx_debug_flac_decode", "wlx_debug_flac_timings", "wlx_debug_adpcm_decode",
@@ -110,6 +112,10 @@ class wlx_mt_spec(C.Structure):
                                          "pad_id", "eos_id", "decoder_start_id", "scale_embedding")]
 
 
+class wlx_spk_cluster_opts(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("max_clusters", C.c_int32)]
+
+
 class wlx_spk_spec(C.Structure):
     _fields_ = [("n_mels", C.c_int32), ("planes", C.c_int32), ("blocks", C.c_int32 * 4), ("embed_dim", C.c_int32),
                 ("max_seconds", C.c_int32), ("pool_eps", C.c_float)]
@@ -118,6 +124,7 @@ class wlx_spk_spec(C.Structure):
 ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
 ERR_DATA = 7            # wlx_status WLX_ERR_DATA: damaged input (the FLAC and telephony WAV front ends)
 SPK_MAX_BATCH = 64      # wlx.h WLX_SPK_MAX_BATCH: segments of one wlx_spk_embed_batch call
+SPK_CLUSTER_MAX = 2048  # wlx.h WLX_SPK_CLUSTER_MAX: rows of one wlx_spk_cluster / windows of one wlx_spk_diarize_pcm call
 VAD_MAX_BATCH = 64      # wlx.h WLX_VAD_MAX_BATCH: sequences of one wlx_vad_probs_batch / wlx_vad_probs_pcm_batch call
 ALIGN_MAX_BATCH = 64    # wlx.h WLX_ALIGN_MAX_BATCH: entries of one wlx_align_batch call
 ALIGN_MAX_MEDIAN = 15   # wlx.h WLX_ALIGN_MAX_MEDIAN: the widest median filter the device post-processing serves
@@ -384,6 +391,12 @@ def load() -> C.CDLL:
     lib.wlx_spk_embed_batch.argtypes = [vp, f32p, i64p, i32, f32p, i32p]
     lib.wlx_spk_embed_pcm_batch.argtypes = [vp, vp, i32, i32, i64p, i64p, i32, f32p, i32p]
     lib.wlx_spk_embed_ring_batch.argtypes = [vp, vp, i64p, i64p, i32, f32p, i32p]
+    copts = C.POINTER(wlx_spk_cluster_opts)
+    lib.wlx_spk_cluster.argtypes = [vp, f32p, i32, i32, copts, i32p, f32p, i32p]
+    lib.wlx_spk_diarize_pcm.argtypes = [vp, vp, i32, i32, i64p, i64p, i32, copts, i32p, i32p, f32p, f32p, f32p, i32p]
+    lib.wlx_spk_debug_affinity.argtypes = [i32, f32p, i32, i32, f32p]
+    lib.wlx_spk_debug_ahc.argtypes = [i32, f32p, i32, copts, i32p, i32p, f32p, i32p, i32p]
+    lib.wlx_spk_debug_cluster_timings.argtypes = [vp, f32p, f32p]
     lib.wlx_spk_debug_timings.argtypes = [vp, f32p, f32p]
     lib.wlx_spk_debug_fbank.argtypes = [i32, f32p, i64, i32, f32p, u16p, i32, i32p]
     lib.wlx_spk_debug_conv.argtypes = [i32, u16p, i32, i32, i32, f32p, f32p, u16p, i32, i32, i32, i32, u16p]

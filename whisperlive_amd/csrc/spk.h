@@ -51,4 +51,15 @@ bool launch_spk_pool_batch(const half_t* x, int F, const int* frames, int n, int
 // pooled [n][D] -> emb [n][E]: emb = W pooled + b (W fp16 [E][D] row-major, D a multiple of 8), then emb /= |emb|. E <= 1024.
 void launch_spk_head_batch(const float* pooled, const half_t* W, const float* b, int E, int D, int n, float* emb, hipStream_t s);
 
+// ---- offline clustering (spk_cluster.hip): n in 1..WLX_SPK_CLUSTER_MAX unit rows of D <= 1024 floats, everything float32.
+// False = nothing launched (a null pointer, n or D out of range, a threshold that is NaN or outside [0, 2], max_clusters < 0).
+// dist [n][n] = 1 - X X^T, exactly symmetric, diagonal exactly 0
+bool launch_spk_affinity(const float* X, int n, int D, float* dist, hipStream_t s);
+// average-linkage clustering of dist IN PLACE, one workgroup (the rules: include/wlx.h wlx_spk_cluster). merges [n - 1][2],
+// heights [n - 1], labels [n], counts [2] = {n_merges, K}
+bool launch_spk_ahc(float* dist, int n, float threshold, int max_clusters, int* merges, float* heights, int* labels, int* counts,
+                    hipStream_t s);
+// cent [K][D], K = counts[1] read on the device (the grid covers n): the normalised sum of each cluster's rows
+bool launch_spk_centroids(const float* X, const int* labels, const int* counts, int n, int D, float* cent, hipStream_t s);
+
 }  // namespace wlx

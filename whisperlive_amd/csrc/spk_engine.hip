@@ -4,7 +4,8 @@
 // by the engine's mutex. ONE pass (spk_run_batch) serves every entry point: up to WLX_SPK_MAX_BATCH segments as one ragged batch
 // through the same buffers (the sum of their lengths is what has to fit max_seconds). wlx_spk_embed is a batch of one;
 // wlx_spk_embed_batch uploads its items; wlx_spk_embed_pcm_batch / _ring_batch run the pass on ranges of audio that is already in HBM
-// (a slot item's PCM, a client's PCM ring), with no upload. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
+// (a slot item's PCM, a client's PCM ring), with no upload. wlx_spk_cluster / wlx_spk_diarize_pcm cluster embeddings on the device
+// (spk_cluster.hip): the second enqueues the passes of a whole file's windows back to back and waits once. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
 // _pool (one item) and _conv_batch / _pool_batch (ragged), each pair on one implementation.
 #include <cmath>
 #include <mutex>
@@ -114,6 +115,16 @@ struct wlx_spk {
     float* h_emb = nullptr;          // pinned [WLX_SPK_MAX_BATCH][embed_dim]: where a batch's embeddings land before they are dealt to rows
     float fbank_ms = 0.f, net_ms = 0.f;
     bool timed = false;
+    // offline clustering (spk_cluster.hip), allocated by the first call that clusters: the table of up to WLX_SPK_CLUSTER_MAX embeddings
+    // the passes of a file write into, its distance matrix, the results, and their pinned landing places
+    bool cl_ready = false;
+    float *cl_emb = nullptr, *cl_dist = nullptr, *cl_cent = nullptr, *cl_heights = nullptr;
+    int *cl_merges = nullptr, *cl_labels = nullptr, *cl_counts = nullptr;
+    float *h_cl_emb = nullptr, *h_cl_cent = nullptr;
+    int* h_cl_int = nullptr;         // [labels WLX_SPK_CLUSTER_MAX | n_merges, K]
+    hipEvent_t ev_cl[4] = {nullptr, nullptr, nullptr, nullptr};
+    float aff_ms = 0.f, ahc_ms = 0.f;
+    bool cl_timed = false;
 };
 
 static void spk_free(wlx_spk* k) {
@@ -124,6 +135,10 @@ static void spk_free(wlx_spk* k) {
         if (e) (void)hipEventDestroy(e);
     for (void* p : k->pool) (void)hipFree(p);
     if (k->h_emb) (void)hipHostFree(k->h_emb);
+    for (hipEvent_t e : k->ev_cl)
+        if (e) (void)hipEventDestroy(e);
+    for (void* p : {(void*)k->h_cl_emb, (void*)k->h_cl_cent, (void*)k->h_cl_int})
+        if (p) (void)hipHostFree(p);
     if (k->st) (void)hipStreamDestroy(k->st);
     delete k;
 }
@@ -256,10 +271,10 @@ static void spk_plan_commit(const wlx_spk* k, const int64_t* n_samples, int n, f
     }
 }
 
-// The pass itself on k->st, behind whatever the caller put there (an upload, a wait for another stream): item a of the plan is the
-// samples src[offs[a] ...) — the engine's upload buffer or resident audio, the launches do not know which. One launch sequence, one
-// download, one wait. k->mu is held and the device is set.
-static int spk_run_batch(wlx_spk* k, const float* src, const SpkPlan& pl, float* out) {
+// The launches of the pass on k->st, behind whatever the caller put there (an upload, a wait for another stream): item a of the plan is
+// the samples src[offs[a] ...) — the engine's upload buffer or resident audio, the launches do not know which; its embedding is row a of
+// `emb` (device). Nothing is waited for: the plan's tables travel in the kernel arguments. k->mu is held and the device is set.
+static int spk_enqueue_batch(wlx_spk* k, const float* src, const SpkPlan& pl, float* emb) {
     const wlx_spk_spec& sp = k->spec;
     hipStream_t st = k->st;
     const int m = pl.m;
@@ -292,9 +307,18 @@ static int spk_run_batch(wlx_spk* k, const float* src, const SpkPlan& pl, float*
     }
     if (!launch_spk_pool_batch(x, H, widths, m, sp.planes << 3, sp.pool_eps, k->pooled, st))
         return set_error(WLX_ERR_ARG, "pooling refused a batch of %d", m);
-    launch_spk_head_batch(k->pooled, k->head_W, k->head_b, sp.embed_dim, k->pool_dim, m, k->emb, st);
+    launch_spk_head_batch(k->pooled, k->head_W, k->head_b, sp.embed_dim, k->pool_dim, m, emb, st);
     CK(hipEventRecord(k->ev[2], st));
     CK(hipGetLastError());
+    return WLX_OK;
+}
+
+// The pass for the embed entry points: one launch sequence, one download, one wait; row a of the pass goes to row pl.row[a] of `out`.
+static int spk_run_batch(wlx_spk* k, const float* src, const SpkPlan& pl, float* out) {
+    const wlx_spk_spec& sp = k->spec;
+    hipStream_t st = k->st;
+    const int m = pl.m;
+    CKR(spk_enqueue_batch(k, src, pl, k->emb));
     CK(hipMemcpyAsync(k->h_emb, k->emb, (size_t)m * sp.embed_dim * sizeof(float), hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
     for (int a = 0; a < m; ++a) std::copy(k->h_emb + (size_t)a * sp.embed_dim, k->h_emb + (size_t)(a + 1) * sp.embed_dim, out + (size_t)pl.row[a] * sp.embed_dim);
@@ -369,6 +393,176 @@ extern "C" int32_t wlx_spk_embed_ring_batch(wlx_spk* k, wlx_ring* r, const int64
     for (int a = 0; a < pl.m; ++a) pl.offs[a] -= (long)L.base;
     CK(hipSetDevice(k->device));
     return spk_run_batch(k, L.buf, pl, out);
+}
+
+// ------------------------------------------------------------------------------------------------ offline clustering (spk_cluster.hip)
+static int spk_cluster_opts_ok(const char* who, const wlx_spk_cluster_opts* o) {
+    if (!(o->threshold >= 0.f && o->threshold <= 2.f))
+        return set_error(WLX_ERR_ARG, "%s: threshold %g is not a cosine distance in [0, 2]", who, (double)o->threshold);
+    if (o->max_clusters < 0) return set_error(WLX_ERR_ARG, "%s: max_clusters %d is negative", who, o->max_clusters);
+    return WLX_OK;
+}
+
+// the buffers of a clustering call, made by the first one (an engine that only embeds never pays for them). k->mu is held.
+static int spk_cluster_reserve(wlx_spk* k) {
+    if (k->cl_ready) return WLX_OK;
+    const size_t N = WLX_SPK_CLUSTER_MAX, E = (size_t)k->spec.embed_dim;
+    if (!k->cl_emb) CKR(dalloc(k->pool, &k->cl_emb, N * E, false));
+    if (!k->cl_cent) CKR(dalloc(k->pool, &k->cl_cent, N * E, false));
+    if (!k->cl_dist) CKR(dalloc(k->pool, &k->cl_dist, N * N, false));
+    if (!k->cl_heights) CKR(dalloc(k->pool, &k->cl_heights, N, false));
+    if (!k->cl_merges) CKR(dalloc(k->pool, &k->cl_merges, 2 * N, false));
+    if (!k->cl_labels) CKR(dalloc(k->pool, &k->cl_labels, N, false));
+    if (!k->cl_counts) CKR(dalloc(k->pool, &k->cl_counts, 2, false));
+    if (!k->h_cl_emb) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_cl_emb), N * E * sizeof(float), hipHostMallocDefault));
+    if (!k->h_cl_cent) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_cl_cent), N * E * sizeof(float), hipHostMallocDefault));
+    if (!k->h_cl_int) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_cl_int), (N + 2) * sizeof(int), hipHostMallocDefault));
+    for (hipEvent_t& e : k->ev_cl)
+        if (!e) CK(hipEventCreate(&e));
+    k->cl_ready = true;
+    return WLX_OK;
+}
+
+// m >= 2 rows of k->cl_emb, written by work already on k->st: distance matrix, clustering, centroids and the downloads into the pinned
+// buffers, all enqueued; the caller waits once. dist_out (host, may be null) gets the matrix before the clustering overwrites it.
+static int spk_cluster_enqueue(wlx_spk* k, int m, const wlx_spk_cluster_opts* o, float* dist_out, bool want_centroids) {
+    hipStream_t st = k->st;
+    const int E = k->spec.embed_dim;
+    CK(hipEventRecord(k->ev_cl[0], st));
+    if (!launch_spk_affinity(k->cl_emb, m, E, k->cl_dist, st)) return set_error(WLX_ERR_ARG, "the distance matrix refused %d x %d", m, E);
+    CK(hipEventRecord(k->ev_cl[1], st));
+    if (dist_out) CK(hipMemcpyAsync(dist_out, k->cl_dist, (size_t)m * m * sizeof(float), hipMemcpyDeviceToHost, st));
+    CK(hipEventRecord(k->ev_cl[2], st));
+    if (!launch_spk_ahc(k->cl_dist, m, o->threshold, o->max_clusters, k->cl_merges, k->cl_heights, k->cl_labels, k->cl_counts, st))
+        return set_error(WLX_ERR_ARG, "the clustering refused %d rows", m);
+    CK(hipEventRecord(k->ev_cl[3], st));
+    if (want_centroids) {
+        if (!launch_spk_centroids(k->cl_emb, k->cl_labels, k->cl_counts, m, E, k->cl_cent, st))
+            return set_error(WLX_ERR_ARG, "the centroids refused %d x %d", m, E);
+        CK(hipMemcpyAsync(k->h_cl_cent, k->cl_cent, (size_t)m * E * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(k->h_cl_int, k->cl_labels, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(k->h_cl_int + WLX_SPK_CLUSTER_MAX, k->cl_counts, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    return WLX_OK;
+}
+
+// after the wait: K, the first K centroids to the caller, the times
+static int spk_cluster_collect(wlx_spk* k, int m, float* centroids, int32_t* n_clusters) {
+    const int K = k->h_cl_int[WLX_SPK_CLUSTER_MAX + 1];
+    if (K < 1 || K > m) return set_error(WLX_ERR_HIP, "the clustering of %d rows reported %d clusters", m, K);
+    *n_clusters = K;
+    if (centroids) std::copy(k->h_cl_cent, k->h_cl_cent + (size_t)K * k->spec.embed_dim, centroids);
+    CK(hipEventElapsedTime(&k->aff_ms, k->ev_cl[0], k->ev_cl[1]));
+    CK(hipEventElapsedTime(&k->ahc_ms, k->ev_cl[2], k->ev_cl[3]));
+    k->cl_timed = true;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_spk_cluster(wlx_spk* k, const float* emb, int32_t n, int32_t dim, const wlx_spk_cluster_opts* opts, int32_t* labels,
+                                   float* centroids, int32_t* n_clusters) {
+    if (!k || !emb || !opts || !labels || !n_clusters) return set_error(WLX_ERR_ARG, "wlx_spk_cluster: null argument");
+    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "wlx_spk_cluster: %d rows outside 1..%d", n, WLX_SPK_CLUSTER_MAX);
+    if (dim != k->spec.embed_dim) return set_error(WLX_ERR_ARG, "wlx_spk_cluster: dim %d is not the engine's %d", dim, k->spec.embed_dim);
+    CKR(spk_cluster_opts_ok("wlx_spk_cluster", opts));
+    if (n == 1) {                     // one row is its own cluster and its own centroid
+        labels[0] = 0, *n_clusters = 1;
+        if (centroids) std::copy(emb, emb + dim, centroids);
+        return WLX_OK;
+    }
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    CKR(spk_cluster_reserve(k));
+    CK(hipMemcpyAsync(k->cl_emb, emb, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice, k->st));
+    CKR(spk_cluster_enqueue(k, n, opts, nullptr, centroids != nullptr));
+    CK(hipStreamSynchronize(k->st));
+    CKR(spk_cluster_collect(k, n, centroids, n_clusters));
+    std::copy(k->h_cl_int, k->h_cl_int + n, labels);
+    return WLX_OK;
+}
+
+// A file's windows: grouped as plan_embed_groups (diarization.py) groups the ranges of wlx_spk_embed_pcm_batch calls — greedily in order,
+// a group closes at WLX_SPK_MAX_BATCH windows or when the next one would take it over max_seconds, short windows counted — every group
+// one ragged pass whose head writes its rows straight into the table, then the clustering on that table; ONE wait.
+extern "C" int32_t wlx_spk_diarize_pcm(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts, const int64_t* n_samples,
+                                       int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, float* emb_out,
+                                       float* dist_out, float* centroids, int32_t* n_clusters) {
+    const char* who = "wlx_spk_diarize_pcm";
+    if (!k || !e || !starts || !n_samples || !opts || !labels || !status || !n_clusters) return set_error(WLX_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "%s: %d windows outside 1..%d", who, n, WLX_SPK_CLUSTER_MAX);
+    CKR(spk_cluster_opts_ok(who, opts));
+    CKR(PcmLease::same_device(who, "engine", e->device, "speaker engine", k->device));
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] < 0 || n_samples[i] > k->max_samples)
+            return set_error(WLX_ERR_ARG, "%s: window %d: %lld samples outside 0..the engine's %d s", who, i, (long long)n_samples[i], k->spec.max_seconds);
+        if (starts[i] < 0) return set_error(WLX_ERR_ARG, "%s: window %d starts at %lld", who, i, (long long)starts[i]);
+    }
+    PcmLease L;
+    CKR(L.open_slot(e, slot));
+    CKR(L.item(who, item));
+    if (L.resident <= 0 || !L.buf) return set_error(WLX_ERR_STATE, "%s: item %d: no PCM resident", who, item);
+    for (int i = 0; i < n; ++i) CKR(L.range(who, starts[i], n_samples[i]));
+    // the passes: plans[g] holds the windows of group g that take part; row_of[a] = the window behind row a of the table
+    std::vector<SpkPlan> plans;
+    std::vector<int> row_of;
+    {
+        SpkPlan cur;
+        int count = 0;
+        for (int i = 0; i < n; ++i) {
+            if (count > 0 && (count >= WLX_SPK_MAX_BATCH || cur.total + (long)n_samples[i] > k->max_samples)) {
+                if (cur.m > 0) plans.push_back(cur);
+                cur = SpkPlan(), count = 0;
+            }
+            if (n_samples[i] >= WLX_SPK_MIN_SAMPLES) {
+                cur.offs[cur.m] = (long)starts[i], cur.widths[cur.m] = spk_frames((long)n_samples[i]), cur.row[cur.m] = (int)row_of.size();
+                ++cur.m;
+                row_of.push_back(i);
+            }
+            cur.total += (long)n_samples[i], ++count;
+        }
+        if (cur.m > 0) plans.push_back(cur);
+    }
+    const int m = (int)row_of.size(), E = k->spec.embed_dim;
+    // every refusal on the arguments has had its turn: what is known without the device
+    for (int i = 0; i < n; ++i) {
+        const bool too_short = n_samples[i] < WLX_SPK_MIN_SAMPLES;
+        status[i] = too_short ? WLX_ERR_TOO_SHORT : WLX_OK;
+        labels[i] = too_short ? -1 : 0;
+        if (too_short && emb_out) std::fill(emb_out + (size_t)i * E, emb_out + (size_t)(i + 1) * E, 0.f);
+    }
+    *n_clusters = m > 0 ? 1 : 0;
+    if (m == 0) return WLX_OK;
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    CKR(spk_cluster_reserve(k));
+    CKR(L.order(k->st));
+    for (const SpkPlan& pl : plans) CKR(spk_enqueue_batch(k, L.buf, pl, k->cl_emb + (size_t)pl.row[0] * E));
+    const bool want_rows = emb_out || (m == 1 && centroids);
+    if (want_rows) CK(hipMemcpyAsync(k->h_cl_emb, k->cl_emb, (size_t)m * E * sizeof(float), hipMemcpyDeviceToHost, k->st));
+    if (m >= 2) CKR(spk_cluster_enqueue(k, m, opts, dist_out, centroids != nullptr));
+    CK(hipStreamSynchronize(k->st));
+    CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));          // (of the last pass)
+    CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
+    k->timed = true;
+    if (emb_out)
+        for (int a = 0; a < m; ++a) std::copy(k->h_cl_emb + (size_t)a * E, k->h_cl_emb + (size_t)(a + 1) * E, emb_out + (size_t)row_of[a] * E);
+    if (m == 1) {                     // one window is its own cluster, its embedding the centroid
+        if (dist_out) dist_out[0] = 0.f;
+        if (centroids) std::copy(k->h_cl_emb, k->h_cl_emb + E, centroids);
+        return WLX_OK;
+    }
+    CKR(spk_cluster_collect(k, m, centroids, n_clusters));
+    for (int a = 0; a < m; ++a) labels[row_of[a]] = k->h_cl_int[a];
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_spk_debug_cluster_timings(wlx_spk* k, float* affinity_ms, float* ahc_ms) {
+    if (!k || !affinity_ms || !ahc_ms) return set_error(WLX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> g(k->mu);
+    if (!k->cl_timed) return set_error(WLX_ERR_STATE, "no clustering has run on this engine");
+    *affinity_ms = k->aff_ms;
+    *ahc_ms = k->ahc_ms;
+    return WLX_OK;
 }
 
 extern "C" int32_t wlx_spk_debug_timings(wlx_spk* k, float* fbank_ms, float* net_ms) {
@@ -503,4 +697,47 @@ extern "C" int32_t wlx_spk_debug_pool_batch(int32_t device, const uint16_t* x, i
     }
     if (Tsum > (1 << 20)) return set_error(WLX_ERR_ARG, "%ld frames in all exceed 2^20", Tsum);
     return spk_debug_pool_run(device, x, F, n, frames, Tsum, C, eps, out);
+}
+
+// ---- the clustering kernels (spk_cluster.hip), one launch each
+extern "C" int32_t wlx_spk_debug_affinity(int32_t device, const float* X, int32_t n, int32_t dim, float* dist_out) {
+    if (!X || !dist_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_CLUSTER_MAX || dim < 1 || dim > 1024)
+        return set_error(WLX_ERR_ARG, "n %d / dim %d: n in 1..%d, dim in 1..1024", n, dim, WLX_SPK_CLUSTER_MAX);
+    HookScope S;
+    CKR(S.begin(device));
+    float *dX, *dD;
+    CKR(S.upload(&dX, X, (size_t)n * dim));
+    CKR(S.alloc(&dD, (size_t)n * n));
+    if (!launch_spk_affinity(dX, n, dim, dD, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CKR(S.download(dist_out, dD, (size_t)n * n));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_spk_debug_ahc(int32_t device, const float* dist, int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels,
+                                     int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
+    if (!dist || !opts || !labels || !merges || !heights || !n_merges || !n_clusters) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "n %d outside 1..%d", n, WLX_SPK_CLUSTER_MAX);
+    CKR(spk_cluster_opts_ok("wlx_spk_debug_ahc", opts));
+    int counts[2] = {0, 0};
+    HookScope S;
+    CKR(S.begin(device));
+    float *dD, *dH;
+    int *dM, *dL, *dC;
+    const size_t nm = (size_t)std::max(n - 1, 1);                  // (n = 1 merges nothing: one row of room, never written)
+    CKR(S.upload(&dD, dist, (size_t)n * n));
+    CKR(S.upload(&dH, n > 1 ? heights : nullptr, nm));
+    CKR(S.upload(&dM, n > 1 ? merges : nullptr, 2 * nm));
+    CKR(S.alloc(&dL, (size_t)n));
+    CKR(S.alloc(&dC, (size_t)2));
+    if (!launch_spk_ahc(dD, n, opts->threshold, opts->max_clusters, dM, dH, dL, dC, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CKR(S.download(labels, dL, (size_t)n));
+    if (n > 1) {
+        CKR(S.download(heights, dH, nm));
+        CKR(S.download(merges, dM, 2 * nm));
+    }
+    CKR(S.download(counts, dC, (size_t)2));
+    CKR(S.finish());
+    *n_merges = counts[0], *n_clusters = counts[1];
+    return WLX_OK;
 }

@@ -8,7 +8,9 @@ base.py `_identify_speaker`).
                            buffers allow (a file's segments; the streaming server embeds one at a time).
                            ``embed_resident(slot, item, ranges)`` / ``embed_ring(ring, ranges)`` do the same on (start, n_samples)
                            ranges of audio that is ALREADY in HBM (a slot item's PCM, a session's PCM ring): nothing is uploaded
-                           (wlx_spk_embed_pcm_batch / wlx_spk_embed_ring_batch). ``shared_embedder``
+                           (wlx_spk_embed_pcm_batch / wlx_spk_embed_ring_batch). ``cluster(X, threshold)`` and
+                           ``diarize_resident(slot, item, windows, threshold)`` cluster embeddings, or embed and cluster a whole
+                           file's windows, on the device (wlx_spk_cluster / wlx_spk_diarize_pcm; file_diarization.py). ``shared_embedder``
                            keeps one per (checkpoint, device), loaded by the first client that asks for diarization.
 * ``SpeakerDiarizer``    — the reference's online clustering, unchanged in behaviour: cosine similarity against the running
                            centroids, threshold 0.55, 0.9 / 0.1 running average with renormalisation, closest speaker at the cap,
@@ -154,6 +156,60 @@ class SpeakerEmbedderHIP:
         """the same on ABSOLUTE stream positions of a device PCM ring (whisperlive_amd.engine.PcmRing); ERR_STATE when a range has been
         trimmed away or has not arrived"""
         return self._embed_ranges(ranges, lambda *a: self.lib.wlx_spk_embed_ring_batch(self.h, ring._h, *a))
+
+    def cluster(self, X, threshold: float, max_clusters: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """wlx_spk_cluster: average-linkage clustering of the unit rows X [n][embed_dim] (n <= _lib.SPK_CLUSTER_MAX) at the cosine
+        DISTANCE `threshold` on the device -> (labels int32 [n], numbered by first appearance; centroids float32 [K][embed_dim]).
+        file_diarization.cluster_host states the rules."""
+        if self.h is None:
+            raise _lib.WlxError("speaker engine is closed")
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2:
+            raise ValueError("X must be [n][embed_dim]")
+        n, dim = X.shape
+        opts = _lib.wlx_spk_cluster_opts(float(threshold), int(max_clusters))
+        labels, cent, k = np.zeros(max(n, 1), dtype=np.int32), np.zeros((max(n, 1), dim), dtype=np.float32), C.c_int32()
+        f32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        _lib.check(self.lib.wlx_spk_cluster(self.h, X.ctypes.data_as(f32p), n, dim, C.byref(opts), labels.ctypes.data_as(i32p),
+                                            cent.ctypes.data_as(f32p), C.byref(k)))
+        return labels[:n], cent[:k.value].copy()
+
+    def diarize_resident(self, slot, item: int, windows, threshold: float, max_clusters: int = 0,
+                         want_embeddings: bool = False, want_distances: bool = False):
+        """wlx_spk_diarize_pcm: every (start, n_samples) window of the PCM resident in `item` of `slot` embedded and all of them
+        clustered on the device behind one wait (up to _lib.SPK_CLUSTER_MAX windows, each within max_seconds) ->
+        (labels int32 [n], -1 for a window under 0.3 s; centroids float32 [K][embed_dim]), and with want_embeddings / want_distances
+        also the rows [n][embed_dim] and the distance matrix [m][m] over the windows that took part."""
+        if self.h is None:
+            raise _lib.WlxError("speaker engine is closed")
+        windows = [(int(a), int(c)) for a, c in windows]
+        n, dim = len(windows), self.spec.embed_dim
+        starts = np.array([a for a, _ in windows], dtype=np.int64)
+        counts = np.array([c for _, c in windows], dtype=np.int64)
+        opts = _lib.wlx_spk_cluster_opts(float(threshold), int(max_clusters))
+        labels, status = np.full(max(n, 1), -1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        cent, k = np.zeros((max(n, 1), dim), dtype=np.float32), C.c_int32()
+        m = int((counts >= 4800).sum())
+        emb = np.zeros((max(n, 1), dim), dtype=np.float32) if want_embeddings else None
+        dist = np.zeros((m, m), dtype=np.float32) if want_distances and m else None
+        f32p, i32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        ptr = lambda a: a.ctypes.data_as(f32p) if a is not None else None
+        with slot.lock:
+            _lib.check(self.lib.wlx_spk_diarize_pcm(self.h, slot.engine._h, slot.sid, int(item), starts.ctypes.data_as(i64p),
+                                                    counts.ctypes.data_as(i64p), n, C.byref(opts), labels.ctypes.data_as(i32p),
+                                                    status.ctypes.data_as(i32p), ptr(emb), ptr(dist), ptr(cent), C.byref(k)))
+        out = (labels[:n], cent[:k.value].copy())
+        if want_embeddings:
+            out += (emb[:n],)
+        if want_distances:
+            out += (dist,)
+        return out
+
+    def cluster_timings(self) -> Tuple[float, float]:
+        """device milliseconds of the last clustering: (distance matrix, agglomeration)"""
+        a, b = C.c_float(), C.c_float()
+        _lib.check(self.lib.wlx_spk_debug_cluster_timings(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def timings(self) -> Tuple[float, float]:
         """device milliseconds of the last embed: (filterbank, network)"""

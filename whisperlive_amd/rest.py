@@ -244,6 +244,43 @@ def _reads_resident(diarizer, resident) -> bool:
     return bool(supports(resident)) if supports is not None else True
 
 
+def diarize_file_segments(segments, diarizer, resident_of, known=None, multichannel: bool = False):
+    """The `diarize=true` route: offline diarization (file_diarization.FileDiarizer) of the audio the transcription left on the device,
+    once per channel of a multichannel request. `resident_of(channel)` -> engine.ResidentPcm or None (channel None: a mono request).
+    -> (speaker per segment, per segment the speaker of each word or None, speakers in order of first appearance). The speakers of a
+    multichannel request carry their channel (`CH1_SPEAKER_00`): the clusters of two channels are not the same people; a name of
+    `known` stays as it is. A word that overlaps no turn (one of no duration) takes its segment's speaker, a segment that overlaps
+    none the speaker of the turn nearest in time. ValueError: nothing resident to read."""
+    from .file_diarization import assign_speakers, merge_spans
+    seg_speakers: List[Optional[str]] = [None] * len(segments)
+    word_speakers: List[Optional[List[Optional[str]]]] = [None] * len(segments)
+    speakers: List[str] = []
+    channels = sorted({s.channel for s in segments if getattr(s, "channel", None) is not None}) if multichannel else [None]
+    for ch in channels:
+        index = [i for i, s in enumerate(segments) if ch is None or s.channel == ch]
+        if not index:
+            continue
+        resident = resident_of(ch)
+        if resident is None:
+            raise ValueError("diarize needs the file's audio resident on the device; this request's was not kept there")
+        turns = diarizer.diarize(resident, merge_spans([segments[i] for i in index]), known=known)
+        if ch is not None:
+            turns = [(a, b, who if known and who in known else f"CH{ch}_{who}") for a, b, who in turns]
+        per_seg, per_word = assign_speakers([segments[i] for i in index], turns)
+        for k, i in enumerate(index):
+            who = per_seg[k]
+            if who is None and turns:
+                seg = segments[i]
+                who = min(turns, key=lambda t: max(t[0] - seg.end, seg.start - t[1], 0.0))[2]
+            seg_speakers[i] = who
+            if per_word[k] is not None:
+                word_speakers[i] = [w if w is not None else who for w in per_word[k]]
+        for _, _, who in turns:
+            if who not in speakers:
+                speakers.append(who)
+    return seg_speakers, word_speakers, speakers
+
+
 class _Upload:
     """one request waiting in the batcher"""
     __slots__ = ("transcriber", "key", "data", "per_file", "shared", "done", "result", "error")
@@ -543,6 +580,17 @@ class RestServer:
         return diarizer
 
 
+    def create_file_diarizer(self, device_index: int, max_speakers: int = 0):
+        """the offline diarizer of a `diarize=true` request on this GPU's shared embedder; ValueError = a 400"""
+        from .artifacts import resolve_diarization_model
+        from .diarization import shared_embedder
+        from .file_diarization import FileDiarizer
+        path = resolve_diarization_model(self.diarization_model)
+        if path is None and self.embedder_factory is None:
+            raise ValueError("known speakers requested but no speaker-embedding checkpoint is available on this server")
+        return FileDiarizer((self.embedder_factory or shared_embedder)(path, device_index), max_speakers=max_speakers)
+
+
 class _Handler(BaseHTTPRequestHandler):
     rest: RestServer = None           # set by RestServer.start()
     server_version = "whisperlive-amd-rest"
@@ -701,6 +749,13 @@ class _Handler(BaseHTTPRequestHandler):
         if stream_s not in _TRUE and stream_s not in _FALSE:
             raise _HttpError(400, {"error": "stream must be a boolean"})
         multichannel = parse_bool_field(one("multichannel", "false"), "multichannel")
+        diarize = parse_bool_field(one("diarize", "false"), "diarize")
+        try:
+            max_speakers = int(one("max_speakers", "0") or "0")
+        except ValueError:
+            max_speakers = -1
+        if max_speakers < 0:
+            raise _HttpError(400, {"error": "max_speakers must be a non-negative integer"})
         timestamp_granularities = normalize_form_list(many("timestamp_granularities") + many("timestamp_granularities[]")) or None
         chunking_strategy = one("chunking_strategy")
         include = many("include") + many("include[]") or None
@@ -733,7 +788,7 @@ class _Handler(BaseHTTPRequestHandler):
             device_index = rest._next_device()
             transcriber = rest.transcriber_for(device_index)
             mc = {"multichannel": True} if multichannel else {}
-            if rest.batcher is not None and not multichannel and not known_speaker_names and not known_speaker_references:
+            if rest.batcher is not None and not multichannel and not known_speaker_names and not known_speaker_references and not diarize:
                 segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
                                                         temperature=temperature, word_timestamps=want_words, hotwords=hotwords)
             else:
@@ -755,7 +810,20 @@ class _Handler(BaseHTTPRequestHandler):
                     rest_diarizer = rest.create_rest_diarizer(known_speaker_names, known_speaker_references, device_index)
                 except ValueError as e:
                     raise _HttpError(400, {"error": str(e)})
-                if rest_diarizer is not None and multichannel:
+                word_speakers = None
+                if diarize:
+                    # offline: every window of the file clustered at once (file_diarization.py); enrolled speakers only name clusters
+                    resident_of = (getattr(transcriber, "resident_file_audio", lambda c: None) if multichannel
+                                   else lambda _ch: rest.resident_audio(transcriber))
+                    try:
+                        file_diarizer = rest.create_file_diarizer(device_index, max_speakers)
+                        seg_speakers, word_speakers, verbose["speakers"] = diarize_file_segments(
+                            segments, file_diarizer, resident_of, known=dict(rest_diarizer.speakers) if rest_diarizer is not None else None,
+                            multichannel=multichannel)
+                    except ValueError as e:
+                        raise _HttpError(400, {"error": str(e)})
+                    speaker_labels = {i: who for i, who in enumerate(seg_speakers) if who}
+                elif rest_diarizer is not None and multichannel:
                     speaker_labels = speaker_labels_per_channel(segments, rest_diarizer, getattr(transcriber, "resident_file_audio", lambda c: None))
                 elif rest_diarizer is not None:
                     # from the audio the transcription left in the thread's slot (held until _release below); the file is decoded
@@ -773,6 +841,10 @@ class _Handler(BaseHTTPRequestHandler):
                         seg_dict["speaker"] = speaker_labels[index]
                     if want_words:
                         seg_dict["words"] = _words(seg)
+                        if word_speakers is not None and word_speakers[index] is not None:
+                            for word, who in zip(seg_dict["words"], word_speakers[index]):
+                                if who:
+                                    word["speaker"] = who
                     verbose["segments"].append(seg_dict)
                 wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
                 return self._json(200, verbose)
