@@ -601,6 +601,22 @@ int32_t wlx_mt_slot_destroy(wlx_mt* mt, int32_t slot);
 int32_t wlx_mt_translate(wlx_mt* mt, int32_t slot, int32_t batch, const int32_t* src_ids, const int32_t* src_lens,
                          int32_t src_stride, const wlx_mt_gen_opts* opts, int32_t* tokens_out, int32_t tokens_stride,
                          int32_t* n_tokens_out, float* scores_out);
+/* Translate a whole transcript as ONE job: `n` sources (1 <= n <= WLX_MT_MANY_MAX; n may exceed the slot's max_batch), arguments
+ * and outputs as wlx_mt_translate. The call orders the sources by length (a stable order), cuts them into groups of at most
+ * max_batch sources that fit the slot's source-token buffers, and runs each group as one encoder pass and one generate whose search
+ * (beam search, greedy search, no_repeat_ngram bans) runs ON THE DEVICE: no table goes up and no candidate comes down per decode
+ * step. The host enqueues decode steps in blocks and, after each block, waits for an event and reads a done word the search kernel
+ * stored to pinned memory behind the results; steps enqueued past the end compute on scratch. Results are written in INPUT order.
+ * Contract: entry i has the tokens, and the bit pattern of the score, that wlx_mt_translate gives for the sources of i's group in
+ * the group's order; wherever a batched wlx_mt_translate equals its single calls (every case the tests run) that is also the
+ * result of a single call on source i alone.
+ * WLX_ERR_ARG, before any launch and with no output written: a null pointer, n outside 1..WLX_MT_MANY_MAX, a source of length 0
+ * or longer than the slot's max_src (or src_stride), a token outside the vocabulary, options wlx_mt_translate refuses.
+ * WLX_ERR_STATE, likewise: a busy slot. wlx_mt_translate itself is unchanged (host search): the live path keeps using it. */
+#define WLX_MT_MANY_MAX 4096     /* sources of one wlx_mt_translate_many call: an hour of speech in segments */
+int32_t wlx_mt_translate_many(wlx_mt* mt, int32_t slot, int32_t n, const int32_t* src_ids, const int32_t* src_lens,
+                              int32_t src_stride, const wlx_mt_gen_opts* opts, int32_t* tokens_out, int32_t tokens_stride,
+                              int32_t* n_tokens_out, float* scores_out);
 
 /* ---- speaker embedding (WeSpeaker ResNet34) — PRODUCT entry points of the `enable_diarization` option ----
  * Replaces the pyannote.audio Inference(window="whole") call of the reference's SpeakerDiarizer._compute_embedding
@@ -729,8 +745,21 @@ int32_t wlx_mt_debug_encode(wlx_mt* mt, int32_t slot, int32_t batch, const int32
 /* translation engine: teacher-forced decoder logits [n][vocab] of one source and decoder tokens dec_tokens[0 .. n) */
 int32_t wlx_mt_debug_decode_logits(wlx_mt* mt, int32_t slot, const int32_t* src_ids, int32_t src_len, const int32_t* dec_tokens,
                                    int32_t n, float* out);
-/* translation engine: device times (HIP events) of the slot's last wlx_mt_translate: encoder pass, decode loop, decode steps */
+/* translation engine: device times (HIP events) of the slot's last wlx_mt_translate (or of the last group of its last
+ * wlx_mt_translate_many): encoder pass, decode loop; decode steps (of all groups). After wlx_mt_translate_many the decode time ends
+ * behind everything the host had enqueued when it saw the done word: with a block length above 1 (libwlx_ab.so, the hook) that
+ * includes the group's decode steps past its end, which `steps` does not count. */
 int32_t wlx_mt_debug_timings(wlx_mt* mt, int32_t slot, float* encode_ms, float* decode_ms, int32_t* steps);
+/* translation engine: the search alone on caller-supplied logits (float32 [steps][batch * num_beams][vocab], host; any vocab in
+ * 2..262144), no network pass: step i's logits go to the production top-k launches, then either the host bookkeeping of
+ * wlx_mt_translate (use_device = 0) or the device search of wlx_mt_translate_many (use_device = 1, decode steps enqueued in blocks of
+ * step_block, 0 = the library's) runs. ban_ld: the row length of the no_repeat_ngram ban table (the slots use 448). Outputs as
+ * wlx_mt_translate, plus the decode steps taken. WLX_ERR_ARG before any launch: a null pointer, batch outside 1..64, ids outside
+ * the vocabulary, options wlx_mt_translate refuses (num_beams <= 16), fewer steps of logits than max_length can take. */
+int32_t wlx_mt_debug_search(int32_t device, const float* logits, int32_t steps, int32_t batch, const wlx_mt_gen_opts* opts,
+                            int32_t vocab, int32_t pad_id, int32_t eos_id, int32_t start_id, int32_t ban_ld, int32_t step_block,
+                            int32_t use_device, int32_t* tokens_out, int32_t tokens_stride, int32_t* n_tokens_out,
+                            float* scores_out, int32_t* steps_run_out);
 /* translation engine kernels, one launch each on host arrays (fp16 as uint16 bits), on a private stream of `device`; every
  * shape the launcher cannot serve fails with WLX_ERR_ARG before any launch.
  * Attention: groups [n_groups][4] = (q0, nq, k0, nk), head h at columns 64 h of Q / K / V / O (strides ldq / ldk / ldv / ldo);

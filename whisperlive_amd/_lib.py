@@ -15,7 +15,7 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "vad.hip", "mt.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
@@ -25,12 +25,12 @@ EXPORTS = [
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_ring_set_format", "wlx_ring_append_frames", "wlx_resample_stream_count",
     "wlx_ring_group_create", "wlx_ring_group_destroy", "wlx_ring_group_lane", "wlx_ring_group_append_frames", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
     "wlx_logmel_chunks", "wlx_logmel_chunks_multi", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
-    "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate",
+    "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate", "wlx_mt_translate_many",
     "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch", "wlx_spk_embed_pcm_batch", "wlx_spk_embed_ring_batch",
     "wlx_spk_cluster", "wlx_spk_diarize_pcm",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_search_batch", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
     "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
-    "wlx_mt_debug_embed",
+    "wlx_mt_debug_embed", "wlx_mt_debug_search",
     "wlx_spk_debug_timings", "wlx_spk_debug_fbank", "wlx_spk_debug_conv", "wlx_spk_debug_pool",
     "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
     "wlx_spk_debug_affinity", "wlx_spk_debug_ahc", "wlx_spk_debug_cluster_timings",
@@ -128,6 +128,7 @@ SPK_CLUSTER_MAX = 2048  # wlx.h WLX_SPK_CLUSTER_MAX: rows of one wlx_spk_cluster
 VAD_MAX_BATCH = 64      # wlx.h WLX_VAD_MAX_BATCH: sequences of one wlx_vad_probs_batch / wlx_vad_probs_pcm_batch call
 ALIGN_MAX_BATCH = 64    # wlx.h WLX_ALIGN_MAX_BATCH: entries of one wlx_align_batch call
 ALIGN_MAX_MEDIAN = 15   # wlx.h WLX_ALIGN_MAX_MEDIAN: the widest median filter the device post-processing serves
+MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
 ERR_STATE = 4           # wlx_status WLX_ERR_STATE
 LM_MAXRANGES = 256      # wlx.h WLX_LM_MAXRANGES: ranges per chunk of wlx_logmel_chunks / wlx_logmel_ring
@@ -377,6 +378,8 @@ def load() -> C.CDLL:
     lib.wlx_mt_slot_create.argtypes = [vp, i32, i32, i32, i32p]
     lib.wlx_mt_slot_destroy.argtypes = [vp, i32]
     lib.wlx_mt_translate.argtypes = [vp, i32, i32, i32p, i32p, i32, C.POINTER(wlx_mt_gen_opts), i32p, i32, i32p, f32p]
+    lib.wlx_mt_translate_many.argtypes = [vp, i32, i32, i32p, i32p, i32, C.POINTER(wlx_mt_gen_opts), i32p, i32, i32p, f32p]
+    lib.wlx_mt_debug_search.argtypes = [i32, f32p, i32, i32, C.POINTER(wlx_mt_gen_opts), i32, i32, i32, i32, i32, i32, i32, i32p, i32, i32p, f32p, i32p]
     lib.wlx_mt_debug_encode.argtypes = [vp, i32, i32, i32p, i32p, i32, f32p, i64]
     lib.wlx_mt_debug_decode_logits.argtypes = [vp, i32, i32p, i32, i32p, i32, f32p]
     lib.wlx_mt_debug_timings.argtypes = [vp, i32, f32p, f32p, i32p]

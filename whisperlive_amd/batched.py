@@ -291,12 +291,21 @@ class BatchedInferencePipeline:
             segments = self._restored(segments, vad_clips[0], self.model.feature_extractor.sampling_rate)
         return segments, info
 
-    def transcribe(self, audio, *args, multichannel: bool = False, **kwargs):
-        """The reference's transcribe — every argument of `_transcribe` above, by position or by name — and ONE keyword-only switch
+    def transcribe(self, audio, *args, multichannel: bool = False, target_language: Optional[str] = None, translator=None, **kwargs):
+        """The reference's transcribe — every argument of `_transcribe` above, by position or by name — and keyword-only options
         the reference does not have. multichannel=False is `_transcribe`, untouched. multichannel=True: every channel of the file is
         transcribed on its own while the chunks of all channels share the decode groups; segments carry `channel` and come sorted by
-        (start, channel) — whisperlive_amd/multichannel.py. (`__wrapped__` below: the signature introspection reports is the
-        reference's, which is what a caller written against the reference binds to.)"""
+        (start, channel) — whisperlive_amd/multichannel.py. target_language (with `translator`, a translation.HipTranslator): the
+        segments come back as a LIST, each with `.translation` — the whole file as one translation job (file_translation.py); None
+        changes nothing. (`__wrapped__` below: the signature introspection reports is the reference's, which is what a caller
+        written against the reference binds to.)"""
+        if target_language is not None:
+            from .file_translation import check_target_language, translate_segments
+            if translator is None:              # before the file is transcribed, as iter_many refuses it
+                raise ValueError("target_language needs a translator")
+            check_target_language(translator, target_language)
+            segments, info = self.transcribe(audio, *args, multichannel=multichannel, **kwargs)
+            return translate_segments(segments, translator, target_language), info
         if not multichannel:
             return self._transcribe(audio, *args, **kwargs)
         from .multichannel import transcribe_multichannel
@@ -308,12 +317,35 @@ class BatchedInferencePipeline:
 
     def iter_many(self, audios, *, batch_size: int = 8, on_error: str = "return", **kwargs):
         """Many files as ONE job whose decode groups mix files (whisperlive_amd/many_files.py): yields (index, segments, info) per
-        file — what `transcribe(audios[index], ...)` returns, the segments as a list — or (index, exception, None) for a damaged file."""
+        file — what `transcribe(audios[index], ...)` returns, the segments as a list — or (index, exception, None) for a damaged file.
+        target_language= (one code, or a list with a code or None per file) with translator=: each file's segments carry
+        `.translation`, one translation job per file as it finishes."""
         from .many_files import iter_many
-        return iter_many(self, audios, batch_size=batch_size, on_error=on_error, **kwargs)
+        target_language, translator = kwargs.pop("target_language", None), kwargs.pop("translator", None)
+        if target_language is None:
+            return iter_many(self, audios, batch_size=batch_size, on_error=on_error, **kwargs)
+        from .file_translation import check_target_language, per_file_languages, translated_job
+        if isinstance(audios, (str, bytes, bytearray, np.ndarray)) or hasattr(audios, "read"):
+            raise TypeError("transcribe_many takes a sequence of files or waveforms; one file goes to transcribe")
+        audios = list(audios)
+        languages = per_file_languages(target_language, len(audios))
+        for lang in {x for x in languages if x is not None}:
+            check_target_language(translator, lang)
+        if translator is None and any(x is not None for x in languages):
+            raise ValueError("target_language needs a translator")
+        return translated_job(iter_many(self, audios, batch_size=batch_size, on_error=on_error, **kwargs), languages, translator)
 
     def transcribe_many(self, audios, *, batch_size: int = 8, on_error: str = "return", **kwargs):
         """`iter_many` to the end -> [(segments, info) or (exception, None)] in input order"""
+        if kwargs.get("target_language") is not None:
+            audios = list(audios) if isinstance(audios, (list, tuple)) or hasattr(audios, "__next__") else audios
+            job = self.iter_many(audios, batch_size=batch_size, on_error=on_error, **kwargs)
+            out: list = [None] * len(audios)
+            for index, segments, info in job:
+                out[index] = (segments, info)
+            return out
+        kwargs.pop("target_language", None)
+        kwargs.pop("translator", None)
         from .many_files import transcribe_many
         return transcribe_many(self, audios, batch_size=batch_size, on_error=on_error, **kwargs)
 

@@ -38,4 +38,42 @@ void launch_mt_kv_append(const half_t* qkv, long ldqkv, int rows, int d, half_t*
 void launch_mt_topk(const float* logits, int rows, int vocab, const int* ban, const int* nban, int ban_ld, int k,
                     float* chunk_scratch, int* chunk_idx_scratch, float* out_val, int* out_idx, hipStream_t s);
 
+// ---- device search (mt_search.hip): Hugging Face's _beam_search / greedy bookkeeping of mt_engine.hip run_generate, statement for
+// statement, on state that stays on the device for a whole generate. Iteration i of the search (i = 0 .. max_length - 2) feeds position
+// t = i with cur_len = i + 1 tokens per row; sequences, finished sequences and the ancestry table are double-buffered on the parity
+// of i (iteration i reads buffer i & 1 and writes the other; greedy search keeps sequences in buffer 0).
+struct MtSearchParams {
+    int B, R, ML, T, V;                 // items, beams per item, max_length (the row stride of the sequence tables), ancestry stride, vocabulary
+    int eos, pad, start, forced_eos;    // forced_eos < 0: none
+    int nng, early_stopping, lp_positive, ban_ld;
+};
+struct MtSearchState {
+    int* run[2];                        // running sequences [rows][ML], decoder start included
+    int* fin[2];                        // finished sequences [rows][ML]
+    float *run_score, *fin_score;       // [rows]
+    int *fin_len, *fin_done;            // [rows]
+    int *unsat, *item_done;             // [B]
+    float* greedy_score;                // [B]
+    int* anc[2];                        // beam ancestry [rows][T]
+    int *tok, *pos;                     // next step's decoder input [rows]
+    MtAttnGroup* gself;                 // next step's self-attention groups [rows]: {r, 1, 0, t + 1}
+    int *ban, *nban;                    // no_repeat_ngram bans of the next top-k [rows][ban_ld], [rows]
+    const float* lp;                    // lp[len] = (float)pow(len, length_penalty), len = 1 .. ML (host-made: the device only divides)
+    int* ctl;                           // device words: done, arrival counter, step flags, cur_len, decode steps
+    int* h_done;                        // PINNED host words: done, cur_len, decode steps — stored after the results below
+    int* h_n;                           // pinned results [B]: generated tokens (decoder start and final EOS excluded)
+    float* h_score;                     // pinned results [B]
+    int* h_tok;                         // pinned results [B][ML]
+};
+// resets the whole state for a generate of P.B items (rows = B * R workgroups)
+void launch_mt_search_init(const MtSearchParams& P, const MtSearchState& S, hipStream_t s);
+// ban / nban of iteration i from the running sequences: the rule, order and ban_ld truncation of run_generate's banned_ngrams
+void launch_mt_search_bans(const MtSearchParams& P, const MtSearchState& S, int i, hipStream_t s);
+// iteration i of the search over the top-k candidates tk_val / tk_idx [rows][K] (K = 1 greedy, 2 R beam search; unread when
+// `force_now`: the forced EOS at max_length - 1 takes no decode step). One workgroup per item; the workgroup that arrives last
+// evaluates the group's stop condition and, when the generate is over, stores the results and then the done words. A launch that
+// finds the group done changes nothing.
+void launch_mt_search_step(const MtSearchParams& P, const MtSearchState& S, const float* tk_val, const int* tk_idx, int i,
+                           int force_now, hipStream_t s);
+
 }  // namespace wlx

@@ -55,6 +55,13 @@ struct MtSlot {
     std::vector<int> src_off, src_len;
     float enc_ms = 0.f, dec_ms = 0.f;
     int steps = 0;
+    // wlx_mt_debug_search: host logits [steps][rows][vocab] that stand in for the network pass of run_generate's steps
+    const float* inject = nullptr;
+    // device search (mt_search.hip; wlx_mt_translate_many): state of one generate, allocated at the slot's first use
+    bool has_search = false;
+    MtSearchState sd{};
+    float *d_lp = nullptr, *h_lp = nullptr;
+    hipEvent_t ev_blk = nullptr;
 };
 
 }  // namespace
@@ -151,20 +158,15 @@ int encode(wlx_mt* m, MtSlot* s, int batch, const int32_t* src, const int32_t* l
     return WLX_OK;
 }
 
-// one decoder step for `rows` rows (R per item over the slot's encoded items) at position t: logits -> s->logits.
-// h_tok / h_pos / h_anc of the rows are set by the caller.
-int decode_step(wlx_mt* m, MtSlot* s, int rows, int R, int t) {
+// the launches of one decoder step for `rows` rows (R per item over the slot's encoded items) at position t: logits -> s->logits.
+// Every table it reads is in device memory: tokens, positions, the ancestry table and the self-attention groups of the rows
+// (d_gcross: the slot's, constant over a generate).
+int decode_launch(wlx_mt* m, MtSlot* s, int rows, int R, int t, const int* d_tok, const int* d_pos, const int* d_anc,
+                  const MtAttnGroup* d_gself) {
     const wlx_mt_spec& sp = m->spec;
     const int d = sp.d_model, F = sp.ffn, H = sp.n_heads, Ld = sp.dec_layers, T = s->tmax;
     hipStream_t st = s->st;
-    for (int r = 0; r < rows; ++r) s->h_gself[r] = MtAttnGroup{r, 1, 0, t + 1};
-    for (int i = 0; i < s->n_items; ++i) s->h_gcross[i] = MtAttnGroup{i * R, R, s->src_off[i], s->src_len[i]};
-    CK(hipMemcpyAsync(s->d_tok, s->h_tok, rows * sizeof(int), hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(s->d_pos, s->h_pos, rows * sizeof(int), hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(s->d_anc, s->h_anc, (size_t)rows * T * sizeof(int), hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(s->d_gself, s->h_gself, rows * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(s->d_gcross, s->h_gcross, s->n_items * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
-    launch_mt_embed(s->d_tok, s->d_pos, rows, m->E, d / 32, m->embed_scale, m->sinpos, d, s->xd, st);
+    launch_mt_embed(d_tok, d_pos, rows, m->E, d / 32, m->embed_scale, m->sinpos, d, s->xd, st);
     const long cache_layer = (long)s->rows_cap * T * d;
     for (int l = 0; l < Ld; ++l) {
         const LayerW& w = m->dec[l];
@@ -173,7 +175,7 @@ int decode_step(wlx_mt* m, MtSlot* s, int rows, int R, int t) {
         launch_layernorm_f16(s->xd, d, w.ln1_g, w.ln1_b, s->hd, d, rows, d, st);
         gemm(s->hd, d, rows, w.Wqkv, d, 3 * d, w.bqkv, GEMM_STORE_F16, s->qkvd, 3 * d, nullptr, 0, st);
         launch_mt_kv_append(s->qkvd, 3 * d, rows, d, kc, vc, T, t, st);
-        launch_mt_attn(s->qkvd, 3 * d, kc, d, vc, d, s->attd, d, s->d_gself, rows, 1, H, s->d_anc, T, T, st);
+        launch_mt_attn(s->qkvd, 3 * d, kc, d, vc, d, s->attd, d, d_gself, rows, 1, H, d_anc, T, T, st);
         gemm(s->attd, d, rows, w.Wo, d, d, w.bo, GEMM_RESID_F32, nullptr, 0, s->xd, d, st);
         launch_layernorm_f16(s->xd, d, w.ln2_g, w.ln2_b, s->hd, d, rows, d, st);
         gemm(s->hd, d, rows, w.Wcq, d, d, w.bcq, GEMM_STORE_F16, s->qd, d, nullptr, 0, st);
@@ -191,6 +193,26 @@ int decode_step(wlx_mt* m, MtSlot* s, int rows, int R, int t) {
     gemm(s->hd, d, rows, m->E, d, sp.vocab, nullptr, GEMM_RESID_F32, nullptr, 0, s->logits, sp.vocab, st);
     CK(hipGetLastError());
     return WLX_OK;
+}
+
+// one decoder step with the host search: h_tok / h_pos / h_anc of the rows are set by the caller and uploaded here.
+// With injected logits (wlx_mt_debug_search) the step's logits are copied in and no network pass runs.
+int decode_step(wlx_mt* m, MtSlot* s, int rows, int R, int t) {
+    const int T = s->tmax;
+    hipStream_t st = s->st;
+    if (s->inject) {
+        const size_t n = (size_t)rows * m->spec.vocab;
+        CK(hipMemcpyAsync(s->logits, s->inject + (size_t)t * n, n * sizeof(float), hipMemcpyHostToDevice, st));
+        return WLX_OK;
+    }
+    for (int r = 0; r < rows; ++r) s->h_gself[r] = MtAttnGroup{r, 1, 0, t + 1};
+    for (int i = 0; i < s->n_items; ++i) s->h_gcross[i] = MtAttnGroup{i * R, R, s->src_off[i], s->src_len[i]};
+    CK(hipMemcpyAsync(s->d_tok, s->h_tok, rows * sizeof(int), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_pos, s->h_pos, rows * sizeof(int), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_anc, s->h_anc, (size_t)rows * T * sizeof(int), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_gself, s->h_gself, rows * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->d_gcross, s->h_gcross, s->n_items * sizeof(MtAttnGroup), hipMemcpyHostToDevice, st));
+    return decode_launch(m, s, rows, R, t, s->d_tok, s->d_pos, s->d_anc, s->d_gself);
 }
 
 // top-k candidates of the step's rows -> pinned host h_tk_val / h_tk_idx [rows][k]; waits for the stream
@@ -407,6 +429,135 @@ int run_generate(wlx_mt* m, MtSlot* s, const wlx_mt_gen_opts& o, int32_t* tokens
     return WLX_OK;
 }
 
+// ---- the same generate with the search on the device (mt_search.hip): nothing is uploaded or downloaded per step. The host enqueues
+// the iterations in blocks of `block` steps and, after each block, waits for an event and reads the pinned done word the search
+// kernel stored behind the results. Iterations enqueued past the end find the group done: their decode steps compute on scratch (the logits,
+// the caches at positions no later launch of this generate reads) and their search launches change nothing.
+// The block length kept is 1, after measuring 1, 2, 4 and 8 on generates of 2-5 and of 31 steps (DESIGN.md §23,
+// scripts/file_translate_time.py): a look at the done word costs ~4 us of a ~500 us step, a decode step enqueued past the end a whole
+// step, so a block of B saves (1 - 1/B) x 0.8 % per step and wastes (B - 1) / 2 steps per group: B = 2 pays from ~125 steps on, B = 4
+// from ~250. What the device search saves is the five uploads, the two downloads and the host bookkeeping of a step, not the wait.
+constexpr int MT_STEP_BLOCK = 1;
+int step_block_default() {
+    static const int v = [] {
+        const char* e = wlx_ab("WLX_MT_STEP_BLOCK");      // (another block length; read by libwlx_ab.so only: common.h)
+        const int n = e ? atoi(e) : 0;
+        return n >= 1 ? n : MT_STEP_BLOCK;
+    }();
+    return v;
+}
+
+// the search state of a slot for `rows` rows of `B` items (S.ban / S.nban are the slot's d_ban / d_nban). The buffers join the slot's
+// free lists only when all of them exist: an allocation that fails midway frees what the call got, so a retry starts from nothing.
+int search_alloc(MtSlot* s, int rows, int B) {
+    if (s->has_search) return WLX_OK;
+    std::vector<void*> A, H;
+    MtSearchState S{};
+    float *d_lp = nullptr, *h_lp = nullptr;
+    hipEvent_t ev = nullptr;
+    const size_t T = s->tmax;
+    const int rc = [&]() -> int {
+        for (int k = 0; k < 2; ++k) {
+            CKR(dalloc(A, &S.run[k], rows * T, false));
+            CKR(dalloc(A, &S.fin[k], rows * T, false));
+            CKR(dalloc(A, &S.anc[k], rows * T, false));
+        }
+        CKR(dalloc(A, &S.run_score, rows, false));
+        CKR(dalloc(A, &S.fin_score, rows, false));
+        CKR(dalloc(A, &S.fin_len, rows, false));
+        CKR(dalloc(A, &S.fin_done, rows, false));
+        CKR(dalloc(A, &S.unsat, B, false));
+        CKR(dalloc(A, &S.item_done, B, false));
+        CKR(dalloc(A, &S.greedy_score, B, false));
+        CKR(dalloc(A, &S.tok, rows, false));
+        CKR(dalloc(A, &S.pos, rows, false));
+        CKR(dalloc(A, &S.gself, rows, false));
+        CKR(dalloc(A, &S.ctl, 8, true));
+        CKR(dalloc(A, &d_lp, T + 1, false));
+        CKR(halloc(H, &h_lp, T + 1));
+        CKR(halloc(H, &S.h_done, 4));
+        CKR(halloc(H, &S.h_n, B));
+        CKR(halloc(H, &S.h_score, B));
+        CKR(halloc(H, &S.h_tok, B * T));
+        CK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        return WLX_OK;
+    }();
+    if (rc != WLX_OK) {
+        for (void* p : A) (void)hipFree(p);
+        for (void* p : H) (void)hipHostFree(p);
+        return rc;
+    }
+    s->allocs.insert(s->allocs.end(), A.begin(), A.end());
+    s->host_allocs.insert(s->host_allocs.end(), H.begin(), H.end());
+    S.ban = s->d_ban;
+    S.nban = s->d_nban;
+    S.lp = d_lp;
+    s->sd = S;
+    s->d_lp = d_lp;
+    s->h_lp = h_lp;
+    s->ev_blk = ev;
+    s->has_search = true;
+    return WLX_OK;
+}
+
+// logits_of(i, &ptr): enqueue whatever produces the logits [rows][V] of iteration i on the slot's stream and point at them.
+// Results: s->sd.h_tok [B][ML] / h_n / h_score, final when this returns. *steps_out: decode steps the search ran.
+template <class LogitsFn>
+int device_generate(MtSlot* s, const wlx_mt_spec& sp, const wlx_mt_gen_opts& o, int B, int block, int* steps_out, LogitsFn&& logits_of) {
+    const int R = o.num_beams, rows = B * R, ML = o.max_length, K = R == 1 ? 1 : 2 * R;
+    const bool forced = o.forced_eos_token_id >= 0;
+    MtSearchParams P{};
+    P.B = B; P.R = R; P.ML = ML; P.T = s->tmax; P.V = sp.vocab;
+    P.eos = sp.eos_id; P.pad = sp.pad_id; P.start = sp.decoder_start_id; P.forced_eos = forced ? o.forced_eos_token_id : -1;
+    P.nng = o.no_repeat_ngram_size; P.early_stopping = o.early_stopping; P.lp_positive = o.length_penalty > 0.f; P.ban_ld = s->ban_ld;
+    const MtSearchState& S = s->sd;
+    hipStream_t st = s->st;
+    s->h_lp[0] = 1.f;
+    for (int len = 1; len <= ML; ++len) s->h_lp[len] = (float)pow((double)len, (double)o.length_penalty);
+    CK(hipMemcpyAsync(s->d_lp, s->h_lp, (ML + 1) * sizeof(float), hipMemcpyHostToDevice, st));
+    volatile int* hd = S.h_done;
+    hd[0] = 0; hd[1] = 0; hd[2] = 0;
+    launch_mt_search_init(P, S, st);
+    const bool bans = P.nng > 0;
+    const int iters = ML - 1;
+    for (int i = 0; i < iters; ++i) {
+        const bool force_now = forced && i == ML - 2;
+        if (!force_now) {
+            if (bans) launch_mt_search_bans(P, S, i, st);
+            const float* lg = nullptr;
+            CKR(logits_of(i, &lg));
+            launch_mt_topk(lg, rows, sp.vocab, bans ? S.ban : nullptr, bans ? S.nban : nullptr, s->ban_ld, K, s->tk_scratch, s->tk_cidx,
+                           s->tk_val, s->tk_idx, st);
+        }
+        launch_mt_search_step(P, S, s->tk_val, s->tk_idx, i, force_now ? 1 : 0, st);
+        if ((i + 1) % block == 0 || i == iters - 1) {
+            CK(hipGetLastError());
+            CK(hipEventRecord(s->ev_blk, st));
+            CK(hipEventSynchronize(s->ev_blk));
+            if (hd[0]) break;
+        }
+    }
+    if (!hd[0]) return set_error(WLX_ERR_HIP, "the device search did not finish within max_length %d", ML);
+    if (steps_out) *steps_out = hd[2];
+    return WLX_OK;
+}
+
+int generate_on_device(wlx_mt* m, MtSlot* s, const wlx_mt_gen_opts& o, int block) {
+    const int B = s->n_items, R = o.num_beams, rows = B * R;
+    for (int i = 0; i < B; ++i) s->h_gcross[i] = MtAttnGroup{i * R, R, s->src_off[i], s->src_len[i]};
+    CK(hipMemcpyAsync(s->d_gcross, s->h_gcross, B * sizeof(MtAttnGroup), hipMemcpyHostToDevice, s->st));
+    CK(hipEventRecord(s->ev[2], s->st));
+    int steps = 0;
+    const MtSearchState& S = s->sd;
+    CKR(device_generate(s, m->spec, o, B, block, &steps, [&](int i, const float** lg) -> int {
+        *lg = s->logits;
+        return decode_launch(m, s, rows, R, i, S.tok, S.pos, S.anc[i & 1], S.gself);
+    }));
+    CK(hipEventRecord(s->ev[3], s->st));
+    s->steps += steps;
+    return WLX_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ entry points
@@ -482,6 +633,7 @@ static void slot_free(MtSlot* s) {
     for (void* p : s->allocs) (void)hipFree(p);
     for (void* p : s->host_allocs) (void)hipHostFree(p);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    if (s->ev_blk) (void)hipEventDestroy(s->ev_blk);
     if (s->st) (void)hipStreamDestroy(s->st);
     delete s;
 }
@@ -627,7 +779,145 @@ extern "C" int32_t wlx_mt_translate(wlx_mt* m, int32_t slot, int32_t batch, cons
     return WLX_OK;
 }
 
+extern "C" int32_t wlx_mt_translate_many(wlx_mt* m, int32_t slot, int32_t n, const int32_t* src_ids, const int32_t* src_lens,
+                                         int32_t src_stride, const wlx_mt_gen_opts* opts, int32_t* tokens_out, int32_t tokens_stride,
+                                         int32_t* n_tokens_out, float* scores_out) {
+    if (!m || !src_ids || !src_lens || !tokens_out || !n_tokens_out || tokens_stride < 1 || src_stride < 1)
+        return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_MT_MANY_MAX) return set_error(WLX_ERR_ARG, "n %d outside 1..%d", n, WLX_MT_MANY_MAX);
+    MtSlot* s = slot_of(m, slot);
+    if (!s) return set_error(WLX_ERR_ARG, "no translation slot %d", slot);
+    Busy busy(s);
+    if (!busy.ok) return set_error(WLX_ERR_STATE, "translation slot %d is busy (a call is in flight)", slot);
+    CKR(check_opts(m, s, opts));
+    for (int i = 0; i < n; ++i) {       // everything encode() would refuse, before the first group is launched
+        const int S = src_lens[i];
+        if (S < 1 || S > s->max_src || S > src_stride)
+            return set_error(WLX_ERR_ARG, "source %d: length %d outside 1..%d", i, S, std::min(s->max_src, (int)src_stride));
+        for (int j = 0; j < S; ++j) {
+            const int tok = src_ids[(long)i * src_stride + j];
+            if (tok < 0 || tok >= m->spec.vocab) return set_error(WLX_ERR_ARG, "source %d: token %d outside the vocabulary", i, tok);
+        }
+    }
+    CK(hipSetDevice(m->device));
+    CKR(search_alloc(s, s->rows_cap, s->B));
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int z) { return src_lens[a] < src_lens[z]; });
+    const int ML = opts->max_length, block = step_block_default();
+    std::vector<int32_t> ids, lens;
+    s->steps = 0;
+    for (int g0 = 0; g0 < n;) {
+        // a group: the next sources in length order, at most max_batch of them and no more tokens than the slot's source buffers hold
+        int g1 = g0, ntok = 0, stride = 0;
+        while (g1 < n && g1 - g0 < s->B && ntok + src_lens[order[g1]] <= s->src_cap) {
+            ntok += src_lens[order[g1]];
+            stride = std::max(stride, (int)src_lens[order[g1]]);
+            ++g1;
+        }
+        const int B = g1 - g0;
+        ids.assign((size_t)B * stride, 0);
+        lens.resize(B);
+        for (int k = 0; k < B; ++k) {
+            const int i = order[g0 + k];
+            lens[k] = src_lens[i];
+            std::copy(src_ids + (long)i * src_stride, src_ids + (long)i * src_stride + lens[k], ids.begin() + (size_t)k * stride);
+        }
+        CKR(encode(m, s, B, ids.data(), lens.data(), stride));
+        CKR(generate_on_device(m, s, *opts, block));
+        const MtSearchState& S = s->sd;
+        for (int k = 0; k < B; ++k) {
+            const int i = order[g0 + k];
+            const int cnt = std::min(S.h_n[k], (int)tokens_stride);
+            for (int j = 0; j < cnt; ++j) tokens_out[(long)i * tokens_stride + j] = S.h_tok[(long)k * ML + j];
+            n_tokens_out[i] = cnt;
+            if (scores_out) scores_out[i] = S.h_score[k];
+        }
+        g0 = g1;
+    }
+    CK(hipStreamSynchronize(s->st));      // (the iterations enqueued past the end of the last group)
+    float a = 0.f, b = 0.f;
+    if (hipEventElapsedTime(&a, s->ev[0], s->ev[1]) == hipSuccess) s->enc_ms = a;
+    if (hipEventElapsedTime(&b, s->ev[2], s->ev[3]) == hipSuccess) s->dec_ms = b;
+    (void)hipGetLastError();
+    return WLX_OK;
+}
+
 // ---- test / profiling hooks
+extern "C" int32_t wlx_mt_debug_search(int32_t device, const float* logits, int32_t steps, int32_t batch, const wlx_mt_gen_opts* opts,
+                                       int32_t vocab, int32_t pad_id, int32_t eos_id, int32_t start_id, int32_t ban_ld,
+                                       int32_t step_block, int32_t use_device, int32_t* tokens_out, int32_t tokens_stride,
+                                       int32_t* n_tokens_out, float* scores_out, int32_t* steps_run_out) {
+    if (!logits || !opts || !tokens_out || !n_tokens_out || tokens_stride < 1) return set_error(WLX_ERR_ARG, "null argument");
+    if (batch < 1 || batch > 64) return set_error(WLX_ERR_ARG, "batch %d outside 1..64", batch);
+    if (vocab < 2 || vocab > WLX_MT_CHUNKS * 4096) return set_error(WLX_ERR_ARG, "vocab %d outside 2..%d", vocab, WLX_MT_CHUNKS * 4096);
+    if (pad_id < 0 || pad_id >= vocab || eos_id < 0 || eos_id >= vocab || start_id < 0 || start_id >= vocab)
+        return set_error(WLX_ERR_ARG, "special ids outside the vocabulary");
+    if (ban_ld < 1 || ban_ld > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "ban_ld %d outside 1..%d", ban_ld, WLX_T_TEXT);
+    if (step_block < 0) return set_error(WLX_ERR_ARG, "step_block < 0");
+    wlx_mt fm;
+    fm.spec.vocab = vocab; fm.spec.pad_id = pad_id; fm.spec.eos_id = eos_id; fm.spec.decoder_start_id = start_id;
+    fm.spec.max_positions = WLX_T_TEXT;
+    MtSlot* s = new MtSlot();
+    s->B = batch; s->R = 16; s->ban_ld = ban_ld; s->n_items = batch;
+    int rc = [&]() -> int {
+        CKR(check_opts(&fm, s, opts));
+        const int R = opts->num_beams, rows = batch * R, V = vocab, T = s->tmax;
+        const int need = opts->max_length - 1 - (opts->forced_eos_token_id >= 0 ? 1 : 0);
+        if (steps < 1 || steps < need) return set_error(WLX_ERR_ARG, "%d steps of logits, max_length %d may take %d", steps, opts->max_length, need);
+        int ndev = 0;
+        CK(hipGetDeviceCount(&ndev));
+        if (device < 0 || device >= ndev) return set_error(WLX_ERR_ARG, "device %d outside 0..%d", device, ndev - 1);
+        CK(hipSetDevice(device));
+        CK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+        for (auto& e : s->ev) CK(hipEventCreate(&e));
+        s->rows_cap = rows;
+        auto& A = s->allocs;
+        auto& H = s->host_allocs;
+        CKR(dalloc(A, &s->logits, (size_t)rows * V, false));
+        CKR(dalloc(A, &s->tk_scratch, (size_t)rows * WLX_MT_CHUNKS * (2 + WLX_MT_MAXK), false));
+        CKR(dalloc(A, &s->tk_cidx, (size_t)rows * WLX_MT_CHUNKS * WLX_MT_MAXK, false));
+        CKR(dalloc(A, &s->tk_val, (size_t)rows * WLX_MT_MAXK, false));
+        CKR(dalloc(A, &s->tk_idx, (size_t)rows * WLX_MT_MAXK, false));
+        CKR(dalloc(A, &s->d_ban, (size_t)rows * ban_ld, false));
+        CKR(dalloc(A, &s->d_nban, rows, false));
+        if (!use_device) {
+            CKR(halloc(H, &s->h_tok, rows));
+            CKR(halloc(H, &s->h_pos, rows));
+            CKR(halloc(H, &s->h_anc, (size_t)rows * T));
+            CKR(halloc(H, &s->h_ban, (size_t)rows * ban_ld));
+            CKR(halloc(H, &s->h_nban, rows));
+            CKR(halloc(H, &s->h_tk_idx, (size_t)rows * WLX_MT_MAXK));
+            CKR(halloc(H, &s->h_tk_val, (size_t)rows * WLX_MT_MAXK));
+            s->inject = logits;
+            CKR(run_generate(&fm, s, *opts, tokens_out, tokens_stride, n_tokens_out, scores_out));
+            CK(hipStreamSynchronize(s->st));
+            if (steps_run_out) *steps_run_out = s->steps;
+            return WLX_OK;
+        }
+        CKR(search_alloc(s, rows, batch));
+        float* dl = nullptr;
+        const size_t per = (size_t)rows * V;
+        CKR(dalloc(A, &dl, per * steps, false));
+        CK(hipMemcpyAsync(dl, logits, per * steps * sizeof(float), hipMemcpyHostToDevice, s->st));
+        int ran = 0;
+        CKR(device_generate(s, fm.spec, *opts, batch, step_block > 0 ? step_block : step_block_default(), &ran,
+                            [&](int i, const float** lg) -> int { *lg = dl + per * i; return WLX_OK; }));
+        CK(hipStreamSynchronize(s->st));
+        const MtSearchState& S = s->sd;
+        for (int b = 0; b < batch; ++b) {
+            const int cnt = std::min(S.h_n[b], (int)tokens_stride);
+            for (int j = 0; j < cnt; ++j) tokens_out[(long)b * tokens_stride + j] = S.h_tok[(long)b * opts->max_length + j];
+            n_tokens_out[b] = cnt;
+            if (scores_out) scores_out[b] = S.h_score[b];
+        }
+        if (steps_run_out) *steps_run_out = ran;
+        return WLX_OK;
+    }();
+    slot_free(s);
+    return rc;
+}
+
 extern "C" int32_t wlx_mt_debug_encode(wlx_mt* m, int32_t slot, int32_t batch, const int32_t* src_ids, const int32_t* src_lens,
                                        int32_t src_stride, float* out, int64_t cap_floats) {
     if (!m || !out) return set_error(WLX_ERR_ARG, "null argument");

@@ -146,13 +146,19 @@ def _words(seg) -> list:
     return [{"word": w.word, "start": w.start, "end": w.end, "probability": w.probability} for w in seg.words]
 
 
-def render_subtitles(segments, response_format: str) -> str:
-    """A segment that carries a channel (a multichannel request) has its cue text prefixed `[ch N] `."""
+def _shown(seg, translated: bool) -> str:
+    """the text a response shows for a segment: its translation for a request with target_language, else its text"""
+    return (seg.translation if translated else seg.text).strip()
+
+
+def render_subtitles(segments, response_format: str, translated: bool = False) -> str:
+    """A segment that carries a channel (a multichannel request) has its cue text prefixed `[ch N] `. translated: the cues carry the
+    segments' translations (file_translation.translate_segments), on the source's times."""
     output = []
     for i, seg in enumerate(segments, 1):
         start, end = _stamp(seg.start), _stamp(seg.end)
         ch = getattr(seg, "channel", None)
-        cue = ("" if ch is None else f"[ch {ch}] ") + seg.text.strip()
+        cue = ("" if ch is None else f"[ch {ch}] ") + _shown(seg, translated)
         if response_format == "srt":
             output.append(f"{i}\n{start.replace('.', ',')} --> {end.replace('.', ',')}\n{cue}\n")
         else:
@@ -160,9 +166,10 @@ def render_subtitles(segments, response_format: str) -> str:
     return "\n".join(output)
 
 
-def render_text(segments, multichannel: bool = False) -> str:
-    """the `text` of a response: the segments joined with spaces; a multichannel request gets one line per segment, in time order"""
-    return ("\n" if multichannel else " ").join([s.text.strip() for s in segments])
+def render_text(segments, multichannel: bool = False, translated: bool = False) -> str:
+    """the `text` of a response: the segments joined with spaces; a multichannel request gets one line per segment, in time order.
+    translated: the same of the segments' translations."""
+    return ("\n" if multichannel else " ").join([_shown(s, translated) for s in segments])
 
 
 def parse_bool_field(value: Optional[str], name: str) -> bool:
@@ -403,8 +410,13 @@ class RestServer:
                  cors_origins: Optional[str] = None, rate_limit_rpm: int = 0, model_factory: Optional[Callable] = None,
                  max_body_bytes: int = 512 << 20, diarization_model: Optional[str] = None,
                  embedder_factory: Optional[Callable] = None, file_batch_size: int = 0, file_batch_window_ms: int = 0,
-                 pipeline_factory: Optional[Callable] = None):
+                 pipeline_factory: Optional[Callable] = None, translation_model: Optional[str] = None,
+                 translator_factory: Optional[Callable] = None):
         self.host, self.port, self.model = host, int(port), model
+        # a small100 / M2M100 checkpoint (a directory or a hub id, resolved as the WebSocket server resolves its own): requests may then
+        # carry target_language. translator_factory: (directory, device index) -> translator; None = translation.shared_translator
+        self.translation_model = translation_model
+        self.translator_factory = translator_factory
         # 0: a file is decoded one window after another (WhisperModelHIP.transcribe). N > 0: the GPU's shared transcriber is built with
         # max_batch = N and a file goes through BatchedInferencePipeline, N speech chunks per decode step
         self.file_batch_size = int(file_batch_size)
@@ -542,6 +554,24 @@ class RestServer:
         request's thread, where the single route would have raised it. Nothing is left for `resident_file_audio` after a pooled job
         (many_files.py), so speaker labels fall back to the second decode; requests with known speakers are not pooled at all."""
         return self._batchers.get(device_index, self.batcher).submit(transcriber, data, dict(language=language, initial_prompt=initial_prompt, hotwords=hotwords), shared)
+
+    def translator_for(self, device_index: int, target_language: str):
+        """the GPU's shared translator for a request with target_language; ValueError = a 400 (no model configured, or a language
+        code the model does not know)"""
+        from .file_translation import check_target_language
+        if not self.translation_model:
+            raise ValueError("target_language: this server has no translation model (start it with --translation_model DIR)")
+        if self.translator_factory is not None:
+            translator = self.translator_factory(self.translation_model, device_index)
+        else:
+            from .artifacts import resolve_translation_model
+            from .translation import shared_translator
+            directory = resolve_translation_model(self.translation_model)
+            if directory is None:
+                raise ValueError(f"target_language: the translation model {self.translation_model!r} cannot be resolved on this server")
+            translator = shared_translator(directory, device_index)
+        check_target_language(translator, target_language)
+        return translator
 
     @staticmethod
     def resident_audio(transcriber):
@@ -750,6 +780,7 @@ class _Handler(BaseHTTPRequestHandler):
             raise _HttpError(400, {"error": "stream must be a boolean"})
         multichannel = parse_bool_field(one("multichannel", "false"), "multichannel")
         diarize = parse_bool_field(one("diarize", "false"), "diarize")
+        target_language = (one("target_language") or "").strip() or None
         try:
             max_speakers = int(one("max_speakers", "0") or "0")
         except ValueError:
@@ -767,7 +798,7 @@ class _Handler(BaseHTTPRequestHandler):
         if stream_s in _TRUE:
             if multichannel:     # the segments of a multichannel file are ordered only when its last group is done: nothing to stream
                 raise _HttpError(400, {"error": "multichannel cannot be combined with stream: send the request without stream"})
-            return self._stream(file, language, prompt, temperature, want_words)
+            return self._stream(file, language, prompt, temperature, want_words, target_language)
 
         ignored_params = []
         if chunking_strategy:
@@ -786,6 +817,12 @@ class _Handler(BaseHTTPRequestHandler):
         transcriber = None
         try:
             device_index = rest._next_device()
+            translator = None
+            if target_language is not None:         # refused before the file is decoded
+                try:
+                    translator = rest.translator_for(device_index, target_language)
+                except ValueError as e:
+                    raise _HttpError(400, {"error": str(e)})
             transcriber = rest.transcriber_for(device_index)
             mc = {"multichannel": True} if multichannel else {}
             if rest.batcher is not None and not multichannel and not known_speaker_names and not known_speaker_references and not diarize:
@@ -796,15 +833,23 @@ class _Handler(BaseHTTPRequestHandler):
                                                       temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)
             segments = list(segments or [])
             text = render_text(segments, multichannel)
+            translated = target_language is not None
+            if translated:      # the whole transcript as one translation job, whichever route transcribed it
+                from .file_translation import translate_segments
+                segments = translate_segments(segments, translator, target_language)
+                translation = render_text(segments, multichannel, translated=True)
             if response_format == "text":
                 wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
-                return self._text(200, text)
+                return self._text(200, translation if translated else text)
             if response_format == "json":
                 wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
-                return self._json(200, {"text": text})
+                return self._json(200, {"text": text, "translation": translation} if translated else {"text": text})
             if response_format == "verbose_json":
                 verbose = {"task": "transcribe", "language": info.language if info else language,
                            "duration": info.duration if info else 0.0, "text": text, "segments": []}
+                if translated:
+                    verbose["target_language"] = target_language
+                    verbose["translation"] = translation
                 speaker_labels = {}
                 try:
                     rest_diarizer = rest.create_rest_diarizer(known_speaker_names, known_speaker_references, device_index)
@@ -835,6 +880,8 @@ class _Handler(BaseHTTPRequestHandler):
                     seg_dict = {"id": seg.id, "seek": seg.seek, "start": seg.start, "end": seg.end, "text": seg.text.strip(),
                                 "tokens": seg.tokens, "temperature": seg.temperature, "avg_logprob": seg.avg_logprob,
                                 "compression_ratio": seg.compression_ratio, "no_speech_prob": seg.no_speech_prob}
+                    if translated:
+                        seg_dict["translation"] = seg.translation.strip()
                     if multichannel:
                         seg_dict["channel"] = seg.channel
                     if index in speaker_labels:
@@ -849,7 +896,7 @@ class _Handler(BaseHTTPRequestHandler):
                 wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
                 return self._json(200, verbose)
             wl_metrics.track_rest_request(endpoint="transcriptions", status=200)
-            return self._text(200, render_subtitles(segments, response_format))
+            return self._text(200, render_subtitles(segments, response_format, translated))
         except _HttpError:
             raise
         except Exception as e:  # noqa: BLE001 — server.py:853-856
@@ -871,8 +918,17 @@ class _Handler(BaseHTTPRequestHandler):
             except Exception:  # noqa: BLE001
                 logging.exception("rest: release_slot failed")
 
-    def _stream(self, file, language, prompt, temperature, want_words):
-        """server.py:490-537: one `data:` event per segment, `[DONE]` at the end, an error as an event of its own"""
+    def _stream(self, file, language, prompt, temperature, want_words, target_language=None):
+        """server.py:490-537: one `data:` event per segment, `[DONE]` at the end, an error as an event of its own. With
+        target_language the translations follow the last segment in ONE event ({"target_language", "translations": [{id,
+        translation}]}): the transcript is translated as one job, once it is complete."""
+        translator = None
+        if target_language is not None:
+            try:
+                device_index = self.rest._next_device()
+                translator = self.rest.translator_for(device_index, target_language)
+            except ValueError as e:
+                raise _HttpError(400, {"error": str(e)})
         self.send_response(200)
         self.send_header("Content-Type", "text/event-stream; charset=utf-8")
         self.send_header("Cache-Control", "no-cache")
@@ -889,14 +945,22 @@ class _Handler(BaseHTTPRequestHandler):
         transcriber = None
         try:
             try:
-                transcriber = self.rest.transcriber_for(self.rest._next_device())
+                transcriber = self.rest.transcriber_for(device_index if translator is not None else self.rest._next_device())
                 segments, _info = self.rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
                                                             temperature=temperature, word_timestamps=want_words)
+                seen = []
                 for seg in segments or []:
                     seg_dict = {"id": seg.id, "start": seg.start, "end": seg.end, "text": seg.text.strip()}
                     if want_words:
                         seg_dict["words"] = _words(seg)
                     emit(f"data: {json.dumps(seg_dict)}\n\n")
+                    if translator is not None:
+                        seen.append(seg)
+                if translator is not None:
+                    from .file_translation import translate_segments
+                    done = translate_segments(seen, translator, target_language)
+                    emit("data: " + json.dumps({"target_language": target_language, "translations": [
+                        {"id": s.id, "translation": s.translation.strip()} for s in done]}) + "\n\n")
                 emit("data: [DONE]\n\n")
             except (BrokenPipeError, ConnectionResetError):
                 raise
@@ -920,6 +984,8 @@ def main(argv=None):
     ap.add_argument("--rate_limit_rpm", type=int, default=0, help="requests per minute per client IP (0 = unlimited)")
     ap.add_argument("--max_body_mb", type=int, default=512)
     ap.add_argument("--diarization_model", default=None)
+    ap.add_argument("--translation_model", default=None,
+                    help="small100 / M2M100 checkpoint directory (or hub id): requests may then carry target_language")
     ap.add_argument("--metrics_port", type=int, default=0)
     ap.add_argument("--file_batch_size", type=int, default=0,
                     help="speech chunks decoded per step by the batched long-form pipeline (0 = decode a file window after window)")
@@ -933,7 +999,7 @@ def main(argv=None):
     RestServer(a.host, a.port, a.model_path, devices=[int(x) for x in a.devices.split(",") if x != ""], api_key=a.api_key,
                cors_origins=a.cors_origins, rate_limit_rpm=a.rate_limit_rpm, max_body_bytes=a.max_body_mb << 20,
                diarization_model=a.diarization_model, file_batch_size=a.file_batch_size,
-               file_batch_window_ms=a.file_batch_window_ms).serve_forever()
+               file_batch_window_ms=a.file_batch_window_ms, translation_model=a.translation_model).serve_forever()
 
 
 if __name__ == "__main__":

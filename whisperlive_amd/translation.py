@@ -70,6 +70,20 @@ class HipMTEngine:
                                              C.byref(o), toks.ctypes.data_as(i32p), cap, n.ctypes.data_as(i32p), sc.ctypes.data_as(f32p)))
         return [toks[i, :n[i]].tolist() for i in range(len(srcs))], sc.tolist()
 
+    def translate_ids_many(self, srcs: Sequence[Sequence[int]], opts: MTGenOptions) -> Tuple[List[List[int]], List[float]]:
+        """Any number of sources (up to _lib.MT_MANY_MAX, more than max_batch included) as ONE wlx_mt_translate_many job: grouped by
+        length inside the library, searched on the device, results in input order."""
+        ids, lens, stride = self._pack(srcs)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        cap = opts.max_length
+        toks = np.zeros((len(srcs), cap), dtype=np.int32)
+        n = np.zeros(len(srcs), dtype=np.int32)
+        sc = np.zeros(len(srcs), dtype=np.float32)
+        o = self._opts(opts)
+        _lib.check(self.lib.wlx_mt_translate_many(self.h, self.slot, len(srcs), ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), stride,
+                                                  C.byref(o), toks.ctypes.data_as(i32p), cap, n.ctypes.data_as(i32p), sc.ctypes.data_as(f32p)))
+        return [toks[i, :n[i]].tolist() for i in range(len(srcs))], sc.tolist()
+
     def encoder_output(self, srcs: Sequence[Sequence[int]]) -> np.ndarray:
         ids, lens, stride = self._pack(srcs)
         out = np.zeros((int(lens.sum()), self.spec.d_model), dtype=np.float32)
@@ -142,8 +156,50 @@ class HipTranslator:
                     out[i] = self.tokenizer.decode(tk)
         return out
 
+    def _source_ids(self, text: str, tgt_lang: str) -> List[int]:
+        ids = self.tokenizer.encode_source(text, tgt_lang)
+        if len(ids) > self.engine.max_src:
+            ids = ids[:self.engine.max_src - 1] + [ids[-1]]
+        return ids
+
+    def translate_many(self, texts: Sequence[str], tgt_lang: str) -> List[str]:
+        """`translate` for a whole transcript: every non-empty text goes to the engine in ONE translate_ids_many call (jobs of more
+        than _lib.MT_MANY_MAX texts: one call per MT_MANY_MAX). Empty and whitespace-only texts come back unchanged and are not sent."""
+        out: List[str] = list(texts)
+        todo = [(i, t) for i, t in enumerate(texts) if t and t.strip()]
+        with self._mu:
+            for k in range(0, len(todo), _lib.MT_MANY_MAX):
+                chunk = todo[k:k + _lib.MT_MANY_MAX]
+                toks, _ = self.engine.translate_ids_many([self._source_ids(t, tgt_lang) for _, t in chunk], self.options)
+                for (i, _), tk in zip(chunk, toks):
+                    out[i] = self.tokenizer.decode(tk)
+        return out
+
     def close(self):
         self.engine.close()
+
+
+def mt_debug_search(logits: np.ndarray, batch: int, opts: MTGenOptions, pad_id: int, eos_id: int, start_id: int, ban_ld: int = 448,
+                    step_block: int = 0, use_device: bool = True, device: int = 0):
+    """wlx_mt_debug_search: the translation engine's search alone on injected logits [steps][batch * num_beams][vocab] — the host
+    bookkeeping of wlx_mt_translate (use_device=False) or the device search of wlx_mt_translate_many.
+    -> (token lists, scores float32 array, decode steps run)"""
+    lib = _lib.load()
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    steps, rows, vocab = lg.shape
+    if rows != batch * opts.num_beams:
+        raise ValueError(f"logits rows {rows} != batch {batch} x num_beams {opts.num_beams}")
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    cap = opts.max_length
+    toks = np.zeros((batch, cap), dtype=np.int32)
+    n = np.zeros(batch, dtype=np.int32)
+    sc = np.zeros(batch, dtype=np.float32)
+    ran = C.c_int32(-1)
+    o = HipMTEngine._opts(opts)
+    _lib.check(lib.wlx_mt_debug_search(device, lg.ctypes.data_as(f32p), steps, batch, C.byref(o), vocab, pad_id, eos_id, start_id, ban_ld,
+                                       step_block, 1 if use_device else 0, toks.ctypes.data_as(i32p), cap, n.ctypes.data_as(i32p),
+                                       sc.ctypes.data_as(f32p), C.byref(ran)))
+    return [toks[i, :n[i]].tolist() for i in range(batch)], sc, ran.value
 
 
 _shared: Dict[Tuple[str, int], HipTranslator] = {}
