@@ -291,6 +291,36 @@ int32_t wlx_pcm_put_wav(wlx_engine* e, int32_t slot, int32_t item, const void* b
  * max_batch is WLX_ERR_ARG: all before any launch, every item's resident PCM left as it was. */
 int32_t wlx_pcm_put_wav_split(wlx_engine* e, int32_t slot, int32_t first_item, const void* bytes, int64_t n_bytes,
                               wlx_wav_info* info_out, int64_t* n_out);
+/* ---- a WAVE of files in one call (PRODUCT entry point of BatchedInferencePipeline.transcribe_many(wave_put=True); csrc/put_many.hip) ----
+ * Entry k (k < n <= WLX_PUT_MANY_MAX) goes into item first_item + k, in the down-mix (mono) form, under the contract of the single-file
+ * entry point of its kind: results[k].status == WLX_OK: the item holds results[k].n_out samples, BIT-IDENTICAL to what wlx_pcm_put /
+ * wlx_pcm_put_frames / wlx_pcm_put_flac / wlx_pcm_put_wav leaves for that input, and a following wlx_logmel_resident behaves as after
+ * that call. WLX_ERR_ARG, a REFUSED entry (an unserved rate, a stream with served = 0, more than 3600 s, an unknown kind, an entry whose
+ * scratch need alone exceeds the budget below): decided on the host before any launch, the item is left exactly as it was. WLX_ERR_DATA,
+ * a DAMAGED entry: what the probe finds is answered before any launch and leaves the item as it was; a FLAC frame that does not decode
+ * on the device leaves NO PCM resident in that item. In every case the other entries are unaffected.
+ * The CALL returns WLX_OK whenever it ran, even if entries failed. WLX_ERR_ARG before anything is touched: n < 1, n > WLX_PUT_MANY_MAX,
+ * first_item < 0, first_item + n > max_batch, a null pointer. WLX_ERR_NOMEM before any launch. A HIP error is the call's error: no item
+ * of the call keeps PCM.
+ * ONE WAIT: every upload (through the slot's pinned staging blocks; waiting for the event that frees a staging half is the only other
+ * wait, as in wlx_pcm_put_frames) and every launch is enqueued on the slot's stream, the host waits once, then reads the FLAC status
+ * words. Launches per call: one ragged resample launch for all entries that are not waveforms, one frame-decode and one finish launch
+ * for all FLAC entries, one decode launch per ADPCM file (it takes no wait) - a count that depends on the kinds present, not on n.
+ * Scratch (file bytes, frame tables, status words, int32 planes, float32 frames) is the slot's FLAC / WAV scratch, bounded by a BUDGET
+ * of 256 MB per call: entries whose needs do not fit it together run as consecutive sub-batches that reuse the scratch in stream order,
+ * still behind the one wait; at most 16 MB stay allocated after the call. wlx_pcm_put's conventions hold: the PCM buffers grow once, to
+ * the longest served entry, before any launch; recorded log-mel requests that read a target item go out first; one call per slot at a
+ * time; never the null stream; the caller's memory may be reused on return. */
+#define WLX_PUT_PCM    0   /* float32 16 kHz mono samples: what wlx_pcm_put takes            */
+#define WLX_PUT_FRAMES 1   /* interleaved frames: what wlx_pcm_put_frames takes (F32 / S16)   */
+#define WLX_PUT_FLAC   2   /* the bytes of a FLAC file: what wlx_pcm_put_flac takes           */
+#define WLX_PUT_WAV    3   /* the bytes of a telephony WAV file: what wlx_pcm_put_wav takes   */
+#define WLX_PUT_MANY_MAX 64
+typedef struct { int32_t kind; const void* data; int64_t n;   /* samples | frames | bytes */
+                 int32_t channels, sample_format, sample_rate; /* WLX_PUT_FRAMES only */ } wlx_put_entry;
+typedef struct { int32_t status; int64_t n_out; } wlx_put_result;
+int32_t wlx_pcm_put_many(wlx_engine* e, int32_t slot, int32_t first_item, int32_t n,
+                         const wlx_put_entry* entries, wlx_put_result* results);
 /* ---- batched long-form front end (PRODUCT entry points of BatchedInferencePipeline: whisperlive_amd/batched.py) ----
  * Replaces faster_whisper.vad.collect_chunks + one FeatureExtractor call per chunk of the reference's BatchedInferencePipeline.transcribe
  * (whisper_live/transcriber/transcriber_faster_whisper.py:424-429): B chunks are cut out of ONE resident PCM buffer into B feature items
@@ -934,6 +964,24 @@ int32_t wlx_debug_resample_stream(int32_t device, const void* frames, int64_t n_
  * first: WLX_ERR_DATA / WLX_ERR_ARG as wlx_flac_probe before any launch; WLX_ERR_DATA after the one wait for a frame that does not decode. */
 int32_t wlx_debug_flac_decode(int32_t device, const void* bytes, int64_t n_bytes, int32_t* samples_out, int64_t cap_samples,
                               int64_t* n_frames_out, int32_t* channels_out);
+/* The ragged kernels of wlx_pcm_put_many (csrc/put_many.hip), ONE launch each on a private stream of `device`, n <= WLX_PUT_MANY_MAX entries.
+ * wlx_debug_resample_many: resample_many_kernel over n entries of their own shapes (frames[k]: [n_frames[k]][channels[k]] in
+ * sample_formats[k], any of the five WLX_PCM_* codes, at sample_rates[k]); entry k's outputs land at out[out_off[k] ..), n_out[k] of
+ * them; `out` (cap floats) is copied in AND out. Entry k is BIT-IDENTICAL to wlx_debug_resample / wlx_debug_resample_stream of that entry
+ * alone. WLX_ERR_ARG before any launch: what wlx_ring_set_format refuses, n_frames outside 0..2^31, an output outside the buffer.
+ * wlx_debug_flac_decode_many: flac_frames_many_kernel + flac_finish_many_kernel over the concatenated frame tables of n FLAC files; entry
+ * k's decoded INTEGER samples land at samples_out[out_off[k] ..) as wlx_debug_flac_decode leaves them, status_out[k] = WLX_OK, or
+ * WLX_ERR_DATA for an entry with a frame that does not decode (its frame's samples are zeros). The index of every entry runs first:
+ * WLX_ERR_DATA / WLX_ERR_ARG as wlx_debug_flac_decode, for the call, before any launch.
+ * wlx_debug_put_many_budget: the scratch budget of wlx_pcm_put_many in this process from now on (bytes >= 64 KB; 0: unchanged; < 0: the
+ * default); *previous (nullable) = the budget before, *last_sub_batches (nullable) = the sub-batches the last call ran as. */
+int32_t wlx_debug_resample_many(int32_t device, int32_t n, const void* const* frames, const int64_t* n_frames, const int32_t* channels,
+                                const int32_t* sample_formats, const int32_t* sample_rates, float* out, const int64_t* out_off,
+                                int64_t cap, int64_t* n_out);
+int32_t wlx_debug_flac_decode_many(int32_t device, int32_t n, const void* const* bytes, const int64_t* n_bytes, int32_t* samples_out,
+                                   const int64_t* out_off, int64_t cap_samples, int64_t* n_frames_out, int32_t* channels_out,
+                                   int32_t* status_out);
+int32_t wlx_debug_put_many_budget(int64_t bytes, int64_t* previous, int32_t* last_sub_batches);
 /* The ADPCM block decoder (csrc/adpcm.hip adpcm_decode_kernel, csrc/adpcm_core.h) without the resampler, on a private stream of `device`:
  * the bytes of an IMA or MS ADPCM WAV file -> samples_out[n][channels], the decoded int16 values, one upload, one launch, one wait; any
  * sample rate. WLX_ERR_DATA as wlx_wav_probe; WLX_ERR_ARG for another tag, a layout the decoder does not take, or cap_samples < n * channels. */

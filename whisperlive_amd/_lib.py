@@ -15,11 +15,11 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "put_many.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
-    "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_put_frames_split", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_put_flac_split", "wlx_wav_probe", "wlx_pcm_put_wav", "wlx_pcm_put_wav_split", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
+    "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_put_frames_split", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_put_flac_split", "wlx_wav_probe", "wlx_pcm_put_wav", "wlx_pcm_put_wav_split", "wlx_pcm_put_many", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
     "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_align_batch", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_ring_set_format", "wlx_ring_append_frames", "wlx_resample_stream_count",
@@ -37,6 +37,7 @@ EXPORTS = [
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
     "wlx_debug_dec_gemv", "wlx_debug_dec_cq_cross_attn",
     "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_resample_stream", "wlx_debug_flac_decode", "wlx_debug_flac_timings", "wlx_debug_adpcm_decode",
+    "wlx_debug_resample_many", "wlx_debug_flac_decode_many", "wlx_debug_put_many_budget",
     "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings",
 ]
 
@@ -107,6 +108,15 @@ class wlx_wav_info(C.Structure):
                 ("n_frames", C.c_int64), ("served", C.c_int32)]
 
 
+class wlx_put_entry(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("data", C.c_void_p), ("n", C.c_int64), ("channels", C.c_int32), ("sample_format", C.c_int32),
+                ("sample_rate", C.c_int32)]
+
+
+class wlx_put_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_out", C.c_int64)]
+
+
 class wlx_mt_spec(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("d_model", "n_heads", "enc_layers", "dec_layers", "ffn", "vocab", "max_positions",
                                          "pad_id", "eos_id", "decoder_start_id", "scale_embedding")]
@@ -130,6 +140,8 @@ ALIGN_MAX_BATCH = 64    # wlx.h WLX_ALIGN_MAX_BATCH: entries of one wlx_align_ba
 ALIGN_MAX_MEDIAN = 15   # wlx.h WLX_ALIGN_MAX_MEDIAN: the widest median filter the device post-processing serves
 MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
+PUT_PCM, PUT_FRAMES, PUT_FLAC, PUT_WAV = 0, 1, 2, 3   # wlx.h WLX_PUT_*: the kinds of a wlx_put_entry
+PUT_MANY_MAX = 64       # wlx.h WLX_PUT_MANY_MAX: entries of one wlx_pcm_put_many call
 ERR_STATE = 4           # wlx_status WLX_ERR_STATE
 LM_MAXRANGES = 256      # wlx.h WLX_LM_MAXRANGES: ranges per chunk of wlx_logmel_chunks / wlx_logmel_ring
 PCM_F32, PCM_S16 = 0, 1           # wlx.h WLX_PCM_F32 / WLX_PCM_S16
@@ -326,6 +338,7 @@ def load() -> C.CDLL:
     lib.wlx_wav_probe.argtypes = [vp, i64, C.POINTER(wlx_wav_info)]
     lib.wlx_pcm_put_wav.argtypes = [vp, i32, i32, vp, i64, C.POINTER(wlx_wav_info), C.POINTER(C.c_int64)]
     lib.wlx_pcm_put_wav_split.argtypes = [vp, i32, i32, vp, i64, C.POINTER(wlx_wav_info), C.POINTER(C.c_int64)]
+    lib.wlx_pcm_put_many.argtypes = [vp, i32, i32, i32, C.POINTER(wlx_put_entry), C.POINTER(wlx_put_result)]
     lib.wlx_pcm_get.argtypes = [vp, i32, i32, f32p, i64, C.POINTER(C.c_int64)]
     lib.wlx_logmel_resident.argtypes = [vp, i32, i32, i32p]
     lib.wlx_features_get.argtypes = [vp, i32, i32, f32p, i64, i32p]
@@ -424,6 +437,9 @@ def load() -> C.CDLL:
     lib.wlx_debug_flac_decode.argtypes = [i32, vp, i64, i32p, i64, C.POINTER(C.c_int64), i32p]
     lib.wlx_debug_flac_timings.argtypes = [vp, i32, f32p]
     lib.wlx_debug_adpcm_decode.argtypes = [i32, vp, i64, C.POINTER(C.c_int16), i64, C.POINTER(C.c_int64), i32p]
+    lib.wlx_debug_resample_many.argtypes = [i32, i32, C.POINTER(vp), i64p, i32p, i32p, i32p, f32p, i64p, i64, i64p]
+    lib.wlx_debug_flac_decode_many.argtypes = [i32, i32, C.POINTER(vp), i64p, i32p, i64p, i64, i64p, i32p, i32p]
+    lib.wlx_debug_put_many_budget.argtypes = [i64, i64p, i32p]
     lib.wlx_debug_dtw.argtypes = [i32, f32p, i32, i32p, i32p, i32p, i32p, i32, i32p]
     lib.wlx_debug_align_post.argtypes = [i32, f32p, i32, i32, i32p, i32, i32p, i32, f32p, i32p, i32p, i32, i32p]
     lib.wlx_debug_align_timings.argtypes = [vp, i32, f32p, f32p]

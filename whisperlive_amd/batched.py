@@ -319,7 +319,9 @@ class BatchedInferencePipeline:
         """Many files as ONE job whose decode groups mix files (whisperlive_amd/many_files.py): yields (index, segments, info) per
         file — what `transcribe(audios[index], ...)` returns, the segments as a list — or (index, exception, None) for a damaged file.
         target_language= (one code, or a list with a code or None per file) with translator=: each file's segments carry
-        `.translation`, one translation job per file as it finishes."""
+        `.translation`, one translation job per file as it finishes.
+        wave_put: bool = False (a keyword of the job, beside those of `transcribe`): True puts the files of a wave in one Slot.put_many
+        call with one wait (a slot without it keeps the per-file puts); the results are the same, the default stays one put per file."""
         from .many_files import iter_many
         target_language, translator = kwargs.pop("target_language", None), kwargs.pop("translator", None)
         if target_language is None:
@@ -336,7 +338,7 @@ class BatchedInferencePipeline:
         return translated_job(iter_many(self, audios, batch_size=batch_size, on_error=on_error, **kwargs), languages, translator)
 
     def transcribe_many(self, audios, *, batch_size: int = 8, on_error: str = "return", **kwargs):
-        """`iter_many` to the end -> [(segments, info) or (exception, None)] in input order"""
+        """`iter_many` to the end -> [(segments, info) or (exception, None)] in input order (wave_put=True: see `iter_many`)"""
         if kwargs.get("target_language") is not None:
             audios = list(audios) if isinstance(audios, (list, tuple)) or hasattr(audios, "__next__") else audios
             job = self.iter_many(audios, batch_size=batch_size, on_error=on_error, **kwargs)
@@ -596,6 +598,70 @@ def _put_audio(model, slot, audio, item: int = 0):
             with slot.lock:
                 slot.pcm_put(audio, item=item)
     return n_samples, host_audio, device
+
+
+def _put_audio_many(model, slot, audios, items) -> list:
+    """`_put_audio` for a wave: audios[k] into item items[k], the files whose route runs on the device going up together in
+    Slot.put_many calls (one per run of neighbouring items, 64 entries at the most each) -> per file what `_put_audio` returns, or the
+    exception it would have raised (ValueError for a damaged file, OSError) — returned, so that one file costs only itself.
+    The kind of each file is chosen exactly as `_put_audio` chooses it: FLAC magic -> the FLAC bytes, `wav_served` -> the WAV bytes, any
+    other file is read on the host and gives frames when `resample_supported`, a waveform gives PCM; anything else (an empty waveform,
+    a shape the resampler does not serve, a slot without the front end) takes `_put_audio`, per file. An entry the device REFUSES
+    falls back to `_put_audio` for that file alone; a damaged one is the ValueError `_put_audio` raises."""
+    sampling_rate = model.feature_extractor.sampling_rate
+    device = all(hasattr(slot, m) for m in ("logmel_chunks", "pcm_put", "pcm", "put_many")) and sampling_rate == 16000
+    out: list = [None] * len(audios)
+    entries: list = [None] * len(audios)
+    for k, audio in enumerate(audios):
+        try:
+            if isinstance(audio, Exception):
+                raise audio
+            if not device:
+                continue
+            if isinstance(audio, np.ndarray):
+                if audio.shape[0] > 0:
+                    entries[k] = ("pcm", np.ascontiguousarray(audio, dtype=np.float32))
+                continue
+            from .audio_io import read_audio, wav_served
+            from .engine import resample_supported
+            data = _file_bytes(audio)
+            if data[:4] == b"fLaC" and hasattr(slot, "put_flac"):
+                entries[k] = ("flac", data)
+            elif hasattr(slot, "put_wav") and wav_served(data):
+                entries[k] = ("wav", data)
+            else:
+                file_frames, file_sr = read_audio(data)
+                if file_frames.shape[0] > 0 and hasattr(slot, "put_frames") and resample_supported(file_sr, file_frames.shape[1]):
+                    entries[k] = ("frames", file_frames, file_sr)
+        except (ValueError, OSError, TypeError) as e:
+            out[k] = e
+    runs: list = []                           # runs of entries whose items are neighbours: one put_many each
+    for k, ent in enumerate(entries):
+        if ent is None:
+            continue
+        if runs and runs[-1][-1] + 1 == k and items[runs[-1][-1]] + 1 == items[k]:
+            runs[-1].append(k)
+        else:
+            runs.append([k])
+    for run in runs:
+        with slot.lock:
+            results = slot.put_many([entries[k] for k in run], first_item=items[run[0]])
+        for k, r in zip(run, results):
+            if isinstance(r, _WlxError):
+                if r.code == _ERR_DATA:
+                    out[k] = ValueError(f"damaged {entries[k][0].upper()} stream: {r}")
+                elif r.code != _ERR_ARG:
+                    raise r
+                entries[k] = None             # refused: nothing was launched for it, the file takes its other routes alone
+            else:
+                out[k] = (r[0], entries[k][1] if entries[k][0] == "pcm" else slot.pcm, True)
+    for k, audio in enumerate(audios):
+        if out[k] is None:
+            try:
+                out[k] = _put_audio(model, slot, audio, items[k])
+            except (ValueError, OSError, _WlxError) as e:
+                out[k] = e
+    return out
 
 
 def _file_bytes(audio) -> bytes:

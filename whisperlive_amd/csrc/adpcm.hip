@@ -17,20 +17,12 @@
 #include <type_traits>
 #include "engine.h"
 #include "adpcm_core.h"
+#include "frontend.h"
 
 namespace wlx {
 
-constexpr int WAV_TAG_MS = 0x02, WAV_TAG_ALAW = 0x06, WAV_TAG_MULAW = 0x07, WAV_TAG_IMA = 0x11, WAV_TAG_EXT = 0xFFFE;
 constexpr int ADPCM_THREADS = 256;
 constexpr size_t ADPCM_MAX_LDS = 64 * 1024;   // byte rows + sample tile of a workgroup (the default dynamic-LDS limit)
-
-struct WavStream {
-    wlx_wav_info info{};
-    int kind = -1;                  // ADPCM_IMA / ADPCM_MS; -1: not an ADPCM tag
-    bool layout_ok = false;         // ADPCM: bits == 4 and a block_align the formulas accept
-    int n_coef = 0;
-    int16_t coefs[2 * ADPCM_MAX_COEF] = {};
-};
 
 struct AdpcmShape { int G, bstride, tstride; size_t lds; };     // blocks per workgroup, LDS bytes per byte row, int16 per tile row
 
@@ -50,7 +42,7 @@ static inline unsigned rd16(const uint8_t* p) { return (unsigned)p[0] | ((unsign
 static inline unsigned long long rd32(const uint8_t* p) { return (unsigned long long)rd16(p) | ((unsigned long long)rd16(p + 2) << 16); }
 
 // WLX_OK: `out` holds the file's shape (served or not). WLX_ERR_DATA: no RIFF / WAVE, no `fmt ` / `data` chunk, a damaged block header.
-static int wav_index(const uint8_t* b, long long n, WavStream& out) {
+int wav_index(const uint8_t* b, long long n, WavStream& out) {
     if (!b || n < 12 || std::memcmp(b, "RIFF", 4) || std::memcmp(b + 8, "WAVE", 4)) return set_error(WLX_ERR_DATA, "WAV: not a RIFF/WAVE file");
     const uint8_t *fmt = nullptr, *data = nullptr;
     long long fmt_len = 0, data_len = 0, fact = 0;
@@ -124,7 +116,7 @@ static int wav_index(const uint8_t* b, long long n, WavStream& out) {
     return WLX_OK;
 }
 
-static int wav_served(const WavStream& w) {
+int wav_served(const WavStream& w) {
     if (w.info.served) return WLX_OK;
     return set_error(WLX_ERR_ARG, "WAV file of tag 0x%x, %d Hz x %d channels x %d bits, block_align %d, %lld frames: outside what the device "
                      "route serves (G.711 / IMA / MS ADPCM, 1..%d channels, <= 3600 s, a rate the resampler serves, a block that fits the "
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(ADPCM_THREADS) void adpcm_decode_kernel(AdpcmArgs p
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the blocks the frame count needs (a `fact` chunk may leave whole blocks unused) and their bytes
-static long long adpcm_blocks(const WavStream& w) { return (w.info.n_frames + w.info.samples_per_block - 1) / w.info.samples_per_block; }
+long long adpcm_blocks(const WavStream& w) { return (w.info.n_frames + w.info.samples_per_block - 1) / w.info.samples_per_block; }
 
 // the decode launch on `st`; no wait. d_bytes: the data chunk's first adpcm_blocks(w) blocks; out: [n_frames][channels] of T
 template <class T>
@@ -220,6 +212,9 @@ static int adpcm_launch(const WavStream& w, const uint8_t* d_bytes, T* out, hipS
     CK(hipGetLastError());
     return WLX_OK;
 }
+
+// the float32 launch by name, for put_many.hip (frontend.h)
+int adpcm_launch_f32(const WavStream& w, const uint8_t* d_bytes, float* out, hipStream_t st) { return adpcm_launch<float>(w, d_bytes, out, st); }
 
 }  // namespace wlx
 

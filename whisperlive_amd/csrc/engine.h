@@ -67,6 +67,7 @@ struct Slot {
     // on demand and owned by name; a call keeps at most 2 * RS_BLOCK_BYTES of it afterwards. ev: upload / frames / finish / resample marks
     // wlx_pcm_put_wav (adpcm.hip) lays its data chunk | float32 frames into the same buf / cap, under the same rule.
     struct FlacScratch { unsigned char* buf = nullptr; size_t cap = 0; hipEvent_t ev[5] = {}; float index_ms = 0.f; bool timed = false; } flac;
+    int* h_put_status = nullptr; size_t h_put_status_cap = 0;   // wlx_pcm_put_many (put_many.hip): pinned copy of a call's FLAC status words, in ints
     long long* d_rng = nullptr;                      // [2 * WLX_LM_MAXRANGES] range table of the last wlx_logmel_ring
     // wlx_logmel_chunks: [B] chunk descriptors and [B][WLX_LM_MAXRANGES][2] range pairs, pinned staging and device copy (allocated at
     // its first call); `ck_staged` is recorded behind the copy: the next call waits for it before it rewrites the pinned side

@@ -17,14 +17,10 @@
 #include <type_traits>
 #include "engine.h"
 #include "flac_core.h"
+#include "frontend.h"
 
 namespace wlx {
 
-struct FlacFrame { long long start, end, first; int n, pad; };     // bytes [start, end), first sample, block size
-struct FlacStream {
-    wlx_flac_info info{};
-    std::vector<FlacFrame> frames;
-};
 
 // ------------------------------------------------------------------------------------------------ CRCs
 struct FlacCrc {
@@ -111,7 +107,7 @@ static int flac_header(const uint8_t* b, long long p, long long nbytes, FlacHead
 // ------------------------------------------------------------------------------------------------ metadata + frame index
 // WLX_OK: `out` holds the stream's shape and its frame table (served or not). WLX_ERR_DATA: damaged. WLX_ERR_ARG: a container or a
 // stream shape this front end does not take apart at all (Ogg, a tag in front of the magic, a mid-stream change of shape).
-static int flac_index(const uint8_t* b, long long nbytes, FlacStream& out) {
+int flac_index(const uint8_t* b, long long nbytes, FlacStream& out) {
     if (!b || nbytes < 4) return set_error(WLX_ERR_DATA, "FLAC: %lld bytes hold no stream", nbytes);
     if (!std::memcmp(b, "OggS", 4)) return set_error(WLX_ERR_ARG, "Ogg FLAC is not served by the device route");
     if (!std::memcmp(b, "ID3", 3)) return set_error(WLX_ERR_ARG, "an ID3 tag in front of the fLaC magic is not served by the device route");
@@ -297,7 +293,7 @@ static int flac_launch(const FlacStream& s, const void* bytes, long long nbytes,
     return WLX_OK;
 }
 
-static int flac_check_status(const int* status, size_t nf) {
+int flac_check_status(const int* status, size_t nf) {
     for (size_t f = 0; f < nf; ++f)
         if ((status[f] & 0xFF) != FLAC_OK)
             return set_error(WLX_ERR_DATA, "FLAC: frame %zu does not decode (status %d: 1 past its end, 2 reserved code, 3 inconsistent partition / "
@@ -305,7 +301,7 @@ static int flac_check_status(const int* status, size_t nf) {
     return WLX_OK;
 }
 
-static int flac_served(const FlacStream& s) {
+int flac_served(const FlacStream& s) {
     if (s.info.served) return WLX_OK;
     return set_error(WLX_ERR_ARG, "FLAC stream of %d Hz x %d channels x %d bits, %lld samples: outside what the device route serves (1..%d "
                      "channels, <= %d bits, <= 3600 s, a rate the resampler serves): decode on the host", s.info.sample_rate, s.info.channels,

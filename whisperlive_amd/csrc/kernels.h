@@ -104,6 +104,7 @@ struct ResamplePlan { int up, down, half_len, tile; const float* taps; }; // til
 // the event recorded behind the copy out of each
 struct ResampleStage { unsigned char* pinned[2]; unsigned char* dev[2]; hipEvent_t copied[2]; bool used[2]; };
 int resample_check_args(const void* frames, long long n_frames, int channels, int sample_format, int sample_rate);
+int resample_ratio(int sample_rate, int* up, int* down, int* tile);      // 16000 / rate reduced and its tile; needs no device
 int resample_plan(int device, int sample_rate, ResamplePlan* out);        // WLX_ERR_ARG for a ratio the kernel does not serve
 long long resample_out_len(const ResamplePlan& pl, long long n_frames);   // ceil(n_frames * up / down)
 long long resample_reach(const ResamplePlan& pl);                         // smallest legal block, in input frames

@@ -426,6 +426,68 @@ class Slot:
         self._grew(n.value)
         return n.value, info
 
+    def put_many(self, entries, first_item: int = 0, with_info: bool = False) -> list:
+        """A wave of files and waveforms into items first_item, first_item + 1, ... with ONE wait (wlx_pcm_put_many). An entry is
+        ("pcm", waveform) | ("frames", frames [n, channels], sample_rate) | ("flac", bytes) | ("wav", bytes): what pcm_put, put_frames,
+        put_flac and put_wav take, and each item ends up bit-identical to that call's. -> per entry (samples resident, info or None), or
+        the WlxError of that entry alone (code ERR_ARG: refused, its item untouched; ERR_DATA: damaged) — it is returned, not raised.
+        info: the probe's wlx_flac_info / wlx_wav_info when `with_info` (a second pass over the file's bytes on the host), else None.
+        More than _lib.PUT_MANY_MAX entries are cut into consecutive calls. A WlxError of a CALL (bad items, no memory, HIP) is raised."""
+        out: list = []
+        for at in range(0, len(entries), _lib.PUT_MANY_MAX):
+            out += self._put_many_call(entries[at:at + _lib.PUT_MANY_MAX], first_item + at, with_info)
+        return out
+
+    def _put_many_call(self, entries, first_item: int, with_info: bool) -> list:
+        n = len(entries)
+        arr, res, keep = (_lib.wlx_put_entry * n)(), (_lib.wlx_put_result * n)(), []
+        for k, ent in enumerate(entries):
+            kind, x = ent[0], ent[1]
+            if kind == "pcm":
+                x = np.ascontiguousarray(x, dtype=np.float32)
+                arr[k].kind, arr[k].data, arr[k].n = _lib.PUT_PCM, x.ctypes.data, x.shape[0]
+                self._grew(x.shape[0])
+            elif kind == "frames":
+                x = np.asarray(x)
+                if x.ndim == 1:
+                    x = x[:, None]
+                fmt = _lib.PCM_S16 if x.dtype == np.int16 else _lib.PCM_F32
+                x = np.ascontiguousarray(x, dtype=np.int16 if fmt == _lib.PCM_S16 else np.float32)
+                arr[k].kind, arr[k].data, arr[k].n = _lib.PUT_FRAMES, x.ctypes.data, x.shape[0]
+                arr[k].channels, arr[k].sample_format, arr[k].sample_rate = x.shape[1], fmt, int(ent[2])
+                self._grew(_at_16k(x.shape[0], int(ent[2])))
+            elif kind in ("flac", "wav"):
+                x = bytes(x)
+                arr[k].kind, arr[k].n = (_lib.PUT_FLAC if kind == "flac" else _lib.PUT_WAV), len(x)
+                arr[k].data = C.cast(C.c_char_p(x), C.c_void_p).value
+                if kind == "flac":
+                    head = FlacFrames(x)                  # (STREAMINFO's count and rate; the bytes are not copied)
+                    self._grew(_at_16k(head.total_samples, head.sample_rate))
+                else:
+                    self._grew(_wav_at_16k(x))
+            else:
+                raise ValueError(f"put_many: unknown entry kind {kind!r} (pcm, frames, flac, wav)")
+            keep.append(x)
+        check(self.lib.wlx_pcm_put_many(self.engine._h, self.sid, first_item, n, arr, res))
+        out = []
+        for k, ent in enumerate(entries):
+            if res[k].status != 0:
+                err = WlxError(f"libwlx error {res[k].status}: put_many entry {k} ({ent[0]}) was "
+                               f"{'refused' if res[k].status == _lib.ERR_ARG else 'found damaged'}")
+                err.code = res[k].status
+                out.append(err)
+                continue
+            self._grew(res[k].n_out)
+            info = None
+            if with_info and ent[0] == "flac":
+                info = _lib.wlx_flac_info()
+                check(self.lib.wlx_flac_probe(keep[k], len(keep[k]), C.byref(info)))
+            elif with_info and ent[0] == "wav":
+                info = _lib.wlx_wav_info()
+                check(self.lib.wlx_wav_probe(keep[k], len(keep[k]), C.byref(info)))
+            out.append((int(res[k].n_out), info))
+        return out
+
     def pcm(self, item: int = 0) -> np.ndarray:
         """Host copy of the item's resident PCM (16 kHz mono float32)."""
         n = C.c_int64(0)

@@ -53,7 +53,7 @@ import numpy as np
 
 from . import vad as _vad
 from . import word_timing as _wt
-from .batched import MAX_DEC_ROWS, DeviceChunks, _collect_ranges, _file_bytes, _options, _put_audio, _segment, _vad_options
+from .batched import MAX_DEC_ROWS, DeviceChunks, _collect_ranges, _file_bytes, _options, _put_audio, _put_audio_many, _segment, _vad_options
 from ._lib import ERR_ARG as _ERR_ARG, WlxError as _WlxError
 from .engine import FlacFrames, _at_16k, _wav_at_16k
 from .multichannel import source_rows_addressable
@@ -165,7 +165,7 @@ class _File:
         self.last_speech = 0.0
 
 
-def transcribe_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **kwargs) -> list:
+def transcribe_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **kwargs) -> list:      # (wave_put rides in kwargs)
     out: list = [None] * len(audios)
     for index, segments, info in iter_many(pipe, audios, batch_size=batch_size, on_error=on_error, **kwargs):
         out[index] = (segments, info)
@@ -178,9 +178,12 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     list with one entry per file. The arguments are checked here, before the first file is read (module docstring).
     Each job leaves `pipe.many_timing` = {"front_s": seconds its waves spent before their first decode (puts, gate, language),
     "total_s": seconds up to the end of the last wave finished, "waves": waves finished} — what scripts/many_files_time.py reports;
-    the next job on the pipeline replaces it."""
+    the next job on the pipeline replaces it.
+    wave_put=True: the files of a wave go up in ONE Slot.put_many call (one wait) instead of one put per file; a slot without put_many
+    keeps the per-file puts. Results are the same either way; the default stays per-file puts."""
     if on_error not in ("return", "raise"):
         raise ValueError(f"on_error {on_error!r}: 'return' or 'raise'")
+    wave_put = bool(kwargs.pop("wave_put", False))
     if kwargs.pop("multichannel", False):
         raise ValueError("transcribe_many: multichannel=True is not part of this route (transcribe the files one by one with "
                          "transcribe(..., multichannel=True))")
@@ -204,10 +207,10 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     max_batch = int(getattr(model, "max_batch", batch_size))
     check_batch(batch_size, max_batch)
     per_file = per_file_arguments(a, len(audios))
-    return _job(pipe, audios, per_file, a, batch_size, max_batch, on_error)
+    return _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put)
 
 
-def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error):
+def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False):
     model = pipe.model
     timing = pipe.many_timing = {"front_s": 0.0, "total_s": 0.0, "waves": 0}
     t_job = time.perf_counter()
@@ -235,23 +238,28 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error):
         files = [_File(i, per_file[i], loaded[i], batch_size + k) for k, i in enumerate(wave)]
         for i in wave:
             loaded[i] = None                # (the job does not hold a file's bytes past its wave)
-        yield from _wave(pipe, slot, files, a, vad_parameters, batch_size, on_error, timing)
+        yield from _wave(pipe, slot, files, a, vad_parameters, batch_size, on_error, timing, wave_put)
         timing["waves"] += 1
         timing["total_s"] = time.perf_counter() - t_job
 
 
-def _wave(pipe, slot, files: List[_File], a, vad_parameters, batch_size, on_error, timing):
+def _wave(pipe, slot, files: List[_File], a, vad_parameters, batch_size, on_error, timing, wave_put: bool = False):
     model = pipe.model
     sampling_rate = model.feature_extractor.sampling_rate
     t0 = time.perf_counter()
     if hasattr(model, "_tls"):
         model._tls.file_audio = None          # (what an earlier call of this thread left resident is about to be overwritten)
-    # ---- every file into its own item
-    for f in files:
+    # ---- every file into its own item: one by one, or (wave_put, on a slot that has put_many) the wave in one call with one wait
+    put = None
+    if wave_put and hasattr(slot, "put_many"):
+        put = _put_audio_many(model, slot, [f.audio for f in files], [f.item for f in files])
+    for k, f in enumerate(files):
         try:
             if isinstance(f.audio, Exception):
                 raise f.audio
-            f.n_samples, _host, _device = _put_audio(model, slot, f.audio, f.item)
+            if put is not None and isinstance(put[k], Exception):
+                raise put[k]
+            f.n_samples, _host, _device = put[k] if put is not None else _put_audio(model, slot, f.audio, f.item)
         except (ValueError, OSError, _WlxError) as e:
             if isinstance(e, _WlxError):
                 # a refusal (nothing was launched: the file is longer than the 3600 s an item holds) is this file's error; any other

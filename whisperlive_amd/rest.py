@@ -305,8 +305,9 @@ class FileBatcher:
     one job; uploads with other options wait for the next job. Each request is answered from its own result as soon as the job yields
     it. `make_pipeline(transcriber)` -> the pipeline (anything with `iter_many`). `jobs` counts the jobs run."""
 
-    def __init__(self, make_pipeline: Callable, batch_size: int, window_s: float):
+    def __init__(self, make_pipeline: Callable, batch_size: int, window_s: float, wave_put: bool = False):
         self.make_pipeline, self.batch_size, self.window_s = make_pipeline, int(batch_size), float(window_s)
+        self.wave_put = bool(wave_put)      # a job's files go up in one Slot.put_many call per wave (iter_many(wave_put=True))
         self.jobs = 0
         self._waiting: List[_Upload] = []
         self._cv = threading.Condition()
@@ -360,7 +361,8 @@ class FileBatcher:
             try:
                 results = self.make_pipeline(transcriber).iter_many(
                     [u.data for u in job], batch_size=self.batch_size, vad_filter=True,
-                    **{name: [u.per_file[name] for u in job] for name in ("language", "initial_prompt", "hotwords")}, **job[0].shared)
+                    **{name: [u.per_file[name] for u in job] for name in ("language", "initial_prompt", "hotwords")}, **job[0].shared,
+                    **({"wave_put": True} if self.wave_put else {}))
                 for index, segments, info in results:
                     up = job[index]
                     if info is None:
@@ -411,8 +413,9 @@ class RestServer:
                  max_body_bytes: int = 512 << 20, diarization_model: Optional[str] = None,
                  embedder_factory: Optional[Callable] = None, file_batch_size: int = 0, file_batch_window_ms: int = 0,
                  pipeline_factory: Optional[Callable] = None, translation_model: Optional[str] = None,
-                 translator_factory: Optional[Callable] = None):
+                 translator_factory: Optional[Callable] = None, file_batch_wave_put: bool = False):
         self.host, self.port, self.model = host, int(port), model
+        self.file_batch_wave_put = bool(file_batch_wave_put)     # the pooled jobs put each wave of files in one call (FileBatcher.wave_put)
         # a small100 / M2M100 checkpoint (a directory or a hub id, resolved as the WebSocket server resolves its own): requests may then
         # carry target_language. translator_factory: (directory, device index) -> translator; None = translation.shared_translator
         self.translation_model = translation_model
@@ -451,7 +454,7 @@ class RestServer:
         # of different devices run side by side; `batcher` is the first device's
         self._batchers: Dict[int, FileBatcher] = {}
         if self.file_batch_window_ms > 0:
-            self._batchers = {d: FileBatcher(self._pipeline, self.file_batch_size, self.file_batch_window_ms / 1000.0) for d in self.devices}
+            self._batchers = {d: FileBatcher(self._pipeline, self.file_batch_size, self.file_batch_window_ms / 1000.0, self.file_batch_wave_put) for d in self.devices}
             self.batcher = self._batchers[self.devices[0]]
 
     # ---- life cycle
@@ -992,6 +995,8 @@ def main(argv=None):
     ap.add_argument("--file_batch_window_ms", type=int, default=0,
                     help="pool uploads that arrive within this many milliseconds into one job whose decode steps mix files "
                          "(needs --file_batch_size; 0 = every request runs alone)")
+    ap.add_argument("--file_batch_wave_put", action="store_true",
+                    help="the pooled jobs of --file_batch_window_ms put each wave of files on the device in one call (off by default)")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if a.metrics_port > 0:
@@ -999,7 +1004,8 @@ def main(argv=None):
     RestServer(a.host, a.port, a.model_path, devices=[int(x) for x in a.devices.split(",") if x != ""], api_key=a.api_key,
                cors_origins=a.cors_origins, rate_limit_rpm=a.rate_limit_rpm, max_body_bytes=a.max_body_mb << 20,
                diarization_model=a.diarization_model, file_batch_size=a.file_batch_size,
-               file_batch_window_ms=a.file_batch_window_ms, translation_model=a.translation_model).serve_forever()
+               file_batch_window_ms=a.file_batch_window_ms, translation_model=a.translation_model,
+               file_batch_wave_put=a.file_batch_wave_put).serve_forever()
 
 
 if __name__ == "__main__":
