@@ -329,31 +329,40 @@ __global__ __launch_bounds__(XA_TPS * 64) void dec_cross_attn_kernel(const half_
 // repeats are L2 hits, not HBM reads. What it buys: one launch boundary (1.6 us) and one launch's fixed latency per
 // layer; what it costs: ~200 load instructions per CU instead of ~60 (2.2 us of issue at ~11 ns each).
 // Eligibility (launcher): d_model = 256 * LNV with KT % 6 == 0 — Whisper-small; other sizes keep the two launches.
+// Argument order (kernel-argument preload, 14 dwords): everything the requests in front of the K / V loads need — row base and stride, gamma, beta,
+// the weights, the group table, R, rows — arrives in SGPRs at wave start; H and KT are the template's (the launcher serves d_model = 256 * LNV only).
+// The tail (bias, q scale, K / V bases and stride, the partials) is fetched by the wave and first waited for behind the weight requests.
 template <int LNV, int KPW>
 __global__ __launch_bounds__(XA_TPS * 64) void dec_cq_cross_attn_kernel(
-    const float* __restrict__ X, long ldx, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const half_t* __restrict__ Wp, const float* __restrict__ bias, float qscale, int KT,
-    const half_t* __restrict__ Kp, const half_t* __restrict__ Vp, long item_stride, int H, int R, int rows,
-    const int* __restrict__ group_item, half_t* __restrict__ part_o, float* __restrict__ part_ml WLX_TR_PARAM) {
+    const float* X, long ldx, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const half_t* __restrict__ Wp, const int* __restrict__ group_item, int R, int rows,
+    const half_t* __restrict__ Kp, const half_t* __restrict__ Vp, long item_stride, const float* __restrict__ bias, float qscale,
+    half_t* __restrict__ part_o, float* __restrict__ part_ml WLX_TR_PARAM) {
     constexpr int TPS = XA_TPS;
-    static_assert(TPS == 6, "six waves: KT/6 k-tiles of the query projection and one key tile each");
+    constexpr int H = 4 * LNV, KT = 8 * LNV;
+    static_assert(TPS == 6 && KT == TPS * KPW, "six waves: KT/6 k-tiles of the query projection and one key tile each");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     WLX_TR_BEGIN();
-    // ---- (head, split) of this workgroup: the 8 splits of a head share blockIdx % 8, i.e. one XCD
-    const int per_grp = H * WLX_XSPLIT;
-    const int grp = blockIdx.x / per_grp, wg = blockIdx.x - grp * per_grp;
+    // ---- grid (H x splits, groups). The group's item is the one value of the front that lives in memory: requested FIRST, from an address made of
+    // preloaded SGPRs alone, and waited for in front of the K / V requests only. (It was requested between the LayerNorm operands and the weights and
+    // waited for right there: a scalar round trip, cache-cold at every launch, behind the argument fetch that H, R and rows needed, with the sixteen
+    // weight requests and the gamma / beta exchange queued behind both.)
+    const int grp = blockIdx.y, wg = blockIdx.x;
+    const int item_rq = group_item[grp];
+    // ---- (head, split) of this workgroup: the 8 splits of a head share blockIdx.x % 8, i.e. one XCD (H * 8 is a multiple of 8: in every group)
     int h, sp;
     {
         const int x = wg & 7, j = wg >> 3, full = H >> 3, rem = H & 7;
-        if (rem == 0 || rem == 4) {
-            if (j < 8 * full) { h = (j >> 3) * 8 + x; sp = j & 7; }
-            else { h = 8 * full + (x >> 1); sp = (x & 1) * 4 + (j - 8 * full); }
+        if (rem == 0 || rem == 4) {                                        // (selects, not branches: H is a constant here)
+            const bool whole = j < 8 * full;
+            h = whole ? (j >> 3) * 8 + x : 8 * full + (x >> 1);
+            sp = whole ? (j & 7) : (x & 1) * 4 + (j - 8 * full);
         } else { h = wg >> 3; sp = wg & 7; }
     }
-    const int d = KT * 32;
-    const int ldxs = d + 8;
+    constexpr int d = KT * 32;
+    constexpr int ldxs = d + 8;
     // LDS: [0, xs_bytes) fp16 LayerNorm rows; then a region shared in time by the K-reduction partials and the
     // attention merge buffers; then the 16 x 64 fp16 query tile
     half_t* xs = reinterpret_cast<half_t*>(smem);
@@ -363,9 +372,13 @@ __global__ __launch_bounds__(XA_TPS * 64) void dec_cq_cross_attn_kernel(
     float* MLs = regB + TPS * 16 * 68;                                     // [6][16][2]
     half_t* qs = reinterpret_cast<half_t*>(MLs + TPS * 16 * 2);            // [16][72]
 
-    // ---- everything this wave will ever load, requested up front — the LayerNorm row of the first trip FIRST (round 2):
-    // vmcnt retires in order, so with the 24 KiB of weights / K / V per wave ahead of it the row arrived last and the
-    // LayerNorm (which everything else waits for) started 2.6 us into a 5.9 us launch
+    // ---- request order: row of the first trip, this wave's [gamma | beta] piece, the 16 weight fragments — nothing in front of
+    // them waits for memory — then the gamma / beta exchange and the first trip's LayerNorm, then K / V and the bias. The row comes FIRST (round 2):
+    // vmcnt retires in order. The workgroup's 174 wave-level loads take ~1.9 us to issue (one per ~11 ns per CU) and every wave used to reach the
+    // exchange's LDS store, the barrier and its LayerNorm only behind all 29 of its own: the rows were normalised when the LAST load had landed. Now
+    // the exchange stands behind 20 requests and the LayerNorm runs while the weights are in flight; K / V, first needed behind the query
+    // projection, are requested behind it. (X is not __restrict__ on purpose: as invariant loads the row requests are tied to nothing and hipcc
+    // placed them behind the weights; as ordinary loads they keep their place between the fences.)
     const int nrow = (rows - grp * R < R) ? rows - grp * R : R;           // live rows of this group
     float4 x0[LNV];
     {
@@ -389,6 +402,7 @@ __global__ __launch_bounds__(XA_TPS * 64) void dec_cq_cross_attn_kernel(
         gbp = reinterpret_cast<const float4*>(src)[lane];
     }
     asm volatile("" ::: "memory");     // compile-time fence: keep the requests below behind the ones above
+    __builtin_amdgcn_sched_barrier(0); // (and the instruction scheduler)
     const int kw0 = wave * KPW;
     const half_t* wp = Wp + ((long)(h * 4) * KT + kw0) * 512 + lane * 8;
     f16x8 wf[KPW][4];
@@ -396,9 +410,48 @@ __global__ __launch_bounds__(XA_TPS * 64) void dec_cq_cross_attn_kernel(
     for (int j = 0; j < KPW; ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) wf[j][i] = ld_nt_f16x8(wp + (long)i * KT * 512 + j * 512);
-    // (Tried: consuming this scalar load through an asm barrier placed here, so that the wave does not wait for it between the LayerNorm operands'
-    // requests and the weights' — hipcc then sinks the ROW loads behind the weights: the order the round-2 reordering removed. Left alone.)
-    const int item = group_item[grp];
+    constexpr float invK = 1.0f / (256.0f * LNV);
+    auto ln_row = [&](float4 (&x)[LNV], int r, bool keep) {           // LayerNorm: wave w normalises rows w, w + 6, ... of the group
+        float sm = 0.f;
+#pragma unroll
+        for (int j = 0; j < LNV; ++j) sm += (x[j].x + x[j].y) + (x[j].z + x[j].w);
+        const float mean = dpp_wave_sum(sm) * invK;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < LNV; ++j) {
+            x[j].x -= mean; x[j].y -= mean; x[j].z -= mean; x[j].w -= mean;
+            q += (x[j].x * x[j].x + x[j].y * x[j].y) + (x[j].z * x[j].z + x[j].w * x[j].w);
+        }
+        const float rstd = rsqrtf(dpp_wave_sum(q) * invK + 1e-5f);
+        half_t* dst = xs + r * ldxs + lane * 4;
+#pragma unroll
+        for (int j = 0; j < LNV; ++j) {
+            const f16x4 hv = {(half_t)(x[j].x * rstd * gq[j].x + bq[j].x), (half_t)(x[j].y * rstd * gq[j].y + bq[j].y),
+                              (half_t)(x[j].z * rstd * gq[j].z + bq[j].z), (half_t)(x[j].w * rstd * gq[j].w + bq[j].w)};
+            if (keep) *reinterpret_cast<f16x4*>(dst + 256 * j) = hv;
+        }
+    };
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    {   // the exchange: waits for this wave's first four loads, sixteen more in flight
+        float4* gbs4 = reinterpret_cast<float4*>(qs + 16 * 72);       // [2 LNV][64] float4 behind the query tile
+        gbs4[wave * 64 + lane] = gbp;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < LNV; ++j) { gq[j] = gbs4[j * 64 + lane]; bq[j] = gbs4[(LNV + j) * 64 + lane]; }
+    }
+    // first trip: straight-line and UNCONDITIONAL (a wave without a row normalises the clamped row it loaded and
+    // keeps nothing): inside an `if (wave < nrow)` hipcc sinks the row loads into the branch, behind the weights.
+    // (The row passes through opaque values: hipcc otherwise lifts the row sums, and the wait for the row, in front of the weight requests.)
+#pragma unroll
+    for (int j = 0; j < LNV; ++j) asm volatile("" : "+v"(x0[j].x), "+v"(x0[j].y), "+v"(x0[j].z), "+v"(x0[j].w));
+    ln_row(x0, (wave < nrow) ? wave : nrow - 1, wave < nrow);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    // the K / V addresses are the first use of the group's item and of the argument tail (compile-time fence and sched_barrier; the item passes
+    // through an opaque value HERE: its address arithmetic, and the scalar wait with it, is otherwise lifted in front of the weights)
+    int item = item_rq, hq = h;        // (the head too: the bias address, which needs the argument tail, is made of it)
+    asm volatile("" : "+s"(item), "+s"(hq));
     const int tile = sp * TPS + wave;
     const int key0 = tile * 32;
     const long toff = (long)item * item_stride + ((long)h * (WLX_T_AUDIO_PAD / 32) + tile) * 2048 + lane * 8;
@@ -409,47 +462,14 @@ __global__ __launch_bounds__(XA_TPS * 64) void dec_cq_cross_attn_kernel(
         for (int kt = 0; kt < 2; ++kt) kf[s2][kt] = ld_f16x8(Kp + toff + (s2 * 2 + kt) * 512);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) vf[dt] = ld_f16x8(Vp + toff + dt * 512);
-    const float4 bq4 = *reinterpret_cast<const float4*>(bias + h * 64 + (wave & 3) * 16 + g * 4);
-    {   // LayerNorm: wave w normalises rows w, w + 6, ... of the group
-        constexpr float invK = 1.0f / (256.0f * LNV);
-        auto ln_row = [&](float4 (&x)[LNV], int r, bool keep) {
-            float sm = 0.f;
-#pragma unroll
-            for (int j = 0; j < LNV; ++j) sm += (x[j].x + x[j].y) + (x[j].z + x[j].w);
-            const float mean = dpp_wave_sum(sm) * invK;
-            float q = 0.f;
-#pragma unroll
-            for (int j = 0; j < LNV; ++j) {
-                x[j].x -= mean; x[j].y -= mean; x[j].z -= mean; x[j].w -= mean;
-                q += (x[j].x * x[j].x + x[j].y * x[j].y) + (x[j].z * x[j].z + x[j].w * x[j].w);
-            }
-            const float rstd = rsqrtf(dpp_wave_sum(q) * invK + 1e-5f);
-            half_t* dst = xs + r * ldxs + lane * 4;
-#pragma unroll
-            for (int j = 0; j < LNV; ++j) {
-                const f16x4 hv = {(half_t)(x[j].x * rstd * gq[j].x + bq[j].x), (half_t)(x[j].y * rstd * gq[j].y + bq[j].y),
-                                  (half_t)(x[j].z * rstd * gq[j].z + bq[j].z), (half_t)(x[j].w * rstd * gq[j].w + bq[j].w)};
-                if (keep) *reinterpret_cast<f16x4*>(dst + 256 * j) = hv;
-            }
-        };
-        {
-            float4* gbs4 = reinterpret_cast<float4*>(qs + 16 * 72);       // [2 LNV][64] float4 behind the query tile
-            gbs4[wave * 64 + lane] = gbp;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < LNV; ++j) { gq[j] = gbs4[j * 64 + lane]; bq[j] = gbs4[(LNV + j) * 64 + lane]; }
-        }
-        // first trip: straight-line and UNCONDITIONAL (a wave without a row normalises the clamped row it loaded and
-        // keeps nothing): inside an `if (wave < nrow)` hipcc sinks the row loads into the branch, behind the weights
-        ln_row(x0, (wave < nrow) ? wave : nrow - 1, wave < nrow);
+    const float4 bq4 = *reinterpret_cast<const float4*>(bias + hq * 64 + (wave & 3) * 16 + g * 4);
 #pragma unroll 1
-        for (int r = wave + TPS; r < nrow; r += TPS) {                      // groups of more than six rows (prefill)
-            const float4* x4 = reinterpret_cast<const float4*>(X + (long)(grp * R + r) * ldx) + lane;
-            float4 x[LNV];
+    for (int r = wave + TPS; r < nrow; r += TPS) {                          // groups of more than six rows (prefill)
+        const float4* x4 = reinterpret_cast<const float4*>(X + (long)(grp * R + r) * ldx) + lane;
+        float4 x[LNV];
 #pragma unroll
-            for (int j = 0; j < LNV; ++j) x[j] = x4[64 * j];
-            ln_row(x, r, true);
-        }
+        for (int j = 0; j < LNV; ++j) x[j] = x4[64 * j];
+        ln_row(x, r, true);
     }
     WLX_TR_MARK(1);
     __syncthreads();
@@ -562,9 +582,9 @@ bool dec_cq_cross_attn_eligible(int d, int H, int R) {
 void launch_dec_cq_cross_attn(const float* X, long ldx, const float* gamma, const float* beta, const half_t* Wp, const float* bias,
                               float qscale, int d, const half_t* Kp, const half_t* Vp, long item_stride, int H, int R, int groups,
                               int rows, const int* group_item, half_t* part_o, float* part_ml, hipStream_t s) {
-    const int KT = d / 32;
-    hipLaunchKernelGGL((dec_cq_cross_attn_kernel<3, 4>), dim3(H * WLX_XSPLIT * groups), dim3(XA_TPS * 64), cq_cross_attn_shm(d, R), s, X, ldx, gamma, beta,
-                       Wp, bias, qscale, KT, Kp, Vp, item_stride, H, R, rows, group_item, part_o, part_ml WLX_TR_ARG("cq_cross_attn"));
+    // d_model 768 and 12 heads (dec_cq_cross_attn_eligible) are template constants of the one instantiation; grid.y walks the groups
+    hipLaunchKernelGGL((dec_cq_cross_attn_kernel<3, 4>), dim3(H * WLX_XSPLIT, groups), dim3(XA_TPS * 64), cq_cross_attn_shm(d, R), s, X, ldx, gamma, beta,
+                       Wp, group_item, R, rows, Kp, Vp, item_stride, bias, qscale, part_o, part_ml WLX_TR_ARG("cq_cross_attn"));
 }
 
 // ------------------------------------------------------------------ split combine of the cross attention, on its own
