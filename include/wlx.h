@@ -391,6 +391,34 @@ int32_t wlx_generate_ex(wlx_engine* e, int32_t slot, int32_t batch, const int32_
                         int32_t* tokens_out, int32_t tokens_stride,
                         int32_t* n_tokens_out, float* scores_out, float* no_speech_prob_out);
 
+/* ---- keyword boosting: a bias table on the slot (the host compiler is whisperlive_amd/biasing.py) ----
+ * While a table is installed every decode step of the slot (wlx_generate / wlx_generate_ex in beam and sampling mode, and the
+ * wlx_debug_search hooks) runs ONE more launch between the vocabulary projection and the token search, which adds to each live row's
+ * logits, BEFORE anything of the search reads them (pre-softmax, like OpenAI's logit_bias: normalisation, suppress mask, timestamp
+ * rules, penalties and sampling all see the biased row, and the scores / avg_logprob move with it):
+ *   1. `boost` on every edge token of the row's node, one float32 add;
+ *   2. then tok_vals[i] on tok_ids[i] for every entry of the token list, one float32 add (in every node).
+ * The table is an Aho-Corasick automaton over token ids with its failure links closed: node n (0 = root) owns the edges
+ * [edge_off[n], edge_off[n + 1]) of (edge_tok, edge_next), the tokens ascending — every token that leads from n to a node other than
+ * the root; any other token leads to the root, and so does every token >= opts->ids.eot (specials, timestamps). A node that ends a
+ * phrase carries the root's edges (the walk restarts). A row's node at position p is next(node of its parent row at p - 1, token
+ * fed at p), the root at the first generated position; the nodes are kept on the device per (cache row, position) and follow the
+ * beam's re-ordering. A bonus given on a partial match is NOT taken back when the match breaks. A row whose raw distribution defines
+ * no_speech_prob inside the search (the prompt ends on <|startoftranscript|>) is not biased at that step: no_speech_prob is the same
+ * with and without a table.
+ * The table, the states and the pinned staging of the upload live in buffers of the slot at fixed addresses (allocated at the first
+ * call): captured step graphs stay valid across calls and across tables. The upload is asynchronous on the slot's stream.
+ * WLX_ERR_ARG, the installed table (if any) untouched: n_nodes outside 1..WLX_BIAS_MAX_NODES, more than WLX_BIAS_MAX_EDGES edges,
+ * n_tok outside 0..WLX_BIAS_MAX_TOKENS, offsets that do not start at 0 and ascend, edge tokens of a node that do not ascend, an
+ * edge_next outside 1..n_nodes - 1, a token outside the vocabulary, a token named twice in tok_ids, a boost or value that is not finite.
+ * wlx_bias_clear: the slot decodes without a table again (its step is the launch list it was before the first wlx_bias_set). */
+#define WLX_BIAS_MAX_NODES 4096
+#define WLX_BIAS_MAX_EDGES 16384
+#define WLX_BIAS_MAX_TOKENS 1024
+int32_t wlx_bias_set(wlx_engine* e, int32_t slot, int32_t n_nodes, const int32_t* edge_off, const int32_t* edge_tok,
+                     const int32_t* edge_next, float boost, int32_t n_tok, const int32_t* tok_ids, const float* tok_vals);
+int32_t wlx_bias_clear(wlx_engine* e, int32_t slot);
+
 /* One decoder step on [sot]; softmax restricted to `lang_ids`; probs_out[batch][n_lang]. */
 int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot,
                             const int32_t* lang_ids, int32_t n_lang, float* probs_out);
@@ -1004,6 +1032,16 @@ int32_t wlx_debug_align_post(int32_t device, const float* scores, int32_t n, int
                              int32_t* time_indices, int32_t path_stride, int32_t* n_path);
 /* HIP-event times of the slot's last wlx_align_batch: the decoder passes with their score capture, and everything behind them. */
 int32_t wlx_debug_align_timings(wlx_engine* e, int32_t slot, float* pass_ms, float* post_ms);
+
+/* ONE launch of the keyword-boosting kernel (csrc/dec_bias.hip dec_bias_kernel), same conventions, no engine: a table as wlx_bias_set
+ * takes it (checked the same way against `vocab`), `rows` decoder rows of ONE item in beam mode (1..320), logits [rows][ldl] float32
+ * copied in AND out (ldl >= vocab). Row r is fed tokens[r] at position pos[r] (0..447) of a prompt of plen tokens (1..448); the row
+ * that held its hypothesis at pos[r] - 1 is parent[r], whose node there is prev_state[r] (rows that name the same parent at the same
+ * position must agree; not read where pos[r] < plen; a row whose parent sits at pos[r] - 1 in this very launch is refused). nsp_row[r] = 1: the row is left as it is. state_out[r]: the row's node. */
+int32_t wlx_debug_bias_apply(int32_t device, int32_t vocab, int32_t eot, int32_t n_nodes, const int32_t* edge_off, const int32_t* edge_tok,
+                             const int32_t* edge_next, float boost, int32_t n_tok, const int32_t* tok_ids, const float* tok_vals,
+                             float* logits, int32_t rows, int64_t ldl, const int32_t* tokens, const int32_t* pos, const int32_t* parent,
+                             int32_t plen, const int32_t* nsp_row, const int16_t* prev_state, int16_t* state_out);
 
 #ifdef __cplusplus
 }

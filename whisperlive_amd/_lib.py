@@ -15,12 +15,12 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "put_many.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "dec_bias.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "put_many.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
     "wlx_slot_create", "wlx_slot_destroy", "wlx_logmel", "wlx_pcm_put", "wlx_pcm_put_frames", "wlx_pcm_put_frames_split", "wlx_flac_probe", "wlx_pcm_put_flac", "wlx_pcm_put_flac_split", "wlx_wav_probe", "wlx_pcm_put_wav", "wlx_pcm_put_wav_split", "wlx_pcm_put_many", "wlx_pcm_get", "wlx_logmel_resident", "wlx_features_get", "wlx_features_set", "wlx_encode",
-    "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_align", "wlx_align_batch", "wlx_timings_get", "wlx_sync",
+    "wlx_encoder_output_get", "wlx_generate", "wlx_generate_ex", "wlx_detect_language", "wlx_bias_set", "wlx_bias_clear", "wlx_align", "wlx_align_batch", "wlx_timings_get", "wlx_sync",
     "wlx_vad_create", "wlx_vad_destroy", "wlx_vad_probs",
     "wlx_ring_create", "wlx_ring_destroy", "wlx_ring_append", "wlx_ring_state", "wlx_ring_set_format", "wlx_ring_append_frames", "wlx_resample_stream_count",
     "wlx_ring_group_create", "wlx_ring_group_destroy", "wlx_ring_group_lane", "wlx_ring_group_append_frames", "wlx_vad_probs_resident", "wlx_vad_segments", "wlx_logmel_ring",
@@ -38,7 +38,7 @@ EXPORTS = [
     "wlx_debug_dec_gemv", "wlx_debug_dec_cq_cross_attn",
     "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_resample_stream", "wlx_debug_flac_decode", "wlx_debug_flac_timings", "wlx_debug_adpcm_decode",
     "wlx_debug_resample_many", "wlx_debug_flac_decode_many", "wlx_debug_put_many_budget",
-    "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings",
+    "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings", "wlx_debug_bias_apply",
 ]
 
 
@@ -138,6 +138,7 @@ SPK_CLUSTER_MAX = 2048  # wlx.h WLX_SPK_CLUSTER_MAX: rows of one wlx_spk_cluster
 VAD_MAX_BATCH = 64      # wlx.h WLX_VAD_MAX_BATCH: sequences of one wlx_vad_probs_batch / wlx_vad_probs_pcm_batch call
 ALIGN_MAX_BATCH = 64    # wlx.h WLX_ALIGN_MAX_BATCH: entries of one wlx_align_batch call
 ALIGN_MAX_MEDIAN = 15   # wlx.h WLX_ALIGN_MAX_MEDIAN: the widest median filter the device post-processing serves
+BIAS_MAX_NODES, BIAS_MAX_EDGES, BIAS_MAX_TOKENS = 4096, 16384, 1024   # wlx.h WLX_BIAS_MAX_*: the caps of a bias table (wlx_bias_set)
 MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
 PUT_PCM, PUT_FRAMES, PUT_FLAC, PUT_WAV = 0, 1, 2, 3   # wlx.h WLX_PUT_*: the kinds of a wlx_put_entry
@@ -443,6 +444,11 @@ def load() -> C.CDLL:
     lib.wlx_debug_dtw.argtypes = [i32, f32p, i32, i32p, i32p, i32p, i32p, i32, i32p]
     lib.wlx_debug_align_post.argtypes = [i32, f32p, i32, i32, i32p, i32, i32p, i32, f32p, i32p, i32p, i32, i32p]
     lib.wlx_debug_align_timings.argtypes = [vp, i32, f32p, f32p]
+    i16p = C.POINTER(C.c_int16)
+    lib.wlx_bias_set.argtypes = [vp, i32, i32, i32p, i32p, i32p, C.c_float, i32, i32p, f32p]
+    lib.wlx_bias_clear.argtypes = [vp, i32]
+    lib.wlx_debug_bias_apply.argtypes = [i32, i32, i32, i32, i32p, i32p, i32p, C.c_float, i32, i32p, f32p, f32p, i32, i64, i32p, i32p, i32p, i32, i32p,
+                                         i16p, i16p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_ring_group_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):

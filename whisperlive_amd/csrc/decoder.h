@@ -1,6 +1,7 @@
 // decoder.h — launchers for the autoregressive-decoder kernels (decoder.hip, dec_gemv.hip, dec_vocab.hip, search.hip).
 #pragma once
 #include "kernels.h"
+#include "../../include/wlx.h"
 
 namespace wlx {
 
@@ -186,6 +187,34 @@ void launch_search_merge_update3(const float* logits, long ldl, int V, const Sea
                                  const SearchState& st, hipStream_t s);
 // zero the per-call search state (step, done, finished counters, per-item / per-row flags, hypothesis lengths)
 void launch_search_reset(const SearchState& st, int items, int rows, hipStream_t s);
+// ---------------------------------------------------------------- dec_bias.hip
+// (the caps are include/wlx.h's: WLX_BIAS_MAX_NODES 4096 = 256 phrases x 16 tokens, so a state fits a short; WLX_BIAS_MAX_EDGES explicit
+// edges after the failure closure; WLX_BIAS_MAX_TOKENS logit_bias entries)
+// A slot's bias table (device pointers at fixed addresses: a captured step graph stays valid across tables) and its per-row states.
+struct BiasTable {
+    const int* hdr;             // [4] n_nodes, n_edges, n_tok, the bits of the float `boost`
+    const int* edge_off;        // [n_nodes + 1] node n's edges are [edge_off[n], edge_off[n + 1])
+    const int* edge_tok;        // [n_edges] ascending within a node
+    const int* edge_next;       // [n_edges] 1 .. n_nodes - 1
+    const int* tok_ids; const float* tok_vals;   // [n_tok] distinct tokens
+    short* state;               // [cache_rows][448] node of cache row r at position p (like RowTables::intok)
+};
+#define WLX_BIAS_TABLE_INTS (4 + (WLX_BIAS_MAX_NODES + 1) + 2 * WLX_BIAS_MAX_EDGES + 2 * WLX_BIAS_MAX_TOKENS)
+// carves the regions of a table out of one block of WLX_BIAS_TABLE_INTS ints (the device block, or its pinned staging: `state` stays as given)
+inline BiasTable bias_table_at(int* base, short* state) {
+    BiasTable t{};
+    t.hdr = base; t.edge_off = base + 4; t.edge_tok = base + 4 + (WLX_BIAS_MAX_NODES + 1);
+    t.edge_next = t.edge_tok + WLX_BIAS_MAX_EDGES; t.tok_ids = t.edge_next + WLX_BIAS_MAX_EDGES;
+    t.tok_vals = reinterpret_cast<const float*>(t.tok_ids + WLX_BIAS_MAX_TOKENS);
+    t.state = state;
+    return t;
+}
+// checks a table as wlx_bias_set documents it (0, or WLX_ERR_ARG with the message set) and writes it into a block laid out as above
+int bias_table_fill(int* block, int V, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, float boost,
+                    int n_tok, const int32_t* tok_ids, const float* tok_vals);
+// one wave per row, between the vocabulary projection and the search: the row's node from its parent's, then the two adds
+void launch_dec_bias(float* logits, const SearchParams* sp_dev, int rows, const SearchState& st, const BiasTable& bt, hipStream_t s);
+
 // softmax over ids [0, vlim) of row r, probability of token toks[r] -> out[r]   (text_token_probs of Whisper.align)
 void launch_token_prob_rows(const float* logits, long ldl, int vlim, int rows, const int* toks, float* out, hipStream_t s);
 // softmax prob of token `tok` in given logits rows -> out[rows]

@@ -19,8 +19,9 @@ namespace wlx {
 struct StepGraphKey {
     int rows, R, groups, nsteps;
     bool busy, sampling;
+    bool bias;                  // the step launches dec_bias_kernel in front of the search (the slot has a bias table: wlx_bias_set)
     bool operator<(const StepGraphKey& o) const {
-        return std::tie(rows, R, groups, nsteps, busy, sampling) < std::tie(o.rows, o.R, o.groups, o.nsteps, o.busy, o.sampling);
+        return std::tie(rows, R, groups, nsteps, busy, sampling, bias) < std::tie(o.rows, o.R, o.groups, o.nsteps, o.busy, o.sampling, o.bias);
     }
 };
 
@@ -94,6 +95,10 @@ struct Slot {
     bool anc_ident = false;                          // the uploaded row tables have ancrow[r] == r (decode steps; upload_rows)
     SearchState st{};
     SearchParams* d_sp = nullptr;
+    // keyword boosting (wlx_bias_set / wlx_bias_clear; dec_bias.hip): the table's device block and the per-(cache row, position) states, allocated
+    // at the first wlx_bias_set and kept at those addresses for the slot's life; `h_bias` is the block's pinned staging (rewritten only behind a
+    // wait for the stream); `bias_on`: the decode steps launch dec_bias_kernel
+    BiasTable bias{}; int* d_bias = nullptr; int* h_bias = nullptr; bool bias_on = false;
     unsigned* d_suppress = nullptr;
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging
@@ -246,6 +251,7 @@ int prefill_tokens(Engine* e, Slot* s, int item, int crow, const int* tokens, in
                    float* nsp_out);
 int set_anc_rows(Slot* s, const std::vector<short>& anc_host, int first_row, int nrows);
 void launch_search(Engine* e, Slot* s, int rows, int R, int groups, bool sampling);
+void launch_bias(Slot* s, int rows);                       // in front of launch_search: nothing without a bias table
 int generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, const int32_t* plens, int pstride, const int32_t* enc_items,
                   const wlx_gen_opts* o, bool injected_logits, const float* inj, int inj_steps, int32_t* tokens_out, int tstride,
                   int32_t* n_tokens_out, float* scores_out, float* nsp_out);

@@ -333,16 +333,23 @@ static int graph_steps_for(const Slot* s, int rows) {
     return alone ? 2 : 1;
 }
 
+// keyword boosting: with a table installed on the slot (wlx_bias_set) one launch between the vocabulary projection and the search adds the
+// row's bias to its logits (dec_bias.hip); a slot without a table launches nothing here, so its step is the launch list it always was
+void wlx::launch_bias(Slot* s, int rows) {
+    if (s->bias_on) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
+}
+
 static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps) {
     for (int k = 0; k < nsteps; ++k) {
         decoder_pass(e, s, s->step, rows, R, groups, true, true);
+        launch_bias(s, rows);
         launch_search(e, s, rows, R, groups, sampling);
     }
 }
 
 static int get_step_graph(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps, hipGraphExec_t* out) {
     s->busy_variant = device_is_busy(s);
-    const StepGraphKey key{rows, R, groups, nsteps, s->busy_variant, sampling};
+    const StepGraphKey key{rows, R, groups, nsteps, s->busy_variant, sampling, s->bias_on};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { *out = it->second; return WLX_OK; }
     hipGraph_t graph;
@@ -580,6 +587,7 @@ static int gen_loop(Engine* e, Slot* s, int batch, int R, bool sampling, int max
             launch_dec_embed(e->tok_emb16, e->dec_pos, e->spec.d_model, rt, rows, sb.xd, nullptr, st);
             CK(hipMemcpy2DAsync(s->logits, (size_t)s->ldl * 4, inj + (size_t)step * rows * V, (size_t)V * 4, (size_t)V * 4, rows,
                                 hipMemcpyHostToDevice, st));
+            launch_bias(s, rows);
             launch_search(e, s, rows, R, batch, sampling);
             CK(hipGetLastError());
         } else {
@@ -745,6 +753,41 @@ extern "C" int32_t wlx_generate(wlx_engine* e, int32_t slot, int32_t batch, cons
                                 float* no_speech_prob_out) {
     return wlx_generate_ex(e, slot, batch, nullptr, prompts, prompt_lens, prompt_stride, opts, tokens_out, tokens_stride,
                            n_tokens_out, scores_out, no_speech_prob_out);
+}
+
+// ---- keyword boosting: the slot's bias table (include/wlx.h; dec_bias.hip). The device block, the state table and the pinned staging are
+// allocated at the first call and stay where they are, so a step graph captured with a table replays with every later one.
+extern "C" int32_t wlx_bias_set(wlx_engine* e, int32_t slot, int32_t n_nodes, const int32_t* edge_off, const int32_t* edge_tok,
+                                const int32_t* edge_next, float boost, int32_t n_tok, const int32_t* tok_ids, const float* tok_vals) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    // a refused table leaves the installed one whole (and allocates nothing): checked into a host copy first
+    std::vector<int> block((size_t)WLX_BIAS_TABLE_INTS, 0);
+    CKR(bias_table_fill(block.data(), e->spec.vocab, n_nodes, edge_off, edge_tok, edge_next, boost, n_tok, tok_ids, tok_vals));
+    CK(hipSetDevice(e->device));
+    if (!s->d_bias) {
+        int *blk = nullptr, *stage = nullptr;
+        short* state = nullptr;
+        CKR(dalloc(s->allocs, &blk, (size_t)WLX_BIAS_TABLE_INTS, true));
+        CKR(dalloc(s->allocs, &state, (size_t)std::max(s->cache_rows, s->rows_cap) * WLX_T_TEXT, true));
+        CKR(halloc(s->host_allocs, &stage, (size_t)WLX_BIAS_TABLE_INTS));
+        memset(stage, 0, sizeof(int) * WLX_BIAS_TABLE_INTS);
+        s->d_bias = blk; s->h_bias = stage; s->bias = bias_table_at(blk, state);
+    }
+    // the staging may still feed the copy of the previous table: wait for the stream, then rewrite it
+    CK(hipStreamSynchronize(s->stream));
+    memcpy(s->h_bias, block.data(), sizeof(int) * WLX_BIAS_TABLE_INTS);
+    CK(hipMemcpyAsync(s->d_bias, s->h_bias, sizeof(int) * WLX_BIAS_TABLE_INTS, hipMemcpyHostToDevice, s->stream));
+    s->bias_on = true;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_bias_clear(wlx_engine* e, int32_t slot) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    sg_.s->bias_on = false;
+    return WLX_OK;
 }
 
 extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot, const int32_t* lang_ids,

@@ -7,6 +7,7 @@
 //   wlx_debug_dec_gemv           launch_dec_gemv: dec_gemv2_kernel, dec_vocab_kernel, dec_gemv_kernel (dec_gemv.hip, dec_vocab.hip)
 //   wlx_debug_dec_cq_cross_attn  launch_dec_cq_cross_attn (decoder.hip)
 //   wlx_debug_dtw, wlx_debug_align_post   launch_align_dtw / launch_align_cost (align.hip)
+//   wlx_debug_bias_apply         launch_dec_bias (dec_bias.hip)
 // The hooks' conventions are HookScope's (host.h). No engine or slot is needed, and no product code path runs differently because
 // these exist.
 #include "align.h"
@@ -541,4 +542,59 @@ extern "C" int32_t wlx_debug_align_post(int32_t device, const float* scores, int
     CKR(S.download(time_indices, dfi, (size_t)n * path_stride));
     CKR(S.download(n_path, dnp, (size_t)n));
     return S.finish();
+}
+
+// wlx_debug_bias_apply: launch_dec_bias (dec_bias.hip) on a search state built here for one item of `rows` beams
+extern "C" int32_t wlx_debug_bias_apply(int32_t device, int32_t vocab, int32_t eot, int32_t n_nodes, const int32_t* edge_off, const int32_t* edge_tok,
+                                        const int32_t* edge_next, float boost, int32_t n_tok, const int32_t* tok_ids, const float* tok_vals,
+                                        float* logits, int32_t rows, int64_t ldl, const int32_t* tokens, const int32_t* pos, const int32_t* parent,
+                                        int32_t plen, const int32_t* nsp_row, const int16_t* prev_state, int16_t* state_out) {
+    if (!logits || !tokens || !pos || !parent || !nsp_row || !prev_state || !state_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (vocab < 1 || vocab > (1 << 20) || ldl < vocab) return set_error(WLX_ERR_ARG, "vocab %d / ldl %lld", vocab, (long long)ldl);
+    if (rows < 1 || rows > WLX_MAX_DEC_ROWS) return set_error(WLX_ERR_ARG, "rows %d outside 1..%d", rows, WLX_MAX_DEC_ROWS);
+    if (plen < 1 || plen > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "plen %d outside 1..%d", plen, WLX_T_TEXT);
+    // (declared before the scope: the copies below read them until the scope's last wait)
+    std::vector<int> block((size_t)WLX_BIAS_TABLE_INTS, 0), zeros((size_t)rows + 4, 0), one_plen(1, plen);
+    std::vector<short> anc((size_t)rows * WLX_T_TEXT, 0), state((size_t)rows * WLX_T_TEXT, 0);
+    SearchParams sp{};
+    CKR(bias_table_fill(block.data(), vocab, n_nodes, edge_off, edge_tok, edge_next, boost, n_tok, tok_ids, tok_vals));
+    for (int r = 0; r < rows; ++r) {
+        if (pos[r] < 0 || pos[r] >= WLX_T_TEXT) return set_error(WLX_ERR_ARG, "row %d: position %d outside 0..%d", r, pos[r], WLX_T_TEXT - 1);
+        if (parent[r] < 0 || parent[r] >= rows) return set_error(WLX_ERR_ARG, "row %d: parent %d outside 0..%d", r, parent[r], rows - 1);
+        if (prev_state[r] < 0 || prev_state[r] >= n_nodes) return set_error(WLX_ERR_ARG, "row %d: state %d outside 0..%d", r, prev_state[r], n_nodes - 1);
+        if (pos[r] >= 1) {
+            anc[(size_t)r * WLX_T_TEXT + pos[r] - 1] = (short)parent[r];
+            state[(size_t)parent[r] * WLX_T_TEXT + pos[r] - 1] = prev_state[r];
+        }
+        anc[(size_t)r * WLX_T_TEXT + pos[r]] = (short)r;
+    }
+    // the launch writes row r's state at pos[r]: no row may read that word as its parent's (in a decode the rows of an item share a position)
+    for (int q = 0; q < rows; ++q)
+        if (pos[q] >= plen && pos[q] >= 1 && pos[parent[q]] == pos[q] - 1)
+            return set_error(WLX_ERR_ARG, "row %d reads the state row %d writes in this launch (position %d)", q, parent[q], pos[q] - 1);
+    sp.V = vocab; sp.ldl = ldl; sp.items = 1; sp.R = rows; sp.rows = rows; sp.sampling = 0; sp.beam = rows; sp.num_hyp = 1; sp.eot = eot;
+    HookScope S;
+    CKR(S.begin(device));
+    int *dblock = nullptr, *dzero = nullptr, *dplen = nullptr, *dtok = nullptr, *dpos = nullptr, *dnsp = nullptr;
+    short *danc = nullptr, *dstate = nullptr;
+    float* dl = nullptr;
+    SearchParams* dsp = nullptr;
+    CKR(S.upload(&dblock, block.data(), block.size()));
+    CKR(S.upload(&dzero, zeros.data(), zeros.size()));
+    CKR(S.upload(&dplen, one_plen.data(), (size_t)1));
+    CKR(S.upload(&dtok, tokens, (size_t)rows));
+    CKR(S.upload(&dpos, pos, (size_t)rows));
+    CKR(S.upload(&dnsp, nsp_row, (size_t)rows));
+    CKR(S.upload(&danc, anc.data(), anc.size()));
+    CKR(S.upload(&dstate, state.data(), state.size()));
+    CKR(S.upload(&dl, logits, (size_t)rows * ldl));
+    CKR(S.upload(&dsp, &sp, (size_t)1));
+    SearchState st{};
+    st.done = dzero; st.item_done = dzero + 1; st.row_done = dzero + 4; st.plen = dplen; st.token = dtok; st.pos = dpos; st.anc = danc; st.nsp_row = dnsp;
+    launch_dec_bias(dl, dsp, rows, st, bias_table_at(dblock, dstate), S.st);
+    CKR(S.download(logits, dl, (size_t)rows * ldl));
+    CKR(S.download(state.data(), dstate, state.size()));
+    CKR(S.finish());
+    for (int r = 0; r < rows; ++r) state_out[r] = state[(size_t)r * WLX_T_TEXT + pos[r]];
+    return WLX_OK;
 }

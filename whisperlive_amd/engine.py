@@ -610,6 +610,24 @@ class Slot:
             out.append(GenerationResult(seqs, scores, float(nsp[b])))
         return out
 
+    # ---- keyword boosting
+    def set_bias(self, table) -> None:
+        """Install a biasing.BiasTable on the slot (wlx_bias_set): every decode step of its generate calls, and of the debug_search
+        hooks, then runs the bias launch in front of the search. The buffers sit at fixed addresses: captured step graphs are re-used
+        across tables. WlxError (ERR_ARG) for a table the library refuses; the installed one stays."""
+        if table.vocab != self.engine.spec.vocab:
+            raise ValueError(f"the bias table was compiled for a vocabulary of {table.vocab}, the model has {self.engine.spec.vocab}")
+        off, tok, nxt = (np.ascontiguousarray(a, dtype=np.int32) for a in (table.edge_off, table.edge_tok, table.edge_next))
+        ids, vals = np.ascontiguousarray(table.tok_ids, dtype=np.int32), np.ascontiguousarray(table.tok_vals, dtype=np.float32)
+        check(self.lib.wlx_bias_set(self.engine._h, self.sid, table.n_nodes, _i32p(off), _i32p(tok), _i32p(nxt), float(table.boost),
+                                    ids.size, _i32p(ids), _f32p(vals)))
+        self._bias_table = table
+
+    def clear_bias(self) -> None:
+        """Decode without a bias table again (wlx_bias_clear)."""
+        check(self.lib.wlx_bias_clear(self.engine._h, self.sid))
+        self._bias_table = None
+
     def align(self, tokens: Sequence[int], n_sot: int, num_frames: int, heads: Sequence[Tuple[int, int]], eot: int,
               median_filter_width: int = 7, item: int = 0):
         """ctranslate2 Whisper.align for one encoded item: tokens = start_sequence + [no_timestamps] + text + [eot].

@@ -20,6 +20,7 @@ routing — so a 429 or a 401 carries no CORS headers, and every request counts 
 from __future__ import annotations
 
 import collections
+import contextlib
 import json
 import logging
 import re
@@ -178,6 +179,31 @@ def parse_bool_field(value: Optional[str], name: str) -> bool:
     if s not in _TRUE and s not in _FALSE:
         raise _HttpError(400, {"error": f"{name} must be a boolean"})
     return s in _TRUE
+
+
+def keyword_scope(transcriber, keywords: Sequence[str], keywords_boost: Optional[str]):
+    """The `keywords` (repeatable) and `keywords_boost` form fields -> the context manager under which the upload is decoded
+    (WhisperModelHIP.keyword_bias on the request's thread), or None without keywords. _HttpError 400: a boost that is not a finite
+    number, an empty keyword, a boost without keywords, a table past a cap (the message names it: nodes, edges), a transcriber that
+    does not bias."""
+    boost = None
+    if keywords_boost is not None and keywords_boost.strip():
+        try:
+            boost = float(keywords_boost)
+        except ValueError:
+            boost = float("nan")
+        if boost != boost or boost in (float("inf"), float("-inf")):
+            raise _HttpError(400, {"error": "keywords_boost must be a finite number"})
+    if not keywords:
+        if boost is not None:
+            raise _HttpError(400, {"error": "keywords_boost needs at least one keywords field"})
+        return None
+    if not hasattr(transcriber, "keyword_bias"):
+        raise _HttpError(400, {"error": "keywords: this server's transcriber does not bias"})
+    try:
+        return transcriber.keyword_bias(phrases=list(keywords), boost=boost)
+    except ValueError as e:
+        raise _HttpError(400, {"error": f"keywords: {e}"})
 
 
 def file_channels(data: bytes) -> int:
@@ -794,6 +820,7 @@ class _Handler(BaseHTTPRequestHandler):
         chunking_strategy = one("chunking_strategy")
         include = many("include") + many("include[]") or None
         known_speaker_names = many("known_speaker_names") + many("known_speaker_names[]")
+        keywords, keywords_boost = many("keywords") + many("keywords[]"), one("keywords_boost")
         known_speaker_references = fields.get("known_speaker_references", []) + fields.get("known_speaker_references[]", [])
         want_words = bool(timestamp_granularities and "word" in timestamp_granularities)
         rest = self.rest
@@ -801,6 +828,8 @@ class _Handler(BaseHTTPRequestHandler):
         if stream_s in _TRUE:
             if multichannel:     # the segments of a multichannel file are ordered only when its last group is done: nothing to stream
                 raise _HttpError(400, {"error": "multichannel cannot be combined with stream: send the request without stream"})
+            if keywords or keywords_boost:
+                raise _HttpError(400, {"error": "keywords cannot be combined with stream: send the request without stream"})
             return self._stream(file, language, prompt, temperature, want_words, target_language)
 
         ignored_params = []
@@ -828,13 +857,17 @@ class _Handler(BaseHTTPRequestHandler):
                     raise _HttpError(400, {"error": str(e)})
             transcriber = rest.transcriber_for(device_index)
             mc = {"multichannel": True} if multichannel else {}
-            if rest.batcher is not None and not multichannel and not known_speaker_names and not known_speaker_references and not diarize:
-                segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
-                                                        temperature=temperature, word_timestamps=want_words, hotwords=hotwords)
-            else:
-                segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
-                                                      temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)
-            segments = list(segments or [])
+            # keywords: the table is compiled (and refused: 400) before the file is decoded; the upload is then decoded in this thread under
+            # it, not pooled — a decode group has one table. The segments may arrive lazily: they are drawn inside the scope.
+            bias = keyword_scope(transcriber, keywords, keywords_boost)
+            with (bias if bias is not None else contextlib.nullcontext()):
+                if rest.batcher is not None and bias is None and not multichannel and not known_speaker_names and not known_speaker_references and not diarize:
+                    segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
+                                                            temperature=temperature, word_timestamps=want_words, hotwords=hotwords)
+                else:
+                    segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
+                                                          temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)
+                segments = list(segments or [])
             text = render_text(segments, multichannel)
             translated = target_language is not None
             if translated:      # the whole transcript as one translation job, whichever route transcribed it

@@ -397,6 +397,22 @@ class ServeClientBase:
             self.text = self.text[-self.MAX_TRANSCRIPT_LENGTH:]
 
 
+def keyword_options(transcriber, keywords, keywords_boost):
+    """`keywords` (a list of strings) and `keywords_boost` (a number, optional) of a session's first message -> the scope under which
+    the session decodes (WhisperModelHIP.keyword_bias). ValueError: not a list of non-empty strings, a boost that is not a finite
+    number or comes without keywords, a table past a cap (named), a transcriber that does not bias."""
+    if keywords is None:
+        raise ValueError("keywords_boost needs keywords")
+    if not isinstance(keywords, (list, tuple)) or not keywords or not all(isinstance(k, str) and k.strip() for k in keywords):
+        raise ValueError("keywords must be a non-empty list of non-empty strings")
+    if keywords_boost is not None and (isinstance(keywords_boost, bool) or not isinstance(keywords_boost, (int, float))
+                                       or keywords_boost != keywords_boost or abs(keywords_boost) == float("inf")):
+        raise ValueError("keywords_boost must be a finite number")
+    if not hasattr(transcriber, "keyword_bias"):
+        raise ValueError("this server's transcriber does not bias")
+    return transcriber.keyword_bias(phrases=list(keywords), boost=keywords_boost)
+
+
 class ServeClientHIP(ServeClientBase):
     """Backend adaptor for the MI355X engine. Class-level registries mirror the reference's SINGLE_MODEL /
     BATCH_WORKER hooks (faster_whisper_backend.py:15-17) but are keyed by GPU: one shared transcriber per device."""
@@ -406,6 +422,7 @@ class ServeClientHIP(ServeClientBase):
     SINGLE_MODEL_LOCK = threading.Lock()
     BATCH_WORKER = None             # optional whisperlive_amd.batching.BatchInferenceWorker (all devices)
     BATCH_WORKERS = {}              # device index -> BatchInferenceWorker (one per GPU; set by TranscriptionServer)
+    _bias = None                    # the session's keyword table as a scope (WhisperModelHIP.keyword_bias); None: a session without keywords
     BACKEND_NAME = "faster_whisper"  # the stock Python client only keeps completed segments for this string (client.py:182,399)
 
     def __init__(self, websocket, task="transcribe", device=None, language=None, client_uid=None, model="small.en",
@@ -413,7 +430,7 @@ class ServeClientHIP(ServeClientBase):
                  no_speech_thresh=0.45, clip_audio=False, same_output_threshold=7, cache_path="~/.cache/whisper-live/",
                  translation_queue=None, hotwords=None, diarization=None, word_timestamps=False, *,
                  device_index: int = 0, transcriber=None, model_factory=None, serialize_single_model: bool = False,
-                 start_thread: bool = True, max_batch: int = 1):
+                 start_thread: bool = True, max_batch: int = 1, keywords=None, keywords_boost=None):
         super().__init__(client_uid, websocket, send_last_n_segments, no_speech_thresh, clip_audio, same_output_threshold,
                          translation_queue, diarization, word_timestamps)
         self.cache_path = cache_path
@@ -448,6 +465,17 @@ class ServeClientHIP(ServeClientBase):
                                             "message": f"Failed to load model: {str(self.model_size_or_path)}"}))
             self.websocket.close()
             return
+        if keywords or keywords_boost is not None:
+            # `keywords` / `keywords_boost` of the first message: compiled once, here; a value past a cap ends the session like a model
+            # that does not load, with the cap named
+            try:
+                self._bias = keyword_options(self.transcriber, keywords, keywords_boost)
+            except ValueError as e:
+                logging.error(f"keywords refused for {self.client_uid}: {e}")
+                self.websocket.send(json.dumps({"uid": self.client_uid, "status": "ERROR", "message": f"Unsupported keywords: {e}"}))
+                self.websocket.close()
+                del self.transcriber            # (what the server reads as "no session")
+                return
         self.use_vad = use_vad
         self.trans_thread = threading.Thread(target=self.speech_to_text, daemon=True)
         if start_thread:
@@ -564,6 +592,11 @@ class ServeClientHIP(ServeClientBase):
             return None
 
     def transcribe_audio(self, input_sample):
+        if self._bias is not None:
+            # a session with keywords decodes on its own slot, in its own thread, under its table: the batch worker's decode groups
+            # mix sessions, and a group has one table
+            with self._bias:
+                return self._transcribe_direct(input_sample)
         worker = ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS.get(self.device_index)
         if worker is not None:
             from .batching import BatchRequest
@@ -587,6 +620,9 @@ class ServeClientHIP(ServeClientBase):
             if self.language is None and req.info is not None:
                 self.set_language(req.info)
             return req.result
+        return self._transcribe_direct(input_sample)
+
+    def _transcribe_direct(self, input_sample):
         kw = dict(initial_prompt=self.initial_prompt, language=self.language, task=self.task, vad_filter=self.use_vad,
                   vad_parameters=self.vad_parameters if self.use_vad else None, hotwords=self.hotwords,
                   word_timestamps=self.word_timestamps)

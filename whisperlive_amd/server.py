@@ -306,6 +306,7 @@ class TranscriptionServer:
                 max_batch=self.batch_config["max_batch_size"] if self.batch_config is not None else 1,
                 translation_queue=translation_queue,
                 diarization=self._create_diarizer(options, diarization_path, device_index) if diarization_path is not None else None,
+                keywords=options.get("keywords"), keywords_boost=options.get("keywords_boost"),
             )
             if translation_client is not None:
                 client.translation_client, client.translation_thread = translation_client, translation_thread
@@ -387,7 +388,8 @@ class TranscriptionServer:
                     same_output_threshold=options.get("same_output_threshold", 10), cache_path=self.cache_path,
                     hotwords=options.get("hotwords"), word_timestamps=options.get("word_timestamps", False),
                     device_index=device_index, model_factory=self.model_factory,
-                    max_batch=self.batch_config["max_batch_size"] if self.batch_config is not None else 1)
+                    max_batch=self.batch_config["max_batch_size"] if self.batch_config is not None else 1,
+                    keywords=options.get("keywords"), keywords_boost=options.get("keywords_boost"))
 
             session = MultichannelSession(websocket, uid, audio_format, channels, sample_rate, make_child)
             if not session.ready:                         # model load failed: ERROR already sent, socket closed

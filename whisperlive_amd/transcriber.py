@@ -30,6 +30,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _lib
+from . import biasing as _biasing
 from . import vad as _vad
 from . import word_timing as _wt
 from ._lib import ERR_ARG as _ERR_ARG, ERR_DATA as _ERR_DATA, WlxError as _WlxError
@@ -223,6 +224,11 @@ class _EngineModel:
         cap_rows = slot_rows * slot_items if isinstance(slot_rows, int) and isinstance(slot_items, int) else 64
         group = max(1, min(self.MAX_DEC_ROWS, max(cap_rows, rows_per_item)) // rows_per_item)
         items = encoder_output.items if encoder_output.items is not None else list(range(encoder_output.batch))
+        # keyword boosting: the calling thread's table (WhisperModelHIP.keyword_bias) goes onto the slot this call decodes on; a slot that
+        # never saw a table is left alone
+        table = _biasing.current()
+        if table is not None or getattr(slot, "_bias_table", None) is not None:
+            _biasing.install(slot, table)
         res = []
         for a in range(0, len(prompts), group):
             res.extend(slot.generate(prompts[a:a + group], o.token_ids, beam_size=beam_size, patience=patience,
@@ -453,6 +459,17 @@ class WhisperModelHIP:
     def _next_seed(self) -> int:
         return next(self._seed)
 
+    def keyword_bias(self, phrases=None, boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None):
+        """Context manager: inside the block every generate of the CALLING THREAD decodes with this bias table on its slot — the
+        streaming transcriber, BatchedInferencePipeline.transcribe, transcribe_many (one table per job) and the temperature fallback
+        alike. `phrases`: strings or token lists to boost (biasing.py: an automaton over token ids, `boost` added to the logit of every
+        token that continues a match; default biasing.DEFAULT_BOOST, which is not tuned); `logit_bias`: {token id: value}, added in
+        every state, OpenAI style. Pre-softmax: the scores / avg_logprob are those of the biased distribution, and a bonus given on a
+        partial match is not taken back. The table is compiled (and refused: ValueError names the cap) here, before the block runs.
+        Other threads are untouched; scopes nest. Decode groups that mix tables are not served: one table per call."""
+        return _biasing.scope(_biasing.compile_bias(phrases, boost, logit_bias, tokenizer=self._base_tokenizer, vocab=self.spec.vocab,
+                                                    eot=self.token_ids.eot))
+
     def close(self):
         with self._slots_lock:
             for s in self._slots:
@@ -588,7 +605,18 @@ class WhisperModelHIP:
                    chunk_length: Optional[int] = None, clip_timestamps: Union[str, List[float]] = "0",
                    hallucination_silence_threshold: Optional[float] = None, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
+                   *, keywords=None, keywords_boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None,
                    ) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
+        if keywords is not None or logit_bias is not None:
+            # keyword boosting for this call alone (see keyword_bias): compiled before any audio work, so a refused table costs nothing
+            with self.keyword_bias(phrases=keywords, boost=keywords_boost, logit_bias=logit_bias):
+                return self.transcribe(audio, language, task, log_progress, beam_size, best_of, patience, length_penalty, repetition_penalty,
+                                       no_repeat_ngram_size, temperature, compression_ratio_threshold, log_prob_threshold,
+                                       no_speech_threshold, condition_on_previous_text, prompt_reset_on_temperature, initial_prompt, prefix,
+                                       suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp, word_timestamps,
+                                       prepend_punctuations, append_punctuations, multilingual, vad_filter, vad_parameters, max_new_tokens,
+                                       chunk_length, clip_timestamps, hallucination_silence_threshold, hotwords,
+                                       language_detection_threshold, language_detection_segments)
         sr = self.feature_extractor.sampling_rate
         if multilingual and not self.model.is_multilingual:
             self.logger.warning("The current model is English-only but the multilingual parameter is set to True; "
