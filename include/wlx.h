@@ -1043,6 +1043,50 @@ int32_t wlx_debug_bias_apply(int32_t device, int32_t vocab, int32_t eot, int32_t
                              float* logits, int32_t rows, int64_t ldl, const int32_t* tokens, const int32_t* pos, const int32_t* parent,
                              int32_t plen, const int32_t* nsp_row, const int16_t* prev_state, int16_t* state_out);
 
+/* The probability kernels of search.hip and the data-movement kernels of the decoder pass, ONE launch each of the launcher the engine
+ * calls, same conventions (host arrays, a private stream of `device`, outputs copied in AND out, WLX_ERR_ARG before any launch with
+ * the outputs untouched: a null pointer and every limit named below).
+ * No call may ask for more than 2^28 elements in any one array: rows * ldl for the logits; vocab * d and rows * d; feats_len, ld, item_stride
+ * and items * featT_stride; cap. The outputs `out` and `probs` hold WLX_DEBUG_GUARD words MORE than the kernel owns (rows + 64, rows * n + 64),
+ * copied in and out with the rest: a store past the last row shows in them.
+ * All three softmax forms compute exp(l_t - max) / sum exp(l_i - max) in float32 over the admitted ids of row r of
+ * logits [rows][ldl] (ldl >= the columns read; columns past them are never read). A logit of -inf contributes exactly 0 and a
+ * target at -inf gives exactly 0. A row whose EVERY admitted logit is -inf is outside the contract (max = -inf, 0 / 0): the engine
+ * never produces one (the raw logits of the vocabulary projection are finite) and the hooks do not look for it.
+ * wlx_debug_token_prob (token_prob_kernel, no_speech_prob of a prefill): out[r] = softmax over ids [0, V) at id tok, the same id for
+ *   every row. 1 <= rows <= 65535, 1 <= V <= 2^20, ldl >= V, 0 <= tok < V.
+ * wlx_debug_token_prob_rows (token_prob_rows_kernel, text_token_probs of wlx_align / wlx_align_batch): out[r] = softmax over ids
+ *   [0, vlim) at id toks[r]; a target outside [0, vlim) gives exactly 0 (ids from vlim on — end-of-text and above — are no text).
+ *   1 <= rows <= 65535, 1 <= vlim <= 2^20, ldl >= vlim; toks[r] is any int32.
+ * wlx_debug_lang_probs (lang_probs_kernel, wlx_detect_language): probs[r][i] = softmax over the n ids `ids` at ids[i], probs
+ *   [rows][n]. 1 <= rows <= 65535, 1 <= n <= WLX_LANG_MAX (the slot's id table; wlx_detect_language has the same limit),
+ *   0 <= ids[i] < ldl. Ids may repeat and come in any order; a repeated id counts once per mention in the denominator. */
+#define WLX_LANG_MAX 256
+#define WLX_DEBUG_GUARD 64
+int32_t wlx_debug_token_prob(int32_t device, const float* logits, int64_t ldl, int32_t V, int32_t rows, int32_t tok, float* out);
+int32_t wlx_debug_token_prob_rows(int32_t device, const float* logits, int64_t ldl, int32_t vlim, int32_t rows, const int32_t* toks,
+                                  float* out);
+int32_t wlx_debug_lang_probs(int32_t device, const float* logits, int64_t ldl, int32_t rows, const int32_t* ids, int32_t n,
+                             float* probs);
+/* launch_dec_embed (dec_embed_kernel): x[r][0 .. d) = float(tok_emb[tokens[r]][.]) + pos_emb[pos[r]][.] in float32 (one rounding), with
+ * tok_emb fp16 [vocab][d] and pos_emb float32 [n_pos][d]; the kernel also notes the token a cache row is fed: the hook gives row r the
+ * cache row r, intok [rows][448] int32 (copied in AND out) gets intok[r][pos[r]] = tokens[r] and nothing else. d a multiple of 4 in
+ * 4..8192 (8-byte loads of the fp16 row), 1 <= vocab <= 2^20, 1 <= n_pos <= 448, 1 <= rows <= 65535, 0 <= tokens[r] < vocab,
+ * 0 <= pos[r] < n_pos. Tokens may repeat. */
+int32_t wlx_debug_dec_embed(int32_t device, const uint16_t* tok_emb, int32_t vocab, const float* pos_emb, int32_t n_pos, int32_t d,
+                            const int32_t* tokens, const int32_t* pos, int32_t rows, float* x, int32_t* intok);
+/* launch_prep_windows (prep_window_kernel): item i reads feats + i * item_stride as [n_mels][ld] float32 and writes its window
+ * featT + i * featT_stride as fp16 rows of n_mels: row 1 + t = frame seek[i] + t for t < seg[i], zeros for seg[i] <= t < 3000; rows 0
+ * and 3001 (the convolution's padding) and everything behind row 3001 are not written. 1 <= n_mels <= 128 (the kernel's LDS tile),
+ * 1 <= items <= 64 (the by-value window table), seek[i] >= 0, 0 <= seg[i] <= 3000, seek[i] + seg[i] <= ld, item_stride >= 0 with
+ * feats_len >= (items - 1) * item_stride + (n_mels - 1) * ld + max(seek + seg), featT_stride >= 3002 * n_mels;
+ * featT holds items * featT_stride halfs. */
+int32_t wlx_debug_prep_windows(int32_t device, const float* feats, int64_t feats_len, int64_t ld, int32_t n_mels, int64_t item_stride,
+                               int32_t items, const int32_t* seek, const int32_t* seg, uint16_t* featT, int64_t featT_stride);
+/* launch_f32_to_f16 (f32_to_f16_kernel, the token embedding's table at engine creation): dst[i] = fp16(src[i]), round to nearest
+ * even, values past the fp16 range to +-inf, NaN to NaN. dst holds cap >= n halfs (copied in AND out). 1 <= n <= cap <= 2^28. */
+int32_t wlx_debug_f32_to_f16(int32_t device, const float* src, int64_t n, uint16_t* dst, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,10 @@ byte no thread owns bit-identical to the +-1000 it was filled with. tests/test_w
 nearest wrong answers fall outside the same bounds. Refusal tests: every documented limit is WLX_ERR_ARG with the outputs
 unchanged (the hooks return before anything is launched). wlx_debug_gemm runs launch_gemm / pack.hip the same way: the engine's
 shapes on the launcher's pick, every form forced, form coverage and bit-identity across forms. The decode GEMV chain and the fused
-dec_cq_cross_attn kernel have their own module of the same kind (tests/test_gpu_dec_gemv_kernels.py); search.hip has token-exact
-injected-logits tests. Out of scope here: log-mel and VAD."""
+dec_cq_cross_attn kernel have their own module of the same kind (tests/test_gpu_dec_gemv_kernels.py), and so have the softmax
+kernels behind no_speech_prob, detect_language and the word probabilities with the data-movement kernels dec_embed, prep_window and
+f32_to_f16 (tests/test_gpu_prob_kernels.py); the search of search.hip has token-exact injected-logits tests. Out of scope here:
+log-mel and VAD, which are held to their oracles."""
 import os
 
 import numpy as np

@@ -39,6 +39,8 @@ EXPORTS = [
     "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_resample_stream", "wlx_debug_flac_decode", "wlx_debug_flac_timings", "wlx_debug_adpcm_decode",
     "wlx_debug_resample_many", "wlx_debug_flac_decode_many", "wlx_debug_put_many_budget",
     "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings", "wlx_debug_bias_apply",
+    "wlx_debug_token_prob", "wlx_debug_token_prob_rows", "wlx_debug_lang_probs", "wlx_debug_dec_embed", "wlx_debug_prep_windows",
+    "wlx_debug_f32_to_f16",
 ]
 
 
@@ -449,6 +451,12 @@ def load() -> C.CDLL:
     lib.wlx_bias_clear.argtypes = [vp, i32]
     lib.wlx_debug_bias_apply.argtypes = [i32, i32, i32, i32, i32p, i32p, i32p, C.c_float, i32, i32p, f32p, f32p, i32, i64, i32p, i32p, i32p, i32, i32p,
                                          i16p, i16p]
+    lib.wlx_debug_token_prob.argtypes = [i32, f32p, i64, i32, i32, i32, f32p]
+    lib.wlx_debug_token_prob_rows.argtypes = [i32, f32p, i64, i32, i32, i32p, f32p]
+    lib.wlx_debug_lang_probs.argtypes = [i32, f32p, i64, i32, i32p, i32, f32p]
+    lib.wlx_debug_dec_embed.argtypes = [i32, u16p, i32, f32p, i32, i32, i32p, i32p, i32, f32p, i32p]
+    lib.wlx_debug_prep_windows.argtypes = [i32, f32p, i64, i64, i32, i64, i32, i32p, i32p, u16p, i64]
+    lib.wlx_debug_f32_to_f16.argtypes = [i32, f32p, i64, u16p, i64]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_ring_group_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):

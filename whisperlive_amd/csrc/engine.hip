@@ -538,8 +538,8 @@ extern "C" int32_t wlx_slot_create(wlx_engine* e, int32_t max_batch, int32_t max
         CKR(dalloc(s->allocs, &s->d_align_prob, (size_t)WLX_T_TEXT, true));
         CKR(dalloc(s->allocs, &s->d_sp, 1, true));
         CKR(dalloc(s->allocs, &s->d_suppress, (size_t)(1024 * 52 / 32), true));
-        CKR(dalloc(s->allocs, &s->d_lang_ids, 256, true));
-        CKR(dalloc(s->allocs, &s->d_probs, (size_t)B * 256, true));
+        CKR(dalloc(s->allocs, &s->d_lang_ids, WLX_LANG_MAX, true));
+        CKR(dalloc(s->allocs, &s->d_probs, (size_t)B * WLX_LANG_MAX, true));
         CKR(dalloc(s->allocs, &s->d_tokprob, (size_t)RC, true));
         s->h_stage_ints = 1 << 16;
         CKR(halloc(s->host_allocs, &s->h_stage, s->h_stage_ints));

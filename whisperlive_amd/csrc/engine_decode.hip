@@ -796,7 +796,7 @@ extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batc
     CKR(slot_acquire(e, slot, sg_));
     Slot* s = sg_.s;
     if (batch < 1 || batch > s->enc_batch) return set_error(WLX_ERR_STATE, "detect_language before encode");
-    if (!lang_ids || n_lang < 1 || n_lang > 256 || !probs_out) return set_error(WLX_ERR_ARG, "bad language id list");
+    if (!lang_ids || n_lang < 1 || n_lang > WLX_LANG_MAX || !probs_out) return set_error(WLX_ERR_ARG, "bad language id list");
     if (sot < 0 || sot >= e->spec.vocab) return set_error(WLX_ERR_ARG, "bad sot id");
     for (int i = 0; i < n_lang; ++i) if (lang_ids[i] < 0 || lang_ids[i] >= e->spec.vocab) return set_error(WLX_ERR_ARG, "bad language id");
     CK(hipSetDevice(e->device));

@@ -8,6 +8,10 @@
 //   wlx_debug_dec_cq_cross_attn  launch_dec_cq_cross_attn (decoder.hip)
 //   wlx_debug_dtw, wlx_debug_align_post   launch_align_dtw / launch_align_cost (align.hip)
 //   wlx_debug_bias_apply         launch_dec_bias (dec_bias.hip)
+//   wlx_debug_token_prob, _token_prob_rows, _lang_probs   launch_token_prob / _token_prob_rows / launch_lang_probs (search.hip)
+//   wlx_debug_dec_embed          launch_dec_embed (decoder.hip)
+//   wlx_debug_prep_windows       launch_prep_windows (logmel.hip)
+//   wlx_debug_f32_to_f16         launch_f32_to_f16 (pack.hip)
 // The hooks' conventions are HookScope's (host.h). No engine or slot is needed, and no product code path runs differently because
 // these exist.
 #include "align.h"
@@ -597,4 +601,142 @@ extern "C" int32_t wlx_debug_bias_apply(int32_t device, int32_t vocab, int32_t e
     CKR(S.finish());
     for (int r = 0; r < rows; ++r) state_out[r] = state[(size_t)r * WLX_T_TEXT + pos[r]];
     return WLX_OK;
+}
+
+// ---- the small softmax kernels of search.hip: the numbers the host thresholds (no_speech_prob, detect_language, word probabilities)
+static int prob_hook_rows(const float* logits, int64_t ldl, int64_t cols, int32_t rows, const void* out) {
+    if (!logits || !out) return set_error(WLX_ERR_ARG, "null argument");
+    if (rows < 1 || rows > 65535) return set_error(WLX_ERR_ARG, "rows %d outside 1..65535", rows);
+    if (cols < 1 || cols > (1 << 20)) return set_error(WLX_ERR_ARG, "%lld admitted ids outside 1..2^20", (long long)cols);
+    if (ldl < cols || ldl > (1 << 28) || (int64_t)rows * ldl > (1 << 28))
+        return set_error(WLX_ERR_ARG, "ldl %lld must cover the %lld admitted ids, rows * ldl stay within 2^28 floats", (long long)ldl, (long long)cols);
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_debug_token_prob(int32_t device, const float* logits, int64_t ldl, int32_t V, int32_t rows, int32_t tok, float* out) {
+    CKR(prob_hook_rows(logits, ldl, V, rows, out));
+    if (tok < 0 || tok >= V) return set_error(WLX_ERR_ARG, "token %d outside 0..%d", tok, V - 1);
+    HookScope S;
+    CKR(S.begin(device));
+    float *dl = nullptr, *dout = nullptr;
+    CKR(S.upload(&dl, logits, (size_t)rows * ldl));
+    CKR(S.upload(&dout, out, (size_t)rows + WLX_DEBUG_GUARD));
+    launch_token_prob(dl, ldl, V, rows, tok, dout, S.st);
+    CKR(S.download(out, dout, (size_t)rows + WLX_DEBUG_GUARD));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_debug_token_prob_rows(int32_t device, const float* logits, int64_t ldl, int32_t vlim, int32_t rows, const int32_t* toks,
+                                             float* out) {
+    CKR(prob_hook_rows(logits, ldl, vlim, rows, out));
+    if (!toks) return set_error(WLX_ERR_ARG, "null argument");
+    HookScope S;
+    CKR(S.begin(device));
+    float *dl = nullptr, *dout = nullptr;
+    int32_t* dt = nullptr;
+    CKR(S.upload(&dl, logits, (size_t)rows * ldl));
+    CKR(S.upload(&dt, toks, (size_t)rows));
+    CKR(S.upload(&dout, out, (size_t)rows + WLX_DEBUG_GUARD));
+    launch_token_prob_rows(dl, ldl, vlim, rows, dt, dout, S.st);
+    CKR(S.download(out, dout, (size_t)rows + WLX_DEBUG_GUARD));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_debug_lang_probs(int32_t device, const float* logits, int64_t ldl, int32_t rows, const int32_t* ids, int32_t n,
+                                        float* probs) {
+    CKR(prob_hook_rows(logits, ldl, 1, rows, probs));
+    if (!ids) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_LANG_MAX) return set_error(WLX_ERR_ARG, "n %d outside 1..%d (the slot's id table)", n, WLX_LANG_MAX);
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= ldl) return set_error(WLX_ERR_ARG, "id %d (entry %d) outside the row of %lld columns", ids[i], i, (long long)ldl);
+    HookScope S;
+    CKR(S.begin(device));
+    float *dl = nullptr, *dp = nullptr;
+    int32_t* di = nullptr;
+    CKR(S.upload(&dl, logits, (size_t)rows * ldl));
+    CKR(S.upload(&di, ids, (size_t)n));
+    CKR(S.upload(&dp, probs, (size_t)rows * n + WLX_DEBUG_GUARD));
+    launch_lang_probs(dl, ldl, rows, di, n, dp, S.st);
+    CKR(S.download(probs, dp, (size_t)rows * n + WLX_DEBUG_GUARD));
+    return S.finish();
+}
+
+// ---- the data-movement kernels of the decoder pass
+extern "C" int32_t wlx_debug_dec_embed(int32_t device, const uint16_t* tok_emb, int32_t vocab, const float* pos_emb, int32_t n_pos, int32_t d,
+                                       const int32_t* tokens, const int32_t* pos, int32_t rows, float* x, int32_t* intok) {
+    if (!tok_emb || !pos_emb || !tokens || !pos || !x || !intok) return set_error(WLX_ERR_ARG, "null argument");
+    // the kernel moves f16x4 / float4 pieces of a row
+    if (d < 4 || d % 4 || d > 8192) return set_error(WLX_ERR_ARG, "d %d must be a multiple of 4 in 4..8192", d);
+    if (vocab < 1 || vocab > (1 << 20)) return set_error(WLX_ERR_ARG, "vocab %d outside 1..2^20", vocab);
+    if (n_pos < 1 || n_pos > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "n_pos %d outside 1..%d", n_pos, WLX_T_TEXT);
+    if (rows < 1 || rows > 65535) return set_error(WLX_ERR_ARG, "rows %d outside 1..65535", rows);
+    if ((int64_t)vocab * d > (1 << 28) || (int64_t)rows * d > (1 << 28))
+        return set_error(WLX_ERR_ARG, "vocab * d and rows * d must stay within 2^28 elements");
+    for (int r = 0; r < rows; ++r) {
+        if (tokens[r] < 0 || tokens[r] >= vocab) return set_error(WLX_ERR_ARG, "row %d: token %d outside 0..%d", r, tokens[r], vocab - 1);
+        if (pos[r] < 0 || pos[r] >= n_pos) return set_error(WLX_ERR_ARG, "row %d: position %d outside 0..%d", r, pos[r], n_pos - 1);
+    }
+    std::vector<int32_t> cache((size_t)rows);                   // (declared before the scope: the copy reads it until the scope's last wait)
+    for (int r = 0; r < rows; ++r) cache[r] = r;
+    HookScope S;
+    CKR(S.begin(device));
+    half_t* dte = nullptr;
+    float *dpe = nullptr, *dx = nullptr;
+    int32_t *dtok = nullptr, *dpos = nullptr, *dcache = nullptr, *dintok = nullptr;
+    CKR(S.upload(&dte, h16(tok_emb), (size_t)vocab * d));
+    CKR(S.upload(&dpe, pos_emb, (size_t)n_pos * d));
+    CKR(S.upload(&dtok, tokens, (size_t)rows));
+    CKR(S.upload(&dpos, pos, (size_t)rows));
+    CKR(S.upload(&dcache, cache.data(), (size_t)rows));
+    CKR(S.upload(&dintok, intok, (size_t)rows * WLX_T_TEXT));
+    CKR(S.upload(&dx, x, (size_t)rows * d));
+    RowTables rt{};
+    rt.token = dtok; rt.pos = dpos; rt.cache = dcache; rt.intok = dintok;
+    launch_dec_embed(dte, dpe, d, rt, rows, dx, nullptr, S.st);
+    CKR(S.download(x, dx, (size_t)rows * d));
+    CKR(S.download(intok, dintok, (size_t)rows * WLX_T_TEXT));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_debug_prep_windows(int32_t device, const float* feats, int64_t feats_len, int64_t ld, int32_t n_mels, int64_t item_stride,
+                                          int32_t items, const int32_t* seek, const int32_t* seg, uint16_t* featT, int64_t featT_stride) {
+    if (!feats || !seek || !seg || !featT) return set_error(WLX_ERR_ARG, "null argument");
+    // prep_window_kernel stages a block's frames in tile[128][33]; PrepWindows holds 64 windows by value
+    if (n_mels < 1 || n_mels > 128) return set_error(WLX_ERR_ARG, "n_mels %d outside 1..128", n_mels);
+    if (items < 1 || items > 64) return set_error(WLX_ERR_ARG, "items %d outside 1..64", items);
+    if (ld < 1 || ld > (1LL << 28) || item_stride < 0 || item_stride > (1LL << 28) || feats_len < 1 || feats_len > (1LL << 28))
+        return set_error(WLX_ERR_ARG, "ld %lld / item_stride %lld / feats_len %lld outside 1 (0 for the stride) .. 2^28", (long long)ld, (long long)item_stride, (long long)feats_len);
+    if (featT_stride < (int64_t)(WLX_N_FRAMES + 2) * n_mels || featT_stride > (1LL << 28) || (int64_t)items * featT_stride > (1LL << 28))
+        return set_error(WLX_ERR_ARG, "featT_stride %lld does not hold %d rows of %d, or items * featT_stride exceeds 2^28", (long long)featT_stride, WLX_N_FRAMES + 2, n_mels);
+    PrepWindows pw{};
+    for (int i = 0; i < items; ++i) {
+        if (seek[i] < 0 || seg[i] < 0 || seg[i] > WLX_N_FRAMES || (int64_t)seek[i] + seg[i] > ld)
+            return set_error(WLX_ERR_ARG, "item %d: window [%d, %d + %d) outside 0..3000 frames of a row of %lld", i, seek[i], seek[i], seg[i], (long long)ld);
+        if ((int64_t)i * item_stride + (int64_t)(n_mels - 1) * ld + seek[i] + seg[i] > feats_len)
+            return set_error(WLX_ERR_ARG, "item %d: its window ends behind feats (%lld floats)", i, (long long)feats_len);
+        pw.seek[i] = seek[i]; pw.seg[i] = seg[i];
+    }
+    HookScope S;
+    CKR(S.begin(device));
+    float* df = nullptr;
+    half_t* dT = nullptr;
+    CKR(S.upload(&df, feats, (size_t)feats_len));
+    CKR(S.upload(&dT, h16(featT), (size_t)items * featT_stride));
+    launch_prep_windows(df, ld, n_mels, item_stride, pw, items, dT, featT_stride, S.st);
+    CKR(S.download(h16(featT), dT, (size_t)items * featT_stride));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_debug_f32_to_f16(int32_t device, const float* src, int64_t n, uint16_t* dst, int64_t cap) {
+    if (!src || !dst) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || cap < n || cap > (1LL << 28)) return set_error(WLX_ERR_ARG, "n %lld outside 1..cap, or cap %lld above 2^28", (long long)n, (long long)cap);
+    HookScope S;
+    CKR(S.begin(device));
+    float* ds = nullptr;
+    half_t* dd = nullptr;
+    CKR(S.upload(&ds, src, (size_t)n));
+    CKR(S.upload(&dd, h16(dst), (size_t)cap));
+    launch_f32_to_f16(ds, dd, n, S.st);
+    CKR(S.download(h16(dst), dd, (size_t)cap));
+    return S.finish();
 }
