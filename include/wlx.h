@@ -758,6 +758,29 @@ int32_t wlx_spk_cluster(wlx_spk* spk, const float* emb, int32_t n, int32_t dim, 
 int32_t wlx_spk_diarize_pcm(wlx_spk* spk, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts, const int64_t* n_samples,
                             int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, float* emb_out,
                             float* dist_out, float* centroids, int32_t* n_clusters);
+/* A wave of files: wlx_spk_diarize_pcm of 1 <= n_files <= WLX_SPK_MANY_MAX_FILES DIFFERENT items of one slot behind ONE wait. File f is
+ * item items[f] with n_windows[f] windows (0..WLX_SPK_CLUSTER_MAX) and options opts[f]; starts / n_samples / labels / status / emb_out /
+ * centroids are packed file by file, file f at window w0_f = n_windows[0] + .. + n_windows[f-1] (centroids: K_f rows from row w0_f).
+ * The windows that take part, of all files in file order, are grouped greedily into ragged passes of at most WLX_SPK_MAX_BATCH windows
+ * and max_seconds of samples — a pass may span files — and enqueued back to back into one table; then ONE distance-matrix launch, ONE
+ * clustering launch (a workgroup per file, the files side by side on as many CUs) and ONE centroid launch over the files with two or
+ * more such windows, and the downloads. For every file labels, status, n_clusters[f], its rows of emb_out and its centroids are, bit
+ * for bit, what wlx_spk_diarize_pcm returns for that item, those windows and those options (short windows, m = 1 and m = 0 included).
+ * file_status[f] = WLX_OK, or WLX_ERR_STATE for an item without resident PCM or with a window past its resident count: that file's
+ * labels are -1, its window status WLX_ERR_STATE, its rows zero, n_clusters[f] = 0, and the other files go on. The call returns
+ * WLX_ERR_STATE for a busy slot, and WLX_ERR_ARG — before any launch and with nothing written — for: a null required pointer (emb_out
+ * and centroids may be null), n_files out of range, a file with a negative count or more than WLX_SPK_CLUSTER_MAX windows, more than
+ * WLX_SPK_MANY_MAX_ROWS windows in all, matrices (the sum of m_f^2 over the windows that take part) over WLX_SPK_MANY_MAX_CELLS
+ * floats, options as above, a negative start or count, a window over max_seconds, different devices, an item outside the slot or named
+ * twice. The buffers are made by the first call: an engine that never calls this pays nothing for them. */
+#define WLX_SPK_MANY_MAX_FILES 64
+#define WLX_SPK_MANY_MAX_ROWS  8192          /* windows of all files together */
+#define WLX_SPK_MANY_MAX_CELLS (4u * WLX_SPK_CLUSTER_MAX * WLX_SPK_CLUSTER_MAX)   /* floats of all distance matrices together */
+int32_t wlx_spk_diarize_many(wlx_spk* spk, wlx_engine* e, int32_t slot, int32_t n_files, const int32_t* items,
+                             const int32_t* n_windows /*[n_files]*/, const int64_t* starts, const int64_t* n_samples /* packed, file by file */,
+                             const wlx_spk_cluster_opts* opts /*[n_files]*/, int32_t* labels, int32_t* status /* per window */,
+                             int32_t* file_status, int32_t* n_clusters /*[n_files]*/,
+                             float* emb_out, float* centroids /* nullable; packed [sum n][E] */);
 
 /* ==== everything below: TEST / PROFILING hooks (used only by tests/, scripts/ and bench.py's roofline leg; not part of
  * the drop-in boundary; the product entry points end here) ================================================================= */
@@ -868,7 +891,16 @@ int32_t wlx_spk_debug_affinity(int32_t device, const float* X, int32_t n, int32_
  * *n_merges, *n_clusters; rows of merges / heights from *n_merges on come back unchanged. */
 int32_t wlx_spk_debug_ahc(int32_t device, const float* dist, int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels,
                           int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters);
-/* device times (HIP events) of the last wlx_spk_cluster or wlx_spk_diarize_pcm that clustered: the distance matrix, the clustering */
+/* The many-forms of the two, one launch each over 1 <= n_files <= WLX_SPK_MANY_MAX_FILES files packed back to back: file f has ns[f]
+ * rows (1..WLX_SPK_CLUSTER_MAX; all together at most WLX_SPK_MANY_MAX_ROWS, their matrices at most WLX_SPK_MANY_MAX_CELLS floats) at
+ * row0_f = ns[0] + .. + ns[f-1] of X / labels / heights, its matrix [ns[f]][ns[f]] at ns[0]^2 + .. + ns[f-1]^2 of dist, its merges at
+ * 2 * row0_f of merges (room for ns[f] pairs, ns[f] - 1 at the most written). opts, n_merges, n_clusters: one entry per file. Every
+ * file's results have the bits of wlx_spk_debug_affinity / wlx_spk_debug_ahc on that file alone. */
+int32_t wlx_spk_debug_affinity_many(int32_t device, const float* X, int32_t n_files, const int32_t* ns, int32_t dim, float* dist_out);
+int32_t wlx_spk_debug_ahc_many(int32_t device, const float* dist, int32_t n_files, const int32_t* ns, const wlx_spk_cluster_opts* opts,
+                               int32_t* labels, int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters);
+/* device times (HIP events) of the last wlx_spk_cluster, wlx_spk_diarize_pcm or wlx_spk_diarize_many that clustered: the distance
+ * matrix launch, the clustering launch (of a many-call: its ONE launch of each, over all its files) */
 int32_t wlx_spk_debug_cluster_timings(wlx_spk* spk, float* affinity_ms, float* ahc_ms);
 
 /* Whisper kernels, one launch each (csrc/kernel_hooks.hip), same conventions: host arrays (fp16 as uint16 bits), a private stream

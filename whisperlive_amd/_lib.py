@@ -27,13 +27,14 @@ EXPORTS = [
     "wlx_logmel_chunks", "wlx_logmel_chunks_multi", "wlx_vad_probs_pcm", "wlx_vad_probs_batch", "wlx_vad_probs_pcm_batch",
     "wlx_mt_create", "wlx_mt_destroy", "wlx_mt_slot_create", "wlx_mt_slot_destroy", "wlx_mt_translate", "wlx_mt_translate_many",
     "wlx_spk_create", "wlx_spk_destroy", "wlx_spk_embed", "wlx_spk_embed_batch", "wlx_spk_embed_pcm_batch", "wlx_spk_embed_ring_batch",
-    "wlx_spk_cluster", "wlx_spk_diarize_pcm",
+    "wlx_spk_cluster", "wlx_spk_diarize_pcm", "wlx_spk_diarize_many",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_search_batch", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
     "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
     "wlx_mt_debug_embed", "wlx_mt_debug_search",
     "wlx_spk_debug_timings", "wlx_spk_debug_fbank", "wlx_spk_debug_conv", "wlx_spk_debug_pool",
     "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
-    "wlx_spk_debug_affinity", "wlx_spk_debug_ahc", "wlx_spk_debug_cluster_timings",
+    "wlx_spk_debug_affinity", "wlx_spk_debug_ahc", "wlx_spk_debug_affinity_many", "wlx_spk_debug_ahc_many",
+    "wlx_spk_debug_cluster_timings",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
     "wlx_debug_dec_gemv", "wlx_debug_dec_cq_cross_attn",
     "wlx_debug_resample", "wlx_debug_resample_split", "wlx_debug_resample_timed", "wlx_debug_resample_stream", "wlx_debug_flac_decode", "wlx_debug_flac_timings", "wlx_debug_adpcm_decode",
@@ -137,6 +138,10 @@ ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
 ERR_DATA = 7            # wlx_status WLX_ERR_DATA: damaged input (the FLAC and telephony WAV front ends)
 SPK_MAX_BATCH = 64      # wlx.h WLX_SPK_MAX_BATCH: segments of one wlx_spk_embed_batch call
 SPK_CLUSTER_MAX = 2048  # wlx.h WLX_SPK_CLUSTER_MAX: rows of one wlx_spk_cluster / windows of one wlx_spk_diarize_pcm call
+SPK_MIN_SAMPLES = 4800  # csrc/spk.h WLX_SPK_MIN_SAMPLES: a shorter window or segment takes no part (WLX_ERR_TOO_SHORT)
+SPK_MANY_MAX_FILES = 64                                   # wlx.h WLX_SPK_MANY_MAX_FILES: files of one wlx_spk_diarize_many call,
+SPK_MANY_MAX_ROWS = 8192                                   # WLX_SPK_MANY_MAX_ROWS: their windows together,
+SPK_MANY_MAX_CELLS = 4 * SPK_CLUSTER_MAX * SPK_CLUSTER_MAX  # WLX_SPK_MANY_MAX_CELLS: floats of their distance matrices together
 VAD_MAX_BATCH = 64      # wlx.h WLX_VAD_MAX_BATCH: sequences of one wlx_vad_probs_batch / wlx_vad_probs_pcm_batch call
 ALIGN_MAX_BATCH = 64    # wlx.h WLX_ALIGN_MAX_BATCH: entries of one wlx_align_batch call
 ALIGN_MAX_MEDIAN = 15   # wlx.h WLX_ALIGN_MAX_MEDIAN: the widest median filter the device post-processing serves
@@ -413,6 +418,9 @@ def load() -> C.CDLL:
     copts = C.POINTER(wlx_spk_cluster_opts)
     lib.wlx_spk_cluster.argtypes = [vp, f32p, i32, i32, copts, i32p, f32p, i32p]
     lib.wlx_spk_diarize_pcm.argtypes = [vp, vp, i32, i32, i64p, i64p, i32, copts, i32p, i32p, f32p, f32p, f32p, i32p]
+    lib.wlx_spk_diarize_many.argtypes = [vp, vp, i32, i32, i32p, i32p, i64p, i64p, copts, i32p, i32p, i32p, i32p, f32p, f32p]
+    lib.wlx_spk_debug_affinity_many.argtypes = [i32, f32p, i32, i32p, i32, f32p]
+    lib.wlx_spk_debug_ahc_many.argtypes = [i32, f32p, i32, i32p, copts, i32p, i32p, f32p, i32p, i32p]
     lib.wlx_spk_debug_affinity.argtypes = [i32, f32p, i32, i32, f32p]
     lib.wlx_spk_debug_ahc.argtypes = [i32, f32p, i32, copts, i32p, i32p, f32p, i32p, i32p]
     lib.wlx_spk_debug_cluster_timings.argtypes = [vp, f32p, f32p]

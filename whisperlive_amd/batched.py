@@ -321,7 +321,9 @@ class BatchedInferencePipeline:
         target_language= (one code, or a list with a code or None per file) with translator=: each file's segments carry
         `.translation`, one translation job per file as it finishes.
         wave_put: bool = False (a keyword of the job, beside those of `transcribe`): True puts the files of a wave in one Slot.put_many
-        call with one wait (a slot without it keeps the per-file puts); the results are the same, the default stays one put per file."""
+        call with one wait (a slot without it keeps the per-file puts); the results are the same, the default stays one put per file.
+        diarize= (False | True | FileDiarizer, or a list with one per file) and max_speakers=: the files of a wave are yielded together
+        after its last decode group, their segments and words carrying `.speaker` (one diarize_many job per wave; many_files.py)."""
         from .many_files import iter_many
         target_language, translator = kwargs.pop("target_language", None), kwargs.pop("translator", None)
         if target_language is None:

@@ -62,4 +62,27 @@ bool launch_spk_ahc(float* dist, int n, float threshold, int max_clusters, int* 
 // cent [K][D], K = counts[1] read on the device (the grid covers n): the normalised sum of each cluster's rows
 bool launch_spk_centroids(const float* X, const int* labels, const int* counts, int n, int D, float* cent, hipStream_t s);
 
+// ---- the same for a wave of files in one launch each: 1..WLX_SPK_MANY_MAX_FILES files, every one a shape the single launchers take.
+// File i is rows [row0, row0 + m) of ONE table X and owns the m x m matrix at dist + doff; the rows of all files end inside
+// WLX_SPK_MANY_MAX_ROWS and the matrices inside WLX_SPK_MANY_MAX_CELLS floats (the caller lays them out without overlap). `files` is a
+// HOST array read before the call returns: the table travels in the kernel arguments. Each file's results have the bits of the single
+// launcher on that file alone. False = nothing launched.
+struct SpkClusterFile {
+    size_t doff;           // first float of the file's matrix
+    int row0, m;
+    float threshold;       // read by launch_spk_ahc_many only, as max_clusters
+    int max_clusters;
+};
+struct SpkClusterTable {
+    int n;
+    SpkClusterFile f[WLX_SPK_MANY_MAX_FILES];
+};
+bool launch_spk_affinity_many(const float* X, const SpkClusterFile* files, int n_files, int D, float* dist, hipStream_t s);
+// one workgroup per file. labels [rows] and heights [rows]: file i at row0; merges [2 * rows]: at 2 * row0; counts [n_files][2]
+bool launch_spk_ahc_many(float* dist, const SpkClusterFile* files, int n_files, int* merges, float* heights, int* labels, int* counts,
+                         hipStream_t s);
+// cent [rows][D]: file i's K_i = counts[i][1] centroids at rows row0 .. row0 + K_i - 1
+bool launch_spk_centroids_many(const float* X, const int* labels, const int* counts, const SpkClusterFile* files, int n_files, int D,
+                               float* cent, hipStream_t s);
+
 }  // namespace wlx

@@ -5,7 +5,8 @@
 // through the same buffers (the sum of their lengths is what has to fit max_seconds). wlx_spk_embed is a batch of one;
 // wlx_spk_embed_batch uploads its items; wlx_spk_embed_pcm_batch / _ring_batch run the pass on ranges of audio that is already in HBM
 // (a slot item's PCM, a client's PCM ring), with no upload. wlx_spk_cluster / wlx_spk_diarize_pcm cluster embeddings on the device
-// (spk_cluster.hip): the second enqueues the passes of a whole file's windows back to back and waits once. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
+// (spk_cluster.hip): the second enqueues the passes of a whole file's windows back to back and waits once, and wlx_spk_diarize_many does
+// the same for a wave of files in different items of one slot — shared passes, the files clustered side by side, one wait. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
 // _pool (one item) and _conv_batch / _pool_batch (ragged), each pair on one implementation.
 #include <cmath>
 #include <mutex>
@@ -125,6 +126,14 @@ struct wlx_spk {
     hipEvent_t ev_cl[4] = {nullptr, nullptr, nullptr, nullptr};
     float aff_ms = 0.f, ahc_ms = 0.f;
     bool cl_timed = false;
+    // a wave of files (wlx_spk_diarize_many), allocated by the first such call and apart from the cl_* buffers: one table of up to
+    // WLX_SPK_MANY_MAX_ROWS embeddings, the files' matrices back to back, results per row / per file, and their pinned landing places
+    bool mn_ready = false;
+    float *mn_emb = nullptr, *mn_dist = nullptr, *mn_cent = nullptr, *mn_heights = nullptr;
+    int *mn_merges = nullptr, *mn_labels = nullptr, *mn_counts = nullptr;
+    float *h_mn_emb = nullptr, *h_mn_cent = nullptr;
+    int* h_mn_int = nullptr;         // [labels WLX_SPK_MANY_MAX_ROWS | (n_merges, K) x WLX_SPK_MANY_MAX_FILES]
+    hipEvent_t ev_mn[3] = {nullptr, nullptr, nullptr};
 };
 
 static void spk_free(wlx_spk* k) {
@@ -137,7 +146,9 @@ static void spk_free(wlx_spk* k) {
     if (k->h_emb) (void)hipHostFree(k->h_emb);
     for (hipEvent_t e : k->ev_cl)
         if (e) (void)hipEventDestroy(e);
-    for (void* p : {(void*)k->h_cl_emb, (void*)k->h_cl_cent, (void*)k->h_cl_int})
+    for (hipEvent_t e : k->ev_mn)
+        if (e) (void)hipEventDestroy(e);
+    for (void* p : {(void*)k->h_cl_emb, (void*)k->h_cl_cent, (void*)k->h_cl_int, (void*)k->h_mn_emb, (void*)k->h_mn_cent, (void*)k->h_mn_int})
         if (p) (void)hipHostFree(p);
     if (k->st) (void)hipStreamDestroy(k->st);
     delete k;
@@ -556,6 +567,168 @@ extern "C" int32_t wlx_spk_diarize_pcm(wlx_spk* k, wlx_engine* e, int32_t slot, 
     return WLX_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ a wave of files (wlx_spk_diarize_many)
+// the buffers of a many-call, made by the first one and apart from the single-file cl_* buffers. k->mu is held.
+static int spk_many_reserve(wlx_spk* k) {
+    if (k->mn_ready) return WLX_OK;
+    const size_t R = WLX_SPK_MANY_MAX_ROWS, F = WLX_SPK_MANY_MAX_FILES, E = (size_t)k->spec.embed_dim;
+    if (!k->mn_emb) CKR(dalloc(k->pool, &k->mn_emb, R * E, false));
+    if (!k->mn_cent) CKR(dalloc(k->pool, &k->mn_cent, R * E, false));
+    if (!k->mn_dist) CKR(dalloc(k->pool, &k->mn_dist, (size_t)WLX_SPK_MANY_MAX_CELLS, false));
+    if (!k->mn_heights) CKR(dalloc(k->pool, &k->mn_heights, R, false));
+    if (!k->mn_merges) CKR(dalloc(k->pool, &k->mn_merges, 2 * R, false));
+    if (!k->mn_labels) CKR(dalloc(k->pool, &k->mn_labels, R, false));
+    if (!k->mn_counts) CKR(dalloc(k->pool, &k->mn_counts, 2 * F, false));
+    if (!k->h_mn_emb) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_emb), R * E * sizeof(float), hipHostMallocDefault));
+    if (!k->h_mn_cent) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_cent), R * E * sizeof(float), hipHostMallocDefault));
+    if (!k->h_mn_int) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_int), (R + 2 * F) * sizeof(int), hipHostMallocDefault));
+    for (hipEvent_t& e : k->ev_mn)
+        if (!e) CK(hipEventCreate(&e));
+    k->mn_ready = true;
+    return WLX_OK;
+}
+
+// The files of a wave lie in the items of ONE slot, rows of one allocation: the front end addresses a window as an offset from item 0
+// (item * pcm_cap + start), so a pass mixes the windows of different files as it mixes those of one. Rows of the table are the windows
+// that take part, file by file; file f owns rows [row0_f, row0_f + m_f) and, with m_f >= 2, a matrix and a workgroup of the clustering.
+extern "C" int32_t wlx_spk_diarize_many(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t n_files, const int32_t* items, const int32_t* n_windows,
+                                        const int64_t* starts, const int64_t* n_samples, const wlx_spk_cluster_opts* opts, int32_t* labels,
+                                        int32_t* status, int32_t* file_status, int32_t* n_clusters, float* emb_out, float* centroids) {
+    const char* who = "wlx_spk_diarize_many";
+    if (!k || !e || !items || !n_windows || !starts || !n_samples || !opts || !labels || !status || !file_status || !n_clusters)
+        return set_error(WLX_ERR_ARG, "%s: null argument", who);
+    if (n_files < 1 || n_files > WLX_SPK_MANY_MAX_FILES) return set_error(WLX_ERR_ARG, "%s: %d files outside 1..%d", who, n_files, WLX_SPK_MANY_MAX_FILES);
+    std::vector<long> w0((size_t)n_files + 1, 0);          // first window of file f in the packed arrays
+    for (int f = 0; f < n_files; ++f) {
+        if (n_windows[f] < 0 || n_windows[f] > WLX_SPK_CLUSTER_MAX)
+            return set_error(WLX_ERR_ARG, "%s: file %d: %d windows outside 0..%d", who, f, n_windows[f], WLX_SPK_CLUSTER_MAX);
+        w0[f + 1] = w0[f] + n_windows[f];
+        CKR(spk_cluster_opts_ok(who, &opts[f]));
+        for (int g = 0; g < f; ++g)
+            if (items[g] == items[f]) return set_error(WLX_ERR_ARG, "%s: files %d and %d both name item %d", who, g, f, items[f]);
+    }
+    if (w0[n_files] > WLX_SPK_MANY_MAX_ROWS)
+        return set_error(WLX_ERR_ARG, "%s: %ld windows in all exceed %d", who, w0[n_files], WLX_SPK_MANY_MAX_ROWS);
+    size_t cells = 0;
+    for (int f = 0; f < n_files; ++f) {
+        size_t m = 0;
+        for (long i = w0[f]; i < w0[f + 1]; ++i) {
+            if (n_samples[i] < 0 || n_samples[i] > k->max_samples)
+                return set_error(WLX_ERR_ARG, "%s: file %d window %ld: %lld samples outside 0..the engine's %d s", who, f, i - w0[f], (long long)n_samples[i], k->spec.max_seconds);
+            if (starts[i] < 0) return set_error(WLX_ERR_ARG, "%s: file %d window %ld starts at %lld", who, f, i - w0[f], (long long)starts[i]);
+            m += n_samples[i] >= WLX_SPK_MIN_SAMPLES;
+        }
+        cells += m * m;
+    }
+    if (cells > (size_t)WLX_SPK_MANY_MAX_CELLS)
+        return set_error(WLX_ERR_ARG, "%s: the distance matrices of the files take %zu floats, over %zu", who, cells, (size_t)WLX_SPK_MANY_MAX_CELLS);
+    CKR(PcmLease::same_device(who, "engine", e->device, "speaker engine", k->device));
+    PcmLease L;
+    CKR(L.open_slot(e, slot));
+    for (int f = 0; f < n_files; ++f) CKR(L.item(who, items[f]));
+    // residency is a file's own matter: an item without PCM, or a window past its count, costs that file only
+    L.view(0);
+    const float* base = L.buf;
+    std::vector<char> ok((size_t)n_files, 0);
+    std::vector<long> item_off((size_t)n_files, 0);
+    for (int f = 0; f < n_files; ++f) {
+        L.view(items[f]);
+        bool good = L.resident > 0 && L.buf;
+        for (long i = w0[f]; good && i < w0[f + 1]; ++i) good = starts[i] <= L.resident - n_samples[i];
+        ok[f] = good, item_off[f] = good ? (long)(L.buf - base) : 0;
+    }
+    // the passes over the windows that take part; win_of[a] = the packed window behind row a of the table
+    std::vector<SpkPlan> plans;
+    std::vector<long> win_of;
+    std::vector<int> row0((size_t)n_files, 0), m_of((size_t)n_files, 0);
+    std::vector<SpkClusterFile> cf;          // the files the clustering launches see (m >= 2), cf_file[c] = which
+    std::vector<int> cf_file;
+    {
+        SpkPlan cur;
+        size_t doff = 0;
+        for (int f = 0; f < n_files; ++f) {
+            if (!ok[f]) continue;
+            row0[f] = (int)win_of.size();
+            for (long i = w0[f]; i < w0[f + 1]; ++i) {
+                if (n_samples[i] < WLX_SPK_MIN_SAMPLES) continue;
+                if (cur.m > 0 && (cur.m >= WLX_SPK_MAX_BATCH || cur.total + (long)n_samples[i] > k->max_samples)) {
+                    plans.push_back(cur);
+                    cur = SpkPlan();
+                }
+                cur.offs[cur.m] = item_off[f] + (long)starts[i], cur.widths[cur.m] = spk_frames((long)n_samples[i]), cur.row[cur.m] = (int)win_of.size();
+                ++cur.m, cur.total += (long)n_samples[i];
+                win_of.push_back(i);
+            }
+            const int m = m_of[f] = (int)win_of.size() - row0[f];
+            if (m >= 2) {
+                cf.push_back(SpkClusterFile{doff, row0[f], m, opts[f].threshold, opts[f].max_clusters});
+                cf_file.push_back(f);
+                doff += (size_t)m * m;
+            }
+        }
+        if (cur.m > 0) plans.push_back(cur);
+    }
+    const int M = (int)win_of.size(), E = k->spec.embed_dim, C = (int)cf.size();
+    // every refusal on the arguments has had its turn: what is known without the device
+    bool any_single = false;
+    for (int f = 0; f < n_files; ++f) {
+        file_status[f] = ok[f] ? WLX_OK : WLX_ERR_STATE;
+        n_clusters[f] = ok[f] && m_of[f] > 0 ? 1 : 0;
+        any_single = any_single || (ok[f] && m_of[f] == 1);
+        for (long i = w0[f]; i < w0[f + 1]; ++i) {
+            const bool out = !ok[f] || n_samples[i] < WLX_SPK_MIN_SAMPLES;
+            status[i] = !ok[f] ? WLX_ERR_STATE : out ? WLX_ERR_TOO_SHORT : WLX_OK;
+            labels[i] = out ? -1 : 0;
+            if (out && emb_out) std::fill(emb_out + (size_t)i * E, emb_out + (size_t)(i + 1) * E, 0.f);
+        }
+    }
+    if (M == 0) return WLX_OK;
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    CKR(spk_many_reserve(k));
+    CKR(L.order(k->st));
+    hipStream_t st = k->st;
+    for (const SpkPlan& pl : plans) CKR(spk_enqueue_batch(k, base, pl, k->mn_emb + (size_t)pl.row[0] * E));
+    if (emb_out || (centroids && any_single)) CK(hipMemcpyAsync(k->h_mn_emb, k->mn_emb, (size_t)M * E * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (C > 0) {
+        CK(hipEventRecord(k->ev_mn[0], st));
+        if (!launch_spk_affinity_many(k->mn_emb, cf.data(), C, E, k->mn_dist, st)) return set_error(WLX_ERR_ARG, "%s: the distance matrices refused %d files", who, C);
+        CK(hipEventRecord(k->ev_mn[1], st));
+        if (!launch_spk_ahc_many(k->mn_dist, cf.data(), C, k->mn_merges, k->mn_heights, k->mn_labels, k->mn_counts, st))
+            return set_error(WLX_ERR_ARG, "%s: the clustering refused %d files", who, C);
+        CK(hipEventRecord(k->ev_mn[2], st));
+        if (centroids) {
+            if (!launch_spk_centroids_many(k->mn_emb, k->mn_labels, k->mn_counts, cf.data(), C, E, k->mn_cent, st))
+                return set_error(WLX_ERR_ARG, "%s: the centroids refused %d files", who, C);
+            CK(hipMemcpyAsync(k->h_mn_cent, k->mn_cent, (size_t)(cf.back().row0 + cf.back().m) * E * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(k->h_mn_int, k->mn_labels, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, st));
+        CK(hipMemcpyAsync(k->h_mn_int + WLX_SPK_MANY_MAX_ROWS, k->mn_counts, (size_t)2 * C * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    CK(hipStreamSynchronize(st));
+    CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));          // (of the last pass)
+    CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
+    k->timed = true;
+    if (emb_out)
+        for (int a = 0; a < M; ++a) std::copy(k->h_mn_emb + (size_t)a * E, k->h_mn_emb + (size_t)(a + 1) * E, emb_out + (size_t)win_of[a] * E);
+    if (centroids)                    // one window is its own cluster, its embedding the centroid
+        for (int f = 0; f < n_files; ++f)
+            if (ok[f] && m_of[f] == 1) std::copy(k->h_mn_emb + (size_t)row0[f] * E, k->h_mn_emb + (size_t)(row0[f] + 1) * E, centroids + (size_t)w0[f] * E);
+    if (C == 0) return WLX_OK;
+    for (int c = 0; c < C; ++c) {
+        const int f = cf_file[c], K = k->h_mn_int[WLX_SPK_MANY_MAX_ROWS + 2 * c + 1];
+        if (K < 1 || K > cf[c].m) return set_error(WLX_ERR_HIP, "%s: the clustering of file %d (%d rows) reported %d clusters", who, f, cf[c].m, K);
+        n_clusters[f] = K;
+        if (centroids) std::copy(k->h_mn_cent + (size_t)cf[c].row0 * E, k->h_mn_cent + (size_t)(cf[c].row0 + K) * E, centroids + (size_t)w0[f] * E);
+        for (int a = cf[c].row0; a < cf[c].row0 + cf[c].m; ++a) labels[win_of[a]] = k->h_mn_int[a];
+    }
+    CK(hipEventElapsedTime(&k->aff_ms, k->ev_mn[0], k->ev_mn[1]));
+    CK(hipEventElapsedTime(&k->ahc_ms, k->ev_mn[1], k->ev_mn[2]));
+    k->cl_timed = true;
+    return WLX_OK;
+}
+
 extern "C" int32_t wlx_spk_debug_cluster_timings(wlx_spk* k, float* affinity_ms, float* ahc_ms) {
     if (!k || !affinity_ms || !ahc_ms) return set_error(WLX_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> g(k->mu);
@@ -739,5 +912,63 @@ extern "C" int32_t wlx_spk_debug_ahc(int32_t device, const float* dist, int32_t 
     CKR(S.download(counts, dC, (size_t)2));
     CKR(S.finish());
     *n_merges = counts[0], *n_clusters = counts[1];
+    return WLX_OK;
+}
+
+// ---- their many-forms: files packed back to back, file f at row0 = ns[0] + .. + ns[f-1], its matrix at ns[0]^2 + .. + ns[f-1]^2
+static int spk_debug_many_table(const int32_t* ns, int n_files, const wlx_spk_cluster_opts* opts, std::vector<SpkClusterFile>& files, size_t& rows,
+                                size_t& cells) {
+    if (n_files < 1 || n_files > WLX_SPK_MANY_MAX_FILES) return set_error(WLX_ERR_ARG, "%d files outside 1..%d", n_files, WLX_SPK_MANY_MAX_FILES);
+    rows = cells = 0;
+    for (int f = 0; f < n_files; ++f) {
+        if (ns[f] < 1 || ns[f] > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "ns[%d] = %d outside 1..%d", f, ns[f], WLX_SPK_CLUSTER_MAX);
+        files.push_back(SpkClusterFile{cells, (int)rows, ns[f], opts ? opts[f].threshold : 0.f, opts ? opts[f].max_clusters : 0});
+        rows += (size_t)ns[f], cells += (size_t)ns[f] * ns[f];
+    }
+    if (rows > WLX_SPK_MANY_MAX_ROWS || cells > (size_t)WLX_SPK_MANY_MAX_CELLS)
+        return set_error(WLX_ERR_ARG, "%zu rows / %zu matrix floats in all exceed %d / %zu", rows, cells, WLX_SPK_MANY_MAX_ROWS, (size_t)WLX_SPK_MANY_MAX_CELLS);
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_spk_debug_affinity_many(int32_t device, const float* X, int32_t n_files, const int32_t* ns, int32_t dim, float* dist_out) {
+    if (!X || !ns || !dist_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (dim < 1 || dim > 1024) return set_error(WLX_ERR_ARG, "dim %d outside 1..1024", dim);
+    std::vector<SpkClusterFile> files;
+    size_t rows, cells;
+    CKR(spk_debug_many_table(ns, n_files, nullptr, files, rows, cells));
+    HookScope S;
+    CKR(S.begin(device));
+    float *dX, *dD;
+    CKR(S.upload(&dX, X, rows * dim));
+    CKR(S.alloc(&dD, cells));
+    if (!launch_spk_affinity_many(dX, files.data(), n_files, dim, dD, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CKR(S.download(dist_out, dD, cells));
+    return S.finish();
+}
+
+extern "C" int32_t wlx_spk_debug_ahc_many(int32_t device, const float* dist, int32_t n_files, const int32_t* ns, const wlx_spk_cluster_opts* opts,
+                                          int32_t* labels, int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
+    if (!dist || !ns || !opts || !labels || !merges || !heights || !n_merges || !n_clusters) return set_error(WLX_ERR_ARG, "null argument");
+    std::vector<SpkClusterFile> files;
+    size_t rows, cells;
+    CKR(spk_debug_many_table(ns, n_files, opts, files, rows, cells));
+    for (int f = 0; f < n_files; ++f) CKR(spk_cluster_opts_ok("wlx_spk_debug_ahc_many", &opts[f]));
+    std::vector<int> counts((size_t)2 * n_files, 0);          // (declared before S: it outlives the stream's copies on every return path)
+    HookScope S;
+    CKR(S.begin(device));
+    float *dD, *dH;
+    int *dM, *dL, *dC;
+    CKR(S.upload(&dD, dist, cells));
+    CKR(S.upload(&dH, heights, rows));                        // (copied in and out: what no merge writes comes back unchanged)
+    CKR(S.upload(&dM, merges, 2 * rows));
+    CKR(S.alloc(&dL, rows));
+    CKR(S.alloc(&dC, (size_t)2 * n_files));
+    if (!launch_spk_ahc_many(dD, files.data(), n_files, dM, dH, dL, dC, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CKR(S.download(labels, dL, rows));
+    CKR(S.download(heights, dH, rows));
+    CKR(S.download(merges, dM, 2 * rows));
+    CKR(S.download(counts.data(), dC, (size_t)2 * n_files));
+    CKR(S.finish());
+    for (int f = 0; f < n_files; ++f) n_merges[f] = counts[2 * f], n_clusters[f] = counts[2 * f + 1];
     return WLX_OK;
 }

@@ -57,6 +57,32 @@ def plan_embed_groups(lengths: Sequence[int], cap_samples: int, max_items: int =
     return groups
 
 
+def plan_diarize_many(n_windows: Sequence[int], n_taking_part: Optional[Sequence[int]] = None, max_files: int = _lib.SPK_MANY_MAX_FILES,
+                      max_rows: int = _lib.SPK_MANY_MAX_ROWS, max_cells: int = _lib.SPK_MANY_MAX_CELLS) -> List[List[int]]:
+    """A list of files -> consecutive wlx_spk_diarize_many calls, as lists of file indices in order: a call is closed when the next
+    file would take it over `max_files` files, over `max_rows` windows in all (n_windows, short ones counted) or over `max_cells`
+    floats of distance matrices (the sum of m^2, m = n_taking_part: the windows of at least 0.3 s; n_windows where it is not given).
+    A file of more than _lib.SPK_CLUSTER_MAX windows fits no call: ValueError."""
+    m_of = list(n_windows) if n_taking_part is None else list(n_taking_part)
+    if len(m_of) != len(n_windows):
+        raise ValueError("n_taking_part must have one entry per file")
+    calls: List[List[int]] = []
+    cur: List[int] = []
+    rows = cells = 0
+    for f, (n, m) in enumerate(zip(n_windows, m_of)):
+        n, m = int(n), int(m)
+        if n < 0 or m < 0 or m > n or n > _lib.SPK_CLUSTER_MAX:
+            raise ValueError(f"file {f}: {n} windows ({m} taking part) outside 0..{_lib.SPK_CLUSTER_MAX}")
+        if cur and (len(cur) >= max_files or rows + n > max_rows or cells + m * m > max_cells):
+            calls.append(cur)
+            cur, rows, cells = [], 0, 0
+        cur.append(f)
+        rows, cells = rows + n, cells + m * m
+    if cur:
+        calls.append(cur)
+    return calls
+
+
 class SpeakerEmbedderHIP:
     """one wlx_spk engine: `weights` are the FOLDED tensors of spk_weights.fold()"""
 
@@ -203,6 +229,55 @@ class SpeakerEmbedderHIP:
             out += (emb[:n],)
         if want_distances:
             out += (dist,)
+        return out
+
+    def diarize_many(self, slot, items, windows_per_file, thresholds, max_clusters=0, want_embeddings: bool = False) -> list:
+        """wlx_spk_diarize_many: `diarize_resident` of a wave of files — file f the (start, n_samples) windows `windows_per_file[f]` of
+        the PCM resident in item `items[f]` of `slot` — with ONE wait per call: the windows of all files share the embed passes, and the
+        files are clustered side by side in one launch. `thresholds` / `max_clusters`: one value, or one per file. -> per file
+        (labels, centroids[, rows]) with the bits of `diarize_resident` on that file, or the WlxError of that file alone (ERR_STATE:
+        nothing resident behind its item, a window past its end) — returned, not raised. More files than one call takes are cut into
+        consecutive calls (`plan_diarize_many`); a file over _lib.SPK_CLUSTER_MAX windows is a ValueError."""
+        if self.h is None:
+            raise _lib.WlxError("speaker engine is closed")
+        n_files, dim = len(items), self.spec.embed_dim
+        per_file = lambda v: [v] * n_files if np.isscalar(v) else list(v)
+        thresholds, max_clusters = per_file(thresholds), per_file(max_clusters)
+        if not (len(windows_per_file) == len(thresholds) == len(max_clusters) == n_files):
+            raise ValueError("diarize_many: items, windows_per_file, thresholds and max_clusters must have one entry per file")
+        windows_per_file = [[(int(a), int(c)) for a, c in ws] for ws in windows_per_file]
+        out: list = [None] * n_files
+        f32p, i32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        ptr = lambda a: a.ctypes.data_as(f32p) if a is not None else None
+        for call in plan_diarize_many([len(ws) for ws in windows_per_file],
+                                      [sum(c >= _lib.SPK_MIN_SAMPLES for _, c in ws) for ws in windows_per_file]):
+            counts = np.array([len(windows_per_file[f]) for f in call], dtype=np.int32)
+            total = max(int(counts.sum()), 1)
+            flat = [w for f in call for w in windows_per_file[f]]
+            starts = np.array([a for a, _ in flat] or [0], dtype=np.int64)
+            samples = np.array([c for _, c in flat] or [0], dtype=np.int64)
+            its = np.array([int(items[f]) for f in call], dtype=np.int32)
+            opts = (_lib.wlx_spk_cluster_opts * len(call))(*[_lib.wlx_spk_cluster_opts(float(thresholds[f]), int(max_clusters[f])) for f in call])
+            labels, status = np.full(total, -1, dtype=np.int32), np.zeros(total, dtype=np.int32)
+            fstat, ks = np.zeros(len(call), dtype=np.int32), np.zeros(len(call), dtype=np.int32)
+            cent = np.zeros((total, dim), dtype=np.float32)
+            emb = np.zeros((total, dim), dtype=np.float32) if want_embeddings else None
+            with slot.lock:
+                _lib.check(self.lib.wlx_spk_diarize_many(self.h, slot.engine._h, slot.sid, len(call), its.ctypes.data_as(i32p),
+                                                         counts.ctypes.data_as(i32p), starts.ctypes.data_as(i64p), samples.ctypes.data_as(i64p),
+                                                         opts, labels.ctypes.data_as(i32p), status.ctypes.data_as(i32p),
+                                                         fstat.ctypes.data_as(i32p), ks.ctypes.data_as(i32p), ptr(emb), ptr(cent)))
+            at = 0
+            for j, f in enumerate(call):
+                n = int(counts[j])
+                if fstat[j] != 0:
+                    err = _lib.WlxError(f"libwlx error {int(fstat[j])}: wlx_spk_diarize_many: item {int(its[j])}: no PCM resident behind "
+                                        f"a window of file {f}")
+                    err.code = int(fstat[j])
+                    out[f] = err
+                else:
+                    out[f] = (labels[at:at + n].copy(), cent[at:at + int(ks[j])].copy()) + ((emb[at:at + n].copy(),) if want_embeddings else ())
+                at += n
         return out
 
     def cluster_timings(self) -> Tuple[float, float]:

@@ -11,7 +11,10 @@ the route of the file endpoint's ``diarize=true``.
 * ``assign_speakers``    — turns -> a speaker per word and per segment.
 * ``match_known``        — clusters renamed after enrolled speakers.
 * ``FileDiarizer``       — the above on the audio a transcription left resident on the device
-                           (``SpeakerEmbedderHIP.diarize_resident``: wlx_spk_diarize_pcm, every window embedded and clustered behind ONE wait).
+                           (``SpeakerEmbedderHIP.diarize_resident``: wlx_spk_diarize_pcm, every window embedded and clustered behind ONE wait);
+                           ``diarize_many`` does a wave of files in one device call (``SpeakerEmbedderHIP.diarize_many``:
+                           wlx_spk_diarize_many), the turns per file those of ``diarize``.
+* ``label_segments``     — ``assign_speakers`` with the gaps closed: what the file routes put on segments and words.
 """
 from __future__ import annotations
 
@@ -203,6 +206,20 @@ def assign_speakers(segments, turns) -> Tuple[List[Optional[object]], List[Optio
     return seg_speakers, word_speakers
 
 
+def label_segments(segments, turns) -> Tuple[List[Optional[object]], List[Optional[List[Optional[object]]]]]:
+    """`assign_speakers` with the gaps closed, as the file routes answer: a segment that overlaps no turn takes the speaker of the turn
+    nearest in time, a word that overlaps none its segment's speaker. Without turns everything stays None."""
+    per_seg, per_word = assign_speakers(segments, turns)
+    seg_speakers: List[Optional[object]] = []
+    word_speakers: List[Optional[List[Optional[object]]]] = []
+    for seg, who, words in zip(segments, per_seg, per_word):
+        if who is None and turns:
+            who = min(turns, key=lambda t: max(t[0] - seg.end, seg.start - t[1], 0.0))[2]
+        seg_speakers.append(who)
+        word_speakers.append(None if words is None else [w if w is not None else who for w in words])
+    return seg_speakers, word_speakers
+
+
 def match_known(centroids, known: Optional[Dict[str, np.ndarray]], distance_threshold: float) -> Dict[int, str]:
     """{cluster: name} for clusters whose centroid has cosine >= 1 - distance_threshold with an enrolled unit embedding: pairs are
     taken best cosine first, each name and each cluster once (ties: the lower cluster, then the earlier name)."""
@@ -250,6 +267,7 @@ class FileDiarizer:
             raise ValueError("max_speakers must be 0 (no cap) or positive")
         self.embedder, self.distance_threshold, self.max_speakers = embedder, float(distance_threshold), int(max_speakers)
         self.window_s, self.hop_s = float(window_s), float(hop_s)
+        self.many_on_device = True          # diarize_many: the wave in one device call where the embedder has one (False: the per-file loop)
 
     def cluster_windows(self, resident, windows) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """-> (label per window, -1 where it took no part; centroids [K][D])"""
@@ -270,18 +288,57 @@ class FileDiarizer:
         labels[took] = got.labels
         return labels, got.centroids
 
-    def diarize(self, resident, spans, known: Optional[Dict[str, np.ndarray]] = None) -> List[Tuple[float, float, str]]:
-        """turns (start_s, end_s, speaker) over the merged [start, end] spans of the ASR segments, on `resident` (engine.ResidentPcm):
-        speakers are SPEAKER_00, SPEAKER_01, ... in order of first appearance, or the name of `known` a cluster matches"""
+    def windows_of(self, resident, spans) -> List[Tuple[int, int, int]]:
+        """the window grid of `diarize` over the spans, cut to the resident audio"""
         limit = resident.n_samples / float(SAMPLE_RATE)
         spans = [(max(0.0, a), min(limit, b)) for a, b in spans if min(limit, b) > max(0.0, a)]
         windows = plan_windows(spans, self.window_s, self.hop_s)
-        windows = [(s, min(n, resident.n_samples - s), i) for s, n, i in windows if s < resident.n_samples]
+        return [(s, min(n, resident.n_samples - s), i) for s, n, i in windows if s < resident.n_samples]
+
+    def _turns(self, windows, labels, centroids, known) -> List[Tuple[float, float, str]]:
+        names = match_known(centroids, known, self.distance_threshold)
+        return [(a, b, names.get(lab, "SPEAKER_%02d" % lab)) for a, b, lab in turns_from_labels(windows, labels)]
+
+    def diarize(self, resident, spans, known: Optional[Dict[str, np.ndarray]] = None) -> List[Tuple[float, float, str]]:
+        """turns (start_s, end_s, speaker) over the merged [start, end] spans of the ASR segments, on `resident` (engine.ResidentPcm):
+        speakers are SPEAKER_00, SPEAKER_01, ... in order of first appearance, or the name of `known` a cluster matches"""
+        windows = self.windows_of(resident, spans)
         if not windows:
             return []
         labels, centroids = self.cluster_windows(resident, windows)
-        names = match_known(centroids, known, self.distance_threshold)
-        return [(a, b, names.get(lab, "SPEAKER_%02d" % lab)) for a, b, lab in turns_from_labels(windows, labels)]
+        return self._turns(windows, labels, centroids, known)
+
+    def diarize_many(self, residents, spans_per_file, known: Optional[Dict[str, np.ndarray]] = None,
+                     max_speakers: Optional[Sequence[int]] = None) -> List[List[Tuple[float, float, str]]]:
+        """`diarize` of a wave of files, `residents[f]` (engine.ResidentPcm, different items of ONE slot) with the spans
+        `spans_per_file[f]` -> the turns per file, those `diarize` gives for that file. With `diarize_many` on the embedder the windows
+        of all files go to the device together (SpeakerEmbedderHIP.diarize_many: wlx_spk_diarize_many, one wait per call); a file with
+        more than _lib.SPK_CLUSTER_MAX windows keeps the host route of `cluster_windows`, and an embedder without `diarize_many` gets
+        the loop over `diarize`. max_speakers: a cap per file in place of the diarizer's own. A file whose audio is not resident
+        raises the error `diarize` raises for it."""
+        if len(residents) != len(spans_per_file) or (max_speakers is not None and len(max_speakers) != len(residents)):
+            raise ValueError("diarize_many: one resident, one list of spans and one max_speakers per file")
+        caps = [self.max_speakers if c is None else int(c) for c in (max_speakers if max_speakers is not None else [None] * len(residents))]
+        if any(c < 0 for c in caps):
+            raise ValueError("max_speakers must be 0 (no cap) or positive")
+        windows = [self.windows_of(r, spans) for r, spans in zip(residents, spans_per_file)]
+        turns: List[List[Tuple[float, float, str]]] = [[] for _ in residents]
+        on_device = getattr(self.embedder, "diarize_many", None) if self.many_on_device else None
+        together = [f for f, ws in enumerate(windows) if ws and on_device is not None and len(ws) <= _lib.SPK_CLUSTER_MAX
+                    and residents[f].slot is residents[0].slot]
+        for f, ws in enumerate(windows):          # the per-file route: no many-call, too many windows, another slot
+            if ws and f not in together:
+                one = self if caps[f] == self.max_speakers else FileDiarizer(self.embedder, self.distance_threshold, caps[f], self.window_s, self.hop_s)
+                labels, centroids = one.cluster_windows(residents[f], ws)
+                turns[f] = self._turns(ws, labels, centroids, known)
+        if together:
+            got = on_device(residents[together[0]].slot, [residents[f].item for f in together], [[(s, n) for s, n, _ in windows[f]] for f in together],
+                            self.distance_threshold, [caps[f] for f in together])
+            for f, result in zip(together, got):
+                if isinstance(result, Exception):
+                    raise result
+                turns[f] = self._turns(windows[f], result[0], result[1], known)
+        return turns
 
 
 def speakers_in_order(turns) -> List[str]:

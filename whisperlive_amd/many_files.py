@@ -28,6 +28,15 @@ at a time, each item of a group with its own file's prompt (tokenizer of that fi
 timestamps are aligned for the whole group in one ``align`` call per start sequence (``wlx_align_batch``). A file is yielded when the
 group of its last chunk has finished, files in input order.
 
+Speakers. ``diarize=True`` (the pipeline's ``file_diarizer``, made from the configured speaker checkpoint when there is none), a
+``FileDiarizer``, or a list with one of those or False per file; ``max_speakers`` an int or a list (None: the diarizer's own cap). The
+sources of a wave are still resident when its last decode group has finished, and only then are all its transcripts known: so with
+``diarize`` on, the files of a wave are yielded TOGETHER, in input order, after the wave's last group, behind ONE
+``FileDiarizer.diarize_many`` job per diarizer over ``merge_spans(segments)`` of every file (wlx_spk_diarize_many: the windows of all
+files share the embed passes, the files are clustered side by side, one wait). Every segment and word of a diarized file gets
+``.speaker`` by ``file_diarization.label_segments`` (``assign_speakers`` with the gaps closed, as the REST route answers), and its
+``info`` gets ``.speakers``, the speakers in order of first appearance. A failed file still yields (index, exception, None).
+
 Language. A file with ``language=None`` on a multilingual model is detected on its own leading chunks, as ``_language`` does, and the
 window the detection encodes is the one ``_language`` builds — the leading chunks' features glued, plus its dummy frame — so that the
 probabilities are the single-file run's. No device entry point glues features, so the leading chunks of all files of the wave are cut
@@ -41,7 +50,8 @@ a file every route refuses (WLX_ERR_ARG, nothing launched: more than the 3600 s 
 other device error is raised as ``transcribe`` raises it. A file without speech yields [] and an info with duration_after_vad == 0.
 
 ``multichannel=True`` is not part of this route. After a job nothing is left for ``resident_file_audio``: item 0 is a destination of
-the decode groups, and the sources are overwritten by the next wave.
+the decode groups, and the sources are overwritten by the next wave. That is why the speakers are found INSIDE the job (``diarize``),
+while the wave's sources still lie behind their items: a caller cannot diarize a pooled file afterwards.
 """
 from __future__ import annotations
 
@@ -55,7 +65,8 @@ from . import vad as _vad
 from . import word_timing as _wt
 from .batched import MAX_DEC_ROWS, DeviceChunks, _collect_ranges, _file_bytes, _options, _put_audio, _put_audio_many, _segment, _vad_options
 from ._lib import ERR_ARG as _ERR_ARG, WlxError as _WlxError
-from .engine import FlacFrames, _at_16k, _wav_at_16k
+from .engine import FlacFrames, ResidentPcm, _at_16k, _wav_at_16k
+from .file_diarization import FileDiarizer, label_segments, merge_spans, speakers_in_order
 from .multichannel import source_rows_addressable
 from .tokenizer import Tokenizer
 from .transcriber import EncoderOutput, restore_speech_timestamps
@@ -147,11 +158,51 @@ def per_file_arguments(a: dict, n_files: int) -> List[dict]:
     return [{**a, **{name: v[i] for name, v in split.items()}} for i in range(n_files)]
 
 
+def per_file_diarizers(pipe, diarize, max_speakers, n_files: int) -> List[tuple]:
+    """the `diarize` / `max_speakers` arguments -> one (FileDiarizer or None, cap or None) per file. `diarize`: False | True |
+    FileDiarizer, or a list with one of those per file; True is the pipeline's `file_diarizer` (made once from the configured speaker
+    checkpoint). `max_speakers`: None (the diarizer's own), an int, or a list with one of those per file."""
+    def spread(v, what):
+        if isinstance(v, (list, tuple)):
+            if len(v) != n_files:
+                raise ValueError(f"{what}: a list of {len(v)} entries for {n_files} files (one entry per file, or one value for all)")
+            return list(v)
+        return [v] * n_files
+    caps = spread(max_speakers, "max_speakers")
+    for c in caps:
+        if c is not None and (isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0):
+            raise ValueError(f"max_speakers {c!r}: 0 (no cap), a positive integer or None")
+    out = []
+    for d, c in zip(spread(diarize, "diarize"), caps):
+        if d is True:
+            d = _pipeline_diarizer(pipe)
+        elif d is False or d is None:
+            d = None
+        elif not hasattr(d, "diarize"):
+            raise ValueError(f"diarize {d!r}: False, True or a FileDiarizer")
+        out.append((d, None if c is None else int(c)))
+    return out
+
+
+def _pipeline_diarizer(pipe):
+    """`diarize=True`: the pipeline's own FileDiarizer, on the shared embedder of the configured speaker checkpoint"""
+    d = getattr(pipe, "file_diarizer", None)
+    if d is None:
+        from .artifacts import resolve_diarization_model
+        from .diarization import shared_embedder
+        path = resolve_diarization_model(None)
+        if path is None:
+            raise ValueError("diarize=True: no speaker checkpoint is configured (set pipe.file_diarizer, or pass a FileDiarizer)")
+        d = pipe.file_diarizer = FileDiarizer(shared_embedder(path, int(getattr(pipe.model, "device_index", 0) or 0)))
+    return d
+
+
 class _File:
     """one file of a wave, from its put to its result"""
 
-    def __init__(self, index: int, a: dict, audio, item: int):
+    def __init__(self, index: int, a: dict, audio, item: int, diarizer=None, max_speakers: Optional[int] = None):
         self.index, self.a, self.audio, self.item = index, a, audio, item
+        self.diarizer, self.max_speakers = diarizer, max_speakers
         self.error = None
         self.n_samples = 0
         self.clips: List[dict] = []
@@ -184,6 +235,7 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     if on_error not in ("return", "raise"):
         raise ValueError(f"on_error {on_error!r}: 'return' or 'raise'")
     wave_put = bool(kwargs.pop("wave_put", False))
+    diarize, max_speakers = kwargs.pop("diarize", False), kwargs.pop("max_speakers", None)
     if kwargs.pop("multichannel", False):
         raise ValueError("transcribe_many: multichannel=True is not part of this route (transcribe the files one by one with "
                          "transcribe(..., multichannel=True))")
@@ -207,10 +259,11 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     max_batch = int(getattr(model, "max_batch", batch_size))
     check_batch(batch_size, max_batch)
     per_file = per_file_arguments(a, len(audios))
-    return _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put)
+    diarizers = per_file_diarizers(pipe, diarize, max_speakers, len(audios))
+    return _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers)
 
 
-def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False):
+def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None):
     model = pipe.model
     timing = pipe.many_timing = {"front_s": 0.0, "total_s": 0.0, "waves": 0}
     t_job = time.perf_counter()
@@ -235,7 +288,7 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: b
         # an earlier job or another route on this thread's slot — and the chunk gather's reach is measured in rows of THAT length
         wave = next_wave(lengths, at, batch_size, max_batch, stride=int(getattr(slot, "pcm_longest", 0)))
         at = wave[-1] + 1
-        files = [_File(i, per_file[i], loaded[i], batch_size + k) for k, i in enumerate(wave)]
+        files = [_File(i, per_file[i], loaded[i], batch_size + k, *(diarizers[i] if diarizers else ())) for k, i in enumerate(wave)]
         for i in wave:
             loaded[i] = None                # (the job does not hold a file's bytes past its wave)
         yield from _wave(pipe, slot, files, a, vad_parameters, batch_size, on_error, timing, wave_put)
@@ -311,13 +364,19 @@ def _wave(pipe, slot, files: List[_File], a, vad_parameters, batch_size, on_erro
     order = iter(files)
     pending = next(order, None)
 
-    def finished():
+    held = any(f.diarizer is not None for f in files)          # speakers: the wave leaves together, behind its last group
+
+    def finished(last: bool = False):
         nonlocal pending
+        if held and not last:
+            return
+        if held:
+            _speakers(slot, good)
         while pending is not None and (pending.error is not None or pending.left == 0):
             f, pending = pending, next(order, None)
             yield (f.index, f.error, None) if f.error is not None else (f.index, f.segments, f.info)
 
-    yield from finished()
+    yield from finished(last=not pool)
     for g in range(0, len(pool), batch_size):
         group = pool[g:g + batch_size]
         with slot.lock:
@@ -331,7 +390,32 @@ def _wave(pipe, slot, files: List[_File], a, vad_parameters, batch_size, on_erro
             f.left -= 1
         if a["log_progress"]:
             model.logger.info("batched transcription: %d / %d chunks of the wave", min(g + batch_size, len(pool)), len(pool))
-        yield from finished()
+        yield from finished(last=g + batch_size >= len(pool))
+
+
+def _speakers(slot, files: List[_File]):
+    """the speakers of a wave whose transcripts are complete and whose sources are still resident behind their items: one
+    FileDiarizer.diarize_many job per diarizer, then `.speaker` on every segment and word and `.speakers` on the info"""
+    by_diarizer: dict = {}
+    for f in files:
+        if f.diarizer is not None:
+            by_diarizer.setdefault(id(f.diarizer), []).append(f)
+    for group in by_diarizer.values():
+        diarizer = group[0].diarizer
+        residents = [ResidentPcm(slot, f.item, f.n_samples) for f in group]
+        spans = [merge_spans(f.segments) for f in group]
+        many = getattr(diarizer, "diarize_many", None)
+        if many is not None:
+            turns = many(residents, spans, max_speakers=[f.max_speakers for f in group])
+        else:          # anything with `diarize` alone: file by file
+            turns = [diarizer.diarize(r, s) for r, s in zip(residents, spans)]
+        for f, file_turns in zip(group, turns):
+            per_seg, per_word = label_segments(f.segments, file_turns)
+            for seg, who, words in zip(f.segments, per_seg, per_word):
+                seg.speaker = who
+                for word, w in zip(seg.words or [], words or []):
+                    word.speaker = w
+            f.info.speakers = speakers_in_order(file_turns)
 
 
 def _gate(model, slot, gated: List[_File], vad_parameters, sampling_rate):

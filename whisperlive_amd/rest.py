@@ -284,7 +284,7 @@ def diarize_file_segments(segments, diarizer, resident_of, known=None, multichan
     multichannel request carry their channel (`CH1_SPEAKER_00`): the clusters of two channels are not the same people; a name of
     `known` stays as it is. A word that overlaps no turn (one of no duration) takes its segment's speaker, a segment that overlaps
     none the speaker of the turn nearest in time. ValueError: nothing resident to read."""
-    from .file_diarization import assign_speakers, merge_spans
+    from .file_diarization import label_segments, merge_spans
     seg_speakers: List[Optional[str]] = [None] * len(segments)
     word_speakers: List[Optional[List[Optional[str]]]] = [None] * len(segments)
     speakers: List[str] = []
@@ -299,15 +299,9 @@ def diarize_file_segments(segments, diarizer, resident_of, known=None, multichan
         turns = diarizer.diarize(resident, merge_spans([segments[i] for i in index]), known=known)
         if ch is not None:
             turns = [(a, b, who if known and who in known else f"CH{ch}_{who}") for a, b, who in turns]
-        per_seg, per_word = assign_speakers([segments[i] for i in index], turns)
+        per_seg, per_word = label_segments([segments[i] for i in index], turns)
         for k, i in enumerate(index):
-            who = per_seg[k]
-            if who is None and turns:
-                seg = segments[i]
-                who = min(turns, key=lambda t: max(t[0] - seg.end, seg.start - t[1], 0.0))[2]
-            seg_speakers[i] = who
-            if per_word[k] is not None:
-                word_speakers[i] = [w if w is not None else who for w in per_word[k]]
+            seg_speakers[i], word_speakers[i] = per_seg[k], per_word[k]
         for _, _, who in turns:
             if who not in speakers:
                 speakers.append(who)
@@ -388,6 +382,8 @@ class FileBatcher:
                 results = self.make_pipeline(transcriber).iter_many(
                     [u.data for u in job], batch_size=self.batch_size, vad_filter=True,
                     **{name: [u.per_file[name] for u in job] for name in ("language", "initial_prompt", "hotwords")}, **job[0].shared,
+                    **({"diarize": [u.per_file.get("diarize") or False for u in job], "max_speakers": [int(u.per_file.get("max_speakers") or 0) for u in job]}
+                       if any(u.per_file.get("diarize") for u in job) else {}),
                     **({"wave_put": True} if self.wave_put else {}))
                 for index, segments, info in results:
                     up = job[index]
@@ -479,6 +475,8 @@ class RestServer:
         # last, when nothing above can refuse the arguments any more: one batcher (one worker thread) per GPU, so that the pooled jobs
         # of different devices run side by side; `batcher` is the first device's
         self._batchers: Dict[int, FileBatcher] = {}
+        self._pooled_diarizers: Dict[int, object] = {}
+        self._pooled_diarizers_mu = threading.Lock()
         if self.file_batch_window_ms > 0:
             self._batchers = {d: FileBatcher(self._pipeline, self.file_batch_size, self.file_batch_window_ms / 1000.0, self.file_batch_wave_put) for d in self.devices}
             self.batcher = self._batchers[self.devices[0]]
@@ -577,12 +575,15 @@ class RestServer:
         return BatchedInferencePipeline(transcriber)
 
     def transcribe_pooled(self, transcriber, data: bytes, *, device_index: Optional[int] = None, language=None, initial_prompt=None,
-                          hotwords=None, **shared):
+                          hotwords=None, diarize=None, max_speakers: int = 0, **shared):
         """`transcribe_file` through the batcher (file_batch_window_ms > 0): the upload joins the uploads that arrive within the window
         and decode with the same `shared` options; -> (list of segments, info) of this upload, or its own error raised here, in the
         request's thread, where the single route would have raised it. Nothing is left for `resident_file_audio` after a pooled job
-        (many_files.py), so speaker labels fall back to the second decode; requests with known speakers are not pooled at all."""
-        return self._batchers.get(device_index, self.batcher).submit(transcriber, data, dict(language=language, initial_prompt=initial_prompt, hotwords=hotwords), shared)
+        (many_files.py), so speaker labels fall back to the second decode; requests with known speakers are not pooled at all.
+        diarize: the FileDiarizer of a `diarize=true` upload (pooled_file_diarizer) with its max_speakers — the job finds the speakers
+        while the wave's files are still resident: the segments and words come back with `.speaker`, the info with `.speakers`."""
+        per_file = dict(language=language, initial_prompt=initial_prompt, hotwords=hotwords, diarize=diarize or False, max_speakers=int(max_speakers))
+        return self._batchers.get(device_index, self.batcher).submit(transcriber, data, per_file, shared)
 
     def translator_for(self, device_index: int, target_language: str):
         """the GPU's shared translator for a request with target_language; ValueError = a 400 (no model configured, or a language
@@ -648,6 +649,14 @@ class RestServer:
         if path is None and self.embedder_factory is None:
             raise ValueError("known speakers requested but no speaker-embedding checkpoint is available on this server")
         return FileDiarizer((self.embedder_factory or shared_embedder)(path, device_index), max_speakers=max_speakers)
+
+    def pooled_file_diarizer(self, device_index: int):
+        """ONE diarizer per GPU for the `diarize=true` uploads that go through the batcher: the job runs one diarize_many per diarizer
+        and wave (many_files.py), so the pooled requests share theirs and carry max_speakers per file; ValueError = a 400"""
+        with self._pooled_diarizers_mu:
+            if device_index not in self._pooled_diarizers:
+                self._pooled_diarizers[device_index] = self.create_file_diarizer(device_index, 0)
+            return self._pooled_diarizers[device_index]
 
 
 class _Handler(BaseHTTPRequestHandler):
@@ -861,9 +870,21 @@ class _Handler(BaseHTTPRequestHandler):
             # it, not pooled — a decode group has one table. The segments may arrive lazily: they are drawn inside the scope.
             bias = keyword_scope(transcriber, keywords, keywords_boost)
             with (bias if bias is not None else contextlib.nullcontext()):
-                if rest.batcher is not None and bias is None and not multichannel and not known_speaker_names and not known_speaker_references and not diarize:
+                # a diarize=true upload without known speakers is pooled too: the job finds its speakers while the wave is resident
+                pooled = rest.batcher is not None and bias is None and not multichannel and not known_speaker_names and not known_speaker_references
+                pooled_diarizer = None
+                # (where the GPU's embedder has the wave call, diarize_many: without it pooling would only queue the per-file route)
+                if pooled and diarize and response_format == "verbose_json":
+                    try:
+                        pooled_diarizer = rest.pooled_file_diarizer(device_index)
+                    except ValueError as e:
+                        raise _HttpError(400, {"error": str(e)})
+                    if not hasattr(pooled_diarizer.embedder, "diarize_many"):
+                        pooled, pooled_diarizer = False, None
+                if pooled:
                     segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
-                                                            temperature=temperature, word_timestamps=want_words, hotwords=hotwords)
+                                                            temperature=temperature, word_timestamps=want_words, hotwords=hotwords,
+                                                            diarize=pooled_diarizer, max_speakers=max_speakers)
                 else:
                     segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
                                                           temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)
@@ -892,7 +913,13 @@ class _Handler(BaseHTTPRequestHandler):
                 except ValueError as e:
                     raise _HttpError(400, {"error": str(e)})
                 word_speakers = None
-                if diarize:
+                if diarize and pooled_diarizer is not None:
+                    # the pooled job has labelled the segments (many_files._speakers), by the rules of diarize_file_segments
+                    seg_speakers = [getattr(seg, "speaker", None) for seg in segments]
+                    word_speakers = [[getattr(w, "speaker", None) for w in seg.words] if getattr(seg, "words", None) else None for seg in segments]
+                    verbose["speakers"] = list(getattr(info, "speakers", None) or [])
+                    speaker_labels = {i: who for i, who in enumerate(seg_speakers) if who}
+                elif diarize:
                     # offline: every window of the file clustered at once (file_diarization.py); enrolled speakers only name clusters
                     resident_of = (getattr(transcriber, "resident_file_audio", lambda c: None) if multichannel
                                    else lambda _ch: rest.resident_audio(transcriber))
