@@ -419,6 +419,9 @@ int32_t wlx_bias_set(wlx_engine* e, int32_t slot, int32_t n_nodes, const int32_t
                      const int32_t* edge_next, float boost, int32_t n_tok, const int32_t* tok_ids, const float* tok_vals);
 int32_t wlx_bias_clear(wlx_engine* e, int32_t slot);
 
+/* Keyword boosting per item — a set of tables on the slot, one selected per item of a decode group (wlx_bias_set_items, wlx_bias_select;
+ * DESIGN.md §27) — is declared in wlx_bias_items.h, which this header includes at its end. */
+
 /* One decoder step on [sot]; softmax restricted to `lang_ids`; probs_out[batch][n_lang]. */
 int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot,
                             const int32_t* lang_ids, int32_t n_lang, float* probs_out);
@@ -1118,6 +1121,8 @@ int32_t wlx_debug_prep_windows(int32_t device, const float* feats, int64_t feats
 /* launch_f32_to_f16 (f32_to_f16_kernel, the token embedding's table at engine creation): dst[i] = fp16(src[i]), round to nearest
  * even, values past the fp16 range to +-inf, NaN to NaN. dst holds cap >= n halfs (copied in AND out). 1 <= n <= cap <= 2^28. */
 int32_t wlx_debug_f32_to_f16(int32_t device, const float* src, int64_t n, uint16_t* dst, int64_t cap);
+
+#include "wlx_bias_items.h"
 
 #ifdef __cplusplus
 }

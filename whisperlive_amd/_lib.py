@@ -43,6 +43,8 @@ EXPORTS = [
     "wlx_debug_token_prob", "wlx_debug_token_prob_rows", "wlx_debug_lang_probs", "wlx_debug_dec_embed", "wlx_debug_prep_windows",
     "wlx_debug_f32_to_f16",
 ]
+# the per-item part of keyword boosting, declared in include/wlx_bias_items.h (which wlx.h includes): EXPORTS is wlx.h's own list
+EXPORTS_BIAS_ITEMS = ["wlx_bias_set_items", "wlx_bias_select", "wlx_debug_bias_apply_items"]
 
 
 # MFMA accumulators in VGPRs (gfx950 has ONE register file; hipcc's default puts C/D in its AGPR half): every VALU touch of
@@ -146,6 +148,9 @@ VAD_MAX_BATCH = 64      # wlx.h WLX_VAD_MAX_BATCH: sequences of one wlx_vad_prob
 ALIGN_MAX_BATCH = 64    # wlx.h WLX_ALIGN_MAX_BATCH: entries of one wlx_align_batch call
 ALIGN_MAX_MEDIAN = 15   # wlx.h WLX_ALIGN_MAX_MEDIAN: the widest median filter the device post-processing serves
 BIAS_MAX_NODES, BIAS_MAX_EDGES, BIAS_MAX_TOKENS = 4096, 16384, 1024   # wlx.h WLX_BIAS_MAX_*: the caps of a bias table (wlx_bias_set)
+# wlx_bias_items.h WLX_BIAS_SET_MAX_*: tables of one set (wlx_bias_set_items) and the caps of its pool; WLX_BIAS_EDGE_SHARED: the flag bit in edge_next
+BIAS_SET_MAX_TABLES, BIAS_SET_MAX_NODES, BIAS_SET_MAX_EDGES, BIAS_SET_MAX_TOKENS = 64, 16384, 65536, 4096
+BIAS_EDGE_SHARED = 0x40000000
 MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
 PUT_PCM, PUT_FRAMES, PUT_FLAC, PUT_WAV = 0, 1, 2, 3   # wlx.h WLX_PUT_*: the kinds of a wlx_put_entry
@@ -205,7 +210,7 @@ def _compile(out: Path, defines=(), verbose: bool = False, force: bool = False) 
     from concurrent.futures import ThreadPoolExecutor
     hipcc = _hipcc()
     defines = list(defines)
-    hdrs = list(CSRC.glob("*.h")) + [PKG_DIR.parent / "include" / "wlx.h"]
+    hdrs = list(CSRC.glob("*.h")) + list((PKG_DIR.parent / "include").glob("*.h"))
     hdr_time = max(h.stat().st_mtime for h in hdrs)
     base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + [f"-D{d}" for d in defines]
 
@@ -271,7 +276,7 @@ def _compile(out: Path, defines=(), verbose: bool = False, force: bool = False) 
 
 
 def _fresh(out: Path) -> bool:
-    deps = [CSRC / s for s in SOURCES] + list(CSRC.glob("*.h")) + [PKG_DIR.parent / "include" / "wlx.h"]
+    deps = [CSRC / s for s in SOURCES] + list(CSRC.glob("*.h")) + list((PKG_DIR.parent / "include").glob("*.h"))
     return out.exists() and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps)
 
 
@@ -457,6 +462,10 @@ def load() -> C.CDLL:
     i16p = C.POINTER(C.c_int16)
     lib.wlx_bias_set.argtypes = [vp, i32, i32, i32p, i32p, i32p, C.c_float, i32, i32p, f32p]
     lib.wlx_bias_clear.argtypes = [vp, i32]
+    lib.wlx_bias_set_items.argtypes = [vp, i32, i32, i32p, i32p, i32p, i32p, f32p, i32p, i32p, f32p]
+    lib.wlx_bias_select.argtypes = [vp, i32, i32, i32p]
+    lib.wlx_debug_bias_apply_items.argtypes = [i32, i32, i32, i32, i32p, i32p, i32p, i32p, f32p, i32p, i32p, f32p, f32p, i32, i32, i32p, i64, i32p, i32p,
+                                               i32p, i32p, i32p, i16p, i16p]
     lib.wlx_debug_bias_apply.argtypes = [i32, i32, i32, i32, i32p, i32p, i32p, C.c_float, i32, i32p, f32p, f32p, i32, i64, i32p, i32p, i32p, i32, i32p,
                                          i16p, i16p]
     lib.wlx_debug_token_prob.argtypes = [i32, f32p, i64, i32, i32, i32, f32p]
@@ -465,7 +474,7 @@ def load() -> C.CDLL:
     lib.wlx_debug_dec_embed.argtypes = [i32, u16p, i32, f32p, i32, i32, i32p, i32p, i32, f32p, i32p]
     lib.wlx_debug_prep_windows.argtypes = [i32, f32p, i64, i64, i32, i64, i32, i32p, i32p, u16p, i64]
     lib.wlx_debug_f32_to_f16.argtypes = [i32, f32p, i64, u16p, i64]
-    for name in EXPORTS:
+    for name in EXPORTS + EXPORTS_BIAS_ITEMS:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_ring_group_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):
             fn.restype = i32

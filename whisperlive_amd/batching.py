@@ -13,6 +13,7 @@ unknown-language item (:283), and a retry re-uses the encoder output already res
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import queue
 import threading
@@ -23,6 +24,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
+from . import biasing as _biasing
 from . import vad as _vad
 from .tokenizer import Tokenizer
 from .transcriber import get_compression_ratio, get_suppressed_tokens, pad_or_trim
@@ -39,6 +41,7 @@ class BatchRequest:
     vad_parameters: Optional[Dict] = None
     word_timestamps: bool = False
     client_uid: Optional[str] = None
+    bias_table: Optional[Any] = None       # the session's compiled keyword table (biasing.BiasTable / CompactTable), None: no keywords
     future: threading.Event = field(default_factory=threading.Event)
     result: Optional[Any] = None
     info: Optional[Any] = None
@@ -160,10 +163,14 @@ class BatchInferenceWorker:
 
     def _process_single(self, req: BatchRequest):
         try:
-            result, info = self.transcriber.transcribe(req.audio, language=req.language, task=req.task,
-                                                       initial_prompt=req.initial_prompt, vad_filter=req.use_vad,
-                                                       vad_parameters=req.vad_parameters if req.use_vad else None)
-            req.result = list(result) if result is not None else []
+            # (a session with keywords alone in its batch: the single-table route, under its table on the worker's thread; the segments
+            # may arrive lazily, so they are drawn inside the scope)
+            with (_biasing.scope(req.bias_table) if getattr(req, "bias_table", None) is not None else contextlib.nullcontext()):
+                result, info = self.transcriber.transcribe(req.audio, language=req.language, task=req.task,
+                                                           initial_prompt=req.initial_prompt, vad_filter=req.use_vad,
+                                                           vad_parameters=req.vad_parameters if req.use_vad else None)
+                result = list(result) if result is not None else []
+            req.result = result
             req.info = info
         except Exception as e:  # noqa: BLE001
             req.error = e
@@ -221,6 +228,37 @@ class BatchInferenceWorker:
                 continue
             ready.append((req, req.audio, count / sr))
         return ready, enc
+
+    def _bias_set_for(self, requests: List[BatchRequest]):
+        """the set a batch with keyworded sessions decodes under, None for a batch without: ONE set kept per lane of the worker, so the same
+        sessions batch after batch upload their tables once (a slot uploads a set again only when it has grown); it is started afresh
+        when a batch's tables would overflow a pool cap. (A single batch holds at most max_batch tables: they fit a fresh set, whose
+        table count is the slot's item count at the most; a table past the pool's own caps raises here, for the whole batch.)"""
+        tables = [_biasing.compact_of(t) for t in (getattr(r, "bias_table", None) for r in requests) if t is not None]
+        if not tables:
+            return None
+        sets = self.__dict__.setdefault("_bias_sets", {})       # one per lane thread, like the slot it decodes on
+        bset = sets.get(threading.get_ident())
+        if bset is not None and all(bset.fits(t) for t in tables):
+            try:
+                for t in tables:
+                    if not t.empty:
+                        bset.add(t)
+                return bset
+            except ValueError:
+                pass
+        bset = sets[threading.get_ident()] = _biasing.BiasSet()
+        for t in tables:
+            if not t.empty:
+                bset.add(t)
+        return bset
+
+    @staticmethod
+    def _bias_scope(requests: List[BatchRequest], bias_set):
+        """the scope a decode group of these requests runs under: biasing.item_scope of their tables, or nothing"""
+        if bias_set is None:
+            return contextlib.nullcontext()
+        return _biasing.item_scope([getattr(r, "bias_table", None) for r in requests], bias_set)
 
     def _process_multi(self, batch: List[BatchRequest]):
         tr = self.transcriber
@@ -281,15 +319,19 @@ class BatchInferenceWorker:
             suppress = get_suppressed_tokens(toks[0], [-1])
             final: List[Optional[tuple]] = [None] * n
             pending = list(range(n))
+            bias_set = self._bias_set_for([r for r, _a, _d in ready])
             for temp in self.TEMPERATURES:
                 if not pending:
                     break
                 sub_enc = enc if len(pending) == n else self._select(enc, pending, [ready[i][1] for i in pending])
-                results = tr.model.generate(
-                    sub_enc, [prompts[i] for i in pending], beam_size=5 if temp == 0.0 else 1, patience=1,
-                    length_penalty=1, max_length=tr.max_length, suppress_blank=True, suppress_tokens=suppress,
-                    return_scores=True, return_no_speech_prob=True, sampling_temperature=temp, repetition_penalty=1,
-                    no_repeat_ngram_size=0)
+                # keyword boosting: the group decodes under an item_scope of its sessions' tables (a re-decoded subset carries its own),
+                # all of them in one set of the group; a group without tables decodes as it always did
+                with self._bias_scope([ready[i][0] for i in pending], bias_set):
+                    results = tr.model.generate(
+                        sub_enc, [prompts[i] for i in pending], beam_size=5 if temp == 0.0 else 1, patience=1,
+                        length_penalty=1, max_length=tr.max_length, suppress_blank=True, suppress_tokens=suppress,
+                        return_scores=True, return_no_speech_prob=True, sampling_temperature=temp, repetition_penalty=1,
+                        no_repeat_ngram_size=0)
                 still = []
                 for j, idx in enumerate(pending):
                     g = results[j]

@@ -1,5 +1,6 @@
 // decoder.h — launchers for the autoregressive-decoder kernels (decoder.hip, dec_gemv.hip, dec_vocab.hip, search.hip).
 #pragma once
+#include <vector>
 #include "kernels.h"
 #include "../../include/wlx.h"
 
@@ -214,6 +215,26 @@ int bias_table_fill(int* block, int V, int n_nodes, const int32_t* edge_off, con
                     int n_tok, const int32_t* tok_ids, const float* tok_vals);
 // one wave per row, between the vocabulary projection and the search: the row's node from its parent's, then the two adds
 void launch_dec_bias(float* logits, const SearchParams* sp_dev, int rows, const SearchState& st, const BiasTable& bt, hipStream_t s);
+
+// Per-item tables (wlx_bias_set_items): up to WLX_BIAS_SET_MAX_TABLES tables in the COMPACT form packed into one pool of ints.
+// The pool starts with one header of BIAS_HDR_INTS ints per table slot (WLX_BIAS_SET_MAX_TABLES of them, so the arrays start at a fixed
+// place); behind them, packed back to back over all tables: the edge offsets (n_nodes + 1 per table, local to the table's edges), the edge
+// tokens, the edge nexts (WLX_BIAS_EDGE_SHARED set on an own edge whose token the root's list has too), the logit_bias ids and values.
+// Header of table t, at pool + t * BIAS_HDR_INTS: the pool index of its offsets, edge tokens, edge nexts, ids, values; n_nodes; n_tok; the
+// bits of its float boost. Node 0's list is the root's; node n != 0 stores only its own edges.
+#define BIAS_HDR_INTS 8
+#define WLX_BIAS_POOL_INTS (WLX_BIAS_SET_MAX_TABLES * BIAS_HDR_INTS + (WLX_BIAS_SET_MAX_NODES + WLX_BIAS_SET_MAX_TABLES) + 2 * WLX_BIAS_SET_MAX_EDGES + 2 * WLX_BIAS_SET_MAX_TOKENS)
+struct BiasItems {
+    const int* pool;            // [WLX_BIAS_POOL_INTS] as above
+    const int* sel;             // [max_batch] table of item b of the decode group, -1: none
+    short* state;               // the slot's [cache_rows][448] states (BiasTable::state): a state is local to the item's table
+};
+// checks a set as wlx_bias_set_items documents it (0, or WLX_ERR_ARG with the message set) and packs it into `pool` (resized to the used
+// length, at most WLX_BIAS_POOL_INTS)
+int bias_items_fill(std::vector<int>& pool, int V, int n_tables, const int32_t* n_nodes, const int32_t* edge_off, const int32_t* edge_tok,
+                    const int32_t* edge_next, const float* boosts, const int32_t* n_tok, const int32_t* tok_ids, const float* tok_vals);
+// one wave per row, like launch_dec_bias: the table of the row's item, the row's node in it, then the adds
+void launch_dec_bias_items(float* logits, const SearchParams* sp_dev, int rows, const SearchState& st, const BiasItems& bi, hipStream_t s);
 
 // softmax over ids [0, vlim) of row r, probability of token toks[r] -> out[r]   (text_token_probs of Whisper.align)
 void launch_token_prob_rows(const float* logits, long ldl, int vlim, int rows, const int* toks, float* out, hipStream_t s);

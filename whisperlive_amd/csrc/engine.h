@@ -15,11 +15,14 @@
 
 namespace wlx {
 
+enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2 };   // a slot's keyword boosting: none, one table, a table per item
+
 // what a captured decode-step graph depends on (engine_decode.hip get_step_graph)
 struct StepGraphKey {
     int rows, R, groups, nsteps;
     bool busy, sampling;
-    bool bias;                  // the step launches dec_bias_kernel in front of the search (the slot has a bias table: wlx_bias_set)
+    int bias;                   // BiasMode of the slot: the step launches dec_bias_kernel (one table: wlx_bias_set) or dec_bias_items_kernel (per item:
+                                // wlx_bias_set_items) in front of the search, or nothing; a graph captured for one mode is never replayed for another
     bool operator<(const StepGraphKey& o) const {
         return std::tie(rows, R, groups, nsteps, busy, sampling, bias) < std::tie(o.rows, o.R, o.groups, o.nsteps, o.busy, o.sampling, o.bias);
     }
@@ -97,8 +100,14 @@ struct Slot {
     SearchParams* d_sp = nullptr;
     // keyword boosting (wlx_bias_set / wlx_bias_clear; dec_bias.hip): the table's device block and the per-(cache row, position) states, allocated
     // at the first wlx_bias_set and kept at those addresses for the slot's life; `h_bias` is the block's pinned staging (rewritten only behind a
-    // wait for the stream); `bias_on`: the decode steps launch dec_bias_kernel
-    BiasTable bias{}; int* d_bias = nullptr; int* h_bias = nullptr; bool bias_on = false;
+    // wait for the stream); `bias_mode`: what the decode steps launch in front of the search (engine_decode.hip launch_bias)
+    BiasTable bias{}; int* d_bias = nullptr; int* h_bias = nullptr; int bias_mode = BIAS_NONE;
+    short* bias_state = nullptr;                     // [max(cache_rows, rows_cap)][448], shared by the two modes (allocated by whichever comes first)
+    // per-item tables (wlx_bias_set_items / wlx_bias_select): the pool, its pinned staging, the selection and its pinned staging, allocated at the
+    // first wlx_bias_set_items and kept at those addresses. `sel_n`: items the selection covers; `ev_sel` is recorded behind the selection's copy,
+    // the next select waits for it before it rewrites the pinned side (the pool's staging waits for the stream, like h_bias)
+    BiasItems bias_items{}; int* d_pool = nullptr; int* h_pool = nullptr; int* d_sel = nullptr; int* h_sel = nullptr;
+    int bias_tables = 0, sel_n = 0; hipEvent_t ev_sel = nullptr; bool sel_pending = false;
     unsigned* d_suppress = nullptr;
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging

@@ -198,6 +198,7 @@ static void slot_free(Slot* s) {
     if (s->ev_en1) (void)hipEventDestroy(s->ev_en1);
     for (hipEvent_t ev : s->rs.copied) if (ev) (void)hipEventDestroy(ev);
     if (s->ck_staged) (void)hipEventDestroy(s->ck_staged);
+    if (s->ev_sel) (void)hipEventDestroy(s->ev_sel);
     if (s->ev_pcm) (void)hipEventDestroy(s->ev_pcm);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;

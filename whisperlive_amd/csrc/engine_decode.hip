@@ -334,9 +334,11 @@ static int graph_steps_for(const Slot* s, int rows) {
 }
 
 // keyword boosting: with a table installed on the slot (wlx_bias_set) one launch between the vocabulary projection and the search adds the
-// row's bias to its logits (dec_bias.hip); a slot without a table launches nothing here, so its step is the launch list it always was
+// row's bias to its logits (dec_bias.hip); a slot without a table launches nothing here, so its step is the launch list it always was. In
+// per-item mode (wlx_bias_set_items) the launch is dec_bias_items_kernel: the table selected for the row's item (wlx_bias_select)
 void wlx::launch_bias(Slot* s, int rows) {
-    if (s->bias_on) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
+    if (s->bias_mode == BIAS_ONE) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
+    else if (s->bias_mode == BIAS_ITEMS) launch_dec_bias_items(s->logits, s->d_sp, rows, s->st, s->bias_items, s->stream);
 }
 
 static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps) {
@@ -349,7 +351,7 @@ static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool s
 
 static int get_step_graph(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps, hipGraphExec_t* out) {
     s->busy_variant = device_is_busy(s);
-    const StepGraphKey key{rows, R, groups, nsteps, s->busy_variant, sampling, s->bias_on};
+    const StepGraphKey key{rows, R, groups, nsteps, s->busy_variant, sampling, s->bias_mode};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { *out = it->second; return WLX_OK; }
     hipGraph_t graph;
@@ -664,6 +666,8 @@ int wlx::generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, co
                        const int32_t* enc_items, const wlx_gen_opts* o, bool injected_logits, const float* inj, int inj_steps,
                        int32_t* tokens_out, int tstride, int32_t* n_tokens_out, float* scores_out, float* nsp_out) {
     CKR(validate_opts(e, s, batch, o));
+    if (s->bias_mode == BIAS_ITEMS && batch > s->sel_n)
+        return set_error(WLX_ERR_STATE, "generate: %d items, but the bias selection covers %d (wlx_bias_select)", batch, s->sel_n);
     static const bool gen_trace = getenv("WLX_GEN_TRACE") != nullptr;
     double tg[2] = {0.0, 0.0};                                  // WLX_GEN_TRACE: host time in graph launch calls / in the polling waits
     const double tg0 = now_us();
@@ -757,6 +761,14 @@ extern "C" int32_t wlx_generate(wlx_engine* e, int32_t slot, int32_t batch, cons
 
 // ---- keyword boosting: the slot's bias table (include/wlx.h; dec_bias.hip). The device block, the state table and the pinned staging are
 // allocated at the first call and stay where they are, so a step graph captured with a table replays with every later one.
+static int bias_state_alloc(Slot* s) {           // the per-(cache row, position) states, shared by the single-table and the per-item mode
+    if (s->bias_state) return WLX_OK;
+    short* state = nullptr;
+    CKR(dalloc(s->allocs, &state, (size_t)std::max(s->cache_rows, s->rows_cap) * WLX_T_TEXT, true));
+    s->bias_state = state;
+    return WLX_OK;
+}
+
 extern "C" int32_t wlx_bias_set(wlx_engine* e, int32_t slot, int32_t n_nodes, const int32_t* edge_off, const int32_t* edge_tok,
                                 const int32_t* edge_next, float boost, int32_t n_tok, const int32_t* tok_ids, const float* tok_vals) {
     SlotGuard sg_;
@@ -766,28 +778,84 @@ extern "C" int32_t wlx_bias_set(wlx_engine* e, int32_t slot, int32_t n_nodes, co
     std::vector<int> block((size_t)WLX_BIAS_TABLE_INTS, 0);
     CKR(bias_table_fill(block.data(), e->spec.vocab, n_nodes, edge_off, edge_tok, edge_next, boost, n_tok, tok_ids, tok_vals));
     CK(hipSetDevice(e->device));
+    CKR(bias_state_alloc(s));
     if (!s->d_bias) {
         int *blk = nullptr, *stage = nullptr;
-        short* state = nullptr;
         CKR(dalloc(s->allocs, &blk, (size_t)WLX_BIAS_TABLE_INTS, true));
-        CKR(dalloc(s->allocs, &state, (size_t)std::max(s->cache_rows, s->rows_cap) * WLX_T_TEXT, true));
         CKR(halloc(s->host_allocs, &stage, (size_t)WLX_BIAS_TABLE_INTS));
         memset(stage, 0, sizeof(int) * WLX_BIAS_TABLE_INTS);
-        s->d_bias = blk; s->h_bias = stage; s->bias = bias_table_at(blk, state);
+        s->d_bias = blk; s->h_bias = stage; s->bias = bias_table_at(blk, s->bias_state);
     }
     // the staging may still feed the copy of the previous table: wait for the stream, then rewrite it
     CK(hipStreamSynchronize(s->stream));
     memcpy(s->h_bias, block.data(), sizeof(int) * WLX_BIAS_TABLE_INTS);
     CK(hipMemcpyAsync(s->d_bias, s->h_bias, sizeof(int) * WLX_BIAS_TABLE_INTS, hipMemcpyHostToDevice, s->stream));
-    s->bias_on = true;
+    s->bias_mode = BIAS_ONE;
     return WLX_OK;
 }
 
 extern "C" int32_t wlx_bias_clear(wlx_engine* e, int32_t slot) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
-    sg_.s->bias_on = false;
+    sg_.s->bias_mode = BIAS_NONE;
     return WLX_OK;
+}
+
+// ---- per-item tables (include/wlx_bias_items.h; dec_bias.hip dec_bias_items_kernel). The pool, the selection and their pinned stagings are allocated at
+// the first call and stay where they are: a step graph captured in per-item mode replays with every later set and selection.
+static int bias_select_upload(Slot* s, int n, const int32_t* table_of_item) {
+    // the pinned side may still feed the previous selection's copy: wait for THAT copy, not for the whole stream
+    if (s->sel_pending) { CK(hipEventSynchronize(s->ev_sel)); s->sel_pending = false; }
+    for (int b = 0; b < s->B; ++b) s->h_sel[b] = (table_of_item && b < n) ? table_of_item[b] : -1;
+    CK(hipMemcpyAsync(s->d_sel, s->h_sel, sizeof(int) * (size_t)s->B, hipMemcpyHostToDevice, s->stream));
+    CK(hipEventRecord(s->ev_sel, s->stream));
+    s->sel_pending = true;
+    s->sel_n = n;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_bias_set_items(wlx_engine* e, int32_t slot, int32_t n_tables, const int32_t* n_nodes, const int32_t* edge_off,
+                                      const int32_t* edge_tok, const int32_t* edge_next, const float* boosts, const int32_t* n_tok,
+                                      const int32_t* tok_ids, const float* tok_vals) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    // a refused set leaves whatever is installed whole (and allocates nothing): checked into a host copy first
+    std::vector<int> pool;
+    CKR(bias_items_fill(pool, e->spec.vocab, n_tables, n_nodes, edge_off, edge_tok, edge_next, boosts, n_tok, tok_ids, tok_vals));
+    CK(hipSetDevice(e->device));
+    CKR(bias_state_alloc(s));
+    if (!s->d_pool) {
+        int *dp = nullptr, *hp = nullptr, *ds = nullptr, *hs = nullptr;
+        CKR(dalloc(s->allocs, &dp, (size_t)WLX_BIAS_POOL_INTS, true));
+        CKR(dalloc(s->allocs, &ds, (size_t)s->B, true));
+        CKR(halloc(s->host_allocs, &hp, (size_t)WLX_BIAS_POOL_INTS));
+        CKR(halloc(s->host_allocs, &hs, (size_t)s->B));
+        CK(hipEventCreateWithFlags(&s->ev_sel, hipEventDisableTiming));
+        s->d_pool = dp; s->h_pool = hp; s->d_sel = ds; s->h_sel = hs;
+        s->bias_items = BiasItems{dp, ds, s->bias_state};
+    }
+    CK(hipStreamSynchronize(s->stream));         // the pool's staging may still feed the copy of the previous set
+    memcpy(s->h_pool, pool.data(), sizeof(int) * pool.size());
+    CK(hipMemcpyAsync(s->d_pool, s->h_pool, sizeof(int) * pool.size(), hipMemcpyHostToDevice, s->stream));   // (the used part only)
+    s->bias_tables = n_tables;
+    CKR(bias_select_upload(s, s->B, nullptr));   // every item deselected: a table index of an earlier set never reaches this one
+    s->bias_mode = BIAS_ITEMS;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_bias_select(wlx_engine* e, int32_t slot, int32_t n, const int32_t* table_of_item) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (s->bias_mode != BIAS_ITEMS) return set_error(WLX_ERR_STATE, "bias select: no table set installed (wlx_bias_set_items)");
+    if (!table_of_item) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > s->B) return set_error(WLX_ERR_ARG, "bias select: %d items outside 1..%d", n, s->B);
+    for (int b = 0; b < n; ++b)
+        if (table_of_item[b] < -1 || table_of_item[b] >= s->bias_tables)
+            return set_error(WLX_ERR_ARG, "bias select: item %d names table %d outside -1..%d", b, table_of_item[b], s->bias_tables - 1);
+    CK(hipSetDevice(e->device));
+    return bias_select_upload(s, n, table_of_item);
 }
 
 extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot, const int32_t* lang_ids,

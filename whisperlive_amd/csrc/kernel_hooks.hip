@@ -8,6 +8,7 @@
 //   wlx_debug_dec_cq_cross_attn  launch_dec_cq_cross_attn (decoder.hip)
 //   wlx_debug_dtw, wlx_debug_align_post   launch_align_dtw / launch_align_cost (align.hip)
 //   wlx_debug_bias_apply         launch_dec_bias (dec_bias.hip)
+//   wlx_debug_bias_apply_items   launch_dec_bias_items (dec_bias.hip)
 //   wlx_debug_token_prob, _token_prob_rows, _lang_probs   launch_token_prob / _token_prob_rows / launch_lang_probs (search.hip)
 //   wlx_debug_dec_embed          launch_dec_embed (decoder.hip)
 //   wlx_debug_prep_windows       launch_prep_windows (logmel.hip)
@@ -596,6 +597,68 @@ extern "C" int32_t wlx_debug_bias_apply(int32_t device, int32_t vocab, int32_t e
     SearchState st{};
     st.done = dzero; st.item_done = dzero + 1; st.row_done = dzero + 4; st.plen = dplen; st.token = dtok; st.pos = dpos; st.anc = danc; st.nsp_row = dnsp;
     launch_dec_bias(dl, dsp, rows, st, bias_table_at(dblock, dstate), S.st);
+    CKR(S.download(logits, dl, (size_t)rows * ldl));
+    CKR(S.download(state.data(), dstate, state.size()));
+    CKR(S.finish());
+    for (int r = 0; r < rows; ++r) state_out[r] = state[(size_t)r * WLX_T_TEXT + pos[r]];
+    return WLX_OK;
+}
+
+// wlx_debug_bias_apply_items: launch_dec_bias_items (dec_bias.hip) on a search state built here for `items` items of R beams each
+extern "C" int32_t wlx_debug_bias_apply_items(int32_t device, int32_t vocab, int32_t eot, int32_t n_tables, const int32_t* n_nodes,
+                                              const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* boosts,
+                                              const int32_t* n_tok, const int32_t* tok_ids, const float* tok_vals, float* logits, int32_t items,
+                                              int32_t R, const int32_t* sel, int64_t ldl, const int32_t* tokens, const int32_t* pos,
+                                              const int32_t* parent, const int32_t* plen, const int32_t* nsp_row, const int16_t* prev_state,
+                                              int16_t* state_out) {
+    if (!logits || !sel || !tokens || !pos || !parent || !plen || !nsp_row || !prev_state || !state_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (vocab < 1 || vocab > (1 << 20) || ldl < vocab) return set_error(WLX_ERR_ARG, "vocab %d / ldl %lld", vocab, (long long)ldl);
+    if (items < 1 || items > 64 || R < 1 || (long)items * R > WLX_MAX_DEC_ROWS)
+        return set_error(WLX_ERR_ARG, "%d items of %d rows: items in 1..64, at most %d rows", items, R, WLX_MAX_DEC_ROWS);
+    const int rows = items * R;
+    std::vector<int> pool, zeros((size_t)rows + items + 4, 0);
+    std::vector<short> anc((size_t)rows * WLX_T_TEXT, 0), state((size_t)rows * WLX_T_TEXT, 0);
+    SearchParams sp{};
+    CKR(bias_items_fill(pool, vocab, n_tables, n_nodes, edge_off, edge_tok, edge_next, boosts, n_tok, tok_ids, tok_vals));
+    for (int b = 0; b < items; ++b) {
+        if (sel[b] < -1 || sel[b] >= n_tables) return set_error(WLX_ERR_ARG, "item %d names table %d outside -1..%d", b, sel[b], n_tables - 1);
+        if (plen[b] < 1 || plen[b] > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "item %d: plen %d outside 1..%d", b, plen[b], WLX_T_TEXT);
+    }
+    for (int r = 0; r < rows; ++r) {
+        if (pos[r] < 0 || pos[r] >= WLX_T_TEXT) return set_error(WLX_ERR_ARG, "row %d: position %d outside 0..%d", r, pos[r], WLX_T_TEXT - 1);
+        if (parent[r] < 0 || parent[r] >= rows) return set_error(WLX_ERR_ARG, "row %d: parent %d outside 0..%d", r, parent[r], rows - 1);
+        if (prev_state[r] < 0) return set_error(WLX_ERR_ARG, "row %d: state %d is negative", r, prev_state[r]);
+        if (pos[r] >= 1) {
+            anc[(size_t)r * WLX_T_TEXT + pos[r] - 1] = (short)parent[r];
+            state[(size_t)parent[r] * WLX_T_TEXT + pos[r] - 1] = prev_state[r];
+        }
+        anc[(size_t)r * WLX_T_TEXT + pos[r]] = (short)r;
+    }
+    // the launch writes row r's state at pos[r]: no row may read that word as its parent's
+    for (int q = 0; q < rows; ++q)
+        if (pos[q] >= plen[q / R] && pos[q] >= 1 && pos[parent[q]] == pos[q] - 1)
+            return set_error(WLX_ERR_ARG, "row %d reads the state row %d writes in this launch (position %d)", q, parent[q], pos[q] - 1);
+    sp.V = vocab; sp.ldl = ldl; sp.items = items; sp.R = R; sp.rows = rows; sp.sampling = 0; sp.beam = R; sp.num_hyp = 1; sp.eot = eot;
+    HookScope S;
+    CKR(S.begin(device));
+    int *dpool = nullptr, *dzero = nullptr, *dplen = nullptr, *dsel = nullptr, *dtok = nullptr, *dpos = nullptr, *dnsp = nullptr;
+    short *danc = nullptr, *dstate = nullptr;
+    float* dl = nullptr;
+    SearchParams* dsp = nullptr;
+    CKR(S.upload(&dpool, pool.data(), pool.size()));
+    CKR(S.upload(&dzero, zeros.data(), zeros.size()));
+    CKR(S.upload(&dplen, plen, (size_t)items));
+    CKR(S.upload(&dsel, sel, (size_t)items));
+    CKR(S.upload(&dtok, tokens, (size_t)rows));
+    CKR(S.upload(&dpos, pos, (size_t)rows));
+    CKR(S.upload(&dnsp, nsp_row, (size_t)rows));
+    CKR(S.upload(&danc, anc.data(), anc.size()));
+    CKR(S.upload(&dstate, state.data(), state.size()));
+    CKR(S.upload(&dl, logits, (size_t)rows * ldl));
+    CKR(S.upload(&dsp, &sp, (size_t)1));
+    SearchState st{};
+    st.done = dzero; st.item_done = dzero + 1; st.row_done = dzero + 1 + items; st.plen = dplen; st.token = dtok; st.pos = dpos; st.anc = danc; st.nsp_row = dnsp;
+    launch_dec_bias_items(dl, dsp, rows, st, BiasItems{dpool, dsel, dstate}, S.st);
     CKR(S.download(logits, dl, (size_t)rows * ldl));
     CKR(S.download(state.data(), dstate, state.size()));
     CKR(S.finish());

@@ -623,6 +623,23 @@ class Slot:
                                     ids.size, _i32p(ids), _f32p(vals)))
         self._bias_table = table
 
+    def set_bias_items(self, bias_set) -> None:
+        """Install a biasing.BiasSet on the slot (wlx_bias_set_items): the slot decodes in per-item mode, every item deselected until
+        `select_bias`. WlxError (ERR_ARG) for a set the library refuses; whatever is installed stays."""
+        if len(bias_set) < 1:
+            raise ValueError("an empty BiasSet installs nothing: clear_bias")
+        if bias_set.vocab != self.engine.spec.vocab:
+            raise ValueError(f"the bias set was compiled for a vocabulary of {bias_set.vocab}, the model has {self.engine.spec.vocab}")
+        nn, off, tok, nxt, boosts, nt, ids, vals = bias_set.packed()
+        check(self.lib.wlx_bias_set_items(self.engine._h, self.sid, len(bias_set), _i32p(nn), _i32p(off), _i32p(tok), _i32p(nxt),
+                                          _f32p(boosts), _i32p(nt), _i32p(ids), _f32p(vals)))
+        self._bias_table, self._bias_set_version = bias_set, bias_set.version
+
+    def select_bias(self, indices: Sequence[int]) -> None:
+        """indices[b]: the table (an index into the installed set, -1: none) of item b of the following generate calls (wlx_bias_select)"""
+        sel = np.ascontiguousarray(list(indices), dtype=np.int32)
+        check(self.lib.wlx_bias_select(self.engine._h, self.sid, sel.size, _i32p(sel)))
+
     def clear_bias(self) -> None:
         """Decode without a bias table again (wlx_bias_clear)."""
         check(self.lib.wlx_bias_clear(self.engine._h, self.sid))

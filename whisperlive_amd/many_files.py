@@ -55,12 +55,14 @@ while the wave's sources still lie behind their items: a caller cannot diarize a
 """
 from __future__ import annotations
 
+import contextlib
 import inspect
 import time
 from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import biasing as _biasing
 from . import vad as _vad
 from . import word_timing as _wt
 from .batched import MAX_DEC_ROWS, DeviceChunks, _collect_ranges, _file_bytes, _options, _put_audio, _put_audio_many, _segment, _vad_options
@@ -158,6 +160,65 @@ def per_file_arguments(a: dict, n_files: int) -> List[dict]:
     return [{**a, **{name: v[i] for name, v in split.items()}} for i in range(n_files)]
 
 
+BIAS_KEYWORDS = ("keywords", "keywords_boost", "logit_bias")     # job keywords of keyword boosting; each may be a list, one entry per file
+
+
+def per_file_tables(model, bias_args: dict, n_files: int) -> list:
+    """the job's `keywords` / `keywords_boost` / `logit_bias` -> per file a biasing.CompactTable, None (nothing to add) or the
+    ValueError its table was refused with (the cap named). `keywords`: a list of strings is ONE list for every file; a list with one
+    entry per file, each None or a list of phrases, is per file. `keywords_boost`: a number or a list of numbers (or None) per file;
+    `logit_bias`: a dict or a list of dicts (or None) per file. Equal lists share one table object."""
+    kw, boost, lb = (bias_args.get(name) for name in BIAS_KEYWORDS)
+    if kw is None and lb is None:
+        if boost is not None:
+            raise ValueError("keywords_boost needs keywords")
+        return [None] * n_files
+
+    def spread(v, what, per_file):
+        if per_file:
+            if len(v) != n_files:
+                raise ValueError(f"{what}: a list of {len(v)} entries for {n_files} files (one entry per file, or one value for all)")
+            return list(v)
+        return [v] * n_files
+    is_list = lambda k: isinstance(k, (list, tuple))
+    token_list = lambda k: is_list(k) and len(k) > 0 and all(isinstance(t, (int, np.integer)) for t in k)
+    # per file: every entry is None or a list of phrases (a list whose entries are all token lists is ONE list of phrases)
+    kws = spread(kw, "keywords", is_list(kw) and len(kw) > 0 and all(k is None or is_list(k) for k in kw) and not all(token_list(k) for k in kw))
+    boosts = spread(boost, "keywords_boost", isinstance(boost, (list, tuple)))
+    lbs = spread(lb, "logit_bias", isinstance(lb, (list, tuple)))
+    if not hasattr(model, "compile_keywords"):
+        raise ValueError("keywords: this transcriber does not bias")
+    out, seen = [], {}
+    for k, b, l in zip(kws, boosts, lbs):
+        if k is None and l is None:
+            out.append(None)
+            continue
+        key = repr((k, b, sorted(l.items()) if isinstance(l, dict) else l))
+        if key not in seen:
+            try:
+                t = model.compile_keywords(k, b, l, compact=True)
+                seen[key] = None if t.empty else t
+            except ValueError as e:
+                seen[key] = e
+        out.append(seen[key])
+    return out
+
+
+def fit_tables(wave: List[int], tables: list):
+    """the longest head of `wave` whose distinct tables fit one biasing.BiasSet (at least one file: a single table always fits, its
+    own caps were checked when it was compiled), and that set (None: no file of it has a table)"""
+    bias_set = _biasing.BiasSet()
+    for k, i in enumerate(wave):
+        t = tables[i]
+        if t is None or isinstance(t, Exception):
+            continue
+        if k and not bias_set.fits(t):
+            wave = wave[:k]
+            break
+        bias_set.add(t)
+    return wave, (bias_set if len(bias_set) else None)
+
+
 def per_file_diarizers(pipe, diarize, max_speakers, n_files: int) -> List[tuple]:
     """the `diarize` / `max_speakers` arguments -> one (FileDiarizer or None, cap or None) per file. `diarize`: False | True |
     FileDiarizer, or a list with one of those per file; True is the pipeline's `file_diarizer` (made once from the configured speaker
@@ -213,6 +274,8 @@ class _File:
         self.language = (None, None, None)
         self.segments: list = []
         self.left = 0                       # chunks not decoded yet
+        self.table = None                   # the file's keyword table (biasing.CompactTable) and the set of its wave's tables
+        self.bias_set = None
         self.last_speech = 0.0
 
 
@@ -235,6 +298,7 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     if on_error not in ("return", "raise"):
         raise ValueError(f"on_error {on_error!r}: 'return' or 'raise'")
     wave_put = bool(kwargs.pop("wave_put", False))
+    bias_args = {name: kwargs.pop(name, None) for name in BIAS_KEYWORDS}
     diarize, max_speakers = kwargs.pop("diarize", False), kwargs.pop("max_speakers", None)
     if kwargs.pop("multichannel", False):
         raise ValueError("transcribe_many: multichannel=True is not part of this route (transcribe the files one by one with "
@@ -260,11 +324,17 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     check_batch(batch_size, max_batch)
     per_file = per_file_arguments(a, len(audios))
     diarizers = per_file_diarizers(pipe, diarize, max_speakers, len(audios))
-    return _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers)
+    tables = per_file_tables(pipe.model, bias_args, len(audios))        # compiled here, before any audio work
+    return _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables)
 
 
-def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None):
+def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None, tables=None):
     model = pipe.model
+    tables = tables if tables is not None else [None] * len(audios)
+    if on_error == "raise":
+        for t in tables:
+            if isinstance(t, Exception):
+                raise t
     timing = pipe.many_timing = {"front_s": 0.0, "total_s": 0.0, "waves": 0}
     t_job = time.perf_counter()
     loaded, lengths = [], []
@@ -287,8 +357,15 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: b
         # sized when the job gets there: the slot's rows are as long as the longest audio it was ever asked to hold — by an earlier wave,
         # an earlier job or another route on this thread's slot — and the chunk gather's reach is measured in rows of THAT length
         wave = next_wave(lengths, at, batch_size, max_batch, stride=int(getattr(slot, "pcm_longest", 0)))
+        wave, bias_set = fit_tables(wave, tables)       # (a wave closes early where its distinct tables would overflow a pool cap)
         at = wave[-1] + 1
         files = [_File(i, per_file[i], loaded[i], batch_size + k, *(diarizers[i] if diarizers else ())) for k, i in enumerate(wave)]
+        for f in files:
+            if isinstance(tables[f.index], Exception):
+                f.audio = tables[f.index]               # a refused table costs only its file: it fails at its turn, like a file not read
+            else:
+                f.table = tables[f.index]
+            f.bias_set = bias_set
         for i in wave:
             loaded[i] = None                # (the job does not hold a file's bytes past its wave)
         yield from _wave(pipe, slot, files, a, vad_parameters, batch_size, on_error, timing, wave_put)
@@ -537,12 +614,17 @@ def _decode_group(pipe, slot, group) -> list:
     for limit in sorted(set(limits)):
         idx = [i for i in range(n) if limits[i] == limit]
         o = group[idx[0]][0].options               # (what a generate call takes from the options is the same for every file of a job)
-        results = model.model.generate(
-            encoder_output if len(idx) == n else encoder_output.select(idx), [prompts[i] for i in idx], beam_size=o.beam_size,
-            patience=o.patience, length_penalty=o.length_penalty, max_length=limit, suppress_blank=o.suppress_blank,
-            suppress_tokens=o.suppress_tokens, return_scores=True, return_no_speech_prob=True,
-            sampling_temperature=o.temperatures[0], repetition_penalty=o.repetition_penalty,
-            no_repeat_ngram_size=o.no_repeat_ngram_size)
+        # keyword boosting per file: the decode runs under an item_scope of the tables of the files ITS items come from (a subset
+        # carries its own), all of them in the wave's one set; a job without tables decodes as it always did
+        biased = group[idx[0]][0].bias_set is not None      # (a group without a table in a wave that has some: every item deselected, the set stays)
+        scope = _biasing.item_scope([group[i][0].table for i in idx], group[idx[0]][0].bias_set) if biased else contextlib.nullcontext()
+        with scope:
+            results = model.model.generate(
+                encoder_output if len(idx) == n else encoder_output.select(idx), [prompts[i] for i in idx], beam_size=o.beam_size,
+                patience=o.patience, length_penalty=o.length_penalty, max_length=limit, suppress_blank=o.suppress_blank,
+                suppress_tokens=o.suppress_tokens, return_scores=True, return_no_speech_prob=True,
+                sampling_temperature=o.temperatures[0], repetition_penalty=o.repetition_penalty,
+                no_repeat_ngram_size=o.no_repeat_ngram_size)
         for i, result in zip(idx, results):
             seq_len = len(result.sequences_ids[0])
             cum_logprob = result.scores[0] * (seq_len ** o.length_penalty)

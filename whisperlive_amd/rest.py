@@ -181,9 +181,10 @@ def parse_bool_field(value: Optional[str], name: str) -> bool:
     return s in _TRUE
 
 
-def keyword_scope(transcriber, keywords: Sequence[str], keywords_boost: Optional[str]):
+def keyword_scope(transcriber, keywords: Sequence[str], keywords_boost: Optional[str], compact: bool = False):
     """The `keywords` (repeatable) and `keywords_boost` form fields -> the context manager under which the upload is decoded
-    (WhisperModelHIP.keyword_bias on the request's thread), or None without keywords. _HttpError 400: a boost that is not a finite
+    (WhisperModelHIP.keyword_bias on the request's thread), or None without keywords. compact=True compiles the compact form, the
+    one a pooled job decodes under (many_files.py): the pooled route validates with it and does not enter the scope. _HttpError 400: a boost that is not a finite
     number, an empty keyword, a boost without keywords, a table past a cap (the message names it: nodes, edges), a transcriber that
     does not bias."""
     boost = None
@@ -201,7 +202,7 @@ def keyword_scope(transcriber, keywords: Sequence[str], keywords_boost: Optional
     if not hasattr(transcriber, "keyword_bias"):
         raise _HttpError(400, {"error": "keywords: this server's transcriber does not bias"})
     try:
-        return transcriber.keyword_bias(phrases=list(keywords), boost=boost)
+        return transcriber.keyword_bias(phrases=list(keywords), boost=boost, **({"compact": True} if compact else {}))
     except ValueError as e:
         raise _HttpError(400, {"error": f"keywords: {e}"})
 
@@ -317,6 +318,12 @@ class _Upload:
         self.done, self.result, self.error = threading.Event(), None, None
 
 
+def pool_upload(has_batcher: bool, multichannel: bool, known_speaker_names, known_speaker_references) -> bool:
+    """whether an upload joins the pooled jobs: keywords do not keep it out (each file of a job has its own table); multichannel
+    files and known speakers do"""
+    return bool(has_batcher) and not multichannel and not known_speaker_names and not known_speaker_references
+
+
 class FileBatcher:
     """Pools concurrent uploads into BatchedInferencePipeline.iter_many jobs (RestServer keeps one per GPU). One worker thread: it takes the oldest waiting upload,
     collects for `window_s` seconds the uploads that arrive for the same transcriber with equal group-wide decode options (`shared`:
@@ -384,6 +391,8 @@ class FileBatcher:
                     **{name: [u.per_file[name] for u in job] for name in ("language", "initial_prompt", "hotwords")}, **job[0].shared,
                     **({"diarize": [u.per_file.get("diarize") or False for u in job], "max_speakers": [int(u.per_file.get("max_speakers") or 0) for u in job]}
                        if any(u.per_file.get("diarize") for u in job) else {}),
+                    **({"keywords": [u.per_file.get("keywords") for u in job], "keywords_boost": [u.per_file.get("keywords_boost") for u in job]}
+                       if any(u.per_file.get("keywords") for u in job) else {}),
                     **({"wave_put": True} if self.wave_put else {}))
                 for index, segments, info in results:
                     up = job[index]
@@ -575,14 +584,15 @@ class RestServer:
         return BatchedInferencePipeline(transcriber)
 
     def transcribe_pooled(self, transcriber, data: bytes, *, device_index: Optional[int] = None, language=None, initial_prompt=None,
-                          hotwords=None, diarize=None, max_speakers: int = 0, **shared):
+                          hotwords=None, diarize=None, max_speakers: int = 0, keywords=None, keywords_boost=None, **shared):
         """`transcribe_file` through the batcher (file_batch_window_ms > 0): the upload joins the uploads that arrive within the window
         and decode with the same `shared` options; -> (list of segments, info) of this upload, or its own error raised here, in the
         request's thread, where the single route would have raised it. Nothing is left for `resident_file_audio` after a pooled job
         (many_files.py), so speaker labels fall back to the second decode; requests with known speakers are not pooled at all.
         diarize: the FileDiarizer of a `diarize=true` upload (pooled_file_diarizer) with its max_speakers — the job finds the speakers
         while the wave's files are still resident: the segments and words come back with `.speaker`, the info with `.speakers`."""
-        per_file = dict(language=language, initial_prompt=initial_prompt, hotwords=hotwords, diarize=diarize or False, max_speakers=int(max_speakers))
+        per_file = dict(language=language, initial_prompt=initial_prompt, hotwords=hotwords, diarize=diarize or False, max_speakers=int(max_speakers),
+                        keywords=keywords, keywords_boost=keywords_boost)       # (per file: each upload of a job decodes under its own table)
         return self._batchers.get(device_index, self.batcher).submit(transcriber, data, per_file, shared)
 
     def translator_for(self, device_index: int, target_language: str):
@@ -866,25 +876,29 @@ class _Handler(BaseHTTPRequestHandler):
                     raise _HttpError(400, {"error": str(e)})
             transcriber = rest.transcriber_for(device_index)
             mc = {"multichannel": True} if multichannel else {}
-            # keywords: the table is compiled (and refused: 400) before the file is decoded; the upload is then decoded in this thread under
-            # it, not pooled — a decode group has one table. The segments may arrive lazily: they are drawn inside the scope.
-            bias = keyword_scope(transcriber, keywords, keywords_boost)
-            with (bias if bias is not None else contextlib.nullcontext()):
-                # a diarize=true upload without known speakers is pooled too: the job finds its speakers while the wave is resident
-                pooled = rest.batcher is not None and bias is None and not multichannel and not known_speaker_names and not known_speaker_references
-                pooled_diarizer = None
-                # (where the GPU's embedder has the wave call, diarize_many: without it pooling would only queue the per-file route)
-                if pooled and diarize and response_format == "verbose_json":
-                    try:
-                        pooled_diarizer = rest.pooled_file_diarizer(device_index)
-                    except ValueError as e:
-                        raise _HttpError(400, {"error": str(e)})
-                    if not hasattr(pooled_diarizer.embedder, "diarize_many"):
-                        pooled, pooled_diarizer = False, None
+            # a diarize=true upload without known speakers is pooled too: the job finds its speakers while the wave is resident
+            pooled = pool_upload(rest.batcher is not None, multichannel, known_speaker_names, known_speaker_references)
+            pooled_diarizer = None
+            # (where the GPU's embedder has the wave call, diarize_many: without it pooling would only queue the per-file route)
+            if pooled and diarize and response_format == "verbose_json":
+                try:
+                    pooled_diarizer = rest.pooled_file_diarizer(device_index)
+                except ValueError as e:
+                    raise _HttpError(400, {"error": str(e)})
+                if not hasattr(pooled_diarizer.embedder, "diarize_many"):
+                    pooled, pooled_diarizer = False, None
+            # keywords: the table is compiled (and refused: 400) before the file is decoded. An upload that is not pooled is decoded in this
+            # thread under it (the segments may arrive lazily: they are drawn inside the scope); a pooled one carries its keywords into the
+            # job, where every file decodes under its own table in the compact form (many_files.py: a decode group takes a table per
+            # item) — so that is the form its list is checked in here, and the scope is not entered.
+            bias = keyword_scope(transcriber, keywords, keywords_boost, compact=pooled)
+            with (bias if bias is not None and not pooled else contextlib.nullcontext()):
                 if pooled:
                     segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
                                                             temperature=temperature, word_timestamps=want_words, hotwords=hotwords,
-                                                            diarize=pooled_diarizer, max_speakers=max_speakers)
+                                                            diarize=pooled_diarizer, max_speakers=max_speakers,
+                                                            keywords=list(keywords) if bias is not None else None,
+                                                            keywords_boost=float(keywords_boost) if bias is not None and keywords_boost is not None and keywords_boost.strip() else None)
                 else:
                     segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
                                                           temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)

@@ -592,18 +592,19 @@ class ServeClientHIP(ServeClientBase):
             return None
 
     def transcribe_audio(self, input_sample):
-        if self._bias is not None:
-            # a session with keywords decodes on its own slot, in its own thread, under its table: the batch worker's decode groups
-            # mix sessions, and a group has one table
+        worker = ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS.get(self.device_index)
+        # a session with keywords stays in the batch worker: its request carries its table, and a decode group that mixes sessions
+        # takes a table per item (batching.py _process_multi). Without a worker it decodes on its own slot under its table.
+        table = self._bias.table if self._bias is not None else None
+        if worker is None and self._bias is not None:
             with self._bias:
                 return self._transcribe_direct(input_sample)
-        worker = ServeClientHIP.BATCH_WORKER or ServeClientHIP.BATCH_WORKERS.get(self.device_index)
         if worker is not None:
             from .batching import BatchRequest
             req = BatchRequest(audio=input_sample, language=self.language, task=self.task,
                                initial_prompt=self.initial_prompt, use_vad=self.use_vad,
                                vad_parameters=self.vad_parameters if self.use_vad else None,
-                               word_timestamps=self.word_timestamps, client_uid=self.client_uid)
+                               word_timestamps=self.word_timestamps, client_uid=self.client_uid, bias_table=table)
             worker.submit(req)
             req.future.wait(timeout=30)
             if isinstance(req.error, _vad.VadUnavailable) and self.use_vad:
@@ -612,7 +613,8 @@ class ServeClientHIP(ServeClientBase):
                 # chunk left the session alive but silent)
                 self._downgrade_vad(req.error)
                 req = BatchRequest(audio=input_sample, language=self.language, task=self.task, initial_prompt=self.initial_prompt,
-                                   use_vad=False, vad_parameters=None, word_timestamps=self.word_timestamps, client_uid=self.client_uid)
+                                   use_vad=False, vad_parameters=None, word_timestamps=self.word_timestamps, client_uid=self.client_uid,
+                                   bias_table=table)
                 worker.submit(req)
                 req.future.wait(timeout=30)
             if req.error:

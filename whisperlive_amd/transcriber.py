@@ -227,10 +227,23 @@ class _EngineModel:
         # keyword boosting: the calling thread's table (WhisperModelHIP.keyword_bias) goes onto the slot this call decodes on; a slot that
         # never saw a table is left alone
         table = _biasing.current()
-        if table is not None or getattr(slot, "_bias_table", None) is not None:
+        # per item: inside a biasing.item_scope every prompt has its own table (None: the thread's table, if any), and a
+        # compact table from keyword_bias(compact=True) is a one-table set selected for every item. The set goes up once per slot, the
+        # selection per decode group.
+        scope_items = _biasing.current_items()
+        sel = None
+        if scope_items is not None:
+            if len(scope_items.tables) != len(prompts):
+                raise ValueError(f"the item_scope names {len(scope_items.tables)} tables for {len(prompts)} prompts")
+            sel = _biasing.install_items(slot, scope_items.tables, scope_items.bias_set, fallback=table)
+        elif isinstance(table, _biasing.CompactTable):
+            sel = _biasing.install_items(slot, [table] * len(prompts), table.own_set())
+        elif table is not None or getattr(slot, "_bias_table", None) is not None:
             _biasing.install(slot, table)
         res = []
         for a in range(0, len(prompts), group):
+            if sel is not None:
+                slot.select_bias(sel[a:a + group])
             res.extend(slot.generate(prompts[a:a + group], o.token_ids, beam_size=beam_size, patience=patience,
                                      num_hypotheses=num_hypotheses, length_penalty=length_penalty,
                                      repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -459,16 +472,23 @@ class WhisperModelHIP:
     def _next_seed(self) -> int:
         return next(self._seed)
 
-    def keyword_bias(self, phrases=None, boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None):
+    def keyword_bias(self, phrases=None, boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None, compact: bool = False):
         """Context manager: inside the block every generate of the CALLING THREAD decodes with this bias table on its slot — the
-        streaming transcriber, BatchedInferencePipeline.transcribe, transcribe_many (one table per job) and the temperature fallback
+        streaming transcriber, BatchedInferencePipeline.transcribe, transcribe_many (this table for every file; its own `keywords=` argument takes a list per file) and the temperature fallback
         alike. `phrases`: strings or token lists to boost (biasing.py: an automaton over token ids, `boost` added to the logit of every
         token that continues a match; default biasing.DEFAULT_BOOST, which is not tuned); `logit_bias`: {token id: value}, added in
         every state, OpenAI style. Pre-softmax: the scores / avg_logprob are those of the biased distribution, and a bonus given on a
         partial match is not taken back. The table is compiled (and refused: ValueError names the cap) here, before the block runs.
-        Other threads are untouched; scopes nest. Decode groups that mix tables are not served: one table per call."""
-        return _biasing.scope(_biasing.compile_bias(phrases, boost, logit_bias, tokenizer=self._base_tokenizer, vocab=self.spec.vocab,
-                                                    eot=self.token_ids.eot))
+        Other threads are untouched; scopes nest. One table per thread here; a table per item of a decode group is biasing.item_scope
+        (transcribe_many, the file endpoint's pool and the batch worker use it). `compact=True` compiles the compact form
+        (biasing.compile_compact) and decodes through a one-table set selected for every item: the route for lists the closed form
+        refuses (its edge cap binds at a few dozen phrases); the same tokens and scores where both forms load."""
+        return _biasing.scope(self.compile_keywords(phrases, boost, logit_bias, compact=compact))
+
+    def compile_keywords(self, phrases=None, boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None, compact: bool = False):
+        """the table keyword_bias decodes under: biasing.BiasTable, or biasing.CompactTable with compact=True (ValueError names the cap)"""
+        fn = _biasing.compile_compact if compact else _biasing.compile_bias
+        return fn(phrases, boost, logit_bias, tokenizer=self._base_tokenizer, vocab=self.spec.vocab, eot=self.token_ids.eot)
 
     def close(self):
         with self._slots_lock:
@@ -606,10 +626,10 @@ class WhisperModelHIP:
                    hallucination_silence_threshold: Optional[float] = None, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    *, keywords=None, keywords_boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None,
-                   ) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
+                   keywords_compact: bool = False) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
         if keywords is not None or logit_bias is not None:
             # keyword boosting for this call alone (see keyword_bias): compiled before any audio work, so a refused table costs nothing
-            with self.keyword_bias(phrases=keywords, boost=keywords_boost, logit_bias=logit_bias):
+            with self.keyword_bias(phrases=keywords, boost=keywords_boost, logit_bias=logit_bias, compact=keywords_compact):
                 return self.transcribe(audio, language, task, log_progress, beam_size, best_of, patience, length_penalty, repetition_penalty,
                                        no_repeat_ngram_size, temperature, compression_ratio_threshold, log_prob_threshold,
                                        no_speech_threshold, condition_on_previous_text, prompt_reset_on_temperature, initial_prompt, prefix,
