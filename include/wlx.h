@@ -1122,6 +1122,22 @@ int32_t wlx_debug_prep_windows(int32_t device, const float* feats, int64_t feats
  * even, values past the fp16 range to +-inf, NaN to NaN. dst holds cap >= n halfs (copied in AND out). 1 <= n <= cap <= 2^28. */
 int32_t wlx_debug_f32_to_f16(int32_t device, const float* src, int64_t n, uint16_t* dst, int64_t cap);
 
+/* The three kernels of the Silero VAD pass (vad.hip), ONE launch each of the launch function the pass itself calls, on the object's
+ * stream under its mutex and with the weights as wlx_vad_create repacked them. Host arrays; the output holds cap_windows rows and
+ * WLX_DEBUG_GUARD words behind them, copied in AND out: words no thread owns come back unchanged. The packed-window geometry is that of
+ * wlx_vad_probs_batch (item i owns windows [sum T_0..i-1, + T_i), items without a window take none). WLX_ERR_ARG before any launch, with
+ * the output untouched: a null pointer (extra_zero_windows may be null: no extras), n outside 1..WLX_VAD_MAX_BATCH, a negative count,
+ * an extra outside 0..4, cap_windows outside 1..2^19, sum T_i > cap_windows. A call whose items have no window launches nothing.
+ * wlx_vad_debug_frontend (vad_frontend_batch_kernel): pcm as wlx_vad_probs_batch takes it -> gx [cap_windows][512], row w the input half
+ *   of the LSTM gates of window w: W_ih f + b_ih + b_hh, gate order i, f, g, o.
+ * wlx_vad_debug_lstm (vad_lstm_batch_kernel): gx [sum T_i][512] as above, item i of T[i] windows from zero state -> hs [cap_windows][512],
+ *   row w = [unit j][4 identical copies of h_j].
+ * wlx_vad_debug_out (vad_out_kernel): hs [T][512] -> probs [cap_windows]: sigmoid(out_w . relu(copy 0 of every unit) + out_b). */
+int32_t wlx_vad_debug_frontend(wlx_vad* v, const float* pcm, const int64_t* n_samples, const int32_t* extra_zero_windows, int32_t n,
+                               float* gx, int64_t cap_windows);
+int32_t wlx_vad_debug_lstm(wlx_vad* v, const float* gx, const int32_t* T, int32_t n, float* hs, int64_t cap_windows);
+int32_t wlx_vad_debug_out(wlx_vad* v, const float* hs, int32_t T, float* probs, int64_t cap_windows);
+
 #include "wlx_bias_items.h"
 
 #ifdef __cplusplus

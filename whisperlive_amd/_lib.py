@@ -42,6 +42,7 @@ EXPORTS = [
     "wlx_debug_dtw", "wlx_debug_align_post", "wlx_debug_align_timings", "wlx_debug_bias_apply",
     "wlx_debug_token_prob", "wlx_debug_token_prob_rows", "wlx_debug_lang_probs", "wlx_debug_dec_embed", "wlx_debug_prep_windows",
     "wlx_debug_f32_to_f16",
+    "wlx_vad_debug_frontend", "wlx_vad_debug_lstm", "wlx_vad_debug_out",
 ]
 # the per-item part of keyword boosting, declared in include/wlx_bias_items.h (which wlx.h includes): EXPORTS is wlx.h's own list
 EXPORTS_BIAS_ITEMS = ["wlx_bias_set_items", "wlx_bias_select", "wlx_debug_bias_apply_items"]
@@ -474,6 +475,9 @@ def load() -> C.CDLL:
     lib.wlx_debug_dec_embed.argtypes = [i32, u16p, i32, f32p, i32, i32, i32p, i32p, i32, f32p, i32p]
     lib.wlx_debug_prep_windows.argtypes = [i32, f32p, i64, i64, i32, i64, i32, i32p, i32p, u16p, i64]
     lib.wlx_debug_f32_to_f16.argtypes = [i32, f32p, i64, u16p, i64]
+    lib.wlx_vad_debug_frontend.argtypes = [vp, f32p, i64p, i32p, i32, f32p, i64]
+    lib.wlx_vad_debug_lstm.argtypes = [vp, f32p, i32p, i32, f32p, i64]
+    lib.wlx_vad_debug_out.argtypes = [vp, f32p, i32, f32p, i64]
     for name in EXPORTS + EXPORTS_BIAS_ITEMS:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_ring_group_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):

@@ -534,12 +534,24 @@ static void vad_plan_one(const float* pcm, long long n, int T, VadPlan& pl) {
 
 // the pass itself on v->stream, behind whatever the caller put there (an upload, a wait for another stream): one launch of each kernel
 // over the packed windows, one download, one wait. v->mu is held, the device is set and the per-window buffers hold pl.windows.
+// The three launches of the pass, each over the packed windows of `pl`. vad_run_batch and the wlx_vad_debug_* hooks call these and
+// nothing else, so a hook launches what the pass launches.
+static void vad_launch_frontend(const VadPlan& pl, const VadW& W, float* gx, hipStream_t st) {
+    hipLaunchKernelGGL(vad_frontend_batch_kernel, dim3(pl.groups), dim3(VAD_FE_THREADS), 0, st, pl.tab, W, gx);
+}
+static void vad_launch_lstm(const VadPlan& pl, const float* gx, const VadW& W, float* hs, hipStream_t st) {
+    hipLaunchKernelGGL(vad_lstm_batch_kernel, dim3(pl.tab.n), dim3(512), 0, st, pl.tab, gx, W.whhP, hs);
+}
+static void vad_launch_out(const float* hs, const VadW& W, float* probs, int T, hipStream_t st) {
+    hipLaunchKernelGGL(vad_out_kernel, dim3((T + 3) / 4), dim3(256), 0, st, hs, W.out_w, W.out_b, probs, T);
+}
+
 static int vad_run_batch(wlx_vad* v, const VadPlan& pl, float* probs_out, float* device_ms_out) {
     const int T = (int)pl.windows;
     CK(hipEventRecord(v->ev0, v->stream));
-    hipLaunchKernelGGL(vad_frontend_batch_kernel, dim3(pl.groups), dim3(VAD_FE_THREADS), 0, v->stream, pl.tab, v->W, v->d_gx);
-    hipLaunchKernelGGL(vad_lstm_batch_kernel, dim3(pl.tab.n), dim3(512), 0, v->stream, pl.tab, v->d_gx, v->W.whhP, v->d_hs);
-    hipLaunchKernelGGL(vad_out_kernel, dim3((T + 3) / 4), dim3(256), 0, v->stream, v->d_hs, v->W.out_w, v->W.out_b, v->d_probs, T);
+    vad_launch_frontend(pl, v->W, v->d_gx, v->stream);
+    vad_launch_lstm(pl, v->d_gx, v->W, v->d_hs, v->stream);
+    vad_launch_out(v->d_hs, v->W, v->d_probs, T, v->stream);
     CK(hipGetLastError());
     CK(hipEventRecord(v->ev1, v->stream));
     CK(hipMemcpyAsync(v->h_probs, v->d_probs, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, v->stream));
@@ -679,6 +691,105 @@ extern "C" int32_t wlx_vad_probs_pcm_batch(wlx_vad* v, wlx_engine* e, int32_t sl
     CKR(L.order(v->stream));
     for (int k = 0; k < pl.tab.n; ++k) pl.tab.it[k].pcm = pcm[pl.src[k]];
     return vad_run_batch(v, pl, probs_out, device_ms_out);
+}
+
+// ------------------------------------------------------------------ kernel-level test hooks (include/wlx.h wlx_vad_debug_*)
+// ONE launch each of the launch functions of the pass, on the object's stream under its mutex, with the object's repacked weights. The
+// output lives in a buffer of the call (not d_gx / d_hs / d_probs, which have no room for guard words): the caller's words go in, the
+// launch runs, all of them come back.
+namespace {
+struct VadHookBufs {       // device buffers of one hook call: the stream is waited for and they are freed on every return path
+    hipStream_t st;
+    std::vector<void*> pool;
+    explicit VadHookBufs(hipStream_t s) : st(s) {}
+    ~VadHookBufs() {
+        (void)hipStreamSynchronize(st);
+        for (void* p : pool) (void)hipFree(p);
+    }
+    int upload(float** d, const float* h, size_t n) {
+        CKR(dalloc(pool, d, n, false));
+        CK(hipMemcpyAsync(*d, h, n * sizeof(float), hipMemcpyHostToDevice, st));
+        return WLX_OK;
+    }
+    int finish(float* h, const float* d, size_t n) {
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(h, d, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        CK(hipStreamSynchronize(st));
+        return WLX_OK;
+    }
+};
+constexpr int64_t VAD_HOOK_MAX_WINDOWS = 1 << 19;      // 2^28 words of gx / hs
+}  // namespace
+
+extern "C" int32_t wlx_vad_debug_frontend(wlx_vad* v, const float* pcm, const int64_t* n_samples, const int32_t* extra_zero_windows, int32_t n,
+                                          float* gx, int64_t cap_windows) {
+    if (!v || !pcm || !n_samples || !gx) return set_error(WLX_ERR_ARG, "wlx_vad_debug_frontend: null argument");
+    if (cap_windows < 1 || cap_windows > VAD_HOOK_MAX_WINDOWS)
+        return set_error(WLX_ERR_ARG, "wlx_vad_debug_frontend: capacity %lld outside 1..2^19 windows", (long long)cap_windows);
+    VadPlan pl;
+    CKR(vad_plan("wlx_vad_debug_frontend", n_samples, extra_zero_windows, n, cap_windows, pl));
+    if (pl.windows == 0) return WLX_OK;
+    std::lock_guard<std::mutex> lk(v->mu);
+    CK(hipSetDevice(v->device));
+    (void)hipGetLastError();
+    CKR(vad_reserve(v, pl.samples));
+    if (pl.samples > 0) {
+        memcpy(v->h_pin, pcm, (size_t)pl.samples * sizeof(float));
+        CK(hipMemcpyAsync(v->d_pcm, v->h_pin, (size_t)pl.samples * sizeof(float), hipMemcpyHostToDevice, v->stream));
+    }
+    std::vector<long long> off(n + 1, 0);
+    for (int i = 0; i < n; ++i) off[i + 1] = off[i] + n_samples[i];
+    for (int k = 0; k < pl.tab.n; ++k) pl.tab.it[k].pcm = v->d_pcm + off[pl.src[k]];
+    VadHookBufs B(v->stream);
+    const size_t words = (size_t)cap_windows * 512 + WLX_DEBUG_GUARD;
+    float* d_gx = nullptr;
+    CKR(B.upload(&d_gx, gx, words));
+    vad_launch_frontend(pl, v->W, d_gx, v->stream);
+    return B.finish(gx, d_gx, words);
+}
+
+extern "C" int32_t wlx_vad_debug_lstm(wlx_vad* v, const float* gx, const int32_t* T, int32_t n, float* hs, int64_t cap_windows) {
+    if (!v || !gx || !T || !hs) return set_error(WLX_ERR_ARG, "wlx_vad_debug_lstm: null argument");
+    if (cap_windows < 1 || cap_windows > VAD_HOOK_MAX_WINDOWS)
+        return set_error(WLX_ERR_ARG, "wlx_vad_debug_lstm: capacity %lld outside 1..2^19 windows", (long long)cap_windows);
+    if (n < 1 || n > WLX_VAD_MAX_BATCH) return set_error(WLX_ERR_ARG, "wlx_vad_debug_lstm: %d items (1..%d)", n, WLX_VAD_MAX_BATCH);
+    int64_t samples[WLX_VAD_MAX_BATCH];                      // T windows are T * 512 samples to vad_plan, which builds the table as is
+    for (int i = 0; i < n; ++i) {
+        if (T[i] < 0) return set_error(WLX_ERR_ARG, "wlx_vad_debug_lstm: item %d has a negative window count", i);
+        samples[i] = (int64_t)T[i] * VAD_WINDOW;
+    }
+    VadPlan pl;
+    CKR(vad_plan("wlx_vad_debug_lstm", samples, nullptr, n, cap_windows, pl));
+    if (pl.windows == 0) return WLX_OK;
+    std::lock_guard<std::mutex> lk(v->mu);
+    CK(hipSetDevice(v->device));
+    (void)hipGetLastError();
+    VadHookBufs B(v->stream);
+    const size_t words = (size_t)cap_windows * 512 + WLX_DEBUG_GUARD;
+    float *d_gx = nullptr, *d_hs = nullptr;
+    CKR(B.upload(&d_gx, gx, (size_t)pl.windows * 512));
+    CKR(B.upload(&d_hs, hs, words));
+    vad_launch_lstm(pl, d_gx, v->W, d_hs, v->stream);
+    return B.finish(hs, d_hs, words);
+}
+
+extern "C" int32_t wlx_vad_debug_out(wlx_vad* v, const float* hs, int32_t T, float* probs, int64_t cap_windows) {
+    if (!v || !hs || !probs) return set_error(WLX_ERR_ARG, "wlx_vad_debug_out: null argument");
+    if (cap_windows < 1 || cap_windows > VAD_HOOK_MAX_WINDOWS)
+        return set_error(WLX_ERR_ARG, "wlx_vad_debug_out: capacity %lld outside 1..2^19 windows", (long long)cap_windows);
+    if (T < 0) return set_error(WLX_ERR_ARG, "wlx_vad_debug_out: negative window count");
+    if (T > cap_windows) return set_error(WLX_ERR_ARG, "wlx_vad_debug_out: %d windows do not fit the output buffer (%lld)", T, (long long)cap_windows);
+    if (T == 0) return WLX_OK;
+    std::lock_guard<std::mutex> lk(v->mu);
+    CK(hipSetDevice(v->device));
+    (void)hipGetLastError();
+    VadHookBufs B(v->stream);
+    const size_t words = (size_t)cap_windows + WLX_DEBUG_GUARD;
+    float *d_hs = nullptr, *d_probs = nullptr;
+    CKR(B.upload(&d_hs, hs, (size_t)T * 512));
+    CKR(B.upload(&d_probs, probs, words));
+    vad_launch_out(d_hs, v->W, d_probs, T, v->stream);
+    return B.finish(probs, d_probs, words);
 }
 
 // ------------------------------------------------------------------ host: hysteresis segmentation of the probabilities
