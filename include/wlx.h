@@ -860,6 +860,14 @@ int32_t wlx_mt_debug_topk(int32_t device, const float* logits, int32_t rows, int
  * sinpos[pos[r]] with sinpos float32 [n_pos][d]; x float32 [rows][d] */
 int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vocab, int32_t d, const int32_t* tok, const int32_t* pos,
                            int32_t rows, float scale, const float* sinpos, int32_t n_pos, float* x);
+/* KV-cache append of a decode step: qkv fp16 [rows][ldqkv] (q | k | v thirds of d columns, d and ldqkv multiples of 8, ldqkv >= 3 d);
+ * the k / v third of row r goes to slot t (0 <= t < tmax) of row r of Kc / Vc fp16 [cache_rows][tmax][d], rows <= cache_rows.
+ * Kc / Vc are copied in and out: every other element comes back unchanged. */
+int32_t wlx_mt_debug_kv_append(int32_t device, const uint16_t* qkv, int64_t ldqkv, int32_t rows, int32_t d, uint16_t* Kc, uint16_t* Vc,
+                               int32_t cache_rows, int32_t tmax, int32_t t);
+/* The in-place ReLU of the MLP: y fp16 [M][ld], columns 0 .. N of every row (N and ld multiples of 8, ld >= N); y is copied in and
+ * out, the columns N .. ld come back unchanged. */
+int32_t wlx_mt_debug_relu(int32_t device, uint16_t* y, int64_t ld, int32_t M, int32_t N);
 
 /* speaker engine: device times (HIP events) of the last wlx_spk_embed, wlx_spk_embed_batch, wlx_spk_embed_pcm_batch or
  * wlx_spk_embed_ring_batch that launched: filterbank, then network + pooling + head */
@@ -881,12 +889,24 @@ int32_t wlx_spk_debug_pool(int32_t device, const uint16_t* x, int32_t F, int32_t
  * [H][widths[i]][Cin] image in `in` and its own [OH][(widths[i] - 1) / stride + 1][Cout] image in `resid` / `out`; the rest as
  * wlx_spk_debug_conv, Cin = 1 included. Pooling: item i is [F][frames[i]][C] (frames[i] >= 2), out float32 [n][2][C][F].
  * wlx_spk_debug_conv and _pool go through the same launchers with n = 1 (for Cin >= 32 the launcher then picks a kernel without the
- * item table around the same tile code, as it does for wlx_spk_embed); the filterbank has no ragged hook. */
+ * item table around the same tile code, as it does for wlx_spk_embed). */
 int32_t wlx_spk_debug_conv_batch(int32_t device, const uint16_t* in, int32_t H, int32_t n, const int32_t* widths, int32_t Cin,
                                  const float* w, const float* bias, const uint16_t* resid, int32_t Cout, int32_t stride, int32_t ksize,
                                  int32_t relu, uint16_t* out);
 int32_t wlx_spk_debug_pool_batch(int32_t device, const uint16_t* x, int32_t F, int32_t n, const int32_t* frames, int32_t C, float eps,
                                  float* out);
+/* The ragged filterbank and mean removal, one launch each over 1 <= n <= WLX_SPK_MAX_BATCH windows of ONE buffer of n_samples samples:
+ * item i is the frames[i] >= 1 frames from sample offsets[i] >= 0 on (any offset; windows may overlap and come in any order; the last
+ * frame ends inside the buffer: offsets[i] + 400 + 160 (frames[i] - 1) <= n_samples). Outputs packed back to back in item order, as the
+ * engine packs them: frames_out float32 [sum T][n_mels], image_out fp16 item by item [n_mels][frames[i]]. Every item has the bits of
+ * wlx_spk_debug_fbank on its samples alone. */
+int32_t wlx_spk_debug_fbank_batch(int32_t device, const float* pcm, int64_t n_samples, int32_t n, const int64_t* offsets,
+                                  const int32_t* frames, int32_t n_mels, float* frames_out, uint16_t* image_out);
+/* The embedding head: pooled float32 [n][D], W float32 [E][D] (rounded to fp16 by the hook as the engine does), b float32 [E] ->
+ * emb float32 [n][E] = W pooled + b (normalize = 0) or that divided by its norm, an all-zero row staying zero (normalize = 1).
+ * D a multiple of 8 (the kernel's 8-wide loads), D and E up to 2^16, n up to 65535. */
+int32_t wlx_spk_debug_head(int32_t device, const float* pooled, const float* W, const float* b, int32_t n, int32_t D, int32_t E,
+                           int32_t normalize, float* emb);
 /* The clustering kernels, one launch each. Affinity: X float32 [n][dim] (1 <= n <= WLX_SPK_CLUSTER_MAX, 1 <= dim <= 1024) ->
  * dist_out [n][n] = 1 - X X^T, exactly symmetric, diagonal exactly 0. */
 int32_t wlx_spk_debug_affinity(int32_t device, const float* X, int32_t n, int32_t dim, float* dist_out);

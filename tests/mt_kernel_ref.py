@@ -305,7 +305,117 @@ def embed_case(vocab, d, scale_embedding, max_positions=1024, pad=1, seed=0):
     return E, tok, pos, scale, sinpos
 
 
-# ------------------------------------------------------------------ the C-ABI hooks (wlx_mt_debug_attn / _topk / _embed)
+# ------------------------------------------------------------------ the row kernels: KV-cache append and ReLU (bit-level, no tolerance)
+# (d, rows, tmax, t, wide): d = 64 leaves 248 of the 256 threads idle, 1024 is half a trip, 2048 one trip exactly full, 2056 a second
+# trip of one thread; one row and ten; a cache of one slot, of five and of the product's 448 with the first, a middle and the last
+# slot; the fused buffer at its product stride 3 d and 8 halfs wider
+KV_CASES = tuple((d, rows, tmax, t, wide) for d in (64, 1024, 2048, 2056) for rows in (1, 10)
+                 for tmax, ts in ((1, (0,)), (5, (0, 2, 4)), (448, (0, 200, 447))) for t in ts for wide in (False, True))
+
+
+def _finite_f16_bits(rng, shape):
+    """seeded fp16 bit patterns of both signs without inf / NaN (exponent field below 31)"""
+    return (rng.integers(0, 0x7c00, size=shape, dtype=np.uint16) | (rng.integers(0, 2, size=shape, dtype=np.uint16) << 15)).astype(np.uint16)
+
+
+def kv_case(d, rows, tmax, t, wide, seed=0):
+    """qkv fp16 [rows][ldqkv]: the K and V thirds seeded normal data with a scale per row and per third, the Q third and the padding
+    columns +-1000; Kc / Vc [rows + 1][tmax][d] preset with seeded bit patterns (one spare cache row behind the last appended one)"""
+    rng = np.random.default_rng(seed + d + 17 * rows + 31 * tmax + 7 * t + int(wide))
+    ld = 3 * d + (8 if wide else 0)
+    qkv = rng.choice([-1000.0, 1000.0], size=(rows, ld))
+    scale = np.geomspace(0.5, 4.0, rows)[:, None]
+    qkv[:, d:2 * d] = rng.standard_normal((rows, d)) * scale
+    qkv[:, 2 * d:3 * d] = rng.standard_normal((rows, d)) * scale * 3.0
+    cache_rows = rows + 1
+    return dict(qkv=_f16(qkv).view(np.uint16), ldqkv=ld, rows=rows, d=d, cache_rows=cache_rows, tmax=tmax, t=t,
+                kc=_finite_f16_bits(rng, (cache_rows, tmax, d)), vc=_finite_f16_bits(rng, (cache_rows, tmax, d)))
+
+
+def kv_append_ref(c, swap=False, dt=0, dr=0, ld=None):
+    """(Kc, Vc) uint16 after the append: slot t of cache row r = the K / V third of qkv row r for r < rows, everything else as preset.
+    The wrong answers: K and V swapped, slot t + dt, cache row r + dr, the source rows taken at stride `ld` from the flat buffer."""
+    d, rows, t = c["d"], c["rows"], c["t"] + dt
+    kc, vc = c["kc"].copy(), c["vc"].copy()
+    flat = c["qkv"].reshape(-1)
+    ld = c["ldqkv"] if ld is None else ld
+    for r in range(rows):
+        k, v = flat[r * ld + d:r * ld + 2 * d], flat[r * ld + 2 * d:r * ld + 3 * d]
+        kc[r + dr, t], vc[r + dr, t] = (v, k) if swap else (k, v)
+    return kc, vc
+
+
+def kv_wrong_answers(c):
+    """{name: (Kc, Vc)} of every wrong answer that exists for the case (no slot t - 1 at t = 0, no narrower stride at ldqkv = 3 d,
+    and at one row the stride does not matter)"""
+    w = {"swap": kv_append_ref(c, swap=True), "row+1": kv_append_ref(c, dr=1)}
+    if c["t"] > 0:
+        w["t-1"] = kv_append_ref(c, dt=-1)
+    if c["t"] + 1 < c["tmax"]:
+        w["t+1"] = kv_append_ref(c, dt=1)
+    if c["ldqkv"] > 3 * c["d"] and c["rows"] > 1:
+        w["ld=3d"] = kv_append_ref(c, ld=3 * c["d"])
+    return w
+
+
+RELU_CASES = ((1, 8, 8), (3, 64, 64), (5, 4096, 4096), (7, 72, 136), (33, 248, 256))      # M N / 8 = 1, 24, 2560, 63, 1023 vectors
+# -0.0 first (must come back as +0.0), +-inf, the smallest and the largest subnormal and normal of both signs, +0.0
+RELU_SPECIALS = np.array([0x8000, 0x7c00, 0xfc00, 0x0001, 0x8001, 0x03ff, 0x83ff, 0x0400, 0x8400, 0x7bff, 0xfbff, 0x0000], np.uint16)
+
+
+def relu_case(M, N, ld, seed=0):
+    """y uint16 [M][ld]: seeded normal values of both signs in every column, the padding columns N .. ld included (garbage there is
+    negative half of the time: a ReLU over them would show); RELU_SPECIALS at the start of row 0 and ending on the last live column of
+    the last row (N = 8 holds the first eight: -0.0, the infinities, the subnormals, the smallest positive normal). No NaN: the
+    kernel's `v > 0 ? v : 0` maps NaN to 0 where torch.relu keeps it, and no product input is NaN (the FFN's GEMM output is finite)."""
+    rng = np.random.default_rng(seed + M + N + ld)
+    y = _f16(rng.standard_normal((M, ld)) * 3.0).view(np.uint16).copy()
+    k = min(N, len(RELU_SPECIALS))
+    y[M - 1, N - k:N] = RELU_SPECIALS[:k][::-1]
+    y[0, :k] = RELU_SPECIALS[:k]
+    return y
+
+
+def relu_ref(y, N, keep_negative_zero=False):
+    """bit-level ReLU of columns 0 .. N: a set sign bit gives +0.0 (0x0000), everything else (NaN is not among the inputs) is kept"""
+    out = y.copy()
+    live = out[:, :N]
+    neg = (live & 0x8000) != 0
+    if keep_negative_zero:
+        neg &= live != 0x8000
+    live[neg] = 0
+    return out
+
+
+# ------------------------------------------------------------------ the C-ABI hooks (wlx_mt_debug_attn / _topk / _embed / _kv_append / _relu)
+def run_kv_append(c, device=0, **over):
+    """-> (rc, Kc, Vc) uint16 of one launch_mt_kv_append through wlx_mt_debug_kv_append; `over` replaces scalar arguments (refusals)"""
+    import ctypes as C
+
+    from whisperlive_amd import _lib
+    lib = _lib.load()
+    a = dict(c)
+    a.update(over)
+    qkv = None if a["qkv"] is None else np.ascontiguousarray(a["qkv"])
+    kc = None if a["kc"] is None else np.ascontiguousarray(a["kc"]).copy()
+    vc = None if a["vc"] is None else np.ascontiguousarray(a["vc"]).copy()
+    rc = lib.wlx_mt_debug_kv_append(device, _ptr(qkv, C.c_uint16), a["ldqkv"], a["rows"], a["d"], _ptr(kc, C.c_uint16), _ptr(vc, C.c_uint16),
+                                    a["cache_rows"], a["tmax"], a["t"])
+    return rc, kc, vc
+
+
+def run_relu(y, N, ld=None, M=None, device=0):
+    """-> (rc, y uint16 [M][ld]) of one launch_mt_relu_f16 through wlx_mt_debug_relu"""
+    import ctypes as C
+
+    from whisperlive_amd import _lib
+    lib = _lib.load()
+    out = None if y is None else np.ascontiguousarray(y).copy()
+    rc = lib.wlx_mt_debug_relu(device, _ptr(out, C.c_uint16), (out.shape[1] if ld is None else ld), (out.shape[0] if M is None else M), N)
+    return rc, out
+
+
+
 def _ptr(a, t):
     import ctypes as C
     return None if a is None else a.ctypes.data_as(C.POINTER(t))

@@ -156,6 +156,45 @@ def test_guard_embed_case(vocab, d, scaled):
         assert (np.abs(wrong - ref) > bound).any(axis=1).sum() >= len(tok) - 2
 
 
+@pytest.mark.parametrize("d,rows,tmax,t,wide", R.KV_CASES)
+def test_guard_kv_case(d, rows, tmax, t, wide):
+    """K and V swapped, slot t +- 1, cache row r + 1 and (where the buffer is wider and has more than one row) the source read at
+    stride 3 d all differ in bits from the reference test_kv_append compares with; the reference itself writes the K / V thirds to
+    slot t of rows 0 .. rows and leaves every other element as preset"""
+    c = R.kv_case(d, rows, tmax, t, wide)
+    kc, vc = R.kv_append_ref(c)
+    q = c["qkv"].reshape(rows, c["ldqkv"])
+    assert np.array_equal(kc[:rows, t], q[:, d:2 * d]) and np.array_equal(vc[:rows, t], q[:, 2 * d:3 * d])
+    untouched = np.ones(kc.shape, bool)
+    untouched[:rows, t] = False
+    assert np.array_equal(kc[untouched], c["kc"][untouched]) and np.array_equal(vc[untouched], c["vc"][untouched])
+    assert not np.array_equal(kc[:rows, t], c["kc"][:rows, t])                  # the preset differs from what is appended
+    wrongs = R.kv_wrong_answers(c)
+    assert {"swap", "row+1"} <= set(wrongs) and (tmax == 1 or {"t-1", "t+1"} & set(wrongs)) and (("ld=3d" in wrongs) == (wide and rows > 1))
+    for name, (wk, wv) in wrongs.items():
+        assert not np.array_equal(wk, kc) and not np.array_equal(wv, vc), name
+    assert np.abs(q[:, :d].view(np.float16).astype(np.float32)).min() == 1000.0     # the Q third is garbage
+
+
+@pytest.mark.parametrize("M,N,ld", R.RELU_CASES)
+def test_guard_relu_case(M, N, ld):
+    """the reference agrees with torch.relu on the live columns (no NaN among the inputs) except that it returns +0.0 for -0.0 as
+    the kernel's compare does; a ReLU that keeps -0.0, one over all ld columns and one that skips the last 8-wide vector of a row
+    differ in bits from it"""
+    y = R.relu_case(M, N, ld)
+    f = y.view(np.float16)
+    assert not np.isnan(f.astype(np.float32)).any() and 0x8000 in y[:, :N] and 0x7c00 in y[:, :N] and 0xfc00 in y[:, :N]
+    assert (y[0, :8] == R.RELU_SPECIALS[:8]).all() and (y[M - 1, N - 1] == 0x8000 or (M, N) == (1, 8))     # (one vector in all: the first eight)
+    ref = R.relu_ref(y, N)
+    want = torch.relu(torch.from_numpy(f[:, :N].astype(np.float32))).numpy().astype(np.float16).view(np.uint16)
+    want[want == 0x8000] = 0                                                    # (torch keeps the sign of -0.0)
+    assert np.array_equal(ref[:, :N], want) and np.array_equal(ref[:, N:], y[:, N:])
+    assert not np.array_equal(R.relu_ref(y, N, keep_negative_zero=True), ref)
+    assert not np.array_equal(R.relu_ref(y, N - 8), ref) if N > 8 else ref[0, 0] == 0
+    if ld > N:
+        assert (y[:, N:] & 0x8000).any() and not np.array_equal(R.relu_ref(y, ld), ref)
+
+
 # ------------------------------------------------------------------ shape checks of the hooks (host side, no device touched)
 @pytest.fixture(scope="module")
 def lib():

@@ -30,9 +30,9 @@ EXPORTS = [
     "wlx_spk_cluster", "wlx_spk_diarize_pcm", "wlx_spk_diarize_many",
     "wlx_debug_logits_get", "wlx_debug_decode_logits", "wlx_debug_search", "wlx_debug_search_batch", "wlx_debug_time_decode_step", "wlx_debug_profile_step", "wlx_debug_trace_step",
     "wlx_mt_debug_encode", "wlx_mt_debug_decode_logits", "wlx_mt_debug_timings", "wlx_mt_debug_attn", "wlx_mt_debug_topk",
-    "wlx_mt_debug_embed", "wlx_mt_debug_search",
+    "wlx_mt_debug_embed", "wlx_mt_debug_search", "wlx_mt_debug_kv_append", "wlx_mt_debug_relu",
     "wlx_spk_debug_timings", "wlx_spk_debug_fbank", "wlx_spk_debug_conv", "wlx_spk_debug_pool",
-    "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch",
+    "wlx_spk_debug_conv_batch", "wlx_spk_debug_pool_batch", "wlx_spk_debug_fbank_batch", "wlx_spk_debug_head",
     "wlx_spk_debug_affinity", "wlx_spk_debug_ahc", "wlx_spk_debug_affinity_many", "wlx_spk_debug_ahc_many",
     "wlx_spk_debug_cluster_timings",
     "wlx_debug_layernorm", "wlx_debug_attn_encoder", "wlx_debug_dec_cross_attn", "wlx_debug_dec_self_attn", "wlx_debug_gemm",
@@ -436,6 +436,10 @@ def load() -> C.CDLL:
     lib.wlx_spk_debug_pool.argtypes = [i32, u16p, i32, i32, i32, C.c_float, f32p]
     lib.wlx_spk_debug_conv_batch.argtypes = [i32, u16p, i32, i32, i32p, i32, f32p, f32p, u16p, i32, i32, i32, i32, u16p]
     lib.wlx_spk_debug_pool_batch.argtypes = [i32, u16p, i32, i32, i32p, i32, C.c_float, f32p]
+    lib.wlx_spk_debug_fbank_batch.argtypes = [i32, f32p, i64, i32, i64p, i32p, i32, f32p, u16p]
+    lib.wlx_spk_debug_head.argtypes = [i32, f32p, f32p, f32p, i32, i32, i32, i32, f32p]
+    lib.wlx_mt_debug_kv_append.argtypes = [i32, u16p, i64, i32, i32, u16p, u16p, i32, i32, i32]
+    lib.wlx_mt_debug_relu.argtypes = [i32, u16p, i64, i32, i32]
     lib.wlx_debug_layernorm.argtypes = [i32, f32p, i64, f32p, f32p, i32, i32, u16p, f32p, i64]
     lib.wlx_debug_attn_encoder.argtypes = [i32, u16p, i64, i64, u16p, i64, i64, u16p, i64, i64, u16p, i64, i64, i32, i32, i32]
     lib.wlx_debug_dec_cross_attn.argtypes = [i32, u16p, i64, u16p, u16p, i64, i32, i32, i32, i32, i32, i32p, u16p, f32p, u16p, i64,

@@ -1075,3 +1075,39 @@ extern "C" int32_t wlx_mt_debug_embed(int32_t device, const float* E, int32_t vo
     CKR(S.download(x, dx, (size_t)rows * d));
     return S.finish();
 }
+
+// the decoder self-attention cache append of one step: rows r < `rows` of the fused qkv buffer into slot t of cache row r
+extern "C" int32_t wlx_mt_debug_kv_append(int32_t device, const uint16_t* qkv, int64_t ldqkv, int32_t rows, int32_t d, uint16_t* Kc,
+                                          uint16_t* Vc, int32_t cache_rows, int32_t tmax, int32_t t) {
+    if (!qkv || !Kc || !Vc) return set_error(WLX_ERR_ARG, "null argument");
+    if (d < 8 || d % 8 || d > (1 << 16) || ldqkv < 3 * (int64_t)d || ldqkv % 8 || ldqkv > (1 << 20))
+        return set_error(WLX_ERR_ARG, "d %d / ldqkv %lld: d a multiple of 8 up to 2^16, ldqkv a multiple of 8 in 3 d .. 2^20", d, (long long)ldqkv);
+    if (rows < 1 || rows > cache_rows || cache_rows > 65535 || tmax < 1 || t < 0 || t >= tmax || (int64_t)cache_rows * tmax * d > (1LL << 28))
+        return set_error(WLX_ERR_ARG, "rows %d / cache_rows %d / tmax %d / t %d: 1 <= rows <= cache_rows <= 65535, 0 <= t < tmax, the cache up to 2^28 halfs",
+                         rows, cache_rows, tmax, t);
+    const size_t n_cache = (size_t)cache_rows * tmax * d;
+    HookScope S;
+    CKR(S.begin(device));
+    half_t *dq, *dK, *dV;
+    CKR(S.upload(&dq, h16(qkv), (size_t)rows * ldqkv));
+    CKR(S.upload(&dK, h16(Kc), n_cache));
+    CKR(S.upload(&dV, h16(Vc), n_cache));
+    launch_mt_kv_append(dq, (long)ldqkv, rows, d, dK, dV, tmax, t, S.st);
+    CKR(S.download(h16(Kc), dK, n_cache));
+    CKR(S.download(h16(Vc), dV, n_cache));
+    return S.finish();
+}
+
+// the in-place ReLU of the MLP on columns 0 .. N of M rows of stride ld
+extern "C" int32_t wlx_mt_debug_relu(int32_t device, uint16_t* y, int64_t ld, int32_t M, int32_t N) {
+    if (!y) return set_error(WLX_ERR_ARG, "null argument");
+    if (M < 1 || N < 8 || N % 8 || ld < N || ld % 8 || (int64_t)M * ld > (1LL << 28))
+        return set_error(WLX_ERR_ARG, "M %d / N %d / ld %lld: M >= 1, N and ld multiples of 8, ld >= N, M ld up to 2^28", M, N, (long long)ld);
+    HookScope S;
+    CKR(S.begin(device));
+    half_t* dy;
+    CKR(S.upload(&dy, h16(y), (size_t)M * ld));
+    launch_mt_relu_f16(dy, (long)ld, M, N, S.st);
+    CKR(S.download(h16(y), dy, (size_t)M * ld));
+    return S.finish();
+}

@@ -48,8 +48,10 @@ inline size_t spk_packed_halfs(int Cout, int Cin, int ks) { return (size_t)(Cout
 // Statistics pooling of x, item i = [F][frames[i]][C], over its frames (frames[i] >= 2): out [n][2][C][F],
 // out[i][c * F + f] = mean, out[i][C * F + c * F + f] = sqrt(var_unbiased + eps). C a multiple of 64.
 bool launch_spk_pool_batch(const half_t* x, int F, const int* frames, int n, int C, float eps, float* out, hipStream_t s);
-// pooled [n][D] -> emb [n][E]: emb = W pooled + b (W fp16 [E][D] row-major, D a multiple of 8), then emb /= |emb|. E <= 1024.
-void launch_spk_head_batch(const float* pooled, const half_t* W, const float* b, int E, int D, int n, float* emb, hipStream_t s);
+// pooled [n][D] -> emb [n][E]: emb = W pooled + b (W fp16 [E][D] row-major, D a multiple of 8), then emb /= |emb| (an all-zero row
+// stays zero) unless `normalize` is false. False, before any launch: a null pointer, n < 1, E < 1, D < 8 or D % 8.
+bool launch_spk_head_batch(const float* pooled, const half_t* W, const float* b, int E, int D, int n, float* emb, hipStream_t s,
+                           bool normalize = true);
 
 // ---- offline clustering (spk_cluster.hip): n in 1..WLX_SPK_CLUSTER_MAX unit rows of D <= 1024 floats, everything float32.
 // False = nothing launched (a null pointer, n or D out of range, a threshold that is NaN or outside [0, 2], max_clusters < 0).

@@ -434,8 +434,10 @@ __device__ __forceinline__ void spk_l2norm_body(float* __restrict__ y, int E) {
     const float ws = wave_sum(acc);
     if ((tid & 63) == 0) part[tid >> 6] = ws;
     __syncthreads();
-    // an all-zero head output stays zero instead of turning into NaN
-    const float inv = 1.f / sqrtf(fmaxf(((part[0] + part[1]) + part[2]) + part[3], 1e-30f));
+    // an all-zero head output stays zero instead of turning into NaN; every other row comes back with unit norm, however small it
+    // was (a floor under the sum of squares would leave a row of norm < 1e-15 short of 1)
+    const float ss = ((part[0] + part[1]) + part[2]) + part[3];
+    const float inv = ss > 0.f ? 1.f / sqrtf(ss) : 0.f;
     for (int i = tid; i < E; i += 256) y[i] *= inv;
 }
 
@@ -446,9 +448,13 @@ __global__ __launch_bounds__(64) void spk_linear_batch_kernel(const float* __res
 
 __global__ __launch_bounds__(256) void spk_l2norm_batch_kernel(float* __restrict__ y, int E) { spk_l2norm_body(y + (long)blockIdx.x * E, E); }
 
-void launch_spk_head_batch(const float* pooled, const half_t* W, const float* b, int E, int D, int n, float* emb, hipStream_t s) {
+// false, before any launch: a null pointer, n < 1, E < 1, or a D the 8-wide loads of spk_linear_body cannot serve (D < 8, D % 8: the last
+// load of a row would run past it). `normalize` false stops behind the linear layer (the one-launch hook of the head).
+bool launch_spk_head_batch(const float* pooled, const half_t* W, const float* b, int E, int D, int n, float* emb, hipStream_t s, bool normalize) {
+    if (!pooled || !W || !b || !emb || n < 1 || E < 1 || D < 8 || D % 8) return false;
     hipLaunchKernelGGL(spk_linear_batch_kernel, dim3((unsigned)E, (unsigned)n), dim3(64), 0, s, pooled, W, b, D, E, emb);
-    hipLaunchKernelGGL(spk_l2norm_batch_kernel, dim3((unsigned)n), dim3(256), 0, s, emb, E);
+    if (normalize) hipLaunchKernelGGL(spk_l2norm_batch_kernel, dim3((unsigned)n), dim3(256), 0, s, emb, E);
+    return true;
 }
 
 }  // namespace wlx

@@ -318,7 +318,8 @@ static int spk_enqueue_batch(wlx_spk* k, const float* src, const SpkPlan& pl, fl
     }
     if (!launch_spk_pool_batch(x, H, widths, m, sp.planes << 3, sp.pool_eps, k->pooled, st))
         return set_error(WLX_ERR_ARG, "pooling refused a batch of %d", m);
-    launch_spk_head_batch(k->pooled, k->head_W, k->head_b, sp.embed_dim, k->pool_dim, m, emb, st);
+    if (!launch_spk_head_batch(k->pooled, k->head_W, k->head_b, sp.embed_dim, k->pool_dim, m, emb, st))
+        return set_error(WLX_ERR_ARG, "head refused a batch of %d at %d -> %d", m, k->pool_dim, sp.embed_dim);
     CK(hipEventRecord(k->ev[2], st));
     CK(hipGetLastError());
     return WLX_OK;
@@ -870,6 +871,64 @@ extern "C" int32_t wlx_spk_debug_pool_batch(int32_t device, const uint16_t* x, i
     }
     if (Tsum > (1 << 20)) return set_error(WLX_ERR_ARG, "%ld frames in all exceed 2^20", Tsum);
     return spk_debug_pool_run(device, x, F, n, frames, Tsum, C, eps, out);
+}
+
+// The ragged filterbank and mean removal over n windows of ONE upload, as spk_enqueue_batch launches them: item i is the frames[i] frames
+// from sample offsets[i] on (any offset: windows may overlap and come in any order), outputs packed back to back in item order.
+extern "C" int32_t wlx_spk_debug_fbank_batch(int32_t device, const float* pcm, int64_t n_samples, int32_t n, const int64_t* offsets,
+                                             const int32_t* frames, int32_t n_mels, float* frames_out, uint16_t* image_out) {
+    if (!pcm || !offsets || !frames || !frames_out || !image_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_MAX_BATCH) return set_error(WLX_ERR_ARG, "%d items outside 1..%d", n, WLX_SPK_MAX_BATCH);
+    if (n_mels < 1 || n_mels > 256) return set_error(WLX_ERR_ARG, "n_mels %d outside 1..256", n_mels);
+    if (n_samples < WLX_SPK_FRAME || n_samples > (1LL << 28)) return set_error(WLX_ERR_ARG, "n_samples %lld outside 400..2^28", (long long)n_samples);
+    long offs[WLX_SPK_MAX_BATCH];
+    long Tsum = 0;
+    for (int i = 0; i < n; ++i) {
+        if (frames[i] < 1 || frames[i] > (1 << 20)) return set_error(WLX_ERR_ARG, "frames[%d] = %d outside 1..2^20", i, frames[i]);
+        if (offsets[i] < 0 || offsets[i] > n_samples - WLX_SPK_FRAME - (int64_t)(frames[i] - 1) * WLX_SPK_SHIFT)
+            return set_error(WLX_ERR_ARG, "item %d: %d frames from sample %lld on leave the %lld samples", i, frames[i], (long long)offsets[i],
+                             (long long)n_samples);
+        offs[i] = (long)offsets[i];
+        Tsum += frames[i];
+    }
+    if (Tsum > (1 << 20)) return set_error(WLX_ERR_ARG, "%ld frames in all exceed 2^20", Tsum);
+    HookScope S;
+    CKR(S.begin(device));
+    float *window, *twiddle, *mel, *dpcm, *dlm;
+    half_t* d16;
+    CKR(upload_tables(S.allocs, n_mels, &window, &twiddle, &mel));
+    CKR(S.upload(&dpcm, pcm, (size_t)n_samples));
+    CKR(S.alloc(&dlm, (size_t)Tsum * n_mels));
+    CKR(S.alloc(&d16, (size_t)Tsum * n_mels));
+    if (!launch_spk_fbank_batch(dpcm, offs, frames, n, window, twiddle, mel, n_mels, dlm, S.st) ||
+        !launch_spk_cmn_batch(dlm, frames, n, n_mels, d16, S.st))
+        return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CKR(S.download(frames_out, dlm, (size_t)Tsum * n_mels));
+    CKR(S.download(h16(image_out), d16, (size_t)Tsum * n_mels));
+    return S.finish();
+}
+
+// The embedding head: W rounded to fp16 as spk_load rounds seg_1.weight, the linear layer alone (normalize = 0) or with the l2norm
+// behind it (normalize = 1); rows of `emb` past n are not touched.
+extern "C" int32_t wlx_spk_debug_head(int32_t device, const float* pooled, const float* W, const float* b, int32_t n, int32_t D, int32_t E,
+                                      int32_t normalize, float* emb) {
+    if (!pooled || !W || !b || !emb) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > 65535 || D < 8 || D % 8 || D > (1 << 16) || E < 1 || E > (1 << 16) || (long)E * D > (1L << 26))
+        return set_error(WLX_ERR_ARG, "n %d / D %d / E %d: n in 1..65535, D a multiple of 8 and E >= 1, both up to 2^16, E D up to 2^26", n, D, E);
+    if (normalize != 0 && normalize != 1) return set_error(WLX_ERR_ARG, "normalize %d must be 0 or 1", normalize);
+    std::vector<half_t> w16((size_t)E * D);          // (declared before S: it outlives the stream's copy on every return path)
+    for (size_t i = 0; i < w16.size(); ++i) w16[i] = (half_t)W[i];
+    HookScope S;
+    CKR(S.begin(device));
+    float *dx, *db, *demb;
+    half_t* dW;
+    CKR(S.upload(&dx, pooled, (size_t)n * D));
+    CKR(S.upload(&dW, w16.data(), w16.size()));
+    CKR(S.upload(&db, b, (size_t)E));
+    CKR(S.alloc(&demb, (size_t)n * E));
+    if (!launch_spk_head_batch(dx, dW, db, E, D, n, demb, S.st, normalize != 0)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    CKR(S.download(emb, demb, (size_t)n * E));
+    return S.finish();
 }
 
 // ---- the clustering kernels (spk_cluster.hip), one launch each
