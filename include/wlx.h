@@ -744,13 +744,17 @@ typedef struct {
 /* host embeddings emb [n][dim] (unit rows, dim = the engine's embed_dim, 1 <= n <= WLX_SPK_CLUSTER_MAX) -> labels [n], *n_clusters = K,
  * and, when `centroids` is not null, its first K rows [dim]: the normalised mean of each cluster's members (the buffer holds up to n
  * rows; rows from K on are not written). n = 1: label 0, nothing launched. One upload, one wait. WLX_ERR_ARG, before any launch and
- * with nothing written: a null pointer, n or dim out of range, a threshold that is NaN or outside [0, 2], max_clusters < 0. */
+ * with nothing written: a null pointer, n or dim out of range, a threshold that is NaN or outside [0, 2], max_clusters < 0.
+ * The first call of an engine that clusters (this one, wlx_spk_diarize_pcm or wlx_spk_diarize_many) makes the buffers all three share,
+ * sized for a wave: WLX_SPK_MANY_MAX_CELLS floats of matrices and tables of WLX_SPK_MANY_MAX_ROWS rows (64 MiB + 16 MiB of HBM and
+ * 16 MiB pinned at embed_dim 256). An engine that only embeds never pays for them. */
 int32_t wlx_spk_cluster(wlx_spk* spk, const float* emb, int32_t n, int32_t dim, const wlx_spk_cluster_opts* opts,
                         int32_t* labels, float* centroids, int32_t* n_clusters);
 /* A whole file: windows [starts[i], starts[i] + n_samples[i]) of the resident PCM of a slot item, 1 <= n <= WLX_SPK_CLUSTER_MAX. ALL of
- * them are embedded — n may exceed WLX_SPK_MAX_BATCH and their sum max_seconds: the call groups them itself, greedily in order, by
- * the rule of one wlx_spk_embed_pcm_batch call per group (at most WLX_SPK_MAX_BATCH windows and max_seconds of samples), and enqueues
- * the ragged passes back to back, each writing its rows into one device table — then clustered as above, with ONE wait at the end.
+ * them are embedded — n may exceed WLX_SPK_MAX_BATCH and their sum max_seconds: the call groups the windows that take part itself,
+ * greedily in order, into ragged passes of at most WLX_SPK_MAX_BATCH windows and max_seconds of samples (a window under 4800 samples
+ * counts toward neither), and enqueues the passes back to back, each writing its rows into one device table — then clustered as above,
+ * with ONE wait at the end. It is wlx_spk_diarize_many of one file behind refusals of its own, plus dist_out.
  * A window under 4800 samples: status[i] = WLX_ERR_TOO_SHORT, labels[i] = -1, a zero row of emb_out; it takes no part. The m others
  * get status WLX_OK and their cluster in labels. Nullable outputs: emb_out [n][embed_dim], row i with the bits wlx_spk_embed_pcm_batch
  * gives for that range; dist_out [m][m], the matrix the device clustered, over the windows that took part in their order;
@@ -775,7 +779,7 @@ int32_t wlx_spk_diarize_pcm(wlx_spk* spk, wlx_engine* e, int32_t slot, int32_t i
  * and centroids may be null), n_files out of range, a file with a negative count or more than WLX_SPK_CLUSTER_MAX windows, more than
  * WLX_SPK_MANY_MAX_ROWS windows in all, matrices (the sum of m_f^2 over the windows that take part) over WLX_SPK_MANY_MAX_CELLS
  * floats, options as above, a negative start or count, a window over max_seconds, different devices, an item outside the slot or named
- * twice. The buffers are made by the first call: an engine that never calls this pays nothing for them. */
+ * twice. One file is the same path: wlx_spk_diarize_pcm and wlx_spk_cluster run it on a wave of one, in the same buffers. */
 #define WLX_SPK_MANY_MAX_FILES 64
 #define WLX_SPK_MANY_MAX_ROWS  8192          /* windows of all files together */
 #define WLX_SPK_MANY_MAX_CELLS (4u * WLX_SPK_CLUSTER_MAX * WLX_SPK_CLUSTER_MAX)   /* floats of all distance matrices together */
@@ -918,7 +922,8 @@ int32_t wlx_spk_debug_ahc(int32_t device, const float* dist, int32_t n, const wl
  * rows (1..WLX_SPK_CLUSTER_MAX; all together at most WLX_SPK_MANY_MAX_ROWS, their matrices at most WLX_SPK_MANY_MAX_CELLS floats) at
  * row0_f = ns[0] + .. + ns[f-1] of X / labels / heights, its matrix [ns[f]][ns[f]] at ns[0]^2 + .. + ns[f-1]^2 of dist, its merges at
  * 2 * row0_f of merges (room for ns[f] pairs, ns[f] - 1 at the most written). opts, n_merges, n_clusters: one entry per file. Every
- * file's results have the bits of wlx_spk_debug_affinity / wlx_spk_debug_ahc on that file alone. */
+ * file's results have the bits of wlx_spk_debug_affinity / wlx_spk_debug_ahc on that file alone: those two are these launches over
+ * one file. */
 int32_t wlx_spk_debug_affinity_many(int32_t device, const float* X, int32_t n_files, const int32_t* ns, int32_t dim, float* dist_out);
 int32_t wlx_spk_debug_ahc_many(int32_t device, const float* dist, int32_t n_files, const int32_t* ns, const wlx_spk_cluster_opts* opts,
                                int32_t* labels, int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters);

@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the many-forms of the clustering kernels (whisperlive_amd/csrc/spk_cluster.hip), one launch each through the
+"""GPU tests (-m gpu) of the clustering kernels (whisperlive_amd/csrc/spk_cluster.hip) over tables of several files, one launch each through the
 hooks wlx_spk_debug_affinity_many and wlx_spk_debug_ahc_many: files of different sizes packed into one call, every file's matrix
 bit-equal to wlx_spk_debug_affinity on that file alone, and every file's merges, heights (bit for bit), labels and counts equal to
 file_diarization.cluster_host on its matrix and to wlx_spk_debug_ahc — under a threshold and a max_clusters of its own. Rows are unit

@@ -151,6 +151,23 @@ def test_rows_labels_and_centroids(spk, slot, rows):
     assert slot.pcm_count() == N and np.array_equal(before.view(np.uint32), after.view(np.uint32))
 
 
+def test_dist_out_is_the_matrix_before_the_clustering(spk, slot):
+    """dist_out against wlx_spk_debug_affinity on the returned rows, bit for bit: with 2 windows (one tile) and 65 (one row past a tile),
+    with and without centroids behind the clustering. Threshold 2 merges everything, so the matrix on the device is overwritten in place
+    down to one cluster: dist_out is the download made before that."""
+    for m in (2, 65):
+        windows = [(k * 2000, 4800 + 16 * k) for k in range(m)]                     # 0.3 s and a little more: several passes at m = 65
+        for want in (("emb", "dist"), ("emb", "dist", "cent")):
+            o = diarize(spk, slot, 0, windows, threshold=2.0, want=want)
+            assert o["rc"] == 0 and o["k"].value == 1 and (o["labels"][:m] == 0).all() and (o["status"][:m] == 0).all()
+            X = np.ascontiguousarray(o["emb"][:m])
+            D = np.full((m, m), SENTINEL, np.float32)
+            assert spk.lib.wlx_spk_debug_affinity(0, X.ctypes.data_as(F32P), m, E, D.ctypes.data_as(F32P)) == 0
+            assert (D != SENTINEL).all()
+            assert (_bits(o["dist"]) == _bits(D)).all(), (m, want)
+            assert (o["cent"] == SENTINEL).all() if "cent" not in want else (o["cent"][1:] == SENTINEL).all() and (o["cent"][0] != SENTINEL).all()
+
+
 def test_a_short_window_in_the_middle(spk, slot, rows):
     windows = WINDOWS[:5] + [(20000, 4799)] + WINDOWS[5:9] + [(N, 0)]
     took = [i for i, (_, c) in enumerate(windows) if c >= 4800]

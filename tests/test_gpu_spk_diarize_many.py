@@ -1,7 +1,9 @@
 """GPU tests (-m gpu) of wlx_spk_diarize_many through the C-ABI: a wave of files, each in an item of its own of one slot, embedded in
 shared ragged passes and clustered side by side behind one wait. The yardstick is wlx_spk_diarize_pcm on each file alone (computed
-once, before any many-call): labels, status, cluster counts, rows and centroids bit for bit. A small seeded speaker engine with
-max_seconds = 6 (four 1.5 s windows per pass), so that passes end inside files and span files.
+once, before any many-call): labels, status, cluster counts, rows and centroids bit for bit — the same path on a wave of one, so
+test_every_file_of_the_wave_against_independent_references anchors the wave to wlx_spk_embed_pcm_batch and cluster_host as well, and
+test_the_shared_buffers_hold_no_state runs the three clustering calls after one another on one engine. A small seeded speaker engine
+with max_seconds = 6 (four 1.5 s windows per pass), so that passes end inside files and span files.
 (The matrix cap WLX_SPK_MANY_MAX_CELLS cannot be passed by arguments the other caps admit — at most 8192 rows in files of at most
 2048 give at most 4 x 2048^2 cells — so its refusal has no case here; diarization.plan_diarize_many is tested on it with caps of its own.)"""
 from __future__ import annotations
@@ -155,6 +157,129 @@ def test_every_file_equals_the_single_call(spk, slot, alone):
     # the resident audio was only read
     for item, pcm in before.items():
         assert np.array_equal(pcm.view(np.uint32), slot.pcm(item).view(np.uint32))
+
+
+def test_every_file_of_the_wave_against_independent_references(spk, slot):
+    """the wave of test_every_file_equals_the_single_call anchored to what shares no clustering code with it: every row to
+    wlx_spk_embed_pcm_batch on the same range bit for bit; labels and K to file_diarization.cluster_host on the matrix
+    wlx_spk_debug_affinity gives for the file's returned rows (the matrix the device clustered, so no threshold sits on a rounding
+    difference); centroids to cluster_host's within the 1e-5 of test_gpu_spk_diarize.py"""
+    from whisperlive_amd import file_diarization as FD
+    names = ["a", "b", "last", "one", "none"]
+    want_rows = {n: spk.embed_resident(slot, FILES[n][0], FILES[n][1]) for n in names}          # before the many-call
+    o = many(spk, slot, [FILES[n] for n in names])
+    assert o["rc"] == 0, spk.lib.wlx_last_error()
+    for f, name in enumerate(names):
+        _item, windows, thr, cap = FILES[name]
+        a, b = int(o["at"][f]), int(o["at"][f + 1])
+        took = [i for i, (_, c) in enumerate(windows) if c >= _lib.SPK_MIN_SAMPLES]
+        m = len(took)
+        assert o["fstat"][f] == 0
+        for i, row in enumerate(want_rows[name]):
+            assert (row is None) == (i not in took)
+            if row is None:
+                assert o["status"][a + i] == _lib.ERR_TOO_SHORT and o["labels"][a + i] == -1 and (o["emb"][a + i] == 0).all(), (name, i)
+            else:
+                assert o["status"][a + i] == 0 and (_bits(o["emb"][a + i]) == _bits(row)).all(), (name, i, "differs from wlx_spk_embed_pcm_batch")
+        if m == 0:
+            assert o["k"][f] == 0 and (o["cent"][a:b] == SENTINEL).all()
+            continue
+        X = np.ascontiguousarray(o["emb"][a:b][took])
+        D = np.full((m, m), SENTINEL, np.float32)
+        assert spk.lib.wlx_spk_debug_affinity(0, X.ctypes.data_as(F32P), m, E, D.ctypes.data_as(F32P)) == 0
+        want = FD.cluster_host(X, thr, cap, dist=D)
+        K = int(want.labels.max()) + 1
+        assert o["k"][f] == K and np.array_equal(o["labels"][a:b][took], want.labels), (name, K, int(o["k"][f]))
+        assert np.abs(o["cent"][a:a + K] - want.centroids).max() <= 1e-5 and (o["cent"][a + K:b] == SENTINEL).all(), name
+    assert [int(k) for k in o["k"]][3:] == [1, 0] and o["k"][1] == 2 and 1 <= o["k"][2] <= 3
+
+
+# ---- the one table behind every clustering call: the three calls of test_the_shared_buffers_hold_no_state, outputs padded with sentinels
+PAD = 3
+WAVE = [(0, grid(12.0)[:5], 0.45, 0), (1, [(0, W), (100, 4799), (12000, W)], 0.0, 2), (5, grid(9.0)[:3], 0.02, 3)]          # 5, 2 and 3 windows take part
+PCM_WINDOWS = [(0, W), (50, 100), (24000, W), (36000, 9999)]                                                               # 3 of 4 take part
+
+
+def _call_wave(spk, slot):
+    total = sum(len(f[1]) for f in WAVE)
+    counts = np.array([len(f[1]) for f in WAVE], np.int32)
+    flat = [w for f in WAVE for w in f[1]]
+    starts, samples = np.array([a for a, _ in flat], np.int64), np.array([c for _, c in flat], np.int64)
+    its = np.array([f[0] for f in WAVE], np.int32)
+    opts = (_lib.wlx_spk_cluster_opts * len(WAVE))(*[_lib.wlx_spk_cluster_opts(f[2], f[3]) for f in WAVE])
+    o = dict(labels=np.full(total + PAD, -7, np.int32), status=np.full(total + PAD, -7, np.int32), fstat=np.full(len(WAVE) + PAD, -7, np.int32),
+             k=np.full(len(WAVE) + PAD, -7, np.int32), emb=np.full((total + PAD, E), SENTINEL, np.float32),
+             cent=np.full((total + PAD, E), SENTINEL, np.float32))
+    rc = spk.lib.wlx_spk_diarize_many(spk.h, slot.engine._h, slot.sid, len(WAVE), its.ctypes.data_as(I32P), counts.ctypes.data_as(I32P),
+                                      starts.ctypes.data_as(I64P), samples.ctypes.data_as(I64P), opts, o["labels"].ctypes.data_as(I32P),
+                                      o["status"].ctypes.data_as(I32P), o["fstat"].ctypes.data_as(I32P), o["k"].ctypes.data_as(I32P),
+                                      o["emb"].ctypes.data_as(F32P), o["cent"].ctypes.data_as(F32P))
+    assert rc == 0, spk.lib.wlx_last_error()
+    # behind every written range: the pads, and the centroid rows past each file's K
+    assert all((o[n][-PAD:] == -7).all() for n in ("labels", "status", "fstat", "k")) and (o["emb"][-PAD:] == SENTINEL).all()
+    at = 0
+    for f, n in enumerate(counts):
+        assert 1 <= o["k"][f] <= n and (o["cent"][at + o["k"][f]:at + n] == SENTINEL).all()
+        at += n
+    assert (o["cent"][at:] == SENTINEL).all() and (o["status"][:total] != -7).all() and (o["emb"][:total] != SENTINEL).all()
+    return o
+
+
+def _call_pcm(spk, slot):
+    n, m = len(PCM_WINDOWS), 3
+    starts, counts = np.array([a for a, _ in PCM_WINDOWS], np.int64), np.array([c for _, c in PCM_WINDOWS], np.int64)
+    o = dict(labels=np.full(n + PAD, -7, np.int32), status=np.full(n + PAD, -7, np.int32), emb=np.full((n + PAD, E), SENTINEL, np.float32),
+             dist=np.full(m * m + PAD, SENTINEL, np.float32), cent=np.full((n + PAD, E), SENTINEL, np.float32), k=np.full(1 + PAD, -7, np.int32))
+    opts = _lib.wlx_spk_cluster_opts(0.0, 2)
+    rc = spk.lib.wlx_spk_diarize_pcm(spk.h, slot.engine._h, slot.sid, 0, starts.ctypes.data_as(I64P), counts.ctypes.data_as(I64P), n, C.byref(opts),
+                                     o["labels"].ctypes.data_as(I32P), o["status"].ctypes.data_as(I32P), o["emb"].ctypes.data_as(F32P),
+                                     o["dist"].ctypes.data_as(F32P), o["cent"].ctypes.data_as(F32P), o["k"].ctypes.data_as(I32P))
+    assert rc == 0, spk.lib.wlx_last_error()
+    assert o["k"][0] == 2 and o["status"][:n].tolist() == [0, _lib.ERR_TOO_SHORT, 0, 0] and o["labels"][1] == -1
+    assert (o["labels"][-PAD:] == -7).all() and (o["status"][-PAD:] == -7).all() and (o["k"][1:] == -7).all()
+    assert (o["emb"][n:] == SENTINEL).all() and (o["dist"][m * m:] == SENTINEL).all() and (o["cent"][2:] == SENTINEL).all()
+    assert (o["emb"][:n] != SENTINEL).all() and (o["dist"][:m * m] != SENTINEL).all() and (o["cent"][:2] != SENTINEL).all()
+    return o
+
+
+def _call_cluster(spk, slot):
+    X = np.random.default_rng(41).standard_normal((3, E))
+    X = np.ascontiguousarray(X / np.linalg.norm(X, axis=1, keepdims=True), dtype=np.float32)
+    o = dict(labels=np.full(3 + PAD, -7, np.int32), cent=np.full((3 + PAD, E), SENTINEL, np.float32), k=np.full(1 + PAD, -7, np.int32))
+    opts = _lib.wlx_spk_cluster_opts(0.0, 2)
+    rc = spk.lib.wlx_spk_cluster(spk.h, X.ctypes.data_as(F32P), 3, E, C.byref(opts), o["labels"].ctypes.data_as(I32P), o["cent"].ctypes.data_as(F32P),
+                                 o["k"].ctypes.data_as(I32P))
+    assert rc == 0, spk.lib.wlx_last_error()
+    assert o["k"][0] == 2 and sorted(o["labels"][:3].tolist()) in ([0, 0, 1], [0, 1, 1])
+    assert (o["labels"][3:] == -7).all() and (o["k"][1:] == -7).all() and (o["cent"][2:] == SENTINEL).all() and (o["cent"][:2] != SENTINEL).all()
+    return o
+
+
+def test_the_shared_buffers_hold_no_state(gpu, slot):
+    """one table, one matrix area and one set of pinned landing buffers serve wlx_spk_diarize_many, wlx_spk_diarize_pcm and
+    wlx_spk_cluster. On ONE engine: a wave of three files (5, 2 and 3 windows take part), a wlx_spk_diarize_pcm of 4 windows (one short)
+    with dist_out, a wlx_spk_cluster of 3 host rows, the wave again — a small file after a larger one on the same rows, on matrix offset 0
+    and in the same landing buffers. Every output of every call, its sentinel pads included, has the bits the same call gives as the
+    FIRST clustering call of a fresh engine."""
+    def fresh():
+        return SpeakerEmbedderHIP(SPEC, spk_weights.fold(spk_weights.random_weights(SPEC, seed=11), SPEC), device=0)
+
+    first = {}
+    for call in (_call_wave, _call_pcm, _call_cluster):
+        e = fresh()
+        try:
+            first[call] = call(e, slot)
+        finally:
+            e.close()
+    e = fresh()
+    try:
+        for step, call in enumerate((_call_wave, _call_pcm, _call_cluster, _call_wave)):
+            got = call(e, slot)
+            for name, want in first[call].items():
+                same = (_bits(got[name]) == _bits(want)).all() if want.dtype == np.float32 else np.array_equal(got[name], want)
+                assert same, (step, call.__name__, name, "differs from the first clustering call of a fresh engine")
+    finally:
+        e.close()
 
 
 def test_the_python_face(spk, slot, alone):

@@ -53,38 +53,32 @@ bool launch_spk_pool_batch(const half_t* x, int F, const int* frames, int n, int
 bool launch_spk_head_batch(const float* pooled, const half_t* W, const float* b, int E, int D, int n, float* emb, hipStream_t s,
                            bool normalize = true);
 
-// ---- offline clustering (spk_cluster.hip): n in 1..WLX_SPK_CLUSTER_MAX unit rows of D <= 1024 floats, everything float32.
-// False = nothing launched (a null pointer, n or D out of range, a threshold that is NaN or outside [0, 2], max_clusters < 0).
-// dist [n][n] = 1 - X X^T, exactly symmetric, diagonal exactly 0
-bool launch_spk_affinity(const float* X, int n, int D, float* dist, hipStream_t s);
-// average-linkage clustering of dist IN PLACE, one workgroup (the rules: include/wlx.h wlx_spk_cluster). merges [n - 1][2],
-// heights [n - 1], labels [n], counts [2] = {n_merges, K}
-bool launch_spk_ahc(float* dist, int n, float threshold, int max_clusters, int* merges, float* heights, int* labels, int* counts,
-                    hipStream_t s);
-// cent [K][D], K = counts[1] read on the device (the grid covers n): the normalised sum of each cluster's rows
-bool launch_spk_centroids(const float* X, const int* labels, const int* counts, int n, int D, float* cent, hipStream_t s);
-
-// ---- the same for a wave of files in one launch each: 1..WLX_SPK_MANY_MAX_FILES files, every one a shape the single launchers take.
-// File i is rows [row0, row0 + m) of ONE table X and owns the m x m matrix at dist + doff; the rows of all files end inside
-// WLX_SPK_MANY_MAX_ROWS and the matrices inside WLX_SPK_MANY_MAX_CELLS floats (the caller lays them out without overlap). `files` is a
-// HOST array read before the call returns: the table travels in the kernel arguments. Each file's results have the bits of the single
-// launcher on that file alone. False = nothing launched.
+// ---- offline clustering (spk_cluster.hip), everything float32: every launch serves a table of 1..WLX_SPK_MANY_MAX_FILES files (one file
+// is a table of one), every file 1..WLX_SPK_CLUSTER_MAX unit rows of D <= 1024 floats. File i is rows [row0, row0 + m) of ONE table X and
+// owns the m x m matrix at dist + doff; the rows of all files end inside WLX_SPK_MANY_MAX_ROWS and the matrices inside
+// WLX_SPK_MANY_MAX_CELLS floats (the caller lays them out without overlap). `files` is a HOST array read before the call returns: the
+// table travels in the kernel arguments. A file's results do not depend on the files around it. False = nothing launched (a null
+// pointer, a count or shape out of range, a threshold that is NaN or outside [0, 2], max_clusters < 0).
 struct SpkClusterFile {
     size_t doff;           // first float of the file's matrix
     int row0, m;
-    float threshold;       // read by launch_spk_ahc_many only, as max_clusters
+    float threshold;       // read by launch_spk_ahc only, as max_clusters
     int max_clusters;
 };
 struct SpkClusterTable {
     int n;
     SpkClusterFile f[WLX_SPK_MANY_MAX_FILES];
 };
-bool launch_spk_affinity_many(const float* X, const SpkClusterFile* files, int n_files, int D, float* dist, hipStream_t s);
-// one workgroup per file. labels [rows] and heights [rows]: file i at row0; merges [2 * rows]: at 2 * row0; counts [n_files][2]
-bool launch_spk_ahc_many(float* dist, const SpkClusterFile* files, int n_files, int* merges, float* heights, int* labels, int* counts,
-                         hipStream_t s);
-// cent [rows][D]: file i's K_i = counts[i][1] centroids at rows row0 .. row0 + K_i - 1
-bool launch_spk_centroids_many(const float* X, const int* labels, const int* counts, const SpkClusterFile* files, int n_files, int D,
-                               float* cent, hipStream_t s);
+// per file, dist [m][m] = 1 - X X^T, exactly symmetric, diagonal exactly 0
+bool launch_spk_affinity(const float* X, const SpkClusterFile* files, int n_files, int D, float* dist, hipStream_t s);
+// average-linkage clustering of every file's matrix IN PLACE, one workgroup per file (the rules: include/wlx.h wlx_spk_cluster).
+// labels [rows] and heights [rows]: file i at row0 (m - 1 heights at the most); merges [2 * rows]: at 2 * row0; counts [n_files][2] =
+// {n_merges, K} per file
+bool launch_spk_ahc(float* dist, const SpkClusterFile* files, int n_files, int* merges, float* heights, int* labels, int* counts,
+                    hipStream_t s);
+// cent [rows][D]: the normalised sum of each cluster's rows, file i's K_i = counts[i][1] (read on the device) centroids at rows
+// row0 .. row0 + K_i - 1
+bool launch_spk_centroids(const float* X, const int* labels, const int* counts, const SpkClusterFile* files, int n_files, int D,
+                          float* cent, hipStream_t s);
 
 }  // namespace wlx

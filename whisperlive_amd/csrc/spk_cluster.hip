@@ -2,9 +2,9 @@
 // the cosine-distance matrix of n <= WLX_SPK_CLUSTER_MAX unit embeddings, average-linkage (UPGMA) agglomerative clustering of that
 // matrix in ONE launch of ONE workgroup, and the unit centroids of the clusters. Everything is float32: the merge threshold sits where
 // fp16 noise would flip merges. The clustering is exact: tests/ compare merges, heights and labels with the NumPy float32 restatement
-// (whisperlive_amd/file_diarization.py cluster_host) for equality. Each kernel has a many-form over a table of up to
-// WLX_SPK_MANY_MAX_FILES files (wlx_spk_diarize_many): the bodies are __device__ functions both forms call, so a file's results have the
-// bits of the single launch on that file alone.
+// (whisperlive_amd/file_diarization.py cluster_host) for equality. Every kernel works over a table of 1..WLX_SPK_MANY_MAX_FILES files
+// that travels in its arguments: wlx_spk_cluster and wlx_spk_diarize_pcm launch a table of one file, wlx_spk_diarize_many
+// a wave's. A file's results depend on its own rows and options only, not on the table around it.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -17,7 +17,9 @@ namespace {
 // ------------------------------------------------------------------------------------------------ distance matrix
 // Dist[i][j] = 1 - dot(X_i, X_j): a 64 x 64 tile per workgroup of 256 threads (4 x 4 outputs each), K in slices of 16 through LDS.
 // Every dot product is ONE chain of fmaf over k = 0 .. D-1 in order, whichever tile it lies in, and a * b = b * a: Dist[i][j] and
-// Dist[j][i] have the same bits. The diagonal is written as 0, not computed.
+// Dist[j][i] have the same bits. The diagonal is written as 0, not computed. File f = blockIdx.z is rows [row0, row0 + m) of one table
+// and writes its own m x m matrix at dist + doff; the grid's tiles cover the largest file and a workgroup whose tile lies outside its file
+// leaves (workgroup-uniform, before any barrier).
 constexpr int AFF_TILE = 64, AFF_K = 16, AFF_THREADS = 256;
 
 __device__ __forceinline__ void spk_affinity_tile(const float* __restrict__ X, int n, int D, float* __restrict__ dist, int i0, int j0) {
@@ -52,15 +54,10 @@ __device__ __forceinline__ void spk_affinity_tile(const float* __restrict__ X, i
         }
 }
 
-__global__ __launch_bounds__(AFF_THREADS) void spk_affinity_kernel(const float* __restrict__ X, int n, int D, float* __restrict__ dist) {
-    spk_affinity_tile(X, n, D, dist, blockIdx.y * AFF_TILE, blockIdx.x * AFF_TILE);
-}
-
-// The matrices of up to WLX_SPK_MANY_MAX_FILES files in one launch: file f = blockIdx.z is rows [row0, row0 + m) of one table and writes
-// its own m x m matrix at dist + doff; the grid's tiles cover the largest file and a workgroup whose tile lies outside its file leaves
-// (workgroup-uniform, before any barrier). The tile code is spk_affinity_kernel's: each matrix has the bits of that kernel on the file alone.
-__global__ __launch_bounds__(AFF_THREADS) void spk_affinity_many_kernel(const float* __restrict__ X, SpkClusterTable tab, int D,
-                                                                         float* __restrict__ dist) {
+// (the tile stays a function of its own: folded into the kernel the compiler allots 78 VGPRs, not the 80 of this form — another schedule
+// of the same arithmetic, which nobody has timed)
+__global__ __launch_bounds__(AFF_THREADS) void spk_affinity_kernel(const float* __restrict__ X, SpkClusterTable tab, int D,
+                                                                    float* __restrict__ dist) {
     const SpkClusterFile f = tab.f[blockIdx.z];
     const int i0 = blockIdx.y * AFF_TILE, j0 = blockIdx.x * AFF_TILE;
     if (i0 >= f.m || j0 >= f.m) return;
@@ -101,6 +98,9 @@ __device__ __forceinline__ void ahc_scan_row(const float* dist, int n, int k, co
     if (lane == 0) nnd[k] = bd, nn[k] = (uint16_t)bj;
 }
 
+// One workgroup per file, blockIdx.x = file: the clusterings are independent, so they run on as many CUs at once (24 KiB of LDS and 1024
+// threads per workgroup: two may share a CU). File f clusters its matrix at dist + doff (n = m) under its own threshold and max_clusters;
+// labels and heights are written at row0, merges at 2 * row0 (room for m each), counts at [f][2].
 // dist [n][n] symmetric, clustered IN PLACE (rows and columns of merged clusters are overwritten). Clusters are named by their lowest
 // member. Each round merges the pair (i, j), i < j, of live clusters with the smallest (distance, i, j); it stops at one cluster, or
 // when that distance is > threshold and (max_clusters == 0 or live <= max_clusters). The minimum comes from a per-row cache of the
@@ -109,9 +109,13 @@ __device__ __forceinline__ void ahc_scan_row(const float* dist, int n, int k, co
 // neighbour was i or j or when it is row i itself, and takes the new d(k, i) when that beats its cache; rows above j see no change.
 // The loop runs at most n - 1 times and waits on nothing but __syncthreads.
 // out: merges [n_merges][2], heights [n_merges], labels [n] (clusters numbered by lowest member, ascending), counts = {n_merges, K}.
-__device__ __forceinline__ void spk_ahc_body(float* __restrict__ dist, int n, float threshold, int max_clusters,
-                                             int* __restrict__ merges, float* __restrict__ heights, int* __restrict__ labels,
-                                             int* __restrict__ counts) {
+__global__ __launch_bounds__(AHC_THREADS) void spk_ahc_kernel(float* __restrict__ dist, SpkClusterTable tab, int* __restrict__ merges,
+                                                             float* __restrict__ heights, int* __restrict__ labels,
+                                                             int* __restrict__ counts) {
+    const SpkClusterFile f = tab.f[blockIdx.x];
+    const int n = f.m, max_clusters = f.max_clusters;
+    const float threshold = f.threshold;
+    dist += f.doff, merges += 2 * (size_t)f.row0, heights += f.row0, labels += f.row0, counts += 2 * blockIdx.x;
     __shared__ uint16_t size[WLX_SPK_CLUSTER_MAX], nn[WLX_SPK_CLUSTER_MAX], parent[WLX_SPK_CLUSTER_MAX], todo[WLX_SPK_CLUSTER_MAX];
     __shared__ float nnd[WLX_SPK_CLUSTER_MAX];
     __shared__ float red_d[AHC_WAVES];
@@ -200,27 +204,16 @@ __device__ __forceinline__ void spk_ahc_body(float* __restrict__ dist, int n, fl
     if (tid == 0) counts[0] = n_merges, counts[1] = live;
 }
 
-__global__ __launch_bounds__(AHC_THREADS) void spk_ahc_kernel(float* __restrict__ dist, int n, float threshold, int max_clusters,
-                                                             int* __restrict__ merges, float* __restrict__ heights,
-                                                             int* __restrict__ labels, int* __restrict__ counts) {
-    spk_ahc_body(dist, n, threshold, max_clusters, merges, heights, labels, counts);
-}
-
-// One workgroup per file, blockIdx.x = file: the clusterings are independent, so they run on as many CUs at once (24 KiB of LDS and 1024
-// threads per workgroup: two may share a CU). File f clusters its matrix at dist + doff in place under its own threshold and
-// max_clusters; labels and heights are written at row0, merges at 2 * row0 (room for m each), counts at [f][2].
-__global__ __launch_bounds__(AHC_THREADS) void spk_ahc_many_kernel(float* __restrict__ dist, SpkClusterTable tab, int* __restrict__ merges,
-                                                                  float* __restrict__ heights, int* __restrict__ labels,
-                                                                  int* __restrict__ counts) {
-    const SpkClusterFile f = tab.f[blockIdx.x];
-    spk_ahc_body(dist + f.doff, f.m, f.threshold, f.max_clusters, merges + 2 * (size_t)f.row0, heights + f.row0, labels + f.row0,
-                 counts + 2 * blockIdx.x);
-}
-
 // ------------------------------------------------------------------------------------------------ centroids
-// cluster c = blockIdx.x (blocks past K = counts[1] leave): the sum of its members' rows in member order, divided by its norm
-__device__ __forceinline__ void spk_centroid_body(const float* __restrict__ X, const int* __restrict__ labels, int n, int D,
-                                                  float* __restrict__ cent, int c) {
+// grid (cluster, file): cluster c = blockIdx.x of file f = blockIdx.y (blocks past K = counts[f][1], and past m, leave): the sum of its
+// members' rows in member order, divided by its norm, to row row0 + c of cent
+__global__ __launch_bounds__(256) void spk_centroid_kernel(const float* __restrict__ X, const int* __restrict__ labels,
+                                                           const int* __restrict__ counts, SpkClusterTable tab, int D,
+                                                           float* __restrict__ cent) {
+    const SpkClusterFile f = tab.f[blockIdx.y];
+    const int c = blockIdx.x, n = f.m;
+    if (c >= n || c >= counts[2 * blockIdx.y + 1]) return;
+    X += (size_t)f.row0 * D, labels += f.row0, cent += (size_t)f.row0 * D;
     __shared__ float red[256];
     float sq = 0.f;
     for (int d = threadIdx.x; d < D; d += 256) {
@@ -241,49 +234,11 @@ __device__ __forceinline__ void spk_centroid_body(const float* __restrict__ X, c
         for (int d = threadIdx.x; d < D; d += 256) cent[(size_t)c * D + d] /= norm;      // (each thread rereads what it wrote itself)
 }
 
-__global__ __launch_bounds__(256) void spk_centroid_kernel(const float* __restrict__ X, const int* __restrict__ labels,
-                                                           const int* __restrict__ counts, int n, int D, float* __restrict__ cent) {
-    const int c = blockIdx.x;
-    if (c >= counts[1]) return;
-    spk_centroid_body(X, labels, n, D, cent, c);
-}
-
-// grid (cluster, file): file f's centroids go to rows row0 .. row0 + K - 1 of cent, K = counts[f][1]; blocks past K (and past m) leave
-__global__ __launch_bounds__(256) void spk_centroid_many_kernel(const float* __restrict__ X, const int* __restrict__ labels,
-                                                                const int* __restrict__ counts, SpkClusterTable tab, int D,
-                                                                float* __restrict__ cent) {
-    const SpkClusterFile f = tab.f[blockIdx.y];
-    const int c = blockIdx.x;
-    if (c >= f.m || c >= counts[2 * blockIdx.y + 1]) return;
-    spk_centroid_body(X + (size_t)f.row0 * D, labels + f.row0, f.m, D, cent + (size_t)f.row0 * D, c);
-}
-
 bool cluster_shape_ok(int n, int D) { return n >= 1 && n <= WLX_SPK_CLUSTER_MAX && D >= 1 && D <= 1024; }
 
 }  // namespace
 
-bool launch_spk_affinity(const float* X, int n, int D, float* dist, hipStream_t s) {
-    if (!X || !dist || !cluster_shape_ok(n, D)) return false;
-    const int t = (n + AFF_TILE - 1) / AFF_TILE;
-    spk_affinity_kernel<<<dim3(t, t), AFF_THREADS, 0, s>>>(X, n, D, dist);
-    return true;
-}
-
-bool launch_spk_ahc(float* dist, int n, float threshold, int max_clusters, int* merges, float* heights, int* labels, int* counts,
-                    hipStream_t s) {
-    if (!dist || !merges || !heights || !labels || !counts || !cluster_shape_ok(n, 1)) return false;
-    if (!(threshold >= 0.f && threshold <= 2.f) || max_clusters < 0) return false;
-    spk_ahc_kernel<<<1, AHC_THREADS, 0, s>>>(dist, n, threshold, max_clusters, merges, heights, labels, counts);
-    return true;
-}
-
-bool launch_spk_centroids(const float* X, const int* labels, const int* counts, int n, int D, float* cent, hipStream_t s) {
-    if (!X || !labels || !counts || !cent || !cluster_shape_ok(n, D)) return false;
-    spk_centroid_kernel<<<n, 256, 0, s>>>(X, labels, counts, n, D, cent);
-    return true;
-}
-
-// the table of a many-launch: every file a shape the single kernels take, rows and matrices inside the caps, offsets filled in here
+// the table of a launch: every file 1..WLX_SPK_CLUSTER_MAX rows of D <= 1024, rows and matrices inside the caps
 static bool cluster_table(const SpkClusterFile* files, int n_files, int D, bool with_opts, SpkClusterTable& tab, int& max_m) {
     if (!files || n_files < 1 || n_files > WLX_SPK_MANY_MAX_FILES) return false;
     size_t cells = 0;
@@ -302,30 +257,30 @@ static bool cluster_table(const SpkClusterFile* files, int n_files, int D, bool 
     return rows <= WLX_SPK_MANY_MAX_ROWS && cells <= WLX_SPK_MANY_MAX_CELLS;
 }
 
-bool launch_spk_affinity_many(const float* X, const SpkClusterFile* files, int n_files, int D, float* dist, hipStream_t s) {
+bool launch_spk_affinity(const float* X, const SpkClusterFile* files, int n_files, int D, float* dist, hipStream_t s) {
     SpkClusterTable tab;
     int max_m;
     if (!X || !dist || !cluster_table(files, n_files, D, false, tab, max_m)) return false;
     const int t = (max_m + AFF_TILE - 1) / AFF_TILE;
-    spk_affinity_many_kernel<<<dim3(t, t, n_files), AFF_THREADS, 0, s>>>(X, tab, D, dist);
+    spk_affinity_kernel<<<dim3(t, t, n_files), AFF_THREADS, 0, s>>>(X, tab, D, dist);
     return true;
 }
 
-bool launch_spk_ahc_many(float* dist, const SpkClusterFile* files, int n_files, int* merges, float* heights, int* labels, int* counts,
-                         hipStream_t s) {
+bool launch_spk_ahc(float* dist, const SpkClusterFile* files, int n_files, int* merges, float* heights, int* labels, int* counts,
+                    hipStream_t s) {
     SpkClusterTable tab;
     int max_m;
     if (!dist || !merges || !heights || !labels || !counts || !cluster_table(files, n_files, 1, true, tab, max_m)) return false;
-    spk_ahc_many_kernel<<<n_files, AHC_THREADS, 0, s>>>(dist, tab, merges, heights, labels, counts);
+    spk_ahc_kernel<<<n_files, AHC_THREADS, 0, s>>>(dist, tab, merges, heights, labels, counts);
     return true;
 }
 
-bool launch_spk_centroids_many(const float* X, const int* labels, const int* counts, const SpkClusterFile* files, int n_files, int D,
-                               float* cent, hipStream_t s) {
+bool launch_spk_centroids(const float* X, const int* labels, const int* counts, const SpkClusterFile* files, int n_files, int D,
+                          float* cent, hipStream_t s) {
     SpkClusterTable tab;
     int max_m;
     if (!X || !labels || !counts || !cent || !cluster_table(files, n_files, D, false, tab, max_m)) return false;
-    spk_centroid_many_kernel<<<dim3(max_m, n_files), 256, 0, s>>>(X, labels, counts, tab, D, cent);
+    spk_centroid_kernel<<<dim3(max_m, n_files), 256, 0, s>>>(X, labels, counts, tab, D, cent);
     return true;
 }
 

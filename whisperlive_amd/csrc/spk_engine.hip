@@ -4,10 +4,11 @@
 // by the engine's mutex. ONE pass (spk_run_batch) serves every entry point: up to WLX_SPK_MAX_BATCH segments as one ragged batch
 // through the same buffers (the sum of their lengths is what has to fit max_seconds). wlx_spk_embed is a batch of one;
 // wlx_spk_embed_batch uploads its items; wlx_spk_embed_pcm_batch / _ring_batch run the pass on ranges of audio that is already in HBM
-// (a slot item's PCM, a client's PCM ring), with no upload. wlx_spk_cluster / wlx_spk_diarize_pcm cluster embeddings on the device
-// (spk_cluster.hip): the second enqueues the passes of a whole file's windows back to back and waits once, and wlx_spk_diarize_many does
-// the same for a wave of files in different items of one slot — shared passes, the files clustered side by side, one wait. Below the engine: the one-launch test hooks wlx_spk_debug_fbank / _conv /
-// _pool (one item) and _conv_batch / _pool_batch (ragged), each pair on one implementation.
+// (a slot item's PCM, a client's PCM ring), with no upload. wlx_spk_cluster / wlx_spk_diarize_pcm / wlx_spk_diarize_many cluster
+// embeddings on the device (spk_cluster.hip) on ONE path, a file being a wave of one: the passes of the windows of a wave of files in
+// different items of one slot enqueued back to back — shared passes, the files clustered side by side — and one wait. Below the engine:
+// the one-launch test hooks wlx_spk_debug_fbank / _conv / _pool (one item) and _conv_batch / _pool_batch (ragged), each pair on one
+// implementation, as are wlx_spk_debug_affinity / _ahc and their many-forms.
 #include <cmath>
 #include <mutex>
 #include "engine.h"
@@ -116,24 +117,17 @@ struct wlx_spk {
     float* h_emb = nullptr;          // pinned [WLX_SPK_MAX_BATCH][embed_dim]: where a batch's embeddings land before they are dealt to rows
     float fbank_ms = 0.f, net_ms = 0.f;
     bool timed = false;
-    // offline clustering (spk_cluster.hip), allocated by the first call that clusters: the table of up to WLX_SPK_CLUSTER_MAX embeddings
-    // the passes of a file write into, its distance matrix, the results, and their pinned landing places
-    bool cl_ready = false;
-    float *cl_emb = nullptr, *cl_dist = nullptr, *cl_cent = nullptr, *cl_heights = nullptr;
-    int *cl_merges = nullptr, *cl_labels = nullptr, *cl_counts = nullptr;
-    float *h_cl_emb = nullptr, *h_cl_cent = nullptr;
-    int* h_cl_int = nullptr;         // [labels WLX_SPK_CLUSTER_MAX | n_merges, K]
-    hipEvent_t ev_cl[4] = {nullptr, nullptr, nullptr, nullptr};
-    float aff_ms = 0.f, ahc_ms = 0.f;
-    bool cl_timed = false;
-    // a wave of files (wlx_spk_diarize_many), allocated by the first such call and apart from the cl_* buffers: one table of up to
-    // WLX_SPK_MANY_MAX_ROWS embeddings, the files' matrices back to back, results per row / per file, and their pinned landing places
+    // offline clustering (spk_cluster.hip), allocated by the first call that clusters and shared by all of them (a file is a wave of one):
+    // one table of up to WLX_SPK_MANY_MAX_ROWS embeddings the passes write into, the files' distance matrices back to back, results per
+    // row / per file, and their pinned landing places
     bool mn_ready = false;
     float *mn_emb = nullptr, *mn_dist = nullptr, *mn_cent = nullptr, *mn_heights = nullptr;
     int *mn_merges = nullptr, *mn_labels = nullptr, *mn_counts = nullptr;
     float *h_mn_emb = nullptr, *h_mn_cent = nullptr;
     int* h_mn_int = nullptr;         // [labels WLX_SPK_MANY_MAX_ROWS | (n_merges, K) x WLX_SPK_MANY_MAX_FILES]
-    hipEvent_t ev_mn[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev_cl[4] = {nullptr, nullptr, nullptr, nullptr};          // around the distance matrices [0, 1] and the clustering [2, 3]
+    float aff_ms = 0.f, ahc_ms = 0.f;
+    bool cl_timed = false;
 };
 
 static void spk_free(wlx_spk* k) {
@@ -146,9 +140,7 @@ static void spk_free(wlx_spk* k) {
     if (k->h_emb) (void)hipHostFree(k->h_emb);
     for (hipEvent_t e : k->ev_cl)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : k->ev_mn)
-        if (e) (void)hipEventDestroy(e);
-    for (void* p : {(void*)k->h_cl_emb, (void*)k->h_cl_cent, (void*)k->h_cl_int, (void*)k->h_mn_emb, (void*)k->h_mn_cent, (void*)k->h_mn_int})
+    for (void* p : {(void*)k->h_mn_emb, (void*)k->h_mn_cent, (void*)k->h_mn_int})
         if (p) (void)hipHostFree(p);
     if (k->st) (void)hipStreamDestroy(k->st);
     delete k;
@@ -408,6 +400,7 @@ extern "C" int32_t wlx_spk_embed_ring_batch(wlx_spk* k, wlx_ring* r, const int64
 }
 
 // ------------------------------------------------------------------------------------------------ offline clustering (spk_cluster.hip)
+// ONE path behind wlx_spk_cluster, wlx_spk_diarize_pcm and wlx_spk_diarize_many: a file is a wave of one.
 static int spk_cluster_opts_ok(const char* who, const wlx_spk_cluster_opts* o) {
     if (!(o->threshold >= 0.f && o->threshold <= 2.f))
         return set_error(WLX_ERR_ARG, "%s: threshold %g is not a cosine distance in [0, 2]", who, (double)o->threshold);
@@ -416,86 +409,172 @@ static int spk_cluster_opts_ok(const char* who, const wlx_spk_cluster_opts* o) {
 }
 
 // the buffers of a clustering call, made by the first one (an engine that only embeds never pays for them). k->mu is held.
-static int spk_cluster_reserve(wlx_spk* k) {
-    if (k->cl_ready) return WLX_OK;
-    const size_t N = WLX_SPK_CLUSTER_MAX, E = (size_t)k->spec.embed_dim;
-    if (!k->cl_emb) CKR(dalloc(k->pool, &k->cl_emb, N * E, false));
-    if (!k->cl_cent) CKR(dalloc(k->pool, &k->cl_cent, N * E, false));
-    if (!k->cl_dist) CKR(dalloc(k->pool, &k->cl_dist, N * N, false));
-    if (!k->cl_heights) CKR(dalloc(k->pool, &k->cl_heights, N, false));
-    if (!k->cl_merges) CKR(dalloc(k->pool, &k->cl_merges, 2 * N, false));
-    if (!k->cl_labels) CKR(dalloc(k->pool, &k->cl_labels, N, false));
-    if (!k->cl_counts) CKR(dalloc(k->pool, &k->cl_counts, 2, false));
-    if (!k->h_cl_emb) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_cl_emb), N * E * sizeof(float), hipHostMallocDefault));
-    if (!k->h_cl_cent) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_cl_cent), N * E * sizeof(float), hipHostMallocDefault));
-    if (!k->h_cl_int) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_cl_int), (N + 2) * sizeof(int), hipHostMallocDefault));
+static int spk_many_reserve(wlx_spk* k) {
+    if (k->mn_ready) return WLX_OK;
+    const size_t R = WLX_SPK_MANY_MAX_ROWS, F = WLX_SPK_MANY_MAX_FILES, E = (size_t)k->spec.embed_dim;
+    if (!k->mn_emb) CKR(dalloc(k->pool, &k->mn_emb, R * E, false));
+    if (!k->mn_cent) CKR(dalloc(k->pool, &k->mn_cent, R * E, false));
+    if (!k->mn_dist) CKR(dalloc(k->pool, &k->mn_dist, (size_t)WLX_SPK_MANY_MAX_CELLS, false));
+    if (!k->mn_heights) CKR(dalloc(k->pool, &k->mn_heights, R, false));
+    if (!k->mn_merges) CKR(dalloc(k->pool, &k->mn_merges, 2 * R, false));
+    if (!k->mn_labels) CKR(dalloc(k->pool, &k->mn_labels, R, false));
+    if (!k->mn_counts) CKR(dalloc(k->pool, &k->mn_counts, 2 * F, false));
+    if (!k->h_mn_emb) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_emb), R * E * sizeof(float), hipHostMallocDefault));
+    if (!k->h_mn_cent) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_cent), R * E * sizeof(float), hipHostMallocDefault));
+    if (!k->h_mn_int) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_int), (R + 2 * F) * sizeof(int), hipHostMallocDefault));
     for (hipEvent_t& e : k->ev_cl)
         if (!e) CK(hipEventCreate(&e));
-    k->cl_ready = true;
+    k->mn_ready = true;
     return WLX_OK;
 }
 
-// m >= 2 rows of k->cl_emb, written by work already on k->st: distance matrix, clustering, centroids and the downloads into the pinned
-// buffers, all enqueued; the caller waits once. dist_out (host, may be null) gets the matrix before the clustering overwrites it.
-static int spk_cluster_enqueue(wlx_spk* k, int m, const wlx_spk_cluster_opts* o, float* dist_out, bool want_centroids) {
+// What the windows of a wave of files come to on the arguments alone. Rows of the table k->mn_emb are the windows that take part, file by
+// file: file f owns rows [row0[f], row0[f] + m_of[f]) and, with m_of[f] >= 2, an entry of `cf`: a matrix and a workgroup of the clustering.
+struct SpkWave {
+    std::vector<long> w0;              // [n_files + 1]: first window of file f in the packed arrays (set by the entry point)
+    std::vector<SpkPlan> plans;        // the ragged passes over the windows that take part
+    std::vector<long> win_of;          // the packed window behind row a of the table
+    std::vector<int> row0, m_of;
+    std::vector<SpkClusterFile> cf;    // the files the clustering launches see, in row order; cf[c] is file cf_file[c]
+    std::vector<int> cf_file;
+    bool any_single = false;           // a file of one window that takes part: its embedding is its centroid
+};
+
+// After every refusal on the arguments has had its turn: the windows of the files with ok[f] that take part, grouped greedily in order
+// into passes — a pass closes at WLX_SPK_MAX_BATCH windows or when the next one would take it over max_seconds; only windows that take
+// part are counted — and what is known without the device: status, n_clusters (1 for a file with a window that takes part), label 0 / -1
+// and the zero row of every window that takes none. Window i of file f starts at sample item_off[f] + starts[i] of the buffer the passes read.
+static void spk_wave_plan(const wlx_spk* k, SpkWave& wv, const char* ok, const long* item_off, const int64_t* starts, const int64_t* n_samples,
+                          const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, int32_t* n_clusters, float* emb_out) {
+    const int n_files = (int)wv.w0.size() - 1, E = k->spec.embed_dim;
+    wv.row0.assign((size_t)n_files, 0), wv.m_of.assign((size_t)n_files, 0);
+    SpkPlan cur;
+    size_t doff = 0;
+    for (int f = 0; f < n_files; ++f) {
+        wv.row0[f] = (int)wv.win_of.size();
+        for (long i = wv.w0[f]; i < wv.w0[f + 1]; ++i) {
+            const bool out = !ok[f] || n_samples[i] < WLX_SPK_MIN_SAMPLES;
+            status[i] = !ok[f] ? WLX_ERR_STATE : out ? WLX_ERR_TOO_SHORT : WLX_OK;
+            labels[i] = out ? -1 : 0;
+            if (out && emb_out) std::fill(emb_out + (size_t)i * E, emb_out + (size_t)(i + 1) * E, 0.f);
+            if (out) continue;
+            if (cur.m > 0 && (cur.m >= WLX_SPK_MAX_BATCH || cur.total + (long)n_samples[i] > k->max_samples)) {
+                wv.plans.push_back(cur);
+                cur = SpkPlan();
+            }
+            cur.offs[cur.m] = item_off[f] + (long)starts[i], cur.widths[cur.m] = spk_frames((long)n_samples[i]), cur.row[cur.m] = (int)wv.win_of.size();
+            ++cur.m, cur.total += (long)n_samples[i];
+            wv.win_of.push_back(i);
+        }
+        const int m = wv.m_of[f] = (int)wv.win_of.size() - wv.row0[f];
+        n_clusters[f] = m > 0 ? 1 : 0;
+        wv.any_single = wv.any_single || m == 1;
+        if (m >= 2) {
+            wv.cf.push_back(SpkClusterFile{doff, wv.row0[f], m, opts[f].threshold, opts[f].max_clusters});
+            wv.cf_file.push_back(f);
+            doff += (size_t)m * m;
+        }
+    }
+    if (cur.m > 0) wv.plans.push_back(cur);
+}
+
+// The files of `cf` (m >= 2 rows each of k->mn_emb, written by work already on k->st): distance matrices, clustering, centroids and the
+// downloads into the pinned buffers, all enqueued; the caller waits once. dist_out (host, may be null) gets the matrices, packed file by
+// file, before the clustering overwrites them: its copy sits between the two timed intervals.
+static int spk_cluster_enqueue(wlx_spk* k, const char* who, const std::vector<SpkClusterFile>& cf, float* dist_out, bool want_centroids) {
     hipStream_t st = k->st;
-    const int E = k->spec.embed_dim;
+    const int E = k->spec.embed_dim, C = (int)cf.size();
+    const size_t rows = (size_t)cf.back().row0 + cf.back().m, cells = cf.back().doff + (size_t)cf.back().m * cf.back().m;
     CK(hipEventRecord(k->ev_cl[0], st));
-    if (!launch_spk_affinity(k->cl_emb, m, E, k->cl_dist, st)) return set_error(WLX_ERR_ARG, "the distance matrix refused %d x %d", m, E);
+    if (!launch_spk_affinity(k->mn_emb, cf.data(), C, E, k->mn_dist, st)) return set_error(WLX_ERR_ARG, "%s: the distance matrices refused %d file(s)", who, C);
     CK(hipEventRecord(k->ev_cl[1], st));
-    if (dist_out) CK(hipMemcpyAsync(dist_out, k->cl_dist, (size_t)m * m * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (dist_out) CK(hipMemcpyAsync(dist_out, k->mn_dist, cells * sizeof(float), hipMemcpyDeviceToHost, st));
     CK(hipEventRecord(k->ev_cl[2], st));
-    if (!launch_spk_ahc(k->cl_dist, m, o->threshold, o->max_clusters, k->cl_merges, k->cl_heights, k->cl_labels, k->cl_counts, st))
-        return set_error(WLX_ERR_ARG, "the clustering refused %d rows", m);
+    if (!launch_spk_ahc(k->mn_dist, cf.data(), C, k->mn_merges, k->mn_heights, k->mn_labels, k->mn_counts, st))
+        return set_error(WLX_ERR_ARG, "%s: the clustering refused %d file(s)", who, C);
     CK(hipEventRecord(k->ev_cl[3], st));
     if (want_centroids) {
-        if (!launch_spk_centroids(k->cl_emb, k->cl_labels, k->cl_counts, m, E, k->cl_cent, st))
-            return set_error(WLX_ERR_ARG, "the centroids refused %d x %d", m, E);
-        CK(hipMemcpyAsync(k->h_cl_cent, k->cl_cent, (size_t)m * E * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (!launch_spk_centroids(k->mn_emb, k->mn_labels, k->mn_counts, cf.data(), C, E, k->mn_cent, st))
+            return set_error(WLX_ERR_ARG, "%s: the centroids refused %d file(s)", who, C);
+        CK(hipMemcpyAsync(k->h_mn_cent, k->mn_cent, rows * E * sizeof(float), hipMemcpyDeviceToHost, st));
     }
     CK(hipGetLastError());
-    CK(hipMemcpyAsync(k->h_cl_int, k->cl_labels, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(k->h_cl_int + WLX_SPK_CLUSTER_MAX, k->cl_counts, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(k->h_mn_int, k->mn_labels, rows * sizeof(int), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(k->h_mn_int + WLX_SPK_MANY_MAX_ROWS, k->mn_counts, (size_t)2 * C * sizeof(int), hipMemcpyDeviceToHost, st));
     return WLX_OK;
 }
 
-// after the wait: K, the first K centroids to the caller, the times
-static int spk_cluster_collect(wlx_spk* k, int m, float* centroids, int32_t* n_clusters) {
-    const int K = k->h_cl_int[WLX_SPK_CLUSTER_MAX + 1];
-    if (K < 1 || K > m) return set_error(WLX_ERR_HIP, "the clustering of %d rows reported %d clusters", m, K);
-    *n_clusters = K;
-    if (centroids) std::copy(k->h_cl_cent, k->h_cl_cent + (size_t)K * k->spec.embed_dim, centroids);
+// after the wait: per clustered file K, its first K centroids and the labels of its rows dealt to the caller's windows; the times
+static int spk_cluster_collect(wlx_spk* k, const char* who, const SpkWave& wv, int32_t* labels, float* centroids, int32_t* n_clusters) {
+    const int E = k->spec.embed_dim;
+    for (size_t c = 0; c < wv.cf.size(); ++c) {
+        const SpkClusterFile& cf = wv.cf[c];
+        const int f = wv.cf_file[c], K = k->h_mn_int[WLX_SPK_MANY_MAX_ROWS + 2 * c + 1];
+        if (K < 1 || K > cf.m) return set_error(WLX_ERR_HIP, "%s: the clustering of file %d (%d rows) reported %d clusters", who, f, cf.m, K);
+        n_clusters[f] = K;
+        if (centroids) std::copy(k->h_mn_cent + (size_t)cf.row0 * E, k->h_mn_cent + (size_t)(cf.row0 + K) * E, centroids + (size_t)wv.w0[f] * E);
+        for (int a = cf.row0; a < cf.row0 + cf.m; ++a) labels[wv.win_of[a]] = k->h_mn_int[a];
+    }
     CK(hipEventElapsedTime(&k->aff_ms, k->ev_cl[0], k->ev_cl[1]));
     CK(hipEventElapsedTime(&k->ahc_ms, k->ev_cl[2], k->ev_cl[3]));
     k->cl_timed = true;
     return WLX_OK;
 }
 
+// host rows: one file whose windows are its rows, uploaded into the table
 extern "C" int32_t wlx_spk_cluster(wlx_spk* k, const float* emb, int32_t n, int32_t dim, const wlx_spk_cluster_opts* opts, int32_t* labels,
                                    float* centroids, int32_t* n_clusters) {
-    if (!k || !emb || !opts || !labels || !n_clusters) return set_error(WLX_ERR_ARG, "wlx_spk_cluster: null argument");
-    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "wlx_spk_cluster: %d rows outside 1..%d", n, WLX_SPK_CLUSTER_MAX);
-    if (dim != k->spec.embed_dim) return set_error(WLX_ERR_ARG, "wlx_spk_cluster: dim %d is not the engine's %d", dim, k->spec.embed_dim);
-    CKR(spk_cluster_opts_ok("wlx_spk_cluster", opts));
+    const char* who = "wlx_spk_cluster";
+    if (!k || !emb || !opts || !labels || !n_clusters) return set_error(WLX_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "%s: %d rows outside 1..%d", who, n, WLX_SPK_CLUSTER_MAX);
+    if (dim != k->spec.embed_dim) return set_error(WLX_ERR_ARG, "%s: dim %d is not the engine's %d", who, dim, k->spec.embed_dim);
+    CKR(spk_cluster_opts_ok(who, opts));
     if (n == 1) {                     // one row is its own cluster and its own centroid
         labels[0] = 0, *n_clusters = 1;
         if (centroids) std::copy(emb, emb + dim, centroids);
         return WLX_OK;
     }
+    SpkWave wv;
+    wv.w0 = {0, n};
+    for (int a = 0; a < n; ++a) wv.win_of.push_back(a);
+    wv.cf.push_back(SpkClusterFile{0, 0, n, opts->threshold, opts->max_clusters});
+    wv.cf_file.push_back(0);
     std::lock_guard<std::mutex> g(k->mu);
     CK(hipSetDevice(k->device));
-    CKR(spk_cluster_reserve(k));
-    CK(hipMemcpyAsync(k->cl_emb, emb, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice, k->st));
-    CKR(spk_cluster_enqueue(k, n, opts, nullptr, centroids != nullptr));
+    CKR(spk_many_reserve(k));
+    CK(hipMemcpyAsync(k->mn_emb, emb, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice, k->st));
+    CKR(spk_cluster_enqueue(k, who, wv.cf, nullptr, centroids != nullptr));
     CK(hipStreamSynchronize(k->st));
-    CKR(spk_cluster_collect(k, n, centroids, n_clusters));
-    std::copy(k->h_cl_int, k->h_cl_int + n, labels);
-    return WLX_OK;
+    return spk_cluster_collect(k, who, wv, labels, centroids, n_clusters);
 }
 
-// A file's windows: grouped as plan_embed_groups (diarization.py) groups the ranges of wlx_spk_embed_pcm_batch calls — greedily in order,
-// a group closes at WLX_SPK_MAX_BATCH windows or when the next one would take it over max_seconds, short windows counted — every group
-// one ragged pass whose head writes its rows straight into the table, then the clustering on that table; ONE wait.
+// The device's part of a planned wave with a window that takes part: every pass a ragged batch whose head writes its rows straight into
+// the table, then the clustering on that table; ONE wait, then the rows, centroids and labels dealt to the caller's windows. `src` is the
+// buffer the plan's offsets count from, inside the lease L.
+static int spk_wave_run(wlx_spk* k, const char* who, PcmLease& L, const float* src, const SpkWave& wv, int32_t* labels, int32_t* n_clusters,
+                        float* emb_out, float* dist_out, float* centroids) {
+    const int M = (int)wv.win_of.size(), E = k->spec.embed_dim, n_files = (int)wv.m_of.size();
+    std::lock_guard<std::mutex> g(k->mu);
+    CK(hipSetDevice(k->device));
+    CKR(spk_many_reserve(k));
+    CKR(L.order(k->st));
+    for (const SpkPlan& pl : wv.plans) CKR(spk_enqueue_batch(k, src, pl, k->mn_emb + (size_t)pl.row[0] * E));
+    if (emb_out || (centroids && wv.any_single)) CK(hipMemcpyAsync(k->h_mn_emb, k->mn_emb, (size_t)M * E * sizeof(float), hipMemcpyDeviceToHost, k->st));
+    if (!wv.cf.empty()) CKR(spk_cluster_enqueue(k, who, wv.cf, dist_out, centroids != nullptr));
+    CK(hipStreamSynchronize(k->st));
+    CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));          // (of the last pass)
+    CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
+    k->timed = true;
+    if (emb_out)
+        for (int a = 0; a < M; ++a) std::copy(k->h_mn_emb + (size_t)a * E, k->h_mn_emb + (size_t)(a + 1) * E, emb_out + (size_t)wv.win_of[a] * E);
+    if (centroids)                    // one window is its own cluster, its embedding the centroid
+        for (int f = 0; f < n_files; ++f)
+            if (wv.m_of[f] == 1) std::copy(k->h_mn_emb + (size_t)wv.row0[f] * E, k->h_mn_emb + (size_t)(wv.row0[f] + 1) * E, centroids + (size_t)wv.w0[f] * E);
+    if (wv.cf.empty()) return WLX_OK;
+    return spk_cluster_collect(k, who, wv, labels, centroids, n_clusters);
+}
+
+// A whole file: a wave of one behind refusals of its own — an item with nothing resident or a window past its end refuses the call.
 extern "C" int32_t wlx_spk_diarize_pcm(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts, const int64_t* n_samples,
                                        int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, float* emb_out,
                                        float* dist_out, float* centroids, int32_t* n_clusters) {
@@ -514,84 +593,20 @@ extern "C" int32_t wlx_spk_diarize_pcm(wlx_spk* k, wlx_engine* e, int32_t slot, 
     CKR(L.item(who, item));
     if (L.resident <= 0 || !L.buf) return set_error(WLX_ERR_STATE, "%s: item %d: no PCM resident", who, item);
     for (int i = 0; i < n; ++i) CKR(L.range(who, starts[i], n_samples[i]));
-    // the passes: plans[g] holds the windows of group g that take part; row_of[a] = the window behind row a of the table
-    std::vector<SpkPlan> plans;
-    std::vector<int> row_of;
-    {
-        SpkPlan cur;
-        int count = 0;
-        for (int i = 0; i < n; ++i) {
-            if (count > 0 && (count >= WLX_SPK_MAX_BATCH || cur.total + (long)n_samples[i] > k->max_samples)) {
-                if (cur.m > 0) plans.push_back(cur);
-                cur = SpkPlan(), count = 0;
-            }
-            if (n_samples[i] >= WLX_SPK_MIN_SAMPLES) {
-                cur.offs[cur.m] = (long)starts[i], cur.widths[cur.m] = spk_frames((long)n_samples[i]), cur.row[cur.m] = (int)row_of.size();
-                ++cur.m;
-                row_of.push_back(i);
-            }
-            cur.total += (long)n_samples[i], ++count;
-        }
-        if (cur.m > 0) plans.push_back(cur);
-    }
-    const int m = (int)row_of.size(), E = k->spec.embed_dim;
-    // every refusal on the arguments has had its turn: what is known without the device
-    for (int i = 0; i < n; ++i) {
-        const bool too_short = n_samples[i] < WLX_SPK_MIN_SAMPLES;
-        status[i] = too_short ? WLX_ERR_TOO_SHORT : WLX_OK;
-        labels[i] = too_short ? -1 : 0;
-        if (too_short && emb_out) std::fill(emb_out + (size_t)i * E, emb_out + (size_t)(i + 1) * E, 0.f);
-    }
-    *n_clusters = m > 0 ? 1 : 0;
-    if (m == 0) return WLX_OK;
-    std::lock_guard<std::mutex> g(k->mu);
-    CK(hipSetDevice(k->device));
-    CKR(spk_cluster_reserve(k));
-    CKR(L.order(k->st));
-    for (const SpkPlan& pl : plans) CKR(spk_enqueue_batch(k, L.buf, pl, k->cl_emb + (size_t)pl.row[0] * E));
-    const bool want_rows = emb_out || (m == 1 && centroids);
-    if (want_rows) CK(hipMemcpyAsync(k->h_cl_emb, k->cl_emb, (size_t)m * E * sizeof(float), hipMemcpyDeviceToHost, k->st));
-    if (m >= 2) CKR(spk_cluster_enqueue(k, m, opts, dist_out, centroids != nullptr));
-    CK(hipStreamSynchronize(k->st));
-    CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));          // (of the last pass)
-    CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
-    k->timed = true;
-    if (emb_out)
-        for (int a = 0; a < m; ++a) std::copy(k->h_cl_emb + (size_t)a * E, k->h_cl_emb + (size_t)(a + 1) * E, emb_out + (size_t)row_of[a] * E);
-    if (m == 1) {                     // one window is its own cluster, its embedding the centroid
-        if (dist_out) dist_out[0] = 0.f;
-        if (centroids) std::copy(k->h_cl_emb, k->h_cl_emb + E, centroids);
-        return WLX_OK;
-    }
-    CKR(spk_cluster_collect(k, m, centroids, n_clusters));
-    for (int a = 0; a < m; ++a) labels[row_of[a]] = k->h_cl_int[a];
+    SpkWave wv;
+    wv.w0 = {0, n};
+    const char ok = 1;
+    const long item_off = 0;          // (the passes read the item's own buffer)
+    spk_wave_plan(k, wv, &ok, &item_off, starts, n_samples, opts, labels, status, n_clusters, emb_out);
+    if (wv.win_of.empty()) return WLX_OK;
+    CKR(spk_wave_run(k, who, L, L.buf, wv, labels, n_clusters, emb_out, dist_out, centroids));
+    if (dist_out && wv.m_of[0] == 1) dist_out[0] = 0.f;
     return WLX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ a wave of files (wlx_spk_diarize_many)
-// the buffers of a many-call, made by the first one and apart from the single-file cl_* buffers. k->mu is held.
-static int spk_many_reserve(wlx_spk* k) {
-    if (k->mn_ready) return WLX_OK;
-    const size_t R = WLX_SPK_MANY_MAX_ROWS, F = WLX_SPK_MANY_MAX_FILES, E = (size_t)k->spec.embed_dim;
-    if (!k->mn_emb) CKR(dalloc(k->pool, &k->mn_emb, R * E, false));
-    if (!k->mn_cent) CKR(dalloc(k->pool, &k->mn_cent, R * E, false));
-    if (!k->mn_dist) CKR(dalloc(k->pool, &k->mn_dist, (size_t)WLX_SPK_MANY_MAX_CELLS, false));
-    if (!k->mn_heights) CKR(dalloc(k->pool, &k->mn_heights, R, false));
-    if (!k->mn_merges) CKR(dalloc(k->pool, &k->mn_merges, 2 * R, false));
-    if (!k->mn_labels) CKR(dalloc(k->pool, &k->mn_labels, R, false));
-    if (!k->mn_counts) CKR(dalloc(k->pool, &k->mn_counts, 2 * F, false));
-    if (!k->h_mn_emb) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_emb), R * E * sizeof(float), hipHostMallocDefault));
-    if (!k->h_mn_cent) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_cent), R * E * sizeof(float), hipHostMallocDefault));
-    if (!k->h_mn_int) CK(hipHostMalloc(reinterpret_cast<void**>(&k->h_mn_int), (R + 2 * F) * sizeof(int), hipHostMallocDefault));
-    for (hipEvent_t& e : k->ev_mn)
-        if (!e) CK(hipEventCreate(&e));
-    k->mn_ready = true;
-    return WLX_OK;
-}
-
 // The files of a wave lie in the items of ONE slot, rows of one allocation: the front end addresses a window as an offset from item 0
-// (item * pcm_cap + start), so a pass mixes the windows of different files as it mixes those of one. Rows of the table are the windows
-// that take part, file by file; file f owns rows [row0_f, row0_f + m_f) and, with m_f >= 2, a matrix and a workgroup of the clustering.
+// (item * pcm_cap + start), so a pass mixes the windows of different files as it mixes those of one.
 extern "C" int32_t wlx_spk_diarize_many(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t n_files, const int32_t* items, const int32_t* n_windows,
                                         const int64_t* starts, const int64_t* n_samples, const wlx_spk_cluster_opts* opts, int32_t* labels,
                                         int32_t* status, int32_t* file_status, int32_t* n_clusters, float* emb_out, float* centroids) {
@@ -599,7 +614,9 @@ extern "C" int32_t wlx_spk_diarize_many(wlx_spk* k, wlx_engine* e, int32_t slot,
     if (!k || !e || !items || !n_windows || !starts || !n_samples || !opts || !labels || !status || !file_status || !n_clusters)
         return set_error(WLX_ERR_ARG, "%s: null argument", who);
     if (n_files < 1 || n_files > WLX_SPK_MANY_MAX_FILES) return set_error(WLX_ERR_ARG, "%s: %d files outside 1..%d", who, n_files, WLX_SPK_MANY_MAX_FILES);
-    std::vector<long> w0((size_t)n_files + 1, 0);          // first window of file f in the packed arrays
+    SpkWave wv;
+    std::vector<long>& w0 = wv.w0;
+    w0.assign((size_t)n_files + 1, 0);
     for (int f = 0; f < n_files; ++f) {
         if (n_windows[f] < 0 || n_windows[f] > WLX_SPK_CLUSTER_MAX)
             return set_error(WLX_ERR_ARG, "%s: file %d: %d windows outside 0..%d", who, f, n_windows[f], WLX_SPK_CLUSTER_MAX);
@@ -637,97 +654,11 @@ extern "C" int32_t wlx_spk_diarize_many(wlx_spk* k, wlx_engine* e, int32_t slot,
         bool good = L.resident > 0 && L.buf;
         for (long i = w0[f]; good && i < w0[f + 1]; ++i) good = starts[i] <= L.resident - n_samples[i];
         ok[f] = good, item_off[f] = good ? (long)(L.buf - base) : 0;
+        file_status[f] = good ? WLX_OK : WLX_ERR_STATE;          // (every refusal on the arguments has had its turn)
     }
-    // the passes over the windows that take part; win_of[a] = the packed window behind row a of the table
-    std::vector<SpkPlan> plans;
-    std::vector<long> win_of;
-    std::vector<int> row0((size_t)n_files, 0), m_of((size_t)n_files, 0);
-    std::vector<SpkClusterFile> cf;          // the files the clustering launches see (m >= 2), cf_file[c] = which
-    std::vector<int> cf_file;
-    {
-        SpkPlan cur;
-        size_t doff = 0;
-        for (int f = 0; f < n_files; ++f) {
-            if (!ok[f]) continue;
-            row0[f] = (int)win_of.size();
-            for (long i = w0[f]; i < w0[f + 1]; ++i) {
-                if (n_samples[i] < WLX_SPK_MIN_SAMPLES) continue;
-                if (cur.m > 0 && (cur.m >= WLX_SPK_MAX_BATCH || cur.total + (long)n_samples[i] > k->max_samples)) {
-                    plans.push_back(cur);
-                    cur = SpkPlan();
-                }
-                cur.offs[cur.m] = item_off[f] + (long)starts[i], cur.widths[cur.m] = spk_frames((long)n_samples[i]), cur.row[cur.m] = (int)win_of.size();
-                ++cur.m, cur.total += (long)n_samples[i];
-                win_of.push_back(i);
-            }
-            const int m = m_of[f] = (int)win_of.size() - row0[f];
-            if (m >= 2) {
-                cf.push_back(SpkClusterFile{doff, row0[f], m, opts[f].threshold, opts[f].max_clusters});
-                cf_file.push_back(f);
-                doff += (size_t)m * m;
-            }
-        }
-        if (cur.m > 0) plans.push_back(cur);
-    }
-    const int M = (int)win_of.size(), E = k->spec.embed_dim, C = (int)cf.size();
-    // every refusal on the arguments has had its turn: what is known without the device
-    bool any_single = false;
-    for (int f = 0; f < n_files; ++f) {
-        file_status[f] = ok[f] ? WLX_OK : WLX_ERR_STATE;
-        n_clusters[f] = ok[f] && m_of[f] > 0 ? 1 : 0;
-        any_single = any_single || (ok[f] && m_of[f] == 1);
-        for (long i = w0[f]; i < w0[f + 1]; ++i) {
-            const bool out = !ok[f] || n_samples[i] < WLX_SPK_MIN_SAMPLES;
-            status[i] = !ok[f] ? WLX_ERR_STATE : out ? WLX_ERR_TOO_SHORT : WLX_OK;
-            labels[i] = out ? -1 : 0;
-            if (out && emb_out) std::fill(emb_out + (size_t)i * E, emb_out + (size_t)(i + 1) * E, 0.f);
-        }
-    }
-    if (M == 0) return WLX_OK;
-    std::lock_guard<std::mutex> g(k->mu);
-    CK(hipSetDevice(k->device));
-    CKR(spk_many_reserve(k));
-    CKR(L.order(k->st));
-    hipStream_t st = k->st;
-    for (const SpkPlan& pl : plans) CKR(spk_enqueue_batch(k, base, pl, k->mn_emb + (size_t)pl.row[0] * E));
-    if (emb_out || (centroids && any_single)) CK(hipMemcpyAsync(k->h_mn_emb, k->mn_emb, (size_t)M * E * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (C > 0) {
-        CK(hipEventRecord(k->ev_mn[0], st));
-        if (!launch_spk_affinity_many(k->mn_emb, cf.data(), C, E, k->mn_dist, st)) return set_error(WLX_ERR_ARG, "%s: the distance matrices refused %d files", who, C);
-        CK(hipEventRecord(k->ev_mn[1], st));
-        if (!launch_spk_ahc_many(k->mn_dist, cf.data(), C, k->mn_merges, k->mn_heights, k->mn_labels, k->mn_counts, st))
-            return set_error(WLX_ERR_ARG, "%s: the clustering refused %d files", who, C);
-        CK(hipEventRecord(k->ev_mn[2], st));
-        if (centroids) {
-            if (!launch_spk_centroids_many(k->mn_emb, k->mn_labels, k->mn_counts, cf.data(), C, E, k->mn_cent, st))
-                return set_error(WLX_ERR_ARG, "%s: the centroids refused %d files", who, C);
-            CK(hipMemcpyAsync(k->h_mn_cent, k->mn_cent, (size_t)(cf.back().row0 + cf.back().m) * E * sizeof(float), hipMemcpyDeviceToHost, st));
-        }
-        CK(hipGetLastError());
-        CK(hipMemcpyAsync(k->h_mn_int, k->mn_labels, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, st));
-        CK(hipMemcpyAsync(k->h_mn_int + WLX_SPK_MANY_MAX_ROWS, k->mn_counts, (size_t)2 * C * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    CK(hipStreamSynchronize(st));
-    CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));          // (of the last pass)
-    CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
-    k->timed = true;
-    if (emb_out)
-        for (int a = 0; a < M; ++a) std::copy(k->h_mn_emb + (size_t)a * E, k->h_mn_emb + (size_t)(a + 1) * E, emb_out + (size_t)win_of[a] * E);
-    if (centroids)                    // one window is its own cluster, its embedding the centroid
-        for (int f = 0; f < n_files; ++f)
-            if (ok[f] && m_of[f] == 1) std::copy(k->h_mn_emb + (size_t)row0[f] * E, k->h_mn_emb + (size_t)(row0[f] + 1) * E, centroids + (size_t)w0[f] * E);
-    if (C == 0) return WLX_OK;
-    for (int c = 0; c < C; ++c) {
-        const int f = cf_file[c], K = k->h_mn_int[WLX_SPK_MANY_MAX_ROWS + 2 * c + 1];
-        if (K < 1 || K > cf[c].m) return set_error(WLX_ERR_HIP, "%s: the clustering of file %d (%d rows) reported %d clusters", who, f, cf[c].m, K);
-        n_clusters[f] = K;
-        if (centroids) std::copy(k->h_mn_cent + (size_t)cf[c].row0 * E, k->h_mn_cent + (size_t)(cf[c].row0 + K) * E, centroids + (size_t)w0[f] * E);
-        for (int a = cf[c].row0; a < cf[c].row0 + cf[c].m; ++a) labels[win_of[a]] = k->h_mn_int[a];
-    }
-    CK(hipEventElapsedTime(&k->aff_ms, k->ev_mn[0], k->ev_mn[1]));
-    CK(hipEventElapsedTime(&k->ahc_ms, k->ev_mn[1], k->ev_mn[2]));
-    k->cl_timed = true;
-    return WLX_OK;
+    spk_wave_plan(k, wv, ok.data(), item_off.data(), starts, n_samples, opts, labels, status, n_clusters, emb_out);
+    if (wv.win_of.empty()) return WLX_OK;
+    return spk_wave_run(k, who, L, base, wv, labels, n_clusters, emb_out, nullptr, centroids);
 }
 
 extern "C" int32_t wlx_spk_debug_cluster_timings(wlx_spk* k, float* affinity_ms, float* ahc_ms) {
@@ -931,50 +862,8 @@ extern "C" int32_t wlx_spk_debug_head(int32_t device, const float* pooled, const
     return S.finish();
 }
 
-// ---- the clustering kernels (spk_cluster.hip), one launch each
-extern "C" int32_t wlx_spk_debug_affinity(int32_t device, const float* X, int32_t n, int32_t dim, float* dist_out) {
-    if (!X || !dist_out) return set_error(WLX_ERR_ARG, "null argument");
-    if (n < 1 || n > WLX_SPK_CLUSTER_MAX || dim < 1 || dim > 1024)
-        return set_error(WLX_ERR_ARG, "n %d / dim %d: n in 1..%d, dim in 1..1024", n, dim, WLX_SPK_CLUSTER_MAX);
-    HookScope S;
-    CKR(S.begin(device));
-    float *dX, *dD;
-    CKR(S.upload(&dX, X, (size_t)n * dim));
-    CKR(S.alloc(&dD, (size_t)n * n));
-    if (!launch_spk_affinity(dX, n, dim, dD, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
-    CKR(S.download(dist_out, dD, (size_t)n * n));
-    return S.finish();
-}
-
-extern "C" int32_t wlx_spk_debug_ahc(int32_t device, const float* dist, int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels,
-                                     int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
-    if (!dist || !opts || !labels || !merges || !heights || !n_merges || !n_clusters) return set_error(WLX_ERR_ARG, "null argument");
-    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "n %d outside 1..%d", n, WLX_SPK_CLUSTER_MAX);
-    CKR(spk_cluster_opts_ok("wlx_spk_debug_ahc", opts));
-    int counts[2] = {0, 0};
-    HookScope S;
-    CKR(S.begin(device));
-    float *dD, *dH;
-    int *dM, *dL, *dC;
-    const size_t nm = (size_t)std::max(n - 1, 1);                  // (n = 1 merges nothing: one row of room, never written)
-    CKR(S.upload(&dD, dist, (size_t)n * n));
-    CKR(S.upload(&dH, n > 1 ? heights : nullptr, nm));
-    CKR(S.upload(&dM, n > 1 ? merges : nullptr, 2 * nm));
-    CKR(S.alloc(&dL, (size_t)n));
-    CKR(S.alloc(&dC, (size_t)2));
-    if (!launch_spk_ahc(dD, n, opts->threshold, opts->max_clusters, dM, dH, dL, dC, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
-    CKR(S.download(labels, dL, (size_t)n));
-    if (n > 1) {
-        CKR(S.download(heights, dH, nm));
-        CKR(S.download(merges, dM, 2 * nm));
-    }
-    CKR(S.download(counts, dC, (size_t)2));
-    CKR(S.finish());
-    *n_merges = counts[0], *n_clusters = counts[1];
-    return WLX_OK;
-}
-
-// ---- their many-forms: files packed back to back, file f at row0 = ns[0] + .. + ns[f-1], its matrix at ns[0]^2 + .. + ns[f-1]^2
+// ---- the clustering kernels (spk_cluster.hip), one launch each over files packed back to back: file f at row0 = ns[0] + .. + ns[f-1], its
+// matrix at ns[0]^2 + .. + ns[f-1]^2. wlx_spk_debug_affinity / _ahc are the case of one file behind refusals of their own.
 static int spk_debug_many_table(const int32_t* ns, int n_files, const wlx_spk_cluster_opts* opts, std::vector<SpkClusterFile>& files, size_t& rows,
                                 size_t& cells) {
     if (n_files < 1 || n_files > WLX_SPK_MANY_MAX_FILES) return set_error(WLX_ERR_ARG, "%d files outside 1..%d", n_files, WLX_SPK_MANY_MAX_FILES);
@@ -1000,34 +889,60 @@ extern "C" int32_t wlx_spk_debug_affinity_many(int32_t device, const float* X, i
     float *dX, *dD;
     CKR(S.upload(&dX, X, rows * dim));
     CKR(S.alloc(&dD, cells));
-    if (!launch_spk_affinity_many(dX, files.data(), n_files, dim, dD, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    if (!launch_spk_affinity(dX, files.data(), n_files, dim, dD, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
     CKR(S.download(dist_out, dD, cells));
     return S.finish();
 }
 
-extern "C" int32_t wlx_spk_debug_ahc_many(int32_t device, const float* dist, int32_t n_files, const int32_t* ns, const wlx_spk_cluster_opts* opts,
-                                          int32_t* labels, int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
-    if (!dist || !ns || !opts || !labels || !merges || !heights || !n_merges || !n_clusters) return set_error(WLX_ERR_ARG, "null argument");
+extern "C" int32_t wlx_spk_debug_affinity(int32_t device, const float* X, int32_t n, int32_t dim, float* dist_out) {
+    if (!X || !dist_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_CLUSTER_MAX || dim < 1 || dim > 1024)
+        return set_error(WLX_ERR_ARG, "n %d / dim %d: n in 1..%d, dim in 1..1024", n, dim, WLX_SPK_CLUSTER_MAX);
+    return wlx_spk_debug_affinity_many(device, X, 1, &n, dim, dist_out);
+}
+
+// The caller's heights and merges hold rows - `less` entries: copied in and out, so what no merge writes comes back unchanged
+static int spk_debug_ahc_run(const char* who, int device, const float* dist, const int32_t* ns, int n_files, const wlx_spk_cluster_opts* opts,
+                             size_t less, int32_t* labels, int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
     std::vector<SpkClusterFile> files;
     size_t rows, cells;
     CKR(spk_debug_many_table(ns, n_files, opts, files, rows, cells));
-    for (int f = 0; f < n_files; ++f) CKR(spk_cluster_opts_ok("wlx_spk_debug_ahc_many", &opts[f]));
+    for (int f = 0; f < n_files; ++f) CKR(spk_cluster_opts_ok(who, &opts[f]));
+    const size_t nh = rows - less;
     std::vector<int> counts((size_t)2 * n_files, 0);          // (declared before S: it outlives the stream's copies on every return path)
     HookScope S;
     CKR(S.begin(device));
     float *dD, *dH;
     int *dM, *dL, *dC;
+    const size_t room = std::max(nh, (size_t)1);              // (one row merges nothing: one entry of room, never written)
     CKR(S.upload(&dD, dist, cells));
-    CKR(S.upload(&dH, heights, rows));                        // (copied in and out: what no merge writes comes back unchanged)
-    CKR(S.upload(&dM, merges, 2 * rows));
+    CKR(S.upload(&dH, nh ? heights : nullptr, room));
+    CKR(S.upload(&dM, nh ? merges : nullptr, 2 * room));
     CKR(S.alloc(&dL, rows));
     CKR(S.alloc(&dC, (size_t)2 * n_files));
-    if (!launch_spk_ahc_many(dD, files.data(), n_files, dM, dH, dL, dC, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
+    if (!launch_spk_ahc(dD, files.data(), n_files, dM, dH, dL, dC, S.st)) return set_error(WLX_ERR_ARG, "the launcher refused the shape");
     CKR(S.download(labels, dL, rows));
-    CKR(S.download(heights, dH, rows));
-    CKR(S.download(merges, dM, 2 * rows));
+    if (nh) {
+        CKR(S.download(heights, dH, nh));
+        CKR(S.download(merges, dM, 2 * nh));
+    }
     CKR(S.download(counts.data(), dC, (size_t)2 * n_files));
     CKR(S.finish());
     for (int f = 0; f < n_files; ++f) n_merges[f] = counts[2 * f], n_clusters[f] = counts[2 * f + 1];
     return WLX_OK;
+}
+
+// heights [n - 1] and merges [n - 1][2]: one file's merges start at row 0 and end inside them
+extern "C" int32_t wlx_spk_debug_ahc(int32_t device, const float* dist, int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels,
+                                     int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
+    if (!dist || !opts || !labels || !merges || !heights || !n_merges || !n_clusters) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "n %d outside 1..%d", n, WLX_SPK_CLUSTER_MAX);
+    return spk_debug_ahc_run("wlx_spk_debug_ahc", device, dist, &n, 1, opts, 1, labels, merges, heights, n_merges, n_clusters);
+}
+
+// heights [rows] and merges [rows][2], file f's at its row0
+extern "C" int32_t wlx_spk_debug_ahc_many(int32_t device, const float* dist, int32_t n_files, const int32_t* ns, const wlx_spk_cluster_opts* opts,
+                                          int32_t* labels, int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
+    if (!dist || !ns || !opts || !labels || !merges || !heights || !n_merges || !n_clusters) return set_error(WLX_ERR_ARG, "null argument");
+    return spk_debug_ahc_run("wlx_spk_debug_ahc_many", device, dist, ns, n_files, opts, 0, labels, merges, heights, n_merges, n_clusters);
 }
