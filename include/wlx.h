@@ -420,7 +420,8 @@ int32_t wlx_bias_set(wlx_engine* e, int32_t slot, int32_t n_nodes, const int32_t
 int32_t wlx_bias_clear(wlx_engine* e, int32_t slot);
 
 /* Keyword boosting per item — a set of tables on the slot, one selected per item of a decode group (wlx_bias_set_items, wlx_bias_select;
- * DESIGN.md §27) — is declared in wlx_bias_items.h, which this header includes at its end. */
+ * DESIGN.md §27) — is declared in wlx_bias_items.h, which this header includes at its end. So is grammar-constrained decoding — a closed
+ * phrase list as a DFA on the slot, whose launch masks where these add (wlx_grammar_set, wlx_grammar_clear) — in wlx_grammar.h. */
 
 /* One decoder step on [sot]; softmax restricted to `lang_ids`; probs_out[batch][n_lang]. */
 int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot,
@@ -1164,6 +1165,7 @@ int32_t wlx_vad_debug_lstm(wlx_vad* v, const float* gx, const int32_t* T, int32_
 int32_t wlx_vad_debug_out(wlx_vad* v, const float* hs, int32_t T, float* probs, int64_t cap_windows);
 
 #include "wlx_bias_items.h"
+#include "wlx_grammar.h"
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "dec_bias.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "put_many.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "dec_bias.hip", "dec_grammar.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "put_many.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
@@ -46,6 +46,8 @@ EXPORTS = [
 ]
 # the per-item part of keyword boosting, declared in include/wlx_bias_items.h (which wlx.h includes): EXPORTS is wlx.h's own list
 EXPORTS_BIAS_ITEMS = ["wlx_bias_set_items", "wlx_bias_select", "wlx_debug_bias_apply_items"]
+# grammar-constrained decoding, declared in include/wlx_grammar.h (which wlx.h includes)
+EXPORTS_GRAMMAR = ["wlx_grammar_set", "wlx_grammar_clear", "wlx_debug_grammar_apply"]
 
 
 # MFMA accumulators in VGPRs (gfx950 has ONE register file; hipcc's default puts C/D in its AGPR half): every VALU touch of
@@ -152,6 +154,8 @@ BIAS_MAX_NODES, BIAS_MAX_EDGES, BIAS_MAX_TOKENS = 4096, 16384, 1024   # wlx.h WL
 # wlx_bias_items.h WLX_BIAS_SET_MAX_*: tables of one set (wlx_bias_set_items) and the caps of its pool; WLX_BIAS_EDGE_SHARED: the flag bit in edge_next
 BIAS_SET_MAX_TABLES, BIAS_SET_MAX_NODES, BIAS_SET_MAX_EDGES, BIAS_SET_MAX_TOKENS = 64, 16384, 65536, 4096
 BIAS_EDGE_SHARED = 0x40000000
+GRAMMAR_MAX_STATES, GRAMMAR_MAX_EDGES = 4096, 16384      # wlx_grammar.h WLX_GRAMMAR_MAX_*: the caps of a grammar table (wlx_grammar_set)
+DEBUG_GUARD = 64        # wlx.h WLX_DEBUG_GUARD: words a debug hook's output carries past what the kernel owns
 MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
 PUT_PCM, PUT_FRAMES, PUT_FLAC, PUT_WAV = 0, 1, 2, 3   # wlx.h WLX_PUT_*: the kinds of a wlx_put_entry
@@ -330,7 +334,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
     except OSError as e:  # e.g. libamdhip64 missing
         raise WlxError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in EXPORTS if not hasattr(lib, s)]
+    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR if not hasattr(lib, s)]
     if missing:
         raise WlxError(f"libwlx.so lacks symbols {missing}")
     i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p
@@ -473,6 +477,9 @@ def load() -> C.CDLL:
                                                i32p, i32p, i32p, i16p, i16p]
     lib.wlx_debug_bias_apply.argtypes = [i32, i32, i32, i32, i32p, i32p, i32p, C.c_float, i32, i32p, f32p, f32p, i32, i64, i32p, i32p, i32p, i32, i32p,
                                          i16p, i16p]
+    lib.wlx_grammar_set.argtypes = [vp, i32, i32, i32, i32p, i32p, i32p, i32p]
+    lib.wlx_grammar_clear.argtypes = [vp, i32]
+    lib.wlx_debug_grammar_apply.argtypes = [i32, i32, i32, i32, i32p, i32p, i32p, i32p, f32p, i32, i64, i32p, i32p, i32p, i32, i32p, i16p, i16p]
     lib.wlx_debug_token_prob.argtypes = [i32, f32p, i64, i32, i32, i32, f32p]
     lib.wlx_debug_token_prob_rows.argtypes = [i32, f32p, i64, i32, i32, i32p, f32p]
     lib.wlx_debug_lang_probs.argtypes = [i32, f32p, i64, i32, i32p, i32, f32p]
@@ -482,7 +489,7 @@ def load() -> C.CDLL:
     lib.wlx_vad_debug_frontend.argtypes = [vp, f32p, i64p, i32p, i32, f32p, i64]
     lib.wlx_vad_debug_lstm.argtypes = [vp, f32p, i32p, i32, f32p, i64]
     lib.wlx_vad_debug_out.argtypes = [vp, f32p, i32, f32p, i64]
-    for name in EXPORTS + EXPORTS_BIAS_ITEMS:
+    for name in EXPORTS + EXPORTS_BIAS_ITEMS + EXPORTS_GRAMMAR:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_ring_group_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):
             fn.restype = i32

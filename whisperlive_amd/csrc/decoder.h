@@ -236,6 +236,18 @@ int bias_items_fill(std::vector<int>& pool, int V, int n_tables, const int32_t* 
 // one wave per row, like launch_dec_bias: the table of the row's item, the row's node in it, then the adds
 void launch_dec_bias_items(float* logits, const SearchParams* sp_dev, int rows, const SearchState& st, const BiasItems& bi, hipStream_t s);
 
+// ---------------------------------------------------------------- dec_grammar.hip
+// A slot's grammar (wlx_grammar_set): a DFA over token ids in one block of GRAMMAR_TABLE_INTS ints at a fixed address
+// (grammar_table.h lays it out and checks it on the host), and the slot's per-(cache row, position) states — the array the bias modes use.
+struct GrammarTable {
+    const int* block;           // [GRAMMAR_TABLE_INTS]: header (n_states, n_edges, eot, 0), edge_off, edge_tok, edge_next, accept
+    short* state;               // [cache_rows][448] DFA state of cache row r at position p (BiasTable::state)
+};
+#define GRAMMAR_TILE 2048       // vocabulary ids per workgroup of dec_grammar_kernel (256 threads x two 16-byte pieces)
+// (rows x ceil(V / GRAMMAR_TILE)) workgroups between the vocabulary projection and the search: the row's state from its parent's, then
+// every logit of [0, eot] that the state does not allow becomes -inf; nothing else is written
+void launch_dec_grammar(float* logits, const SearchParams* sp_dev, int rows, int V, const SearchState& st, const GrammarTable& g, hipStream_t s);
+
 // softmax over ids [0, vlim) of row r, probability of token toks[r] -> out[r]   (text_token_probs of Whisper.align)
 void launch_token_prob_rows(const float* logits, long ldl, int vlim, int rows, const int* toks, float* out, hipStream_t s);
 // softmax prob of token `tok` in given logits rows -> out[rows]

@@ -15,14 +15,17 @@
 
 namespace wlx {
 
-enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2 };   // a slot's keyword boosting: none, one table, a table per item
+// the launch of a slot's decode step between the vocabulary projection and the search: none, keyword boosting with one table or a table per
+// item, or a grammar (wlx_grammar_set: masks where the others add). One mode at a time: the last set call decides.
+enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3 };
 
 // what a captured decode-step graph depends on (engine_decode.hip get_step_graph)
 struct StepGraphKey {
     int rows, R, groups, nsteps;
     bool busy, sampling;
     int bias;                   // BiasMode of the slot: the step launches dec_bias_kernel (one table: wlx_bias_set) or dec_bias_items_kernel (per item:
-                                // wlx_bias_set_items) in front of the search, or nothing; a graph captured for one mode is never replayed for another
+                                // wlx_bias_set_items) or dec_grammar_kernel (wlx_grammar_set) in front of the search, or nothing; a graph captured for
+                                // one mode is never replayed for another
     bool operator<(const StepGraphKey& o) const {
         return std::tie(rows, R, groups, nsteps, busy, sampling, bias) < std::tie(o.rows, o.R, o.groups, o.nsteps, o.busy, o.sampling, o.bias);
     }
@@ -108,6 +111,9 @@ struct Slot {
     // the next select waits for it before it rewrites the pinned side (the pool's staging waits for the stream, like h_bias)
     BiasItems bias_items{}; int* d_pool = nullptr; int* h_pool = nullptr; int* d_sel = nullptr; int* h_sel = nullptr;
     int bias_tables = 0, sel_n = 0; hipEvent_t ev_sel = nullptr; bool sel_pending = false;
+    // grammar (wlx_grammar_set / wlx_grammar_clear; dec_grammar.hip): the table's device block and its pinned staging, allocated at the first
+    // wlx_grammar_set and kept at those addresses; the states are `bias_state`. `grammar_eot`: the end-of-text id the table was checked against
+    GrammarTable grammar{}; int* d_grammar = nullptr; int* h_grammar = nullptr; int grammar_eot = -1;
     unsigned* d_suppress = nullptr;
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging

@@ -1,6 +1,7 @@
 // engine_decode.hip — the decode half of the Whisper engine: decoder pass, prompt prefill, step graphs, search parameters and options,
 // wlx_generate, language detection and word alignment (engine.hip: slots, audio, encoder; engine.h: what the files share).
 #include "engine.h"
+#include "grammar_table.h"
 #include <sched.h>
 #include <limits>
 #include <algorithm>
@@ -335,10 +336,12 @@ static int graph_steps_for(const Slot* s, int rows) {
 
 // keyword boosting: with a table installed on the slot (wlx_bias_set) one launch between the vocabulary projection and the search adds the
 // row's bias to its logits (dec_bias.hip); a slot without a table launches nothing here, so its step is the launch list it always was. In
-// per-item mode (wlx_bias_set_items) the launch is dec_bias_items_kernel: the table selected for the row's item (wlx_bias_select)
+// per-item mode (wlx_bias_set_items) the launch is dec_bias_items_kernel: the table selected for the row's item (wlx_bias_select). With a
+// grammar (wlx_grammar_set) it is dec_grammar_kernel (dec_grammar.hip), which masks where the others add.
 void wlx::launch_bias(Slot* s, int rows) {
     if (s->bias_mode == BIAS_ONE) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
     else if (s->bias_mode == BIAS_ITEMS) launch_dec_bias_items(s->logits, s->d_sp, rows, s->st, s->bias_items, s->stream);
+    else if (s->bias_mode == BIAS_GRAMMAR) launch_dec_grammar(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->grammar, s->stream);
 }
 
 static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps) {
@@ -668,6 +671,8 @@ int wlx::generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, co
     CKR(validate_opts(e, s, batch, o));
     if (s->bias_mode == BIAS_ITEMS && batch > s->sel_n)
         return set_error(WLX_ERR_STATE, "generate: %d items, but the bias selection covers %d (wlx_bias_select)", batch, s->sel_n);
+    if (s->bias_mode == BIAS_GRAMMAR && o->ids.eot != s->grammar_eot)
+        return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's grammar was compiled for %d (wlx_grammar_set)", o->ids.eot, s->grammar_eot);
     static const bool gen_trace = getenv("WLX_GEN_TRACE") != nullptr;
     double tg[2] = {0.0, 0.0};                                  // WLX_GEN_TRACE: host time in graph launch calls / in the polling waits
     const double tg0 = now_us();
@@ -856,6 +861,43 @@ extern "C" int32_t wlx_bias_select(wlx_engine* e, int32_t slot, int32_t n, const
             return set_error(WLX_ERR_ARG, "bias select: item %d names table %d outside -1..%d", b, table_of_item[b], s->bias_tables - 1);
     CK(hipSetDevice(e->device));
     return bias_select_upload(s, n, table_of_item);
+}
+
+// ---- grammar-constrained decoding: the slot's DFA (include/wlx_grammar.h; dec_grammar.hip). Like the bias table: the device block and the pinned
+// staging are allocated at the first call and stay where they are, the states are the slot's bias_state.
+extern "C" int32_t wlx_grammar_set(wlx_engine* e, int32_t slot, int32_t eot, int32_t n_states, const int32_t* edge_off, const int32_t* edge_tok,
+                                   const int32_t* edge_next, const int32_t* accept) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    // a refused grammar leaves whatever is installed whole (and allocates nothing)
+    char why[200];
+    if (!grammar_table_check(e->spec.vocab, eot, n_states, edge_off, edge_tok, edge_next, accept, why, sizeof(why))) return set_error(WLX_ERR_ARG, "%s", why);
+    CK(hipSetDevice(e->device));
+    CKR(bias_state_alloc(s));
+    if (!s->d_grammar) {
+        int *blk = nullptr, *stage = nullptr;
+        CKR(dalloc(s->allocs, &blk, (size_t)GRAMMAR_TABLE_INTS, true));
+        CKR(halloc(s->host_allocs, &stage, (size_t)GRAMMAR_TABLE_INTS));
+        memset(stage, 0, sizeof(int) * GRAMMAR_TABLE_INTS);
+        s->d_grammar = blk; s->h_grammar = stage; s->grammar = GrammarTable{blk, s->bias_state};
+    }
+    // the staging may still feed the copy of the previous grammar: wait for the stream, then rewrite it
+    CK(hipStreamSynchronize(s->stream));
+    grammar_table_pack(s->h_grammar, eot, n_states, edge_off, edge_tok, edge_next, accept);
+    // (the used parts only: everything up to the last edge_next, and the accept flags at their fixed place)
+    CK(hipMemcpyAsync(s->d_grammar, s->h_grammar, sizeof(int) * (size_t)(GRAMMAR_NEXT_AT + edge_off[n_states]), hipMemcpyHostToDevice, s->stream));
+    CK(hipMemcpyAsync(s->d_grammar + GRAMMAR_ACCEPT_AT, s->h_grammar + GRAMMAR_ACCEPT_AT, sizeof(int) * (size_t)n_states, hipMemcpyHostToDevice, s->stream));
+    s->grammar_eot = eot;
+    s->bias_mode = BIAS_GRAMMAR;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_grammar_clear(wlx_engine* e, int32_t slot) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    if (sg_.s->bias_mode == BIAS_GRAMMAR) sg_.s->bias_mode = BIAS_NONE;      // (a bias table installed since stays)
+    return WLX_OK;
 }
 
 extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot, const int32_t* lang_ids,

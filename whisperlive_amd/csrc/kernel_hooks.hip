@@ -9,6 +9,7 @@
 //   wlx_debug_dtw, wlx_debug_align_post   launch_align_dtw / launch_align_cost (align.hip)
 //   wlx_debug_bias_apply         launch_dec_bias (dec_bias.hip)
 //   wlx_debug_bias_apply_items   launch_dec_bias_items (dec_bias.hip)
+//   wlx_debug_grammar_apply      launch_dec_grammar (dec_grammar.hip)
 //   wlx_debug_token_prob, _token_prob_rows, _lang_probs   launch_token_prob / _token_prob_rows / launch_lang_probs (search.hip)
 //   wlx_debug_dec_embed          launch_dec_embed (decoder.hip)
 //   wlx_debug_prep_windows       launch_prep_windows (logmel.hip)
@@ -17,6 +18,7 @@
 // these exist.
 #include "align.h"
 #include "decoder.h"
+#include "grammar_table.h"
 #include "host.h"
 
 using namespace wlx;
@@ -660,6 +662,65 @@ extern "C" int32_t wlx_debug_bias_apply_items(int32_t device, int32_t vocab, int
     st.done = dzero; st.item_done = dzero + 1; st.row_done = dzero + 1 + items; st.plen = dplen; st.token = dtok; st.pos = dpos; st.anc = danc; st.nsp_row = dnsp;
     launch_dec_bias_items(dl, dsp, rows, st, BiasItems{dpool, dsel, dstate}, S.st);
     CKR(S.download(logits, dl, (size_t)rows * ldl));
+    CKR(S.download(state.data(), dstate, state.size()));
+    CKR(S.finish());
+    for (int r = 0; r < rows; ++r) state_out[r] = state[(size_t)r * WLX_T_TEXT + pos[r]];
+    return WLX_OK;
+}
+
+// wlx_debug_grammar_apply: launch_dec_grammar (dec_grammar.hip) on a search state built here for one item of `rows` beams
+extern "C" int32_t wlx_debug_grammar_apply(int32_t device, int32_t vocab, int32_t eot, int32_t n_states, const int32_t* edge_off,
+                                           const int32_t* edge_tok, const int32_t* edge_next, const int32_t* accept, float* logits, int32_t rows,
+                                           int64_t ldl, const int32_t* tokens, const int32_t* pos, const int32_t* parent, int32_t plen,
+                                           const int32_t* nsp_row, const int16_t* prev_state, int16_t* state_out) {
+    if (!logits || !tokens || !pos || !parent || !nsp_row || !prev_state || !state_out) return set_error(WLX_ERR_ARG, "null argument");
+    if (vocab < 1 || vocab > (1 << 20) || ldl < vocab || ldl > (1 << 20)) return set_error(WLX_ERR_ARG, "vocab %d / ldl %lld", vocab, (long long)ldl);
+    if (rows < 1 || rows > WLX_MAX_DEC_ROWS) return set_error(WLX_ERR_ARG, "rows %d outside 1..%d", rows, WLX_MAX_DEC_ROWS);
+    if (plen < 1 || plen > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "plen %d outside 1..%d", plen, WLX_T_TEXT);
+    char why[200];
+    if (!grammar_table_check(vocab, eot, n_states, edge_off, edge_tok, edge_next, accept, why, sizeof(why))) return set_error(WLX_ERR_ARG, "%s", why);
+    // (declared before the scope: the copies below read them until the scope's last wait)
+    std::vector<int> block((size_t)GRAMMAR_TABLE_INTS, 0), zeros((size_t)rows + 4, 0), one_plen(1, plen);
+    std::vector<short> anc((size_t)rows * WLX_T_TEXT, 0), state((size_t)rows * WLX_T_TEXT, 0);
+    SearchParams sp{};
+    grammar_table_pack(block.data(), eot, n_states, edge_off, edge_tok, edge_next, accept);
+    for (int r = 0; r < rows; ++r) {
+        if (tokens[r] < 0 || tokens[r] >= vocab) return set_error(WLX_ERR_ARG, "row %d: token %d outside the vocabulary (%d)", r, tokens[r], vocab);
+        if (pos[r] < 0 || pos[r] >= WLX_T_TEXT) return set_error(WLX_ERR_ARG, "row %d: position %d outside 0..%d", r, pos[r], WLX_T_TEXT - 1);
+        if (parent[r] < 0 || parent[r] >= rows) return set_error(WLX_ERR_ARG, "row %d: parent %d outside 0..%d", r, parent[r], rows - 1);
+        if (prev_state[r] < 0) return set_error(WLX_ERR_ARG, "row %d: state %d is negative", r, prev_state[r]);
+        if (pos[r] >= 1) {
+            anc[(size_t)r * WLX_T_TEXT + pos[r] - 1] = (short)parent[r];
+            state[(size_t)parent[r] * WLX_T_TEXT + pos[r] - 1] = prev_state[r];
+        }
+        anc[(size_t)r * WLX_T_TEXT + pos[r]] = (short)r;
+    }
+    // the launch writes row r's state at pos[r]: no row may read that word as its parent's (in a decode the rows of an item share a position)
+    for (int q = 0; q < rows; ++q)
+        if (pos[q] >= plen && pos[q] >= 1 && pos[parent[q]] == pos[q] - 1)
+            return set_error(WLX_ERR_ARG, "row %d reads the state row %d writes in this launch (position %d)", q, parent[q], pos[q] - 1);
+    sp.V = vocab; sp.ldl = ldl; sp.items = 1; sp.R = rows; sp.rows = rows; sp.sampling = 0; sp.beam = rows; sp.num_hyp = 1; sp.eot = eot;
+    const size_t words = (size_t)rows * ldl + WLX_DEBUG_GUARD;
+    HookScope S;
+    CKR(S.begin(device));
+    int *dblock = nullptr, *dzero = nullptr, *dplen = nullptr, *dtok = nullptr, *dpos = nullptr, *dnsp = nullptr;
+    short *danc = nullptr, *dstate = nullptr;
+    float* dl = nullptr;
+    SearchParams* dsp = nullptr;
+    CKR(S.upload(&dblock, block.data(), block.size()));
+    CKR(S.upload(&dzero, zeros.data(), zeros.size()));
+    CKR(S.upload(&dplen, one_plen.data(), (size_t)1));
+    CKR(S.upload(&dtok, tokens, (size_t)rows));
+    CKR(S.upload(&dpos, pos, (size_t)rows));
+    CKR(S.upload(&dnsp, nsp_row, (size_t)rows));
+    CKR(S.upload(&danc, anc.data(), anc.size()));
+    CKR(S.upload(&dstate, state.data(), state.size()));
+    CKR(S.upload(&dl, logits, words));
+    CKR(S.upload(&dsp, &sp, (size_t)1));
+    SearchState st{};
+    st.done = dzero; st.item_done = dzero + 1; st.row_done = dzero + 4; st.plen = dplen; st.token = dtok; st.pos = dpos; st.anc = danc; st.nsp_row = dnsp;
+    launch_dec_grammar(dl, dsp, rows, (int)ldl, st, GrammarTable{dblock, dstate}, S.st);
+    CKR(S.download(logits, dl, words));
     CKR(S.download(state.data(), dstate, state.size()));
     CKR(S.finish());
     for (int r = 0; r < rows; ++r) state_out[r] = state[(size_t)r * WLX_T_TEXT + pos[r]];

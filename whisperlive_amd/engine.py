@@ -621,7 +621,7 @@ class Slot:
         ids, vals = np.ascontiguousarray(table.tok_ids, dtype=np.int32), np.ascontiguousarray(table.tok_vals, dtype=np.float32)
         check(self.lib.wlx_bias_set(self.engine._h, self.sid, table.n_nodes, _i32p(off), _i32p(tok), _i32p(nxt), float(table.boost),
                                     ids.size, _i32p(ids), _f32p(vals)))
-        self._bias_table = table
+        self._bias_table, self._grammar = table, None       # (one mode at a time: the last set call decides)
 
     def set_bias_items(self, bias_set) -> None:
         """Install a biasing.BiasSet on the slot (wlx_bias_set_items): the slot decodes in per-item mode, every item deselected until
@@ -633,7 +633,7 @@ class Slot:
         nn, off, tok, nxt, boosts, nt, ids, vals = bias_set.packed()
         check(self.lib.wlx_bias_set_items(self.engine._h, self.sid, len(bias_set), _i32p(nn), _i32p(off), _i32p(tok), _i32p(nxt),
                                           _f32p(boosts), _i32p(nt), _i32p(ids), _f32p(vals)))
-        self._bias_table, self._bias_set_version = bias_set, bias_set.version
+        self._bias_table, self._bias_set_version, self._grammar = bias_set, bias_set.version, None
 
     def select_bias(self, indices: Sequence[int]) -> None:
         """indices[b]: the table (an index into the installed set, -1: none) of item b of the following generate calls (wlx_bias_select)"""
@@ -643,7 +643,24 @@ class Slot:
     def clear_bias(self) -> None:
         """Decode without a bias table again (wlx_bias_clear)."""
         check(self.lib.wlx_bias_clear(self.engine._h, self.sid))
-        self._bias_table = None
+        self._bias_table = self._grammar = None
+
+    # ---- grammar-constrained decoding
+    def set_grammar(self, grammar) -> None:
+        """Install a grammar.Grammar on the slot (wlx_grammar_set): every decode step of its generate calls, and of the debug_search
+        hooks, then runs the grammar launch in front of the search, in place of a keyword table's (one mode at a time). The buffers sit
+        at fixed addresses: captured step graphs are re-used across grammars. WlxError (ERR_ARG) for a table the library refuses; what is
+        installed stays."""
+        if grammar.vocab != self.engine.spec.vocab:
+            raise ValueError(f"the grammar was compiled for a vocabulary of {grammar.vocab}, the model has {self.engine.spec.vocab}")
+        off, tok, nxt, acc = (np.ascontiguousarray(a, dtype=np.int32) for a in (grammar.edge_off, grammar.edge_tok, grammar.edge_next, grammar.accept))
+        check(self.lib.wlx_grammar_set(self.engine._h, self.sid, int(grammar.eot), grammar.n_states, _i32p(off), _i32p(tok), _i32p(nxt), _i32p(acc)))
+        self._grammar, self._bias_table = grammar, None
+
+    def clear_grammar(self) -> None:
+        """Decode without a grammar again (wlx_grammar_clear): the step is the launch list of a slot that never had one."""
+        check(self.lib.wlx_grammar_clear(self.engine._h, self.sid))
+        self._grammar = None
 
     def align(self, tokens: Sequence[int], n_sot: int, num_frames: int, heads: Sequence[Tuple[int, int]], eot: int,
               median_filter_width: int = 7, item: int = 0):

@@ -63,6 +63,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import biasing as _biasing
+from . import grammar as _grammar
 from . import vad as _vad
 from . import word_timing as _wt
 from .batched import MAX_DEC_ROWS, DeviceChunks, _collect_ranges, _file_bytes, _options, _put_audio, _put_audio_many, _segment, _vad_options
@@ -299,6 +300,7 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
         raise ValueError(f"on_error {on_error!r}: 'return' or 'raise'")
     wave_put = bool(kwargs.pop("wave_put", False))
     bias_args = {name: kwargs.pop(name, None) for name in BIAS_KEYWORDS}
+    grammar, grammar_repeat = kwargs.pop("grammar", None), kwargs.pop("grammar_repeat", True)
     diarize, max_speakers = kwargs.pop("diarize", False), kwargs.pop("max_speakers", None)
     if kwargs.pop("multichannel", False):
         raise ValueError("transcribe_many: multichannel=True is not part of this route (transcribe the files one by one with "
@@ -325,7 +327,27 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     per_file = per_file_arguments(a, len(audios))
     diarizers = per_file_diarizers(pipe, diarize, max_speakers, len(audios))
     tables = per_file_tables(pipe.model, bias_args, len(audios))        # compiled here, before any audio work
-    return _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables)
+    job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables)
+    if grammar is None:
+        return job
+    # ONE grammar for all files (a grammar per file is not served: one grammar serves a whole decode group, and groups mix files)
+    if any(t is not None for t in tables):
+        raise ValueError("grammar and keywords / logit_bias in one job: a slot decodes under one of them")
+    if not hasattr(pipe.model, "compile_grammar"):
+        raise ValueError("grammar: this transcriber takes no grammar")
+    return _under_grammar(job, pipe.model.compile_grammar(grammar, grammar_repeat))
+
+
+def _under_grammar(job, gram):
+    """`job`, every step of it taken under the calling thread's grammar scope (left again before the file is handed out)"""
+    it = iter(job)
+    while True:
+        with _grammar.scope(gram):
+            try:
+                item = next(it)
+            except StopIteration:
+                return
+        yield item
 
 
 def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None, tables=None):

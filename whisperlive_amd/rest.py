@@ -318,6 +318,28 @@ class _Upload:
         self.done, self.result, self.error = threading.Event(), None, None
 
 
+def grammar_scope(transcriber, grammar: Sequence[str], grammar_repeat: Optional[str], keywords=None, keywords_boost=None):
+    """The `grammar` (repeatable: one phrase per field) and `grammar_repeat` form fields -> the context manager under which the upload
+    is decoded (WhisperModelHIP.grammar on the request's thread), or None without a grammar. 400: a repeat flag that is no boolean or
+    comes without a grammar, an empty phrase, a grammar together with keywords, a list past a limit (the message names it: states,
+    edges), a transcriber that takes no grammar."""
+    repeat = True
+    if grammar_repeat is not None and grammar_repeat.strip():
+        repeat = parse_bool_field(grammar_repeat, "grammar_repeat")
+        if not grammar:
+            raise _HttpError(400, {"error": "grammar_repeat needs at least one grammar field"})
+    if not grammar:
+        return None
+    if keywords or (keywords_boost is not None and keywords_boost.strip()):
+        raise _HttpError(400, {"error": "grammar cannot be combined with keywords: a file decodes under one of them"})
+    if not hasattr(transcriber, "grammar"):
+        raise _HttpError(400, {"error": "grammar: this server's transcriber takes no grammar"})
+    try:
+        return transcriber.grammar(phrases=list(grammar), repeat=repeat)
+    except ValueError as e:
+        raise _HttpError(400, {"error": f"grammar: {e}"})
+
+
 def pool_upload(has_batcher: bool, multichannel: bool, known_speaker_names, known_speaker_references) -> bool:
     """whether an upload joins the pooled jobs: keywords do not keep it out (each file of a job has its own table); multichannel
     files and known speakers do"""
@@ -840,6 +862,7 @@ class _Handler(BaseHTTPRequestHandler):
         include = many("include") + many("include[]") or None
         known_speaker_names = many("known_speaker_names") + many("known_speaker_names[]")
         keywords, keywords_boost = many("keywords") + many("keywords[]"), one("keywords_boost")
+        grammar, grammar_repeat = many("grammar") + many("grammar[]"), one("grammar_repeat")
         known_speaker_references = fields.get("known_speaker_references", []) + fields.get("known_speaker_references[]", [])
         want_words = bool(timestamp_granularities and "word" in timestamp_granularities)
         rest = self.rest
@@ -849,6 +872,8 @@ class _Handler(BaseHTTPRequestHandler):
                 raise _HttpError(400, {"error": "multichannel cannot be combined with stream: send the request without stream"})
             if keywords or keywords_boost:
                 raise _HttpError(400, {"error": "keywords cannot be combined with stream: send the request without stream"})
+            if grammar or grammar_repeat:
+                raise _HttpError(400, {"error": "grammar cannot be combined with stream: send the request without stream"})
             return self._stream(file, language, prompt, temperature, want_words, target_language)
 
         ignored_params = []
@@ -891,8 +916,13 @@ class _Handler(BaseHTTPRequestHandler):
             # thread under it (the segments may arrive lazily: they are drawn inside the scope); a pooled one carries its keywords into the
             # job, where every file decodes under its own table in the compact form (many_files.py: a decode group takes a table per
             # item) — so that is the form its list is checked in here, and the scope is not entered.
+            # grammar: compiled (and refused: 400) before the file is decoded too. One grammar serves a whole decode group, so an upload with
+            # one is not pooled with other uploads: it is decoded in this thread under its grammar.
+            gram = grammar_scope(transcriber, grammar, grammar_repeat, keywords, keywords_boost)
+            if gram is not None:
+                pooled, pooled_diarizer = False, None
             bias = keyword_scope(transcriber, keywords, keywords_boost, compact=pooled)
-            with (bias if bias is not None and not pooled else contextlib.nullcontext()):
+            with (bias if bias is not None and not pooled else contextlib.nullcontext()), (gram if gram is not None else contextlib.nullcontext()):
                 if pooled:
                     segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
                                                             temperature=temperature, word_timestamps=want_words, hotwords=hotwords,

@@ -413,6 +413,24 @@ def keyword_options(transcriber, keywords, keywords_boost):
     return transcriber.keyword_bias(phrases=list(keywords), boost=keywords_boost)
 
 
+def grammar_options(transcriber, grammar, grammar_repeat, keywords=None, keywords_boost=None):
+    """`grammar` (a list of strings: the closed phrase list) and `grammar_repeat` (a boolean, optional; default true) of a session's first
+    message -> the scope under which the session decodes (WhisperModelHIP.grammar). ValueError: not a list of non-empty strings, a
+    repeat flag that is no boolean or comes without a grammar, a grammar together with keywords, a list past a limit (named), a
+    transcriber that takes no grammar."""
+    if grammar is None:
+        raise ValueError("grammar_repeat needs grammar")
+    if not isinstance(grammar, (list, tuple)) or not grammar or not all(isinstance(k, str) and k.strip() for k in grammar):
+        raise ValueError("grammar must be a non-empty list of non-empty strings")
+    if grammar_repeat is not None and not isinstance(grammar_repeat, bool):
+        raise ValueError("grammar_repeat must be a boolean")
+    if keywords or keywords_boost is not None:
+        raise ValueError("grammar cannot be combined with keywords: a session decodes under one of them")
+    if not hasattr(transcriber, "grammar"):
+        raise ValueError("this server's transcriber takes no grammar")
+    return transcriber.grammar(phrases=list(grammar), repeat=True if grammar_repeat is None else grammar_repeat)
+
+
 class ServeClientHIP(ServeClientBase):
     """Backend adaptor for the MI355X engine. Class-level registries mirror the reference's SINGLE_MODEL /
     BATCH_WORKER hooks (faster_whisper_backend.py:15-17) but are keyed by GPU: one shared transcriber per device."""
@@ -423,6 +441,7 @@ class ServeClientHIP(ServeClientBase):
     BATCH_WORKER = None             # optional whisperlive_amd.batching.BatchInferenceWorker (all devices)
     BATCH_WORKERS = {}              # device index -> BatchInferenceWorker (one per GPU; set by TranscriptionServer)
     _bias = None                    # the session's keyword table as a scope (WhisperModelHIP.keyword_bias); None: a session without keywords
+    _grammar = None                 # the session's grammar as a scope (WhisperModelHIP.grammar); None: a session without one
     BACKEND_NAME = "faster_whisper"  # the stock Python client only keeps completed segments for this string (client.py:182,399)
 
     def __init__(self, websocket, task="transcribe", device=None, language=None, client_uid=None, model="small.en",
@@ -430,7 +449,8 @@ class ServeClientHIP(ServeClientBase):
                  no_speech_thresh=0.45, clip_audio=False, same_output_threshold=7, cache_path="~/.cache/whisper-live/",
                  translation_queue=None, hotwords=None, diarization=None, word_timestamps=False, *,
                  device_index: int = 0, transcriber=None, model_factory=None, serialize_single_model: bool = False,
-                 start_thread: bool = True, max_batch: int = 1, keywords=None, keywords_boost=None):
+                 start_thread: bool = True, max_batch: int = 1, keywords=None, keywords_boost=None, grammar=None,
+                 grammar_repeat=None):
         super().__init__(client_uid, websocket, send_last_n_segments, no_speech_thresh, clip_audio, same_output_threshold,
                          translation_queue, diarization, word_timestamps)
         self.cache_path = cache_path
@@ -465,7 +485,17 @@ class ServeClientHIP(ServeClientBase):
                                             "message": f"Failed to load model: {str(self.model_size_or_path)}"}))
             self.websocket.close()
             return
-        if keywords or keywords_boost is not None:
+        if grammar is not None or grammar_repeat is not None:
+            # `grammar` / `grammar_repeat` of the first message: compiled once, here; a refused list ends the session with the limit named
+            try:
+                self._grammar = grammar_options(self.transcriber, grammar, grammar_repeat, keywords, keywords_boost)
+            except ValueError as e:
+                logging.error(f"grammar refused for {self.client_uid}: {e}")
+                self.websocket.send(json.dumps({"uid": self.client_uid, "status": "ERROR", "message": f"Unsupported grammar: {e}"}))
+                self.websocket.close()
+                del self.transcriber            # (what the server reads as "no session")
+                return
+        elif keywords or keywords_boost is not None:
             # `keywords` / `keywords_boost` of the first message: compiled once, here; a value past a cap ends the session like a model
             # that does not load, with the cap named
             try:
@@ -596,6 +626,11 @@ class ServeClientHIP(ServeClientBase):
         # a session with keywords stays in the batch worker: its request carries its table, and a decode group that mixes sessions
         # takes a table per item (batching.py _process_multi). Without a worker it decodes on its own slot under its table.
         table = self._bias.table if self._bias is not None else None
+        if self._grammar is not None:
+            # one grammar serves every item of a decode group, so a session with a grammar does not join the worker's mixed groups: it
+            # decodes on its own slot under its grammar
+            with self._grammar:
+                return self._transcribe_direct(input_sample)
         if worker is None and self._bias is not None:
             with self._bias:
                 return self._transcribe_direct(input_sample)

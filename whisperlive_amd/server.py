@@ -307,6 +307,7 @@ class TranscriptionServer:
                 translation_queue=translation_queue,
                 diarization=self._create_diarizer(options, diarization_path, device_index) if diarization_path is not None else None,
                 keywords=options.get("keywords"), keywords_boost=options.get("keywords_boost"),
+                grammar=options.get("grammar"), grammar_repeat=options.get("grammar_repeat"),
             )
             if translation_client is not None:
                 client.translation_client, client.translation_thread = translation_client, translation_thread
@@ -389,7 +390,8 @@ class TranscriptionServer:
                     hotwords=options.get("hotwords"), word_timestamps=options.get("word_timestamps", False),
                     device_index=device_index, model_factory=self.model_factory,
                     max_batch=self.batch_config["max_batch_size"] if self.batch_config is not None else 1,
-                    keywords=options.get("keywords"), keywords_boost=options.get("keywords_boost"))
+                    keywords=options.get("keywords"), keywords_boost=options.get("keywords_boost"),
+                    grammar=options.get("grammar"), grammar_repeat=options.get("grammar_repeat"))
 
             session = MultichannelSession(websocket, uid, audio_format, channels, sample_rate, make_child)
             if not session.ready:                         # model load failed: ERROR already sent, socket closed

@@ -31,6 +31,7 @@ import numpy as np
 
 from . import _lib
 from . import biasing as _biasing
+from . import grammar as _grammar
 from . import vad as _vad
 from . import word_timing as _wt
 from ._lib import ERR_ARG as _ERR_ARG, ERR_DATA as _ERR_DATA, WlxError as _WlxError
@@ -232,6 +233,23 @@ class _EngineModel:
         # selection per decode group.
         scope_items = _biasing.current_items()
         sel = None
+        # a grammar (WhisperModelHIP.grammar) takes the slot's one launch in front of the search: not together with keywords
+        gram = _grammar.current()
+        if gram is not None:
+            if table is not None or scope_items is not None:
+                raise ValueError("a grammar and keyword boosting on one slot are not served: decode under one of them")
+            if gram.eot != o.token_ids.eot:
+                raise ValueError(f"the grammar was compiled for end-of-text {gram.eot}, this model's is {o.token_ids.eot}")
+            # a state whose every token the call suppresses would leave its row without a finite logit, which is outside the search's
+            # contract (a suppressed token of a state that has others is merely unreachable)
+            dead = gram.dead_states(sup, o.token_ids.blank if suppress_blank else None)
+            if dead:
+                raise ValueError(f"every token the grammar allows in state {dead[0]} is one this call suppresses (suppress_tokens"
+                                 f"{', suppress_blank' if dead[0] == 0 and suppress_blank else ''}): nothing would be left to emit there")
+            _grammar.install(slot, gram)
+        elif getattr(slot, "_grammar", None) is not None:
+            _grammar.install(slot, None)
+        # (under a grammar none of the keyword routes below applies: no table, no item scope, and install has forgotten the slot's table)
         if scope_items is not None:
             if len(scope_items.tables) != len(prompts):
                 raise ValueError(f"the item_scope names {len(scope_items.tables)} tables for {len(prompts)} prompts")
@@ -485,6 +503,20 @@ class WhisperModelHIP:
         refuses (its edge cap binds at a few dozen phrases); the same tokens and scores where both forms load."""
         return _biasing.scope(self.compile_keywords(phrases, boost, logit_bias, compact=compact))
 
+    def grammar(self, phrases=None, repeat: bool = True):
+        """Context manager: inside the block every generate of the CALLING THREAD decodes under this grammar on its slot — the transcript
+        of a window is a sequence of phrases from the list (`repeat=True`) or one phrase or nothing (`repeat=False`), and nothing else:
+        the streaming transcriber, BatchedInferencePipeline.transcribe and the temperature fallback alike. `phrases`: strings or token
+        lists (grammar.compile_grammar: a DFA over text tokens; timestamps are transparent). The scores are those of the masked
+        distribution. One grammar for every item of a decode group; a grammar per item, and a grammar together with keyword boosting,
+        are not served (ValueError where both are asked for). ValueError names the limit a list breaks. Other threads are untouched;
+        scopes nest."""
+        return _grammar.scope(self.compile_grammar(phrases, repeat))
+
+    def compile_grammar(self, phrases=None, repeat: bool = True):
+        """the grammar.Grammar `grammar` decodes under"""
+        return _grammar.compile_grammar(self._base_tokenizer, phrases, repeat, vocab=self.spec.vocab, eot=self.token_ids.eot)
+
     def compile_keywords(self, phrases=None, boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None, compact: bool = False):
         """the table keyword_bias decodes under: biasing.BiasTable, or biasing.CompactTable with compact=True (ValueError names the cap)"""
         fn = _biasing.compile_compact if compact else _biasing.compile_bias
@@ -626,7 +658,20 @@ class WhisperModelHIP:
                    hallucination_silence_threshold: Optional[float] = None, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    *, keywords=None, keywords_boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None,
-                   keywords_compact: bool = False) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
+                   keywords_compact: bool = False, grammar=None,
+                   grammar_repeat: bool = True) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
+        if grammar is not None:
+            # a closed phrase list for this call alone (see `grammar`): compiled before any audio work, so a refused list costs nothing
+            if keywords is not None or logit_bias is not None:
+                raise ValueError("grammar and keywords / logit_bias in one call: a slot decodes under one of them")
+            with self.grammar(phrases=grammar, repeat=grammar_repeat):
+                return self.transcribe(audio, language, task, log_progress, beam_size, best_of, patience, length_penalty, repetition_penalty,
+                                       no_repeat_ngram_size, temperature, compression_ratio_threshold, log_prob_threshold,
+                                       no_speech_threshold, condition_on_previous_text, prompt_reset_on_temperature, initial_prompt, prefix,
+                                       suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp, word_timestamps,
+                                       prepend_punctuations, append_punctuations, multilingual, vad_filter, vad_parameters, max_new_tokens,
+                                       chunk_length, clip_timestamps, hallucination_silence_threshold, hotwords,
+                                       language_detection_threshold, language_detection_segments)
         if keywords is not None or logit_bias is not None:
             # keyword boosting for this call alone (see keyword_bias): compiled before any audio work, so a refused table costs nothing
             with self.keyword_bias(phrases=keywords, boost=keywords_boost, logit_bias=logit_bias, compact=keywords_compact):
