@@ -11,7 +11,7 @@ recovered at :1412-1414) and ``no_speech_prob``. CTranslate2's source is not in 
   which tests/ cross-check against;
 * beam search follows the CT2 contract of SURVEY.md Appendix A.5: 2*beam candidates per step ranked by cumulative
   log-prob; a candidate ending in EOT inside the top `beam` becomes a finished hypothesis; the first `beam`
-  non-EOT candidates continue; the search stops once round(beam*patience) hypotheses are finished (or, with
+  non-EOT candidates continue; the search stops once round(beam*patience) hypotheses are finished, halves rounded up (or, with
   length_penalty == 0, as soon as the best candidate is finished), or at max_length; hypotheses are ranked by
   sum_logp / len^length_penalty. Ties: higher score first, then lower token id / lower beam index.
   CT2's own tie-breaking and RNG stream are parity-unpinned.
@@ -230,7 +230,7 @@ def generate(provider: LogitsProvider, prompt: Sequence[int], o: GenOptions, row
     if not sampling:
         B = o.beam_size
         ncand = 2 * B
-        max_hyp = max(1, int(round(B * o.patience)))
+        max_hyp = max(1, int(np.floor(B * float(o.patience) + 0.5)))   # halves away from zero, as the engine's std::lround (Python's round() goes to even: 4.5 -> 4)
         allow_early_exit = o.length_penalty == 0
         cum = np.full(B, NEG_INF, dtype=np.float32)
         cum[0] = 0.0
