@@ -21,7 +21,8 @@
  * has no edge for the token (a caller-forced prefix) — and a parent's state outside 0..n_states - 1, which another grammar or a bias
  * table left behind, counts as the start state. The states live per (cache row, position) in the array the bias modes use and follow
  * the beam's re-ordering. A row whose raw distribution defines no_speech_prob inside the search is not masked at that step (its state
- * is written): no_speech_prob is the same with and without a grammar. One grammar serves every item of the decode group.
+ * is written): no_speech_prob is the same with and without a grammar. One grammar serves every item of the decode group (a grammar
+ * per item: wlx_grammar_items.h).
  * `eot` is the end-of-text id the table is checked against; a generate whose opts->ids.eot differs is refused with WLX_ERR_ARG.
  * The table and the pinned staging of the upload live in buffers of the slot at fixed addresses (allocated at the first call):
  * captured step graphs stay valid across calls and across grammars. The upload is asynchronous on the slot's stream.

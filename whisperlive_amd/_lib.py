@@ -48,6 +48,8 @@ EXPORTS = [
 EXPORTS_BIAS_ITEMS = ["wlx_bias_set_items", "wlx_bias_select", "wlx_debug_bias_apply_items"]
 # grammar-constrained decoding, declared in include/wlx_grammar.h (which wlx.h includes)
 EXPORTS_GRAMMAR = ["wlx_grammar_set", "wlx_grammar_clear", "wlx_debug_grammar_apply"]
+# a grammar per item, declared in include/wlx_grammar_items.h (which wlx.h includes)
+EXPORTS_GRAMMAR_ITEMS = ["wlx_grammar_set_items", "wlx_grammar_select", "wlx_debug_grammar_apply_items"]
 
 
 # MFMA accumulators in VGPRs (gfx950 has ONE register file; hipcc's default puts C/D in its AGPR half): every VALU touch of
@@ -155,6 +157,8 @@ BIAS_MAX_NODES, BIAS_MAX_EDGES, BIAS_MAX_TOKENS = 4096, 16384, 1024   # wlx.h WL
 BIAS_SET_MAX_TABLES, BIAS_SET_MAX_NODES, BIAS_SET_MAX_EDGES, BIAS_SET_MAX_TOKENS = 64, 16384, 65536, 4096
 BIAS_EDGE_SHARED = 0x40000000
 GRAMMAR_MAX_STATES, GRAMMAR_MAX_EDGES = 4096, 16384      # wlx_grammar.h WLX_GRAMMAR_MAX_*: the caps of a grammar table (wlx_grammar_set)
+# wlx_grammar_items.h WLX_GRAMMAR_SET_MAX_*: tables of one set (wlx_grammar_set_items) and the caps of its pool over all tables
+GRAMMAR_SET_MAX_TABLES, GRAMMAR_SET_MAX_STATES, GRAMMAR_SET_MAX_EDGES = 64, 16384, 65536
 DEBUG_GUARD = 64        # wlx.h WLX_DEBUG_GUARD: words a debug hook's output carries past what the kernel owns
 MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
@@ -334,7 +338,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
     except OSError as e:  # e.g. libamdhip64 missing
         raise WlxError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR if not hasattr(lib, s)]
+    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS if not hasattr(lib, s)]
     if missing:
         raise WlxError(f"libwlx.so lacks symbols {missing}")
     i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p
@@ -489,6 +493,13 @@ def load() -> C.CDLL:
     lib.wlx_vad_debug_frontend.argtypes = [vp, f32p, i64p, i32p, i32, f32p, i64]
     lib.wlx_vad_debug_lstm.argtypes = [vp, f32p, i32p, i32, f32p, i64]
     lib.wlx_vad_debug_out.argtypes = [vp, f32p, i32, f32p, i64]
+    if EXPORTS_GRAMMAR_ITEMS:       # (scripts/grammar_items_time.py alone empties the list, to load a library of the parent commit beside this one)
+        lib.wlx_grammar_set_items.argtypes = [vp, i32, i32, i32, i32p, i32p, i32p, i32p, i32p]
+        lib.wlx_grammar_select.argtypes = [vp, i32, i32, i32p]
+        lib.wlx_debug_grammar_apply_items.argtypes = [i32, i32, i32, i32, i32p, i32p, i32p, i32p, i32p, f32p, i32, i32, i32p, i64, i32p, i32p, i32p, i32p,
+                                                      i32p, i16p, i16p]
+        for name in EXPORTS_GRAMMAR_ITEMS:
+            getattr(lib, name).restype = i32
     for name in EXPORTS + EXPORTS_BIAS_ITEMS + EXPORTS_GRAMMAR:
         fn = getattr(lib, name)
         if name not in ("wlx_last_error", "wlx_engine_destroy", "wlx_vad_destroy", "wlx_ring_destroy", "wlx_ring_group_destroy", "wlx_mt_destroy", "wlx_spk_destroy"):

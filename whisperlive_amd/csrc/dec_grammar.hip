@@ -12,8 +12,10 @@
 // reads the parent's state at p - 1, a word no workgroup of this launch writes (the rows of an item share a position) — and the workgroup
 // of tile 0 alone stores it. The allowed set of a tile is a bitmap in LDS (64 words) that the threads fill from the state's edge list; a
 // 16-byte piece with no allowed id is stored without being read, one with all four allowed is not touched at all.
+// A slot that holds a POOL of grammars, one selected per item of the decode group (wlx_grammar_set_items / wlx_grammar_select; DESIGN.md
+// §29), launches dec_grammar_items_kernel (below) in its place.
 #include "decoder.h"
-#include "grammar_table.h"
+#include "grammar_pool.h"
 #include "host.h"
 
 namespace wlx {
@@ -106,6 +108,124 @@ __global__ __launch_bounds__(GRAMMAR_THREADS) void dec_grammar_kernel(float* __r
 void launch_dec_grammar(float* logits, const SearchParams* sp_dev, int rows, int V, const SearchState& st, const GrammarTable& g, hipStream_t s) {
     const int tiles = (V + GRAMMAR_TILE - 1) / GRAMMAR_TILE;
     hipLaunchKernelGGL(dec_grammar_kernel, dim3(tiles, rows), dim3(GRAMMAR_THREADS), 0, s, logits, sp_dev, st, g);
+}
+
+// ---- a grammar per item (wlx_grammar_set_items / wlx_grammar_select): a pool of tables (grammar_pool.h), the row's table
+// the one selected for its item of the decode group. The semantics per row are dec_grammar_kernel's on that table; the grid is the same
+// (row, tile of GRAMMAR_TILE ids), the work inside a workgroup is laid out for a group in which FEW items have a table:
+//   - the selection is the first thing read behind the row's own early returns: a workgroup of an item without a table leaves at once
+//     (tile 0 stores state 0), before any table word, LDS word or barrier; so does every tile but 0 of a row whose logits stay raw
+//     (nsp_row), which owes the launch its state alone;
+//   - the table is found through ONE 16-byte header (state base, edge base, n_states, n_edges), uniform in the workgroup;
+//   - the walk needs no LDS and no barrier: each of the four waves scans the parent state's edge list for the fed token by itself,
+//     64 edges per trip with a ballot, and stops at the first trip that holds a larger token (the tokens of a state ascend) — a wave's
+//     trips are uniform, and the four waves arrive at the same state;
+//   - the tile's allowed set is the bitmap in LDS of dec_grammar_kernel, filled between the kernel's only two barriers; a thread stops
+//     at its first edge behind the tile (ascending again), which shortens each thread's stride through a wide state's list in the low
+//     tiles only: the high tiles still scan the whole list.
+// The stores are dec_grammar_kernel's: a 16-byte piece without an allowed id is stored unread, one whose four ids are allowed is not
+// touched, a mixed one is loaded once; rows that are not 16-byte aligned take one word per thread. Static LDS only (64 words): nothing
+// about the launch is raised at run time, inside a capture or outside.
+__global__ __launch_bounds__(GRAMMAR_THREADS) void dec_grammar_items_kernel(float* __restrict__ logits, const SearchParams* __restrict__ spp,
+                                                                            SearchState st, GrammarItems gi) {
+    if (*st.done) return;                       // scratch steps behind the end of the call
+    const int r = blockIdx.y, tile = blockIdx.x, c0 = tile * GRAMMAR_TILE;
+    const int R = spp->R, eot = spp->eot;
+    const long ldl = spp->ldl;
+    if (c0 > eot) return;                       // ids above end-of-text keep their bits: nothing to do in this tile
+    const int item = r / R, rb = r - item * R;
+    if (st.item_done[item]) return;
+    if (spp->sampling) { if (rb >= spp->num_hyp || st.row_done[r]) return; }
+    else if (rb >= spp->beam) return;
+    const int tid = threadIdx.x;
+    const int p = st.pos[r];
+    if (p < 0 || p >= WLX_T_TEXT) return;
+    const int t = gi.sel[item];
+    if (t < 0) {                                // no table for this item: the start state, and the row's logits stay as they are
+        if (tile == 0 && tid == 0) gi.state[(long)r * WLX_T_TEXT + p] = 0;
+        return;
+    }
+    const bool raw = st.nsp_row[r] > 0;         // the row's RAW distribution defines no_speech_prob: its state is written, its logits stay
+    if (raw && tile != 0) return;
+    // (every return above depends on the row and the tile alone: the workgroup is whole at each barrier below)
+    const int4 hdr = reinterpret_cast<const int4*>(gi.pool)[t];        // state base, edge base, n_states, n_edges
+    const int n_states = hdr.z;
+    const int* off = gi.pool + GRAMMAR_POOL_OFF_AT + hdr.x + t;
+    const int* etok = gi.pool + GRAMMAR_POOL_TOK_AT + hdr.y;
+    const int* enext = gi.pool + GRAMMAR_POOL_NEXT_AT + hdr.y;
+    __shared__ unsigned s_keep[GRAMMAR_TILE / 32];
+    if (tid < GRAMMAR_TILE / 32) s_keep[tid] = 0u;
+    // ---- the row's state: the start state while the fed token is a prompt token (the first generated position)
+    int state = 0;
+    const int plen = st.plen[item], tok = st.token[r];
+    if (p >= plen && p >= 1) {
+        const int parent = st.anc[(long)r * WLX_T_TEXT + p - 1];
+        int ps = gi.state[(long)parent * WLX_T_TEXT + p - 1];
+        if (ps < 0 || ps >= n_states) ps = 0;   // (a state local to ANOTHER table, or what a bias table left behind: never indexes past this one)
+        state = ps;                             // a special or a timestamp is transparent: the parent's state
+        if (tok < eot) {                        // a text token: its edge, or the start state
+            state = 0;
+            const int lane = tid & 63;
+            const int lo = off[ps], hi = off[ps + 1];
+            for (int base = lo; base < hi; base += 64) {        // (uniform within the wave: lo, hi and both ballots)
+                const int i = base + lane;
+                const int v = i < hi ? etok[i] : 0x7fffffff;
+                const unsigned long long hit = __ballot(v == tok);
+                if (hit) { state = enext[base + __ffsll((long long)hit) - 1]; break; }
+                if (__ballot(v > tok)) break;   // the tokens of a state ascend: the token has no edge here
+            }
+        }
+    }
+    if (tile == 0 && tid == 0) gi.state[(long)r * WLX_T_TEXT + p] = (short)state;
+    if (raw) return;
+    __syncthreads();                            // the bitmap is clear
+    // ---- the tile's allowed ids: the state's edge tokens, and end-of-text where the state accepts
+    const int e0 = off[state], e1 = off[state + 1];
+    for (int i = e0 + tid; i < e1; i += GRAMMAR_THREADS) {
+        const int k = etok[i] - c0;
+        if (k >= GRAMMAR_TILE) break;           // ascending: this thread's later edges lie behind the tile too
+        if (k >= 0) atomicOr(&s_keep[k >> 5], 1u << (k & 31));
+    }
+    if (tid == 0 && (unsigned)(eot - c0) < (unsigned)GRAMMAR_TILE && gi.pool[GRAMMAR_POOL_ACCEPT_AT + hdr.x + state])
+        atomicOr(&s_keep[(eot - c0) >> 5], 1u << ((eot - c0) & 31));
+    __syncthreads();
+    float* lrow = logits + (long)r * ldl;
+    if ((ldl & 3) == 0 && (reinterpret_cast<unsigned long long>(logits) & 15ull) == 0) {
+        // 16-byte pieces, two per thread: piece k covers ids c0 + 4k .. c0 + 4k + 3, all below ldl (a multiple of 4 above eot)
+#pragma unroll
+        for (int j = 0; j < GRAMMAR_TILE / 4 / GRAMMAR_THREADS; ++j) {
+            const int k = tid + j * GRAMMAR_THREADS;
+            const int col = c0 + 4 * k;
+            if (col > eot) break;
+            unsigned keep = (s_keep[k >> 3] >> ((k & 7) * 4)) & 0xfu;
+            if (col + 3 > eot) keep |= (0xfu << (eot + 1 - col)) & 0xfu;        // ids above end-of-text keep their bits
+            if (keep == 0xfu) continue;
+            uint4* q = reinterpret_cast<uint4*>(lrow + col);
+            uint4 v = make_uint4(GRAMMAR_NEG_INF, GRAMMAR_NEG_INF, GRAMMAR_NEG_INF, GRAMMAR_NEG_INF);
+            if (keep) {
+                const uint4 in = *q;
+                if (keep & 1u) v.x = in.x;
+                if (keep & 2u) v.y = in.y;
+                if (keep & 4u) v.z = in.z;
+                if (keep & 8u) v.w = in.w;
+            }
+            *q = v;
+        }
+    } else {
+        // any other row stride: one word per thread and trip
+        unsigned* urow = reinterpret_cast<unsigned*>(lrow);
+        for (int k = tid; k < GRAMMAR_TILE; k += GRAMMAR_THREADS) {
+            const int col = c0 + k;
+            if (col > eot) break;
+            if (!((s_keep[k >> 5] >> (k & 31)) & 1u)) urow[col] = GRAMMAR_NEG_INF;
+        }
+    }
+}
+
+void launch_dec_grammar_items(float* logits, const SearchParams* sp_dev, int rows, int V, const SearchState& st, const GrammarItems& gi,
+                              hipStream_t s) {
+    const int tiles = (V + GRAMMAR_TILE - 1) / GRAMMAR_TILE;
+    hipLaunchKernelGGL(dec_grammar_items_kernel, dim3(tiles, rows), dim3(GRAMMAR_THREADS), 0, s, logits, sp_dev, st, gi);
 }
 
 }  // namespace wlx

@@ -247,6 +247,16 @@ struct GrammarTable {
 // (rows x ceil(V / GRAMMAR_TILE)) workgroups between the vocabulary projection and the search: the row's state from its parent's, then
 // every logit of [0, eot] that the state does not allow becomes -inf; nothing else is written
 void launch_dec_grammar(float* logits, const SearchParams* sp_dev, int rows, int V, const SearchState& st, const GrammarTable& g, hipStream_t s);
+// A grammar per item (wlx_grammar_set_items): up to GRAMMAR_SET_MAX_TABLES tables in one pool of GRAMMAR_POOL_INTS ints at a
+// fixed address (grammar_pool.h lays it out and checks it on the host), the selection, and the same states — local to the item's table.
+struct GrammarItems {
+    const int* pool;            // [GRAMMAR_POOL_INTS], 16-byte aligned: a header per table slot, then edge_off, edge_tok, edge_next, accept
+    const int* sel;             // [max_batch] table of item b of the decode group, -1: none
+    short* state;               // the slot's [cache_rows][448] states (BiasTable::state)
+};
+// the grid of launch_dec_grammar; a workgroup of an item without a table returns at once (tile 0 stores state 0)
+void launch_dec_grammar_items(float* logits, const SearchParams* sp_dev, int rows, int V, const SearchState& st, const GrammarItems& gi,
+                              hipStream_t s);
 
 // softmax over ids [0, vlim) of row r, probability of token toks[r] -> out[r]   (text_token_probs of Whisper.align)
 void launch_token_prob_rows(const float* logits, long ldl, int vlim, int rows, const int* toks, float* out, hipStream_t s);

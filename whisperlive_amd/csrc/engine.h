@@ -16,16 +16,18 @@
 namespace wlx {
 
 // the launch of a slot's decode step between the vocabulary projection and the search: none, keyword boosting with one table or a table per
-// item, or a grammar (wlx_grammar_set: masks where the others add). One mode at a time: the last set call decides.
-enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3 };
+// item, or a grammar (wlx_grammar_set: masks where the others add) or a grammar per item (wlx_grammar_set_items). One mode at a time: the
+// last set call decides.
+enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3, BIAS_GRAMMAR_ITEMS = 4 };
 
 // what a captured decode-step graph depends on (engine_decode.hip get_step_graph)
 struct StepGraphKey {
     int rows, R, groups, nsteps;
     bool busy, sampling;
     int bias;                   // BiasMode of the slot: the step launches dec_bias_kernel (one table: wlx_bias_set) or dec_bias_items_kernel (per item:
-                                // wlx_bias_set_items) or dec_grammar_kernel (wlx_grammar_set) in front of the search, or nothing; a graph captured for
-                                // one mode is never replayed for another
+                                // wlx_bias_set_items) or dec_grammar_kernel (wlx_grammar_set) or dec_grammar_items_kernel (per item:
+                                // wlx_grammar_set_items) in front of the search, or nothing; a graph captured for one mode is never replayed
+                                // for another
     bool operator<(const StepGraphKey& o) const {
         return std::tie(rows, R, groups, nsteps, busy, sampling, bias) < std::tie(o.rows, o.R, o.groups, o.nsteps, o.busy, o.sampling, o.bias);
     }
@@ -114,6 +116,10 @@ struct Slot {
     // grammar (wlx_grammar_set / wlx_grammar_clear; dec_grammar.hip): the table's device block and its pinned staging, allocated at the first
     // wlx_grammar_set and kept at those addresses; the states are `bias_state`. `grammar_eot`: the end-of-text id the table was checked against
     GrammarTable grammar{}; int* d_grammar = nullptr; int* h_grammar = nullptr; int grammar_eot = -1;
+    // a grammar per item (wlx_grammar_set_items / wlx_grammar_select; dec_grammar.hip dec_grammar_items_kernel): the pool and its pinned staging,
+    // allocated at the first wlx_grammar_set_items and kept at those addresses. The selection is d_sel / h_sel / sel_n / ev_sel above, which
+    // the two per-item modes share (a set call of either deselects every item). `gpool_eot`: the end-of-text id the pool was checked against
+    GrammarItems grammar_items{}; int* d_gpool = nullptr; int* h_gpool = nullptr; int grammar_tables = 0, gpool_eot = -1;
     unsigned* d_suppress = nullptr;
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging

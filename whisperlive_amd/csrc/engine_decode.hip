@@ -1,7 +1,7 @@
 // engine_decode.hip — the decode half of the Whisper engine: decoder pass, prompt prefill, step graphs, search parameters and options,
 // wlx_generate, language detection and word alignment (engine.hip: slots, audio, encoder; engine.h: what the files share).
 #include "engine.h"
-#include "grammar_table.h"
+#include "grammar_pool.h"
 #include <sched.h>
 #include <limits>
 #include <algorithm>
@@ -337,11 +337,13 @@ static int graph_steps_for(const Slot* s, int rows) {
 // keyword boosting: with a table installed on the slot (wlx_bias_set) one launch between the vocabulary projection and the search adds the
 // row's bias to its logits (dec_bias.hip); a slot without a table launches nothing here, so its step is the launch list it always was. In
 // per-item mode (wlx_bias_set_items) the launch is dec_bias_items_kernel: the table selected for the row's item (wlx_bias_select). With a
-// grammar (wlx_grammar_set) it is dec_grammar_kernel (dec_grammar.hip), which masks where the others add.
+// grammar (wlx_grammar_set) it is dec_grammar_kernel (dec_grammar.hip), which masks where the others add; with a pool of grammars
+// (wlx_grammar_set_items) dec_grammar_items_kernel, under the table selected for the row's item (wlx_grammar_select).
 void wlx::launch_bias(Slot* s, int rows) {
     if (s->bias_mode == BIAS_ONE) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
     else if (s->bias_mode == BIAS_ITEMS) launch_dec_bias_items(s->logits, s->d_sp, rows, s->st, s->bias_items, s->stream);
     else if (s->bias_mode == BIAS_GRAMMAR) launch_dec_grammar(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->grammar, s->stream);
+    else if (s->bias_mode == BIAS_GRAMMAR_ITEMS) launch_dec_grammar_items(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->grammar_items, s->stream);
 }
 
 static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps) {
@@ -673,6 +675,10 @@ int wlx::generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, co
         return set_error(WLX_ERR_STATE, "generate: %d items, but the bias selection covers %d (wlx_bias_select)", batch, s->sel_n);
     if (s->bias_mode == BIAS_GRAMMAR && o->ids.eot != s->grammar_eot)
         return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's grammar was compiled for %d (wlx_grammar_set)", o->ids.eot, s->grammar_eot);
+    if (s->bias_mode == BIAS_GRAMMAR_ITEMS && batch > s->sel_n)
+        return set_error(WLX_ERR_STATE, "generate: %d items, but the grammar selection covers %d (wlx_grammar_select)", batch, s->sel_n);
+    if (s->bias_mode == BIAS_GRAMMAR_ITEMS && o->ids.eot != s->gpool_eot)
+        return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's grammars were compiled for %d (wlx_grammar_set_items)", o->ids.eot, s->gpool_eot);
     static const bool gen_trace = getenv("WLX_GEN_TRACE") != nullptr;
     double tg[2] = {0.0, 0.0};                                  // WLX_GEN_TRACE: host time in graph launch calls / in the polling waits
     const double tg0 = now_us();
@@ -808,6 +814,16 @@ extern "C" int32_t wlx_bias_clear(wlx_engine* e, int32_t slot) {
 
 // ---- per-item tables (include/wlx_bias_items.h; dec_bias.hip dec_bias_items_kernel). The pool, the selection and their pinned stagings are allocated at
 // the first call and stay where they are: a step graph captured in per-item mode replays with every later set and selection.
+static int select_alloc(Slot* s) {              // the selection and its pinned staging: shared by the two per-item modes (bias, grammar)
+    if (s->d_sel) return WLX_OK;
+    int *ds = nullptr, *hs = nullptr;
+    CKR(dalloc(s->allocs, &ds, (size_t)s->B, true));
+    CKR(halloc(s->host_allocs, &hs, (size_t)s->B));
+    CK(hipEventCreateWithFlags(&s->ev_sel, hipEventDisableTiming));
+    s->d_sel = ds; s->h_sel = hs;
+    return WLX_OK;
+}
+
 static int bias_select_upload(Slot* s, int n, const int32_t* table_of_item) {
     // the pinned side may still feed the previous selection's copy: wait for THAT copy, not for the whole stream
     if (s->sel_pending) { CK(hipEventSynchronize(s->ev_sel)); s->sel_pending = false; }
@@ -830,15 +846,13 @@ extern "C" int32_t wlx_bias_set_items(wlx_engine* e, int32_t slot, int32_t n_tab
     CKR(bias_items_fill(pool, e->spec.vocab, n_tables, n_nodes, edge_off, edge_tok, edge_next, boosts, n_tok, tok_ids, tok_vals));
     CK(hipSetDevice(e->device));
     CKR(bias_state_alloc(s));
+    CKR(select_alloc(s));
     if (!s->d_pool) {
-        int *dp = nullptr, *hp = nullptr, *ds = nullptr, *hs = nullptr;
+        int *dp = nullptr, *hp = nullptr;
         CKR(dalloc(s->allocs, &dp, (size_t)WLX_BIAS_POOL_INTS, true));
-        CKR(dalloc(s->allocs, &ds, (size_t)s->B, true));
         CKR(halloc(s->host_allocs, &hp, (size_t)WLX_BIAS_POOL_INTS));
-        CKR(halloc(s->host_allocs, &hs, (size_t)s->B));
-        CK(hipEventCreateWithFlags(&s->ev_sel, hipEventDisableTiming));
-        s->d_pool = dp; s->h_pool = hp; s->d_sel = ds; s->h_sel = hs;
-        s->bias_items = BiasItems{dp, ds, s->bias_state};
+        s->d_pool = dp; s->h_pool = hp;
+        s->bias_items = BiasItems{dp, s->d_sel, s->bias_state};
     }
     CK(hipStreamSynchronize(s->stream));         // the pool's staging may still feed the copy of the previous set
     memcpy(s->h_pool, pool.data(), sizeof(int) * pool.size());
@@ -896,8 +910,63 @@ extern "C" int32_t wlx_grammar_set(wlx_engine* e, int32_t slot, int32_t eot, int
 extern "C" int32_t wlx_grammar_clear(wlx_engine* e, int32_t slot) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
-    if (sg_.s->bias_mode == BIAS_GRAMMAR) sg_.s->bias_mode = BIAS_NONE;      // (a bias table installed since stays)
+    if (sg_.s->bias_mode == BIAS_GRAMMAR || sg_.s->bias_mode == BIAS_GRAMMAR_ITEMS) sg_.s->bias_mode = BIAS_NONE;      // (a bias table installed since stays)
     return WLX_OK;
+}
+
+// ---- a grammar per item (include/wlx_grammar_items.h; dec_grammar.hip dec_grammar_items_kernel). The pool and its pinned staging are allocated
+// at the first call and stay where they are, like the selection (select_alloc): a step graph captured in this mode replays with every later
+// set and selection.
+extern "C" int32_t wlx_grammar_set_items(wlx_engine* e, int32_t slot, int32_t eot, int32_t n_tables, const int32_t* n_states, const int32_t* edge_off,
+                                         const int32_t* edge_tok, const int32_t* edge_next, const int32_t* accept) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    // a refused set leaves whatever is installed whole (and allocates nothing): checked and packed into a host copy first
+    char why[240];
+    int states = 0, edges = 0;
+    if (!grammar_pool_check(e->spec.vocab, eot, n_tables, n_states, edge_off, edge_tok, edge_next, accept, &states, &edges, why, sizeof(why)))
+        return set_error(WLX_ERR_ARG, "%s", why);
+    std::vector<int> pool((size_t)GRAMMAR_POOL_INTS);
+    grammar_pool_pack(pool.data(), n_tables, n_states, edge_off, edge_tok, edge_next, accept);
+    CK(hipSetDevice(e->device));
+    CKR(bias_state_alloc(s));
+    CKR(select_alloc(s));
+    if (!s->d_gpool) {
+        int *dp = nullptr, *hp = nullptr;
+        CKR(dalloc(s->allocs, &dp, (size_t)GRAMMAR_POOL_INTS, true));
+        CKR(halloc(s->host_allocs, &hp, (size_t)GRAMMAR_POOL_INTS));
+        s->d_gpool = dp; s->h_gpool = hp;
+        s->grammar_items = GrammarItems{dp, s->d_sel, s->bias_state};
+    }
+    CK(hipStreamSynchronize(s->stream));         // the pool's staging may still feed the copies of the previous set
+    // (the used parts only: the headers and the offsets, which lie together, then the edge tokens, the edge nexts and the accept flags)
+    const struct { int at, n; } parts[4] = {{0, GRAMMAR_POOL_OFF_AT + states + n_tables}, {GRAMMAR_POOL_TOK_AT, edges}, {GRAMMAR_POOL_NEXT_AT, edges},
+                                            {GRAMMAR_POOL_ACCEPT_AT, states}};
+    for (const auto& part : parts) {
+        if (!part.n) continue;
+        memcpy(s->h_gpool + part.at, pool.data() + part.at, sizeof(int) * (size_t)part.n);
+        CK(hipMemcpyAsync(s->d_gpool + part.at, s->h_gpool + part.at, sizeof(int) * (size_t)part.n, hipMemcpyHostToDevice, s->stream));
+    }
+    s->grammar_tables = n_tables;
+    s->gpool_eot = eot;
+    CKR(bias_select_upload(s, s->B, nullptr));   // every item deselected: a table index of an earlier set never reaches this one
+    s->bias_mode = BIAS_GRAMMAR_ITEMS;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_grammar_select(wlx_engine* e, int32_t slot, int32_t n, const int32_t* table_of_item) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (s->bias_mode != BIAS_GRAMMAR_ITEMS) return set_error(WLX_ERR_STATE, "grammar select: no grammar set installed (wlx_grammar_set_items)");
+    if (!table_of_item) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > s->B) return set_error(WLX_ERR_ARG, "grammar select: %d items outside 1..%d", n, s->B);
+    for (int b = 0; b < n; ++b)
+        if (table_of_item[b] < -1 || table_of_item[b] >= s->grammar_tables)
+            return set_error(WLX_ERR_ARG, "grammar select: item %d names table %d outside -1..%d", b, table_of_item[b], s->grammar_tables - 1);
+    CK(hipSetDevice(e->device));
+    return bias_select_upload(s, n, table_of_item);
 }
 
 extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot, const int32_t* lang_ids,

@@ -662,6 +662,23 @@ class Slot:
         check(self.lib.wlx_grammar_clear(self.engine._h, self.sid))
         self._grammar = None
 
+    def set_grammars(self, grammar_set) -> None:
+        """Install a grammar.GrammarSet on the slot (wlx_grammar_set_items): the slot decodes in per-item grammar mode, every item
+        deselected (unconstrained) until `select_grammars`. WlxError (ERR_ARG) for a set the library refuses; whatever is installed stays."""
+        if len(grammar_set) < 1:
+            raise ValueError("an empty GrammarSet installs nothing: clear_grammar")
+        if grammar_set.vocab != self.engine.spec.vocab:
+            raise ValueError(f"the grammar set was compiled for a vocabulary of {grammar_set.vocab}, the model has {self.engine.spec.vocab}")
+        ns, off, tok, nxt, acc = grammar_set.packed()
+        check(self.lib.wlx_grammar_set_items(self.engine._h, self.sid, int(grammar_set.eot), len(grammar_set), _i32p(ns), _i32p(off), _i32p(tok),
+                                             _i32p(nxt), _i32p(acc)))
+        self._grammar, self._grammar_set_version, self._bias_table = grammar_set, grammar_set.version, None
+
+    def select_grammars(self, indices: Sequence[int]) -> None:
+        """indices[b]: the grammar (an index into the installed set, -1: none) of item b of the following generate calls (wlx_grammar_select)"""
+        sel = np.ascontiguousarray(list(indices), dtype=np.int32)
+        check(self.lib.wlx_grammar_select(self.engine._h, self.sid, sel.size, _i32p(sel)))
+
     def align(self, tokens: Sequence[int], n_sot: int, num_frames: int, heads: Sequence[Tuple[int, int]], eot: int,
               median_filter_width: int = 7, item: int = 0):
         """ctranslate2 Whisper.align for one encoded item: tokens = start_sequence + [no_timestamps] + text + [eot].

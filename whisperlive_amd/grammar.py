@@ -24,7 +24,7 @@ from typing import Dict, FrozenSet, Iterable, List, Optional, Sequence, Tuple, U
 
 import numpy as np
 
-from ._lib import GRAMMAR_MAX_EDGES, GRAMMAR_MAX_STATES
+from ._lib import GRAMMAR_MAX_EDGES, GRAMMAR_MAX_STATES, GRAMMAR_SET_MAX_EDGES, GRAMMAR_SET_MAX_STATES, GRAMMAR_SET_MAX_TABLES
 from .biasing import encode_phrases
 
 _END = -1       # every trie leaf in a subset: a phrase has ended and nothing continues it
@@ -208,3 +208,124 @@ def install(slot, grammar: Optional[Grammar]) -> None:
         slot.set_grammar(grammar)
         slot._bias_table = None
     slot._grammar = grammar
+
+
+# ---- a grammar PER ITEM (include/wlx_grammar_items.h wlx_grammar_set_items / wlx_grammar_select)
+class GrammarSet:
+    """Up to 64 compiled Grammars packed into the pool of wlx_grammar_set_items. `add` returns the grammar's index, storing one that is
+    already there (the same object, or equal content) once; ValueError names the limit a new grammar would pass and leaves the set as it
+    was. `version` moves with every stored grammar: a slot uploads a set again only when it has grown (install_items)."""
+
+    def __init__(self, grammars: Iterable[Grammar] = ()):
+        self.tables: List[Grammar] = []
+        self._index: Dict[bytes, int] = {}
+        self.n_states = self.n_edges = 0
+        self.version = 0
+        for g in grammars:
+            self.add(g)
+
+    def __len__(self) -> int:
+        return len(self.tables)
+
+    @property
+    def vocab(self) -> Optional[int]:
+        return self.tables[0].vocab if self.tables else None
+
+    @property
+    def eot(self) -> Optional[int]:
+        return self.tables[0].eot if self.tables else None
+
+    @staticmethod
+    def _key(g: Grammar) -> bytes:
+        parts = (g.edge_off, g.edge_tok, g.edge_next, g.accept)
+        return np.asarray([g.vocab, g.eot, g.n_states], np.int64).tobytes() + b"".join(np.ascontiguousarray(a, np.int32).tobytes() for a in parts)
+
+    def index(self, g: Grammar) -> Optional[int]:
+        return self._index.get(self._key(g))
+
+    def _refusal(self, g: Grammar) -> Optional[str]:
+        if not isinstance(g, Grammar):
+            return "a GrammarSet holds compiled grammars (compile_grammar)"
+        if self.tables and (g.vocab, g.eot) != (self.vocab, self.eot):
+            return "the grammars of a set are compiled for one vocabulary and one end-of-text"
+        if g.n_states > GRAMMAR_MAX_STATES:
+            return f"a grammar has {g.n_states} states (at most {GRAMMAR_MAX_STATES} states per grammar)"
+        if g.n_edges > GRAMMAR_MAX_EDGES:
+            return f"a grammar has {g.n_edges} edges (at most {GRAMMAR_MAX_EDGES} edges per grammar)"
+        if len(self.tables) + 1 > GRAMMAR_SET_MAX_TABLES:
+            return f"the set would hold {len(self.tables) + 1} grammars (at most {GRAMMAR_SET_MAX_TABLES} grammars in one set)"
+        if self.n_states + g.n_states > GRAMMAR_SET_MAX_STATES:
+            return f"the set would hold {self.n_states + g.n_states} states (at most {GRAMMAR_SET_MAX_STATES} states in one set)"
+        if self.n_edges + g.n_edges > GRAMMAR_SET_MAX_EDGES:
+            return f"the set would hold {self.n_edges + g.n_edges} edges (at most {GRAMMAR_SET_MAX_EDGES} edges in one set)"
+        return None
+
+    def fits(self, g: Grammar) -> bool:
+        """`add(g)` would succeed (a grammar already stored always fits)"""
+        return (isinstance(g, Grammar) and self._key(g) in self._index) or self._refusal(g) is None
+
+    def add(self, g: Grammar) -> int:
+        if isinstance(g, Grammar):
+            i = self._index.get(self._key(g))
+            if i is not None:
+                return i
+        why = self._refusal(g)
+        if why:
+            raise ValueError(why)
+        self._index[self._key(g)] = len(self.tables)
+        self.tables.append(g)
+        self.n_states += g.n_states
+        self.n_edges += g.n_edges
+        self.version += 1
+        return len(self.tables) - 1
+
+    def packed(self):
+        """the arrays of wlx_grammar_set_items: (n_states [T], edge_off [states + T] local per table, edge_tok, edge_next, accept [states])"""
+        cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32).ravel() for x in xs]) if xs else np.zeros(0, np.int32), dtype=np.int32)
+        ts = self.tables
+        return (np.asarray([g.n_states for g in ts], np.int32), cat([g.edge_off for g in ts]), cat([g.edge_tok for g in ts]),
+                cat([g.edge_next for g in ts]), cat([g.accept for g in ts]))
+
+
+def current_items() -> Optional["item_scope"]:
+    return getattr(_tls, "items", None)
+
+
+class item_scope:
+    """context manager: `grammars[i]` (a Grammar, or None: that item decodes unconstrained) is the grammar of prompt i of every generate
+    call the calling thread makes inside the block; scopes nest, other threads are untouched. `grammar_set`: the set the grammars go into
+    (a job passes one set for all its decode groups, so a slot uploads it once); without one the scope owns a set of its own."""
+
+    def __init__(self, grammars: Sequence[Optional[Grammar]], grammar_set: Optional[GrammarSet] = None):
+        self.grammars = list(grammars)
+        self.grammar_set = grammar_set if grammar_set is not None else GrammarSet()
+
+    def __enter__(self):
+        self._prev = current_items()
+        _tls.items = self
+        return self
+
+    def __exit__(self, *exc):
+        _tls.items = self._prev
+        return False
+
+
+def install_items(slot, grammars: Sequence[Optional[Grammar]], grammar_set: GrammarSet) -> List[int]:
+    """Bring `slot` to the per-item route for a generate call over `grammars` (one per prompt, None: unconstrained): every grammar is
+    stored in `grammar_set` (ValueError names a pool limit), the slot uploads the set unless it holds it already, and the table index of
+    every prompt is returned (-1: none) for Slot.select_grammars per decode group. A call none of whose prompts has a grammar keeps a
+    slot that holds THIS set in per-item mode with every item deselected (the kernel then touches no logit), and clears any other slot.
+    A slot that cannot take a set (no `set_grammars`) with one asked for is an error, never a silent unconstrained decode."""
+    idx = [-1 if g is None else grammar_set.add(g) for g in grammars]
+    holds = getattr(slot, "_grammar", None) is grammar_set and getattr(slot, "_grammar_set_version", None) == grammar_set.version
+    if holds:
+        return idx
+    if all(i < 0 for i in idx):
+        if getattr(slot, "_grammar", None) is not None:
+            install(slot, None)
+        return idx
+    if not hasattr(slot, "set_grammars"):
+        raise RuntimeError("a grammar per item asked for, but this slot has no set_grammars")
+    slot.set_grammars(grammar_set)
+    slot._grammar, slot._grammar_set_version, slot._bias_table = grammar_set, grammar_set.version, None
+    return idx

@@ -220,6 +220,62 @@ def fit_tables(wave: List[int], tables: list):
     return wave, (bias_set if len(bias_set) else None)
 
 
+def per_file_grammars(model, grammars, repeat, a: dict, n_files: int) -> list:
+    """the job's `grammars` / `grammars_repeat` -> per file a grammar.Grammar, None (unconstrained) or the ValueError its list was
+    refused with: a limit of the compiler, or a state whose every token the job's `suppress_tokens` / `suppress_blank` remove
+    (Grammar.dead_states). `grammars`: one entry per file, each None or a list of phrases; `grammars_repeat`: one bool or one per file.
+    Equal lists share one Grammar object."""
+    if isinstance(grammars, (str, bytes)) or not isinstance(grammars, (list, tuple)) or len(grammars) != n_files:
+        raise ValueError(f"grammars: a list with one entry per file ({n_files}), each None or a list of phrases; one list for all files is grammar=")
+    if isinstance(repeat, (list, tuple)):
+        if len(repeat) != n_files:
+            raise ValueError(f"grammars_repeat: a list of {len(repeat)} entries for {n_files} files (one entry per file, or one value for all)")
+        repeats = [bool(r) for r in repeat]
+    else:
+        repeats = [bool(repeat)] * n_files
+    if all(g is None for g in grammars):
+        return [None] * n_files
+    if not hasattr(model, "compile_grammar"):
+        raise ValueError("grammars: this transcriber takes no grammar")
+    from .transcriber import get_suppressed_tokens
+    sup = get_suppressed_tokens(model._base_tokenizer, a["suppress_tokens"])
+    blank = model.token_ids.blank if a["suppress_blank"] else None
+    out, seen = [], {}
+    for phrases, rep in zip(grammars, repeats):
+        if phrases is None:
+            out.append(None)
+            continue
+        key = repr((list(phrases) if isinstance(phrases, (list, tuple)) else phrases, rep))
+        if key not in seen:
+            try:
+                g = model.compile_grammar(phrases, rep)
+                dead = g.dead_states(sup, blank)
+                if dead:
+                    raise ValueError(f"every token the grammar allows in state {dead[0]} is one this call suppresses (suppress_tokens"
+                                     f"{', suppress_blank' if dead[0] == 0 and blank is not None else ''}): nothing would be left to emit there")
+                g._checked_for = (model.token_ids.eot, tuple(sup), bool(a["suppress_blank"]))      # (generate does not repeat the check)
+                seen[key] = g
+            except ValueError as e:
+                seen[key] = e
+        out.append(seen[key])
+    return out
+
+
+def fit_grammars(wave: List[int], grammars: list):
+    """the longest head of `wave` whose distinct grammars fit one grammar.GrammarSet (at least one file: a single grammar always fits, its
+    own limits were checked when it was compiled), and that set (None: no file of it has a grammar)"""
+    gset = _grammar.GrammarSet()
+    for k, i in enumerate(wave):
+        g = grammars[i]
+        if g is None or isinstance(g, Exception):
+            continue
+        if k and not gset.fits(g):
+            wave = wave[:k]
+            break
+        gset.add(g)
+    return wave, (gset if len(gset) else None)
+
+
 def per_file_diarizers(pipe, diarize, max_speakers, n_files: int) -> List[tuple]:
     """the `diarize` / `max_speakers` arguments -> one (FileDiarizer or None, cap or None) per file. `diarize`: False | True |
     FileDiarizer, or a list with one of those per file; True is the pipeline's `file_diarizer` (made once from the configured speaker
@@ -277,6 +333,8 @@ class _File:
         self.left = 0                       # chunks not decoded yet
         self.table = None                   # the file's keyword table (biasing.CompactTable) and the set of its wave's tables
         self.bias_set = None
+        self.grammar = None                 # the file's grammar (grammar.Grammar) and the set of its wave's grammars
+        self.grammar_set = None
         self.last_speech = 0.0
 
 
@@ -291,6 +349,9 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     """-> generator of (index, segments: List[Segment], info) — or (index, exception, None) — file by file as the groups finish, in
     input order. `audios`: a sequence of what `transcribe` takes; kwargs: every keyword of `_transcribe`, those of PER_FILE also as a
     list with one entry per file. The arguments are checked here, before the first file is read (module docstring).
+    grammars=[[...], None, [...]]: a closed phrase list PER FILE (None: that file decodes unconstrained), `grammars_repeat` one bool or
+    one per file; every decode group selects the table of each chunk's file (wlx_grammar_select). A refused list costs only its file.
+    `grammar=` stays one list for all files; both, or `grammars` next to keywords / logit_bias, is a ValueError.
     Each job leaves `pipe.many_timing` = {"front_s": seconds its waves spent before their first decode (puts, gate, language),
     "total_s": seconds up to the end of the last wave finished, "waves": waves finished} — what scripts/many_files_time.py reports;
     the next job on the pipeline replaces it.
@@ -301,6 +362,7 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     wave_put = bool(kwargs.pop("wave_put", False))
     bias_args = {name: kwargs.pop(name, None) for name in BIAS_KEYWORDS}
     grammar, grammar_repeat = kwargs.pop("grammar", None), kwargs.pop("grammar_repeat", True)
+    grammars, grammars_repeat = kwargs.pop("grammars", None), kwargs.pop("grammars_repeat", True)
     diarize, max_speakers = kwargs.pop("diarize", False), kwargs.pop("max_speakers", None)
     if kwargs.pop("multichannel", False):
         raise ValueError("transcribe_many: multichannel=True is not part of this route (transcribe the files one by one with "
@@ -327,10 +389,18 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     per_file = per_file_arguments(a, len(audios))
     diarizers = per_file_diarizers(pipe, diarize, max_speakers, len(audios))
     tables = per_file_tables(pipe.model, bias_args, len(audios))        # compiled here, before any audio work
-    job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables)
+    file_grammars = None
+    if grammars is not None:
+        # a grammar PER FILE: the decode groups select the table of each chunk's file; compiled here too
+        if grammar is not None:
+            raise ValueError("grammars (one per file) and grammar (one for all files) in one job: give one of them")
+        if any(v is not None for v in bias_args.values()):
+            raise ValueError("grammars and keywords / logit_bias in one job: a slot decodes under one of them")
+        file_grammars = per_file_grammars(pipe.model, grammars, grammars_repeat, a, len(audios))
+    job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables, file_grammars)
     if grammar is None:
         return job
-    # ONE grammar for all files (a grammar per file is not served: one grammar serves a whole decode group, and groups mix files)
+    # ONE grammar for all files, through the thread's grammar scope (a grammar per file is `grammars=`, above)
     if any(t is not None for t in tables):
         raise ValueError("grammar and keywords / logit_bias in one job: a slot decodes under one of them")
     if not hasattr(pipe.model, "compile_grammar"):
@@ -350,11 +420,12 @@ def _under_grammar(job, gram):
         yield item
 
 
-def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None, tables=None):
+def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None, tables=None, grammars=None):
     model = pipe.model
     tables = tables if tables is not None else [None] * len(audios)
+    grammars = grammars if grammars is not None else [None] * len(audios)
     if on_error == "raise":
-        for t in tables:
+        for t in list(tables) + list(grammars):
             if isinstance(t, Exception):
                 raise t
     timing = pipe.many_timing = {"front_s": 0.0, "total_s": 0.0, "waves": 0}
@@ -380,6 +451,8 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: b
         # an earlier job or another route on this thread's slot — and the chunk gather's reach is measured in rows of THAT length
         wave = next_wave(lengths, at, batch_size, max_batch, stride=int(getattr(slot, "pcm_longest", 0)))
         wave, bias_set = fit_tables(wave, tables)       # (a wave closes early where its distinct tables would overflow a pool cap)
+        # (grammars= and keywords exclude each other in one job, so at most one of the two fits shortens the wave and the other's set is None)
+        wave, grammar_set = fit_grammars(wave, grammars)
         at = wave[-1] + 1
         files = [_File(i, per_file[i], loaded[i], batch_size + k, *(diarizers[i] if diarizers else ())) for k, i in enumerate(wave)]
         for f in files:
@@ -388,6 +461,11 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: b
             else:
                 f.table = tables[f.index]
             f.bias_set = bias_set
+            if isinstance(grammars[f.index], Exception):
+                f.audio = grammars[f.index]             # a refused grammar costs only its file, the same way
+            else:
+                f.grammar = grammars[f.index]
+            f.grammar_set = grammar_set
         for i in wave:
             loaded[i] = None                # (the job does not hold a file's bytes past its wave)
         yield from _wave(pipe, slot, files, a, vad_parameters, batch_size, on_error, timing, wave_put)
@@ -640,6 +718,9 @@ def _decode_group(pipe, slot, group) -> list:
         # carries its own), all of them in the wave's one set; a job without tables decodes as it always did
         biased = group[idx[0]][0].bias_set is not None      # (a group without a table in a wave that has some: every item deselected, the set stays)
         scope = _biasing.item_scope([group[i][0].table for i in idx], group[idx[0]][0].bias_set) if biased else contextlib.nullcontext()
+        # a grammar per file, the same way: an item_scope of the grammars of the files the items come from, in the wave's one set
+        if group[idx[0]][0].grammar_set is not None:
+            scope = _grammar.item_scope([group[i][0].grammar for i in idx], group[idx[0]][0].grammar_set)
         with scope:
             results = model.model.generate(
                 encoder_output if len(idx) == n else encoder_output.select(idx), [prompts[i] for i in idx], beam_size=o.beam_size,

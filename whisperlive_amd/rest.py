@@ -341,8 +341,8 @@ def grammar_scope(transcriber, grammar: Sequence[str], grammar_repeat: Optional[
 
 
 def pool_upload(has_batcher: bool, multichannel: bool, known_speaker_names, known_speaker_references) -> bool:
-    """whether an upload joins the pooled jobs: keywords do not keep it out (each file of a job has its own table); multichannel
-    files and known speakers do"""
+    """whether an upload joins the pooled jobs: neither keywords nor a grammar keep it out (each file of a job has its own table);
+    multichannel files and known speakers do"""
     return bool(has_batcher) and not multichannel and not known_speaker_names and not known_speaker_references
 
 
@@ -365,7 +365,8 @@ class FileBatcher:
         self._thread.start()
 
     def submit(self, transcriber, data: bytes, per_file: dict, shared: dict):
-        up = _Upload(transcriber, (id(transcriber), repr(sorted(shared.items()))), data, per_file, shared)
+        # (a job decodes under keyword tables or under grammars, not both: uploads with a grammar form jobs of their own)
+        up = _Upload(transcriber, (id(transcriber), repr(sorted(shared.items())), bool(per_file.get("grammar"))), data, per_file, shared)
         with self._cv:
             if self._closed:
                 raise RuntimeError("the server is shutting down")
@@ -415,6 +416,8 @@ class FileBatcher:
                        if any(u.per_file.get("diarize") for u in job) else {}),
                     **({"keywords": [u.per_file.get("keywords") for u in job], "keywords_boost": [u.per_file.get("keywords_boost") for u in job]}
                        if any(u.per_file.get("keywords") for u in job) else {}),
+                    **({"grammars": [u.per_file.get("grammar") for u in job], "grammars_repeat": [u.per_file.get("grammar_repeat", True) for u in job]}
+                       if any(u.per_file.get("grammar") for u in job) else {}),
                     **({"wave_put": True} if self.wave_put else {}))
                 for index, segments, info in results:
                     up = job[index]
@@ -606,7 +609,8 @@ class RestServer:
         return BatchedInferencePipeline(transcriber)
 
     def transcribe_pooled(self, transcriber, data: bytes, *, device_index: Optional[int] = None, language=None, initial_prompt=None,
-                          hotwords=None, diarize=None, max_speakers: int = 0, keywords=None, keywords_boost=None, **shared):
+                          hotwords=None, diarize=None, max_speakers: int = 0, keywords=None, keywords_boost=None, grammar=None, grammar_repeat=True,
+                          **shared):
         """`transcribe_file` through the batcher (file_batch_window_ms > 0): the upload joins the uploads that arrive within the window
         and decode with the same `shared` options; -> (list of segments, info) of this upload, or its own error raised here, in the
         request's thread, where the single route would have raised it. Nothing is left for `resident_file_audio` after a pooled job
@@ -614,7 +618,8 @@ class RestServer:
         diarize: the FileDiarizer of a `diarize=true` upload (pooled_file_diarizer) with its max_speakers — the job finds the speakers
         while the wave's files are still resident: the segments and words come back with `.speaker`, the info with `.speakers`."""
         per_file = dict(language=language, initial_prompt=initial_prompt, hotwords=hotwords, diarize=diarize or False, max_speakers=int(max_speakers),
-                        keywords=keywords, keywords_boost=keywords_boost)       # (per file: each upload of a job decodes under its own table)
+                        keywords=keywords, keywords_boost=keywords_boost,       # (per file: each upload of a job decodes under its own table)
+                        grammar=grammar, grammar_repeat=bool(grammar_repeat))   # (... or under its own grammar: iter_many(grammars=))
         return self._batchers.get(device_index, self.batcher).submit(transcriber, data, per_file, shared)
 
     def translator_for(self, device_index: int, target_language: str):
@@ -916,19 +921,22 @@ class _Handler(BaseHTTPRequestHandler):
             # thread under it (the segments may arrive lazily: they are drawn inside the scope); a pooled one carries its keywords into the
             # job, where every file decodes under its own table in the compact form (many_files.py: a decode group takes a table per
             # item) — so that is the form its list is checked in here, and the scope is not entered.
-            # grammar: compiled (and refused: 400) before the file is decoded too. One grammar serves a whole decode group, so an upload with
-            # one is not pooled with other uploads: it is decoded in this thread under its grammar.
+            # grammar: compiled (and refused: 400) before the file is decoded too. An upload that is not pooled is decoded in this thread
+            # under it; a pooled one carries its phrases into a job whose decode groups select a table per item (many_files.py
+            # `grammars=`), and the scope is not entered. (A scope that does not show its compiled grammar — a transcriber
+            # of another kind — keeps the upload in this thread.)
             gram = grammar_scope(transcriber, grammar, grammar_repeat, keywords, keywords_boost)
-            if gram is not None:
+            if gram is not None and getattr(gram, "grammar", None) is None:
                 pooled, pooled_diarizer = False, None
             bias = keyword_scope(transcriber, keywords, keywords_boost, compact=pooled)
-            with (bias if bias is not None and not pooled else contextlib.nullcontext()), (gram if gram is not None else contextlib.nullcontext()):
+            with (bias if bias is not None and not pooled else contextlib.nullcontext()), (gram if gram is not None and not pooled else contextlib.nullcontext()):
                 if pooled:
                     segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
                                                             temperature=temperature, word_timestamps=want_words, hotwords=hotwords,
                                                             diarize=pooled_diarizer, max_speakers=max_speakers,
                                                             keywords=list(keywords) if bias is not None else None,
-                                                            keywords_boost=float(keywords_boost) if bias is not None and keywords_boost is not None and keywords_boost.strip() else None)
+                                                            keywords_boost=float(keywords_boost) if bias is not None and keywords_boost is not None and keywords_boost.strip() else None,
+                                                            **(dict(grammar=list(grammar), grammar_repeat=gram.grammar.repeat) if gram is not None else {}))
                 else:
                     segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
                                                           temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)

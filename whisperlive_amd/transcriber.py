@@ -247,7 +247,28 @@ class _EngineModel:
                 raise ValueError(f"every token the grammar allows in state {dead[0]} is one this call suppresses (suppress_tokens"
                                  f"{', suppress_blank' if dead[0] == 0 and suppress_blank else ''}): nothing would be left to emit there")
             _grammar.install(slot, gram)
-        elif getattr(slot, "_grammar", None) is not None:
+        # a grammar per item: inside a grammar.item_scope every prompt has its own grammar, or none; the set goes up once per
+        # slot, the selection per decode group
+        gram_items = _grammar.current_items()
+        gsel = None
+        if gram_items is not None:
+            if gram is not None or table is not None or scope_items is not None:
+                raise ValueError("a grammar per item next to a grammar or keyword boosting on one slot is not served: decode under one of them")
+            if len(gram_items.grammars) != len(prompts):
+                raise ValueError(f"the item_scope names {len(gram_items.grammars)} grammars for {len(prompts)} prompts")
+            verdict = (o.token_ids.eot, tuple(sup), suppress_blank)     # (checked once per grammar and suppress set, not per decode group)
+            for g in {id(g): g for g in gram_items.grammars if g is not None}.values():
+                if getattr(g, "_checked_for", None) == verdict:
+                    continue
+                if g.eot != o.token_ids.eot:
+                    raise ValueError(f"the grammar was compiled for end-of-text {g.eot}, this model's is {o.token_ids.eot}")
+                dead = g.dead_states(sup, o.token_ids.blank if suppress_blank else None)
+                if dead:
+                    raise ValueError(f"every token the grammar allows in state {dead[0]} is one this call suppresses (suppress_tokens"
+                                     f"{', suppress_blank' if dead[0] == 0 and suppress_blank else ''}): nothing would be left to emit there")
+                g._checked_for = verdict
+            gsel = _grammar.install_items(slot, gram_items.grammars, gram_items.grammar_set)
+        elif gram is None and getattr(slot, "_grammar", None) is not None:
             _grammar.install(slot, None)
         # (under a grammar none of the keyword routes below applies: no table, no item scope, and install has forgotten the slot's table)
         if scope_items is not None:
@@ -262,6 +283,8 @@ class _EngineModel:
         for a in range(0, len(prompts), group):
             if sel is not None:
                 slot.select_bias(sel[a:a + group])
+            if gsel is not None and getattr(slot, "_grammar", None) is gram_items.grammar_set:
+                slot.select_grammars(gsel[a:a + group])
             res.extend(slot.generate(prompts[a:a + group], o.token_ids, beam_size=beam_size, patience=patience,
                                      num_hypotheses=num_hypotheses, length_penalty=length_penalty,
                                      repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -508,8 +531,8 @@ class WhisperModelHIP:
         of a window is a sequence of phrases from the list (`repeat=True`) or one phrase or nothing (`repeat=False`), and nothing else:
         the streaming transcriber, BatchedInferencePipeline.transcribe and the temperature fallback alike. `phrases`: strings or token
         lists (grammar.compile_grammar: a DFA over text tokens; timestamps are transparent). The scores are those of the masked
-        distribution. One grammar for every item of a decode group; a grammar per item, and a grammar together with keyword boosting,
-        are not served (ValueError where both are asked for). ValueError names the limit a list breaks. Other threads are untouched;
+        distribution. One grammar for every item of a decode group (a grammar per item is grammar.item_scope, which
+        transcribe_many(grammars=) uses); a grammar together with keyword boosting is not served (ValueError where both are asked for). ValueError names the limit a list breaks. Other threads are untouched;
         scopes nest."""
         return _grammar.scope(self.compile_grammar(phrases, repeat))
 
