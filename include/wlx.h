@@ -423,7 +423,8 @@ int32_t wlx_bias_clear(wlx_engine* e, int32_t slot);
  * DESIGN.md §27) — is declared in wlx_bias_items.h, which this header includes at its end. So is grammar-constrained decoding — a closed
  * phrase list as a DFA on the slot, whose launch masks where these add (wlx_grammar_set, wlx_grammar_clear) — in wlx_grammar.h,
  * and its per-item form, a pool of DFAs with one selected per item (wlx_grammar_set_items, wlx_grammar_select), in
- * wlx_grammar_items.h. */
+ * wlx_grammar_items.h; and regular-expression grammars, a DFA over the BYTES of the text walked in the decode step (wlx_pattern_set,
+ * wlx_pattern_vocab_set), in wlx_pattern.h. */
 
 /* One decoder step on [sot]; softmax restricted to `lang_ids`; probs_out[batch][n_lang]. */
 int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot,
@@ -1169,6 +1170,7 @@ int32_t wlx_vad_debug_out(wlx_vad* v, const float* hs, int32_t T, float* probs, 
 #include "wlx_bias_items.h"
 #include "wlx_grammar.h"
 #include "wlx_grammar_items.h"
+#include "wlx_pattern.h"
 
 #ifdef __cplusplus
 }

@@ -291,14 +291,22 @@ class BatchedInferencePipeline:
             segments = self._restored(segments, vad_clips[0], self.model.feature_extractor.sampling_rate)
         return segments, info
 
-    def transcribe(self, audio, *args, multichannel: bool = False, target_language: Optional[str] = None, translator=None, **kwargs):
+    def transcribe(self, audio, *args, multichannel: bool = False, target_language: Optional[str] = None, translator=None,
+                   grammar_pattern: Optional[str] = None, grammar_ignore_case: bool = False, **kwargs):
         """The reference's transcribe — every argument of `_transcribe` above, by position or by name — and keyword-only options
         the reference does not have. multichannel=False is `_transcribe`, untouched. multichannel=True: every channel of the file is
         transcribed on its own while the chunks of all channels share the decode groups; segments carry `channel` and come sorted by
         (start, channel) — whisperlive_amd/multichannel.py. target_language (with `translator`, a translation.HipTranslator): the
         segments come back as a LIST, each with `.translation` — the whole file as one translation job (file_translation.py); None
-        changes nothing. (`__wrapped__` below: the signature introspection reports is the reference's, which is what a caller
+        changes nothing. grammar_pattern (with grammar_ignore_case): every window's text fully matches this regular expression
+        (WhisperModelHIP.grammar(pattern=)) — the segments come back as a LIST, decoded inside the pattern's scope.
+        (`__wrapped__` below: the signature introspection reports is the reference's, which is what a caller
         written against the reference binds to.)"""
+        if grammar_pattern is not None:
+            with self.model.grammar(pattern=grammar_pattern, ignore_case=grammar_ignore_case):
+                segments, info = self.transcribe(audio, *args, multichannel=multichannel, target_language=target_language,
+                                                 translator=translator, **kwargs)
+                return list(segments), info
         if target_language is not None:
             from .file_translation import check_target_language, translate_segments
             if translator is None:              # before the file is transcribed, as iter_many refuses it

@@ -258,6 +258,20 @@ struct GrammarItems {
 void launch_dec_grammar_items(float* logits, const SearchParams* sp_dev, int rows, int V, const SearchState& st, const GrammarItems& gi,
                               hipStream_t s);
 
+// ---------------------------------------------------------------- dec_pattern.hip
+// A slot's regular-expression grammar (wlx_pattern_set): a DFA over the BYTES of the text in one block of
+// PATTERN_TABLE_WORDS words at a fixed address (pattern_table.h lays it out and checks it on the host), the engine's vocabulary bytes
+// (wlx_pattern_vocab_set), and the slot's per-(cache row, position) states — the array the bias modes use.
+struct PatternTable {
+    const unsigned* block;      // [PATTERN_TABLE_WORDS], 16-byte aligned: header (n_states, n_classes, eot, cells), class map, trans, accept
+    const int* tok_off;         // [eot + 1] token t's bytes are [tok_off[t], tok_off[t + 1]) of `bytes`
+    const unsigned char* bytes; // 16-byte aligned and padded to a multiple of 16 bytes
+    short* state;               // [cache_rows][448] DFA state of cache row r at position p (BiasTable::state)
+};
+// the grid of launch_dec_grammar: the row's state from its parent's and the fed token's bytes, then every text token whose bytes cannot be
+// walked from that state (and end-of-text unless it accepts) becomes -inf; nothing else is written
+void launch_dec_pattern(float* logits, const SearchParams* sp_dev, int rows, int V, const SearchState& st, const PatternTable& p, hipStream_t s);
+
 // softmax over ids [0, vlim) of row r, probability of token toks[r] -> out[r]   (text_token_probs of Whisper.align)
 void launch_token_prob_rows(const float* logits, long ldl, int vlim, int rows, const int* toks, float* out, hipStream_t s);
 // softmax prob of token `tok` in given logits rows -> out[rows]

@@ -16,9 +16,9 @@
 namespace wlx {
 
 // the launch of a slot's decode step between the vocabulary projection and the search: none, keyword boosting with one table or a table per
-// item, or a grammar (wlx_grammar_set: masks where the others add) or a grammar per item (wlx_grammar_set_items). One mode at a time: the
-// last set call decides.
-enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3, BIAS_GRAMMAR_ITEMS = 4 };
+// item, or a grammar (wlx_grammar_set: masks where the others add) or a grammar per item (wlx_grammar_set_items), or a regular-expression
+// grammar over the text's bytes (wlx_pattern_set). One mode at a time: the last set call decides.
+enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3, BIAS_GRAMMAR_ITEMS = 4, BIAS_PATTERN = 5 };
 
 // what a captured decode-step graph depends on (engine_decode.hip get_step_graph)
 struct StepGraphKey {
@@ -26,7 +26,8 @@ struct StepGraphKey {
     bool busy, sampling;
     int bias;                   // BiasMode of the slot: the step launches dec_bias_kernel (one table: wlx_bias_set) or dec_bias_items_kernel (per item:
                                 // wlx_bias_set_items) or dec_grammar_kernel (wlx_grammar_set) or dec_grammar_items_kernel (per item:
-                                // wlx_grammar_set_items) in front of the search, or nothing; a graph captured for one mode is never replayed
+                                // wlx_grammar_set_items) or dec_pattern_kernel (wlx_pattern_set) in front of the search, or nothing; a graph
+                                // captured for one mode is never replayed
                                 // for another
     bool operator<(const StepGraphKey& o) const {
         return std::tie(rows, R, groups, nsteps, busy, sampling, bias) < std::tie(o.rows, o.R, o.groups, o.nsteps, o.busy, o.sampling, o.bias);
@@ -120,6 +121,9 @@ struct Slot {
     // allocated at the first wlx_grammar_set_items and kept at those addresses. The selection is d_sel / h_sel / sel_n / ev_sel above, which
     // the two per-item modes share (a set call of either deselects every item). `gpool_eot`: the end-of-text id the pool was checked against
     GrammarItems grammar_items{}; int* d_gpool = nullptr; int* h_gpool = nullptr; int grammar_tables = 0, gpool_eot = -1;
+    // a regular-expression grammar (wlx_pattern_set / wlx_pattern_clear; dec_pattern.hip): the table's device block and its pinned staging,
+    // allocated at the first wlx_pattern_set and kept at those addresses; the vocabulary bytes are the engine's, the states are `bias_state`
+    PatternTable pattern{}; unsigned* d_pattern = nullptr; unsigned* h_pattern = nullptr; int pattern_eot = -1;
     unsigned* d_suppress = nullptr;
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging
@@ -197,6 +201,10 @@ struct Engine {
     std::mutex mu;
     std::vector<Slot*> slots;
     bool use_graph = true;
+    // the vocabulary's byte strings (wlx_pattern_vocab_set; dec_pattern.hip), uploaded once under `mu` and never moved: d_tok_off [eot + 1],
+    // d_tok_bytes padded to a multiple of 16 bytes; the host copies answer a second call (identical: nothing to do, else WLX_ERR_STATE)
+    int* d_tok_off = nullptr; unsigned char* d_tok_bytes = nullptr; int pattern_vocab_eot = -1;
+    std::vector<int32_t> h_tok_off; std::vector<uint8_t> h_tok_bytes;
 };
 
 }  // namespace wlx

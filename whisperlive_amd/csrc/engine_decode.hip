@@ -2,6 +2,7 @@
 // wlx_generate, language detection and word alignment (engine.hip: slots, audio, encoder; engine.h: what the files share).
 #include "engine.h"
 #include "grammar_pool.h"
+#include "pattern_table.h"
 #include <sched.h>
 #include <limits>
 #include <algorithm>
@@ -338,12 +339,14 @@ static int graph_steps_for(const Slot* s, int rows) {
 // row's bias to its logits (dec_bias.hip); a slot without a table launches nothing here, so its step is the launch list it always was. In
 // per-item mode (wlx_bias_set_items) the launch is dec_bias_items_kernel: the table selected for the row's item (wlx_bias_select). With a
 // grammar (wlx_grammar_set) it is dec_grammar_kernel (dec_grammar.hip), which masks where the others add; with a pool of grammars
-// (wlx_grammar_set_items) dec_grammar_items_kernel, under the table selected for the row's item (wlx_grammar_select).
+// (wlx_grammar_set_items) dec_grammar_items_kernel, under the table selected for the row's item (wlx_grammar_select); with a
+// regular-expression grammar (wlx_pattern_set) dec_pattern_kernel (dec_pattern.hip), which walks every text token's bytes.
 void wlx::launch_bias(Slot* s, int rows) {
     if (s->bias_mode == BIAS_ONE) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
     else if (s->bias_mode == BIAS_ITEMS) launch_dec_bias_items(s->logits, s->d_sp, rows, s->st, s->bias_items, s->stream);
     else if (s->bias_mode == BIAS_GRAMMAR) launch_dec_grammar(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->grammar, s->stream);
     else if (s->bias_mode == BIAS_GRAMMAR_ITEMS) launch_dec_grammar_items(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->grammar_items, s->stream);
+    else if (s->bias_mode == BIAS_PATTERN) launch_dec_pattern(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->pattern, s->stream);
 }
 
 static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps) {
@@ -675,6 +678,8 @@ int wlx::generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, co
         return set_error(WLX_ERR_STATE, "generate: %d items, but the bias selection covers %d (wlx_bias_select)", batch, s->sel_n);
     if (s->bias_mode == BIAS_GRAMMAR && o->ids.eot != s->grammar_eot)
         return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's grammar was compiled for %d (wlx_grammar_set)", o->ids.eot, s->grammar_eot);
+    if (s->bias_mode == BIAS_PATTERN && o->ids.eot != s->pattern_eot)
+        return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's pattern was compiled for %d (wlx_pattern_set)", o->ids.eot, s->pattern_eot);
     if (s->bias_mode == BIAS_GRAMMAR_ITEMS && batch > s->sel_n)
         return set_error(WLX_ERR_STATE, "generate: %d items, but the grammar selection covers %d (wlx_grammar_select)", batch, s->sel_n);
     if (s->bias_mode == BIAS_GRAMMAR_ITEMS && o->ids.eot != s->gpool_eot)
@@ -967,6 +972,77 @@ extern "C" int32_t wlx_grammar_select(wlx_engine* e, int32_t slot, int32_t n, co
             return set_error(WLX_ERR_ARG, "grammar select: item %d names table %d outside -1..%d", b, table_of_item[b], s->grammar_tables - 1);
     CK(hipSetDevice(e->device));
     return bias_select_upload(s, n, table_of_item);
+}
+
+// ---- regular-expression grammars (include/wlx_pattern.h; dec_pattern.hip). The vocabulary's bytes belong to the engine: they go up once,
+// complete on return, and never move, so every slot's table and every captured step graph may name them.
+extern "C" int32_t wlx_pattern_vocab_set(wlx_engine* e, int32_t eot, const int32_t* tok_off, const uint8_t* bytes) {
+    if (!e) return set_error(WLX_ERR_ARG, "null argument");
+    char why[200];
+    if (!pattern_vocab_check(e->spec.vocab, eot, tok_off, bytes, why, sizeof(why))) return set_error(WLX_ERR_ARG, "%s", why);
+    const size_t n_bytes = (size_t)tok_off[eot];
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->d_tok_off) {
+        const bool same = eot == e->pattern_vocab_eot && !memcmp(tok_off, e->h_tok_off.data(), sizeof(int32_t) * ((size_t)eot + 1)) &&
+                          (n_bytes == 0 || !memcmp(bytes, e->h_tok_bytes.data(), n_bytes));
+        if (same) return WLX_OK;
+        return set_error(WLX_ERR_STATE, "pattern vocabulary: the engine holds other vocabulary bytes already (they are set once)");
+    }
+    CK(hipSetDevice(e->device));
+    const size_t padded = (n_bytes + 15) / 16 * 16 + 16;        // the kernel stages whole 16-byte pieces
+    std::vector<int32_t> off(tok_off, tok_off + eot + 1);
+    std::vector<uint8_t> host(padded, 0);
+    if (n_bytes) memcpy(host.data(), bytes, n_bytes);
+    int* d_off = nullptr;
+    unsigned char* d_bytes = nullptr;
+    CKR(dalloc(e->allocs, &d_off, (size_t)eot + 1, false));
+    CKR(dalloc(e->allocs, &d_bytes, padded, false));
+    CKR(upload_sync(d_off, off.data(), sizeof(int32_t) * off.size()));
+    CKR(upload_sync(d_bytes, host.data(), padded));
+    e->h_tok_off.swap(off); e->h_tok_bytes.swap(host);
+    e->d_tok_off = d_off; e->d_tok_bytes = d_bytes; e->pattern_vocab_eot = eot;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_pattern_set(wlx_engine* e, int32_t slot, int32_t eot, int32_t n_states, int32_t n_classes, const uint8_t* byte_class,
+                                   const uint16_t* trans, const uint8_t* accept) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    // a refused table leaves whatever is installed whole (and allocates nothing)
+    int vocab_eot;
+    { std::lock_guard<std::mutex> lk(e->mu); vocab_eot = e->d_tok_off ? e->pattern_vocab_eot : -1; }
+    if (vocab_eot < 0) return set_error(WLX_ERR_STATE, "pattern: the engine has no vocabulary bytes yet (wlx_pattern_vocab_set)");
+    char why[200];
+    if (!pattern_table_check(e->spec.vocab, eot, n_states, n_classes, byte_class, trans, accept, why, sizeof(why))) return set_error(WLX_ERR_ARG, "%s", why);
+    if (eot != vocab_eot) return set_error(WLX_ERR_ARG, "pattern: end-of-text is %d, the vocabulary bytes were set for %d (wlx_pattern_vocab_set)", eot, vocab_eot);
+    CK(hipSetDevice(e->device));
+    CKR(bias_state_alloc(s));
+    if (!s->d_pattern) {
+        unsigned *blk = nullptr, *stage = nullptr;
+        CKR(dalloc(s->allocs, &blk, (size_t)PATTERN_TABLE_WORDS, true));
+        CKR(halloc(s->host_allocs, &stage, (size_t)PATTERN_TABLE_WORDS));
+        memset(stage, 0, sizeof(unsigned) * PATTERN_TABLE_WORDS);
+        s->d_pattern = blk; s->h_pattern = stage;
+        s->pattern = PatternTable{blk, e->d_tok_off, e->d_tok_bytes, s->bias_state};
+    }
+    // the staging may still feed the copy of the previous pattern: wait for the stream, then rewrite it
+    CK(hipStreamSynchronize(s->stream));
+    const int used = pattern_table_pack(s->h_pattern, eot, n_states, n_classes, byte_class, trans, accept);
+    // (the used parts only: everything up to the last cell, and the accept flags at their fixed place)
+    CK(hipMemcpyAsync(s->d_pattern, s->h_pattern, sizeof(unsigned) * (size_t)used, hipMemcpyHostToDevice, s->stream));
+    CK(hipMemcpyAsync(s->d_pattern + PATTERN_ACCEPT_AT, s->h_pattern + PATTERN_ACCEPT_AT, sizeof(unsigned) * (size_t)((n_states + 3) / 4),
+                      hipMemcpyHostToDevice, s->stream));
+    s->pattern_eot = eot;
+    s->bias_mode = BIAS_PATTERN;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_pattern_clear(wlx_engine* e, int32_t slot) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    if (sg_.s->bias_mode == BIAS_PATTERN) sg_.s->bias_mode = BIAS_NONE;         // (a table of another mode installed since stays)
+    return WLX_OK;
 }
 
 extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot, const int32_t* lang_ids,

@@ -82,6 +82,17 @@ class HipWhisperEngine:
         together from the interleaved packets in their wire format (_lib.PCM_*)."""
         return PcmRingGroup(self, fmt, channels, rate, capacity_samples)
 
+    def set_pattern_vocab(self, eot: int, tok_off: np.ndarray, tok_bytes: np.ndarray) -> None:
+        """The byte strings of the text tokens 0 .. eot - 1 (pattern.token_bytes), engine-wide and set once (wlx_pattern_vocab_set): what
+        the pattern launch of every slot walks. The same contents again are not sent again; other contents are refused (ERR_STATE)."""
+        with self._lock:
+            if getattr(self, "_pattern_vocab", None) is tok_bytes:
+                return
+            off = np.ascontiguousarray(tok_off, dtype=np.int32)
+            by = np.ascontiguousarray(tok_bytes, dtype=np.uint8)
+            check(self.lib.wlx_pattern_vocab_set(self._h, int(eot), _i32p(off), by.ctypes.data_as(C.POINTER(C.c_uint8))))
+            self._pattern_vocab, self.pattern_vocab_eot = tok_bytes, int(eot)
+
     def create_slot(self, max_batch: int = 1, max_rows_per_item: int = 5) -> "Slot":
         sid = C.c_int32(-1)
         check(self.lib.wlx_slot_create(self._h, max_batch, max_rows_per_item, C.byref(sid)))
@@ -621,7 +632,7 @@ class Slot:
         ids, vals = np.ascontiguousarray(table.tok_ids, dtype=np.int32), np.ascontiguousarray(table.tok_vals, dtype=np.float32)
         check(self.lib.wlx_bias_set(self.engine._h, self.sid, table.n_nodes, _i32p(off), _i32p(tok), _i32p(nxt), float(table.boost),
                                     ids.size, _i32p(ids), _f32p(vals)))
-        self._bias_table, self._grammar = table, None       # (one mode at a time: the last set call decides)
+        self._bias_table, self._grammar, self._pattern = table, None, None      # (one mode at a time: the last set call decides)
 
     def set_bias_items(self, bias_set) -> None:
         """Install a biasing.BiasSet on the slot (wlx_bias_set_items): the slot decodes in per-item mode, every item deselected until
@@ -633,7 +644,7 @@ class Slot:
         nn, off, tok, nxt, boosts, nt, ids, vals = bias_set.packed()
         check(self.lib.wlx_bias_set_items(self.engine._h, self.sid, len(bias_set), _i32p(nn), _i32p(off), _i32p(tok), _i32p(nxt),
                                           _f32p(boosts), _i32p(nt), _i32p(ids), _f32p(vals)))
-        self._bias_table, self._bias_set_version, self._grammar = bias_set, bias_set.version, None
+        self._bias_table, self._bias_set_version, self._grammar, self._pattern = bias_set, bias_set.version, None, None
 
     def select_bias(self, indices: Sequence[int]) -> None:
         """indices[b]: the table (an index into the installed set, -1: none) of item b of the following generate calls (wlx_bias_select)"""
@@ -643,7 +654,7 @@ class Slot:
     def clear_bias(self) -> None:
         """Decode without a bias table again (wlx_bias_clear)."""
         check(self.lib.wlx_bias_clear(self.engine._h, self.sid))
-        self._bias_table = self._grammar = None
+        self._bias_table = self._grammar = self._pattern = None
 
     # ---- grammar-constrained decoding
     def set_grammar(self, grammar) -> None:
@@ -655,7 +666,7 @@ class Slot:
             raise ValueError(f"the grammar was compiled for a vocabulary of {grammar.vocab}, the model has {self.engine.spec.vocab}")
         off, tok, nxt, acc = (np.ascontiguousarray(a, dtype=np.int32) for a in (grammar.edge_off, grammar.edge_tok, grammar.edge_next, grammar.accept))
         check(self.lib.wlx_grammar_set(self.engine._h, self.sid, int(grammar.eot), grammar.n_states, _i32p(off), _i32p(tok), _i32p(nxt), _i32p(acc)))
-        self._grammar, self._bias_table = grammar, None
+        self._grammar, self._bias_table, self._pattern = grammar, None, None
 
     def clear_grammar(self) -> None:
         """Decode without a grammar again (wlx_grammar_clear): the step is the launch list of a slot that never had one."""
@@ -672,12 +683,32 @@ class Slot:
         ns, off, tok, nxt, acc = grammar_set.packed()
         check(self.lib.wlx_grammar_set_items(self.engine._h, self.sid, int(grammar_set.eot), len(grammar_set), _i32p(ns), _i32p(off), _i32p(tok),
                                              _i32p(nxt), _i32p(acc)))
-        self._grammar, self._grammar_set_version, self._bias_table = grammar_set, grammar_set.version, None
+        self._grammar, self._grammar_set_version, self._bias_table, self._pattern = grammar_set, grammar_set.version, None, None
 
     def select_grammars(self, indices: Sequence[int]) -> None:
         """indices[b]: the grammar (an index into the installed set, -1: none) of item b of the following generate calls (wlx_grammar_select)"""
         sel = np.ascontiguousarray(list(indices), dtype=np.int32)
         check(self.lib.wlx_grammar_select(self.engine._h, self.sid, sel.size, _i32p(sel)))
+
+    # ---- regular-expression grammars
+    def set_pattern(self, pattern) -> None:
+        """Install a pattern.Pattern on the slot (wlx_pattern_set): every decode step of its generate calls, and of the debug_search
+        hooks, then runs the pattern launch in front of the search, in place of a keyword table's or a grammar's (one mode at a time).
+        The engine holds the vocabulary's bytes by then (HipWhisperEngine.set_pattern_vocab; pattern.install sends them). The buffers
+        sit at fixed addresses: captured step graphs are re-used across patterns. WlxError for a table the library refuses (ERR_ARG) or
+        an engine without vocabulary bytes (ERR_STATE); what is installed stays."""
+        u8p = C.POINTER(C.c_uint8)
+        cls, acc = (np.ascontiguousarray(a, dtype=np.uint8) for a in (pattern.byte_class, pattern.accept))
+        trans = np.ascontiguousarray(pattern.trans, dtype=np.uint16)
+        eot = getattr(self.engine, "pattern_vocab_eot", -1)
+        check(self.lib.wlx_pattern_set(self.engine._h, self.sid, int(eot), pattern.n_states, pattern.n_classes, cls.ctypes.data_as(u8p),
+                                       trans.ctypes.data_as(C.POINTER(C.c_uint16)), acc.ctypes.data_as(u8p)))
+        self._pattern, self._grammar, self._bias_table = pattern, None, None
+
+    def clear_pattern(self) -> None:
+        """Decode without a pattern again (wlx_pattern_clear): the step is the launch list of a slot that never had one."""
+        check(self.lib.wlx_pattern_clear(self.engine._h, self.sid))
+        self._pattern = None
 
     def align(self, tokens: Sequence[int], n_sot: int, num_frames: int, heads: Sequence[Tuple[int, int]], eot: int,
               median_filter_width: int = 7, item: int = 0):

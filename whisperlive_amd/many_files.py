@@ -64,6 +64,7 @@ import numpy as np
 
 from . import biasing as _biasing
 from . import grammar as _grammar
+from . import pattern as _pattern
 from . import vad as _vad
 from . import word_timing as _wt
 from .batched import MAX_DEC_ROWS, DeviceChunks, _collect_ranges, _file_bytes, _options, _put_audio, _put_audio_many, _segment, _vad_options
@@ -352,6 +353,9 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     grammars=[[...], None, [...]]: a closed phrase list PER FILE (None: that file decodes unconstrained), `grammars_repeat` one bool or
     one per file; every decode group selects the table of each chunk's file (wlx_grammar_select). A refused list costs only its file.
     `grammar=` stays one list for all files; both, or `grammars` next to keywords / logit_bias, is a ValueError.
+    grammar_pattern=r"..." (with grammar_ignore_case): ONE regular expression for all files (pattern.compile_pattern).
+    A pattern per file or per item, a pattern together with keyword boosting and a pattern together with a phrase list are out of scope:
+    each a ValueError.
     Each job leaves `pipe.many_timing` = {"front_s": seconds its waves spent before their first decode (puts, gate, language),
     "total_s": seconds up to the end of the last wave finished, "waves": waves finished} — what scripts/many_files_time.py reports;
     the next job on the pipeline replaces it.
@@ -363,6 +367,17 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     bias_args = {name: kwargs.pop(name, None) for name in BIAS_KEYWORDS}
     grammar, grammar_repeat = kwargs.pop("grammar", None), kwargs.pop("grammar_repeat", True)
     grammars, grammars_repeat = kwargs.pop("grammars", None), kwargs.pop("grammars_repeat", True)
+    grammar_pattern, grammar_ignore_case = kwargs.pop("grammar_pattern", None), kwargs.pop("grammar_ignore_case", False)
+    pat = None
+    if grammar_pattern is not None:
+        # compiled (and refused) here, before the first file is read
+        if not isinstance(grammar_pattern, str):
+            raise ValueError("grammar_pattern: one regular expression for all files (a pattern per file or per item is out of scope)")
+        if grammar is not None or grammars is not None:
+            raise ValueError("grammar_pattern and grammar / grammars in one job: a pattern together with a phrase list is out of scope")
+        if any(v is not None for v in bias_args.values()):
+            raise ValueError("grammar_pattern and keywords / logit_bias in one job: a pattern together with keyword boosting is out of scope")
+        pat = _pattern.compile_pattern(grammar_pattern, ignore_case=bool(grammar_ignore_case))
     diarize, max_speakers = kwargs.pop("diarize", False), kwargs.pop("max_speakers", None)
     if kwargs.pop("multichannel", False):
         raise ValueError("transcribe_many: multichannel=True is not part of this route (transcribe the files one by one with "
@@ -398,6 +413,8 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
             raise ValueError("grammars and keywords / logit_bias in one job: a slot decodes under one of them")
         file_grammars = per_file_grammars(pipe.model, grammars, grammars_repeat, a, len(audios))
     job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables, file_grammars)
+    if pat is not None:
+        return _under_grammar(job, pat, _pattern.scope)
     if grammar is None:
         return job
     # ONE grammar for all files, through the thread's grammar scope (a grammar per file is `grammars=`, above)
@@ -408,11 +425,11 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     return _under_grammar(job, pipe.model.compile_grammar(grammar, grammar_repeat))
 
 
-def _under_grammar(job, gram):
-    """`job`, every step of it taken under the calling thread's grammar scope (left again before the file is handed out)"""
+def _under_grammar(job, gram, scope=_grammar.scope):
+    """`job`, every step of it taken under the calling thread's grammar scope — or pattern scope — (left again before the file is handed out)"""
     it = iter(job)
     while True:
-        with _grammar.scope(gram):
+        with scope(gram):
             try:
                 item = next(it)
             except StopIteration:

@@ -318,11 +318,29 @@ class _Upload:
         self.done, self.result, self.error = threading.Event(), None, None
 
 
-def grammar_scope(transcriber, grammar: Sequence[str], grammar_repeat: Optional[str], keywords=None, keywords_boost=None):
+def grammar_scope(transcriber, grammar: Sequence[str], grammar_repeat: Optional[str], keywords=None, keywords_boost=None,
+                  grammar_pattern: Optional[str] = None, grammar_ignore_case: Optional[str] = None):
     """The `grammar` (repeatable: one phrase per field) and `grammar_repeat` form fields -> the context manager under which the upload
     is decoded (WhisperModelHIP.grammar on the request's thread), or None without a grammar. 400: a repeat flag that is no boolean or
     comes without a grammar, an empty phrase, a grammar together with keywords, a list past a limit (the message names it: states,
-    edges), a transcriber that takes no grammar."""
+    edges), a transcriber that takes no grammar.
+    `grammar_pattern` (one regular expression) with `grammar_ignore_case`: the scope of WhisperModelHIP.grammar(pattern=)
+    — it shows no compiled phrase list, so the upload is decoded in the request's thread. 400 with the compiler's message for a pattern
+    it refuses; a pattern together with grammar fields or keywords is out of scope (400)."""
+    if grammar_ignore_case is not None and grammar_ignore_case.strip() and not (grammar_pattern and grammar_pattern.strip()):
+        raise _HttpError(400, {"error": "grammar_ignore_case needs grammar_pattern"})
+    if grammar_pattern is not None and grammar_pattern.strip():
+        ignore_case = parse_bool_field(grammar_ignore_case, "grammar_ignore_case") if grammar_ignore_case is not None and grammar_ignore_case.strip() else False
+        if grammar or (grammar_repeat is not None and grammar_repeat.strip()):
+            raise _HttpError(400, {"error": "grammar_pattern cannot be combined with grammar: a pattern together with a phrase list is out of scope"})
+        if keywords or (keywords_boost is not None and keywords_boost.strip()):
+            raise _HttpError(400, {"error": "grammar_pattern cannot be combined with keywords: a pattern together with keyword boosting is out of scope"})
+        if not hasattr(transcriber, "grammar"):
+            raise _HttpError(400, {"error": "grammar_pattern: this server's transcriber takes no grammar"})
+        try:
+            return transcriber.grammar(pattern=grammar_pattern, ignore_case=ignore_case)
+        except (ValueError, TypeError) as e:
+            raise _HttpError(400, {"error": f"grammar_pattern: {e}"})
     repeat = True
     if grammar_repeat is not None and grammar_repeat.strip():
         repeat = parse_bool_field(grammar_repeat, "grammar_repeat")
@@ -868,6 +886,7 @@ class _Handler(BaseHTTPRequestHandler):
         known_speaker_names = many("known_speaker_names") + many("known_speaker_names[]")
         keywords, keywords_boost = many("keywords") + many("keywords[]"), one("keywords_boost")
         grammar, grammar_repeat = many("grammar") + many("grammar[]"), one("grammar_repeat")
+        grammar_pattern, grammar_ignore_case = one("grammar_pattern"), one("grammar_ignore_case")
         known_speaker_references = fields.get("known_speaker_references", []) + fields.get("known_speaker_references[]", [])
         want_words = bool(timestamp_granularities and "word" in timestamp_granularities)
         rest = self.rest
@@ -877,7 +896,7 @@ class _Handler(BaseHTTPRequestHandler):
                 raise _HttpError(400, {"error": "multichannel cannot be combined with stream: send the request without stream"})
             if keywords or keywords_boost:
                 raise _HttpError(400, {"error": "keywords cannot be combined with stream: send the request without stream"})
-            if grammar or grammar_repeat:
+            if grammar or grammar_repeat or grammar_pattern:
                 raise _HttpError(400, {"error": "grammar cannot be combined with stream: send the request without stream"})
             return self._stream(file, language, prompt, temperature, want_words, target_language)
 
@@ -925,7 +944,7 @@ class _Handler(BaseHTTPRequestHandler):
             # under it; a pooled one carries its phrases into a job whose decode groups select a table per item (many_files.py
             # `grammars=`), and the scope is not entered. (A scope that does not show its compiled grammar — a transcriber
             # of another kind — keeps the upload in this thread.)
-            gram = grammar_scope(transcriber, grammar, grammar_repeat, keywords, keywords_boost)
+            gram = grammar_scope(transcriber, grammar, grammar_repeat, keywords, keywords_boost, grammar_pattern, grammar_ignore_case)
             if gram is not None and getattr(gram, "grammar", None) is None:
                 pooled, pooled_diarizer = False, None
             bias = keyword_scope(transcriber, keywords, keywords_boost, compact=pooled)

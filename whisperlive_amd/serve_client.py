@@ -431,6 +431,26 @@ def grammar_options(transcriber, grammar, grammar_repeat, keywords=None, keyword
     return transcriber.grammar(phrases=list(grammar), repeat=True if grammar_repeat is None else grammar_repeat)
 
 
+def pattern_options(transcriber, grammar_pattern, grammar_ignore_case, grammar=None, grammar_repeat=None, keywords=None, keywords_boost=None):
+    """`grammar_pattern` (one regular expression) and `grammar_ignore_case` (a boolean, optional) of a session's first
+    message -> the scope under which the session decodes (WhisperModelHIP.grammar(pattern=)). ValueError: not a non-empty string, a
+    flag that is no boolean or comes without a pattern, a pattern together with a phrase list or with keywords (out of scope), a
+    pattern the compiler refuses (its message names the construct or the limit), a transcriber that takes no grammar."""
+    if grammar_pattern is None:
+        raise ValueError("grammar_ignore_case needs grammar_pattern")
+    if not isinstance(grammar_pattern, str) or not grammar_pattern.strip():
+        raise ValueError("grammar_pattern must be a non-empty string (a pattern per item is out of scope)")
+    if grammar_ignore_case is not None and not isinstance(grammar_ignore_case, bool):
+        raise ValueError("grammar_ignore_case must be a boolean")
+    if grammar is not None or grammar_repeat is not None:
+        raise ValueError("grammar_pattern cannot be combined with grammar: a pattern together with a phrase list is out of scope")
+    if keywords or keywords_boost is not None:
+        raise ValueError("grammar_pattern cannot be combined with keywords: a pattern together with keyword boosting is out of scope")
+    if not hasattr(transcriber, "grammar"):
+        raise ValueError("this server's transcriber takes no grammar")
+    return transcriber.grammar(pattern=grammar_pattern, ignore_case=bool(grammar_ignore_case))
+
+
 class ServeClientHIP(ServeClientBase):
     """Backend adaptor for the MI355X engine. Class-level registries mirror the reference's SINGLE_MODEL /
     BATCH_WORKER hooks (faster_whisper_backend.py:15-17) but are keyed by GPU: one shared transcriber per device."""
@@ -450,7 +470,7 @@ class ServeClientHIP(ServeClientBase):
                  translation_queue=None, hotwords=None, diarization=None, word_timestamps=False, *,
                  device_index: int = 0, transcriber=None, model_factory=None, serialize_single_model: bool = False,
                  start_thread: bool = True, max_batch: int = 1, keywords=None, keywords_boost=None, grammar=None,
-                 grammar_repeat=None):
+                 grammar_repeat=None, grammar_pattern=None, grammar_ignore_case=None):
         super().__init__(client_uid, websocket, send_last_n_segments, no_speech_thresh, clip_audio, same_output_threshold,
                          translation_queue, diarization, word_timestamps)
         self.cache_path = cache_path
@@ -485,7 +505,17 @@ class ServeClientHIP(ServeClientBase):
                                             "message": f"Failed to load model: {str(self.model_size_or_path)}"}))
             self.websocket.close()
             return
-        if grammar is not None or grammar_repeat is not None:
+        if grammar_pattern is not None or grammar_ignore_case is not None:
+            # `grammar_pattern` / `grammar_ignore_case` of the first message: compiled once, here; refused the way a refused phrase list is
+            try:
+                self._grammar = pattern_options(self.transcriber, grammar_pattern, grammar_ignore_case, grammar, grammar_repeat, keywords, keywords_boost)
+            except (ValueError, TypeError) as e:
+                logging.error(f"grammar_pattern refused for {self.client_uid}: {e}")
+                self.websocket.send(json.dumps({"uid": self.client_uid, "status": "ERROR", "message": f"Unsupported grammar: {e}"}))
+                self.websocket.close()
+                del self.transcriber            # (what the server reads as "no session")
+                return
+        elif grammar is not None or grammar_repeat is not None:
             # `grammar` / `grammar_repeat` of the first message: compiled once, here; a refused list ends the session with the limit named
             try:
                 self._grammar = grammar_options(self.transcriber, grammar, grammar_repeat, keywords, keywords_boost)

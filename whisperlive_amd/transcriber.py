@@ -32,6 +32,7 @@ import numpy as np
 from . import _lib
 from . import biasing as _biasing
 from . import grammar as _grammar
+from . import pattern as _pattern
 from . import vad as _vad
 from . import word_timing as _wt
 from ._lib import ERR_ARG as _ERR_ARG, ERR_DATA as _ERR_DATA, WlxError as _WlxError
@@ -270,6 +271,21 @@ class _EngineModel:
             gsel = _grammar.install_items(slot, gram_items.grammars, gram_items.grammar_set)
         elif gram is None and getattr(slot, "_grammar", None) is not None:
             _grammar.install(slot, None)
+        # a regular-expression grammar (WhisperModelHIP.grammar(pattern=)): a DFA over the text's bytes, one for every item
+        pat = _pattern.current()
+        if pat is not None:
+            if table is not None or scope_items is not None:
+                raise ValueError("a pattern together with keyword boosting is out of scope: decode under one of them")
+            if gram is not None or gram_items is not None:
+                raise ValueError("a pattern together with a phrase list is out of scope: decode under one of them")
+            tok_off, tok_bytes = _pattern.token_bytes(o._base_tokenizer, o.token_ids.eot)
+            dead = pat.dead_states(tok_off, tok_bytes, sup, o.token_ids.blank if suppress_blank else None)
+            if dead:
+                raise ValueError(f"every token the grammar allows in state {dead[0]} is one this call suppresses (suppress_tokens"
+                                 f"{', suppress_blank' if dead[0] == 0 and suppress_blank else ''}): nothing would be left to emit there")
+            _pattern.install(slot, pat, (o.token_ids.eot, tok_off, tok_bytes))
+        elif getattr(slot, "_pattern", None) is not None:
+            _pattern.install(slot, None)
         # (under a grammar none of the keyword routes below applies: no table, no item scope, and install has forgotten the slot's table)
         if scope_items is not None:
             if len(scope_items.tables) != len(prompts):
@@ -526,14 +542,22 @@ class WhisperModelHIP:
         refuses (its edge cap binds at a few dozen phrases); the same tokens and scores where both forms load."""
         return _biasing.scope(self.compile_keywords(phrases, boost, logit_bias, compact=compact))
 
-    def grammar(self, phrases=None, repeat: bool = True):
-        """Context manager: inside the block every generate of the CALLING THREAD decodes under this grammar on its slot — the transcript
+    def grammar(self, phrases=None, repeat: bool = True, *, pattern: Optional[str] = None, ignore_case: bool = False):
+        """`pattern=r"..."` (with `ignore_case`): a regular expression in place of a phrase list — every window's text fully matches it
+        (pattern.compile_pattern names the syntax; a DFA over the text's BYTES, so every tokenisation is admitted and `\\d{8}` is nine
+        states). Together with `phrases` it raises a ValueError. One pattern for every item; a pattern per file or per
+        item, a pattern together with keyword boosting and a pattern together with a phrase list are out of scope (ValueError).
+        Context manager: inside the block every generate of the CALLING THREAD decodes under this grammar on its slot — the transcript
         of a window is a sequence of phrases from the list (`repeat=True`) or one phrase or nothing (`repeat=False`), and nothing else:
         the streaming transcriber, BatchedInferencePipeline.transcribe and the temperature fallback alike. `phrases`: strings or token
         lists (grammar.compile_grammar: a DFA over text tokens; timestamps are transparent). The scores are those of the masked
         distribution. One grammar for every item of a decode group (a grammar per item is grammar.item_scope, which
         transcribe_many(grammars=) uses); a grammar together with keyword boosting is not served (ValueError where both are asked for). ValueError names the limit a list breaks. Other threads are untouched;
         scopes nest."""
+        if pattern is not None:
+            if phrases is not None:
+                raise ValueError("grammar: a pattern together with a phrase list is out of scope: give phrases= or pattern=")
+            return _pattern.scope(_pattern.compile_pattern(pattern, ignore_case=ignore_case))
         return _grammar.scope(self.compile_grammar(phrases, repeat))
 
     def compile_grammar(self, phrases=None, repeat: bool = True):
@@ -682,7 +706,20 @@ class WhisperModelHIP:
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    *, keywords=None, keywords_boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None,
                    keywords_compact: bool = False, grammar=None,
-                   grammar_repeat: bool = True) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
+                   grammar_repeat: bool = True, grammar_pattern: Optional[str] = None,
+                   grammar_ignore_case: bool = False) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
+        if grammar_pattern is not None:
+            # a regular expression for this call alone (see `grammar`): compiled before any audio work, so a refused pattern costs nothing
+            if keywords is not None or logit_bias is not None:
+                raise ValueError("grammar_pattern and keywords / logit_bias in one call: a pattern together with keyword boosting is out of scope")
+            with self.grammar(phrases=grammar, pattern=grammar_pattern, ignore_case=grammar_ignore_case):
+                return self.transcribe(audio, language, task, log_progress, beam_size, best_of, patience, length_penalty, repetition_penalty,
+                                       no_repeat_ngram_size, temperature, compression_ratio_threshold, log_prob_threshold,
+                                       no_speech_threshold, condition_on_previous_text, prompt_reset_on_temperature, initial_prompt, prefix,
+                                       suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp, word_timestamps,
+                                       prepend_punctuations, append_punctuations, multilingual, vad_filter, vad_parameters, max_new_tokens,
+                                       chunk_length, clip_timestamps, hallucination_silence_threshold, hotwords,
+                                       language_detection_threshold, language_detection_segments)
         if grammar is not None:
             # a closed phrase list for this call alone (see `grammar`): compiled before any audio work, so a refused list costs nothing
             if keywords is not None or logit_bias is not None:
