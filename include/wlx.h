@@ -424,7 +424,8 @@ int32_t wlx_bias_clear(wlx_engine* e, int32_t slot);
  * phrase list as a DFA on the slot, whose launch masks where these add (wlx_grammar_set, wlx_grammar_clear) — in wlx_grammar.h,
  * and its per-item form, a pool of DFAs with one selected per item (wlx_grammar_set_items, wlx_grammar_select), in
  * wlx_grammar_items.h; and regular-expression grammars, a DFA over the BYTES of the text walked in the decode step (wlx_pattern_set,
- * wlx_pattern_vocab_set), in wlx_pattern.h. */
+ * wlx_pattern_vocab_set), in wlx_pattern.h, with their per-item form, a pool of byte DFAs with one selected per item
+ * (wlx_pattern_set_items, wlx_pattern_select), in wlx_pattern_items.h. */
 
 /* One decoder step on [sot]; softmax restricted to `lang_ids`; probs_out[batch][n_lang]. */
 int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot,
@@ -1171,6 +1172,7 @@ int32_t wlx_vad_debug_out(wlx_vad* v, const float* hs, int32_t T, float* probs, 
 #include "wlx_grammar.h"
 #include "wlx_grammar_items.h"
 #include "wlx_pattern.h"
+#include "wlx_pattern_items.h"
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,8 @@ EXPORTS_GRAMMAR = ["wlx_grammar_set", "wlx_grammar_clear", "wlx_debug_grammar_ap
 EXPORTS_GRAMMAR_ITEMS = ["wlx_grammar_set_items", "wlx_grammar_select", "wlx_debug_grammar_apply_items"]
 # regular-expression grammars, declared in include/wlx_pattern.h (which wlx.h includes)
 EXPORTS_PATTERN = ["wlx_pattern_vocab_set", "wlx_pattern_set", "wlx_pattern_clear", "wlx_debug_pattern_apply"]
+# a pattern per item, declared in include/wlx_pattern_items.h (which wlx.h includes)
+EXPORTS_PATTERN_ITEMS = ["wlx_pattern_set_items", "wlx_pattern_select", "wlx_debug_pattern_apply_items"]
 
 
 # MFMA accumulators in VGPRs (gfx950 has ONE register file; hipcc's default puts C/D in its AGPR half): every VALU touch of
@@ -163,6 +165,8 @@ GRAMMAR_MAX_STATES, GRAMMAR_MAX_EDGES = 4096, 16384      # wlx_grammar.h WLX_GRA
 GRAMMAR_SET_MAX_TABLES, GRAMMAR_SET_MAX_STATES, GRAMMAR_SET_MAX_EDGES = 64, 16384, 65536
 # wlx_pattern.h WLX_PATTERN_MAX_*: the caps of a pattern table (wlx_pattern_set) and of the vocabulary bytes (wlx_pattern_vocab_set)
 PATTERN_MAX_STATES, PATTERN_MAX_CELLS, PATTERN_MAX_TOKEN_BYTES, PATTERN_MAX_VOCAB_BYTES = 4096, 24576, 255, 1 << 22
+# wlx_pattern_items.h WLX_PATTERN_SET_MAX_*: tables of one set (wlx_pattern_set_items) and the caps of its pool over all tables
+PATTERN_SET_MAX_TABLES, PATTERN_SET_MAX_CELLS, PATTERN_SET_MAX_STATES = 64, 393216, 65536
 PATTERN_DEAD = 0xFFFF   # a transition into no state
 DEBUG_GUARD = 64        # wlx.h WLX_DEBUG_GUARD: words a debug hook's output carries past what the kernel owns
 MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
@@ -343,7 +347,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
     except OSError as e:  # e.g. libamdhip64 missing
         raise WlxError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS + EXPORTS_PATTERN if not hasattr(lib, s)]
+    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS + EXPORTS_PATTERN + EXPORTS_PATTERN_ITEMS if not hasattr(lib, s)]
     if missing:
         raise WlxError(f"libwlx.so lacks symbols {missing}")
     i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p
@@ -512,6 +516,14 @@ def load() -> C.CDLL:
         lib.wlx_pattern_clear.argtypes = [vp, i32]
         lib.wlx_debug_pattern_apply.argtypes = [i32, i32, i32, i32, i32, u8p, u16p_, u8p, i32p, u8p, f32p, i32, i64, i32p, i32p, i32p, i32, i32p, i16p, i16p]
         for name in EXPORTS_PATTERN:
+            getattr(lib, name).restype = i32
+    if EXPORTS_PATTERN_ITEMS:       # (scripts/pattern_items_time.py alone empties the list, to load a library of the parent commit beside this one)
+        u8p, u16p_ = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
+        lib.wlx_pattern_set_items.argtypes = [vp, i32, i32, i32, i32p, i32p, u8p, u16p_, u8p]
+        lib.wlx_pattern_select.argtypes = [vp, i32, i32, i32p]
+        lib.wlx_debug_pattern_apply_items.argtypes = [i32, i32, i32, i32, i32p, i32p, u8p, u16p_, u8p, i32p, u8p, f32p, i32, i32, i32p, i64, i32p, i32p,
+                                                      i32p, i32p, i32p, i16p, i16p]
+        for name in EXPORTS_PATTERN_ITEMS:
             getattr(lib, name).restype = i32
     for name in EXPORTS + EXPORTS_BIAS_ITEMS + EXPORTS_GRAMMAR:
         fn = getattr(lib, name)

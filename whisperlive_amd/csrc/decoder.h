@@ -271,6 +271,20 @@ struct PatternTable {
 // the grid of launch_dec_grammar: the row's state from its parent's and the fed token's bytes, then every text token whose bytes cannot be
 // walked from that state (and end-of-text unless it accepts) becomes -inf; nothing else is written
 void launch_dec_pattern(float* logits, const SearchParams* sp_dev, int rows, int V, const SearchState& st, const PatternTable& p, hipStream_t s);
+// A pattern per item (wlx_pattern_set_items): up to PATTERN_SET_MAX_TABLES byte DFAs in one pool of PATTERN_POOL_WORDS words
+// at a fixed address (pattern_table.h lays it out and checks it on the host), the selection, the engine's vocabulary bytes and the same
+// states — local to the item's table.
+struct PatternItems {
+    const unsigned* pool;       // [PATTERN_POOL_WORDS], 16-byte aligned: a header per table slot, the class maps, trans, accept
+    const int* sel;             // [max_batch] table of item b of the decode group, -1: none
+    const int* tok_off;         // PatternTable::tok_off
+    const unsigned char* bytes; // PatternTable::bytes
+    short* state;               // the slot's [cache_rows][448] states (BiasTable::state)
+};
+// (items x ceil(V / GRAMMAR_TILE)) workgroups: ONE workgroup stages its item's table and its tile's bytes once and walks every beam row of
+// the item out of them, with dec_pattern_kernel's semantics per row; an item without a table has its states written as 0, nothing else
+void launch_dec_pattern_items(float* logits, const SearchParams* sp_dev, int items, int V, const SearchState& st, const PatternItems& pi,
+                              hipStream_t s);
 
 // softmax over ids [0, vlim) of row r, probability of token toks[r] -> out[r]   (text_token_probs of Whisper.align)
 void launch_token_prob_rows(const float* logits, long ldl, int vlim, int rows, const int* toks, float* out, hipStream_t s);

@@ -17,8 +17,8 @@ namespace wlx {
 
 // the launch of a slot's decode step between the vocabulary projection and the search: none, keyword boosting with one table or a table per
 // item, or a grammar (wlx_grammar_set: masks where the others add) or a grammar per item (wlx_grammar_set_items), or a regular-expression
-// grammar over the text's bytes (wlx_pattern_set). One mode at a time: the last set call decides.
-enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3, BIAS_GRAMMAR_ITEMS = 4, BIAS_PATTERN = 5 };
+// grammar over the text's bytes (wlx_pattern_set) or one per item (wlx_pattern_set_items). One mode at a time: the last set call decides.
+enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3, BIAS_GRAMMAR_ITEMS = 4, BIAS_PATTERN = 5, BIAS_PATTERN_ITEMS = 6 };
 
 // what a captured decode-step graph depends on (engine_decode.hip get_step_graph)
 struct StepGraphKey {
@@ -26,7 +26,8 @@ struct StepGraphKey {
     bool busy, sampling;
     int bias;                   // BiasMode of the slot: the step launches dec_bias_kernel (one table: wlx_bias_set) or dec_bias_items_kernel (per item:
                                 // wlx_bias_set_items) or dec_grammar_kernel (wlx_grammar_set) or dec_grammar_items_kernel (per item:
-                                // wlx_grammar_set_items) or dec_pattern_kernel (wlx_pattern_set) in front of the search, or nothing; a graph
+                                // wlx_grammar_set_items) or dec_pattern_kernel (wlx_pattern_set) or dec_pattern_items_kernel (per item:
+                                // wlx_pattern_set_items) in front of the search, or nothing; a graph
                                 // captured for one mode is never replayed
                                 // for another
     bool operator<(const StepGraphKey& o) const {
@@ -124,6 +125,9 @@ struct Slot {
     // a regular-expression grammar (wlx_pattern_set / wlx_pattern_clear; dec_pattern.hip): the table's device block and its pinned staging,
     // allocated at the first wlx_pattern_set and kept at those addresses; the vocabulary bytes are the engine's, the states are `bias_state`
     PatternTable pattern{}; unsigned* d_pattern = nullptr; unsigned* h_pattern = nullptr; int pattern_eot = -1;
+    // a pattern per item (wlx_pattern_set_items / wlx_pattern_select; dec_pattern.hip dec_pattern_items_kernel): the pool and its pinned staging,
+    // allocated at the first wlx_pattern_set_items and kept at those addresses; the selection is the one the per-item modes share (d_sel)
+    PatternItems pattern_items{}; unsigned* d_ppool = nullptr; unsigned* h_ppool = nullptr; int pattern_tables = 0, ppool_eot = -1;
     unsigned* d_suppress = nullptr;
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging
@@ -280,7 +284,7 @@ int prefill_tokens(Engine* e, Slot* s, int item, int crow, const int* tokens, in
                    float* nsp_out);
 int set_anc_rows(Slot* s, const std::vector<short>& anc_host, int first_row, int nrows);
 void launch_search(Engine* e, Slot* s, int rows, int R, int groups, bool sampling);
-void launch_bias(Slot* s, int rows);                       // in front of launch_search: nothing without a bias table
+void launch_bias(Slot* s, int rows, int R);                     // in front of launch_search: nothing without a bias table
 int generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, const int32_t* plens, int pstride, const int32_t* enc_items,
                   const wlx_gen_opts* o, bool injected_logits, const float* inj, int inj_steps, int32_t* tokens_out, int tstride,
                   int32_t* n_tokens_out, float* scores_out, float* nsp_out);

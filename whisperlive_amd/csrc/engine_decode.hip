@@ -340,19 +340,21 @@ static int graph_steps_for(const Slot* s, int rows) {
 // per-item mode (wlx_bias_set_items) the launch is dec_bias_items_kernel: the table selected for the row's item (wlx_bias_select). With a
 // grammar (wlx_grammar_set) it is dec_grammar_kernel (dec_grammar.hip), which masks where the others add; with a pool of grammars
 // (wlx_grammar_set_items) dec_grammar_items_kernel, under the table selected for the row's item (wlx_grammar_select); with a
-// regular-expression grammar (wlx_pattern_set) dec_pattern_kernel (dec_pattern.hip), which walks every text token's bytes.
-void wlx::launch_bias(Slot* s, int rows) {
+// regular-expression grammar (wlx_pattern_set) dec_pattern_kernel (dec_pattern.hip), which walks every text token's bytes; with a pool of
+// them (wlx_pattern_set_items) dec_pattern_items_kernel, one workgroup per (item, tile) where the others take one per (row, tile).
+void wlx::launch_bias(Slot* s, int rows, int R) {
     if (s->bias_mode == BIAS_ONE) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
     else if (s->bias_mode == BIAS_ITEMS) launch_dec_bias_items(s->logits, s->d_sp, rows, s->st, s->bias_items, s->stream);
     else if (s->bias_mode == BIAS_GRAMMAR) launch_dec_grammar(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->grammar, s->stream);
     else if (s->bias_mode == BIAS_GRAMMAR_ITEMS) launch_dec_grammar_items(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->grammar_items, s->stream);
     else if (s->bias_mode == BIAS_PATTERN) launch_dec_pattern(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->pattern, s->stream);
+    else if (s->bias_mode == BIAS_PATTERN_ITEMS) launch_dec_pattern_items(s->logits, s->d_sp, rows / R, (int)s->ldl, s->st, s->pattern_items, s->stream);
 }
 
 static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps) {
     for (int k = 0; k < nsteps; ++k) {
         decoder_pass(e, s, s->step, rows, R, groups, true, true);
-        launch_bias(s, rows);
+        launch_bias(s, rows, R);
         launch_search(e, s, rows, R, groups, sampling);
     }
 }
@@ -597,7 +599,7 @@ static int gen_loop(Engine* e, Slot* s, int batch, int R, bool sampling, int max
             launch_dec_embed(e->tok_emb16, e->dec_pos, e->spec.d_model, rt, rows, sb.xd, nullptr, st);
             CK(hipMemcpy2DAsync(s->logits, (size_t)s->ldl * 4, inj + (size_t)step * rows * V, (size_t)V * 4, (size_t)V * 4, rows,
                                 hipMemcpyHostToDevice, st));
-            launch_bias(s, rows);
+            launch_bias(s, rows, R);
             launch_search(e, s, rows, R, batch, sampling);
             CK(hipGetLastError());
         } else {
@@ -684,6 +686,10 @@ int wlx::generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, co
         return set_error(WLX_ERR_STATE, "generate: %d items, but the grammar selection covers %d (wlx_grammar_select)", batch, s->sel_n);
     if (s->bias_mode == BIAS_GRAMMAR_ITEMS && o->ids.eot != s->gpool_eot)
         return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's grammars were compiled for %d (wlx_grammar_set_items)", o->ids.eot, s->gpool_eot);
+    if (s->bias_mode == BIAS_PATTERN_ITEMS && batch > s->sel_n)
+        return set_error(WLX_ERR_STATE, "generate: %d items, but the pattern selection covers %d (wlx_pattern_select)", batch, s->sel_n);
+    if (s->bias_mode == BIAS_PATTERN_ITEMS && o->ids.eot != s->ppool_eot)
+        return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's patterns were compiled for %d (wlx_pattern_set_items)", o->ids.eot, s->ppool_eot);
     static const bool gen_trace = getenv("WLX_GEN_TRACE") != nullptr;
     double tg[2] = {0.0, 0.0};                                  // WLX_GEN_TRACE: host time in graph launch calls / in the polling waits
     const double tg0 = now_us();
@@ -1041,8 +1047,66 @@ extern "C" int32_t wlx_pattern_set(wlx_engine* e, int32_t slot, int32_t eot, int
 extern "C" int32_t wlx_pattern_clear(wlx_engine* e, int32_t slot) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
-    if (sg_.s->bias_mode == BIAS_PATTERN) sg_.s->bias_mode = BIAS_NONE;         // (a table of another mode installed since stays)
+    if (sg_.s->bias_mode == BIAS_PATTERN || sg_.s->bias_mode == BIAS_PATTERN_ITEMS) sg_.s->bias_mode = BIAS_NONE;      // (a table of another mode installed since stays)
     return WLX_OK;
+}
+
+// ---- a pattern per item (include/wlx_pattern_items.h; dec_pattern.hip dec_pattern_items_kernel). The pool and its pinned staging are allocated
+// at the first call and stay where they are, like the selection (select_alloc): a step graph captured in this mode replays with every later
+// set and selection.
+extern "C" int32_t wlx_pattern_set_items(wlx_engine* e, int32_t slot, int32_t eot, int32_t n_tables, const int32_t* n_states, const int32_t* n_classes,
+                                         const uint8_t* byte_class, const uint16_t* trans, const uint8_t* accept) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    // a refused set leaves whatever is installed whole (and allocates nothing): checked and packed into a host copy first
+    int vocab_eot;
+    { std::lock_guard<std::mutex> lk(e->mu); vocab_eot = e->d_tok_off ? e->pattern_vocab_eot : -1; }
+    if (vocab_eot < 0) return set_error(WLX_ERR_STATE, "pattern set: the engine has no vocabulary bytes yet (wlx_pattern_vocab_set)");
+    char why[280];
+    int cells = 0, states = 0;
+    if (!pattern_pool_check(e->spec.vocab, eot, n_tables, n_states, n_classes, byte_class, trans, accept, &cells, &states, why, sizeof(why)))
+        return set_error(WLX_ERR_ARG, "%s", why);
+    if (eot != vocab_eot) return set_error(WLX_ERR_ARG, "pattern set: end-of-text is %d, the vocabulary bytes were set for %d (wlx_pattern_vocab_set)", eot, vocab_eot);
+    std::vector<uint32_t> pool((size_t)PATTERN_POOL_WORDS);
+    pattern_pool_pack(pool.data(), n_tables, n_states, n_classes, byte_class, trans, accept);
+    CK(hipSetDevice(e->device));
+    CKR(bias_state_alloc(s));
+    CKR(select_alloc(s));
+    if (!s->d_ppool) {
+        unsigned *dp = nullptr, *hp = nullptr;
+        CKR(dalloc(s->allocs, &dp, (size_t)PATTERN_POOL_WORDS, true));
+        CKR(halloc(s->host_allocs, &hp, (size_t)PATTERN_POOL_WORDS));
+        s->d_ppool = dp; s->h_ppool = hp;
+        s->pattern_items = PatternItems{dp, s->d_sel, e->d_tok_off, e->d_tok_bytes, s->bias_state};
+    }
+    CK(hipStreamSynchronize(s->stream));         // the pool's staging may still feed the copies of the previous set
+    // (the used parts only: the headers and the class maps, which lie together, then the cells up to the last table's pad, then the accept bytes)
+    const struct { int at, n; } parts[3] = {{0, PATTERN_POOL_CLASS_AT + 64 * n_tables}, {PATTERN_POOL_TRANS_AT, ((cells + 7) / 8 * 8) / 2},
+                                            {PATTERN_POOL_ACCEPT_AT, (states + 3) / 4}};
+    for (const auto& part : parts) {
+        memcpy(s->h_ppool + part.at, pool.data() + part.at, sizeof(unsigned) * (size_t)part.n);
+        CK(hipMemcpyAsync(s->d_ppool + part.at, s->h_ppool + part.at, sizeof(unsigned) * (size_t)part.n, hipMemcpyHostToDevice, s->stream));
+    }
+    s->pattern_tables = n_tables;
+    s->ppool_eot = eot;
+    CKR(bias_select_upload(s, s->B, nullptr));   // every item deselected: a table index of an earlier set never reaches this one
+    s->bias_mode = BIAS_PATTERN_ITEMS;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_pattern_select(wlx_engine* e, int32_t slot, int32_t n, const int32_t* table_of_item) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (s->bias_mode != BIAS_PATTERN_ITEMS) return set_error(WLX_ERR_STATE, "pattern select: no pattern set installed (wlx_pattern_set_items)");
+    if (!table_of_item) return set_error(WLX_ERR_ARG, "null argument");
+    if (n < 1 || n > s->B) return set_error(WLX_ERR_ARG, "pattern select: %d items outside 1..%d", n, s->B);
+    for (int b = 0; b < n; ++b)
+        if (table_of_item[b] < -1 || table_of_item[b] >= s->pattern_tables)
+            return set_error(WLX_ERR_ARG, "pattern select: item %d names table %d outside -1..%d", b, table_of_item[b], s->pattern_tables - 1);
+    CK(hipSetDevice(e->device));
+    return bias_select_upload(s, n, table_of_item);
 }
 
 extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot, const int32_t* lang_ids,

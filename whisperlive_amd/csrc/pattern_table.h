@@ -58,6 +58,77 @@ inline int pattern_table_pack(uint32_t* block, int eot, int n_states, int n_clas
     return PATTERN_TRANS_AT + (cells + 1) / 2;
 }
 
+// ---- a POOL of tables (wlx_pattern_set_items; dec_pattern.hip dec_pattern_items_kernel): up to PATTERN_SET_MAX_TABLES tables, each within
+// the limits of one table above. In 32-bit words, every part at a fixed place: one header of PATTERN_POOL_HDR_WORDS words per table SLOT
+// (first cell, first accept byte, n_states, n_classes; n_states 0: no table); the 256-byte class maps, one per slot; the trans arrays
+// back to back as uint16 cells, EACH starting on a 16-byte boundary (a multiple of 8 cells: the kernel copies a table with 16-byte loads,
+// so a 1 x 1 table in front must not misalign the next — the region holds the pad of every table on top of the cap); the accept bytes
+// back to back. A state stays a number local to its table.
+constexpr int PATTERN_SET_MAX_TABLES = 64;      // include/wlx_pattern_items.h WLX_PATTERN_SET_MAX_TABLES
+constexpr int PATTERN_SET_MAX_CELLS = 393216;   // WLX_PATTERN_SET_MAX_CELLS, over all tables: sixteen tables at the per-table cap, 768 KiB
+constexpr int PATTERN_SET_MAX_STATES = 65536;   // WLX_PATTERN_SET_MAX_STATES, over all tables
+constexpr int PATTERN_POOL_HDR_WORDS = 4;
+constexpr int PATTERN_POOL_CLASS_AT = PATTERN_SET_MAX_TABLES * PATTERN_POOL_HDR_WORDS;
+constexpr int PATTERN_POOL_TRANS_AT = PATTERN_POOL_CLASS_AT + PATTERN_SET_MAX_TABLES * (256 / 4);
+constexpr int PATTERN_POOL_TRANS_CELLS = PATTERN_SET_MAX_CELLS + 8 * PATTERN_SET_MAX_TABLES;
+constexpr int PATTERN_POOL_ACCEPT_AT = PATTERN_POOL_TRANS_AT + PATTERN_POOL_TRANS_CELLS / 2;
+constexpr int PATTERN_POOL_WORDS = PATTERN_POOL_ACCEPT_AT + PATTERN_SET_MAX_STATES / 4;
+
+// the format of include/wlx_pattern_items.h, violation by violation: true with the totals in *cells_out (the pads included: the cells the
+// trans region holds up to the last table's end) and *states_out, or false with the reason in `msg`. A table's arrays are read only after
+// the tables before it passed and the totals so far are within the caps.
+inline bool pattern_pool_check(int V, int eot, int n_tables, const int32_t* n_states, const int32_t* n_classes, const uint8_t* byte_class,
+                               const uint16_t* trans, const uint8_t* accept, int* cells_out, int* states_out, char* msg, size_t msg_len) {
+    auto fail = [&](const char* fmt, long a, long b) { if (msg && msg_len) snprintf(msg, msg_len, fmt, a, b); return false; };
+    if (V < 1 || eot < 1 || eot >= V) return fail("pattern set: eot %ld outside 1..%ld (the vocabulary)", eot, (long)V - 1);
+    if (n_tables < 1 || n_tables > PATTERN_SET_MAX_TABLES) return fail("pattern set: %ld tables outside 1..%ld", n_tables, PATTERN_SET_MAX_TABLES);
+    if (!n_states || !n_classes || !byte_class || !trans || !accept) return fail("pattern set: null argument", 0, 0);
+    long cells = 0, states = 0, padded = 0;
+    for (int t = 0; t < n_tables; ++t) {
+        const long ns = n_states[t], nc = n_classes[t];
+        char why[200] = "";
+        // (the counts first, without the arrays: the totals decide whether this table's cells may be read at all)
+        if (ns < 1 || ns > PATTERN_MAX_STATES || nc < 1 || nc > 256 || ns * nc > PATTERN_MAX_CELLS) {
+            pattern_table_check(V, eot, (int)ns, (int)nc, nullptr, nullptr, nullptr, why, sizeof(why));
+            if (msg && msg_len) snprintf(msg, msg_len, "pattern set: table %d: %s", t, why);
+            return false;
+        }
+        if (cells + ns * nc > PATTERN_SET_MAX_CELLS) return fail("pattern set: more than %ld cells in all (at table %ld)", PATTERN_SET_MAX_CELLS, t);
+        if (states + ns > PATTERN_SET_MAX_STATES) return fail("pattern set: more than %ld states in all (at table %ld)", PATTERN_SET_MAX_STATES, t);
+        if (!pattern_table_check(V, eot, (int)ns, (int)nc, byte_class + (size_t)t * 256, trans + cells, accept + states, why, sizeof(why))) {
+            if (msg && msg_len) snprintf(msg, msg_len, "pattern set: table %d: %s", t, why);
+            return false;
+        }
+        cells += ns * nc;
+        states += ns;
+        padded = (padded + 7) / 8 * 8 + ns * nc;
+    }
+    if (cells_out) *cells_out = (int)padded;
+    if (states_out) *states_out = (int)states;
+    return true;
+}
+
+// a CHECKED set into a block of PATTERN_POOL_WORDS words. The used parts: [0, CLASS_AT + 64 * n_tables) words, the cells pattern_pool_check
+// counted at TRANS_AT, `states` bytes at ACCEPT_AT; the headers of the table slots behind n_tables are zeroed, and so is every pad
+inline void pattern_pool_pack(uint32_t* block, int n_tables, const int32_t* n_states, const int32_t* n_classes, const uint8_t* byte_class,
+                              const uint16_t* trans, const uint8_t* accept) {
+    memset(block, 0, sizeof(uint32_t) * (size_t)PATTERN_POOL_CLASS_AT);
+    memcpy(block + PATTERN_POOL_CLASS_AT, byte_class, (size_t)n_tables * 256);
+    uint16_t* cells = reinterpret_cast<uint16_t*>(block + PATTERN_POOL_TRANS_AT);
+    uint8_t* acc = reinterpret_cast<uint8_t*>(block + PATTERN_POOL_ACCEPT_AT);
+    int src = 0, at = 0, sb = 0;
+    for (int t = 0; t < n_tables; ++t) {
+        const int n = n_states[t] * n_classes[t];
+        while (at & 7) cells[at++] = 0;         // the table starts on a 16-byte boundary
+        uint32_t* hdr = block + t * PATTERN_POOL_HDR_WORDS;
+        hdr[0] = (uint32_t)at; hdr[1] = (uint32_t)sb; hdr[2] = (uint32_t)n_states[t]; hdr[3] = (uint32_t)n_classes[t];
+        memcpy(cells + at, trans + src, sizeof(uint16_t) * (size_t)n);
+        memcpy(acc + sb, accept + sb, (size_t)n_states[t]);
+        src += n; at += n; sb += n_states[t];
+    }
+    while (at & 7) cells[at++] = 0;             // (the kernel's last 16-byte load of the last table)
+}
+
 // the vocabulary's byte strings (wlx_pattern_vocab_set): tok_off[eot + 1] starts at 0 and ascends, no token longer than
 // PATTERN_MAX_TOKEN_BYTES, at most PATTERN_MAX_VOCAB_BYTES bytes in all
 inline bool pattern_vocab_check(int V, int eot, const int32_t* tok_off, const uint8_t* bytes, char* msg, size_t msg_len) {

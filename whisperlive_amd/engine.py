@@ -710,6 +710,24 @@ class Slot:
         check(self.lib.wlx_pattern_clear(self.engine._h, self.sid))
         self._pattern = None
 
+    def set_patterns(self, pattern_set) -> None:
+        """Install a pattern.PatternSet on the slot (wlx_pattern_set_items): the slot decodes in per-item pattern mode, every item
+        deselected (unconstrained) until `select_patterns`. The engine holds the vocabulary's bytes by then, as for `set_pattern`.
+        WlxError (ERR_ARG) for a set the library refuses; whatever is installed stays."""
+        if len(pattern_set) < 1:
+            raise ValueError("an empty PatternSet installs nothing: clear_pattern")
+        ns, nc, cls, trans, acc = pattern_set.packed()
+        u8p = C.POINTER(C.c_uint8)
+        eot = getattr(self.engine, "pattern_vocab_eot", -1)
+        check(self.lib.wlx_pattern_set_items(self.engine._h, self.sid, int(eot), len(pattern_set), _i32p(ns), _i32p(nc), cls.ctypes.data_as(u8p),
+                                             trans.ctypes.data_as(C.POINTER(C.c_uint16)), acc.ctypes.data_as(u8p)))
+        self._pattern, self._pattern_set_version, self._grammar, self._bias_table = pattern_set, pattern_set.version, None, None
+
+    def select_patterns(self, indices: Sequence[int]) -> None:
+        """indices[b]: the pattern (an index into the installed set, -1: none) of item b of the following generate calls (wlx_pattern_select)"""
+        sel = np.ascontiguousarray(list(indices), dtype=np.int32)
+        check(self.lib.wlx_pattern_select(self.engine._h, self.sid, sel.size, _i32p(sel)))
+
     def align(self, tokens: Sequence[int], n_sot: int, num_frames: int, heads: Sequence[Tuple[int, int]], eot: int,
               median_filter_width: int = 7, item: int = 0):
         """ctranslate2 Whisper.align for one encoded item: tokens = start_sequence + [no_timestamps] + text + [eot].

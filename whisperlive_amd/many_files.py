@@ -277,6 +277,63 @@ def fit_grammars(wave: List[int], grammars: list):
     return wave, (gset if len(gset) else None)
 
 
+def per_file_patterns(model, patterns, ignore_case, a: dict, n_files: int) -> list:
+    """the job's `grammar_patterns` / `grammar_patterns_ignore_case` -> per file a pattern.Pattern, None (unconstrained) or the ValueError
+    its expression was refused with: by the compiler, or for a state whose every token the job's `suppress_tokens` / `suppress_blank`
+    remove (Pattern.dead_states). One entry per file, each None or a regular expression; the flag one bool or one per file. Equal
+    expressions share one Pattern object."""
+    if isinstance(patterns, (str, bytes)) or not isinstance(patterns, (list, tuple)) or len(patterns) != n_files:
+        raise ValueError(f"grammar_patterns: a list with one entry per file ({n_files}), each None or a regular expression; one expression "
+                         "for all files is grammar_pattern=")
+    if isinstance(ignore_case, (list, tuple)):
+        if len(ignore_case) != n_files:
+            raise ValueError(f"grammar_patterns_ignore_case: a list of {len(ignore_case)} entries for {n_files} files (one entry per file, or one value for all)")
+        flags = [bool(v) for v in ignore_case]
+    else:
+        flags = [bool(ignore_case)] * n_files
+    if all(p is None for p in patterns):
+        return [None] * n_files
+    if not hasattr(model, "_base_tokenizer"):
+        raise ValueError("grammar_patterns: this transcriber takes no pattern")
+    from .transcriber import get_suppressed_tokens
+    sup = get_suppressed_tokens(model._base_tokenizer, a["suppress_tokens"])
+    blank = model.token_ids.blank if a["suppress_blank"] else None
+    tok_off, tok_bytes = _pattern.token_bytes(model._base_tokenizer, model.token_ids.eot)
+    out, seen = [], {}
+    for regex, flag in zip(patterns, flags):
+        if regex is None:
+            out.append(None)
+            continue
+        key = (regex, flag) if isinstance(regex, str) else (id(regex), flag)
+        if key not in seen:
+            try:
+                pat = _pattern.compile_pattern(regex, ignore_case=flag)
+                dead = pat.dead_states(tok_off, tok_bytes, sup, blank)
+                if dead:
+                    raise ValueError(f"every token the grammar allows in state {dead[0]} is one this call suppresses (suppress_tokens"
+                                     f"{', suppress_blank' if dead[0] == 0 and blank is not None else ''}): nothing would be left to emit there")
+                seen[key] = pat
+            except ValueError as e:
+                seen[key] = e
+        out.append(seen[key])
+    return out
+
+
+def fit_patterns(wave: List[int], patterns: list):
+    """the longest head of `wave` whose distinct patterns fit one pattern.PatternSet (at least one file: a single pattern always fits, its
+    own limits were checked when it was compiled), and that set (None: no file of it has a pattern)"""
+    pset = _pattern.PatternSet()
+    for k, i in enumerate(wave):
+        p = patterns[i]
+        if p is None or isinstance(p, Exception):
+            continue
+        if k and not pset.fits(p):
+            wave = wave[:k]
+            break
+        pset.add(p)
+    return wave, (pset if len(pset) else None)
+
+
 def per_file_diarizers(pipe, diarize, max_speakers, n_files: int) -> List[tuple]:
     """the `diarize` / `max_speakers` arguments -> one (FileDiarizer or None, cap or None) per file. `diarize`: False | True |
     FileDiarizer, or a list with one of those per file; True is the pipeline's `file_diarizer` (made once from the configured speaker
@@ -336,6 +393,8 @@ class _File:
         self.bias_set = None
         self.grammar = None                 # the file's grammar (grammar.Grammar) and the set of its wave's grammars
         self.grammar_set = None
+        self.pattern = None                 # the file's pattern (pattern.Pattern) and the set of its wave's patterns
+        self.pattern_set = None
         self.last_speech = 0.0
 
 
@@ -354,8 +413,10 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     one per file; every decode group selects the table of each chunk's file (wlx_grammar_select). A refused list costs only its file.
     `grammar=` stays one list for all files; both, or `grammars` next to keywords / logit_bias, is a ValueError.
     grammar_pattern=r"..." (with grammar_ignore_case): ONE regular expression for all files (pattern.compile_pattern).
-    A pattern per file or per item, a pattern together with keyword boosting and a pattern together with a phrase list are out of scope:
-    each a ValueError.
+    grammar_patterns=[r"...", None, r"..."]: a regular expression PER FILE (None: unconstrained), `grammar_patterns_ignore_case` one bool
+    or one per file; every decode group selects the table of each chunk's file (wlx_pattern_select). An expression the
+    compiler refuses, or one with a state the job's suppress list empties, costs only its file. Both pattern arguments in one job, or
+    a pattern together with keyword boosting or with a phrase list, is out of scope: each a ValueError.
     Each job leaves `pipe.many_timing` = {"front_s": seconds its waves spent before their first decode (puts, gate, language),
     "total_s": seconds up to the end of the last wave finished, "waves": waves finished} — what scripts/many_files_time.py reports;
     the next job on the pipeline replaces it.
@@ -368,7 +429,15 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     grammar, grammar_repeat = kwargs.pop("grammar", None), kwargs.pop("grammar_repeat", True)
     grammars, grammars_repeat = kwargs.pop("grammars", None), kwargs.pop("grammars_repeat", True)
     grammar_pattern, grammar_ignore_case = kwargs.pop("grammar_pattern", None), kwargs.pop("grammar_ignore_case", False)
+    grammar_patterns, patterns_ignore_case = kwargs.pop("grammar_patterns", None), kwargs.pop("grammar_patterns_ignore_case", False)
     pat = None
+    if grammar_patterns is not None:
+        if grammar_pattern is not None:
+            raise ValueError("grammar_patterns (one per file) and grammar_pattern (one for all files) in one job: give one of them")
+        if grammar is not None or grammars is not None:
+            raise ValueError("grammar_patterns and grammar / grammars in one job: a pattern together with a phrase list is out of scope")
+        if any(v is not None for v in bias_args.values()):
+            raise ValueError("grammar_patterns and keywords / logit_bias in one job: a pattern together with keyword boosting is out of scope")
     if grammar_pattern is not None:
         # compiled (and refused) here, before the first file is read
         if not isinstance(grammar_pattern, str):
@@ -412,7 +481,9 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
         if any(v is not None for v in bias_args.values()):
             raise ValueError("grammars and keywords / logit_bias in one job: a slot decodes under one of them")
         file_grammars = per_file_grammars(pipe.model, grammars, grammars_repeat, a, len(audios))
-    job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables, file_grammars)
+    # a pattern PER FILE, the same way: compiled here, before any audio work
+    file_patterns = per_file_patterns(pipe.model, grammar_patterns, patterns_ignore_case, a, len(audios)) if grammar_patterns is not None else None
+    job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables, file_grammars, file_patterns)
     if pat is not None:
         return _under_grammar(job, pat, _pattern.scope)
     if grammar is None:
@@ -437,12 +508,14 @@ def _under_grammar(job, gram, scope=_grammar.scope):
         yield item
 
 
-def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None, tables=None, grammars=None):
+def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None, tables=None, grammars=None,
+         patterns=None):
     model = pipe.model
     tables = tables if tables is not None else [None] * len(audios)
     grammars = grammars if grammars is not None else [None] * len(audios)
+    patterns = patterns if patterns is not None else [None] * len(audios)
     if on_error == "raise":
-        for t in list(tables) + list(grammars):
+        for t in list(tables) + list(grammars) + list(patterns):
             if isinstance(t, Exception):
                 raise t
     timing = pipe.many_timing = {"front_s": 0.0, "total_s": 0.0, "waves": 0}
@@ -470,6 +543,7 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: b
         wave, bias_set = fit_tables(wave, tables)       # (a wave closes early where its distinct tables would overflow a pool cap)
         # (grammars= and keywords exclude each other in one job, so at most one of the two fits shortens the wave and the other's set is None)
         wave, grammar_set = fit_grammars(wave, grammars)
+        wave, pattern_set = fit_patterns(wave, patterns)
         at = wave[-1] + 1
         files = [_File(i, per_file[i], loaded[i], batch_size + k, *(diarizers[i] if diarizers else ())) for k, i in enumerate(wave)]
         for f in files:
@@ -483,6 +557,11 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: b
             else:
                 f.grammar = grammars[f.index]
             f.grammar_set = grammar_set
+            if isinstance(patterns[f.index], Exception):
+                f.audio = patterns[f.index]             # a refused pattern costs only its file, the same way
+            else:
+                f.pattern = patterns[f.index]
+            f.pattern_set = pattern_set
         for i in wave:
             loaded[i] = None                # (the job does not hold a file's bytes past its wave)
         yield from _wave(pipe, slot, files, a, vad_parameters, batch_size, on_error, timing, wave_put)
@@ -738,6 +817,8 @@ def _decode_group(pipe, slot, group) -> list:
         # a grammar per file, the same way: an item_scope of the grammars of the files the items come from, in the wave's one set
         if group[idx[0]][0].grammar_set is not None:
             scope = _grammar.item_scope([group[i][0].grammar for i in idx], group[idx[0]][0].grammar_set)
+        if group[idx[0]][0].pattern_set is not None:    # a pattern per file, the same way
+            scope = _pattern.item_scope([group[i][0].pattern for i in idx], group[idx[0]][0].pattern_set)
         with scope:
             results = model.model.generate(
                 encoder_output if len(idx) == n else encoder_output.select(idx), [prompts[i] for i in idx], beam_size=o.beam_size,

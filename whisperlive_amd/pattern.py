@@ -24,7 +24,8 @@ from typing import Dict, FrozenSet, Iterable, List, Optional, Sequence, Tuple, U
 
 import numpy as np
 
-from ._lib import PATTERN_DEAD, PATTERN_MAX_CELLS, PATTERN_MAX_STATES, PATTERN_MAX_TOKEN_BYTES, PATTERN_MAX_VOCAB_BYTES
+from ._lib import (PATTERN_DEAD, PATTERN_MAX_CELLS, PATTERN_MAX_STATES, PATTERN_MAX_TOKEN_BYTES, PATTERN_MAX_VOCAB_BYTES, PATTERN_SET_MAX_CELLS,
+                   PATTERN_SET_MAX_STATES, PATTERN_SET_MAX_TABLES)
 
 DEAD = PATTERN_DEAD
 MAX_REPEAT = 1000               # the largest count of a `{m,n}`
@@ -548,3 +549,120 @@ def install(slot, pattern: Optional[Pattern], vocab: Optional[Tuple[int, np.ndar
         slot.set_pattern(pattern)
         slot._bias_table = slot._grammar = None
     slot._pattern = pattern
+
+
+# ---- a pattern PER ITEM (include/wlx_pattern_items.h wlx_pattern_set_items / wlx_pattern_select)
+class PatternSet:
+    """Up to 64 compiled Patterns packed into the pool of wlx_pattern_set_items. `add` returns the pattern's index, storing one that is
+    already there (the same object, or equal tables) once; ValueError names the limit a new pattern would pass and leaves the set as it
+    was. `version` moves with every stored pattern: a slot uploads a set again only when it has grown (install_items)."""
+
+    def __init__(self, patterns: Iterable[Pattern] = ()):
+        self.tables: List[Pattern] = []
+        self._index: Dict[bytes, int] = {}
+        self.n_states = self.n_cells = 0
+        self.version = 0
+        for p in patterns:
+            self.add(p)
+
+    def __len__(self) -> int:
+        return len(self.tables)
+
+    @staticmethod
+    def _key(p: Pattern) -> bytes:
+        parts = ((p.byte_class, np.uint8), (p.trans, np.uint16), (p.accept, np.uint8))
+        return np.asarray(p.trans.shape, np.int64).tobytes() + b"".join(np.ascontiguousarray(a, t).tobytes() for a, t in parts)
+
+    def index(self, p: Pattern) -> Optional[int]:
+        return self._index.get(self._key(p))
+
+    def _refusal(self, p: Pattern) -> Optional[str]:
+        if not isinstance(p, Pattern):
+            return "a PatternSet holds compiled patterns (compile_pattern)"
+        cells = p.n_states * p.n_classes
+        if p.n_states > PATTERN_MAX_STATES:
+            return f"a pattern has {p.n_states} states (at most {PATTERN_MAX_STATES} states per pattern)"
+        if cells > PATTERN_MAX_CELLS:
+            return f"a pattern has {cells} cells (at most {PATTERN_MAX_CELLS} cells per pattern)"
+        if len(self.tables) + 1 > PATTERN_SET_MAX_TABLES:
+            return f"the set would hold {len(self.tables) + 1} patterns (at most {PATTERN_SET_MAX_TABLES} patterns in one set)"
+        if self.n_cells + cells > PATTERN_SET_MAX_CELLS:
+            return f"the set would hold {self.n_cells + cells} cells (at most {PATTERN_SET_MAX_CELLS} cells in one set)"
+        if self.n_states + p.n_states > PATTERN_SET_MAX_STATES:
+            return f"the set would hold {self.n_states + p.n_states} states (at most {PATTERN_SET_MAX_STATES} states in one set)"
+        return None
+
+    def fits(self, p: Pattern) -> bool:
+        """`add(p)` would succeed (a pattern already stored always fits)"""
+        return (isinstance(p, Pattern) and self._key(p) in self._index) or self._refusal(p) is None
+
+    def add(self, p: Pattern) -> int:
+        if isinstance(p, Pattern):
+            i = self._index.get(self._key(p))
+            if i is not None:
+                return i
+        why = self._refusal(p)
+        if why:
+            raise ValueError(why)
+        self._index[self._key(p)] = len(self.tables)
+        self.tables.append(p)
+        self.n_states += p.n_states
+        self.n_cells += p.n_states * p.n_classes
+        self.version += 1
+        return len(self.tables) - 1
+
+    def packed(self):
+        """the arrays of wlx_pattern_set_items: (n_states [T], n_classes [T], byte_class [T * 256], trans [cells], accept [states]), the
+        tables back to back without pads"""
+        ts = self.tables
+        cat = lambda xs, t: np.ascontiguousarray(np.concatenate([np.asarray(x, t).ravel() for x in xs]) if xs else np.zeros(0, t), dtype=t)
+        return (np.asarray([p.n_states for p in ts], np.int32), np.asarray([p.n_classes for p in ts], np.int32),
+                cat([p.byte_class for p in ts], np.uint8), cat([p.trans for p in ts], np.uint16), cat([p.accept for p in ts], np.uint8))
+
+
+def current_items() -> Optional["item_scope"]:
+    return getattr(_tls, "items", None)
+
+
+class item_scope:
+    """context manager: `patterns[i]` (a Pattern, or None: that item decodes unconstrained) is the pattern of prompt i of every generate
+    call the calling thread makes inside the block; scopes nest, other threads are untouched. `pattern_set`: the set the patterns go into
+    (a job passes one set for all its decode groups, so a slot uploads it once); without one the scope owns a set of its own."""
+
+    def __init__(self, patterns: Sequence[Optional[Pattern]], pattern_set: Optional[PatternSet] = None):
+        self.patterns = list(patterns)
+        self.pattern_set = pattern_set if pattern_set is not None else PatternSet()
+
+    def __enter__(self):
+        self._prev = current_items()
+        _tls.items = self
+        return self
+
+    def __exit__(self, *exc):
+        _tls.items = self._prev
+        return False
+
+
+def install_items(slot, patterns: Sequence[Optional[Pattern]], pattern_set: PatternSet,
+                  vocab: Optional[Tuple[int, np.ndarray, np.ndarray]] = None) -> List[int]:
+    """Bring `slot` to the per-item route for a generate call over `patterns` (one per prompt, None: unconstrained): every pattern is
+    stored in `pattern_set` (ValueError names a pool limit), the slot uploads the set unless it holds it already, and the table index of
+    every prompt is returned (-1: none) for Slot.select_patterns per decode group. A call none of whose prompts has a pattern keeps a
+    slot that holds THIS set in per-item mode with every item deselected (the kernel then touches no logit), and clears any other slot.
+    `vocab` as for `install`. A slot that cannot take a set (no `set_patterns`) with one asked for is an error, never a silent
+    unconstrained decode."""
+    idx = [-1 if p is None else pattern_set.add(p) for p in patterns]
+    if getattr(slot, "_pattern", None) is pattern_set and getattr(slot, "_pattern_set_version", None) == pattern_set.version:
+        return idx
+    if all(i < 0 for i in idx):
+        if getattr(slot, "_pattern", None) is not None:
+            install(slot, None)
+        return idx
+    if not hasattr(slot, "set_patterns"):
+        raise RuntimeError("a pattern per item asked for, but this slot has no set_patterns")
+    eng = getattr(slot, "engine", None)
+    if vocab is not None and hasattr(eng, "set_pattern_vocab"):
+        eng.set_pattern_vocab(*vocab)
+    slot.set_patterns(pattern_set)
+    slot._pattern, slot._pattern_set_version, slot._bias_table, slot._grammar = pattern_set, pattern_set.version, None, None
+    return idx

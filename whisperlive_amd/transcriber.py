@@ -284,7 +284,23 @@ class _EngineModel:
                 raise ValueError(f"every token the grammar allows in state {dead[0]} is one this call suppresses (suppress_tokens"
                                  f"{', suppress_blank' if dead[0] == 0 and suppress_blank else ''}): nothing would be left to emit there")
             _pattern.install(slot, pat, (o.token_ids.eot, tok_off, tok_bytes))
-        elif getattr(slot, "_pattern", None) is not None:
+        # a pattern per item: inside a pattern.item_scope every prompt has its own pattern, or none; the set goes up once per
+        # slot, the selection per decode group
+        pat_items = _pattern.current_items()
+        psel = None
+        if pat_items is not None:
+            if pat is not None or gram is not None or gram_items is not None or table is not None or scope_items is not None:
+                raise ValueError("a pattern per item next to a pattern, a phrase list or keyword boosting on one slot is not served: decode under one of them")
+            if len(pat_items.patterns) != len(prompts):
+                raise ValueError(f"the item_scope names {len(pat_items.patterns)} patterns for {len(prompts)} prompts")
+            tok_off, tok_bytes = _pattern.token_bytes(o._base_tokenizer, o.token_ids.eot)
+            for p in {id(p): p for p in pat_items.patterns if p is not None}.values():       # (dead_states caches per suppress set)
+                dead = p.dead_states(tok_off, tok_bytes, sup, o.token_ids.blank if suppress_blank else None)
+                if dead:
+                    raise ValueError(f"every token the grammar allows in state {dead[0]} is one this call suppresses (suppress_tokens"
+                                     f"{', suppress_blank' if dead[0] == 0 and suppress_blank else ''}): nothing would be left to emit there")
+            psel = _pattern.install_items(slot, pat_items.patterns, pat_items.pattern_set, (o.token_ids.eot, tok_off, tok_bytes))
+        elif pat is None and getattr(slot, "_pattern", None) is not None:
             _pattern.install(slot, None)
         # (under a grammar none of the keyword routes below applies: no table, no item scope, and install has forgotten the slot's table)
         if scope_items is not None:
@@ -301,6 +317,8 @@ class _EngineModel:
                 slot.select_bias(sel[a:a + group])
             if gsel is not None and getattr(slot, "_grammar", None) is gram_items.grammar_set:
                 slot.select_grammars(gsel[a:a + group])
+            if psel is not None and getattr(slot, "_pattern", None) is pat_items.pattern_set:
+                slot.select_patterns(psel[a:a + group])
             res.extend(slot.generate(prompts[a:a + group], o.token_ids, beam_size=beam_size, patience=patience,
                                      num_hypotheses=num_hypotheses, length_penalty=length_penalty,
                                      repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -545,8 +563,9 @@ class WhisperModelHIP:
     def grammar(self, phrases=None, repeat: bool = True, *, pattern: Optional[str] = None, ignore_case: bool = False):
         """`pattern=r"..."` (with `ignore_case`): a regular expression in place of a phrase list — every window's text fully matches it
         (pattern.compile_pattern names the syntax; a DFA over the text's BYTES, so every tokenisation is admitted and `\\d{8}` is nine
-        states). Together with `phrases` it raises a ValueError. One pattern for every item; a pattern per file or per
-        item, a pattern together with keyword boosting and a pattern together with a phrase list are out of scope (ValueError).
+        states). Together with `phrases` it raises a ValueError. One pattern for every item (a pattern per item is
+        pattern.item_scope, which transcribe_many(grammar_patterns=) uses); a pattern together with keyword boosting and
+        a pattern together with a phrase list are out of scope (ValueError).
         Context manager: inside the block every generate of the CALLING THREAD decodes under this grammar on its slot — the transcript
         of a window is a sequence of phrases from the list (`repeat=True`) or one phrase or nothing (`repeat=False`), and nothing else:
         the streaming transcriber, BatchedInferencePipeline.transcribe and the temperature fallback alike. `phrases`: strings or token
