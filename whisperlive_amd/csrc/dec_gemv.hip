@@ -344,11 +344,18 @@ __device__ __forceinline__ float wave_sum_dpp(float v) { return dpp_wave_sum(v);
 // `after_first_loads` runs once, between the first trip's global loads and its LDS stores (every lane runs it, also lanes without a unit): the caller
 // requests its weight stream there, behind the activation loads.
 template <int P, class F>
-__device__ __forceinline__ void stage_rows_f16_wave(const half_t* __restrict__ X, long ldx, int M, int K, half_t* xs, int ldxs, int lane,
+// (X without __restrict__: as invariant loads the first trip's requests are tied to no fence, and with the short index arithmetic hipcc issued two of
+// the four behind the weight requests — the order round 2 removed.)
+__device__ __forceinline__ void stage_rows_f16_wave(const half_t* X, long ldx, int M, int K, half_t* xs, int ldxs, int lane,
                                                     F&& after_first_loads) {
     // P units per lane are requested together before anything is stored (P = what five rows of the slice need: one round trip); a unit index past
     // the end is clamped to the lane's previous unit, which is then stored twice with its own value
     const int kv8 = K >> 3, total = M * kv8;
+    // u / kv8 by a rounded reciprocal (exact: u < 16 rows x 1020 units, and (u + 0.5) / kv8 lies 0.5 / kv8 >= 2^-11 off every integer, a
+    // thousand times the error of the reciprocal and the product). An integer division by a run-time divisor is ~30 dependent VALU
+    // instructions; four of them stood in front of the wave's FIRST request, 0.5 KiB of cold code ahead of the activation and weight loads.
+    const float rkv8 = __builtin_amdgcn_rcpf((float)kv8);
+    auto div_kv8 = [&](int u) { return (int)(((float)u + 0.5f) * rkv8); };
     {
         int m_[P], k_[P];
         f16x8 v_[P];
@@ -356,7 +363,7 @@ __device__ __forceinline__ void stage_rows_f16_wave(const half_t* __restrict__ X
         for (int q = 0; q < P; ++q) {
             int u = lane + 64 * q;
             if (u >= total) u = (q == 0) ? total - 1 : (lane + 64 * (q - 1) < total ? lane + 64 * (q - 1) : total - 1);
-            m_[q] = u / kv8; k_[q] = u - m_[q] * kv8;
+            m_[q] = div_kv8(u); k_[q] = u - m_[q] * kv8;
             v_[q] = ld_f16x8(X + (long)m_[q] * ldx + k_[q] * 8);
         }
         after_first_loads();
@@ -366,9 +373,9 @@ __device__ __forceinline__ void stage_rows_f16_wave(const half_t* __restrict__ X
 #pragma unroll 1
     for (int u0 = lane + 64 * P; u0 < total; u0 += 128) {
         const int u1 = u0 + 64;
-        const int m0 = u0 / kv8, k0 = u0 - m0 * kv8;
+        const int m0 = div_kv8(u0), k0 = u0 - m0 * kv8;
         const int uc = (u1 < total) ? u1 : u0;
-        const int m1 = uc / kv8, k1 = uc - m1 * kv8;
+        const int m1 = div_kv8(uc), k1 = uc - m1 * kv8;
         const f16x8 v0 = ld_f16x8(X + (long)m0 * ldx + k0 * 8);
         const f16x8 v1 = ld_f16x8(X + (long)m1 * ldx + k1 * 8);
         *reinterpret_cast<f16x8*>(xs + m0 * ldxs + k0 * 8) = v0;
@@ -544,7 +551,8 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
             for (int sl = 0; sl < WLX_FC2_KS; ++sl)
                 slab_e[sl] = *reinterpret_cast<const float4*>(p.slab + sl * p.slab_stride + (long)row_q * p.ldxres + n_e);
         }
-        if constexpr (OUT == GEMV_OUT_SLAB) { if (blockIdx.y != 0) bias_e = make_float4(0.f, 0.f, 0.f, 0.f); }   // the bias once: slice 0
+        // (K-split form, the bias once, on slice 0: the other slices zero it in the epilogue, where it is added. Zeroed here, the value is needed —
+        // a wait for vmcnt(0), the whole weight slice and the bias behind it — in front of the fragment reads and the MFMAs.)
     };
     // Their addresses come from the struct. With the argument head they are requested BEHIND the weight stream (load_weights), so that the wait for
     // the struct's scalar fetch stands behind the first trip's loads and the weight request instead of in front of them; vmcnt retires in order and
@@ -581,10 +589,31 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[i][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     f16x8 xf[CH][MT];
+    // the MFMAs of the wave's last (for one stream's step: only) chunk, in k-tile order
+    auto mfma_chunk = [&]() {
+        WLX_TR_MARK(2);
+#pragma unroll
+        for (int j = 0; j < CH; ++j)
+#pragma unroll
+            for (int i = 0; i < NTB; ++i)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma16(wf[j][i], xf[j][mt], acc[i][mt]);
+    };
+    // the B fragments of the wave's K slice from the fp16 rows in LDS (lanes of rows >= M re-read a valid row, never stored)
+    auto read_xf_lds = [&](int ldxs) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const half_t* xr = xs + crow[mt] * ldxs + kx0 * 32 + g * 8;
+#pragma unroll
+            for (int j = 0; j < CH; ++j) xf[j][mt] = *reinterpret_cast<const f16x8*>(xr + j * 32);
+        }
+    };
+    (void)read_xf_lds;
 
     if constexpr (IN == GEMV_IN_F16) {
         const half_t* xr[MT];
         int xstep;                                                          // halfs between k-tiles of a row
+        bool staged_one = false;                                            // staged rows, one chunk: multiplied inside the staged branch
         if (MT == 1 && p.xstage) {
             // One stream (M <= 16): the fp16 rows go through LDS — fetching B fragments straight from global costs CH
             // loads per wave of 64-byte pieces (16 waves x 6 = 96 load instructions per workgroup for K = 3072, as many
@@ -599,6 +628,12 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             xr[0] = xs + crow[0] * ldxs + kx0 * 32 + g * 8;                 // lanes of rows >= M re-read a valid row (never stored)
             xstep = 32;
+            // One chunk per wave (every staged projection of one stream's step): the fragments are read HERE, as LDS reads. Below the join
+            // with the straight-from-global way xr is a generic pointer, its reads are flat loads, and a flat load counts as a vector memory
+            // request issued behind the weights — the first MFMA then waited for vmcnt(0): the whole weight slice and the epilogue operands.
+            // With LDS reads the MFMAs wait weight by weight.
+            staged_one = p.NCH == 1;
+            if (staged_one) { read_xf_lds(ldxs); mfma_chunk(); }
         } else {
             // batched rows, or K too large for the LDS budget (large-v3 fc2: 5 x 5120 fp16 + partials > 64 KiB):
             // fragments straight from global
@@ -606,6 +641,7 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
             for (int mt = 0; mt < MT; ++mt) xr[mt] = p.Xh + (long)crow[mt] * p.ldxh + kw0 * 32 + g * 8;
             xstep = 32;
         }
+        if (!staged_one) {
 #pragma unroll
         for (int j = 0; j < CH; ++j)
 #pragma unroll
@@ -632,6 +668,8 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) xf[j][mt] = xn[j][mt];
             }
+        }
+        mfma_chunk();
         }
     } else if constexpr (IN == GEMV_IN_LN && XS != GEMV_X_PLAIN) {
         // rows from slabs or the embedding tables: ONE row per wave in the first trip (its pieces are 3-5x the registers of a
@@ -775,6 +813,7 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
 #pragma unroll
             for (int j = 0; j < CH; ++j) xf[j][mt] = *reinterpret_cast<const f16x8*>(xr + j * 32);
         }
+        mfma_chunk();
     } else if constexpr (IN == GEMV_IN_LN) {
         // wave w normalises rows w, w + nw, ...; a row = LNV float4 per lane (d_model = 256 LNV)
         // first trip's rows (this wave's row and the one nw below it) are requested before anything else
@@ -857,6 +896,7 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
 #pragma unroll
             for (int j = 0; j < CH; ++j) xf[j][mt] = *reinterpret_cast<const f16x8*>(xr + j * 32);
         }
+        mfma_chunk();
     } else {   // GEMV_IN_XATTN: the WLX_XSPLIT partials (normalised fp16 O, fp32 (m, l) contiguous per row) are combined into fp16 rows in LDS, like the
         // LayerNorm rows. (A CU retires one wave-level load instruction per ~11 ns: the fp32 / 4-dim / separate-(m,l) form needed 240 of them per
         // workgroup, the forms below 90.)
@@ -920,6 +960,14 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
 #pragma unroll
                 for (int q = 0; q < NPL; ++q) finish(mlq[q], ovq[q], mq[q], colq[q], lane + 64 * q < n_w);
             }
+            auto combined = [&]() {
+                WLX_TR_MARK(1);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                read_xf_lds(ldxs);
+                mfma_chunk();
+            };
 #pragma unroll 1
             for (int u = lane + 64 * ((CH * 4 * 5 + 63) / 64 < 2 ? 2 : (CH * 4 * 5 + 63) / 64); u < n_w; u += 64) {   // more items per wave than the peeled ones (batched rows up to 16)
                 const float4* mlp; const half_t* op; int m, col;
@@ -932,10 +980,7 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
                 for (int sp = 0; sp < WLX_XSPLIT; ++sp) ov[sp] = ld_f16x8(op + sp * 1024);
                 finish(ml, ov, m, col, true);
             }
-            WLX_TR_MARK(1);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            combined();
         } else {
             // Batched rows (two or three row tiles): every wave of the workgroup (more than the nw MFMA waves) combines — one (row, head, 8-dim
             // group) per thread, 12 16-byte loads in flight.
@@ -981,21 +1026,10 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
             WLX_TR_MARK(1);
             __syncthreads();
             if (!streams) return;                                           // helper waves are done (no later barrier needs them: ended waves leave the barrier count)
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const half_t* xr = xs + crow[mt] * ldxs + kx0 * 32 + g * 8;
-#pragma unroll
-            for (int j = 0; j < CH; ++j) xf[j][mt] = *reinterpret_cast<const f16x8*>(xr + j * 32);
+            read_xf_lds(ldxs);
+            mfma_chunk();
         }
     }
-    WLX_TR_MARK(2);
-#pragma unroll
-    for (int j = 0; j < CH; ++j)
-#pragma unroll
-        for (int i = 0; i < NTB; ++i)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma16(wf[j][i], xf[j][mt], acc[i][mt]);
 
     // ---- cross-wave K reduction through LDS in a fixed order; wave w finishes pairs w, w + nw, ...
 #pragma unroll
@@ -1024,9 +1058,9 @@ __global__ __launch_bounds__((IN == GEMV_IN_LN || OUT == GEMV_OUT_SLAB || MT > 1
             for (int sl = 0; sl < WLX_FC2_KS; ++sl)
                 slab_e[sl] = *reinterpret_cast<const float4*>(p.slab + sl * p.slab_stride + (long)rr * p.ldxres + n_p);
         }
-        if constexpr (OUT == GEMV_OUT_SLAB) { if (blockIdx.y != 0) bias_e = make_float4(0.f, 0.f, 0.f, 0.f); }
         if constexpr (OUT == GEMV_OUT_QKV) { rc_e = p.row_cache[rr]; rp_e = p.row_pos[rr]; }
     }
+    if constexpr (OUT == GEMV_OUT_SLAB) { if (blockIdx.y != 0) bias_e = make_float4(0.f, 0.f, 0.f, 0.f); }   // the bias once: slice 0
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     const float* ar = accred + (pair * 64 + lane) * 4;
 #pragma unroll 2
