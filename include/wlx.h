@@ -752,7 +752,10 @@ typedef struct {
  * with nothing written: a null pointer, n or dim out of range, a threshold that is NaN or outside [0, 2], max_clusters < 0.
  * The first call of an engine that clusters (this one, wlx_spk_diarize_pcm or wlx_spk_diarize_many) makes the buffers all three share,
  * sized for a wave: WLX_SPK_MANY_MAX_CELLS floats of matrices and tables of WLX_SPK_MANY_MAX_ROWS rows (64 MiB + 16 MiB of HBM and
- * 16 MiB pinned at embed_dim 256). An engine that only embeds never pays for them. */
+ * 16 MiB pinned at embed_dim 256). An engine that only embeds never pays for them.
+ * WLX_SPK_CLUSTER_MAX windows at a 0.75 s hop are 25.6 minutes of speech. The long form of this call and of wlx_spk_diarize_pcm, one
+ * file of up to WLX_SPK_LONG_MAX = 8192 windows under the same rules, is declared in wlx_spk_long.h, which this header includes at its
+ * end. */
 int32_t wlx_spk_cluster(wlx_spk* spk, const float* emb, int32_t n, int32_t dim, const wlx_spk_cluster_opts* opts,
                         int32_t* labels, float* centroids, int32_t* n_clusters);
 /* A whole file: windows [starts[i], starts[i] + n_samples[i]) of the resident PCM of a slot item, 1 <= n <= WLX_SPK_CLUSTER_MAX. ALL of
@@ -1173,6 +1176,7 @@ int32_t wlx_vad_debug_out(wlx_vad* v, const float* hs, int32_t T, float* probs, 
 #include "wlx_grammar_items.h"
 #include "wlx_pattern.h"
 #include "wlx_pattern_items.h"
+#include "wlx_spk_long.h"
 
 #ifdef __cplusplus
 }

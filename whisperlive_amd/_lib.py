@@ -54,6 +54,8 @@ EXPORTS_GRAMMAR_ITEMS = ["wlx_grammar_set_items", "wlx_grammar_select", "wlx_deb
 EXPORTS_PATTERN = ["wlx_pattern_vocab_set", "wlx_pattern_set", "wlx_pattern_clear", "wlx_debug_pattern_apply"]
 # a pattern per item, declared in include/wlx_pattern_items.h (which wlx.h includes)
 EXPORTS_PATTERN_ITEMS = ["wlx_pattern_set_items", "wlx_pattern_select", "wlx_debug_pattern_apply_items"]
+# the long form of the offline speaker clustering, declared in include/wlx_spk_long.h (which wlx.h includes)
+EXPORTS_SPK_LONG = ["wlx_spk_cluster_long", "wlx_spk_diarize_pcm_long", "wlx_spk_debug_ahc_long"]
 
 
 # MFMA accumulators in VGPRs (gfx950 has ONE register file; hipcc's default puts C/D in its AGPR half): every VALU touch of
@@ -149,6 +151,7 @@ ERR_TOO_SHORT = 6       # wlx_status WLX_ERR_TOO_SHORT
 ERR_DATA = 7            # wlx_status WLX_ERR_DATA: damaged input (the FLAC and telephony WAV front ends)
 SPK_MAX_BATCH = 64      # wlx.h WLX_SPK_MAX_BATCH: segments of one wlx_spk_embed_batch call
 SPK_CLUSTER_MAX = 2048  # wlx.h WLX_SPK_CLUSTER_MAX: rows of one wlx_spk_cluster / windows of one wlx_spk_diarize_pcm call
+SPK_LONG_MAX = 8192     # wlx_spk_long.h WLX_SPK_LONG_MAX: rows of one wlx_spk_cluster_long / windows of one wlx_spk_diarize_pcm_long call
 SPK_MIN_SAMPLES = 4800  # csrc/spk.h WLX_SPK_MIN_SAMPLES: a shorter window or segment takes no part (WLX_ERR_TOO_SHORT)
 SPK_MANY_MAX_FILES = 64                                   # wlx.h WLX_SPK_MANY_MAX_FILES: files of one wlx_spk_diarize_many call,
 SPK_MANY_MAX_ROWS = 8192                                   # WLX_SPK_MANY_MAX_ROWS: their windows together,
@@ -347,7 +350,8 @@ def load() -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
     except OSError as e:  # e.g. libamdhip64 missing
         raise WlxError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS + EXPORTS_PATTERN + EXPORTS_PATTERN_ITEMS if not hasattr(lib, s)]
+    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS + EXPORTS_PATTERN + EXPORTS_PATTERN_ITEMS + EXPORTS_SPK_LONG
+               if not hasattr(lib, s)]
     if missing:
         raise WlxError(f"libwlx.so lacks symbols {missing}")
     i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p
@@ -524,6 +528,12 @@ def load() -> C.CDLL:
         lib.wlx_debug_pattern_apply_items.argtypes = [i32, i32, i32, i32, i32p, i32p, u8p, u16p_, u8p, i32p, u8p, f32p, i32, i32, i32p, i64, i32p, i32p,
                                                       i32p, i32p, i32p, i16p, i16p]
         for name in EXPORTS_PATTERN_ITEMS:
+            getattr(lib, name).restype = i32
+    if EXPORTS_SPK_LONG:            # (scripts/spk_long_time.py alone empties the list, to load a library of the parent commit beside this one)
+        lib.wlx_spk_cluster_long.argtypes = lib.wlx_spk_cluster.argtypes
+        lib.wlx_spk_diarize_pcm_long.argtypes = lib.wlx_spk_diarize_pcm.argtypes
+        lib.wlx_spk_debug_ahc_long.argtypes = lib.wlx_spk_debug_ahc.argtypes
+        for name in EXPORTS_SPK_LONG:
             getattr(lib, name).restype = i32
     for name in EXPORTS + EXPORTS_BIAS_ITEMS + EXPORTS_GRAMMAR:
         fn = getattr(lib, name)

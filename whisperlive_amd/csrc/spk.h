@@ -81,4 +81,13 @@ bool launch_spk_ahc(float* dist, const SpkClusterFile* files, int n_files, int* 
 bool launch_spk_centroids(const float* X, const int* labels, const int* counts, const SpkClusterFile* files, int n_files, int D,
                           float* cent, hipStream_t s);
 
+// ---- the long form (include/wlx_spk_long.h): ONE file of 1..WLX_SPK_LONG_MAX rows, rows of X from row 0, a matrix of m * m floats of
+// its own. Affinity and centroids are the kernels above without the cap of the table; the clustering is spk_ahc_long_kernel, one
+// workgroup with 12 n bytes of dynamic LDS, same rules and same bits. parent: n uint16_t of device scratch. counts [2]. False = nothing
+// launched (a null pointer, a shape out of range, options as above, the raised LDS limit refused).
+bool launch_spk_affinity_long(const float* X, int m, int D, float* dist, hipStream_t s);
+bool launch_spk_ahc_long(float* dist, int n, float threshold, int max_clusters, uint16_t* parent, int* merges, float* heights, int* labels,
+                         int* counts, hipStream_t s);
+bool launch_spk_centroids_long(const float* X, const int* labels, const int* counts, int m, int D, float* cent, hipStream_t s);
+
 }  // namespace wlx

@@ -128,6 +128,11 @@ struct wlx_spk {
     hipEvent_t ev_cl[4] = {nullptr, nullptr, nullptr, nullptr};          // around the distance matrices [0, 1] and the clustering [2, 3]
     float aff_ms = 0.f, ahc_ms = 0.f;
     bool cl_timed = false;
+    // the long form (include/wlx_spk_long.h): a matrix of its own, made by the first long call at that call's size and grown when a later
+    // one needs more (not in `pool`: it is freed on the way), and the parent scratch of spk_ahc_long_kernel
+    float* lg_dist = nullptr;
+    size_t lg_cells = 0;
+    uint16_t* lg_parent = nullptr;
 };
 
 static void spk_free(wlx_spk* k) {
@@ -137,6 +142,7 @@ static void spk_free(wlx_spk* k) {
     for (hipEvent_t e : k->ev)
         if (e) (void)hipEventDestroy(e);
     for (void* p : k->pool) (void)hipFree(p);
+    if (k->lg_dist) (void)hipFree(k->lg_dist);
     if (k->h_emb) (void)hipHostFree(k->h_emb);
     for (hipEvent_t e : k->ev_cl)
         if (e) (void)hipEventDestroy(e);
@@ -504,6 +510,44 @@ static int spk_cluster_enqueue(wlx_spk* k, const char* who, const std::vector<Sp
     return WLX_OK;
 }
 
+// the long form's own buffers, behind spk_many_reserve: a matrix of m * m floats (grown when a call needs more: the stream is idle
+// between calls, each waits at its end) and the parent scratch. k->mu is held.
+static int spk_long_reserve(wlx_spk* k, int m) {
+    CKR(spk_many_reserve(k));
+    if (!k->lg_parent) CKR(dalloc(k->pool, &k->lg_parent, (size_t)WLX_SPK_LONG_MAX, false));
+    const size_t cells = (size_t)m * m;
+    if (cells <= k->lg_cells) return WLX_OK;
+    CK(hipStreamSynchronize(k->st));
+    if (k->lg_dist) CK(hipFree(k->lg_dist));
+    k->lg_dist = nullptr, k->lg_cells = 0;
+    CK(hipMalloc(reinterpret_cast<void**>(&k->lg_dist), cells * sizeof(float)));
+    k->lg_cells = cells;
+    return WLX_OK;
+}
+
+// spk_cluster_enqueue for ONE file of up to WLX_SPK_LONG_MAX rows (rows 0 .. m - 1 of k->mn_emb) through the long launchers and k->lg_dist
+static int spk_long_enqueue(wlx_spk* k, const char* who, const SpkClusterFile& f, float* dist_out, bool want_centroids) {
+    hipStream_t st = k->st;
+    const int E = k->spec.embed_dim, m = f.m;
+    CK(hipEventRecord(k->ev_cl[0], st));
+    if (!launch_spk_affinity_long(k->mn_emb, m, E, k->lg_dist, st)) return set_error(WLX_ERR_ARG, "%s: the distance matrix refused %d rows", who, m);
+    CK(hipEventRecord(k->ev_cl[1], st));
+    if (dist_out) CK(hipMemcpyAsync(dist_out, k->lg_dist, (size_t)m * m * sizeof(float), hipMemcpyDeviceToHost, st));
+    CK(hipEventRecord(k->ev_cl[2], st));
+    if (!launch_spk_ahc_long(k->lg_dist, m, f.threshold, f.max_clusters, k->lg_parent, k->mn_merges, k->mn_heights, k->mn_labels, k->mn_counts, st))
+        return set_error(WLX_ERR_ARG, "%s: the clustering refused %d rows", who, m);
+    CK(hipEventRecord(k->ev_cl[3], st));
+    if (want_centroids) {
+        if (!launch_spk_centroids_long(k->mn_emb, k->mn_labels, k->mn_counts, m, E, k->mn_cent, st))
+            return set_error(WLX_ERR_ARG, "%s: the centroids refused %d rows", who, m);
+        CK(hipMemcpyAsync(k->h_mn_cent, k->mn_cent, (size_t)m * E * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(k->h_mn_int, k->mn_labels, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(k->h_mn_int + WLX_SPK_MANY_MAX_ROWS, k->mn_counts, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    return WLX_OK;
+}
+
 // after the wait: per clustered file K, its first K centroids and the labels of its rows dealt to the caller's windows; the times
 static int spk_cluster_collect(wlx_spk* k, const char* who, const SpkWave& wv, int32_t* labels, float* centroids, int32_t* n_clusters) {
     const int E = k->spec.embed_dim;
@@ -521,12 +565,11 @@ static int spk_cluster_collect(wlx_spk* k, const char* who, const SpkWave& wv, i
     return WLX_OK;
 }
 
-// host rows: one file whose windows are its rows, uploaded into the table
-extern "C" int32_t wlx_spk_cluster(wlx_spk* k, const float* emb, int32_t n, int32_t dim, const wlx_spk_cluster_opts* opts, int32_t* labels,
-                                   float* centroids, int32_t* n_clusters) {
-    const char* who = "wlx_spk_cluster";
+// host rows: one file whose windows are its rows, uploaded into the table. `cap` rows at the most; long_form: the long kernel and matrix
+static int spk_cluster_rows(const char* who, int cap, bool long_form, wlx_spk* k, const float* emb, int n, int dim, const wlx_spk_cluster_opts* opts,
+                            int32_t* labels, float* centroids, int32_t* n_clusters) {
     if (!k || !emb || !opts || !labels || !n_clusters) return set_error(WLX_ERR_ARG, "%s: null argument", who);
-    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "%s: %d rows outside 1..%d", who, n, WLX_SPK_CLUSTER_MAX);
+    if (n < 1 || n > cap) return set_error(WLX_ERR_ARG, "%s: %d rows outside 1..%d", who, n, cap);
     if (dim != k->spec.embed_dim) return set_error(WLX_ERR_ARG, "%s: dim %d is not the engine's %d", who, dim, k->spec.embed_dim);
     CKR(spk_cluster_opts_ok(who, opts));
     if (n == 1) {                     // one row is its own cluster and its own centroid
@@ -541,26 +584,37 @@ extern "C" int32_t wlx_spk_cluster(wlx_spk* k, const float* emb, int32_t n, int3
     wv.cf_file.push_back(0);
     std::lock_guard<std::mutex> g(k->mu);
     CK(hipSetDevice(k->device));
-    CKR(spk_many_reserve(k));
+    CKR(long_form ? spk_long_reserve(k, n) : spk_many_reserve(k));
     CK(hipMemcpyAsync(k->mn_emb, emb, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice, k->st));
-    CKR(spk_cluster_enqueue(k, who, wv.cf, nullptr, centroids != nullptr));
+    CKR(long_form ? spk_long_enqueue(k, who, wv.cf[0], nullptr, centroids != nullptr) : spk_cluster_enqueue(k, who, wv.cf, nullptr, centroids != nullptr));
     CK(hipStreamSynchronize(k->st));
     return spk_cluster_collect(k, who, wv, labels, centroids, n_clusters);
 }
 
+extern "C" int32_t wlx_spk_cluster(wlx_spk* k, const float* emb, int32_t n, int32_t dim, const wlx_spk_cluster_opts* opts, int32_t* labels,
+                                   float* centroids, int32_t* n_clusters) {
+    return spk_cluster_rows("wlx_spk_cluster", WLX_SPK_CLUSTER_MAX, false, k, emb, n, dim, opts, labels, centroids, n_clusters);
+}
+
+extern "C" int32_t wlx_spk_cluster_long(wlx_spk* k, const float* emb, int32_t n, int32_t dim, const wlx_spk_cluster_opts* opts, int32_t* labels,
+                                        float* centroids, int32_t* n_clusters) {
+    return spk_cluster_rows("wlx_spk_cluster_long", WLX_SPK_LONG_MAX, true, k, emb, n, dim, opts, labels, centroids, n_clusters);
+}
+
 // The device's part of a planned wave with a window that takes part: every pass a ragged batch whose head writes its rows straight into
 // the table, then the clustering on that table; ONE wait, then the rows, centroids and labels dealt to the caller's windows. `src` is the
-// buffer the plan's offsets count from, inside the lease L.
+// buffer the plan's offsets count from, inside the lease L. long_form: a wave of one file through the long kernel and matrix.
 static int spk_wave_run(wlx_spk* k, const char* who, PcmLease& L, const float* src, const SpkWave& wv, int32_t* labels, int32_t* n_clusters,
-                        float* emb_out, float* dist_out, float* centroids) {
+                        float* emb_out, float* dist_out, float* centroids, bool long_form = false) {
     const int M = (int)wv.win_of.size(), E = k->spec.embed_dim, n_files = (int)wv.m_of.size();
     std::lock_guard<std::mutex> g(k->mu);
     CK(hipSetDevice(k->device));
-    CKR(spk_many_reserve(k));
+    CKR(long_form && !wv.cf.empty() ? spk_long_reserve(k, wv.cf[0].m) : spk_many_reserve(k));
     CKR(L.order(k->st));
     for (const SpkPlan& pl : wv.plans) CKR(spk_enqueue_batch(k, src, pl, k->mn_emb + (size_t)pl.row[0] * E));
     if (emb_out || (centroids && wv.any_single)) CK(hipMemcpyAsync(k->h_mn_emb, k->mn_emb, (size_t)M * E * sizeof(float), hipMemcpyDeviceToHost, k->st));
-    if (!wv.cf.empty()) CKR(spk_cluster_enqueue(k, who, wv.cf, dist_out, centroids != nullptr));
+    if (!wv.cf.empty())
+        CKR(long_form ? spk_long_enqueue(k, who, wv.cf[0], dist_out, centroids != nullptr) : spk_cluster_enqueue(k, who, wv.cf, dist_out, centroids != nullptr));
     CK(hipStreamSynchronize(k->st));
     CK(hipEventElapsedTime(&k->fbank_ms, k->ev[0], k->ev[1]));          // (of the last pass)
     CK(hipEventElapsedTime(&k->net_ms, k->ev[1], k->ev[2]));
@@ -575,12 +629,12 @@ static int spk_wave_run(wlx_spk* k, const char* who, PcmLease& L, const float* s
 }
 
 // A whole file: a wave of one behind refusals of its own — an item with nothing resident or a window past its end refuses the call.
-extern "C" int32_t wlx_spk_diarize_pcm(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts, const int64_t* n_samples,
-                                       int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, float* emb_out,
-                                       float* dist_out, float* centroids, int32_t* n_clusters) {
-    const char* who = "wlx_spk_diarize_pcm";
+// `cap` windows at the most; long_form: the long kernel and matrix.
+static int spk_diarize_item(const char* who, int cap, bool long_form, wlx_spk* k, wlx_engine* e, int slot, int item, const int64_t* starts,
+                            const int64_t* n_samples, int n, const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, float* emb_out,
+                            float* dist_out, float* centroids, int32_t* n_clusters) {
     if (!k || !e || !starts || !n_samples || !opts || !labels || !status || !n_clusters) return set_error(WLX_ERR_ARG, "%s: null argument", who);
-    if (n < 1 || n > WLX_SPK_CLUSTER_MAX) return set_error(WLX_ERR_ARG, "%s: %d windows outside 1..%d", who, n, WLX_SPK_CLUSTER_MAX);
+    if (n < 1 || n > cap) return set_error(WLX_ERR_ARG, "%s: %d windows outside 1..%d", who, n, cap);
     CKR(spk_cluster_opts_ok(who, opts));
     CKR(PcmLease::same_device(who, "engine", e->device, "speaker engine", k->device));
     for (int i = 0; i < n; ++i) {
@@ -599,9 +653,23 @@ extern "C" int32_t wlx_spk_diarize_pcm(wlx_spk* k, wlx_engine* e, int32_t slot, 
     const long item_off = 0;          // (the passes read the item's own buffer)
     spk_wave_plan(k, wv, &ok, &item_off, starts, n_samples, opts, labels, status, n_clusters, emb_out);
     if (wv.win_of.empty()) return WLX_OK;
-    CKR(spk_wave_run(k, who, L, L.buf, wv, labels, n_clusters, emb_out, dist_out, centroids));
+    CKR(spk_wave_run(k, who, L, L.buf, wv, labels, n_clusters, emb_out, dist_out, centroids, long_form));
     if (dist_out && wv.m_of[0] == 1) dist_out[0] = 0.f;
     return WLX_OK;
+}
+
+extern "C" int32_t wlx_spk_diarize_pcm(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts, const int64_t* n_samples,
+                                       int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, float* emb_out,
+                                       float* dist_out, float* centroids, int32_t* n_clusters) {
+    return spk_diarize_item("wlx_spk_diarize_pcm", WLX_SPK_CLUSTER_MAX, false, k, e, slot, item, starts, n_samples, n, opts, labels, status, emb_out,
+                            dist_out, centroids, n_clusters);
+}
+
+extern "C" int32_t wlx_spk_diarize_pcm_long(wlx_spk* k, wlx_engine* e, int32_t slot, int32_t item, const int64_t* starts, const int64_t* n_samples,
+                                            int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels, int32_t* status, float* emb_out,
+                                            float* dist_out, float* centroids, int32_t* n_clusters) {
+    return spk_diarize_item("wlx_spk_diarize_pcm_long", WLX_SPK_LONG_MAX, true, k, e, slot, item, starts, n_samples, n, opts, labels, status,
+                            emb_out, dist_out, centroids, n_clusters);
 }
 
 // ------------------------------------------------------------------------------------------------ a wave of files (wlx_spk_diarize_many)
@@ -945,4 +1013,36 @@ extern "C" int32_t wlx_spk_debug_ahc_many(int32_t device, const float* dist, int
                                           int32_t* labels, int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
     if (!dist || !ns || !opts || !labels || !merges || !heights || !n_merges || !n_clusters) return set_error(WLX_ERR_ARG, "null argument");
     return spk_debug_ahc_run("wlx_spk_debug_ahc_many", device, dist, ns, n_files, opts, 0, labels, merges, heights, n_merges, n_clusters);
+}
+
+// ONE launch of spk_ahc_long_kernel: heights [n - 1] and merges [n - 1][2] copied in and out, the clustered matrix stays on the device
+extern "C" int32_t wlx_spk_debug_ahc_long(int32_t device, const float* dist, int32_t n, const wlx_spk_cluster_opts* opts, int32_t* labels,
+                                          int32_t* merges, float* heights, int32_t* n_merges, int32_t* n_clusters) {
+    const char* who = "wlx_spk_debug_ahc_long";
+    if (!dist || !opts || !labels || !merges || !heights || !n_merges || !n_clusters) return set_error(WLX_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > WLX_SPK_LONG_MAX) return set_error(WLX_ERR_ARG, "%s: n %d outside 1..%d", who, n, WLX_SPK_LONG_MAX);
+    CKR(spk_cluster_opts_ok(who, opts));
+    const size_t nh = (size_t)n - 1, room = std::max(nh, (size_t)1);      // (one row merges nothing: one entry of room, never written)
+    int counts[2] = {0, 0};                                   // (declared before S: it outlives the stream's copies on every return path)
+    HookScope S;
+    CKR(S.begin(device));
+    float *dD, *dH;
+    int *dM, *dL, *dC;
+    uint16_t* dP;
+    CKR(S.upload(&dD, dist, (size_t)n * n));
+    CKR(S.upload(&dH, nh ? heights : nullptr, room));
+    CKR(S.upload(&dM, nh ? merges : nullptr, 2 * room));
+    CKR(S.alloc(&dL, (size_t)n));
+    CKR(S.alloc(&dC, (size_t)2));
+    CKR(S.alloc(&dP, (size_t)n));
+    if (!launch_spk_ahc_long(dD, n, opts->threshold, opts->max_clusters, dP, dM, dH, dL, dC, S.st)) return set_error(WLX_ERR_ARG, "%s: the launcher refused the shape", who);
+    CKR(S.download(labels, dL, (size_t)n));
+    if (nh) {
+        CKR(S.download(heights, dH, nh));
+        CKR(S.download(merges, dM, 2 * nh));
+    }
+    CKR(S.download(counts, dC, (size_t)2));
+    CKR(S.finish());
+    *n_merges = counts[0], *n_clusters = counts[1];
+    return WLX_OK;
 }

@@ -183,10 +183,11 @@ class SpeakerEmbedderHIP:
         trimmed away or has not arrived"""
         return self._embed_ranges(ranges, lambda *a: self.lib.wlx_spk_embed_ring_batch(self.h, ring._h, *a))
 
-    def cluster(self, X, threshold: float, max_clusters: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    def cluster(self, X, threshold: float, max_clusters: int = 0, _long: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """wlx_spk_cluster: average-linkage clustering of the unit rows X [n][embed_dim] (n <= _lib.SPK_CLUSTER_MAX) at the cosine
         DISTANCE `threshold` on the device -> (labels int32 [n], numbered by first appearance; centroids float32 [K][embed_dim]).
         file_diarization.cluster_host states the rules."""
+        call = self.lib.wlx_spk_cluster_long if _long else self.lib.wlx_spk_cluster
         if self.h is None:
             raise _lib.WlxError("speaker engine is closed")
         X = np.ascontiguousarray(X, dtype=np.float32)
@@ -196,12 +197,22 @@ class SpeakerEmbedderHIP:
         opts = _lib.wlx_spk_cluster_opts(float(threshold), int(max_clusters))
         labels, cent, k = np.zeros(max(n, 1), dtype=np.int32), np.zeros((max(n, 1), dim), dtype=np.float32), C.c_int32()
         f32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-        _lib.check(self.lib.wlx_spk_cluster(self.h, X.ctypes.data_as(f32p), n, dim, C.byref(opts), labels.ctypes.data_as(i32p),
-                                            cent.ctypes.data_as(f32p), C.byref(k)))
+        _lib.check(call(self.h, X.ctypes.data_as(f32p), n, dim, C.byref(opts), labels.ctypes.data_as(i32p), cent.ctypes.data_as(f32p), C.byref(k)))
         return labels[:n], cent[:k.value].copy()
 
+    def cluster_long(self, X, threshold: float, max_clusters: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """wlx_spk_cluster_long: `cluster` for n <= _lib.SPK_LONG_MAX rows, on the long kernel; the same rules and, where both serve n,
+        the same results"""
+        return self.cluster(X, threshold, max_clusters, _long=True)
+
+    def diarize_resident_long(self, slot, item: int, windows, threshold: float, max_clusters: int = 0,
+                              want_embeddings: bool = False, want_distances: bool = False):
+        """wlx_spk_diarize_pcm_long: `diarize_resident` for up to _lib.SPK_LONG_MAX windows — an hour of speech at a 0.75 s hop is 4800 —
+        on the long kernel; the same rules and outputs. The first call allocates the matrix at m * m floats (92 MiB at 4800 windows)."""
+        return self.diarize_resident(slot, item, windows, threshold, max_clusters, want_embeddings, want_distances, _long=True)
+
     def diarize_resident(self, slot, item: int, windows, threshold: float, max_clusters: int = 0,
-                         want_embeddings: bool = False, want_distances: bool = False):
+                         want_embeddings: bool = False, want_distances: bool = False, _long: bool = False):
         """wlx_spk_diarize_pcm: every (start, n_samples) window of the PCM resident in `item` of `slot` embedded and all of them
         clustered on the device behind one wait (up to _lib.SPK_CLUSTER_MAX windows, each within max_seconds) ->
         (labels int32 [n], -1 for a window under 0.3 s; centroids float32 [K][embed_dim]), and with want_embeddings / want_distances
@@ -220,10 +231,10 @@ class SpeakerEmbedderHIP:
         dist = np.zeros((m, m), dtype=np.float32) if want_distances and m else None
         f32p, i32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
         ptr = lambda a: a.ctypes.data_as(f32p) if a is not None else None
+        call = self.lib.wlx_spk_diarize_pcm_long if _long else self.lib.wlx_spk_diarize_pcm
         with slot.lock:
-            _lib.check(self.lib.wlx_spk_diarize_pcm(self.h, slot.engine._h, slot.sid, int(item), starts.ctypes.data_as(i64p),
-                                                    counts.ctypes.data_as(i64p), n, C.byref(opts), labels.ctypes.data_as(i32p),
-                                                    status.ctypes.data_as(i32p), ptr(emb), ptr(dist), ptr(cent), C.byref(k)))
+            _lib.check(call(self.h, slot.engine._h, slot.sid, int(item), starts.ctypes.data_as(i64p), counts.ctypes.data_as(i64p), n,
+                            C.byref(opts), labels.ctypes.data_as(i32p), status.ctypes.data_as(i32p), ptr(emb), ptr(dist), ptr(cent), C.byref(k)))
         out = (labels[:n], cent[:k.value].copy())
         if want_embeddings:
             out += (emb[:n],)

@@ -275,8 +275,12 @@ class FileDiarizer:
         on_device = getattr(self.embedder, "diarize_resident", None)
         if on_device is not None and len(ranges) <= _lib.SPK_CLUSTER_MAX:
             return on_device(resident.slot, resident.item, ranges, self.distance_threshold, self.max_speakers)
+        long_form = getattr(self.embedder, "diarize_resident_long", None)          # (an hour of speech is about 4800 windows)
+        if long_form is not None and len(ranges) <= _lib.SPK_LONG_MAX:
+            return long_form(resident.slot, resident.item, ranges, self.distance_threshold, self.max_speakers)
         if on_device is not None:
-            logging.warning(f"file diarization: {len(ranges)} windows exceed the device's {_lib.SPK_CLUSTER_MAX}; clustering on the host")
+            cap = _lib.SPK_LONG_MAX if long_form is not None else _lib.SPK_CLUSTER_MAX
+            logging.warning(f"file diarization: {len(ranges)} windows exceed the device's {cap}; clustering on the host")
         embs = self.embedder.embed_resident(resident.slot, resident.item, ranges)
         took = [i for i, e in enumerate(embs) if e is not None]
         labels = np.full(len(ranges), -1, dtype=np.int32)
@@ -313,7 +317,8 @@ class FileDiarizer:
         """`diarize` of a wave of files, `residents[f]` (engine.ResidentPcm, different items of ONE slot) with the spans
         `spans_per_file[f]` -> the turns per file, those `diarize` gives for that file. With `diarize_many` on the embedder the windows
         of all files go to the device together (SpeakerEmbedderHIP.diarize_many: wlx_spk_diarize_many, one wait per call); a file with
-        more than _lib.SPK_CLUSTER_MAX windows keeps the host route of `cluster_windows`, and an embedder without `diarize_many` gets
+        more than _lib.SPK_CLUSTER_MAX windows takes the per-file route of `cluster_windows` (the long device form up to
+        _lib.SPK_LONG_MAX windows, the host beyond), and an embedder without `diarize_many` gets
         the loop over `diarize`. max_speakers: a cap per file in place of the diarizer's own. A file whose audio is not resident
         raises the error `diarize` raises for it."""
         if len(residents) != len(spans_per_file) or (max_speakers is not None and len(max_speakers) != len(residents)):
