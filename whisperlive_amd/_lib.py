@@ -15,7 +15,7 @@ CSRC = PKG_DIR / "csrc"
 # WLX_LIB selects another build of the same sources (scripts/trace_step.py: libwlx_trace.so, compiled with -DWLX_TRACE)
 DEFAULT_LIB = PKG_DIR / "libwlx.so"
 LIB_PATH = Path(os.environ["WLX_LIB"]).resolve() if os.environ.get("WLX_LIB") else DEFAULT_LIB
-SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "dec_bias.hip", "dec_grammar.hip", "dec_pattern.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "put_many.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
+SOURCES = ["pack.hip", "logmel.hip", "gemm.hip", "attention.hip", "decoder.hip", "align.hip", "dec_gemv.hip", "dec_vocab.hip", "search.hip", "dec_bias.hip", "dec_grammar.hip", "dec_pattern.hip", "dec_lm.hip", "host.hip", "engine.hip", "ring.hip", "engine_decode.hip", "engine_debug.hip", "resample.hip", "flac.hip", "adpcm.hip", "put_many.hip", "vad.hip", "mt.hip", "mt_search.hip", "mt_engine.hip", "spk.hip", "spk_cluster.hip", "spk_engine.hip",
            "kernel_hooks.hip"]
 EXPORTS = [
     "wlx_abi_version", "wlx_last_error", "wlx_engine_create", "wlx_engine_destroy", "wlx_engine_spec",
@@ -54,6 +54,8 @@ EXPORTS_GRAMMAR_ITEMS = ["wlx_grammar_set_items", "wlx_grammar_select", "wlx_deb
 EXPORTS_PATTERN = ["wlx_pattern_vocab_set", "wlx_pattern_set", "wlx_pattern_clear", "wlx_debug_pattern_apply"]
 # a pattern per item, declared in include/wlx_pattern_items.h (which wlx.h includes)
 EXPORTS_PATTERN_ITEMS = ["wlx_pattern_set_items", "wlx_pattern_select", "wlx_debug_pattern_apply_items"]
+# n-gram language-model fusion, declared in include/wlx_lm.h (which wlx.h includes)
+EXPORTS_LM = ["wlx_lm_create", "wlx_lm_destroy", "wlx_lm_set", "wlx_lm_clear", "wlx_debug_lm_apply"]
 # the long form of the offline speaker clustering, declared in include/wlx_spk_long.h (which wlx.h includes)
 EXPORTS_SPK_LONG = ["wlx_spk_cluster_long", "wlx_spk_diarize_pcm_long", "wlx_spk_debug_ahc_long"]
 
@@ -171,6 +173,8 @@ PATTERN_MAX_STATES, PATTERN_MAX_CELLS, PATTERN_MAX_TOKEN_BYTES, PATTERN_MAX_VOCA
 # wlx_pattern_items.h WLX_PATTERN_SET_MAX_*: tables of one set (wlx_pattern_set_items) and the caps of its pool over all tables
 PATTERN_SET_MAX_TABLES, PATTERN_SET_MAX_CELLS, PATTERN_SET_MAX_STATES = 64, 393216, 65536
 PATTERN_DEAD = 0xFFFF   # a transition into no state
+# wlx_lm.h WLX_LM_MAX_*: the caps of an n-gram language model (wlx_lm_create) and the models of one engine
+LM_MAX_ORDER, LM_MAX_STATES, LM_MAX_EDGES, LM_MAX_VOCAB, LM_MAX_MODELS = 5, 1 << 20, 1 << 22, 65536, 8
 DEBUG_GUARD = 64        # wlx.h WLX_DEBUG_GUARD: words a debug hook's output carries past what the kernel owns
 MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
@@ -350,7 +354,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
     except OSError as e:  # e.g. libamdhip64 missing
         raise WlxError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS + EXPORTS_PATTERN + EXPORTS_PATTERN_ITEMS + EXPORTS_SPK_LONG
+    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS + EXPORTS_PATTERN + EXPORTS_PATTERN_ITEMS + EXPORTS_LM + EXPORTS_SPK_LONG
                if not hasattr(lib, s)]
     if missing:
         raise WlxError(f"libwlx.so lacks symbols {missing}")
@@ -528,6 +532,15 @@ def load() -> C.CDLL:
         lib.wlx_debug_pattern_apply_items.argtypes = [i32, i32, i32, i32, i32p, i32p, u8p, u16p_, u8p, i32p, u8p, f32p, i32, i32, i32p, i64, i32p, i32p,
                                                       i32p, i32p, i32p, i16p, i16p]
         for name in EXPORTS_PATTERN_ITEMS:
+            getattr(lib, name).restype = i32
+    if EXPORTS_LM:                  # (scripts/lm_time.py alone empties the list, to load a library of the parent commit beside this one)
+        table = [i32p, i32p, f32p, i32p, f32p, i32p, f32p, i32p]     # edge_off, backoff_state, backoff_weight, edge tok / logp / next, unigram logp / next
+        lib.wlx_lm_create.argtypes = [vp, i32, i32, i32, i32] + table + [i32p]
+        lib.wlx_lm_destroy.argtypes = [vp, i32]
+        lib.wlx_lm_set.argtypes = [vp, i32, i32, C.c_float]
+        lib.wlx_lm_clear.argtypes = [vp, i32]
+        lib.wlx_debug_lm_apply.argtypes = [i32, i32, i32, i32, i32, i32] + table + [C.c_float, f32p, i32, i64, i32p, i32p, i32p, i32, i32p, i32p, i32p]
+        for name in EXPORTS_LM:
             getattr(lib, name).restype = i32
     if EXPORTS_SPK_LONG:            # (scripts/spk_long_time.py alone empties the list, to load a library of the parent commit beside this one)
         lib.wlx_spk_cluster_long.argtypes = lib.wlx_spk_cluster.argtypes

@@ -292,7 +292,8 @@ class BatchedInferencePipeline:
         return segments, info
 
     def transcribe(self, audio, *args, multichannel: bool = False, target_language: Optional[str] = None, translator=None,
-                   grammar_pattern: Optional[str] = None, grammar_ignore_case: bool = False, **kwargs):
+                   grammar_pattern: Optional[str] = None, grammar_ignore_case: bool = False, lm=None, lm_weight: Optional[float] = None,
+                   **kwargs):
         """The reference's transcribe — every argument of `_transcribe` above, by position or by name — and keyword-only options
         the reference does not have. multichannel=False is `_transcribe`, untouched. multichannel=True: every channel of the file is
         transcribed on its own while the chunks of all channels share the decode groups; segments carry `channel` and come sorted by
@@ -301,7 +302,16 @@ class BatchedInferencePipeline:
         changes nothing. grammar_pattern (with grammar_ignore_case): every window's text fully matches this regular expression
         (WhisperModelHIP.grammar(pattern=)) — the segments come back as a LIST, decoded inside the pattern's scope.
         (`__wrapped__` below: the signature introspection reports is the reference's, which is what a caller
-        written against the reference binds to.)"""
+        written against the reference binds to.) lm (an lm.NgramLM, with lm_weight): the n-gram model fused into every window's search
+        (WhisperModelHIP.language_model) — the segments come back as a LIST, decoded inside the model's scope; together
+        with grammar_pattern it is a ValueError."""
+        if lm is not None:
+            if grammar_pattern is not None:
+                raise ValueError("lm and grammar_pattern in one call: a language model together with a grammar is out of scope")
+            with self.model.language_model(lm, lm_weight):
+                segments, info = self.transcribe(audio, *args, multichannel=multichannel, target_language=target_language,
+                                                 translator=translator, **kwargs)
+                return list(segments), info
         if grammar_pattern is not None:
             with self.model.grammar(pattern=grammar_pattern, ignore_case=grammar_ignore_case):
                 segments, info = self.transcribe(audio, *args, multichannel=multichannel, target_language=target_language,

@@ -286,6 +286,31 @@ struct PatternItems {
 void launch_dec_pattern_items(float* logits, const SearchParams* sp_dev, int items, int V, const SearchState& st, const PatternItems& pi,
                               hipStream_t s);
 
+// ---------------------------------------------------------------- dec_lm.hip
+// An n-gram language model fused into the search (wlx_lm_create / wlx_lm_set): a backoff automaton over token ids
+// (lm_table.h checks it on the host). The arrays belong to the engine's model; the slot owns this descriptor, at a fixed device
+// address, and its per-(cache row, position) states. The kernel reads the descriptor from memory: one captured step graph serves any
+// model and any weight.
+struct LmDesc {
+    const int* edge_off;        // [n_states + 1] state n's edges are [edge_off[n], edge_off[n + 1]); state 0 (the empty context) has none
+    const int* backoff_state;   // [n_states] a strictly shorter context; every chain ends in state 0
+    const float* backoff_weight;    // [n_states]
+    const int* tok;             // [n_edges] ascending within a state, 0 .. eot
+    const float* logp;          // [n_edges]
+    const int* next;            // [n_edges]
+    const float* unigram_logp;  // [NGLM_MAX_VOCAB] dense scores of state 0, zero behind eot (the kernel fills whole chunks from it)
+    const int* unigram_next;    // [vocab]
+    float w;                    // the fusion weight
+    int eot, start, n_states;
+};
+struct LmFusion {
+    const LmDesc* desc;         // the slot's descriptor
+    int* state;                 // [cache_rows][448] context state of cache row r at position p (an array of this mode's own: a state needs 20 bits)
+};
+// one workgroup of 1024 threads per row, between the vocabulary projection and the search: the row's state from its parent's, then
+// l'(v) = l(v) + w s(v) - c over the text tokens and end-of-text; nothing else is written
+void launch_dec_lm(float* logits, const SearchParams* sp_dev, int rows, const SearchState& st, const LmFusion& lm, hipStream_t s);
+
 // softmax over ids [0, vlim) of row r, probability of token toks[r] -> out[r]   (text_token_probs of Whisper.align)
 void launch_token_prob_rows(const float* logits, long ldl, int vlim, int rows, const int* toks, float* out, hipStream_t s);
 // softmax prob of token `tok` in given logits rows -> out[rows]

@@ -17,8 +17,10 @@ namespace wlx {
 
 // the launch of a slot's decode step between the vocabulary projection and the search: none, keyword boosting with one table or a table per
 // item, or a grammar (wlx_grammar_set: masks where the others add) or a grammar per item (wlx_grammar_set_items), or a regular-expression
-// grammar over the text's bytes (wlx_pattern_set) or one per item (wlx_pattern_set_items). One mode at a time: the last set call decides.
-enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3, BIAS_GRAMMAR_ITEMS = 4, BIAS_PATTERN = 5, BIAS_PATTERN_ITEMS = 6 };
+// grammar over the text's bytes (wlx_pattern_set) or one per item (wlx_pattern_set_items), or the fusion of an n-gram language model
+// (wlx_lm_set). One mode at a time: the last set call decides.
+enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3, BIAS_GRAMMAR_ITEMS = 4, BIAS_PATTERN = 5, BIAS_PATTERN_ITEMS = 6,
+                      BIAS_LM = 7 };
 
 // what a captured decode-step graph depends on (engine_decode.hip get_step_graph)
 struct StepGraphKey {
@@ -27,7 +29,7 @@ struct StepGraphKey {
     int bias;                   // BiasMode of the slot: the step launches dec_bias_kernel (one table: wlx_bias_set) or dec_bias_items_kernel (per item:
                                 // wlx_bias_set_items) or dec_grammar_kernel (wlx_grammar_set) or dec_grammar_items_kernel (per item:
                                 // wlx_grammar_set_items) or dec_pattern_kernel (wlx_pattern_set) or dec_pattern_items_kernel (per item:
-                                // wlx_pattern_set_items) in front of the search, or nothing; a graph
+                                // wlx_pattern_set_items) or dec_lm_kernel (wlx_lm_set) in front of the search, or nothing; a graph
                                 // captured for one mode is never replayed
                                 // for another
     bool operator<(const StepGraphKey& o) const {
@@ -128,6 +130,10 @@ struct Slot {
     // a pattern per item (wlx_pattern_set_items / wlx_pattern_select; dec_pattern.hip dec_pattern_items_kernel): the pool and its pinned staging,
     // allocated at the first wlx_pattern_set_items and kept at those addresses; the selection is the one the per-item modes share (d_sel)
     PatternItems pattern_items{}; unsigned* d_ppool = nullptr; unsigned* h_ppool = nullptr; int pattern_tables = 0, ppool_eot = -1;
+    // n-gram language-model fusion (wlx_lm_set / wlx_lm_clear; dec_lm.hip): the descriptor's device copy and its pinned staging and the
+    // int32 states, allocated at the first wlx_lm_set and kept at those addresses. `nglm_id`: the engine's model the slot points at (-1:
+    // none; wlx_lm_destroy reads it under the engine's mutex), `nglm_eot` that model's end-of-text id
+    LmFusion nglm{}; LmDesc* d_nglm = nullptr; LmDesc* h_nglm = nullptr; std::atomic<int> nglm_id{-1}; int nglm_eot = -1;
     unsigned* d_suppress = nullptr;
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging
@@ -209,6 +215,10 @@ struct Engine {
     // d_tok_bytes padded to a multiple of 16 bytes; the host copies answer a second call (identical: nothing to do, else WLX_ERR_STATE)
     int* d_tok_off = nullptr; unsigned char* d_tok_bytes = nullptr; int pattern_vocab_eot = -1;
     std::vector<int32_t> h_tok_off; std::vector<uint8_t> h_tok_bytes;
+    // n-gram language models (wlx_lm_create / wlx_lm_destroy; dec_lm.hip), under `mu`: the device arrays of model i live in models[i].allocs
+    // and never move while the model lives; `desc` names them (w unset: a slot's descriptor is this plus its weight)
+    struct LmModel { bool live = false; std::vector<void*> allocs; LmDesc desc{}; };
+    LmModel models[8];
 };
 
 }  // namespace wlx

@@ -210,6 +210,7 @@ extern "C" void wlx_engine_destroy(wlx_engine* e) {
     (void)hipDeviceSynchronize();
     for (Slot* s : e->slots) slot_free(s);
     for (void* p : e->allocs) (void)hipFree(p);
+    for (auto& m : e->models) for (void* p : m.allocs) (void)hipFree(p);
     delete e;
 }
 

@@ -3,6 +3,7 @@
 #include "engine.h"
 #include "grammar_pool.h"
 #include "pattern_table.h"
+#include "lm_table.h"
 #include <sched.h>
 #include <limits>
 #include <algorithm>
@@ -341,7 +342,8 @@ static int graph_steps_for(const Slot* s, int rows) {
 // grammar (wlx_grammar_set) it is dec_grammar_kernel (dec_grammar.hip), which masks where the others add; with a pool of grammars
 // (wlx_grammar_set_items) dec_grammar_items_kernel, under the table selected for the row's item (wlx_grammar_select); with a
 // regular-expression grammar (wlx_pattern_set) dec_pattern_kernel (dec_pattern.hip), which walks every text token's bytes; with a pool of
-// them (wlx_pattern_set_items) dec_pattern_items_kernel, one workgroup per (item, tile) where the others take one per (row, tile).
+// them (wlx_pattern_set_items) dec_pattern_items_kernel, one workgroup per (item, tile) where the others take one per (row, tile); with an
+// n-gram language model (wlx_lm_set) dec_lm_kernel (dec_lm.hip), one workgroup per row, which rescores every text token.
 void wlx::launch_bias(Slot* s, int rows, int R) {
     if (s->bias_mode == BIAS_ONE) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
     else if (s->bias_mode == BIAS_ITEMS) launch_dec_bias_items(s->logits, s->d_sp, rows, s->st, s->bias_items, s->stream);
@@ -349,6 +351,7 @@ void wlx::launch_bias(Slot* s, int rows, int R) {
     else if (s->bias_mode == BIAS_GRAMMAR_ITEMS) launch_dec_grammar_items(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->grammar_items, s->stream);
     else if (s->bias_mode == BIAS_PATTERN) launch_dec_pattern(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->pattern, s->stream);
     else if (s->bias_mode == BIAS_PATTERN_ITEMS) launch_dec_pattern_items(s->logits, s->d_sp, rows / R, (int)s->ldl, s->st, s->pattern_items, s->stream);
+    else if (s->bias_mode == BIAS_LM) launch_dec_lm(s->logits, s->d_sp, rows, s->st, s->nglm, s->stream);
 }
 
 static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps) {
@@ -690,6 +693,8 @@ int wlx::generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, co
         return set_error(WLX_ERR_STATE, "generate: %d items, but the pattern selection covers %d (wlx_pattern_select)", batch, s->sel_n);
     if (s->bias_mode == BIAS_PATTERN_ITEMS && o->ids.eot != s->ppool_eot)
         return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's patterns were compiled for %d (wlx_pattern_set_items)", o->ids.eot, s->ppool_eot);
+    if (s->bias_mode == BIAS_LM && o->ids.eot != s->nglm_eot)
+        return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's language model was built for %d (wlx_lm_create)", o->ids.eot, s->nglm_eot);
     static const bool gen_trace = getenv("WLX_GEN_TRACE") != nullptr;
     double tg[2] = {0.0, 0.0};                                  // WLX_GEN_TRACE: host time in graph launch calls / in the polling waits
     const double tg0 = now_us();
@@ -820,6 +825,7 @@ extern "C" int32_t wlx_bias_clear(wlx_engine* e, int32_t slot) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
     sg_.s->bias_mode = BIAS_NONE;
+    sg_.s->nglm_id.store(-1);                    // (the slot points at no language model any more: wlx_lm_destroy)
     return WLX_OK;
 }
 
@@ -1107,6 +1113,110 @@ extern "C" int32_t wlx_pattern_select(wlx_engine* e, int32_t slot, int32_t n, co
             return set_error(WLX_ERR_ARG, "pattern select: item %d names table %d outside -1..%d", b, table_of_item[b], s->pattern_tables - 1);
     CK(hipSetDevice(e->device));
     return bias_select_upload(s, n, table_of_item);
+}
+
+// ---- n-gram language-model fusion (include/wlx_lm.h; dec_lm.hip). A model's arrays belong to the engine, go up once, complete on return, and
+// never move while it lives; a slot holds only a descriptor that names them, at a fixed address, and the states.
+extern "C" int32_t wlx_lm_create(wlx_engine* e, int32_t eot, int32_t order, int32_t n_states, int32_t start_state, const int32_t* edge_off,
+                                 const int32_t* backoff_state, const float* backoff_weight, const int32_t* edge_tok, const float* edge_logp,
+                                 const int32_t* edge_next, const float* unigram_logp, const int32_t* unigram_next, int32_t* lm_out) {
+    if (!e || !lm_out) return set_error(WLX_ERR_ARG, "null argument");
+    char why[240];
+    const int V = e->spec.vocab;
+    if (!lm_table_check(V, eot, order, n_states, start_state, edge_off, backoff_state, backoff_weight, edge_tok, edge_logp, edge_next,
+                        unigram_logp, unigram_next, why, sizeof(why)))
+        return set_error(WLX_ERR_ARG, "%s", why);
+    std::lock_guard<std::mutex> lk(e->mu);
+    int id = -1;
+    for (int i = 0; i < NGLM_MAX_MODELS && id < 0; ++i) if (!e->models[i].live) id = i;
+    if (id < 0) return set_error(WLX_ERR_STATE, "lm: the engine holds %d models already (models)", NGLM_MAX_MODELS);
+    CK(hipSetDevice(e->device));
+    Engine::LmModel& m = e->models[id];
+    const size_t n_edges = (size_t)edge_off[n_states];
+    // the unigram scores padded to whole chunks (the kernel fills LDS with 16-byte loads), zero behind end-of-text
+    std::vector<float> uni((size_t)NGLM_MAX_VOCAB, 0.f);
+    std::vector<int> unext((size_t)V, 0), boff(backoff_state, backoff_state + n_states);
+    std::vector<float> bw(backoff_weight, backoff_weight + n_states);
+    for (int v = 0; v <= eot; ++v) { uni[v] = unigram_logp[v]; unext[v] = unigram_next[v]; }
+    boff[0] = 0; bw[0] = 0.f;
+    int *d_off = nullptr, *d_boff = nullptr, *d_tok = nullptr, *d_next = nullptr, *d_unext = nullptr;
+    float *d_bw = nullptr, *d_logp = nullptr, *d_uni = nullptr;
+    auto up = [&](auto** dst, const auto* src, size_t n) -> int {
+        CKR(dalloc(m.allocs, dst, n, false));
+        if (n) CKR(upload_sync(*dst, src, n * sizeof(**dst)));
+        return WLX_OK;
+    };
+    int rc = up(&d_off, edge_off, (size_t)n_states + 1);
+    if (rc == WLX_OK) rc = up(&d_boff, boff.data(), boff.size());
+    if (rc == WLX_OK) rc = up(&d_bw, bw.data(), bw.size());
+    if (rc == WLX_OK) rc = up(&d_tok, edge_tok, n_edges);
+    if (rc == WLX_OK) rc = up(&d_logp, edge_logp, n_edges);
+    if (rc == WLX_OK) rc = up(&d_next, edge_next, n_edges);
+    if (rc == WLX_OK) rc = up(&d_uni, uni.data(), uni.size());
+    if (rc == WLX_OK) rc = up(&d_unext, unext.data(), unext.size());
+    if (rc != WLX_OK) {
+        for (void* p : m.allocs) (void)hipFree(p);
+        m.allocs.clear();
+        return rc;
+    }
+    m.desc = LmDesc{d_off, d_boff, d_bw, d_tok, d_logp, d_next, d_uni, d_unext, 0.f, eot, start_state, n_states};
+    m.live = true;
+    *lm_out = id;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_lm_destroy(wlx_engine* e, int32_t lm) {
+    if (!e) return set_error(WLX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (lm < 0 || lm >= NGLM_MAX_MODELS || !e->models[lm].live) return set_error(WLX_ERR_ARG, "lm: no model %d", lm);
+    for (const Slot* s : e->slots)
+        if (s && s->nglm_id.load() == lm) return set_error(WLX_ERR_STATE, "lm: a slot points at model %d (wlx_lm_clear)", lm);
+    CK(hipSetDevice(e->device));
+    Engine::LmModel& m = e->models[lm];
+    for (void* p : m.allocs) (void)hipFree(p);  // (hipFree waits for the device: no launch still reads the arrays)
+    m.allocs.clear();
+    m.live = false;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_lm_set(wlx_engine* e, int32_t slot, int32_t lm, float weight) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    // a refused call leaves whatever is installed whole (and allocates nothing)
+    if (!std::isfinite(weight) || !(weight > 0.f)) return set_error(WLX_ERR_ARG, "lm: the weight must be finite and above 0");
+    LmDesc desc;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (lm < 0 || lm >= NGLM_MAX_MODELS || !e->models[lm].live) return set_error(WLX_ERR_ARG, "lm: no model %d", lm);
+        desc = e->models[lm].desc;
+        s->nglm_id.store(lm);                   // (under the engine's mutex: wlx_lm_destroy sees the slot from here on)
+    }
+    desc.w = weight;
+    CK(hipSetDevice(e->device));
+    if (!s->d_nglm) {
+        LmDesc *dd = nullptr, *hd = nullptr;
+        int* state = nullptr;
+        CKR(dalloc(s->allocs, &dd, (size_t)1, true));
+        CKR(halloc(s->host_allocs, &hd, (size_t)1));
+        CKR(dalloc(s->allocs, &state, (size_t)std::max(s->cache_rows, s->rows_cap) * WLX_T_TEXT, true));
+        s->d_nglm = dd; s->h_nglm = hd; s->nglm = LmFusion{dd, state};
+    }
+    // the staging may still feed the copy of the previous descriptor: wait for the stream, then rewrite it
+    CK(hipStreamSynchronize(s->stream));
+    *s->h_nglm = desc;
+    CK(hipMemcpyAsync(s->d_nglm, s->h_nglm, sizeof(LmDesc), hipMemcpyHostToDevice, s->stream));
+    s->nglm_eot = desc.eot;
+    s->bias_mode = BIAS_LM;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_lm_clear(wlx_engine* e, int32_t slot) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    if (sg_.s->bias_mode == BIAS_LM) sg_.s->bias_mode = BIAS_NONE;      // (a table of another mode installed since stays)
+    sg_.s->nglm_id.store(-1);
+    return WLX_OK;
 }
 
 extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot, const int32_t* lang_ids,

@@ -93,6 +93,33 @@ class HipWhisperEngine:
             check(self.lib.wlx_pattern_vocab_set(self._h, int(eot), _i32p(off), by.ctypes.data_as(C.POINTER(C.c_uint8))))
             self._pattern_vocab, self.pattern_vocab_eot = tok_bytes, int(eot)
 
+    def create_lm(self, lm) -> int:
+        """The engine's handle of an lm.NgramLM (wlx_lm_create): the model goes to the device once and serves every slot
+        (Slot.set_lm). The same object again returns the same handle. ValueError for a model built for another vocabulary or beyond
+        the engine's models cap; WlxError (ERR_ARG) for a table the library refuses."""
+        with self._lock:
+            held = self.__dict__.setdefault("_lms", {})
+            if id(lm) in held:
+                return held[id(lm)][0]
+            if lm.vocab != self.spec.vocab:
+                raise ValueError(f"the language model was built for a vocabulary of {lm.vocab}, the model has {self.spec.vocab}")
+            if len(held) >= _lib.LM_MAX_MODELS:
+                raise ValueError(f"lm: the engine holds {_lib.LM_MAX_MODELS} models already (models): destroy_lm one first")
+            off, boff, bw, tok, logp, nxt, uni, unext = lm.packed()
+            h = C.c_int32(-1)
+            check(self.lib.wlx_lm_create(self._h, lm.eot, lm.order, lm.n_states, lm.start_state, _i32p(off), _i32p(boff), _f32p(bw),
+                                         _i32p(tok), _f32p(logp), _i32p(nxt), _f32p(uni), _i32p(unext), C.byref(h)))
+            held[id(lm)] = (h.value, lm)        # (the object is kept: its id is the key)
+            return h.value
+
+    def destroy_lm(self, lm) -> None:
+        """Free the engine's copy of `lm` (wlx_lm_destroy): WlxError (ERR_STATE) while a slot points at it."""
+        with self._lock:
+            held = self.__dict__.get("_lms", {})
+            if id(lm) in held:
+                check(self.lib.wlx_lm_destroy(self._h, held[id(lm)][0]))
+                del held[id(lm)]
+
     def create_slot(self, max_batch: int = 1, max_rows_per_item: int = 5) -> "Slot":
         sid = C.c_int32(-1)
         check(self.lib.wlx_slot_create(self._h, max_batch, max_rows_per_item, C.byref(sid)))
@@ -654,7 +681,7 @@ class Slot:
     def clear_bias(self) -> None:
         """Decode without a bias table again (wlx_bias_clear)."""
         check(self.lib.wlx_bias_clear(self.engine._h, self.sid))
-        self._bias_table = self._grammar = self._pattern = None
+        self._bias_table = self._grammar = self._pattern = self._lm = None
 
     # ---- grammar-constrained decoding
     def set_grammar(self, grammar) -> None:
@@ -727,6 +754,20 @@ class Slot:
         """indices[b]: the pattern (an index into the installed set, -1: none) of item b of the following generate calls (wlx_pattern_select)"""
         sel = np.ascontiguousarray(list(indices), dtype=np.int32)
         check(self.lib.wlx_pattern_select(self.engine._h, self.sid, sel.size, _i32p(sel)))
+
+    # ---- n-gram language-model fusion
+    def set_lm(self, lm, weight: float) -> None:
+        """Point the slot at an lm.NgramLM with fusion weight `weight` (wlx_lm_set): every decode step of its generate calls, and of the
+        debug_search hooks, then runs the fusion launch in front of the search, in place of a keyword table's or a grammar's (one mode
+        at a time). The model is the engine's (HipWhisperEngine.create_lm sends it once); the slot's descriptor sits at a fixed address:
+        captured step graphs serve any model and any weight."""
+        check(self.lib.wlx_lm_set(self.engine._h, self.sid, self.engine.create_lm(lm), float(weight)))
+        self._lm, self._grammar, self._bias_table, self._pattern = (lm, float(weight)), None, None, None
+
+    def clear_lm(self) -> None:
+        """Decode without a language model again (wlx_lm_clear): the step is the launch list of a slot that never had one."""
+        check(self.lib.wlx_lm_clear(self.engine._h, self.sid))
+        self._lm = None
 
     def align(self, tokens: Sequence[int], n_sot: int, num_frames: int, heads: Sequence[Tuple[int, int]], eot: int,
               median_filter_width: int = 7, item: int = 0):

@@ -64,6 +64,7 @@ import numpy as np
 
 from . import biasing as _biasing
 from . import grammar as _grammar
+from . import lm as _lm
 from . import pattern as _pattern
 from . import vad as _vad
 from . import word_timing as _wt
@@ -430,6 +431,19 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     grammars, grammars_repeat = kwargs.pop("grammars", None), kwargs.pop("grammars_repeat", True)
     grammar_pattern, grammar_ignore_case = kwargs.pop("grammar_pattern", None), kwargs.pop("grammar_ignore_case", False)
     grammar_patterns, patterns_ignore_case = kwargs.pop("grammar_patterns", None), kwargs.pop("grammar_patterns_ignore_case", False)
+    lm, lm_weight = kwargs.pop("lm", None), kwargs.pop("lm_weight", None)
+    lm_scope = None
+    if lm is not None:
+        # ONE n-gram language model for the job, refused here, before the first file is read
+        if not isinstance(lm, _lm.NgramLM):
+            raise ValueError("lm: one NgramLM for all files (a language model per file or per item is out of scope)")
+        if grammar is not None or grammars is not None or grammar_pattern is not None or grammar_patterns is not None:
+            raise ValueError("lm and a grammar in one job: a language model together with a grammar is out of scope")
+        if any(v is not None for v in bias_args.values()):
+            raise ValueError("lm and keywords / logit_bias in one job: a language model together with keyword boosting is out of scope")
+        if not hasattr(pipe.model, "language_model"):
+            raise ValueError("lm: this transcriber takes no language model")
+        lm_scope = pipe.model.language_model(lm, lm_weight)
     pat = None
     if grammar_patterns is not None:
         if grammar_pattern is not None:
@@ -484,6 +498,8 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     # a pattern PER FILE, the same way: compiled here, before any audio work
     file_patterns = per_file_patterns(pipe.model, grammar_patterns, patterns_ignore_case, a, len(audios)) if grammar_patterns is not None else None
     job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables, file_grammars, file_patterns)
+    if lm_scope is not None:
+        return _under_grammar(job, lm_scope.value, lambda v: _lm.scope(*v))
     if pat is not None:
         return _under_grammar(job, pat, _pattern.scope)
     if grammar is None:

@@ -487,8 +487,18 @@ class RestServer:
                  max_body_bytes: int = 512 << 20, diarization_model: Optional[str] = None,
                  embedder_factory: Optional[Callable] = None, file_batch_size: int = 0, file_batch_window_ms: int = 0,
                  pipeline_factory: Optional[Callable] = None, translation_model: Optional[str] = None,
-                 translator_factory: Optional[Callable] = None, file_batch_wave_put: bool = False):
+                 translator_factory: Optional[Callable] = None, file_batch_wave_put: bool = False, lm: Optional[str] = None,
+                 lm_weight: Optional[float] = None):
         self.host, self.port, self.model = host, int(port), model
+        # an ARPA file over token ids (lm.NgramLM.from_arpa): every upload is then decoded with the model fused into the
+        # search at `lm_weight` (None: lm.DEFAULT_WEIGHT, which is not tuned) unless its `lm_weight` form field says otherwise
+        self.lm_path, self.lm_weight = lm, lm_weight
+        if lm_weight is not None and not (lm_weight == lm_weight and 0 < lm_weight < float("inf")):
+            raise ValueError("lm_weight must be a finite number above 0")
+        if lm_weight is not None and lm is None:
+            raise ValueError("lm_weight needs lm (an ARPA file)")
+        self._lms: Dict[int, object] = {}
+        self._lms_mu = threading.Lock()
         self.file_batch_wave_put = bool(file_batch_wave_put)     # the pooled jobs put each wave of files in one call (FileBatcher.wave_put)
         # a small100 / M2M100 checkpoint (a directory or a hub id, resolved as the WebSocket server resolves its own): requests may then
         # carry target_language. translator_factory: (directory, device index) -> translator; None = translation.shared_translator
@@ -600,6 +610,38 @@ class RestServer:
                 else:
                     ServeClientHIP.MODELS[device_index] = ServeClientHIP.create_model(self.model, device_index, **kw)
             return ServeClientHIP.MODELS[device_index]
+
+    def lm_scope(self, transcriber, lm_weight: Optional[str], exclusive: bool):
+        """The `lm_weight` form field -> the context manager under which the upload is decoded (WhisperModelHIP.language_model on the
+        request's thread), or None. Absent: the server's weight; `0`: no fusion for this upload. 400: a field on a server started
+        without --lm, a weight that is no number or is negative, a model together with keywords or a grammar (`exclusive`), a
+        transcriber that takes no language model. The ARPA file is read once per transcriber."""
+        given = lm_weight is not None and lm_weight.strip() != ""
+        if self.lm_path is None:
+            if given:
+                raise _HttpError(400, {"error": "lm_weight: this server was started without --lm"})
+            return None
+        weight = self.lm_weight
+        if given:
+            try:
+                weight = float(lm_weight)
+            except ValueError:
+                weight = -1.0
+            if not 0 <= weight < float("inf"):
+                raise _HttpError(400, {"error": "lm_weight must be a non-negative number (0: no language model for this request)"})
+            if weight == 0:
+                return None
+        if exclusive:
+            if not given:
+                return None                     # the request's own keywords or grammar take the slot's launch: the server's model stands back
+            raise _HttpError(400, {"error": "lm_weight cannot be combined with keywords or a grammar: a language model together with either is out of scope"})
+        if not hasattr(transcriber, "language_model"):
+            raise _HttpError(400, {"error": "lm_weight: this server's transcriber takes no language model"})
+        with self._lms_mu:
+            if id(transcriber) not in self._lms:
+                self._lms[id(transcriber)] = transcriber.load_lm(self.lm_path)
+            model = self._lms[id(transcriber)]
+        return transcriber.language_model(model, weight)
 
     def transcribe_file(self, transcriber, data: bytes, multichannel: bool = False, **kw):
         """-> (iterable of segments or None, info or None). file_batch_size = 0: today's sequential path, exactly. Otherwise the batched
@@ -887,6 +929,7 @@ class _Handler(BaseHTTPRequestHandler):
         keywords, keywords_boost = many("keywords") + many("keywords[]"), one("keywords_boost")
         grammar, grammar_repeat = many("grammar") + many("grammar[]"), one("grammar_repeat")
         grammar_pattern, grammar_ignore_case = one("grammar_pattern"), one("grammar_ignore_case")
+        lm_weight = one("lm_weight")
         known_speaker_references = fields.get("known_speaker_references", []) + fields.get("known_speaker_references[]", [])
         want_words = bool(timestamp_granularities and "word" in timestamp_granularities)
         rest = self.rest
@@ -898,6 +941,8 @@ class _Handler(BaseHTTPRequestHandler):
                 raise _HttpError(400, {"error": "keywords cannot be combined with stream: send the request without stream"})
             if grammar or grammar_repeat or grammar_pattern:
                 raise _HttpError(400, {"error": "grammar cannot be combined with stream: send the request without stream"})
+            if lm_weight and lm_weight.strip():
+                raise _HttpError(400, {"error": "lm_weight cannot be combined with stream: send the request without stream"})
             return self._stream(file, language, prompt, temperature, want_words, target_language)
 
         ignored_params = []
@@ -947,8 +992,13 @@ class _Handler(BaseHTTPRequestHandler):
             gram = grammar_scope(transcriber, grammar, grammar_repeat, keywords, keywords_boost, grammar_pattern, grammar_ignore_case)
             if gram is not None and getattr(gram, "grammar", None) is None:
                 pooled, pooled_diarizer = False, None
+            # a language model (--lm): the upload is decoded in this thread under the model's scope, never pooled
+            fused = rest.lm_scope(transcriber, lm_weight, exclusive=bool(keywords or grammar or (grammar_pattern and grammar_pattern.strip())))
+            if fused is not None:
+                pooled, pooled_diarizer = False, None
             bias = keyword_scope(transcriber, keywords, keywords_boost, compact=pooled)
-            with (bias if bias is not None and not pooled else contextlib.nullcontext()), (gram if gram is not None and not pooled else contextlib.nullcontext()):
+            with (bias if bias is not None and not pooled else contextlib.nullcontext()), (gram if gram is not None and not pooled else contextlib.nullcontext()), \
+                    (fused if fused is not None else contextlib.nullcontext()):
                 if pooled:
                     segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
                                                             temperature=temperature, word_timestamps=want_words, hotwords=hotwords,
@@ -1128,6 +1178,10 @@ def main(argv=None):
                          "(needs --file_batch_size; 0 = every request runs alone)")
     ap.add_argument("--file_batch_wave_put", action="store_true",
                     help="the pooled jobs of --file_batch_window_ms put each wave of files on the device in one call (off by default)")
+    ap.add_argument("--lm", default=None,
+                    help="ARPA file of an n-gram language model over token ids, fused into every upload's search (shallow fusion)")
+    ap.add_argument("--lm_weight", type=float, default=None,
+                    help="fusion weight of --lm (default 0.3, not tuned); a request's lm_weight form field overrides it, 0 turns it off")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if a.metrics_port > 0:
@@ -1136,7 +1190,7 @@ def main(argv=None):
                cors_origins=a.cors_origins, rate_limit_rpm=a.rate_limit_rpm, max_body_bytes=a.max_body_mb << 20,
                diarization_model=a.diarization_model, file_batch_size=a.file_batch_size,
                file_batch_window_ms=a.file_batch_window_ms, translation_model=a.translation_model,
-               file_batch_wave_put=a.file_batch_wave_put).serve_forever()
+               file_batch_wave_put=a.file_batch_wave_put, lm=a.lm, lm_weight=a.lm_weight).serve_forever()
 
 
 if __name__ == "__main__":

@@ -451,6 +451,33 @@ def pattern_options(transcriber, grammar_pattern, grammar_ignore_case, grammar=N
     return transcriber.grammar(pattern=grammar_pattern, ignore_case=bool(grammar_ignore_case))
 
 
+def lm_options(transcriber, lm_path, server_weight, lm_weight, exclusive: bool, cache: dict):
+    """`lm_weight` of a session's first message on a server started with --lm -> the scope under which the session decodes
+    (WhisperModelHIP.language_model), or None: absent means the server's weight, 0 means no fusion for this session. ValueError: a
+    weight on a server without --lm, one that is no non-negative number, a model together with keywords or a grammar (out of scope), a
+    transcriber that takes no language model. The ARPA file is read once per transcriber (`cache`)."""
+    if lm_path is None:
+        if lm_weight is not None:
+            raise ValueError("lm_weight: this server was started without --lm")
+        return None
+    weight = server_weight
+    if lm_weight is not None:
+        if isinstance(lm_weight, bool) or not isinstance(lm_weight, (int, float)) or not 0 <= lm_weight < float("inf"):
+            raise ValueError("lm_weight must be a non-negative number (0: no language model for this session)")
+        if lm_weight == 0:
+            return None
+        weight = float(lm_weight)
+    if exclusive:
+        if lm_weight is None:
+            return None                         # the session's own keywords or grammar take the slot's launch: the server's model stands back
+        raise ValueError("lm_weight cannot be combined with keywords or a grammar: a language model together with either is out of scope")
+    if not hasattr(transcriber, "language_model"):
+        raise ValueError("this server's transcriber takes no language model")
+    if id(transcriber) not in cache:
+        cache[id(transcriber)] = transcriber.load_lm(lm_path)
+    return transcriber.language_model(cache[id(transcriber)], weight)
+
+
 class ServeClientHIP(ServeClientBase):
     """Backend adaptor for the MI355X engine. Class-level registries mirror the reference's SINGLE_MODEL /
     BATCH_WORKER hooks (faster_whisper_backend.py:15-17) but are keyed by GPU: one shared transcriber per device."""
@@ -462,6 +489,9 @@ class ServeClientHIP(ServeClientBase):
     BATCH_WORKERS = {}              # device index -> BatchInferenceWorker (one per GPU; set by TranscriptionServer)
     _bias = None                    # the session's keyword table as a scope (WhisperModelHIP.keyword_bias); None: a session without keywords
     _grammar = None                 # the session's grammar as a scope (WhisperModelHIP.grammar); None: a session without one
+    _lm = None                      # the session's language model as a scope (WhisperModelHIP.language_model); None: a session without one
+    LM_PATH, LM_WEIGHT = None, None  # the server's --lm ARPA file and --lm_weight (set by TranscriptionServer.run); LM_MODELS: read once per transcriber
+    LM_MODELS = {}
     BACKEND_NAME = "faster_whisper"  # the stock Python client only keeps completed segments for this string (client.py:182,399)
 
     def __init__(self, websocket, task="transcribe", device=None, language=None, client_uid=None, model="small.en",
@@ -470,7 +500,7 @@ class ServeClientHIP(ServeClientBase):
                  translation_queue=None, hotwords=None, diarization=None, word_timestamps=False, *,
                  device_index: int = 0, transcriber=None, model_factory=None, serialize_single_model: bool = False,
                  start_thread: bool = True, max_batch: int = 1, keywords=None, keywords_boost=None, grammar=None,
-                 grammar_repeat=None, grammar_pattern=None, grammar_ignore_case=None):
+                 grammar_repeat=None, grammar_pattern=None, grammar_ignore_case=None, lm_weight=None):
         super().__init__(client_uid, websocket, send_last_n_segments, no_speech_thresh, clip_audio, same_output_threshold,
                          translation_queue, diarization, word_timestamps)
         self.cache_path = cache_path
@@ -536,6 +566,16 @@ class ServeClientHIP(ServeClientBase):
                 self.websocket.close()
                 del self.transcriber            # (what the server reads as "no session")
                 return
+        try:
+            with ServeClientHIP.MODELS_LOCK:
+                self._lm = lm_options(self.transcriber, ServeClientHIP.LM_PATH, ServeClientHIP.LM_WEIGHT, lm_weight,
+                                      self._grammar is not None or self._bias is not None, ServeClientHIP.LM_MODELS)
+        except (ValueError, TypeError, OSError) as e:
+            logging.error(f"lm_weight refused for {self.client_uid}: {e}")
+            self.websocket.send(json.dumps({"uid": self.client_uid, "status": "ERROR", "message": f"Unsupported language model: {e}"}))
+            self.websocket.close()
+            del self.transcriber                # (what the server reads as "no session")
+            return
         self.use_vad = use_vad
         self.trans_thread = threading.Thread(target=self.speech_to_text, daemon=True)
         if start_thread:
@@ -660,6 +700,10 @@ class ServeClientHIP(ServeClientBase):
             # one grammar serves every item of a decode group, so a session with a grammar does not join the worker's mixed groups: it
             # decodes on its own slot under its grammar
             with self._grammar:
+                return self._transcribe_direct(input_sample)
+        if self._lm is not None:
+            # one model and weight serve every item of a decode group too: the session decodes on its own slot under its scope
+            with self._lm:
                 return self._transcribe_direct(input_sample)
         if worker is None and self._bias is not None:
             with self._bias:

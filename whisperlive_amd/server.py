@@ -309,6 +309,7 @@ class TranscriptionServer:
                 keywords=options.get("keywords"), keywords_boost=options.get("keywords_boost"),
                 grammar=options.get("grammar"), grammar_repeat=options.get("grammar_repeat"),
                 grammar_pattern=options.get("grammar_pattern"), grammar_ignore_case=options.get("grammar_ignore_case"),
+                lm_weight=options.get("lm_weight"),
             )
             if translation_client is not None:
                 client.translation_client, client.translation_thread = translation_client, translation_thread
@@ -393,7 +394,8 @@ class TranscriptionServer:
                     max_batch=self.batch_config["max_batch_size"] if self.batch_config is not None else 1,
                     keywords=options.get("keywords"), keywords_boost=options.get("keywords_boost"),
                     grammar=options.get("grammar"), grammar_repeat=options.get("grammar_repeat"),
-                    grammar_pattern=options.get("grammar_pattern"), grammar_ignore_case=options.get("grammar_ignore_case"))
+                    grammar_pattern=options.get("grammar_pattern"), grammar_ignore_case=options.get("grammar_ignore_case"),
+                    lm_weight=options.get("lm_weight"))
 
             session = MultichannelSession(websocket, uid, audio_format, channels, sample_rate, make_child)
             if not session.ready:                         # model load failed: ERROR already sent, socket closed
@@ -612,14 +614,19 @@ class TranscriptionServer:
             batch_enabled=False, batch_max_size=8, batch_window_ms=50, raw_pcm_input=False, metrics_port: int = 0,
             api_key: Optional[str] = None, rate_limit_rpm: int = 0, segment_post_processor=None,
             devices: Optional[Sequence[int]] = None, model_factory=None, ready: Optional[threading.Event] = None,
-            vad_weights: Optional[str] = None, batch_lanes: int = 2):
-        """Serve until ``shutdown()``. Same arguments as the reference (server.py:600-622) plus ``devices`` (GPU
+            vad_weights: Optional[str] = None, batch_lanes: int = 2, lm: Optional[str] = None, lm_weight: Optional[float] = None):
+        """``lm`` (an ARPA file over token ids) with ``lm_weight``: every session decodes with the n-gram model fused into its search
+         unless the `lm_weight` of its first message says otherwise (0: off).
+        Serve until ``shutdown()``. Same arguments as the reference (server.py:600-622) plus ``devices`` (GPU
         indices to shard connections over), ``model_factory`` and ``ready`` (set once the socket is listening;
         ``self.port`` then holds the bound port — pass ``port=0`` for an ephemeral one)."""
         backend_type = self.configure(backend, faster_whisper_custom_model_path, whisper_tensorrt_path, single_model,
                                       max_clients, max_connection_time, cache_path, enable_rest, batch_enabled,
                                       batch_max_size, batch_window_ms, raw_pcm_input, segment_post_processor, devices,
                                       model_factory, vad_weights, batch_lanes)
+        if lm_weight is not None and (lm is None or not 0 < lm_weight < float("inf")):
+            raise ValueError("lm_weight needs lm (an ARPA file) and must be a finite number above 0")
+        ServeClientHIP.LM_PATH, ServeClientHIP.LM_WEIGHT = lm, lm_weight
         if metrics_port > 0:
             wl_metrics.start_metrics_server(metrics_port)
         extra = {}
@@ -669,13 +676,17 @@ def main(argv=None):
     ap.add_argument("--vad_weights", default=os.environ.get("WLX_SILERO_VAD_ONNX") or os.environ.get("WLX_SILERO_VAD_NPZ"),
                     help="Silero VAD weights: the silero_vad.onnx the reference downloads, or an .npz export of it "
                          "(python -m whisperlive_amd.silero_export); without it use_vad is refused with a WARNING")
+    ap.add_argument("--lm", default=None, help="ARPA file of an n-gram language model over token ids, fused into every session's search")
+    ap.add_argument("--lm_weight", type=float, default=None,
+                    help="fusion weight of --lm (default 0.3, not tuned); `lm_weight` in a session's first message overrides it, 0 turns it off")
     a = ap.parse_args(argv)
     TranscriptionServer().run(
         a.host, port=a.port, backend=a.backend, faster_whisper_custom_model_path=a.model_path,
         single_model=not a.no_single_model, max_clients=a.max_clients, max_connection_time=a.max_connection_time,
         batch_enabled=a.batch_inference, batch_max_size=a.batch_max_size, batch_window_ms=a.batch_window_ms, batch_lanes=a.batch_lanes,
         raw_pcm_input=a.raw_pcm_input, metrics_port=a.metrics_port, api_key=a.api_key,
-        devices=[int(x) for x in a.devices.split(",") if x != ""], vad_weights=a.vad_weights)
+        devices=[int(x) for x in a.devices.split(",") if x != ""], vad_weights=a.vad_weights,
+        **(dict(lm=a.lm, lm_weight=a.lm_weight) if a.lm is not None or a.lm_weight is not None else {}))
 
 
 if __name__ == "__main__":

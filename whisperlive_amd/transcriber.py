@@ -32,6 +32,7 @@ import numpy as np
 from . import _lib
 from . import biasing as _biasing
 from . import grammar as _grammar
+from . import lm as _lm
 from . import pattern as _pattern
 from . import vad as _vad
 from . import word_timing as _wt
@@ -226,6 +227,19 @@ class _EngineModel:
         cap_rows = slot_rows * slot_items if isinstance(slot_rows, int) and isinstance(slot_items, int) else 64
         group = max(1, min(self.MAX_DEC_ROWS, max(cap_rows, rows_per_item)) // rows_per_item)
         items = encoder_output.items if encoder_output.items is not None else list(range(encoder_output.batch))
+        # an n-gram language model (WhisperModelHIP.language_model) takes the slot's one launch in front of the search: not
+        # together with keywords or a grammar. One model for every item; the engine holds it, the slot only points at it
+        lmv = _lm.current()
+        if lmv is not None:
+            if _biasing.current() is not None or _biasing.current_items() is not None:
+                raise ValueError("a language model together with keyword boosting is out of scope: decode under one of them")
+            if any(c is not None for c in (_grammar.current(), _grammar.current_items(), _pattern.current(), _pattern.current_items())):
+                raise ValueError("a language model together with a grammar is out of scope: decode under one of them")
+            if lmv[0].eot != o.token_ids.eot:
+                raise ValueError(f"the language model was built for end-of-text {lmv[0].eot}, this model's is {o.token_ids.eot}")
+            _lm.install(slot, lmv)
+        elif getattr(slot, "_lm", None) is not None:
+            _lm.install(slot, None)
         # keyword boosting: the calling thread's table (WhisperModelHIP.keyword_bias) goes onto the slot this call decodes on; a slot that
         # never saw a table is left alone
         table = _biasing.current()
@@ -579,6 +593,28 @@ class WhisperModelHIP:
             return _pattern.scope(_pattern.compile_pattern(pattern, ignore_case=ignore_case))
         return _grammar.scope(self.compile_grammar(phrases, repeat))
 
+    def language_model(self, lm, weight: Optional[float] = None):
+        """Context manager: inside the block every generate of the CALLING THREAD decodes with the n-gram model `lm` (lm.NgramLM:
+        from_arpa, from_corpus) fused into the search on its slot (shallow fusion) — the streaming transcriber,
+        BatchedInferencePipeline.transcribe, transcribe_many and the temperature fallback alike. Over the text tokens and end-of-text
+        l' = l + weight * s - c, normalised so that the mass of text against timestamps stays the acoustic model's; the scores /
+        avg_logprob are those of the fused distribution. `weight` defaults to lm.DEFAULT_WEIGHT (0.3), which is NOT tuned: there is no
+        real checkpoint or corpus here. One model for every item; a model per file or item, a model together with keyword boosting or
+        a grammar, word-level ARPA files and feeding the prompt's text to the model are out of scope (ValueError). Other threads are
+        untouched; scopes nest."""
+        if lm is not None:
+            if _biasing.current() is not None or _biasing.current_items() is not None:
+                raise ValueError("a language model together with keyword boosting is out of scope: decode under one of them")
+            if any(c is not None for c in (_grammar.current(), _grammar.current_items(), _pattern.current(), _pattern.current_items())):
+                raise ValueError("a language model together with a grammar is out of scope: decode under one of them")
+            if isinstance(lm, _lm.NgramLM) and lm.eot != self.token_ids.eot:
+                raise ValueError(f"the language model was built for end-of-text {lm.eot}, this model's is {self.token_ids.eot}")
+        return _lm.scope(lm, _lm.DEFAULT_WEIGHT if weight is None else weight)
+
+    def load_lm(self, path_or_text):
+        """lm.NgramLM.from_arpa for this model's vocabulary and end-of-text id"""
+        return _lm.NgramLM.from_arpa(path_or_text, eot=self.token_ids.eot, vocab=self.spec.vocab)
+
     def compile_grammar(self, phrases=None, repeat: bool = True):
         """the grammar.Grammar `grammar` decodes under"""
         return _grammar.compile_grammar(self._base_tokenizer, phrases, repeat, vocab=self.spec.vocab, eot=self.token_ids.eot)
@@ -726,7 +762,20 @@ class WhisperModelHIP:
                    *, keywords=None, keywords_boost: Optional[float] = None, logit_bias: Optional[Dict[int, float]] = None,
                    keywords_compact: bool = False, grammar=None,
                    grammar_repeat: bool = True, grammar_pattern: Optional[str] = None,
-                   grammar_ignore_case: bool = False) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
+                   grammar_ignore_case: bool = False, lm=None,
+                   lm_weight: Optional[float] = None) -> Tuple[Optional[List[Segment]], Optional[TranscriptionInfo]]:
+        if lm is not None:
+            # an n-gram language model for this call alone (see `language_model`): refused before any audio work
+            if keywords is not None or logit_bias is not None or grammar is not None or grammar_pattern is not None:
+                raise ValueError("lm and keywords / logit_bias / grammar in one call: a language model together with keyword boosting or a grammar is out of scope")
+            with self.language_model(lm, lm_weight):
+                return self.transcribe(audio, language, task, log_progress, beam_size, best_of, patience, length_penalty, repetition_penalty,
+                                       no_repeat_ngram_size, temperature, compression_ratio_threshold, log_prob_threshold,
+                                       no_speech_threshold, condition_on_previous_text, prompt_reset_on_temperature, initial_prompt, prefix,
+                                       suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp, word_timestamps,
+                                       prepend_punctuations, append_punctuations, multilingual, vad_filter, vad_parameters, max_new_tokens,
+                                       chunk_length, clip_timestamps, hallucination_silence_threshold, hotwords,
+                                       language_detection_threshold, language_detection_segments)
         if grammar_pattern is not None:
             # a regular expression for this call alone (see `grammar`): compiled before any audio work, so a refused pattern costs nothing
             if keywords is not None or logit_bias is not None:
