@@ -1177,6 +1177,7 @@ int32_t wlx_vad_debug_out(wlx_vad* v, const float* hs, int32_t T, float* probs, 
 #include "wlx_pattern.h"
 #include "wlx_pattern_items.h"
 #include "wlx_lm.h"
+#include "wlx_lm_items.h"
 #include "wlx_spk_long.h"
 
 #ifdef __cplusplus

@@ -34,8 +34,8 @@
  * wlx_lm_set: the slot points at model `lm` with weight `weight` (finite, > 0). A small descriptor of the slot at a fixed device
  * address names the model's arrays and the weight, and the kernel reads it from memory: captured step graphs serve any model and any
  * weight. ONE mode at a time and the last set call decides, as documented in wlx_grammar.h. A generate whose opts->ids.eot differs from
- * the model's is refused with WLX_ERR_ARG.
- * wlx_lm_clear: a slot in this mode decodes without the launch again — its step is the launch list of a slot that never had a model —
+ * the model's is refused with WLX_ERR_ARG. A model and a weight PER ITEM of a decode group is wlx_lm_set_items (wlx_lm_items.h).
+ * wlx_lm_clear: a slot in this mode (or in the per-item one) decodes without the launch again — its step is the launch list of a slot that never had a model —
  * and points at no model; a slot in another mode only stops pointing at one (wlx_bias_clear clears every mode, this one included). */
 #define WLX_LM_MAX_ORDER 5
 #define WLX_LM_MAX_STATES (1 << 20)

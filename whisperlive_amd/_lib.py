@@ -56,6 +56,8 @@ EXPORTS_PATTERN = ["wlx_pattern_vocab_set", "wlx_pattern_set", "wlx_pattern_clea
 EXPORTS_PATTERN_ITEMS = ["wlx_pattern_set_items", "wlx_pattern_select", "wlx_debug_pattern_apply_items"]
 # n-gram language-model fusion, declared in include/wlx_lm.h (which wlx.h includes)
 EXPORTS_LM = ["wlx_lm_create", "wlx_lm_destroy", "wlx_lm_set", "wlx_lm_clear", "wlx_debug_lm_apply"]
+# a model and a weight per item, declared in include/wlx_lm_items.h (which wlx.h includes)
+EXPORTS_LM_ITEMS = ["wlx_lm_set_items", "wlx_lm_select", "wlx_debug_lm_apply_items"]
 # the long form of the offline speaker clustering, declared in include/wlx_spk_long.h (which wlx.h includes)
 EXPORTS_SPK_LONG = ["wlx_spk_cluster_long", "wlx_spk_diarize_pcm_long", "wlx_spk_debug_ahc_long"]
 
@@ -175,6 +177,7 @@ PATTERN_SET_MAX_TABLES, PATTERN_SET_MAX_CELLS, PATTERN_SET_MAX_STATES = 64, 3932
 PATTERN_DEAD = 0xFFFF   # a transition into no state
 # wlx_lm.h WLX_LM_MAX_*: the caps of an n-gram language model (wlx_lm_create) and the models of one engine
 LM_MAX_ORDER, LM_MAX_STATES, LM_MAX_EDGES, LM_MAX_VOCAB, LM_MAX_MODELS = 5, 1 << 20, 1 << 22, 65536, 8
+LM_SET_MAX_ENTRIES = 64  # wlx_lm_items.h WLX_LM_SET_MAX_ENTRIES: (model, weight) entries of one pool (wlx_lm_set_items)
 DEBUG_GUARD = 64        # wlx.h WLX_DEBUG_GUARD: words a debug hook's output carries past what the kernel owns
 MT_MANY_MAX = 4096      # wlx.h WLX_MT_MANY_MAX: sources of one wlx_mt_translate_many call
 ERR_ARG = 1             # wlx_status WLX_ERR_ARG
@@ -354,8 +357,8 @@ def load() -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
     except OSError as e:  # e.g. libamdhip64 missing
         raise WlxError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS + EXPORTS_PATTERN + EXPORTS_PATTERN_ITEMS + EXPORTS_LM + EXPORTS_SPK_LONG
-               if not hasattr(lib, s)]
+    missing = [s for s in EXPORTS + EXPORTS_GRAMMAR + EXPORTS_GRAMMAR_ITEMS + EXPORTS_PATTERN + EXPORTS_PATTERN_ITEMS + EXPORTS_LM + EXPORTS_LM_ITEMS
+               + EXPORTS_SPK_LONG if not hasattr(lib, s)]
     if missing:
         raise WlxError(f"libwlx.so lacks symbols {missing}")
     i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p
@@ -541,6 +544,14 @@ def load() -> C.CDLL:
         lib.wlx_lm_clear.argtypes = [vp, i32]
         lib.wlx_debug_lm_apply.argtypes = [i32, i32, i32, i32, i32, i32] + table + [C.c_float, f32p, i32, i64, i32p, i32p, i32p, i32, i32p, i32p, i32p]
         for name in EXPORTS_LM:
+            getattr(lib, name).restype = i32
+    if EXPORTS_LM_ITEMS:            # (scripts/lm_items_time.py alone empties the list, to load a library of the parent commit beside this one)
+        table = [i32p, i32p, f32p, i32p, f32p, i32p, f32p, i32p]
+        lib.wlx_lm_set_items.argtypes = [vp, i32, i32, i32p, f32p]
+        lib.wlx_lm_select.argtypes = [vp, i32, i32, i32p]
+        lib.wlx_debug_lm_apply_items.argtypes = ([i32, i32, i32, i32, i32p, i32p, i32p] + table + [i32, i32p, f32p, f32p, i32, i32, i32, i32p, i64] +
+                                                 [i32p] * 8)
+        for name in EXPORTS_LM_ITEMS:
             getattr(lib, name).restype = i32
     if EXPORTS_SPK_LONG:            # (scripts/spk_long_time.py alone empties the list, to load a library of the parent commit beside this one)
         lib.wlx_spk_cluster_long.argtypes = lib.wlx_spk_cluster.argtypes

@@ -1,5 +1,7 @@
 // dec_lm.hip — n-gram language-model fusion: the one launch between the vocabulary projection and the token search of a decode step
-// whose slot points at a model (wlx_lm_set). A step of a slot without one does not launch it.
+// whose slot points at a model (wlx_lm_set). A step of a slot without one does not launch it. Two kernels share one body
+// (lm_fuse_row): dec_lm_kernel under the slot's one descriptor, dec_lm_items_kernel under the pool entry selected for the row's item
+// (wlx_lm_set_items / wlx_lm_select), described above it.
 //
 // The model is a backoff automaton over token ids, built on the host (whisperlive_amd/lm.py) and checked by lm_table.h: state 0 is the
 // empty context with the dense unigram arrays; state n > 0 carries its sorted explicit edges (token, log-probability, next state), a
@@ -81,23 +83,17 @@ __device__ __forceinline__ void lse_add8(float& m, float& s, const float (&x)[8]
     s = a; m = nm;
 }
 
-__global__ __launch_bounds__(NGLM_THREADS) void dec_lm_kernel(float* __restrict__ logits, const SearchParams* __restrict__ spp, SearchState st,
-                                                              LmFusion lm) {
-    if (*st.done) return;                       // scratch steps behind the end of the call
-    const int r = blockIdx.x;
-    const int R = spp->R, eot = spp->eot;
-    const long ldl = spp->ldl;
-    const int item = r / R, rb = r - item * R;
-    if (st.item_done[item]) return;
-    if (spp->sampling) { if (rb >= spp->num_hyp || st.row_done[r]) return; }
-    else if (rb >= spp->beam) return;
+// The fusion of ONE row, shared by the two kernels below: `r` the decoder row, `item` its item, `d` the RESOLVED descriptor (by value:
+// in SGPRs, every field uniform in the workgroup), `state` the slot's context states. The callers have returned for a finished call, a
+// finished item and a row outside the beam; every return in here depends on the row and the descriptor alone, so the workgroup is whole
+// at each barrier.
+__device__ __forceinline__ void lm_fuse_row(float* __restrict__ logits, const SearchState& st, const LmDesc d, int* __restrict__ state_of, const int r,
+                                            const int item, const int eot, const long ldl) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int p = st.pos[r], plen = st.plen[item], tok = st.token[r];
     if (p < 0 || p >= WLX_T_TEXT) return;
-    const LmDesc d = *lm.desc;
-    if (eot != d.eot || eot < 1 || eot >= NGLM_MAX_VOCAB) return;       // (generate refuses another eot: never indexes past the unigram arrays)
+    if (eot < 1 || eot >= NGLM_MAX_VOCAB) return;
     const bool raw = st.nsp_row[r] > 0;         // the row's RAW distribution defines no_speech_prob: its state is written, its logits stay
-    // (every return above depends on the row alone: the workgroup is whole at each barrier below)
     __shared__ __attribute__((aligned(16))) float s_sc[NGLM_CHUNK];
     __shared__ int s_bnd[NGLM_LEVELS][NGLM_MAX_CHUNKS + 1];     // level j's edges of chunk c are [s_bnd[j][c], s_bnd[j][c + 1])
     __shared__ float s_above[NGLM_LEVELS + 1];                  // the weights above level j; [nlev]: all of the chain
@@ -129,7 +125,10 @@ __global__ __launch_bounds__(NGLM_THREADS) void dec_lm_kernel(float* __restrict_
             }
         }
     }
-    // (and the unigram scores of chunk 0, which depend on nothing: one chunk ahead from here on)
+    // the descriptor's FIRST use, behind the requests for the row: in the per-item kernel its fetch depends on the selection, and up to
+    // here nothing has waited for it. (generate refuses another eot: never indexes past the unigram arrays. Uniform in the workgroup.)
+    if (eot != d.eot) return;
+    // (and the unigram scores of chunk 0, which depend on nothing else: one chunk ahead from here on)
     float4 un[NGLM_PIECES];
 #pragma unroll
     for (int q = 0; q < NGLM_PIECES; ++q) un[q] = *reinterpret_cast<const float4*>(d.unigram_logp + (q * NGLM_THREADS + tid) * 4);
@@ -137,7 +136,7 @@ __global__ __launch_bounds__(NGLM_THREADS) void dec_lm_kernel(float* __restrict_
     if (wave == 0) {
         int state = d.start;
         if (p >= plen && p >= 1) {              // a generated position: the parent's state, advanced by a text token
-            int ps = lm.state[(long)st.anc[(long)r * WLX_T_TEXT + p - 1] * WLX_T_TEXT + p - 1];
+            int ps = state_of[(long)st.anc[(long)r * WLX_T_TEXT + p - 1] * WLX_T_TEXT + p - 1];
             if (ps < 0 || ps >= d.n_states) ps = d.start;       // (a state another model left behind: never indexes past this one)
             state = ps;
             if ((unsigned)tok < (unsigned)eot) {
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(NGLM_THREADS) void dec_lm_kernel(float* __restrict_
                 if (state < 0 || state >= d.n_states) state = 0;
             }
         }
-        if (lane == 0) lm.state[(long)r * WLX_T_TEXT + p] = state;
+        if (lane == 0) state_of[(long)r * WLX_T_TEXT + p] = state;
         if (!raw && lane == 0) {
             int n = 0, s = state;
             float acc = 0.f;
@@ -263,8 +262,50 @@ __global__ __launch_bounds__(NGLM_THREADS) void dec_lm_kernel(float* __restrict_
     }
 }
 
+__global__ __launch_bounds__(NGLM_THREADS) void dec_lm_kernel(float* __restrict__ logits, const SearchParams* __restrict__ spp, SearchState st,
+                                                              LmFusion lm) {
+    if (*st.done) return;                       // scratch steps behind the end of the call
+    const int r = blockIdx.x;
+    const int R = spp->R, eot = spp->eot;
+    const long ldl = spp->ldl;
+    const int item = r / R, rb = r - item * R;
+    if (st.item_done[item]) return;
+    if (spp->sampling) { if (rb >= spp->num_hyp || st.row_done[r]) return; }
+    else if (rb >= spp->beam) return;
+    lm_fuse_row(logits, st, *lm.desc, lm.state, r, item, eot, ldl);
+}
+
+// The per-item form (wlx_lm_set_items / wlx_lm_select): the grid is (row of the item, item), so a workgroup finds its item
+// without a division, and the descriptor is entry sel[item] of the slot's pool. Both sit at fixed addresses and are read from memory:
+// one captured step graph serves any pool and any selection. A workgroup whose item has no entry (sel < 0) returns before it has asked
+// for one word of the row: such an item pays the dispatch of its empty workgroups and writes neither a state nor a logit.
+// The entry is fetched through the SCALAR cache: sel[item] and pool[sel] are uniform in the workgroup, so the 80 bytes land in SGPRs (two
+// s_load) and cost no VGPR — the kernel holds the whole row in registers, 115 VGPRs of the 128 that 1024 threads leave, and a descriptor
+// fetched by one lane and broadcast would need twenty readlanes or spill. The fetch depends on sel, which the exit needs anyway, and is
+// asked for here, in front of the call; lm_fuse_row first reads a field of it BEHIND its requests for the row (step 1), so the entry
+// arrives under the row's loads and wave 0's state walk starts where it starts in dec_lm_kernel: the entry is no new link in the chain.
+__global__ __launch_bounds__(NGLM_THREADS) void dec_lm_items_kernel(float* __restrict__ logits, const SearchParams* __restrict__ spp, SearchState st,
+                                                                    LmItems li) {
+    const int item = blockIdx.y, rb = blockIdx.x;
+    // everything the exits read is asked for at once (each word is there whatever the others hold), so the selection is no link of its
+    // own in front of them: one wait where dec_lm_kernel's exits, written one behind the other, wait four times
+    const int done = *st.done, e = li.sel[item], idone = st.item_done[item];
+    const int R = spp->R, eot = spp->eot, sampling = spp->sampling, width = sampling ? spp->num_hyp : spp->beam;
+    const long ldl = spp->ldl;
+    if (done) return;                           // scratch steps behind the end of the call
+    if (e < 0 || e >= NGLM_MAX_ENTRIES) return; // not fused (and never past the pool)
+    if (idone || rb >= R || rb >= width) return;
+    const int r = item * R + rb;
+    if (sampling && st.row_done[r]) return;
+    lm_fuse_row(logits, st, li.pool[e], li.state, r, item, eot, ldl);
+}
+
 void launch_dec_lm(float* logits, const SearchParams* sp_dev, int rows, const SearchState& st, const LmFusion& lm, hipStream_t s) {
     hipLaunchKernelGGL(dec_lm_kernel, dim3(rows), dim3(NGLM_THREADS), 0, s, logits, sp_dev, st, lm);
+}
+
+void launch_dec_lm_items(float* logits, const SearchParams* sp_dev, int items, int R, const SearchState& st, const LmItems& li, hipStream_t s) {
+    hipLaunchKernelGGL(dec_lm_items_kernel, dim3(R, items), dim3(NGLM_THREADS), 0, s, logits, sp_dev, st, li);
 }
 
 }  // namespace wlx

@@ -310,6 +310,16 @@ struct LmFusion {
 // one workgroup of 1024 threads per row, between the vocabulary projection and the search: the row's state from its parent's, then
 // l'(v) = l(v) + w s(v) - c over the text tokens and end-of-text; nothing else is written
 void launch_dec_lm(float* logits, const SearchParams* sp_dev, int rows, const SearchState& st, const LmFusion& lm, hipStream_t s);
+// A model and a weight per item (wlx_lm_set_items / wlx_lm_select): a pool of descriptors of the slot's own — entry e is
+// (the arrays of one of the engine's models, a weight) — and the selection the per-item modes share, both at fixed device addresses.
+struct LmItems {
+    const LmDesc* pool;         // [NGLM_MAX_ENTRIES]
+    const int* sel;             // [max_batch] the entry of each item, -1: the item is not fused
+    int* state;                 // LmFusion::state: the two modes share the array (a state out of range for the entry reads as its start)
+};
+// one workgroup of 1024 threads per (row of the item, item): dec_lm_kernel's fusion under the entry of the row's item; a workgroup of
+// an item without an entry returns before it loads anything of the row
+void launch_dec_lm_items(float* logits, const SearchParams* sp_dev, int items, int R, const SearchState& st, const LmItems& li, hipStream_t s);
 
 // softmax over ids [0, vlim) of row r, probability of token toks[r] -> out[r]   (text_token_probs of Whisper.align)
 void launch_token_prob_rows(const float* logits, long ldl, int vlim, int rows, const int* toks, float* out, hipStream_t s);

@@ -18,9 +18,9 @@ namespace wlx {
 // the launch of a slot's decode step between the vocabulary projection and the search: none, keyword boosting with one table or a table per
 // item, or a grammar (wlx_grammar_set: masks where the others add) or a grammar per item (wlx_grammar_set_items), or a regular-expression
 // grammar over the text's bytes (wlx_pattern_set) or one per item (wlx_pattern_set_items), or the fusion of an n-gram language model
-// (wlx_lm_set). One mode at a time: the last set call decides.
+// (wlx_lm_set) or of a model and a weight per item (wlx_lm_set_items). One mode at a time: the last set call decides.
 enum BiasMode : int { BIAS_NONE = 0, BIAS_ONE = 1, BIAS_ITEMS = 2, BIAS_GRAMMAR = 3, BIAS_GRAMMAR_ITEMS = 4, BIAS_PATTERN = 5, BIAS_PATTERN_ITEMS = 6,
-                      BIAS_LM = 7 };
+                      BIAS_LM = 7, BIAS_LM_ITEMS = 8 };
 
 // what a captured decode-step graph depends on (engine_decode.hip get_step_graph)
 struct StepGraphKey {
@@ -29,7 +29,8 @@ struct StepGraphKey {
     int bias;                   // BiasMode of the slot: the step launches dec_bias_kernel (one table: wlx_bias_set) or dec_bias_items_kernel (per item:
                                 // wlx_bias_set_items) or dec_grammar_kernel (wlx_grammar_set) or dec_grammar_items_kernel (per item:
                                 // wlx_grammar_set_items) or dec_pattern_kernel (wlx_pattern_set) or dec_pattern_items_kernel (per item:
-                                // wlx_pattern_set_items) or dec_lm_kernel (wlx_lm_set) in front of the search, or nothing; a graph
+                                // wlx_pattern_set_items) or dec_lm_kernel (wlx_lm_set) or dec_lm_items_kernel (per item:
+                                // wlx_lm_set_items) in front of the search, or nothing; a graph
                                 // captured for one mode is never replayed
                                 // for another
     bool operator<(const StepGraphKey& o) const {
@@ -134,6 +135,12 @@ struct Slot {
     // int32 states, allocated at the first wlx_lm_set and kept at those addresses. `nglm_id`: the engine's model the slot points at (-1:
     // none; wlx_lm_destroy reads it under the engine's mutex), `nglm_eot` that model's end-of-text id
     LmFusion nglm{}; LmDesc* d_nglm = nullptr; LmDesc* h_nglm = nullptr; std::atomic<int> nglm_id{-1}; int nglm_eot = -1;
+    // a model and a weight per item (wlx_lm_set_items / wlx_lm_select; dec_lm.hip dec_lm_items_kernel): the pool of descriptors and its
+    // pinned staging, allocated at the first wlx_lm_set_items and kept at those addresses; the states are nglm.state, the selection is
+    // the one the per-item modes share (d_sel). `nglm_pool_models`: bit i is set while an entry of the pool points at the engine's
+    // model i (wlx_lm_destroy reads it under the engine's mutex), `lpool_eot` the end-of-text id all entries share
+    LmItems nglm_items{}; LmDesc* d_lpool = nullptr; LmDesc* h_lpool = nullptr; int nglm_entries = 0, lpool_eot = -1;
+    std::atomic<unsigned> nglm_pool_models{0};
     unsigned* d_suppress = nullptr;
     int* d_lang_ids = nullptr; float* d_probs = nullptr; float* d_tokprob = nullptr;
     // pinned host staging

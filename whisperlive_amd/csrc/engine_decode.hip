@@ -343,7 +343,8 @@ static int graph_steps_for(const Slot* s, int rows) {
 // (wlx_grammar_set_items) dec_grammar_items_kernel, under the table selected for the row's item (wlx_grammar_select); with a
 // regular-expression grammar (wlx_pattern_set) dec_pattern_kernel (dec_pattern.hip), which walks every text token's bytes; with a pool of
 // them (wlx_pattern_set_items) dec_pattern_items_kernel, one workgroup per (item, tile) where the others take one per (row, tile); with an
-// n-gram language model (wlx_lm_set) dec_lm_kernel (dec_lm.hip), one workgroup per row, which rescores every text token.
+// n-gram language model (wlx_lm_set) dec_lm_kernel (dec_lm.hip), one workgroup per row, which rescores every text token; with a pool of
+// (model, weight) entries (wlx_lm_set_items) dec_lm_items_kernel, the same fusion under the entry selected for the row's item.
 void wlx::launch_bias(Slot* s, int rows, int R) {
     if (s->bias_mode == BIAS_ONE) launch_dec_bias(s->logits, s->d_sp, rows, s->st, s->bias, s->stream);
     else if (s->bias_mode == BIAS_ITEMS) launch_dec_bias_items(s->logits, s->d_sp, rows, s->st, s->bias_items, s->stream);
@@ -352,6 +353,7 @@ void wlx::launch_bias(Slot* s, int rows, int R) {
     else if (s->bias_mode == BIAS_PATTERN) launch_dec_pattern(s->logits, s->d_sp, rows, (int)s->ldl, s->st, s->pattern, s->stream);
     else if (s->bias_mode == BIAS_PATTERN_ITEMS) launch_dec_pattern_items(s->logits, s->d_sp, rows / R, (int)s->ldl, s->st, s->pattern_items, s->stream);
     else if (s->bias_mode == BIAS_LM) launch_dec_lm(s->logits, s->d_sp, rows, s->st, s->nglm, s->stream);
+    else if (s->bias_mode == BIAS_LM_ITEMS) launch_dec_lm_items(s->logits, s->d_sp, rows / R, R, s->st, s->nglm_items, s->stream);
 }
 
 static void launch_steps(Engine* e, Slot* s, int rows, int R, int groups, bool sampling, int nsteps) {
@@ -695,6 +697,10 @@ int wlx::generate_impl(Engine* e, Slot* s, int batch, const int32_t* prompts, co
         return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's patterns were compiled for %d (wlx_pattern_set_items)", o->ids.eot, s->ppool_eot);
     if (s->bias_mode == BIAS_LM && o->ids.eot != s->nglm_eot)
         return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's language model was built for %d (wlx_lm_create)", o->ids.eot, s->nglm_eot);
+    if (s->bias_mode == BIAS_LM_ITEMS && batch > s->sel_n)
+        return set_error(WLX_ERR_STATE, "generate: %d items, but the language-model selection covers %d (wlx_lm_select)", batch, s->sel_n);
+    if (s->bias_mode == BIAS_LM_ITEMS && o->ids.eot != s->lpool_eot)
+        return set_error(WLX_ERR_ARG, "generate: end-of-text is %d, the slot's language models were built for %d (wlx_lm_set_items)", o->ids.eot, s->lpool_eot);
     static const bool gen_trace = getenv("WLX_GEN_TRACE") != nullptr;
     double tg[2] = {0.0, 0.0};                                  // WLX_GEN_TRACE: host time in graph launch calls / in the polling waits
     const double tg0 = now_us();
@@ -826,6 +832,7 @@ extern "C" int32_t wlx_bias_clear(wlx_engine* e, int32_t slot) {
     CKR(slot_acquire(e, slot, sg_));
     sg_.s->bias_mode = BIAS_NONE;
     sg_.s->nglm_id.store(-1);                    // (the slot points at no language model any more: wlx_lm_destroy)
+    sg_.s->nglm_pool_models.store(0u);
     return WLX_OK;
 }
 
@@ -1170,12 +1177,24 @@ extern "C" int32_t wlx_lm_destroy(wlx_engine* e, int32_t lm) {
     std::lock_guard<std::mutex> lk(e->mu);
     if (lm < 0 || lm >= NGLM_MAX_MODELS || !e->models[lm].live) return set_error(WLX_ERR_ARG, "lm: no model %d", lm);
     for (const Slot* s : e->slots)
-        if (s && s->nglm_id.load() == lm) return set_error(WLX_ERR_STATE, "lm: a slot points at model %d (wlx_lm_clear)", lm);
+        if (s && (s->nglm_id.load() == lm || (s->nglm_pool_models.load() >> lm & 1u)))
+            return set_error(WLX_ERR_STATE, "lm: a slot points at model %d (wlx_lm_clear)", lm);
     CK(hipSetDevice(e->device));
     Engine::LmModel& m = e->models[lm];
     for (void* p : m.allocs) (void)hipFree(p);  // (hipFree waits for the device: no launch still reads the arrays)
     m.allocs.clear();
     m.live = false;
+    return WLX_OK;
+}
+
+static int nglm_alloc(Slot* s) {                // the descriptor, its pinned staging and the states: shared by the single and the per-item mode
+    if (s->d_nglm) return WLX_OK;
+    LmDesc *dd = nullptr, *hd = nullptr;
+    int* state = nullptr;
+    CKR(dalloc(s->allocs, &dd, (size_t)1, true));
+    CKR(halloc(s->host_allocs, &hd, (size_t)1));
+    CKR(dalloc(s->allocs, &state, (size_t)std::max(s->cache_rows, s->rows_cap) * WLX_T_TEXT, true));
+    s->d_nglm = dd; s->h_nglm = hd; s->nglm = LmFusion{dd, state};
     return WLX_OK;
 }
 
@@ -1191,17 +1210,11 @@ extern "C" int32_t wlx_lm_set(wlx_engine* e, int32_t slot, int32_t lm, float wei
         if (lm < 0 || lm >= NGLM_MAX_MODELS || !e->models[lm].live) return set_error(WLX_ERR_ARG, "lm: no model %d", lm);
         desc = e->models[lm].desc;
         s->nglm_id.store(lm);                   // (under the engine's mutex: wlx_lm_destroy sees the slot from here on)
+        s->nglm_pool_models.store(0u);          // (a pool of the per-item mode is not applied any more, and is rewritten before it is again)
     }
     desc.w = weight;
     CK(hipSetDevice(e->device));
-    if (!s->d_nglm) {
-        LmDesc *dd = nullptr, *hd = nullptr;
-        int* state = nullptr;
-        CKR(dalloc(s->allocs, &dd, (size_t)1, true));
-        CKR(halloc(s->host_allocs, &hd, (size_t)1));
-        CKR(dalloc(s->allocs, &state, (size_t)std::max(s->cache_rows, s->rows_cap) * WLX_T_TEXT, true));
-        s->d_nglm = dd; s->h_nglm = hd; s->nglm = LmFusion{dd, state};
-    }
+    CKR(nglm_alloc(s));
     // the staging may still feed the copy of the previous descriptor: wait for the stream, then rewrite it
     CK(hipStreamSynchronize(s->stream));
     *s->h_nglm = desc;
@@ -1214,9 +1227,72 @@ extern "C" int32_t wlx_lm_set(wlx_engine* e, int32_t slot, int32_t lm, float wei
 extern "C" int32_t wlx_lm_clear(wlx_engine* e, int32_t slot) {
     SlotGuard sg_;
     CKR(slot_acquire(e, slot, sg_));
-    if (sg_.s->bias_mode == BIAS_LM) sg_.s->bias_mode = BIAS_NONE;      // (a table of another mode installed since stays)
+    if (sg_.s->bias_mode == BIAS_LM || sg_.s->bias_mode == BIAS_LM_ITEMS) sg_.s->bias_mode = BIAS_NONE;     // (a table of another mode installed since stays)
     sg_.s->nglm_id.store(-1);
+    sg_.s->nglm_pool_models.store(0u);
     return WLX_OK;
+}
+
+// ---- a model and a weight per item (include/wlx_lm_items.h; dec_lm.hip dec_lm_items_kernel). The pool of descriptors and its pinned staging
+// are allocated at the first call and stay where they are, like the selection (select_alloc): a step graph captured in this mode replays
+// with every later pool and selection. An entry only points at a model of the engine: two entries may share one at different weights.
+extern "C" int32_t wlx_lm_set_items(wlx_engine* e, int32_t slot, int32_t n_entries, const int32_t* models, const float* weights) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    // a refused call leaves whatever is installed whole (and allocates nothing): checked into a host copy first
+    if (!models || !weights) return set_error(WLX_ERR_ARG, "null argument");
+    if (n_entries < 1 || n_entries > NGLM_MAX_ENTRIES) return set_error(WLX_ERR_ARG, "lm items: %d entries outside 1..%d", n_entries, NGLM_MAX_ENTRIES);
+    for (int i = 0; i < n_entries; ++i)
+        if (!std::isfinite(weights[i]) || !(weights[i] > 0.f)) return set_error(WLX_ERR_ARG, "lm items: the weight of entry %d must be finite and above 0", i);
+    LmDesc pool[NGLM_MAX_ENTRIES];
+    unsigned used = 0u;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        for (int i = 0; i < n_entries; ++i) {
+            const int m = models[i];
+            if (m < 0 || m >= NGLM_MAX_MODELS || !e->models[m].live) return set_error(WLX_ERR_ARG, "lm items: entry %d names model %d, which does not exist", i, m);
+            pool[i] = e->models[m].desc;
+            pool[i].w = weights[i];
+            if (pool[i].eot != pool[0].eot)
+                return set_error(WLX_ERR_ARG, "lm items: entry %d was built for end-of-text %d, entry 0 for %d (one generate call has one)", i, pool[i].eot, pool[0].eot);
+            used |= 1u << m;
+        }
+        s->nglm_pool_models.store(used);        // (under the engine's mutex: wlx_lm_destroy sees the slot from here on)
+        s->nglm_id.store(-1);
+    }
+    CK(hipSetDevice(e->device));
+    CKR(nglm_alloc(s));
+    CKR(select_alloc(s));
+    if (!s->d_lpool) {
+        LmDesc *dp = nullptr, *hp = nullptr;
+        CKR(dalloc(s->allocs, &dp, (size_t)NGLM_MAX_ENTRIES, true));
+        CKR(halloc(s->host_allocs, &hp, (size_t)NGLM_MAX_ENTRIES));
+        s->d_lpool = dp; s->h_lpool = hp;
+        s->nglm_items = LmItems{dp, s->d_sel, s->nglm.state};
+    }
+    CK(hipStreamSynchronize(s->stream));         // the pool's staging may still feed the copy of the previous set
+    memcpy(s->h_lpool, pool, sizeof(LmDesc) * (size_t)n_entries);
+    CK(hipMemcpyAsync(s->d_lpool, s->h_lpool, sizeof(LmDesc) * (size_t)n_entries, hipMemcpyHostToDevice, s->stream));   // (the used part only)
+    s->nglm_entries = n_entries;
+    s->lpool_eot = pool[0].eot;
+    CKR(bias_select_upload(s, s->B, nullptr));   // every item deselected: an entry index of an earlier pool never reaches this one
+    s->bias_mode = BIAS_LM_ITEMS;
+    return WLX_OK;
+}
+
+extern "C" int32_t wlx_lm_select(wlx_engine* e, int32_t slot, int32_t batch, const int32_t* sel) {
+    SlotGuard sg_;
+    CKR(slot_acquire(e, slot, sg_));
+    Slot* s = sg_.s;
+    if (s->bias_mode != BIAS_LM_ITEMS) return set_error(WLX_ERR_STATE, "lm select: no pool installed (wlx_lm_set_items)");
+    if (!sel) return set_error(WLX_ERR_ARG, "null argument");
+    if (batch < 1 || batch > s->B) return set_error(WLX_ERR_ARG, "lm select: %d items outside 1..%d", batch, s->B);
+    for (int b = 0; b < batch; ++b)
+        if (sel[b] < -1 || sel[b] >= s->nglm_entries)
+            return set_error(WLX_ERR_ARG, "lm select: item %d names entry %d outside -1..%d", b, sel[b], s->nglm_entries - 1);
+    CK(hipSetDevice(e->device));
+    return bias_select_upload(s, batch, sel);
 }
 
 extern "C" int32_t wlx_detect_language(wlx_engine* e, int32_t slot, int32_t batch, int32_t sot, const int32_t* lang_ids,

@@ -14,6 +14,7 @@
 //   wlx_debug_pattern_apply      launch_dec_pattern (dec_pattern.hip)
 //   wlx_debug_pattern_apply_items launch_dec_pattern_items (dec_pattern.hip)
 //   wlx_debug_lm_apply           launch_dec_lm (dec_lm.hip)
+//   wlx_debug_lm_apply_items     launch_dec_lm_items (dec_lm.hip)
 //   wlx_debug_token_prob, _token_prob_rows, _lang_probs   launch_token_prob / _token_prob_rows / launch_lang_probs (search.hip)
 //   wlx_debug_dec_embed          launch_dec_embed (decoder.hip)
 //   wlx_debug_prep_windows       launch_prep_windows (logmel.hip)
@@ -873,6 +874,121 @@ extern "C" int32_t wlx_debug_lm_apply(int32_t device, int32_t vocab, int32_t eot
     SearchState st{};
     st.done = dzero; st.item_done = dzero + 1; st.row_done = dzero + 4; st.plen = dplen; st.token = dtok; st.pos = dpos; st.anc = danc; st.nsp_row = dnsp;
     launch_dec_lm(dl, dsp, rows, st, LmFusion{ddesc, dstate}, S.st);
+    CKR(S.download(logits, dl, words));
+    CKR(S.download(state.data(), dstate, state.size()));
+    CKR(S.finish());
+    for (int r = 0; r < rows; ++r) state_out[r] = state[(size_t)r * WLX_T_TEXT + pos[r]];
+    return WLX_OK;
+}
+
+// wlx_debug_lm_apply_items: launch_dec_lm_items (dec_lm.hip) on a search state built here for `items` items of R rows each, under a pool of
+// (model, weight) entries over `n_models` tables
+extern "C" int32_t wlx_debug_lm_apply_items(int32_t device, int32_t vocab, int32_t eot, int32_t n_models, const int32_t* order, const int32_t* n_states,
+                                            const int32_t* start_state, const int32_t* edge_off, const int32_t* backoff_state,
+                                            const float* backoff_weight, const int32_t* edge_tok, const float* edge_logp, const int32_t* edge_next,
+                                            const float* unigram_logp, const int32_t* unigram_next, int32_t n_entries, const int32_t* entry_model,
+                                            const float* entry_weight, float* logits, int32_t items, int32_t R, int32_t sampling, const int32_t* sel,
+                                            int64_t ldl, const int32_t* tokens, const int32_t* pos, const int32_t* parent, const int32_t* plen,
+                                            const int32_t* nsp_row, const int32_t* row_done, const int32_t* prev_state, int32_t* state_out) {
+    if (!order || !n_states || !start_state || !edge_off || !backoff_state || !backoff_weight || !edge_tok || !edge_logp || !edge_next || !unigram_logp ||
+        !unigram_next || !entry_model || !entry_weight || !logits || !sel || !tokens || !pos || !parent || !plen || !nsp_row || !row_done || !prev_state ||
+        !state_out)
+        return set_error(WLX_ERR_ARG, "null argument");
+    if (vocab < 1 || vocab > (1 << 20) || ldl < vocab || ldl > (1 << 20)) return set_error(WLX_ERR_ARG, "vocab %d / ldl %lld", vocab, (long long)ldl);
+    if (items < 1 || items > 64 || R < 1 || R > 16 || (long)items * R > WLX_MAX_DEC_ROWS)
+        return set_error(WLX_ERR_ARG, "%d items of %d rows: items in 1..64, rows per item in 1..16, at most %d rows", items, R, WLX_MAX_DEC_ROWS);
+    if (n_models < 1 || n_models > NGLM_MAX_MODELS) return set_error(WLX_ERR_ARG, "%d models outside 1..%d", n_models, NGLM_MAX_MODELS);
+    if (n_entries < 1 || n_entries > NGLM_MAX_ENTRIES) return set_error(WLX_ERR_ARG, "%d entries outside 1..%d", n_entries, NGLM_MAX_ENTRIES);
+    const int rows = items * R;
+    char why[240];
+    // the tables lie back to back: model m's states start at s0[m] (its offsets at s0[m] + m), its edges at e0[m]
+    std::vector<size_t> s0((size_t)n_models + 1, 0), e0((size_t)n_models + 1, 0);
+    for (int m = 0; m < n_models; ++m) {
+        if (n_states[m] < 1 || n_states[m] > NGLM_MAX_STATES) return set_error(WLX_ERR_ARG, "model %d: %d states outside 1..%d", m, n_states[m], NGLM_MAX_STATES);
+        if (!lm_table_check(vocab, eot, order[m], n_states[m], start_state[m], edge_off + s0[m] + m, backoff_state + s0[m], backoff_weight + s0[m],
+                            edge_tok + e0[m], edge_logp + e0[m], edge_next + e0[m], unigram_logp + (size_t)m * vocab, unigram_next + (size_t)m * vocab,
+                            why, sizeof(why)))
+            return set_error(WLX_ERR_ARG, "model %d: %s", m, why);
+        s0[m + 1] = s0[m] + (size_t)n_states[m];
+        e0[m + 1] = e0[m] + (size_t)edge_off[s0[m] + m + n_states[m]];
+    }
+    for (int i = 0; i < n_entries; ++i) {
+        if (entry_model[i] < 0 || entry_model[i] >= n_models) return set_error(WLX_ERR_ARG, "entry %d names model %d outside 0..%d", i, entry_model[i], n_models - 1);
+        if (!std::isfinite(entry_weight[i]) || !(entry_weight[i] > 0.f)) return set_error(WLX_ERR_ARG, "lm: the weight of entry %d must be finite and above 0", i);
+    }
+    for (int b = 0; b < items; ++b) {
+        if (sel[b] < -1 || sel[b] >= n_entries) return set_error(WLX_ERR_ARG, "item %d names entry %d outside -1..%d", b, sel[b], n_entries - 1);
+        if (plen[b] < 1 || plen[b] > WLX_T_TEXT) return set_error(WLX_ERR_ARG, "item %d: plen %d outside 1..%d", b, plen[b], WLX_T_TEXT);
+    }
+    // (declared before the scope: the copies below read them until the scope's last wait)
+    std::vector<float> uni((size_t)n_models * NGLM_MAX_VOCAB, 0.f), bw(backoff_weight, backoff_weight + s0[n_models]);
+    std::vector<int> unext((size_t)n_models * vocab, 0), boff(backoff_state, backoff_state + s0[n_models]);
+    std::vector<int> flags((size_t)1 + items + rows, 0), state((size_t)rows * WLX_T_TEXT, 0);
+    std::vector<short> anc((size_t)rows * WLX_T_TEXT, 0);
+    std::vector<LmDesc> pool((size_t)n_entries);
+    SearchParams sp{};
+    for (int m = 0; m < n_models; ++m) {
+        for (int v = 0; v <= eot; ++v) {
+            uni[(size_t)m * NGLM_MAX_VOCAB + v] = unigram_logp[(size_t)m * vocab + v];
+            unext[(size_t)m * vocab + v] = unigram_next[(size_t)m * vocab + v];
+        }
+        boff[s0[m]] = 0; bw[s0[m]] = 0.f;
+    }
+    for (int r = 0; r < rows; ++r) {
+        if (tokens[r] < 0 || tokens[r] >= vocab) return set_error(WLX_ERR_ARG, "row %d: token %d outside the vocabulary (%d)", r, tokens[r], vocab);
+        if (pos[r] < 0 || pos[r] >= WLX_T_TEXT) return set_error(WLX_ERR_ARG, "row %d: position %d outside 0..%d", r, pos[r], WLX_T_TEXT - 1);
+        if (parent[r] < 0 || parent[r] >= rows) return set_error(WLX_ERR_ARG, "row %d: parent %d outside 0..%d", r, parent[r], rows - 1);
+        if (prev_state[r] < 0) return set_error(WLX_ERR_ARG, "row %d: state %d is negative", r, prev_state[r]);
+        if (pos[r] >= 1) {
+            anc[(size_t)r * WLX_T_TEXT + pos[r] - 1] = (short)parent[r];
+            state[(size_t)parent[r] * WLX_T_TEXT + pos[r] - 1] = prev_state[r];
+        }
+        anc[(size_t)r * WLX_T_TEXT + pos[r]] = (short)r;
+        flags[(size_t)1 + items + r] = row_done[r] != 0;
+    }
+    // the launch writes row r's state at pos[r]: no row may read that word as its parent's
+    for (int q = 0; q < rows; ++q)
+        if (pos[q] >= plen[q / R] && pos[q] >= 1 && pos[parent[q]] == pos[q] - 1)
+            return set_error(WLX_ERR_ARG, "row %d reads the state row %d writes in this launch (position %d)", q, parent[q], pos[q] - 1);
+    // (the word a row writes starts as the caller's state_out: a row the launch leaves alone hands it back)
+    for (int r = 0; r < rows; ++r) state[(size_t)r * WLX_T_TEXT + pos[r]] = state_out[r];
+    sp.V = vocab; sp.ldl = ldl; sp.items = items; sp.R = R; sp.rows = rows; sp.sampling = sampling != 0; sp.beam = R; sp.num_hyp = sampling ? R : 1; sp.eot = eot;
+    const size_t words = (size_t)rows * ldl + WLX_DEBUG_GUARD;
+    HookScope S;
+    CKR(S.begin(device));
+    int *doff = nullptr, *dboff = nullptr, *detok = nullptr, *dnext = nullptr, *dunext = nullptr, *dstate = nullptr;
+    int *dflags = nullptr, *dplen = nullptr, *dsel = nullptr, *dtok = nullptr, *dpos = nullptr, *dnsp = nullptr;
+    float *dbw = nullptr, *dlogp = nullptr, *duni = nullptr, *dl = nullptr;
+    short* danc = nullptr;
+    SearchParams* dsp = nullptr;
+    LmDesc* dpool = nullptr;
+    CKR(S.upload(&doff, edge_off, s0[n_models] + n_models));
+    CKR(S.upload(&dboff, boff.data(), boff.size()));
+    CKR(S.upload(&dbw, bw.data(), bw.size()));
+    CKR(S.upload(&detok, edge_tok, e0[n_models]));
+    CKR(S.upload(&dlogp, edge_logp, e0[n_models]));
+    CKR(S.upload(&dnext, edge_next, e0[n_models]));
+    CKR(S.upload(&duni, uni.data(), uni.size()));
+    CKR(S.upload(&dunext, unext.data(), unext.size()));
+    for (int i = 0; i < n_entries; ++i) {
+        const int m = entry_model[i];
+        pool[i] = LmDesc{doff + s0[m] + m, dboff + s0[m], dbw + s0[m], detok + e0[m], dlogp + e0[m], dnext + e0[m], duni + (size_t)m * NGLM_MAX_VOCAB,
+                         dunext + (size_t)m * vocab, entry_weight[i], eot, start_state[m], n_states[m]};
+    }
+    CKR(S.upload(&dpool, pool.data(), pool.size()));
+    CKR(S.upload(&dflags, flags.data(), flags.size()));
+    CKR(S.upload(&dplen, plen, (size_t)items));
+    CKR(S.upload(&dsel, sel, (size_t)items));
+    CKR(S.upload(&dtok, tokens, (size_t)rows));
+    CKR(S.upload(&dpos, pos, (size_t)rows));
+    CKR(S.upload(&dnsp, nsp_row, (size_t)rows));
+    CKR(S.upload(&danc, anc.data(), anc.size()));
+    CKR(S.upload(&dstate, state.data(), state.size()));
+    CKR(S.upload(&dl, logits, words));
+    CKR(S.upload(&dsp, &sp, (size_t)1));
+    SearchState st{};
+    st.done = dflags; st.item_done = dflags + 1; st.row_done = dflags + 1 + items; st.plen = dplen; st.token = dtok; st.pos = dpos; st.anc = danc; st.nsp_row = dnsp;
+    launch_dec_lm_items(dl, dsp, items, R, st, LmItems{dpool, dsel, dstate}, S.st);
     CKR(S.download(logits, dl, words));
     CKR(S.download(state.data(), dstate, state.size()));
     CKR(S.finish());

@@ -14,6 +14,7 @@ constexpr int NGLM_MAX_STATES = 1 << 20;        // WLX_LM_MAX_STATES
 constexpr int NGLM_MAX_EDGES = 1 << 22;         // WLX_LM_MAX_EDGES
 constexpr int NGLM_MAX_VOCAB = 65536;           // WLX_LM_MAX_VOCAB: a row's fused values stay in the registers of one workgroup
 constexpr int NGLM_MAX_MODELS = 8;              // WLX_LM_MAX_MODELS
+constexpr int NGLM_MAX_ENTRIES = 64;            // include/wlx_lm_items.h WLX_LM_SET_MAX_ENTRIES: (model, weight) entries of a slot's pool
 
 // the format of include/wlx_lm.h, violation by violation: true, or false with the reason in `msg`. Reads nothing past what the counts
 // checked so far allow.

@@ -769,6 +769,23 @@ class Slot:
         check(self.lib.wlx_lm_clear(self.engine._h, self.sid))
         self._lm = None
 
+    def set_lms(self, lm_set) -> None:
+        """Install an lm.LmSet on the slot (wlx_lm_set_items): the slot decodes in per-item fusion mode, every item deselected (not
+        fused) until `select_lms`. The set's models go to the engine once each (HipWhisperEngine.create_lm); an entry only points at
+        one. WlxError (ERR_ARG) for a set the library refuses; whatever is installed stays."""
+        if len(lm_set) < 1:
+            raise ValueError("an empty LmSet installs nothing: clear_lm")
+        handles = [self.engine.create_lm(m) for m in lm_set.models]
+        models = np.ascontiguousarray([handles[m] for m, _ in lm_set.entries], dtype=np.int32)
+        weights = np.ascontiguousarray([w for _, w in lm_set.entries], dtype=np.float32)
+        check(self.lib.wlx_lm_set_items(self.engine._h, self.sid, len(lm_set), _i32p(models), _f32p(weights)))
+        self._lm, self._lm_set_version, self._grammar, self._bias_table, self._pattern = lm_set, lm_set.version, None, None, None
+
+    def select_lms(self, indices: Sequence[int]) -> None:
+        """indices[b]: the entry (an index into the installed set, -1: none) of item b of the following generate calls (wlx_lm_select)"""
+        sel = np.ascontiguousarray(list(indices), dtype=np.int32)
+        check(self.lib.wlx_lm_select(self.engine._h, self.sid, sel.size, _i32p(sel)))
+
     def align(self, tokens: Sequence[int], n_sot: int, num_frames: int, heads: Sequence[Tuple[int, int]], eot: int,
               median_filter_width: int = 7, item: int = 0):
         """ctranslate2 Whisper.align for one encoded item: tokens = start_sequence + [no_timestamps] + text + [eot].

@@ -305,3 +305,106 @@ def install(slot, value: Optional[Tuple[NgramLM, float]]) -> None:
         slot.set_lm(value[0], value[1])
         slot._bias_table = slot._grammar = slot._pattern = None
     slot._lm = value
+
+
+# ---- a model and a weight PER ITEM (include/wlx_lm_items.h wlx_lm_set_items / wlx_lm_select)
+class LmSet:
+    """Up to 64 (model, weight) entries: the pool of wlx_lm_set_items. `add` returns the entry's index, storing a pair that is already
+    there (the same model object at the same weight) once; the models themselves are stored once each (`models`, at most 8: the engine
+    holds that many), so one model at two weights is two entries over one model. ValueError names the limit a new entry would pass and
+    leaves the set as it was. `version` moves with every stored entry: a slot uploads a set again only when it has grown
+    (install_items)."""
+
+    def __init__(self, entries: Iterable[Tuple[NgramLM, float]] = ()):
+        self.models: list = []
+        self.entries: list = []                 # (index into `models`, weight)
+        self._index: Dict[Tuple[int, float], int] = {}
+        self.version = 0
+        for m, w in entries:
+            self.add(m, w)
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    def _model(self, lm: NgramLM) -> Optional[int]:
+        return next((i for i, m in enumerate(self.models) if m is lm), None)
+
+    def _refusal(self, lm, weight) -> Optional[str]:
+        if not isinstance(lm, NgramLM):
+            return "an LmSet holds NgramLM models (NgramLM.from_arpa, NgramLM.from_corpus)"
+        if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not (math.isfinite(weight) and weight > 0):
+            return f"lm: the weight {weight} must be finite and above 0"
+        if self.models and (lm.eot, lm.vocab) != (self.models[0].eot, self.models[0].vocab):
+            return (f"lm: a model for end-of-text {lm.eot} in a vocabulary of {lm.vocab} next to one for {self.models[0].eot} in "
+                    f"{self.models[0].vocab}: the models of one set serve one vocabulary")
+        if len(self.entries) + 1 > _lib.LM_SET_MAX_ENTRIES:
+            return f"the set would hold {len(self.entries) + 1} entries (at most {_lib.LM_SET_MAX_ENTRIES} entries in one set)"
+        if self._model(lm) is None and len(self.models) + 1 > _lib.LM_MAX_MODELS:
+            return f"the set would hold {len(self.models) + 1} models (at most {_lib.LM_MAX_MODELS} models in one set)"
+        return None
+
+    def index(self, lm: NgramLM, weight: float) -> Optional[int]:
+        m = self._model(lm)
+        return None if m is None else self._index.get((m, float(weight)))
+
+    def fits(self, lm: NgramLM, weight: float) -> bool:
+        """`add(lm, weight)` would succeed (an entry already stored always fits)"""
+        return self._refusal(lm, weight) is None or (isinstance(lm, NgramLM) and self.index(lm, weight) is not None)
+
+    def add(self, lm: NgramLM, weight: float = DEFAULT_WEIGHT) -> int:
+        if isinstance(lm, NgramLM) and isinstance(weight, (int, float)) and self.index(lm, weight) is not None:
+            return self.index(lm, weight)
+        why = self._refusal(lm, weight)
+        if why:
+            raise ValueError(why)
+        m = self._model(lm)
+        if m is None:
+            self.models.append(lm)
+            m = len(self.models) - 1
+        self._index[(m, float(weight))] = len(self.entries)
+        self.entries.append((m, float(weight)))
+        self.version += 1
+        return len(self.entries) - 1
+
+
+def current_items() -> Optional["item_scope"]:
+    return getattr(_tls, "items", None)
+
+
+class item_scope:
+    """context manager: `values[i]` — an (NgramLM, weight) pair, or None: that item is not fused — is the model of prompt i of every
+    generate call the calling thread makes inside the block; scopes nest, other threads are untouched. `lm_set`: the set the pairs go
+    into (a job passes one set for all its decode groups, so a slot uploads it once); without one the scope owns a set of its own."""
+
+    def __init__(self, values: Sequence[Optional[Tuple[NgramLM, float]]], lm_set: Optional[LmSet] = None):
+        self.values = list(values)
+        self.lm_set = lm_set if lm_set is not None else LmSet()
+
+    def __enter__(self):
+        self._prev = current_items()
+        _tls.items = self
+        return self
+
+    def __exit__(self, *exc):
+        _tls.items = self._prev
+        return False
+
+
+def install_items(slot, values: Sequence[Optional[Tuple[NgramLM, float]]], lm_set: LmSet) -> list:
+    """Bring `slot` to the per-item route for a generate call over `values` (one per prompt, None: not fused): every pair is stored in
+    `lm_set` (ValueError names a limit), the slot uploads the set unless it holds it already, and the entry index of every prompt is
+    returned (-1: none) for Slot.select_lms per decode group. A call none of whose prompts has a model keeps a slot that holds THIS set
+    in per-item mode with every item deselected (the kernel then touches nothing), and clears any other slot. A slot that cannot take a
+    set (no `set_lms`) with one asked for is an error, never a silent unfused decode."""
+    idx = [-1 if v is None else lm_set.add(v[0], v[1]) for v in values]
+    if getattr(slot, "_lm", None) is lm_set and getattr(slot, "_lm_set_version", None) == lm_set.version:
+        return idx
+    if all(i < 0 for i in idx):
+        if getattr(slot, "_lm", None) is not None:
+            install(slot, None)
+        return idx
+    if not hasattr(slot, "set_lms"):
+        raise RuntimeError("a language model per item asked for, but this slot has no set_lms")
+    slot.set_lms(lm_set)
+    slot._lm, slot._lm_set_version, slot._bias_table, slot._grammar, slot._pattern = lm_set, lm_set.version, None, None, None
+    return idx

@@ -335,6 +335,49 @@ def fit_patterns(wave: List[int], patterns: list):
     return wave, (pset if len(pset) else None)
 
 
+def per_file_lms(model, lms, weights, n_files: int) -> list:
+    """the job's `lms` / `lm_weights` -> per file an (lm.NgramLM, weight) pair, None (not fused) or the ValueError the entry was refused
+    with (no NgramLM, a model built for another end-of-text id or vocabulary, a weight that is not finite and above 0). One entry per
+    file, each None or an NgramLM; the weights one number for all files or one per file (None: lm.DEFAULT_WEIGHT)."""
+    if not isinstance(lms, (list, tuple)) or len(lms) != n_files:
+        raise ValueError(f"lms: a list with one entry per file ({n_files}), each None or an NgramLM; one model for all files is lm=")
+    if isinstance(weights, (list, tuple)):
+        if len(weights) != n_files:
+            raise ValueError(f"lm_weights: a list of {len(weights)} entries for {n_files} files (one entry per file, or one value for all)")
+        weights = list(weights)
+    else:
+        weights = [weights] * n_files
+    if any(m is not None for m in lms) and not hasattr(model, "language_model"):
+        raise ValueError("lms: this transcriber takes no language model")
+    out = []
+    for m, w in zip(lms, weights):
+        if m is None:
+            out.append(None)
+            continue
+        try:
+            out.append(model.language_model(m, w).value)    # (its checks: an NgramLM of this model's end-of-text, a weight above 0)
+        except TypeError:
+            out.append(ValueError(f"lm: the weight {w!r} must be finite and above 0"))
+        except ValueError as e:
+            out.append(e)
+    return out
+
+
+def fit_lms(wave: List[int], lms: list):
+    """the longest head of `wave` whose distinct (model, weight) pairs fit one lm.LmSet (at least one file: a single pair always fits),
+    and that set (None: no file of it has a model)"""
+    lset = _lm.LmSet()
+    for k, i in enumerate(wave):
+        v = lms[i]
+        if v is None or isinstance(v, Exception):
+            continue
+        if k and not lset.fits(*v):
+            wave = wave[:k]
+            break
+        lset.add(*v)
+    return wave, (lset if len(lset) else None)
+
+
 def per_file_diarizers(pipe, diarize, max_speakers, n_files: int) -> List[tuple]:
     """the `diarize` / `max_speakers` arguments -> one (FileDiarizer or None, cap or None) per file. `diarize`: False | True |
     FileDiarizer, or a list with one of those per file; True is the pipeline's `file_diarizer` (made once from the configured speaker
@@ -396,6 +439,8 @@ class _File:
         self.grammar_set = None
         self.pattern = None                 # the file's pattern (pattern.Pattern) and the set of its wave's patterns
         self.pattern_set = None
+        self.lm = None                      # the file's (lm.NgramLM, weight) and the set of its wave's pairs
+        self.lm_set = None
         self.last_speech = 0.0
 
 
@@ -418,7 +463,11 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
     or one per file; every decode group selects the table of each chunk's file (wlx_pattern_select). An expression the
     compiler refuses, or one with a state the job's suppress list empties, costs only its file. Both pattern arguments in one job, or
     a pattern together with keyword boosting or with a phrase list, is out of scope: each a ValueError.
-    Each job leaves `pipe.many_timing` = {"front_s": seconds its waves spent before their first decode (puts, gate, language),
+    lms=[lm_a, None, lm_b] (with lm_weights: one number for all files or one per file, None: lm.DEFAULT_WEIGHT): an n-gram language model
+    PER FILE (None: not fused); every decode group selects the (model, weight) entry of each chunk's file (wlx_lm_select; DESIGN.md
+    §34). A refused entry costs only its file. `lm=` stays one model for all files; both, or `lms` next to keywords / logit_bias or any
+    grammar, is a ValueError.
+    Each job leaves `pipe.many_timing` ={"front_s": seconds its waves spent before their first decode (puts, gate, language),
     "total_s": seconds up to the end of the last wave finished, "waves": waves finished} — what scripts/many_files_time.py reports;
     the next job on the pipeline replaces it.
     wave_put=True: the files of a wave go up in ONE Slot.put_many call (one wait) instead of one put per file; a slot without put_many
@@ -444,6 +493,17 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
         if not hasattr(pipe.model, "language_model"):
             raise ValueError("lm: this transcriber takes no language model")
         lm_scope = pipe.model.language_model(lm, lm_weight)
+    lms, lm_weights = kwargs.pop("lms", None), kwargs.pop("lm_weights", None)
+    if lms is not None:
+        # a model and a weight PER FILE: the decode groups select the entry of each chunk's file
+        if lm is not None:
+            raise ValueError("lms (one per file) and lm (one for all files) in one job: give one of them")
+        if grammar is not None or grammars is not None or grammar_pattern is not None or grammar_patterns is not None:
+            raise ValueError("lms and a grammar in one job: a language model together with a grammar is out of scope")
+        if any(v is not None for v in bias_args.values()):
+            raise ValueError("lms and keywords / logit_bias in one job: a language model together with keyword boosting is out of scope")
+    elif lm_weights is not None:
+        raise ValueError("lm_weights goes with lms (one model per file); the weight of lm= is lm_weight")
     pat = None
     if grammar_patterns is not None:
         if grammar_pattern is not None:
@@ -497,7 +557,8 @@ def iter_many(pipe, audios, *, batch_size: int = 8, on_error: str = "return", **
         file_grammars = per_file_grammars(pipe.model, grammars, grammars_repeat, a, len(audios))
     # a pattern PER FILE, the same way: compiled here, before any audio work
     file_patterns = per_file_patterns(pipe.model, grammar_patterns, patterns_ignore_case, a, len(audios)) if grammar_patterns is not None else None
-    job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables, file_grammars, file_patterns)
+    file_lms = per_file_lms(pipe.model, lms, lm_weights, len(audios)) if lms is not None else None
+    job = _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put, diarizers, tables, file_grammars, file_patterns, file_lms)
     if lm_scope is not None:
         return _under_grammar(job, lm_scope.value, lambda v: _lm.scope(*v))
     if pat is not None:
@@ -525,13 +586,14 @@ def _under_grammar(job, gram, scope=_grammar.scope):
 
 
 def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: bool = False, diarizers=None, tables=None, grammars=None,
-         patterns=None):
+         patterns=None, lms=None):
     model = pipe.model
     tables = tables if tables is not None else [None] * len(audios)
     grammars = grammars if grammars is not None else [None] * len(audios)
     patterns = patterns if patterns is not None else [None] * len(audios)
+    lms = lms if lms is not None else [None] * len(audios)
     if on_error == "raise":
-        for t in list(tables) + list(grammars) + list(patterns):
+        for t in list(tables) + list(grammars) + list(patterns) + list(lms):
             if isinstance(t, Exception):
                 raise t
     timing = pipe.many_timing = {"front_s": 0.0, "total_s": 0.0, "waves": 0}
@@ -560,6 +622,7 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: b
         # (grammars= and keywords exclude each other in one job, so at most one of the two fits shortens the wave and the other's set is None)
         wave, grammar_set = fit_grammars(wave, grammars)
         wave, pattern_set = fit_patterns(wave, patterns)
+        wave, lm_set = fit_lms(wave, lms)
         at = wave[-1] + 1
         files = [_File(i, per_file[i], loaded[i], batch_size + k, *(diarizers[i] if diarizers else ())) for k, i in enumerate(wave)]
         for f in files:
@@ -578,6 +641,11 @@ def _job(pipe, audios, per_file, a, batch_size, max_batch, on_error, wave_put: b
             else:
                 f.pattern = patterns[f.index]
             f.pattern_set = pattern_set
+            if isinstance(lms[f.index], Exception):
+                f.audio = lms[f.index]                  # a refused model or weight costs only its file, the same way
+            else:
+                f.lm = lms[f.index]
+            f.lm_set = lm_set
         for i in wave:
             loaded[i] = None                # (the job does not hold a file's bytes past its wave)
         yield from _wave(pipe, slot, files, a, vad_parameters, batch_size, on_error, timing, wave_put)
@@ -835,6 +903,8 @@ def _decode_group(pipe, slot, group) -> list:
             scope = _grammar.item_scope([group[i][0].grammar for i in idx], group[idx[0]][0].grammar_set)
         if group[idx[0]][0].pattern_set is not None:    # a pattern per file, the same way
             scope = _pattern.item_scope([group[i][0].pattern for i in idx], group[idx[0]][0].pattern_set)
+        if group[idx[0]][0].lm_set is not None:         # a model and a weight per file, the same way
+            scope = _lm.item_scope([group[i][0].lm for i in idx], group[idx[0]][0].lm_set)
         with scope:
             results = model.model.generate(
                 encoder_output if len(idx) == n else encoder_output.select(idx), [prompts[i] for i in idx], beam_size=o.beam_size,

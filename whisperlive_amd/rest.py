@@ -383,8 +383,10 @@ class FileBatcher:
         self._thread.start()
 
     def submit(self, transcriber, data: bytes, per_file: dict, shared: dict):
-        # (a job decodes under keyword tables or under grammars, not both: uploads with a grammar form jobs of their own)
-        up = _Upload(transcriber, (id(transcriber), repr(sorted(shared.items())), bool(per_file.get("grammar"))), data, per_file, shared)
+        # (a job decodes under keyword tables, under grammars or under language models, one of them: uploads with a grammar form jobs of
+        # their own, and so do uploads with a model — whatever their weights: a decode group takes an entry per item)
+        mode = "grammar" if per_file.get("grammar") else "lm" if per_file.get("lm") else ""
+        up = _Upload(transcriber, (id(transcriber), repr(sorted(shared.items())), mode), data, per_file, shared)
         with self._cv:
             if self._closed:
                 raise RuntimeError("the server is shutting down")
@@ -436,6 +438,8 @@ class FileBatcher:
                        if any(u.per_file.get("keywords") for u in job) else {}),
                     **({"grammars": [u.per_file.get("grammar") for u in job], "grammars_repeat": [u.per_file.get("grammar_repeat", True) for u in job]}
                        if any(u.per_file.get("grammar") for u in job) else {}),
+                    **({"lms": [u.per_file["lm"][0] for u in job], "lm_weights": [u.per_file["lm"][1] for u in job]}
+                       if any(u.per_file.get("lm") for u in job) else {}),
                     **({"wave_put": True} if self.wave_put else {}))
                 for index, segments, info in results:
                     up = job[index]
@@ -670,7 +674,7 @@ class RestServer:
 
     def transcribe_pooled(self, transcriber, data: bytes, *, device_index: Optional[int] = None, language=None, initial_prompt=None,
                           hotwords=None, diarize=None, max_speakers: int = 0, keywords=None, keywords_boost=None, grammar=None, grammar_repeat=True,
-                          **shared):
+                          lm=None, **shared):
         """`transcribe_file` through the batcher (file_batch_window_ms > 0): the upload joins the uploads that arrive within the window
         and decode with the same `shared` options; -> (list of segments, info) of this upload, or its own error raised here, in the
         request's thread, where the single route would have raised it. Nothing is left for `resident_file_audio` after a pooled job
@@ -679,7 +683,8 @@ class RestServer:
         while the wave's files are still resident: the segments and words come back with `.speaker`, the info with `.speakers`."""
         per_file = dict(language=language, initial_prompt=initial_prompt, hotwords=hotwords, diarize=diarize or False, max_speakers=int(max_speakers),
                         keywords=keywords, keywords_boost=keywords_boost,       # (per file: each upload of a job decodes under its own table)
-                        grammar=grammar, grammar_repeat=bool(grammar_repeat))   # (... or under its own grammar: iter_many(grammars=))
+                        grammar=grammar, grammar_repeat=bool(grammar_repeat),   # (... or under its own grammar: iter_many(grammars=))
+                        lm=lm)                                                  # (... or its own (model, weight): iter_many(lms=))
         return self._batchers.get(device_index, self.batcher).submit(transcriber, data, per_file, shared)
 
     def translator_for(self, device_index: int, target_language: str):
@@ -992,20 +997,23 @@ class _Handler(BaseHTTPRequestHandler):
             gram = grammar_scope(transcriber, grammar, grammar_repeat, keywords, keywords_boost, grammar_pattern, grammar_ignore_case)
             if gram is not None and getattr(gram, "grammar", None) is None:
                 pooled, pooled_diarizer = False, None
-            # a language model (--lm): the upload is decoded in this thread under the model's scope, never pooled
+            # a language model (--lm): an upload that is not pooled is decoded in this thread under the model's scope; a
+            # pooled one carries its (model, weight) into a job whose decode groups select an entry per item (many_files.py `lms=`,
+            # DESIGN.md §34), and the scope is not entered
             fused = rest.lm_scope(transcriber, lm_weight, exclusive=bool(keywords or grammar or (grammar_pattern and grammar_pattern.strip())))
-            if fused is not None:
+            if fused is not None and getattr(fused, "value", None) is None:
                 pooled, pooled_diarizer = False, None
             bias = keyword_scope(transcriber, keywords, keywords_boost, compact=pooled)
             with (bias if bias is not None and not pooled else contextlib.nullcontext()), (gram if gram is not None and not pooled else contextlib.nullcontext()), \
-                    (fused if fused is not None else contextlib.nullcontext()):
+                    (fused if fused is not None and not pooled else contextlib.nullcontext()):
                 if pooled:
                     segments, info = rest.transcribe_pooled(transcriber, file.data, device_index=device_index, language=language, initial_prompt=prompt,
                                                             temperature=temperature, word_timestamps=want_words, hotwords=hotwords,
                                                             diarize=pooled_diarizer, max_speakers=max_speakers,
                                                             keywords=list(keywords) if bias is not None else None,
                                                             keywords_boost=float(keywords_boost) if bias is not None and keywords_boost is not None and keywords_boost.strip() else None,
-                                                            **(dict(grammar=list(grammar), grammar_repeat=gram.grammar.repeat) if gram is not None else {}))
+                                                            **(dict(grammar=list(grammar), grammar_repeat=gram.grammar.repeat) if gram is not None else {}),
+                                                            **(dict(lm=fused.value) if fused is not None else {}))
                 else:
                     segments, info = rest.transcribe_file(transcriber, file.data, language=language, initial_prompt=prompt,
                                                           temperature=temperature, word_timestamps=want_words, hotwords=hotwords, **mc)

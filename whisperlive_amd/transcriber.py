@@ -238,7 +238,24 @@ class _EngineModel:
             if lmv[0].eot != o.token_ids.eot:
                 raise ValueError(f"the language model was built for end-of-text {lmv[0].eot}, this model's is {o.token_ids.eot}")
             _lm.install(slot, lmv)
-        elif getattr(slot, "_lm", None) is not None:
+        # a model and a weight per item: inside an lm.item_scope every prompt has its own (model, weight), or none; the
+        # set goes up once per slot, the selection per decode group
+        lm_items = _lm.current_items()
+        lsel = None
+        if lm_items is not None:
+            if lmv is not None:
+                raise ValueError("a language model per item next to one for every item on one slot is not served: decode under one of them")
+            if _biasing.current() is not None or _biasing.current_items() is not None:
+                raise ValueError("a language model together with keyword boosting is out of scope: decode under one of them")
+            if any(c is not None for c in (_grammar.current(), _grammar.current_items(), _pattern.current(), _pattern.current_items())):
+                raise ValueError("a language model together with a grammar is out of scope: decode under one of them")
+            if len(lm_items.values) != len(prompts):
+                raise ValueError(f"the item_scope names {len(lm_items.values)} language models for {len(prompts)} prompts")
+            for v in lm_items.values:
+                if v is not None and v[0].eot != o.token_ids.eot:
+                    raise ValueError(f"the language model was built for end-of-text {v[0].eot}, this model's is {o.token_ids.eot}")
+            lsel = _lm.install_items(slot, lm_items.values, lm_items.lm_set)
+        elif lmv is None and getattr(slot, "_lm", None) is not None:
             _lm.install(slot, None)
         # keyword boosting: the calling thread's table (WhisperModelHIP.keyword_bias) goes onto the slot this call decodes on; a slot that
         # never saw a table is left alone
@@ -333,6 +350,8 @@ class _EngineModel:
                 slot.select_grammars(gsel[a:a + group])
             if psel is not None and getattr(slot, "_pattern", None) is pat_items.pattern_set:
                 slot.select_patterns(psel[a:a + group])
+            if lsel is not None and getattr(slot, "_lm", None) is lm_items.lm_set:
+                slot.select_lms(lsel[a:a + group])
             res.extend(slot.generate(prompts[a:a + group], o.token_ids, beam_size=beam_size, patience=patience,
                                      num_hypotheses=num_hypotheses, length_penalty=length_penalty,
                                      repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -599,7 +618,8 @@ class WhisperModelHIP:
         BatchedInferencePipeline.transcribe, transcribe_many and the temperature fallback alike. Over the text tokens and end-of-text
         l' = l + weight * s - c, normalised so that the mass of text against timestamps stays the acoustic model's; the scores /
         avg_logprob are those of the fused distribution. `weight` defaults to lm.DEFAULT_WEIGHT (0.3), which is NOT tuned: there is no
-        real checkpoint or corpus here. One model for every item; a model per file or item, a model together with keyword boosting or
+        real checkpoint or corpus here. One model for every item: a list here is a ValueError (a model and a weight per item is
+        lm.item_scope, which transcribe_many(lms=, lm_weights=) uses); a model together with keyword boosting or
         a grammar, word-level ARPA files and feeding the prompt's text to the model are out of scope (ValueError). Other threads are
         untouched; scopes nest."""
         if lm is not None:
